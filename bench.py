@@ -6,7 +6,7 @@ Workload (BASELINE.json configs[1], SURVEY.md 8d "cfg 2"): 3D P1 Poisson on the 
 (omega 0.9), V(1,1), max_coarse_size 50.  One "step" = one preconditioner application x = C b
 (amgx_apply, i.e. BaseAMGPC::Mult of the reference) with b and x resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 (one rank per GPU; started by torch.distributed.run or, without a launcher, by this script itself): STRONG scaling
 of the same problem -- BASELINE.json's metric is "3D H1 ~10M DOF at 1/2/4/8 GPU": the 215^3 grid (the very matrix of the
@@ -17,9 +17,12 @@ of the first replicated level, the coarse hierarchy replicated; torch.distribute
 128-byte RCCL id, the host-side setup messages and the barriers of the timed region.  --scaling weak: one 215^3 box per
 rank instead (value = ranks x steps / time); --config cfg4: the 342^3 = 40M-DOF grid over a box of ranks.
 
-Prints ONE JSON line on rank 0 (contract of the driver) with the extra objects "roofline" (dominant kernel: the fused
-level-0 pre-smoothing + residual + restriction pass, HIP-event timed inside the running cycle) and "cpu_baseline" (the
-CPU oracle = restatement of the reference's cycle, timed on this box's host cores on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0 (contract of the driver).  A plain run sets up, warms up, times the K steps and prints it;
+--dump-outputs DIR also writes the x of the last timed step.  --full adds what the headline figure does not need: the
+objects "roofline" (dominant kernel: the fused level-0 pre-smoothing + residual + restriction pass, HIP-event timed inside
+the running cycle) and "cpu_baseline" (the CPU oracle = restatement of the reference's cycle, timed on the host cores on a
+bounded sample of the same workload, with GPU-vs-oracle parity and PCG / GMRES solves), "continuity", the host-pointer
+rate and the Gauss-Seidel iteration counts.
 """
 from __future__ import annotations
 
@@ -52,6 +55,28 @@ def emit(line):
         sys.stdout.flush()
     else:
         os.write(_RESULT_FD, data)
+
+
+DUMP_BYTES = 60_000_000     # --dump-outputs: all files of one run together (64 MB cap, room for the .npy headers)
+DUMP_SEED = 20261016        # positions of the sample of an output vector larger than its share of DUMP_BYTES
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: each array as <out_dir>/<name>.npy in float64.  An array larger than its share of `budget` is written as a
+    fixed, seeded sample of its entries (sorted positions), the positions beside it as <name>_index.npy (float64, exact):
+    the same arguments give the same inputs and the same positions, so two builds can be compared entry for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.nbytes <= share:
+            np.save(os.path.join(out_dir, f"{name}.npy"), a)
+            continue
+        k = share // 16                      # sample + positions, 8 bytes each
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, k, replace=False))
+        np.save(os.path.join(out_dir, f"{name}.npy"), a[idx])
+        np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+    log(f"outputs written to {out_dir}: {sorted(arrays)}")
 
 
 def sp_nnz(A):
@@ -149,10 +174,12 @@ def run_distributed(args, torch, dist, world, rank, device, nv):
     xn = torch.tensor([xn_loc], dtype=torch.float64)
     dist.all_reduce(xn)
     ms_per_step = 1e3 * elapsed / args.steps
-    # the dominant kernel timed INSIDE the collective cycle (amgx_dist_time_kernel: every rank runs whole cycles with direct
+    if args.dump_outputs:             # each rank its owned rows (the kernel probe below overwrites b, not x)
+        dump_outputs(args.dump_outputs, {f"x_rank{rank}": x.cpu().numpy()}, DUMP_BYTES // world)
+    # --full: the dominant kernel timed INSIDE the collective cycle (amgx_dist_time_kernel: every rank runs whole cycles with direct
     # launches, HIP events around the level-0 launch over the interior rows, the halo exchange in flight beside it)
     k_probe, k_in_cycle, k_op = None, False, (8 if args.smoother == "jacobi" and not elast else 9 if args.smoother == "gs" else 0)
-    if k_op:
+    if args.full and k_op:
         ok = 1
         try:
             with torch.cuda.stream(stream):
@@ -168,21 +195,22 @@ def run_distributed(args, torch, dist, world, rank, device, nv):
             k_probe, k_in_cycle = None, False
     # PCG to 1e-8 through the rank-partitioned preconditioner (amgx_dist_pcg): iteration count of THIS hierarchy
     dpcg = None
-    try:
-        with torch.cuda.stream(stream):
-            bb = b[:st.n * bs0].clone()
-            xx = torch.zeros_like(bb)
-            its, errs = amg.pcg([bb], [xx], tol=1e-8, maxsteps=200)
-            torch.cuda.synchronize()
-            t_s = time.perf_counter()
-            xx.zero_()
-            its, errs = amg.pcg([bb], [xx], tol=1e-8, maxsteps=200)
-            torch.cuda.synchronize()
-            dpcg = {"tol": 1e-8, "iterations": int(its), "solve_ms": round(1e3 * (time.perf_counter() - t_s), 3),
-                    "rel_err_estimate": float(errs[-1] / errs[0]) if len(errs) and errs[0] else None}
-    except Exception as e:
-        if rank == 0:
-            log(f"distributed PCG failed: {e!r}")
+    if args.full:
+        try:
+            with torch.cuda.stream(stream):
+                bb = b[:st.n * bs0].clone()
+                xx = torch.zeros_like(bb)
+                its, errs = amg.pcg([bb], [xx], tol=1e-8, maxsteps=200)
+                torch.cuda.synchronize()
+                t_s = time.perf_counter()
+                xx.zero_()
+                its, errs = amg.pcg([bb], [xx], tol=1e-8, maxsteps=200)
+                torch.cuda.synchronize()
+                dpcg = {"tol": 1e-8, "iterations": int(its), "solve_ms": round(1e3 * (time.perf_counter() - t_s), 3),
+                        "rel_err_estimate": float(errs[-1] / errs[0]) if len(errs) and errs[0] else None}
+        except Exception as e:
+            if rank == 0:
+                log(f"distributed PCG failed: {e!r}")
     dist.barrier()
     # the hierarchy the ranks built together: global level sizes / entries, operator complexity
     lvl_n = torch.tensor([lv[0].n for lv in amg.dist_levels], dtype=torch.int64)
@@ -194,7 +222,9 @@ def run_distributed(args, torch, dist, world, rank, device, nv):
     sizes = [int(v) for v in lvl_n.tolist()[:amg.k]] + tail_n
     nnzs = [int(v) for v in lvl_nnz.tolist()[:amg.k]] + tail_nnz
     hier_info = {"level_sizes": sizes, "operator_complexity": round(sum(nnzs) / max(1, nnzs[0]), 3),
-                 "rank_partitioned_levels": int(amg.k), "pcg": dpcg}
+                 "rank_partitioned_levels": int(amg.k)}
+    if args.full:
+        hier_info["pcg"] = dpcg
     # strong scaling (default): a step applies the GLOBAL preconditioner of the fixed problem once: value = steps / time.
     # weak scaling: the unit is one V-cycle over one rank's nv^3 share, a step is `world` such units
     applies_per_s = (1 if strong else world) * args.steps / elapsed
@@ -202,22 +232,23 @@ def run_distributed(args, torch, dist, world, rank, device, nv):
     dist.all_reduce(ndof_glob)
     rows_all = [None] * world
     dist.all_gather_object(rows_all, int(st.n))
-    lv0 = amg.tops[0].levels[0]
-    spmv_bytes = matrix_bytes(lv0.A) + 3 * 8 * lv0.A.n_rows * lv0.A.br
-    k_name = "sell_spmv_kernel<EP_RES> (level 0 owned rows, rank 0)" if not elast else f"block residual kernel {lv0.A.br}x{lv0.A.br} (level 0 owned rows x [owned | ghost], rank 0)"
-    k_ms = k_probe
-    n_int0 = int(getattr(amg.dist_levels[0][0], "n_interior", lv0.A.n_rows))
-    frac_int = n_int0 / max(1, lv0.A.n_rows)
-    if k_ms is not None and k_op == 8:   # the dominant kernel of the folded cycle (same accounting as the single-GPU line), interior rows
-        spmv_bytes = int(frac_int * (matrix_bytes(lv0.A) + matrix_bytes(lv0.PT) + 7 * 8 * lv0.A.n_rows + 8 * amg.tops[0].levels[1].A.n_rows))
-        k_name = (f"sell_pre_restrict_kernel<512> (level 0, the {n_int0} interior rows of rank 0's {lv0.A.n_rows}: x = w Dinv b, r = b - A x, "
-                  "b_c = P^T r in one pass, beside the halo exchange)")
-    elif k_ms is not None and k_op == 9:
-        spmv_bytes = int(frac_int * (matrix_bytes(lv0.A) + 4 * 8 * lv0.A.n_rows * lv0.A.br + (8 * lv0.A.br * lv0.A.br * lv0.A.n_rows if lv0.A.br > 1 else 0)))
-        k_name = f"backward block-hybrid Gauss-Seidel sweep (level 0, interior blocks of rank 0: {n_int0} of {lv0.A.n_rows} rows, beside the halo exchange)"
-    else:
-        k_ms = amg.ops[0].top.time_op(0, 0, reps=50)
-    achieved = spmv_bytes / (k_ms * 1e-3) / 1e9
+    if args.full:
+        lv0 = amg.tops[0].levels[0]
+        spmv_bytes = matrix_bytes(lv0.A) + 3 * 8 * lv0.A.n_rows * lv0.A.br
+        k_name = "sell_spmv_kernel<EP_RES> (level 0 owned rows, rank 0)" if not elast else f"block residual kernel {lv0.A.br}x{lv0.A.br} (level 0 owned rows x [owned | ghost], rank 0)"
+        k_ms = k_probe
+        n_int0 = int(getattr(amg.dist_levels[0][0], "n_interior", lv0.A.n_rows))
+        frac_int = n_int0 / max(1, lv0.A.n_rows)
+        if k_ms is not None and k_op == 8:   # the dominant kernel of the folded cycle (same accounting as the single-GPU line), interior rows
+            spmv_bytes = int(frac_int * (matrix_bytes(lv0.A) + matrix_bytes(lv0.PT) + 7 * 8 * lv0.A.n_rows + 8 * amg.tops[0].levels[1].A.n_rows))
+            k_name = (f"sell_pre_restrict_kernel<512> (level 0, the {n_int0} interior rows of rank 0's {lv0.A.n_rows}: x = w Dinv b, r = b - A x, "
+                      "b_c = P^T r in one pass, beside the halo exchange)")
+        elif k_ms is not None and k_op == 9:
+            spmv_bytes = int(frac_int * (matrix_bytes(lv0.A) + 4 * 8 * lv0.A.n_rows * lv0.A.br + (8 * lv0.A.br * lv0.A.br * lv0.A.n_rows if lv0.A.br > 1 else 0)))
+            k_name = f"backward block-hybrid Gauss-Seidel sweep (level 0, interior blocks of rank 0: {n_int0} of {lv0.A.n_rows} rows, beside the halo exchange)"
+        else:
+            k_ms = amg.ops[0].top.time_op(0, 0, reps=50)
+        achieved = spmv_bytes / (k_ms * 1e-3) / 1e9
     if rank == 0:
         out = {
             "metric": ("V-cycle applies/sec (3D H1 Poisson %s, %s V(1,1))" % ("~10M DOF" if strong and nv == 215 else f"{int(ndof_glob.item())} DOF" if strong else "~10M DOF per GPU",
@@ -244,18 +275,19 @@ def run_distributed(args, torch, dist, world, rank, device, nv):
             "x_norm": float(xn.item()) ** 0.5,
             "hierarchy": hier_info,
             "device_memory": {"per_rank_bytes": hier_bytes},
-            "roofline": {"bound": "hbm", "kernel": k_name,
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                         "traffic_note": "PMC counters need a profiler pass per rank; the single-GPU line carries the counter traffic of the same kernel",
-                         "kernel_ms": round(k_ms, 4),
-                         "kernel_ms_timing": ("HIP events around the kernel inside the running collective cycle (amgx_dist_time_kernel)" if k_in_cycle
-                                              else "HIP events, back-to-back repetitions"),
-                         "algorithmic_bytes": int(spmv_bytes), "cycle_algorithmic_bytes_per_rank": int(per_rank),
-                         "algorithmic_model_GBs_per_gpu": round(per_rank / (ms_per_step * 1e-3) / 1e9, 1)},
         }
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "kernel": k_name,
+                               "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                               "traffic_note": "PMC counters need a profiler pass per rank; the single-GPU line carries the counter traffic of the same kernel",
+                               "kernel_ms": round(k_ms, 4),
+                               "kernel_ms_timing": ("HIP events around the kernel inside the running collective cycle (amgx_dist_time_kernel)" if k_in_cycle
+                                                    else "HIP events, back-to-back repetitions"),
+                               "algorithmic_bytes": int(spmv_bytes), "cycle_algorithmic_bytes_per_rank": int(per_rank),
+                               "algorithmic_model_GBs_per_gpu": round(per_rank / (ms_per_step * 1e-3) / 1e9, 1)}
         cpu = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 cpu = _dist_cpu_baseline(args, nv, world, strong, elast, hier_kw)
             except Exception as e:        # the baseline never takes the measured line down with it
@@ -335,6 +367,118 @@ def _dist_cpu_baseline(args, nv, world, strong, elast, hier_kw):
                        + f" ({prob.n * prob.bs} DOF, {H.n_levels} levels, OC {sum(nnz) / max(1, nnz[0]):.3f}; oracle/oracle.c, OpenMP over rows, "
                          f"{cores} threads on rank 0 while the other ranks wait in the final barrier; setup {t1 - t0:.1f} s, not timed)"),
             "hierarchy_note": "the rank-partitioned hierarchy (`hierarchy` above) is built by the distributed setup: same rules, rank-local aggregates"}
+
+
+def _roofline(args, amg, H, stream, b, x, nv, bs0, cycle_bytes, folded, ms_per_step):
+    """--full, one GPU: the dominant kernel timed inside the running cycle against its algorithmic bytes, and the whole cycle's
+    streamed bytes over the measured step time"""
+    import torch
+    from ngsamg_amd.device import matrix_bytes
+    # Jacobi cycle: sell_pre_restrict_kernel on level 0 = Jacobi pre-smoothing from zero, residual and restriction in one
+    # pass.  Algorithmic bytes per launch (SURVEY.md 8d, the un-fused op sequence it replaces):
+    #   x = w Dinv b: 3 V_0;  r = b - A x: B(A_0) + 3 V_0;  b_c = P^T r: B(PT_0) + V_0 + V_1
+    # Gauss-Seidel cycle (or no fused kernel): level-0 residual SpMV r = b - A x: B(A_0) + 3 V_0
+    lv0 = H.levels[0]
+    V0 = 8 * lv0.n * lv0.bs
+    with torch.cuda.stream(stream):
+        amg.Mult(b, x)
+        stream.synchronize()
+    k_name, tname = "sell_spmv_kernel<EP_RES> (level 0: r = b - A x)", "traffic_spmv_l0.json"
+    spmv_bytes = matrix_bytes(lv0.A) + 3 * V0
+    k_ms = k_ms_b2b = None
+    if args.smoother == "jacobi" and args.config == "cfg2":
+        try:
+            # timed INSIDE the cycle (HIP events around the one kernel while whole cycles run): the figure rocprofv3's
+            # kernel trace reports for it; the back-to-back repetition time is kept beside it
+            k_ms = amg.time_op(0, 8, reps=50)
+            if args.ops:          # back-to-back repetitions only on request: they would mix into the rocprofv3 --stats average
+                k_ms_b2b = amg.time_op(0, 7, reps=50)
+            spmv_bytes = matrix_bytes(lv0.A) + matrix_bytes(lv0.PT) + 7 * V0 + 8 * H.levels[1].n * H.levels[1].bs
+            k_name = "sell_pre_restrict_kernel<512> (level 0: x = w Dinv b, r = b - A x, b_c = P^T r in one pass)"
+            tname = "traffic_pre_restrict_l0.json"
+        except Exception as e:
+            log(f"in-cycle timing of the fused kernel unavailable: {e!r}")
+            k_ms = None
+    in_cycle = k_ms is not None
+    if args.smoother == "gs" and args.config == "cfg2" and lv0.bs == 1:
+        # Gauss-Seidel cycle: the backward block-hybrid sweep of level 0 (x' = GS_back(x + P x_c)) is the largest kernel.
+        # Algorithmic bytes of one sweep in the RHS form (SURVEY.md 8d: "each read A once"): B(A_0) + dinv + x in, b, x out
+        try:
+            k_ms = amg.time_op(0, 9, reps=50)
+            spmv_bytes = matrix_bytes(lv0.A) + 4 * V0
+            k_name = "gsb_sweep_kernel<256, 1, false> (level 0: backward block-hybrid Gauss-Seidel sweep, x' = GS(x + P x_c))"
+            tname = "traffic_gsb_sweep_l0.json"
+            in_cycle = True
+        except Exception as e:
+            log(f"in-cycle timing of the Gauss-Seidel sweep unavailable: {e!r}")
+            k_ms = None
+    if args.smoother == "gs" and args.config != "cfg2" and lv0.bs > 1:
+        # block levels: the backward block-hybrid sweep (bgsb_sweep_kernel) timed inside the cycle, same byte model
+        try:
+            k_ms = amg.time_op(0, 9, reps=30)
+            spmv_bytes = matrix_bytes(lv0.A) + 4 * V0 + 8 * lv0.bs * lv0.bs * lv0.n        # + the inverted block diagonals
+            k_name = f"bgsb_sweep_kernel<{bs0}, false> (level 0: backward block-hybrid Gauss-Seidel sweep, {bs0}x{bs0} blocks)"
+            tname = f"traffic_bgsb_sweep_{args.config}.json"
+            in_cycle = True
+        except Exception as e:
+            log(f"in-cycle timing of the block Gauss-Seidel sweep unavailable: {e!r}")
+            k_ms = None
+    if k_ms is None:
+        k_ms = amg.time_op(0, 0, reps=50)
+        if args.config != "cfg2":
+            k_name = f"bsell_spmv_kernel<{bs0}, EP_RES> (level 0: r = b - A x, {bs0}x{bs0} blocks)"
+            tname = f"traffic_bsell_res_{args.config}.json"
+    achieved = spmv_bytes / (k_ms * 1e-3) / 1e9
+    traffic = traffic_src = None
+    if args.hierarchy == "spw":          # (the counters were collected per hierarchy: the level-0 kernels stream different P^T / Q)
+        tname = tname.replace(".json", "_spw.json")
+    tpath = os.path.join(ROOT, "profiles", tname)
+    if os.path.exists(tpath) and nv == (215 if args.config == "cfg2" else 126):
+        try:
+            tj = json.load(open(tpath))
+            traffic = tj.get("hbm_bytes_per_launch")
+            # PMC counters cannot be collected from inside this process: the figure comes from a separate rocprofv3 --pmc
+            # pass (profiles/), valid for the kernel build named here
+            traffic_src = {"file": "profiles/" + tname, "commit": tj.get("commit"), "collected": tj.get("collected")}
+        except Exception:
+            traffic = None
+    roofline = {"bound": "hbm", "kernel": k_name,
+                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                "kernel_ms": round(k_ms, 4), "kernel_ms_timing": "HIP events around the kernel inside the running cycle (amgx_time_op op 8 / 9)" if in_cycle else "HIP events, back-to-back repetitions",
+                "kernel_ms_back_to_back": round(k_ms_b2b, 4) if k_ms_b2b else None,
+                "algorithmic_bytes": int(spmv_bytes)}
+    # whole cycle: bytes the cycle actually streams (device encodings) / time.  The algorithmic byte count of the reference's
+    # op sequence (SURVEY 8d) divided by the same time is NOT a bandwidth for the folded cycle (it skips a pass over A and the
+    # pass over P): it is reported as the speed-up measure it is.
+    if folded and args.config == "cfg2":
+        sb = 0
+        for l in range(H.n_levels - 1):
+            Vl, Vc = 8 * H.levels[l].n * H.levels[l].bs, 8 * H.levels[l + 1].n * H.levels[l + 1].bs
+            # (the images the cycle actually reads: the local-window forms of A' and Q where a level has them)
+            def _sb(plain, lw):
+                i = amg.matrix_info(l, lw)
+                return i["stream_bytes"] if i["fmt"] is not None else amg.matrix_info(l, plain)["stream_bytes"]
+            sb += _sb("Apre", "ApreLW") + amg.matrix_info(l, "PT")["stream_bytes"] + _sb("Q", "QLW") + 5 * Vl + 2 * Vc
+    elif args.config != "cfg2":
+        # block levels: folded where Q exists (A once + PT + Q), literal otherwise (A twice + P + PT), device encodings
+        sb = 0
+        for l in range(H.n_levels - 1):
+            Vl, Vc = 8 * H.levels[l].n * H.levels[l].bs, 8 * H.levels[l + 1].n * H.levels[l + 1].bs
+            mi = {w: amg.matrix_info(l, w) for w in ("A", "P", "PT", "Q")}
+            if mi["Q"]["fmt"] is not None:
+                sb += mi["A"]["stream_bytes"] + mi["PT"]["stream_bytes"] + mi["Q"]["stream_bytes"] + 8 * Vl + 2 * Vc
+            else:
+                sb += 2 * mi["A"]["stream_bytes"] + mi["P"]["stream_bytes"] + mi["PT"]["stream_bytes"] + 15 * Vl + 2 * Vc
+    else:
+        sb = cycle_bytes
+    roofline["cycle_streamed_bytes"] = int(sb)
+    roofline["cycle_GBs"] = round(sb / (ms_per_step * 1e-3) / 1e9, 1)
+    roofline["cycle_frac"] = round(sb / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+    roofline["algorithmic_model"] = {"cycle_bytes": int(cycle_bytes), "bytes_over_time_GBs": round(cycle_bytes / (ms_per_step * 1e-3) / 1e9, 1),
+                                     "speedup_vs_literal_bytes": round(cycle_bytes / sb, 3),
+                                     "note": "bytes of the reference's un-fused op sequence over the measured time: a speed-up measure, not a bandwidth"}
+    return roofline
 
 
 def _wait_ranks(procs, limit):
@@ -437,6 +581,13 @@ def main():
                     help="skip the second hierarchy (the round-1..3 continuity line)")
     ap.add_argument("--multistep", action="store_true", help="cfg2, one GPU: hierarchy with ngs_amg_enable_multistep (the reference's H1 default; "
                     "not the measured configuration: denser P, fewer iterations)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: roofline of the dominant kernel, CPU baseline with "
+                         "GPU-vs-oracle parity and PCG / GMRES solves, the continuity hierarchy, the host-pointer rate, Gauss-Seidel iteration "
+                         "counts; N > 1: in-cycle kernel timing, rank-partitioned PCG, roofline, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result x of the last timed application as DIR/<name>.npy (float64; a fixed, "
+                         "seeded sample of it with the sampled positions beside it when the whole vector exceeds the size budget)")
     args = ap.parse_args()
 
     # stdout carries exactly ONE line (the result): everything libraries print (RCCL / gloo banners) goes to stderr
@@ -582,113 +733,15 @@ def main():
     x_norm = float(torch.linalg.norm(x).item())
     applies_per_s = world * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": x.cpu().numpy()})
 
-    # ---- roofline of the dominant kernel ---------------------------------------------------------------
-    # Jacobi cycle: sell_pre_restrict_kernel on level 0 = Jacobi pre-smoothing from zero, residual and restriction in one
-    # pass.  Algorithmic bytes per launch (the un-fused op sequence it replaces):
-    #   x = w Dinv b: 3 V_0;  r = b - A x: B(A_0) + 3 V_0;  b_c = P^T r: B(PT_0) + V_0 + V_1
-    # Gauss-Seidel cycle (or no fused kernel): level-0 residual SpMV r = b - A x: B(A_0) + 3 V_0
     lv0 = H.levels[0]
-    V0 = 8 * lv0.n * lv0.bs
-    with torch.cuda.stream(stream):
-        amg.Mult(b, x)
-        stream.synchronize()
     folded = amg.matrix_info(0, "Q")["fmt"] is not None
-    k_name, tname = "sell_spmv_kernel<EP_RES> (level 0: r = b - A x)", "traffic_spmv_l0.json"
-    spmv_bytes = matrix_bytes(lv0.A) + 3 * V0
-    k_ms = k_ms_b2b = None
-    if args.smoother == "jacobi" and args.config == "cfg2":
-        try:
-            # timed INSIDE the cycle (HIP events around the one kernel while whole cycles run): the figure rocprofv3's
-            # kernel trace reports for it; the back-to-back repetition time is kept beside it
-            k_ms = amg.time_op(0, 8, reps=50)
-            if args.ops:          # back-to-back repetitions only on request: they would mix into the rocprofv3 --stats average
-                k_ms_b2b = amg.time_op(0, 7, reps=50)
-            spmv_bytes = matrix_bytes(lv0.A) + matrix_bytes(lv0.PT) + 7 * V0 + 8 * H.levels[1].n * H.levels[1].bs
-            k_name = "sell_pre_restrict_kernel<512> (level 0: x = w Dinv b, r = b - A x, b_c = P^T r in one pass)"
-            tname = "traffic_pre_restrict_l0.json"
-        except Exception as e:
-            log(f"in-cycle timing of the fused kernel unavailable: {e!r}")
-            k_ms = None
-    in_cycle = k_ms is not None
-    if args.smoother == "gs" and args.config == "cfg2" and lv0.bs == 1:
-        # Gauss-Seidel cycle: the backward block-hybrid sweep of level 0 (x' = GS_back(x + P x_c)) is the largest kernel.
-        # Algorithmic bytes of one sweep in the RHS form ("each read A once"): B(A_0) + dinv + x in, b, x out
-        try:
-            k_ms = amg.time_op(0, 9, reps=50)
-            spmv_bytes = matrix_bytes(lv0.A) + 4 * V0
-            k_name = "gsb_sweep_kernel<256, 1, false> (level 0: backward block-hybrid Gauss-Seidel sweep, x' = GS(x + P x_c))"
-            tname = "traffic_gsb_sweep_l0.json"
-            in_cycle = True
-        except Exception as e:
-            log(f"in-cycle timing of the Gauss-Seidel sweep unavailable: {e!r}")
-            k_ms = None
-    if args.smoother == "gs" and args.config != "cfg2" and lv0.bs > 1:
-        # block levels: the backward block-hybrid sweep (bgsb_sweep_kernel) timed inside the cycle, same byte model
-        try:
-            k_ms = amg.time_op(0, 9, reps=30)
-            spmv_bytes = matrix_bytes(lv0.A) + 4 * V0 + 8 * lv0.bs * lv0.bs * lv0.n        # + the inverted block diagonals
-            k_name = f"bgsb_sweep_kernel<{bs0}, false> (level 0: backward block-hybrid Gauss-Seidel sweep, {bs0}x{bs0} blocks)"
-            tname = f"traffic_bgsb_sweep_{args.config}.json"
-            in_cycle = True
-        except Exception as e:
-            log(f"in-cycle timing of the block Gauss-Seidel sweep unavailable: {e!r}")
-            k_ms = None
-    if k_ms is None:
-        k_ms = amg.time_op(0, 0, reps=50)
-        if args.config != "cfg2":
-            k_name = f"bsell_spmv_kernel<{bs0}, EP_RES> (level 0: r = b - A x, {bs0}x{bs0} blocks)"
-            tname = f"traffic_bsell_res_{args.config}.json"
-    achieved = spmv_bytes / (k_ms * 1e-3) / 1e9
-    traffic = traffic_src = None
-    if args.hierarchy == "spw":          # (the counters were collected per hierarchy: the level-0 kernels stream different P^T / Q)
-        tname = tname.replace(".json", "_spw.json")
-    tpath = os.path.join(ROOT, "profiles", tname)
-    if os.path.exists(tpath) and nv == (215 if args.config == "cfg2" else 126):
-        try:
-            tj = json.load(open(tpath))
-            traffic = tj.get("hbm_bytes_per_launch")
-            # PMC counters cannot be collected from inside this process: the figure comes from a separate rocprofv3 --pmc
-            # pass (profiles/), valid for the kernel build named here
-            traffic_src = {"file": "profiles/" + tname, "commit": tj.get("commit"), "collected": tj.get("collected")}
-        except Exception:
-            traffic = None
-    roofline = {"bound": "hbm", "kernel": k_name,
-                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "kernel_ms": round(k_ms, 4), "kernel_ms_timing": "HIP events around the kernel inside the running cycle (amgx_time_op op 8 / 9)" if in_cycle else "HIP events, back-to-back repetitions",
-                "kernel_ms_back_to_back": round(k_ms_b2b, 4) if k_ms_b2b else None,
-                "algorithmic_bytes": int(spmv_bytes)}
-    # whole cycle: bytes the cycle actually streams (device encodings) / time.  The algorithmic byte count of the reference's
-    # op sequence divided by the same time is NOT a bandwidth for the folded cycle (it skips a pass over A and the
-    # pass over P): it is reported as the speed-up measure it is.
-    if folded and args.config == "cfg2":
-        sb = 0
-        for l in range(H.n_levels - 1):
-            Vl, Vc = 8 * H.levels[l].n * H.levels[l].bs, 8 * H.levels[l + 1].n * H.levels[l + 1].bs
-            # (the images the cycle actually reads: the local-window forms of A' and Q where a level has them)
-            def _sb(plain, lw):
-                i = amg.matrix_info(l, lw)
-                return i["stream_bytes"] if i["fmt"] is not None else amg.matrix_info(l, plain)["stream_bytes"]
-            sb += _sb("Apre", "ApreLW") + amg.matrix_info(l, "PT")["stream_bytes"] + _sb("Q", "QLW") + 5 * Vl + 2 * Vc
-    elif args.config != "cfg2":
-        # block levels: folded where Q exists (A once + PT + Q), literal otherwise (A twice + P + PT), device encodings
-        sb = 0
-        for l in range(H.n_levels - 1):
-            Vl, Vc = 8 * H.levels[l].n * H.levels[l].bs, 8 * H.levels[l + 1].n * H.levels[l + 1].bs
-            mi = {w: amg.matrix_info(l, w) for w in ("A", "P", "PT", "Q")}
-            if mi["Q"]["fmt"] is not None:
-                sb += mi["A"]["stream_bytes"] + mi["PT"]["stream_bytes"] + mi["Q"]["stream_bytes"] + 8 * Vl + 2 * Vc
-            else:
-                sb += 2 * mi["A"]["stream_bytes"] + mi["P"]["stream_bytes"] + mi["PT"]["stream_bytes"] + 15 * Vl + 2 * Vc
-    else:
-        sb = cycle_bytes
-    roofline["cycle_streamed_bytes"] = int(sb)
-    roofline["cycle_GBs"] = round(sb / (ms_per_step * 1e-3) / 1e9, 1)
-    roofline["cycle_frac"] = round(sb / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-    roofline["algorithmic_model"] = {"cycle_bytes": int(cycle_bytes), "bytes_over_time_GBs": round(cycle_bytes / (ms_per_step * 1e-3) / 1e9, 1),
-                                     "speedup_vs_literal_bytes": round(cycle_bytes / sb, 3),
-                                     "note": "bytes of the reference's un-fused op sequence over the measured time: a speed-up measure, not a bandwidth"}
+    # ---- --full: roofline of the dominant kernel, whole-cycle bytes -------------------------------------
+    roofline = None
+    if args.full:
+        roofline = _roofline(args, amg, H, stream, b, x, nv, bs0, cycle_bytes, folded, ms_per_step)
 
     if args.ops and rank == 0:
         names = {0: "residual r=b-Ax", 1: "jacobi fused", 2: "restrict PT r", 3: "prolong x+P xc"}
@@ -715,7 +768,7 @@ def main():
 
     # ---- CPU baseline: the oracle (restatement of the reference's cycle) on this box's cores ----------
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         if not os.environ.get("NGSAMG_NO_BUILD"):
             ge.build_oracle()
         from oracle.pyoracle import Oracle      # measured as the CPU baseline, never part of the product path
@@ -833,7 +886,7 @@ def main():
 
     # ---- continuity: the hierarchy of rounds 1-3 beside the measured (default = reference) one ---------------------------
     cont = None
-    if rank == 0 and args.hierarchy == "spw" and not args.no_continuity and not args.multistep:
+    if args.full and rank == 0 and args.hierarchy == "spw" and not args.no_continuity and not args.multistep:
         try:
             tr0 = time.time()
             if args.config == "cfg2":
@@ -874,19 +927,20 @@ def main():
 
     # what an unmodified host-pointer caller gets (vectors cross PCIe in both directions inside the call): never `value`
     host_rate = None
-    try:
-        xh = np.empty(n_s)
-        amg.Mult(b_host, xh)
-        th = time.perf_counter()
-        for _ in range(5):
+    if args.full:
+        try:
+            xh = np.empty(n_s)
             amg.Mult(b_host, xh)
-        host_rate = round(5.0 / (time.perf_counter() - th), 1)
-    except Exception as e:
-        log(f"host-pointer probe failed: {e!r}")
+            th = time.perf_counter()
+            for _ in range(5):
+                amg.Mult(b_host, xh)
+            host_rate = round(5.0 / (time.perf_counter() - th), 1)
+        except Exception as e:
+            log(f"host-pointer probe failed: {e!r}")
 
     # Gauss-Seidel: iteration counts of PCG (1e-8) with the GPU's sweep order and with the reference's sequential order
     gs_its = None
-    if args.smoother in ("gs", "gs_mc") and rank == 0 and not args.no_cpu_baseline:
+    if args.full and args.smoother in ("gs", "gs_mc") and rank == 0 and not args.no_cpu_baseline:
         try:
             from oracle.pyoracle import Oracle as _O
             if args.smoother == "gs":
@@ -920,9 +974,10 @@ def main():
             "x_norm": x_norm,
             "device_memory": {"hierarchy_bytes": hier_bytes, "level0_csr_bytes": int(matrix_bytes(lv0.A)),
                               "ratio_to_level0_csr": round(hier_bytes / max(1, matrix_bytes(lv0.A)), 2)},
-            "host_ptr_applies_per_s": host_rate,
-            "roofline": roofline,
         }
+        if args.full:
+            out["host_ptr_applies_per_s"] = host_rate
+            out["roofline"] = roofline
         if gs_its is not None:
             out["gs_iterations"] = gs_its
         if cont is not None:

@@ -1,9 +1,12 @@
-"""bench.py's multi-rank launcher logic without GPUs: the watchdog that ends a run when a rank dies or nothing comes back."""
+"""bench.py's host-side logic without GPUs: the watchdog of the multi-rank launcher that ends a run when a rank dies or nothing
+comes back, the cpu_baseline object of the multi-rank line, the files --dump-outputs writes."""
 import importlib.util
 import os
 import subprocess
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -60,3 +63,25 @@ def test_cpu_baseline_of_the_multi_rank_line():
     e = b._dist_cpu_baseline(args, 6, 2, True, True, {"spw": 1})
     assert e["value"] > 0 and "648 DOF" in e["sample"]
     assert b._dist_cpu_baseline(args, 400, 8, True, True, {"spw": 1}) is None
+
+
+def test_dump_outputs_whole_or_seeded_sample(tmp_path):
+    """--dump-outputs: float64 .npy files within the byte budget; a vector larger than its share is written as the same seeded
+    sample on every run, its sorted positions beside it"""
+    b = _bench()
+    small = np.arange(10, dtype=np.float32)
+    big = np.random.default_rng(1).standard_normal(5000)
+    budget = 40000
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"s": small, "x": big}, budget=budget)
+    s = np.load(tmp_path / "a" / "s.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small)
+    assert not (tmp_path / "a" / "s_index.npy").exists()
+    x, idx = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "x_index.npy")
+    assert x.dtype == np.float64 and idx.dtype == np.float64 and 0 < x.size == idx.size < big.size
+    pos = idx.astype(np.int64)
+    assert np.array_equal(pos, idx) and np.all(np.diff(pos) > 0) and pos[-1] < big.size
+    assert np.array_equal(x, big[pos])
+    assert x.nbytes + idx.nbytes + s.nbytes <= budget
+    for name in ("s.npy", "x.npy", "x_index.npy"):
+        assert (tmp_path / "a" / name).read_bytes() == (tmp_path / "b" / name).read_bytes()

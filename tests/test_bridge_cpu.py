@@ -11,6 +11,13 @@ from oracle.pyoracle import Oracle
 from tests.dist_cpu_backend import cpu_backend
 
 
+@pytest.fixture(autouse=True)
+def _stage_backend_allowed(monkeypatch):
+    """these tests check the stage-by-stage CPU backend itself, which DistributedAMG refuses where a GPU is visible unless
+    NGSAMG_STAGE_BACKEND_OK is set: set here (and inherited by spawned ranks), so that the verdict does not depend on the machine"""
+    monkeypatch.setenv("NGSAMG_STAGE_BACKEND_OK", "1")
+
+
 def _setup(pgrid, gshape):
     R = int(np.prod(pgrid))
     comm = D.LoopbackComm(R)

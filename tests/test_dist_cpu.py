@@ -12,6 +12,13 @@ from tests.dist_cpu_backend import cpu_backend
 from tests.dist_oracle import oracle_bgs, oracle_sm_types
 
 
+@pytest.fixture(autouse=True)
+def _stage_backend_allowed(monkeypatch):
+    """these tests check the stage-by-stage CPU backend itself, which DistributedAMG refuses where a GPU is visible unless
+    NGSAMG_STAGE_BACKEND_OK is set: set here (and inherited by spawned ranks), so that the verdict does not depend on the machine"""
+    monkeypatch.setenv("NGSAMG_STAGE_BACKEND_OK", "1")
+
+
 def _run_loopback(R, box, dim, dist_min_rows, sm="jacobi", fold=True, **extra):
     comm = D.LoopbackComm(R)
     pg = D.proc_grid(R, dim)

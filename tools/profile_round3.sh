@@ -17,7 +17,7 @@ HB=$!
 trap "kill $HB 2>/dev/null" EXIT
 kt() {   # kt <tag> <bench args...>: kernel trace + stats of one bench command; stats of the launches after amgx_create beside rocprof's own
   tag=$1; shift
-  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$tag -- python bench.py "$@" > $OUT/bench_under_rocprof_$tag.json 2> $OUT/kt_$tag.log
+  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$tag -- python bench.py --full "$@" > $OUT/bench_under_rocprof_$tag.json 2> $OUT/kt_$tag.log
   f=$(find $OUT/kt_$tag -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/kernel_stats_$tag.csv
   f=$(find $OUT/kt_$tag -name "*kernel_trace.csv" | head -1); [ -n "$f" ] && python tools/stats_after_setup.py $f $OUT/kernel_stats_${tag}_after_setup.csv
   rm -rf $OUT/kt_$tag; echo "kt $tag done" >> $OUT/progress.txt
@@ -39,10 +39,10 @@ if [[ $PART == *a* ]]; then
   kt gs --smoother gs --steps 50 --warmup 10 --no-cpu-baseline --no-reference-defaults
   pmc jacobi
   pmc gs --smoother gs
-  python bench.py > $OUT/bench_jacobi.json 2> $OUT/bench_jacobi.err; echo "bench jacobi" >> $OUT/progress.txt
-  python bench.py --smoother gs --steps 100 --no-reference-defaults > $OUT/bench_gs.json 2> $OUT/bench_gs.err; echo "bench gs" >> $OUT/progress.txt
-  python bench.py --hierarchy spw --steps 100 --no-cpu-baseline > $OUT/bench_jacobi_spw_hierarchy.json 2> /dev/null
-  python bench.py --nv 108 --no-cpu-baseline --no-reference-defaults > $OUT/bench_nv108.json 2> /dev/null
+  python bench.py --full > $OUT/bench_jacobi.json 2> $OUT/bench_jacobi.err; echo "bench jacobi" >> $OUT/progress.txt
+  python bench.py --full --smoother gs --steps 100 --no-reference-defaults > $OUT/bench_gs.json 2> $OUT/bench_gs.err; echo "bench gs" >> $OUT/progress.txt
+  python bench.py --full --hierarchy spw --steps 100 --no-cpu-baseline > $OUT/bench_jacobi_spw_hierarchy.json 2> /dev/null
+  python bench.py --full --nv 108 --no-cpu-baseline --no-reference-defaults > $OUT/bench_nv108.json 2> /dev/null
 fi
 if [[ $PART == *b* ]]; then
   for cfg in cfg3 cfg5; do
@@ -50,18 +50,18 @@ if [[ $PART == *b* ]]; then
     kt ${cfg}_gs --config $cfg --smoother gs --steps 50 --warmup 10 --no-cpu-baseline --no-reference-defaults
     pmc ${cfg}_jacobi --config $cfg
     pmc ${cfg}_gs --config $cfg --smoother gs
-    python bench.py --config $cfg --steps 50 --warmup 10 --cpu-seconds 8 > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
-    python bench.py --config $cfg --smoother gs --steps 50 --warmup 10 --cpu-seconds 8 > $OUT/bench_${cfg}_gs.json 2> $OUT/bench_${cfg}_gs.err
+    python bench.py --full --config $cfg --steps 50 --warmup 10 --cpu-seconds 8 > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
+    python bench.py --full --config $cfg --smoother gs --steps 50 --warmup 10 --cpu-seconds 8 > $OUT/bench_${cfg}_gs.json 2> $OUT/bench_${cfg}_gs.err
     echo "bench $cfg" >> $OUT/progress.txt
   done
 fi
 if [[ $PART == *c* ]]; then
-  NGSAMG_FORCE_DIST=1 python bench.py --steps 100 --no-cpu-baseline > $OUT/bench_dist_world1.json 2> $OUT/bench_dist_world1.err
-  NGSAMG_FORCE_DIST=1 python bench.py --nv 108 --steps 200 --no-cpu-baseline > $OUT/bench_dist_world1_nv108.json 2> /dev/null
-  AMGX_DIST_GRAPH=0 NGSAMG_FORCE_DIST=1 python bench.py --nv 108 --steps 200 --no-cpu-baseline > $OUT/bench_dist_world1_nv108_direct_launches.json 2> /dev/null
-  NGSAMG_FORCE_DIST=1 python bench.py --smoother gs --steps 50 --no-cpu-baseline > $OUT/bench_dist_world1_gs.json 2> /dev/null
-  NGSAMG_FORCE_DIST=1 python bench.py --config cfg3 --steps 30 --warmup 5 > $OUT/bench_dist_world1_cfg3.json 2> /dev/null
-  NGSAMG_FORCE_DIST=1 python bench.py --config cfg5 --smoother gs --steps 30 --warmup 5 > $OUT/bench_dist_world1_cfg5_gs.json 2> /dev/null; echo "bench dist" >> $OUT/progress.txt
+  NGSAMG_FORCE_DIST=1 python bench.py --full --steps 100 --no-cpu-baseline > $OUT/bench_dist_world1.json 2> $OUT/bench_dist_world1.err
+  NGSAMG_FORCE_DIST=1 python bench.py --full --nv 108 --steps 200 --no-cpu-baseline > $OUT/bench_dist_world1_nv108.json 2> /dev/null
+  AMGX_DIST_GRAPH=0 NGSAMG_FORCE_DIST=1 python bench.py --full --nv 108 --steps 200 --no-cpu-baseline > $OUT/bench_dist_world1_nv108_direct_launches.json 2> /dev/null
+  NGSAMG_FORCE_DIST=1 python bench.py --full --smoother gs --steps 50 --no-cpu-baseline > $OUT/bench_dist_world1_gs.json 2> /dev/null
+  NGSAMG_FORCE_DIST=1 python bench.py --full --config cfg3 --steps 30 --warmup 5 > $OUT/bench_dist_world1_cfg3.json 2> /dev/null
+  NGSAMG_FORCE_DIST=1 python bench.py --full --config cfg5 --smoother gs --steps 30 --warmup 5 > $OUT/bench_dist_world1_cfg5_gs.json 2> /dev/null; echo "bench dist" >> $OUT/progress.txt
   NGSAMG_FORCE_DIST=1 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_d1 -- python bench.py --nv 108 --steps 5 --warmup 3 --no-cpu-baseline > /dev/null 2> $OUT/trace_d1.log
   f=$(find $OUT/trace_d1 -name "*kernel_trace.csv" | head -1); [ -n "$f" ] && python tools/trace_gaps.py $f 2 60,1000 25 > $OUT/trace_dist_world1_nv108.txt
   rm -rf $OUT/trace_d1
