@@ -176,6 +176,15 @@ int amgh_transpose_fill(const amgh_matrix* A, const int64_t* rowptr_T, int32_t* 
 /* C = A*B in two calls: first with col_out == NULL to obtain rowptr (size n_rows+1), then fill */
 int amgh_matmul(const amgh_matrix* A, const amgh_matrix* B, int64_t* rowptr_out, int32_t* col_out, double* val_out);
 
+/* symmetric diagonal (DIA) image of a scalar square matrix (the device library's level-0 pre-smoothing image, amgx.h):
+ * amgh_dia_detect sets *K_out = K > 0 and offsets_out[0 .. K) = the upper offsets col - row > 0, ascending, when every entry lies
+ * on one of at most max_diags (<= 16) diagonals, the offset set is symmetric, (number of diagonals) x n_rows <= max_fill x nnz
+ * and A equals its transpose bit for bit; otherwise *K_out < 0: -1 not square / blocked, -2 too many diagonals, -3 offsets
+ * not symmetric, -4 too much zero fill, -5 not bitwise symmetric, -6 diagonal matrix.  offsets_out holds 8 entries.
+ * amgh_dia_image fills vals_out [K * n_rows]: U_k[i] = A[i][i + offsets[k]] at vals_out[k * n_rows + i], exact 0 where absent. */
+int amgh_dia_detect(const amgh_matrix* A, int32_t max_diags, double max_fill, int32_t* offsets_out, int32_t* K_out);
+int amgh_dia_image(const amgh_matrix* A, int32_t K, const int32_t* offsets, double* vals_out);
+
 /* Galerkin product on an accelerator: when a pair is installed, amgh_setup hands the products (P^T A) P of levels
  * with at least `min_rows` fine (block) rows to `run` (which returns 0 = done with *n_rows / *nnz set, 2 = "not for me": the host
  * product runs, anything else = error) and reads the arrays back with `fetch` (which also releases the result).  The device

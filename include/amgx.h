@@ -191,7 +191,9 @@ int amgx_cycle_info(amgx_handle h, int32_t* tail_level, int32_t* dense_level, in
  * kernel of a long-row level reads (chunk-local 16-bit columns, gathered vector staged in LDS), 6 the local-window image of Q
  * (window-local columns, the coarse values of a 512-row window staged in LDS); fmt: -1 not built, 0 CSR-vector,
  * 1 sliced-ELL, 2 block sliced-ELL, 3 sliced-ELL with length-sorted row windows, 5 local-window sliced-ELL, 4 rigid-body transfer blocks (P_ik = w_ik Q(t_ik)
- * stored as (column, w, t): detected block by block at amgx_create, elasticity_energy.hpp:447-490); stored_entries counts padding
+ * stored as (column, w, t): detected block by block at amgx_create, elasticity_energy.hpp:447-490), 6 (which = 3 only) the
+ * symmetric diagonal image of A that replaces A' on levels whose A lies on at most 16 diagonals and is symmetric bit for bit
+ * (stored_entries = upper diagonals x rows; AMGX_NO_DIA=1 at amgx_create keeps A'); stored_entries counts padding
  * (for the traffic model in DESIGN.md) */
 int amgx_matrix_info(amgx_handle h, int level, int which, int32_t* fmt, int64_t* stored_entries, int32_t* lanes_per_row);
 

@@ -100,6 +100,8 @@ def host():
     lib.amgh_kuhn_pattern.argtypes = [C.c_int, c_i64p, c_i64p]
     lib.amgh_kuhn_assemble.argtypes = [C.c_int, c_i64p, c_f64p, C.c_int, C.c_int, C.c_double, C.c_double,
                                        c_f64p, c_i64p, c_i32p, c_f64p, c_f64p]
+    lib.amgh_dia_detect.argtypes = [C.POINTER(amgh_matrix), C.c_int32, C.c_double, c_i32p, c_i32p]
+    lib.amgh_dia_image.argtypes = [C.POINTER(amgh_matrix), C.c_int32, c_i32p, c_f64p]
     _host = lib
     return lib
 
@@ -253,7 +255,7 @@ AMGH_SYMBOLS = [
     "amgh_coarse_inverse", "amgh_log", "amgh_destroy", "amgh_calc_dinv", "amgh_coloring", "amgh_transpose_count",
     "amgh_transpose_fill", "amgh_matmul", "amgh_kuhn_pattern", "amgh_kuhn_assemble", "amgh_bgs_dinv", "amgh_bgs_coloring",
     "amgh_coloring_blocked", "amgh_hybrid_dinv", "amgh_hybrid_dinv_ext", "amgh_hybrid_dinv_block", "amgh_compact_blocks", "amgh_coloring_blockids", "amgh_hybrid_dinv_block_ids",
-    "amgh_set_galerkin_hook", "amgh_robust_pair_soc",
+    "amgh_set_galerkin_hook", "amgh_robust_pair_soc", "amgh_dia_detect", "amgh_dia_image",
 ]
 
 

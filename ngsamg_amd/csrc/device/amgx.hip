@@ -9,6 +9,7 @@
 // of kernel launches on one HIP stream, captured once per (b, x) pair into a hipGraph and replayed.
 #include "../../../include/amgx.h"
 #include "kernels.hpp"
+#include "../host/dia.hpp"
 #include <dlfcn.h>
 #include <algorithm>
 #include <array>
@@ -250,6 +251,21 @@ struct DevRestrict {                    // column-blocked P^T (see restrict_chun
   bool empty() const { return n_chunks == 0; }
 };
 
+// symmetric diagonal image of a scalar Jacobi level's A for the fused down kernel (dia_pre_restrict_kernel; host/dia.hpp):
+// replaces the SELL image of A' = A diag(omega Dinv) on that level
+struct DevDia {
+  int K = 0;                            // upper diagonals (0: the level has no DIA image)
+  int xcd = 0;
+  int32_t off[DIA_MAX_UPPER] = {};
+  DevBuf<double> val;                   // [K * n]
+  bool on() const { return K > 0; }
+  DiaMat view() const {
+    DiaMat m{val.p, xcd, {}};
+    for (int k = 0; k < DIA_MAX_UPPER; ++k) m.off[k] = off[k];
+    return m;
+  }
+};
+
 struct DevCsr {                         // plain CSR copy for the single-workgroup coarse tail
   DevBuf<int32_t> rowptr, col;
   DevBuf<double> val;
@@ -271,6 +287,7 @@ struct DevLevel {
   int fused_block = 1024;               // workgroup size = rows per chunk of the fused kernel
   DevMatrix A, P, PT;
   DevMatrix Apre;                       // scalar Jacobi levels: A * diag(omega * dinv), see EP_PRE in kernels.hpp
+  DevDia dia;                           // ... or, on levels whose A qualifies, its symmetric diagonal image (then Apre stays empty)
   // long-row levels: a second image of A' for the fused down kernel only, with chunk-local 16-bit columns into the sorted list of
   // the distinct columns of every 256-row chunk (sell_lw_pre_restrict_kernel: the gathered vector is staged in LDS)
   DevMatrix ApreLW;
@@ -1683,7 +1700,7 @@ struct Handle {
 
   bool plain(const DevLevel& L) const { return L.sm_steps <= 1 && !L.sm_symm; }
   // (a level without rows -- a rank that owns nothing -- is trivially folded: every kernel on it is a no-op)
-  bool folded(const DevLevel& L) const { return plain(L) && L.sm_type == AMGX_SM_JACOBI && (L.n == 0 || (!L.Q.empty() && (L.bs > 1 || !L.Apre.empty()))); }
+  bool folded(const DevLevel& L) const { return plain(L) && L.sm_type == AMGX_SM_JACOBI && (L.n == 0 || (!L.Q.empty() && (L.bs > 1 || !L.Apre.empty() || L.dia.on()))); }
 
   // pre-smoothing step of the cycles: x = 0; r = b; Smooth(x, b, r, 1, 1, 1)   (amg_matrix.cpp:193-206)
   // fold (only with folded(L)): x receives z = x + omega*Dinv*r, to be completed by post_smooth(..., fold = true)
@@ -1803,6 +1820,40 @@ struct Handle {
       }
       if (probe) HIPCHK(hipEventRecord(probe_e1, stream));
       if (!skip_rsum && sp.part != PART_INT)
+        hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
+                           R.oidx.p, R.part.p, b_coarse);
+      HIPCHK(hipGetLastError());
+      return;
+    }
+    if (plain(L) && L.sm_type == AMGX_SM_JACOBI && !L.RF.empty() && L.dia.on()) {
+      // symmetric diagonal image: 512-row chunks, one thread per row, whole level in one launch
+      const DevRestrict& R = L.RF;
+      const int ns = (int)((L.n + WAVE - 1) / WAVE);
+      const int nch = R.slice_list.n ? R.n_chunks : (ns + (512 / WAVE) - 1) / (512 / WAVE);
+      if (nch != R.n_chunks || L.fused_block != 512) throw Err("fused restriction (diagonal image): chunk / slice mismatch");
+      if (sp.part != PART_ALL) throw Err("fused restriction (diagonal image): the level is not split into interior / boundary parts");
+      const bool probe = probe_level == l && probe_kind == 8 && probe_e0;
+      if (probe) HIPCHK(hipEventRecord(probe_e0, stream));
+      if (nch > 0) {
+#define LAUNCH_DIA(K_, EPT_) hipLaunchKernelGGL((dia_pre_restrict_kernel<K_, EPT_>), dim3(nch), dim3(512), 0, stream, (int)L.n, ns, L.dia.view(), b, L.dinv.p, \
+                             L.omega, epf, x, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, (const int32_t*)R.slice_list.p)
+#define LAUNCH_DIA_K(K_) { if (R.ept == 4) LAUNCH_DIA(K_, 4); else LAUNCH_DIA(K_, 6); } break
+        switch (L.dia.K) {
+          case 1: LAUNCH_DIA_K(1);
+          case 2: LAUNCH_DIA_K(2);
+          case 3: LAUNCH_DIA_K(3);
+          case 4: LAUNCH_DIA_K(4);
+          case 5: LAUNCH_DIA_K(5);
+          case 6: LAUNCH_DIA_K(6);
+          case 7: LAUNCH_DIA_K(7);
+          case 8: LAUNCH_DIA_K(8);
+          default: throw Err("fused restriction (diagonal image): bad number of diagonals");
+        }
+#undef LAUNCH_DIA_K
+#undef LAUNCH_DIA
+      }
+      if (probe) HIPCHK(hipEventRecord(probe_e1, stream));
+      if (!skip_rsum)
         hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
                            R.oidx.p, R.part.p, b_coarse);
       HIPCHK(hipGetLastError());
@@ -3277,6 +3328,20 @@ static Handle* create(const amgx_hierarchy_desc* d, int dense_first = 1) {
       }, "smoother data");
       if (s.sm_type == AMGX_SM_JACOBI && s.A.br == 1 && s.sm_steps <= 1 && !s.sm_symm) {
         tasks.run([&] {
+        // dinv_i * A_ii == 1 (to 1e-13) on every row with dinv_i != 0
+        auto host_diag_plain = [&] {
+          std::vector<char> notplain(setup_threads(), 0);
+          par_for(s.A.n_rows, [&](int64_t i0, int64_t i1, int t) {
+            for (int64_t i = i0; i < i1; ++i) {
+              if (s.dinv[i] == 0.0) continue;
+              double aii = 0.0;
+              for (int64_t k = s.A.rowptr[i]; k < s.A.rowptr[i + 1]; ++k) if (s.A.col[k] == i) { aii = s.A.val[k]; break; }
+              if (!(std::fabs(s.dinv[i] * aii - 1.0) < 1e-13)) { notplain[t] = 1; break; }
+            }
+          });
+          for (char cc : notplain) if (cc) return false;
+          return true;
+        };
         // long-row levels (>= 1) of a reference-shaped hierarchy: the "local window" image for the fused down kernel
         auto lw_image = [&]() -> bool {
           const int64_t nnzA = s.A.rowptr[s.A.n_rows];
@@ -3322,6 +3387,48 @@ static Handle* create(const amgx_hierarchy_desc* d, int dense_first = 1) {
           if (L.RF.empty()) { L.ApreLW = DevMatrix(); L.lw_cptr.release(); L.lw_ccol.release(); return false; }
           return true;
         };
+        // levels whose A lies on at most 16 diagonals and equals its transpose bit for bit (Kuhn P1 matrices in natural vertex order):
+        // the fused down kernel streams the symmetric diagonal image of A instead of A' (dia_pre_restrict_kernel) -- 7 of the 15
+        // diagonals from HBM at cfg 2, the lower ones are shifted re-reads of the same arrays, and no index stream.  Not on levels
+        // a rank-partitioned driver runs stage by stage (dense_first < 0), nor below AMGX_DIA_MIN_ROWS rows (2 M: the smaller levels
+        // keep the SELL image).  AMGX_NO_DIA=1 disables it.
+        auto dia_image = [&]() -> bool {
+          int64_t min_rows = 2000000;
+          if (const char* e = std::getenv("AMGX_DIA_MIN_ROWS")) min_rows = std::atoll(e);
+          if (std::getenv("AMGX_NO_DIA") || dense_first < 0 || s.A.n_rows != s.A.n_cols || s.A.n_rows < std::max<int64_t>(1, min_rows) ||
+              s.omega == 0.0 || std::getenv("AMGX_NO_WDIAG") || s.P.br != 1 || s.P.bc != 1 || s.P.rowptr[s.P.n_rows] >= (int64_t)2147483647 ||
+              std::getenv("AMGX_NO_FUSED_RESTRICT")) return false;
+          // the kernel puts the diagonal term back as omega*b_i (0 where dinv_i = 0): dinv must be the plain inverse diagonal
+          if (dev_images ? !diagA.plain : !host_diag_plain()) return false;
+          auto par = [](int64_t nb, auto&& f) { par_for(nb, [&](int64_t a, int64_t b, int) { for (int64_t q = a; q < b; ++q) f(q); }, 1); };
+          int32_t off[dia::MAX_UPPER];
+          const int K = dia::detect(s.A.n_rows, s.A.n_cols, s.A.rowptr, s.A.col, s.A.val, dia::MAX_DIAGS, 1.05, off, par);
+          if (K <= 0 || K > DIA_MAX_UPPER) return false;
+          DevDia& D = L.dia;
+          D.K = K;
+          for (int k = 0; k < K; ++k) D.off[k] = off[k];
+          std::vector<double> hv;
+          if (!dev_images || verify_images) {
+            hv.resize((size_t)K * (size_t)s.A.n_rows);
+            dia::upper_image(s.A.n_rows, s.A.rowptr, s.A.col, s.A.val, K, off, hv.data(), par);
+          }
+          if (dev_images) {
+            dev_build_dia(csrA, D);
+            if (verify_images && std::memcmp(db_download(D.val, hv.size()).data(), hv.data(), hv.size() * sizeof(double)) != 0)
+              throw Err("AMGX_VERIFY_IMAGES: the diagonal image differs");
+          } else
+            D.val.upload(hv);
+          L.fused_block = 512;
+          int64_t cc_min = 200000;
+          if (const char* e = std::getenv("AMGX_COMPACT_CHUNKS_MIN_ROWS")) cc_min = std::atoll(e);
+          if (s.A.n_rows >= cc_min && !std::getenv("AMGX_NO_COMPACT_CHUNKS")) {
+            const std::vector<int32_t> sl = cluster_slices(s.P, 512 / WAVE);
+            build_restrict(s.P, L.RF, 512, 6 * 512, 512, &sl);
+          } else
+            build_restrict(s.P, L.RF, 512, 6 * 512, 512);
+          if (L.RF.empty()) { L.dia = DevDia(); return false; }
+          return true;
+        };
         auto fused_restrict = [&] {
           if (lw_image()) return;
           // fused pre-smoothing + restriction when A' is in the one-thread-per-row SELL form (big levels).
@@ -3352,6 +3459,7 @@ static Handle* create(const amgx_hierarchy_desc* d, int dense_first = 1) {
             build_restrict(s.P, L.RF, L.fused_block / G, 6 * L.fused_block, L.fused_block);
           }
         };
+        if (dia_image()) return;
         // (device builder: A' = A diag(omega Dinv) from the CSR of A that is already there; the diagonal slot carries omega*Dinv_i
         //  under the same conditions as below)
         const bool dev_wdiag = s.omega != 0.0 && !std::getenv("AMGX_NO_WDIAG") && diagA.plain;
@@ -3376,18 +3484,7 @@ static Handle* create(const amgx_hierarchy_desc* d, int dense_first = 1) {
         std::vector<double> wdv;
         if (s.omega != 0.0 && !std::getenv("AMGX_NO_WDIAG")) {
           // the epilogue re-inserts A'_ii b_i as omega*b_i (or 0 where dinv_i = 0): valid iff dinv is the plain inverse diagonal
-          std::vector<char> notplain(setup_threads(), 0);
-          par_for(s.A.n_rows, [&](int64_t i0, int64_t i1, int t) {
-            for (int64_t i = i0; i < i1; ++i) {
-              if (s.dinv[i] == 0.0) continue;
-              double aii = 0.0;
-              for (int64_t k = s.A.rowptr[i]; k < s.A.rowptr[i + 1]; ++k) if (s.A.col[k] == i) { aii = s.A.val[k]; break; }
-              if (!(std::fabs(s.dinv[i] * aii - 1.0) < 1e-13)) { notplain[t] = 1; break; }
-            }
-          });
-          bool plain = true;
-          for (char cc : notplain) if (cc) plain = false;
-          if (plain) {
+          if (host_diag_plain()) {
             wdv.resize((size_t)s.A.n_rows);
             par_for(s.A.n_rows, [&](int64_t i0, int64_t i1, int) { for (int64_t i = i0; i < i1; ++i) wdv[i] = s.omega * s.dinv[i]; }, 1 << 16);
           }
@@ -3525,6 +3622,7 @@ static Handle* create(const amgx_hierarchy_desc* d, int dense_first = 1) {
       const double avg = s.A.n_rows ? (double)s.A.rowptr[s.A.n_rows] / (double)s.A.n_rows : 0.0;
       const int on = mode >= 2 || (mode == 1 && avg >= 24.0 && s.A.n_rows >= 200000);
       L.A.sell.xcd = L.Apre.sell.xcd = L.Q.sell.xcd = L.gsb.rest.sell.xcd = on;
+      L.dia.xcd = std::getenv("AMGX_DIA_XCD") ? 1 : 0;        // (A/B hook: each XCD walks one contiguous eighth of the chunks)
       if (mode >= 3) L.P.sell.xcd = L.PT.sell.xcd = on;
     }
     const size_t len = (size_t)std::max<int64_t>(1, L.ext_len());
@@ -4061,6 +4159,12 @@ int amgx_matrix_info(amgx_handle hh, int level, int which, int32_t* fmt, int64_t
     if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_matrix_info: level out of range");
     if (which < 0 || which > 6) throw amgx::Err("matrix query: which must be 0..6");
     const amgx::DevLevel& LV = h.lev[level];
+    if (which == 3 && LV.dia.on()) {          // the symmetric diagonal image of A stands in for A' (format 6)
+      if (fmt) *fmt = 6;
+      if (stored) *stored = (int64_t)LV.dia.K * LV.n;
+      if (lanes) *lanes = 1;
+      return;
+    }
     const amgx::DevMatrix& M = which == 0 ? LV.A : which == 1 ? LV.P : which == 2 ? LV.PT : which == 3 ? LV.Apre : which == 4 ? LV.Q : which == 5 ? LV.ApreLW : LV.QLW;
     if (fmt) *fmt = M.empty() ? -1 : (which >= 5 ? 5 : ((M.fmt == amgx::FMT_SELL && M.sell.win) ? 3 : M.fmt));
     if (stored) *stored = M.stored;
@@ -4073,6 +4177,9 @@ int amgx_matrix_stream_bytes(amgx_handle hh, int level, int which, int64_t* byte
     if (level < 0 || level >= h.n_levels() || !bytes) throw amgx::Err("amgx_matrix_stream_bytes: bad arguments");
     if (which < 0 || which > 6) throw amgx::Err("matrix query: which must be 0..6");
     const amgx::DevLevel& LV = h.lev[level];
+    // diagonal image: the K upper diagonals (the lower ones are re-reads of the same arrays) + the dinv stream the kernel reads in
+    // place of the wdiag slot
+    if (which == 3 && LV.dia.on()) { *bytes = (int64_t)(LV.dia.K + 1) * LV.n * (int64_t)sizeof(double); return; }
     const amgx::DevMatrix& M = which == 0 ? LV.A : which == 1 ? LV.P : which == 2 ? LV.PT : which == 3 ? LV.Apre : which == 4 ? LV.Q : which == 5 ? LV.ApreLW : LV.QLW;
     *bytes = M.stream_bytes;
   });

@@ -404,6 +404,30 @@ static bool dev_images_wanted(const amgx_matrix& A) {
   return G == 1;
 }
 
+// symmetric diagonal image (DevDia; host builder: dia::upper_image) of a scalar CSR matrix on the device: U_k[i] = A[i][i + off[k]],
+// exact 0 where absent (the caller zeroes the array); one thread per row, entries with col > row only
+__global__ void db_dia_kernel(int64_t n, const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const double* __restrict__ val,
+                              DiaMat D, int K, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+    const int64_t d = (int64_t)col[k] - i;
+    if (d <= 0) continue;
+    for (int q = 0; q < K; ++q)
+      if (D.off[q] == d) { out[q * n + i] = val[k]; break; }
+  }
+}
+
+static void dev_build_dia(const DevCsrSrc& A, DevDia& D) {
+  const size_t len = (size_t)D.K * (size_t)A.n_rows;
+  D.val.alloc(len);
+  HIPCHK(hipMemset(D.val.p, 0, len * sizeof(double)));
+  hipLaunchKernelGGL(db_dia_kernel, dim3((unsigned)((A.n_rows + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, 0, A.n_rows, A.rowptr.p, A.col.p, A.val.p,
+                     D.view(), D.K, D.val.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+}
+
 struct DbDiagInfo { bool all_diag = false, plain = false; };
 
 static DbDiagInfo dev_diag_check(const DevCsrSrc& A, const double* d_dinv) {

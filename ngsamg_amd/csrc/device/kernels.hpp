@@ -1348,6 +1348,108 @@ __global__ __launch_bounds__(FUSED_BLOCK) void sell_pre_restrict_kernel(int64_t 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Symmetric diagonal (DIA) image of a level matrix A (host/dia.hpp): the K upper diagonals U_k[i] = A[i][i + o_k] as
+// row-aligned arrays (exact 0 where absent); the lower couplings of row i are A[i][i - o_k] = U_k[i - o_k], the same
+// arrays shifted by o_k -- lines another workgroup streamed shortly before (reuse distance <= o_K rows, ~10 MB of traffic
+// at cfg 2), so they come from L2 / Infinity Cache instead of a second copy of the matrix in HBM.  No index stream.
+constexpr int DIA_MAX_UPPER = 8;
+struct DiaMat {
+  const double* val;          // [K * n]: U_k at val + k * n
+  int xcd;                    // workgroup -> chunk mapping as SellMat::xcd
+  int off[DIA_MAX_UPPER];     // o_1 < ... < o_K
+};
+
+// Fused Jacobi pre-smoothing + residual + chunk-local restriction (sell_pre_restrict_kernel<512, 0, EPT, 1>) on the DIA
+// image of A itself: A' = A diag(omega Dinv) cannot be stored symmetrically, so the kernel forms the neighbours'
+// x_j = omega * (dinv_j * b_j) -- bitwise the value the kernel stores for row j -- and computes r = b - A x with the
+// diagonal term omega * b_i (0 where dinv_i = 0) as the wdiag image carries it; couplings in ascending column order.
+// Same DevRestrict data (chunk_slot / slot_ptr / w / fi / dest, compact chunks via slice_list), same outputs.
+template <int K, int EPT = 4>
+__global__ __launch_bounds__(512) void dia_pre_restrict_kernel(int n_rows, int n_slices, DiaMat D, const double* __restrict__ b,
+                                                               const double* __restrict__ dinv, double omega, int nt, double* __restrict__ x,
+                                                               const int32_t* __restrict__ chunk_slot, const int32_t* __restrict__ slot_ptr,
+                                                               const double* __restrict__ w, const uint16_t* __restrict__ fi,
+                                                               double* __restrict__ part, const int32_t* __restrict__ dest,
+                                                               const int32_t* __restrict__ slice_list) {
+  constexpr int FB = 512;
+  constexpr int FUSED_MAX_ENTRIES = EPT * FB;
+  __shared__ double rl[FB];
+  __shared__ double pr[FUSED_MAX_ENTRIES];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int c = D.xcd ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+  const int sq = c * (FB / WAVE) + (threadIdx.x >> 6);
+  const int s_raw = slice_list ? slice_list[sq] : sq;
+  const int s = __builtin_amdgcn_readfirstlane(s_raw < 0 ? n_slices : s_raw);
+  const int row = s * WAVE + lane;
+  // chunk-local restriction data first (see sell_pre_restrict_kernel)
+  const int s0 = chunk_slot[c], s1 = chunk_slot[c + 1];
+  const int e0 = slot_ptr[s0], e1 = slot_ptr[s1];
+  double wq[EPT];
+  int fq[EPT];
+#pragma unroll
+  for (int q = 0; q < EPT; ++q) {
+    const int e = e0 + threadIdx.x + q * FB;
+    wq[q] = e < e1 ? ld_nt(w + e) : 0.0;
+    fq[q] = e < e1 ? (int)ld_nt(fi + e) : 0;
+  }
+  const int myslot = s0 + threadIdx.x;
+  int mydest = myslot, pa_raw = 0, pb_raw = 0;
+  if (myslot < s1) {
+    if (dest) mydest = dest[myslot];
+    pa_raw = slot_ptr[myslot];
+    pb_raw = slot_ptr[myslot + 1];
+  }
+  double r = 0.0;
+  if (s < n_slices && row < n_rows) {
+    // every operand requested before the first product (out-of-range neighbours read row i itself and are masked)
+    double al[K], au[K], bl[K], bu[K], dl[K], du[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const double* __restrict__ U = D.val + (int64_t)k * n_rows;
+      const int o = D.off[k];
+      const int jl = row - o >= 0 ? row - o : row;
+      const int ju = row + o < n_rows ? row + o : row;
+      al[k] = U[jl]; bl[k] = b[jl]; dl[k] = dinv[jl];
+      au[k] = U[row]; bu[k] = b[ju]; du[k] = dinv[ju];
+    }
+    const double bi = b[row], di = dinv[row];
+    double acc = 0.0;
+#pragma unroll
+    for (int k = K - 1; k >= 0; --k)
+      if (row - D.off[k] >= 0) acc += al[k] * (omega * (dl[k] * bl[k]));
+    if (di != 0.0) acc += omega * bi;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (row + D.off[k] < n_rows) acc += au[k] * (omega * (du[k] * bu[k]));
+    r = bi - acc;
+    double xi = omega * (di * bi);
+    if (nt & EPF_FOLD) xi += omega * (di * r);
+    if (nt & EPF_NT) __builtin_nontemporal_store(xi, x + row);
+    else x[row] = xi;
+  }
+  rl[threadIdx.x] = r;
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < EPT; ++q) {
+    const int e = threadIdx.x + q * FB;
+    if (e0 + e < e1) pr[e] = wq[q] * rl[fq[q]];
+  }
+  __syncthreads();
+  if (myslot < s1) {
+    const int pa = pa_raw - e0, pb = pb_raw - e0;
+    double acc = 0.0;
+    for (int k = pa; k < pb; ++k) acc += pr[k];
+    part[mydest] = acc;
+  }
+  for (int slot = myslot + FB; slot < s1; slot += FB) {
+    const int a = slot_ptr[slot] - e0, bnd = slot_ptr[slot + 1] - e0;
+    double acc = 0.0;
+    for (int k = a; k < bnd; ++k) acc += pr[k];
+    part[dest ? dest[slot] : slot] = acc;
+  }
+}
+
 // The residual after a block-hybrid Gauss-Seidel sweep from zero, r = c .* x - A_rest x, fused with the chunk-local
 // restriction like sell_pre_restrict_kernel<.., 1>, for the WINDOWED SELL form (rows of a 512-row window stored by
 // decreasing length): A_rest has ragged rows (each row lost its in-block lower-colour couplings), plain slices pad ~27 %.

@@ -1,6 +1,7 @@
 // C ABI of the host setup library, see include/amgh.h.
 #include "../../../include/amgh.h"
 #include "hierarchy.hpp"
+#include "dia.hpp"
 #include <cstring>
 #include <memory>
 
@@ -410,6 +411,30 @@ int amgh_kuhn_assemble(int dim, const int64_t* shape, const double* coords, int 
     if ((kind == 0 && bs != 1) || (kind == 1 && bs != dim) || (kind == 2 && bs != dim + nrot) || kind < 0 || kind > 2)
       throw amgh::Error("kuhn: kind / block size mismatch");
     amgh::kuhn_assemble(dim, shape, coords, kind, bs, mu, lam, cell_coef_or_null, rowptr, col_out, val_out, load_out_or_null);
+  });
+}
+
+int amgh_dia_detect(const amgh_matrix* A, int32_t max_diags, double max_fill, int32_t* offsets_out, int32_t* K_out) {
+  return guard([&] {
+    check_matrix(A);
+    if (!offsets_out || !K_out) throw amgh::Error("amgh_dia_detect: bad arguments");
+    if (A->br != 1 || A->bc != 1) { *K_out = dia::NOT_SQUARE; return; }
+    *K_out = dia::detect(A->n_rows, A->n_cols, A->rowptr, A->col, A->val, max_diags, max_fill, offsets_out, [](int64_t nb, auto&& f) {
+#pragma omp parallel for schedule(dynamic, 4)
+      for (int64_t b = 0; b < nb; b++) f(b);
+    });
+  });
+}
+
+int amgh_dia_image(const amgh_matrix* A, int32_t K, const int32_t* offsets, double* vals_out) {
+  return guard([&] {
+    check_matrix(A);
+    if (A->br != 1 || A->bc != 1 || A->n_rows != A->n_cols || K < 1 || K > dia::MAX_UPPER || !offsets || !vals_out)
+      throw amgh::Error("amgh_dia_image: bad arguments");
+    dia::upper_image(A->n_rows, A->rowptr, A->col, A->val, K, offsets, vals_out, [](int64_t nb, auto&& f) {
+#pragma omp parallel for schedule(dynamic, 4)
+      for (int64_t b = 0; b < nb; b++) f(b);
+    });
   });
 }
 
