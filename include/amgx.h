@@ -201,6 +201,22 @@ int amgx_matrix_info(amgx_handle h, int level, int which, int32_t* fmt, int64_t*
  * streams from HBM -- the model value behind "traffic" in DESIGN.md */
 int amgx_matrix_stream_bytes(amgx_handle h, int level, int which, int64_t* bytes);
 
+/* read-only report of the paths amgx_create chose for one level (changes nothing).  Fills out[0 .. min(n_out, 19)):
+ *    0 fused Jacobi down kernel: 0 none, 1 sliced-ELL, 2 sliced-ELL with row windows, 3 local-window sliced-ELL, 4 diagonal image
+ *    1 its workgroup size (rows per chunk x lanes)      2 its lanes per row (0: none)
+ *    3 entries of P per thread of its chunk-local restriction (0: none)     4 compact chunks (1: chunks of listed slices)
+ *    5 most slots (distinct coarse columns) in one chunk                    6 most entries of P in one chunk
+ *    7 upper diagonals K of the diagonal image (0: none)
+ *    8 .. 11 remapped workgroup placement (1) of A, A', Q and of the diagonal image
+ *   12, 13 slices of A with 16-bit columns, all slices of A (sliced-ELL forms; 0 otherwise)
+ *   14, 15 the same for A'
+ *   16 chunks of the local-window image of A' that keep global columns (no window)
+ *   17 folded post-smoothing (1: the V-cycle runs Q on the way up)
+ *   18 chunks of the chunk-local restriction
+ * Returns 0, or non-zero for a bad level or n_out < 1. */
+#define AMGX_LEVEL_PATHS_N 19
+int amgx_level_paths(amgx_handle h, int level, int64_t* out, int n_out);
+
 /* measurement hook for bench.py: launches one hot-path kernel `reps` times on the handle's stream,
  * bracketed by HIP events, and returns the average duration in milliseconds.
  *   op = 0: residual SpMV  r = b - A_level x      (the dominant kernel of the Jacobi V-cycle)

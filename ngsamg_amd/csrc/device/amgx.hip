@@ -245,6 +245,8 @@ struct DevRestrict {                    // column-blocked P^T (see restrict_chun
   DevBuf<double> w, part;
   DevBuf<uint16_t> fi;
   int ept = 4;                          // entries of P per thread of the fused kernels (4 or 6: the fullest chunk decides)
+  int max_slots = 0;                    // most slots / entries of P in one chunk (amgx_level_paths reports them)
+  int64_t max_entries = 0;
   // compact chunks (cluster_slices): chunk c works on the 64-row slices slice_list[c * spc .. (c + 1) * spc) instead of spc
   // consecutive ones (-1: no slice); empty = consecutive slices
   DevBuf<int32_t> slice_list;
@@ -1038,6 +1040,8 @@ static void build_restrict(const amgx_matrix& P, DevRestrict& R, int CH = RESTRI
   R.n_chunks = (int)nch; R.n_slots = ns;
   int64_t mx_chunk = 0;
   for (int64_t v : fullest) mx_chunk = std::max(mx_chunk, v);
+  for (int64_t c = 0; c < nch; ++c) R.max_slots = std::max(R.max_slots, chunk_slot[c + 1] - chunk_slot[c]);
+  R.max_entries = mx_chunk;
   R.ept = mx_chunk <= (int64_t)4 * threads ? 4 : 6;
   if ((CH == 256 || CH == 128) && threads == 512 && max_entries == 4 * 512) R.ept = mx_chunk <= (int64_t)2 * threads ? 2 : 4;     // (local-window chunks: see lw_image)
   if (const char* e = std::getenv("AMGX_FUSED_EPT_MAX")) if (R.ept > std::atoi(e)) { R = DevRestrict(); return; }     // (A/B hook: keep the separate kernels instead)
@@ -3457,6 +3461,9 @@ static Handle* create(const amgx_hierarchy_desc* d, int dense_first = 1) {
               build_restrict(s.P, L.RF, L.fused_block, 6 * L.fused_block, L.fused_block, &sl);
             } else
             build_restrict(s.P, L.RF, L.fused_block / G, 6 * L.fused_block, L.fused_block);
+            // several lanes per row: the kernel exists for 4 entries of P per thread only; a chunk of 512 / G rows with more
+            // than 2048 entries (a prolongation with more than 4 G entries per row) keeps the separate kernels
+            if (G > 1 && L.RF.ept != 4) L.RF = DevRestrict();
           }
         };
         if (dia_image()) return;
@@ -4182,6 +4189,46 @@ int amgx_matrix_stream_bytes(amgx_handle hh, int level, int which, int64_t* byte
     if (which == 3 && LV.dia.on()) { *bytes = (int64_t)(LV.dia.K + 1) * LV.n * (int64_t)sizeof(double); return; }
     const amgx::DevMatrix& M = which == 0 ? LV.A : which == 1 ? LV.P : which == 2 ? LV.PT : which == 3 ? LV.Apre : which == 4 ? LV.Q : which == 5 ? LV.ApreLW : LV.QLW;
     *bytes = M.stream_bytes;
+  });
+}
+
+int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
+  return guard(hh, [&](amgx::Handle& h) {
+    if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_level_paths: level out of range");
+    if (!out || n_out < 1) throw amgx::Err("amgx_level_paths: bad arguments");
+    const amgx::DevLevel& L = h.lev[level];
+    const amgx::DevRestrict& R = L.RF;
+    int64_t v[AMGX_LEVEL_PATHS_N] = {};
+    // the branch order of pre_smooth_restrict
+    const bool fused = h.plain(L) && L.sm_type == AMGX_SM_JACOBI && !R.empty();
+    if (fused) {
+      v[0] = !L.ApreLW.empty() ? 3 : L.dia.on() ? 4 : L.Apre.sell.win ? 2 : 1;
+      v[1] = L.fused_block;
+      v[2] = v[0] == 3 ? L.ApreLW.lanes : v[0] == 4 ? 1 : L.Apre.lanes;
+      v[3] = R.ept;
+    }
+    if (!R.empty()) {
+      v[4] = R.slice_list.n ? 1 : 0;
+      v[5] = R.max_slots;
+      v[6] = R.max_entries;
+      v[18] = R.n_chunks;
+    }
+    v[7] = L.dia.K;
+    v[8] = L.A.sell.xcd; v[9] = L.Apre.sell.xcd; v[10] = L.Q.sell.xcd; v[11] = L.dia.xcd;
+    auto slices = [](const amgx::DevMatrix& M, int64_t* c16, int64_t* all) {
+      if (M.empty() || M.fmt != amgx::FMT_SELL || M.n_slices <= 0) return;
+      const std::vector<int64_t> sp = amgx::db_download(M.sell.slice_ptr, (size_t)M.n_slices);
+      *all = M.n_slices;
+      for (int64_t p : sp) *c16 += p & 1;
+    };
+    slices(L.A, &v[12], &v[13]);
+    slices(L.Apre, &v[14], &v[15]);
+    if (!L.ApreLW.empty() && L.lw_cptr.n > 1) {
+      const std::vector<int32_t> cp = amgx::db_download(L.lw_cptr, L.lw_cptr.n);
+      for (size_t c = 0; c + 1 < cp.size(); ++c) v[16] += cp[c + 1] == cp[c];
+    }
+    v[17] = h.folded(L) ? 1 : 0;
+    for (int k = 0; k < std::min(n_out, AMGX_LEVEL_PATHS_N); ++k) out[k] = v[k];
   });
 }
 

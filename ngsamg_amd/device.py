@@ -425,6 +425,20 @@ class DeviceAMGMatrix:
         return {"fmt": {-1: None, 0: "csrvec", 1: "sell", 2: "bsell", 3: "sellwin", 4: "rigid-body", 5: "sell-lw", 6: "dia"}.get(fmt.value, "?"), "stored": stored.value, "lanes": lanes.value,
                 "stream_bytes": nb.value}
 
+    _PATH_KEYS = ("kernel", "fused_block", "lanes", "ept", "compact", "max_slots", "max_entries", "dia_k", "xcd_A", "xcd_Apre",
+                  "xcd_Q", "xcd_dia", "A_slices16", "A_slices", "Apre_slices16", "Apre_slices", "lw_no_window", "folded", "chunks")
+
+    def level_paths(self, level):
+        """the paths amgx_create chose for one level (amgx_level_paths, read-only): the fused Jacobi down kernel (None, "sell",
+        "sell-win", "sell-lw" or "dia"), its workgroup size and lanes per row, the chunk-local restriction (entries of P per thread,
+        compact chunks, most slots / entries in one chunk, number of chunks), the diagonals of the DIA image, the XCD placement
+        flags, the 16-bit / all slices of A and A', the local-window chunks without a window and whether the level is folded"""
+        out = np.zeros(len(self._PATH_KEYS), dtype=np.int64)
+        self._ck(self._lib.amgx_level_paths(self._h, int(level), out.ctypes.data_as(_lib.c_i64p), out.size))
+        d = dict(zip(self._PATH_KEYS, (int(v) for v in out)))
+        d["kernel"] = {0: None, 1: "sell", 2: "sell-win", 3: "sell-lw", 4: "dia"}[d["kernel"]]
+        return d
+
     def time_op(self, level, op, reps=20):
         ms = C.c_double()
         self._ck(self._lib.amgx_time_op(self._h, level, int(op), int(reps), C.byref(ms)))

@@ -107,3 +107,44 @@ def test_block_level_and_non_symmetric_pattern_refused():
     rowptr = np.concatenate([[0], np.cumsum([2] * (n - 1) + [1])])
     col = np.concatenate([[i, i + 1] for i in range(n - 1)] + [[n - 1]])
     assert detect(n, rowptr, col, np.ones(col.size))[0] == -3
+
+
+# the stencil generators of tests/reorder.py: every number of upper diagonals K = 1 .. 6 the detector can give a non-Kuhn level
+STENCILS = [("chain", (5000,), 1), ("fd5", (130, 110), 2), ("fd7", (41, 37, 29), 3), ("fd9", (130, 110), 4),
+            ("offsets:1,3,64,65,500", (20000,), 5), ("offsets:1,2,7,64,130,131", (20000,), 6)]
+
+
+@pytest.mark.parametrize("kind,shape,K", STENCILS)
+def test_stencils_detected_with_their_diagonals(kind, shape, K):
+    from tests import reorder as R
+    A, _ = R.stencil(kind, shape, seed=K)
+    offs = R.upper_offsets(A)
+    assert len(offs) == K and detect(A.shape[0], A.indptr, A.indices, A.data) == (K, offs)
+    if kind == "fd9":
+        assert offs == [1, shape[0] - 1, shape[0], shape[0] + 1]
+    U = image(A.shape[0], A.indptr, A.indices, A.data, offs)
+    for k, o in enumerate(offs):
+        assert np.array_equal(U[k, :A.shape[0] - o], A.diagonal(o))
+    # reversal keeps the offsets (A[i][i + o] becomes A[n - 1 - i - o][n - 1 - i]: the same diagonals)
+    p = R.permutation("reverse", A.shape[0])
+    B = A[p][:, p].tocsr()
+    B.sort_indices()
+    assert detect(B.shape[0], B.indptr, B.indices, B.data) == (K, offs)
+    # random orderings, and RCM orderings of the 2D / 3D grids (level sets of varying width), scatter the entries over more
+    # than 16 diagonals
+    for pk in ("random", "rcm") if kind.startswith("fd") else ("random",):
+        p = R.permutation(pk, A.shape[0], seed=1, A=A)
+        B = A[p][:, p].tocsr()
+        B.sort_indices()
+        assert detect(B.shape[0], B.indptr, B.indices, B.data)[0] == -2, pk
+
+
+@pytest.mark.parametrize("shape", [(41, 37, 29), (130, 110)])
+def test_reversed_kuhn_keeps_its_diagonals(shape):
+    from tests import reorder as R
+    p = fem.poisson_fast(shape, dirichlet="right|top")
+    K, offs = detect(p.n, p.rowptr, p.col, p.val)
+    q = R.permutation("reverse", p.n)
+    from ngsamg_amd._lib import Matrix
+    B = R.permute_matrix(Matrix(p.n, p.n, 1, 1, p.rowptr, p.col, p.val), q, q)
+    assert detect(p.n, B.rowptr, B.col, B.val) == (K, offs) and K == (7 if len(shape) == 3 else 3)

@@ -53,6 +53,8 @@ def test_dia_cycles_match_oracle_and_sell_path(shape, diri, mcs, cycle, monkeypa
         assert _rel(_apply(nofold, b), ref) < 1e-12
         # compact chunks (on by default from 200 k rows) on the same image
         compact = _dev(H, monkeypatch, env=[("AMGX_COMPACT_CHUNKS_MIN_ROWS", "0")])
+        assert compact.level_paths(0)["kernel"] == "dia" and compact.level_paths(0)["compact"] == 1
+        assert dev.level_paths(0)["compact"] == 0
         assert _rel(_apply(compact, b), x) < 1e-13
     # levels >= 1 (aggregated, not on <= 16 diagonals) keep their formats
     for l in range(1, dev.GetNLevels() - 1):

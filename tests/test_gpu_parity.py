@@ -663,4 +663,6 @@ def test_compact_chunks_of_the_fused_down_kernel(monkeypatch):
     plain = DeviceAMGMatrix(H, sm_type="jacobi", device=0)
     xp = plain.apply(b)
     assert np.linalg.norm(x - xp) <= 1e-13 * np.linalg.norm(xp)
-    assert not np.array_equal(x, xp) or True
+    # the forced path ran: level 0 has compact chunks, the AMGX_NO_COMPACT_CHUNKS handle consecutive ones
+    assert dev.level_paths(0)["kernel"] == "sell" and dev.level_paths(0)["compact"] == 1
+    assert plain.level_paths(0)["kernel"] == "sell" and plain.level_paths(0)["compact"] == 0
