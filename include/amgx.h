@@ -213,8 +213,23 @@ int amgx_matrix_stream_bytes(amgx_handle h, int level, int which, int64_t* bytes
  *   16 chunks of the local-window image of A' that keep global columns (no window)
  *   17 folded post-smoothing (1: the V-cycle runs Q on the way up)
  *   18 chunks of the chunk-local restriction
+ *   Gauss-Seidel sweep (0 where the level has none):
+ *   19 form: 0 none, 1 multicolour scalar (gs_color_kernel), 2 multicolour block row-list (bgs_color_kernel),
+ *      3 multicolour block BSELL (bgs_bsell_color_kernel), 4 block-hybrid scalar (gsb_sweep_kernel),
+ *      5 block-hybrid square-block (bgsb_sweep_kernel), 6 block-coloured square-block (bgsb_sweep_kernel per block colour),
+ *      7 aggregate block Gauss-Seidel (bgs_block_kernel)
+ *   20 lanes per row G (forms 1 and 4)     21 workgroup size of the sweep (forms 1 .. 6)
+ *   22 rows per sweep block (form 4: B, forms 5 and 6: block rows BB)
+ *   23 colours (in-block colours for forms 4 .. 6)     24 block colours (form 6)
+ *   25 split images present (form 1: lower / upper, 3: block lower / upper, 4: lowin / rest, 5 and 6: rest)
+ *   26, 27 form 4: widest slice (entries per lane) of the lower in-block image and of the whole image
+ *   28 form 4: the sweep from zero takes the narrow kernel (2 entries per lane and pass; otherwise 8)
+ *   29 form 4: the general sweep takes the mid-width kernel (5 entries per lane and pass; otherwise 8)
+ *   30 form 4: the general sweep reads the local-window image
+ *   31 form 2: bitmask of the lanes per block row W (1, 2, 4, 8) its colours launch with
+ *   32 form 4: blocks of the local-window image that keep global 32-bit columns
  * Returns 0, or non-zero for a bad level or n_out < 1. */
-#define AMGX_LEVEL_PATHS_N 19
+#define AMGX_LEVEL_PATHS_N 33
 int amgx_level_paths(amgx_handle h, int level, int64_t* out, int n_out);
 
 /* measurement hook for bench.py: launches one hot-path kernel `reps` times on the handle's stream,

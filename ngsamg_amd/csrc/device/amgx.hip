@@ -188,6 +188,7 @@ struct DevGSB {                         // block-hybrid Gauss-Seidel (gsb_sweep_
   DevMatrix::Sell fullLW;
   DevBuf<int32_t> flw_cptr, flw_ccol;
   bool has_fullLW = false;
+  int64_t flw_no_window = 0;            // blocks of `fullLW` that keep global 32-bit columns (list over GSB_LW_CAP)
   int full_maxw = 0;                    // widest slice of `full`: <= 11 selects the mid-width general sweep (fewer registers: two 1024-lane
                                         //   workgroups per CU instead of one, so that one block's colour phases hide behind another's loads)
   DevMatrix::Sell full, lowin;          // block-local SELL-G copies (slots colour-sorted inside a block): all entries /
@@ -199,6 +200,21 @@ struct DevGSB {                         // block-hybrid Gauss-Seidel (gsb_sweep_
   bool has_split = false;
   bool on() const { return B > 0; }
 };
+
+// launch-time choices of the block-hybrid sweep (gsb_sweep) and of the multicolour row-list kernel (gs_sweep); amgx_level_paths
+// reports them through the same functions
+// the sweep from zero over `lowin` takes the narrow kernel (2 entries per lane and pass)
+static bool gsb_narrow(const DevGSB& g) { return g.lowin_maxw > 0 && g.lowin_maxw <= 5 && !std::getenv("AMGX_GSB_NO_NARROW"); }
+// the general sweep over `full` takes the mid-width kernel (5 entries per lane and pass)
+static bool gsb_mid(const DevGSB& g) { return g.G > 1 && g.full_maxw > 0 && g.full_maxw <= 11 && !std::getenv("AMGX_GSB_NO_MID"); }
+// ... and reads its local-window image
+static bool gsb_lw(const DevGSB& g) { return g.has_fullLW && g.G > 1; }
+// lanes per block row W of bgs_color_kernel for a colour of `rows` rows on a level with `avg` blocks per row
+static int bgs_rowlist_w(double avg, int64_t rows) {
+  int W = avg >= 48.0 ? 4 : (avg >= 20.0 ? 2 : 1);
+  if (avg >= 32.0 && rows <= 4096) W = 8;      // short colours of long rows: latency, not bandwidth -- spread the row further
+  return W;
+}
 
 struct DevBGSB {                        // block-hybrid Gauss-Seidel on square-block levels (bgsb_sweep_kernel)
   int BB = 0;                           // block rows per workgroup
@@ -1496,8 +1512,7 @@ struct Handle {
         const int r0 = g.color_row_ptr[c], r1 = g.color_row_ptr[c + 1];
         if (r1 == r0) continue;
         const double avg = L.A.n_rows ? (double)L.A.nnz / (double)L.A.n_rows : 0.0;
-        int W = avg >= 48.0 ? 4 : (avg >= 20.0 ? 2 : 1);
-        if (avg >= 32.0 && r1 - r0 <= 4096) W = 8;      // short colours of long rows: latency, not bandwidth -- spread the row further
+        const int W = bgs_rowlist_w(avg, r1 - r0);
         const int rpw = WAVE / (L.bs * W);
         const int64_t waves = ((int64_t)(r1 - r0) + rpw - 1) / rpw;
         const int grid = (int)std::max<int64_t>(1, (waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
@@ -1527,12 +1542,12 @@ struct Handle {
     if (blk1 <= blk0) return;
     if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
     const bool fz = xin == nullptr;
-    const bool lw = !fz && &copy == &g.full && g.has_fullLW && g.G > 1;
+    const bool lw = !fz && &copy == &g.full && gsb_lw(g);
     GsbArgs a{g.rowid.p, g.slotcolor.p, L.dinv.p, b, g.n_colors, dir, lw ? g.flw_cptr.p : nullptr, lw ? g.flw_ccol.p : nullptr};
     const SellMat M = lw ? g.fullLW.view() : copy.view();
-    const bool narrow = fz && &copy == &g.lowin && g.lowin_maxw > 0 && g.lowin_maxw <= 5 && !std::getenv("AMGX_GSB_NO_NARROW");
+    const bool narrow = fz && &copy == &g.lowin && gsb_narrow(g);
 #define LAUNCH_GSB3(TT, GG, ZZ, WW) hipLaunchKernelGGL((gsb_sweep_kernel<TT, GG, ZZ, WW>), dim3(blk1 - blk0), dim3(TT), 0, stream, L.n, blk0, M, a, xin, xout)
-    const bool mid = !fz && &copy == &g.full && g.G > 1 && g.full_maxw > 0 && g.full_maxw <= 11 && !std::getenv("AMGX_GSB_NO_MID");
+    const bool mid = !fz && &copy == &g.full && gsb_mid(g);
 #define LAUNCH_GSBL(TT, GG, WW) hipLaunchKernelGGL((gsb_sweep_kernel<TT, GG, false, WW, true>), dim3(blk1 - blk0), dim3(TT), 0, stream, L.n, blk0, M, a, xin, xout)
 #define LAUNCH_GSB2(TT, GG) { if (narrow) LAUNCH_GSB3(TT, GG, true, 2); else if (fz) LAUNCH_GSB3(TT, GG, true, GSB_WP); \
                               else if (lw && mid && GG > 1) LAUNCH_GSBL(TT, (GG > 1 ? GG : 2), 5); else if (lw && GG > 1) LAUNCH_GSBL(TT, (GG > 1 ? GG : 2), GSB_WP); \
@@ -2359,6 +2374,7 @@ static bool build_gsb_full_lw(const amgx_matrix& A, const std::vector<int32_t>& 
   g.flw_cptr.upload(cnt);
   g.flw_ccol.upload(ccol);
   g.has_fullLW = true;
+  g.flw_no_window = overs;
   return true;
 }
 
@@ -4228,6 +4244,34 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
       for (size_t c = 0; c + 1 < cp.size(); ++c) v[16] += cp[c + 1] == cp[c];
     }
     v[17] = h.folded(L) ? 1 : 0;
+    // Gauss-Seidel sweep: the branch order of base_smooth / gs_sweep
+    const amgx::DevGS& gs = L.gs;
+    const amgx::DevGSB& gsb = L.gsb;
+    const amgx::DevBGSB& bgsb = L.bgsb;
+    if (L.sm_type == AMGX_SM_BGS) {
+      v[19] = 7; v[23] = L.bgs.n_colors;
+    } else if (L.sm_type == AMGX_SM_GS && bgsb.on()) {
+      v[19] = bgsb.bc ? 6 : 5; v[21] = amgx::BLOCK; v[22] = bgsb.BB; v[23] = bgsb.n_colors; v[24] = bgsb.n_bcolors; v[25] = bgsb.has_split;
+    } else if (L.sm_type == AMGX_SM_GS && gsb.on()) {
+      v[19] = 4; v[20] = gsb.G; v[21] = gsb.TH; v[22] = gsb.B; v[23] = gsb.n_colors; v[25] = gsb.has_split;
+      v[26] = gsb.lowin_maxw; v[27] = gsb.full_maxw;
+      v[28] = gsb.has_split && amgx::gsb_narrow(gsb);
+      v[29] = amgx::gsb_mid(gsb);
+      v[30] = amgx::gsb_lw(gsb);
+      v[32] = gsb.has_fullLW ? gsb.flw_no_window : 0;
+    } else if (L.sm_type == AMGX_SM_GS && gs.n_colors > 0) {
+      v[23] = gs.n_colors; v[21] = amgx::BLOCK;
+      if (L.bs == 1) { v[19] = 1; v[20] = gs.lanes; v[25] = gs.has_split; }
+      else if (gs.bsell_ok) { v[19] = 3; v[25] = gs.bsplit; }
+      else {
+        v[19] = 2;
+        const double avg = L.A.n_rows ? (double)L.A.nnz / (double)L.A.n_rows : 0.0;
+        for (int c = 0; c < gs.n_colors; ++c) {
+          const int64_t rows = gs.color_row_ptr[c + 1] - gs.color_row_ptr[c];
+          if (rows > 0) v[31] |= amgx::bgs_rowlist_w(avg, rows);
+        }
+      }
+    }
     for (int k = 0; k < std::min(n_out, AMGX_LEVEL_PATHS_N); ++k) out[k] = v[k];
   });
 }

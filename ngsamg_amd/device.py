@@ -426,17 +426,27 @@ class DeviceAMGMatrix:
                 "stream_bytes": nb.value}
 
     _PATH_KEYS = ("kernel", "fused_block", "lanes", "ept", "compact", "max_slots", "max_entries", "dia_k", "xcd_A", "xcd_Apre",
-                  "xcd_Q", "xcd_dia", "A_slices16", "A_slices", "Apre_slices16", "Apre_slices", "lw_no_window", "folded", "chunks")
+                  "xcd_Q", "xcd_dia", "A_slices16", "A_slices", "Apre_slices16", "Apre_slices", "lw_no_window", "folded", "chunks",
+                  "gs_form", "gs_lanes", "gs_threads", "gs_block", "gs_colors", "gs_block_colors", "gs_split", "gs_lowin_maxw",
+                  "gs_full_maxw", "gs_narrow", "gs_mid", "gs_lw", "gs_w_mask", "gs_lw_no_window")
+    _GS_FORMS = {0: None, 1: "mc", 2: "mc-block-rowlist", 3: "mc-block-bsell", 4: "hybrid", 5: "hybrid-block", 6: "block-coloured",
+                 7: "bgs"}
 
     def level_paths(self, level):
         """the paths amgx_create chose for one level (amgx_level_paths, read-only): the fused Jacobi down kernel (None, "sell",
         "sell-win", "sell-lw" or "dia"), its workgroup size and lanes per row, the chunk-local restriction (entries of P per thread,
         compact chunks, most slots / entries in one chunk, number of chunks), the diagonals of the DIA image, the XCD placement
-        flags, the 16-bit / all slices of A and A', the local-window chunks without a window and whether the level is folded"""
+        flags, the 16-bit / all slices of A and A', the local-window chunks without a window and whether the level is folded;
+        the Gauss-Seidel sweep ("gs_form": None, "mc", "mc-block-rowlist", "mc-block-bsell", "hybrid", "hybrid-block",
+        "block-coloured" or "bgs"), its lanes per row, workgroup size, rows per block, colours, block colours, split images, the
+        widest slices of the block-hybrid images, the block-hybrid kernel choices (narrow sweep from zero, mid-width and
+        local-window general sweep, blocks of the local-window image without a window) and the row-list kernel's lanes per block
+        row (bitmask of W)"""
         out = np.zeros(len(self._PATH_KEYS), dtype=np.int64)
         self._ck(self._lib.amgx_level_paths(self._h, int(level), out.ctypes.data_as(_lib.c_i64p), out.size))
         d = dict(zip(self._PATH_KEYS, (int(v) for v in out)))
         d["kernel"] = {0: None, 1: "sell", 2: "sell-win", 3: "sell-lw", 4: "dia"}[d["kernel"]]
+        d["gs_form"] = self._GS_FORMS[d["gs_form"]]
         return d
 
     def time_op(self, level, op, reps=20):

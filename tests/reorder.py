@@ -8,6 +8,7 @@ result is exactly the permuted one; only summation orders of the kernels change.
 permutation(kind, n, seed) makes the orderings the device formats react to, stencil(...) symmetric M-matrices on chosen
 diagonals (the DIA image with K = 1 .. 7 upper diagonals), hand_hierarchy(...) a hierarchy around such a matrix with
 prolongation of chosen width."""
+import functools
 from types import SimpleNamespace
 
 import numpy as np
@@ -233,3 +234,147 @@ def hand_hierarchy(A, per_row=(2,), agg=8, seed=0, first_P=()):
                                       free=np.ones(nn, dtype=np.uint8), dinv=plain_dinv(M), color=np.zeros(nn, dtype=np.int32), n_colors=1,
                                       coords=None, agg=None, n=nn, bs=1, bgs=None))
     return FixtureHierarchy(levels)
+
+
+# ---- Gauss-Seidel levels with chosen row lengths (tests/test_gpu_gs_paths.py) -------------------------------------------
+
+GS_LENGTHS = [17, 18, 22, 23, 32, 33, 44, 45, 64, 65, 88, 89, 128, 129, 176, 177, 256]
+GS_ORDERS = ["identity", "random", "slice64"]
+
+
+def long_row_matrix(L, n=6037, seed=0, shift=0.05):
+    """SPD M-matrix on a 1D index space whose longest row has exactly L >= 3 entries: couplings i -- i + o for o = 1 .. L // 2
+    with random weights (as stencil("offsets:...")).  For even L the pairs (i, i + o) with even i and o the largest odd offset are
+    dropped (every row lies in one such pair) and their weights stay on both diagonals.  Returns scipy CSR."""
+    rng = np.random.default_rng(seed)
+    m = L // 2
+    offs = np.arange(1, m + 1)
+    I = np.concatenate([np.arange(n - o) for o in offs])
+    J = I + np.repeat(offs, n - offs)
+    w = rng.uniform(0.5, 1.5, size=I.size)
+    extra = np.zeros(n)
+    if L % 2 == 0:
+        o = m if m % 2 else m - 1
+        drop = (J - I == o) & (I % 2 == 0)
+        extra = np.bincount(I[drop], weights=w[drop], minlength=n) + np.bincount(J[drop], weights=w[drop], minlength=n)
+        I, J, w = I[~drop], J[~drop], w[~drop]
+    return _assemble(n, I, J, w, shift + extra)
+
+
+def reorder_matrix(A, kind, seed=0):
+    """Pi A Pi^T for permutation(kind) (scipy CSR, columns sorted); returns (A', p)"""
+    p = permutation(kind, A.shape[0], seed, A)
+    Ap = sp.csr_matrix(A)[p][:, p].tocsr()
+    Ap.sort_indices()
+    return Ap, p
+
+
+def coloring(M, free=None):
+    """a colouring of the (block) graph of M by the host library (amgh_coloring): coupled rows differ, -1 on non-free rows"""
+    import ctypes as C
+    from ngsamg_amd import _lib
+    lib = _lib.host()
+    d = M.desc()
+    fr = np.ascontiguousarray(np.ones(M.n_rows, np.uint8) if free is None else free, dtype=np.uint8)
+    color = np.full(M.n_rows, -1, dtype=np.int32)
+    nc = C.c_int32()
+    _lib.hcheck(lib.amgh_coloring(C.byref(d), _lib.ptr(fr, C.c_uint8), _lib.ptr(color, C.c_int32), C.byref(nc)))
+    return color, int(nc.value)
+
+
+def _block_inv_diag(A, bs, l1=False):
+    """inverse of the diagonal (blocks) of a scipy matrix with bs x bs blocks; l1: of the l1-modified diagonal (adds the row sums
+    of |a_ij| outside the diagonal block to its diagonal) -- not the plain inverse"""
+    n = A.shape[0] // bs
+    B = sp.bsr_matrix(A, blocksize=(bs, bs))
+    B.sort_indices()
+    r = np.repeat(np.arange(n), np.diff(B.indptr))
+    D = np.zeros((n, bs, bs))
+    on = B.indices == r
+    D[r[on]] = B.data[on]
+    if l1:
+        off = np.asarray(abs(A).sum(axis=1)).reshape(n, bs) - np.abs(D).sum(axis=2)
+        D = D + off[:, :, None] * np.eye(bs)[None]
+    return np.ascontiguousarray(np.linalg.inv(D).reshape(-1))
+
+
+def gs_hierarchy(A, free=None, bs=1, l1_dinv=False, agg=8, per_row=2, seed=0):
+    """two levels around the SPD matrix A (scipy, bs x bs blocks) for the Gauss-Seidel tests: P_0 = (prolongation with per_row
+    entries per row, _prolongation) x I_bs with empty rows on the non-free block rows, A_1 = P^T A P + 0.05 I (a whole non-free
+    block leaves aggregates without fine rows); a valid colouring of both levels (coloring, -1 on the non-free rows); dinv the
+    plain inverse diagonal (blocks), or with l1_dinv the l1-modified one on level 0.  A golden_io.FixtureHierarchy."""
+    rng = np.random.default_rng(seed)
+    n = A.shape[0] // bs
+    free = np.ones(n, np.uint8) if free is None else np.ascontiguousarray(free, dtype=np.uint8)
+    P = sp.diags(free.astype(np.float64)) @ _prolongation(n, per_row, agg, rng)
+    P = sp.csr_matrix(sp.kron(P, sp.identity(bs)))
+    P.eliminate_zeros()
+    P.sort_indices()
+    Ac = (P.T @ A @ P).tocsr()
+    Ac = (((Ac + Ac.T) * 0.5) + 0.05 * sp.identity(Ac.shape[0])).tocsr()
+    Ac.sort_indices()
+    levels = []
+    for l, (M, fr) in enumerate(((sp.csr_matrix(A), free), (Ac, np.ones(Ac.shape[0] // bs, np.uint8)))):
+        m = Matrix.from_scipy(M, bs) if bs > 1 else Matrix.from_scipy(M)
+        Pl = PT = None
+        if l == 0:
+            Pl = Matrix.from_scipy(P, bs) if bs > 1 else Matrix.from_scipy(P)
+            PT = Matrix.from_scipy(P.T.tocsr(), bs) if bs > 1 else Matrix.from_scipy(P.T.tocsr())
+        color, nc = coloring(m, fr)
+        dinv = _block_inv_diag(M, bs, l1_dinv and l == 0) if bs > 1 else \
+            (1.0 / np.asarray(abs(M).sum(axis=1)).reshape(-1) if l1_dinv and l == 0 else plain_dinv(M))
+        levels.append(SimpleNamespace(A=m, P=Pl, PT=PT, free=np.ascontiguousarray(fr), dinv=np.ascontiguousarray(dinv), color=color,
+                                      n_colors=nc, coords=None, agg=None, n=m.n_rows, bs=bs, bgs=None))
+    return FixtureHierarchy(levels)
+
+
+def nonfree_mask(n, B, seed=0, scattered=40, block=3):
+    """free flags with `scattered` random non-free rows and the whole block [block * B, (block + 1) * B) non-free"""
+    rng = np.random.default_rng(seed)
+    free = np.ones(n, np.uint8)
+    free[rng.choice(n, size=min(scattered, n), replace=False)] = 0
+    free[block * B:min(n, (block + 1) * B)] = 0
+    return free
+
+
+def block_long_row_matrix(bs, L, n, seed=0, odd_only=False):
+    """square-block SPD matrix (scipy CSR, bs x bs blocks) on the block graph of long_row_matrix(L, n) (odd_only, L odd: only the
+    odd offsets 1, 3, .., L - 2 -- a bipartite graph with two colours; the longest block row still has L blocks): a random non-symmetric block E per
+    edge (i, j), i < j, with A_ij = -E and A_ji = -E^T, and diagonal blocks A_ii = S_i + (row sums of |a| outside + 1) I with
+    S_i random symmetric without diagonal, so that A is symmetric and strictly diagonally dominant."""
+    rng = np.random.default_rng(seed)
+    if odd_only:
+        offs = np.arange(1, L - 1, 2)
+        I = np.concatenate([np.arange(n - o) for o in offs])
+        J = I + np.repeat(offs, n - offs)
+    else:
+        S = sp.triu(long_row_matrix(L, n, seed), k=1).tocoo()
+        I, J = S.row.astype(np.int64), S.col.astype(np.int64)
+    E = rng.uniform(-1.0, 1.0, size=(I.size, bs, bs))
+    Sd = rng.uniform(-0.3, 0.3, size=(n, bs, bs))
+    Sd = np.triu(Sd, 1)
+    Sd = Sd + Sd.transpose(0, 2, 1)
+    rowabs = np.zeros((n, bs))
+    np.add.at(rowabs, I, np.abs(E).sum(axis=2))
+    np.add.at(rowabs, J, np.abs(E).sum(axis=1))
+    rowabs += np.abs(Sd).sum(axis=2)
+    D = Sd + (rowabs + 1.0)[:, :, None] * np.eye(bs)[None]
+    rows = np.concatenate([I, J, np.arange(n)])
+    cols = np.concatenate([J, I, np.arange(n)])
+    blocks = np.concatenate([-E, -E.transpose(0, 2, 1), D])
+    order = np.lexsort((cols, rows))
+    rows, cols, blocks = rows[order], cols[order], blocks[order]
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))])
+    return sp.bsr_matrix((blocks, cols, indptr), shape=(n * bs, n * bs)).tocsr()
+
+
+@functools.lru_cache(maxsize=None)
+def gs_scalar_case(L, kind, nonfree=False, n=6037):
+    """(A, B, free, hierarchy) of one scalar Gauss-Seidel input: long_row_matrix(L, n) under the ordering `kind`, B the rows per
+    block gs_block_rows picks (0: multicolour), gs_hierarchy around it; nonfree: nonfree_mask (40 scattered non-free rows and
+    the whole 4th block of B rows).  Cached: the tests only read it."""
+    from ngsamg_amd.device import gs_block_rows
+    A, _ = reorder_matrix(long_row_matrix(L, n, seed=L), kind, seed=3)
+    B = gs_block_rows(Matrix.from_scipy(A))
+    free = nonfree_mask(n, B or 64, seed=L) if nonfree else np.ones(n, np.uint8)
+    return A, B, free, gs_hierarchy(A, free, seed=L)

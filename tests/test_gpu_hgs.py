@@ -71,6 +71,8 @@ def test_hgs_variants(threads, split, monkeypatch):
     p, H = _case((26, 24, 22))
     dev = DeviceAMGMatrix(H, sm_type="hgs", device=0)
     assert dev.hgs[0]["B"] == int(threads)
+    lp = dev.level_paths(0)
+    assert lp["gs_form"] == "hybrid" and lp["gs_lanes"] == 1 and lp["gs_threads"] == int(threads) and lp["gs_split"] == int(split)
     lv, types = hgs_levels(H.levels, dev.hgs)
     rng = np.random.default_rng(1)
     b = rng.standard_normal(p.n) * p.free
@@ -134,6 +136,9 @@ def test_block_gs_on_colour_major_bsell(rot, cycle, split, monkeypatch):
         monkeypatch.setenv("AMGX_NO_BGS_SPLIT", "1")
     p, H = elasticity_case((9, 8, 7), rot, 10)
     dev = DeviceAMGMatrix(H, sm_type="gs", mg_cycle=cycle, device=0)
+    assert dev.level_paths(0)["gs_form"] == "mc-block-bsell"
+    if not split:
+        assert dev.level_paths(0)["gs_split"] == 0
     rng = np.random.default_rng(3)
     b = rng.standard_normal(p.n * p.bs) * np.repeat(p.free, p.bs)
     for rep in range(2):
@@ -185,6 +190,8 @@ def test_block_levels_hgs_cycles_match_hybrid_oracle(rot, shape, cycle, split, m
     p, H = elasticity_case(shape, rotations=rot, max_coarse_size=10)
     dev = DeviceAMGMatrix(H, sm_type="hgs", mg_cycle=cycle, device=0)
     assert dev.hgs[0] is not None and dev.hgs[0]["B"] % (64 // H.levels[0].bs) == 0, "level 0 did not take the block-hybrid path"
+    lp = dev.level_paths(0)
+    assert lp["gs_form"] == "hybrid-block" and lp["gs_block"] == dev.hgs[0]["B"] and (split or lp["gs_split"] == 0)
     lv, types = hgs_levels(H.levels, dev.hgs)
     rng = np.random.default_rng(0)
     b = rng.standard_normal(p.n * p.bs) * np.repeat(p.free, p.bs)
@@ -210,6 +217,9 @@ def test_block_levels_block_coloured_gs_matches_ordered_oracle(rot, shape, cycle
     p, H = elasticity_case(shape, rotations=rot, max_coarse_size=10)
     dev = DeviceAMGMatrix(H, sm_type="hgs", mg_cycle=cycle, device=0)
     assert dev.hgs[0] is not None and dev.hgs[0]["block_color"] is not None and dev.hgs[0]["n_block_colors"] >= 2
+    lp = dev.level_paths(0)
+    assert lp["gs_form"] == "block-coloured" and lp["gs_block"] == dev.hgs[0]["B"] and lp["gs_block_colors"] == dev.hgs[0]["n_block_colors"]
+    assert split or lp["gs_split"] == 0
     lv, types = hgs_levels(H.levels, dev.hgs)
     assert lv[0].gs_block is None
     rng = np.random.default_rng(0)
