@@ -50,10 +50,12 @@ enum {
   AMGX_HOST_PTR = 0,          /* vectors are host arrays: copied H2D / D2H inside the call            */
   AMGX_DEVICE_PTR = 1,        /* vectors are device arrays on the handle's GPU (no copies)            */
   AMGX_NO_GRAPH = 2,          /* launch the kernels directly instead of replaying the captured graph  */
-  AMGX_PCG_SINGLE_REDUCTION = 16  /* amgx_pcg / amgx_dist_pcg with a preconditioner: the Chronopoulos / Gear form of the   */
+  AMGX_PCG_SINGLE_REDUCTION = 16, /* amgx_pcg / amgx_dist_pcg with a preconditioner: the Chronopoulos / Gear form of the   */
                               /* same recurrence -- ONE reduction point (one all-reduce of two scalars) per iteration and  */
                               /* three launches beside the cycle and the level-0 product instead of five; histories agree   */
                               /* with the classical form to ~1e-6                                                            */
+  AMGX_MULTI_INTERLEAVED = 32 /* multi-vector calls: entry (row i, column j) of a multi-vector lives at i*k + j and ld is      */
+                              /* ignored.  Without it: column-major, column j starts at j*ld, ld >= level size                */
 };
 
 typedef struct amgx_level_desc {
@@ -289,6 +291,33 @@ int amgx_gss4_mult_add(amgx_gss4 g, double s, const double* b, double* x, int fl
 int amgx_pcg(amgx_handle h, const double* b, double* x, double tol, int maxit, int use_precond, int flags, double* errs, int32_t* iters);
 int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit, int restart, int use_precond, int flags, double* errs,
                int32_t* iters);
+
+/* ---- multi-vectors: k right-hand sides per matrix pass -------------------------------------------------------------------
+ * Reference interface: BaseMatrix::Mult / MultAdd on an NGSolve MultiVector (the block of vectors of LOBPCG / PINVIT, several
+ * load cases for one operator); the reference applies AMGMatrix::Mult (amg_matrix.cpp:377-378) once per vector.  1 <= k <=
+ * AMGX_MULTI_MAX; layout by AMGX_MULTI_INTERLEAVED, host / device pointers and AMGX_NO_GRAPH as in amgx_apply.
+ *   amgx_apply_multi : column j of X = C (column j of B), the operator of amgx_apply; k = 1 IS amgx_apply
+ *   amgx_matvec_multi: column j of Y = A_level (column j of X)   (GetMatrix(level).Mult per vector)
+ *   amgx_pcg_multi   : k INDEPENDENT recurrences of amgx_pcg (not block CG) that share the level-0 product and the
+ *                      preconditioner application; per column err_k = sqrt(|<C r_k, r_k>|), stop at err_k <= tol * err_0.  A column
+ *                      that has met its criterion (or has err_0 == 0) is frozen: its x is not touched again, iters[j] is the
+ *                      iteration at which it stopped; the call returns when every column is frozen or at maxit.  errs (optional,
+ *                      k rows of maxit + 1 entries): row j holds err_0 .. err_iters[j] of column j.  iters: [k], required.  The
+ *                      host reads k scalars per iteration in one copy.  (AMGX_PCG_SINGLE_REDUCTION is ignored: classical form.)
+ * A handle whose smoothed levels are all scalar (1x1), plain Jacobi (sm_steps = 1, no sm_symm), square, and whose cycle is V runs
+ * FUSED: the literal cycle (x = w Dinv b, r = b - A x, b_c = P^T r, ..., t = x + P x_c, x = t + w Dinv (b - A t)) on A, P, P^T with
+ * every matrix entry read once for 2 or 4 interleaved vectors; any other k is cut greedily into groups of those widths (8 = 4 + 4:
+ * a width-8 kernel measured slower per column) plus at most one single column, which takes the single-vector path.  Every other handle (Gauss-Seidel in any form, block levels, W / BS
+ * cycles, ProxySmoother) answers the same calls through a column loop over the single-vector path -- all or nothing per handle.
+ *   amgx_multi_info  : fused = 1 / 0 as above; the groups a call with k columns runs as (group_width: AMGX_MULTI_MAX entries,
+ *                      0 beyond n_groups; all 1 when fused = 0); work_bytes = device memory of the multi-vector work space such a
+ *                      call allocates (kept until amgx_destroy).  Any of the output pointers may be NULL. */
+#define AMGX_MULTI_MAX 8
+int amgx_apply_multi(amgx_handle h, int k, const double* B, int64_t ldb, double* X, int64_t ldx, int b_status, int flags);
+int amgx_matvec_multi(amgx_handle h, int level, int k, const double* X, int64_t ldx, double* Y, int64_t ldy, int flags);
+int amgx_pcg_multi(amgx_handle h, int k, const double* B, int64_t ldb, double* X, int64_t ldx, double tol, int maxit, int use_precond, int flags,
+                   double* errs, int32_t* iters);
+int amgx_multi_info(amgx_handle h, int k, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Rank-partitioned hierarchies (one process per GPU; SURVEY.md 8b "halo tables + RCCL communicator", 8e).

@@ -231,6 +231,10 @@ class AMGMatrix:
     def Mult(self, b, x):
         return self._dev.Mult(b, x)
 
+    def MultMulti(self, B, X, interleaved=False):
+        """BaseMatrix::Mult on a MultiVector: X[j] = C B[j], k right-hand sides per matrix pass (DeviceAMGMatrix.MultMulti)"""
+        return self._dev.MultMulti(B, X, interleaved=interleaved)
+
     def MultAdd(self, s, b, x):
         return self._dev.MultAdd(s, b, x)
 
@@ -391,6 +395,9 @@ class _AMGPreconditioner:
     # ---- BaseMatrix interface (amg_pc.cpp:443-488) ---------------------------------------------------
     def Mult(self, b, x):
         return self._need().Mult(b, x)
+
+    def MultMulti(self, B, X, interleaved=False):
+        return self._need().MultMulti(B, X, interleaved=interleaved)
 
     def MultAdd(self, s, b, x):
         return self._need().MultAdd(s, b, x)

@@ -26,6 +26,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -1211,6 +1212,9 @@ static bool build_sell_lw_windowed(int64_t n, int64_t n_cols, const int64_t* row
 
 enum { PART_ALL = 0, PART_INT = 1, PART_BND = 2 };
 struct Span { int part = PART_ALL; int64_t n_int = 0; };   // see Handle::spmv_ep
+struct MultiState;                      // multi-vector work space and captured graphs (multi.hpp)
+void multi_drop_graphs(MultiState* s);
+void multi_free(MultiState* s);
 
 struct Handle {
   int device = 0;
@@ -1240,6 +1244,7 @@ struct Handle {
   struct GraphKey { const double* b; double* x; int kind; bool operator<(const GraphKey& o) const { return std::tie(b, x, kind) < std::tie(o.b, o.x, o.kind); } };
   std::map<GraphKey, hipGraphExec_t> graphs;
   std::vector<GraphKey> graph_age;      // capture order
+  MultiState* multi = nullptr;          // created by the first multi-vector call (multi.hpp)
   // staging for host-pointer calls
   DevBuf<double> stage[3];
   DevBuf<double> kr_ws[6];              // work vectors of amgx_pcg / amgx_gmres (krylov.hpp), kept between solves
@@ -1262,6 +1267,7 @@ struct Handle {
   }
 
   ~Handle() {
+    if (multi) multi_free(multi);
     for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
     if (own_stream) (void)hipStreamDestroy(own_stream);
   }
@@ -2159,6 +2165,7 @@ struct Handle {
     for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
     graphs.clear();
     graph_age.clear();
+    if (multi) multi_drop_graphs(multi);
   }
 };
 
@@ -4360,5 +4367,6 @@ int amgx_time_op(amgx_handle hh, int level, int op, int reps, double* avg_ms) {
 }  // extern "C"
 
 #include "krylov.hpp"
+#include "multi.hpp"
 #include "dist.hpp"
 #include "gss4.hpp"

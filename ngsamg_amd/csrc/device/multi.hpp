@@ -1,0 +1,839 @@
+// Multi-vector apply path: k right-hand sides per matrix pass.
+//
+// Reference interface: BaseMatrix::Mult on an NGSolve MultiVector (what LOBPCG / PINVIT and callers with several load cases
+// hand to a preconditioner); the reference runs AMGMatrix::Mult once per vector.  Here a handle whose smoothed levels are all
+// scalar, plain Jacobi levels of a V-cycle runs the LITERAL cycle (x = w Dinv b, r = b - A x, b_c = P^T r, ..., t = x + P x_c,
+// x = t + w Dinv (b - A t): amg_matrix.cpp:183-302) on the level images A, P, P^T with every matrix entry read ONCE for NV = 2 or 4
+// vectors.  Inside the handle multi-vectors are interleaved, entry (row i, column j) at i*NV + j: a gathered column index
+// then costs one address and 8*NV contiguous bytes.  Every other handle answers the same calls through a column loop over the
+// single-vector path.
+//
+// The kernels keep the order of additions of their single-vector counterparts per column (pair accumulators, odd trailing
+// column last, shuffle reduction), and no operation mixes two columns: a column's result does not depend on its neighbours.
+#pragma once
+
+namespace amgx {
+
+constexpr int MULTI_MAX = AMGX_MULTI_MAX;
+
+// NV consecutive doubles at p (16-byte aligned for even NV: interleaved vectors start at 16-byte aligned addresses)
+template <int NV>
+__device__ __forceinline__ void ldv(const double* __restrict__ p, double (&v)[NV]) {
+  if constexpr (NV % 2 == 0) {
+    const double2* __restrict__ q = reinterpret_cast<const double2*>(p);
+#pragma unroll
+    for (int j = 0; j < NV / 2; ++j) { const double2 t = q[j]; v[2 * j] = t.x; v[2 * j + 1] = t.y; }
+  } else {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = p[j];
+  }
+}
+template <int NV>
+__device__ __forceinline__ void stv(double* __restrict__ p, const double (&v)[NV]) {
+  if constexpr (NV % 2 == 0) {
+    double2* __restrict__ q = reinterpret_cast<double2*>(p);
+#pragma unroll
+    for (int j = 0; j < NV / 2; ++j) q[j] = make_double2(v[2 * j], v[2 * j + 1]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) p[j] = v[j];
+  }
+}
+
+// epilogue of one row for NV columns; dinv and omega are per row, shared by the columns (arithmetic of store_scalar)
+template <int NV, int EP>
+__device__ __forceinline__ void store_multi(int64_t row, const double (&acc)[NV], double* y, const EpArgs& ep) {
+  double out[NV];
+  if constexpr (EP == EP_MULT) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) out[j] = acc[j];
+  } else if constexpr (EP == EP_RES) {
+    double b[NV];
+    ldv<NV>(ep.b + row * NV, b);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) out[j] = b[j] - acc[j];
+  } else if constexpr (EP == EP_AXPY) {
+    double yin[NV];
+    ldv<NV>(ep.yin + row * NV, yin);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) out[j] = yin[j] + ep.s * acc[j];
+  } else {
+    static_assert(EP == EP_JAC, "multi-vector epilogues: MULT, RES, AXPY, JAC");
+    double b[NV], yin[NV];
+    ldv<NV>(ep.b + row * NV, b);
+    ldv<NV>(ep.yin + row * NV, yin);
+    const double d = ep.dinv[row];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) out[j] = yin[j] + ep.s * (d * (b[j] - acc[j]));
+  }
+  stv<NV>(y + row * NV, out);
+}
+
+// ---- SELL row product for NV interleaved vectors: the batch pipeline of sell_pairs with the gather widened to NV values ----
+template <int K, bool C16, int NV>
+__device__ __forceinline__ void sell_consume_nv(const SellRegs<K>& R, const int32_t* __restrict__ cb, int r0, int p,
+                                                const double* __restrict__ x, double (&acc0)[NV], double (&acc1)[NV]) {
+  double x0[K][NV], x1[K][NV];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int q = p + k;
+    const int c0 = C16 ? r0 + cb[2 * q] + (int)(R.ca[k] & 0xffffu) : (int)R.ca[k];
+    const int c1 = C16 ? r0 + cb[2 * q + 1] + (int)(R.ca[k] >> 16) : (int)R.cb2[k];
+    ldv<NV>(x + (int64_t)c0 * NV, x0[k]);
+    ldv<NV>(x + (int64_t)c1 * NV, x1[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) { acc0[j] += R.v0[k] * x0[k][j]; acc1[j] += R.v1[k] * x1[k][j]; }
+  }
+}
+
+template <int K, int REM, bool C16, int NV>
+__device__ __forceinline__ void sell_tail_nv(int rem, const SellRegs<K>* last, int p_last, const double* __restrict__ vb,
+                                             const void* __restrict__ cpv, const int32_t* __restrict__ cb, int r0, int p, int lane,
+                                             const double* __restrict__ x, double (&acc0)[NV], double (&acc1)[NV]) {
+  if (rem == REM) {
+    SellRegs<REM> R;
+    sell_load<REM, C16>(R, vb, cpv, p, lane);
+    if (last) sell_consume_nv<K, C16, NV>(*last, cb, r0, p_last, x, acc0, acc1);
+    sell_consume_nv<REM, C16, NV>(R, cb, r0, p, x, acc0, acc1);
+  } else if constexpr (REM > 1) sell_tail_nv<K, REM - 1, C16, NV>(rem, last, p_last, vb, cpv, cb, r0, p, lane, x, acc0, acc1);
+}
+
+template <bool C16, int NV, int K = SELL_BATCH>
+__device__ __forceinline__ void sell_pairs_nv(int np, const double* __restrict__ vb, const void* __restrict__ cpv, const int32_t* __restrict__ cb,
+                                              int r0, int lane, const double* __restrict__ x, double (&acc0)[NV], double (&acc1)[NV]) {
+  const int nfull = np / K, rem = np - nfull * K;
+  if (nfull > 0) {
+    SellRegs<K> A;
+    sell_load<K, C16>(A, vb, cpv, 0, lane);
+    for (int b = 1; b < nfull; ++b) {
+      SellRegs<K> B;
+      sell_load<K, C16>(B, vb, cpv, b * K, lane);
+      sell_consume_nv<K, C16, NV>(A, cb, r0, (b - 1) * K, x, acc0, acc1);
+      A = B;
+    }
+    if (K > 1 && rem) sell_tail_nv<K, (K > 1 ? K - 1 : 1), C16, NV>(rem, &A, (nfull - 1) * K, vb, cpv, cb, r0, nfull * K, lane, x, acc0, acc1);
+    else sell_consume_nv<K, C16, NV>(A, cb, r0, (nfull - 1) * K, x, acc0, acc1);
+  } else if (K > 1 && rem) sell_tail_nv<K, (K > 1 ? K - 1 : 1), C16, NV>(rem, nullptr, 0, vb, cpv, cb, r0, 0, lane, x, acc0, acc1);
+}
+
+// acc[j] = (SELL row of slice s, this lane) . column j of x          (sell_row_dot_sp for NV vectors)
+template <int NV>
+__device__ __forceinline__ void sell_row_dot_nv(const SellMat& M, int s, int lane, int row, const double* __restrict__ x, double (&acc)[NV]) {
+  const int64_t sp0 = M.slice_ptr[s], sp1 = M.slice_ptr[s + 1];
+  const int64_t base = sp0 & ~(int64_t)63;
+  const int w = (int)(((sp1 & ~(int64_t)63) - base) >> 6);
+  const int np = w >> 1;
+  const double* __restrict__ vb = M.val + base;
+  double acc0[NV], acc1[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) { acc0[j] = 0.0; acc1[j] = 0.0; }
+  const bool c16 = sp0 & 1;
+  const int32_t* __restrict__ cb = M.cbase + (base >> 6);
+  const int r0 = (c16 && M.rowrel) ? row : 0;
+  double vs = 0.0;
+  int cs = 0;
+  if (w & 1) {                                  // odd trailing column: its matrix loads go out first, its gather comes last
+    const int64_t o = (int64_t)(w - 1) * WAVE + lane;
+    vs = ld_nt(vb + o);
+    cs = c16 ? (int)ld_nt(M.col16 + base + o) : ld_nt(M.col32 + base + o);
+  }
+  if (c16) sell_pairs_nv<true, NV>(np, vb, M.col16 + base, cb, r0, lane, x, acc0, acc1);
+  else sell_pairs_nv<false, NV>(np, vb, M.col32 + base, nullptr, 0, lane, x, acc0, acc1);
+  if (w & 1) {
+    const int c = c16 ? r0 + cb[w - 1] + cs : cs;
+    double xs[NV];
+    ldv<NV>(x + (int64_t)c * NV, xs);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc0[j] += vs * xs[j];
+  }
+#pragma unroll
+  for (int j = 0; j < NV; ++j) acc[j] = acc0[j] + acc1[j];
+}
+
+// SELL-64-pair, G lanes per row, NV interleaved vectors (sell_spmv_kernel's multi-vector form, same SellMat view)
+template <int G, int NV, int EP>
+__global__ __launch_bounds__(BLOCK) void sell_spmm_kernel(int64_t n_rows, int n_slices, SellMat M, const double* __restrict__ x, double* y, EpArgs ep) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int s = __builtin_amdgcn_readfirstlane(sell_unit(M) * WAVES_PER_BLOCK + (threadIdx.x >> 6));
+  if (s >= n_slices) return;
+  const int row = s * (WAVE / G) + lane / G;
+  double acc[NV];
+  sell_row_dot_nv<NV>(M, s, lane, row, x, acc);
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+#pragma unroll
+    for (int o = G >> 1; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o, G);
+  }
+  if ((lane % G) == 0 && row < n_rows) store_multi<NV, EP>(row, acc, y, ep);
+}
+
+// windowed SELL (sell_win_spmv_kernel's multi-vector form): the NV row sums go through LDS back to natural order
+template <int WB, int NV, int EP>
+__global__ __launch_bounds__(WB) void sell_win_spmm_kernel(int64_t n_rows, SellMat M, const uint16_t* __restrict__ rowloc,
+                                                           const double* __restrict__ x, double* y, EpArgs ep) {
+  __shared__ double buf[WB * NV];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wb = sell_unit(M);
+  const int s = __builtin_amdgcn_readfirstlane(wb * (WB / WAVE) + (threadIdx.x >> 6));
+  const int64_t slot = (int64_t)s * WAVE + lane;
+  const int64_t row = (int64_t)wb * WB + threadIdx.x;
+  if (slot < n_rows) {
+    double acc[NV];
+    sell_row_dot_nv<NV>(M, s, lane, 0, x, acc);
+    const int loc = rowloc[slot];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) buf[loc * NV + j] = acc[j];
+  }
+  __syncthreads();
+  if (row < n_rows) {
+    double acc[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] = buf[threadIdx.x * NV + j];
+    store_multi<NV, EP>(row, acc, y, ep);
+  }
+}
+
+// CSR-vector, G lanes per row, NV interleaved vectors (csrvec_spmv_kernel's multi-vector form)
+template <int G, int NV, int EP>
+__global__ __launch_bounds__(BLOCK) void csrvec_spmm_kernel(int64_t n_rows, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ cols,
+                                                            const double* __restrict__ vals, const double* __restrict__ x, double* y, EpArgs ep) {
+  const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  const int64_t row = t / G;
+  const int sub = (int)(t % G);
+  double acc[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+  if (row < n_rows) {
+    const int e = rowptr[row + 1];
+    for (int k = rowptr[row] + sub; k < e; k += G) {
+      const double v = vals[k];
+      double xv[NV];
+      ldv<NV>(x + (int64_t)cols[k] * NV, xv);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) acc[j] += v * xv[j];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+#pragma unroll
+    for (int o = G >> 1; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o, G);
+  }
+  if (row < n_rows && sub == 0) store_multi<NV, EP>(row, acc, y, ep);
+}
+
+// dense Y = M X for NV interleaved vectors, one wave per row: the coarse inverse and the collapsed dense operator are read once
+template <int NV>
+__global__ __launch_bounds__(BLOCK) void dense_gemm_nv_kernel(int n, int ld, const double* __restrict__ M, const double* __restrict__ x, double* __restrict__ y) {
+  const int row = blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & (WAVE - 1);
+  if (row >= n) return;
+  const double* __restrict__ m = M + (int64_t)row * ld;
+  double acc[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+  int c = lane;
+  for (; c + 3 * WAVE < n; c += 4 * WAVE) {     // four matrix loads and their gathers in flight per lane
+    double mv[4], xv[4][NV];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) mv[q] = m[c + q * WAVE];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) ldv<NV>(x + (int64_t)(c + q * WAVE) * NV, xv[q]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) acc[j] += mv[q] * xv[q][j];
+    }
+  }
+  for (; c < n; c += WAVE) {
+    const double mv = m[c];
+    double xv[NV];
+    ldv<NV>(x + (int64_t)c * NV, xv);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] += mv * xv[j];
+  }
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+#pragma unroll
+    for (int o = WAVE >> 1; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o, WAVE);
+  }
+  if (lane == 0) stv<NV>(y + (int64_t)row * NV, acc);
+}
+
+// ---- element-wise pieces on interleaved vectors (one thread per entry) -------------------------------------------------------
+// x = omega * Dinv * b, width 1 << sh      (diag_apply_kernel<1, false> per column)
+__global__ __launch_bounds__(BLOCK) void multi_diag_kernel(int64_t len, int sh, const double* __restrict__ dinv, const double* __restrict__ b,
+                                                           double* __restrict__ x, double omega) {
+  const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (t < len) x[t] = omega * (dinv[t >> sh] * b[t]);
+}
+// dst[i*w + j] = src[i*rs + (c0 + j)*cs]: columns c0 .. c0+w of a column-major (rs = 1, cs = ld) or interleaved (rs = k, cs = 1)
+// multi-vector into an interleaved one of width w
+__global__ __launch_bounds__(BLOCK) void multi_pack_kernel(int64_t n, int w, const double* __restrict__ src, int64_t rs, int64_t cs, int c0,
+                                                           double* __restrict__ dst) {
+  const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= n * w) return;
+  const int64_t i = t / w;
+  const int j = (int)(t - i * w);
+  dst[t] = src[i * rs + (c0 + j) * cs];
+}
+// and back
+__global__ __launch_bounds__(BLOCK) void multi_unpack_kernel(int64_t n, int w, const double* __restrict__ src, double* __restrict__ dst, int64_t rs,
+                                                             int64_t cs, int c0) {
+  const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= n * w) return;
+  const int64_t i = t / w;
+  const int j = (int)(t - i * w);
+  dst[i * rs + (c0 + j) * cs] = src[t];
+}
+
+// ---- BLAS-1 of the k independent CG recurrences, interleaved vectors, one launch per operation for all columns ---------------
+// partial[j * KR_BLOCKS + block] = this block's grid-stride share of <a_j, b_j>; kr_dot_final_kernel adds them (fixed order)
+__global__ __launch_bounds__(BLOCK) void kr_dot_multi_partial_kernel(int64_t n, int k, const double* __restrict__ a, const double* __restrict__ b,
+                                                                     double* __restrict__ partial) {
+  __shared__ double red[MULTI_MAX][BLOCK / WAVE];
+  double acc[MULTI_MAX];
+#pragma unroll
+  for (int j = 0; j < MULTI_MAX; ++j) acc[j] = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+#pragma unroll
+    for (int j = 0; j < MULTI_MAX; ++j)
+      if (j < k) acc[j] += a[i * k + j] * b[i * k + j];
+  }
+#pragma unroll
+  for (int j = 0; j < MULTI_MAX; ++j) {
+#pragma unroll
+    for (int o = WAVE >> 1; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o, WAVE);
+    if ((threadIdx.x & (WAVE - 1)) == 0) red[j][threadIdx.x >> 6] = acc[j];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < k) {
+    double s = 0.0;
+    for (int w = 0; w < BLOCK / WAVE; ++w) s += red[threadIdx.x][w];
+    partial[(int64_t)threadIdx.x * KR_BLOCKS + blockIdx.x] = s;
+  }
+}
+// x_j += alpha_j s_j, d_j -= alpha_j q_j with alpha_j = num[j] / den[j]; columns with active[j] == 0 are not touched
+__global__ __launch_bounds__(BLOCK) void kr_cg_update_multi_kernel(int64_t len, int k, const double* __restrict__ num, const double* __restrict__ den,
+                                                                   const int32_t* __restrict__ active, const double* __restrict__ s,
+                                                                   const double* __restrict__ q, double* __restrict__ x, double* __restrict__ d) {
+  const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= len) return;
+  const int j = (int)(t % k);
+  if (!active[j]) return;
+  const double alpha = num[j] / den[j];
+  x[t] += alpha * s[t];
+  d[t] -= alpha * q[t];
+}
+// s_j = w_j + (num[j] / den[j]) s_j on the active columns
+__global__ __launch_bounds__(BLOCK) void kr_xpby_multi_kernel(int64_t len, int k, const double* __restrict__ num, const double* __restrict__ den,
+                                                              const int32_t* __restrict__ active, const double* __restrict__ w, double* __restrict__ s) {
+  const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= len) return;
+  const int j = (int)(t % k);
+  if (!active[j]) return;
+  s[t] = w[t] + (num[j] / den[j]) * s[t];
+}
+// d = b - w
+__global__ __launch_bounds__(BLOCK) void multi_sub_kernel(int64_t len, const double* __restrict__ b, const double* __restrict__ w, double* __restrict__ d) {
+  const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (t < len) d[t] = b[t] - w[t];
+}
+
+// ---------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------
+
+// greedy cut of k columns into fused widths 4, 2 plus at most one single column.  The kernels are written for any NV, but width 8
+// is not instantiated: sell_spmm_kernel<G, 8, EP> needs 134-144 VGPRs = 3 waves per SIMD (66 / 90-98 VGPRs, 7 / 4-5 waves at
+// widths 2 / 4), and measured at cfg 2 its level-0 passes cost 183 us per column against 145 us at width 4, the
+// whole cycle 1.23 x k single applications against 1.40 x -- so 8 columns run as 4 + 4
+inline int multi_groups(int k, bool fused, int32_t* width) {
+  int n = 0;
+  if (!fused) { for (int j = 0; j < k; ++j) width[n++] = 1; return n; }
+  for (int w : {4, 2, 1})
+    while (k >= w) { width[n++] = w; k -= w; }
+  return n;
+}
+
+struct MultiWork {                      // work vectors of one fused width, kept from call to call
+  struct Lev { DevBuf<double> x, rhs, res, tmp; };
+  std::vector<Lev> lev;
+  DevBuf<double> in, out;               // interleaved copies of a group of the caller's columns (arguments that are not used in place)
+};
+
+struct MultiState {
+  int fused = -1;                       // -1: not decided yet
+  std::string why;                      // fused == 0: the first reason
+  MultiWork work[MULTI_MAX + 1];        // by width (2, 4)
+  DevBuf<double> col_in, col_out;       // one contiguous column (single-vector path behind an interleaved argument)
+  DevBuf<double> stage_b, stage_x;      // host-pointer calls
+  DevBuf<double> kr[5];                 // amgx_pcg_multi: b, x, d, w, s (interleaved, width k)
+  DevBuf<double> kr_sc, kr_partial;
+  DevBuf<int32_t> kr_active;
+  using Key = std::tuple<const double*, double*, int, int, int64_t, int64_t>;   // b, x, k, layout, ldb, ldx
+  std::map<Key, hipGraphExec_t> graphs;
+  std::vector<Key> graph_age;
+  ~MultiState() { drop(); }
+  void drop() {
+    for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
+    graphs.clear();
+    graph_age.clear();
+  }
+};
+
+void multi_drop_graphs(MultiState* s) { s->drop(); }       // amgx_set_stream: captures of the old stream go
+void multi_free(MultiState* s) { delete s; }
+
+struct Multi {
+  Handle& h;
+  MultiState& st;
+  explicit Multi(Handle& hh) : h(hh), st(state(hh)) {}
+
+  static MultiState& state(Handle& h) {
+    if (!h.multi) h.multi = new MultiState;
+    MultiState& s = *h.multi;
+    if (s.fused < 0) decide(h, s);
+    return s;
+  }
+  static bool spmm_ok(const DevMatrix& M) { return M.br == 1 && M.bc == 1 && (M.fmt == FMT_SELL || M.fmt == FMT_CSRVEC); }
+  // all-or-nothing rule of the fused path: V-cycle; every smoothed level scalar, plain Jacobi, square, in the caller's numbering
+  static void decide(Handle& h, MultiState& s) {
+    s.fused = 0;
+    const int L = h.n_levels();
+    if (h.cycle != AMGX_CYCLE_V) { s.why = "cycle is not V"; return; }
+    for (int l = 0; l < L; ++l) {
+      const DevLevel& V = h.lev[l];
+      const std::string at = " (level " + std::to_string(l) + ")";
+      if (V.bs != 1) { s.why = "block level" + at; return; }
+      if (V.n != V.ncols) { s.why = "ghost columns" + at; return; }
+      if (h.permuted(l)) { s.why = "renumbered level" + at; return; }
+      if (V.n > 0 && !spmm_ok(V.A)) { s.why = "level matrix format" + at; return; }
+      if (l + 1 == L) break;
+      if (V.sm_type != AMGX_SM_JACOBI) { s.why = "smoother is not Jacobi" + at; return; }
+      if (!h.plain(V)) { s.why = "sm_steps > 1 or sm_symm" + at; return; }
+      if (V.n > 0 && (!spmm_ok(V.P) || !spmm_ok(V.PT))) { s.why = "transfer format" + at; return; }
+    }
+    s.fused = 1;
+  }
+
+  // first level that the multi cycle hands to ONE dense product (collapsed operator or the coarsest level's inverse)
+  // (0: the whole cycle is the dense operator, no level work vectors)
+  int top() const { return h.dense_level >= 0 ? h.dense_level : h.n_levels() - 1; }
+
+  int64_t work_bytes(int k) const {
+    if (k == 1) return 0;                                       // amgx_apply itself
+    int32_t wd[MULTI_MAX];
+    const int ng = multi_groups(k, st.fused == 1, wd);
+    const int64_t n0 = h.lev[0].len();
+    const int T = top();
+    int64_t per_col = 2 * n0;                                  // the two interleaved copies of a group of the caller's columns
+    for (int l = 0; l <= T && l < h.n_levels(); ++l) per_col += ((l > 0 ? 2 : 0) + (l < T ? 2 : 0)) * h.lev[l].len();
+    int64_t bytes = 0;
+    bool single = false, seen[MULTI_MAX + 1] = {};              // (groups of one width share their work space)
+    for (int g = 0; g < ng; ++g) {
+      if (wd[g] == 1) single = true;
+      else if (!seen[wd[g]]) { seen[wd[g]] = true; bytes += per_col * wd[g] * (int64_t)sizeof(double); }
+    }
+    if (single) bytes += 2 * n0 * (int64_t)sizeof(double);    // one contiguous column in, one out
+    return bytes;
+  }
+
+  static void fit(DevBuf<double>& b, int64_t n) { if ((int64_t)b.n < n) b.alloc((size_t)n); }
+  MultiWork& work(int w) {
+    MultiWork& W = st.work[w];
+    if (W.lev.empty()) {
+      const int T = top();
+      W.lev.resize(T + 1);
+      for (int l = 0; l <= T; ++l) {
+        const size_t len = (size_t)h.lev[l].len() * w;
+        if (l > 0) { W.lev[l].x.alloc(len); W.lev[l].rhs.alloc(len); }
+        if (l < T) { W.lev[l].res.alloc(len); W.lev[l].tmp.alloc(len); }
+      }
+    }
+    return W;
+  }
+
+  // ------------------------------------------------------------------ launches
+  template <int NV, int EP>
+  void spmm_nv(const DevMatrix& M, const double* x, double* y, const EpArgs& ep) {
+    if (M.n_rows == 0) return;
+    hipStream_t s = h.stream;
+    if (M.fmt == FMT_SELL && M.sell.win) {
+      if (M.sell.win != SELL_WIN) throw Err("windowed SELL: unexpected window size");
+      const int nw = (int)((M.n_rows + SELL_WIN - 1) / SELL_WIN);
+      hipLaunchKernelGGL((sell_win_spmm_kernel<SELL_WIN, NV, EP>), dim3(nw), dim3(SELL_WIN), 0, s, M.n_rows, M.sell.view(), M.sell.rowloc.p, x, y, ep);
+    } else if (M.fmt == FMT_SELL) {
+      const int grid = (M.n_slices + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+#define LAUNCH_SELLM(G) hipLaunchKernelGGL((sell_spmm_kernel<G, NV, EP>), dim3(grid), dim3(BLOCK), 0, s, M.n_rows, M.n_slices, M.sell.view(), x, y, ep)
+      switch (M.lanes) {
+        case 1: LAUNCH_SELLM(1); break;
+        case 2: LAUNCH_SELLM(2); break;
+        case 4: LAUNCH_SELLM(4); break;
+        case 8: LAUNCH_SELLM(8); break;
+        default: LAUNCH_SELLM(16); break;
+      }
+#undef LAUNCH_SELLM
+    } else if (M.fmt == FMT_CSRVEC && M.br == 1 && M.bc == 1) {
+      const int grid = Handle::grid_for(M.n_rows * M.lanes);
+#define LAUNCH_CSRM(G) hipLaunchKernelGGL((csrvec_spmm_kernel<G, NV, EP>), dim3(grid), dim3(BLOCK), 0, s, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep)
+      switch (M.lanes) {
+        case 2: LAUNCH_CSRM(2); break;
+        case 4: LAUNCH_CSRM(4); break;
+        case 8: LAUNCH_CSRM(8); break;
+        case 16: LAUNCH_CSRM(16); break;
+        case 32: LAUNCH_CSRM(32); break;
+        default: LAUNCH_CSRM(64); break;
+      }
+#undef LAUNCH_CSRM
+    } else throw Err("multi-vector product: matrix format has no multi-vector kernel");
+    HIPCHK(hipGetLastError());
+  }
+  template <int EP>
+  void spmm(int w, const DevMatrix& M, const double* x, double* y, const EpArgs& ep) {
+    if (w == 2) spmm_nv<2, EP>(M, x, y, ep);
+    else if (w == 4) spmm_nv<4, EP>(M, x, y, ep);
+    else throw Err("multi-vector product: width must be 2 or 4");
+  }
+  void gemm(int w, int n, int ld, const double* M, const double* x, double* y) {
+    if (n <= 0) return;
+    const int grid = (n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    if (w == 2) hipLaunchKernelGGL((dense_gemm_nv_kernel<2>), dim3(grid), dim3(BLOCK), 0, h.stream, n, ld, M, x, y);
+    else if (w == 4) hipLaunchKernelGGL((dense_gemm_nv_kernel<4>), dim3(grid), dim3(BLOCK), 0, h.stream, n, ld, M, x, y);
+    else throw Err("multi-vector dense product: width must be 2 or 4");
+    HIPCHK(hipGetLastError());
+  }
+  void pack(int64_t n, int w, const double* src, int64_t rs, int64_t cs, int c0, double* dst) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(multi_pack_kernel, dim3(Handle::grid_for(n * w)), dim3(BLOCK), 0, h.stream, n, w, src, rs, cs, c0, dst);
+    HIPCHK(hipGetLastError());
+  }
+  void unpack(int64_t n, int w, const double* src, double* dst, int64_t rs, int64_t cs, int c0) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(multi_unpack_kernel, dim3(Handle::grid_for(n * w)), dim3(BLOCK), 0, h.stream, n, w, src, dst, rs, cs, c0);
+    HIPCHK(hipGetLastError());
+  }
+
+  void coarse_multi(int w, const double* rhs, double* x) {
+    const DevLevel& V = h.lev.back();
+    if (h.clev != AMGX_CLEV_INV || h.coarse_n == 0) { h.zero(x, V.len() * w); return; }
+    gemm(w, (int)h.coarse_n, (int)h.coarse_ld, h.coarse_inv.p, rhs, x);
+  }
+
+  // the literal V-cycle on w interleaved vectors (stage order of pre_smooth / transfer_f2c / post_smooth without folding)
+  void cycle_v_multi(int w, double* x, const double* b) {
+    const int L = h.n_levels();
+    if (h.dense_level == 0) { gemm(w, h.dense_n, h.dense_ld, h.dense_op.p, b, x); return; }
+    if (L == 1) { coarse_multi(w, b, x); return; }
+    MultiWork& W = work(w);
+    const int T = top();
+    const int sh = w == 2 ? 1 : 2;
+    for (int l = 0; l < T; ++l) {
+      const DevLevel& V = h.lev[l];
+      double* xl = l == 0 ? x : W.lev[l].x.p;
+      const double* bl = l == 0 ? b : W.lev[l].rhs.p;
+      if (V.n > 0) {
+        hipLaunchKernelGGL(multi_diag_kernel, dim3(Handle::grid_for(V.n * w)), dim3(BLOCK), 0, h.stream, V.n * w, sh, V.dinv.p, bl, xl, V.omega);
+        HIPCHK(hipGetLastError());
+      }
+      spmm<EP_RES>(w, V.A, xl, W.lev[l].res.p, EpArgs{bl, nullptr, nullptr, 0.0, nullptr, 0});
+      spmm<EP_MULT>(w, V.PT, W.lev[l].res.p, W.lev[l + 1].rhs.p, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0});
+    }
+    if (h.dense_level > 0) gemm(w, h.dense_n, h.dense_ld, h.dense_op.p, W.lev[T].rhs.p, W.lev[T].x.p);
+    else coarse_multi(w, W.lev[T].rhs.p, W.lev[T].x.p);
+    for (int l = T - 1; l >= 0; --l) {
+      const DevLevel& V = h.lev[l];
+      double* xl = l == 0 ? x : W.lev[l].x.p;
+      const double* bl = l == 0 ? b : W.lev[l].rhs.p;
+      spmm<EP_AXPY>(w, V.P, W.lev[l + 1].x.p, W.lev[l].tmp.p, EpArgs{nullptr, xl, nullptr, 1.0, nullptr, 0});
+      spmm<EP_JAC>(w, V.A, W.lev[l].tmp.p, xl, EpArgs{bl, W.lev[l].tmp.p, V.dinv.p, V.omega, nullptr, 0});
+    }
+  }
+
+  // one application through the single-vector path on contiguous device vectors (what amgx_apply does with device pointers)
+  void apply_single(const double* b, double* x, bool graph_ok, bool capturing) {
+    if (capturing) { h.do_cycle(x, b); return; }              // (fused handles only: never renumbered)
+    Staged sg(h, AMGX_DEVICE_PTR);
+    const int64_t n = h.lev[0].len();
+    const double* db = sg.in(0, b, n, 0);
+    double* dx = sg.inout(1, x, n, false, 0);
+    h.run_cycle(dx, db, graph_ok);
+    sg.out(1, x, n, 0);
+  }
+
+  // X = C B on device multi-vectors; (rs, cs) strides of B / X: entry (i, j) at i*rs + j*cs
+  void apply_body(int k, const double* B, int64_t brs, int64_t bcs, double* X, int64_t xrs, int64_t xcs, bool graph_ok, bool capturing) {
+    const int64_t n = h.lev[0].len();
+    int32_t wd[MULTI_MAX];
+    const int ng = multi_groups(k, st.fused == 1, wd);
+    int c0 = 0;
+    for (int g = 0; g < ng; c0 += wd[g], ++g) {
+      const int w = wd[g];
+      if (w == 1) {
+        const double* b1 = B + c0 * bcs;
+        double* x1 = X + c0 * xcs;
+        if (brs != 1) { fit(st.col_in, n); pack(n, 1, B, brs, bcs, c0, st.col_in.p); b1 = st.col_in.p; }
+        if (xrs != 1) { fit(st.col_out, n); x1 = st.col_out.p; }
+        apply_single(b1, x1, graph_ok, capturing);
+        if (xrs != 1) unpack(n, 1, st.col_out.p, X, xrs, xcs, c0);
+        continue;
+      }
+      MultiWork& W = work(w);
+      // interleaved arguments of exactly this width (16-byte aligned) are used in place
+      const bool b_inplace = brs == w && bcs == 1 && k == w && (reinterpret_cast<uintptr_t>(B) & 15) == 0;
+      const bool x_inplace = xrs == w && xcs == 1 && k == w && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+      const double* bw = B;
+      double* xw = X;
+      if (!b_inplace) { fit(W.in, n * w); pack(n, w, B, brs, bcs, c0, W.in.p); bw = W.in.p; }
+      if (!x_inplace) { fit(W.out, n * w); xw = W.out.p; }
+      cycle_v_multi(w, xw, bw);
+      if (!x_inplace) unpack(n, w, W.out.p, X, xrs, xcs, c0);
+    }
+  }
+
+  void apply(int k, const double* B, int64_t ldb, double* X, int64_t ldx, bool interleaved, bool graph_ok) {
+    const int64_t brs = interleaved ? k : 1, bcs = interleaved ? 1 : ldb, xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx;
+    // only the fused path is captured as a whole; the column loop replays the single-vector graphs of run_cycle
+    if (st.fused != 1 || !(h.use_graph && graph_ok) || h.stream == nullptr) { apply_body(k, B, brs, bcs, X, xrs, xcs, graph_ok, false); return; }
+    const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx};
+    auto it = st.graphs.find(key);
+    if (it == st.graphs.end()) {
+      int32_t wd[MULTI_MAX];
+      const int ng = multi_groups(k, true, wd);
+      for (int g = 0; g < ng; ++g) {                           // allocations happen before the capture
+        if (wd[g] > 1) { MultiWork& W = work(wd[g]); fit(W.in, h.lev[0].len() * wd[g]); fit(W.out, h.lev[0].len() * wd[g]); }
+        else { fit(st.col_in, h.lev[0].len()); fit(st.col_out, h.lev[0].len()); }
+      }
+      hipGraph_t g = nullptr;
+      HIPCHK(hipStreamBeginCapture(h.stream, hipStreamCaptureModeThreadLocal));
+      try { apply_body(k, B, brs, bcs, X, xrs, xcs, false, true); }
+      catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(h.stream, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
+      HIPCHK(hipStreamEndCapture(h.stream, &g));
+      hipGraphExec_t ge = nullptr;
+      hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+      (void)hipGraphDestroy(g);
+      if (e != hipSuccess) throw Err(std::string("hipGraphInstantiate failed: ") + hipGetErrorString(e));
+      if (st.graphs.size() >= 16 && !st.graph_age.empty()) {
+        auto old = st.graphs.find(st.graph_age.front());
+        st.graph_age.erase(st.graph_age.begin());
+        if (old != st.graphs.end()) { (void)hipGraphExecDestroy(old->second); st.graphs.erase(old); }
+      }
+      it = st.graphs.emplace(key, ge).first;
+      st.graph_age.push_back(key);
+    }
+    HIPCHK(hipGraphLaunch(it->second, h.stream));
+  }
+
+  // Y = A_level X on device multi-vectors
+  void matvec(int level, int k, const double* X, int64_t ldx, double* Y, int64_t ldy, bool interleaved) {
+    const DevLevel& V = h.lev[level];
+    const int64_t n = V.len(), nx = V.ext_len();
+    const int64_t xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx, yrs = interleaved ? k : 1, ycs = interleaved ? 1 : ldy;
+    int32_t wd[MULTI_MAX];
+    const int ng = multi_groups(k, st.fused == 1, wd);
+    int c0 = 0;
+    for (int g = 0; g < ng; c0 += wd[g], ++g) {
+      const int w = wd[g];
+      if (w == 1) {                                            // amgx_matvec with device pointers
+        const double* x1 = X + c0 * xcs;
+        double* y1 = Y + c0 * ycs;
+        if (xrs != 1) { fit(st.col_in, std::max(nx, h.lev[0].len())); pack(nx, 1, X, xrs, xcs, c0, st.col_in.p); x1 = st.col_in.p; }
+        if (yrs != 1) { fit(st.col_out, std::max(n, h.lev[0].len())); y1 = st.col_out.p; }
+        Staged sg(h, AMGX_DEVICE_PTR);
+        const double* dx = sg.in(0, x1, nx, level);
+        double* dy = sg.inout(1, y1, n, false, level);
+        h.mult(V.A, dx, dy);
+        sg.out(1, y1, n, level);
+        if (yrs != 1) unpack(n, 1, st.col_out.p, Y, yrs, ycs, c0);
+        continue;
+      }
+      MultiWork& W = work(w);
+      const bool x_inplace = xrs == w && xcs == 1 && k == w && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+      const bool y_inplace = yrs == w && ycs == 1 && k == w && (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
+      const double* xw = X;
+      double* yw = Y;
+      // (the interleaved copies are sized for level 0, the largest level)
+      if (!x_inplace) { fit(W.in, h.lev[0].len() * w); pack(n, w, X, xrs, xcs, c0, W.in.p); xw = W.in.p; }
+      if (!y_inplace) { fit(W.out, h.lev[0].len() * w); yw = W.out.p; }
+      spmm<EP_MULT>(w, V.A, xw, yw, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0});
+      if (!y_inplace) unpack(n, w, W.out.p, Y, yrs, ycs, c0);
+    }
+  }
+
+  // k independent preconditioned CG recurrences (Krylov::pcg per column) that share the operator product and the preconditioner
+  // application.  B, X: device multi-vectors (strides as apply_body).
+  void pcg(int k, const double* B, int64_t brs, int64_t bcs, double* X, int64_t xrs, int64_t xcs, double tol, int maxit, bool use_pre,
+           bool graph_ok, double* errs, int32_t* iters) {
+    if (h.lev[0].n != h.lev[0].ncols) throw Err("Krylov solvers need a square level-0 matrix (single rank)");
+    const int64_t n = h.lev[0].len(), len = n * k;
+    for (auto& v : st.kr) fit(v, len);
+    if (st.kr_sc.n < (size_t)3 * MULTI_MAX) { st.kr_sc.alloc(3 * MULTI_MAX); st.kr_partial.alloc((size_t)KR_BLOCKS * MULTI_MAX); st.kr_active.alloc(MULTI_MAX); }
+    double *b = st.kr[0].p, *x = st.kr[1].p, *d = st.kr[2].p, *w = st.kr[3].p, *s = st.kr[4].p;
+    double* sc = st.kr_sc.p;                                  // rows of MULTI_MAX scalars: 0 / 1 = <w, d> of the last two iterations, 2 = <s, A s>
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(KR_BLOCKS, (n + BLOCK - 1) / BLOCK));
+    const int grid = Handle::grid_for(len);
+    hipStream_t sm = h.stream;
+    auto dot = [&](const double* a, const double* c, int slot) {
+      hipLaunchKernelGGL(kr_dot_multi_partial_kernel, dim3(nb), dim3(BLOCK), 0, sm, n, k, a, c, st.kr_partial.p);
+      hipLaunchKernelGGL(kr_dot_final_kernel, dim3(k), dim3(BLOCK), 0, sm, nb, st.kr_partial.p, sc + slot * MULTI_MAX);
+      HIPCHK(hipGetLastError());
+    };
+    auto read = [&](int slot, double* out) {
+      HIPCHK(hipMemcpyAsync(out, sc + slot * MULTI_MAX, k * sizeof(double), hipMemcpyDeviceToHost, sm));
+      HIPCHK(hipStreamSynchronize(sm));
+    };
+    auto precond = [&](const double* r, double* z) {
+      if (use_pre) apply(k, r, 0, z, 0, true, graph_ok);
+      else h.copy(z, r, len);
+    };
+    int32_t active[MULTI_MAX];
+    auto push_active = [&]() {
+      HIPCHK(hipMemcpyAsync(st.kr_active.p, active, k * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+      HIPCHK(hipStreamSynchronize(sm));                       // (the host array changes again before the next copy)
+    };
+    pack(n, k, B, brs, bcs, 0, b);
+    pack(n, k, X, xrs, xcs, 0, x);
+    matvec(0, k, x, 0, w, 0, true);                           // d = b - A x
+    hipLaunchKernelGGL(multi_sub_kernel, dim3(grid), dim3(BLOCK), 0, sm, len, b, w, d);
+    precond(d, w);
+    h.copy(s, w, len);
+    int cur = 1;
+    dot(w, d, cur);
+    double err0[MULTI_MAX], v[MULTI_MAX];
+    read(cur, v);
+    int n_active = 0;
+    for (int j = 0; j < k; ++j) {
+      err0[j] = std::sqrt(std::fabs(v[j]));
+      if (errs) errs[(size_t)j * (maxit + 1)] = err0[j];
+      iters[j] = 0;
+      active[j] = err0[j] != 0.0 && maxit > 0;                // (NaN: the column iterates to maxit, like amgx_pcg)
+      n_active += active[j];
+    }
+    push_active();
+    for (int it = 1; it <= maxit && n_active > 0; ++it) {
+      matvec(0, k, s, 0, w, 0, true);                         // w = A s
+      const int old = cur;
+      cur = 1 - cur;
+      dot(s, w, 2);
+      hipLaunchKernelGGL(kr_cg_update_multi_kernel, dim3(grid), dim3(BLOCK), 0, sm, len, k, sc + old * MULTI_MAX, sc + 2 * MULTI_MAX, st.kr_active.p, s, w, x, d);
+      precond(d, w);
+      dot(w, d, cur);
+      hipLaunchKernelGGL(kr_xpby_multi_kernel, dim3(grid), dim3(BLOCK), 0, sm, len, k, sc + cur * MULTI_MAX, sc + old * MULTI_MAX, st.kr_active.p, w, s);
+      HIPCHK(hipGetLastError());
+      read(cur, v);                                           // k scalars per iteration, one copy
+      bool changed = false;
+      for (int j = 0; j < k; ++j) {
+        if (!active[j]) continue;
+        const double err = std::sqrt(std::fabs(v[j]));
+        if (errs) errs[(size_t)j * (maxit + 1) + it] = err;
+        iters[j] = it;
+        if (err <= tol * err0[j]) { active[j] = 0; --n_active; changed = true; }    // frozen: its x is not touched again
+      }
+      if (changed && n_active > 0) push_active();
+    }
+    unpack(n, k, x, X, xrs, xcs, 0);
+  }
+};
+
+// host-pointer arguments of the multi-vector calls: one staged copy per multi-vector, laid out as the caller's (column-major
+// copies are compacted to ld = rows)
+struct MultiStaged {
+  Handle& h;
+  bool host;
+  MultiStaged(Handle& hh, int flags) : h(hh), host(!(flags & AMGX_DEVICE_PTR)) {}
+  const double* in(DevBuf<double>& buf, const double* p, int64_t rows, int k, bool interleaved, int64_t ld, bool load = true) {
+    if (!host) return p;
+    // (sized once for the widest call: the graphs of apply() are keyed on the address, which must not move when k grows)
+    Multi::fit(buf, std::max<int64_t>(rows * k, h.lev[0].ext_len() * MULTI_MAX));
+    if (load) {
+      if (interleaved || ld == rows) HIPCHK(hipMemcpyAsync(buf.p, p, (size_t)rows * k * sizeof(double), hipMemcpyHostToDevice, h.stream));
+      else for (int j = 0; j < k; ++j) HIPCHK(hipMemcpyAsync(buf.p + j * rows, p + j * ld, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, h.stream));
+    }
+    return buf.p;
+  }
+  void out(const DevBuf<double>& buf, double* p, int64_t rows, int k, bool interleaved, int64_t ld) {
+    if (!host) return;
+    if (interleaved || ld == rows) HIPCHK(hipMemcpyAsync(p, buf.p, (size_t)rows * k * sizeof(double), hipMemcpyDeviceToHost, h.stream));
+    else for (int j = 0; j < k; ++j) HIPCHK(hipMemcpyAsync(p + j * ld, buf.p + j * rows, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, h.stream));
+    HIPCHK(hipStreamSynchronize(h.stream));
+  }
+};
+
+inline void multi_check(const char* fn, int k, const void* a, const void* b, int64_t lda, int64_t ldb, int64_t rows_a, int64_t rows_b, bool interleaved) {
+  const std::string f(fn);
+  if (k < 1 || k > MULTI_MAX) throw Err(f + ": k must be 1 .. " + std::to_string(MULTI_MAX) + " (got " + std::to_string(k) + ")");
+  if (!a || !b) throw Err(f + ": null multi-vector");
+  if (a == b) throw Err(f + ": the multi-vectors must not alias");
+  if (!interleaved && k > 1 && (lda < rows_a || ldb < rows_b)) throw Err(f + ": leading dimension below the level size");
+}
+
+}  // namespace amgx
+
+extern "C" {
+
+int amgx_apply_multi(amgx_handle hh, int k, const double* B, int64_t ldb, double* X, int64_t ldx, int b_status, int flags) {
+  if (k == 1 && hh && hh->h) return amgx_apply(hh, B, X, b_status, flags & ~AMGX_MULTI_INTERLEAVED);   // the single-vector path itself
+  (void)b_status;   // single GPU: DISTRIBUTED == CUMULATED, as in amgx_apply
+  return guard(hh, [&](amgx::Handle& h) {
+    const int64_t n = h.lev[0].len();
+    const bool il = flags & AMGX_MULTI_INTERLEAVED;
+    amgx::multi_check("amgx_apply_multi", k, B, X, ldb, ldx, n, n, il);
+    amgx::Multi M(h);
+    amgx::MultiStaged sg(h, flags);
+    const int64_t lb = (sg.host && !il) ? n : ldb, lx = (sg.host && !il) ? n : ldx;      // (staged copies are compact)
+    const double* dB = sg.in(M.st.stage_b, B, n, k, il, ldb);
+    double* dX = const_cast<double*>(sg.in(M.st.stage_x, X, n, k, il, ldx, false));
+    M.apply(k, dB, lb, dX, lx, il, !(flags & AMGX_NO_GRAPH));
+    sg.out(M.st.stage_x, X, n, k, il, ldx);
+  });
+}
+
+int amgx_matvec_multi(amgx_handle hh, int level, int k, const double* X, int64_t ldx, double* Y, int64_t ldy, int flags) {
+  return guard(hh, [&](amgx::Handle& h) {
+    if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_matvec_multi: level out of range");
+    const int64_t n = h.lev[level].len(), nx = h.lev[level].ext_len();
+    const bool il = flags & AMGX_MULTI_INTERLEAVED;
+    amgx::multi_check("amgx_matvec_multi", k, X, Y, ldx, ldy, nx, n, il);
+    amgx::Multi M(h);
+    amgx::MultiStaged sg(h, flags);
+    const int64_t lx = (sg.host && !il) ? nx : ldx, ly = (sg.host && !il) ? n : ldy;
+    const double* dX = sg.in(M.st.stage_b, X, nx, k, il, ldx);
+    double* dY = const_cast<double*>(sg.in(M.st.stage_x, Y, n, k, il, ldy, false));
+    M.matvec(level, k, dX, lx, dY, ly, il);
+    sg.out(M.st.stage_x, Y, n, k, il, ldy);
+  });
+}
+
+int amgx_pcg_multi(amgx_handle hh, int k, const double* B, int64_t ldb, double* X, int64_t ldx, double tol, int maxit, int use_precond, int flags,
+                   double* errs, int32_t* iters) {
+  return guard(hh, [&](amgx::Handle& h) {
+    const int64_t n = h.lev[0].len();
+    const bool il = flags & AMGX_MULTI_INTERLEAVED;
+    amgx::multi_check("amgx_pcg_multi", k, B, X, ldb, ldx, n, n, il);
+    if (maxit < 0 || !iters) throw amgx::Err("amgx_pcg_multi: bad arguments (maxit < 0 or iters == NULL)");
+    amgx::Multi M(h);
+    amgx::MultiStaged sg(h, flags);
+    const int64_t lb = (sg.host && !il) ? n : ldb, lx = (sg.host && !il) ? n : ldx;
+    const double* dB = sg.in(M.st.stage_b, B, n, k, il, ldb);
+    double* dX = const_cast<double*>(sg.in(M.st.stage_x, X, n, k, il, ldx));
+    M.pcg(k, dB, il ? k : 1, il ? 1 : lb, dX, il ? k : 1, il ? 1 : lx, tol, maxit, use_precond != 0, !(flags & AMGX_NO_GRAPH), errs, iters);
+    sg.out(M.st.stage_x, X, n, k, il, ldx);
+  });
+}
+
+int amgx_multi_info(amgx_handle hh, int k, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes) {
+  return guard(hh, [&](amgx::Handle& h) {
+    if (k < 1 || k > amgx::MULTI_MAX) throw amgx::Err("amgx_multi_info: k must be 1 .. " + std::to_string(amgx::MULTI_MAX) + " (got " + std::to_string(k) + ")");
+    amgx::Multi M(h);
+    int32_t wd[amgx::MULTI_MAX];
+    const int ng = amgx::multi_groups(k, M.st.fused == 1, wd);
+    if (fused) *fused = M.st.fused;
+    if (n_groups) *n_groups = ng;
+    if (group_width) for (int g = 0; g < amgx::MULTI_MAX; ++g) group_width[g] = g < ng ? wd[g] : 0;
+    if (work_bytes) *work_bytes = M.work_bytes(k);
+  });
+}
+
+}  // extern "C"

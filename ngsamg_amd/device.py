@@ -137,6 +137,49 @@ class _Vec:
             self.addr = a.ctypes.data
 
 
+def check_multi(vecs, sizes, interleaved=False, names=None):
+    """Validate the multi-vector arguments of MultMulti / MatVecMulti / SolveMulti (a plain function: no handle, no native call).
+
+    vecs: 2-D float64, C-contiguous numpy arrays or torch CUDA tensors (all of one kind); sizes: rows each must have.
+    Layout: shape (k, n) -- every right-hand side contiguous, i.e. column-major with ld = n -- or, interleaved, (n, k).
+    Returns (k, addresses, leading dimensions, on_device); raises NgsAMGError for a wrong shape, dtype, stride, kind or k."""
+    names = names or [f"argument {i}" for i in range(len(vecs))]
+    kinds = [_is_torch(v) for v in vecs]
+    if any(kinds) and not all(kinds):
+        raise NgsAMGError("mixing host arrays and device tensors in one call is not supported")
+    k, addrs, lds = None, [], []
+    for v, n, name in zip(vecs, sizes, names):
+        if _is_torch(v):
+            import torch
+            if not v.is_cuda:
+                raise NgsAMGError(f"{name}: torch tensors must live on the GPU")
+            ok_type, contig, addr = v.dtype == torch.float64, v.is_contiguous(), v.data_ptr
+            shape = tuple(v.shape)
+        elif isinstance(v, np.ndarray):
+            ok_type, contig, addr = v.dtype == np.float64, bool(v.flags.c_contiguous), (lambda v=v: v.ctypes.data)
+            shape = v.shape
+        else:
+            raise NgsAMGError(f"{name}: need a 2-D float64 numpy array or CUDA tensor")
+        if len(shape) != 2:
+            raise NgsAMGError(f"{name}: multi-vectors are 2-D, got {len(shape)} dimension(s)")
+        if not ok_type:
+            raise NgsAMGError(f"{name}: need float64")
+        if not contig:
+            raise NgsAMGError(f"{name}: need a C-contiguous array")
+        kk, rows = (shape[1], shape[0]) if interleaved else shape
+        if not (1 <= kk <= _lib.AMGX_MULTI_MAX):
+            raise NgsAMGError(f"{name}: {kk} right-hand sides, need 1 .. {_lib.AMGX_MULTI_MAX}")
+        if rows != n:
+            want = f"({n}, k)" if interleaved else f"(k, {n})"
+            raise NgsAMGError(f"{name}: shape {shape}, need {want}")
+        if k is not None and kk != k:
+            raise NgsAMGError(f"{name}: {kk} right-hand sides, the other argument has {k}")
+        k = kk
+        addrs.append(addr())
+        lds.append(int(n))
+    return k, addrs, lds, all(kinds) and bool(kinds)
+
+
 def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V", clev="inv", device=0,
                    use_graph=True):
     """amgx_hierarchy_desc over the host arrays of a hierarchy.  Returns (desc, keep): `keep` holds everything the
@@ -318,6 +361,46 @@ class DeviceAMGMatrix:
 
     MultTrans = Mult
     MultTransAdd = MultAdd
+
+    # multi-vectors: BaseMatrix::Mult on a MultiVector, k right-hand sides per matrix pass (amgx_apply_multi) ----------
+    def _multi_flags(self, on_device, interleaved, graph=True):
+        f = _lib.AMGX_DEVICE_PTR if on_device else _lib.AMGX_HOST_PTR
+        if on_device:
+            import torch
+            s = int(torch.cuda.current_stream().cuda_stream)
+            if s != self._stream:
+                self._ck(self._lib.amgx_set_stream(self._h, C.c_void_p(s)))
+                self._stream = s
+        if interleaved:
+            f |= _lib.AMGX_MULTI_INTERLEAVED
+        if not graph:
+            f |= _lib.AMGX_NO_GRAPH
+        return f
+
+    def MultMulti(self, B, X, interleaved=False, graph=True):
+        """X[j] = C B[j] for k = 1 .. 8 right-hand sides: 2-D float64 arrays / CUDA tensors of shape (k, n), or (n, k) with
+        interleaved=True.  Handles that qualify (multi_info) read every level matrix once per group of 2, 4 or 8 columns."""
+        n = self.sizes[0]
+        k, (ab, ax), (lb, lx), dev = check_multi((B, X), (n, n), interleaved, ("B", "X"))
+        self._ck(self._lib.amgx_apply_multi(self._h, k, ab, lb, ax, lx, 0, self._multi_flags(dev, interleaved, graph)))
+        return X
+
+    def MatVecMulti(self, level, X, Y, interleaved=False):
+        """Y[j] = A_level X[j]"""
+        n = self._size(level)
+        k, (ax, ay), (lx, ly), dev = check_multi((X, Y), (self.ext_sizes[level], n), interleaved, ("X", "Y"))
+        self._ck(self._lib.amgx_matvec_multi(self._h, int(level), k, ax, lx, ay, ly, self._multi_flags(dev, interleaved)))
+        return Y
+
+    def multi_info(self, k):
+        """how a multi-vector call with k columns runs: fused (True: the multi-vector kernels; False: a column loop over the
+        single-vector path), the widths of the column groups and the bytes of multi-vector work space"""
+        if not (1 <= int(k) <= _lib.AMGX_MULTI_MAX):
+            raise NgsAMGError(f"multi_info: k = {k}, need 1 .. {_lib.AMGX_MULTI_MAX}")
+        fused, ng, wb = C.c_int32(), C.c_int32(), C.c_int64()
+        wd = (C.c_int32 * _lib.AMGX_MULTI_MAX)()
+        self._ck(self._lib.amgx_multi_info(self._h, int(k), C.byref(fused), C.byref(ng), wd, C.byref(wb)))
+        return {"fused": int(fused.value), "groups": [int(wd[i]) for i in range(ng.value)], "work_bytes": int(wb.value)}
 
     def apply(self, b):
         """convenience: returns a new vector C b of the same kind as b"""

@@ -1,0 +1,174 @@
+#!/usr/bin/env python3
+"""k right-hand sides: k single-vector calls against one multi-vector call, same handle, same process, alternating.
+
+    python tools/bench_multi_rhs.py [nv] [--k 1,2,4,8] [--rounds 5] [--reps 30] [--pcg-reps 30] [--out FILE] [--commit ID]
+
+Builds the cfg-2 hierarchy as tools/ab_cycle.py does (fem.poisson_fast((nv,)*3), nv = 215, Jacobi) and times, with device vectors and
+graph replay on one stream, per k and per round
+  (a) k calls of amgx_apply on k vector pairs            (b) one amgx_apply_multi of width k (interleaved, used in place)
+  (b') the same with column-major arguments (one transposition in, one out)
+and the same for amgx_pcg x k against amgx_pcg_multi (tol 1e-8).  Cross-run numbers differ by several per cent between boxes and
+processes, so the only yardstick is (a) of the same round.  Before any time is printed every column of (b) is compared
+with (a): 1e-12 relative for the cycle, 1e-8 for the PCG solutions.  Needs a GPU."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _commit():
+    try:
+        return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
+    except Exception:
+        return "unknown"
+
+
+def _stats(ts):
+    return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts), "rounds_ms": ts}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("nv", nargs="?", type=int, default=215)
+    ap.add_argument("--k", default="1,2,4,8")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--pcg-reps", type=int, default=30)
+    ap.add_argument("--no-pcg", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06", "multi_rhs.json"))
+    ap.add_argument("--commit", default=None)
+    ap.add_argument("--cycle-only-k", type=int, default=0, help="run nothing but REPS multi-vector cycles of this width (for a kernel trace)")
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("bench_multi_rhs: needs a GPU")
+    from ngsamg_amd import fem, Matrix
+    from ngsamg_amd.hierarchy import Hierarchy
+    from ngsamg_amd.device import DeviceAMGMatrix
+    from ngsamg_amd.krylov import NativeCGSolver
+    nv = args.nv
+    ks = [int(v) for v in args.k.split(",")]
+    p = fem.poisson_fast((nv, nv, nv))
+    H = Hierarchy(Matrix(p.n, p.n, 1, 1, p.rowptr, p.col, p.val), p.free, p.coords, dim=3, energy=0, max_coarse_size=50)
+    free0, _ = torch.cuda.mem_get_info()
+    dev = DeviceAMGMatrix(H, sm_type="jacobi", device=0)
+    torch.cuda.synchronize()
+    free1, _ = torch.cuda.mem_get_info()
+    n = p.n
+    rng = np.random.default_rng(0)
+    stream = torch.cuda.Stream()                               # (the legacy default stream cannot be captured into a graph)
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(fn, reps):
+        with torch.cuda.stream(stream):
+            ev0.record(stream)
+            for _ in range(reps):
+                fn()
+            ev1.record(stream)
+        ev1.synchronize()
+        return ev0.elapsed_time(ev1) / reps
+
+    if args.cycle_only_k:
+        k = args.cycle_only_k
+        Bi = torch.from_numpy(rng.standard_normal((n, k)) * p.free[:, None]).cuda()
+        Xi = torch.empty_like(Bi)
+        torch.cuda.synchronize()
+        print("ms per multi cycle:", timed(lambda: dev.MultMulti(Bi, Xi, interleaved=True), args.reps))
+        return
+
+    out = {"commit": args.commit or _commit(), "nv": nv, "n": int(n), "levels": H.n_levels, "cycle_info": dev.cycle_info(),
+           "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps, "pcg_reps": args.pcg_reps,
+           "handle_bytes": int(free0 - free1), "k": {}}
+    for k in ks:
+        info = dev.multi_info(k)
+        B = rng.standard_normal((k, n)) * p.free
+        bs = [torch.from_numpy(np.ascontiguousarray(B[j])).cuda() for j in range(k)]
+        xs = [torch.empty_like(b) for b in bs]
+        Bi = torch.from_numpy(np.ascontiguousarray(B.T)).cuda()
+        Xi = torch.full_like(Bi, float("nan"))
+        Bc = torch.from_numpy(B).cuda()
+        Xc = torch.full_like(Bc, float("nan"))
+        torch.cuda.synchronize()
+
+        def a():
+            for j in range(k):
+                dev.Mult(bs[j], xs[j])
+
+        def b():
+            dev.MultMulti(Bi, Xi, interleaved=True)
+
+        def c():
+            dev.MultMulti(Bc, Xc)
+
+        m0, _ = torch.cuda.mem_get_info()
+        for fn in (a, b, c):                                    # warm-up: captures the graphs, allocates the work space
+            timed(fn, 3)
+        torch.cuda.synchronize()
+        m1, _ = torch.cuda.mem_get_info()
+        # (b) equals (a) column by column before any time counts
+        Xa = torch.stack(xs)
+        worst = 0.0
+        for j in range(k):
+            for got in (Xi[:, j], Xc[j]):
+                worst = max(worst, float((got - Xa[j]).norm() / Xa[j].norm()))
+        if not worst < 1e-12:
+            sys.exit(f"bench_multi_rhs: k = {k}: multi-vector cycle deviates from the single-vector one by {worst:.3e}")
+        ta, tb, tc = [], [], []
+        for _ in range(args.rounds):                            # alternating blocks
+            ta.append(timed(a, args.reps))
+            tb.append(timed(b, args.reps))
+            tc.append(timed(c, args.reps))
+        rec = {"multi_info": info, "work_bytes_allocated": int(m0 - m1), "max_rel_diff": worst,
+               "cycle": {"single_x_k": _stats(ta), "multi_interleaved": _stats(tb), "multi_colmajor": _stats(tc),
+                         "ratio_rounds": [x / y for x, y in zip(ta, tb)], "ratio_median": statistics.median(ta) / statistics.median(tb),
+                         "ratio_colmajor_median": statistics.median(ta) / statistics.median(tc),
+                         "multi_wins_every_round": all(x > y for x, y in zip(ta, tb))}}
+        if not args.no_pcg:
+            cg = NativeCGSolver(dev, dev, tol=1e-8, maxsteps=100)
+            its_a = []
+
+            def pa():
+                its_a.clear()
+                for j in range(k):
+                    xs[j].zero_()
+                    cg.Solve(bs[j], xs[j])
+                    its_a.append(cg.iterations)
+
+            def pb():
+                Xi.zero_()
+                cg.SolveMulti(Bi, Xi, interleaved=True)
+
+            with torch.cuda.stream(stream):
+                pa()
+                pb()
+            torch.cuda.synchronize()
+            its_b = list(cg.iterations)
+            wp = max(float((Xi[:, j] - xs[j]).norm() / xs[j].norm()) for j in range(k))
+            if not wp < 1e-8 or any(abs(x - y) > 1 for x, y in zip(its_a, its_b)):
+                sys.exit(f"bench_multi_rhs: k = {k}: PCG differs: solutions {wp:.3e}, iterations {its_a} vs {its_b}")
+            pta, ptb = [], []
+            for _ in range(args.rounds):
+                pta.append(timed(pa, args.pcg_reps))
+                ptb.append(timed(pb, args.pcg_reps))
+            rec["pcg"] = {"iterations_single": list(its_a), "iterations_multi": its_b, "max_rel_diff": wp, "single_x_k": _stats(pta),
+                          "multi_interleaved": _stats(ptb), "ratio_rounds": [x / y for x, y in zip(pta, ptb)],
+                          "ratio_median": statistics.median(pta) / statistics.median(ptb),
+                          "multi_wins_every_round": all(x > y for x, y in zip(pta, ptb))}
+        out["k"][str(k)] = rec
+        print(f"k = {k}: cycle (a) {statistics.median(ta):.3f} ms  (b) {statistics.median(tb):.3f} ms  (b') {statistics.median(tc):.3f} ms  "
+              f"ratio (a)/(b) {rec['cycle']['ratio_median']:.2f}" + (f"   pcg ratio {rec['pcg']['ratio_median']:.2f}" if "pcg" in rec else ""), flush=True)
+        del bs, xs, Bi, Xi, Bc, Xc
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps({"out": args.out, "ratios": {k: v["cycle"]["ratio_median"] for k, v in out["k"].items()}}))
+
+
+if __name__ == "__main__":
+    main()
