@@ -286,8 +286,13 @@ int amgx_gss4_mult_add(amgx_gss4 g, double s, const double* b, double* x, int fl
  * preconditioner = the handle's cycle (use_precond = 0: none).  x holds the initial guess and receives the solution.
  *   amgx_pcg  : err_k = sqrt(|<C r_k, r_k>|), stops at err_k <= tol * err_0 (CGSolver's criterion)
  *   amgx_gmres: restarted GMRES(restart), left-preconditioned, err_k = |C r_k|
- * errs (optional, maxit + 1 entries) receives err_0 ... err_iters; *iters the iteration count.  BLAS-1 work runs in
- * hand-written kernels with deterministic reductions; the host reads one scalar per iteration. */
+ * errs (optional, maxit + 1 entries) receives err_0 ... err_iters; *iters (optional) the iteration count.  BLAS-1 work runs in
+ * hand-written kernels with deterministic reductions; the host reads one scalar per iteration.
+ * Edges: err_0 == 0 returns at once with 0 iterations.  amgx_pcg tests its criterion after an iteration, amgx_gmres before a restart
+ * cycle as well: tol >= 1 gives 1 PCG iteration and 0 GMRES iterations.  maxit = 0 leaves x as it is; amgx_pcg then still writes
+ * errs[0] = err_0, amgx_gmres (which computes err_0 inside its first cycle) does not touch errs.  maxit counts iterations over all
+ * restart cycles: a cycle cut short by maxit still updates x.  1 <= restart <= 40; a larger value is an error ("restart lengths
+ * above 40 are not supported"), restart > maxit is allowed.  AMGX_PCG_SINGLE_REDUCTION with use_precond = 0 runs the classical form. */
 int amgx_pcg(amgx_handle h, const double* b, double* x, double tol, int maxit, int use_precond, int flags, double* errs, int32_t* iters);
 int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit, int restart, int use_precond, int flags, double* errs,
                int32_t* iters);

@@ -590,6 +590,91 @@ def test_distributed_pcg_history_equals_serial_oracle(R, box, dmin, sm):
     assert errs2[0] <= 1e-7 * errs[0]
 
 
+@pytest.mark.parametrize("R,box,dmin,sm", [(2, (14, 12, 12), 100, "jacobi"), (4, (10, 10, 10), 50, "jacobi"), (3, (9, 12, 12), 80, "gs"), (2, (14, 12, 12), 100, "hgs")])
+def test_distributed_solvers_from_initial_guess_equal_serial_oracle(R, box, dmin, sm):
+    """xs hold the initial guess: amgx_dist_pcg, its single-reduction form and amgx_dist_gmres started from x0 = 10 * standard_normal
+    on the free dofs of every rank, against the serial oracle's pcg / gmres from the concatenated guess (tolerances of the tests
+    around this one)"""
+    import torch
+    from ngsamg_amd import dist as D
+    from oracle.pyoracle import Oracle
+    from tests.dist_oracle import oracle_bgs, oracle_sm_types
+    pg = (R, 1, 1)
+    states = [D.assemble_poisson_owned(r, pg, box) for r in range(R)]
+    amg = D.DistributedAMG(D.LoopbackComm(R), states, dim=3, dist_min_rows=dmin, device=0, max_coarse_size=10, sm_type=sm,
+                           **({"hgs_block_rows": 256} if sm == "hgs" else {}))
+    rng = np.random.default_rng(11)
+    sts = amg.dist_levels[0]
+    bh = [rng.standard_normal(s.n) * s.free for s in sts]
+    x0h = [10.0 * rng.standard_normal(s.n) * s.free for s in sts]
+    bs = [torch.from_numpy(v).cuda() for v in bh]
+    glv = amg.global_levels()
+    orc = Oracle(glv, sm_type=oracle_sm_types(amg), bgs=oracle_bgs(amg, glv))
+    bg, x0g = np.concatenate(bh), np.concatenate(x0h)
+    cold = orc.pcg(bg, tol=1e-8, maxit=0)[2][0]
+
+    def start():
+        return [torch.from_numpy(v.copy()).cuda() for v in x0h]
+
+    def result(xs):
+        torch.cuda.synchronize()
+        return np.concatenate([x.cpu().numpy() for x in xs])
+
+    xo, ito, erro = orc.pcg(bg, x0=x0g, tol=1e-8, maxit=100)
+    assert abs(erro[0] - cold) > 0.1 * cold                  # the guess moves err_0 far from the cold start's
+    xs = start()
+    it, errs = amg.pcg(bs, xs, tol=1e-8, maxsteps=100)
+    got = result(xs)
+    print(f"R={R} {sm} pcg: it {it} / {ito}, history {np.max(np.abs(errs - erro[:it + 1])) / erro[0]:.2e} err_0")
+    assert it == ito and it < 60
+    assert np.all(np.abs(errs - erro) <= 1e-6 * erro[0]) and np.allclose(errs[:5], erro[:5], rtol=1e-9)
+    assert np.linalg.norm(got - xo) <= 1e-8 * np.linalg.norm(xo)
+
+    xs = start()
+    it, errs = amg.pcg(bs, xs, tol=1e-8, maxsteps=100, single_reduction=True)
+    got = result(xs)
+    assert abs(it - ito) <= 1
+    k = min(it, ito)
+    assert np.allclose(errs[:k], erro[:k], rtol=1e-6)
+    assert np.linalg.norm(got - xo) <= 1e-7 * np.linalg.norm(xo)
+
+    xo, ito, erro = orc.gmres(bg, x0=x0g, tol=1e-9, maxit=150, restart=12)
+    xs = start()
+    it, errs = amg.gmres(bs, xs, tol=1e-9, maxsteps=150, restart=12)
+    got = result(xs)
+    print(f"R={R} {sm} gmres(12): it {it} / {ito}")
+    assert it == ito
+    assert errs.shape == erro.shape and np.all(np.abs(errs - erro) <= 1e-6 * erro[0])
+    assert np.linalg.norm(got - xo) <= 1e-7 * np.linalg.norm(xo)
+
+
+@pytest.mark.parametrize("R,box,dmin", [(2, (14, 12, 12), 100), (4, (10, 10, 10), 50), (3, (9, 12, 12), 80)])
+def test_distributed_first_history_entry_is_the_exact_global_norm(R, box, dmin):
+    """amg.pcg(use_pre=False) from x = 0: err_0 = sqrt(<b, b>) summed over the ranks.  Integer entries make every partial sum exact,
+    so the value is independent of the order of the additions: bitwise the square root of the global integer sum"""
+    import math
+    import torch
+    from ngsamg_amd import dist as D
+    pg = (R, 1, 1)
+    states = [D.assemble_poisson_owned(r, pg, box) for r in range(R)]
+    amg = D.DistributedAMG(D.LoopbackComm(R), states, dim=3, dist_min_rows=dmin, device=0, max_coarse_size=10, sm_type="jacobi")
+    sts = amg.dist_levels[0]
+    rng = np.random.default_rng(13)
+    cases = [[np.ones(s.n) for s in sts], [rng.integers(-8, 9, size=s.n).astype(np.float64) for s in sts]]
+    for r in (0, R - 1):                                     # one entry on one rank: its first and its last row
+        for row in (0, sts[r].n - 1):
+            v = [np.zeros(s.n) for s in sts]
+            v[r][row] = 3.0
+            cases.append(v)
+    for bh in cases:
+        total = sum(int(t) * int(t) for v in bh for t in v.astype(np.int64).tolist())
+        xs = [torch.zeros(s.n, dtype=torch.float64, device="cuda") for s in sts]
+        it, errs = amg.pcg([torch.from_numpy(v).cuda() for v in bh], xs, tol=1e-8, maxsteps=0, use_pre=False)
+        torch.cuda.synchronize()
+        assert it == 0 and errs.tolist() == [math.sqrt(float(total))], (errs, total)
+        assert not any(x.any().item() for x in xs)
+
+
 @pytest.mark.parametrize("pg,gshape,dmin,sm", [((3, 1, 1), (23, 14, 13), 100, "jacobi"), ((8, 1, 1), (43, 9, 10), 40, "jacobi"), ((5, 1, 1), (27, 12, 11), 60, "hgs")])
 def test_strong_split_device_matches_serial_oracle(pg, gshape, dmin, sm):
     """bench.py --gpus N in miniature: ONE global grid cut into balanced, unequal slabs (virtual ranks on this GPU), two
