@@ -39,8 +39,15 @@ typedef struct amgx_matrix {
 enum {
   AMGX_SM_JACOBI = 0,         /* JacobiSmoother<TM>, base_smoother.cpp:61-114         */
   AMGX_SM_GS = 1,             /* Gauss-Seidel (GSS3, gssmoother.cpp:196-398) executed as multicolour GS */
-  AMGX_SM_BGS = 2             /* block Gauss-Seidel over aggregate blocks (BSmoother, block_gssmoother.cpp:17-498), */
+  AMGX_SM_BGS = 2,            /* block Gauss-Seidel over aggregate blocks (BSmoother, block_gssmoother.cpp:17-498), */
                               /*   blocks of one colour relaxed in parallel (the reference's sm_shm sweep does too) */
+  AMGX_SM_CHEBY = 3           /* Chebyshev polynomial smoother in the (block-)Jacobi-preconditioned operator Dinv A (no reference */
+                              /*   counterpart; an own option).  Degree k on [lmin, lmax], lmin = lmax / ratio:                    */
+                              /*     theta = (lmax+lmin)/2, delta = (lmax-lmin)/2, sigma = theta/delta, rho_1 = 1/sigma            */
+                              /*     step 1:        d = (1/theta) Dinv r,  x += d                                                  */
+                              /*     step j = 2..k: rho_j = 1/(2 sigma - rho_{j-1}),  d = rho_j rho_{j-1} d + (2 rho_j/delta) Dinv (b - A x),  x += d */
+                              /*   r of step 1 follows the flag contract of amgx_smooth (b from zero, res when updated, else b - A x); */
+                              /*   Smooth == SmoothBack; sm_steps / sm_symm compose as for every smoother.  Not on rank-partitioned levels. */
 };
 enum { AMGX_CYCLE_V = 0, AMGX_CYCLE_W = 1, AMGX_CYCLE_BS = 2 };   /* ngs_amg_mg_cycle, amg_matrix.hpp:37-43 */
 enum { AMGX_CLEV_NONE = 0, AMGX_CLEV_INV = 1 };                   /* ngs_amg_clev,     amg_matrix.cpp:217-247 */
@@ -102,6 +109,11 @@ typedef struct amgx_level_desc {
                               /*   parallel order -- instead of the hybrid form's frozen couplings between blocks; `dinv` is then     */
                               /*   the plain (pseudo-)inverse of the diagonal blocks (amgh_calc_dinv), no l1 modification.            */
   int32_t gs_n_block_colors;  /*   number of block colours (0: none, hybrid form)                                                    */
+  /* AMGX_SM_CHEBY only; zero-initialised = defaults: */
+  int32_t cheb_degree;        /*   1 .. 8 steps per smooth (0: 2)                                                                    */
+  double cheb_lambda_max;     /*   upper end of the interval (0: 1.1 x a 30-step power-iteration estimate of lambda_max(Dinv A),     */
+                              /*   computed by amgx_create on the device; amgx_smoother_info reports it)                             */
+  double cheb_ratio;          /*   lmin = lmax / ratio, ratio > 1 (0: 10)                                                            */
 } amgx_level_desc;
 
 typedef struct amgx_hierarchy_desc {
@@ -188,6 +200,9 @@ int amgx_level_info(amgx_handle h, int level, int64_t* n, int32_t* bs, int64_t* 
  * as one dense GEMV of dense_n x dense_n doubles (same operator, summation order differs: rounding-level differences).
  * Environment of amgx_create: AMGX_NO_DENSE_TAIL=1 disables, AMGX_DENSE_MAX=<n> caps dense_n (default 8192). */
 int amgx_cycle_info(amgx_handle h, int32_t* tail_level, int32_t* dense_level, int64_t* dense_n);
+/* the smoother of a level: type (AMGX_SM_*) and, for AMGX_SM_CHEBY, degree, interval and whether amgx_create estimated
+ * lambda_max itself (degree = 0, interval = 0 for the other types).  Any output pointer may be NULL. */
+int amgx_smoother_info(amgx_handle h, int level, int32_t* sm_type, int32_t* degree, double* lambda_max, double* lambda_min, int32_t* estimated);
 /* device-format report per level matrix: which = 0 A, 1 P, 2 PT, 3 A' = A*omega*Dinv (pre-smoothing image),
  * 4 Q = (I - omega*Dinv*A) P (post-smoothing folded into the prolongation), 5 the "local window" image of A' that the fused down
  * kernel of a long-row level reads (chunk-local 16-bit columns, gathered vector staged in LDS), 6 the local-window image of Q
@@ -204,7 +219,8 @@ int amgx_matrix_info(amgx_handle h, int level, int which, int32_t* fmt, int64_t*
 int amgx_matrix_stream_bytes(amgx_handle h, int level, int which, int64_t* bytes);
 
 /* read-only report of the paths amgx_create chose for one level (changes nothing).  Fills out[0 .. min(n_out, 19)):
- *    0 fused Jacobi down kernel: 0 none, 1 sliced-ELL, 2 sliced-ELL with row windows, 3 local-window sliced-ELL, 4 diagonal image
+ *    0 fused Jacobi down kernel: 0 none, 1 sliced-ELL, 2 sliced-ELL with row windows, 3 local-window sliced-ELL, 4 diagonal image;
+ *      5: the fused residual + restriction kernel of a Chebyshev level (sliced-ELL image of A; 1 .. 3 then describe it)
  *    1 its workgroup size (rows per chunk x lanes)      2 its lanes per row (0: none)
  *    3 entries of P per thread of its chunk-local restriction (0: none)     4 compact chunks (1: chunks of listed slices)
  *    5 most slots (distinct coarse columns) in one chunk                    6 most entries of P in one chunk
@@ -246,7 +262,9 @@ int amgx_level_paths(amgx_handle h, int level, int64_t* out, int n_out);
  *   op = 8: the same kernel timed INSIDE the cycle: `reps` whole cycles are launched directly (no graph) with HIP events
  *           around that one kernel; the average is what rocprofv3 --kernel-trace reports for it (roofline.achieved)
  *   op = 9: like 8 for the backward block-hybrid Gauss-Seidel sweep of the level (gsb_sweep_kernel, the dominant kernel
- *           of a Gauss-Seidel cycle); error if the level has no such sweep */
+ *           of a Gauss-Seidel cycle); error if the level has no such sweep
+ *   op = 10: one fused Chebyshev step  x' = x + d', d' = c1 d + c2 dinv*(b - A_level x)  (a middle step: d read and stored);
+ *           error if the level has no Chebyshev smoother */
 int amgx_time_op(amgx_handle h, int level, int op, int reps, double* avg_ms);
 
 /* ---- GSS4: Gauss-Seidel on a subset of the rows, on a compressed device copy ------------------------------------------
@@ -312,7 +330,7 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  * A handle whose smoothed levels are all scalar (1x1), plain Jacobi (sm_steps = 1, no sm_symm), square, and whose cycle is V runs
  * FUSED: the literal cycle (x = w Dinv b, r = b - A x, b_c = P^T r, ..., t = x + P x_c, x = t + w Dinv (b - A t)) on A, P, P^T with
  * every matrix entry read once for 2 or 4 interleaved vectors; any other k is cut greedily into groups of those widths (8 = 4 + 4:
- * a width-8 kernel measured slower per column) plus at most one single column, which takes the single-vector path.  Every other handle (Gauss-Seidel in any form, block levels, W / BS
+ * a width-8 kernel measured slower per column) plus at most one single column, which takes the single-vector path.  Every other handle (Gauss-Seidel in any form, Chebyshev, block levels, W / BS
  * cycles, ProxySmoother) answers the same calls through a column loop over the single-vector path -- all or nothing per handle.
  *   amgx_multi_info  : fused = 1 / 0 as above; the groups a call with k columns runs as (group_width: AMGX_MULTI_MAX entries,
  *                      0 beyond n_groups; all 1 when fused = 0); work_bytes = device memory of the multi-vector work space such a

@@ -354,12 +354,13 @@ class _AMGPreconditioner:
         hier = Hierarchy(A, self._freedofs, self._coords, dim=dim, energy=self._energy, **opts)
         sm_type = str(f.get("sm_type", "gs")).lower()                     # amg_pc.hpp:63
         spec = f.get("sm_type_spec")
-        if sm_type not in ("gs", "jacobi", "bgs"):
+        # "cheby": Chebyshev polynomial smoother in the (block-)Jacobi-preconditioned operator -- an own option, the reference has none
+        if sm_type not in ("gs", "jacobi", "bgs", "cheby"):
             sm_type = "gs"                                                # dyn_block_gs ... fall back to gs (amg_pc_vertex_impl.hpp:587-593)
         types = [sm_type] * hier.n_levels
         if spec:
             for i, t in enumerate(spec[: hier.n_levels]):
-                types[i] = t if t in ("gs", "jacobi", "bgs") else "gs"
+                types[i] = t if t in ("gs", "jacobi", "bgs", "cheby") else "gs"
         # Gauss-Seidel runs in the block-hybrid form by default (one launch per sweep: workgroups sweep blocks of consecutive
         # rows like the ranks of the reference's HybridGSSmoother, gssmoother.cpp:709-861); ngs_amg_gs_hybrid=False selects the
         # multicolour form (exact Gauss-Seidel in colour order, one launch per colour).  Block levels stay multicolour.
@@ -378,7 +379,8 @@ class _AMGPreconditioner:
         dev = DeviceAMGMatrix(hier, sm_type=types, omega=float(f.get("sm_omega", 0.9)),
                               sm_steps=steps, sm_symm=symm,
                               mg_cycle=str(f.get("mg_cycle", "V")).upper(), clev="inv" if clev == "inv" else "none",
-                              device=self._device, use_graph=bool(f.get("use_graph", True)))
+                              device=self._device, use_graph=bool(f.get("use_graph", True)),
+                              cheb_degree=int(f.get("cheb_degree", 2)), cheb_ratio=float(f.get("cheb_ratio", 10)))
         self._amg = AMGMatrix(hier, dev)
         if f.get("do_test", False):
             self.Test()
@@ -553,15 +555,23 @@ class _SingleLevel:
 
 
 class _StandaloneSmoother(BaseSmoother):
-    def __init__(self, mat, freedofs, sm_type, pinv=False, nsteps=1, symm=False, omega=0.9, device=0):
+    def __init__(self, mat, freedofs, sm_type, pinv=False, nsteps=1, symm=False, omega=0.9, device=0, **cheb):
         A = _as_matrix(mat, 1)
         hier = _SingleLevel(A, freedofs, pinv)
-        dev = DeviceAMGMatrix(hier, sm_type=sm_type, omega=omega, sm_steps=nsteps, sm_symm=symm, clev="none", device=device)
+        dev = DeviceAMGMatrix(hier, sm_type=sm_type, omega=omega, sm_steps=nsteps, sm_symm=symm, clev="none", device=device, **cheb)
         super().__init__(AMGMatrix(hier, dev), 0)
 
 
 def CreateJacobiSmoother(mat, freedofs=None, omega=0.9, device=0):
     return _StandaloneSmoother(mat, freedofs, "jacobi", omega=omega, device=device)
+
+
+def CreateChebyshevSmoother(mat, freedofs=None, degree=2, ratio=10, lambda_max=None, pinv=False, device=0):
+    """stand-alone Chebyshev polynomial smoother of the given degree in the Jacobi-preconditioned operator on the interval
+    [lambda_max / ratio, lambda_max] (no reference counterpart); lambda_max=None: 1.1 x a power-iteration estimate on the device.
+    Smooth == SmoothBack."""
+    return _StandaloneSmoother(mat, freedofs, "cheby", pinv=pinv, device=device, cheb_degree=degree, cheb_ratio=ratio,
+                               cheb_lambda_max=lambda_max)
 
 
 def CreateHybridGSS(mat, freedofs=None, pinv=False, NG_MPI_overlap=True, NG_MPI_thread=False, symm=False,

@@ -202,7 +202,8 @@ class amgx_level_desc(C.Structure):
                 ("bgs_n_blocks", C.c_int32), ("bgs_block_ptr", c_i32p), ("bgs_block_rows", c_i32p),
                 ("bgs_dinv_ptr", c_i64p), ("bgs_dinv", c_f64p), ("bgs_color", c_i32p), ("bgs_n_colors", C.c_int32),
                 ("Q", amgx_matrix), ("gs_block_rows", C.c_int32), ("gs_block_ids", c_i32p),
-                ("gs_block_color", c_i32p), ("gs_n_block_colors", C.c_int32)]
+                ("gs_block_color", c_i32p), ("gs_n_block_colors", C.c_int32),
+                ("cheb_degree", C.c_int32), ("cheb_lambda_max", C.c_double), ("cheb_ratio", C.c_double)]
 
 
 class amgx_hierarchy_desc(C.Structure):
@@ -227,7 +228,7 @@ class amgx_gss4_desc(C.Structure):
                 ("n_colors", C.c_int32), ("device", C.c_int32)]
 
 
-AMGX_SM_JACOBI, AMGX_SM_GS, AMGX_SM_BGS = 0, 1, 2
+AMGX_SM_JACOBI, AMGX_SM_GS, AMGX_SM_BGS, AMGX_SM_CHEBY = 0, 1, 2, 3
 AMGX_COMM_RCCL, AMGX_COMM_LOCAL = 0, 1
 AMGX_UNIQUE_ID_BYTES = 128
 AMGX_CYCLE = {"V": 0, "W": 1, "BS": 2}
@@ -251,6 +252,7 @@ AMGX_SYMBOLS = [
     "amgx_gss4_info", "amgx_gss4_smooth", "amgx_gss4_smooth_res", "amgx_gss4_mult_add",
     "amgx_device_count", "amgx_spgemm", "amgx_galerkin", "amgx_csr_result_fetch",
     "amgx_apply_multi", "amgx_matvec_multi", "amgx_pcg_multi", "amgx_multi_info",
+    "amgx_smoother_info",
 ]
 
 AMGH_SYMBOLS = [
@@ -296,6 +298,7 @@ def hip():
     lib.amgx_matrix_info.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_i64p, c_i32p]
     lib.amgx_matrix_stream_bytes.argtypes = [vp, C.c_int, C.c_int, c_i64p]
     lib.amgx_level_paths.argtypes = [vp, C.c_int, c_i64p, C.c_int]
+    lib.amgx_smoother_info.argtypes = [vp, C.c_int, c_i32p, c_i32p, c_f64p, c_f64p, c_i32p]
     lib.amgx_time_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_f64p]
     lib.amgx_pcg.argtypes = [vp, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int, c_f64p, c_i32p]
     lib.amgx_gmres.argtypes = [vp, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, c_f64p, c_i32p]

@@ -330,6 +330,24 @@ struct DevLevel {
   int64_t len() const { return n * bs; }
   int64_t ext_len() const { return ncols * bs; }
   DevBuf<double> x, rhs, res, tmp;      // x_level / rhs_level / res_level (amg_matrix.cpp:19-26) + ping-pong buffer
+  // AMGX_SM_CHEBY: degree k, interval [lmin, lmax] of Dinv A, coefficients of the recurrence
+  //   step 1: d = c0 Dinv r;  step j >= 2: d = c1[j] d + c2[j] Dinv (b - A x);  x += d      (fp64, fixed at create time)
+  int cheb_degree = 0, cheb_estimated = 0;
+  double cheb_ratio = 10.0, cheb_lmax = 0.0, cheb_lmin = 0.0, cheb_c0 = 0.0;
+  double cheb_c1[9] = {}, cheb_c2[9] = {};
+  DevBuf<double> d;                     // the update vector of the recurrence
+  void cheb_set_interval(double lmax) {
+    cheb_lmax = lmax; cheb_lmin = lmax / cheb_ratio;
+    const double theta = 0.5 * (cheb_lmax + cheb_lmin), delta = 0.5 * (cheb_lmax - cheb_lmin), sigma = theta / delta;
+    cheb_c0 = 1.0 / theta;
+    double rho = 1.0 / sigma;
+    for (int j = 2; j <= 8; ++j) {
+      const double rn = 1.0 / (2.0 * sigma - rho);
+      cheb_c1[j] = rn * rho;
+      cheb_c2[j] = 2.0 * rn / delta;
+      rho = rn;
+    }
+  }
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -1372,7 +1390,7 @@ struct Handle {
       else hipLaunchKernelGGL((bsell_spmv_kernel<2, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(), x, y, ep);
     } else if (sp.part == PART_INT) {
       return;                                   // the CSR block formats are not split: everything runs in the boundary part
-    } else if (M.br >= 2 && M.bc >= 2 && (EP != EP_JAC || M.br == M.bc) && (M.br == M.bc || M.nnz >= 6 * M.n_rows)) {
+    } else if (M.br >= 2 && M.bc >= 2 && ((EP != EP_JAC && EP != EP_CHEB) || M.br == M.bc) && (M.br == M.bc || M.nnz >= 6 * M.n_rows)) {
       // (short rectangular rows, i.e. prolongations with <= 4 blocks per row, stay with the lane-per-block kernel: measured)
       // row-per-lane block CSR kernel; W lane groups per block row chosen from the average row length
       const double avg = M.n_rows ? (double)M.nnz / (double)M.n_rows : 0.0;
@@ -1383,7 +1401,7 @@ struct Handle {
 #define LAUNCH_RL(BR, BC, WW) hipLaunchKernelGGL((bcsr_rowlane_kernel<BR, BC, WW, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep)
 #define LAUNCH_RLW(BR, BC) { if (W == 4) LAUNCH_RL(BR, BC, 4); else if (W == 2) LAUNCH_RL(BR, BC, 2); else LAUNCH_RL(BR, BC, 1); }
       const int key = M.br * 10 + M.bc;
-      if constexpr (EP == EP_JAC) {
+      if constexpr (EP == EP_JAC || EP == EP_CHEB) {
         switch (key) {
           case 22: LAUNCH_RLW(2, 2); break;
           case 33: LAUNCH_RLW(3, 3); break;
@@ -1442,6 +1460,61 @@ struct Handle {
   void jacobi_fused(const DevLevel& L, const double* xin, const double* b, double* xout, const Span sp = Span()) {
     if (xin == xout) throw Err("jacobi_fused: in-place update is not allowed");
     spmv_ep<EP_JAC>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, L.omega, nullptr, ep_nt}, sp);
+  }
+
+  // ---- Chebyshev smoother (AMGX_SM_CHEBY) ----
+  // xout = (xin ? xin : 0) + c0 * Dinv * v, dout (optional) = the update
+  void cheb_first(const DevLevel& L, const double* v, const double* xin, double* xout, double* dout, double c0) {
+    if (L.n == 0) return;
+    const int grid = grid_for(L.n);
+#define LAUNCH_CF(BS) hipLaunchKernelGGL((cheb_first_kernel<BS>), dim3(grid), dim3(BLOCK), 0, stream, L.n, L.dinv.p, v, xin, xout, dout, c0)
+    switch (L.bs) {
+      case 1: LAUNCH_CF(1); break;
+      case 2: LAUNCH_CF(2); break;
+      case 3: LAUNCH_CF(3); break;
+      case 6: LAUNCH_CF(6); break;
+      default: throw Err("unsupported block size " + std::to_string(L.bs));
+    }
+#undef LAUNCH_CF
+    HIPCHK(hipGetLastError());
+  }
+  // one fused step: xout = xin + d_new, d_new = c1 * d_old + c2 * Dinv * (b - A xin); d_old == nullptr: xin; d_new == nullptr: not stored
+  void cheb_step(const DevLevel& L, const double* xin, const double* b, double* xout, double c1, double c2, const double* d_old, double* d_new) {
+    if (xin == xout) throw Err("cheb_step: in-place update is not allowed");
+    spmv_ep<EP_CHEB>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, c2, d_new, ep_nt, d_old, c1});
+  }
+  // One Chebyshev smooth of degree k with the flag contract of base_smooth.  The iterate lives in `src` (x itself or L.tmp, ignored
+  // with x_zero) and ends in x; the fused steps are out of place and ping-pong between x and L.tmp, so a caller that can choose
+  // (post_smooth) puts the iterate where an even number of passes is left; otherwise one copy moves the result.
+  int cheb_passes(const DevLevel& L, bool res_updated, bool x_zero) const { return L.cheb_degree - 1 + ((!res_updated && !x_zero) ? 1 : 0); }
+  void cheb_smooth(DevLevel& L, const double* src, double* x, const double* b, double* res, bool res_updated, bool update_res, bool x_zero) {
+    const int k = L.cheb_degree;
+    if (k < 1 || !L.d.p) throw Err("Chebyshev smoother: the level has no coefficients");
+    if (L.ncols != L.n) throw Err("Chebyshev smoother: rank-partitioned levels are not supported");
+    double* const tmp = L.tmp.p;
+    if (!x_zero && src != x && src != tmp) throw Err("Chebyshev smoother: the iterate must live in x or in the level's ping-pong buffer");
+    const double* cur;
+    const double* dcur = L.d.p;           // where d of the previous step lives (nullptr: in the iterate itself)
+    int j = 2;                            // next step of the recurrence
+    if (res_updated || x_zero) {
+      double* t0 = ((k - 1) & 1) ? tmp : x;
+      // (from zero: d == x afterwards, nothing stored; otherwise d is stored when another step follows)
+      cheb_first(L, (res_updated ? res : b), x_zero ? nullptr : src, t0, (!x_zero && k > 1) ? L.d.p : nullptr, L.cheb_c0);
+      if (x_zero) dcur = nullptr;
+      cur = t0;
+    } else {
+      double* t0 = src == x ? tmp : x;
+      cheb_step(L, src, b, t0, 0.0, L.cheb_c0, nullptr, k > 1 ? L.d.p : nullptr);
+      cur = t0;
+    }
+    for (; j <= k; ++j) {
+      double* nxt = cur == x ? tmp : x;
+      cheb_step(L, cur, b, nxt, L.cheb_c1[j], L.cheb_c2[j], dcur, j < k ? L.d.p : nullptr);
+      dcur = L.d.p;
+      cur = nxt;
+    }
+    if (cur != x) copy(x, cur, L.len());
+    if (update_res) residual(L.A, x, b, res);
   }
 
   void zero(double* v, int64_t n) {
@@ -1679,6 +1752,9 @@ struct Handle {
         diag_apply(L, res, x, true);
       }
       if (update_res) residual(L.A, x, b, res);
+    } else if (L.sm_type == AMGX_SM_CHEBY) {
+      // symmetric polynomial smoother: Smooth and SmoothBack are the same operation
+      cheb_smooth(L, x, x, b, res, res_updated, update_res, x_zero);
     } else if (L.sm_type == AMGX_SM_BGS) {
       // BSmoother::Smooth / SmoothBack (block_gssmoother.cpp:434-498): like GSS3 the reference updates the residual by
       // row-transpose scatters when asked for it; here: gather (RHS) form + one residual SpMV, same x and res
@@ -1751,6 +1827,8 @@ struct Handle {
         residual(L.A, x, b, r);              // r = b - A x
         if (fold) diag_apply(L, r, x, true); // z = x + omega * Dinv * r  (folded post-smoothing, see fold_prolongation)
       }
+    } else if (plain(L) && L.sm_type == AMGX_SM_CHEBY) {
+      cheb_smooth(L, x, x, b, r, false, true, true);     // from zero: step 1 reads b, no SpMV
     } else if (plain(L) && L.sm_type == AMGX_SM_GS && L.bgsb.on()) {
       // forward block-hybrid sweep from x = 0 (nothing outside the workgroup's rows is read), then the residual; with the
       // split copies A is read once in total: r = rest * x (see DevBGSB)
@@ -1927,6 +2005,32 @@ struct Handle {
       HIPCHK(hipGetLastError());
       return;
     }
+    if (plain(L) && L.sm_type == AMGX_SM_CHEBY && !L.RF.empty() && sp.part == PART_ALL) {
+      // Chebyshev pre-smoothing from zero, then residual on the SELL image of A + chunk-local restriction in one pass (r stays in LDS)
+      cheb_smooth(L, x, x, b, r, false, false, true);
+      const DevRestrict& R = L.RF;
+      const int G = L.A.lanes;
+      const int nch = R.slice_list.n ? R.n_chunks : (L.A.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
+      if (nch != R.n_chunks || L.fused_block != 512 || L.A.fmt != FMT_SELL || L.A.sell.win) throw Err("fused Chebyshev residual: chunk / slice mismatch");
+      if (nch > 0) {
+#define LAUNCH_CRF(EPT_) hipLaunchKernelGGL((sell_pre_restrict_kernel<512, 2, EPT_>), dim3(nch), dim3(512), 0, stream, L.A.n_rows, 0, L.A.n_slices, L.A.sell.view(), \
+                             (const double*)x, b, 0.0, ep_nt, (double*)nullptr, (double*)nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, \
+                             (const int32_t*)R.slice_list.p)
+#define LAUNCH_CRG(G_) hipLaunchKernelGGL((sell_pre_restrict_kernel<512, 2, 4, G_>), dim3(nch), dim3(512), 0, stream, L.A.n_rows, 0, L.A.n_slices, L.A.sell.view(), \
+                             (const double*)x, b, 0.0, ep_nt, (double*)nullptr, (double*)nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p)
+        if (G > 1) {
+          if (R.ept != 4 || R.slice_list.n) throw Err("fused Chebyshev residual with several lanes per row: unexpected chunk shape");
+          if (G == 2) LAUNCH_CRG(2); else if (G == 4) LAUNCH_CRG(4); else if (G == 8) LAUNCH_CRG(8); else throw Err("fused Chebyshev residual: unexpected lanes per row");
+        } else { if (R.ept == 4) LAUNCH_CRF(4); else LAUNCH_CRF(6); }
+#undef LAUNCH_CRG
+#undef LAUNCH_CRF
+      }
+      if (!skip_rsum)
+        hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
+                           R.oidx.p, R.part.p, b_coarse);
+      HIPCHK(hipGetLastError());
+      return;
+    }
     if (plain(L) && L.sm_type == AMGX_SM_GS && L.gsb.on() && L.gsb.has_split && !L.RG.empty() && sp.part == PART_ALL) {
       // sweep from zero, then residual of the untouched part + chunk-local restriction in one pass (r stays in LDS)
       gsb_sweep(L, 0, L.gsb.lowin, nullptr, x, b);
@@ -2003,6 +2107,11 @@ struct Handle {
     } else if (plain(L) && L.sm_type == AMGX_SM_JACOBI) {
       mult_add(L.P, 1.0, xc, x, L.tmp.p);  // tmp = x + P x_c
       jacobi_fused(L, L.tmp.p, b, x);      // x = tmp + omega * Dinv * (b - A tmp); res is not needed afterwards
+    } else if (plain(L) && L.sm_type == AMGX_SM_CHEBY) {
+      // k out-of-place passes follow: x + P x_c goes where the last of them lands in x
+      double* t = (L.cheb_degree & 1) ? L.tmp.p : x;
+      mult_add(L.P, 1.0, xc, x, t);
+      cheb_smooth(L, t, x, b, r, false, false, false);
     } else if (plain(L) && L.sm_type == AMGX_SM_GS && L.bgsb.on()) {
       const bool probe = probe_level == l && probe_kind == 9 && probe_e0;
       if (L.bgsb.bc) {
@@ -3161,6 +3270,7 @@ static void build_dense_tail(Handle& h, const amgx_hierarchy_desc* d, const amgx
     const DevLevel& V = h.lev[m];
     const int k = std::max(1, V.sm_steps) * (V.sm_symm ? 2 : 1);
     if (V.sm_type == AMGX_SM_JACOBI) return h.folded(V) ? 3.0 : 2.0 + 3.0 * k;
+    if (V.sm_type == AMGX_SM_CHEBY) return 3.0 + 2.0 * k * (V.cheb_degree + 1);
     if (V.sm_type == AMGX_SM_BGS) return 3.0 + 2.0 * k * std::max(1, V.bgs.n_colors);
     if (V.gsb.on() || V.bgsb.on()) return 2.0 + 3.0 * k;
     return 3.0 + 2.0 * k * std::max(1, V.gs.n_colors);
@@ -3209,6 +3319,10 @@ static void build_dense_tail(Handle& h, const amgx_hierarchy_desc* d, const amgx
   h.dense_ld = ld;
 }
 
+// Chebyshev levels without an interval from the caller: lmax = 1.1 x a 30-step power-iteration estimate (defined next to the
+// deterministic reductions it uses, at the end of this file)
+static void cheb_estimate(Handle& h);
+
 // dense_first: first level that may be collapsed into the dense operator (see build_dense_tail); < 0: never
 static Handle* create(const amgx_hierarchy_desc* d, int dense_first = 1) {
   if (!d || d->n_levels < 1 || !d->levels) throw Err("amgx_create: empty hierarchy descriptor");
@@ -3243,8 +3357,18 @@ static Handle* create(const amgx_hierarchy_desc* d, int dense_first = 1) {
     if (s.A.n_cols < s.A.n_rows || s.A.br != s.A.bc) throw Err("level matrix must have n_cols >= n_rows and square blocks");
     L.n = s.A.n_rows; L.ncols = s.A.n_cols; L.bs = s.A.br;
     L.sm_type = s.sm_type; L.omega = s.omega; L.sm_steps = s.sm_steps; L.sm_symm = s.sm_symm;
-    if (s.sm_type != AMGX_SM_JACOBI && s.sm_type != AMGX_SM_GS && s.sm_type != AMGX_SM_BGS) throw Err("unknown smoother type");
+    if (s.sm_type != AMGX_SM_JACOBI && s.sm_type != AMGX_SM_GS && s.sm_type != AMGX_SM_BGS && s.sm_type != AMGX_SM_CHEBY) throw Err("unknown smoother type");
     const bool last = (l + 1 == d->n_levels);
+    if (s.sm_type == AMGX_SM_CHEBY) {
+      const int deg = s.cheb_degree == 0 ? 2 : s.cheb_degree;
+      if (deg < 1 || deg > 8) throw Err("amgx_create: cheb_degree must be 1 .. 8 (0: default 2), got " + std::to_string(s.cheb_degree));
+      if (!(s.cheb_lambda_max >= 0.0)) throw Err("amgx_create: cheb_lambda_max must be >= 0 (0: estimated on the device)");
+      if (s.cheb_ratio != 0.0 && !(s.cheb_ratio > 1.0)) throw Err("amgx_create: cheb_ratio must be > 1 (0: default 10)");
+      if (s.A.n_cols != s.A.n_rows) throw Err("amgx_create: the Chebyshev smoother is not available on rank-partitioned levels");
+      L.cheb_degree = deg;
+      L.cheb_ratio = s.cheb_ratio == 0.0 ? 10.0 : s.cheb_ratio;
+      if (s.cheb_lambda_max > 0.0) L.cheb_set_interval(s.cheb_lambda_max);
+    }
     check_matrix(s.A, "A");            // (before anything reads rowptr[n_rows]: a NULL / garbage descriptor is an error, not a crash)
     // (declared BEFORE the task pool: its worker lambdas capture these by reference, and an exception between tasks.run() and
     //  tasks.wait() must join the workers -- ~SetupTasks -- before the buffers they read are freed)
@@ -3635,6 +3759,25 @@ static Handle* create(const amgx_hierarchy_desc* d, int dense_first = 1) {
         });
       }
       tasks.wait();
+      // scalar Chebyshev levels: the residual after pre-smoothing feeds the chunk-local restriction without going through HBM
+      // (sell_pre_restrict_kernel<.., MODE 2> on the SELL image of A itself), under the rule of the Jacobi levels' fused down kernel.
+      // AMGX_CHEB_NO_FUSED_RESTRICT=1 (or AMGX_NO_FUSED_RESTRICT=1) keeps EP_RES + the separate restriction kernels.
+      if (s.sm_type == AMGX_SM_CHEBY && s.A.br == 1 && s.sm_steps <= 1 && !s.sm_symm && L.A.fmt == FMT_SELL && !L.A.sell.win &&
+          (L.A.lanes == 1 || L.A.lanes == 2 || L.A.lanes == 4 || L.A.lanes == 8) && s.P.br == 1 && s.P.bc == 1 &&
+          s.P.rowptr[s.P.n_rows] < (int64_t)2147483647 && !std::getenv("AMGX_NO_FUSED_RESTRICT") && !std::getenv("AMGX_CHEB_NO_FUSED_RESTRICT") &&
+          !(L.A.lanes > 1 && std::getenv("AMGX_NO_FUSED_RESTRICT_MULTI")))
+      {
+        const int G = L.A.lanes;
+        L.fused_block = 512;
+        int64_t cc_min = 200000;
+        if (const char* e = std::getenv("AMGX_COMPACT_CHUNKS_MIN_ROWS")) cc_min = std::atoll(e);
+        if (G == 1 && dense_first >= 0 && s.A.n_rows >= cc_min && !std::getenv("AMGX_NO_COMPACT_CHUNKS")) {
+          const std::vector<int32_t> sl = cluster_slices(s.P, 512 / WAVE);
+          build_restrict(s.P, L.RF, 512, 6 * 512, 512, &sl);
+        } else
+          build_restrict(s.P, L.RF, 512 / G, 6 * 512, 512);
+        if (G > 1 && L.RF.ept != 4) L.RF = DevRestrict();
+      }
       clk.lap("level images (A, P, P^T, smoother data, A', Q: concurrent host tasks)", l);
     } else if (s.dinv) {
       tasks.wait();
@@ -3661,7 +3804,10 @@ static Handle* create(const amgx_hierarchy_desc* d, int dense_first = 1) {
     HIPCHK(hipMemset(L.rhs.p, 0, len * sizeof(double)));
     HIPCHK(hipMemset(L.res.p, 0, len * sizeof(double)));
     HIPCHK(hipMemset(L.tmp.p, 0, len * sizeof(double)));
+    if (L.sm_type == AMGX_SM_CHEBY) { L.d.alloc(len); HIPCHK(hipMemset(L.d.p, 0, len * sizeof(double))); }
   }
+  cheb_estimate(*h);
+  clk.lap("Chebyshev intervals (power iteration)");
   if (d->clev == AMGX_CLEV_INV) {
     const DevLevel& L = h->lev.back();
     if (d->coarse_n != L.len()) throw Err("clev = inv: coarse_n does not match the coarsest level");
@@ -4224,6 +4370,9 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
     int64_t v[AMGX_LEVEL_PATHS_N] = {};
     // the branch order of pre_smooth_restrict
     const bool fused = h.plain(L) && L.sm_type == AMGX_SM_JACOBI && !R.empty();
+    if (h.plain(L) && L.sm_type == AMGX_SM_CHEBY && !R.empty()) {
+      v[0] = 5; v[1] = L.fused_block; v[2] = L.A.lanes; v[3] = R.ept;
+    }
     if (fused) {
       v[0] = !L.ApreLW.empty() ? 3 : L.dia.on() ? 4 : L.Apre.sell.win ? 2 : 1;
       v[1] = L.fused_block;
@@ -4291,10 +4440,12 @@ int amgx_time_op(amgx_handle hh, int level, int op, int reps, double* avg_ms) {
     const bool has_c = level + 1 < h.n_levels();
     if ((op == 2 || op == 3 || op == 5 || op == 6 || op == 7) && !has_c) throw amgx::Err("amgx_time_op: no transfer on the coarsest level");
     if (op == 1 && (!L.dinv.p || L.sm_type != AMGX_SM_JACOBI)) throw amgx::Err("amgx_time_op: level has no Jacobi smoother");
+    if (op == 10 && (!L.dinv.p || L.sm_type != AMGX_SM_CHEBY || !L.d.p || L.cheb_degree < 1)) throw amgx::Err("amgx_time_op: level has no Chebyshev smoother");
     auto launch = [&]() {
       switch (op) {
         case 0: h.residual(L.A, L.x.p, L.rhs.p, L.res.p); break;
         case 1: h.jacobi_fused(L, L.tmp.p, L.rhs.p, L.x.p); break;
+        case 10: h.cheb_step(L, L.tmp.p, L.rhs.p, L.x.p, L.cheb_c1[2], L.cheb_c2[2], L.d.p, L.d.p); break;   // a middle step: reads and stores d
         case 2: h.transfer_f2c(level, L.res.p, h.lev[level + 1].rhs.p); break;
         case 3: h.mult_add(L.P, 1.0, h.lev[level + 1].x.p, L.x.p, L.tmp.p); break;
         case 4: h.run_cycle(h.lev[0].x.p, h.lev[0].rhs.p, true); break;
@@ -4364,9 +4515,66 @@ int amgx_time_op(amgx_handle hh, int level, int op, int reps, double* avg_ms) {
   });
 }
 
+int amgx_smoother_info(amgx_handle hh, int level, int32_t* sm_type, int32_t* degree, double* lambda_max, double* lambda_min, int32_t* estimated) {
+  return guard(hh, [&](amgx::Handle& h) {
+    if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_smoother_info: level out of range");
+    const amgx::DevLevel& L = h.lev[level];
+    const bool ch = L.sm_type == AMGX_SM_CHEBY;
+    if (sm_type) *sm_type = L.sm_type;
+    if (degree) *degree = ch ? L.cheb_degree : 0;
+    if (lambda_max) *lambda_max = ch ? L.cheb_lmax : 0.0;
+    if (lambda_min) *lambda_min = ch ? L.cheb_lmin : 0.0;
+    if (estimated) *estimated = ch ? L.cheb_estimated : 0;
+  });
+}
+
 }  // extern "C"
 
 #include "krylov.hpp"
+
+namespace amgx {
+// lambda_max(Dinv A) of the Chebyshev levels that got none: power iteration with the Rayleigh quotient in the A inner product,
+//   v_0 = Dinv A f (f = fill_kernel(seed 1): non-free rows become zero),   t = A v,  w = Dinv t,  lambda = <t, w> / <t, v>,  v <- w / lambda
+// 30 steps, lmax = 1.1 x the last lambda.  For symmetric positive semi-definite A and Dinv the quotient equals
+// <u, A^1/2 Dinv A^1/2 u> / <u, u> with u = A^1/2 v, so it never exceeds lambda_max.  Deterministic reductions (kr_dot_*).
+static void cheb_estimate(Handle& h) {
+  DevBuf<double> partial, sc;
+  for (int l = 0; l < h.n_levels(); ++l) {
+    DevLevel& L = h.lev[l];
+    if (L.sm_type != AMGX_SM_CHEBY || L.cheb_lmax > 0.0) continue;
+    const int64_t n = L.len();
+    if (n == 0 || !L.dinv.p || L.A.empty()) { L.cheb_set_interval(1.0); L.cheb_estimated = 1; continue; }
+    if (!partial.p) { partial.alloc((size_t)2 * KR_BLOCKS); sc.alloc(2); }
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(KR_BLOCKS, (n + BLOCK - 1) / BLOCK));
+    double *v = L.x.p, *t = L.res.p, *w = L.tmp.p;
+    hipLaunchKernelGGL(fill_kernel, dim3(Handle::grid_for(n)), dim3(BLOCK), 0, h.stream, n, (uint64_t)1, w);
+    h.mult(L.A, w, t);
+    h.cheb_first(L, t, nullptr, v, nullptr, 1.0);
+    double lam = 0.0;
+    for (int it = 0; it < 30; ++it) {
+      h.mult(L.A, v, t);
+      h.cheb_first(L, t, nullptr, w, nullptr, 1.0);
+      hipLaunchKernelGGL(kr_dot_partial_kernel, dim3(nb), dim3(BLOCK), 0, h.stream, n, (const double*)t, (const double*)w, partial.p);
+      hipLaunchKernelGGL(kr_dot_partial_kernel, dim3(nb), dim3(BLOCK), 0, h.stream, n, (const double*)t, (const double*)v, partial.p + KR_BLOCKS);
+      hipLaunchKernelGGL(kr_dot_final_kernel, dim3(2), dim3(BLOCK), 0, h.stream, nb, (const double*)partial.p, sc.p);
+      HIPCHK(hipGetLastError());
+      double two[2] = {0.0, 0.0};
+      HIPCHK(hipMemcpyAsync(two, sc.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h.stream));
+      HIPCHK(hipStreamSynchronize(h.stream));
+      if (!(two[1] > 0.0) || !(two[0] > 0.0) || !std::isfinite(two[0] / two[1])) break;      // A v = 0 (no free row): keep the last value
+      lam = two[0] / two[1];
+      hipLaunchKernelGGL(kr_scale_kernel, dim3(Handle::grid_for(n)), dim3(BLOCK), 0, h.stream, n, 1.0 / lam, (const double*)w, v, 0);
+    }
+    if (!(lam > 0.0)) lam = 1.0;
+    L.cheb_set_interval(1.1 * lam);
+    L.cheb_estimated = 1;
+    const size_t len = (size_t)std::max<int64_t>(1, L.ext_len());
+    for (double* q : {L.x.p, L.res.p, L.tmp.p}) HIPCHK(hipMemsetAsync(q, 0, len * sizeof(double), h.stream));
+    HIPCHK(hipStreamSynchronize(h.stream));
+  }
+}
+}  // namespace amgx
+
 #include "multi.hpp"
 #include "dist.hpp"
 #include "gss4.hpp"

@@ -371,6 +371,10 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d) {
   if (D->k < 1) throw Err("amgx_dist_create: need at least one rank-partitioned level and the gathered level");
   if (!d->halo || !d->counts || !d->kmap) throw Err("amgx_dist_create: halo tables / level-k tables missing");
   D->sm_type = d->top.levels[0].sm_type;
+  for (const amgx_hierarchy_desc* hd : {&d->top, &d->tail})
+    for (int l = 0; l < hd->n_levels; ++l)
+      if (hd->levels && hd->levels[l].sm_type == AMGX_SM_CHEBY)
+        throw Err("amgx_dist_create: the Chebyshev smoother (AMGX_SM_CHEBY) is not available on rank-partitioned hierarchies");
   D->fold = d->fold != 0;
   D->cycle = d->top.cycle;
   if (D->cycle != AMGX_CYCLE_V && D->cycle != AMGX_CYCLE_W) throw Err("amgx_dist_create: rank-partitioned hierarchies run V and W cycles");

@@ -44,8 +44,11 @@ enum Epilogue : int {
   EP_JAC = 3,    // y = yin + omega * dinv * (b - A yin)   with x == yin gathered, y != yin
   EP_PRE = 4,    // Jacobi pre-smoothing from x = 0 in one pass over the column-scaled image A' = A * omega*Dinv:
                  //   y = b - A' b  (= b - A x with x = omega*Dinv*b),  y2 = omega * dinv * b  (= x)
-  EP_CRES = 5    // y = c .* v - A x  with c = ep.dinv, v = ep.b (own-row entries): residual right after a block-hybrid
+  EP_CRES = 5,   // y = c .* v - A x  with c = ep.dinv, v = ep.b (own-row entries): residual right after a block-hybrid
                  //   Gauss-Seidel sweep from zero, A = the part of the matrix the sweep did not use (see gsb_sweep_kernel)
+  EP_CHEB = 6    // one step of the Chebyshev recurrence, x == yin gathered, y != yin:
+                 //   d_new = s2 * d_old + s * dinv * (b - A yin),  y = yin + d_new,  y2 = d_new (nullptr: not stored -- last step)
+                 //   d_old = ep.d, or yin itself when ep.d == nullptr (step 2 after a first step from x = 0, where d == x)
 };
 
 struct EpArgs {
@@ -53,12 +56,14 @@ struct EpArgs {
   const double* yin;
   const double* dinv;
   double s;      // AXPY factor or Jacobi omega
-  double* y2;    // second output of EP_PRE; block EP_JAC: optional output of the residual b - A x (nullptr: none)
+  double* y2;    // second output of EP_PRE; block EP_JAC: optional output of the residual b - A x (nullptr: none); EP_CHEB: d_new
   int nt;        // bit 0: stream the epilogue's own-row operands / results non-temporally (read / written once per cycle)
                  // bit 1 (EP_PRE): second output is z = x + omega*Dinv*r, the pre-smoothed iterate smoothed once more
                  //        without a coarse correction (cycle with the post-smoothing folded into the prolongation)
                  // bit 2: request the own-row operands BEFORE the row product (their latency then overlaps the matrix
                  //        stream instead of extending every wave's life by one dependent memory round trip)
+  const double* d;  // EP_CHEB: d_old (nullptr: yin)
+  double s2;        // EP_CHEB: factor of d_old (s: factor of dinv * residual)
 };
 constexpr int EPF_NT = 1, EPF_FOLD = 2, EPF_HOIST = 4;
 
@@ -83,6 +88,11 @@ __device__ __forceinline__ void store_scalar(int64_t row, double acc, double* y,
   else if (EP == EP_JAC) {
     if (ep.nt & EPF_NT) __builtin_nontemporal_store((have_xd ? xd : ep.yin[row]) + ep.s * (ld_nt(ep.dinv + row) * (ld_nt(ep.b + row) - acc)), y + row);
     else y[row] = (have_xd ? xd : ep.yin[row]) + ep.s * (ep.dinv[row] * (ep.b[row] - acc));
+  } else if (EP == EP_CHEB) {
+    const double yi = have_xd ? xd : ep.yin[row];
+    const double dn = ep.s2 * (ep.d ? ep.d[row] : yi) + ep.s * (ep.dinv[row] * (ep.b[row] - acc));
+    if (ep.y2) ep.y2[row] = dn;
+    y[row] = yi + dn;
   } else {
     const double bi = have_xd ? xd : ep.b[row];
     const double r = bi - acc;
@@ -96,7 +106,7 @@ __device__ __forceinline__ void store_scalar(int64_t row, double acc, double* y,
 }
 
 // own-row operands of an epilogue, loaded ahead of the row product (EPF_HOIST)
-struct EpOps { double b, d, yin; };
+struct EpOps { double b, d, yin, dd; };
 template <int EP>
 __device__ __forceinline__ EpOps ep_operands(int64_t row, const EpArgs& ep, bool have_xd, bool skip_d = false) {
   EpOps o{0.0, 0.0, 0.0};
@@ -108,6 +118,11 @@ __device__ __forceinline__ EpOps ep_operands(int64_t row, const EpArgs& ep, bool
     o.d = nt ? ld_nt(ep.dinv + row) : ep.dinv[row];
     o.b = nt ? ld_nt(ep.b + row) : ep.b[row];
     if (!have_xd) o.yin = ep.yin[row];
+  } else if (EP == EP_CHEB) {
+    o.d = nt ? ld_nt(ep.dinv + row) : ep.dinv[row];
+    o.b = nt ? ld_nt(ep.b + row) : ep.b[row];
+    if (!have_xd) o.yin = ep.yin[row];
+    if (ep.d) o.dd = nt ? ld_nt(ep.d + row) : ep.d[row];
   } else if (EP == EP_PRE) {
     if (!skip_d) o.d = nt ? ld_nt(ep.dinv + row) : ep.dinv[row];
     if (!have_xd) o.b = ep.b[row];
@@ -124,6 +139,11 @@ __device__ __forceinline__ void store_scalar_ops(int64_t row, double acc, double
   else if (EP == EP_JAC) {
     const double v = (have_xd ? xd : o.yin) + ep.s * (o.d * (o.b - acc));
     if (nt) __builtin_nontemporal_store(v, y + row); else y[row] = v;
+  } else if (EP == EP_CHEB) {
+    const double yi = have_xd ? xd : o.yin;
+    const double dn = ep.s2 * (ep.d ? o.dd : yi) + ep.s * (o.d * (o.b - acc));
+    if (ep.y2) { if (nt) __builtin_nontemporal_store(dn, ep.y2 + row); else ep.y2[row] = dn; }
+    if (nt) __builtin_nontemporal_store(yi + dn, y + row); else y[row] = yi + dn;
   } else {
     const double bi = have_xd ? xd : o.b;
     const double r = bi - acc;
@@ -307,7 +327,7 @@ __global__ __launch_bounds__(BLOCK) void sell_spmv_kernel(int64_t n_rows, int sl
   if (s >= n_slices) return;
   const int row = s * (WAVE / G) + lane / G;
   double xd[2] = {0.0, 0.0};
-  const bool use_xd = G == 1 && (EP == EP_JAC || EP == EP_PRE) && M.diag_first;
+  const bool use_xd = G == 1 && (EP == EP_JAC || EP == EP_PRE || EP == EP_CHEB) && M.diag_first;
   const bool wdiag = EP == EP_PRE && use_xd && M.wdiag;
   const bool writer = (lane % G) == 0 && row < n_rows;
   const bool hoist = (ep.nt & EPF_HOIST) && EP != EP_MULT;
@@ -441,6 +461,22 @@ __global__ __launch_bounds__(BLOCK) void bcsrvec_spmv_kernel(int64_t n_rows, con
         for (int c = 0; c < BR; ++c) u += d[r * BR + c] * tt[c];
         yo[r] = ep.yin[row * BR + r] + ep.s * u;
       }
+    } else if (EP == EP_CHEB) {
+      // Chebyshev step: square blocks only, like EP_JAC
+      double tt[BR];
+#pragma unroll
+      for (int r = 0; r < BR; ++r) tt[r] = ep.b[row * BR + r] - acc[r];
+      const double* __restrict__ d = ep.dinv + row * (BR * BR);
+#pragma unroll
+      for (int r = 0; r < BR; ++r) {
+        double u = 0.0;
+#pragma unroll
+        for (int c = 0; c < BR; ++c) u += d[r * BR + c] * tt[c];
+        const double yi = ep.yin[row * BR + r];
+        const double dn = ep.s2 * (ep.d ? ep.d[row * BR + r] : yi) + ep.s * u;
+        if (ep.y2) ep.y2[row * BR + r] = dn;
+        yo[r] = yi + dn;
+      }
     }
   }
 }
@@ -555,13 +591,14 @@ __global__ __launch_bounds__(BLOCK) void bsell_spmv_kernel(int64_t n_rows, int s
   const int64_t i = brow * BS + r;
   // own-row epilogue operands requested ahead of the matrix stream (EPF_HOIST, see sell_spmv_kernel)
   const bool hoist = (ep.nt & EPF_HOIST) && active && EP != EP_MULT;
-  double ob = 0.0, oy = 0.0, od[BS];
+  double ob = 0.0, oy = 0.0, odd = 0.0, od[BS];
 #pragma unroll
   for (int c = 0; c < BS; ++c) od[c] = 0.0;
   if (hoist) {
-    if (EP == EP_RES || EP == EP_JAC) ob = ep.b[i];
-    if (EP == EP_AXPY || EP == EP_JAC) oy = ep.yin[i];
-    if (EP == EP_JAC) {
+    if (EP == EP_RES || EP == EP_JAC || EP == EP_CHEB) ob = ep.b[i];
+    if (EP == EP_AXPY || EP == EP_JAC || EP == EP_CHEB) oy = ep.yin[i];
+    if (EP == EP_CHEB && ep.d) odd = ep.d[i];
+    if (EP == EP_JAC || EP == EP_CHEB) {
 #pragma unroll
       for (int c = 0; c < BS; ++c) od[c] = ep.dinv[brow * (BS * BS) + r * BS + c];
     }
@@ -592,9 +629,9 @@ __global__ __launch_bounds__(BLOCK) void bsell_spmv_kernel(int64_t n_rows, int s
     }
   }
   double out = 0.0;
-  if (EP == EP_JAC) {
+  if (EP == EP_JAC || EP == EP_CHEB) {
     const double t = active ? (hoist ? ob : ep.b[i]) - acc : 0.0;
-    if (active && ep.y2) ep.y2[i] = t;
+    if (EP == EP_JAC && active && ep.y2) ep.y2[i] = t;
     const int base = lane - r;
     double u = 0.0;
 #pragma unroll
@@ -602,7 +639,14 @@ __global__ __launch_bounds__(BLOCK) void bsell_spmv_kernel(int64_t n_rows, int s
       const double tc = __shfl(t, base + c, WAVE);
       if (active) u += (hoist ? od[c] : ep.dinv[brow * (BS * BS) + r * BS + c]) * tc;
     }
-    if (active) out = (hoist ? oy : ep.yin[i]) + ep.s * u;
+    if (EP == EP_CHEB) {
+      if (active) {
+        const double yi = hoist ? oy : ep.yin[i];
+        const double dn = ep.s2 * (ep.d ? (hoist ? odd : ep.d[i]) : yi) + ep.s * u;
+        if (ep.y2) ep.y2[i] = dn;
+        out = yi + dn;
+      }
+    } else if (active) out = (hoist ? oy : ep.yin[i]) + ep.s * u;
   } else if (active) {
     if (EP == EP_MULT) out = acc;
     else if (EP == EP_RES) out = (hoist ? ob : ep.b[i]) - acc;
@@ -679,9 +723,9 @@ __global__ __launch_bounds__(BLOCK) void bcsr_rowlane_kernel(int64_t n_rows, con
   // lanes with g == 0 now hold (A x)_r of their block row
   const int64_t i = row * BR + r;
   double out = 0.0;
-  if (EP == EP_JAC) {           // square blocks only
+  if (EP == EP_JAC || EP == EP_CHEB) {           // square blocks only
     const double t = (active && g == 0) ? ep.b[i] - acc : 0.0;
-    if (active && g == 0 && ep.y2) ep.y2[i] = t;
+    if (EP == EP_JAC && active && g == 0 && ep.y2) ep.y2[i] = t;
     const int base = lane - r;
     double u = 0.0;
 #pragma unroll
@@ -689,7 +733,14 @@ __global__ __launch_bounds__(BLOCK) void bcsr_rowlane_kernel(int64_t n_rows, con
       const double tc = __shfl(t, base + c, WAVE);
       if (active && g == 0) u += ep.dinv[row * (BR * BR) + r * BR + c] * tc;
     }
-    if (active && g == 0) out = ep.yin[i] + ep.s * u;
+    if (EP == EP_CHEB) {
+      if (active && g == 0) {
+        const double yi = ep.yin[i];
+        const double dn = ep.s2 * (ep.d ? ep.d[i] : yi) + ep.s * u;
+        if (ep.y2) ep.y2[i] = dn;
+        out = yi + dn;
+      }
+    } else if (active && g == 0) out = ep.yin[i] + ep.s * u;
   } else if (active && g == 0) {
     if (EP == EP_MULT) out = acc;
     else if (EP == EP_RES) out = ep.b[i] - acc;
@@ -1238,6 +1289,8 @@ __global__ __launch_bounds__(BLOCK) void restrict_chunk_kernel(int64_t n_fine, c
 // FB = workgroup size = rows per chunk (1024 or 512); 4 entries of P per row at most
 // MODE 0: Jacobi pre-smoothing as described above.  MODE 1: residual after a block-hybrid Gauss-Seidel sweep from zero,
 // r = c .* x - A_rest x (EP_CRES; b = the swept x, dinv = c, nothing written to x), with the same chunk-local restriction.
+// MODE 2: residual after Chebyshev pre-smoothing on the level's SELL image of A itself, r = rhs - A x (b = the smoothed x that is
+// gathered, dinv = the right-hand side, nothing written to x), with the same chunk-local restriction.
 // EPT: entries of P per thread the chunk may hold (4: prolongations with <= 3 entries per row; 6: the up to 5 of the reference's
 // "classic" rows; chosen per level by build_restrict from the fullest chunk)
 // G = lanes per row (SELL-G image, long rows of the coarser levels): the chunk then holds FUSED_BLOCK / G rows, the G partial
@@ -1300,6 +1353,16 @@ __global__ __launch_bounds__(FUSED_BLOCK) void sell_pre_restrict_kernel(int64_t 
 #pragma unroll
       for (int o = G >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, G);
       if (writer && row < n_rows) { r = ci * xi - acc; if (r_out) r_out[row] = r; }
+    }
+  } else if (MODE == 2) {
+    if (s < n_slices) {
+      double bi = 0.0;
+      if (writer && row < n_rows) bi = (nt & EPF_NT) ? ld_nt(dinv + row) : dinv[row];
+      double xdd[2];
+      double acc = sell_row_dot_sp(M, sp0, sp1, lane, row, b, xdd);
+#pragma unroll
+      for (int o = G >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, G);
+      if (writer && row < n_rows) { r = bi - acc; if (r_out) r_out[row] = r; }
     }
   } else if (s < n_slices) {
     double bi = 0.0, di = 0.0;
@@ -1809,6 +1872,28 @@ __global__ __launch_bounds__(BLOCK) void diag_apply_kernel(int64_t n, const doub
       u *= omega;
       x[i * BS + r] = ADD ? x[i * BS + r] + u : u;
     }
+  }
+}
+
+// first step of a Chebyshev smooth: d = c0 * Dinv * v, xout = (xin ? xin : 0) + d; d is stored when asked for (dout != nullptr;
+// from x = 0 the step leaves d == x and the next step reads x for it).  xout may alias xin.
+template <int BS>
+__global__ __launch_bounds__(BLOCK) void cheb_first_kernel(int64_t n, const double* __restrict__ dinv, const double* __restrict__ v,
+                                                           const double* xin, double* xout, double* dout, double c0) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  double vv[BS];
+#pragma unroll
+  for (int c = 0; c < BS; ++c) vv[c] = v[i * BS + c];
+  const double* __restrict__ d = dinv + i * (BS * BS);
+#pragma unroll
+  for (int r = 0; r < BS; ++r) {
+    double u = 0.0;
+#pragma unroll
+    for (int c = 0; c < BS; ++c) u += d[r * BS + c] * vv[c];
+    u *= c0;
+    if (dout) dout[i * BS + r] = u;
+    xout[i * BS + r] = xin ? xin[i * BS + r] + u : u;
   }
 }
 

@@ -18,7 +18,35 @@ from . import _lib
 from ._lib import Matrix, NgsAMGError
 
 # "hgs" = Gauss-Seidel in the block-hybrid form (one launch per sweep, amgx_level_desc.gs_block_rows); "gs" = multicolour
-_SM = {"jacobi": _lib.AMGX_SM_JACOBI, "gs": _lib.AMGX_SM_GS, "hgs": _lib.AMGX_SM_GS, "bgs": _lib.AMGX_SM_BGS}
+# "cheby" = Chebyshev polynomial smoother in the (block-)Jacobi-preconditioned operator (an own option)
+_SM = {"jacobi": _lib.AMGX_SM_JACOBI, "gs": _lib.AMGX_SM_GS, "hgs": _lib.AMGX_SM_GS, "bgs": _lib.AMGX_SM_BGS,
+       "cheby": _lib.AMGX_SM_CHEBY}
+
+
+def _per_level(v, i, n, name):
+    """scalar or per-level list"""
+    if isinstance(v, (list, tuple, np.ndarray)):
+        if len(v) != n:
+            raise NgsAMGError(f"{name} list must have one entry per level")
+        return v[i]
+    return v
+
+
+def cheby_args(degree, ratio, lambda_max, i=0, n=1):
+    """validated (degree, lambda_max, ratio) of one Chebyshev level as the descriptor carries them (0 = default / estimate)"""
+    deg = _per_level(degree, i, n, "cheb_degree")
+    rat = _per_level(ratio, i, n, "cheb_ratio")
+    lam = _per_level(lambda_max, i, n, "cheb_lambda_max")
+    deg = 2 if deg is None else int(deg)
+    rat = 10.0 if rat is None else float(rat)
+    lam = 0.0 if lam is None else float(lam)
+    if not (1 <= deg <= 8):
+        raise NgsAMGError(f"cheb_degree = {deg}: need 1 .. 8")
+    if not (rat > 1.0):
+        raise NgsAMGError(f"cheb_ratio = {rat}: need a ratio > 1")
+    if not (lam >= 0.0):
+        raise NgsAMGError(f"cheb_lambda_max = {lam}: need a value >= 0 (0 / None: estimated on the device)")
+    return deg, lam, rat
 
 
 def gs_block_rows(A):
@@ -181,9 +209,11 @@ def check_multi(vecs, sizes, interleaved=False, names=None):
 
 
 def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V", clev="inv", device=0,
-                   use_graph=True):
+                   use_graph=True, cheb_degree=2, cheb_ratio=10, cheb_lambda_max=None):
     """amgx_hierarchy_desc over the host arrays of a hierarchy.  Returns (desc, keep): `keep` holds everything the
-    descriptor points to and must outlive the amgx_create / amgx_dist_create call."""
+    descriptor points to and must outlive the amgx_create / amgx_dist_create call.
+    cheb_*: levels with sm_type "cheby" (each a scalar or a per-level list); the descriptor carries 0 for a default
+    (degree 2, ratio 10) and for a lambda_max that amgx_create estimates on the device."""
     levels = hierarchy.levels
     n = len(levels)
     types = sm_type if isinstance(sm_type, (list, tuple)) else [sm_type] * n
@@ -201,8 +231,13 @@ def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False
         d.dinv = _lib.ptr(lv.dinv, C.c_double)
         d.free_dofs = _lib.ptr(lv.free, C.c_uint8)
         if types[i] not in _SM:
-            raise NgsAMGError(f"unknown smoother type '{types[i]}' (jacobi | gs | bgs)")
+            raise NgsAMGError(f"unknown smoother type '{types[i]}' (jacobi | gs | hgs | bgs | cheby)")
         d.sm_type = _SM[types[i]]
+        if types[i] == "cheby":
+            deg, lam, rat = cheby_args(cheb_degree, cheb_ratio, cheb_lambda_max, i, n)
+            d.cheb_degree = deg
+            d.cheb_lambda_max = lam
+            d.cheb_ratio = 0.0 if rat == 10.0 else rat
         d.omega = float(omega)
         d.sm_steps = int(sm_steps[i] if isinstance(sm_steps, (list, tuple)) else sm_steps)      # per level: ..._spec flags
         d.sm_symm = int(bool(sm_symm[i] if isinstance(sm_symm, (list, tuple)) else sm_symm))
@@ -280,13 +315,15 @@ def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False
 
 class DeviceAMGMatrix:
     def __init__(self, hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V",
-                 clev="inv", device=0, use_graph=True):
+                 clev="inv", device=0, use_graph=True, cheb_degree=2, cheb_ratio=10, cheb_lambda_max=None):
         lib = _lib.hip()
         self._lib = lib
         self._cfg = dict(sm_type=sm_type, omega=omega, sm_steps=sm_steps, sm_symm=sm_symm, mg_cycle=mg_cycle, clev=clev,
-                         device=device, use_graph=use_graph)
+                         device=device, use_graph=use_graph, cheb_degree=cheb_degree, cheb_ratio=cheb_ratio,
+                         cheb_lambda_max=cheb_lambda_max)
         self.hierarchy = hierarchy
-        desc, self._keep, self.hgs = hierarchy_desc(hierarchy, sm_type, omega, sm_steps, sm_symm, mg_cycle, clev, device, use_graph)
+        desc, self._keep, self.hgs = hierarchy_desc(hierarchy, sm_type, omega, sm_steps, sm_symm, mg_cycle, clev, device, use_graph,
+                                                    cheb_degree, cheb_ratio, cheb_lambda_max)
         self._h = C.c_void_p()
         self._owned = True
         if lib.amgx_create(C.byref(desc), C.byref(self._h)) != 0:
@@ -528,9 +565,20 @@ class DeviceAMGMatrix:
         out = np.zeros(len(self._PATH_KEYS), dtype=np.int64)
         self._ck(self._lib.amgx_level_paths(self._h, int(level), out.ctypes.data_as(_lib.c_i64p), out.size))
         d = dict(zip(self._PATH_KEYS, (int(v) for v in out)))
-        d["kernel"] = {0: None, 1: "sell", 2: "sell-win", 3: "sell-lw", 4: "dia"}[d["kernel"]]
+        d["kernel"] = {0: None, 1: "sell", 2: "sell-win", 3: "sell-lw", 4: "dia", 5: "cheby-res"}[d["kernel"]]
         d["gs_form"] = self._GS_FORMS[d["gs_form"]]
         return d
+
+    _SM_NAMES = {_lib.AMGX_SM_JACOBI: "jacobi", _lib.AMGX_SM_GS: "gs", _lib.AMGX_SM_BGS: "bgs", _lib.AMGX_SM_CHEBY: "cheby"}
+
+    def smoother_info(self, level):
+        """the smoother of a level (amgx_smoother_info): type and, for "cheby", degree, interval [lambda_min, lambda_max] of Dinv A
+        and whether lambda_max was estimated on the device"""
+        t, deg, est = C.c_int32(), C.c_int32(), C.c_int32()
+        lmax, lmin = C.c_double(), C.c_double()
+        self._ck(self._lib.amgx_smoother_info(self._h, int(level), C.byref(t), C.byref(deg), C.byref(lmax), C.byref(lmin), C.byref(est)))
+        return {"sm_type": self._SM_NAMES.get(t.value, "?"), "degree": deg.value, "lambda_max": lmax.value, "lambda_min": lmin.value,
+                "estimated": est.value}
 
     def time_op(self, level, op, reps=20):
         ms = C.c_double()

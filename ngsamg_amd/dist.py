@@ -856,7 +856,8 @@ class DistributedAMG:
     def __init__(self, comm, states0, dim=3, omega=0.9, dist_min_rows=50000, max_dist_levels=3, device=0,
                  backend=None, sm_type="jacobi", fold=True, sm_steps=1, sm_symm=False, mg_cycle="V", **opts):
         if sm_type not in ("jacobi", "gs", "hgs", "bgs"):
-            raise NgsAMGError("DistributedAMG: sm_type must be jacobi, gs (multicolour stages), hgs (block-hybrid Gauss-Seidel) or bgs")
+            raise NgsAMGError("DistributedAMG: sm_type must be jacobi, gs (multicolour stages), hgs (block-hybrid Gauss-Seidel) or bgs"
+                              + (" (the Chebyshev smoother 'cheby' is not available on rank-partitioned levels)" if sm_type == "cheby" else ""))
         self.comm, self.dim, self.omega, self.sm_type = comm, dim, omega, sm_type
         # energy = 1: linear elasticity (states from assemble_elasticity_owned: block levels, rigid-body prolongation blocks,
         # coarse block size dim + nrot); block levels run block-Jacobi in the literal stage order
