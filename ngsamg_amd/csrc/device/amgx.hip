@@ -9,6 +9,7 @@
 // of kernel launches on one HIP stream, captured once per (b, x) pair into a hipGraph and replayed.
 #include "../../../include/amgx.h"
 #include "kernels.hpp"
+#include "knobs.hpp"
 #include "../host/dia.hpp"
 #include <dlfcn.h>
 #include <algorithm>
@@ -103,14 +104,10 @@ struct DevBuf {
 
 enum Fmt : int { FMT_CSRVEC = 0, FMT_SELL = 1, FMT_BSELL = 2, FMT_RB = 4 };     // (3 is reported for windowed SELL, see amgx_matrix_info)
 
-// gathered-vector access of the BSELL kernels (BSellMat::xmode); AMGX_BSELL_XMODE overrides (same arithmetic in every mode).
+// gathered-vector access of the BSELL kernels (BSellMat::xmode; Knobs::bsell_xmode, same arithmetic in every mode).
 // Same box, cfg 3 GS / cfg 5 GS / cfg 5 block-Jacobi applications per second (profiles/r04/gs_experiments.txt):
 //   0 (BS 8-byte loads) 281.9 / 160.6 / 193.1    1 (16-byte loads) 277.7 / 160.4 / 189.3    2 (one load + lane exchange) 246.2 / 149.9 / 189.3
 // another box: 0 270.4 / 158.5 / 194.1; column indices 2 / 3 / 4 steps ahead (3 / 5 / 4): 261.6 / 154.7 / 193.9, 267.1 / 157.2 / 186.6, 229.5 / 126.7 / 186.3
-static int bsell_xmode() {
-  static const int m = [] { const char* e = std::getenv("AMGX_BSELL_XMODE"); return e ? std::max(0, std::min(5, std::atoi(e))) : 0; }();
-  return m;
-}
 
 struct DevMatrix {
   int64_t n_rows = 0, n_cols = 0, nnz = 0;
@@ -150,7 +147,7 @@ struct DevMatrix {
     DevBuf<int64_t> slice_ptr;
     DevBuf<int32_t> col;
     DevBuf<double> val;
-    BSellMat view() const { return BSellMat{slice_ptr.p, col.p, val.p, bsell_xmode()}; }
+    BSellMat view(int xmode) const { return BSellMat{slice_ptr.p, col.p, val.p, xmode}; }
   } bsell;
   bool empty() const { return n_rows == 0; }
 };
@@ -182,6 +179,8 @@ struct DevGSB {                         // block-hybrid Gauss-Seidel (gsb_sweep_
   int B = 0, G = 1, TH = 1024;          // rows per block, lanes per row, workgroup size (B * G == TH)
   int n_blocks = 0, n_colors = 0;
   int lowin_maxw = 0;                   // widest slice of `lowin` (entries per lane): <= 5 selects the narrow sweep-from-zero kernel
+  // launch-time choices of the sweep, decided once by build_gsb (gsb_set_paths); gsb_sweep and amgx_level_paths read them
+  bool narrow = false, mid = false, lw = false;
   // long-row levels: local-window image of `rest` (sell_lw_pre_restrict_kernel, MODE 1) for the fused residual + restriction
   DevMatrix restLW;
   DevBuf<int32_t> lw_cptr, lw_ccol;
@@ -203,13 +202,15 @@ struct DevGSB {                         // block-hybrid Gauss-Seidel (gsb_sweep_
 };
 
 // launch-time choices of the block-hybrid sweep (gsb_sweep) and of the multicolour row-list kernel (gs_sweep); amgx_level_paths
-// reports them through the same functions
-// the sweep from zero over `lowin` takes the narrow kernel (2 entries per lane and pass)
-static bool gsb_narrow(const DevGSB& g) { return g.lowin_maxw > 0 && g.lowin_maxw <= 5 && !std::getenv("AMGX_GSB_NO_NARROW"); }
-// the general sweep over `full` takes the mid-width kernel (5 entries per lane and pass)
-static bool gsb_mid(const DevGSB& g) { return g.G > 1 && g.full_maxw > 0 && g.full_maxw <= 11 && !std::getenv("AMGX_GSB_NO_MID"); }
-// ... and reads its local-window image
-static bool gsb_lw(const DevGSB& g) { return g.has_fullLW && g.G > 1; }
+// reports the same values
+static void gsb_set_paths(const Knobs& K, DevGSB& g) {
+  // the sweep from zero over `lowin` takes the narrow kernel (2 entries per lane and pass)
+  g.narrow = g.lowin_maxw > 0 && g.lowin_maxw <= 5 && !K.gsb_no_narrow;
+  // the general sweep over `full` takes the mid-width kernel (5 entries per lane and pass)
+  g.mid = g.G > 1 && g.full_maxw > 0 && g.full_maxw <= 11 && !K.gsb_no_mid;
+  // ... and reads its local-window image
+  g.lw = g.has_fullLW && g.G > 1;
+}
 // lanes per block row W of bgs_color_kernel for a colour of `rows` rows on a level with `avg` blocks per row
 static int bgs_rowlist_w(double avg, int64_t rows) {
   int W = avg >= 48.0 ? 4 : (avg >= 20.0 ? 2 : 1);
@@ -367,7 +368,8 @@ template <class T> using RawVec = std::vector<T, NoInitAlloc<T>>;
 
 // AMGX_SETUP_LOG=1: wall-clock time of the stages of amgx_create on stderr
 struct SetupClock {
-  bool on = std::getenv("AMGX_SETUP_LOG") != nullptr;
+  bool on;
+  explicit SetupClock(const Knobs& K) : on(K.setup_log) {}
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   void lap(const char* what, int level = -1) {
     if (!on) return;
@@ -378,13 +380,10 @@ struct SetupClock {
 };
 
 // Host threads for the format builders of amgx_create (cold path, but 10^8 entries at cfg 2: serial loops were 7.5 s of
-// "upload"): contiguous index ranges, one per thread; f(begin, end, thread).  AMGX_SETUP_THREADS overrides the count.
+// "upload"): contiguous index ranges, one per thread; f(begin, end, thread).  AMGX_SETUP_THREADS overrides the count, which is
+// fixed at its first use in the process.
 static int setup_threads() {
-  static int T = [] {
-    int t = (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 32u);
-    if (const char* e = std::getenv("AMGX_SETUP_THREADS")) t = std::max(1, std::atoi(e));
-    return t;
-  }();
+  static const int T = Knobs::from_env().setup_threads;
   return T;
 }
 template <class F>
@@ -407,13 +406,12 @@ static void par_for(int64_t n, F&& f, int64_t min_per_thread = 4096) {
 // loops of the others.  AMGX_SETUP_SERIAL=1 runs them one after the other.
 struct SetupTasks {
   int device;
-  bool serial = std::getenv("AMGX_SETUP_SERIAL") != nullptr;
+  bool serial, log;
   std::vector<std::thread> th;
   std::vector<std::exception_ptr> errs;
   std::mutex mu;
-  explicit SetupTasks(int dev) : device(dev) {}
+  SetupTasks(int dev, const Knobs& K) : device(dev), serial(K.setup_serial), log(K.setup_log) {}
   ~SetupTasks() { for (auto& t : th) if (t.joinable()) t.join(); }
-  bool log = std::getenv("AMGX_SETUP_LOG") != nullptr;
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   template <class F>
   void timed(F& f, const char* name) {
@@ -465,10 +463,9 @@ static int pick_lanes(double avg_len) {
 // lanes of a wave gather entry k of 64 DIFFERENT rows per step -- 64 unrelated cache lines, the kernel is bound by the
 // address path (0.45 T gathers/s measured at the 1.24 M-row level of cfg 2, 4.5 TB/s) -- while G lanes per row walk G
 // consecutive (ascending, hence neighbouring) columns of ONE row.  Lanes per row for rows of this average length:
-static int sell_long_row_lanes(double avg) {
-  int g = 1;        // measured at that level (same box, 1 / 2 / 4 / 8 lanes): 193 / 176 / 188 / 204 us -- no win, the default stays one lane
-  if (const char* e = std::getenv("AMGX_SELL_LONG_ROW_LANES")) g = avg >= 24.0 ? std::max(1, std::atoi(e)) : 1;
-  return g;
+static int sell_long_row_lanes(const Knobs& K, double avg) {
+  // measured at that level (same box, 1 / 2 / 4 / 8 lanes): 193 / 176 / 188 / 204 us -- no win, the default stays one lane
+  return avg >= 24.0 ? K.sell_long_row_lanes : 1;
 }
 
 // SELL-64-pair image of the rows `rows[0..m)` of a scalar CSR matrix (row id < 0 => empty padding row).
@@ -518,7 +515,7 @@ static void build_sell(const amgx_matrix& A, const int32_t* rows, int64_t m, boo
   // diagonal-first entry order (one thread per row, square matrix, every row has its diagonal stored): the Jacobi
   // epilogues then get the own-row value of the gathered vector from entry 0 instead of a second streaming read
   std::vector<int32_t> dpos;
-  bool diag_first = want_diag_first && G == 1 && !rows && A.n_rows <= A.n_cols && !std::getenv("AMGX_NO_DIAG_FIRST");
+  bool diag_first = want_diag_first && G == 1 && !rows && A.n_rows <= A.n_cols;
   if (diag_first) {
     dpos.assign(A.n_rows, -1);
     std::vector<char> bad(setup_threads(), 0);
@@ -717,8 +714,8 @@ static bool build_bsell(const amgx_matrix& A, DevMatrix& D, double max_pad, cons
 
 // Rigid-body structure of a transfer matrix (see RbMat): every block of P (bf x bc) must be w Q(t), every block of P^T (bc x bf)
 // its transpose.  Returns false (and leaves D untouched) if any block deviates: the general block formats take over.
-static bool try_build_rb(const amgx_matrix& M, bool transposed, DevMatrix& D) {
-  if (std::getenv("AMGX_NO_RB_TRANSFER")) return false;
+static bool try_build_rb(const Knobs& K, const amgx_matrix& M, bool transposed, DevMatrix& D) {
+  if (K.no_rb_transfer) return false;
   const int bf = transposed ? M.bc : M.br, bc = transposed ? M.br : M.bc;
   int dim;
   if (bc == 6 && (bf == 3 || bf == 6)) dim = 3;
@@ -726,7 +723,7 @@ static bool try_build_rb(const amgx_matrix& M, bool transposed, DevMatrix& D) {
   else if (bc == 2 && bf == 2) dim = 0;
   else return false;
   const int64_t nnz = M.rowptr[M.n_rows];
-  if (nnz == 0 || nnz >= (int64_t)2147483647) return false;
+  if (nnz == 0 || nnz >= I32_MAX) return false;
   std::vector<double> w((size_t)nnz), t((size_t)std::max(1, dim) * nnz, 0.0);
   std::vector<char> bad(setup_threads(), 0);
   const int br = M.br, bcm = M.bc;
@@ -775,8 +772,8 @@ static void check_matrix(const amgx_matrix& A, const char* what) {
   if (A.br < 1 || A.br > 6 || A.bc < 1 || A.bc > 6) throw Err(std::string(what) + ": block sizes must be in 1..6");
   const int64_t nnz = A.rowptr[A.n_rows];
   if (nnz > 0 && (!A.col || !A.val)) throw Err(std::string(what) + ": col / val missing");
-  if (nnz >= (int64_t)2147483647) throw Err(std::string(what) + ": more than 2^31-1 stored blocks are not supported on the device");
-  if (A.n_cols >= (int64_t)2147483647 / 8) throw Err(std::string(what) + ": too many columns for int32 indices");
+  if (nnz >= I32_MAX) throw Err(std::string(what) + ": more than 2^31-1 stored blocks are not supported on the device");
+  if (A.n_cols >= I32_MAX / 8) throw Err(std::string(what) + ": too many columns for int32 indices");
   par_for(A.n_rows, [&](int64_t i0, int64_t i1, int) {
     for (int64_t i = i0; i < i1; ++i)
       if (A.rowptr[i + 1] < A.rowptr[i]) throw Err(std::string(what) + ": rowptr is not monotone");
@@ -788,12 +785,12 @@ static void check_matrix(const amgx_matrix& A, const char* what) {
 }
 
 // rb_mode: 1 = A is a prolongation, 2 = its transpose: block matrices are first tried in the rigid-body form (try_build_rb)
-static void upload_matrix(const amgx_matrix& A, DevMatrix& D, const char* what, bool allow_sell = true, bool rowrel_ok = false, bool keep_csr = false,
+static void upload_matrix(const Knobs& K, const amgx_matrix& A, DevMatrix& D, const char* what, bool allow_sell = true, bool rowrel_ok = false, bool keep_csr = false,
                           double max_pad = 1.35, int win = 0, const double* diag_override = nullptr, int rb_mode = 0) {
   check_matrix(A, what);
   D.n_rows = A.n_rows; D.n_cols = A.n_cols; D.br = A.br; D.bc = A.bc;
   D.nnz = A.rowptr[A.n_rows];
-  if (rb_mode && (A.br > 1 || A.bc > 1) && try_build_rb(A, rb_mode == 2, D)) return;
+  if (rb_mode && (A.br > 1 || A.bc > 1) && try_build_rb(K, A, rb_mode == 2, D)) return;
   const double avg = D.n_rows ? (double)D.nnz / (double)D.n_rows : 0.0;
   D.lanes = pick_lanes(avg);
   // scalar matrices: sliced ELL with G lanes per row; G = the smallest power of two that yields >= 2^20
@@ -802,8 +799,8 @@ static void upload_matrix(const amgx_matrix& A, DevMatrix& D, const char* what, 
   if (allow_sell && A.br == 1 && A.bc == 1 && D.n_rows > 0 && D.nnz > 0) {
     int G = 1;
     while (G < 16 && D.n_rows * G < ((int64_t)1 << 20) && avg > 3.0 * G) G <<= 1;
-    G = std::max(G, sell_long_row_lanes(avg));
-    if (const char* e = std::getenv("AMGX_SELL_MAX_LANES")) G = std::max(1, std::min(G, std::atoi(e)));   // test hook
+    G = std::max(G, sell_long_row_lanes(K, avg));
+    if (K.sell_max_lanes) G = std::min(G, K.sell_max_lanes);
     for (int g = G; g >= 1; g >>= 1)
       if ((double)sell_stored(A, g) <= max_pad * (double)D.nnz) { sellG = g; break; }
   }
@@ -813,9 +810,9 @@ static void upload_matrix(const amgx_matrix& A, DevMatrix& D, const char* what, 
   // (win < 0: the windowed form only as that fallback, never instead of an acceptable plain SELL image)
   const bool win_fallback_only = win < 0;
   if (win < 0) win = -win;
-  bool windowed = win > 0 && !win_fallback_only && sellG == 1 && (double)sell_stored(A, 1) > 1.10 * (double)D.nnz && !std::getenv("AMGX_NO_SELL_WINDOW");
+  bool windowed = win > 0 && !win_fallback_only && sellG == 1 && (double)sell_stored(A, 1) > 1.10 * (double)D.nnz && !K.no_sell_window;
   const bool try_win = win > 0 && sellG == 0 && allow_sell && A.br == 1 && A.bc == 1 && D.n_rows >= 4 * win && D.nnz > 0 && avg <= 12.0 &&
-                       !std::getenv("AMGX_NO_SELL_WINDOW") && !std::getenv("AMGX_NO_SELL_WINDOW_SHORT");
+                       !K.no_sell_window && !K.no_sell_window_short;
   std::vector<int32_t> rows;
   std::vector<uint16_t> rowloc;
   if (windowed || try_win) {
@@ -852,7 +849,7 @@ static void upload_matrix(const amgx_matrix& A, DevMatrix& D, const char* what, 
     D.sell.rowloc.upload(rowloc);
   } else if (sellG) {
     HostSell S;
-    build_sell(A, nullptr, A.n_rows, rowrel_ok && A.n_cols >= A.n_rows, sellG, S, rowrel_ok);
+    build_sell(A, nullptr, A.n_rows, rowrel_ok && A.n_cols >= A.n_rows, sellG, S, rowrel_ok && !K.no_diag_first);
     const bool wdiag = diag_override && S.diag_first && sellG == 1;
     if (wdiag) patch_sell_diag(S, A.n_rows, diag_override);
     D.fmt = FMT_SELL;
@@ -869,7 +866,7 @@ static void upload_matrix(const amgx_matrix& A, DevMatrix& D, const char* what, 
     // square blocks with near-uniform row lengths: block SELL (one lane per scalar row); the CSR arrays are kept only
     // if a block Gauss-Seidel sweep needs them
     bool bsell = false;
-    if (A.br == A.bc && (A.br == 2 || A.br == 3 || A.br == 6) && A.n_rows == A.n_cols && D.nnz > 0 && !std::getenv("AMGX_NO_BSELL"))
+    if (A.br == A.bc && (A.br == 2 || A.br == 3 || A.br == 6) && A.n_rows == A.n_cols && D.nnz > 0 && !K.no_bsell)
       bsell = build_bsell(A, D, 1.30);   // BSELL streams at ~5.6 TB/s vs ~4.0 TB/s of the CSR block kernels: worth up to ~35 % padding
     if (bsell && !keep_csr) return;
     std::vector<int32_t> rp(A.n_rows + 1);
@@ -924,7 +921,7 @@ static void build_bgs(const amgx_level_desc& d, DevLevel& L) {
   g.dinv_ptr.upload(d.bgs_dinv_ptr, (size_t)nb + 1);
   g.dinv.upload(d.bgs_dinv, (size_t)d.bgs_dinv_ptr[nb]);
   const int64_t nnz = d.A.rowptr[n];
-  if (nnz >= (int64_t)2147483647) throw Err("block Gauss-Seidel: too many entries for 32-bit offsets");
+  if (nnz >= I32_MAX) throw Err("block Gauss-Seidel: too many entries for 32-bit offsets");
   std::vector<int32_t> rp(n + 1);
   for (int64_t i = 0; i <= n; ++i) rp[i] = (int32_t)d.A.rowptr[i];
   g.rowptr.upload(rp);
@@ -1003,7 +1000,7 @@ static std::vector<int32_t> cluster_slices(const amgx_matrix& P, int spc) {
 
 // CH = fine rows per chunk; threads = workgroup size of the kernel that consumes the chunk (= CH unless several lanes share a row)
 // slice_list (optional, one thread per row only): chunk c = the 64-row slices slice_list[c * CH / 64 ...) (cluster_slices)
-static void build_restrict(const amgx_matrix& P, DevRestrict& R, int CH = RESTRICT_CHUNK, int max_entries = RESTRICT_MAX_ENTRIES, int threads = 0,
+static void build_restrict(const Knobs& K, const amgx_matrix& P, DevRestrict& R, int CH = RESTRICT_CHUNK, int max_entries = RESTRICT_MAX_ENTRIES, int threads = 0,
                            const std::vector<int32_t>* slice_list = nullptr) {
   if (threads <= 0) threads = CH;
   const int64_t nf = P.n_rows, nc = P.n_cols;
@@ -1079,11 +1076,11 @@ static void build_restrict(const amgx_matrix& P, DevRestrict& R, int CH = RESTRI
   R.max_entries = mx_chunk;
   R.ept = mx_chunk <= (int64_t)4 * threads ? 4 : 6;
   if ((CH == 256 || CH == 128) && threads == 512 && max_entries == 4 * 512) R.ept = mx_chunk <= (int64_t)2 * threads ? 2 : 4;     // (local-window chunks: see lw_image)
-  if (const char* e = std::getenv("AMGX_FUSED_EPT_MAX")) if (R.ept > std::atoi(e)) { R = DevRestrict(); return; }     // (A/B hook: keep the separate kernels instead)
+  if (R.ept > K.fused_ept_max) { R = DevRestrict(); return; }     // (A/B hook: keep the separate kernels instead)
   R.chunk_slot.upload(chunk_slot); R.slot_ptr.upload(slot_ptr); R.optr.upload(optr);
   // Measured NON-win (profiles/r01/restrict_fused.txt): storing the partial sums row by row (scattered stores in the
   // producer, streaming loads in restrict_sum_kernel) makes the cycle 2-4 % slower at cfg 2; off unless AMGX_RSUM_SORT=1.
-  if (!std::getenv("AMGX_RSUM_SORT")) R.oidx.upload(oidx);
+  if (!K.rsum_sort) R.oidx.upload(oidx);
   else {
     std::vector<int32_t> dest(ns);
     for (int64_t k = 0; k < ns; ++k) dest[oidx[k]] = (int32_t)k;
@@ -1094,10 +1091,21 @@ static void build_restrict(const amgx_matrix& P, DevRestrict& R, int CH = RESTRI
   if (slice_list) R.slice_list.upload(*slice_list);
 }
 
+// the chunk-local P^T of a fused down kernel: chunks of rows_per_chunk rows with up to `entries` entries of P, `threads` lanes per
+// workgroup.  The one place that decides between compact chunks (cluster_slices) and consecutive ones: compact where the caller's
+// own precondition (`compact`) holds and the level has AMGX_COMPACT_CHUNKS_MIN_ROWS rows
+static void build_restrict_chunks(const Knobs& K, const amgx_matrix& P, DevRestrict& R, int rows_per_chunk, int entries, int threads, bool compact) {
+  if (compact && K.compact_chunks_wanted(P.n_rows)) {
+    const std::vector<int32_t> sl = cluster_slices(P, rows_per_chunk / WAVE);
+    build_restrict(K, P, R, rows_per_chunk, entries, threads, &sl);
+  } else
+    build_restrict(K, P, R, rows_per_chunk, entries, threads);
+}
+
 // "local window" image of a long-row scalar matrix (sell_lw_pre_restrict_kernel): per chunk of LW_ROWS consecutive rows the sorted
 // list of its distinct columns; the SELL-2 image stores indices into that list.  vals: the (scaled) values in CSR order.
 // Returns false (nothing built) if a chunk touches more than LW_CAP distinct columns.
-static bool build_sell_lw(const amgx_matrix& A, const double* vals, int G, DevMatrix& D, DevBuf<int32_t>& d_cptr, DevBuf<int32_t>& d_ccol) {
+static bool build_sell_lw(const Knobs& K, const amgx_matrix& A, const double* vals, int G, DevMatrix& D, DevBuf<int32_t>& d_cptr, DevBuf<int32_t>& d_ccol) {
   const int64_t n = A.n_rows, nnz = A.rowptr[n];
   const int LW_ROWS = 512 / G;
   const int64_t nch = (n + LW_ROWS - 1) / LW_ROWS;
@@ -1106,9 +1114,8 @@ static bool build_sell_lw(const amgx_matrix& A, const double* vals, int G, DevMa
   lcol.resize((size_t)std::max<int64_t>(1, nnz));
   std::vector<std::vector<int32_t>> lists((size_t)nch);
   std::vector<char> no16((size_t)n, 0);                 // rows of chunks whose window would not fit: global 32-bit columns, no window
-  int64_t cap = LW_CAP;
-  const char* tcap = std::getenv("AMGX_LW_TEST_CAP");    // (tests: a smaller capacity sends some chunks through the no-window path)
-  if (tcap) cap = std::min<int64_t>(cap, std::atoll(tcap));
+  const int64_t cap = K.lw_cap(LW_CAP);
+  const bool tcap = K.lw_test_cap_on;
   std::vector<int64_t> n_over(setup_threads(), 0);
   par_for(nch, [&](int64_t c0, int64_t c1, int t) {
     std::vector<int32_t> u;
@@ -1158,12 +1165,12 @@ static bool build_sell_lw(const amgx_matrix& A, const double* vals, int G, DevMa
 // local-window form of a WINDOWED SELL image (sell_lw_win_spmv_kernel): windows of SELL_WIN consecutive rows stored by decreasing
 // length as in upload_matrix, columns = indices into the window's sorted list of distinct columns (at most QW_CAP; windows beyond
 // that keep 32-bit global columns).  rowptr / col / val: host CSR.  Returns false if too many windows miss the capacity.
-static bool build_sell_lw_windowed(int64_t n, int64_t n_cols, const int64_t* rowptr, const int32_t* col, const double* val, DevMatrix& D,
+static bool build_sell_lw_windowed(const Knobs& K, int64_t n, int64_t n_cols, const int64_t* rowptr, const int32_t* col, const double* val, DevMatrix& D,
                                    DevBuf<int32_t>& d_cptr, DevBuf<int32_t>& d_ccol) {
   const int win = SELL_WIN;
   const int64_t nnz = rowptr[n];
   const int64_t nw = (n + win - 1) / win;
-  SetupClock clk;
+  SetupClock clk(K);
   std::vector<int32_t> cnt((size_t)nw + 1, 0);
   RawVec<int32_t> lcol;
   lcol.resize((size_t)std::max<int64_t>(1, nnz));
@@ -1172,9 +1179,8 @@ static bool build_sell_lw_windowed(int64_t n, int64_t n_cols, const int64_t* row
   std::vector<int32_t> rows((size_t)n);
   std::vector<uint16_t> rowloc((size_t)n);
   std::vector<int64_t> n_over(setup_threads(), 0);
-  int64_t cap = QW_CAP;
-  const char* tcap = std::getenv("AMGX_LW_TEST_CAP");
-  if (tcap) cap = std::min<int64_t>(cap, std::max<int64_t>(8, std::atoll(tcap) / 4));
+  const int64_t cap = K.lw_cap_small(QW_CAP);
+  const bool tcap = K.lw_test_cap_on;
   par_for(nw, [&](int64_t q0, int64_t q1, int t) {
     std::vector<int32_t> u;
     for (int64_t q = q0; q < q1; ++q) {
@@ -1234,8 +1240,50 @@ struct MultiState;                      // multi-vector work space and captured 
 void multi_drop_graphs(MultiState* s);
 void multi_free(MultiState* s);
 
+// captured applications, keyed by what identifies one (the vector addresses): at most 16, the oldest capture goes first
+template <class Key>
+struct GraphCache {
+  std::map<Key, hipGraphExec_t> graphs;
+  std::vector<Key> age;                 // capture order
+  GraphCache() = default;
+  GraphCache(const GraphCache&) = delete;
+  GraphCache& operator=(const GraphCache&) = delete;
+  ~GraphCache() { drop(); }
+  void drop() {
+    for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
+    graphs.clear();
+    age.clear();
+  }
+  bool has(const Key& key) const { return graphs.count(key) != 0; }
+  // replays the graph of `key`; the first call with a key captures body() on `stream`
+  template <class Body>
+  void run(const Key& key, hipStream_t stream, Body&& body) {
+    auto it = graphs.find(key);
+    if (it == graphs.end()) {
+      hipGraph_t g = nullptr;
+      HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+      try { body(); }
+      catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(stream, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
+      HIPCHK(hipStreamEndCapture(stream, &g));
+      hipGraphExec_t ge = nullptr;
+      hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+      (void)hipGraphDestroy(g);
+      if (e != hipSuccess) throw Err(std::string("hipGraphInstantiate failed: ") + hipGetErrorString(e));
+      if (graphs.size() >= 16 && !age.empty()) {             // the oldest capture goes, the hot ones stay
+        auto old = graphs.find(age.front());
+        age.erase(age.begin());
+        if (old != graphs.end()) { (void)hipGraphExecDestroy(old->second); graphs.erase(old); }
+      }
+      it = graphs.emplace(key, ge).first;
+      age.push_back(key);
+    }
+    HIPCHK(hipGraphLaunch(it->second, stream));
+  }
+};
+
 struct Handle {
   int device = 0;
+  Knobs knobs;                          // the switches as amgx_create found them (knobs.hpp)
   std::vector<DevLevel> lev;
   int cycle = AMGX_CYCLE_V, clev = AMGX_CLEV_INV;
   int64_t coarse_n = 0;
@@ -1260,8 +1308,7 @@ struct Handle {
   DevBuf<double> dense_op;
   std::string err;
   struct GraphKey { const double* b; double* x; int kind; bool operator<(const GraphKey& o) const { return std::tie(b, x, kind) < std::tie(o.b, o.x, o.kind); } };
-  std::map<GraphKey, hipGraphExec_t> graphs;
-  std::vector<GraphKey> graph_age;      // capture order
+  GraphCache<GraphKey> graphs;
   MultiState* multi = nullptr;          // created by the first multi-vector call (multi.hpp)
   // staging for host-pointer calls
   DevBuf<double> stage[3];
@@ -1286,7 +1333,7 @@ struct Handle {
 
   ~Handle() {
     if (multi) multi_free(multi);
-    for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
+    graphs.drop();
     if (own_stream) (void)hipStreamDestroy(own_stream);
   }
 
@@ -1385,9 +1432,9 @@ struct Handle {
       unit_range(sp, WAVE / M.br, M.n_slices, a, b);
       if (b <= a) return;
       const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-      if (M.br == 6) hipLaunchKernelGGL((bsell_spmv_kernel<6, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(), x, y, ep);
-      else if (M.br == 3) hipLaunchKernelGGL((bsell_spmv_kernel<3, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(), x, y, ep);
-      else hipLaunchKernelGGL((bsell_spmv_kernel<2, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(), x, y, ep);
+      if (M.br == 6) hipLaunchKernelGGL((bsell_spmv_kernel<6, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(knobs.bsell_xmode), x, y, ep);
+      else if (M.br == 3) hipLaunchKernelGGL((bsell_spmv_kernel<3, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(knobs.bsell_xmode), x, y, ep);
+      else hipLaunchKernelGGL((bsell_spmv_kernel<2, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(knobs.bsell_xmode), x, y, ep);
     } else if (sp.part == PART_INT) {
       return;                                   // the CSR block formats are not split: everything runs in the boundary part
     } else if (M.br >= 2 && M.bc >= 2 && ((EP != EP_JAC && EP != EP_CHEB) || M.br == M.bc) && (M.br == M.bc || M.nnz >= 6 * M.n_rows)) {
@@ -1583,7 +1630,7 @@ struct Handle {
         const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
         if (s1 == s0) continue;
         const int grid = (s1 - s0 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-        const BSellMat BM = (lower_only && g.bsplit) ? g.blower.bsell.view() : g.bcopy.bsell.view();
+        const BSellMat BM = (lower_only && g.bsplit) ? g.blower.bsell.view(knobs.bsell_xmode) : g.bcopy.bsell.view(knobs.bsell_xmode);
         if (L.bs == 6) hipLaunchKernelGGL((bgs_bsell_color_kernel<6>), dim3(grid), dim3(BLOCK), 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x);
         else if (L.bs == 3) hipLaunchKernelGGL((bgs_bsell_color_kernel<3>), dim3(grid), dim3(BLOCK), 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x);
         else hipLaunchKernelGGL((bgs_bsell_color_kernel<2>), dim3(grid), dim3(BLOCK), 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x);
@@ -1621,12 +1668,12 @@ struct Handle {
     if (blk1 <= blk0) return;
     if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
     const bool fz = xin == nullptr;
-    const bool lw = !fz && &copy == &g.full && gsb_lw(g);
+    const bool lw = !fz && &copy == &g.full && g.lw;
     GsbArgs a{g.rowid.p, g.slotcolor.p, L.dinv.p, b, g.n_colors, dir, lw ? g.flw_cptr.p : nullptr, lw ? g.flw_ccol.p : nullptr};
     const SellMat M = lw ? g.fullLW.view() : copy.view();
-    const bool narrow = fz && &copy == &g.lowin && gsb_narrow(g);
+    const bool narrow = fz && &copy == &g.lowin && g.narrow;
 #define LAUNCH_GSB3(TT, GG, ZZ, WW) hipLaunchKernelGGL((gsb_sweep_kernel<TT, GG, ZZ, WW>), dim3(blk1 - blk0), dim3(TT), 0, stream, L.n, blk0, M, a, xin, xout)
-    const bool mid = !fz && &copy == &g.full && gsb_mid(g);
+    const bool mid = !fz && &copy == &g.full && g.mid;
 #define LAUNCH_GSBL(TT, GG, WW) hipLaunchKernelGGL((gsb_sweep_kernel<TT, GG, false, WW, true>), dim3(blk1 - blk0), dim3(TT), 0, stream, L.n, blk0, M, a, xin, xout)
 #define LAUNCH_GSB2(TT, GG) { if (narrow) LAUNCH_GSB3(TT, GG, true, 2); else if (fz) LAUNCH_GSB3(TT, GG, true, GSB_WP); \
                               else if (lw && mid && GG > 1) LAUNCH_GSBL(TT, (GG > 1 ? GG : 2), 5); else if (lw && GG > 1) LAUNCH_GSBL(TT, (GG > 1 ? GG : 2), GSB_WP); \
@@ -1648,7 +1695,7 @@ struct Handle {
     const DevBGSB& g = L.bgsb;
     const size_t lds = (size_t)2 * g.BB * L.bs * sizeof(double) + (size_t)g.BB * sizeof(int);
     // forward: colour phases over the couplings to lower colours, the upper ones stream with the sweep-start values; backward: reversed
-    const BSellMat IN = dir == 0 ? g.in.bsell.view() : g.upin.bsell.view(), OTH = dir == 0 ? g.upin.bsell.view() : g.in.bsell.view();
+    const BSellMat IN = dir == 0 ? g.in.bsell.view(knobs.bsell_xmode) : g.upin.bsell.view(knobs.bsell_xmode), OTH = dir == 0 ? g.upin.bsell.view(knobs.bsell_xmode) : g.in.bsell.view(knobs.bsell_xmode);
 #define LAUNCH_BGSB(BS_, MODE_, OFF_, LIST_, B0_, NB_, XIN_) hipLaunchKernelGGL((bgsb_sweep_kernel<BS_, MODE_>), dim3(NB_), dim3(BLOCK), lds, stream, g.BB, B0_, LIST_, \
                                                g.blk_ptr.p, g.blk_rows.p, OFF_, g.off_ptr.p, IN, OTH, g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, XIN_, xout)
 #define LAUNCH_BGSB_BS(MODE_, OFF_, LIST_, B0_, NB_, XIN_)                                       \
@@ -1666,7 +1713,7 @@ struct Handle {
       const bool fz = xin == nullptr;
       if (fz && dir != 0) throw Err("block-coloured Gauss-Seidel: the sweep from zero is a forward sweep");
       if (fz && !(lower_only && g.has_split)) throw Err("block-coloured Gauss-Seidel from zero needs the split images (zero x and sweep in place instead)");
-      const BSellMat OFFA = g.off.bsell.view(), OFFL = g.offlo.bsell.view();
+      const BSellMat OFFA = g.off.bsell.view(knobs.bsell_xmode), OFFL = g.offlo.bsell.view(knobs.bsell_xmode);
       for (int q = 0; q < g.n_bcolors; ++q) {
         const int c = dir ? g.n_bcolors - 1 - q : q;
         const int b0 = g.bc_ptr[c], nb = g.bc_ptr[c + 1] - b0;
@@ -1682,7 +1729,7 @@ struct Handle {
     if (blk1 <= blk0) return;
     if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
     (void)lower_only;
-    const BSellMat OFF = g.off.bsell.view();
+    const BSellMat OFF = g.off.bsell.view(knobs.bsell_xmode);
     const bool fz = xin == nullptr;
     if (fz) { LAUNCH_BGSB_BS(1, OFF, (const int32_t*)nullptr, blk0, blk1 - blk0, xin); }
     else { LAUNCH_BGSB_BS(0, OFF, (const int32_t*)nullptr, blk0, blk1 - blk0, xin); }
@@ -1730,14 +1777,20 @@ struct Handle {
     HIPCHK(hipGetLastError());
   }
 
+  // adds the partial sums of the chunk-local restriction of level l (restrict_chunk_kernel and the fused down kernels leave
+  // them in R.part) into the right-hand side of level l + 1
+  void restrict_sum(int l, const DevRestrict& R, double* b_coarse) {
+    hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
+                       R.oidx.p, R.part.p, b_coarse);
+  }
+
   void transfer_f2c(int l, const double* xf, double* xc) {                                               // dof_map.cpp:636-654
     Range rg("ProlMap::TransferF2C");
     const DevRestrict& R = lev[l].R;
     if (R.empty()) { mult(lev[l].PT, xf, xc); return; }
     hipLaunchKernelGGL(restrict_chunk_kernel, dim3(R.n_chunks), dim3(BLOCK), 0, stream, lev[l].n, R.chunk_slot.p, R.slot_ptr.p,
                        R.w.p, R.fi.p, xf, R.part.p, R.dest.p);
-    hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
-                       R.oidx.p, R.part.p, xc);
+    restrict_sum(l, R, xc);
     HIPCHK(hipGetLastError());
   }
   void add_c2f(int l, double fac, double* xf, const double* xc) { Range rg("ProlMap::TransferC2F"); mult_add(lev[l].P, fac, xc, xf, xf); }   // dof_map.cpp:697-709
@@ -1880,7 +1933,7 @@ struct Handle {
       const DevGS& g = L.gs;
       const int ns = g.bupper.n_slices;
       const int grid = (ns + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-      const BSellMat UM = g.bupper.bsell.view();
+      const BSellMat UM = g.bupper.bsell.view(knobs.bsell_xmode);
       if (L.bs == 6) hipLaunchKernelGGL((bgs_bsell_upper_residual_kernel<6>), dim3(grid), dim3(BLOCK), 0, stream, ns, UM, g.rowid.p, x, r);
       else if (L.bs == 3) hipLaunchKernelGGL((bgs_bsell_upper_residual_kernel<3>), dim3(grid), dim3(BLOCK), 0, stream, ns, UM, g.rowid.p, x, r);
       else hipLaunchKernelGGL((bgs_bsell_upper_residual_kernel<2>), dim3(grid), dim3(BLOCK), 0, stream, ns, UM, g.rowid.p, x, r);
@@ -1923,8 +1976,7 @@ struct Handle {
       }
       if (probe) HIPCHK(hipEventRecord(probe_e1, stream));
       if (!skip_rsum && sp.part != PART_INT)
-        hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
-                           R.oidx.p, R.part.p, b_coarse);
+        restrict_sum(l, R, b_coarse);
       HIPCHK(hipGetLastError());
       return;
     }
@@ -1957,8 +2009,7 @@ struct Handle {
       }
       if (probe) HIPCHK(hipEventRecord(probe_e1, stream));
       if (!skip_rsum)
-        hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
-                           R.oidx.p, R.part.p, b_coarse);
+        restrict_sum(l, R, b_coarse);
       HIPCHK(hipGetLastError());
       return;
     }
@@ -2000,8 +2051,7 @@ struct Handle {
       }
       if (probe) HIPCHK(hipEventRecord(probe_e1, stream));
       if (!skip_rsum && sp.part != PART_INT)
-        hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
-                           R.oidx.p, R.part.p, b_coarse);
+        restrict_sum(l, R, b_coarse);
       HIPCHK(hipGetLastError());
       return;
     }
@@ -2026,8 +2076,7 @@ struct Handle {
 #undef LAUNCH_CRF
       }
       if (!skip_rsum)
-        hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
-                           R.oidx.p, R.part.p, b_coarse);
+        restrict_sum(l, R, b_coarse);
       HIPCHK(hipGetLastError());
       return;
     }
@@ -2057,8 +2106,7 @@ struct Handle {
       if (M.lanes == 2) { if (R.ept == 2) LAUNCH_LWC(2, 2); else LAUNCH_LWC(4, 2); }
       else { if (R.ept == 2) LAUNCH_LWC(2, 4); else LAUNCH_LWC(4, 4); }
 #undef LAUNCH_LWC
-      hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
-                         R.oidx.p, R.part.p, b_coarse);
+      restrict_sum(l, R, b_coarse);
       HIPCHK(hipGetLastError());
       return;
     }
@@ -2080,8 +2128,7 @@ struct Handle {
       else { if (R.ept == 4) LAUNCH_PCR(4); else LAUNCH_PCR(6); }
 #undef LAUNCH_WCR
 #undef LAUNCH_PCR
-      hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
-                         R.oidx.p, R.part.p, b_coarse);
+      restrict_sum(l, R, b_coarse);
       HIPCHK(hipGetLastError());
     }
   }
@@ -2247,33 +2294,11 @@ struct Handle {
   void run_cycle(double* x, const double* b, bool graph_ok) {
     // the legacy default stream cannot be captured: launch directly there
     if (!(use_graph && graph_ok) || stream == nullptr) { do_cycle(x, b); return; }
-    GraphKey key{b, x, 0};
-    auto it = graphs.find(key);
-    if (it == graphs.end()) {
-      hipGraph_t g = nullptr;
-      HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-      try { do_cycle(x, b); }
-      catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(stream, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
-      HIPCHK(hipStreamEndCapture(stream, &g));
-      hipGraphExec_t ge = nullptr;
-      hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      if (e != hipSuccess) throw Err(std::string("hipGraphInstantiate failed: ") + hipGetErrorString(e));
-      if (graphs.size() >= 16 && !graph_age.empty()) {       // the oldest capture goes, the hot ones stay
-        auto old = graphs.find(graph_age.front());
-        graph_age.erase(graph_age.begin());
-        if (old != graphs.end()) { (void)hipGraphExecDestroy(old->second); graphs.erase(old); }
-      }
-      it = graphs.emplace(key, ge).first;
-      graph_age.push_back(key);
-    }
-    HIPCHK(hipGraphLaunch(it->second, stream));
+    graphs.run(GraphKey{b, x, 0}, stream, [&] { do_cycle(x, b); });
   }
 
   void drop_graphs() {
-    for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
-    graphs.clear();
-    graph_age.clear();
+    graphs.drop();
     if (multi) multi_drop_graphs(multi);
   }
 };
@@ -2282,7 +2307,7 @@ struct Handle {
 // construction
 // ---------------------------------------------------------------------------------------------------
 
-static void build_gs(const amgx_level_desc& d, DevLevel& L) {
+static void build_gs(const Knobs& K, const amgx_level_desc& d, DevLevel& L) {
   const int64_t n = d.A.n_rows;
   if (!d.color || d.n_colors <= 0) { if (n > 0) throw Err("AMGX_SM_GS needs a row colouring (color / n_colors)"); return; }
   const int nc = d.n_colors;
@@ -2320,7 +2345,7 @@ static void build_gs(const amgx_level_desc& d, DevLevel& L) {
     for (int c = 0; c <= nc; ++c) g.color_slice_ptr[c] = (int)(cstart[c] / R);
     HostSell S;
     // (absolute 16-bit column bases, not row-relative: the row product then does not depend on the rowid load)
-    const bool gs_rowrel = std::getenv("AMGX_GS_ROWREL") != nullptr;
+    const bool gs_rowrel = K.gs_rowrel;
     build_sell(d.A, rows.data(), (int64_t)rows.size(), gs_rowrel, G, S);
     upload_sell(S, g.sell);
     g.rowid.upload(rows);
@@ -2369,9 +2394,7 @@ static void build_gs(const amgx_level_desc& d, DevLevel& L) {
     // colour-major BSELL copy: every colour padded to whole slices of RB block rows (big levels: one more copy of A,
     // 2x the sweep speed; small levels keep the CSR row-list kernel: their colours are shorter than a slice)
     const int bs = d.A.br;
-    int64_t min_rows = 4096;
-    if (const char* e = std::getenv("AMGX_BGS_BSELL_MIN")) min_rows = std::atoll(e);      // test hook
-    if ((bs == 2 || bs == 3 || bs == 6) && n / std::max(1, nc) >= min_rows && !std::getenv("AMGX_NO_BGS_BSELL")) {
+    if ((bs == 2 || bs == 3 || bs == 6) && n / std::max(1, nc) >= K.bgs_bsell_min && !K.no_bgs_bsell) {
       const int RB = WAVE / bs;
       std::vector<int64_t> cstart(nc + 1, 0);
       for (int c = 0; c < nc; ++c) cstart[c + 1] = cstart[c] + ((cnt[c + 1] + RB - 1) / RB) * RB;
@@ -2384,7 +2407,7 @@ static void build_gs(const amgx_level_desc& d, DevLevel& L) {
         g.rowid.upload(prow);
         g.bsell_ok = true;
         // split copies (see the scalar case): need x_B = Dinv_B (b - L x)_B to imply (b - L x - D x)_B = 0, i.e. Dinv_B = A_BB^-1
-        bool plain_diag = d.dinv != nullptr && d.A.n_rows == d.A.n_cols && !std::getenv("AMGX_NO_BGS_SPLIT");
+        bool plain_diag = d.dinv != nullptr && d.A.n_rows == d.A.n_cols && !K.no_bgs_split;
         const int bb = bs * bs;
         for (int64_t i = 0; i < n && plain_diag; ++i) {
           if (d.color[i] < 0) continue;
@@ -2430,6 +2453,12 @@ static void build_gs(const amgx_level_desc& d, DevLevel& L) {
   }
 }
 
+struct HostCsr {
+  std::vector<int64_t> rowptr;
+  std::vector<int32_t> col;
+  std::vector<double> val;
+};
+
 }  // namespace amgx
 #include "devbuild.hpp"
 #include "spgemm.hpp"
@@ -2441,7 +2470,7 @@ namespace amgx {
 // local-window image of the colour-sorted block image `full` (gsb_sweep_kernel<..., LW>): per block of B rows the sorted list of its
 // distinct off-block columns; entries carry codes (in-block: row - r0 < B; off-block: B + position in the list).  Blocks whose list
 // exceeds GSB_LW_CAP keep global 32-bit columns.  rows: the slot -> row list of the block image (-1 = padding), slots = n_blocks * B.
-static bool build_gsb_full_lw(const amgx_matrix& A, const std::vector<int32_t>& rows, int64_t slots, int B, int G, DevGSB& g) {
+static bool build_gsb_full_lw(const Knobs& K, const amgx_matrix& A, const std::vector<int32_t>& rows, int64_t slots, int B, int G, DevGSB& g) {
   const int64_t n = A.n_rows, nnz = A.rowptr[n];
   const int64_t nb = (n + B - 1) / B;
   std::vector<int32_t> cnt((size_t)nb + 1, 0);
@@ -2450,9 +2479,8 @@ static bool build_gsb_full_lw(const amgx_matrix& A, const std::vector<int32_t>& 
   std::vector<std::vector<int32_t>> lists((size_t)nb);
   std::vector<char> no16((size_t)n, 0);
   std::vector<int64_t> n_over(setup_threads(), 0);
-  int64_t cap = GSB_LW_CAP;
-  const char* tcap = std::getenv("AMGX_LW_TEST_CAP");
-  if (tcap) cap = std::min<int64_t>(cap, std::max<int64_t>(8, std::atoll(tcap) / 4));
+  const int64_t cap = K.lw_cap_small(GSB_LW_CAP);
+  const bool tcap = K.lw_test_cap_on;
   par_for(nb, [&](int64_t b0, int64_t b1, int t) {
     std::vector<int32_t> u;
     for (int64_t kb = b0; kb < b1; ++kb) {
@@ -2494,7 +2522,7 @@ static bool build_gsb_full_lw(const amgx_matrix& A, const std::vector<int32_t>& 
   return true;
 }
 
-static void build_gsb(const amgx_level_desc& d, DevLevel& L, const amgx_matrix* P, const DevCsrSrc* csr = nullptr) {
+static void build_gsb_images(const Knobs& K, const amgx_level_desc& d, DevLevel& L, const amgx_matrix* P, const DevCsrSrc* csr) {
   const int64_t n = d.A.n_rows;
   DevGSB& g = L.gsb;
   const int B = d.gs_block_rows;
@@ -2561,13 +2589,11 @@ static void build_gsb(const amgx_level_desc& d, DevLevel& L, const amgx_matrix* 
   {
     // long-row square levels: local-window image of `full` for the general sweep
     const double avgA = n ? (double)d.A.rowptr[n] / (double)n : 0.0;
-    int64_t lw_min_rows = 100000;
-    if (const char* e = std::getenv("AMGX_LW_MIN_ROWS")) lw_min_rows = std::atoll(e);
     // Measured NON-win at cfg 2 (profiles/r04/gs_experiments.txt): level-1 backward sweep 231 us with the window against 196 us without
     // (the extra barrier and the window's registers cost more than the gathers of the off-block values, which this kernel issues
     // back to back in one burst).  Built and tested, off unless AMGX_GSB_LW=1.
-    if (avgA >= 24.0 && n >= lw_min_rows && d.A.n_cols == n && G > 1 && !std::getenv("AMGX_NO_LW") && std::getenv("AMGX_GSB_LW"))
-      build_gsb_full_lw(d.A, rows, slots, B, G, g);
+    if (avgA >= 24.0 && K.lw_wanted(n) && d.A.n_cols == n && G > 1 && K.gsb_lw)
+      build_gsb_full_lw(K, d.A, rows, slots, B, G, g);
   }
   if (csr) {
     // device builders: the colour-sorted image of A, the split by kernels, the images of its two parts
@@ -2609,30 +2635,27 @@ static void build_gsb(const amgx_level_desc& d, DevLevel& L, const amgx_matrix* 
     HIPCHK(hipGetLastError());
     int hbad = 0;
     HIPCHK(hipMemcpy(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (hbad || std::getenv("AMGX_GSB_NO_SPLIT")) { g.cvec.release(); return; }
+    if (hbad || K.gsb_no_split) { g.cvec.release(); return; }
     {
       DevBuf<int64_t> sp;
       const int64_t stored = dev_slice_offsets(part[0], g.rowid.p, slots, sp, G);
       dev_build_sell(part[0], g.rowid.p, slots, G, false, false, nullptr, 0.0, nullptr, sp, stored, g.lowin, nullptr);
       g.lowin_maxw = max_width(g.lowin, "lower part");
     }
-    if (!dev_upload_matrix(part[1], g.rest, false, 1.6, SELL_WIN, nullptr)) {
+    if (!dev_upload_matrix(K, part[1], g.rest, false, 1.6, SELL_WIN, nullptr)) {
       // (the host builder's CSR fallback for a badly padded remainder: from the host copy of the part)
       std::vector<int64_t> rp = db_download(part[1].rowptr, (size_t)n + 1);
       std::vector<int32_t> cc = db_download(part[1].col, (size_t)std::max<int64_t>(1, part[1].nnz));
       std::vector<double> vv = db_download(part[1].val, (size_t)std::max<int64_t>(1, part[1].nnz));
       amgx_matrix F = d.A;
       F.rowptr = rp.data(); F.col = cc.data(); F.val = vv.data();
-      upload_matrix(F, g.rest, "A (block-hybrid Gauss-Seidel: rest)", true, false, false, 1.6, SELL_WIN);
+      upload_matrix(K, F, g.rest, "A (block-hybrid Gauss-Seidel: rest)", true, false, false, 1.6, SELL_WIN);
     }
     g.has_split = true;
     {
       // long-row levels: local-window image of the rest part (host builder from the downloaded part)
       const double avgA = n ? (double)csr->nnz / (double)n : 0.0;
-      int64_t lw_min_rows = 100000;
-      if (const char* e = std::getenv("AMGX_LW_MIN_ROWS")) lw_min_rows = std::atoll(e);
-      if (P && avgA >= 24.0 && n >= lw_min_rows && d.A.n_cols == n && P->br == 1 && P->bc == 1 && P->rowptr[P->n_rows] < (int64_t)2147483647 &&
-          !std::getenv("AMGX_NO_LW") && !std::getenv("AMGX_NO_FUSED_RESTRICT")) {
+      if (P && avgA >= 24.0 && K.lw_wanted(n) && d.A.n_cols == n && K.fused_restrict_ok(*P, 1)) {
         // (device builder first, devbuild.hpp dev_build_lw; the host builder works from the downloaded part)
         std::vector<int64_t> rp;
         std::vector<int32_t> cc;
@@ -2645,18 +2668,15 @@ static void build_gsb(const amgx_level_desc& d, DevLevel& L, const amgx_matrix* 
             vv = db_download(part[1].val, (size_t)std::max<int64_t>(1, part[1].nnz));
             F.rowptr = rp.data(); F.col = cc.data(); F.val = vv.data();
           }
-          return build_sell_lw(F, F.val, gg, M, cp, cl);
+          return build_sell_lw(K, F, F.val, gg, M, cp, cl);
         };
-        const bool dev_lw = !std::getenv("AMGX_HOST_LW");
-        const bool verify_lw = std::getenv("AMGX_VERIFY_IMAGES") != nullptr;
+        const bool dev_lw = !K.host_lw;
+        const bool verify_lw = K.verify_images;
         int G = 0;
         for (int gg : {2, 4}) {
           bool ok = false;
           if (dev_lw) {
-            int64_t cap = LW_CAP;
-            const char* tcap = std::getenv("AMGX_LW_TEST_CAP");
-            if (tcap) cap = std::min<int64_t>(cap, std::atoll(tcap));
-            ok = dev_build_lw(part[1], false, gg, cap, tcap != nullptr, nullptr, 0.0, g.restLW, g.lw_cptr, g.lw_ccol);
+            ok = dev_build_lw(part[1], false, gg, K.lw_cap(LW_CAP), K.lw_test_cap_on, nullptr, 0.0, g.restLW, g.lw_cptr, g.lw_ccol);
             if (ok && verify_lw) {
               DevMatrix H; DevBuf<int32_t> hp, hc;
               if (!host_lw(gg, H, hp, hc)) throw Err("AMGX_VERIFY_IMAGES: Gauss-Seidel rest (local window): the host builder declines what the device builder forms");
@@ -2669,15 +2689,14 @@ static void build_gsb(const amgx_level_desc& d, DevLevel& L, const amgx_matrix* 
           g.restLW = DevMatrix();
         }
         if (G) {
-          build_restrict(*P, L.RG, 512 / G, 4 * 512, 512);
+          build_restrict(K, *P, L.RG, 512 / G, 4 * 512, 512);
           if (!L.RG.empty()) return;
           g.restLW = DevMatrix(); g.lw_cptr.release(); g.lw_ccol.release();
         }
       }
     }
-    if (P && g.rest.fmt == FMT_SELL && g.rest.lanes == 1 && P->br == 1 && P->bc == 1 &&
-        P->rowptr[P->n_rows] < (int64_t)2147483647 && !std::getenv("AMGX_NO_FUSED_RESTRICT"))
-      build_restrict(*P, L.RG, 512, 6 * 512);
+    if (P && g.rest.fmt == FMT_SELL && g.rest.lanes == 1 && K.fused_restrict_ok(*P, 1))
+      build_restrict(K, *P, L.RG, 512, 6 * 512);
     return;
   }
   {
@@ -2739,7 +2758,7 @@ static void build_gsb(const amgx_level_desc& d, DevLevel& L, const amgx_matrix* 
   });
   bool ok = true;
   for (char c : bad) if (c) ok = false;
-  if (ok && !std::getenv("AMGX_GSB_NO_SPLIT")) {
+  if (ok && !K.gsb_no_split) {
     amgx_matrix F = d.A;
     F.rowptr = rp[0].data(); F.col = cc[0].data(); F.val = vv[0].data();
     HostSell S;
@@ -2750,28 +2769,29 @@ static void build_gsb(const amgx_level_desc& d, DevLevel& L, const amgx_matrix* 
     for (size_t q = 0; q + 1 < S.slice_ptr.size(); ++q)
       g.lowin_maxw = std::max(g.lowin_maxw, (int)(((S.slice_ptr[q + 1] & ~(int64_t)63) - (S.slice_ptr[q] & ~(int64_t)63)) / WAVE));
     F.rowptr = rp[1].data(); F.col = cc[1].data(); F.val = vv[1].data();
-    upload_matrix(F, g.rest, "A (block-hybrid Gauss-Seidel: rest)", true, false, false, 1.6, SELL_WIN);
+    upload_matrix(K, F, g.rest, "A (block-hybrid Gauss-Seidel: rest)", true, false, false, 1.6, SELL_WIN);
     g.cvec.upload(cv);
     g.has_split = true;
     {
       const double avgA = n ? (double)d.A.rowptr[n] / (double)n : 0.0;
-      int64_t lw_min_rows = 100000;
-      if (const char* e = std::getenv("AMGX_LW_MIN_ROWS")) lw_min_rows = std::atoll(e);
-      if (P && avgA >= 24.0 && n >= lw_min_rows && d.A.n_cols == n && P->br == 1 && P->bc == 1 && P->rowptr[P->n_rows] < (int64_t)2147483647 &&
-          !std::getenv("AMGX_NO_LW") && !std::getenv("AMGX_NO_FUSED_RESTRICT")) {
+      if (P && avgA >= 24.0 && K.lw_wanted(n) && d.A.n_cols == n && K.fused_restrict_ok(*P, 1)) {
         int G = 0;
-        for (int gg : {2, 4}) if (build_sell_lw(F, F.val, gg, g.restLW, g.lw_cptr, g.lw_ccol)) { G = gg; break; } else g.restLW = DevMatrix();
+        for (int gg : {2, 4}) if (build_sell_lw(K, F, F.val, gg, g.restLW, g.lw_cptr, g.lw_ccol)) { G = gg; break; } else g.restLW = DevMatrix();
         if (G) {
-          build_restrict(*P, L.RG, 512 / G, 4 * 512, 512);
+          build_restrict(K, *P, L.RG, 512 / G, 4 * 512, 512);
           if (!L.RG.empty()) return;
           g.restLW = DevMatrix(); g.lw_cptr.release(); g.lw_ccol.release();
         }
       }
     }
-    if (P && g.rest.fmt == FMT_SELL && g.rest.lanes == 1 && P->br == 1 && P->bc == 1 &&
-        P->rowptr[P->n_rows] < (int64_t)2147483647 && !std::getenv("AMGX_NO_FUSED_RESTRICT"))
-      build_restrict(*P, L.RG, 512, 6 * 512);
+    if (P && g.rest.fmt == FMT_SELL && g.rest.lanes == 1 && K.fused_restrict_ok(*P, 1))
+      build_restrict(K, *P, L.RG, 512, 6 * 512);
   }
+}
+
+static void build_gsb(const Knobs& K, const amgx_level_desc& d, DevLevel& L, const amgx_matrix* P, const DevCsrSrc* csr = nullptr) {
+  build_gsb_images(K, d, L, P, csr);
+  gsb_set_paths(K, L.gsb);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2853,7 +2873,7 @@ static void build_bsell_sel(const amgx_matrix& A, const std::vector<int32_t>& ro
 // Block-hybrid Gauss-Seidel data of a square-block level (bgsb_sweep_kernel); the blocked colouring is validated (two coupled
 // rows of one workgroup block sharing a colour would be a data race)
 // csr: the level matrix on the device (big levels): the images are then gathered there (devbuild.hpp, dev_build_bsell)
-static void build_bgsb(const amgx_level_desc& d, DevLevel& L, const DevBcsrSrc* csr = nullptr) {
+static void build_bgsb(const Knobs& K, const amgx_level_desc& d, DevLevel& L, const DevBcsrSrc* csr = nullptr) {
   const int64_t n = d.A.n_rows;
   const int bs = d.A.br, RB = WAVE / bs;
   DevBGSB& g = L.bgsb;
@@ -3008,7 +3028,7 @@ static void build_bgsb(const amgx_level_desc& d, DevLevel& L, const DevBcsrSrc* 
   g.blk_ptr.upload(blk_ptr); g.blk_rows.upload(blk_rows);
   g.off_ptr.upload(off_ptr); g.in_ptr.upload(in_ptr); g.in_row.upload(in_row);
   // ---- one-pass pre-smoothing from zero: valid where dinv_k is a true inverse of fac_k * A_kk (not a pseudo-inverse) ----------
-  if (std::getenv("AMGX_BGSB_NO_SPLIT")) return;
+  if (K.bgsb_no_split) return;
   std::vector<double> fac((size_t)n, 1.0);
   std::vector<char> nofac(setup_threads(), 0);
   par_for(n, [&](int64_t i0, int64_t i1, int t) {
@@ -3061,12 +3081,6 @@ static void build_bgsb(const amgx_level_desc& d, DevLevel& L, const DevBcsrSrc* 
                   [&](int32_t i, int32_t j) { return (i == j && d.color[i] >= 0) ? fac[i] - 1.0 : -1.0; });
   g.has_split = true;
 }
-
-struct HostCsr {
-  std::vector<int64_t> rowptr;
-  std::vector<int32_t> col;
-  std::vector<double> val;
-};
 
 // (block form: A has bs x bs blocks, P and Q bs x bc blocks, dinv bs x bs per block row)
 static void fold_prolongation(const amgx_matrix& A, const amgx_matrix& P, const double* dinv, double omega, HostCsr& Q) {
@@ -3204,12 +3218,12 @@ static void permute_matrix(const amgx_matrix& M, const int32_t* rperm, const int
 static void use_csr(amgx_matrix& M, const HostCsr& c) { M.rowptr = c.rowptr.data(); M.col = c.col.data(); M.val = c.val.data(); }
 
 // fills pl (mutable copies of the level descriptors) with colour-major versions of the GS levels; store owns the data
-static void permute_gs_levels(const amgx_hierarchy_desc* d, std::vector<amgx_level_desc>& pl, std::vector<LevelPerm>& store) {
+static void permute_gs_levels(const Knobs& K, const amgx_hierarchy_desc* d, std::vector<amgx_level_desc>& pl, std::vector<LevelPerm>& store) {
   const int L = d->n_levels;
   // Measured NON-win (profiles/r01/gs_perm.txt): the colour kernels gain 7-20 %, but the transfers lose far more
   // (P^T gathers its ~30 fine residuals per coarse row from 8 colour blocks: 129 -> 370 us; P: 78 -> 132 us) and the two
   // translation passes cost 125 us: cycle 2.35 -> 2.54 ms at cfg 2.  Off unless AMGX_GS_PERM=1 (kept under test).
-  if (!std::getenv("AMGX_GS_PERM")) return;
+  if (!K.gs_perm) return;
   for (int l = 0; l < L; ++l) if (pl[l].A.n_rows != pl[l].A.n_cols) return;     // rank-partitioned handle: vectors carry ghosts
   bool any = false;
   for (int l = 0; l + 1 < L; ++l) {
@@ -3251,695 +3265,7 @@ static void permute_gs_levels(const amgx_hierarchy_desc* d, std::vector<amgx_lev
 
 }  // namespace amgx
 #include "dense_spd.hpp"
-namespace amgx {
-
-// ---- collapsed coarse levels (see dense_op_gemv_kernel) -----------------------------------------------------------
-// Picks the first level l_c >= 1 from which the sub-cycle is cheaper as one dense GEMV than as its dependent launches,
-// forms B column by column with the handle's own kernels (so B is exactly the operator the separate launches apply,
-// whatever the smoother form) and stores it row-major.  AMGX_NO_DENSE_TAIL=1 disables, AMGX_DENSE_MAX=<n> caps n.
-// first_level: 1 for a handle whose level 0 carries the caller's vectors; 0 for the replicated tail of a rank-partitioned
-// hierarchy, where the whole handle may become one GEMV on the gathered vector
-static void build_dense_tail(Handle& h, const amgx_hierarchy_desc* d, const amgx_level_desc* levels, int first_level = 1) {
-  const int L = d->n_levels;
-  if (d->cycle != AMGX_CYCLE_V || L < 2 + first_level || std::getenv("AMGX_NO_DENSE_TAIL")) return;
-  int64_t cap = 8192;
-  if (const char* e = std::getenv("AMGX_DENSE_MAX")) cap = std::max<int64_t>(0, std::atoll(e));
-  for (int l = 0; l < L; ++l) if (h.lev[l].ncols != h.lev[l].n) return;       // rank-partitioned levels are driven stage by stage
-  // dependent launches one cycle spends on level m (both directions), ~5 us each
-  auto launches = [&](int m) -> double {
-    const DevLevel& V = h.lev[m];
-    const int k = std::max(1, V.sm_steps) * (V.sm_symm ? 2 : 1);
-    if (V.sm_type == AMGX_SM_JACOBI) return h.folded(V) ? 3.0 : 2.0 + 3.0 * k;
-    if (V.sm_type == AMGX_SM_CHEBY) return 3.0 + 2.0 * k * (V.cheb_degree + 1);
-    if (V.sm_type == AMGX_SM_BGS) return 3.0 + 2.0 * k * std::max(1, V.bgs.n_colors);
-    if (V.gsb.on() || V.bgsb.on()) return 2.0 + 3.0 * k;
-    return 3.0 + 2.0 * k * std::max(1, V.gs.n_colors);
-  };
-  int lc = -1;
-  double est = 5.0;                               // the coarse solve
-  std::vector<double> est_from(L, 0.0);
-  for (int m = L - 2; m >= first_level; --m) { est += 5.0 * launches(m); est_from[m] = est; }
-  for (int m = first_level; m <= L - 2; ++m) {
-    const int64_t N = h.lev[m].len();
-    if (N < 1 || N > cap) continue;
-    const double dense_us = 4.0 + 8.0 * (double)N * (double)N / 4.0e6;      // ~4 TB/s on a few hundred workgroups
-    if (dense_us < 0.8 * est_from[m]) { lc = m; break; }
-  }
-  if (lc < first_level) return;
-  const int N = (int)h.lev[lc].len();
-  const int ld = (N + 1) & ~1;
-  DevBuf<double> Bt;
-  Bt.alloc((size_t)N * ld);
-  h.dense_op.alloc((size_t)N * ld);
-  HIPCHK(hipMemsetAsync(Bt.p, 0, (size_t)N * ld * sizeof(double), h.stream));
-  HIPCHK(hipMemsetAsync(h.dense_op.p, 0, (size_t)N * ld * sizeof(double), h.stream));
-  const int saved_tail = h.tail_level;
-  h.tail_level = -1;                              // the sub-cycle runs as separate launches from level lc
-  DevLevel& V = h.lev[lc];
-  try {
-    for (int j = 0; j < N; ++j) {
-      hipLaunchKernelGGL(dense_unit_kernel, dim3(Handle::grid_for(N)), dim3(BLOCK), 0, h.stream, (int64_t)N, (int64_t)j, V.rhs.p);
-      h.cycle_v(V.x.p, V.rhs.p, lc);                // (dense_level is still -1: separate launches)
-      HIPCHK(hipMemcpyAsync(Bt.p + (size_t)j * ld, V.x.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, h.stream));
-      if ((j & 255) == 255) HIPCHK(hipStreamSynchronize(h.stream));          // bound the depth of the launch queue
-    }
-    const int tb = (N + 15) / 16;
-    hipLaunchKernelGGL(dense_transpose_kernel, dim3(tb, tb), dim3(BLOCK), 0, h.stream, N, ld, Bt.p, h.dense_op.p);
-    HIPCHK(hipGetLastError());
-    // leave the work vectors of the collapsed levels as create() made them
-    for (int m = lc; m < L; ++m) {
-      const size_t len = (size_t)std::max<int64_t>(1, h.lev[m].ext_len());
-      for (double* v : {h.lev[m].x.p, h.lev[m].rhs.p, h.lev[m].res.p, h.lev[m].tmp.p}) HIPCHK(hipMemsetAsync(v, 0, len * sizeof(double), h.stream));
-    }
-    HIPCHK(hipStreamSynchronize(h.stream));
-  } catch (...) { h.tail_level = saved_tail; throw; }
-  h.tail_level = saved_tail;
-  h.dense_level = lc;
-  h.dense_n = N;
-  h.dense_ld = ld;
-}
-
-// Chebyshev levels without an interval from the caller: lmax = 1.1 x a 30-step power-iteration estimate (defined next to the
-// deterministic reductions it uses, at the end of this file)
-static void cheb_estimate(Handle& h);
-
-// dense_first: first level that may be collapsed into the dense operator (see build_dense_tail); < 0: never
-static Handle* create(const amgx_hierarchy_desc* d, int dense_first = 1) {
-  if (!d || d->n_levels < 1 || !d->levels) throw Err("amgx_create: empty hierarchy descriptor");
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev == 0) throw Err("amgx_create: no HIP device available (the apply path has no CPU fallback)");
-  if (d->device < 0 || d->device >= ndev) throw Err("amgx_create: device ordinal out of range");
-  HIPCHK(hipSetDevice(d->device));
-  auto h = std::make_unique<Handle>();
-  h->device = d->device;
-  h->cycle = d->cycle;
-  h->clev = d->clev;
-  h->use_graph = d->use_graph != 0;
-  h->ep_nt = (std::getenv("AMGX_NO_EP_NT") ? 0 : EPF_NT) | (std::getenv("AMGX_NO_EP_HOIST") ? 0 : EPF_HOIST);   // A/B: -0.4 % cycle time (profiles/r01/restrict_fused.txt)
-  if (d->cycle < 0 || d->cycle > 2) throw Err("amgx_create: unknown cycle");
-  HIPCHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-  h->stream = h->own_stream;
-  h->lev.resize(d->n_levels);
-  std::vector<amgx_level_desc> pl(d->levels, d->levels + d->n_levels);
-  std::vector<LevelPerm> pstore(d->n_levels);
-  permute_gs_levels(d, pl, pstore);
-  SetupClock clk;
-  clk.lap("renumbering of Gauss-Seidel levels");
-  h->perm.resize(d->n_levels);
-  for (int l = 0; l < d->n_levels; ++l) if (!pstore[l].perm.empty()) h->perm[l].upload(pstore[l].perm);
-  const amgx_level_desc* levels = pl.data();
-  for (int l = 0; l < d->n_levels; ++l) {
-    const amgx_level_desc& s = levels[l];
-    DevLevel& L = h->lev[l];
-    // n_cols > n_rows: the trailing columns are ghost entries of a rank-partitioned level (filled by the caller's
-    // halo exchange before every operation that gathers from them)
-    if (s.A.n_cols < s.A.n_rows || s.A.br != s.A.bc) throw Err("level matrix must have n_cols >= n_rows and square blocks");
-    L.n = s.A.n_rows; L.ncols = s.A.n_cols; L.bs = s.A.br;
-    L.sm_type = s.sm_type; L.omega = s.omega; L.sm_steps = s.sm_steps; L.sm_symm = s.sm_symm;
-    if (s.sm_type != AMGX_SM_JACOBI && s.sm_type != AMGX_SM_GS && s.sm_type != AMGX_SM_BGS && s.sm_type != AMGX_SM_CHEBY) throw Err("unknown smoother type");
-    const bool last = (l + 1 == d->n_levels);
-    if (s.sm_type == AMGX_SM_CHEBY) {
-      const int deg = s.cheb_degree == 0 ? 2 : s.cheb_degree;
-      if (deg < 1 || deg > 8) throw Err("amgx_create: cheb_degree must be 1 .. 8 (0: default 2), got " + std::to_string(s.cheb_degree));
-      if (!(s.cheb_lambda_max >= 0.0)) throw Err("amgx_create: cheb_lambda_max must be >= 0 (0: estimated on the device)");
-      if (s.cheb_ratio != 0.0 && !(s.cheb_ratio > 1.0)) throw Err("amgx_create: cheb_ratio must be > 1 (0: default 10)");
-      if (s.A.n_cols != s.A.n_rows) throw Err("amgx_create: the Chebyshev smoother is not available on rank-partitioned levels");
-      L.cheb_degree = deg;
-      L.cheb_ratio = s.cheb_ratio == 0.0 ? 10.0 : s.cheb_ratio;
-      if (s.cheb_lambda_max > 0.0) L.cheb_set_interval(s.cheb_lambda_max);
-    }
-    check_matrix(s.A, "A");            // (before anything reads rowptr[n_rows]: a NULL / garbage descriptor is an error, not a crash)
-    // (declared BEFORE the task pool: its worker lambdas capture these by reference, and an exception between tasks.run() and
-    //  tasks.wait() must join the workers -- ~SetupTasks -- before the buffers they read are freed)
-    DevCsrSrc csrA;
-    DbDiagInfo diagA;
-    DevBcsrSrc csrB;
-    SetupTasks tasks(d->device);
-    // big scalar levels: the CSR arrays go to the device once and kernels write the images of A, A' and Q there (devbuild.hpp)
-    const bool dev_images = dev_images_wanted(s.A);
-    const bool verify_images = dev_images && std::getenv("AMGX_VERIFY_IMAGES") != nullptr;
-    if (dev_images) {
-      check_matrix(s.A, "A");
-      csrA.upload(s.A);
-      if (s.dinv) L.dinv.upload(s.dinv, (size_t)(last ? L.n : L.ncols) * L.bs * L.bs);
-      diagA = dev_diag_check(csrA, (s.dinv && s.A.n_rows <= s.A.n_cols) ? L.dinv.p : nullptr);
-      clk.lap("CSR of A to the device", l);
-    }
-    // big square-block levels: the block-CSR arrays go to the device once, the BSELL images (A; the block-hybrid Gauss-Seidel
-    // images) are gathered there
-    const bool keep_csr_A = s.sm_type == AMGX_SM_GS && s.A.br > 1 && s.gs_block_rows == 0;
-    const bool dev_bsell = dev_bsell_wanted(s.A) && s.A.n_rows == s.A.n_cols && !keep_csr_A;
-    const bool verify_bsell = dev_bsell && std::getenv("AMGX_VERIFY_IMAGES") != nullptr;
-    if (dev_bsell) {
-      check_matrix(s.A, "A");
-      csrB.upload(s.A);
-      clk.lap("block CSR of A to the device", l);
-    }
-    // block GS walks the CSR arrays of A, so keep A in CSR there
-    tasks.run([&] {
-      if (dev_bsell) {
-        if (dev_build_bsell(csrB, nullptr, 0, BB_ALL, DbBgsbMaps(), 0, 1.30, L.A)) {
-          L.A.n_rows = s.A.n_rows; L.A.n_cols = s.A.n_cols; L.A.br = s.A.br; L.A.bc = s.A.bc;
-          L.A.nnz = s.A.rowptr[s.A.n_rows];
-          L.A.lanes = pick_lanes(L.A.n_rows ? (double)L.A.nnz / (double)L.A.n_rows : 0.0);
-          if (verify_bsell) { DevMatrix H; upload_matrix(s.A, H, "A", true, true, false); if (H.lanes != L.A.lanes || H.nnz != L.A.nnz) throw Err("AMGX_VERIFY_IMAGES: A: descriptors differ"); verify_same_bsell(L.A, H, "A"); }
-          return;
-        }
-        L.A = DevMatrix();
-      }
-      if (dev_images && dev_upload_matrix(csrA, L.A, true, 1.35, 0, &diagA)) {
-        if (verify_images) { DevMatrix H; upload_matrix(s.A, H, "A", true, true, false); verify_same_image(L.A, H, "A"); }
-        return;
-      }
-      if (verify_images) {
-        DevMatrix H;
-        upload_matrix(s.A, H, "A", true, true, false);
-        if (H.fmt == FMT_SELL && H.lanes == 1) throw Err("AMGX_VERIFY_IMAGES: the device builder declined A where the host builder forms a SELL image");
-      }
-      upload_matrix(s.A, L.A, "A", true, true, s.sm_type == AMGX_SM_GS && s.A.br > 1 && s.gs_block_rows == 0);
-    }, "A");
-    if (!last) {
-      const amgx_level_desc& c = levels[l + 1];
-      if (s.P.n_rows != s.A.n_rows || s.P.n_cols > c.A.n_cols || s.P.n_cols < c.A.n_rows || s.P.br != s.A.br || s.P.bc != c.A.br)
-        throw Err("P does not match the level matrices");
-      if (s.PT.n_rows != s.P.n_cols || s.PT.n_cols != s.P.n_rows || s.PT.br != s.P.bc || s.PT.bc != s.P.br)
-        throw Err("PT does not match P");
-      if (!s.dinv) throw Err("dinv missing");
-      tasks.run([&] {
-        upload_matrix(s.P, L.P, "P", true, false, false, 1.35, s.P.br == 1 && s.P.bc == 1 ? -SELL_WIN : 0, nullptr, 1);
-        upload_matrix(s.PT, L.PT, "PT", true, false, false, 1.35, 0, nullptr, 2);
-        // big scalar levels restrict through the column-blocked form (the P^T gather is TA/L2-bound there)
-        // Measured non-win (profiles/r01/restrict_blocked.txt): 121 + 22 us vs 134 us for the P^T gather at cfg 2,
-        // so the blocked form is OFF unless AMGX_RESTRICT_MIN_ROWS asks for it (kept for the fused-residual plan).
-        int64_t min_rows = INT64_MAX;
-        if (const char* e = std::getenv("AMGX_RESTRICT_MIN_ROWS")) min_rows = std::atoll(e);
-        if (s.P.br == 1 && s.P.bc == 1 && s.P.n_rows >= min_rows && s.P.rowptr[s.P.n_rows] < (int64_t)2147483647)
-          build_restrict(s.P, L.R);
-      }, "P, PT");
-      tasks.run([&] {
-        if (!dev_images) L.dinv.upload(s.dinv, (size_t)L.ncols * L.bs * L.bs);
-        if (s.sm_type == AMGX_SM_GS && s.gs_block_rows > 0 && s.A.br > 1) {
-          build_bgsb(s, L, dev_bsell ? &csrB : nullptr);
-          if (verify_bsell) {
-            DevLevel H;
-            H.n = L.n; H.ncols = L.ncols; H.bs = L.bs;
-            build_bgsb(s, H, nullptr);
-            const DevBGSB &x = L.bgsb, &y = H.bgsb;
-            if (x.BB != y.BB || x.n_blocks != y.n_blocks || x.n_colors != y.n_colors || x.has_split != y.has_split) throw Err("AMGX_VERIFY_IMAGES: block-hybrid Gauss-Seidel (blocks): the descriptors differ");
-            verify_same_bsell(x.off, y.off, "block-hybrid Gauss-Seidel: off");
-            verify_same_bsell(x.in, y.in, "block-hybrid Gauss-Seidel: in");
-            verify_same_bsell(x.upin, y.upin, "block-hybrid Gauss-Seidel: upin");
-            if (x.has_split) verify_same_bsell(x.rest, y.rest, "block-hybrid Gauss-Seidel: rest");
-            if (x.bc != y.bc || x.n_bcolors != y.n_bcolors) throw Err("AMGX_VERIFY_IMAGES: block-coloured Gauss-Seidel: the descriptors differ");
-            if (x.bc && x.has_split) verify_same_bsell(x.offlo, y.offlo, "block-coloured Gauss-Seidel: offlo");
-          }
-        }
-        else if (s.sm_type == AMGX_SM_GS && s.gs_block_rows > 0) {
-          build_gsb(s, L, &s.P, dev_images ? &csrA : nullptr);
-          if (verify_images) {
-            DevLevel H;
-            H.n = L.n; H.ncols = L.ncols; H.bs = L.bs;
-            build_gsb(s, H, &s.P, nullptr);
-            const DevGSB &x = L.gsb, &y = H.gsb;
-            if (x.B != y.B || x.G != y.G || x.TH != y.TH || x.n_blocks != y.n_blocks || x.n_colors != y.n_colors || x.lowin_maxw != y.lowin_maxw || x.full_maxw != y.full_maxw ||
-                x.has_split != y.has_split) throw Err("AMGX_VERIFY_IMAGES: block-hybrid Gauss-Seidel: the descriptors differ");
-            const size_t nsl = (size_t)((int64_t)x.n_blocks * x.B / (WAVE / x.G));
-            verify_same_sell(x.full, y.full, nsl, 0, "block-hybrid Gauss-Seidel: A");
-            if (x.has_split) {
-              verify_same_sell(x.lowin, y.lowin, nsl, 0, "block-hybrid Gauss-Seidel: lower part");
-              verify_same_image(x.rest, y.rest, "block-hybrid Gauss-Seidel: rest");
-              const auto cx = db_download(x.cvec, (size_t)L.n), cy = db_download(y.cvec, (size_t)L.n);
-              if (std::memcmp(cx.data(), cy.data(), (size_t)L.n * sizeof(double)) != 0) throw Err("AMGX_VERIFY_IMAGES: block-hybrid Gauss-Seidel: cvec differs");
-            }
-          }
-        }
-        else if (s.sm_type == AMGX_SM_GS) build_gs(s, L);
-        if (s.sm_type == AMGX_SM_BGS) build_bgs(s, L);
-      }, "smoother data");
-      if (s.sm_type == AMGX_SM_JACOBI && s.A.br == 1 && s.sm_steps <= 1 && !s.sm_symm) {
-        tasks.run([&] {
-        // dinv_i * A_ii == 1 (to 1e-13) on every row with dinv_i != 0
-        auto host_diag_plain = [&] {
-          std::vector<char> notplain(setup_threads(), 0);
-          par_for(s.A.n_rows, [&](int64_t i0, int64_t i1, int t) {
-            for (int64_t i = i0; i < i1; ++i) {
-              if (s.dinv[i] == 0.0) continue;
-              double aii = 0.0;
-              for (int64_t k = s.A.rowptr[i]; k < s.A.rowptr[i + 1]; ++k) if (s.A.col[k] == i) { aii = s.A.val[k]; break; }
-              if (!(std::fabs(s.dinv[i] * aii - 1.0) < 1e-13)) { notplain[t] = 1; break; }
-            }
-          });
-          for (char cc : notplain) if (cc) return false;
-          return true;
-        };
-        // long-row levels (>= 1) of a reference-shaped hierarchy: the "local window" image for the fused down kernel
-        auto lw_image = [&]() -> bool {
-          const int64_t nnzA = s.A.rowptr[s.A.n_rows];
-          const double avgA = s.A.n_rows ? (double)nnzA / (double)s.A.n_rows : 0.0;
-          int64_t lw_min_rows = 100000;
-          if (const char* e = std::getenv("AMGX_LW_MIN_ROWS")) lw_min_rows = std::atoll(e);
-          // (rank-partitioned levels too: the window of an interior chunk holds owned columns only, ghost columns are just columns)
-          if (l == 0 || avgA < 24.0 || s.A.n_rows < lw_min_rows || std::getenv("AMGX_NO_LW") ||
-              s.P.br != 1 || s.P.bc != 1 || s.P.rowptr[s.P.n_rows] >= (int64_t)2147483647 || std::getenv("AMGX_NO_FUSED_RESTRICT")) return false;
-          // two lanes per row (256-row chunks); levels whose 256-row chunks touch too many columns: four lanes (128-row chunks)
-          int G = 0;
-          std::unique_ptr<double[]> sv;
-          auto host_lw = [&](int g, DevMatrix& M, DevBuf<int32_t>& cp, DevBuf<int32_t>& cc) {
-            if (!sv) {
-              sv.reset(new double[(size_t)std::max<int64_t>(1, nnzA)]);
-              par_for(nnzA, [&](int64_t k0, int64_t k1, int) { for (int64_t k = k0; k < k1; ++k) sv[k] = s.A.val[k] * (s.omega * s.dinv[s.A.col[k]]); }, 1 << 16);
-            }
-            return build_sell_lw(s.A, sv.get(), g, M, cp, cc);
-          };
-          // (device: window lists by a bitmap in LDS, devbuild.hpp dev_build_lw; AMGX_HOST_LW=1 keeps the host builder)
-          const bool dev_lw = dev_images && !std::getenv("AMGX_HOST_LW") && !std::getenv("AMGX_HOST_IMAGES");
-          for (int g : {2, 4}) {
-            bool ok = false;
-            if (dev_lw) {
-              int64_t cap = LW_CAP;
-              const char* tcap = std::getenv("AMGX_LW_TEST_CAP");
-              if (tcap) cap = std::min<int64_t>(cap, std::atoll(tcap));
-              ok = dev_build_lw(csrA, false, g, cap, tcap != nullptr, L.dinv.p, s.omega, L.ApreLW, L.lw_cptr, L.lw_ccol);
-              if (ok && verify_images) {
-                DevMatrix H; DevBuf<int32_t> hp, hc;
-                if (!host_lw(g, H, hp, hc)) throw Err("AMGX_VERIFY_IMAGES: A' (local window): the host builder declines what the device builder forms");
-                verify_same_lw(L.ApreLW, L.lw_cptr, L.lw_ccol, H, hp, hc, "A' (local window)");
-              }
-              if (!ok) { L.ApreLW = DevMatrix(); L.lw_cptr.release(); L.lw_ccol.release(); }
-            }
-            if (!ok) ok = host_lw(g, L.ApreLW, L.lw_cptr, L.lw_ccol);
-            if (ok) { G = g; break; }
-            L.ApreLW = DevMatrix();
-          }
-          if (!G) return false;
-          L.fused_block = 512;
-          build_restrict(s.P, L.RF, 512 / G, 4 * 512, 512);
-          if (L.RF.empty()) { L.ApreLW = DevMatrix(); L.lw_cptr.release(); L.lw_ccol.release(); return false; }
-          return true;
-        };
-        // levels whose A lies on at most 16 diagonals and equals its transpose bit for bit (Kuhn P1 matrices in natural vertex order):
-        // the fused down kernel streams the symmetric diagonal image of A instead of A' (dia_pre_restrict_kernel) -- 7 of the 15
-        // diagonals from HBM at cfg 2, the lower ones are shifted re-reads of the same arrays, and no index stream.  Not on levels
-        // a rank-partitioned driver runs stage by stage (dense_first < 0), nor below AMGX_DIA_MIN_ROWS rows (2 M: the smaller levels
-        // keep the SELL image).  AMGX_NO_DIA=1 disables it.
-        auto dia_image = [&]() -> bool {
-          int64_t min_rows = 2000000;
-          if (const char* e = std::getenv("AMGX_DIA_MIN_ROWS")) min_rows = std::atoll(e);
-          if (std::getenv("AMGX_NO_DIA") || dense_first < 0 || s.A.n_rows != s.A.n_cols || s.A.n_rows < std::max<int64_t>(1, min_rows) ||
-              s.omega == 0.0 || std::getenv("AMGX_NO_WDIAG") || s.P.br != 1 || s.P.bc != 1 || s.P.rowptr[s.P.n_rows] >= (int64_t)2147483647 ||
-              std::getenv("AMGX_NO_FUSED_RESTRICT")) return false;
-          // the kernel puts the diagonal term back as omega*b_i (0 where dinv_i = 0): dinv must be the plain inverse diagonal
-          if (dev_images ? !diagA.plain : !host_diag_plain()) return false;
-          auto par = [](int64_t nb, auto&& f) { par_for(nb, [&](int64_t a, int64_t b, int) { for (int64_t q = a; q < b; ++q) f(q); }, 1); };
-          int32_t off[dia::MAX_UPPER];
-          const int K = dia::detect(s.A.n_rows, s.A.n_cols, s.A.rowptr, s.A.col, s.A.val, dia::MAX_DIAGS, 1.05, off, par);
-          if (K <= 0 || K > DIA_MAX_UPPER) return false;
-          DevDia& D = L.dia;
-          D.K = K;
-          for (int k = 0; k < K; ++k) D.off[k] = off[k];
-          std::vector<double> hv;
-          if (!dev_images || verify_images) {
-            hv.resize((size_t)K * (size_t)s.A.n_rows);
-            dia::upper_image(s.A.n_rows, s.A.rowptr, s.A.col, s.A.val, K, off, hv.data(), par);
-          }
-          if (dev_images) {
-            dev_build_dia(csrA, D);
-            if (verify_images && std::memcmp(db_download(D.val, hv.size()).data(), hv.data(), hv.size() * sizeof(double)) != 0)
-              throw Err("AMGX_VERIFY_IMAGES: the diagonal image differs");
-          } else
-            D.val.upload(hv);
-          L.fused_block = 512;
-          int64_t cc_min = 200000;
-          if (const char* e = std::getenv("AMGX_COMPACT_CHUNKS_MIN_ROWS")) cc_min = std::atoll(e);
-          if (s.A.n_rows >= cc_min && !std::getenv("AMGX_NO_COMPACT_CHUNKS")) {
-            const std::vector<int32_t> sl = cluster_slices(s.P, 512 / WAVE);
-            build_restrict(s.P, L.RF, 512, 6 * 512, 512, &sl);
-          } else
-            build_restrict(s.P, L.RF, 512, 6 * 512, 512);
-          if (L.RF.empty()) { L.dia = DevDia(); return false; }
-          return true;
-        };
-        auto fused_restrict = [&] {
-          if (lw_image()) return;
-          // fused pre-smoothing + restriction when A' is in the one-thread-per-row SELL form (big levels).
-          // Same-process A/B with 4 instances per variant (profiles/r01/restrict_fused.txt): 1-3 % faster cycle than the
-          // separate pre-smoothing + P^T gather kernels, and r is never written to HBM.  AMGX_NO_FUSED_RESTRICT=1 disables it.
-          const int G = L.Apre.lanes;
-          if (L.Apre.fmt == FMT_SELL && L.Apre.sell.win == SELL_WIN && G == 1 && SELL_WIN == 512 && s.P.br == 1 && s.P.bc == 1 &&
-              s.P.rowptr[s.P.n_rows] < (int64_t)2147483647 && !std::getenv("AMGX_NO_FUSED_RESTRICT"))
-          {
-            L.fused_block = SELL_WIN;              // windowed A': a chunk = a window (sell_win_pre_restrict_kernel)
-            build_restrict(s.P, L.RF, SELL_WIN, 6 * SELL_WIN, SELL_WIN);
-          }
-          else if (L.Apre.fmt == FMT_SELL && !L.Apre.sell.win && (G == 1 || G == 2 || G == 4 || G == 8) && s.P.br == 1 && s.P.bc == 1 &&
-              s.P.rowptr[s.P.n_rows] < (int64_t)2147483647 && !std::getenv("AMGX_NO_FUSED_RESTRICT") && !(G > 1 && std::getenv("AMGX_NO_FUSED_RESTRICT_MULTI")))
-          {
-            L.fused_block = 512;       // same-process A/B: 512 < 1024 (epilogues of more, smaller workgroups overlap better)
-            if (const char* e = std::getenv("AMGX_FUSED_BLOCK")) { const int v = std::atoi(e); L.fused_block = (v == 256 || v == 1024) ? v : 512; }
-            if (G > 1) L.fused_block = 512;        // (several lanes per row: the chunk holds 512 / G rows)
-            // big square one-thread-per-row levels: compact chunks (cluster_slices) -- fewer partial sums per coarse row
-            int64_t cc_min = 200000;
-            if (const char* e = std::getenv("AMGX_COMPACT_CHUNKS_MIN_ROWS")) cc_min = std::atoll(e);
-            // (not on a handle that a rank-partitioned driver runs stage by stage -- dense_first < 0 --: its launches cover interior and
-            //  boundary chunk RANGES, which only consecutive chunks have; a rank without ghost columns, e.g. world size 1, has a square level)
-            if (G == 1 && dense_first >= 0 && s.A.n_rows == s.A.n_cols && s.A.n_rows >= cc_min && !std::getenv("AMGX_NO_COMPACT_CHUNKS")) {
-              const std::vector<int32_t> sl = cluster_slices(s.P, L.fused_block / WAVE);
-              build_restrict(s.P, L.RF, L.fused_block, 6 * L.fused_block, L.fused_block, &sl);
-            } else
-            build_restrict(s.P, L.RF, L.fused_block / G, 6 * L.fused_block, L.fused_block);
-            // several lanes per row: the kernel exists for 4 entries of P per thread only; a chunk of 512 / G rows with more
-            // than 2048 entries (a prolongation with more than 4 G entries per row) keeps the separate kernels
-            if (G > 1 && L.RF.ept != 4) L.RF = DevRestrict();
-          }
-        };
-        if (dia_image()) return;
-        // (device builder: A' = A diag(omega Dinv) from the CSR of A that is already there; the diagonal slot carries omega*Dinv_i
-        //  under the same conditions as below)
-        const bool dev_wdiag = s.omega != 0.0 && !std::getenv("AMGX_NO_WDIAG") && diagA.plain;
-        // levels >= 1 of a reference-shaped hierarchy have ragged long rows (plain slices pad 20 % at the 1.24 M-row level of cfg 2,
-        // length-sorted windows 3.6 %).  Measured NON-win (profiles/r04/l1_experiments.txt): the windowed image with its fused kernel
-        // (sell_win_pre_restrict_kernel) runs that level in 256 us against 215 us -- these levels are bound by the scattered gathers
-        // of x, and sorting the rows of a window by length puts unrelated rows into neighbouring lanes.  Opt-in: AMGX_APRE_WINDOW=1.
-        const int apre_win = (l >= 1 && s.A.n_rows == s.A.n_cols && std::getenv("AMGX_APRE_WINDOW")) ? SELL_WIN : 0;
-        if (dev_images && !verify_images && dev_upload_matrix(csrA, L.Apre, true, 1.35, apre_win, &diagA, L.dinv.p, s.omega, dev_wdiag ? L.dinv.p : nullptr)) {
-          fused_restrict();
-          return;
-        }
-        // column-scaled image for the fused pre-smoothing pass (memory for bandwidth: one more copy of A)
-        const int64_t nnz = s.A.rowptr[s.A.n_rows];
-        std::unique_ptr<double[]> sv(new double[(size_t)std::max<int64_t>(1, nnz)]);      // (uninitialised: every entry is written below)
-        // (rank-partitioned levels: dinv must cover the ghost columns too, i.e. n_cols entries)
-        par_for(nnz, [&](int64_t k0, int64_t k1, int) { for (int64_t k = k0; k < k1; ++k) sv[k] = s.A.val[k] * (s.omega * s.dinv[s.A.col[k]]); }, 1 << 16);
-        amgx_matrix As = s.A;
-        As.val = sv.get();
-        // one-thread-per-row form: the diagonal slot carries omega*Dinv_i (SellMat::wdiag), the epilogue then needs no
-        // dinv stream (80 MB per pass at cfg 2); AMGX_NO_WDIAG=1 keeps A'_ii there
-        std::vector<double> wdv;
-        if (s.omega != 0.0 && !std::getenv("AMGX_NO_WDIAG")) {
-          // the epilogue re-inserts A'_ii b_i as omega*b_i (or 0 where dinv_i = 0): valid iff dinv is the plain inverse diagonal
-          if (host_diag_plain()) {
-            wdv.resize((size_t)s.A.n_rows);
-            par_for(s.A.n_rows, [&](int64_t i0, int64_t i1, int) { for (int64_t i = i0; i < i1; ++i) wdv[i] = s.omega * s.dinv[i]; }, 1 << 16);
-          }
-        }
-        if (dev_images && verify_images) {
-          DevMatrix H;
-          upload_matrix(As, H, "A (pre-smoothing image)", true, true, false, 1.35, apre_win, wdv.empty() ? nullptr : wdv.data());
-          if (dev_upload_matrix(csrA, L.Apre, true, 1.35, apre_win, &diagA, L.dinv.p, s.omega, dev_wdiag ? L.dinv.p : nullptr)) verify_same_image(L.Apre, H, "A'");
-          else if (H.fmt == FMT_SELL && H.lanes == 1) throw Err("AMGX_VERIFY_IMAGES: the device builder declined A' where the host builder forms a SELL image");
-          else L.Apre = std::move(H);
-        } else
-          upload_matrix(As, L.Apre, "A (pre-smoothing image)", true, true, false, 1.35, apre_win, wdv.empty() ? nullptr : wdv.data());
-        fused_restrict();
-        }, "A' + fused restriction");
-        // post-smoothing folded into the prolongation (V-cycle).  Square levels: Q is built here.  Rank-partitioned
-        // levels: Q needs the P rows of the ghost vertices, so the caller supplies it (amgx_level_desc.Q) and drives
-        // the level through amgx_cycle_down / amgx_cycle_up.
-        auto qlw_wanted = [](int64_t rows) {
-          int64_t mn = 100000;
-          if (const char* e = std::getenv("AMGX_LW_MIN_ROWS")) mn = std::atoll(e);
-          return rows >= mn && !std::getenv("AMGX_NO_LW") && !std::getenv("AMGX_NO_QLW");
-        };
-        if (d->cycle == AMGX_CYCLE_V && s.P.br == 1 && s.P.bc == 1 && !std::getenv("AMGX_NO_FOLD")) {
-          double qpad = 1.6;
-          if (const char* e = std::getenv("AMGX_Q_MAX_PAD")) qpad = std::atof(e);
-          if (s.Q.rowptr) {
-            if (s.Q.n_rows != s.A.n_rows || s.Q.br != 1 || s.Q.bc != 1 || s.Q.n_cols < c.A.n_rows || s.Q.n_cols > c.A.n_cols)
-              throw Err("Q does not match the level matrices");
-            if (s.Q.rowptr[s.Q.n_rows] >= (int64_t)2147483647) throw Err("Q: too many entries");
-            tasks.run([&, qpad] {
-              upload_matrix(s.Q, L.Q, "Q (folded post-smoothing prolongation)", true, false, false, qpad, SELL_WIN);
-              // (rank-partitioned level: the caller's Q, columns [owned | ghost] of the coarse level)
-              if (qlw_wanted(s.A.n_rows) &&
-                  !build_sell_lw_windowed(s.Q.n_rows, s.Q.n_cols, s.Q.rowptr, s.Q.col, s.Q.val, L.QLW, L.qlw_cptr, L.qlw_ccol)) L.QLW = DevMatrix();
-            });
-          } else if (s.A.n_rows == s.A.n_cols && s.P.n_cols == c.A.n_rows) {
-            tasks.run([&, qpad] {
-              // (device: the sparse product and the windowed image of its result, devbuild.hpp)
-              if (dev_images) {
-                check_matrix(s.P, "P");
-                DevCsrSrc csrP, csrQ;
-                csrP.upload(s.P);
-                if (dev_fold_prolongation(csrA, csrP, L.dinv.p, s.omega, csrQ) && dev_upload_matrix(csrQ, L.Q, false, qpad, SELL_WIN, nullptr)) {
-                  bool qlw_done = false;
-                  if (qlw_wanted(s.A.n_rows) && !std::getenv("AMGX_HOST_LW")) {
-                    int64_t cap = QW_CAP;
-                    const char* tcap = std::getenv("AMGX_LW_TEST_CAP");
-                    if (tcap) cap = std::min<int64_t>(cap, std::max<int64_t>(8, std::atoll(tcap) / 4));
-                    qlw_done = dev_build_lw(csrQ, true, 1, cap, tcap != nullptr, nullptr, 0.0, L.QLW, L.qlw_cptr, L.qlw_ccol);
-                    if (!qlw_done) { L.QLW = DevMatrix(); L.qlw_cptr.release(); L.qlw_ccol.release(); }
-                    else if (verify_images) {
-                      std::vector<int64_t> rp = db_download(csrQ.rowptr, (size_t)s.A.n_rows + 1);
-                      std::vector<int32_t> cc = db_download(csrQ.col, (size_t)std::max<int64_t>(1, csrQ.nnz));
-                      std::vector<double> vv = db_download(csrQ.val, (size_t)std::max<int64_t>(1, csrQ.nnz));
-                      DevMatrix H; DevBuf<int32_t> hp, hc;
-                      if (!build_sell_lw_windowed(s.A.n_rows, csrQ.n_cols, rp.data(), cc.data(), vv.data(), H, hp, hc))
-                        throw Err("AMGX_VERIFY_IMAGES: Q (local window): the host builder declines what the device builder forms");
-                      verify_same_lw(L.QLW, L.qlw_cptr, L.qlw_ccol, H, hp, hc, "Q (local window)");
-                    }
-                  }
-                  if (qlw_wanted(s.A.n_rows) && !qlw_done) {
-                    SetupClock qclk;
-                    std::vector<int64_t> rp = db_download(csrQ.rowptr, (size_t)s.A.n_rows + 1);
-                    std::vector<int32_t> cc = db_download(csrQ.col, (size_t)std::max<int64_t>(1, csrQ.nnz));
-                    std::vector<double> vv = db_download(csrQ.val, (size_t)std::max<int64_t>(1, csrQ.nnz));
-                    qclk.lap("  lw-win: download of Q", l);
-                    if (!build_sell_lw_windowed(s.A.n_rows, csrQ.n_cols, rp.data(), cc.data(), vv.data(), L.QLW, L.qlw_cptr, L.qlw_ccol)) L.QLW = DevMatrix();
-                  }
-                  if (verify_images) {
-                    HostCsr q;
-                    fold_prolongation(s.A, s.P, s.dinv, s.omega, q);
-                    if ((int64_t)q.rowptr[s.A.n_rows] != csrQ.nnz) throw Err("AMGX_VERIFY_IMAGES: Q: different numbers of entries");
-                    amgx_matrix Qm = s.P;
-                    Qm.rowptr = q.rowptr.data(); Qm.col = q.col.data(); Qm.val = q.val.data();
-                    DevMatrix H;
-                    upload_matrix(Qm, H, "Q (folded post-smoothing prolongation)", true, false, false, qpad, SELL_WIN);
-                    verify_same_image(L.Q, H, "Q");
-                  }
-                  return;
-                }
-                L.Q = DevMatrix();
-                if (verify_images) std::fprintf(stderr, "[amgx_create] AMGX_VERIFY_IMAGES: level %d: Q is left to the host builder\n", l);
-              }
-              HostCsr q;
-              fold_prolongation(s.A, s.P, s.dinv, s.omega, q);
-              if (q.rowptr[s.A.n_rows] < (int64_t)2147483647) {
-                amgx_matrix Qm = s.P;
-                Qm.rowptr = q.rowptr.data(); Qm.col = q.col.data(); Qm.val = q.val.data();
-                upload_matrix(Qm, L.Q, "Q (folded post-smoothing prolongation)", true, false, false, qpad, SELL_WIN);
-                if (qlw_wanted(s.A.n_rows) &&
-                    !build_sell_lw_windowed(s.A.n_rows, s.P.n_cols, q.rowptr.data(), q.col.data(), q.val.data(), L.QLW, L.qlw_cptr, L.qlw_ccol)) L.QLW = DevMatrix();
-              }
-            }, "Q = (I - w Dinv A) P");
-          }
-        }
-      }
-      // block Jacobi levels of the V-cycle: the same fold in block form (Q has the block shape of P)
-      if (s.sm_type == AMGX_SM_JACOBI && s.A.br > 1 && s.sm_steps <= 1 && !s.sm_symm && d->cycle == AMGX_CYCLE_V &&
-          s.A.n_rows == s.A.n_cols && s.P.n_cols == c.A.n_rows && s.P.br == s.A.br && !std::getenv("AMGX_NO_FOLD") &&
-          !std::getenv("AMGX_NO_BLOCK_FOLD"))
-      {
-        tasks.run([&] {
-        HostCsr q;
-        fold_prolongation(s.A, s.P, s.dinv, s.omega, q);
-        // Fold only where it pays: the way up then streams Q instead of A + P (+ the round trip of x + P x_c), but
-        // rectangular-block Q runs through the CSR block kernels (~4.5 TB/s) while square-block A streams as BSELL
-        // (~6.5 TB/s).  Measured at the cfg 3 shapes (profiles/r01/block_fold.txt): 3x3 fine level with 3x6 blocks in
-        // P: Q has 10.8 blocks/row = 1.6 GB vs A + P = 1.65 GB -> literal is 55 us faster; 6x6 levels: Q = 0.36 GB
-        // vs 1.04 GB -> folded is 100 us faster.
-        auto bytes = [](int64_t nnz, int br, int bc) { return (double)nnz * (8.0 * br * bc + 4.0); };
-        const double bq = bytes(q.rowptr[s.A.n_rows], s.P.br, s.P.bc);
-        const double blit = bytes(s.A.rowptr[s.A.n_rows], s.A.br, s.A.bc) + bytes(s.P.rowptr[s.P.n_rows], s.P.br, s.P.bc);
-        if (q.rowptr[s.A.n_rows] < (int64_t)2147483647 && bq < 0.7 * blit) {
-          amgx_matrix Qm = s.P;
-          Qm.rowptr = q.rowptr.data(); Qm.col = q.col.data(); Qm.val = q.val.data();
-          upload_matrix(Qm, L.Q, "Q (folded post-smoothing prolongation)");
-        }
-        });
-      }
-      tasks.wait();
-      // scalar Chebyshev levels: the residual after pre-smoothing feeds the chunk-local restriction without going through HBM
-      // (sell_pre_restrict_kernel<.., MODE 2> on the SELL image of A itself), under the rule of the Jacobi levels' fused down kernel.
-      // AMGX_CHEB_NO_FUSED_RESTRICT=1 (or AMGX_NO_FUSED_RESTRICT=1) keeps EP_RES + the separate restriction kernels.
-      if (s.sm_type == AMGX_SM_CHEBY && s.A.br == 1 && s.sm_steps <= 1 && !s.sm_symm && L.A.fmt == FMT_SELL && !L.A.sell.win &&
-          (L.A.lanes == 1 || L.A.lanes == 2 || L.A.lanes == 4 || L.A.lanes == 8) && s.P.br == 1 && s.P.bc == 1 &&
-          s.P.rowptr[s.P.n_rows] < (int64_t)2147483647 && !std::getenv("AMGX_NO_FUSED_RESTRICT") && !std::getenv("AMGX_CHEB_NO_FUSED_RESTRICT") &&
-          !(L.A.lanes > 1 && std::getenv("AMGX_NO_FUSED_RESTRICT_MULTI")))
-      {
-        const int G = L.A.lanes;
-        L.fused_block = 512;
-        int64_t cc_min = 200000;
-        if (const char* e = std::getenv("AMGX_COMPACT_CHUNKS_MIN_ROWS")) cc_min = std::atoll(e);
-        if (G == 1 && dense_first >= 0 && s.A.n_rows >= cc_min && !std::getenv("AMGX_NO_COMPACT_CHUNKS")) {
-          const std::vector<int32_t> sl = cluster_slices(s.P, 512 / WAVE);
-          build_restrict(s.P, L.RF, 512, 6 * 512, 512, &sl);
-        } else
-          build_restrict(s.P, L.RF, 512 / G, 6 * 512, 512);
-        if (G > 1 && L.RF.ept != 4) L.RF = DevRestrict();
-      }
-      clk.lap("level images (A, P, P^T, smoother data, A', Q: concurrent host tasks)", l);
-    } else if (s.dinv) {
-      tasks.wait();
-      L.dinv.upload(s.dinv, (size_t)L.n * L.bs * L.bs);
-      if (s.sm_type == AMGX_SM_GS && s.color && s.gs_block_rows > 0 && s.A.br > 1) build_bgsb(s, L);
-      else if (s.sm_type == AMGX_SM_GS && s.color && s.gs_block_rows > 0) build_gsb(s, L, nullptr);
-      else if (s.sm_type == AMGX_SM_GS && s.color) build_gs(s, L);
-      if (s.sm_type == AMGX_SM_BGS && s.bgs_n_blocks > 0) build_bgs(s, L);
-    }
-    tasks.wait();
-    {
-      // workgroup -> rows mapping of the streaming kernels on this level (SellMat::xcd)
-      int mode = 1;
-      if (const char* e = std::getenv("AMGX_XCD")) mode = std::atoi(e);
-      const double avg = s.A.n_rows ? (double)s.A.rowptr[s.A.n_rows] / (double)s.A.n_rows : 0.0;
-      const int on = mode >= 2 || (mode == 1 && avg >= 24.0 && s.A.n_rows >= 200000);
-      L.A.sell.xcd = L.Apre.sell.xcd = L.Q.sell.xcd = L.gsb.rest.sell.xcd = on;
-      L.dia.xcd = std::getenv("AMGX_DIA_XCD") ? 1 : 0;        // (A/B hook: each XCD walks one contiguous eighth of the chunks)
-      if (mode >= 3) L.P.sell.xcd = L.PT.sell.xcd = on;
-    }
-    const size_t len = (size_t)std::max<int64_t>(1, L.ext_len());
-    L.x.alloc(len); L.rhs.alloc(len); L.res.alloc(len); L.tmp.alloc(len);
-    HIPCHK(hipMemset(L.x.p, 0, len * sizeof(double)));
-    HIPCHK(hipMemset(L.rhs.p, 0, len * sizeof(double)));
-    HIPCHK(hipMemset(L.res.p, 0, len * sizeof(double)));
-    HIPCHK(hipMemset(L.tmp.p, 0, len * sizeof(double)));
-    if (L.sm_type == AMGX_SM_CHEBY) { L.d.alloc(len); HIPCHK(hipMemset(L.d.p, 0, len * sizeof(double))); }
-  }
-  cheb_estimate(*h);
-  clk.lap("Chebyshev intervals (power iteration)");
-  if (d->clev == AMGX_CLEV_INV) {
-    const DevLevel& L = h->lev.back();
-    if (d->coarse_n != L.len()) throw Err("clev = inv: coarse_n does not match the coarsest level");
-    h->coarse_n = d->coarse_n;
-    if (d->coarse_inv) {
-      h->coarse_ld = d->coarse_n;
-      h->coarse_inv.upload(d->coarse_inv, (size_t)d->coarse_n * d->coarse_n);
-    } else {
-      // no inverse handed over (the host setup stops at 4096 unknowns): invert the coarsest matrix on its free dofs here
-      // (dense_spd.hpp: blocked Gauss-Jordan, trailing updates on the matrix cores)
-      const amgx_level_desc& s = levels[d->n_levels - 1];
-      int64_t cap = 16384;
-      if (const char* e = std::getenv("AMGX_COARSE_DENSE_MAX")) cap = std::atoll(e);
-      if (s.A.n_rows != s.A.n_cols) throw Err("clev = inv: the coarsest level of a rank-partitioned hierarchy cannot be inverted locally");
-      if (d->coarse_n > cap) throw Err("clev = inv: coarsest level has " + std::to_string(d->coarse_n) + " unknowns, more than AMGX_COARSE_DENSE_MAX = " +
-                                       std::to_string(cap) + " (a dense inverse would stream " + std::to_string(8 * d->coarse_n * d->coarse_n / 1000000) + " MB per application)");
-      const int64_t n = d->coarse_n, npad = (n + GJ_T - 1) / GJ_T * GJ_T;
-      const int bs = s.A.br;
-      struct { DevBuf<int32_t> rowptr, col; DevBuf<double> val; } cA;       // (DevCsr holds scalar matrices only)
-      {
-        const int64_t nnzc = s.A.rowptr[s.A.n_rows];
-        std::vector<int32_t> rp((size_t)s.A.n_rows + 1);
-        for (int64_t i = 0; i <= s.A.n_rows; ++i) rp[i] = (int32_t)s.A.rowptr[i];
-        cA.rowptr.upload(rp);
-        cA.col.upload(s.A.col, (size_t)nnzc);
-        cA.val.upload(s.A.val, (size_t)nnzc * bs * bs);
-      }
-      DevBuf<uint8_t> fr;
-      if (s.free_dofs) fr.upload(s.free_dofs, (size_t)s.A.n_rows);
-      h->coarse_inv.alloc((size_t)npad * npad);
-      h->coarse_ld = npad;
-      hipLaunchKernelGGL(gj_zero_kernel, dim3(Handle::grid_for(npad * npad)), dim3(BLOCK), 0, h->stream, npad * npad, h->coarse_inv.p);
-      hipLaunchKernelGGL(gj_scatter_kernel, dim3(Handle::grid_for(s.A.n_rows)), dim3(BLOCK), 0, h->stream, s.A.n_rows, bs, cA.rowptr.p, cA.col.p, cA.val.p,
-                         fr.p, npad, h->coarse_inv.p);
-      hipLaunchKernelGGL(gj_fix_diag_kernel, dim3(Handle::grid_for(npad)), dim3(BLOCK), 0, h->stream, npad, n, bs, fr.p, npad, 1.0, h->coarse_inv.p);
-      HIPCHK(hipGetLastError());
-      h->coarse_pivot = dense_spd_inverse(h->coarse_inv.p, npad, npad, h->stream);
-      if (!(h->coarse_pivot > 1e-14)) throw Err("clev = inv: the coarsest matrix is not positive definite on its free dofs (pivot ratio " +
-                                                std::to_string(h->coarse_pivot) + "); use clev = none or a smaller coarsest level");
-      hipLaunchKernelGGL(gj_fix_diag_kernel, dim3(Handle::grid_for(npad)), dim3(BLOCK), 0, h->stream, npad, n, bs, fr.p, npad, 0.0, h->coarse_inv.p);
-      HIPCHK(hipStreamSynchronize(h->stream));
-    }
-  }
-  // ---- single-workgroup coarse tail (V-cycle, plain scalar smoothers, exact coarse solve, square levels) ----------
-  {
-    const int L = d->n_levels;
-    int T = -1;
-    if (d->cycle == AMGX_CYCLE_V && d->clev == AMGX_CLEV_INV && L >= 2 && !std::getenv("AMGX_NO_TAIL_KERNEL")) {
-      T = L - 1;
-      while (T - 1 >= 1) {
-        const amgx_level_desc& s = levels[T - 1];
-        const int64_t cap = s.sm_type == AMGX_SM_GS ? TAIL_MAX_ROWS_GS : TAIL_MAX_ROWS;
-        const bool ok = s.A.br == 1 && s.A.n_rows == s.A.n_cols && s.A.n_rows <= cap &&
-                        (s.sm_type == AMGX_SM_JACOBI || (s.sm_type == AMGX_SM_GS && s.color && s.n_colors > 0 && s.gs_block_rows == 0)) &&
-                        s.sm_steps <= 1 && !s.sm_symm && s.P.br == 1 && s.P.bc == 1 && h->coarse_n <= 512 && h->coarse_ld == h->coarse_n;
-        if (!ok) break;
-        --T;
-      }
-      if (T > L - 2) T = -1;                  // no smoothed level qualifies
-    }
-    if (T > 0) {
-      std::vector<TailOp> prog;
-      const EpArgs none{nullptr, nullptr, nullptr, 0.0, nullptr, 0};
-      auto spmv = [&](int ep, const DevCsr& M, int n, const double* x, double* y, EpArgs a) {
-        prog.push_back(TailOp{T_SPMV, ep, n, M.rowptr.p, M.col.p, M.val.p, x, y, a, nullptr, nullptr, 0, 0, 0, nullptr});
-      };
-      auto gs = [&](DevLevel& V, int nc, int backward, int lds_ok) {
-        prog.push_back(TailOp{T_GS, 0, (int)V.n, V.tA.rowptr.p, V.tA.col.p, V.tA.val.p, nullptr, V.x.p,
-                              EpArgs{V.rhs.p, nullptr, V.dinv.p, 0.0, nullptr, 0}, V.t_rowlist.p, V.t_cptr.p, nc, backward, lds_ok, V.t_rowcolor.p});
-      };
-      auto gs_lds_ok = [&](int l) {
-        const amgx_matrix& A = levels[l].A;
-        if (A.n_rows > TAIL_BLOCK / TAIL_G || std::getenv("AMGX_NO_TAIL_LDS")) return 0;
-        for (int64_t i = 0; i < A.n_rows; ++i) if (A.rowptr[i + 1] - A.rowptr[i] > TAIL_G * TAIL_GS_K) return 0;
-        return 1;
-      };
-      for (int l = T; l + 1 < L; ++l) {
-        const amgx_level_desc& s = levels[l];
-        DevLevel& V = h->lev[l];
-        const int64_t nnz = s.A.rowptr[s.A.n_rows];
-        V.tA.upload(s.A); V.tP.upload(s.P); V.tPT.upload(s.PT);
-        if (s.sm_type == AMGX_SM_JACOBI) {
-          std::vector<double> sv((size_t)nnz);
-          for (int64_t k = 0; k < nnz; ++k) sv[k] = s.A.val[k] * (s.omega * s.dinv[s.A.col[k]]);
-          V.tApre.upload(s.A, sv.data());
-        } else {
-          std::vector<int32_t> cptr(s.n_colors + 1, 0), rl;
-          for (int64_t i = 0; i < s.A.n_rows; ++i) if (s.color[i] >= 0) cptr[s.color[i] + 1]++;
-          for (int c = 0; c < s.n_colors; ++c) cptr[c + 1] += cptr[c];
-          rl.resize(cptr[s.n_colors]);
-          std::vector<int32_t> pos(cptr.begin(), cptr.end() - 1);
-          for (int64_t i = 0; i < s.A.n_rows; ++i) if (s.color[i] >= 0) rl[pos[s.color[i]]++] = (int32_t)i;
-          V.t_rowlist.upload(rl); V.t_cptr.upload(cptr);
-          V.t_rowcolor.upload(s.color, (size_t)s.A.n_rows);
-        }
-      }
-      for (int l = T; l + 1 < L; ++l) {       // down
-        DevLevel& V = h->lev[l];
-        if (V.sm_type == AMGX_SM_JACOBI) {     // r = b - A'b, x = omega*Dinv*b
-          spmv(EP_PRE, V.tApre, (int)V.n, V.rhs.p, V.res.p, EpArgs{V.rhs.p, nullptr, V.dinv.p, V.omega, V.x.p, 0});
-        } else {                               // x = 0; forward sweep; r = b - A x
-          prog.push_back(TailOp{T_ZERO, 0, (int)V.n, nullptr, nullptr, nullptr, nullptr, V.x.p, none, nullptr, nullptr, 0, 0, 0, nullptr});
-          gs(V, levels[l].n_colors, 0, gs_lds_ok(l));
-          spmv(EP_RES, V.tA, (int)V.n, V.x.p, V.res.p, EpArgs{V.rhs.p, nullptr, nullptr, 0.0, nullptr, 0});
-        }
-        spmv(EP_MULT, V.tPT, (int)h->lev[l + 1].n, V.res.p, h->lev[l + 1].rhs.p, none);   // b_{l+1} = P^T r
-      }
-      prog.push_back(TailOp{T_DENSE, 0, (int)h->coarse_n, nullptr, nullptr, h->coarse_inv.p, h->lev[L - 1].rhs.p, h->lev[L - 1].x.p,
-                            none, nullptr, nullptr, 0, 0, 0, nullptr});
-      for (int l = L - 2; l >= T; --l) {      // up
-        DevLevel& V = h->lev[l];
-        if (V.sm_type == AMGX_SM_JACOBI) {     // tmp = x + P x_{l+1} ; x = tmp + omega*Dinv*(b - A tmp)
-          spmv(EP_AXPY, V.tP, (int)V.n, h->lev[l + 1].x.p, V.tmp.p, EpArgs{nullptr, V.x.p, nullptr, 1.0, nullptr, 0});
-          spmv(EP_JAC, V.tA, (int)V.n, V.tmp.p, V.x.p, EpArgs{V.rhs.p, V.tmp.p, V.dinv.p, V.omega, nullptr, 0});
-        } else {                               // x += P x_{l+1} ; backward sweep
-          spmv(EP_AXPY, V.tP, (int)V.n, h->lev[l + 1].x.p, V.x.p, EpArgs{nullptr, V.x.p, nullptr, 1.0, nullptr, 0});
-          gs(V, levels[l].n_colors, 1, gs_lds_ok(l));
-        }
-      }
-      h->tail_prog.upload(prog);
-      h->tail_ops = (int)prog.size();
-      h->tail_level = T;
-    }
-  }
-  HIPCHK(hipDeviceSynchronize());
-  clk.lap("coarse inverse, tail program");
-  if (dense_first >= 0) build_dense_tail(*h, d, levels, dense_first);
-  clk.lap("collapsed coarse levels (dense operator)");
-  return h.release();
-}
-
-}  // namespace amgx
+#include "build_level.hpp"
 
 // ---------------------------------------------------------------------------------------------------
 // C ABI
@@ -4019,7 +3345,7 @@ const char* amgx_last_error(amgx_handle h) { return (h && h->h) ? h->h->err.c_st
 int amgx_create(const amgx_hierarchy_desc* desc, amgx_handle* out) {
   try {
     if (!out) throw amgx::Err("amgx_create: null output");
-    amgx::Handle* h = amgx::create(desc);
+    amgx::Handle* h = amgx::create(desc, amgx::Knobs::from_env());
     *out = new amgx_handle_t{h};
     return 0;
   } catch (const std::exception& e) { g_create_err = e.what(); return 1; }
@@ -4411,9 +3737,9 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
     } else if (L.sm_type == AMGX_SM_GS && gsb.on()) {
       v[19] = 4; v[20] = gsb.G; v[21] = gsb.TH; v[22] = gsb.B; v[23] = gsb.n_colors; v[25] = gsb.has_split;
       v[26] = gsb.lowin_maxw; v[27] = gsb.full_maxw;
-      v[28] = gsb.has_split && amgx::gsb_narrow(gsb);
-      v[29] = amgx::gsb_mid(gsb);
-      v[30] = amgx::gsb_lw(gsb);
+      v[28] = gsb.has_split && gsb.narrow;
+      v[29] = gsb.mid;
+      v[30] = gsb.lw;
       v[32] = gsb.has_fullLW ? gsb.flw_no_window : 0;
     } else if (L.sm_type == AMGX_SM_GS && gs.n_colors > 0) {
       v[23] = gs.n_colors; v[21] = amgx::BLOCK;

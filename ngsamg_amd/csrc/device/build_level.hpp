@@ -1,0 +1,717 @@
+// Construction of a Handle (amgx_create): create() is the orchestration, every image of a level is built by one named step over
+// the LevelBuild context.  The steps start the concurrent host tasks of a level (SetupTasks) in the order and grouping of the
+// "task" lines of AMGX_SETUP_LOG; which path a level takes is decided here, from the switches in knobs.hpp.
+//
+// Included from amgx.hip (after the builders it calls); not a stand-alone header.
+#pragma once
+
+namespace amgx {
+
+// What the steps of one level share.  Declared BEFORE the task pool: the workers capture it by reference, and an exception between
+// tasks.run() and tasks.wait() must join the workers -- ~SetupTasks -- before the buffers they read are freed.
+struct LevelBuild {
+  const Knobs& K;
+  SetupClock& clk;
+  const amgx_level_desc& s;             // this level ...
+  const amgx_level_desc* c;             // ... and the next coarser one (null on the last level)
+  DevLevel& L;
+  int l;
+  int cycle;
+  int dense_first;                      // see create()
+  // big scalar levels: the CSR arrays go to the device once and kernels write the images of A, A' and Q there (devbuild.hpp)
+  DevCsrSrc csrA;
+  DbDiagInfo diagA;
+  bool dev_images = false, verify_images = false;
+  // big square-block levels: the block-CSR arrays go to the device once, the BSELL images (A; the block-hybrid Gauss-Seidel
+  // images) are gathered there
+  DevBcsrSrc csrB;
+  bool dev_bsell = false, verify_bsell = false;
+  bool last() const { return c == nullptr; }
+};
+
+// shape and smoother-parameter validation; the scalar fields of the level
+static void check_level(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  // n_cols > n_rows: the trailing columns are ghost entries of a rank-partitioned level (filled by the caller's
+  // halo exchange before every operation that gathers from them)
+  if (s.A.n_cols < s.A.n_rows || s.A.br != s.A.bc) throw Err("level matrix must have n_cols >= n_rows and square blocks");
+  L.n = s.A.n_rows; L.ncols = s.A.n_cols; L.bs = s.A.br;
+  L.sm_type = s.sm_type; L.omega = s.omega; L.sm_steps = s.sm_steps; L.sm_symm = s.sm_symm;
+  if (s.sm_type != AMGX_SM_JACOBI && s.sm_type != AMGX_SM_GS && s.sm_type != AMGX_SM_BGS && s.sm_type != AMGX_SM_CHEBY) throw Err("unknown smoother type");
+  if (s.sm_type == AMGX_SM_CHEBY) {
+    const int deg = s.cheb_degree == 0 ? 2 : s.cheb_degree;
+    if (deg < 1 || deg > 8) throw Err("amgx_create: cheb_degree must be 1 .. 8 (0: default 2), got " + std::to_string(s.cheb_degree));
+    if (!(s.cheb_lambda_max >= 0.0)) throw Err("amgx_create: cheb_lambda_max must be >= 0 (0: estimated on the device)");
+    if (s.cheb_ratio != 0.0 && !(s.cheb_ratio > 1.0)) throw Err("amgx_create: cheb_ratio must be > 1 (0: default 10)");
+    if (s.A.n_cols != s.A.n_rows) throw Err("amgx_create: the Chebyshev smoother is not available on rank-partitioned levels");
+    L.cheb_degree = deg;
+    L.cheb_ratio = s.cheb_ratio == 0.0 ? 10.0 : s.cheb_ratio;
+    if (s.cheb_lambda_max > 0.0) L.cheb_set_interval(s.cheb_lambda_max);
+  }
+  check_matrix(s.A, "A");            // (before anything reads rowptr[n_rows]: a NULL / garbage descriptor is an error, not a crash)
+}
+
+// task "A": the image of the level matrix -- device BSELL builder, device SELL builder, host builder, in this order
+static void level_matrix_task(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  if (B.dev_bsell) {
+    if (dev_build_bsell(B.csrB, nullptr, 0, BB_ALL, DbBgsbMaps(), 0, 1.30, L.A)) {
+      L.A.n_rows = s.A.n_rows; L.A.n_cols = s.A.n_cols; L.A.br = s.A.br; L.A.bc = s.A.bc;
+      L.A.nnz = s.A.rowptr[s.A.n_rows];
+      L.A.lanes = pick_lanes(L.A.n_rows ? (double)L.A.nnz / (double)L.A.n_rows : 0.0);
+      if (B.verify_bsell) verify_level_bsell(B.K, s.A, L.A);
+      return;
+    }
+    L.A = DevMatrix();
+  }
+  if (B.dev_images && dev_upload_matrix(B.K, B.csrA, L.A, true, 1.35, 0, &B.diagA)) {
+    if (B.verify_images) verify_level_image(B.K, s.A, L.A);
+    return;
+  }
+  if (B.verify_images) verify_level_declined(B.K, s.A);
+  // block GS walks the CSR arrays of A, so keep A in CSR there
+  upload_matrix(B.K, s.A, L.A, "A", true, true, s.sm_type == AMGX_SM_GS && s.A.br > 1 && s.gs_block_rows == 0);
+}
+
+// the CSR arrays of a big level to the device (calling thread), then task "A"
+static void upload_level_matrix(LevelBuild& B, SetupTasks& tasks) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  B.dev_images = dev_images_wanted(B.K, s.A);
+  B.verify_images = B.dev_images && B.K.verify_images;
+  if (B.dev_images) {
+    check_matrix(s.A, "A");
+    B.csrA.upload(s.A);
+    if (s.dinv) L.dinv.upload(s.dinv, (size_t)(B.last() ? L.n : L.ncols) * L.bs * L.bs);
+    B.diagA = dev_diag_check(B.csrA, (s.dinv && s.A.n_rows <= s.A.n_cols) ? L.dinv.p : nullptr);
+    B.clk.lap("CSR of A to the device", B.l);
+  }
+  const bool keep_csr_A = s.sm_type == AMGX_SM_GS && s.A.br > 1 && s.gs_block_rows == 0;
+  B.dev_bsell = dev_bsell_wanted(B.K, s.A) && s.A.n_rows == s.A.n_cols && !keep_csr_A;
+  B.verify_bsell = B.dev_bsell && B.K.verify_images;
+  if (B.dev_bsell) {
+    check_matrix(s.A, "A");
+    B.csrB.upload(s.A);
+    B.clk.lap("block CSR of A to the device", B.l);
+  }
+  tasks.run([&B] { level_matrix_task(B); }, "A");
+}
+
+// task "P, PT": the transfer matrices and, where asked for, the column-blocked restriction
+static void upload_transfers(LevelBuild& B, SetupTasks& tasks) {
+  const amgx_level_desc &s = B.s, &c = *B.c;
+  if (s.P.n_rows != s.A.n_rows || s.P.n_cols > c.A.n_cols || s.P.n_cols < c.A.n_rows || s.P.br != s.A.br || s.P.bc != c.A.br)
+    throw Err("P does not match the level matrices");
+  if (s.PT.n_rows != s.P.n_cols || s.PT.n_cols != s.P.n_rows || s.PT.br != s.P.bc || s.PT.bc != s.P.br)
+    throw Err("PT does not match P");
+  if (!s.dinv) throw Err("dinv missing");
+  tasks.run([&B] {
+    const amgx_level_desc& s = B.s;
+    DevLevel& L = B.L;
+    upload_matrix(B.K, s.P, L.P, "P", true, false, false, 1.35, s.P.br == 1 && s.P.bc == 1 ? -SELL_WIN : 0, nullptr, 1);
+    upload_matrix(B.K, s.PT, L.PT, "PT", true, false, false, 1.35, 0, nullptr, 2);
+    // big scalar levels restrict through the column-blocked form (the P^T gather is TA/L2-bound there)
+    // Measured non-win (profiles/r01/restrict_blocked.txt): 121 + 22 us vs 134 us for the P^T gather at cfg 2,
+    // so the blocked form is OFF unless AMGX_RESTRICT_MIN_ROWS asks for it (kept for the fused-residual plan).
+    if (s.P.br == 1 && s.P.bc == 1 && s.P.n_rows >= B.K.restrict_min_rows && s.P.rowptr[s.P.n_rows] < I32_MAX)
+      build_restrict(B.K, s.P, L.R);
+  }, "P, PT");
+}
+
+// task "smoother data": dinv and the Gauss-Seidel forms
+static void build_smoother_data(LevelBuild& B, SetupTasks& tasks) {
+  tasks.run([&B] {
+    const amgx_level_desc& s = B.s;
+    DevLevel& L = B.L;
+    if (!B.dev_images) L.dinv.upload(s.dinv, (size_t)L.ncols * L.bs * L.bs);
+    if (s.sm_type == AMGX_SM_GS && s.gs_block_rows > 0 && s.A.br > 1) {
+      build_bgsb(B.K, s, L, B.dev_bsell ? &B.csrB : nullptr);
+      if (B.verify_bsell) verify_bgsb(B.K, s, L);
+    }
+    else if (s.sm_type == AMGX_SM_GS && s.gs_block_rows > 0) {
+      build_gsb(B.K, s, L, &s.P, B.dev_images ? &B.csrA : nullptr);
+      if (B.verify_images) verify_gsb(B.K, s, L);
+    }
+    else if (s.sm_type == AMGX_SM_GS) build_gs(B.K, s, L);
+    if (s.sm_type == AMGX_SM_BGS) build_bgs(s, L);
+  }, "smoother data");
+}
+
+// the coarsest level has no transfers: its smoother data on the calling thread
+static void build_coarsest_smoother_data(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  L.dinv.upload(s.dinv, (size_t)L.n * L.bs * L.bs);
+  if (s.sm_type == AMGX_SM_GS && s.color && s.gs_block_rows > 0 && s.A.br > 1) build_bgsb(B.K, s, L);
+  else if (s.sm_type == AMGX_SM_GS && s.color && s.gs_block_rows > 0) build_gsb(B.K, s, L, nullptr);
+  else if (s.sm_type == AMGX_SM_GS && s.color) build_gs(B.K, s, L);
+  if (s.sm_type == AMGX_SM_BGS && s.bgs_n_blocks > 0) build_bgs(s, L);
+}
+
+// ---- scalar Jacobi levels: the image for the fused down pass (pre-smoothing + restriction) ----------------------------------
+
+// dinv_i * A_ii == 1 (to 1e-13) on every row with dinv_i != 0
+static bool host_diag_plain(const amgx_level_desc& s) {
+  std::vector<char> notplain(setup_threads(), 0);
+  par_for(s.A.n_rows, [&](int64_t i0, int64_t i1, int t) {
+    for (int64_t i = i0; i < i1; ++i) {
+      if (s.dinv[i] == 0.0) continue;
+      double aii = 0.0;
+      for (int64_t k = s.A.rowptr[i]; k < s.A.rowptr[i + 1]; ++k) if (s.A.col[k] == i) { aii = s.A.val[k]; break; }
+      if (!(std::fabs(s.dinv[i] * aii - 1.0) < 1e-13)) { notplain[t] = 1; break; }
+    }
+  });
+  for (char cc : notplain) if (cc) return false;
+  return true;
+}
+
+// A' = A diag(omega Dinv) in CSR order (uninitialised allocation: every entry is written)
+// (rank-partitioned levels: dinv must cover the ghost columns too, i.e. n_cols entries)
+static std::unique_ptr<double[]> scaled_values(const amgx_level_desc& s) {
+  const int64_t nnz = s.A.rowptr[s.A.n_rows];
+  std::unique_ptr<double[]> sv(new double[(size_t)std::max<int64_t>(1, nnz)]);
+  par_for(nnz, [&](int64_t k0, int64_t k1, int) { for (int64_t k = k0; k < k1; ++k) sv[k] = s.A.val[k] * (s.omega * s.dinv[s.A.col[k]]); }, 1 << 16);
+  return sv;
+}
+
+// long-row levels (>= 1) of a reference-shaped hierarchy: the "local window" image for the fused down kernel
+static bool lw_image(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  const int64_t nnzA = s.A.rowptr[s.A.n_rows];
+  const double avgA = s.A.n_rows ? (double)nnzA / (double)s.A.n_rows : 0.0;
+  // (rank-partitioned levels too: the window of an interior chunk holds owned columns only, ghost columns are just columns)
+  if (B.l == 0 || avgA < 24.0 || !B.K.lw_wanted(s.A.n_rows) || !B.K.fused_restrict_ok(s.P, 1)) return false;
+  // two lanes per row (256-row chunks); levels whose 256-row chunks touch too many columns: four lanes (128-row chunks)
+  int G = 0;
+  std::unique_ptr<double[]> sv;
+  auto host_lw = [&](int g, DevMatrix& M, DevBuf<int32_t>& cp, DevBuf<int32_t>& cc) {
+    if (!sv) sv = scaled_values(s);
+    return build_sell_lw(B.K, s.A, sv.get(), g, M, cp, cc);
+  };
+  // (device: window lists by a bitmap in LDS, devbuild.hpp dev_build_lw; AMGX_HOST_LW=1 keeps the host builder)
+  const bool dev_lw = B.dev_images && !B.K.host_lw && !B.K.host_images;
+  for (int g : {2, 4}) {
+    bool ok = false;
+    if (dev_lw) {
+      ok = dev_build_lw(B.csrA, false, g, B.K.lw_cap(LW_CAP), B.K.lw_test_cap_on, L.dinv.p, s.omega, L.ApreLW, L.lw_cptr, L.lw_ccol);
+      if (ok && B.verify_images) verify_apre_lw(L, g, host_lw);
+      if (!ok) { L.ApreLW = DevMatrix(); L.lw_cptr.release(); L.lw_ccol.release(); }
+    }
+    if (!ok) ok = host_lw(g, L.ApreLW, L.lw_cptr, L.lw_ccol);
+    if (ok) { G = g; break; }
+    L.ApreLW = DevMatrix();
+  }
+  if (!G) return false;
+  L.fused_block = 512;
+  build_restrict(B.K, s.P, L.RF, 512 / G, 4 * 512, 512);
+  if (L.RF.empty()) { L.ApreLW = DevMatrix(); L.lw_cptr.release(); L.lw_ccol.release(); return false; }
+  return true;
+}
+
+// levels whose A lies on at most 16 diagonals and equals its transpose bit for bit (Kuhn P1 matrices in natural vertex order):
+// the fused down kernel streams the symmetric diagonal image of A instead of A' (dia_pre_restrict_kernel) -- 7 of the 15
+// diagonals from HBM at cfg 2, the lower ones are shifted re-reads of the same arrays, and no index stream.  Not on levels
+// a rank-partitioned driver runs stage by stage (dense_first < 0), nor below AMGX_DIA_MIN_ROWS rows (2 M: the smaller levels
+// keep the SELL image).  AMGX_NO_DIA=1 disables it.
+static bool dia_image(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  if (B.K.no_dia || B.dense_first < 0 || s.A.n_rows != s.A.n_cols || s.A.n_rows < std::max<int64_t>(1, B.K.dia_min_rows) ||
+      s.omega == 0.0 || B.K.no_wdiag || !B.K.fused_restrict_ok(s.P, 1)) return false;
+  // the kernel puts the diagonal term back as omega*b_i (0 where dinv_i = 0): dinv must be the plain inverse diagonal
+  if (B.dev_images ? !B.diagA.plain : !host_diag_plain(s)) return false;
+  auto par = [](int64_t nb, auto&& f) { par_for(nb, [&](int64_t a, int64_t b, int) { for (int64_t q = a; q < b; ++q) f(q); }, 1); };
+  int32_t off[dia::MAX_UPPER];
+  const int K = dia::detect(s.A.n_rows, s.A.n_cols, s.A.rowptr, s.A.col, s.A.val, dia::MAX_DIAGS, 1.05, off, par);
+  if (K <= 0 || K > DIA_MAX_UPPER) return false;
+  DevDia& D = L.dia;
+  D.K = K;
+  for (int k = 0; k < K; ++k) D.off[k] = off[k];
+  std::vector<double> hv;
+  if (!B.dev_images || B.verify_images) {
+    hv.resize((size_t)K * (size_t)s.A.n_rows);
+    dia::upper_image(s.A.n_rows, s.A.rowptr, s.A.col, s.A.val, K, off, hv.data(), par);
+  }
+  if (B.dev_images) {
+    dev_build_dia(B.csrA, D);
+    if (B.verify_images) verify_dia(D, hv);
+  } else
+    D.val.upload(hv);
+  L.fused_block = 512;
+  build_restrict_chunks(B.K, s.P, L.RF, 512, 6 * 512, 512, true);
+  if (L.RF.empty()) { L.dia = DevDia(); return false; }
+  return true;
+}
+
+// the chunk-local restriction for the image of A' the level got: the local-window image first, the SELL chunk form after it
+static void fused_restrict(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  if (lw_image(B)) return;
+  // fused pre-smoothing + restriction when A' is in the one-thread-per-row SELL form (big levels).
+  // Same-process A/B with 4 instances per variant (profiles/r01/restrict_fused.txt): 1-3 % faster cycle than the
+  // separate pre-smoothing + P^T gather kernels, and r is never written to HBM.  AMGX_NO_FUSED_RESTRICT=1 disables it.
+  const int G = L.Apre.lanes;
+  if (L.Apre.fmt == FMT_SELL && L.Apre.sell.win == SELL_WIN && G == 1 && SELL_WIN == 512 && B.K.fused_restrict_ok(s.P, 1))
+  {
+    L.fused_block = SELL_WIN;              // windowed A': a chunk = a window (sell_win_pre_restrict_kernel)
+    build_restrict(B.K, s.P, L.RF, SELL_WIN, 6 * SELL_WIN, SELL_WIN);
+  }
+  else if (L.Apre.fmt == FMT_SELL && !L.Apre.sell.win && (G == 1 || G == 2 || G == 4 || G == 8) && B.K.fused_restrict_ok(s.P, G))
+  {
+    L.fused_block = B.K.fused_block;       // same-process A/B: 512 < 1024 (epilogues of more, smaller workgroups overlap better)
+    if (G > 1) L.fused_block = 512;        // (several lanes per row: the chunk holds 512 / G rows)
+    // big square one-thread-per-row levels: compact chunks (cluster_slices) -- fewer partial sums per coarse row
+    // (not on a handle that a rank-partitioned driver runs stage by stage -- dense_first < 0 --: its launches cover interior and
+    //  boundary chunk RANGES, which only consecutive chunks have; a rank without ghost columns, e.g. world size 1, has a square level)
+    build_restrict_chunks(B.K, s.P, L.RF, L.fused_block / G, 6 * L.fused_block, L.fused_block, G == 1 && B.dense_first >= 0 && s.A.n_rows == s.A.n_cols);
+    // several lanes per row: the kernel exists for 4 entries of P per thread only; a chunk of 512 / G rows with more
+    // than 2048 entries (a prolongation with more than 4 G entries per row) keeps the separate kernels
+    if (G > 1 && L.RF.ept != 4) L.RF = DevRestrict();
+  }
+}
+
+// task "A' + fused restriction": the diagonal image, else A' on the device, else A' on the host; then the chunk-local restriction
+static void jacobi_down_task(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  if (dia_image(B)) return;
+  // (device builder: A' = A diag(omega Dinv) from the CSR of A that is already there; the diagonal slot carries omega*Dinv_i
+  //  under the same conditions as below)
+  const bool dev_wdiag = s.omega != 0.0 && !B.K.no_wdiag && B.diagA.plain;
+  // levels >= 1 of a reference-shaped hierarchy have ragged long rows (plain slices pad 20 % at the 1.24 M-row level of cfg 2,
+  // length-sorted windows 3.6 %).  Measured NON-win (profiles/r04/l1_experiments.txt): the windowed image with its fused kernel
+  // (sell_win_pre_restrict_kernel) runs that level in 256 us against 215 us -- these levels are bound by the scattered gathers
+  // of x, and sorting the rows of a window by length puts unrelated rows into neighbouring lanes.  Opt-in: AMGX_APRE_WINDOW=1.
+  const int apre_win = (B.l >= 1 && s.A.n_rows == s.A.n_cols && B.K.apre_window) ? SELL_WIN : 0;
+  if (B.dev_images && !B.verify_images &&
+      dev_upload_matrix(B.K, B.csrA, L.Apre, true, 1.35, apre_win, &B.diagA, L.dinv.p, s.omega, dev_wdiag ? L.dinv.p : nullptr)) {
+    fused_restrict(B);
+    return;
+  }
+  // column-scaled image for the fused pre-smoothing pass (memory for bandwidth: one more copy of A)
+  const std::unique_ptr<double[]> sv = scaled_values(s);
+  amgx_matrix As = s.A;
+  As.val = sv.get();
+  // one-thread-per-row form: the diagonal slot carries omega*Dinv_i (SellMat::wdiag), the epilogue then needs no
+  // dinv stream (80 MB per pass at cfg 2); AMGX_NO_WDIAG=1 keeps A'_ii there
+  std::vector<double> wdv;
+  if (s.omega != 0.0 && !B.K.no_wdiag) {
+    // the epilogue re-inserts A'_ii b_i as omega*b_i (or 0 where dinv_i = 0): valid iff dinv is the plain inverse diagonal
+    if (host_diag_plain(s)) {
+      wdv.resize((size_t)s.A.n_rows);
+      par_for(s.A.n_rows, [&](int64_t i0, int64_t i1, int) { for (int64_t i = i0; i < i1; ++i) wdv[i] = s.omega * s.dinv[i]; }, 1 << 16);
+    }
+  }
+  const double* wd = wdv.empty() ? nullptr : wdv.data();
+  if (B.dev_images && B.verify_images) verify_build_apre(B.K, As, B.csrA, B.diagA, s.omega, apre_win, wd, dev_wdiag, L);
+  else upload_matrix(B.K, As, L.Apre, "A (pre-smoothing image)", true, true, false, 1.35, apre_win, wd);
+  fused_restrict(B);
+}
+
+static void build_jacobi_down(LevelBuild& B, SetupTasks& tasks) {
+  tasks.run([&B] { jacobi_down_task(B); }, "A' + fused restriction");
+}
+
+// ---- post-smoothing folded into the prolongation (V-cycle) -----------------------------------------------------------------
+
+// the local-window image of a Q that the device product left in csrQ: device builder, else the host builder from a download
+static void build_qlw_of_dev_q(LevelBuild& B, const DevCsrSrc& csrQ) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  bool qlw_done = false;
+  if (!B.K.host_lw) {
+    qlw_done = dev_build_lw(csrQ, true, 1, B.K.lw_cap_small(QW_CAP), B.K.lw_test_cap_on, nullptr, 0.0, L.QLW, L.qlw_cptr, L.qlw_ccol);
+    if (!qlw_done) { L.QLW = DevMatrix(); L.qlw_cptr.release(); L.qlw_ccol.release(); }
+    else if (B.verify_images) verify_qlw(B.K, csrQ, s.A.n_rows, L);
+  }
+  if (!qlw_done) {
+    SetupClock qclk(B.K);
+    std::vector<int64_t> rp = db_download(csrQ.rowptr, (size_t)s.A.n_rows + 1);
+    std::vector<int32_t> cc = db_download(csrQ.col, (size_t)std::max<int64_t>(1, csrQ.nnz));
+    std::vector<double> vv = db_download(csrQ.val, (size_t)std::max<int64_t>(1, csrQ.nnz));
+    qclk.lap("  lw-win: download of Q", B.l);
+    if (!build_sell_lw_windowed(B.K, s.A.n_rows, csrQ.n_cols, rp.data(), cc.data(), vv.data(), L.QLW, L.qlw_cptr, L.qlw_ccol)) L.QLW = DevMatrix();
+  }
+}
+
+// task "Q = (I - w Dinv A) P" on a square scalar level: the sparse product and the windowed image of its result on the device
+// (devbuild.hpp), else on the host
+static void scalar_q_task(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  const double qpad = B.K.q_max_pad;
+  if (B.dev_images) {
+    check_matrix(s.P, "P");
+    DevCsrSrc csrP, csrQ;
+    csrP.upload(s.P);
+    if (dev_fold_prolongation(B.csrA, csrP, L.dinv.p, s.omega, csrQ) && dev_upload_matrix(B.K, csrQ, L.Q, false, qpad, SELL_WIN, nullptr)) {
+      if (B.K.qlw_wanted(s.A.n_rows)) build_qlw_of_dev_q(B, csrQ);
+      if (B.verify_images) verify_q(B.K, s, csrQ, qpad, L.Q);
+      return;
+    }
+    L.Q = DevMatrix();
+    if (B.verify_images) std::fprintf(stderr, "[amgx_create] AMGX_VERIFY_IMAGES: level %d: Q is left to the host builder\n", B.l);
+  }
+  HostCsr q;
+  fold_prolongation(s.A, s.P, s.dinv, s.omega, q);
+  if (q.rowptr[s.A.n_rows] < I32_MAX) {
+    amgx_matrix Qm = s.P;
+    Qm.rowptr = q.rowptr.data(); Qm.col = q.col.data(); Qm.val = q.val.data();
+    upload_matrix(B.K, Qm, L.Q, "Q (folded post-smoothing prolongation)", true, false, false, qpad, SELL_WIN);
+    if (B.K.qlw_wanted(s.A.n_rows) &&
+        !build_sell_lw_windowed(B.K, s.A.n_rows, s.P.n_cols, q.rowptr.data(), q.col.data(), q.val.data(), L.QLW, L.qlw_cptr, L.qlw_ccol)) L.QLW = DevMatrix();
+  }
+}
+
+// block Jacobi levels of the V-cycle: the same fold in block form (Q has the block shape of P)
+static void block_q_task(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  HostCsr q;
+  fold_prolongation(s.A, s.P, s.dinv, s.omega, q);
+  // Fold only where it pays: the way up then streams Q instead of A + P (+ the round trip of x + P x_c), but
+  // rectangular-block Q runs through the CSR block kernels (~4.5 TB/s) while square-block A streams as BSELL
+  // (~6.5 TB/s).  Measured at the cfg 3 shapes (profiles/r01/block_fold.txt): 3x3 fine level with 3x6 blocks in
+  // P: Q has 10.8 blocks/row = 1.6 GB vs A + P = 1.65 GB -> literal is 55 us faster; 6x6 levels: Q = 0.36 GB
+  // vs 1.04 GB -> folded is 100 us faster.
+  auto bytes = [](int64_t nnz, int br, int bc) { return (double)nnz * (8.0 * br * bc + 4.0); };
+  const double bq = bytes(q.rowptr[s.A.n_rows], s.P.br, s.P.bc);
+  const double blit = bytes(s.A.rowptr[s.A.n_rows], s.A.br, s.A.bc) + bytes(s.P.rowptr[s.P.n_rows], s.P.br, s.P.bc);
+  if (q.rowptr[s.A.n_rows] < I32_MAX && bq < 0.7 * blit) {
+    amgx_matrix Qm = s.P;
+    Qm.rowptr = q.rowptr.data(); Qm.col = q.col.data(); Qm.val = q.val.data();
+    upload_matrix(B.K, Qm, L.Q, "Q (folded post-smoothing prolongation)");
+  }
+}
+
+// Square levels: Q is built here.  Rank-partitioned levels: Q needs the P rows of the ghost vertices, so the caller supplies it
+// (amgx_level_desc.Q) and drives the level through amgx_cycle_down / amgx_cycle_up.
+static void build_folded_prolongation(LevelBuild& B, SetupTasks& tasks) {
+  const amgx_level_desc &s = B.s, &c = *B.c;
+  const bool one_step = s.sm_type == AMGX_SM_JACOBI && s.sm_steps <= 1 && !s.sm_symm;
+  if (one_step && s.A.br == 1 && B.cycle == AMGX_CYCLE_V && s.P.br == 1 && s.P.bc == 1 && !B.K.no_fold) {
+    if (s.Q.rowptr) {
+      if (s.Q.n_rows != s.A.n_rows || s.Q.br != 1 || s.Q.bc != 1 || s.Q.n_cols < c.A.n_rows || s.Q.n_cols > c.A.n_cols)
+        throw Err("Q does not match the level matrices");
+      if (s.Q.rowptr[s.Q.n_rows] >= I32_MAX) throw Err("Q: too many entries");
+      tasks.run([&B] {
+        const amgx_level_desc& s = B.s;
+        DevLevel& L = B.L;
+        upload_matrix(B.K, s.Q, L.Q, "Q (folded post-smoothing prolongation)", true, false, false, B.K.q_max_pad, SELL_WIN);
+        // (rank-partitioned level: the caller's Q, columns [owned | ghost] of the coarse level)
+        if (B.K.qlw_wanted(s.A.n_rows) &&
+            !build_sell_lw_windowed(B.K, s.Q.n_rows, s.Q.n_cols, s.Q.rowptr, s.Q.col, s.Q.val, L.QLW, L.qlw_cptr, L.qlw_ccol)) L.QLW = DevMatrix();
+      });
+    } else if (s.A.n_rows == s.A.n_cols && s.P.n_cols == c.A.n_rows)
+      tasks.run([&B] { scalar_q_task(B); }, "Q = (I - w Dinv A) P");
+  }
+  if (one_step && s.A.br > 1 && B.cycle == AMGX_CYCLE_V && s.A.n_rows == s.A.n_cols && s.P.n_cols == c.A.n_rows && s.P.br == s.A.br &&
+      !B.K.no_fold && !B.K.no_block_fold)
+    tasks.run([&B] { block_q_task(B); });
+}
+
+// scalar Chebyshev levels: the residual after pre-smoothing feeds the chunk-local restriction without going through HBM
+// (sell_pre_restrict_kernel<.., MODE 2> on the SELL image of A itself), under the rule of the Jacobi levels' fused down kernel.
+// AMGX_CHEB_NO_FUSED_RESTRICT=1 (or AMGX_NO_FUSED_RESTRICT=1) keeps EP_RES + the separate restriction kernels.
+static void cheb_fused_restrict(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  if (s.sm_type == AMGX_SM_CHEBY && s.A.br == 1 && s.sm_steps <= 1 && !s.sm_symm && L.A.fmt == FMT_SELL && !L.A.sell.win &&
+      (L.A.lanes == 1 || L.A.lanes == 2 || L.A.lanes == 4 || L.A.lanes == 8) && B.K.fused_restrict_ok(s.P, L.A.lanes) &&
+      !B.K.cheb_no_fused_restrict)
+  {
+    const int G = L.A.lanes;
+    L.fused_block = 512;
+    build_restrict_chunks(B.K, s.P, L.RF, 512 / G, 6 * 512, 512, G == 1 && B.dense_first >= 0);
+    if (G > 1 && L.RF.ept != 4) L.RF = DevRestrict();
+  }
+}
+
+// workgroup -> rows mapping of the streaming kernels on this level (SellMat::xcd)
+static void set_xcd_modes(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  const int mode = B.K.xcd;
+  const double avg = s.A.n_rows ? (double)s.A.rowptr[s.A.n_rows] / (double)s.A.n_rows : 0.0;
+  const int on = mode >= 2 || (mode == 1 && avg >= 24.0 && s.A.n_rows >= 200000);
+  L.A.sell.xcd = L.Apre.sell.xcd = L.Q.sell.xcd = L.gsb.rest.sell.xcd = on;
+  L.dia.xcd = B.K.dia_xcd ? 1 : 0;        // (A/B hook: each XCD walks one contiguous eighth of the chunks)
+  if (mode >= 3) L.P.sell.xcd = L.PT.sell.xcd = on;
+}
+
+static void alloc_level_vectors(LevelBuild& B) {
+  DevLevel& L = B.L;
+  const size_t len = (size_t)std::max<int64_t>(1, L.ext_len());
+  L.x.alloc(len); L.rhs.alloc(len); L.res.alloc(len); L.tmp.alloc(len);
+  HIPCHK(hipMemset(L.x.p, 0, len * sizeof(double)));
+  HIPCHK(hipMemset(L.rhs.p, 0, len * sizeof(double)));
+  HIPCHK(hipMemset(L.res.p, 0, len * sizeof(double)));
+  HIPCHK(hipMemset(L.tmp.p, 0, len * sizeof(double)));
+  if (L.sm_type == AMGX_SM_CHEBY) { L.d.alloc(len); HIPCHK(hipMemset(L.d.p, 0, len * sizeof(double))); }
+}
+
+// ---- after the level loop ---------------------------------------------------------------------------------------------------
+
+// clev = inv: the inverse handed over by the host, or the coarsest matrix inverted on its free dofs here
+static void build_coarse_inverse(Handle& h, const amgx_hierarchy_desc* d, const amgx_level_desc& s) {
+  const DevLevel& L = h.lev.back();
+  if (d->coarse_n != L.len()) throw Err("clev = inv: coarse_n does not match the coarsest level");
+  h.coarse_n = d->coarse_n;
+  if (d->coarse_inv) {
+    h.coarse_ld = d->coarse_n;
+    h.coarse_inv.upload(d->coarse_inv, (size_t)d->coarse_n * d->coarse_n);
+    return;
+  }
+  // no inverse handed over (the host setup stops at 4096 unknowns): invert the coarsest matrix on its free dofs here
+  // (dense_spd.hpp: blocked Gauss-Jordan, trailing updates on the matrix cores)
+  const int64_t cap = h.knobs.coarse_dense_max;
+  if (s.A.n_rows != s.A.n_cols) throw Err("clev = inv: the coarsest level of a rank-partitioned hierarchy cannot be inverted locally");
+  if (d->coarse_n > cap) throw Err("clev = inv: coarsest level has " + std::to_string(d->coarse_n) + " unknowns, more than AMGX_COARSE_DENSE_MAX = " +
+                                   std::to_string(cap) + " (a dense inverse would stream " + std::to_string(8 * d->coarse_n * d->coarse_n / 1000000) + " MB per application)");
+  const int64_t n = d->coarse_n, npad = (n + GJ_T - 1) / GJ_T * GJ_T;
+  const int bs = s.A.br;
+  struct { DevBuf<int32_t> rowptr, col; DevBuf<double> val; } cA;       // (DevCsr holds scalar matrices only)
+  {
+    const int64_t nnzc = s.A.rowptr[s.A.n_rows];
+    std::vector<int32_t> rp((size_t)s.A.n_rows + 1);
+    for (int64_t i = 0; i <= s.A.n_rows; ++i) rp[i] = (int32_t)s.A.rowptr[i];
+    cA.rowptr.upload(rp);
+    cA.col.upload(s.A.col, (size_t)nnzc);
+    cA.val.upload(s.A.val, (size_t)nnzc * bs * bs);
+  }
+  DevBuf<uint8_t> fr;
+  if (s.free_dofs) fr.upload(s.free_dofs, (size_t)s.A.n_rows);
+  h.coarse_inv.alloc((size_t)npad * npad);
+  h.coarse_ld = npad;
+  hipLaunchKernelGGL(gj_zero_kernel, dim3(Handle::grid_for(npad * npad)), dim3(BLOCK), 0, h.stream, npad * npad, h.coarse_inv.p);
+  hipLaunchKernelGGL(gj_scatter_kernel, dim3(Handle::grid_for(s.A.n_rows)), dim3(BLOCK), 0, h.stream, s.A.n_rows, bs, cA.rowptr.p, cA.col.p, cA.val.p,
+                     fr.p, npad, h.coarse_inv.p);
+  hipLaunchKernelGGL(gj_fix_diag_kernel, dim3(Handle::grid_for(npad)), dim3(BLOCK), 0, h.stream, npad, n, bs, fr.p, npad, 1.0, h.coarse_inv.p);
+  HIPCHK(hipGetLastError());
+  h.coarse_pivot = dense_spd_inverse(h.coarse_inv.p, npad, npad, h.stream);
+  if (!(h.coarse_pivot > 1e-14)) throw Err("clev = inv: the coarsest matrix is not positive definite on its free dofs (pivot ratio " +
+                                           std::to_string(h.coarse_pivot) + "); use clev = none or a smaller coarsest level");
+  hipLaunchKernelGGL(gj_fix_diag_kernel, dim3(Handle::grid_for(npad)), dim3(BLOCK), 0, h.stream, npad, n, bs, fr.p, npad, 0.0, h.coarse_inv.p);
+  HIPCHK(hipStreamSynchronize(h.stream));
+}
+
+// first level of the single-workgroup coarse tail (V-cycle, plain scalar smoothers, exact coarse solve, square levels); -1: none
+static int tail_first_level(const Handle& h, const amgx_hierarchy_desc* d, const amgx_level_desc* levels) {
+  const int L = d->n_levels;
+  if (!(d->cycle == AMGX_CYCLE_V && d->clev == AMGX_CLEV_INV && L >= 2 && !h.knobs.no_tail_kernel)) return -1;
+  int T = L - 1;
+  while (T - 1 >= 1) {
+    const amgx_level_desc& s = levels[T - 1];
+    const int64_t cap = s.sm_type == AMGX_SM_GS ? TAIL_MAX_ROWS_GS : TAIL_MAX_ROWS;
+    const bool ok = s.A.br == 1 && s.A.n_rows == s.A.n_cols && s.A.n_rows <= cap &&
+                    (s.sm_type == AMGX_SM_JACOBI || (s.sm_type == AMGX_SM_GS && s.color && s.n_colors > 0 && s.gs_block_rows == 0)) &&
+                    s.sm_steps <= 1 && !s.sm_symm && s.P.br == 1 && s.P.bc == 1 && h.coarse_n <= 512 && h.coarse_ld == h.coarse_n;
+    if (!ok) break;
+    --T;
+  }
+  return T > L - 2 ? -1 : T;              // (-1: no smoothed level qualifies)
+}
+
+// plain CSR copies of the tail levels' matrices (and the colour-major row lists of their Gauss-Seidel sweeps)
+static void upload_tail_level(const amgx_level_desc& s, DevLevel& V) {
+  const int64_t nnz = s.A.rowptr[s.A.n_rows];
+  V.tA.upload(s.A); V.tP.upload(s.P); V.tPT.upload(s.PT);
+  if (s.sm_type == AMGX_SM_JACOBI) {
+    std::vector<double> sv((size_t)nnz);
+    for (int64_t k = 0; k < nnz; ++k) sv[k] = s.A.val[k] * (s.omega * s.dinv[s.A.col[k]]);
+    V.tApre.upload(s.A, sv.data());
+  } else {
+    std::vector<int32_t> cptr(s.n_colors + 1, 0), rl;
+    for (int64_t i = 0; i < s.A.n_rows; ++i) if (s.color[i] >= 0) cptr[s.color[i] + 1]++;
+    for (int c = 0; c < s.n_colors; ++c) cptr[c + 1] += cptr[c];
+    rl.resize(cptr[s.n_colors]);
+    std::vector<int32_t> pos(cptr.begin(), cptr.end() - 1);
+    for (int64_t i = 0; i < s.A.n_rows; ++i) if (s.color[i] >= 0) rl[pos[s.color[i]]++] = (int32_t)i;
+    V.t_rowlist.upload(rl); V.t_cptr.upload(cptr);
+    V.t_rowcolor.upload(s.color, (size_t)s.A.n_rows);
+  }
+}
+
+// ---- single-workgroup coarse tail: the program of tail_kernel for the levels >= T ----------
+static void build_tail_program(Handle& h, const amgx_hierarchy_desc* d, const amgx_level_desc* levels) {
+  const int L = d->n_levels;
+  const int T = tail_first_level(h, d, levels);
+  if (T <= 0) return;
+  std::vector<TailOp> prog;
+  const EpArgs none{nullptr, nullptr, nullptr, 0.0, nullptr, 0};
+  auto spmv = [&](int ep, const DevCsr& M, int n, const double* x, double* y, EpArgs a) {
+    prog.push_back(TailOp{T_SPMV, ep, n, M.rowptr.p, M.col.p, M.val.p, x, y, a, nullptr, nullptr, 0, 0, 0, nullptr});
+  };
+  auto gs = [&](DevLevel& V, int nc, int backward, int lds_ok) {
+    prog.push_back(TailOp{T_GS, 0, (int)V.n, V.tA.rowptr.p, V.tA.col.p, V.tA.val.p, nullptr, V.x.p,
+                          EpArgs{V.rhs.p, nullptr, V.dinv.p, 0.0, nullptr, 0}, V.t_rowlist.p, V.t_cptr.p, nc, backward, lds_ok, V.t_rowcolor.p});
+  };
+  auto gs_lds_ok = [&](int l) {
+    const amgx_matrix& A = levels[l].A;
+    if (A.n_rows > TAIL_BLOCK / TAIL_G || h.knobs.no_tail_lds) return 0;
+    for (int64_t i = 0; i < A.n_rows; ++i) if (A.rowptr[i + 1] - A.rowptr[i] > TAIL_G * TAIL_GS_K) return 0;
+    return 1;
+  };
+  for (int l = T; l + 1 < L; ++l) upload_tail_level(levels[l], h.lev[l]);
+  for (int l = T; l + 1 < L; ++l) {       // down
+    DevLevel& V = h.lev[l];
+    if (V.sm_type == AMGX_SM_JACOBI) {     // r = b - A'b, x = omega*Dinv*b
+      spmv(EP_PRE, V.tApre, (int)V.n, V.rhs.p, V.res.p, EpArgs{V.rhs.p, nullptr, V.dinv.p, V.omega, V.x.p, 0});
+    } else {                               // x = 0; forward sweep; r = b - A x
+      prog.push_back(TailOp{T_ZERO, 0, (int)V.n, nullptr, nullptr, nullptr, nullptr, V.x.p, none, nullptr, nullptr, 0, 0, 0, nullptr});
+      gs(V, levels[l].n_colors, 0, gs_lds_ok(l));
+      spmv(EP_RES, V.tA, (int)V.n, V.x.p, V.res.p, EpArgs{V.rhs.p, nullptr, nullptr, 0.0, nullptr, 0});
+    }
+    spmv(EP_MULT, V.tPT, (int)h.lev[l + 1].n, V.res.p, h.lev[l + 1].rhs.p, none);   // b_{l+1} = P^T r
+  }
+  prog.push_back(TailOp{T_DENSE, 0, (int)h.coarse_n, nullptr, nullptr, h.coarse_inv.p, h.lev[L - 1].rhs.p, h.lev[L - 1].x.p,
+                        none, nullptr, nullptr, 0, 0, 0, nullptr});
+  for (int l = L - 2; l >= T; --l) {      // up
+    DevLevel& V = h.lev[l];
+    if (V.sm_type == AMGX_SM_JACOBI) {     // tmp = x + P x_{l+1} ; x = tmp + omega*Dinv*(b - A tmp)
+      spmv(EP_AXPY, V.tP, (int)V.n, h.lev[l + 1].x.p, V.tmp.p, EpArgs{nullptr, V.x.p, nullptr, 1.0, nullptr, 0});
+      spmv(EP_JAC, V.tA, (int)V.n, V.tmp.p, V.x.p, EpArgs{V.rhs.p, V.tmp.p, V.dinv.p, V.omega, nullptr, 0});
+    } else {                               // x += P x_{l+1} ; backward sweep
+      spmv(EP_AXPY, V.tP, (int)V.n, h.lev[l + 1].x.p, V.x.p, EpArgs{nullptr, V.x.p, nullptr, 1.0, nullptr, 0});
+      gs(V, levels[l].n_colors, 1, gs_lds_ok(l));
+    }
+  }
+  h.tail_prog.upload(prog);
+  h.tail_ops = (int)prog.size();
+  h.tail_level = T;
+}
+
+// ---- collapsed coarse levels (see dense_op_gemv_kernel) -----------------------------------------------------------
+// Picks the first level l_c >= 1 from which the sub-cycle is cheaper as one dense GEMV than as its dependent launches,
+// forms B column by column with the handle's own kernels (so B is exactly the operator the separate launches apply,
+// whatever the smoother form) and stores it row-major.  AMGX_NO_DENSE_TAIL=1 disables, AMGX_DENSE_MAX=<n> caps n.
+// first_level: 1 for a handle whose level 0 carries the caller's vectors; 0 for the replicated tail of a rank-partitioned
+// hierarchy, where the whole handle may become one GEMV on the gathered vector
+static void build_dense_tail(Handle& h, const amgx_hierarchy_desc* d, const amgx_level_desc* levels, int first_level = 1) {
+  const int L = d->n_levels;
+  if (d->cycle != AMGX_CYCLE_V || L < 2 + first_level || h.knobs.no_dense_tail) return;
+  const int64_t cap = h.knobs.dense_max;
+  for (int l = 0; l < L; ++l) if (h.lev[l].ncols != h.lev[l].n) return;       // rank-partitioned levels are driven stage by stage
+  // dependent launches one cycle spends on level m (both directions), ~5 us each
+  auto launches = [&](int m) -> double {
+    const DevLevel& V = h.lev[m];
+    const int k = std::max(1, V.sm_steps) * (V.sm_symm ? 2 : 1);
+    if (V.sm_type == AMGX_SM_JACOBI) return h.folded(V) ? 3.0 : 2.0 + 3.0 * k;
+    if (V.sm_type == AMGX_SM_CHEBY) return 3.0 + 2.0 * k * (V.cheb_degree + 1);
+    if (V.sm_type == AMGX_SM_BGS) return 3.0 + 2.0 * k * std::max(1, V.bgs.n_colors);
+    if (V.gsb.on() || V.bgsb.on()) return 2.0 + 3.0 * k;
+    return 3.0 + 2.0 * k * std::max(1, V.gs.n_colors);
+  };
+  int lc = -1;
+  double est = 5.0;                               // the coarse solve
+  std::vector<double> est_from(L, 0.0);
+  for (int m = L - 2; m >= first_level; --m) { est += 5.0 * launches(m); est_from[m] = est; }
+  for (int m = first_level; m <= L - 2; ++m) {
+    const int64_t N = h.lev[m].len();
+    if (N < 1 || N > cap) continue;
+    const double dense_us = 4.0 + 8.0 * (double)N * (double)N / 4.0e6;      // ~4 TB/s on a few hundred workgroups
+    if (dense_us < 0.8 * est_from[m]) { lc = m; break; }
+  }
+  if (lc < first_level) return;
+  const int N = (int)h.lev[lc].len();
+  const int ld = (N + 1) & ~1;
+  DevBuf<double> Bt;
+  Bt.alloc((size_t)N * ld);
+  h.dense_op.alloc((size_t)N * ld);
+  HIPCHK(hipMemsetAsync(Bt.p, 0, (size_t)N * ld * sizeof(double), h.stream));
+  HIPCHK(hipMemsetAsync(h.dense_op.p, 0, (size_t)N * ld * sizeof(double), h.stream));
+  const int saved_tail = h.tail_level;
+  h.tail_level = -1;                              // the sub-cycle runs as separate launches from level lc
+  DevLevel& V = h.lev[lc];
+  try {
+    for (int j = 0; j < N; ++j) {
+      hipLaunchKernelGGL(dense_unit_kernel, dim3(Handle::grid_for(N)), dim3(BLOCK), 0, h.stream, (int64_t)N, (int64_t)j, V.rhs.p);
+      h.cycle_v(V.x.p, V.rhs.p, lc);                // (dense_level is still -1: separate launches)
+      HIPCHK(hipMemcpyAsync(Bt.p + (size_t)j * ld, V.x.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, h.stream));
+      if ((j & 255) == 255) HIPCHK(hipStreamSynchronize(h.stream));          // bound the depth of the launch queue
+    }
+    const int tb = (N + 15) / 16;
+    hipLaunchKernelGGL(dense_transpose_kernel, dim3(tb, tb), dim3(BLOCK), 0, h.stream, N, ld, Bt.p, h.dense_op.p);
+    HIPCHK(hipGetLastError());
+    // leave the work vectors of the collapsed levels as create() made them
+    for (int m = lc; m < L; ++m) {
+      const size_t len = (size_t)std::max<int64_t>(1, h.lev[m].ext_len());
+      for (double* v : {h.lev[m].x.p, h.lev[m].rhs.p, h.lev[m].res.p, h.lev[m].tmp.p}) HIPCHK(hipMemsetAsync(v, 0, len * sizeof(double), h.stream));
+    }
+    HIPCHK(hipStreamSynchronize(h.stream));
+  } catch (...) { h.tail_level = saved_tail; throw; }
+  h.tail_level = saved_tail;
+  h.dense_level = lc;
+  h.dense_n = N;
+  h.dense_ld = ld;
+}
+
+// Chebyshev levels without an interval from the caller: lmax = 1.1 x a 30-step power-iteration estimate (defined next to the
+// deterministic reductions it uses, at the end of amgx.hip)
+static void cheb_estimate(Handle& h);
+
+// K: the switches as the C-ABI entry point read them (Knobs::from_env, on the calling thread)
+// dense_first: first level that may be collapsed into the dense operator (see build_dense_tail); < 0: never
+static Handle* create(const amgx_hierarchy_desc* d, const Knobs& K, int dense_first = 1) {
+  if (!d || d->n_levels < 1 || !d->levels) throw Err("amgx_create: empty hierarchy descriptor");
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev == 0) throw Err("amgx_create: no HIP device available (the apply path has no CPU fallback)");
+  if (d->device < 0 || d->device >= ndev) throw Err("amgx_create: device ordinal out of range");
+  HIPCHK(hipSetDevice(d->device));
+  auto h = std::make_unique<Handle>();
+  h->knobs = K;
+  h->device = d->device;
+  h->cycle = d->cycle;
+  h->clev = d->clev;
+  h->use_graph = d->use_graph != 0;
+  h->ep_nt = (K.no_ep_nt ? 0 : EPF_NT) | (K.no_ep_hoist ? 0 : EPF_HOIST);   // A/B: -0.4 % cycle time (profiles/r01/restrict_fused.txt)
+  if (d->cycle < 0 || d->cycle > 2) throw Err("amgx_create: unknown cycle");
+  HIPCHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+  h->stream = h->own_stream;
+  h->lev.resize(d->n_levels);
+  std::vector<amgx_level_desc> pl(d->levels, d->levels + d->n_levels);
+  std::vector<LevelPerm> pstore(d->n_levels);
+  permute_gs_levels(K, d, pl, pstore);
+  SetupClock clk(K);
+  clk.lap("renumbering of Gauss-Seidel levels");
+  h->perm.resize(d->n_levels);
+  for (int l = 0; l < d->n_levels; ++l) if (!pstore[l].perm.empty()) h->perm[l].upload(pstore[l].perm);
+  const amgx_level_desc* levels = pl.data();
+  for (int l = 0; l < d->n_levels; ++l) {
+    LevelBuild B{h->knobs, clk, levels[l], l + 1 < d->n_levels ? &levels[l + 1] : nullptr, h->lev[l], l, d->cycle, dense_first};
+    check_level(B);
+    SetupTasks tasks(d->device, K);       // (after B: see LevelBuild)
+    upload_level_matrix(B, tasks);
+    if (!B.last()) {
+      upload_transfers(B, tasks);
+      build_smoother_data(B, tasks);
+      if (B.s.sm_type == AMGX_SM_JACOBI && B.s.A.br == 1 && B.s.sm_steps <= 1 && !B.s.sm_symm) build_jacobi_down(B, tasks);
+      build_folded_prolongation(B, tasks);
+      tasks.wait();
+      cheb_fused_restrict(B);
+      clk.lap("level images (A, P, P^T, smoother data, A', Q: concurrent host tasks)", l);
+    } else if (B.s.dinv) {
+      tasks.wait();
+      build_coarsest_smoother_data(B);
+    }
+    tasks.wait();
+    set_xcd_modes(B);
+    alloc_level_vectors(B);
+  }
+  cheb_estimate(*h);
+  clk.lap("Chebyshev intervals (power iteration)");
+  if (d->clev == AMGX_CLEV_INV) build_coarse_inverse(*h, d, levels[d->n_levels - 1]);
+  build_tail_program(*h, d, levels);
+  HIPCHK(hipDeviceSynchronize());
+  clk.lap("coarse inverse, tail program");
+  if (dense_first >= 0) build_dense_tail(*h, d, levels, dense_first);
+  clk.lap("collapsed coarse levels (dense operator)");
+  return h.release();
+}
+
+}  // namespace amgx

@@ -387,20 +387,18 @@ __global__ __launch_bounds__(BLOCK) void db_fill_i32_kernel(int64_t n, int32_t v
 // ---------------------------------------------------------------------------------------------------
 // host side
 
-static bool dev_images_wanted(const amgx_matrix& A) {
-  if (std::getenv("AMGX_HOST_IMAGES")) return false;
+static bool dev_images_wanted(const Knobs& K, const amgx_matrix& A) {
+  if (K.host_images) return false;
   if (A.br != 1 || A.bc != 1 || A.n_rows <= 0) return false;
   const int64_t nnz = A.rowptr[A.n_rows];
-  if (nnz <= 0 || nnz >= (int64_t)2147483647) return false;
-  int64_t min_rows = 65536;
-  if (const char* e = std::getenv("AMGX_DEV_IMAGES_MIN_ROWS")) min_rows = std::atoll(e);
-  if (A.n_rows < min_rows) return false;
+  if (nnz <= 0 || nnz >= I32_MAX) return false;
+  if (A.n_rows < K.dev_images_min_rows) return false;
   // upload_matrix's choice of lanes per row: the device builder is the one-thread-per-row form
   const double avg = (double)nnz / (double)A.n_rows;
   int G = 1;
   while (G < 16 && A.n_rows * G < ((int64_t)1 << 20) && avg > 3.0 * G) G <<= 1;
-  G = std::max(G, sell_long_row_lanes(avg));
-  if (const char* e = std::getenv("AMGX_SELL_MAX_LANES")) G = std::max(1, std::min(G, std::atoi(e)));
+  G = std::max(G, sell_long_row_lanes(K, avg));
+  if (K.sell_max_lanes) G = std::min(G, K.sell_max_lanes);
   return G == 1;
 }
 
@@ -498,14 +496,14 @@ static void dev_build_sell(const DevCsrSrc& A, const int32_t* d_rows, int64_t m,
 // upload_matrix for a scalar matrix already on the device (same decisions, same image).  Returns false, D untouched, where the
 // host builder would not produce a one-thread-per-row SELL image (the caller then runs the host builder).
 //   d_colscale / omega: image of A * diag(omega * colscale);  d_wdiag: the diagonal slot carries omega * wdiag[row] (needs info.plain)
-static bool dev_upload_matrix(const DevCsrSrc& A, DevMatrix& D, bool rowrel_ok, double max_pad, int win, const DbDiagInfo* info,
+static bool dev_upload_matrix(const Knobs& K, const DevCsrSrc& A, DevMatrix& D, bool rowrel_ok, double max_pad, int win, const DbDiagInfo* info,
                               const double* d_colscale = nullptr, double omega = 0.0, const double* d_wdiag = nullptr) {
   const int64_t m = A.n_rows;
   if (m <= 0 || A.nnz <= 0) return false;
   DevBuf<int64_t> sp;
   int64_t stored = dev_slice_offsets(A, nullptr, m, sp);
   if (!((double)stored <= max_pad * (double)A.nnz)) return false;                       // host: sellG = 0 -> CSR kernels
-  const bool windowed = win > 0 && (double)stored > 1.10 * (double)A.nnz && !std::getenv("AMGX_NO_SELL_WINDOW");
+  const bool windowed = win > 0 && (double)stored > 1.10 * (double)A.nnz && !K.no_sell_window;
   DevBuf<int32_t> rows;
   DevBuf<uint16_t> rowloc;
   if (windowed) {
@@ -517,7 +515,7 @@ static bool dev_upload_matrix(const DevCsrSrc& A, DevMatrix& D, bool rowrel_ok, 
   }
   const int64_t ns = (m + WAVE - 1) / WAVE;
   const bool rowrel = !windowed && rowrel_ok && A.n_cols >= A.n_rows;
-  const bool diag_first = !windowed && rowrel_ok && A.n_rows <= A.n_cols && !std::getenv("AMGX_NO_DIAG_FIRST") && info && info->all_diag;
+  const bool diag_first = !windowed && rowrel_ok && A.n_rows <= A.n_cols && !K.no_diag_first && info && info->all_diag;
   const bool wdiag = d_wdiag && diag_first;
   DevMatrix::Sell& S = D.sell;
   int64_t bytes = 0;
@@ -554,7 +552,7 @@ static bool dev_fold_prolongation(const DevCsrSrc& A, const DevCsrSrc& P, const 
   int64_t nnz = 0;
   HIPCHK(hipMemcpy(&ho, over.p, sizeof(int), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(&nnz, Q.rowptr.p + n, sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (ho || nnz >= (int64_t)2147483647) return false;
+  if (ho || nnz >= I32_MAX) return false;
   Q.n_rows = n; Q.n_cols = P.n_cols; Q.nnz = nnz;
   Q.col.alloc((size_t)std::max<int64_t>(1, nnz));
   Q.val.alloc((size_t)std::max<int64_t>(1, nnz));
@@ -750,14 +748,12 @@ struct DevBcsrSrc {                      // a square-block CSR matrix on the dev
 };
 struct DbBgsbMaps { const int32_t* blk_of = nullptr; const int32_t* lpos = nullptr; const int32_t* color = nullptr; const double* fac = nullptr; const int32_t* bcolor = nullptr; };
 
-static bool dev_bsell_wanted(const amgx_matrix& A) {
-  if (std::getenv("AMGX_HOST_IMAGES") || std::getenv("AMGX_NO_BSELL")) return false;
+static bool dev_bsell_wanted(const Knobs& K, const amgx_matrix& A) {
+  if (K.host_images || K.no_bsell) return false;
   if (A.br != A.bc || (A.br != 2 && A.br != 3 && A.br != 6) || A.n_rows <= 0) return false;
   const int64_t nnz = A.rowptr[A.n_rows];
-  if (nnz <= 0 || nnz >= (int64_t)2147483647) return false;
-  int64_t min_rows = 65536;
-  if (const char* e = std::getenv("AMGX_DEV_IMAGES_MIN_ROWS")) min_rows = std::atoll(e);
-  return A.n_rows * A.br >= min_rows;
+  if (nnz <= 0 || nnz >= I32_MAX) return false;
+  return A.n_rows * A.br >= K.dev_images_min_rows;
 }
 
 // build_bsell / build_bsell_sel on the device.  d_rows [m]: list of block rows, m a multiple of 64 / bs (null: natural order, all
@@ -871,6 +867,111 @@ static void verify_same_lw(const DevMatrix& a, const DevBuf<int32_t>& ap, const 
   const size_t used = pa.empty() ? 0 : (size_t)pa.back();
   if (ac.n < used || bc.n < used) throw Err(std::string("AMGX_VERIFY_IMAGES: ") + what + ": column lists are too short");
   if (db_download(ac, used) != db_download(bc, used)) throw Err(std::string("AMGX_VERIFY_IMAGES: ") + what + ": column lists differ");
+}
+
+// ---- AMGX_VERIFY_IMAGES: the cross-checks of the construction steps (build_level.hpp), one call from the step that built the
+// image.  Each forms the host builder's image of the same input and compares the two bit by bit.
+static void build_gsb(const Knobs& K, const amgx_level_desc& d, DevLevel& L, const amgx_matrix* P, const DevCsrSrc* csr);     // (amgx.hip)
+static void build_bgsb(const Knobs& K, const amgx_level_desc& d, DevLevel& L, const DevBcsrSrc* csr);
+static void fold_prolongation(const amgx_matrix& A, const amgx_matrix& P, const double* dinv, double omega, HostCsr& Q);
+
+// the level matrix: device BSELL image / device SELL image / declined by the device builder
+static void verify_level_bsell(const Knobs& K, const amgx_matrix& A, const DevMatrix& D) {
+  DevMatrix H;
+  upload_matrix(K, A, H, "A", true, true, false);
+  if (H.lanes != D.lanes || H.nnz != D.nnz) throw Err("AMGX_VERIFY_IMAGES: A: descriptors differ");
+  verify_same_bsell(D, H, "A");
+}
+static void verify_level_image(const Knobs& K, const amgx_matrix& A, const DevMatrix& D) {
+  DevMatrix H;
+  upload_matrix(K, A, H, "A", true, true, false);
+  verify_same_image(D, H, "A");
+}
+static void verify_level_declined(const Knobs& K, const amgx_matrix& A) {
+  DevMatrix H;
+  upload_matrix(K, A, H, "A", true, true, false);
+  if (H.fmt == FMT_SELL && H.lanes == 1) throw Err("AMGX_VERIFY_IMAGES: the device builder declined A where the host builder forms a SELL image");
+}
+
+// block-hybrid Gauss-Seidel data of a square-block level
+static void verify_bgsb(const Knobs& K, const amgx_level_desc& s, const DevLevel& L) {
+  DevLevel H;
+  H.n = L.n; H.ncols = L.ncols; H.bs = L.bs;
+  build_bgsb(K, s, H, nullptr);
+  const DevBGSB &x = L.bgsb, &y = H.bgsb;
+  if (x.BB != y.BB || x.n_blocks != y.n_blocks || x.n_colors != y.n_colors || x.has_split != y.has_split) throw Err("AMGX_VERIFY_IMAGES: block-hybrid Gauss-Seidel (blocks): the descriptors differ");
+  verify_same_bsell(x.off, y.off, "block-hybrid Gauss-Seidel: off");
+  verify_same_bsell(x.in, y.in, "block-hybrid Gauss-Seidel: in");
+  verify_same_bsell(x.upin, y.upin, "block-hybrid Gauss-Seidel: upin");
+  if (x.has_split) verify_same_bsell(x.rest, y.rest, "block-hybrid Gauss-Seidel: rest");
+  if (x.bc != y.bc || x.n_bcolors != y.n_bcolors) throw Err("AMGX_VERIFY_IMAGES: block-coloured Gauss-Seidel: the descriptors differ");
+  if (x.bc && x.has_split) verify_same_bsell(x.offlo, y.offlo, "block-coloured Gauss-Seidel: offlo");
+}
+
+// ... of a scalar level
+static void verify_gsb(const Knobs& K, const amgx_level_desc& s, const DevLevel& L) {
+  DevLevel H;
+  H.n = L.n; H.ncols = L.ncols; H.bs = L.bs;
+  build_gsb(K, s, H, &s.P, nullptr);
+  const DevGSB &x = L.gsb, &y = H.gsb;
+  if (x.B != y.B || x.G != y.G || x.TH != y.TH || x.n_blocks != y.n_blocks || x.n_colors != y.n_colors || x.lowin_maxw != y.lowin_maxw || x.full_maxw != y.full_maxw ||
+      x.has_split != y.has_split) throw Err("AMGX_VERIFY_IMAGES: block-hybrid Gauss-Seidel: the descriptors differ");
+  const size_t nsl = (size_t)((int64_t)x.n_blocks * x.B / (WAVE / x.G));
+  verify_same_sell(x.full, y.full, nsl, 0, "block-hybrid Gauss-Seidel: A");
+  if (x.has_split) {
+    verify_same_sell(x.lowin, y.lowin, nsl, 0, "block-hybrid Gauss-Seidel: lower part");
+    verify_same_image(x.rest, y.rest, "block-hybrid Gauss-Seidel: rest");
+    const auto cx = db_download(x.cvec, (size_t)L.n), cy = db_download(y.cvec, (size_t)L.n);
+    if (std::memcmp(cx.data(), cy.data(), (size_t)L.n * sizeof(double)) != 0) throw Err("AMGX_VERIFY_IMAGES: block-hybrid Gauss-Seidel: cvec differs");
+  }
+}
+
+// local-window image of A' with g lanes per row; host_lw(g, image, offsets, columns) is the caller's host builder
+template <class HostLw>
+static void verify_apre_lw(const DevLevel& L, int g, HostLw&& host_lw) {
+  DevMatrix H; DevBuf<int32_t> hp, hc;
+  if (!host_lw(g, H, hp, hc)) throw Err("AMGX_VERIFY_IMAGES: A' (local window): the host builder declines what the device builder forms");
+  verify_same_lw(L.ApreLW, L.lw_cptr, L.lw_ccol, H, hp, hc, "A' (local window)");
+}
+
+// symmetric diagonal image against the host's (dia::upper_image)
+static void verify_dia(const DevDia& D, const std::vector<double>& hv) {
+  if (std::memcmp(db_download(D.val, hv.size()).data(), hv.data(), hv.size() * sizeof(double)) != 0)
+    throw Err("AMGX_VERIFY_IMAGES: the diagonal image differs");
+}
+
+// A' (As: the host's column-scaled copy of A): both builders run; L.Apre gets the device image where the device builder forms one,
+// else the host image -- unless the host image is one the device builder should have formed
+static void verify_build_apre(const Knobs& K, const amgx_matrix& As, const DevCsrSrc& csrA, const DbDiagInfo& diagA, double omega, int apre_win,
+                              const double* wdiag_host, bool dev_wdiag, DevLevel& L) {
+  DevMatrix H;
+  upload_matrix(K, As, H, "A (pre-smoothing image)", true, true, false, 1.35, apre_win, wdiag_host);
+  if (dev_upload_matrix(K, csrA, L.Apre, true, 1.35, apre_win, &diagA, L.dinv.p, omega, dev_wdiag ? L.dinv.p : nullptr)) verify_same_image(L.Apre, H, "A'");
+  else if (H.fmt == FMT_SELL && H.lanes == 1) throw Err("AMGX_VERIFY_IMAGES: the device builder declined A' where the host builder forms a SELL image");
+  else L.Apre = std::move(H);
+}
+
+// local-window image of the device-built Q (n rows)
+static void verify_qlw(const Knobs& K, const DevCsrSrc& csrQ, int64_t n, const DevLevel& L) {
+  std::vector<int64_t> rp = db_download(csrQ.rowptr, (size_t)n + 1);
+  std::vector<int32_t> cc = db_download(csrQ.col, (size_t)std::max<int64_t>(1, csrQ.nnz));
+  std::vector<double> vv = db_download(csrQ.val, (size_t)std::max<int64_t>(1, csrQ.nnz));
+  DevMatrix H; DevBuf<int32_t> hp, hc;
+  if (!build_sell_lw_windowed(K, n, csrQ.n_cols, rp.data(), cc.data(), vv.data(), H, hp, hc))
+    throw Err("AMGX_VERIFY_IMAGES: Q (local window): the host builder declines what the device builder forms");
+  verify_same_lw(L.QLW, L.qlw_cptr, L.qlw_ccol, H, hp, hc, "Q (local window)");
+}
+
+// the device-built Q = (I - omega Dinv A) P against the host product
+static void verify_q(const Knobs& K, const amgx_level_desc& s, const DevCsrSrc& csrQ, double qpad, const DevMatrix& Q) {
+  HostCsr q;
+  fold_prolongation(s.A, s.P, s.dinv, s.omega, q);
+  if ((int64_t)q.rowptr[s.A.n_rows] != csrQ.nnz) throw Err("AMGX_VERIFY_IMAGES: Q: different numbers of entries");
+  amgx_matrix Qm = s.P;
+  Qm.rowptr = q.rowptr.data(); Qm.col = q.col.data(); Qm.val = q.val.data();
+  DevMatrix H;
+  upload_matrix(K, Qm, H, "Q (folded post-smoothing prolongation)", true, false, false, qpad, SELL_WIN);
+  verify_same_image(Q, H, "Q");
 }
 
 }  // namespace amgx

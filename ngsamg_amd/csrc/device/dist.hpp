@@ -98,7 +98,7 @@ struct HaloTable {                       // one level of one rank
     if (send_ptr[0] != 0 || recv_ptr[0] != 0) throw Err("halo table: pointers must start at 0");
     if (recv_ptr.back() != n_ghost) throw Err("halo table: the receive segments must cover the ghost block exactly");
     const int64_t ns = n_send();
-    if (ns >= (int64_t)2147483647) throw Err("halo table: too many send entries");
+    if (ns >= I32_MAX) throw Err("halo table: too many send entries");
     if (ns > 0 && !d.send_idx) throw Err("halo table: send_idx missing");
     for (int64_t i = 0; i < ns; ++i) if (d.send_idx[i] < 0 || d.send_idx[i] >= n) throw Err("halo table: send index out of the owned range");
     // the boundary-row contract behind the overlap: a row that READS a ghost must not be interior -- a property of the matrix,
@@ -172,7 +172,7 @@ struct Comm {
     if (comm_stream) (void)hipStreamDestroy(comm_stream);
     if (own_compute) (void)hipStreamDestroy(own_compute);
   }
-  void init_streams() {
+  void init_streams(const Knobs& K) {
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamCreateWithFlags(&own_compute, hipStreamNonBlocking));
     compute = own_compute;
@@ -187,8 +187,8 @@ struct Comm {
     }
     int can = 0;
     if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device) != hipSuccess) can = 0;
-    use_values = can && !std::getenv("AMGX_DIST_EVENTS");
-    if (const char* e = std::getenv("AMGX_DIST_GRAPH")) graph_ok = std::atoi(e) != 0;
+    use_values = can && !K.dist_events;
+    graph_ok = K.dist_graph;
     if (use_values) {
       HIPCHK(hipMalloc((void**)&flags, 2 * NEV * 64));
       HIPCHK(hipMemset(flags, 0, 2 * NEV * 64));
@@ -357,7 +357,7 @@ static void dist_check_interior(const amgx_matrix& A, int64_t n_int) {
       if (A.col[e] >= A.n_rows) throw Err("rank-partitioned level: a row below n_interior has a ghost column");
 }
 
-static Dist* dist_create(Comm* c, const amgx_dist_desc* d) {
+static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
   if (!c || !d) throw Err("amgx_dist_create: null argument");
   if (c->kind == AMGX_COMM_RCCL && !c->members.empty()) throw Err("amgx_dist_create: an RCCL communicator carries one rank per process");
   if (c->kind == AMGX_COMM_LOCAL && (int)c->members.size() >= c->nranks) throw Err("amgx_dist_create: all local ranks exist already");
@@ -380,14 +380,14 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d) {
   if (D->cycle != AMGX_CYCLE_V && D->cycle != AMGX_CYCLE_W) throw Err("amgx_dist_create: rank-partitioned hierarchies run V and W cycles");
   if (d->tail.cycle != d->top.cycle) throw Err("amgx_dist_create: the replicated tail must run the same cycle as the rank-partitioned levels");
   if (D->cycle == AMGX_CYCLE_W) D->generic = true;
-  D->overlap = !std::getenv("AMGX_DIST_NO_OVERLAP");
+  D->overlap = !K.dist_no_overlap;
   amgx_hierarchy_desc td = d->top;
   td.device = c->device; td.use_graph = 0; td.clev = AMGX_CLEV_NONE; td.coarse_n = 0; td.coarse_inv = nullptr;
   td.cycle = AMGX_CYCLE_V;                 // (the top handle is driven stage by stage: its own cycle type plays no role)
-  D->top.reset(create(&td, -1));           // (driven stage by stage: no collapsed coarse levels)
+  D->top.reset(create(&td, K, -1));           // (driven stage by stage: no collapsed coarse levels)
   amgx_hierarchy_desc ld = d->tail;
   ld.device = c->device;
-  D->tail.reset(create(&ld, 0));           // the replicated tail may collapse completely: x_glob = B b_glob in one GEMV
+  D->tail.reset(create(&ld, K, 0));           // the replicated tail may collapse completely: x_glob = B b_glob in one GEMV
   // both handles work on the communicator's compute stream
   for (Handle* h : {D->top.get(), D->tail.get()}) { HIPCHK(hipStreamSynchronize(h->stream)); h->stream = c->compute; }
   const int k = D->k;
@@ -464,9 +464,9 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d) {
   // AMGX_DIST_FORCE_ALLGATHER (tests, one-GPU rehearsals): world size 1 goes through ncclAllGather too instead of the copy
   // shortcut; "pad" additionally pretends the pieces differ in size (every slot is 5 rows longer than the longest piece), so
   // that the padded all-gather and the compaction kernel run
-  if (const char* e = std::getenv("AMGX_DIST_FORCE_ALLGATHER")) {
+  if (K.dist_force_allgather) {
     D->force_allgather = true;
-    if (std::string(e) == "pad") D->mcount += 5;
+    if (K.dist_force_allgather == 2) D->mcount += 5;
   }
   const int bsk = D->top->lev[k].bs;
   if (D->counts[self] * bsk != D->n(k)) throw Err("amgx_dist_create: counts[rank] does not match level k");
@@ -497,9 +497,6 @@ struct DistCycle {
   std::vector<Dist*>& M;
   std::vector<double*> x;                // level-0 solution vectors (device)
   using Span = Handle::Span;
-  // replicated tail: direct launches by default -- a graph launch between directly launched kernels costs ~10 us of
-  // stream time (profiles/r02/trace_dist_world1.txt), the tail's handful of kernels do not pay that back
-  bool tail_graph = std::getenv("AMGX_DIST_TAIL_GRAPH") != nullptr;
 
   std::vector<Comm::Item> items(int l, int which) {      // which: 0 bext, 1 xext, 2 text
     std::vector<Comm::Item> it;
@@ -532,7 +529,9 @@ struct DistCycle {
 
   void tail_and_pick() {
     for (Dist* d : M) {
-      d->tail->run_cycle(d->xglob.p, d->bglob.p, tail_graph && !c.capturing);
+      // replicated tail: direct launches by default -- a graph launch between directly launched kernels costs ~10 us of
+      // stream time (profiles/r02/trace_dist_world1.txt), the tail's handful of kernels do not pay that back
+      d->tail->run_cycle(d->xglob.p, d->bglob.p, d->tail->knobs.dist_tail_graph && !c.capturing);
       const int64_t len = d->next(d->k);
       if (len) hipLaunchKernelGGL(index_gather_kernel, dim3(Handle::grid_for(len)), dim3(BLOCK), 0, c.compute, len, d->kmap.p, d->xglob.p, d->xk_ext.p);
       HIPCHK(hipGetLastError());
@@ -1248,7 +1247,7 @@ int amgx_comm_create(int kind, int n_ranks, int rank, const char* id128, int dev
     auto c = std::make_unique<amgx::Comm>();
     c->kind = kind; c->nranks = n_ranks; c->device = device;
     c->rank = kind == AMGX_COMM_RCCL ? rank : 0;
-    c->init_streams();
+    c->init_streams(amgx::Knobs::from_env());
     if (kind == AMGX_COMM_RCCL) {
       if (rank < 0 || rank >= n_ranks || !id128) throw amgx::Err("amgx_comm_create: RCCL needs rank in [0, n_ranks) and the unique id of rank 0");
       ncclUniqueId id;
@@ -1312,7 +1311,7 @@ const char* amgx_comm_graph_note(amgx_comm c) { return (c && c->c) ? c->c->graph
 int amgx_dist_create(amgx_comm cc, const amgx_dist_desc* desc, amgx_dist* out) {
   return cguard(cc, [&](amgx::Comm& c) {
     if (!out) throw amgx::Err("amgx_dist_create: null output");
-    amgx::Dist* d = amgx::dist_create(&c, desc);
+    amgx::Dist* d = amgx::dist_create(&c, desc, amgx::Knobs::from_env());
     c.members.push_back(d);
     *out = new amgx_dist_t{d};
     c.dist_wrappers.push_back(*out);

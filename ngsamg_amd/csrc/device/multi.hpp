@@ -374,17 +374,10 @@ struct MultiState {
   DevBuf<double> kr_sc, kr_partial;
   DevBuf<int32_t> kr_active;
   using Key = std::tuple<const double*, double*, int, int, int64_t, int64_t>;   // b, x, k, layout, ldb, ldx
-  std::map<Key, hipGraphExec_t> graphs;
-  std::vector<Key> graph_age;
-  ~MultiState() { drop(); }
-  void drop() {
-    for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
-    graphs.clear();
-    graph_age.clear();
-  }
+  GraphCache<Key> graphs;
 };
 
-void multi_drop_graphs(MultiState* s) { s->drop(); }       // amgx_set_stream: captures of the old stream go
+void multi_drop_graphs(MultiState* s) { s->graphs.drop(); }       // amgx_set_stream: captures of the old stream go
 void multi_free(MultiState* s) { delete s; }
 
 struct Multi {
@@ -598,32 +591,15 @@ struct Multi {
     // only the fused path is captured as a whole; the column loop replays the single-vector graphs of run_cycle
     if (st.fused != 1 || !(h.use_graph && graph_ok) || h.stream == nullptr) { apply_body(k, B, brs, bcs, X, xrs, xcs, graph_ok, false); return; }
     const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx};
-    auto it = st.graphs.find(key);
-    if (it == st.graphs.end()) {
+    if (!st.graphs.has(key)) {
       int32_t wd[MULTI_MAX];
       const int ng = multi_groups(k, true, wd);
       for (int g = 0; g < ng; ++g) {                           // allocations happen before the capture
         if (wd[g] > 1) { MultiWork& W = work(wd[g]); fit(W.in, h.lev[0].len() * wd[g]); fit(W.out, h.lev[0].len() * wd[g]); }
         else { fit(st.col_in, h.lev[0].len()); fit(st.col_out, h.lev[0].len()); }
       }
-      hipGraph_t g = nullptr;
-      HIPCHK(hipStreamBeginCapture(h.stream, hipStreamCaptureModeThreadLocal));
-      try { apply_body(k, B, brs, bcs, X, xrs, xcs, false, true); }
-      catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(h.stream, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
-      HIPCHK(hipStreamEndCapture(h.stream, &g));
-      hipGraphExec_t ge = nullptr;
-      hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      if (e != hipSuccess) throw Err(std::string("hipGraphInstantiate failed: ") + hipGetErrorString(e));
-      if (st.graphs.size() >= 16 && !st.graph_age.empty()) {
-        auto old = st.graphs.find(st.graph_age.front());
-        st.graph_age.erase(st.graph_age.begin());
-        if (old != st.graphs.end()) { (void)hipGraphExecDestroy(old->second); st.graphs.erase(old); }
-      }
-      it = st.graphs.emplace(key, ge).first;
-      st.graph_age.push_back(key);
     }
-    HIPCHK(hipGraphLaunch(it->second, h.stream));
+    st.graphs.run(key, h.stream, [&] { apply_body(k, B, brs, bcs, X, xrs, xcs, false, true); });
   }
 
   // Y = A_level X on device multi-vectors

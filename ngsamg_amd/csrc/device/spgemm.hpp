@@ -368,7 +368,7 @@ static bool dev_spgemm(const SpCsr& A, const SpCsr& B, SpCsr& C) {
   HIPCHK(hipGetLastError());
   int64_t nnz = 0;
   HIPCHK(hipMemcpy(&nnz, C.rowptr.p + n, sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (nnz >= (int64_t)2147483647) return false;
+  if (nnz >= I32_MAX) return false;
   C.nnz = nnz;
   C.col.alloc((size_t)std::max<int64_t>(1, nnz));
   C.val.alloc((size_t)std::max<int64_t>(1, nnz) * cbs);
