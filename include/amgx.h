@@ -114,7 +114,21 @@ typedef struct amgx_level_desc {
   double cheb_lambda_max;     /*   upper end of the interval (0: 1.1 x a 30-step power-iteration estimate of lambda_max(Dinv A),     */
                               /*   computed by amgx_create on the device; amgx_smoother_info reports it)                             */
   double cheb_ratio;          /*   lmin = lmax / ratio, ratio > 1 (0: 10)                                                            */
+  int32_t mat_prec;           /* AMGX_PREC_*: storage of the values of A that the smoother passes of this level read (0 = fp64, today's  */
+                              /*   behaviour).  AMGX_PREC_F32, levels smoothed with AMGX_SM_CHEBY only (an error on any other smoothed    */
+                              /*   level; ignored on the coarsest of several): amgx_create keeps a second image of A whose values are float, the     */
+                              /*   fp64 image rounded to nearest with every index array shared (+ half of A's value bytes of device      */
+                              /*   memory).  Every product with A that the SMOOTHER and the CYCLE launch reads it: the Chebyshev steps,    */
+                              /*   the residual before the restriction (fused form included) and update_res of amgx_smooth.  All vectors, */
+                              /*   dinv, the transfers and the accumulation stay fp64: the result is the fp64 cycle on the rounded A.      */
+                              /*   amgx_matvec, amgx_residual, amgx_matvec_multi, the level-0 operator of amgx_pcg / amgx_gmres /          */
+                              /*   amgx_pcg_multi and the lambda_max estimate keep the fp64 image: a solve converges to the solution of    */
+                              /*   the TRUE system and amgx_smoother_info is that of the double handle.  Images: A in plain sliced-ELL or  */
+                              /*   block sliced-ELL form; levels in another format (CSR-vector, windowed, block CSR: the small ones) stay  */
+                              /*   fp64 silently -- amgx_matrix_info(which = 7) tells.  A value that rounds to +-inf is an error.          */
+                              /*   Environment of amgx_create: AMGX_NO_MAT_F32=1 ignores every request.                                    */
 } amgx_level_desc;
+enum { AMGX_PREC_F64 = 0, AMGX_PREC_F32 = 1 };                    /* amgx_level_desc.mat_prec */
 
 typedef struct amgx_hierarchy_desc {
   int32_t n_levels;
@@ -211,11 +225,14 @@ int amgx_smoother_info(amgx_handle h, int level, int32_t* sm_type, int32_t* degr
  * stored as (column, w, t): detected block by block at amgx_create, elasticity_energy.hpp:447-490), 6 (which = 3 only) the
  * symmetric diagonal image of A that replaces A' on levels whose A lies on at most 16 diagonals and is symmetric bit for bit
  * (stored_entries = upper diagonals x rows; AMGX_NO_DIA=1 at amgx_create keeps A'); stored_entries counts padding
- * (for the traffic model in DESIGN.md) */
+ * (for the traffic model in DESIGN.md).  which = 7: the single-precision image of A that the smoother passes of a level with
+ * mat_prec = AMGX_PREC_F32 read: fmt 1 or 2 (-1: not built), stored_entries and lanes those of A -- 4-byte values, the indices are
+ * the ones of which = 0.  `which` outside 0 .. 7 is an error. */
 int amgx_matrix_info(amgx_handle h, int level, int which, int32_t* fmt, int64_t* stored_entries, int32_t* lanes_per_row);
 
 /* bytes of matrix data (values, indices, pointers, in the device encoding) that one SpMV with this matrix
- * streams from HBM -- the model value behind "traffic" in DESIGN.md */
+ * streams from HBM -- the model value behind "traffic" in DESIGN.md; which as above (7: 4 bytes per stored value + the shared
+ * indices and pointers of A; 0 when the level has no single-precision image) */
 int amgx_matrix_stream_bytes(amgx_handle h, int level, int which, int64_t* bytes);
 
 /* read-only report of the paths amgx_create chose for one level (changes nothing).  Fills out[0 .. min(n_out, 19)):
@@ -264,7 +281,9 @@ int amgx_level_paths(amgx_handle h, int level, int64_t* out, int n_out);
  *   op = 9: like 8 for the backward block-hybrid Gauss-Seidel sweep of the level (gsb_sweep_kernel, the dominant kernel
  *           of a Gauss-Seidel cycle); error if the level has no such sweep
  *   op = 10: one fused Chebyshev step  x' = x + d', d' = c1 d + c2 dinv*(b - A_level x)  (a middle step: d read and stored);
- *           error if the level has no Chebyshev smoother */
+ *           error if the level has no Chebyshev smoother
+ * ops 5 and 10 time what the cycle runs: on a level with a single-precision image (mat_prec) they read that image; op 0 is
+ * amgx_residual's kernel and reads the fp64 image. */
 int amgx_time_op(amgx_handle h, int level, int op, int reps, double* avg_ms);
 
 /* ---- GSS4: Gauss-Seidel on a subset of the rows, on a compressed device copy ------------------------------------------

@@ -33,6 +33,14 @@ def _flags(kwargs):
     return out
 
 
+def _mat_prec_flag(v):
+    """ngs_amg_mat_prec = double | single, or one of the two per level (an own option: single-precision storage of the level matrix
+    for the smoother passes of the Chebyshev levels); validated by device.mat_prec_levels"""
+    if isinstance(v, (list, tuple)):
+        return [x.lower() if isinstance(x, str) else x for x in v]
+    return v.lower() if isinstance(v, str) else v
+
+
 def _energy_flag(f, energy, name="ngs_amg"):
     """ngs_amg_energy = triv | alg | elmat (amg_pc.cpp:333; reference default alg).  H1: alg is what the setup does (edge weights
     from the matrix entries, BuildAlgMesh_ALG_scal).  Elasticity: an explicit alg selects the reference's edge matrices from the
@@ -380,7 +388,8 @@ class _AMGPreconditioner:
                               sm_steps=steps, sm_symm=symm,
                               mg_cycle=str(f.get("mg_cycle", "V")).upper(), clev="inv" if clev == "inv" else "none",
                               device=self._device, use_graph=bool(f.get("use_graph", True)),
-                              cheb_degree=int(f.get("cheb_degree", 2)), cheb_ratio=float(f.get("cheb_ratio", 10)))
+                              cheb_degree=int(f.get("cheb_degree", 2)), cheb_ratio=float(f.get("cheb_ratio", 10)),
+                              mat_prec=_mat_prec_flag(f.get("mat_prec", "double")))
         self._amg = AMGMatrix(hier, dev)
         if f.get("do_test", False):
             self.Test()
@@ -566,12 +575,13 @@ def CreateJacobiSmoother(mat, freedofs=None, omega=0.9, device=0):
     return _StandaloneSmoother(mat, freedofs, "jacobi", omega=omega, device=device)
 
 
-def CreateChebyshevSmoother(mat, freedofs=None, degree=2, ratio=10, lambda_max=None, pinv=False, device=0):
+def CreateChebyshevSmoother(mat, freedofs=None, degree=2, ratio=10, lambda_max=None, pinv=False, device=0, mat_prec="double"):
     """stand-alone Chebyshev polynomial smoother of the given degree in the Jacobi-preconditioned operator on the interval
     [lambda_max / ratio, lambda_max] (no reference counterpart); lambda_max=None: 1.1 x a power-iteration estimate on the device.
+    mat_prec="single": the steps read a single-precision image of the matrix (vectors and accumulation stay fp64).
     Smooth == SmoothBack."""
     return _StandaloneSmoother(mat, freedofs, "cheby", pinv=pinv, device=device, cheb_degree=degree, cheb_ratio=ratio,
-                               cheb_lambda_max=lambda_max)
+                               cheb_lambda_max=lambda_max, mat_prec=mat_prec)
 
 
 def CreateHybridGSS(mat, freedofs=None, pinv=False, NG_MPI_overlap=True, NG_MPI_thread=False, symm=False,

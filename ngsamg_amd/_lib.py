@@ -203,7 +203,8 @@ class amgx_level_desc(C.Structure):
                 ("bgs_dinv_ptr", c_i64p), ("bgs_dinv", c_f64p), ("bgs_color", c_i32p), ("bgs_n_colors", C.c_int32),
                 ("Q", amgx_matrix), ("gs_block_rows", C.c_int32), ("gs_block_ids", c_i32p),
                 ("gs_block_color", c_i32p), ("gs_n_block_colors", C.c_int32),
-                ("cheb_degree", C.c_int32), ("cheb_lambda_max", C.c_double), ("cheb_ratio", C.c_double)]
+                ("cheb_degree", C.c_int32), ("cheb_lambda_max", C.c_double), ("cheb_ratio", C.c_double),
+                ("mat_prec", C.c_int32)]
 
 
 class amgx_hierarchy_desc(C.Structure):
@@ -232,6 +233,7 @@ AMGX_SM_JACOBI, AMGX_SM_GS, AMGX_SM_BGS, AMGX_SM_CHEBY = 0, 1, 2, 3
 AMGX_COMM_RCCL, AMGX_COMM_LOCAL = 0, 1
 AMGX_UNIQUE_ID_BYTES = 128
 AMGX_CYCLE = {"V": 0, "W": 1, "BS": 2}
+AMGX_PREC_F64, AMGX_PREC_F32 = 0, 1          # amgx_level_desc.mat_prec
 AMGX_CLEV_NONE, AMGX_CLEV_INV = 0, 1
 AMGX_HOST_PTR, AMGX_DEVICE_PTR, AMGX_NO_GRAPH = 0, 1, 2
 AMGX_PCG_SINGLE_REDUCTION = 16

@@ -133,6 +133,7 @@ struct DevMatrix {
     int win = 0;
     DevBuf<uint16_t> rowloc;
     SellMat view() const { return SellMat{slice_ptr.p, col32.p, col16.p, cbase.p, val.p, rowrel, diag_first, wdiag, xcd}; }
+    SellMatT<float> view32(const float* v32) const { return SellMatT<float>{slice_ptr.p, col32.p, col16.p, cbase.p, v32, rowrel, diag_first, wdiag, xcd}; }
   } sell;
   struct Rb {                          // rigid-body transfer blocks (kernels.hpp, RbMat): P_ik = w_ik Q(t_ik), or its transpose
     int dim = 0, bf = 0, bc = 0;       // spatial dimension of Q (0: w I), fine / coarse block size
@@ -148,7 +149,14 @@ struct DevMatrix {
     DevBuf<int32_t> col;
     DevBuf<double> val;
     BSellMat view(int xmode) const { return BSellMat{slice_ptr.p, col.p, val.p, xmode}; }
+    BSellMatT<float> view32(const float* v32, int xmode) const { return BSellMatT<float>{slice_ptr.p, col.p, v32, xmode}; }
   } bsell;
+  // single-precision image (A of a Chebyshev level with mat_prec = AMGX_PREC_F32, plain SELL or BSELL only): the
+  // value array of the format above rounded to float, same layout, every index array shared.  Built by mat_f32_image
+  // (build_level.hpp); read by the smoother passes of spmv_ep and by the fused residual + restriction, by nothing else.
+  DevBuf<float> val32;
+  bool has32() const { return val32.p != nullptr; }
+  int64_t stream_bytes32() const { return stream_bytes - 4 * (int64_t)val32.n; }
   bool empty() const { return n_rows == 0; }
 };
 
@@ -1356,9 +1364,14 @@ struct Handle {
     else { a = split; b = n_units; }
   }
 
+  // sm_pass: a product the smoother or the cycle launches on a level (EP_CHEB steps, the residual after smoothing).  It reads the
+  // single-precision image where amgx_create gave the level one (DevMatrix::has32); every other caller reads the fp64 image.
   template <int EP>
-  void spmv_ep(const DevMatrix& M, const double* x, double* y, const EpArgs& ep, const Span sp = Span()) {
+  void spmv_ep(const DevMatrix& M, const double* x, double* y, const EpArgs& ep, const Span sp = Span(), bool sm_pass = false) {
     if (M.n_rows == 0) return;
+    if constexpr (EP == EP_RES || EP == EP_CHEB) {
+      if (sm_pass && M.has32()) { spmv_ep32<EP>(M, x, y, ep, sp); return; }
+    }
     if (M.fmt == FMT_RB) {
       if constexpr (EP != EP_MULT && EP != EP_AXPY) throw Err("rigid-body transfer blocks: y = M x and y = yin + s M x only");
       else {
@@ -1499,8 +1512,41 @@ struct Handle {
     HIPCHK(hipGetLastError());
   }
 
+  // the smoother passes on the single-precision image: the float instantiations of the two kernel families that carry one
+  template <int EP>
+  void spmv_ep32(const DevMatrix& M, const double* x, double* y, const EpArgs& ep, const Span sp) {
+    if (M.fmt == FMT_SELL && !M.sell.win) {
+      int64_t a, b;
+      unit_range(sp, WAVE / M.lanes, M.n_slices, a, b);
+      if (b <= a) return;
+      const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+#define LAUNCH_SELL32(G) hipLaunchKernelGGL((sell_spmv_kernel<G, EP, float>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.sell.view32(M.val32.p), x, y, ep)
+      switch (M.lanes) {
+        case 1: LAUNCH_SELL32(1); break;
+        case 2: LAUNCH_SELL32(2); break;
+        case 4: LAUNCH_SELL32(4); break;
+        case 8: LAUNCH_SELL32(8); break;
+        default: LAUNCH_SELL32(16); break;
+      }
+#undef LAUNCH_SELL32
+    } else if (M.fmt == FMT_BSELL) {
+      int64_t a, b;
+      unit_range(sp, WAVE / M.br, M.n_slices, a, b);
+      if (b <= a) return;
+      const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+      const BSellMatT<float> V = M.bsell.view32(M.val32.p, knobs.bsell_xmode);
+      if (M.br == 6) hipLaunchKernelGGL((bsell_spmv_kernel<6, EP, float>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep);
+      else if (M.br == 3) hipLaunchKernelGGL((bsell_spmv_kernel<3, EP, float>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep);
+      else if (M.br == 2) hipLaunchKernelGGL((bsell_spmv_kernel<2, EP, float>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep);
+      else throw Err("single-precision image: unsupported block size");
+    } else throw Err("single-precision image on a format that has none");
+    HIPCHK(hipGetLastError());
+  }
+
   void mult(const DevMatrix& M, const double* x, double* y, const Span sp = Span()) { spmv_ep<EP_MULT>(M, x, y, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}, sp); }
   void residual(const DevMatrix& M, const double* x, const double* b, double* r, const Span sp = Span()) { spmv_ep<EP_RES>(M, x, r, EpArgs{b, nullptr, nullptr, 0.0, nullptr, ep_nt & EPF_HOIST}, sp); }
+  // the residual a smoother or the cycle forms on its level (update_res, the residual before the restriction): a smoother pass
+  void residual_sm(const DevLevel& L, const double* x, const double* b, double* r) { spmv_ep<EP_RES>(L.A, x, r, EpArgs{b, nullptr, nullptr, 0.0, nullptr, ep_nt & EPF_HOIST}, Span(), true); }
   // y = yin + s * M x
   void mult_add(const DevMatrix& M, double s, const double* x, const double* yin, double* y, const Span sp = Span()) { spmv_ep<EP_AXPY>(M, x, y, EpArgs{nullptr, yin, nullptr, s, nullptr, ep_nt & EPF_HOIST}, sp); }
   // xout = xin + omega * dinv * (b - A xin)
@@ -1528,7 +1574,7 @@ struct Handle {
   // one fused step: xout = xin + d_new, d_new = c1 * d_old + c2 * Dinv * (b - A xin); d_old == nullptr: xin; d_new == nullptr: not stored
   void cheb_step(const DevLevel& L, const double* xin, const double* b, double* xout, double c1, double c2, const double* d_old, double* d_new) {
     if (xin == xout) throw Err("cheb_step: in-place update is not allowed");
-    spmv_ep<EP_CHEB>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, c2, d_new, ep_nt, d_old, c1});
+    spmv_ep<EP_CHEB>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, c2, d_new, ep_nt, d_old, c1}, Span(), true);
   }
   // One Chebyshev smooth of degree k with the flag contract of base_smooth.  The iterate lives in `src` (x itself or L.tmp, ignored
   // with x_zero) and ends in x; the fused steps are out of place and ping-pong between x and L.tmp, so a caller that can choose
@@ -1561,7 +1607,7 @@ struct Handle {
       cur = nxt;
     }
     if (cur != x) copy(x, cur, L.len());
-    if (update_res) residual(L.A, x, b, res);
+    if (update_res) residual_sm(L, x, b, res);
   }
 
   void zero(double* v, int64_t n) {
@@ -2063,15 +2109,22 @@ struct Handle {
       const int nch = R.slice_list.n ? R.n_chunks : (L.A.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
       if (nch != R.n_chunks || L.fused_block != 512 || L.A.fmt != FMT_SELL || L.A.sell.win) throw Err("fused Chebyshev residual: chunk / slice mismatch");
       if (nch > 0) {
-#define LAUNCH_CRF(EPT_) hipLaunchKernelGGL((sell_pre_restrict_kernel<512, 2, EPT_>), dim3(nch), dim3(512), 0, stream, L.A.n_rows, 0, L.A.n_slices, L.A.sell.view(), \
+        // (a smoother pass: V_ = float and VIEW_ = the single-precision image where the level has one)
+#define LAUNCH_CRF(EPT_, V_, VIEW_) hipLaunchKernelGGL((sell_pre_restrict_kernel<512, 2, EPT_, 1, V_>), dim3(nch), dim3(512), 0, stream, L.A.n_rows, 0, L.A.n_slices, VIEW_, \
                              (const double*)x, b, 0.0, ep_nt, (double*)nullptr, (double*)nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, \
                              (const int32_t*)R.slice_list.p)
-#define LAUNCH_CRG(G_) hipLaunchKernelGGL((sell_pre_restrict_kernel<512, 2, 4, G_>), dim3(nch), dim3(512), 0, stream, L.A.n_rows, 0, L.A.n_slices, L.A.sell.view(), \
-                             (const double*)x, b, 0.0, ep_nt, (double*)nullptr, (double*)nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p)
-        if (G > 1) {
-          if (R.ept != 4 || R.slice_list.n) throw Err("fused Chebyshev residual with several lanes per row: unexpected chunk shape");
-          if (G == 2) LAUNCH_CRG(2); else if (G == 4) LAUNCH_CRG(4); else if (G == 8) LAUNCH_CRG(8); else throw Err("fused Chebyshev residual: unexpected lanes per row");
-        } else { if (R.ept == 4) LAUNCH_CRF(4); else LAUNCH_CRF(6); }
+#define LAUNCH_CRG(G_, V_, VIEW_) hipLaunchKernelGGL((sell_pre_restrict_kernel<512, 2, 4, G_, V_>), dim3(nch), dim3(512), 0, stream, L.A.n_rows, 0, L.A.n_slices, VIEW_, \
+                             (const double*)x, b, 0.0, ep_nt, (double*)nullptr, (double*)nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, \
+                             (const int32_t*)nullptr)
+#define LAUNCH_CR(V_, VIEW_)                                                                                                                     \
+        if (G > 1) {                                                                                                                              \
+          if (R.ept != 4 || R.slice_list.n) throw Err("fused Chebyshev residual with several lanes per row: unexpected chunk shape");           \
+          if (G == 2) LAUNCH_CRG(2, V_, VIEW_); else if (G == 4) LAUNCH_CRG(4, V_, VIEW_); else if (G == 8) LAUNCH_CRG(8, V_, VIEW_);              \
+          else throw Err("fused Chebyshev residual: unexpected lanes per row");                                                                  \
+        } else { if (R.ept == 4) LAUNCH_CRF(4, V_, VIEW_); else LAUNCH_CRF(6, V_, VIEW_); }
+        if (L.A.has32()) { LAUNCH_CR(float, L.A.sell.view32(L.A.val32.p)) }
+        else { LAUNCH_CR(double, L.A.sell.view()) }
+#undef LAUNCH_CR
 #undef LAUNCH_CRG
 #undef LAUNCH_CRF
       }
@@ -3659,8 +3712,15 @@ int amgx_cycle_info(amgx_handle hh, int32_t* tail_level, int32_t* dense_level, i
 int amgx_matrix_info(amgx_handle hh, int level, int which, int32_t* fmt, int64_t* stored, int32_t* lanes) {
   return guard(hh, [&](amgx::Handle& h) {
     if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_matrix_info: level out of range");
-    if (which < 0 || which > 6) throw amgx::Err("matrix query: which must be 0..6");
+    if (which < 0 || which > 7) throw amgx::Err("matrix query: which must be 0..7");
     const amgx::DevLevel& LV = h.lev[level];
+    if (which == 7) {                         // the single-precision image of A: the format, entries and lanes of A itself
+      const amgx::DevMatrix& M = LV.A;
+      if (fmt) *fmt = M.has32() ? M.fmt : -1;
+      if (stored) *stored = M.has32() ? M.stored : 0;
+      if (lanes) *lanes = M.has32() ? M.lanes : 0;
+      return;
+    }
     if (which == 3 && LV.dia.on()) {          // the symmetric diagonal image of A stands in for A' (format 6)
       if (fmt) *fmt = 6;
       if (stored) *stored = (int64_t)LV.dia.K * LV.n;
@@ -3677,8 +3737,10 @@ int amgx_matrix_info(amgx_handle hh, int level, int which, int32_t* fmt, int64_t
 int amgx_matrix_stream_bytes(amgx_handle hh, int level, int which, int64_t* bytes) {
   return guard(hh, [&](amgx::Handle& h) {
     if (level < 0 || level >= h.n_levels() || !bytes) throw amgx::Err("amgx_matrix_stream_bytes: bad arguments");
-    if (which < 0 || which > 6) throw amgx::Err("matrix query: which must be 0..6");
+    if (which < 0 || which > 7) throw amgx::Err("matrix query: which must be 0..7");
     const amgx::DevLevel& LV = h.lev[level];
+    // single-precision image of A: the indices and pointers of A + 4 bytes per stored value (0: not built)
+    if (which == 7) { *bytes = LV.A.has32() ? LV.A.stream_bytes32() : 0; return; }
     // diagonal image: the K upper diagonals (the lower ones are re-reads of the same arrays) + the dinv stream the kernel reads in
     // place of the wdiag slot
     if (which == 3 && LV.dia.on()) { *bytes = (int64_t)(LV.dia.K + 1) * LV.n * (int64_t)sizeof(double); return; }

@@ -18,6 +18,7 @@ struct LevelBuild {
   int l;
   int cycle;
   int dense_first;                      // see create()
+  int n_levels;
   // big scalar levels: the CSR arrays go to the device once and kernels write the images of A, A' and Q there (devbuild.hpp)
   DevCsrSrc csrA;
   DbDiagInfo diagA;
@@ -27,6 +28,8 @@ struct LevelBuild {
   DevBcsrSrc csrB;
   bool dev_bsell = false, verify_bsell = false;
   bool last() const { return c == nullptr; }
+  // levels whose smoother runs: all but the coarsest, and the only level of a single-level handle (a stand-alone smoother)
+  bool smoothed() const { return !last() || n_levels == 1; }
 };
 
 // shape and smoother-parameter validation; the scalar fields of the level
@@ -48,6 +51,13 @@ static void check_level(LevelBuild& B) {
     L.cheb_degree = deg;
     L.cheb_ratio = s.cheb_ratio == 0.0 ? 10.0 : s.cheb_ratio;
     if (s.cheb_lambda_max > 0.0) L.cheb_set_interval(s.cheb_lambda_max);
+  }
+  // single-precision matrix storage (the coarsest level of a cycle, which has no smoother passes, ignores the field)
+  if (B.smoothed()) {
+    if (s.mat_prec != AMGX_PREC_F64 && s.mat_prec != AMGX_PREC_F32)
+      throw Err("amgx_create: level " + std::to_string(B.l) + ": mat_prec must be AMGX_PREC_F64 (0) or AMGX_PREC_F32 (1), got " + std::to_string(s.mat_prec));
+    if (s.mat_prec == AMGX_PREC_F32 && s.sm_type != AMGX_SM_CHEBY)
+      throw Err("amgx_create: level " + std::to_string(B.l) + ": mat_prec = AMGX_PREC_F32 is available on Chebyshev levels (sm_type = AMGX_SM_CHEBY) only");
   }
   check_matrix(s.A, "A");            // (before anything reads rowptr[n_rows]: a NULL / garbage descriptor is an error, not a crash)
 }
@@ -431,6 +441,27 @@ static void cheb_fused_restrict(LevelBuild& B) {
   }
 }
 
+// Chebyshev levels with mat_prec = AMGX_PREC_F32: the single-precision image of A -- the value array of the level's
+// image rounded to float on the device, every index array shared.  From here on every smoother pass of the level (the EP_CHEB steps,
+// update_res, the residual before the restriction incl. its fused form) reads it; amgx_matvec, amgx_residual, the Krylov operator and
+// the lambda_max estimate keep the fp64 image.  Which levels get one is decided HERE and nowhere else:
+//   plain sliced-ELL (any lanes per row) and BSELL (2x2, 3x3, 6x6) -- the formats of the levels that carry bytes; CSR-vector,
+//   windowed SELL and block CSR levels (small / irregular) stay fp64 silently.
+// AMGX_NO_MAT_F32=1 ignores every request (the handle is then the double handle, bit for bit).
+static void mat_f32_image(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  if (!B.smoothed() || s.mat_prec != AMGX_PREC_F32 || s.sm_type != AMGX_SM_CHEBY || B.K.no_mat_f32) return;
+  const bool sell = L.A.fmt == FMT_SELL && !L.A.sell.win;
+  const bool bsell = L.A.fmt == FMT_BSELL && (L.A.br == 2 || L.A.br == 3 || L.A.br == 6);
+  if (!sell && !bsell) return;
+  const int64_t bad = dev_round_to_f32(sell ? L.A.sell.val : L.A.bsell.val, L.A.val32);
+  if (bad) {
+    L.A.val32.release();
+    throw Err("amgx_create: level " + std::to_string(B.l) + ": " + std::to_string(bad) + " value(s) of A are beyond the range of single precision (mat_prec = AMGX_PREC_F32)");
+  }
+}
+
 // workgroup -> rows mapping of the streaming kernels on this level (SellMat::xcd)
 static void set_xcd_modes(LevelBuild& B) {
   const amgx_level_desc& s = B.s;
@@ -683,7 +714,7 @@ static Handle* create(const amgx_hierarchy_desc* d, const Knobs& K, int dense_fi
   for (int l = 0; l < d->n_levels; ++l) if (!pstore[l].perm.empty()) h->perm[l].upload(pstore[l].perm);
   const amgx_level_desc* levels = pl.data();
   for (int l = 0; l < d->n_levels; ++l) {
-    LevelBuild B{h->knobs, clk, levels[l], l + 1 < d->n_levels ? &levels[l + 1] : nullptr, h->lev[l], l, d->cycle, dense_first};
+    LevelBuild B{h->knobs, clk, levels[l], l + 1 < d->n_levels ? &levels[l + 1] : nullptr, h->lev[l], l, d->cycle, dense_first, d->n_levels};
     check_level(B);
     SetupTasks tasks(d->device, K);       // (after B: see LevelBuild)
     upload_level_matrix(B, tasks);
@@ -700,6 +731,7 @@ static Handle* create(const amgx_hierarchy_desc* d, const Knobs& K, int dense_fi
       build_coarsest_smoother_data(B);
     }
     tasks.wait();
+    mat_f32_image(B);
     set_xcd_modes(B);
     alloc_level_vectors(B);
   }

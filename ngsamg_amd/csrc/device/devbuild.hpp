@@ -384,8 +384,33 @@ __global__ __launch_bounds__(BLOCK) void db_fill_i32_kernel(int64_t n, int32_t v
   if (i < n) p[i] = v;
 }
 
+// single-precision image of a value array (DevMatrix::val32): dst = src rounded to nearest float, element by element, so the layout
+// of the fp64 image carries over; *n_bad counts the results that are not finite (a value beyond the range of float)
+__global__ __launch_bounds__(BLOCK) void db_to_f32_kernel(int64_t n, const double* __restrict__ src, float* __restrict__ dst, unsigned int* __restrict__ n_bad) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const float v = (float)src[i];
+  dst[i] = v;
+  if (!isfinite(v)) atomicAdd(n_bad, 1u);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // host side
+
+// the float twin of a device value array; returns the number of non-finite results
+static int64_t dev_round_to_f32(const DevBuf<double>& src, DevBuf<float>& dst) {
+  const int64_t n = (int64_t)src.n;
+  dst.alloc(src.n);
+  if (n == 0) return 0;
+  DevBuf<unsigned int> bad;
+  bad.alloc(1);
+  HIPCHK(hipMemset(bad.p, 0, sizeof(unsigned int)));
+  hipLaunchKernelGGL(db_to_f32_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, 0, n, src.p, dst.p, bad.p);
+  HIPCHK(hipGetLastError());
+  unsigned int h = 0;
+  HIPCHK(hipMemcpy(&h, bad.p, sizeof(h), hipMemcpyDeviceToHost));
+  return (int64_t)h;
+}
 
 static bool dev_images_wanted(const Knobs& K, const amgx_matrix& A) {
   if (K.host_images) return false;

@@ -76,6 +76,16 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
 template <class T>
 __device__ __forceinline__ T ld_nt(const T* p) { return __builtin_nontemporal_load(p); }
 
+// One value pair of a lane from a matrix stream whose values are V = double (two 8-byte loads of neighbouring elements: one 16-byte
+// instruction) or V = float (the single-precision image of a Chebyshev level, DESIGN.md 5.12: ONE 8-byte load).  The kernels widen a
+// float to double where they multiply, so everything after the load is the arithmetic of the fp64 kernel on the rounded values.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <class V>
+__device__ __forceinline__ void ld_nt_pair(const V* __restrict__ p, V& a, V& b) {
+  if constexpr (sizeof(V) == 4) { const f32x2 t = ld_nt(reinterpret_cast<const f32x2*>(p)); a = t.x; b = t.y; }
+  else { a = ld_nt(p); b = ld_nt(p + 1); }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // scalar epilogue
 // have_xd: xd is the value of the gathered vector at the own row (EP_JAC: yin[row], EP_PRE: b[row]) and need not be loaded
@@ -161,12 +171,14 @@ __device__ __forceinline__ void store_scalar_ops(int64_t row, double acc, double
 // where `column` = (base >> 6) + j numbers the 64-entry columns of all slices.  On FEM matrices the offset
 // col - row is (nearly) the same for all 64 rows of a slice column, so the 16-bit form almost always applies
 // and the index stream shrinks from 4 to ~2 bytes per entry (-13 % kernel time measured).
-struct SellMat {
+// V = type of the stored values: double, or float for the single-precision image (same index arrays, see ld_nt_pair)
+template <class V>
+struct SellMatT {
   const int64_t* slice_ptr;   // [n_slices+1] element offset (multiple of 64) | encoding flag in bit 0
   const int32_t* col32;
   const uint16_t* col16;
   const int32_t* cbase;
-  const double* val;
+  const V* val;
   int rowrel;
   int diag_first;             // G == 1 only: entry 0 of every row is its diagonal, so the gathered x[row] comes for free
   int wdiag;                  // pre-smoothing image A' only (implies diag_first): the diagonal slot holds omega*Dinv_i instead of
@@ -175,7 +187,9 @@ struct SellMat {
                               //   eighth of the rows.  For long-row levels whose gathered vector does not fit an L2 next to the rows in flight
                               //   (the 1.24 M x 52 level of cfg 2: 10 MB of x, 40 % of the rows in flight at once); level 0 keeps 0 (xcd_remap)
 };
-__device__ __forceinline__ int sell_unit(const SellMat& M) { return M.xcd ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x; }
+using SellMat = SellMatT<double>;
+template <class V>
+__device__ __forceinline__ int sell_unit(const SellMatT<V>& M) { return M.xcd ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x; }
 
 // SELL row product, software-pipelined in batches of K pair-steps: the matrix loads (values + packed indices) of batch
 // i+1 are requested BEFORE the gathers of batch i are consumed, so a wave always has a matrix batch in flight while it
@@ -189,19 +203,18 @@ __device__ __forceinline__ int sell_unit(const SellMat& M) { return M.xcd ? xcd_
 #define SELL_PIPELINE 1
 #endif
 
-template <int K>
+template <int K, class V = double>
 struct SellRegs {
-  double v0[K], v1[K];
+  V v0[K], v1[K];
   uint32_t ca[K], cb2[K];    // C16: ca = packed 16-bit pair; 32-bit: ca, cb2 = the two columns
 };
 
-template <int K, bool C16>
-__device__ __forceinline__ void sell_load(SellRegs<K>& R, const double* __restrict__ vb, const void* __restrict__ cpv, int p, int lane) {
+template <int K, bool C16, class V>
+__device__ __forceinline__ void sell_load(SellRegs<K, V>& R, const V* __restrict__ vb, const void* __restrict__ cpv, int p, int lane) {
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int q = p + k;
-    R.v0[k] = ld_nt(vb + (q * WAVE + lane) * 2);
-    R.v1[k] = ld_nt(vb + (q * WAVE + lane) * 2 + 1);
+    ld_nt_pair(vb + (q * WAVE + lane) * 2, R.v0[k], R.v1[k]);
     if (C16) R.ca[k] = ld_nt(static_cast<const uint32_t*>(cpv) + q * WAVE + lane);
     else {
       const int32_t* __restrict__ cp = static_cast<const int32_t*>(cpv);
@@ -211,8 +224,8 @@ __device__ __forceinline__ void sell_load(SellRegs<K>& R, const double* __restri
   }
 }
 
-template <int K, bool C16>
-__device__ __forceinline__ void sell_consume(const SellRegs<K>& R, const int32_t* __restrict__ cb, int r0, int p,
+template <int K, bool C16, class V>
+__device__ __forceinline__ void sell_consume(const SellRegs<K, V>& R, const int32_t* __restrict__ cb, int r0, int p,
                                              const double* __restrict__ x, double& acc0, double& acc1, double* xd) {
   double x0[K], x1[K];
 #pragma unroll
@@ -223,49 +236,49 @@ __device__ __forceinline__ void sell_consume(const SellRegs<K>& R, const int32_t
     x0[k] = x[c0];
     x1[k] = x[c1];
   }
-  if (p == 0) { xd[0] = x0[0]; xd[1] = R.v0[0]; }
+  if (p == 0) { xd[0] = x0[0]; xd[1] = (double)R.v0[0]; }
 #pragma unroll
-  for (int k = 0; k < K; ++k) { acc0 += R.v0[k] * x0[k]; acc1 += R.v1[k] * x1[k]; }
+  for (int k = 0; k < K; ++k) { acc0 += (double)R.v0[k] * x0[k]; acc1 += (double)R.v1[k] * x1[k]; }
 }
 
 // remainder batch of REM < K steps; `last` (may be null) is a full batch whose gathers are consumed after the
 // remainder's matrix loads went out
-template <int K, int REM, bool C16>
-__device__ __forceinline__ void sell_tail(int rem, const SellRegs<K>* last, int p_last, const double* __restrict__ vb,
+template <int K, int REM, bool C16, class V>
+__device__ __forceinline__ void sell_tail(int rem, const SellRegs<K, V>* last, int p_last, const V* __restrict__ vb,
                                           const void* __restrict__ cpv, const int32_t* __restrict__ cb, int r0, int p, int lane,
                                           const double* __restrict__ x, double& acc0, double& acc1, double* xd) {
   if (rem == REM) {
-    SellRegs<REM> R;
+    SellRegs<REM, V> R;
     sell_load<REM, C16>(R, vb, cpv, p, lane);
     if (last) sell_consume<K, C16>(*last, cb, r0, p_last, x, acc0, acc1, xd);
     sell_consume<REM, C16>(R, cb, r0, p, x, acc0, acc1, xd);
   } else if constexpr (REM > 1) sell_tail<K, REM - 1, C16>(rem, last, p_last, vb, cpv, cb, r0, p, lane, x, acc0, acc1, xd);
 }
 
-template <bool C16, int K = SELL_BATCH>
-__device__ __forceinline__ void sell_pairs(int np, const double* __restrict__ vb, const void* __restrict__ cpv, const int32_t* __restrict__ cb,
+template <bool C16, int K = SELL_BATCH, class V>
+__device__ __forceinline__ void sell_pairs(int np, const V* __restrict__ vb, const void* __restrict__ cpv, const int32_t* __restrict__ cb,
                                            int r0, int lane, const double* __restrict__ x, double& acc0, double& acc1, double* xd) {
   const int nfull = np / K, rem = np - nfull * K;
 #if SELL_PIPELINE
   if (nfull > 0) {
-    SellRegs<K> A;
+    SellRegs<K, V> A;
     sell_load<K, C16>(A, vb, cpv, 0, lane);
     for (int b = 1; b < nfull; ++b) {
-      SellRegs<K> B;
+      SellRegs<K, V> B;
       sell_load<K, C16>(B, vb, cpv, b * K, lane);
       sell_consume<K, C16>(A, cb, r0, (b - 1) * K, x, acc0, acc1, xd);
       A = B;
     }
     if (K > 1 && rem) sell_tail<K, (K > 1 ? K - 1 : 1), C16>(rem, &A, (nfull - 1) * K, vb, cpv, cb, r0, nfull * K, lane, x, acc0, acc1, xd);
     else sell_consume<K, C16>(A, cb, r0, (nfull - 1) * K, x, acc0, acc1, xd);
-  } else if (K > 1 && rem) sell_tail<K, (K > 1 ? K - 1 : 1), C16>(rem, nullptr, 0, vb, cpv, cb, r0, 0, lane, x, acc0, acc1, xd);
+  } else if (K > 1 && rem) sell_tail<K, (K > 1 ? K - 1 : 1), C16>(rem, (const SellRegs<K, V>*)nullptr, 0, vb, cpv, cb, r0, 0, lane, x, acc0, acc1, xd);
 #else
   for (int b = 0; b < nfull; ++b) {
-    SellRegs<K> A;
+    SellRegs<K, V> A;
     sell_load<K, C16>(A, vb, cpv, b * K, lane);
     sell_consume<K, C16>(A, cb, r0, b * K, x, acc0, acc1, xd);
   }
-  if (K > 1 && rem) sell_tail<K, (K > 1 ? K - 1 : 1), C16>(rem, nullptr, 0, vb, cpv, cb, r0, nfull * K, lane, x, acc0, acc1, xd);
+  if (K > 1 && rem) sell_tail<K, (K > 1 ? K - 1 : 1), C16>(rem, (const SellRegs<K, V>*)nullptr, 0, vb, cpv, cb, r0, nfull * K, lane, x, acc0, acc1, xd);
 #endif
 }
 
@@ -277,19 +290,19 @@ __device__ __forceinline__ void sell_pairs(int np, const double* __restrict__ vb
 // (sp0, sp1 = slice_ptr[s], slice_ptr[s + 1]: callers with a long prologue load them first, see sell_pre_restrict_kernel)
 // x32 (optional): the vector slices in the 32-bit encoding gather from (local-window images: 16-bit slices index the LDS window,
 // 32-bit slices -- chunks whose window would not fit -- carry global columns)
-template <int K = SELL_BATCH>
-__device__ __forceinline__ double sell_row_dot_sp(const SellMat& M, int64_t sp0, int64_t sp1, int lane, int row, const double* x, double* xd,
+template <int K = SELL_BATCH, class V = double>
+__device__ __forceinline__ double sell_row_dot_sp(const SellMatT<V>& M, int64_t sp0, int64_t sp1, int lane, int row, const double* x, double* xd,
                                                   const double* x32 = nullptr) {
   const int64_t base = sp0 & ~(int64_t)63;
   const int w = (int)(((sp1 & ~(int64_t)63) - base) >> 6);
   const int np = w >> 1;
-  const double* __restrict__ vb = M.val + base;
+  const V* __restrict__ vb = M.val + base;
   double acc0 = 0.0, acc1 = 0.0;
   const bool c16 = sp0 & 1;
   const int32_t* __restrict__ cb = M.cbase + (base >> 6);
   const int r0 = (c16 && M.rowrel) ? row : 0;
   // odd trailing column: its matrix loads go out first, its gather comes last
-  double vs = 0.0;
+  V vs = 0;
   int cs = 0;
   if (w & 1) {
     const int64_t o = (int64_t)(w - 1) * WAVE + lane;
@@ -301,13 +314,13 @@ __device__ __forceinline__ double sell_row_dot_sp(const SellMat& M, int64_t sp0,
   else sell_pairs<false, K>(np, vb, M.col32 + base, nullptr, 0, lane, xw32, acc0, acc1, xd);
   if (w & 1) {
     const double x0 = c16 ? x[r0 + cb[w - 1] + cs] : xw32[cs];
-    if (np == 0) { xd[0] = x0; xd[1] = vs; }
-    acc0 += vs * x0;
+    if (np == 0) { xd[0] = x0; xd[1] = (double)vs; }
+    acc0 += (double)vs * x0;
   }
   return acc0 + acc1;
 }
-template <int K = SELL_BATCH>
-__device__ __forceinline__ double sell_row_dot(const SellMat& M, int s, int lane, int row, const double* x, double* xd) {
+template <int K = SELL_BATCH, class V = double>
+__device__ __forceinline__ double sell_row_dot(const SellMatT<V>& M, int s, int lane, int row, const double* x, double* xd) {
   return sell_row_dot_sp<K>(M, M.slice_ptr[s], M.slice_ptr[s + 1], lane, row, x, xd);
 }
 template <int K = SELL_BATCH>
@@ -317,8 +330,9 @@ __device__ __forceinline__ double sell_row_dot(const SellMat& M, int s, int lane
 }
 
 // SELL-64-pair, scalar, G lanes per row (G = 1: one thread per row), one wave per slice of 64/G rows
-template <int G, int EP>
-__global__ __launch_bounds__(BLOCK) void sell_spmv_kernel(int64_t n_rows, int slice0, int n_slices, SellMat M,
+// V = float: the same kernel on the single-precision image (EP_RES and EP_CHEB are instantiated: the smoother passes of a Chebyshev level)
+template <int G, int EP, class V = double>
+__global__ __launch_bounds__(BLOCK) void sell_spmv_kernel(int64_t n_rows, int slice0, int n_slices, SellMatT<V> M,
                                                           const double* __restrict__ x, double* y, EpArgs ep) {
   const int lane = threadIdx.x & (WAVE - 1);
   // the slice index is wave-uniform: tell the compiler, so slice pointers and column bases use scalar loads
@@ -488,13 +502,15 @@ __global__ __launch_bounds__(BLOCK) void bcsrvec_spmv_kernel(int64_t n_rows, con
 // so every wave instruction streams one aligned 1 KiB (or 512 B) chunk, exactly like the scalar SELL kernel; the block
 // column index is stored once per (k, block row).  Used when the slice padding stays small (FEM fine levels); irregular
 // coarse levels keep the CSR row-per-lane kernels.
-struct BSellMat {
+template <class V>
+struct BSellMatT {
   const int64_t* slice_ptr;   // [n_slices+1] cumulative block steps
   const int32_t* col;         // [steps * RB]
-  const double* val;          // [steps * BS * 64]
+  const V* val;               // [steps * BS * 64]; V = float: the single-precision image, same layout (8 bytes per lane and column pair)
   int xmode;                  // row product: 0 = plain loop, BS 8-byte gathers per lane, 1 = 16-byte gathers, 2 = one load + lane exchange,
                               // 3 / 4 / 5 = column indices one batch of 2 / 4 / 3 steps ahead (bsell_row_dot_ahead)
 };
+using BSellMat = BSellMatT<double>;
 
 #ifndef BSELL_UNROLL
 #define BSELL_UNROLL 2
@@ -505,8 +521,8 @@ struct BSellMat {
 // block step six 8-byte gathers (ten distinct lines each: one per block row of the wave) next to three streaming loads.  Halving the
 // gather instructions (V2) or replacing them by one load + a lane exchange (bsell_block_step_shfl) did NOT pay (BSellMat::xmode 1 / 2,
 // measured neutral / 7-13 % slower, see amgx.hip bsell_xmode): both stay opt-in.
-template <int BS, bool V2>
-__device__ __forceinline__ void bsell_block_step(const double* __restrict__ vk, const double* __restrict__ xv, int lane, double& acc) {
+template <int BS, bool V2, class V>
+__device__ __forceinline__ void bsell_block_step(const V* __restrict__ vk, const double* __restrict__ xv, int lane, double& acc) {
   if (V2 && (BS % 2) == 0) {
     const double2* __restrict__ x2 = reinterpret_cast<const double2*>(xv);
     double2 xx[BS / 2];
@@ -514,22 +530,24 @@ __device__ __forceinline__ void bsell_block_step(const double* __restrict__ vk, 
     for (int cp = 0; cp < BS / 2; ++cp) xx[cp] = x2[cp];
 #pragma unroll
     for (int cp = 0; cp < BS / 2; ++cp) {
-      const double v0 = ld_nt(vk + cp * (2 * WAVE) + lane * 2), v1 = ld_nt(vk + cp * (2 * WAVE) + lane * 2 + 1);
-      acc += v0 * xx[cp].x + v1 * xx[cp].y;
+      V v0, v1;
+      ld_nt_pair(vk + cp * (2 * WAVE) + lane * 2, v0, v1);
+      acc += (double)v0 * xx[cp].x + (double)v1 * xx[cp].y;
     }
   } else {
 #pragma unroll
     for (int cp = 0; cp < BS / 2; ++cp) {
-      const double v0 = ld_nt(vk + cp * (2 * WAVE) + lane * 2), v1 = ld_nt(vk + cp * (2 * WAVE) + lane * 2 + 1);
-      acc += v0 * xv[2 * cp] + v1 * xv[2 * cp + 1];
+      V v0, v1;
+      ld_nt_pair(vk + cp * (2 * WAVE) + lane * 2, v0, v1);
+      acc += (double)v0 * xv[2 * cp] + (double)v1 * xv[2 * cp + 1];
     }
-    if (BS & 1) acc += ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xv[BS - 1];
+    if (BS & 1) acc += (double)ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xv[BS - 1];
   }
 }
 // the same step with ONE 8-byte gather per lane: lane r of a block row reads x[c * BS + r] and the BS lanes of the block row exchange
 // their values through the cross-lane network (base = first lane of the block row).  Same products in the same order.
-template <int BS>
-__device__ __forceinline__ void bsell_block_step_shfl(const double* __restrict__ vk, const double* __restrict__ xv, int lane, int r, int base,
+template <int BS, class V>
+__device__ __forceinline__ void bsell_block_step_shfl(const V* __restrict__ vk, const double* __restrict__ xv, int lane, int r, int base,
                                                       double& acc) {
   const double mine = xv[r];
   double xb[BS];
@@ -537,10 +555,11 @@ __device__ __forceinline__ void bsell_block_step_shfl(const double* __restrict__
   for (int c = 0; c < BS; ++c) xb[c] = __shfl(mine, base + c, WAVE);
 #pragma unroll
   for (int cp = 0; cp < BS / 2; ++cp) {
-    const double v0 = ld_nt(vk + cp * (2 * WAVE) + lane * 2), v1 = ld_nt(vk + cp * (2 * WAVE) + lane * 2 + 1);
-    acc += v0 * xb[2 * cp] + v1 * xb[2 * cp + 1];
+    V v0, v1;
+    ld_nt_pair(vk + cp * (2 * WAVE) + lane * 2, v0, v1);
+    acc += (double)v0 * xb[2 * cp] + (double)v1 * xb[2 * cp + 1];
   }
-  if (BS & 1) acc += ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xb[BS - 1];
+  if (BS & 1) acc += (double)ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xb[BS - 1];
 }
 
 // Row product of one BSELL slice with the column indices one batch AHEAD: the plain loop asks for a step's column index, waits,
@@ -548,8 +567,8 @@ __device__ __forceinline__ void bsell_block_step_shfl(const double* __restrict__
 // at the end of every iteration) -- two dependent memory round trips per iteration and nothing in flight across iterations.  Here
 // the indices of batch n + 1 are requested before the values and gathers of batch n, so an iteration waits for ONE round trip.
 // Same products in the same order.
-template <int BS, bool V2, int U>
-__device__ __forceinline__ double bsell_row_dot_ahead(const double* __restrict__ vb, const int32_t* __restrict__ cb, int w, int rbl, int lane,
+template <int BS, bool V2, int U, class V>
+__device__ __forceinline__ double bsell_row_dot_ahead(const V* __restrict__ vb, const int32_t* __restrict__ cb, int w, int rbl, int lane,
                                                       const double* x) {
   constexpr int RB = WAVE / BS;
   double acc = 0.0;
@@ -572,8 +591,9 @@ __device__ __forceinline__ double bsell_row_dot_ahead(const double* __restrict__
   return acc;
 }
 
-template <int BS, int EP>
-__global__ __launch_bounds__(BLOCK) void bsell_spmv_kernel(int64_t n_rows, int slice0, int n_slices, BSellMat M,
+// V = float: the same kernel on the single-precision image (EP_RES and EP_CHEB are instantiated)
+template <int BS, int EP, class V = double>
+__global__ __launch_bounds__(BLOCK) void bsell_spmv_kernel(int64_t n_rows, int slice0, int n_slices, BSellMatT<V> M,
                                                            const double* __restrict__ x, double* y, EpArgs ep) {
   constexpr int RB = WAVE / BS;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -586,7 +606,7 @@ __global__ __launch_bounds__(BLOCK) void bsell_spmv_kernel(int64_t n_rows, int s
   const bool active = lane < RB * BS && brow < n_rows;
   const int64_t k0 = M.slice_ptr[s];
   const int w = (int)(M.slice_ptr[s + 1] - k0);
-  const double* __restrict__ vb = M.val + k0 * (BS * WAVE);
+  const V* __restrict__ vb = M.val + k0 * (BS * WAVE);
   const int32_t* __restrict__ cb = M.col + k0 * RB;
   const int64_t i = brow * BS + r;
   // own-row epilogue operands requested ahead of the matrix stream (EPF_HOIST, see sell_spmv_kernel)
@@ -1295,8 +1315,9 @@ __global__ __launch_bounds__(BLOCK) void restrict_chunk_kernel(int64_t n_fine, c
 // "classic" rows; chosen per level by build_restrict from the fullest chunk)
 // G = lanes per row (SELL-G image, long rows of the coarser levels): the chunk then holds FUSED_BLOCK / G rows, the G partial
 // row sums are combined by a wave shuffle and the first lane of every group runs the epilogue
-template <int FUSED_BLOCK, int MODE = 0, int EPT = 4, int G = 1>
-__global__ __launch_bounds__(FUSED_BLOCK) void sell_pre_restrict_kernel(int64_t n_rows, int chunk0, int n_slices, SellMat M,
+// V = float (MODE 2 only): A is the single-precision image of the level
+template <int FUSED_BLOCK, int MODE = 0, int EPT = 4, int G = 1, class V = double>
+__global__ __launch_bounds__(FUSED_BLOCK) void sell_pre_restrict_kernel(int64_t n_rows, int chunk0, int n_slices, SellMatT<V> M,
                                                                         const double* __restrict__ b, const double* __restrict__ dinv,
                                                                         double omega, int nt, double* __restrict__ x, double* r_out,
                                                                         const int32_t* __restrict__ chunk_slot,

@@ -49,6 +49,35 @@ def cheby_args(degree, ratio, lambda_max, i=0, n=1):
     return deg, lam, rat
 
 
+_PREC = {"double": _lib.AMGX_PREC_F64, "single": _lib.AMGX_PREC_F32}
+
+
+def mat_prec_levels(mat_prec, types):
+    """amgx_level_desc.mat_prec of every level for the smoother types `types` (one per level, the last = the coarsest, which
+    ignores the field).  mat_prec: "double", "single" or a per-level list of the two.  A scalar "single" applies to the
+    Chebyshev levels and needs at least one; a list may say "single" on Chebyshev levels only."""
+    n = len(types)
+    per_level = isinstance(mat_prec, (list, tuple))
+    vals = list(mat_prec) if per_level else [mat_prec] * n
+    if len(vals) != n:
+        raise NgsAMGError("mat_prec list must have one entry per level")
+    for v in vals:
+        if not isinstance(v, str) or v not in _PREC:
+            raise NgsAMGError(f"unknown mat_prec {v!r} (double | single)")
+    out = [0] * n
+    for i in (range(n - 1) if n > 1 else range(n)):       # smoothed levels (a single level: a stand-alone smoother)
+        if vals[i] != "single":
+            continue
+        if types[i] == "cheby":
+            out[i] = _lib.AMGX_PREC_F32
+        elif per_level:
+            raise NgsAMGError(f"mat_prec 'single' on level {i}: single-precision matrix storage is available on Chebyshev "
+                              f"levels only (sm_type '{types[i]}')")
+    if not per_level and mat_prec == "single" and not any(out):
+        raise NgsAMGError("mat_prec 'single': the hierarchy has no Chebyshev level (sm_type 'cheby') to apply it to")
+    return out
+
+
 def gs_block_rows(A):
     """rows per block of the block-hybrid Gauss-Seidel kernel for a scalar level matrix.  G lanes share a row, each holds
     at most 16 entries (+1 when G = 1) in registers; the workgroup has B * G lanes.  Measured at cfg 2:
@@ -209,16 +238,19 @@ def check_multi(vecs, sizes, interleaved=False, names=None):
 
 
 def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V", clev="inv", device=0,
-                   use_graph=True, cheb_degree=2, cheb_ratio=10, cheb_lambda_max=None):
+                   use_graph=True, cheb_degree=2, cheb_ratio=10, cheb_lambda_max=None, mat_prec="double"):
     """amgx_hierarchy_desc over the host arrays of a hierarchy.  Returns (desc, keep): `keep` holds everything the
     descriptor points to and must outlive the amgx_create / amgx_dist_create call.
     cheb_*: levels with sm_type "cheby" (each a scalar or a per-level list); the descriptor carries 0 for a default
-    (degree 2, ratio 10) and for a lambda_max that amgx_create estimates on the device."""
+    (degree 2, ratio 10) and for a lambda_max that amgx_create estimates on the device.
+    mat_prec: "double" (default), "single" (single-precision storage of A for the smoother passes of the Chebyshev levels) or a
+    per-level list; see mat_prec_levels."""
     levels = hierarchy.levels
     n = len(levels)
     types = sm_type if isinstance(sm_type, (list, tuple)) else [sm_type] * n
     if len(types) != n:
         raise NgsAMGError("sm_type list must have one entry per level")
+    prec = mat_prec_levels(mat_prec, types)
     arr = (_lib.amgx_level_desc * n)()
     keep = [arr, hierarchy]
     info = [None] * n            # per level: block-hybrid Gauss-Seidel data actually used (tests configure the oracle with it)
@@ -238,6 +270,7 @@ def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False
             d.cheb_degree = deg
             d.cheb_lambda_max = lam
             d.cheb_ratio = 0.0 if rat == 10.0 else rat
+        d.mat_prec = prec[i]
         d.omega = float(omega)
         d.sm_steps = int(sm_steps[i] if isinstance(sm_steps, (list, tuple)) else sm_steps)      # per level: ..._spec flags
         d.sm_symm = int(bool(sm_symm[i] if isinstance(sm_symm, (list, tuple)) else sm_symm))
@@ -315,15 +348,18 @@ def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False
 
 class DeviceAMGMatrix:
     def __init__(self, hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V",
-                 clev="inv", device=0, use_graph=True, cheb_degree=2, cheb_ratio=10, cheb_lambda_max=None):
+                 clev="inv", device=0, use_graph=True, cheb_degree=2, cheb_ratio=10, cheb_lambda_max=None, mat_prec="double"):
+        if mat_prec != "double":             # a request that cannot be met is refused before the library is loaded
+            n_lev = len(hierarchy.levels)
+            mat_prec_levels(mat_prec, list(sm_type) if isinstance(sm_type, (list, tuple)) else [sm_type] * n_lev)
         lib = _lib.hip()
         self._lib = lib
         self._cfg = dict(sm_type=sm_type, omega=omega, sm_steps=sm_steps, sm_symm=sm_symm, mg_cycle=mg_cycle, clev=clev,
                          device=device, use_graph=use_graph, cheb_degree=cheb_degree, cheb_ratio=cheb_ratio,
-                         cheb_lambda_max=cheb_lambda_max)
+                         cheb_lambda_max=cheb_lambda_max, mat_prec=mat_prec)
         self.hierarchy = hierarchy
         desc, self._keep, self.hgs = hierarchy_desc(hierarchy, sm_type, omega, sm_steps, sm_symm, mg_cycle, clev, device, use_graph,
-                                                    cheb_degree, cheb_ratio, cheb_lambda_max)
+                                                    cheb_degree, cheb_ratio, cheb_lambda_max, mat_prec)
         self._h = C.c_void_p()
         self._owned = True
         if lib.amgx_create(C.byref(desc), C.byref(self._h)) != 0:
@@ -536,12 +572,15 @@ class DeviceAMGMatrix:
         self._ck(self._lib.amgx_cycle_info(self._h, C.byref(t), C.byref(d), C.byref(n)))
         return {"tail_level": t.value, "dense_level": d.value, "dense_n": n.value}
 
+    _WHICH = {"A": 0, "P": 1, "PT": 2, "Apre": 3, "Q": 4, "ApreLW": 5, "QLW": 6, "A32": 7}
+
     def matrix_info(self, level, which):
+        """device format of one image of a level ("A32": the single-precision image of A that the smoother passes read, fmt None
+        where the level has none)"""
         fmt, stored, lanes = C.c_int32(), C.c_int64(), C.c_int32()
-        self._ck(self._lib.amgx_matrix_info(self._h, level, {"A": 0, "P": 1, "PT": 2, "Apre": 3, "Q": 4, "ApreLW": 5, "QLW": 6}[which], C.byref(fmt),
-                                            C.byref(stored), C.byref(lanes)))
+        self._ck(self._lib.amgx_matrix_info(self._h, level, self._WHICH[which], C.byref(fmt), C.byref(stored), C.byref(lanes)))
         nb = C.c_int64()
-        self._ck(self._lib.amgx_matrix_stream_bytes(self._h, level, {"A": 0, "P": 1, "PT": 2, "Apre": 3, "Q": 4, "ApreLW": 5, "QLW": 6}[which], C.byref(nb)))
+        self._ck(self._lib.amgx_matrix_stream_bytes(self._h, level, self._WHICH[which], C.byref(nb)))
         return {"fmt": {-1: None, 0: "csrvec", 1: "sell", 2: "bsell", 3: "sellwin", 4: "rigid-body", 5: "sell-lw", 6: "dia"}.get(fmt.value, "?"), "stored": stored.value, "lanes": lanes.value,
                 "stream_bytes": nb.value}
 
