@@ -10,6 +10,7 @@
 #include "../../../include/amgx.h"
 #include "kernels.hpp"
 #include "knobs.hpp"
+#include "launch.hpp"          // Err, HIPCHK, dispatch, launch
 #include "../host/dia.hpp"
 #include <dlfcn.h>
 #include <algorithm>
@@ -32,15 +33,6 @@
 #include <vector>
 
 namespace amgx {
-
-struct Err : std::runtime_error { using std::runtime_error::runtime_error; };
-
-#define HIPCHK(call)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (call);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      throw ::amgx::Err(std::string(#call) + " failed: " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-  } while (0)
 
 // roctx ranges named like the reference's timers (AMGMatrix::SmoothV: "AMGMatrix::Mult", "level 0" .. "level 3", "rest",
 // "coarse inv", src/base/solve/amg_matrix.cpp:166-178; "ProlMap::TransferF2C" / "ProlMap::TransferC2F",
@@ -307,7 +299,29 @@ struct DevCsr {                         // plain CSR copy for the single-workgro
   }
 };
 
+// The paths of a level through the cycle.  resolve_paths() turns the presence of the level's images into these values once, when
+// amgx_create has built (and possibly released) them; the apply side, the reports and the timers read the values and never probe
+// the images again.  The numbers of the first two are the codes amgx_level_paths reports (include/amgx.h, entries 0 and 19).
+enum DownPath : int {                   // fused down kernel (pre-smoothing + restriction)
+  DOWN_NONE = 0, DOWN_SELL = 1, DOWN_WIN = 2, DOWN_LW = 3, DOWN_DIA = 4,     // Jacobi: A' as SELL / windowed SELL / local window; diagonal image
+  DOWN_CHEB = 5,                        // Chebyshev from zero, then residual + restriction
+  DOWN_GSB = 6                          // block-hybrid sweep from zero + gsb_residual_restrict (internal: entry 0 reports it as 0)
+};
+enum SweepPath : int {                  // Gauss-Seidel form
+  SWEEP_NONE = 0, SWEEP_MC = 1, SWEEP_MC_ROWLIST = 2, SWEEP_MC_BSELL = 3, SWEEP_GSB = 4, SWEEP_BGSB = 5, SWEEP_BGSB_BC = 6, SWEEP_BGS = 7
+};
+struct LevelPaths {
+  int down = DOWN_NONE;
+  int sweep = SWEEP_NONE;
+  bool plain = true;                    // sm_steps <= 1 && !sm_symm: the smoother is one base step, no ProxySmoother around it
+  bool folded = false;                  // the V-cycle runs Q on the way up (see fold_prolongation)
+  bool jacobi_down() const { return down == DOWN_SELL || down == DOWN_WIN || down == DOWN_LW || down == DOWN_DIA; }
+  bool bgsb() const { return sweep == SWEEP_BGSB || sweep == SWEEP_BGSB_BC; }     // block-hybrid forms: square-block levels,
+  bool hybrid() const { return sweep == SWEEP_GSB || bgsb(); }                    //   ... or any level
+};
+
 struct DevLevel {
+  LevelPaths paths;
   DevCsr tA, tApre, tP, tPT;            // only on tail levels
   DevBuf<int32_t> t_rowlist, t_cptr, t_rowcolor;    // colour-major row list (and the colour of every row) of a Gauss-Seidel tail level
   DevRestrict R;
@@ -358,6 +372,26 @@ struct DevLevel {
     }
   }
 };
+
+// The ONLY place where image presence becomes a path.  Precedence of the down kernels: local window before diagonal image before
+// SELL; of the sweeps: bgsb before gsb before multicolour.  Conditions on call-time arguments (the part of a split level, the fold
+// flag) stay with the callers.
+static void resolve_paths(DevLevel& L) {
+  LevelPaths p;
+  p.plain = L.sm_steps <= 1 && !L.sm_symm;
+  // (a level without rows -- a rank that owns nothing -- is trivially folded: every kernel on it is a no-op)
+  p.folded = p.plain && L.sm_type == AMGX_SM_JACOBI && (L.n == 0 || (!L.Q.empty() && (L.bs > 1 || !L.Apre.empty() || L.dia.on())));
+  if (L.sm_type == AMGX_SM_BGS) p.sweep = SWEEP_BGS;
+  else if (L.sm_type != AMGX_SM_GS) p.sweep = SWEEP_NONE;
+  else if (L.bgsb.on()) p.sweep = L.bgsb.bc ? SWEEP_BGSB_BC : SWEEP_BGSB;
+  else if (L.gsb.on()) p.sweep = SWEEP_GSB;
+  else if (L.gs.n_colors > 0) p.sweep = L.bs == 1 ? SWEEP_MC : (L.gs.bsell_ok ? SWEEP_MC_BSELL : SWEEP_MC_ROWLIST);
+  if (p.plain && L.sm_type == AMGX_SM_JACOBI && !L.RF.empty())
+    p.down = !L.ApreLW.empty() ? DOWN_LW : L.dia.on() ? DOWN_DIA : L.Apre.sell.win ? DOWN_WIN : DOWN_SELL;
+  else if (p.plain && L.sm_type == AMGX_SM_CHEBY && !L.RF.empty()) p.down = DOWN_CHEB;
+  else if (p.plain && p.sweep == SWEEP_GSB && L.gsb.has_split && !L.RG.empty()) p.down = DOWN_GSB;
+  L.paths = p;
+}
 
 // ---------------------------------------------------------------------------------------------------
 // host-side format construction
@@ -1329,14 +1363,12 @@ struct Handle {
   void perm_gather(int l, const double* src, double* dst) {
     const int64_t len = lev[l].len();
     if (!len) return;
-    hipLaunchKernelGGL(perm_gather_kernel, dim3(grid_for(len)), dim3(BLOCK), 0, stream, len, lev[l].bs, perm[l].p, src, dst);
-    HIPCHK(hipGetLastError());
+    launch(perm_gather_kernel, grid_for(len), BLOCK, 0, stream, len, lev[l].bs, perm[l].p, src, dst);
   }
   void perm_scatter(int l, const double* src, double* dst) {
     const int64_t len = lev[l].len();
     if (!len) return;
-    hipLaunchKernelGGL(perm_scatter_kernel, dim3(grid_for(len)), dim3(BLOCK), 0, stream, len, lev[l].bs, perm[l].p, src, dst);
-    HIPCHK(hipGetLastError());
+    launch(perm_scatter_kernel, grid_for(len), BLOCK, 0, stream, len, lev[l].bs, perm[l].p, src, dst);
   }
 
   ~Handle() {
@@ -1378,27 +1410,17 @@ struct Handle {
         if (sp.part == PART_INT) return;             // (not split: everything runs in the boundary part)
         const DevMatrix::Rb& R = M.rb;
         const RbMat V = R.view();
-        if (!R.transposed) {
-          const int grid = grid_for(M.n_rows);
-#define LAUNCH_RBP(BF, BC, DM) hipLaunchKernelGGL((rb_prolong_kernel<BF, BC, DM, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, V, x, y, ep)
-          if (R.dim == 3 && R.bf == 6) LAUNCH_RBP(6, 6, 3);
-          else if (R.dim == 3) LAUNCH_RBP(3, 6, 3);
-          else if (R.dim == 2 && R.bf == 3) LAUNCH_RBP(3, 3, 2);
-          else if (R.dim == 2) LAUNCH_RBP(2, 3, 2);
-          else LAUNCH_RBP(2, 2, 0);
-#undef LAUNCH_RBP
-        } else {
+        // (fine block, coarse block, dimension of Q) = 663, 363, 332, 232, else 220
+        auto run = [&](auto BF, auto BC, auto DM) {
           constexpr int G = 16;
-          const int grid = grid_for(M.n_rows * G);
-#define LAUNCH_RBR(BF, BC, DM) hipLaunchKernelGGL((rb_restrict_kernel<BF, BC, DM, G, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, V, x, y, ep)
-          if (R.dim == 3 && R.bf == 6) LAUNCH_RBR(6, 6, 3);
-          else if (R.dim == 3) LAUNCH_RBR(3, 6, 3);
-          else if (R.dim == 2 && R.bf == 3) LAUNCH_RBR(3, 3, 2);
-          else if (R.dim == 2) LAUNCH_RBR(2, 3, 2);
-          else LAUNCH_RBR(2, 2, 0);
-#undef LAUNCH_RBR
-        }
-        HIPCHK(hipGetLastError());
+          if (!R.transposed) launch(rb_prolong_kernel<BF(), BC(), DM(), EP>, grid_for(M.n_rows), BLOCK, 0, stream, M.n_rows, V, x, y, ep);
+          else launch(rb_restrict_kernel<BF(), BC(), DM(), G, EP>, grid_for(M.n_rows * G), BLOCK, 0, stream, M.n_rows, V, x, y, ep);
+        };
+        if (R.dim == 3 && R.bf == 6) run(Int<6>{}, Int<6>{}, Int<3>{});
+        else if (R.dim == 3) run(Int<3>{}, Int<6>{}, Int<3>{});
+        else if (R.dim == 2 && R.bf == 3) run(Int<3>{}, Int<3>{}, Int<2>{});
+        else if (R.dim == 2) run(Int<2>{}, Int<3>{}, Int<2>{});
+        else run(Int<2>{}, Int<2>{}, Int<0>{});
         return;
       }
     }
@@ -1407,36 +1429,21 @@ struct Handle {
       int64_t a, b;
       unit_range(sp, SELL_WIN, (M.n_rows + SELL_WIN - 1) / SELL_WIN, a, b);
       if (b > a)
-        hipLaunchKernelGGL((sell_win_spmv_kernel<SELL_WIN, EP>), dim3((int)(b - a)), dim3(SELL_WIN), 0, stream, M.n_rows, (int)a, M.sell.view(), M.sell.rowloc.p, x, y, ep);
+        launch(sell_win_spmv_kernel<SELL_WIN, EP>, (int)(b - a), SELL_WIN, 0, stream, M.n_rows, (int)a, M.sell.view(), M.sell.rowloc.p, x, y, ep);
     } else if (M.fmt == FMT_SELL) {
       int64_t a, b;
       unit_range(sp, WAVE / M.lanes, M.n_slices, a, b);
       if (b <= a) return;
       const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-#define LAUNCH_SELL(G) hipLaunchKernelGGL((sell_spmv_kernel<G, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.sell.view(), x, y, ep)
-      switch (M.lanes) {
-        case 1: LAUNCH_SELL(1); break;
-        case 2: LAUNCH_SELL(2); break;
-        case 4: LAUNCH_SELL(4); break;
-        case 8: LAUNCH_SELL(8); break;
-        default: LAUNCH_SELL(16); break;
-      }
-#undef LAUNCH_SELL
+      auto run = [&](auto G) { launch(sell_spmv_kernel<G(), EP>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, M.sell.view(), x, y, ep); };
+      if (!dispatch<1, 2, 4, 8>(M.lanes, run)) run(Int<16>{});       // any other lane count: the 16-lane kernel
     } else if (M.br == 1 && M.bc == 1) {
       int64_t a, b;
       unit_range(sp, 1, M.n_rows, a, b);
       if (b <= a) return;
       const int grid = grid_for((b - a) * M.lanes);
-#define LAUNCH_CSR(G) hipLaunchKernelGGL((csrvec_spmv_kernel<G, EP>), dim3(grid), dim3(BLOCK), 0, stream, a, b, M.rowptr.p, M.col.p, M.val.p, x, y, ep)
-      switch (M.lanes) {
-        case 2: LAUNCH_CSR(2); break;
-        case 4: LAUNCH_CSR(4); break;
-        case 8: LAUNCH_CSR(8); break;
-        case 16: LAUNCH_CSR(16); break;
-        case 32: LAUNCH_CSR(32); break;
-        default: LAUNCH_CSR(64); break;
-      }
-#undef LAUNCH_CSR
+      auto run = [&](auto G) { launch(csrvec_spmv_kernel<G(), EP>, grid, BLOCK, 0, stream, a, b, M.rowptr.p, M.col.p, M.val.p, x, y, ep); };
+      if (!dispatch<2, 4, 8, 16, 32>(M.lanes, run)) run(Int<64>{});  // any other lane count: one wave per row
     } else if constexpr (EP == EP_PRE) {
       throw Err("EP_PRE is only built for scalar matrices");
     } else if (M.fmt == FMT_BSELL) {
@@ -1445,9 +1452,8 @@ struct Handle {
       unit_range(sp, WAVE / M.br, M.n_slices, a, b);
       if (b <= a) return;
       const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-      if (M.br == 6) hipLaunchKernelGGL((bsell_spmv_kernel<6, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(knobs.bsell_xmode), x, y, ep);
-      else if (M.br == 3) hipLaunchKernelGGL((bsell_spmv_kernel<3, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(knobs.bsell_xmode), x, y, ep);
-      else hipLaunchKernelGGL((bsell_spmv_kernel<2, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(knobs.bsell_xmode), x, y, ep);
+      auto run = [&](auto BS) { launch(bsell_spmv_kernel<BS(), EP>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(knobs.bsell_xmode), x, y, ep); };
+      if (!dispatch<6, 3>(M.br, run)) run(Int<2>{});                 // any other block size: the 2 x 2 kernel
     } else if (sp.part == PART_INT) {
       return;                                   // the CSR block formats are not split: everything runs in the boundary part
     } else if (M.br >= 2 && M.bc >= 2 && ((EP != EP_JAC && EP != EP_CHEB) || M.br == M.bc) && (M.br == M.bc || M.nnz >= 6 * M.n_rows)) {
@@ -1458,58 +1464,29 @@ struct Handle {
       const int rpw = WAVE / (M.br * W);
       const int64_t waves = (M.n_rows + rpw - 1) / rpw;
       const int grid = (int)std::max<int64_t>(1, (waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-#define LAUNCH_RL(BR, BC, WW) hipLaunchKernelGGL((bcsr_rowlane_kernel<BR, BC, WW, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep)
-#define LAUNCH_RLW(BR, BC) { if (W == 4) LAUNCH_RL(BR, BC, 4); else if (W == 2) LAUNCH_RL(BR, BC, 2); else LAUNCH_RL(BR, BC, 1); }
+      // key = 10 * br + bc; EP_JAC / EP_CHEB are built for the square shapes only
+      auto run = [&](auto KEY) {
+        constexpr int BR = KEY() / 10, BC = KEY() % 10;
+        auto run_w = [&](auto WW) { launch(bcsr_rowlane_kernel<BR, BC, WW(), EP>, grid, BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep); };
+        if (!dispatch<4, 2>(W, run_w)) run_w(Int<1>{});
+      };
       const int key = M.br * 10 + M.bc;
       if constexpr (EP == EP_JAC || EP == EP_CHEB) {
-        switch (key) {
-          case 22: LAUNCH_RLW(2, 2); break;
-          case 33: LAUNCH_RLW(3, 3); break;
-          case 66: LAUNCH_RLW(6, 6); break;
-          default: throw Err("unsupported block shape");
-        }
+        if (!dispatch<22, 33, 66>(key, run)) throw Err("unsupported block shape");
       } else {
-        switch (key) {
-          case 22: LAUNCH_RLW(2, 2); break;
-          case 33: LAUNCH_RLW(3, 3); break;
-          case 66: LAUNCH_RLW(6, 6); break;
-          case 36: LAUNCH_RLW(3, 6); break;
-          case 63: LAUNCH_RLW(6, 3); break;
-          case 23: LAUNCH_RLW(2, 3); break;
-          case 32: LAUNCH_RLW(3, 2); break;
-          default: throw Err("unsupported block shape " + std::to_string(M.br) + "x" + std::to_string(M.bc));
-        }
+        if (!dispatch<22, 33, 66, 36, 63, 23, 32>(key, run)) throw Err("unsupported block shape " + std::to_string(M.br) + "x" + std::to_string(M.bc));
       }
-#undef LAUNCH_RLW
-#undef LAUNCH_RL
     } else {
       const int G = std::min(M.lanes, 16) < 2 ? 2 : std::min(M.lanes, 16);
       const int grid = grid_for(M.n_rows * G);
-#define LAUNCH_B(BR, BC, GG) hipLaunchKernelGGL((bcsrvec_spmv_kernel<BR, BC, GG, EP>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep)
-#define LAUNCH_BG(BR, BC)                                                                   \
-  switch (G) { case 2: LAUNCH_B(BR, BC, 2); break; case 4: LAUNCH_B(BR, BC, 4); break;     \
-               case 8: LAUNCH_B(BR, BC, 8); break; default: LAUNCH_B(BR, BC, 16); break; }
-      const int key = M.br * 10 + M.bc;
-      switch (key) {
-        case 22: LAUNCH_BG(2, 2); break;
-        case 33: LAUNCH_BG(3, 3); break;
-        case 66: LAUNCH_BG(6, 6); break;
-        case 36: LAUNCH_BG(3, 6); break;
-        case 63: LAUNCH_BG(6, 3); break;
-        case 23: LAUNCH_BG(2, 3); break;
-        case 32: LAUNCH_BG(3, 2); break;
-        case 13: LAUNCH_BG(1, 3); break;
-        case 31: LAUNCH_BG(3, 1); break;
-        case 16: LAUNCH_BG(1, 6); break;
-        case 61: LAUNCH_BG(6, 1); break;
-        case 12: LAUNCH_BG(1, 2); break;
-        case 21: LAUNCH_BG(2, 1); break;
-        default: throw Err("unsupported block shape " + std::to_string(M.br) + "x" + std::to_string(M.bc));
-      }
-#undef LAUNCH_BG
-#undef LAUNCH_B
+      auto run = [&](auto KEY) {                                     // key = 10 * br + bc
+        constexpr int BR = KEY() / 10, BC = KEY() % 10;
+        auto run_g = [&](auto GG) { launch(bcsrvec_spmv_kernel<BR, BC, GG(), EP>, grid, BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep); };
+        if (!dispatch<2, 4, 8>(G, run_g)) run_g(Int<16>{});
+      };
+      if (!dispatch<22, 33, 66, 36, 63, 23, 32, 13, 31, 16, 61, 12, 21>(M.br * 10 + M.bc, run))
+        throw Err("unsupported block shape " + std::to_string(M.br) + "x" + std::to_string(M.bc));
     }
-    HIPCHK(hipGetLastError());
   }
 
   // the smoother passes on the single-precision image: the float instantiations of the two kernel families that carry one
@@ -1520,27 +1497,17 @@ struct Handle {
       unit_range(sp, WAVE / M.lanes, M.n_slices, a, b);
       if (b <= a) return;
       const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-#define LAUNCH_SELL32(G) hipLaunchKernelGGL((sell_spmv_kernel<G, EP, float>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, M.sell.view32(M.val32.p), x, y, ep)
-      switch (M.lanes) {
-        case 1: LAUNCH_SELL32(1); break;
-        case 2: LAUNCH_SELL32(2); break;
-        case 4: LAUNCH_SELL32(4); break;
-        case 8: LAUNCH_SELL32(8); break;
-        default: LAUNCH_SELL32(16); break;
-      }
-#undef LAUNCH_SELL32
+      auto run = [&](auto G) { launch(sell_spmv_kernel<G(), EP, float>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, M.sell.view32(M.val32.p), x, y, ep); };
+      if (!dispatch<1, 2, 4, 8>(M.lanes, run)) run(Int<16>{});       // any other lane count: the 16-lane kernel
     } else if (M.fmt == FMT_BSELL) {
       int64_t a, b;
       unit_range(sp, WAVE / M.br, M.n_slices, a, b);
       if (b <= a) return;
       const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
       const BSellMatT<float> V = M.bsell.view32(M.val32.p, knobs.bsell_xmode);
-      if (M.br == 6) hipLaunchKernelGGL((bsell_spmv_kernel<6, EP, float>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep);
-      else if (M.br == 3) hipLaunchKernelGGL((bsell_spmv_kernel<3, EP, float>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep);
-      else if (M.br == 2) hipLaunchKernelGGL((bsell_spmv_kernel<2, EP, float>), dim3(grid), dim3(BLOCK), 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep);
-      else throw Err("single-precision image: unsupported block size");
+      auto run = [&](auto BS) { launch(bsell_spmv_kernel<BS(), EP, float>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep); };
+      if (!dispatch<6, 3, 2>(M.br, run)) throw Err("single-precision image: unsupported block size");
     } else throw Err("single-precision image on a format that has none");
-    HIPCHK(hipGetLastError());
   }
 
   void mult(const DevMatrix& M, const double* x, double* y, const Span sp = Span()) { spmv_ep<EP_MULT>(M, x, y, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}, sp); }
@@ -1560,16 +1527,8 @@ struct Handle {
   void cheb_first(const DevLevel& L, const double* v, const double* xin, double* xout, double* dout, double c0) {
     if (L.n == 0) return;
     const int grid = grid_for(L.n);
-#define LAUNCH_CF(BS) hipLaunchKernelGGL((cheb_first_kernel<BS>), dim3(grid), dim3(BLOCK), 0, stream, L.n, L.dinv.p, v, xin, xout, dout, c0)
-    switch (L.bs) {
-      case 1: LAUNCH_CF(1); break;
-      case 2: LAUNCH_CF(2); break;
-      case 3: LAUNCH_CF(3); break;
-      case 6: LAUNCH_CF(6); break;
-      default: throw Err("unsupported block size " + std::to_string(L.bs));
-    }
-#undef LAUNCH_CF
-    HIPCHK(hipGetLastError());
+    auto run = [&](auto BS) { launch(cheb_first_kernel<BS()>, grid, BLOCK, 0, stream, L.n, L.dinv.p, v, xin, xout, dout, c0); };
+    if (!dispatch<1, 2, 3, 6>(L.bs, run)) throw Err("unsupported block size " + std::to_string(L.bs));
   }
   // one fused step: xout = xin + d_new, d_new = c1 * d_old + c2 * Dinv * (b - A xin); d_old == nullptr: xin; d_new == nullptr: not stored
   void cheb_step(const DevLevel& L, const double* xin, const double* b, double* xout, double c1, double c2, const double* d_old, double* d_new) {
@@ -1612,13 +1571,11 @@ struct Handle {
 
   void zero(double* v, int64_t n) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(vec_zero_kernel, dim3(grid_for((n + 1) / 2)), dim3(BLOCK), 0, stream, n, v);
-    HIPCHK(hipGetLastError());
+    launch(vec_zero_kernel, grid_for((n + 1) / 2), BLOCK, 0, stream, n, v);
   }
   void copy(double* dst, const double* src, int64_t n) {
     if (n <= 0 || dst == src) return;
-    hipLaunchKernelGGL(vec_copy_kernel, dim3(grid_for((n + 1) / 2)), dim3(BLOCK), 0, stream, n, src, dst);
-    HIPCHK(hipGetLastError());
+    launch(vec_copy_kernel, grid_for((n + 1) / 2), BLOCK, 0, stream, n, src, dst);
   }
 
   // x (+)= omega * dinv * v
@@ -1627,24 +1584,16 @@ struct Handle {
     if (rows < 0) rows = L.n;
     if (rows == 0) return;
     const int grid = grid_for(rows);
-#define LAUNCH_D(BS)                                                                                                   \
-  if (add) hipLaunchKernelGGL((diag_apply_kernel<BS, true>), dim3(grid), dim3(BLOCK), 0, stream, rows, L.dinv.p, v, x, L.omega); \
-  else hipLaunchKernelGGL((diag_apply_kernel<BS, false>), dim3(grid), dim3(BLOCK), 0, stream, rows, L.dinv.p, v, x, L.omega)
-    switch (L.bs) {
-      case 1: LAUNCH_D(1); break;
-      case 2: LAUNCH_D(2); break;
-      case 3: LAUNCH_D(3); break;
-      case 6: LAUNCH_D(6); break;
-      default: throw Err("unsupported block size " + std::to_string(L.bs));
-    }
-#undef LAUNCH_D
-    HIPCHK(hipGetLastError());
+    auto run = [&](auto BS) {
+      if (add) launch(diag_apply_kernel<BS(), true>, grid, BLOCK, 0, stream, rows, L.dinv.p, v, x, L.omega);
+      else launch(diag_apply_kernel<BS(), false>, grid, BLOCK, 0, stream, rows, L.dinv.p, v, x, L.omega);
+    };
+    if (!dispatch<1, 2, 3, 6>(L.bs, run)) throw Err("unsupported block size " + std::to_string(L.bs));
   }
 
   void axpy(int64_t n, double s, const double* x, double* y) {
     if (!n) return;
-    hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, stream, n, s, x, y);
-    HIPCHK(hipGetLastError());
+    launch(axpy_kernel, grid_for(n), BLOCK, 0, stream, n, s, x, y);
   }
 
   // one multicolour GS sweep (RHS form), forward: colours ascending, backward: descending
@@ -1654,7 +1603,7 @@ struct Handle {
     Range rg("GSS3<bs=" + std::to_string(L.bs) + ">::SmoothRHS");
     const DevGS& g = L.gs;
     const DevMatrix::Sell& copy = (lower_only && g.has_split) ? g.lower : g.sell;
-    if (L.gsb.on() || L.bgsb.on()) throw Err("gs_sweep: the level uses the block-hybrid form");
+    if (L.paths.hybrid()) throw Err("gs_sweep: the level uses the block-hybrid form");
     if (g.n_colors == 0 && L.n > 0) throw Err("Gauss-Seidel requested but the level has no colouring");
     if (cend < 0 || cend > g.n_colors) cend = g.n_colors;
     for (int q = cbeg; q < cend; ++q) {
@@ -1663,23 +1612,15 @@ struct Handle {
         const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
         if (s1 == s0) continue;
         const int grid = (s1 - s0 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-#define LAUNCH_GSC(GG) hipLaunchKernelGGL((gs_color_kernel<GG>), dim3(grid), dim3(BLOCK), 0, stream, s0, s1, copy.view(), g.rowid.p, L.dinv.p, b, x)
-        switch (g.lanes) {
-          case 1: LAUNCH_GSC(1); break;
-          case 2: LAUNCH_GSC(2); break;
-          case 4: LAUNCH_GSC(4); break;
-          case 8: LAUNCH_GSC(8); break;
-          default: LAUNCH_GSC(16); break;
-        }
-#undef LAUNCH_GSC
+        auto run = [&](auto GG) { launch(gs_color_kernel<GG()>, grid, BLOCK, 0, stream, s0, s1, copy.view(), g.rowid.p, L.dinv.p, b, x); };
+        if (!dispatch<1, 2, 4, 8>(g.lanes, run)) run(Int<16>{});     // any other lane count: the 16-lane kernel
       } else if (g.bsell_ok) {
         const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
         if (s1 == s0) continue;
         const int grid = (s1 - s0 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
         const BSellMat BM = (lower_only && g.bsplit) ? g.blower.bsell.view(knobs.bsell_xmode) : g.bcopy.bsell.view(knobs.bsell_xmode);
-        if (L.bs == 6) hipLaunchKernelGGL((bgs_bsell_color_kernel<6>), dim3(grid), dim3(BLOCK), 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x);
-        else if (L.bs == 3) hipLaunchKernelGGL((bgs_bsell_color_kernel<3>), dim3(grid), dim3(BLOCK), 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x);
-        else hipLaunchKernelGGL((bgs_bsell_color_kernel<2>), dim3(grid), dim3(BLOCK), 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x);
+        auto run = [&](auto BS) { launch(bgs_bsell_color_kernel<BS()>, grid, BLOCK, 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x); };
+        if (!dispatch<6, 3>(L.bs, run)) run(Int<2>{});               // any other block size: the 2 x 2 kernel
       } else {
         const int r0 = g.color_row_ptr[c], r1 = g.color_row_ptr[c + 1];
         if (r1 == r0) continue;
@@ -1688,18 +1629,12 @@ struct Handle {
         const int rpw = WAVE / (L.bs * W);
         const int64_t waves = ((int64_t)(r1 - r0) + rpw - 1) / rpw;
         const int grid = (int)std::max<int64_t>(1, (waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-#define LAUNCH_GS(BS, WW) hipLaunchKernelGGL((bgs_color_kernel<BS, WW>), dim3(grid), dim3(BLOCK), 0, stream, r0, r1, g.rowlist.p, L.A.rowptr.p, L.A.col.p, L.A.val.p, L.dinv.p, b, x)
-#define LAUNCH_GSW(BS) { if (W == 8) LAUNCH_GS(BS, 8); else if (W == 4) LAUNCH_GS(BS, 4); else if (W == 2) LAUNCH_GS(BS, 2); else LAUNCH_GS(BS, 1); }
-        switch (L.bs) {
-          case 2: LAUNCH_GSW(2); break;
-          case 3: LAUNCH_GSW(3); break;
-          case 6: LAUNCH_GSW(6); break;
-          default: throw Err("unsupported block size for GS");
-        }
-#undef LAUNCH_GSW
-#undef LAUNCH_GS
+        auto run = [&](auto BS) {
+          auto run_w = [&](auto WW) { launch(bgs_color_kernel<BS(), WW()>, grid, BLOCK, 0, stream, r0, r1, g.rowlist.p, L.A.rowptr.p, L.A.col.p, L.A.val.p, L.dinv.p, b, x); };
+          if (!dispatch<8, 4, 2>(W, run_w)) run_w(Int<1>{});
+        };
+        if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("unsupported block size for GS");
       }
-      HIPCHK(hipGetLastError());
     }
   }
 
@@ -1718,20 +1653,28 @@ struct Handle {
     GsbArgs a{g.rowid.p, g.slotcolor.p, L.dinv.p, b, g.n_colors, dir, lw ? g.flw_cptr.p : nullptr, lw ? g.flw_ccol.p : nullptr};
     const SellMat M = lw ? g.fullLW.view() : copy.view();
     const bool narrow = fz && &copy == &g.lowin && g.narrow;
-#define LAUNCH_GSB3(TT, GG, ZZ, WW) hipLaunchKernelGGL((gsb_sweep_kernel<TT, GG, ZZ, WW>), dim3(blk1 - blk0), dim3(TT), 0, stream, L.n, blk0, M, a, xin, xout)
     const bool mid = !fz && &copy == &g.full && g.mid;
-#define LAUNCH_GSBL(TT, GG, WW) hipLaunchKernelGGL((gsb_sweep_kernel<TT, GG, false, WW, true>), dim3(blk1 - blk0), dim3(TT), 0, stream, L.n, blk0, M, a, xin, xout)
-#define LAUNCH_GSB2(TT, GG) { if (narrow) LAUNCH_GSB3(TT, GG, true, 2); else if (fz) LAUNCH_GSB3(TT, GG, true, GSB_WP); \
-                              else if (lw && mid && GG > 1) LAUNCH_GSBL(TT, (GG > 1 ? GG : 2), 5); else if (lw && GG > 1) LAUNCH_GSBL(TT, (GG > 1 ? GG : 2), GSB_WP); \
-                              else if (mid && GG > 1) LAUNCH_GSB3(TT, (GG > 1 ? GG : 2), false, 5); else LAUNCH_GSB3(TT, GG, false, GSB_WP); }
-#define LAUNCH_GSB(TT) switch (g.G) { case 1: LAUNCH_GSB2(TT, 1); break; case 2: LAUNCH_GSB2(TT, 2); break; case 4: LAUNCH_GSB2(TT, 4); break; \
-                                      case 8: LAUNCH_GSB2(TT, 8); break; default: LAUNCH_GSB2(TT, 16); break; }
-    if (g.TH == 256) LAUNCH_GSB(256) else if (g.TH == 512) LAUNCH_GSB(512) else LAUNCH_GSB(1024)
-#undef LAUNCH_GSB
-#undef LAUNCH_GSB2
-#undef LAUNCH_GSBL
-#undef LAUNCH_GSB3
-    HIPCHK(hipGetLastError());
+    // <workgroup size, lanes per row, from zero, entries per lane and pass, local-window image>; the mid-width and local-window
+    // forms exist for more than one lane per row only
+    auto run = [&](auto TT) {
+      auto run_g = [&](auto GG) {
+        auto sweep = [&](auto ZZ, auto WW, auto LW) {
+          launch(gsb_sweep_kernel<TT(), GG(), ZZ(), WW(), LW()>, blk1 - blk0, TT(), 0, stream, L.n, blk0, M, a, xin, xout);
+        };
+        constexpr std::false_type no{};
+        constexpr std::true_type yes{};
+        if (narrow) return sweep(yes, Int<2>{}, no);
+        if (fz) return sweep(yes, Int<GSB_WP>{}, no);
+        if constexpr (GG() > 1) {
+          if (lw && mid) return sweep(no, Int<5>{}, yes);
+          if (lw) return sweep(no, Int<GSB_WP>{}, yes);
+          if (mid) return sweep(no, Int<5>{}, no);
+        }
+        sweep(no, Int<GSB_WP>{}, no);
+      };
+      if (!dispatch<1, 2, 4, 8>(g.G, run_g)) run_g(Int<16>{});       // any other lane count: the 16-lane kernel
+    };
+    if (!dispatch<256, 512>(g.TH, run)) run(Int<1024>{});            // any other workgroup size: 1024
   }
 
   // one block-hybrid Gauss-Seidel sweep on a square-block level (bgsb_sweep_kernel): ONE launch; xin == nullptr: from x = 0
@@ -1742,15 +1685,13 @@ struct Handle {
     const size_t lds = (size_t)2 * g.BB * L.bs * sizeof(double) + (size_t)g.BB * sizeof(int);
     // forward: colour phases over the couplings to lower colours, the upper ones stream with the sweep-start values; backward: reversed
     const BSellMat IN = dir == 0 ? g.in.bsell.view(knobs.bsell_xmode) : g.upin.bsell.view(knobs.bsell_xmode), OTH = dir == 0 ? g.upin.bsell.view(knobs.bsell_xmode) : g.in.bsell.view(knobs.bsell_xmode);
-#define LAUNCH_BGSB(BS_, MODE_, OFF_, LIST_, B0_, NB_, XIN_) hipLaunchKernelGGL((bgsb_sweep_kernel<BS_, MODE_>), dim3(NB_), dim3(BLOCK), lds, stream, g.BB, B0_, LIST_, \
-                                               g.blk_ptr.p, g.blk_rows.p, OFF_, g.off_ptr.p, IN, OTH, g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, XIN_, xout)
-#define LAUNCH_BGSB_BS(MODE_, OFF_, LIST_, B0_, NB_, XIN_)                                       \
-    switch (L.bs) {                                                                              \
-      case 2: LAUNCH_BGSB(2, MODE_, OFF_, LIST_, B0_, NB_, XIN_); break;                         \
-      case 3: LAUNCH_BGSB(3, MODE_, OFF_, LIST_, B0_, NB_, XIN_); break;                         \
-      case 6: LAUNCH_BGSB(6, MODE_, OFF_, LIST_, B0_, NB_, XIN_); break;                         \
-      default: throw Err("block-hybrid Gauss-Seidel: unsupported block size");                   \
-    }
+    auto sweep = [&](auto MODE, const BSellMat& OFF, const int32_t* list, int b0, int nb, const double* x0) {
+      auto run = [&](auto BS) {
+        launch(bgsb_sweep_kernel<BS(), MODE()>, nb, BLOCK, lds, stream, g.BB, b0, list, g.blk_ptr.p, g.blk_rows.p, OFF, g.off_ptr.p, IN, OTH,
+               g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, x0, xout);
+      };
+      if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("block-hybrid Gauss-Seidel: unsupported block size");
+    };
     if (g.bc) {
       // block-coloured form: one in-place launch per block colour; from zero (xin == nullptr) the first colour reads nothing
       // outside its blocks, the later ones the finished blocks of lower colours through `offlo` (lower_only: the split exists)
@@ -1764,11 +1705,10 @@ struct Handle {
         const int c = dir ? g.n_bcolors - 1 - q : q;
         const int b0 = g.bc_ptr[c], nb = g.bc_ptr[c + 1] - b0;
         if (nb <= 0) continue;
-        if (!fz) { LAUNCH_BGSB_BS(0, OFFA, g.blk_list.p, b0, nb, (const double*)xout); }
-        else if (q == 0) { LAUNCH_BGSB_BS(1, OFFL, g.blk_list.p, b0, nb, (const double*)nullptr); }
-        else { LAUNCH_BGSB_BS(2, OFFL, g.blk_list.p, b0, nb, (const double*)xout); }
+        if (!fz) sweep(Int<0>{}, OFFA, g.blk_list.p, b0, nb, xout);
+        else if (q == 0) sweep(Int<1>{}, OFFL, g.blk_list.p, b0, nb, nullptr);
+        else sweep(Int<2>{}, OFFL, g.blk_list.p, b0, nb, xout);
       }
-      HIPCHK(hipGetLastError());
       return;
     }
     if (blk1 < 0 || blk1 > g.n_blocks) blk1 = g.n_blocks;
@@ -1777,11 +1717,8 @@ struct Handle {
     (void)lower_only;
     const BSellMat OFF = g.off.bsell.view(knobs.bsell_xmode);
     const bool fz = xin == nullptr;
-    if (fz) { LAUNCH_BGSB_BS(1, OFF, (const int32_t*)nullptr, blk0, blk1 - blk0, xin); }
-    else { LAUNCH_BGSB_BS(0, OFF, (const int32_t*)nullptr, blk0, blk1 - blk0, xin); }
-#undef LAUNCH_BGSB_BS
-#undef LAUNCH_BGSB
-    HIPCHK(hipGetLastError());
+    if (fz) sweep(Int<1>{}, OFF, nullptr, blk0, blk1 - blk0, xin);
+    else sweep(Int<0>{}, OFF, nullptr, blk0, blk1 - blk0, xin);
   }
 
   // one block Gauss-Seidel sweep: colours of the block graph ascending (forward) or descending (backward)
@@ -1797,19 +1734,19 @@ struct Handle {
       const double avg = L.A.n_rows ? (double)L.A.nnz / (double)L.A.n_rows : 0.0;
       const int G = avg > 30.0 ? (g.max_m * 16 <= 1024 ? 16 : 8) : 4;
       const int TH = g.max_m * G <= 256 ? 256 : (g.max_m * G <= 512 ? 512 : 1024);
-#define LAUNCH_BGS2(BS, TT, GG) hipLaunchKernelGGL((bgs_block_kernel<BS, TT, GG>), dim3(b1 - b0), dim3(TT), 0, stream, b0, g.blocklist.p, g.block_ptr.p, g.block_rows.p, g.rowptr.p, g.col.p, g.val.p, g.dinv_ptr.p, g.dinv.p, b, x)
-#define LAUNCH_BGS(BS) { if (G == 4 && TH == 256) LAUNCH_BGS2(BS, 256, 4); else if (G == 4 && TH == 512) LAUNCH_BGS2(BS, 512, 4); else if (G == 4) LAUNCH_BGS2(BS, 1024, 4); \
-                         else if (G == 8 && TH <= 512) LAUNCH_BGS2(BS, 512, 8); else if (G == 8) LAUNCH_BGS2(BS, 1024, 8); else LAUNCH_BGS2(BS, 1024, 16); }
-      switch (L.bs) {
-        case 1: LAUNCH_BGS(1); break;
-        case 2: LAUNCH_BGS(2); break;
-        case 3: LAUNCH_BGS(3); break;
-        case 6: LAUNCH_BGS(6); break;
-        default: throw Err("unsupported block size for block Gauss-Seidel");
-      }
-#undef LAUNCH_BGS2
-#undef LAUNCH_BGS
-      HIPCHK(hipGetLastError());
+      auto run = [&](auto BS) {
+        auto block = [&](auto TT, auto GG) {
+          launch(bgs_block_kernel<BS(), TT(), GG()>, b1 - b0, TT(), 0, stream, b0, g.blocklist.p, g.block_ptr.p, g.block_rows.p, g.rowptr.p, g.col.p, g.val.p,
+                 g.dinv_ptr.p, g.dinv.p, b, x);
+        };
+        if (G == 4 && TH == 256) block(Int<256>{}, Int<4>{});
+        else if (G == 4 && TH == 512) block(Int<512>{}, Int<4>{});
+        else if (G == 4) block(Int<1024>{}, Int<4>{});
+        else if (G == 8 && TH <= 512) block(Int<512>{}, Int<8>{});
+        else if (G == 8) block(Int<1024>{}, Int<8>{});
+        else block(Int<1024>{}, Int<16>{});
+      };
+      if (!dispatch<1, 2, 3, 6>(L.bs, run)) throw Err("unsupported block size for block Gauss-Seidel");
     }
   }
 
@@ -1818,26 +1755,22 @@ struct Handle {
     const DevLevel& L = lev.back();
     if (clev != AMGX_CLEV_INV || coarse_n == 0) { zero(x, L.len()); return; }   // amg_matrix.cpp:242-246
     const int grid = (int)((coarse_n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-    if (coarse_ld != coarse_n) hipLaunchKernelGGL(dense_op_gemv_kernel, dim3(grid), dim3(BLOCK), 0, stream, (int)coarse_n, (int)coarse_ld, coarse_inv.p, rhs, x);
-    else hipLaunchKernelGGL(dense_gemv_kernel, dim3(grid), dim3(BLOCK), 0, stream, (int)coarse_n, coarse_inv.p, rhs, x);
-    HIPCHK(hipGetLastError());
+    if (coarse_ld != coarse_n) launch(dense_op_gemv_kernel, grid, BLOCK, 0, stream, (int)coarse_n, (int)coarse_ld, coarse_inv.p, rhs, x);
+    else launch(dense_gemv_kernel, grid, BLOCK, 0, stream, (int)coarse_n, coarse_inv.p, rhs, x);
   }
 
   // adds the partial sums of the chunk-local restriction of level l (restrict_chunk_kernel and the fused down kernels leave
   // them in R.part) into the right-hand side of level l + 1
   void restrict_sum(int l, const DevRestrict& R, double* b_coarse) {
-    hipLaunchKernelGGL(restrict_sum_kernel, dim3(grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G)), dim3(BLOCK), 0, stream, lev[l + 1].n, R.optr.p,
-                       R.oidx.p, R.part.p, b_coarse);
+    launch(restrict_sum_kernel, grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G), BLOCK, 0, stream, lev[l + 1].n, R.optr.p, R.oidx.p, R.part.p, b_coarse);
   }
 
   void transfer_f2c(int l, const double* xf, double* xc) {                                               // dof_map.cpp:636-654
     Range rg("ProlMap::TransferF2C");
     const DevRestrict& R = lev[l].R;
     if (R.empty()) { mult(lev[l].PT, xf, xc); return; }
-    hipLaunchKernelGGL(restrict_chunk_kernel, dim3(R.n_chunks), dim3(BLOCK), 0, stream, lev[l].n, R.chunk_slot.p, R.slot_ptr.p,
-                       R.w.p, R.fi.p, xf, R.part.p, R.dest.p);
+    launch(restrict_chunk_kernel, R.n_chunks, BLOCK, 0, stream, lev[l].n, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, xf, R.part.p, R.dest.p);
     restrict_sum(l, R, xc);
-    HIPCHK(hipGetLastError());
   }
   void add_c2f(int l, double fac, double* xf, const double* xc) { Range rg("ProlMap::TransferC2F"); mult_add(lev[l].P, fac, xc, xf, xf); }   // dof_map.cpp:697-709
 
@@ -1859,14 +1792,14 @@ struct Handle {
       // row-transpose scatters when asked for it; here: gather (RHS) form + one residual SpMV, same x and res
       bgs_sweep(L, dir, x, b);
       if (update_res) residual(L.A, x, b, res);
-    } else if (L.bgsb.on()) {
-      if (L.bgsb.bc) bgsb_sweep(L, dir, x, x, b);           // block-coloured form: in place
-      else {
-        copy(L.tmp.p, x, L.ext_len());
-        bgsb_sweep(L, dir, L.tmp.p, x, b);
-      }
+    } else if (L.paths.sweep == SWEEP_BGSB_BC) {
+      bgsb_sweep(L, dir, x, x, b);                          // block-coloured form: in place
       if (update_res) residual(L.A, x, b, res);
-    } else if (L.gsb.on()) {
+    } else if (L.paths.sweep == SWEEP_BGSB) {
+      copy(L.tmp.p, x, L.ext_len());
+      bgsb_sweep(L, dir, L.tmp.p, x, b);
+      if (update_res) residual(L.A, x, b, res);
+    } else if (L.paths.sweep == SWEEP_GSB) {
       // block-hybrid sweep (out of place: the off-block values are those from the start of the sweep)
       copy(L.tmp.p, x, L.ext_len());
       gsb_sweep(L, dir, L.gsb.full, L.tmp.p, x, b);
@@ -1898,25 +1831,34 @@ struct Handle {
     }
   }
 
-  bool plain(const DevLevel& L) const { return L.sm_steps <= 1 && !L.sm_symm; }
-  // (a level without rows -- a rank that owns nothing -- is trivially folded: every kernel on it is a no-op)
-  bool folded(const DevLevel& L) const { return plain(L) && L.sm_type == AMGX_SM_JACOBI && (L.n == 0 || (!L.Q.empty() && (L.bs > 1 || !L.Apre.empty() || L.dia.on()))); }
+  // (accessors of what resolve_paths decided: multi.hpp and dist.hpp ask through the handle)
+  bool plain(const DevLevel& L) const { return L.paths.plain; }
+  bool folded(const DevLevel& L) const { return L.paths.folded; }
+  // HIP events of amgx_time_op (ops 8 and 9) around the launches of `body`
+  template <class F>
+  void probed(bool on, F&& body) {
+    if (on) HIPCHK(hipEventRecord(probe_e0, stream));
+    body();
+    if (on) HIPCHK(hipEventRecord(probe_e1, stream));
+  }
 
   // pre-smoothing step of the cycles: x = 0; r = b; Smooth(x, b, r, 1, 1, 1)   (amg_matrix.cpp:193-206)
   // fold (only with folded(L)): x receives z = x + omega*Dinv*r, to be completed by post_smooth(..., fold = true)
   void pre_smooth(DevLevel& L, double* x, const double* b, double* r, bool fold = false, const Span sp = Span()) {
-    if (plain(L) && L.sm_type == AMGX_SM_JACOBI && !L.Apre.empty()) {
+    const LevelPaths& P = L.paths;
+    const bool jacobi = P.plain && L.sm_type == AMGX_SM_JACOBI;
+    if (jacobi && !L.Apre.empty()) {
       // one pass: r = b - A' b, x = omega * Dinv * b   (A' = A * omega*Dinv built at create time)
       spmv_ep<EP_PRE>(L.Apre, b, r, EpArgs{b, nullptr, L.dinv.p, L.omega, x, ep_nt | (fold ? EPF_FOLD : 0)}, sp);
     } else if (sp.part == PART_INT) {
       return;                                  // the other forms are not split: they run completely in the boundary part
-    } else if (plain(L) && L.sm_type == AMGX_SM_JACOBI && L.ncols > L.n && !fold) {
+    } else if (jacobi && L.ncols > L.n && !fold) {
       // rank-partitioned level without a pre-smoothing image (block levels): x = omega * Dinv * b is needed on the ghost
       // rows too (their b and dinv entries came with the exchange / the setup), so it is formed in the gathered buffer
       diag_apply(L, b, L.tmp.p, false, L.ncols);
       residual(L.A, L.tmp.p, b, r);
       copy(x, L.tmp.p, L.len());
-    } else if (plain(L) && L.sm_type == AMGX_SM_JACOBI) {
+    } else if (jacobi) {
       if (fold && L.bs > 1) {
         // x_pre = omega * Dinv * b into tmp; then ONE pass: r = b - A x_pre and z = x_pre + omega * Dinv * r
         diag_apply(L, b, L.tmp.p, false);
@@ -1926,15 +1868,15 @@ struct Handle {
         residual(L.A, x, b, r);              // r = b - A x
         if (fold) diag_apply(L, r, x, true); // z = x + omega * Dinv * r  (folded post-smoothing, see fold_prolongation)
       }
-    } else if (plain(L) && L.sm_type == AMGX_SM_CHEBY) {
+    } else if (P.plain && L.sm_type == AMGX_SM_CHEBY) {
       cheb_smooth(L, x, x, b, r, false, true, true);     // from zero: step 1 reads b, no SpMV
-    } else if (plain(L) && L.sm_type == AMGX_SM_GS && L.bgsb.on()) {
+    } else if (P.plain && P.bgsb()) {
       // forward block-hybrid sweep from x = 0 (nothing outside the workgroup's rows is read), then the residual; with the
       // split copies A is read once in total: r = rest * x (see DevBGSB)
       if (L.bgsb.has_split) {
         bgsb_sweep(L, 0, nullptr, x, b, true);
         mult(L.bgsb.rest, x, r);
-      } else if (L.bgsb.bc) {
+      } else if (P.sweep == SWEEP_BGSB_BC) {
         zero(x, L.len());                      // (pseudo-inverted diagonal blocks: no split images)
         bgsb_sweep(L, 0, x, x, b);
         residual(L.A, x, b, r);
@@ -1942,7 +1884,7 @@ struct Handle {
         bgsb_sweep(L, 0, nullptr, x, b);
         residual(L.A, x, b, r);
       }
-    } else if (plain(L) && L.sm_type == AMGX_SM_GS && L.gsb.on()) {
+    } else if (P.plain && P.sweep == SWEEP_GSB) {
       // forward block-hybrid sweep from x = 0: inside a block only couplings to lower colours contribute (all other
       // values are still 0); afterwards (b - L_in x)_k = x_k / dinv_k on every swept row, hence
       // r = b - A x = (1/dinv - a_kk) .* x - (A - L_in - D) x = c .* x - rest x
@@ -1953,7 +1895,7 @@ struct Handle {
         gsb_sweep(L, 0, L.gsb.full, nullptr, x, b);
         residual(L.A, x, b, r);
       }
-    } else if (plain(L) && L.sm_type == AMGX_SM_GS && L.gs.has_split && L.bs == 1) {
+    } else if (P.plain && L.sm_type == AMGX_SM_GS && L.gs.has_split && L.bs == 1) {
       // forward sweep from x = 0: only couplings to lower colours contribute; afterwards b - L x - D x = 0 on every
       // swept row, hence r = -U x (r on non-free rows is not needed: their prolongation rows are empty)
       zero(x, L.len());
@@ -1961,17 +1903,9 @@ struct Handle {
       gs_sweep(L, 0, x, b, true);
       const DevGS& g = L.gs;
       const int grid = (g.n_slices_total + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-#define LAUNCH_UR(GG) hipLaunchKernelGGL((gs_upper_residual_kernel<GG>), dim3(grid), dim3(BLOCK), 0, stream, g.n_slices_total, g.upper.view(), g.rowid.p, x, r)
-      switch (g.lanes) {
-        case 1: LAUNCH_UR(1); break;
-        case 2: LAUNCH_UR(2); break;
-        case 4: LAUNCH_UR(4); break;
-        case 8: LAUNCH_UR(8); break;
-        default: LAUNCH_UR(16); break;
-      }
-#undef LAUNCH_UR
-      HIPCHK(hipGetLastError());
-    } else if (plain(L) && L.sm_type == AMGX_SM_GS && L.gs.bsplit && L.bs > 1) {
+      auto run = [&](auto GG) { launch(gs_upper_residual_kernel<GG()>, grid, BLOCK, 0, stream, g.n_slices_total, g.upper.view(), g.rowid.p, x, r); };
+      if (!dispatch<1, 2, 4, 8>(g.lanes, run)) run(Int<16>{});       // any other lane count: the 16-lane kernel
+    } else if (P.plain && L.sm_type == AMGX_SM_GS && L.gs.bsplit && L.bs > 1) {
       // block levels, same identity: forward sweep over the lower-colour couplings, then r_B = -(U x)_B in one launch
       zero(x, L.len());
       zero(r, L.len());
@@ -1980,11 +1914,9 @@ struct Handle {
       const int ns = g.bupper.n_slices;
       const int grid = (ns + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
       const BSellMat UM = g.bupper.bsell.view(knobs.bsell_xmode);
-      if (L.bs == 6) hipLaunchKernelGGL((bgs_bsell_upper_residual_kernel<6>), dim3(grid), dim3(BLOCK), 0, stream, ns, UM, g.rowid.p, x, r);
-      else if (L.bs == 3) hipLaunchKernelGGL((bgs_bsell_upper_residual_kernel<3>), dim3(grid), dim3(BLOCK), 0, stream, ns, UM, g.rowid.p, x, r);
-      else hipLaunchKernelGGL((bgs_bsell_upper_residual_kernel<2>), dim3(grid), dim3(BLOCK), 0, stream, ns, UM, g.rowid.p, x, r);
-      HIPCHK(hipGetLastError());
-    } else if (plain(L) && L.sm_type == AMGX_SM_GS) {
+      auto run = [&](auto BS) { launch(bgs_bsell_upper_residual_kernel<BS()>, grid, BLOCK, 0, stream, ns, UM, g.rowid.p, x, r); };
+      if (!dispatch<6, 3>(L.bs, run)) run(Int<2>{});                 // any other block size: the 2 x 2 kernel
+    } else if (P.plain && L.sm_type == AMGX_SM_GS) {
       zero(x, L.len());
       gs_sweep(L, 0, x, b);
       residual(L.A, x, b, r);
@@ -2000,144 +1932,129 @@ struct Handle {
   // everything that needs all rows (partial-sum reduction / P^T gather)
   void pre_smooth_restrict(int l, double* x, const double* b, double* r, double* b_coarse, bool fold = false, const Span sp = Span()) {
     DevLevel& L = lev[l];
-    if (fold && !folded(L)) throw Err("pre_smooth_restrict: level has no folded prolongation");
+    if (fold && !L.paths.folded) throw Err("pre_smooth_restrict: level has no folded prolongation");
     const int epf = ep_nt | (fold ? EPF_FOLD : 0);
-    if (plain(L) && L.sm_type == AMGX_SM_JACOBI && !L.RF.empty() && !L.ApreLW.empty()) {
-      // long-row level: the local-window image (gathers from LDS), chunks of 512 / lanes rows
-      const DevRestrict& R = L.RF;
-      const int nch = (L.ApreLW.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
-      if (nch != R.n_chunks) throw Err("fused restriction (local-window image): chunk / slice mismatch");
-      int64_t ca, cb;
-      const int LG = L.ApreLW.lanes;
-      unit_range(sp, 512 / LG, nch, ca, cb);
-      const int grid = (int)(cb - ca), c0 = (int)ca;
-      const bool probe = probe_level == l && probe_kind == 8 && probe_e0 && sp.part != PART_BND;
-      if (probe) HIPCHK(hipEventRecord(probe_e0, stream));
-      if (grid > 0) {
-#define LAUNCH_LW(EPT_, G_) hipLaunchKernelGGL((sell_lw_pre_restrict_kernel<EPT_, G_, 0>), dim3(grid), dim3(512), 0, stream, L.ApreLW.n_rows, c0, L.ApreLW.n_slices, \
-                           L.ApreLW.sell.view(), L.lw_cptr.p, L.lw_ccol.p, b, L.dinv.p, L.omega, epf, x, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p)
-        if (LG == 2) { if (R.ept == 2) LAUNCH_LW(2, 2); else LAUNCH_LW(4, 2); }
-        else { if (R.ept == 2) LAUNCH_LW(2, 4); else LAUNCH_LW(4, 4); }
-#undef LAUNCH_LW
+    const DevRestrict& R = L.RF;
+    // (rank-partitioned level: the events go around the interior launch, which runs beside the halo exchange)
+    const bool probe = probe_level == l && probe_kind == 8 && probe_e0 && sp.part != PART_BND;
+    switch (L.paths.down) {
+      case DOWN_LW: {
+        // long-row level: the local-window image (gathers from LDS), chunks of 512 / lanes rows
+        const int nch = (L.ApreLW.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
+        if (nch != R.n_chunks) throw Err("fused restriction (local-window image): chunk / slice mismatch");
+        int64_t ca, cb;
+        const int LG = L.ApreLW.lanes;
+        unit_range(sp, 512 / LG, nch, ca, cb);
+        const int grid = (int)(cb - ca), c0 = (int)ca;
+        probed(probe, [&] {
+          if (grid <= 0) return;
+          auto run_g = [&](auto G) {
+            auto run = [&](auto EPT) {
+              launch(sell_lw_pre_restrict_kernel<EPT(), G(), 0>, grid, 512, 0, stream, L.ApreLW.n_rows, c0, L.ApreLW.n_slices, L.ApreLW.sell.view(), L.lw_cptr.p,
+                     L.lw_ccol.p, b, L.dinv.p, L.omega, epf, x, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+            };
+            if (!dispatch<2>(R.ept, run)) run(Int<4>{});
+          };
+          if (!dispatch<2>(LG, run_g)) run_g(Int<4>{});
+        });
+        if (!skip_rsum && sp.part != PART_INT) restrict_sum(l, R, b_coarse);
+        return;
       }
-      if (probe) HIPCHK(hipEventRecord(probe_e1, stream));
-      if (!skip_rsum && sp.part != PART_INT)
-        restrict_sum(l, R, b_coarse);
-      HIPCHK(hipGetLastError());
-      return;
-    }
-    if (plain(L) && L.sm_type == AMGX_SM_JACOBI && !L.RF.empty() && L.dia.on()) {
-      // symmetric diagonal image: 512-row chunks, one thread per row, whole level in one launch
-      const DevRestrict& R = L.RF;
-      const int ns = (int)((L.n + WAVE - 1) / WAVE);
-      const int nch = R.slice_list.n ? R.n_chunks : (ns + (512 / WAVE) - 1) / (512 / WAVE);
-      if (nch != R.n_chunks || L.fused_block != 512) throw Err("fused restriction (diagonal image): chunk / slice mismatch");
-      if (sp.part != PART_ALL) throw Err("fused restriction (diagonal image): the level is not split into interior / boundary parts");
-      const bool probe = probe_level == l && probe_kind == 8 && probe_e0;
-      if (probe) HIPCHK(hipEventRecord(probe_e0, stream));
-      if (nch > 0) {
-#define LAUNCH_DIA(K_, EPT_) hipLaunchKernelGGL((dia_pre_restrict_kernel<K_, EPT_>), dim3(nch), dim3(512), 0, stream, (int)L.n, ns, L.dia.view(), b, L.dinv.p, \
-                             L.omega, epf, x, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, (const int32_t*)R.slice_list.p)
-#define LAUNCH_DIA_K(K_) { if (R.ept == 4) LAUNCH_DIA(K_, 4); else LAUNCH_DIA(K_, 6); } break
-        switch (L.dia.K) {
-          case 1: LAUNCH_DIA_K(1);
-          case 2: LAUNCH_DIA_K(2);
-          case 3: LAUNCH_DIA_K(3);
-          case 4: LAUNCH_DIA_K(4);
-          case 5: LAUNCH_DIA_K(5);
-          case 6: LAUNCH_DIA_K(6);
-          case 7: LAUNCH_DIA_K(7);
-          case 8: LAUNCH_DIA_K(8);
-          default: throw Err("fused restriction (diagonal image): bad number of diagonals");
+      case DOWN_DIA: {
+        // symmetric diagonal image: 512-row chunks, one thread per row, whole level in one launch
+        const int ns = (int)((L.n + WAVE - 1) / WAVE);
+        const int nch = R.slice_list.n ? R.n_chunks : (ns + (512 / WAVE) - 1) / (512 / WAVE);
+        if (nch != R.n_chunks || L.fused_block != 512) throw Err("fused restriction (diagonal image): chunk / slice mismatch");
+        if (sp.part != PART_ALL) throw Err("fused restriction (diagonal image): the level is not split into interior / boundary parts");
+        probed(probe, [&] {
+          if (nch <= 0) return;
+          auto run_k = [&](auto K) {
+            auto run = [&](auto EPT) {
+              launch(dia_pre_restrict_kernel<K(), EPT()>, nch, 512, 0, stream, (int)L.n, ns, L.dia.view(), b, L.dinv.p, L.omega, epf, x, R.chunk_slot.p,
+                     R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, R.slice_list.p);
+            };
+            if (!dispatch<4>(R.ept, run)) run(Int<6>{});
+          };
+          if (!dispatch<1, 2, 3, 4, 5, 6, 7, 8>(L.dia.K, run_k)) throw Err("fused restriction (diagonal image): bad number of diagonals");
+        });
+        if (!skip_rsum) restrict_sum(l, R, b_coarse);
+        return;
+      }
+      case DOWN_SELL:
+      case DOWN_WIN: {
+        const int FB = L.fused_block;
+        const int G = L.Apre.lanes;
+        const int nch = R.slice_list.n ? R.n_chunks : (L.Apre.n_slices + (FB / WAVE) - 1) / (FB / WAVE);
+        if (nch != R.n_chunks) throw Err("fused restriction: chunk / slice mismatch");
+        if (R.slice_list.n && sp.part != PART_ALL) throw Err("fused restriction: compact chunks are not split into interior / boundary parts");
+        int64_t ca, cb;
+        unit_range(sp, FB / G, nch, ca, cb);
+        const int grid = (int)(cb - ca), c0 = (int)ca;
+        probed(probe, [&] {
+          if (grid <= 0) return;
+          // <rows per chunk, MODE 0, entries of P per thread, lanes per row>(..., compact chunk list)
+          auto sell = [&](auto FB_, auto EPT, auto G_, const int32_t* slice_list) {
+            launch(sell_pre_restrict_kernel<FB_(), 0, EPT(), G_()>, grid, FB_(), 0, stream, L.Apre.n_rows, c0, L.Apre.n_slices, L.Apre.sell.view(), b, L.dinv.p,
+                   L.omega, epf, x, nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, slice_list);
+          };
+          if (L.paths.down == DOWN_WIN) {
+            if (FB != SELL_WIN || G != 1) throw Err("fused restriction on a windowed image: unexpected chunk shape");
+            auto run = [&](auto EPT) {
+              launch(sell_win_pre_restrict_kernel<SELL_WIN, EPT()>, grid, SELL_WIN, 0, stream, L.Apre.n_rows, c0, L.Apre.sell.view(), L.Apre.sell.rowloc.p, b,
+                     L.dinv.p, L.omega, epf, x, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+            };
+            if (!dispatch<4>(R.ept, run)) run(Int<6>{});
+          } else if (G > 1) {
+            if (FB != 512 || R.ept != 4) throw Err("fused restriction with several lanes per row: unexpected chunk shape");
+            auto run = [&](auto G_) { sell(Int<512>{}, Int<4>{}, G_, nullptr); };
+            if (!dispatch<2, 4>(G, run)) run(Int<8>{});
+          } else {
+            auto run_fb = [&](auto FB_) {
+              auto run = [&](auto EPT) { sell(FB_, EPT, Int<1>{}, R.slice_list.p); };
+              if (!dispatch<4>(R.ept, run)) run(Int<6>{});
+            };
+            if (!dispatch<256, 512>(FB, run_fb)) run_fb(Int<1024>{});
+          }
+        });
+        if (!skip_rsum && sp.part != PART_INT) restrict_sum(l, R, b_coarse);
+        return;
+      }
+      case DOWN_CHEB: {
+        if (sp.part != PART_ALL) break;
+        // Chebyshev pre-smoothing from zero, then residual on the SELL image of A + chunk-local restriction in one pass (r stays in LDS)
+        cheb_smooth(L, x, x, b, r, false, false, true);
+        const int G = L.A.lanes;
+        const int nch = R.slice_list.n ? R.n_chunks : (L.A.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
+        if (nch != R.n_chunks || L.fused_block != 512 || L.A.fmt != FMT_SELL || L.A.sell.win) throw Err("fused Chebyshev residual: chunk / slice mismatch");
+        if (nch > 0) {
+          // (a smoother pass: the float kernel on the single-precision image where the level has one)
+          auto run_v = [&](auto view) {
+            using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;
+            auto cres = [&](auto EPT, auto G_, const int32_t* slice_list) {
+              launch(sell_pre_restrict_kernel<512, 2, EPT(), G_(), V>, nch, 512, 0, stream, L.A.n_rows, 0, L.A.n_slices, view, x, b, 0.0, ep_nt, nullptr, nullptr,
+                     R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, slice_list);
+            };
+            if (G > 1) {
+              if (R.ept != 4 || R.slice_list.n) throw Err("fused Chebyshev residual with several lanes per row: unexpected chunk shape");
+              if (!dispatch<2, 4, 8>(G, [&](auto G_) { cres(Int<4>{}, G_, nullptr); })) throw Err("fused Chebyshev residual: unexpected lanes per row");
+            } else {
+              auto run = [&](auto EPT) { cres(EPT, Int<1>{}, R.slice_list.p); };
+              if (!dispatch<4>(R.ept, run)) run(Int<6>{});
+            }
+          };
+          if (L.A.has32()) run_v(L.A.sell.view32(L.A.val32.p));
+          else run_v(L.A.sell.view());
         }
-#undef LAUNCH_DIA_K
-#undef LAUNCH_DIA
+        if (!skip_rsum) restrict_sum(l, R, b_coarse);
+        return;
       }
-      if (probe) HIPCHK(hipEventRecord(probe_e1, stream));
-      if (!skip_rsum)
-        restrict_sum(l, R, b_coarse);
-      HIPCHK(hipGetLastError());
-      return;
-    }
-    if (plain(L) && L.sm_type == AMGX_SM_JACOBI && !L.RF.empty()) {
-      const DevRestrict& R = L.RF;
-      const int FB = L.fused_block;
-      const int G = L.Apre.lanes;
-      const int nch = R.slice_list.n ? R.n_chunks : (L.Apre.n_slices + (FB / WAVE) - 1) / (FB / WAVE);
-      if (nch != R.n_chunks) throw Err("fused restriction: chunk / slice mismatch");
-      if (R.slice_list.n && sp.part != PART_ALL) throw Err("fused restriction: compact chunks are not split into interior / boundary parts");
-      int64_t ca, cb;
-      unit_range(sp, FB / G, nch, ca, cb);
-      const int grid = (int)(cb - ca), c0 = (int)ca;
-      // (rank-partitioned level: the events go around the interior launch, which runs beside the halo exchange)
-      const bool probe = probe_level == l && probe_kind == 8 && probe_e0 && sp.part != PART_BND;
-      if (probe) HIPCHK(hipEventRecord(probe_e0, stream));
-      if (grid > 0) {
-#define LAUNCH_PRF(FB_, EPT_) hipLaunchKernelGGL((sell_pre_restrict_kernel<FB_, 0, EPT_>), dim3(grid), dim3(FB_), 0, stream, L.Apre.n_rows, c0, L.Apre.n_slices, \
-                             L.Apre.sell.view(), b, L.dinv.p, L.omega, epf, x, (double*)nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, \
-                             (const int32_t*)R.slice_list.p)
-#define LAUNCH_PRG(G_) hipLaunchKernelGGL((sell_pre_restrict_kernel<512, 0, 4, G_>), dim3(grid), dim3(512), 0, stream, L.Apre.n_rows, c0, L.Apre.n_slices, \
-                             L.Apre.sell.view(), b, L.dinv.p, L.omega, epf, x, (double*)nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p)
-        if (L.Apre.sell.win) {
-          if (FB != SELL_WIN || G != 1) throw Err("fused restriction on a windowed image: unexpected chunk shape");
-#define LAUNCH_WPR(EPT_) hipLaunchKernelGGL((sell_win_pre_restrict_kernel<SELL_WIN, EPT_>), dim3(grid), dim3(SELL_WIN), 0, stream, L.Apre.n_rows, c0, L.Apre.sell.view(), \
-                             L.Apre.sell.rowloc.p, b, L.dinv.p, L.omega, epf, x, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p)
-          if (R.ept == 4) LAUNCH_WPR(4); else LAUNCH_WPR(6);
-#undef LAUNCH_WPR
-        }
-        else if (G > 1) {
-          if (FB != 512 || R.ept != 4) throw Err("fused restriction with several lanes per row: unexpected chunk shape");
-          if (G == 2) LAUNCH_PRG(2); else if (G == 4) LAUNCH_PRG(4); else LAUNCH_PRG(8);
-        }
-        else if (FB == 256) { if (R.ept == 4) LAUNCH_PRF(256, 4); else LAUNCH_PRF(256, 6); }
-        else if (FB == 512) { if (R.ept == 4) LAUNCH_PRF(512, 4); else LAUNCH_PRF(512, 6); }
-        else { if (R.ept == 4) LAUNCH_PRF(1024, 4); else LAUNCH_PRF(1024, 6); }
-#undef LAUNCH_PRG
-#undef LAUNCH_PRF
-      }
-      if (probe) HIPCHK(hipEventRecord(probe_e1, stream));
-      if (!skip_rsum && sp.part != PART_INT)
-        restrict_sum(l, R, b_coarse);
-      HIPCHK(hipGetLastError());
-      return;
-    }
-    if (plain(L) && L.sm_type == AMGX_SM_CHEBY && !L.RF.empty() && sp.part == PART_ALL) {
-      // Chebyshev pre-smoothing from zero, then residual on the SELL image of A + chunk-local restriction in one pass (r stays in LDS)
-      cheb_smooth(L, x, x, b, r, false, false, true);
-      const DevRestrict& R = L.RF;
-      const int G = L.A.lanes;
-      const int nch = R.slice_list.n ? R.n_chunks : (L.A.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
-      if (nch != R.n_chunks || L.fused_block != 512 || L.A.fmt != FMT_SELL || L.A.sell.win) throw Err("fused Chebyshev residual: chunk / slice mismatch");
-      if (nch > 0) {
-        // (a smoother pass: V_ = float and VIEW_ = the single-precision image where the level has one)
-#define LAUNCH_CRF(EPT_, V_, VIEW_) hipLaunchKernelGGL((sell_pre_restrict_kernel<512, 2, EPT_, 1, V_>), dim3(nch), dim3(512), 0, stream, L.A.n_rows, 0, L.A.n_slices, VIEW_, \
-                             (const double*)x, b, 0.0, ep_nt, (double*)nullptr, (double*)nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, \
-                             (const int32_t*)R.slice_list.p)
-#define LAUNCH_CRG(G_, V_, VIEW_) hipLaunchKernelGGL((sell_pre_restrict_kernel<512, 2, 4, G_, V_>), dim3(nch), dim3(512), 0, stream, L.A.n_rows, 0, L.A.n_slices, VIEW_, \
-                             (const double*)x, b, 0.0, ep_nt, (double*)nullptr, (double*)nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, \
-                             (const int32_t*)nullptr)
-#define LAUNCH_CR(V_, VIEW_)                                                                                                                     \
-        if (G > 1) {                                                                                                                              \
-          if (R.ept != 4 || R.slice_list.n) throw Err("fused Chebyshev residual with several lanes per row: unexpected chunk shape");           \
-          if (G == 2) LAUNCH_CRG(2, V_, VIEW_); else if (G == 4) LAUNCH_CRG(4, V_, VIEW_); else if (G == 8) LAUNCH_CRG(8, V_, VIEW_);              \
-          else throw Err("fused Chebyshev residual: unexpected lanes per row");                                                                  \
-        } else { if (R.ept == 4) LAUNCH_CRF(4, V_, VIEW_); else LAUNCH_CRF(6, V_, VIEW_); }
-        if (L.A.has32()) { LAUNCH_CR(float, L.A.sell.view32(L.A.val32.p)) }
-        else { LAUNCH_CR(double, L.A.sell.view()) }
-#undef LAUNCH_CR
-#undef LAUNCH_CRG
-#undef LAUNCH_CRF
-      }
-      if (!skip_rsum)
-        restrict_sum(l, R, b_coarse);
-      HIPCHK(hipGetLastError());
-      return;
-    }
-    if (plain(L) && L.sm_type == AMGX_SM_GS && L.gsb.on() && L.gsb.has_split && !L.RG.empty() && sp.part == PART_ALL) {
-      // sweep from zero, then residual of the untouched part + chunk-local restriction in one pass (r stays in LDS)
-      gsb_sweep(L, 0, L.gsb.lowin, nullptr, x, b);
-      gsb_residual_restrict(l, x, r, b_coarse);
-      return;
+      case DOWN_GSB:
+        if (sp.part != PART_ALL) break;
+        // sweep from zero, then residual of the untouched part + chunk-local restriction in one pass (r stays in LDS)
+        gsb_sweep(L, 0, L.gsb.lowin, nullptr, x, b);
+        gsb_residual_restrict(l, x, r, b_coarse);
+        return;
+      default: break;
     }
     pre_smooth(L, x, b, r, fold, sp);
     if (sp.part != PART_INT) transfer_f2c(l, r, b_coarse);
@@ -2147,49 +2064,48 @@ struct Handle {
   void gsb_residual_restrict(int l, const double* x, double* r, double* b_coarse) {
     DevLevel& L = lev[l];
     if (!L.gsb.has_split) throw Err("gsb_residual_restrict: the level has no lower / rest split");
-    if (!L.gsb.restLW.empty() && !L.RG.empty()) {
-      // long-row level: local-window image of the rest part (the swept x is staged in LDS per chunk)
-      const DevRestrict& R = L.RG;
-      const DevMatrix& M = L.gsb.restLW;
-      const int nch = (M.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
-      if (nch != R.n_chunks) throw Err("fused Gauss-Seidel residual (local-window image): chunk / slice mismatch");
-#define LAUNCH_LWC(EPT_, G_) hipLaunchKernelGGL((sell_lw_pre_restrict_kernel<EPT_, G_, 1>), dim3(nch), dim3(512), 0, stream, M.n_rows, 0, M.n_slices, M.sell.view(), \
-                             L.gsb.lw_cptr.p, L.gsb.lw_ccol.p, (const double*)x, (const double*)L.gsb.cvec.p, 0.0, 0, (double*)nullptr, \
-                             R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p)
-      if (M.lanes == 2) { if (R.ept == 2) LAUNCH_LWC(2, 2); else LAUNCH_LWC(4, 2); }
-      else { if (R.ept == 2) LAUNCH_LWC(2, 4); else LAUNCH_LWC(4, 4); }
-#undef LAUNCH_LWC
-      restrict_sum(l, R, b_coarse);
-      HIPCHK(hipGetLastError());
-      return;
-    }
-    if (L.RG.empty()) {
+    const DevRestrict& R = L.RG;
+    if (R.empty()) {
       spmv_ep<EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
       transfer_f2c(l, r, b_coarse);
       return;
     }
-    {
-      const DevRestrict& R = L.RG;
+    if (!L.gsb.restLW.empty()) {
+      // long-row level: local-window image of the rest part (the swept x is staged in LDS per chunk)
+      const DevMatrix& M = L.gsb.restLW;
+      const int nch = (M.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
+      if (nch != R.n_chunks) throw Err("fused Gauss-Seidel residual (local-window image): chunk / slice mismatch");
+      auto run_g = [&](auto G) {
+        auto run = [&](auto EPT) {
+          launch(sell_lw_pre_restrict_kernel<EPT(), G(), 1>, nch, 512, 0, stream, M.n_rows, 0, M.n_slices, M.sell.view(), L.gsb.lw_cptr.p, L.gsb.lw_ccol.p, x,
+                 L.gsb.cvec.p, 0.0, 0, nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+        };
+        if (!dispatch<2>(R.ept, run)) run(Int<4>{});
+      };
+      if (!dispatch<2>(M.lanes, run_g)) run_g(Int<4>{});
+    } else {
       const DevMatrix& M = L.gsb.rest;
       const int nch = (M.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
       if (nch != R.n_chunks) throw Err("fused Gauss-Seidel residual: chunk / slice mismatch");
-#define LAUNCH_WCR(EPT_) hipLaunchKernelGGL((sell_win_cres_restrict_kernel<SELL_WIN, EPT_>), dim3(nch), dim3(SELL_WIN), 0, stream, M.n_rows, M.sell.view(), M.sell.rowloc.p, \
-                           (const double*)x, (const double*)L.gsb.cvec.p, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p)
-#define LAUNCH_PCR(EPT_) hipLaunchKernelGGL((sell_pre_restrict_kernel<512, 1, EPT_>), dim3(nch), dim3(512), 0, stream, M.n_rows, 0, M.n_slices, M.sell.view(), (const double*)x, \
-                         (const double*)L.gsb.cvec.p, 0.0, 0, (double*)nullptr, (double*)nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p)
-      if (M.sell.win) { if (R.ept == 4) LAUNCH_WCR(4); else LAUNCH_WCR(6); }
-      else { if (R.ept == 4) LAUNCH_PCR(4); else LAUNCH_PCR(6); }
-#undef LAUNCH_WCR
-#undef LAUNCH_PCR
-      restrict_sum(l, R, b_coarse);
-      HIPCHK(hipGetLastError());
+      auto run = [&](auto EPT) {
+        if (M.sell.win)
+          launch(sell_win_cres_restrict_kernel<SELL_WIN, EPT()>, nch, SELL_WIN, 0, stream, M.n_rows, M.sell.view(), M.sell.rowloc.p, x, L.gsb.cvec.p, R.chunk_slot.p,
+                 R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+        else
+          launch(sell_pre_restrict_kernel<512, 1, EPT()>, nch, 512, 0, stream, M.n_rows, 0, M.n_slices, M.sell.view(), x, L.gsb.cvec.p, 0.0, 0, nullptr, nullptr,
+                 R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, nullptr);
+      };
+      if (!dispatch<4>(R.ept, run)) run(Int<6>{});
     }
+    restrict_sum(l, R, b_coarse);
   }
 
   // coarse-grid correction + post-smoothing: x += P x_c; SmoothBack(x, b, r, 0, 0, 0)   (amg_matrix.cpp:263-302)
   // fold: x holds z of the folded pre-smoothing pass; x' = z + Q x_c (see fold_prolongation)
   void post_smooth(int l, double* x, const double* b, double* r, const double* xc, bool fold = false, const Span sp = Span()) {
     DevLevel& L = lev[l];
+    const LevelPaths& P = L.paths;
+    const bool probe = probe_level == l && probe_kind == 9 && probe_e0;
     if (fold && !L.QLW.empty()) {
       // local-window form of Q: the coarse values a window needs are staged in LDS (sell_lw_win_spmv_kernel); interior / boundary
       // window ranges on rank-partitioned levels (the list of an interior window holds owned coarse columns only)
@@ -2197,40 +2113,29 @@ struct Handle {
       int64_t wa, wb;
       unit_range(sp, SELL_WIN, nw, wa, wb);
       if (wb > wa)
-        hipLaunchKernelGGL((sell_lw_win_spmv_kernel<SELL_WIN, EP_AXPY>), dim3((int)(wb - wa)), dim3(SELL_WIN), 0, stream, L.QLW.n_rows, (int)wa, L.QLW.sell.view(),
-                           L.QLW.sell.rowloc.p, L.qlw_cptr.p, L.qlw_ccol.p, xc, x, EpArgs{nullptr, x, nullptr, 1.0, nullptr, ep_nt & EPF_HOIST});
-      HIPCHK(hipGetLastError());
+        launch(sell_lw_win_spmv_kernel<SELL_WIN, EP_AXPY>, (int)(wb - wa), SELL_WIN, 0, stream, L.QLW.n_rows, (int)wa, L.QLW.sell.view(), L.QLW.sell.rowloc.p,
+               L.qlw_cptr.p, L.qlw_ccol.p, xc, x, EpArgs{nullptr, x, nullptr, 1.0, nullptr, ep_nt & EPF_HOIST});
     } else if (fold) {
       mult_add(L.Q, 1.0, xc, x, x, sp);
     } else if (sp.part == PART_INT) {
       return;                                  // literal forms are driven stage by stage (Dist), not through this function
-    } else if (plain(L) && L.sm_type == AMGX_SM_JACOBI) {
+    } else if (P.plain && L.sm_type == AMGX_SM_JACOBI) {
       mult_add(L.P, 1.0, xc, x, L.tmp.p);  // tmp = x + P x_c
       jacobi_fused(L, L.tmp.p, b, x);      // x = tmp + omega * Dinv * (b - A tmp); res is not needed afterwards
-    } else if (plain(L) && L.sm_type == AMGX_SM_CHEBY) {
+    } else if (P.plain && L.sm_type == AMGX_SM_CHEBY) {
       // k out-of-place passes follow: x + P x_c goes where the last of them lands in x
       double* t = (L.cheb_degree & 1) ? L.tmp.p : x;
       mult_add(L.P, 1.0, xc, x, t);
       cheb_smooth(L, t, x, b, r, false, false, false);
-    } else if (plain(L) && L.sm_type == AMGX_SM_GS && L.bgsb.on()) {
-      const bool probe = probe_level == l && probe_kind == 9 && probe_e0;
-      if (L.bgsb.bc) {
-        mult_add(L.P, 1.0, xc, x, x);      // x += P x_c
-        if (probe) HIPCHK(hipEventRecord(probe_e0, stream));
-        bgsb_sweep(L, 1, x, x, b);         // backward block-coloured sweep, in place (one launch per block colour)
-        if (probe) HIPCHK(hipEventRecord(probe_e1, stream));
-      } else {
+    } else if (P.plain && P.sweep == SWEEP_BGSB_BC) {
+      mult_add(L.P, 1.0, xc, x, x);        // x += P x_c
+      probed(probe, [&] { bgsb_sweep(L, 1, x, x, b); });          // backward block-coloured sweep, in place (one launch per block colour)
+    } else if (P.plain && P.sweep == SWEEP_BGSB) {
       mult_add(L.P, 1.0, xc, x, L.tmp.p);  // tmp = x + P x_c
-      if (probe) HIPCHK(hipEventRecord(probe_e0, stream));
-      bgsb_sweep(L, 1, L.tmp.p, x, b);     // backward block-hybrid sweep, tmp -> x
-      if (probe) HIPCHK(hipEventRecord(probe_e1, stream));
-      }
-    } else if (plain(L) && L.sm_type == AMGX_SM_GS && L.gsb.on() && L.n == L.ncols) {
+      probed(probe, [&] { bgsb_sweep(L, 1, L.tmp.p, x, b); });    // backward block-hybrid sweep, tmp -> x
+    } else if (P.plain && P.sweep == SWEEP_GSB && L.n == L.ncols) {
       mult_add(L.P, 1.0, xc, x, L.tmp.p);  // tmp = x + P x_c
-      const bool probe = probe_level == l && probe_kind == 9 && probe_e0;
-      if (probe) HIPCHK(hipEventRecord(probe_e0, stream));
-      gsb_sweep(L, 1, L.gsb.full, L.tmp.p, x, b);   // backward block-hybrid sweep, tmp -> x
-      if (probe) HIPCHK(hipEventRecord(probe_e1, stream));
+      probed(probe, [&] { gsb_sweep(L, 1, L.gsb.full, L.tmp.p, x, b); });   // backward block-hybrid sweep, tmp -> x
     } else {
       add_c2f(l, 1.0, x, xc);
       level_smooth(L, 1, x, b, r, false, false, false);
@@ -3756,15 +3661,11 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
     const amgx::DevLevel& L = h.lev[level];
     const amgx::DevRestrict& R = L.RF;
     int64_t v[AMGX_LEVEL_PATHS_N] = {};
-    // the branch order of pre_smooth_restrict
-    const bool fused = h.plain(L) && L.sm_type == AMGX_SM_JACOBI && !R.empty();
-    if (h.plain(L) && L.sm_type == AMGX_SM_CHEBY && !R.empty()) {
-      v[0] = 5; v[1] = L.fused_block; v[2] = L.A.lanes; v[3] = R.ept;
-    }
-    if (fused) {
-      v[0] = !L.ApreLW.empty() ? 3 : L.dia.on() ? 4 : L.Apre.sell.win ? 2 : 1;
+    const int down = L.paths.down;
+    if (down != amgx::DOWN_NONE && down != amgx::DOWN_GSB) {          // (the fused block-hybrid form is not a kernel of entry 0)
+      v[0] = down;
       v[1] = L.fused_block;
-      v[2] = v[0] == 3 ? L.ApreLW.lanes : v[0] == 4 ? 1 : L.Apre.lanes;
+      v[2] = down == amgx::DOWN_CHEB ? L.A.lanes : down == amgx::DOWN_LW ? L.ApreLW.lanes : down == amgx::DOWN_DIA ? 1 : L.Apre.lanes;
       v[3] = R.ept;
     }
     if (!R.empty()) {
@@ -3787,34 +3688,37 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
       const std::vector<int32_t> cp = amgx::db_download(L.lw_cptr, L.lw_cptr.n);
       for (size_t c = 0; c + 1 < cp.size(); ++c) v[16] += cp[c + 1] == cp[c];
     }
-    v[17] = h.folded(L) ? 1 : 0;
-    // Gauss-Seidel sweep: the branch order of base_smooth / gs_sweep
+    v[17] = L.paths.folded ? 1 : 0;
     const amgx::DevGS& gs = L.gs;
     const amgx::DevGSB& gsb = L.gsb;
     const amgx::DevBGSB& bgsb = L.bgsb;
-    if (L.sm_type == AMGX_SM_BGS) {
-      v[19] = 7; v[23] = L.bgs.n_colors;
-    } else if (L.sm_type == AMGX_SM_GS && bgsb.on()) {
-      v[19] = bgsb.bc ? 6 : 5; v[21] = amgx::BLOCK; v[22] = bgsb.BB; v[23] = bgsb.n_colors; v[24] = bgsb.n_bcolors; v[25] = bgsb.has_split;
-    } else if (L.sm_type == AMGX_SM_GS && gsb.on()) {
-      v[19] = 4; v[20] = gsb.G; v[21] = gsb.TH; v[22] = gsb.B; v[23] = gsb.n_colors; v[25] = gsb.has_split;
-      v[26] = gsb.lowin_maxw; v[27] = gsb.full_maxw;
-      v[28] = gsb.has_split && gsb.narrow;
-      v[29] = gsb.mid;
-      v[30] = gsb.lw;
-      v[32] = gsb.has_fullLW ? gsb.flw_no_window : 0;
-    } else if (L.sm_type == AMGX_SM_GS && gs.n_colors > 0) {
-      v[23] = gs.n_colors; v[21] = amgx::BLOCK;
-      if (L.bs == 1) { v[19] = 1; v[20] = gs.lanes; v[25] = gs.has_split; }
-      else if (gs.bsell_ok) { v[19] = 3; v[25] = gs.bsplit; }
-      else {
-        v[19] = 2;
+    v[19] = L.paths.sweep;
+    switch (L.paths.sweep) {
+      case amgx::SWEEP_BGS: v[23] = L.bgs.n_colors; break;
+      case amgx::SWEEP_BGSB:
+      case amgx::SWEEP_BGSB_BC:
+        v[21] = amgx::BLOCK; v[22] = bgsb.BB; v[23] = bgsb.n_colors; v[24] = bgsb.n_bcolors; v[25] = bgsb.has_split;
+        break;
+      case amgx::SWEEP_GSB:
+        v[20] = gsb.G; v[21] = gsb.TH; v[22] = gsb.B; v[23] = gsb.n_colors; v[25] = gsb.has_split;
+        v[26] = gsb.lowin_maxw; v[27] = gsb.full_maxw;
+        v[28] = gsb.has_split && gsb.narrow;
+        v[29] = gsb.mid;
+        v[30] = gsb.lw;
+        v[32] = gsb.has_fullLW ? gsb.flw_no_window : 0;
+        break;
+      case amgx::SWEEP_MC: v[20] = gs.lanes; v[21] = amgx::BLOCK; v[23] = gs.n_colors; v[25] = gs.has_split; break;
+      case amgx::SWEEP_MC_BSELL: v[21] = amgx::BLOCK; v[23] = gs.n_colors; v[25] = gs.bsplit; break;
+      case amgx::SWEEP_MC_ROWLIST: {
+        v[21] = amgx::BLOCK; v[23] = gs.n_colors;
         const double avg = L.A.n_rows ? (double)L.A.nnz / (double)L.A.n_rows : 0.0;
         for (int c = 0; c < gs.n_colors; ++c) {
           const int64_t rows = gs.color_row_ptr[c + 1] - gs.color_row_ptr[c];
           if (rows > 0) v[31] |= amgx::bgs_rowlist_w(avg, rows);
         }
+        break;
       }
+      default: break;
     }
     for (int k = 0; k < std::min(n_out, AMGX_LEVEL_PATHS_N); ++k) out[k] = v[k];
   });
@@ -3840,7 +3744,7 @@ int amgx_time_op(amgx_handle hh, int level, int op, int reps, double* avg_ms) {
         case 5: h.pre_smooth_restrict(level, L.x.p, L.rhs.p, L.res.p, h.lev[level + 1].rhs.p, h.folded(L)); break;
         case 6: h.post_smooth(level, L.x.p, L.rhs.p, L.res.p, h.lev[level + 1].x.p, h.folded(L)); break;
         case 7:
-          if (L.RF.empty()) throw amgx::Err("amgx_time_op: level has no fused pre-smoothing + restriction kernel");
+          if (!L.paths.jacobi_down() && L.paths.down != amgx::DOWN_CHEB) throw amgx::Err("amgx_time_op: level has no fused pre-smoothing + restriction kernel");
           h.skip_rsum = true;
           try { h.pre_smooth_restrict(level, L.x.p, L.rhs.p, L.res.p, h.lev[level + 1].rhs.p, h.folded(L)); } catch (...) { h.skip_rsum = false; throw; }
           h.skip_rsum = false;
@@ -3851,8 +3755,8 @@ int amgx_time_op(amgx_handle hh, int level, int op, int reps, double* avg_ms) {
     if (op == 8 || op == 9) {
       // the dominant kernel timed where it runs: inside the cycle, between the previous cycle's last kernel and the
       // partial-sum reduction (cache state and clocks of the real application), averaged over `reps` cycles
-      if (op == 8 && (L.RF.empty() || !(h.plain(L) && L.sm_type == AMGX_SM_JACOBI))) throw amgx::Err("amgx_time_op: level has no fused pre-smoothing + restriction kernel");
-      if (op == 9 && !(has_c && h.plain(L) && L.sm_type == AMGX_SM_GS && (L.gsb.on() || L.bgsb.on()) && L.n == L.ncols && !h.folded(L)))
+      if (op == 8 && !L.paths.jacobi_down()) throw amgx::Err("amgx_time_op: level has no fused pre-smoothing + restriction kernel");
+      if (op == 9 && !(has_c && L.paths.plain && L.paths.hybrid() && L.n == L.ncols && !L.paths.folded))
         throw amgx::Err("amgx_time_op: level has no block-hybrid Gauss-Seidel sweep");
       h.probe_kind = op;
       if (h.stream == nullptr) throw amgx::Err("amgx_time_op: op 8 needs a non-default stream");

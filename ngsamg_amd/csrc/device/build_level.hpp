@@ -631,10 +631,10 @@ static void build_dense_tail(Handle& h, const amgx_hierarchy_desc* d, const amgx
   auto launches = [&](int m) -> double {
     const DevLevel& V = h.lev[m];
     const int k = std::max(1, V.sm_steps) * (V.sm_symm ? 2 : 1);
-    if (V.sm_type == AMGX_SM_JACOBI) return h.folded(V) ? 3.0 : 2.0 + 3.0 * k;
+    if (V.sm_type == AMGX_SM_JACOBI) return V.paths.folded ? 3.0 : 2.0 + 3.0 * k;
     if (V.sm_type == AMGX_SM_CHEBY) return 3.0 + 2.0 * k * (V.cheb_degree + 1);
     if (V.sm_type == AMGX_SM_BGS) return 3.0 + 2.0 * k * std::max(1, V.bgs.n_colors);
-    if (V.gsb.on() || V.bgsb.on()) return 2.0 + 3.0 * k;
+    if (V.paths.hybrid()) return 2.0 + 3.0 * k;
     return 3.0 + 2.0 * k * std::max(1, V.gs.n_colors);
   };
   int lc = -1;
@@ -734,6 +734,7 @@ static Handle* create(const amgx_hierarchy_desc* d, const Knobs& K, int dense_fi
     mat_f32_image(B);
     set_xcd_modes(B);
     alloc_level_vectors(B);
+    resolve_paths(B.L);                   // every image of the level is final here; nothing before this line runs a cycle or asks folded()
   }
   cheb_estimate(*h);
   clk.lap("Chebyshev intervals (power iteration)");

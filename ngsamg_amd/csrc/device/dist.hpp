@@ -428,13 +428,13 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
         if (s.color[hd.send_idx[i]] >= g[2]) { D->stage[l] = {g[0], g[1], nc, nc}; break; }
     }
     D->send_early.push_back(1);
-    if (D->top->lev[l].gsb.on() || D->top->lev[l].bgsb.on()) {
+    if (const LevelPaths& lp = D->top->lev[l].paths; lp.hybrid()) {
       // block-hybrid form: the boundary blocks [n_int / B, end) are swept first, then x travels beside the interior blocks
       const amgx_halo_desc& hd = d->halo[l];
       const int64_t ns = hd.n_peers > 0 ? hd.send_ptr[hd.n_peers] : 0;
-      if (D->top->lev[l].bgsb.on() && s.gs_block_ids) throw Err("amgx_dist_create: rank-partitioned block levels sweep runs of consecutive rows (no gs_block_ids)");
-      if (D->top->lev[l].bgsb.bc) throw Err("amgx_dist_create: rank-partitioned block levels sweep in the hybrid form (no gs_block_color)");
-      const int64_t B = D->top->lev[l].gsb.on() ? D->top->lev[l].gsb.B : D->top->lev[l].bgsb.BB;
+      if (lp.bgsb() && s.gs_block_ids) throw Err("amgx_dist_create: rank-partitioned block levels sweep runs of consecutive rows (no gs_block_ids)");
+      if (lp.sweep == SWEEP_BGSB_BC) throw Err("amgx_dist_create: rank-partitioned block levels sweep in the hybrid form (no gs_block_color)");
+      const int64_t B = lp.sweep == SWEEP_GSB ? D->top->lev[l].gsb.B : D->top->lev[l].bgsb.BB;
       const int64_t first_bnd = (D->halo[l].n_int / B) * B;
       for (int64_t i = 0; i < ns; ++i)
         if (hd.send_idx[i] < first_bnd) { D->send_early[l] = 0; break; }
@@ -447,7 +447,7 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
   }
   if (D->sm_type == AMGX_SM_GS) {
     int on = 0;
-    for (int l = 0; l < k; ++l) on += (D->top->lev[l].gsb.on() || D->top->lev[l].bgsb.on()) ? 1 : 0;
+    for (int l = 0; l < k; ++l) on += D->top->lev[l].paths.hybrid() ? 1 : 0;
     if (on != 0 && on != k) throw Err("amgx_dist_create: either all or none of the rank-partitioned Gauss-Seidel levels use gs_block_rows");
     D->gsb = on == k;
   }
@@ -619,17 +619,17 @@ struct DistCycle {
     // (a level with a sent row inside an interior block sweeps all its blocks before the exchange: see Dist::send_early)
     auto nbi = [&](Dist* d, int l) {
       const DevLevel& L = d->top->lev[l];
-      return d->send_early[l] ? (int)(d->halo[l].n_int / (L.gsb.on() ? L.gsb.B : L.bgsb.BB)) : 0;
+      return d->send_early[l] ? (int)(d->halo[l].n_int / (L.paths.sweep == SWEEP_GSB ? L.gsb.B : L.bgsb.BB)) : 0;
     };
     // scalar levels: gsb_sweep_kernel; square-block levels: bgsb_sweep_kernel (same block ranges, same stages)
     auto sweep_zero = [&](Dist* d, int l, double* xout, const double* b, int q0, int q1) {
       DevLevel& L = d->top->lev[l];
-      if (L.bgsb.on()) d->top->bgsb_sweep(L, 0, nullptr, xout, b, L.bgsb.has_split, q0, q1);
+      if (L.paths.bgsb()) d->top->bgsb_sweep(L, 0, nullptr, xout, b, L.bgsb.has_split, q0, q1);
       else d->top->gsb_sweep(L, 0, L.gsb.has_split ? L.gsb.lowin : L.gsb.full, nullptr, xout, b, q0, q1);
     };
     auto sweep_back = [&](Dist* d, int l, const double* xin, double* xout, const double* b, int q0, int q1) {
       DevLevel& L = d->top->lev[l];
-      if (L.bgsb.on()) d->top->bgsb_sweep(L, 1, xin, xout, b, false, q0, q1);
+      if (L.paths.bgsb()) d->top->bgsb_sweep(L, 1, xin, xout, b, false, q0, q1);
       else d->top->gsb_sweep(L, 1, L.gsb.full, xin, xout, b, q0, q1);
     };
     for (int l = 0; l < k; ++l) {
@@ -644,9 +644,9 @@ struct DistCycle {
       for (size_t i = 0; i < M.size(); ++i) {
         Dist* d = M[i];
         DevLevel& L = d->top->lev[l];
-        if (L.gsb.on() && L.gsb.has_split) d->top->gsb_residual_restrict(l, d->xext[l].p, d->rl[l].p, bnext(d, l));
+        if (L.paths.sweep == SWEEP_GSB && L.gsb.has_split) d->top->gsb_residual_restrict(l, d->xext[l].p, d->rl[l].p, bnext(d, l));
         else {
-          if (L.bgsb.on() && L.bgsb.has_split) d->top->mult(L.bgsb.rest, d->xext[l].p, d->rl[l].p);      // r = rest x (see DevBGSB)
+          if (L.paths.bgsb() && L.bgsb.has_split) d->top->mult(L.bgsb.rest, d->xext[l].p, d->rl[l].p);      // r = rest x (see DevBGSB)
           else d->top->residual(L.A, d->xext[l].p, bl(d, i, l), d->rl[l].p);
           d->top->transfer_f2c(l, d->rl[l].p, bnext(d, l));
         }
@@ -738,8 +738,8 @@ struct DistCycle {
       double*& oth = gx[l].oth[i];
       const double* b = gbl(i, l);
       if (d->sm_type == AMGX_SM_JACOBI) { h.jacobi_fused(L, cur, b, oth); std::swap(cur, oth); }
-      else if (L.bgsb.on()) { h.bgsb_sweep(L, dir, cur, oth, b); std::swap(cur, oth); }
-      else if (L.gsb.on()) { h.gsb_sweep(L, dir, L.gsb.full, cur, oth, b); std::swap(cur, oth); }
+      else if (L.paths.bgsb()) { h.bgsb_sweep(L, dir, cur, oth, b); std::swap(cur, oth); }
+      else if (L.paths.sweep == SWEEP_GSB) { h.gsb_sweep(L, dir, L.gsb.full, cur, oth, b); std::swap(cur, oth); }
       else if (d->sm_type == AMGX_SM_BGS) h.bgs_sweep(L, dir, cur, b);
       else h.gs_sweep(L, dir, cur, b);
     }
@@ -1354,8 +1354,8 @@ int amgx_dist_time_kernel(amgx_comm cc, int level, int op, int reps, double* avg
     if (level < 0 || level >= d0->k) throw Err("amgx_dist_time_kernel: not a rank-partitioned level");
     Handle& h = *d0->top;
     DevLevel& L = h.lev[level];
-    if (op == 8 && (L.RF.empty() || !(h.plain(L) && L.sm_type == AMGX_SM_JACOBI) || !d0->fold)) throw Err("amgx_dist_time_kernel: level has no fused pre-smoothing + restriction kernel");
-    if (op == 9 && !(d0->gsb && (L.gsb.on() || L.bgsb.on()))) throw Err("amgx_dist_time_kernel: level has no block-hybrid Gauss-Seidel sweep");
+    if (op == 8 && (!L.paths.jacobi_down() || !d0->fold)) throw Err("amgx_dist_time_kernel: level has no fused pre-smoothing + restriction kernel");
+    if (op == 9 && !(d0->gsb && L.paths.hybrid())) throw Err("amgx_dist_time_kernel: level has no block-hybrid Gauss-Seidel sweep");
     std::vector<const double*> bb;
     std::vector<double*> xx;
     for (Dist* d : c.members) {

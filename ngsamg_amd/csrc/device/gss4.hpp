@@ -110,18 +110,9 @@ struct Gss4 {
     const int32_t* cc = M ? M->col.p : nullptr;
     const double* vv = M ? M->val.p : nullptr;
     const int grid = grid_for_rows(q1 - q0, BS, W);
-#define GSS4_LAUNCH(WW) hipLaunchKernelGGL((gss4_rows_kernel<BS, WW, MODE>), dim3(grid), dim3(BLOCK), 0, stream, q0, q1, lst, rp, cc, vv, \
-                                          (const double*)dinv.p, xg, bo, bmap, xo, omap, s)
-    switch (W) {
-      case 1: GSS4_LAUNCH(1); break;
-      case 2: GSS4_LAUNCH(2); break;
-      case 4: GSS4_LAUNCH(4); break;
-      default:
-        if constexpr (BS * 8 <= WAVE) { GSS4_LAUNCH(8); } else { GSS4_LAUNCH(4); }
-        break;
-    }
-#undef GSS4_LAUNCH
-    HIPCHK(hipGetLastError());
+    auto run = [&](auto WW) { ::amgx::launch(gss4_rows_kernel<BS, WW(), MODE>, grid, BLOCK, 0, stream, q0, q1, lst, rp, cc, vv, dinv.p, xg, bo, bmap, xo, omap, s); };
+    // any other width: 8 lanes per block row where a wave holds them (BS * 8 <= WAVE), else 4
+    if (!dispatch<1, 2, 4>(W, run)) { if constexpr (BS * 8 <= WAVE) run(Int<8>{}); else run(Int<4>{}); }
   }
   template <int MODE>
   void launch(int q0, int q1, const int32_t* lst, const Gss4Csr* M, const double* xg, const double* bo, const int32_t* bmap, double* xo,

@@ -457,32 +457,16 @@ struct Multi {
     if (M.fmt == FMT_SELL && M.sell.win) {
       if (M.sell.win != SELL_WIN) throw Err("windowed SELL: unexpected window size");
       const int nw = (int)((M.n_rows + SELL_WIN - 1) / SELL_WIN);
-      hipLaunchKernelGGL((sell_win_spmm_kernel<SELL_WIN, NV, EP>), dim3(nw), dim3(SELL_WIN), 0, s, M.n_rows, M.sell.view(), M.sell.rowloc.p, x, y, ep);
+      launch(sell_win_spmm_kernel<SELL_WIN, NV, EP>, nw, SELL_WIN, 0, s, M.n_rows, M.sell.view(), M.sell.rowloc.p, x, y, ep);
     } else if (M.fmt == FMT_SELL) {
       const int grid = (M.n_slices + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-#define LAUNCH_SELLM(G) hipLaunchKernelGGL((sell_spmm_kernel<G, NV, EP>), dim3(grid), dim3(BLOCK), 0, s, M.n_rows, M.n_slices, M.sell.view(), x, y, ep)
-      switch (M.lanes) {
-        case 1: LAUNCH_SELLM(1); break;
-        case 2: LAUNCH_SELLM(2); break;
-        case 4: LAUNCH_SELLM(4); break;
-        case 8: LAUNCH_SELLM(8); break;
-        default: LAUNCH_SELLM(16); break;
-      }
-#undef LAUNCH_SELLM
+      auto run = [&](auto G) { launch(sell_spmm_kernel<G(), NV, EP>, grid, BLOCK, 0, s, M.n_rows, M.n_slices, M.sell.view(), x, y, ep); };
+      if (!dispatch<1, 2, 4, 8>(M.lanes, run)) run(Int<16>{});       // any other lane count: the 16-lane kernel
     } else if (M.fmt == FMT_CSRVEC && M.br == 1 && M.bc == 1) {
       const int grid = Handle::grid_for(M.n_rows * M.lanes);
-#define LAUNCH_CSRM(G) hipLaunchKernelGGL((csrvec_spmm_kernel<G, NV, EP>), dim3(grid), dim3(BLOCK), 0, s, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep)
-      switch (M.lanes) {
-        case 2: LAUNCH_CSRM(2); break;
-        case 4: LAUNCH_CSRM(4); break;
-        case 8: LAUNCH_CSRM(8); break;
-        case 16: LAUNCH_CSRM(16); break;
-        case 32: LAUNCH_CSRM(32); break;
-        default: LAUNCH_CSRM(64); break;
-      }
-#undef LAUNCH_CSRM
+      auto run = [&](auto G) { launch(csrvec_spmm_kernel<G(), NV, EP>, grid, BLOCK, 0, s, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep); };
+      if (!dispatch<2, 4, 8, 16, 32>(M.lanes, run)) run(Int<64>{});  // any other lane count: one wave per row
     } else throw Err("multi-vector product: matrix format has no multi-vector kernel");
-    HIPCHK(hipGetLastError());
   }
   template <int EP>
   void spmm(int w, const DevMatrix& M, const double* x, double* y, const EpArgs& ep) {

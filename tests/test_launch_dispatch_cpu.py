@@ -1,0 +1,70 @@
+"""The host part of ngsamg_amd/csrc/device/launch.hpp (dispatch<V0, V1, ...>(value, f)) compiled by a plain C++17 host compiler:
+every listed value reaches its own constant exactly once, an unlisted value returns false and calls nothing, and the written-out
+fallback form `if (!dispatch<...>(v, run)) run(Int<F>{})` reaches the fallback constant."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+PROGRAM = r"""
+#include "launch.hpp"
+#include <cstdio>
+#include <map>
+#include <type_traits>
+
+template <int V> struct Tag { static constexpr int value = V; };   // the constant must be usable as a template argument
+
+int main() {
+  std::map<int, int> calls;                  // constant -> number of calls
+  auto run = [&](auto G) {
+    static_assert(std::is_same<decltype(G), amgx::Int<G()>>::value, "f receives std::integral_constant<int, Vi>");
+    calls[Tag<G()>::value]++;
+  };
+  int bad = 0;
+  const int listed[] = {1, 2, 4, 8};
+  for (int v : listed) {
+    calls.clear();
+    if (!amgx::dispatch<1, 2, 4, 8>(v, run)) { std::printf("listed value %d: returned false\n", v); ++bad; }
+    if (calls.size() != 1 || calls[v] != 1) { std::printf("listed value %d: wrong calls\n", v); ++bad; }
+  }
+  const int unlisted[] = {0, 3, 16, -1, 64};
+  for (int v : unlisted) {
+    calls.clear();
+    if (amgx::dispatch<1, 2, 4, 8>(v, run)) { std::printf("unlisted value %d: returned true\n", v); ++bad; }
+    if (!calls.empty()) { std::printf("unlisted value %d: something was called\n", v); ++bad; }
+  }
+  for (int v : unlisted) {                   // the fallback form of the SELL families: any other lane count -> 16
+    calls.clear();
+    if (!amgx::dispatch<1, 2, 4, 8>(v, run)) run(amgx::Int<16>{});
+    if (calls.size() != 1 || calls[16] != 1) { std::printf("fallback for %d: wrong calls\n", v); ++bad; }
+  }
+  for (int v : listed) {                     // ... and a listed value does not take it
+    calls.clear();
+    if (!amgx::dispatch<1, 2, 4, 8>(v, run)) run(amgx::Int<16>{});
+    if (calls.size() != 1 || calls[v] != 1) { std::printf("fallback form, listed value %d: wrong calls\n", v); ++bad; }
+  }
+  calls.clear();                             // an empty list matches nothing
+  if (amgx::dispatch<>(1, run) || !calls.empty()) { std::printf("empty list matched\n"); ++bad; }
+  std::printf("bad=%d\n", bad);
+  return bad ? 1 : 0;
+}
+"""
+
+
+def test_dispatch_host_program(tmp_path):
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.fail("g++ is needed to compile the host part of launch.hpp")
+    src = tmp_path / "dispatch_check.cpp"
+    exe = tmp_path / "dispatch_check"
+    src.write_text(PROGRAM)
+    inc = os.path.join(ROOT, "ngsamg_amd", "csrc", "device")
+    cc = subprocess.run([cxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", inc, "-o", str(exe), str(src)],
+                        capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert run.stdout.strip().endswith("bad=0")
