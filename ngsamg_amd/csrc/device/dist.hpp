@@ -901,13 +901,12 @@ static void dist_apply(Comm& c, const double* const* b, double* const* x, int b_
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Preconditioned CG over the rank-partitioned level-0 operator (SURVEY.md 8f-3 for several ranks).  On the reference side
-// this is NGSolve's CGSolver on ParallelVectors (tests/h1/amg_utils.py:337-363): every rank runs the recurrences on its
-// owned entries, the level-0 product needs the ghost values of the search direction (one owner -> ghost exchange, hidden
-// behind the interior rows), the two inner products per iteration are sums over the ranks (MPI all-reduce there;
-// ncclAllReduce of one device scalar here, deterministic local reductions), the preconditioner is the collective cycle
-// (dist_apply, replayed from its graph).  The residual lives in the level-0 right-hand-side buffer of the cycle, so
-// the preconditioner reads it in place.  err_k = sqrt(|<C r_k, r_k>|); stop at err_k <= tol * err_0.
+// The Krylov solvers of krylov_core.hpp over the rank-partitioned level-0 operator (SURVEY.md 8f-3 for several ranks).  On the
+// reference side these are NGSolve's CGSolver / GMRes on ParallelVectors (tests/h1/amg_utils.py:337-363): every rank runs the
+// recurrences on its owned entries, the level-0 product needs the ghost values of its operand (one owner -> ghost exchange,
+// hidden behind the interior rows), every inner product is a sum over the ranks (MPI all-reduce there; ncclAllReduce of the
+// device scalars here, deterministic local reductions), the preconditioner is the collective cycle (dist_apply, replayed from
+// its graph).
 // out[j] = sum over the local ranks i and their KR_BLOCKS partials of product j (partial laid out [rank][64][KR_BLOCKS]); fixed order
 __global__ __launch_bounds__(BLOCK) void kr_dist_multi_final_kernel(int n_local, const double* __restrict__ partial, double* __restrict__ out) {
   __shared__ double red[BLOCK];
@@ -923,278 +922,158 @@ __global__ __launch_bounds__(BLOCK) void kr_dist_multi_final_kernel(int n_local,
   if (threadIdx.x == 0) out[j] = red[0];
 }
 
+// The rank space of krylov_core.hpp: a vector is one pointer per local rank (owned entries).  The residual role is the cycle's
+// level-0 right-hand-side buffer, so the preconditioner reads it in place; the operand role is the [owned | ghost] buffer the
+// level-0 product reads, so CG's direction and the single-reduction form's u are multiplied in place.  Any other vector is
+// copied there first (Handle::copy does nothing when source and destination are the same).  Kept with the communicator
+// (Comm::krylov_ws).  A rank without rows launches nothing element-wise; its buffers have one entry.
 struct DistKrylov {
+  struct Vec { double* const* p; int64_t col; };             // rank i: p[i] + col * (its owned entries); col != 0 only in the basis
+  struct CVec { const double* const* p; int64_t col; CVec(const double* const* pp) : p(pp), col(0) {} CVec(Vec v) : p(v.p), col(v.col) {} };
+  using Bufs = std::vector<DevBuf<double>>;
   Comm& c;
   std::vector<Dist*>& M;
-  std::vector<DevBuf<double>> sext, w;           // search direction [owned | ghost], work vector (owned)
-  DevBuf<double> partial, sc;
-  explicit DistKrylov(Comm& cc) : c(cc), M(cc.members) {
-    sext.resize(M.size()); w.resize(M.size());
-    for (size_t i = 0; i < M.size(); ++i) {
+  const size_t R;
+  Bufs sext, w;                                  // operand of A [owned | ghost], work vector (owned)
+  Bufs sr_p, sr_s;                               // single-reduction form: p, s
+  Bufs gV, gt;                                   // GMRES: basis (m + 1) x n_owned, work vector
+  DevBuf<double> partial, sr_partial, gpartial;  // partial sums of dot / sr_reduce / multi_dot, each zeroed once: slots a short rank never writes stay 0
+  DevBuf<double> sc, hdev;                       // device scalars; coefficients of basis_update
+  int g_m = 0;
+  enum { RES, OP, W0, W1, W2, BASIS, N_ROLES };
+  std::vector<double*> rows[N_ROLES];            // what the Vec handles name: per role, one pointer per local rank (set by begin)
+  explicit DistKrylov(Comm& cc) : c(cc), M(cc.members), R(cc.members.size()) {
+    sext.resize(R); w.resize(R);
+    for (size_t i = 0; i < R; ++i) {
       sext[i].alloc((size_t)std::max<int64_t>(1, M[i]->next(0)));
-      w[i].alloc((size_t)std::max<int64_t>(1, M[i]->n(0)));
+      w[i].alloc((size_t)std::max<int64_t>(1, n(i)));
       HIPCHK(hipMemsetAsync(sext[i].p, 0, std::max<int64_t>(1, M[i]->next(0)) * sizeof(double), c.compute));
     }
-    partial.alloc((size_t)KR_BLOCKS * M.size());
+    partial.alloc((size_t)KR_BLOCKS * R);
     sc.alloc(64);
-    HIPCHK(hipMemsetAsync(partial.p, 0, (size_t)KR_BLOCKS * M.size() * sizeof(double), c.compute));    // slots a short rank never writes stay 0
+    HIPCHK(hipMemsetAsync(partial.p, 0, (size_t)KR_BLOCKS * R * sizeof(double), c.compute));
     HIPCHK(hipMemsetAsync(sc.p, 0, 64 * sizeof(double), c.compute));
   }
+  int64_t n(size_t i) const { return M[i]->n(0); }
+  Handle& top(size_t i) { return *M[i]->top; }
   static int nb(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(KR_BLOCKS, (n + BLOCK - 1) / BLOCK)); }
-  double* d(size_t i) { return M[i]->bext[0].p; }              // residual = right-hand side of the cycle
-  // sc[slot] = sum over all ranks of <a_i, b_i> (owned entries)
-  void dot(const std::vector<const double*>& a, const std::vector<const double*>& b, int slot) {
-    for (size_t i = 0; i < M.size(); ++i) {
-      const int64_t n = M[i]->n(0);
-      if (n) hipLaunchKernelGGL(kr_dot_partial_kernel, dim3(nb(n)), dim3(BLOCK), 0, c.compute, n, a[i], b[i], partial.p + i * KR_BLOCKS);
+  int grid(size_t i) const { return Handle::grid_for(n(i)); }
+  double* at(Vec v, size_t i) const { return v.p[i] + v.col * n(i); }
+  const double* at(CVec v, size_t i) const { return v.p[i] + v.col * n(i); }
+  void name(int role, Bufs& b) { rows[role].resize(R); for (size_t i = 0; i < R; ++i) rows[role][i] = b[i].p; }
+  void alloc_owned(Bufs& b, size_t vectors) { b.clear(); b.resize(R); for (size_t i = 0; i < R; ++i) b[i].alloc(vectors * (size_t)std::max<int64_t>(1, n(i))); }
+
+  void begin(Form f, int restart) {
+    rows[RES].resize(R);
+    for (size_t i = 0; i < R; ++i) rows[RES][i] = M[i]->bext[0].p;        // residual = right-hand side of the cycle
+    name(OP, sext); name(W0, w);
+    if (f == Form::CG_SR) {
+      if (sr_p.size() != R) {
+        alloc_owned(sr_p, 1); alloc_owned(sr_s, 1);
+        sr_partial.alloc((size_t)2 * KR_BLOCKS * R);
+        HIPCHK(hipMemsetAsync(sr_partial.p, 0, (size_t)2 * KR_BLOCKS * R * sizeof(double), c.compute));
+      }
+      name(W1, sr_p); name(W2, sr_s);
     }
-    hipLaunchKernelGGL(kr_dot_final_kernel, dim3(1), dim3(BLOCK), 0, c.compute, (int)(KR_BLOCKS * M.size()), partial.p, sc.p + slot);
-    HIPCHK(hipGetLastError());
-    if (c.kind == AMGX_COMM_RCCL && (c.nranks > 1 || M[0]->force_allgather))      // (world 1: only when the collectives are forced)
-      NCCLCHK(Rccl::get().AllReduce(sc.p + slot, sc.p + slot, 1, ncclDouble, ncclSum, c.nccl, c.compute));
+    if (f == Form::GMRES) {
+      if (restart > 40) throw Err("amgx_dist_gmres: restart lengths above 40 are not supported (got " + std::to_string(restart) + ")");
+      const int m = std::max(1, restart);
+      if (g_m < m || gV.size() != R) {
+        alloc_owned(gV, (size_t)(m + 1)); alloc_owned(gt, 1);
+        gpartial.alloc((size_t)KR_BLOCKS * 64 * R);
+        HIPCHK(hipMemsetAsync(gpartial.p, 0, (size_t)KR_BLOCKS * 64 * R * sizeof(double), c.compute));
+        hdev.alloc(64);
+        g_m = m;
+      }
+      name(W1, gt); name(BASIS, gV);
+    }
   }
-  double read(int slot) {
-    double v = 0.0;
-    HIPCHK(hipMemcpyAsync(&v, sc.p + slot, sizeof(double), hipMemcpyDeviceToHost, c.compute));
-    HIPCHK(hipStreamSynchronize(c.compute));
-    return v;
-  }
-  // y_i = A_i [v_i | ghosts of v]: exchange of the ghost part of vext behind the interior rows
+  Vec residual_vec() { return {rows[RES].data(), 0}; }
+  Vec operand() { return {rows[OP].data(), 0}; }
+  Vec work(int k) { return {rows[W0 + k].data(), 0}; }
+  Vec basis(int j) { return {rows[BASIS].data(), j}; }
+
+  // rows(i, span) for every rank behind the owner -> ghost exchange of the operand buffer: interior rows before it ends
   template <class F>
-  void with_halo(std::vector<DevBuf<double>>& vext, F&& rows) {
+  void with_halo(F&& rows_of) {
     std::vector<Comm::Item> it;
-    for (size_t i = 0; i < M.size(); ++i) it.push_back({&M[i]->halo[0], vext[i].p});
+    for (size_t i = 0; i < R; ++i) it.push_back({&M[i]->halo[0], sext[i].p});
     const int tk = c.exchange_begin(it);
     const bool ov = M[0]->overlap;
-    if (ov) for (size_t i = 0; i < M.size(); ++i) rows(i, Handle::Span{Handle::PART_INT, M[i]->n_int_span(0)});
+    if (ov) for (size_t i = 0; i < R; ++i) rows_of(i, Handle::Span{Handle::PART_INT, M[i]->n_int_span(0)});
     c.exchange_end(tk);
-    for (size_t i = 0; i < M.size(); ++i) rows(i, ov ? Handle::Span{Handle::PART_BND, M[i]->n_int_span(0)} : Handle::Span());
+    for (size_t i = 0; i < R; ++i) rows_of(i, ov ? Handle::Span{Handle::PART_BND, M[i]->n_int_span(0)} : Handle::Span());
   }
-  void precond(bool use_pre) {                   // w = C d
-    if (!use_pre) { for (size_t i = 0; i < M.size(); ++i) M[i]->top->copy(w[i].p, d(i), M[i]->n(0)); return; }
-    std::vector<const double*> bp(M.size());
-    std::vector<double*> xp(M.size());
-    for (size_t i = 0; i < M.size(); ++i) { bp[i] = d(i); xp[i] = w[i].p; }
-    dist_apply(c, bp.data(), xp.data(), 1, AMGX_DEVICE_PTR);
+  void residual(CVec x, CVec b, Vec r) {
+    copy(operand(), x);
+    with_halo([&](size_t i, Handle::Span sp) { top(i).residual(top(i).lev[0].A, sext[i].p, at(b, i), at(r, i), sp); });
   }
-  int pcg(const double* const* b, double* const* x, double tol, int maxit, bool use_pre, double* errs) {
-    const size_t R = M.size();
-    std::vector<const double*> wv(R), dv(R), sv(R);
-    for (size_t i = 0; i < R; ++i) { wv[i] = w[i].p; dv[i] = d(i); sv[i] = sext[i].p; }
-    // d = b - A x
-    for (size_t i = 0; i < R; ++i) M[i]->top->copy(sext[i].p, x[i], M[i]->n(0));
-    with_halo(sext, [&](size_t i, Handle::Span sp) { M[i]->top->residual(M[i]->top->lev[0].A, sext[i].p, b[i], d(i), sp); });
-    precond(use_pre);
-    for (size_t i = 0; i < R; ++i) M[i]->top->copy(sext[i].p, w[i].p, M[i]->n(0));
-    constexpr int SAS = 2;
-    int cur = 1;
-    dot(wv, dv, cur);
-    const double err0 = std::sqrt(std::fabs(read(cur)));
-    if (errs) errs[0] = err0;
-    if (err0 == 0.0) return 0;
-    int it = 0;
-    for (it = 1; it <= maxit; ++it) {
-      with_halo(sext, [&](size_t i, Handle::Span sp) { M[i]->top->mult(M[i]->top->lev[0].A, sext[i].p, w[i].p, sp); });     // w = A s
-      const int old = cur;
-      cur = 1 - cur;
-      dot(sv, wv, SAS);
-      for (size_t i = 0; i < R; ++i) {
-        const int64_t n = M[i]->n(0);
-        if (n) hipLaunchKernelGGL(kr_cg_update_kernel, dim3(Handle::grid_for(n)), dim3(BLOCK), 0, c.compute, n, sc.p, old, SAS, sext[i].p, w[i].p, x[i], d(i));
-      }
-      precond(use_pre);
-      dot(wv, dv, cur);
-      for (size_t i = 0; i < R; ++i) {
-        const int64_t n = M[i]->n(0);
-        if (n) hipLaunchKernelGGL(kr_xpby_kernel, dim3(Handle::grid_for(n)), dim3(BLOCK), 0, c.compute, n, sc.p, cur, old, w[i].p, sext[i].p);
-      }
-      HIPCHK(hipGetLastError());
-      const double err = std::sqrt(std::fabs(read(cur)));
-      if (errs) errs[it] = err;
-      if (err <= tol * err0) break;
-    }
-    if (it > maxit) it = maxit;
-    return it;
+  void mult(CVec v, Vec y) {
+    copy(operand(), v);
+    with_halo([&](size_t i, Handle::Span sp) { top(i).mult(top(i).lev[0].A, sext[i].p, at(y, i), sp); });
+  }
+  void precond(CVec r, Vec z, bool use_pre) {
+    copy(use_pre ? residual_vec() : z, r);
+    if (!use_pre) return;
+    std::vector<double*> xp(R);
+    for (size_t i = 0; i < R; ++i) xp[i] = at(z, i);
+    dist_apply(c, rows[RES].data(), xp.data(), 1, AMGX_DEVICE_PTR);
   }
 
-  // ---- single-reduction PCG over the ranks (Krylov::pcg_sr): u = C r, w = A u, ONE ncclAllReduce of (gamma, delta) per iteration
-  // instead of two all-reduces of one scalar; the residual lives in the cycle's right-hand-side buffer, u in the [owned | ghost]
-  // buffer the level-0 product reads
-  std::vector<DevBuf<double>> sr_p, sr_s;
-  DevBuf<double> sr_partial;
-  int pcg_sr(const double* const* b, double* const* x, double tol, int maxit, double* errs) {
-    const size_t R = M.size();
-    if (sr_p.size() != R) {
-      sr_p.clear(); sr_s.clear(); sr_p.resize(R); sr_s.resize(R);
-      for (size_t i = 0; i < R; ++i) { sr_p[i].alloc((size_t)std::max<int64_t>(1, M[i]->n(0))); sr_s[i].alloc((size_t)std::max<int64_t>(1, M[i]->n(0))); }
-      sr_partial.alloc((size_t)2 * KR_BLOCKS * R);
-      HIPCHK(hipMemsetAsync(sr_partial.p, 0, (size_t)2 * KR_BLOCKS * R * sizeof(double), c.compute));
-    }
-    for (size_t i = 0; i < R; ++i) { M[i]->top->zero(sr_p[i].p, M[i]->n(0)); M[i]->top->zero(sr_s[i].p, M[i]->n(0)); }
-    const double one = 1.0;
-    HIPCHK(hipMemcpyAsync(sc.p + SR_FIRST, &one, sizeof(double), hipMemcpyHostToDevice, c.compute));
-    auto precond_u = [&]() {                               // u = C r, written into the owned part of sext
-      std::vector<const double*> bp(R);
-      std::vector<double*> xp(R);
-      for (size_t i = 0; i < R; ++i) { bp[i] = d(i); xp[i] = sext[i].p; }
-      dist_apply(c, bp.data(), xp.data(), 1, AMGX_DEVICE_PTR);
-    };
-    auto av = [&]() { with_halo(sext, [&](size_t i, Handle::Span sp) { M[i]->top->mult(M[i]->top->lev[0].A, sext[i].p, w[i].p, sp); }); };   // w = A u
-    auto reduce = [&]() {
-      for (size_t i = 0; i < R; ++i) {
-        const int64_t n = M[i]->n(0);
-        if (n) hipLaunchKernelGGL(kr_dot2_partial_kernel, dim3(nb(n)), dim3(BLOCK), 0, c.compute, n, d(i), sext[i].p, w[i].p, sr_partial.p + (size_t)i * 2 * KR_BLOCKS);
-      }
-      hipLaunchKernelGGL(kr_sr_reduce_kernel, dim3(2), dim3(BLOCK), 0, c.compute, (int)R, sr_partial.p, sc.p);
-      HIPCHK(hipGetLastError());
-      if (c.kind == AMGX_COMM_RCCL && (c.nranks > 1 || M[0]->force_allgather))
-        NCCLCHK(Rccl::get().AllReduce(sc.p + SR_GNEW, sc.p + SR_GNEW, 2, ncclDouble, ncclSum, c.nccl, c.compute));
-      hipLaunchKernelGGL(kr_sr_scalars_kernel, dim3(1), dim3(1), 0, c.compute, sc.p);
-      HIPCHK(hipGetLastError());
-    };
-    // r = b - A x
-    for (size_t i = 0; i < R; ++i) M[i]->top->copy(sext[i].p, x[i], M[i]->n(0));
-    with_halo(sext, [&](size_t i, Handle::Span sp) { M[i]->top->residual(M[i]->top->lev[0].A, sext[i].p, b[i], d(i), sp); });
-    precond_u();
-    av();
-    reduce();
-    const double err0 = std::sqrt(std::fabs(read(SR_GOLD)));
-    if (errs) errs[0] = err0;
-    if (err0 == 0.0) return 0;
-    int it = 0;
-    for (it = 1; it <= maxit; ++it) {
-      for (size_t i = 0; i < R; ++i) {
-        const int64_t n = M[i]->n(0);
-        if (n) hipLaunchKernelGGL(kr_sr_update_kernel, dim3(Handle::grid_for(n)), dim3(BLOCK), 0, c.compute, n, sc.p, sext[i].p, w[i].p, sr_p[i].p, sr_s[i].p, x[i], d(i));
-      }
-      precond_u();
-      av();
-      reduce();
-      const double err = std::sqrt(std::fabs(read(SR_GOLD)));
-      if (errs) errs[it] = err;
-      if (err <= tol * err0) break;
-    }
-    if (it > maxit) it = maxit;
-    return it;
-  }
-
-  // ---- restarted GMRES(m), left-preconditioned, over the ranks: Krylov::gmres with rank-local vectors.  The Arnoldi inner
-  // products h = V^T w are ONE fused local pass + ONE ncclAllReduce of j + 1 scalars per Gram-Schmidt pass (the reference's
-  // driver is ngsolve.krylovspace.GMRes on ParallelVectors: one MPI all-reduce per inner product); Givens rotations on the
-  // host, identically on every rank (all ranks read the same reduced values).  err_k = |C r_k|, stop at err_k <= tol * err_0.
-  std::vector<DevBuf<double>> gV, gt;      // per local rank: basis (m + 1) x n_owned, work vector
-  DevBuf<double> hdev, gpartial;
-  int g_m = 0;
-  // sc[0 .. m) = sum over all ranks of <V_j, w> (owned entries)
-  void multi_dot(int m, const std::vector<double*>& w) {
-    if (m > 48) throw Err("multi_dot: too many vectors");
-    for (size_t i = 0; i < M.size(); ++i) {
-      const int64_t n = M[i]->n(0);
-      if (n) hipLaunchKernelGGL(kr_multi_dot_partial_kernel, dim3(nb(n)), dim3(BLOCK), 0, c.compute, n, m, gV[i].p, n, w[i], gpartial.p + (size_t)i * 64 * KR_BLOCKS);
-    }
-    hipLaunchKernelGGL(kr_dist_multi_final_kernel, dim3(m), dim3(BLOCK), 0, c.compute, (int)M.size(), gpartial.p, sc.p);
-    HIPCHK(hipGetLastError());
+  // (world 1: the all-reduce runs only when the collectives are forced)
+  void all_reduce(int s, size_t count) {
     if (c.kind == AMGX_COMM_RCCL && (c.nranks > 1 || M[0]->force_allgather))
-      NCCLCHK(Rccl::get().AllReduce(sc.p, sc.p, (size_t)m, ncclDouble, ncclSum, c.nccl, c.compute));
+      NCCLCHK(Rccl::get().AllReduce(sc.p + s, sc.p + s, count, ncclDouble, ncclSum, c.nccl, c.compute));
   }
-  void read_n(int m, double* out) {
-    HIPCHK(hipMemcpyAsync(out, sc.p, m * sizeof(double), hipMemcpyDeviceToHost, c.compute));
+  void dot(CVec a, CVec b, int s) {
+    for (size_t i = 0; i < R; ++i)
+      if (n(i)) launch(kr_dot_partial_kernel, nb(n(i)), BLOCK, 0, c.compute, n(i), at(a, i), at(b, i), partial.p + i * KR_BLOCKS);
+    launch(kr_dot_final_kernel, 1, BLOCK, 0, c.compute, (int)(KR_BLOCKS * R), partial.p, sc.p + s);
+    all_reduce(s, 1);
+  }
+  void multi_dot(int m, CVec v) {
+    if (m > 48) throw Err("multi_dot: too many vectors");
+    for (size_t i = 0; i < R; ++i)
+      if (n(i)) launch(kr_multi_dot_partial_kernel, nb(n(i)), BLOCK, 0, c.compute, n(i), m, gV[i].p, n(i), at(v, i), gpartial.p + i * 64 * KR_BLOCKS);
+    launch(kr_dist_multi_final_kernel, m, BLOCK, 0, c.compute, (int)R, gpartial.p, sc.p);
+    all_reduce(0, (size_t)m);
+  }
+  void sr_reduce(CVec r, CVec u, CVec v) {
+    for (size_t i = 0; i < R; ++i)
+      if (n(i)) launch(kr_dot2_partial_kernel, nb(n(i)), BLOCK, 0, c.compute, n(i), at(r, i), at(u, i), at(v, i), sr_partial.p + i * 2 * KR_BLOCKS);
+    launch(kr_sr_reduce_kernel, 2, BLOCK, 0, c.compute, (int)R, sr_partial.p, sc.p);
+    all_reduce(SR_GNEW, 2);
+    launch(kr_sr_scalars_kernel, 1, 1, 0, c.compute, sc.p);
+  }
+  double read(int s) {
+    double v = 0.0;
+    read(s, 1, &v);
+    return v;
+  }
+  void read(int s0, int m, double* out) {
+    HIPCHK(hipMemcpyAsync(out, sc.p + s0, m * sizeof(double), hipMemcpyDeviceToHost, c.compute));
     HIPCHK(hipStreamSynchronize(c.compute));
   }
-  void precond_vec(const std::vector<double*>& r, const std::vector<double*>& z, bool use_pre) {      // z = C r (r is copied into the cycle's rhs buffer)
-    for (size_t i = 0; i < M.size(); ++i) M[i]->top->copy(use_pre ? d(i) : z[i], r[i], M[i]->n(0));
-    if (!use_pre) return;
-    std::vector<const double*> bp(M.size());
-    std::vector<double*> xp(M.size());
-    for (size_t i = 0; i < M.size(); ++i) { bp[i] = d(i); xp[i] = z[i]; }
-    dist_apply(c, bp.data(), xp.data(), 1, AMGX_DEVICE_PTR);
+  void write(int s, double v) { HIPCHK(hipMemcpyAsync(sc.p + s, &v, sizeof(double), hipMemcpyHostToDevice, c.compute)); }
+
+  void copy(Vec dst, CVec src) { for (size_t i = 0; i < R; ++i) top(i).copy(at(dst, i), at(src, i), n(i)); }
+  void zero(Vec a, Vec b) { for (size_t i = 0; i < R; ++i) { top(i).zero(at(a, i), n(i)); top(i).zero(at(b, i), n(i)); } }
+  void scale(double alpha, CVec x, Vec y) {
+    for (size_t i = 0; i < R; ++i) if (n(i)) launch(kr_scale_kernel, grid(i), BLOCK, 0, c.compute, n(i), alpha, at(x, i), at(y, i), 0);
   }
-  void matvec(const std::vector<double*>& v, const std::vector<double*>& y) {                         // y = A v (level 0, ghosts of v exchanged)
-    for (size_t i = 0; i < M.size(); ++i) M[i]->top->copy(sext[i].p, v[i], M[i]->n(0));
-    with_halo(sext, [&](size_t i, Handle::Span sp) { M[i]->top->mult(M[i]->top->lev[0].A, sext[i].p, y[i], sp); });
+  void cg_update(int num, int den, CVec s, CVec q, Vec x, Vec d) {
+    for (size_t i = 0; i < R; ++i) if (n(i)) launch(kr_cg_update_kernel, grid(i), BLOCK, 0, c.compute, n(i), sc.p, num, den, at(s, i), at(q, i), at(x, i), at(d, i));
   }
-  int gmres(const double* const* b, double* const* x, double tol, int maxit, int restart, bool use_pre, double* errs) {
-    if (restart > 40) throw Err("amgx_dist_gmres: restart lengths above 40 are not supported (got " + std::to_string(restart) + ")");
-    const int m = std::max(1, restart);
-    const size_t R = M.size();
-    if (g_m < m || gV.size() != R) {
-      gV.clear(); gt.clear(); gV.resize(R); gt.resize(R);
-      for (size_t i = 0; i < R; ++i) { gV[i].alloc((size_t)(m + 1) * std::max<int64_t>(1, M[i]->n(0))); gt[i].alloc((size_t)std::max<int64_t>(1, M[i]->n(0))); }
-      gpartial.alloc((size_t)KR_BLOCKS * 64 * R);      // (its own buffer: slots a short rank never writes must stay 0, here and in dot())
-      HIPCHK(hipMemsetAsync(gpartial.p, 0, (size_t)KR_BLOCKS * 64 * R * sizeof(double), c.compute));
-      hdev.alloc(64);
-      g_m = m;
-    }
-    auto grid = [&](size_t i) { return Handle::grid_for(M[i]->n(0)); };
-    auto vj = [&](int j) { std::vector<double*> v(R); for (size_t i = 0; i < R; ++i) v[i] = gV[i].p + (size_t)j * M[i]->n(0); return v; };
-    std::vector<double*> wv(R), tv(R), xv(R);
-    for (size_t i = 0; i < R; ++i) { wv[i] = w[i].p; tv[i] = gt[i].p; xv[i] = x[i]; }
-    std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), hcol(m + 1), hc2(m + 1), y(m);
-    int it = 0;
-    double err0 = -1.0;
-    while (it < maxit) {
-      // t = b - A x
-      for (size_t i = 0; i < R; ++i) M[i]->top->copy(sext[i].p, x[i], M[i]->n(0));
-      with_halo(sext, [&](size_t i, Handle::Span sp) { M[i]->top->residual(M[i]->top->lev[0].A, sext[i].p, b[i], tv[i], sp); });
-      precond_vec(tv, vj(0), use_pre);                       // v_0 = C t (not yet normalised)
-      { std::vector<const double*> a(R), bb(R); for (size_t i = 0; i < R; ++i) { a[i] = vj(0)[i]; bb[i] = a[i]; } dot(a, bb, 0); }
-      const double beta = std::sqrt(read(0));
-      if (err0 < 0.0) { err0 = beta; if (errs) errs[0] = err0; }
-      if (beta == 0.0 || beta <= tol * err0) break;
-      for (size_t i = 0; i < R; ++i) if (M[i]->n(0)) hipLaunchKernelGGL(kr_scale_kernel, dim3(grid(i)), dim3(BLOCK), 0, c.compute, M[i]->n(0), 1.0 / beta, vj(0)[i], vj(0)[i], 0);
-      std::fill(g.begin(), g.end(), 0.0);
-      g[0] = beta;
-      int j = 0;
-      bool done = false;
-      for (j = 0; j < m && it < maxit; ++j) {
-        ++it;
-        matvec(vj(j), tv);
-        precond_vec(tv, wv, use_pre);                        // w = C A v_j
-        std::fill(hcol.begin(), hcol.end(), 0.0);
-        for (int pass = 0; pass < 2; ++pass) {
-          multi_dot(j + 1, wv);
-          read_n(j + 1, hc2.data());
-          HIPCHK(hipMemcpyAsync(hdev.p, hc2.data(), (j + 1) * sizeof(double), hipMemcpyHostToDevice, c.compute));
-          for (size_t i = 0; i < R; ++i) if (M[i]->n(0)) hipLaunchKernelGGL(kr_multi_axpy_kernel, dim3(grid(i)), dim3(BLOCK), 0, c.compute, M[i]->n(0), j + 1, gV[i].p, M[i]->n(0), hdev.p, -1.0, wv[i]);
-          HIPCHK(hipStreamSynchronize(c.compute));           // hc2 is reused by the next pass
-          for (int i = 0; i <= j; ++i) hcol[i] += hc2[i];
-        }
-        { std::vector<const double*> a(R); for (size_t i = 0; i < R; ++i) a[i] = wv[i]; dot(a, a, 0); }
-        const double hn = std::sqrt(read(0));
-        hcol[j + 1] = hn;
-        if (hn > 0.0) for (size_t i = 0; i < R; ++i) if (M[i]->n(0)) hipLaunchKernelGGL(kr_scale_kernel, dim3(grid(i)), dim3(BLOCK), 0, c.compute, M[i]->n(0), 1.0 / hn, wv[i], vj(j + 1)[i], 0);
-        for (int i = 0; i < j; ++i) {                        // previous rotations
-          const double a = cs[i] * hcol[i] + sn[i] * hcol[i + 1];
-          hcol[i + 1] = -sn[i] * hcol[i] + cs[i] * hcol[i + 1];
-          hcol[i] = a;
-        }
-        const double den = std::hypot(hcol[j], hcol[j + 1]);
-        cs[j] = den > 0 ? hcol[j] / den : 1.0;
-        sn[j] = den > 0 ? hcol[j + 1] / den : 0.0;
-        hcol[j] = den;
-        g[j + 1] = -sn[j] * g[j];
-        g[j] = cs[j] * g[j];
-        for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] = hcol[i];
-        const double err = std::fabs(g[j + 1]);
-        if (errs) errs[it] = err;
-        if (err <= tol * err0 || hn == 0.0) { done = true; ++j; break; }
-      }
-      const int k = j;
-      for (int i = k - 1; i >= 0; --i) {
-        double sacc = g[i];
-        for (int q = i + 1; q < k; ++q) sacc -= H[(size_t)i * m + q] * y[q];
-        const double piv = H[(size_t)i * m + i];
-        y[i] = piv != 0.0 ? sacc / piv : 0.0;
-      }
-      if (k > 0) {
-        HIPCHK(hipMemcpyAsync(hdev.p, y.data(), k * sizeof(double), hipMemcpyHostToDevice, c.compute));
-        for (size_t i = 0; i < R; ++i) if (M[i]->n(0)) hipLaunchKernelGGL(kr_multi_axpy_kernel, dim3(grid(i)), dim3(BLOCK), 0, c.compute, M[i]->n(0), k, gV[i].p, M[i]->n(0), hdev.p, 1.0, xv[i]);
-        HIPCHK(hipStreamSynchronize(c.compute));
-      }
-      if (done) break;
-    }
-    HIPCHK(hipGetLastError());
-    return it;
+  void xpby(int num, int den, CVec v, Vec s) {
+    for (size_t i = 0; i < R; ++i) if (n(i)) launch(kr_xpby_kernel, grid(i), BLOCK, 0, c.compute, n(i), sc.p, num, den, at(v, i), at(s, i));
+  }
+  void sr_update(CVec u, CVec v, Vec p, Vec s, Vec x, Vec r) {
+    for (size_t i = 0; i < R; ++i) if (n(i)) launch(kr_sr_update_kernel, grid(i), BLOCK, 0, c.compute, n(i), sc.p, at(u, i), at(v, i), at(p, i), at(s, i), at(x, i), at(r, i));
+  }
+  void basis_update(int m, const double* coef, double sign, Vec v) {
+    HIPCHK(hipMemcpyAsync(hdev.p, coef, m * sizeof(double), hipMemcpyHostToDevice, c.compute));
+    for (size_t i = 0; i < R; ++i) if (n(i)) launch(kr_multi_axpy_kernel, grid(i), BLOCK, 0, c.compute, n(i), m, gV[i].p, n(i), hdev.p, sign, at(v, i));
+    HIPCHK(hipStreamSynchronize(c.compute));
   }
 };
 
@@ -1218,6 +1097,30 @@ int cguard(amgx_comm cc, F&& f) {
     if (cc && cc->c) cc->c->err = e.what(); else g_create_err = e.what();
     return 1;
   }
+}
+
+// argument checks of the rank solvers.  fn: the entry point's name, so every Err text names its caller; bad_args: the entry
+// point's own test of its scalar arguments (amgx_dist_gmres also rejects restart < 1), evaluated there because b and x are read
+// here only after it; alias_note: what the entry point appends to the aliasing message (amgx_dist_pcg says why, amgx_dist_gmres "")
+void check_dist_solve(const char* fn, amgx::Comm& c, bool bad_args, const double* const* b, double* const* x, int flags, const char* alias_note) {
+  const std::string f(fn);
+  if (bad_args) throw amgx::Err(f + ": bad arguments");
+  if (!(flags & AMGX_DEVICE_PTR)) throw amgx::Err(f + ": device vectors only (AMGX_DEVICE_PTR)");
+  if (c.members.empty() || (c.kind == AMGX_COMM_LOCAL && (int)c.members.size() != c.nranks)) throw amgx::Err(f + ": not all ranks have a hierarchy");
+  for (size_t i = 0; i < c.members.size(); ++i) {
+    amgx::Dist* d = c.members[i];
+    if ((!b[i] || !x[i]) && d->n(0) > 0) throw amgx::Err(f + ": null vector");
+    if (b[i] == d->bext[0].p || x[i] == d->bext[0].p) throw amgx::Err(f + ": b / x alias the cycle's right-hand-side buffer" + alias_note);
+  }
+}
+// the workspace lives with the communicator: the preconditioner's whole-cycle graph is keyed on the vector addresses, so a
+// second solve replays the graph of the first instead of capturing a new one (and leaving a stale one behind)
+amgx::DistKrylov& dist_krylov(amgx::Comm& c) {
+  if (!c.krylov_ws || c.krylov_members != c.members.size()) {
+    c.krylov_ws = std::shared_ptr<void>(new amgx::DistKrylov(c), [](void* p) { delete static_cast<amgx::DistKrylov*>(p); });
+    c.krylov_members = c.members.size();
+  }
+  return *static_cast<amgx::DistKrylov*>(c.krylov_ws.get());
 }
 }  // namespace
 
@@ -1388,22 +1291,10 @@ int amgx_dist_time_kernel(amgx_comm cc, int level, int op, int reps, double* avg
 int amgx_dist_pcg(amgx_comm cc, const double* const* b, double* const* x, double tol, int maxit, int use_precond, int flags, double* errs,
                   int32_t* iters) {
   return cguard(cc, [&](amgx::Comm& c) {
-    if (!b || !x || maxit < 0) throw amgx::Err("amgx_dist_pcg: bad arguments");
-    if (!(flags & AMGX_DEVICE_PTR)) throw amgx::Err("amgx_dist_pcg: device vectors only (AMGX_DEVICE_PTR)");
-    if (c.members.empty() || (c.kind == AMGX_COMM_LOCAL && (int)c.members.size() != c.nranks)) throw amgx::Err("amgx_dist_pcg: not all ranks have a hierarchy");
-    for (size_t i = 0; i < c.members.size(); ++i) {
-      amgx::Dist* d = c.members[i];
-      if ((!b[i] || !x[i]) && d->n(0) > 0) throw amgx::Err("amgx_dist_pcg: null vector");
-      if (b[i] == d->bext[0].p || x[i] == d->bext[0].p) throw amgx::Err("amgx_dist_pcg: b / x alias the cycle's right-hand-side buffer (it holds the residual)");
-    }
-    // the workspace lives with the communicator: the preconditioner's whole-cycle graph is keyed on the vector addresses, so a
-    // second solve replays the graph of the first instead of capturing a new one (and leaving a stale one behind)
-    if (!c.krylov_ws || c.krylov_members != c.members.size()) {
-      c.krylov_ws = std::shared_ptr<void>(new amgx::DistKrylov(c), [](void* p) { delete static_cast<amgx::DistKrylov*>(p); });
-      c.krylov_members = c.members.size();
-    }
-    amgx::DistKrylov& K = *static_cast<amgx::DistKrylov*>(c.krylov_ws.get());
-    const int it = ((flags & AMGX_PCG_SINGLE_REDUCTION) && use_precond) ? K.pcg_sr(b, x, tol, maxit, errs) : K.pcg(b, x, tol, maxit, use_precond != 0, errs);
+    check_dist_solve("amgx_dist_pcg", c, !b || !x || maxit < 0, b, x, flags, " (it holds the residual)");
+    amgx::DistKrylov& K = dist_krylov(c);
+    const amgx::DistKrylov::Vec xv{x, 0};
+    const int it = ((flags & AMGX_PCG_SINGLE_REDUCTION) && use_precond) ? amgx::pcg_sr(K, b, xv, tol, maxit, errs) : amgx::pcg(K, b, xv, tol, maxit, use_precond != 0, errs);
     if (iters) *iters = it;
   });
 }
@@ -1411,20 +1302,8 @@ int amgx_dist_pcg(amgx_comm cc, const double* const* b, double* const* x, double
 int amgx_dist_gmres(amgx_comm cc, const double* const* b, double* const* x, double tol, int maxit, int restart, int use_precond, int flags,
                     double* errs, int32_t* iters) {
   return cguard(cc, [&](amgx::Comm& c) {
-    if (!b || !x || maxit < 0 || restart < 1) throw amgx::Err("amgx_dist_gmres: bad arguments");
-    if (!(flags & AMGX_DEVICE_PTR)) throw amgx::Err("amgx_dist_gmres: device vectors only (AMGX_DEVICE_PTR)");
-    if (c.members.empty() || (c.kind == AMGX_COMM_LOCAL && (int)c.members.size() != c.nranks)) throw amgx::Err("amgx_dist_gmres: not all ranks have a hierarchy");
-    for (size_t i = 0; i < c.members.size(); ++i) {
-      amgx::Dist* d = c.members[i];
-      if ((!b[i] || !x[i]) && d->n(0) > 0) throw amgx::Err("amgx_dist_gmres: null vector");
-      if (b[i] == d->bext[0].p || x[i] == d->bext[0].p) throw amgx::Err("amgx_dist_gmres: b / x alias the cycle's right-hand-side buffer");
-    }
-    if (!c.krylov_ws || c.krylov_members != c.members.size()) {
-      c.krylov_ws = std::shared_ptr<void>(new amgx::DistKrylov(c), [](void* p) { delete static_cast<amgx::DistKrylov*>(p); });
-      c.krylov_members = c.members.size();
-    }
-    amgx::DistKrylov& K = *static_cast<amgx::DistKrylov*>(c.krylov_ws.get());
-    const int it = K.gmres(b, x, tol, maxit, restart, use_precond != 0, errs);
+    check_dist_solve("amgx_dist_gmres", c, !b || !x || maxit < 0 || restart < 1, b, x, flags, "");
+    const int it = amgx::gmres(dist_krylov(c), b, amgx::DistKrylov::Vec{x, 0}, tol, maxit, restart, use_precond != 0, errs);
     if (iters) *iters = it;
   });
 }

@@ -6,6 +6,7 @@
 // Reductions are deterministic: a fixed grid of workgroups writes partial sums, one workgroup adds them in a fixed order.
 // The scalars of the recurrences (alpha, beta) stay on the device; kernels read them from memory.
 #pragma once
+#include "krylov_core.hpp"       // pcg, pcg_sr, gmres over a space; the SR_* scalar slots
 
 namespace amgx {
 
@@ -131,8 +132,6 @@ __global__ __launch_bounds__(BLOCK) void kr_dot2_partial_kernel(int64_t n, const
     partial[KR_BLOCKS + blockIdx.x] = s1;
   }
 }
-// scalar slots of the single-reduction recurrence
-enum { SR_GOLD = 0, SR_GNEW = 1, SR_DELTA = 2, SR_ALPHA = 3, SR_BETA = 4, SR_FIRST = 5 };
 // sc[SR_GNEW], sc[SR_DELTA] = sums of the n_local x KR_BLOCKS partials of the two products (fixed order); two workgroups
 __global__ __launch_bounds__(BLOCK) void kr_sr_reduce_kernel(int n_local, const double* __restrict__ partial, double* __restrict__ sc) {
   __shared__ double red[BLOCK];
@@ -169,11 +168,17 @@ __global__ __launch_bounds__(BLOCK) void kr_sr_update_kernel(int64_t n, const do
   r[i] -= alpha * si;
 }
 
+// The single-rank space of krylov_core.hpp: one pointer per vector, the operator and the cycle of one handle, every sum in one
+// ticketed launch.  Built per solve (its constructor re-arms the scalars and the ticket).
 struct Krylov {
+  using Vec = double*;
+  using CVec = const double*;
   Handle& h;
   int64_t n;
-  DevBuf<double> partial, sc;              // partial sums; device scalars
+  DevBuf<double> partial, sc, hdev;        // partial sums; device scalars; coefficients of basis_update
   DevBuf<unsigned int> ticket;             // kr_dot_kernel's arrival counter (0 between launches)
+  bool sr_partial_clean = false;
+  int res = 0, op = 0, work_[3] = {0, 0, 0};     // Handle::kr_ws slots of the residual, the operand of A and the work vectors
   explicit Krylov(Handle& hh) : h(hh), n(hh.lev[0].len()) {
     if (hh.lev[0].n != hh.lev[0].ncols) throw Err("Krylov solvers need a square level-0 matrix (single rank)");
     partial.alloc((size_t)KR_BLOCKS * 64);
@@ -183,190 +188,79 @@ struct Krylov {
     HIPCHK(hipMemsetAsync(ticket.p, 0, sizeof(unsigned int), h.stream));
   }
   int nb() const { return (int)std::max<int64_t>(1, std::min<int64_t>(KR_BLOCKS, (n + BLOCK - 1) / BLOCK)); }
-  void dot(const double* a, const double* b, int slot) {
-    hipLaunchKernelGGL(kr_dot_kernel, dim3(nb()), dim3(BLOCK), 0, h.stream, n, a, b, partial.p, ticket.p, sc.p + slot);
-    HIPCHK(hipGetLastError());
-  }
-  void multi_dot(int m, const double* V, const double* w, int slot0) {
-    if (m > 48) throw Err("multi_dot: too many vectors");
-    hipLaunchKernelGGL(kr_multi_dot_partial_kernel, dim3(nb()), dim3(BLOCK), 0, h.stream, n, m, V, n, w, partial.p);
-    hipLaunchKernelGGL(kr_dot_final_kernel, dim3(m), dim3(BLOCK), 0, h.stream, nb(), partial.p, sc.p + slot0);
-    HIPCHK(hipGetLastError());
-  }
-  double read(int slot) {
-    double v = 0.0;
-    HIPCHK(hipMemcpyAsync(&v, sc.p + slot, sizeof(double), hipMemcpyDeviceToHost, h.stream));
-    HIPCHK(hipStreamSynchronize(h.stream));
-    return v;
-  }
-  void read(int slot0, int m, double* out) {
-    HIPCHK(hipMemcpyAsync(out, sc.p + slot0, m * sizeof(double), hipMemcpyDeviceToHost, h.stream));
-    HIPCHK(hipStreamSynchronize(h.stream));
-  }
   int grid() const { return Handle::grid_for(n); }
   // work vectors live in the handle (grow-only) and keep their addresses from solve to solve: the cycle's graph is keyed on the
   // (right-hand side, result) pointers, so a solver that allocated per call paid a fresh capture + instantiation -- and the
   // hipMalloc / hipFree of its vectors (GMRES(30) at cfg 2: 2.6 GB) -- on every solve
-  struct WsBuf { double* p; };
-  WsBuf ws(int slot, size_t count) {
-    DevBuf<double>& b = h.kr_ws[slot];
+  double* ws(int s, size_t count) {
+    DevBuf<double>& b = h.kr_ws[s];
     if (b.n < count) b.alloc(count);
-    return WsBuf{b.p};
+    return b.p;
   }
+  // Handle::kr_ws slots by role: 0 / 1 / 2 serve CG (which feeds s = slot 2 to A), 0 .. 4 the single-reduction form (which feeds
+  // u = slot 1), 5 / 1 / 2 GMRES (basis, w, t)
+  void begin(Form f, int restart) {
+    int first = 0, last = 2;                 // the slots of n entries this form uses
+    if (f == Form::CG) { res = 0; work_[0] = 1; op = 2; }
+    else if (f == Form::CG_SR) { res = 0; op = 1; work_[0] = 2; work_[1] = 3; work_[2] = 4; last = 4; }
+    else {
+      // (the basis lives in HBM: (restart + 1) vectors; multi_dot handles up to 48 of them per pass)
+      if (restart > 40) throw Err("amgx_gmres: restart lengths above 40 are not supported (got " + std::to_string(restart) + ")");
+      ws(5, (size_t)(std::max(1, restart) + 1) * n);
+      work_[0] = 1; work_[1] = 2; first = 1;
+      res = op = work_[2] = 5;               // GMRES has no residual / operand / third work vector: a use would name the basis, never an unsized slot
+    }
+    for (int s = first; s <= last; ++s) ws(s, n);
+    if (f == Form::GMRES) hdev.alloc(64);
+  }
+  Vec residual_vec() { return h.kr_ws[res].p; }
+  Vec operand() { return h.kr_ws[op].p; }
+  Vec work(int k) { return h.kr_ws[work_[k]].p; }
+  Vec basis(int j) { return h.kr_ws[5].p + (size_t)j * n; }
 
-  // x = b - A x style helpers through the handle's SpMV kernels
-  void precond(const double* r, double* z, bool use_pre) {
+  void residual(CVec x, CVec b, Vec r) { h.residual(h.lev[0].A, x, b, r); }
+  void mult(CVec v, Vec y) { h.mult(h.lev[0].A, v, y); }
+  void precond(CVec r, Vec z, bool use_pre) {
     if (use_pre) h.run_cycle(z, r, true);
     else h.copy(z, r, n);
   }
 
-  // preconditioned CG (NGSolve CGSolver as the reference's drivers use it: err_k = sqrt(|<C r_k, r_k>|), stop at
-  // err_k <= tol * err_0; reference tests/h1/amg_utils.py:337-363).  x holds the initial guess.
-  int pcg(const double* b, double* x, double tol, int maxit, bool use_pre, double* errs) {
-    WsBuf d = ws(0, n), w = ws(1, n), s = ws(2, n);
-    constexpr int SAS = 2;                                   // scalar slots: 0 / 1 = <w, d> of the last two iterations, 2 = <s, A s>
-    h.residual(h.lev[0].A, x, b, d.p);                       // d = b - A x
-    precond(d.p, w.p, use_pre);
-    h.copy(s.p, w.p, n);
-    int cur = 1;
-    dot(w.p, d.p, cur);
-    const double err0 = std::sqrt(std::fabs(read(cur)));
-    if (errs) errs[0] = err0;
-    if (err0 == 0.0) return 0;
-    int it = 0;
-    for (it = 1; it <= maxit; ++it) {
-      h.mult(h.lev[0].A, s.p, w.p);                          // w = A s
-      const int old = cur;
-      cur = 1 - cur;
-      dot(s.p, w.p, SAS);
-      hipLaunchKernelGGL(kr_cg_update_kernel, dim3(grid()), dim3(BLOCK), 0, h.stream, n, sc.p, old, SAS, s.p, w.p, x, d.p);   // alpha = <w,d> / <s, A s>
-      precond(d.p, w.p, use_pre);
-      dot(w.p, d.p, cur);
-      hipLaunchKernelGGL(kr_xpby_kernel, dim3(grid()), dim3(BLOCK), 0, h.stream, n, sc.p, cur, old, w.p, s.p);               // beta = <w,d>_new / <w,d>_old
-      HIPCHK(hipGetLastError());
-      const double err = std::sqrt(std::fabs(read(cur)));
-      if (errs) errs[it] = err;
-      if (err <= tol * err0) break;
-    }
-    if (it > maxit) it = maxit;
-    return it;
+  void dot(CVec a, CVec b, int s) { launch(kr_dot_kernel, nb(), BLOCK, 0, h.stream, n, a, b, partial.p, ticket.p, sc.p + s); }
+  void multi_dot(int m, CVec w) {
+    if (m > 48) throw Err("multi_dot: too many vectors");
+    launch(kr_multi_dot_partial_kernel, nb(), BLOCK, 0, h.stream, n, m, basis(0), n, w, partial.p);
+    launch(kr_dot_final_kernel, m, BLOCK, 0, h.stream, nb(), partial.p, sc.p);
   }
-
-  // The same preconditioned CG with ONE reduction point per iteration (Chronopoulos / Gear): u = C r, w = A u, gamma = <r, u> and
-  // delta = <w, u> in one fused pass, alpha and beta from (gamma, delta) on the device, then p, s, x, r in one fused pass -- three
-  // launches per iteration beside the cycle and the level-0 product instead of five, and one device -> host scalar.  Mathematically
-  // the recurrence of pcg() (alpha_k = gamma_k / (delta_k - beta_k gamma_k / alpha_{k-1}) equals <C r, r> / <p, A p>); the rounding
-  // differs, histories agree to ~1e-6 (tests/test_gpu_krylov.py).  err_k = sqrt(|<C r_k, r_k>|) as in pcg().
-  int pcg_sr(const double* b, double* x, double tol, int maxit, double* errs) {
-    WsBuf r = ws(0, n), u = ws(1, n), w = ws(2, n), p = ws(3, n), s = ws(4, n);
-    h.zero(p.p, n); h.zero(s.p, n);
-    const double one = 1.0;
-    HIPCHK(hipMemcpyAsync(sc.p + SR_FIRST, &one, sizeof(double), hipMemcpyHostToDevice, h.stream));
-    auto reduce = [&]() {
-      hipLaunchKernelGGL(kr_dot2_partial_kernel, dim3(nb()), dim3(BLOCK), 0, h.stream, n, r.p, u.p, w.p, partial.p);
-      hipLaunchKernelGGL(kr_sr_reduce_kernel, dim3(2), dim3(BLOCK), 0, h.stream, 1, partial.p, sc.p);
-      hipLaunchKernelGGL(kr_sr_scalars_kernel, dim3(1), dim3(1), 0, h.stream, sc.p);
-      HIPCHK(hipGetLastError());
-    };
-    h.residual(h.lev[0].A, x, b, r.p);                       // r = b - A x
-    precond(r.p, u.p, true);
-    h.mult(h.lev[0].A, u.p, w.p);
-    HIPCHK(hipMemsetAsync(partial.p, 0, (size_t)2 * KR_BLOCKS * sizeof(double), h.stream));   // (slots a short vector never writes)
-    reduce();
-    const double err0 = std::sqrt(std::fabs(read(SR_GOLD)));
-    if (errs) errs[0] = err0;
-    if (err0 == 0.0) return 0;
-    int it = 0;
-    for (it = 1; it <= maxit; ++it) {
-      hipLaunchKernelGGL(kr_sr_update_kernel, dim3(grid()), dim3(BLOCK), 0, h.stream, n, sc.p, u.p, w.p, p.p, s.p, x, r.p);
-      precond(r.p, u.p, true);
-      h.mult(h.lev[0].A, u.p, w.p);
-      reduce();
-      const double err = std::sqrt(std::fabs(read(SR_GOLD)));
-      if (errs) errs[it] = err;
-      if (err <= tol * err0) break;
+  void sr_reduce(CVec r, CVec u, CVec w) {
+    if (!sr_partial_clean) {                 // (slots a short vector never writes)
+      HIPCHK(hipMemsetAsync(partial.p, 0, (size_t)2 * KR_BLOCKS * sizeof(double), h.stream));
+      sr_partial_clean = true;
     }
-    if (it > maxit) it = maxit;
-    return it;
+    launch(kr_dot2_partial_kernel, nb(), BLOCK, 0, h.stream, n, r, u, w, partial.p);
+    launch(kr_sr_reduce_kernel, 2, BLOCK, 0, h.stream, 1, partial.p, sc.p);
+    launch(kr_sr_scalars_kernel, 1, 1, 0, h.stream, sc.p);
   }
+  double read(int s) {
+    double v = 0.0;
+    read(s, 1, &v);
+    return v;
+  }
+  void read(int s0, int m, double* out) {
+    HIPCHK(hipMemcpyAsync(out, sc.p + s0, m * sizeof(double), hipMemcpyDeviceToHost, h.stream));
+    HIPCHK(hipStreamSynchronize(h.stream));
+  }
+  void write(int s, double v) { HIPCHK(hipMemcpyAsync(sc.p + s, &v, sizeof(double), hipMemcpyHostToDevice, h.stream)); }
 
-  // restarted GMRES(m), left-preconditioned: minimises |C (b - A x)|; classical Gram-Schmidt with one re-orthogonalisation
-  // pass (two fused passes over the basis instead of 2 j dependent dot / axpy pairs), Givens rotations on the host.
-  // err_k = |C r_k| (the recurrence value), stop at err_k <= tol * err_0.
-  int gmres(const double* b, double* x, double tol, int maxit, int restart, bool use_pre, double* errs) {
-    // (the basis lives in HBM: (restart + 1) vectors; multi_dot handles up to 48 of them per pass)
-    if (restart > 40) throw Err("amgx_gmres: restart lengths above 40 are not supported (got " + std::to_string(restart) + ")");
-    const int m = std::max(1, restart);
-    WsBuf V = ws(5, (size_t)(m + 1) * n), w = ws(1, n), t = ws(2, n);
-    DevBuf<double> hdev;
-    hdev.alloc(64);
-    std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), hcol(m + 1), hc2(m + 1), y(m);
-    int it = 0;
-    double err0 = -1.0;
-    while (it < maxit) {
-      h.residual(h.lev[0].A, x, b, t.p);                     // t = b - A x
-      precond(t.p, V.p, use_pre);                            // v_0 = C t (not yet normalised)
-      dot(V.p, V.p, 0);
-      const double beta = std::sqrt(read(0));
-      if (err0 < 0.0) { err0 = beta; if (errs) errs[0] = err0; }
-      if (beta == 0.0 || beta <= tol * err0) break;
-      hipLaunchKernelGGL(kr_scale_kernel, dim3(grid()), dim3(BLOCK), 0, h.stream, n, 1.0 / beta, V.p, V.p, 0);
-      std::fill(g.begin(), g.end(), 0.0);
-      g[0] = beta;
-      int j = 0;
-      bool done = false;
-      for (j = 0; j < m && it < maxit; ++j) {
-        ++it;
-        h.mult(h.lev[0].A, V.p + (size_t)j * n, t.p);
-        precond(t.p, w.p, use_pre);                          // w = C A v_j
-        std::fill(hcol.begin(), hcol.end(), 0.0);
-        for (int pass = 0; pass < 2; ++pass) {
-          multi_dot(j + 1, V.p, w.p, 0);
-          read(0, j + 1, hc2.data());
-          HIPCHK(hipMemcpyAsync(hdev.p, hc2.data(), (j + 1) * sizeof(double), hipMemcpyHostToDevice, h.stream));
-          hipLaunchKernelGGL(kr_multi_axpy_kernel, dim3(grid()), dim3(BLOCK), 0, h.stream, n, j + 1, V.p, n, hdev.p, -1.0, w.p);
-          HIPCHK(hipStreamSynchronize(h.stream));            // hc2 is reused by the next pass
-          for (int i = 0; i <= j; ++i) hcol[i] += hc2[i];
-        }
-        dot(w.p, w.p, 0);
-        const double hn = std::sqrt(read(0));
-        hcol[j + 1] = hn;
-        if (hn > 0.0) hipLaunchKernelGGL(kr_scale_kernel, dim3(grid()), dim3(BLOCK), 0, h.stream, n, 1.0 / hn, w.p, V.p + (size_t)(j + 1) * n, 0);
-        for (int i = 0; i < j; ++i) {                        // previous rotations
-          const double a = cs[i] * hcol[i] + sn[i] * hcol[i + 1];
-          hcol[i + 1] = -sn[i] * hcol[i] + cs[i] * hcol[i + 1];
-          hcol[i] = a;
-        }
-        const double den = std::hypot(hcol[j], hcol[j + 1]);
-        cs[j] = den > 0 ? hcol[j] / den : 1.0;
-        sn[j] = den > 0 ? hcol[j + 1] / den : 0.0;
-        hcol[j] = den;
-        g[j + 1] = -sn[j] * g[j];
-        g[j] = cs[j] * g[j];
-        for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] = hcol[i];
-        const double err = std::fabs(g[j + 1]);
-        if (errs) errs[it] = err;
-        if (err <= tol * err0 || hn == 0.0) { done = true; ++j; break; }
-      }
-      // y = H^-1 g (upper triangular), x += V y
-      const int k = j;
-      for (int i = k - 1; i >= 0; --i) {
-        double sacc = g[i];
-        for (int q = i + 1; q < k; ++q) sacc -= H[(size_t)i * m + q] * y[q];
-        const double piv = H[(size_t)i * m + i];
-        // a zero pivot = the Krylov space stopped growing with a singular projected system (breakdown without convergence,
-        // e.g. a singular operator): that direction gets no update instead of an inf / nan
-        y[i] = piv != 0.0 ? sacc / piv : 0.0;
-      }
-      if (k > 0) {
-        HIPCHK(hipMemcpyAsync(hdev.p, y.data(), k * sizeof(double), hipMemcpyHostToDevice, h.stream));
-        hipLaunchKernelGGL(kr_multi_axpy_kernel, dim3(grid()), dim3(BLOCK), 0, h.stream, n, k, V.p, n, hdev.p, 1.0, x);
-        HIPCHK(hipStreamSynchronize(h.stream));
-      }
-      if (done) break;
-    }
-    HIPCHK(hipGetLastError());
-    return it;
+  void copy(Vec dst, CVec src) { h.copy(dst, src, n); }
+  void zero(Vec a, Vec b) { h.zero(a, n); h.zero(b, n); }
+  void scale(double alpha, CVec x, Vec y) { launch(kr_scale_kernel, grid(), BLOCK, 0, h.stream, n, alpha, x, y, 0); }
+  void cg_update(int num, int den, CVec s, CVec q, Vec x, Vec d) { launch(kr_cg_update_kernel, grid(), BLOCK, 0, h.stream, n, sc.p, num, den, s, q, x, d); }
+  void xpby(int num, int den, CVec w, Vec s) { launch(kr_xpby_kernel, grid(), BLOCK, 0, h.stream, n, sc.p, num, den, w, s); }
+  void sr_update(CVec u, CVec w, Vec p, Vec s, Vec x, Vec r) { launch(kr_sr_update_kernel, grid(), BLOCK, 0, h.stream, n, sc.p, u, w, p, s, x, r); }
+  void basis_update(int m, const double* c, double sign, Vec w) {
+    HIPCHK(hipMemcpyAsync(hdev.p, c, m * sizeof(double), hipMemcpyHostToDevice, h.stream));
+    launch(kr_multi_axpy_kernel, grid(), BLOCK, 0, h.stream, n, m, basis(0), n, hdev.p, sign, w);
+    HIPCHK(hipStreamSynchronize(h.stream));
   }
 };
 
@@ -383,7 +277,7 @@ int amgx_pcg(amgx_handle hh, const double* b, double* x, double tol, int maxit, 
     double* dx = st.inout(1, x, n, true, 0);
     if (use_precond && (db == h.lev[0].x.p || dx == h.lev[0].x.p)) throw amgx::Err("amgx_pcg: vectors alias the handle's work vectors");
     amgx::Krylov K(h);
-    const int it = ((flags & AMGX_PCG_SINGLE_REDUCTION) && use_precond) ? K.pcg_sr(db, dx, tol, maxit, errs) : K.pcg(db, dx, tol, maxit, use_precond != 0, errs);
+    const int it = ((flags & AMGX_PCG_SINGLE_REDUCTION) && use_precond) ? amgx::pcg_sr(K, db, dx, tol, maxit, errs) : amgx::pcg(K, db, dx, tol, maxit, use_precond != 0, errs);
     if (iters) *iters = it;
     st.out(1, x, n, 0);
     st.finish();
@@ -400,7 +294,7 @@ int amgx_gmres(amgx_handle hh, const double* b, double* x, double tol, int maxit
     double* dx = st.inout(1, x, n, true, 0);
     if (use_precond && (db == h.lev[0].x.p || dx == h.lev[0].x.p)) throw amgx::Err("amgx_gmres: vectors alias the handle's work vectors");
     amgx::Krylov K(h);
-    const int it = K.gmres(db, dx, tol, maxit, restart, use_precond != 0, errs);
+    const int it = amgx::gmres(K, db, dx, tol, maxit, restart, use_precond != 0, errs);
     if (iters) *iters = it;
     st.out(1, x, n, 0);
     st.finish();

@@ -648,6 +648,70 @@ def test_distributed_solvers_from_initial_guess_equal_serial_oracle(R, box, dmin
     assert np.linalg.norm(got - xo) <= 1e-7 * np.linalg.norm(xo)
 
 
+def test_distributed_solvers_with_a_rank_without_rows():
+    """the three rank solvers on the communicator of test_loopback_device_rank_without_rows (virtual rank 0 owns nothing: it launches
+    nothing element-wise and its partial sums read 0), cold start, against the serial oracle on the concatenated system with the
+    tolerances of test_distributed_solvers_from_initial_guess_equal_serial_oracle"""
+    import scipy.sparse as sp
+    import torch
+    from ngsamg_amd import bridge as B, dist as D
+    from oracle.pyoracle import Oracle
+    from tests.dist_oracle import oracle_sm_types
+    pgrid, gshape = (2, 2, 1), (17, 17, 9)
+    R = 5
+    comm = D.LoopbackComm(R)
+    locs = []
+    for r in range(R - 1):
+        L, _ = B.shared_poisson_partition(r, pgrid, gshape)
+        L.rank = r + 1
+        L.dist_procs = [np.asarray(p) + 1 for p in L.dist_procs]
+        locs.append(L)
+    empty = B.SharedLocal(0, sp.csr_matrix((0, 0)), [], free=np.zeros(0, dtype=np.uint8), coords=np.zeros((0, 3)))
+    states, vmaps = B.from_shared_layout(comm, [empty] + locs)
+    assert states[0].n == 0
+    amg = D.DistributedAMG(comm, states, dim=3, dist_min_rows=60, device=0, max_coarse_size=10, sm_type="jacobi", hgs_block_rows=256,
+                           gs_stage_min_rows=50)
+    rng = np.random.default_rng(1)
+    bh = [rng.standard_normal(s.n) * s.free for s in states]
+    bs = [torch.from_numpy(b).cuda() for b in bh]
+    bg = np.concatenate(bh)
+    orc = Oracle(amg.global_levels(), sm_type=oracle_sm_types(amg))
+
+    def start():
+        return [torch.zeros(s.n, dtype=torch.float64, device="cuda") for s in states]
+
+    def result(xs):
+        torch.cuda.synchronize()
+        return np.concatenate([x.cpu().numpy() for x in xs])
+
+    xo, ito, erro = orc.pcg(bg, tol=1e-8, maxit=100)
+    xs = start()
+    it, errs = amg.pcg(bs, xs, tol=1e-8, maxsteps=100)
+    got = result(xs)
+    print(f"pcg: it {it} / {ito}, history {np.max(np.abs(errs - erro[:it + 1])) / erro[0]:.2e} err_0")
+    assert it == ito
+    assert np.all(np.abs(errs - erro) <= 1e-6 * erro[0]) and np.allclose(errs[:5], erro[:5], rtol=1e-9)
+    assert np.linalg.norm(got - xo) <= 1e-8 * np.linalg.norm(xo)
+
+    xs = start()
+    it, errs = amg.pcg(bs, xs, tol=1e-8, maxsteps=100, single_reduction=True)
+    got = result(xs)
+    print(f"pcg, single reduction: it {it} / {ito}")
+    assert abs(it - ito) <= 1
+    k = min(it, ito)
+    assert np.allclose(errs[:k], erro[:k], rtol=1e-6)
+    assert np.linalg.norm(got - xo) <= 1e-7 * np.linalg.norm(xo)
+
+    xo, ito, erro = orc.gmres(bg, tol=1e-9, maxit=150, restart=12)
+    xs = start()
+    it, errs = amg.gmres(bs, xs, tol=1e-9, maxsteps=150, restart=12)
+    got = result(xs)
+    print(f"gmres(12): it {it} / {ito}")
+    assert it == ito
+    assert errs.shape == erro.shape and np.all(np.abs(errs - erro) <= 1e-6 * erro[0])
+    assert np.linalg.norm(got - xo) <= 1e-7 * np.linalg.norm(xo)
+
+
 @pytest.mark.parametrize("R,box,dmin", [(2, (14, 12, 12), 100), (4, (10, 10, 10), 50), (3, (9, 12, 12), 80)])
 def test_distributed_first_history_entry_is_the_exact_global_norm(R, box, dmin):
     """amg.pcg(use_pre=False) from x = 0: err_0 = sqrt(<b, b>) summed over the ranks.  Integer entries make every partial sum exact,
