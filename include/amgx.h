@@ -263,8 +263,12 @@ int amgx_matrix_stream_bytes(amgx_handle h, int level, int which, int64_t* bytes
  *   30 form 4: the general sweep reads the local-window image
  *   31 form 2: bitmask of the lanes per block row W (1, 2, 4, 8) its colours launch with
  *   32 form 4: blocks of the local-window image that keep global 32-bit columns
+ *   33 form 4: the fused residual + restriction kernel the down pass of the cycle runs after the sweep from zero: 0 none (separate
+ *      residual and restriction, also on a level whose down pass is not the plain one-step sweep), 1 sliced-ELL, 2 sliced-ELL with
+ *      row windows, 3 local-window sliced-ELL (the image of the couplings the sweep did not use).  (The rank-partitioned driver
+ *      calls the same kernels on its own condition; this entry describes the single-rank cycle.)
  * Returns 0, or non-zero for a bad level or n_out < 1. */
-#define AMGX_LEVEL_PATHS_N 33
+#define AMGX_LEVEL_PATHS_N 34
 int amgx_level_paths(amgx_handle h, int level, int64_t* out, int n_out);
 
 /* measurement hook for bench.py: launches one hot-path kernel `reps` times on the handle's stream,

@@ -269,6 +269,7 @@ struct DevRestrict {                    // column-blocked P^T (see restrict_chun
   // consecutive ones (-1: no slice); empty = consecutive slices
   DevBuf<int32_t> slice_list;
   bool empty() const { return n_chunks == 0; }
+  RestrictMat view() const { return RestrictMat{chunk_slot.p, slot_ptr.p, w.p, fi.p, part.p, dest.p}; }
 };
 
 // symmetric diagonal image of a scalar Jacobi level's A for the fused down kernel (dia_pre_restrict_kernel; host/dia.hpp):
@@ -2001,7 +2002,7 @@ struct Handle {
             if (FB != SELL_WIN || G != 1) throw Err("fused restriction on a windowed image: unexpected chunk shape");
             auto run = [&](auto EPT) {
               launch(sell_win_pre_restrict_kernel<SELL_WIN, EPT()>, grid, SELL_WIN, 0, stream, L.Apre.n_rows, c0, L.Apre.sell.view(), L.Apre.sell.rowloc.p, b,
-                     L.dinv.p, L.omega, epf, x, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+                     L.dinv.p, L.omega, epf, x, R.view());
             };
             if (!dispatch<4>(R.ept, run)) run(Int<6>{});
           } else if (G > 1) {
@@ -2089,8 +2090,8 @@ struct Handle {
       if (nch != R.n_chunks) throw Err("fused Gauss-Seidel residual: chunk / slice mismatch");
       auto run = [&](auto EPT) {
         if (M.sell.win)
-          launch(sell_win_cres_restrict_kernel<SELL_WIN, EPT()>, nch, SELL_WIN, 0, stream, M.n_rows, M.sell.view(), M.sell.rowloc.p, x, L.gsb.cvec.p, R.chunk_slot.p,
-                 R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+          launch(sell_win_pre_restrict_kernel<SELL_WIN, EPT(), 1>, nch, SELL_WIN, 0, stream, M.n_rows, 0, M.sell.view(), M.sell.rowloc.p, x, L.gsb.cvec.p, 0.0, 0, nullptr,
+                 R.view());
         else
           launch(sell_pre_restrict_kernel<512, 1, EPT()>, nch, 512, 0, stream, M.n_rows, 0, M.n_slices, M.sell.view(), x, L.gsb.cvec.p, 0.0, 0, nullptr, nullptr,
                  R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, nullptr);
@@ -3706,6 +3707,8 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
         v[29] = gsb.mid;
         v[30] = gsb.lw;
         v[32] = gsb.has_fullLW ? gsb.flw_no_window : 0;
+        // (the form gsb_residual_restrict picks; only where the cycle's down pass runs it)
+        if (down == amgx::DOWN_GSB) v[33] = !gsb.restLW.empty() ? 3 : gsb.rest.sell.win ? 2 : 1;
         break;
       case amgx::SWEEP_MC: v[20] = gs.lanes; v[21] = amgx::BLOCK; v[23] = gs.n_colors; v[25] = gs.has_split; break;
       case amgx::SWEEP_MC_BSELL: v[21] = amgx::BLOCK; v[23] = gs.n_colors; v[25] = gs.bsplit; break;

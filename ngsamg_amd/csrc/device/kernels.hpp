@@ -86,6 +86,43 @@ __device__ __forceinline__ void ld_nt_pair(const V* __restrict__ p, V& a, V& b) 
   else { a = ld_nt(p); b = ld_nt(p + 1); }
 }
 
+// sum of acc over the G neighbouring lanes that share a row (G = 1: acc itself); every lane of the group receives it.
+// The fused down kernels use it.  The kernels outside that family keep the loop written out: through the helper the compiler
+// schedules each of them differently (same registers, other instruction order), and their code stays as compiled before.
+template <int G>
+__device__ __forceinline__ double lane_group_sum(double acc) {
+#pragma unroll
+  for (int o = G >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, G);
+  return acc;
+}
+
+// Stages a gathered vector in LDS: xw[k] = src[ccol[k0 + k]] for the k1 - k0 <= CAP listed columns of unit c (the chunk or window of
+// a workgroup of TB threads).  request() issues the loads into registers and consumes nothing, so that they travel beside the
+// caller's other prologue loads; publish() writes them to LDS: every thread of the workgroup takes part, the caller's barrier follows.
+// (sell_lw_pre_restrict_kernel, sell_lw_win_spmv_kernel; the local-window branch of gsb_sweep_kernel holds the same steps between
+// its own phases and keeps them written out: with the helper its instruction order changes.)
+template <int CAP, int TB>
+struct LdsWindow {
+  static constexpr int NQ = (CAP + TB - 1) / TB;
+  int k0, k1;
+  double xv[NQ];
+  __device__ __forceinline__ void request(int c, const int32_t* __restrict__ cptr, const int32_t* __restrict__ ccol, const double* __restrict__ src) {
+    k0 = cptr[c]; k1 = cptr[c + 1];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int k = k0 + threadIdx.x + q * TB;
+      xv[q] = k < k1 ? src[ccol[k]] : 0.0;
+    }
+  }
+  __device__ __forceinline__ void publish(double* xw) const {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int k = threadIdx.x + q * TB;
+      if (k0 + k < k1) xw[k] = xv[q];
+    }
+  }
+};
+
 // ---------------------------------------------------------------------------------------------------
 // scalar epilogue
 // have_xd: xd is the value of the gathered vector at the own row (EP_JAC: yin[row], EP_PRE: b[row]) and need not be loaded
@@ -1273,6 +1310,18 @@ __global__ __launch_bounds__(BLOCK) void bgsb_sweep_kernel(int BB, int block0, c
 constexpr int RESTRICT_CHUNK = 1024;          // fine rows per workgroup
 constexpr int RESTRICT_MAX_ENTRIES = 4096;    // entries of P per chunk (P has <= sp_max_per_row entries per row)
 
+// device view of the chunk-local transpose of P (DevRestrict)
+struct RestrictMat {
+  const int32_t* chunk_slot;  // [n_chunks + 1] first slot of every chunk
+  const int32_t* slot_ptr;    // [n_slots + 1] first entry of every slot
+  const double* w;            // [entries] weight
+  const uint16_t* fi;         // [entries] fine row inside the chunk
+  double* part;               // [n_slots] partial sums, added per coarse row by restrict_sum_kernel
+  const int32_t* dest;        // optional (AMGX_RSUM_SORT=1): slot -> place in part, the partials of one coarse row next to each other,
+                              //   so that restrict_sum_kernel streams them -- scattered stores here instead of scattered loads there;
+                              //   measured slower overall
+};
+
 // phase A: every thread streams entries (coalesced, independent loads) and leaves the products in LDS;
 // phase B: one thread per (chunk, coarse column) slot adds its contiguous segment of products.
 __global__ __launch_bounds__(BLOCK) void restrict_chunk_kernel(int64_t n_fine, const int32_t* __restrict__ chunk_slot,
@@ -1300,22 +1349,91 @@ __global__ __launch_bounds__(BLOCK) void restrict_chunk_kernel(int64_t n_fine, c
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The fused "down" kernels: pre-smoothing (or the residual after a sweep), r = b - A x and the chunk-local P^T r in one pass.  A
+// workgroup of FB threads owns one chunk of rows; r never goes to HBM: it is left in LDS, multiplied with the chunk-local transpose
+// of P (entries: fp64 weight + 16-bit local row) and reduced per (chunk, coarse column) slot; restrict_sum_kernel then adds the ~10
+// partial sums of every coarse row in a fixed order.  Every kernel of the family is
+//     ChunkRestrict::request  ->  its own row product, r of the chunk's rows into LDS, a barrier  ->  ChunkRestrict::reduce
+// and differs from the others in the row product alone (SELL slice, windowed SELL, local-window SELL; dia_pre_restrict_kernel runs
+// the same steps from its own copy, see there).
+//
+// ChunkRestrict<FB, EPT>: the restriction half.  EPT = entries of P per thread the chunk may hold (chosen per level by build_restrict
+// from the fullest chunk).
+// request(c, R) asks for the chunk-local restriction data of this thread FIRST, so that it arrives while the row product streams the
+// matrix; reduce() after the barrier then touches LDS only.  NOTHING request() loads may be CONSUMED before the row product: a
+// subtraction on a freshly loaded slot pointer there made every wave wait for all of its restriction data -- two full memory round
+// trips -- before it requested a byte of the matrix.  Hence the raw slot pointers pa_raw / pb_raw, rebased in reduce().
+// reduce(r_lds, pr, R): r_lds holds r of the chunk's rows (the caller's barrier has passed); pr = EPT * FB doubles of LDS.
+template <int FB, int EPT>
+struct ChunkRestrict {
+  int s1, e0, e1, myslot, mydest, pa_raw, pb_raw;
+  double wq[EPT];
+  int fq[EPT];
+  __device__ __forceinline__ void request(int c, const RestrictMat& R) {
+    const int s0 = R.chunk_slot[c];
+    s1 = R.chunk_slot[c + 1];
+    e0 = R.slot_ptr[s0];
+    e1 = R.slot_ptr[s1];
+#pragma unroll
+    for (int q = 0; q < EPT; ++q) {
+      const int e = e0 + threadIdx.x + q * FB;
+      wq[q] = e < e1 ? ld_nt(R.w + e) : 0.0;
+      fq[q] = e < e1 ? (int)ld_nt(R.fi + e) : 0;
+    }
+    myslot = s0 + threadIdx.x;
+    mydest = myslot; pa_raw = 0; pb_raw = 0;
+    if (myslot < s1) {
+      if (R.dest) mydest = R.dest[myslot];
+      pa_raw = R.slot_ptr[myslot];
+      pb_raw = R.slot_ptr[myslot + 1];
+    }
+  }
+  __device__ __forceinline__ void reduce(const double* r_lds, double* pr, const RestrictMat& R) const {
+#pragma unroll
+    for (int q = 0; q < EPT; ++q) {
+      const int e = threadIdx.x + q * FB;
+      if (e0 + e < e1) pr[e] = wq[q] * r_lds[fq[q]];
+    }
+    __syncthreads();
+    if (myslot < s1) {
+      const int pa = pa_raw - e0, pb = pb_raw - e0;
+      double acc = 0.0;
+      for (int k = pa; k < pb; ++k) acc += pr[k];
+      R.part[mydest] = acc;
+    }
+    for (int slot = myslot + FB; slot < s1; slot += FB) {     // chunks with more slots than threads
+      const int a = R.slot_ptr[slot] - e0, bnd = R.slot_ptr[slot + 1] - e0;
+      double acc = 0.0;
+      for (int k = a; k < bnd; ++k) acc += pr[k];
+      R.part[R.dest ? R.dest[slot] : slot] = acc;
+    }
+  }
+};
+
+// x_i = omega * Dinv_i * b_i of the Jacobi pre-smoothing from zero (EPF_FOLD: smoothed once more, + omega * Dinv_i * r_i)
+template <class I>
+__device__ __forceinline__ void jacobi_down_store(double bi, double di, double r, double omega, int nt, double* __restrict__ x, I row) {
+  double xi = omega * (di * bi);
+  if (nt & EPF_FOLD) xi += omega * (di * r);
+  if (nt & EPF_NT) __builtin_nontemporal_store(xi, x + row);
+  else x[row] = xi;
+}
+
 // Fused Jacobi pre-smoothing + restriction for big scalar levels (the level-0 hot spot):
 //   x = omega*Dinv*b,  r = b - A'b  (EP_PRE, one pass over the column-scaled image),  part = chunk-local P^T r
-// One 1024-thread workgroup owns 16 consecutive SELL slices = FUSED_CHUNK rows; r never goes to HBM: it is left in
-// LDS, multiplied with the chunk-local transpose of P (entries: fp64 weight + 16-bit local row) and reduced per
-// (chunk, coarse column) slot; restrict_sum_kernel then adds the ~10 partial sums of every coarse row in a fixed
-// order.  Replaces: 80 MB write of r + the P^T gather kernel (134 us at cfg 2, TA/L2-bound).
+// One workgroup owns FUSED_BLOCK / 64 consecutive SELL slices.
+// Replaces: 80 MB write of r + the P^T gather kernel (134 us at cfg 2, TA/L2-bound).
 // FB = workgroup size = rows per chunk (1024 or 512); 4 entries of P per row at most
 // MODE 0: Jacobi pre-smoothing as described above.  MODE 1: residual after a block-hybrid Gauss-Seidel sweep from zero,
 // r = c .* x - A_rest x (EP_CRES; b = the swept x, dinv = c, nothing written to x), with the same chunk-local restriction.
 // MODE 2: residual after Chebyshev pre-smoothing on the level's SELL image of A itself, r = rhs - A x (b = the smoothed x that is
 // gathered, dinv = the right-hand side, nothing written to x), with the same chunk-local restriction.
-// EPT: entries of P per thread the chunk may hold (4: prolongations with <= 3 entries per row; 6: the up to 5 of the reference's
-// "classic" rows; chosen per level by build_restrict from the fullest chunk)
+// EPT: 4: prolongations with <= 3 entries per row; 6: the up to 5 of the reference's "classic" rows
 // G = lanes per row (SELL-G image, long rows of the coarser levels): the chunk then holds FUSED_BLOCK / G rows, the G partial
 // row sums are combined by a wave shuffle and the first lane of every group runs the epilogue
 // V = float (MODE 2 only): A is the single-precision image of the level
+// (This kernel and sell_lw_pre_restrict_kernel take the six pointers of RestrictMat one by one: with the struct as a kernel argument
+// the compiler holds more of them in scalar registers across the row product -- 2 to 6 SGPRs more here, one fewer there.)
 template <int FUSED_BLOCK, int MODE = 0, int EPT = 4, int G = 1, class V = double>
 __global__ __launch_bounds__(FUSED_BLOCK) void sell_pre_restrict_kernel(int64_t n_rows, int chunk0, int n_slices, SellMatT<V> M,
                                                                         const double* __restrict__ b, const double* __restrict__ dinv,
@@ -1326,10 +1444,10 @@ __global__ __launch_bounds__(FUSED_BLOCK) void sell_pre_restrict_kernel(int64_t 
                                                                         double* __restrict__ part,
                                                                         const int32_t* __restrict__ dest,
                                                                         const int32_t* __restrict__ slice_list = nullptr) {
-  constexpr int FUSED_MAX_ENTRIES = EPT * FUSED_BLOCK;
+  const RestrictMat R{chunk_slot, slot_ptr, w, fi, part, dest};
   constexpr int RPC = FUSED_BLOCK / G;         // rows per chunk
   __shared__ double rl[RPC];
-  __shared__ double pr[FUSED_MAX_ENTRIES];
+  __shared__ double pr[EPT * FUSED_BLOCK];
   const int lane = threadIdx.x & (WAVE - 1);
   const int c = chunk0 + sell_unit(M);         // chunk0: first chunk of the launch (interior / boundary chunks of a rank-partitioned level)
   // compact chunks (G == 1, cluster_slices): the chunk's slices come from a list (-1: none) instead of being consecutive
@@ -1339,97 +1457,44 @@ __global__ __launch_bounds__(FUSED_BLOCK) void sell_pre_restrict_kernel(int64_t 
   const int row = s * (WAVE / G) + lane / G;
   const int lrow = (threadIdx.x >> 6) * (WAVE / G) + lane / G;     // row inside the chunk
   const bool writer = (lane % G) == 0;
-  // the chunk-local restriction data of this thread is requested FIRST, so that it arrives while the row product
-  // streams A'; the epilogue after the barriers then touches LDS only
-  // (nothing in this prologue is CONSUMED before the row product: a subtraction on a freshly loaded slot pointer here made
-  // every wave wait for all of its restriction data -- two full memory round trips -- before it requested a byte of A')
   const bool has_slice = s < n_slices;
   const int64_t sp0 = has_slice ? M.slice_ptr[s] : 0, sp1 = has_slice ? M.slice_ptr[s + 1] : 0;
-  const int s0 = chunk_slot[c], s1 = chunk_slot[c + 1];
-  const int e0 = slot_ptr[s0], e1 = slot_ptr[s1];
-  double wq[FUSED_MAX_ENTRIES / FUSED_BLOCK];
-  int fq[FUSED_MAX_ENTRIES / FUSED_BLOCK];
-#pragma unroll
-  for (int q = 0; q < FUSED_MAX_ENTRIES / FUSED_BLOCK; ++q) {
-    const int e = e0 + threadIdx.x + q * FUSED_BLOCK;
-    wq[q] = e < e1 ? ld_nt(w + e) : 0.0;
-    fq[q] = e < e1 ? (int)ld_nt(fi + e) : 0;
-  }
-  const int myslot = s0 + threadIdx.x;
-  // dest (optional, AMGX_RSUM_SORT=1): the partials of one coarse row stored next to each other, so that
-  // restrict_sum_kernel streams them -- scattered stores here instead of scattered loads there; measured slower overall
-  int mydest = myslot, pa_raw = 0, pb_raw = 0;
-  if (myslot < s1) {
-    if (dest) mydest = dest[myslot];
-    pa_raw = slot_ptr[myslot];
-    pb_raw = slot_ptr[myslot + 1];
-  }
+  ChunkRestrict<FUSED_BLOCK, EPT> cr;
+  cr.request(c, R);
   double r = 0.0;
-  if (MODE == 1) {
-    if (s < n_slices) {
-      double ci = 0.0, xi = 0.0;
-      if (writer && row < n_rows) { ci = dinv[row]; xi = b[row]; }
-      double xdd[2];
-      double acc = sell_row_dot_sp(M, sp0, sp1, lane, row, b, xdd);
-#pragma unroll
-      for (int o = G >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, G);
-      if (writer && row < n_rows) { r = ci * xi - acc; if (r_out) r_out[row] = r; }
-    }
-  } else if (MODE == 2) {
-    if (s < n_slices) {
-      double bi = 0.0;
-      if (writer && row < n_rows) bi = (nt & EPF_NT) ? ld_nt(dinv + row) : dinv[row];
-      double xdd[2];
-      double acc = sell_row_dot_sp(M, sp0, sp1, lane, row, b, xdd);
-#pragma unroll
-      for (int o = G >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, G);
-      if (writer && row < n_rows) { r = bi - acc; if (r_out) r_out[row] = r; }
-    }
-  } else if (s < n_slices) {
+  if (s < n_slices) {
+    // own-row operands ahead of the row product: MODE 0: b_i and Dinv_i (unless they come with the gather or are not hoisted),
+    // MODE 1: x_i and c_i, MODE 2: the right-hand side
     double bi = 0.0, di = 0.0;
+    const bool wdiag = MODE == 0 && G == 1 && M.wdiag && M.diag_first;
+    const bool hoist = MODE != 0 || G > 1 || (nt & EPF_HOIST);
+    if (!wdiag && hoist && writer && row < n_rows) {
+      if (MODE != 2) bi = b[row];
+      di = (MODE != 1 && (nt & EPF_NT)) ? ld_nt(dinv + row) : dinv[row];
+    }
+    // the row step of all modes
     double xd[2] = {0.0, 0.0};
-    const bool wdiag = G == 1 && M.wdiag && M.diag_first;
-    const bool hoist = G > 1 || (nt & EPF_HOIST);
-    if (!wdiag && hoist && writer && row < n_rows) { bi = b[row]; di = (nt & EPF_NT) ? ld_nt(dinv + row) : dinv[row]; }
-    double acc = sell_row_dot_sp(M, sp0, sp1, lane, row, b, xd);
-#pragma unroll
-    for (int o = G >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, G);
+    double acc = lane_group_sum<G>(sell_row_dot_sp(M, sp0, sp1, lane, row, b, xd));
     if (writer && row < n_rows) {
-      if (wdiag) {
-        // diagonal slot = omega*Dinv_i (no dinv stream, b_i from the gather): see sell_spmv_kernel
-        bi = xd[0];
-        const double wd = xd[1];
-        acc = acc - wd * bi + (wd != 0.0 ? omega * bi : 0.0);
-        di = wd / omega;
-      } else if (!hoist) { bi = b[row]; di = (nt & EPF_NT) ? ld_nt(dinv + row) : dinv[row]; }
-      r = bi - acc;
-      double xi = omega * (di * bi);
-      if (nt & EPF_FOLD) xi += omega * (di * r);
-      if (nt & EPF_NT) __builtin_nontemporal_store(xi, x + row);
-      else x[row] = xi;
+      if (MODE == 1) r = di * bi - acc;
+      else if (MODE == 2) r = di - acc;
+      else {
+        if (wdiag) {
+          // diagonal slot = omega*Dinv_i (no dinv stream, b_i from the gather): see sell_spmv_kernel
+          bi = xd[0];
+          const double wd = xd[1];
+          acc = acc - wd * bi + (wd != 0.0 ? omega * bi : 0.0);
+          di = wd / omega;
+        } else if (!hoist) { bi = b[row]; di = (nt & EPF_NT) ? ld_nt(dinv + row) : dinv[row]; }
+        r = bi - acc;
+        jacobi_down_store(bi, di, r, omega, nt, x, row);
+      }
       if (r_out) r_out[row] = r;
     }
   }
   if (writer) rl[lrow] = r;
   __syncthreads();
-#pragma unroll
-  for (int q = 0; q < FUSED_MAX_ENTRIES / FUSED_BLOCK; ++q) {
-    const int e = threadIdx.x + q * FUSED_BLOCK;
-    if (e0 + e < e1) pr[e] = wq[q] * rl[fq[q]];
-  }
-  __syncthreads();
-  if (myslot < s1) {
-    const int pa = pa_raw - e0, pb = pb_raw - e0;
-    double acc = 0.0;
-    for (int k = pa; k < pb; ++k) acc += pr[k];
-    part[mydest] = acc;
-  }
-  for (int slot = myslot + FUSED_BLOCK; slot < s1; slot += FUSED_BLOCK) {     // chunks with more than 1024 slots
-    const int a = slot_ptr[slot] - e0, bnd = slot_ptr[slot + 1] - e0;
-    double acc = 0.0;
-    for (int k = a; k < bnd; ++k) acc += pr[k];
-    part[dest ? dest[slot] : slot] = acc;
-  }
+  cr.reduce(rl, pr, R);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1449,6 +1514,9 @@ struct DiaMat {
 // x_j = omega * (dinv_j * b_j) -- bitwise the value the kernel stores for row j -- and computes r = b - A x with the
 // diagonal term omega * b_i (0 where dinv_i = 0) as the wdiag image carries it; couplings in ascending column order.
 // Same DevRestrict data (chunk_slot / slot_ptr / w / fi / dest, compact chunks via slice_list), same outputs.
+// (This kernel keeps its own copy of the restriction prologue, epilogue and Jacobi store: with ChunkRestrict it has the same registers
+// and 16 to 23 instructions fewer, and measured 1.4 us slower on level 0 of cfg 2 (357.1 against 355.7 us, profiles/r11/refactor_ab.txt).
+// The ordering rule of ChunkRestrict::request holds for the prologue below.)
 template <int K, int EPT = 4>
 __global__ __launch_bounds__(512) void dia_pre_restrict_kernel(int n_rows, int n_slices, DiaMat D, const double* __restrict__ b,
                                                                const double* __restrict__ dinv, double omega, int nt, double* __restrict__ x,
@@ -1534,135 +1602,42 @@ __global__ __launch_bounds__(512) void dia_pre_restrict_kernel(int n_rows, int n
   }
 }
 
-// The residual after a block-hybrid Gauss-Seidel sweep from zero, r = c .* x - A_rest x, fused with the chunk-local
-// restriction like sell_pre_restrict_kernel<.., 1>, for the WINDOWED SELL form (rows of a 512-row window stored by
-// decreasing length): A_rest has ragged rows (each row lost its in-block lower-colour couplings), plain slices pad ~27 %.
-template <int WB, int EPT = 4>
-__global__ __launch_bounds__(WB) void sell_win_cres_restrict_kernel(int64_t n_rows, SellMat M, const uint16_t* __restrict__ rowloc,
-                                                                    const double* __restrict__ x, const double* __restrict__ cvec,
-                                                                    const int32_t* __restrict__ chunk_slot, const int32_t* __restrict__ slot_ptr,
-                                                                    const double* __restrict__ w, const uint16_t* __restrict__ fi,
-                                                                    double* __restrict__ part, const int32_t* __restrict__ dest) {
-  constexpr int MAXE = EPT * WB;
-  __shared__ double buf[WB];
-  __shared__ double pr[MAXE];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int c = sell_unit(M);
-  const int s = __builtin_amdgcn_readfirstlane(c * (WB / WAVE) + (threadIdx.x >> 6));
-  const int64_t slot = (int64_t)s * WAVE + lane;
-  const int64_t row = (int64_t)c * WB + threadIdx.x;
-  const int s0 = chunk_slot[c], s1 = chunk_slot[c + 1];
-  const int e0 = slot_ptr[s0], e1 = slot_ptr[s1];
-  double wq[MAXE / WB];
-  int fq[MAXE / WB];
-#pragma unroll
-  for (int q = 0; q < MAXE / WB; ++q) {
-    const int e = e0 + threadIdx.x + q * WB;
-    wq[q] = e < e1 ? ld_nt(w + e) : 0.0;
-    fq[q] = e < e1 ? (int)ld_nt(fi + e) : 0;
-  }
-  const int myslot = s0 + threadIdx.x;
-  int mydest = myslot, pa_raw = 0, pb_raw = 0;               // (consumed after the row product: see sell_pre_restrict_kernel)
-  if (myslot < s1) {
-    if (dest) mydest = dest[myslot];
-    pa_raw = slot_ptr[myslot];
-    pb_raw = slot_ptr[myslot + 1];
-  }
-  double ci = 0.0, xi = 0.0;
-  if (row < n_rows) { ci = cvec[row]; xi = x[row]; }
-  if (slot < n_rows) buf[rowloc[slot]] = sell_row_dot(M, s, lane, 0, x);
-  __syncthreads();
-  const double r = row < n_rows ? ci * xi - buf[threadIdx.x] : 0.0;
-  buf[threadIdx.x] = r;                      // (same thread, same entry: the residuals replace the row sums in place)
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < MAXE / WB; ++q) {
-    const int e = threadIdx.x + q * WB;
-    if (e0 + e < e1) pr[e] = wq[q] * buf[fq[q]];
-  }
-  __syncthreads();
-  if (myslot < s1) {
-    const int pa = pa_raw - e0, pb = pb_raw - e0;
-    double acc = 0.0;
-    for (int k = pa; k < pb; ++k) acc += pr[k];
-    part[mydest] = acc;
-  }
-  for (int sl = myslot + WB; sl < s1; sl += WB) {
-    const int a = slot_ptr[sl] - e0, bnd = slot_ptr[sl + 1] - e0;
-    double acc = 0.0;
-    for (int k = a; k < bnd; ++k) acc += pr[k];
-    part[dest ? dest[sl] : sl] = acc;
-  }
-}
-
-// Jacobi pre-smoothing from zero + residual + chunk-local restriction (sell_pre_restrict_kernel, MODE 0) for the WINDOWED SELL form
-// of A': the coarser levels of a reference-shaped hierarchy have ragged rows (34 ... 63 entries at the 1.24 M-row level of cfg 2),
-// plain 64-row slices pad 20 %, length-sorted 512-row windows 3.6 %.  No diagonal-first trick here (the rows of a window are stored
-// by decreasing length): b and dinv of the own row are read in natural order, which on these levels is 1 % of the matrix stream.
-template <int WB, int EPT = 4>
+// The fused down kernel for the WINDOWED SELL form (rows of a 512-row window stored by decreasing length), MODE as in
+// sell_pre_restrict_kernel:
+// MODE 0: Jacobi pre-smoothing from zero + residual on a windowed image of A': the coarser levels of a reference-shaped hierarchy
+// have ragged rows (34 ... 63 entries at the 1.24 M-row level of cfg 2), plain 64-row slices pad 20 %, length-sorted 512-row windows
+// 3.6 %.  No diagonal-first trick here (the rows of a window are stored by decreasing length): b and dinv of the own row are read in
+// natural order, which on these levels is 1 % of the matrix stream.
+// MODE 1: the residual after a block-hybrid Gauss-Seidel sweep from zero, r = c .* x - A_rest x (b = the swept x, dinv = c, win0 = 0,
+// nothing written to x): A_rest has ragged rows (each row lost its in-block lower-colour couplings), plain slices pad ~27 %.
+template <int WB, int EPT = 4, int MODE = 0>
 __global__ __launch_bounds__(WB) void sell_win_pre_restrict_kernel(int64_t n_rows, int win0, SellMat M, const uint16_t* __restrict__ rowloc,
                                                                    const double* __restrict__ b, const double* __restrict__ dinv, double omega, int nt,
-                                                                   double* __restrict__ x,
-                                                                   const int32_t* __restrict__ chunk_slot, const int32_t* __restrict__ slot_ptr,
-                                                                   const double* __restrict__ w, const uint16_t* __restrict__ fi,
-                                                                   double* __restrict__ part, const int32_t* __restrict__ dest) {
-  constexpr int MAXE = EPT * WB;
+                                                                   double* __restrict__ x, RestrictMat R) {
   __shared__ double buf[WB];
-  __shared__ double pr[MAXE];
+  __shared__ double pr[EPT * WB];
   const int lane = threadIdx.x & (WAVE - 1);
   const int c = win0 + sell_unit(M);
   const int s = __builtin_amdgcn_readfirstlane(c * (WB / WAVE) + (threadIdx.x >> 6));
   const int64_t slot = (int64_t)s * WAVE + lane;
   const int64_t row = (int64_t)c * WB + threadIdx.x;
-  const int s0 = chunk_slot[c], s1 = chunk_slot[c + 1];
-  const int e0 = slot_ptr[s0], e1 = slot_ptr[s1];
-  double wq[MAXE / WB];
-  int fq[MAXE / WB];
-#pragma unroll
-  for (int q = 0; q < MAXE / WB; ++q) {
-    const int e = e0 + threadIdx.x + q * WB;
-    wq[q] = e < e1 ? ld_nt(w + e) : 0.0;
-    fq[q] = e < e1 ? (int)ld_nt(fi + e) : 0;
-  }
-  const int myslot = s0 + threadIdx.x;
-  int mydest = myslot, pa_raw = 0, pb_raw = 0;               // (consumed after the row product: see sell_pre_restrict_kernel)
-  if (myslot < s1) {
-    if (dest) mydest = dest[myslot];
-    pa_raw = slot_ptr[myslot];
-    pb_raw = slot_ptr[myslot + 1];
-  }
+  ChunkRestrict<WB, EPT> cr;
+  cr.request(c, R);
   double bi = 0.0, di = 0.0;
-  if (row < n_rows) { bi = b[row]; di = (nt & EPF_NT) ? ld_nt(dinv + row) : dinv[row]; }
+  if (row < n_rows) { bi = b[row]; di = (MODE == 0 && (nt & EPF_NT)) ? ld_nt(dinv + row) : dinv[row]; }
   if (slot < n_rows) buf[rowloc[slot]] = sell_row_dot(M, s, lane, 0, b);
   __syncthreads();
   double r = 0.0;
   if (row < n_rows) {
-    r = bi - buf[threadIdx.x];
-    double xi = omega * (di * bi);
-    if (nt & EPF_FOLD) xi += omega * (di * r);
-    if (nt & EPF_NT) __builtin_nontemporal_store(xi, x + row);
-    else x[row] = xi;
+    if (MODE == 1) r = di * bi - buf[threadIdx.x];
+    else {
+      r = bi - buf[threadIdx.x];
+      jacobi_down_store(bi, di, r, omega, nt, x, row);
+    }
   }
   buf[threadIdx.x] = r;                      // (same thread, same entry: the residuals replace the row sums in place)
   __syncthreads();
-#pragma unroll
-  for (int q = 0; q < MAXE / WB; ++q) {
-    const int e = threadIdx.x + q * WB;
-    if (e0 + e < e1) pr[e] = wq[q] * buf[fq[q]];
-  }
-  __syncthreads();
-  if (myslot < s1) {
-    const int pa = pa_raw - e0, pb = pb_raw - e0;
-    double acc = 0.0;
-    for (int k = pa; k < pb; ++k) acc += pr[k];
-    part[mydest] = acc;
-  }
-  for (int sl = myslot + WB; sl < s1; sl += WB) {
-    const int a = slot_ptr[sl] - e0, bnd = slot_ptr[sl + 1] - e0;
-    double acc = 0.0;
-    for (int k = a; k < bnd; ++k) acc += pr[k];
-    part[dest ? dest[sl] : sl] = acc;
-  }
+  cr.reduce(buf, pr, R);
 }
 
 // Fused Jacobi pre-smoothing + residual + chunk-local restriction (sell_pre_restrict_kernel, MODE 0) for the LONG-ROW levels of a
@@ -1680,7 +1655,7 @@ constexpr int LW_CAP = 4608;                 // distinct columns per chunk the L
 // G = lanes per row (2: 256-row chunks; 4: 128-row chunks for levels with ~80+ entries per row, whose 256-row chunks would not fit).
 // MODE 0: Jacobi pre-smoothing from zero as described above (b = right-hand side, dinv, x receives omega*Dinv*b [+ fold]).
 // MODE 1: residual after a block-hybrid Gauss-Seidel sweep from zero, r = c .* x - A_rest x (b = the swept x, dinv = c; nothing is
-//         written to x) -- sell_win_cres_restrict_kernel's job on a local-window image of A_rest.
+//         written to x) -- sell_win_pre_restrict_kernel<.., 1>'s job on a local-window image of A_rest.
 template <int EPT = 4, int G = 2, int MODE = 0>
 __global__ __launch_bounds__(512, (EPT <= 2 ? 6 : 4)) void sell_lw_pre_restrict_kernel(int64_t n_rows, int chunk0, int n_slices, SellMat M,
                                                                    const int32_t* __restrict__ lw_cptr, const int32_t* __restrict__ lw_ccol,
@@ -1691,62 +1666,37 @@ __global__ __launch_bounds__(512, (EPT <= 2 ? 6 : 4)) void sell_lw_pre_restrict_
                                                                    double* __restrict__ part, const int32_t* __restrict__ dest) {
   constexpr int FB = 512;
   constexpr int ROWS = FB / G;
-  constexpr int MAXE = EPT * FB;
+  const RestrictMat R{chunk_slot, slot_ptr, w, fi, part, dest};
   __shared__ double xw[LW_CAP];
   __shared__ double rl[ROWS];
-  __shared__ double pr[MAXE];
+  __shared__ double pr[EPT * FB];
   const int lane = threadIdx.x & (WAVE - 1);
   const int c = chunk0 + sell_unit(M);
   const int s = __builtin_amdgcn_readfirstlane(c * (FB / WAVE) + (threadIdx.x >> 6));
   const int row = s * (WAVE / G) + lane / G;
   const int lrow = (threadIdx.x >> 6) * (WAVE / G) + lane / G;
   const bool writer = (lane % G) == 0;
-  // stage the window: xw[k] = b[ccol[k]]  (all loads of the prologue are requested before anything is consumed)
-  const int k0 = lw_cptr[c], k1 = lw_cptr[c + 1];
-  double xv[LW_CAP / FB];
-#pragma unroll
-  for (int q = 0; q < LW_CAP / FB; ++q) {
-    const int k = k0 + threadIdx.x + q * FB;
-    xv[q] = k < k1 ? b[lw_ccol[k]] : 0.0;
-  }
+  // the window xw[k] = b[ccol[k]] and the restriction data: all loads of the prologue are requested before anything is consumed
+  LdsWindow<LW_CAP, FB> win;
+  win.request(c, lw_cptr, lw_ccol, b);
   const bool has_slice = s < n_slices;
   const int64_t sp0 = has_slice ? M.slice_ptr[s] : 0, sp1 = has_slice ? M.slice_ptr[s + 1] : 0;
-  const int s0 = chunk_slot[c], s1 = chunk_slot[c + 1];
-  const int e0 = slot_ptr[s0], e1 = slot_ptr[s1];
-  double wq[EPT];
-  int fq[EPT];
-#pragma unroll
-  for (int q = 0; q < EPT; ++q) {
-    const int e = e0 + threadIdx.x + q * FB;
-    wq[q] = e < e1 ? ld_nt(w + e) : 0.0;
-    fq[q] = e < e1 ? (int)ld_nt(fi + e) : 0;
-  }
-  const int myslot = s0 + threadIdx.x;
-  int mydest = myslot, pa_raw = 0, pb_raw = 0;
-  if (myslot < s1) {
-    if (dest) mydest = dest[myslot];
-    pa_raw = slot_ptr[myslot];
-    pb_raw = slot_ptr[myslot + 1];
-  }
+  ChunkRestrict<FB, EPT> cr;
+  cr.request(c, R);
   double bi = 0.0, di = 0.0;
   if (writer && has_slice && row < n_rows) { bi = b[row]; di = (MODE == 0 && (nt & EPF_NT)) ? ld_nt(dinv + row) : dinv[row]; }
-#pragma unroll
-  for (int q = 0; q < LW_CAP / FB; ++q) {
-    const int k = threadIdx.x + q * FB;
-    if (k0 + k < k1) xw[k] = xv[q];
-  }
+  win.publish(xw);
   __syncthreads();
   double r = 0.0;
   if (has_slice) {
     double xd[2] = {0.0, 0.0};
     double acc = sell_row_dot_sp(M, sp0, sp1, lane, 0, xw, xd, b);       // 16-bit slices: indices into the window; 32-bit: global columns
-#pragma unroll
-    for (int o = G >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, G);
+    acc = lane_group_sum<G>(acc);
     if (writer && row < n_rows) {
       if (MODE == 1) r = di * bi - acc;
       else {
         r = bi - acc;
-        double xi = omega * (di * bi);
+        double xi = omega * (di * bi);             // (jacobi_down_store written out: through the helper MODE 0 takes one VGPR more)
         if (nt & EPF_FOLD) xi += omega * (di * r);
         if (nt & EPF_NT) __builtin_nontemporal_store(xi, x + row);
         else x[row] = xi;
@@ -1755,24 +1705,7 @@ __global__ __launch_bounds__(512, (EPT <= 2 ? 6 : 4)) void sell_lw_pre_restrict_
   }
   if (writer) rl[lrow] = r;
   __syncthreads();
-#pragma unroll
-  for (int q = 0; q < EPT; ++q) {
-    const int e = threadIdx.x + q * FB;
-    if (e0 + e < e1) pr[e] = wq[q] * rl[fq[q]];
-  }
-  __syncthreads();
-  if (myslot < s1) {
-    const int pa = pa_raw - e0, pb = pb_raw - e0;
-    double acc = 0.0;
-    for (int k = pa; k < pb; ++k) acc += pr[k];
-    part[mydest] = acc;
-  }
-  for (int slot = myslot + FB; slot < s1; slot += FB) {
-    const int a = slot_ptr[slot] - e0, bnd = slot_ptr[slot + 1] - e0;
-    double acc = 0.0;
-    for (int k = a; k < bnd; ++k) acc += pr[k];
-    part[dest ? dest[slot] : slot] = acc;
-  }
+  cr.reduce(rl, pr, R);
 }
 
 // x = z + Q x_c (windowed SELL, EP_AXPY and friends) with the gathered COARSE vector staged in LDS: the local-window form of
@@ -1792,21 +1725,12 @@ __global__ __launch_bounds__(WB) void sell_lw_win_spmv_kernel(int64_t n_rows, in
   const int s = __builtin_amdgcn_readfirstlane(wb * (WB / WAVE) + (threadIdx.x >> 6));
   const int64_t slot = (int64_t)s * WAVE + lane;
   const int64_t row = (int64_t)wb * WB + threadIdx.x;
-  const int k0 = lw_cptr[wb], k1 = lw_cptr[wb + 1];
-  double xv[QW_CAP / WB];
-#pragma unroll
-  for (int q = 0; q < QW_CAP / WB; ++q) {
-    const int k = k0 + threadIdx.x + q * WB;
-    xv[q] = k < k1 ? x[lw_ccol[k]] : 0.0;
-  }
+  LdsWindow<QW_CAP, WB> win;
+  win.request(wb, lw_cptr, lw_ccol, x);
   const bool hoist = (ep.nt & EPF_HOIST) && EP != EP_MULT;
   EpOps ops{0.0, 0.0, 0.0};
   if (hoist && row < n_rows) ops = ep_operands<EP>(row, ep, false);
-#pragma unroll
-  for (int q = 0; q < QW_CAP / WB; ++q) {
-    const int k = threadIdx.x + q * WB;
-    if (k0 + k < k1) xw[k] = xv[q];
-  }
+  win.publish(xw);
   __syncthreads();
   if (slot < n_rows) {
     double xd[2];

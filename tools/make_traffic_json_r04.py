@@ -48,7 +48,7 @@ def main():
             ("jacobi_spw", "sell_lw_win_spmv_kernel<512, 2>", 1, "traffic_q_l1_spw.json", "sell_lw_win_spmv_kernel<512, EP_AXPY> on Q, level 1 (cfg 2, default hierarchy)"),
             ("jacobi_spw", "restrict_sum_kernel", 0, "traffic_restrict_sum_l0_spw.json", "restrict_sum_kernel level 0 -> 1 (cfg 2, default hierarchy)"),
             ("gs_spw", "gsb_sweep_kernel<256, 1, false", 0, "traffic_gsb_sweep_l0_spw.json", "gsb_sweep_kernel<256, 1, false, 8> level 0 (cfg 2, default hierarchy)"),
-            ("gs_spw", "sell_win_cres_restrict_kernel<512", 0, "traffic_gs_res_restrict_l0_spw.json", "sell_win_cres_restrict_kernel<512> level 0 (cfg 2, default hierarchy)"),
+            ("gs_spw", "sell_win_pre_restrict_kernel<512", 0, "traffic_gs_res_restrict_l0_spw.json", "sell_win_pre_restrict_kernel<512, EPT, 1> level 0 (cfg 2, default hierarchy)"),
             ("gs_spw", "sell_spmv_kernel<1, 1>", 0, "traffic_spmv_l0_spw.json", "sell_spmv_kernel<1, EP_RES> level 0 (cfg 2, default hierarchy)"),
             ("cfg3_gs_spw", "bgsb_sweep_kernel<3, 0>", 0, "traffic_bgsb_sweep_cfg3_spw.json", "bgsb_sweep_kernel<3, 0> level 0 (cfg 3: ONE block colour of the backward block-coloured sweep; a sweep = the launches of all colours)"),
             ("cfg5_gs_spw", "bgsb_sweep_kernel<6, 0>", 0, "traffic_bgsb_sweep_cfg5_spw.json", "bgsb_sweep_kernel<6, 0> level 0 (cfg 5: ONE block colour of the backward block-coloured sweep)")]
