@@ -11,6 +11,7 @@
 #include "kernels.hpp"
 #include "knobs.hpp"
 #include "launch.hpp"          // Err, HIPCHK, dispatch, launch
+#include "graph_cache.hpp"     // GraphCache
 #include "../host/dia.hpp"
 #include <dlfcn.h>
 #include <algorithm>
@@ -1283,47 +1284,6 @@ struct MultiState;                      // multi-vector work space and captured 
 void multi_drop_graphs(MultiState* s);
 void multi_free(MultiState* s);
 
-// captured applications, keyed by what identifies one (the vector addresses): at most 16, the oldest capture goes first
-template <class Key>
-struct GraphCache {
-  std::map<Key, hipGraphExec_t> graphs;
-  std::vector<Key> age;                 // capture order
-  GraphCache() = default;
-  GraphCache(const GraphCache&) = delete;
-  GraphCache& operator=(const GraphCache&) = delete;
-  ~GraphCache() { drop(); }
-  void drop() {
-    for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
-    graphs.clear();
-    age.clear();
-  }
-  bool has(const Key& key) const { return graphs.count(key) != 0; }
-  // replays the graph of `key`; the first call with a key captures body() on `stream`
-  template <class Body>
-  void run(const Key& key, hipStream_t stream, Body&& body) {
-    auto it = graphs.find(key);
-    if (it == graphs.end()) {
-      hipGraph_t g = nullptr;
-      HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-      try { body(); }
-      catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(stream, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
-      HIPCHK(hipStreamEndCapture(stream, &g));
-      hipGraphExec_t ge = nullptr;
-      hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      if (e != hipSuccess) throw Err(std::string("hipGraphInstantiate failed: ") + hipGetErrorString(e));
-      if (graphs.size() >= 16 && !age.empty()) {             // the oldest capture goes, the hot ones stay
-        auto old = graphs.find(age.front());
-        age.erase(age.begin());
-        if (old != graphs.end()) { (void)hipGraphExecDestroy(old->second); graphs.erase(old); }
-      }
-      it = graphs.emplace(key, ge).first;
-      age.push_back(key);
-    }
-    HIPCHK(hipGraphLaunch(it->second, stream));
-  }
-};
-
 struct Handle {
   int device = 0;
   Knobs knobs;                          // the switches as amgx_create found them (knobs.hpp)
@@ -1842,6 +1802,26 @@ struct Handle {
     body();
     if (on) HIPCHK(hipEventRecord(probe_e1, stream));
   }
+  // the life of the probe events (amgx_time_op ops 8 / 9, amgx_dist_time_kernel): both exist while the scope does; the cycle
+  // records them once `probe_level` is set (after the warm-up), and leaving the scope by any path switches the probe off
+  struct ProbeScope {
+    Handle& h;
+    ProbeScope(Handle& hh, int kind) : h(hh) {
+      h.probe_kind = kind;
+      HIPCHK(hipEventCreate(&h.probe_e0));
+      const hipError_t e = hipEventCreate(&h.probe_e1);
+      if (e != hipSuccess) { release(); HIPCHK(e); }
+    }
+    ProbeScope(const ProbeScope&) = delete;
+    ~ProbeScope() { release(); }
+    void release() {
+      h.probe_level = -1;
+      if (h.probe_e0) (void)hipEventDestroy(h.probe_e0);
+      if (h.probe_e1) (void)hipEventDestroy(h.probe_e1);
+      h.probe_e0 = h.probe_e1 = nullptr;
+    }
+    float elapsed_ms() const { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h.probe_e0, h.probe_e1)); return ms; }
+  };
 
   // pre-smoothing step of the cycles: x = 0; r = b; Smooth(x, b, r, 1, 1, 1)   (amg_matrix.cpp:193-206)
   // fold (only with folded(L)): x receives z = x + omega*Dinv*r, to be completed by post_smooth(..., fold = true)
@@ -2149,9 +2129,8 @@ struct Handle {
     const int L = n_levels();
     if (dense_level >= 0 && dense_level == l0) {           // the whole (sub-)cycle is the dense operator: x = B b
       Range rg("rest");
-      hipLaunchKernelGGL(dense_op_gemv_kernel, dim3((dense_n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(BLOCK), 0, stream,
+      launch(dense_op_gemv_kernel, (dense_n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, BLOCK, 0, stream,
                          dense_n, dense_ld, dense_op.p, b, x);
-      HIPCHK(hipGetLastError());
       return;
     }
     if (l0 == L - 1) { coarse_solve(b, x); return; }
@@ -2166,13 +2145,11 @@ struct Handle {
     }
     if (dense) {
       Range rg("rest");                                    // levels >= dense_level incl. "coarse inv": x_T = B b_T
-      hipLaunchKernelGGL(dense_op_gemv_kernel, dim3((dense_n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(BLOCK), 0, stream,
+      launch(dense_op_gemv_kernel, (dense_n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, BLOCK, 0, stream,
                          dense_n, dense_ld, dense_op.p, lev[T].rhs.p, lev[T].x.p);
-      HIPCHK(hipGetLastError());
     } else if (tail) {
       Range rg("rest");                                    // the coarse tail incl. "coarse inv" in one workgroup
-      hipLaunchKernelGGL(tail_kernel, dim3(1), dim3(TAIL_BLOCK), 0, stream, tail_ops, tail_prog.p);
-      HIPCHK(hipGetLastError());
+      launch(tail_kernel, 1, TAIL_BLOCK, 0, stream, tail_ops, tail_prog.p);
     } else coarse_solve(lev[L - 1].rhs.p, lev[L - 1].x.p);
     for (int l = T - 1; l >= l0; --l) {
       Range rg(level_range_name(l));
@@ -2576,11 +2553,9 @@ static void build_gsb_images(const Knobs& K, const amgx_level_desc& d, DevLevel&
     DevCsrSrc part[2];
     for (int q = 0; q < 2; ++q) { part[q].n_rows = n; part[q].n_cols = d.A.n_cols; part[q].rowptr.alloc((size_t)n + 1); }
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(db_split_count_kernel, dim3(grid), dim3(BLOCK), 0, 0, a, part[0].rowptr.p, part[1].rowptr.p);
-    HIPCHK(hipGetLastError());
+    launch(db_split_count_kernel, grid, BLOCK, 0, 0, a, part[0].rowptr.p, part[1].rowptr.p);
     for (int q = 0; q < 2; ++q) {
-      hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(1024), 0, 0, n, part[q].rowptr.p);
-      HIPCHK(hipGetLastError());
+      launch(db_scan_kernel, 1, 1024, 0, 0, n, part[q].rowptr.p);
       HIPCHK(hipMemcpy(&part[q].nnz, part[q].rowptr.p + n, sizeof(int64_t), hipMemcpyDeviceToHost));
       part[q].col.alloc((size_t)std::max<int64_t>(1, part[q].nnz));
       part[q].val.alloc((size_t)std::max<int64_t>(1, part[q].nnz));
@@ -2589,9 +2564,8 @@ static void build_gsb_images(const Knobs& K, const amgx_level_desc& d, DevLevel&
     DevBuf<int> bad;
     bad.alloc(1);
     HIPCHK(hipMemset(bad.p, 0, sizeof(int)));
-    hipLaunchKernelGGL(db_split_fill_kernel, dim3(grid), dim3(BLOCK), 0, 0, a, part[0].rowptr.p, part[1].rowptr.p, part[0].col.p, part[0].val.p,
+    launch(db_split_fill_kernel, grid, BLOCK, 0, 0, a, part[0].rowptr.p, part[1].rowptr.p, part[0].col.p, part[0].val.p,
                        part[1].col.p, part[1].val.p, g.cvec.p, bad.p);
-    HIPCHK(hipGetLastError());
     int hbad = 0;
     HIPCHK(hipMemcpy(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost));
     if (hbad || K.gsb_no_split) { g.cvec.release(); return; }
@@ -3761,37 +3735,27 @@ int amgx_time_op(amgx_handle hh, int level, int op, int reps, double* avg_ms) {
       if (op == 8 && !L.paths.jacobi_down()) throw amgx::Err("amgx_time_op: level has no fused pre-smoothing + restriction kernel");
       if (op == 9 && !(has_c && L.paths.plain && L.paths.hybrid() && L.n == L.ncols && !L.paths.folded))
         throw amgx::Err("amgx_time_op: level has no block-hybrid Gauss-Seidel sweep");
-      h.probe_kind = op;
       if (h.stream == nullptr) throw amgx::Err("amgx_time_op: op 8 needs a non-default stream");
-      HIPCHK(hipEventCreate(&h.probe_e0));
-      HIPCHK(hipEventCreate(&h.probe_e1));
+      amgx::Handle::ProbeScope probe(h, op);
       double tot = 0.0;
-      if (h.lev[0].len()) hipLaunchKernelGGL(amgx::fill_kernel, dim3(amgx::Handle::grid_for(h.lev[0].len())), dim3(amgx::BLOCK), 0, h.stream, h.lev[0].len(), (uint64_t)2, h.lev[0].rhs.p);
-      try {
-        h.do_cycle(h.lev[0].x.p, h.lev[0].rhs.p);              // warm-up
-        h.probe_level = level;
-        for (int i = 0; i < reps; ++i) {
-          h.do_cycle(h.lev[0].x.p, h.lev[0].rhs.p);
-          HIPCHK(hipEventSynchronize(h.probe_e1));
-          float ms = 0;
-          HIPCHK(hipEventElapsedTime(&ms, h.probe_e0, h.probe_e1));
-          tot += ms;
-        }
-      } catch (...) { h.probe_level = -1; (void)hipEventDestroy(h.probe_e0); (void)hipEventDestroy(h.probe_e1); h.probe_e0 = h.probe_e1 = nullptr; throw; }
-      h.probe_level = -1;
+      if (h.lev[0].len()) amgx::launch(amgx::fill_kernel, amgx::Handle::grid_for(h.lev[0].len()), amgx::BLOCK, 0, h.stream, h.lev[0].len(), (uint64_t)2, h.lev[0].rhs.p);
+      h.do_cycle(h.lev[0].x.p, h.lev[0].rhs.p);              // warm-up
+      h.probe_level = level;
+      for (int i = 0; i < reps; ++i) {
+        h.do_cycle(h.lev[0].x.p, h.lev[0].rhs.p);
+        HIPCHK(hipEventSynchronize(h.probe_e1));
+        tot += probe.elapsed_ms();
+      }
       HIPCHK(hipStreamSynchronize(h.stream));
-      (void)hipEventDestroy(h.probe_e0); (void)hipEventDestroy(h.probe_e1);
-      h.probe_e0 = h.probe_e1 = nullptr;
       *avg_ms = tot / reps;
       return;
     }
     if (op != 4) {   // time on non-trivial data (the work vectors are otherwise zero in device-pointer mode)
       auto fill = [&](double* v, int64_t n, uint64_t seed) {
-        if (n) hipLaunchKernelGGL(amgx::fill_kernel, dim3(amgx::Handle::grid_for(n)), dim3(amgx::BLOCK), 0, h.stream, n, seed, v);
+        if (n) amgx::launch(amgx::fill_kernel, amgx::Handle::grid_for(n), amgx::BLOCK, 0, h.stream, n, seed, v);
       };
       fill(L.x.p, L.len(), 1); fill(L.rhs.p, L.len(), 2); fill(L.res.p, L.len(), 3); fill(L.tmp.p, L.len(), 4);
       if (has_c) fill(h.lev[level + 1].x.p, h.lev[level + 1].len(), 5);
-      HIPCHK(hipGetLastError());
     }
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0));
@@ -3842,23 +3806,22 @@ static void cheb_estimate(Handle& h) {
     if (!partial.p) { partial.alloc((size_t)2 * KR_BLOCKS); sc.alloc(2); }
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(KR_BLOCKS, (n + BLOCK - 1) / BLOCK));
     double *v = L.x.p, *t = L.res.p, *w = L.tmp.p;
-    hipLaunchKernelGGL(fill_kernel, dim3(Handle::grid_for(n)), dim3(BLOCK), 0, h.stream, n, (uint64_t)1, w);
+    launch(fill_kernel, Handle::grid_for(n), BLOCK, 0, h.stream, n, (uint64_t)1, w);
     h.mult(L.A, w, t);
     h.cheb_first(L, t, nullptr, v, nullptr, 1.0);
     double lam = 0.0;
     for (int it = 0; it < 30; ++it) {
       h.mult(L.A, v, t);
       h.cheb_first(L, t, nullptr, w, nullptr, 1.0);
-      hipLaunchKernelGGL(kr_dot_partial_kernel, dim3(nb), dim3(BLOCK), 0, h.stream, n, (const double*)t, (const double*)w, partial.p);
-      hipLaunchKernelGGL(kr_dot_partial_kernel, dim3(nb), dim3(BLOCK), 0, h.stream, n, (const double*)t, (const double*)v, partial.p + KR_BLOCKS);
-      hipLaunchKernelGGL(kr_dot_final_kernel, dim3(2), dim3(BLOCK), 0, h.stream, nb, (const double*)partial.p, sc.p);
-      HIPCHK(hipGetLastError());
+      launch(kr_dot_partial_kernel, nb, BLOCK, 0, h.stream, n, (const double*)t, (const double*)w, partial.p);
+      launch(kr_dot_partial_kernel, nb, BLOCK, 0, h.stream, n, (const double*)t, (const double*)v, partial.p + KR_BLOCKS);
+      launch(kr_dot_final_kernel, 2, BLOCK, 0, h.stream, nb, (const double*)partial.p, sc.p);
       double two[2] = {0.0, 0.0};
       HIPCHK(hipMemcpyAsync(two, sc.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h.stream));
       HIPCHK(hipStreamSynchronize(h.stream));
       if (!(two[1] > 0.0) || !(two[0] > 0.0) || !std::isfinite(two[0] / two[1])) break;      // A v = 0 (no free row): keep the last value
       lam = two[0] / two[1];
-      hipLaunchKernelGGL(kr_scale_kernel, dim3(Handle::grid_for(n)), dim3(BLOCK), 0, h.stream, n, 1.0 / lam, (const double*)w, v, 0);
+      launch(kr_scale_kernel, Handle::grid_for(n), BLOCK, 0, h.stream, n, 1.0 / lam, (const double*)w, v, 0);
     }
     if (!(lam > 0.0)) lam = 1.0;
     L.cheb_set_interval(1.1 * lam);

@@ -518,15 +518,14 @@ static void build_coarse_inverse(Handle& h, const amgx_hierarchy_desc* d, const 
   if (s.free_dofs) fr.upload(s.free_dofs, (size_t)s.A.n_rows);
   h.coarse_inv.alloc((size_t)npad * npad);
   h.coarse_ld = npad;
-  hipLaunchKernelGGL(gj_zero_kernel, dim3(Handle::grid_for(npad * npad)), dim3(BLOCK), 0, h.stream, npad * npad, h.coarse_inv.p);
-  hipLaunchKernelGGL(gj_scatter_kernel, dim3(Handle::grid_for(s.A.n_rows)), dim3(BLOCK), 0, h.stream, s.A.n_rows, bs, cA.rowptr.p, cA.col.p, cA.val.p,
+  launch(gj_zero_kernel, Handle::grid_for(npad * npad), BLOCK, 0, h.stream, npad * npad, h.coarse_inv.p);
+  launch(gj_scatter_kernel, Handle::grid_for(s.A.n_rows), BLOCK, 0, h.stream, s.A.n_rows, bs, cA.rowptr.p, cA.col.p, cA.val.p,
                      fr.p, npad, h.coarse_inv.p);
-  hipLaunchKernelGGL(gj_fix_diag_kernel, dim3(Handle::grid_for(npad)), dim3(BLOCK), 0, h.stream, npad, n, bs, fr.p, npad, 1.0, h.coarse_inv.p);
-  HIPCHK(hipGetLastError());
+  launch(gj_fix_diag_kernel, Handle::grid_for(npad), BLOCK, 0, h.stream, npad, n, bs, fr.p, npad, 1.0, h.coarse_inv.p);
   h.coarse_pivot = dense_spd_inverse(h.coarse_inv.p, npad, npad, h.stream);
   if (!(h.coarse_pivot > 1e-14)) throw Err("clev = inv: the coarsest matrix is not positive definite on its free dofs (pivot ratio " +
                                            std::to_string(h.coarse_pivot) + "); use clev = none or a smaller coarsest level");
-  hipLaunchKernelGGL(gj_fix_diag_kernel, dim3(Handle::grid_for(npad)), dim3(BLOCK), 0, h.stream, npad, n, bs, fr.p, npad, 0.0, h.coarse_inv.p);
+  launch(gj_fix_diag_kernel, Handle::grid_for(npad), BLOCK, 0, h.stream, npad, n, bs, fr.p, npad, 0.0, h.coarse_inv.p);
   HIPCHK(hipStreamSynchronize(h.stream));
 }
 
@@ -660,14 +659,13 @@ static void build_dense_tail(Handle& h, const amgx_hierarchy_desc* d, const amgx
   DevLevel& V = h.lev[lc];
   try {
     for (int j = 0; j < N; ++j) {
-      hipLaunchKernelGGL(dense_unit_kernel, dim3(Handle::grid_for(N)), dim3(BLOCK), 0, h.stream, (int64_t)N, (int64_t)j, V.rhs.p);
+      launch(dense_unit_kernel, Handle::grid_for(N), BLOCK, 0, h.stream, (int64_t)N, (int64_t)j, V.rhs.p);
       h.cycle_v(V.x.p, V.rhs.p, lc);                // (dense_level is still -1: separate launches)
       HIPCHK(hipMemcpyAsync(Bt.p + (size_t)j * ld, V.x.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, h.stream));
       if ((j & 255) == 255) HIPCHK(hipStreamSynchronize(h.stream));          // bound the depth of the launch queue
     }
     const int tb = (N + 15) / 16;
-    hipLaunchKernelGGL(dense_transpose_kernel, dim3(tb, tb), dim3(BLOCK), 0, h.stream, N, ld, Bt.p, h.dense_op.p);
-    HIPCHK(hipGetLastError());
+    launch(dense_transpose_kernel, dim3(tb, tb), BLOCK, 0, h.stream, N, ld, Bt.p, h.dense_op.p);
     // leave the work vectors of the collapsed levels as create() made them
     for (int m = lc; m < L; ++m) {
       const size_t len = (size_t)std::max<int64_t>(1, h.lev[m].ext_len());

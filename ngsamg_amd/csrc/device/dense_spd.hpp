@@ -142,16 +142,15 @@ static double dense_spd_inverse(double* D, int64_t n_pad, int64_t ld, hipStream_
   const double big = 1e300;
   HIPCHK(hipMemcpyAsync(status.p, &big, sizeof(double), hipMemcpyHostToDevice, stream));
   for (int k = 0; k < nt; ++k) {
-    hipLaunchKernelGGL(gj_pivot_kernel, dim3(1), dim3(256), 0, stream, k, ld, D, P.p, status.p);
+    launch(gj_pivot_kernel, 1, 256, 0, stream, k, ld, D, P.p, status.p);
     if (nt > 1) {
-      hipLaunchKernelGGL(gj_tile_kernel, dim3(nt), dim3(256), 0, stream, 0, k, nt, ld, D, P.p);
-      hipLaunchKernelGGL(gj_tile_kernel, dim3(nt, nt), dim3(256), 0, stream, 2, k, nt, ld, D, P.p);
-      hipLaunchKernelGGL(gj_tile_kernel, dim3(nt), dim3(256), 0, stream, 1, k, nt, ld, D, P.p);
+      launch(gj_tile_kernel, nt, 256, 0, stream, 0, k, nt, ld, D, P.p);
+      launch(gj_tile_kernel, dim3(nt, nt), 256, 0, stream, 2, k, nt, ld, D, P.p);
+      launch(gj_tile_kernel, nt, 256, 0, stream, 1, k, nt, ld, D, P.p);
     }
-    hipLaunchKernelGGL(gj_store_pivot_kernel, dim3(1), dim3(256), 0, stream, k, ld, D, P.p);
+    launch(gj_store_pivot_kernel, 1, 256, 0, stream, k, ld, D, P.p);
     if ((k & 31) == 31) HIPCHK(hipStreamSynchronize(stream));
   }
-  HIPCHK(hipGetLastError());
   double st = 0.0;
   HIPCHK(hipMemcpyAsync(&st, status.p, sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));

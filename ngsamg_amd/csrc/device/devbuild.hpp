@@ -405,8 +405,7 @@ static int64_t dev_round_to_f32(const DevBuf<double>& src, DevBuf<float>& dst) {
   DevBuf<unsigned int> bad;
   bad.alloc(1);
   HIPCHK(hipMemset(bad.p, 0, sizeof(unsigned int)));
-  hipLaunchKernelGGL(db_to_f32_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, 0, n, src.p, dst.p, bad.p);
-  HIPCHK(hipGetLastError());
+  launch(db_to_f32_kernel, (unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, 0, n, src.p, dst.p, bad.p);
   unsigned int h = 0;
   HIPCHK(hipMemcpy(&h, bad.p, sizeof(h), hipMemcpyDeviceToHost));
   return (int64_t)h;
@@ -445,9 +444,8 @@ static void dev_build_dia(const DevCsrSrc& A, DevDia& D) {
   const size_t len = (size_t)D.K * (size_t)A.n_rows;
   D.val.alloc(len);
   HIPCHK(hipMemset(D.val.p, 0, len * sizeof(double)));
-  hipLaunchKernelGGL(db_dia_kernel, dim3((unsigned)((A.n_rows + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, 0, A.n_rows, A.rowptr.p, A.col.p, A.val.p,
+  launch(db_dia_kernel, (unsigned)((A.n_rows + BLOCK - 1) / BLOCK), BLOCK, 0, 0, A.n_rows, A.rowptr.p, A.col.p, A.val.p,
                      D.view(), D.K, D.val.p);
-  HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());
 }
 
@@ -457,8 +455,7 @@ static DbDiagInfo dev_diag_check(const DevCsrSrc& A, const double* d_dinv) {
   DevBuf<int> fl;
   fl.alloc(2);
   HIPCHK(hipMemset(fl.p, 0, 2 * sizeof(int)));
-  hipLaunchKernelGGL(db_diag_check_kernel, dim3((unsigned)((A.n_rows + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, 0, A.n_rows, A.rowptr.p, A.col.p, A.val.p, d_dinv, fl.p);
-  HIPCHK(hipGetLastError());
+  launch(db_diag_check_kernel, (unsigned)((A.n_rows + BLOCK - 1) / BLOCK), BLOCK, 0, 0, A.n_rows, A.rowptr.p, A.col.p, A.val.p, d_dinv, fl.p);
   int h[2];
   HIPCHK(hipMemcpy(h, fl.p, sizeof(h), hipMemcpyDeviceToHost));
   return DbDiagInfo{h[0] == 0, h[1] == 0};
@@ -469,10 +466,8 @@ static int64_t dev_slice_offsets(const DevCsrSrc& A, const int32_t* d_rows, int6
   const int R = WAVE / G;
   const int64_t ns = (m + R - 1) / R;
   sp.alloc((size_t)ns + 1);
-  hipLaunchKernelGGL(db_width_kernel, dim3((unsigned)((ns + 3) / 4)), dim3(DB_BLOCK), 0, 0, m, d_rows, A.rowptr.p, G, ns, sp.p);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(1024), 0, 0, ns, sp.p);
-  HIPCHK(hipGetLastError());
+  launch(db_width_kernel, (unsigned)((ns + 3) / 4), DB_BLOCK, 0, 0, m, d_rows, A.rowptr.p, G, ns, sp.p);
+  launch(db_scan_kernel, 1, 1024, 0, 0, ns, sp.p);
   int64_t stored = 0;
   HIPCHK(hipMemcpy(&stored, sp.p + ns, sizeof(int64_t), hipMemcpyDeviceToHost));
   return stored;
@@ -500,10 +495,8 @@ static void dev_build_sell(const DevCsrSrc& A, const int32_t* d_rows, int64_t m,
            d_colscale, omega, d_wdiag, A.n_rows, sp.p, S.col32.p, S.col16.p, S.cbase.p, S.val.p, comp.p, counters.p,
            d_col_stored ? A.col.p : nullptr, d_no16};
   if (ns > 0) {
-    hipLaunchKernelGGL(db_fill_kernel, dim3((unsigned)((ns + 3) / 4)), dim3(DB_BLOCK), 0, 0, f);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(db_flag_kernel, dim3((unsigned)((ns + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, 0, ns, comp.p, sp.p);
-    HIPCHK(hipGetLastError());
+    launch(db_fill_kernel, (unsigned)((ns + 3) / 4), DB_BLOCK, 0, 0, f);
+    launch(db_flag_kernel, (unsigned)((ns + BLOCK - 1) / BLOCK), BLOCK, 0, 0, ns, comp.p, sp.p);
   }
   unsigned long long cnt[2];
   HIPCHK(hipMemcpy(cnt, counters.p, sizeof(cnt), hipMemcpyDeviceToHost));
@@ -534,8 +527,7 @@ static bool dev_upload_matrix(const Knobs& K, const DevCsrSrc& A, DevMatrix& D, 
   if (windowed) {
     if (win != SELL_WIN) throw Err("windowed SELL: unexpected window size");
     rows.alloc((size_t)m); rowloc.alloc((size_t)m);
-    hipLaunchKernelGGL((db_window_sort_kernel<SELL_WIN>), dim3((unsigned)((m + SELL_WIN - 1) / SELL_WIN)), dim3(SELL_WIN), 0, 0, m, A.rowptr.p, rows.p, rowloc.p);
-    HIPCHK(hipGetLastError());
+    launch(db_window_sort_kernel<SELL_WIN>, (unsigned)((m + SELL_WIN - 1) / SELL_WIN), SELL_WIN, 0, 0, m, A.rowptr.p, rows.p, rowloc.p);
     stored = dev_slice_offsets(A, rows.p, m, sp);
   }
   const int64_t ns = (m + WAVE - 1) / WAVE;
@@ -569,10 +561,8 @@ static bool dev_fold_prolongation(const DevCsrSrc& A, const DevCsrSrc& P, const 
   HIPCHK(hipMemset(over.p, 0, sizeof(int)));
   Q.rowptr.alloc((size_t)n + 1);
   const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-  hipLaunchKernelGGL((db_fold_kernel<false>), dim3(grid), dim3(BLOCK), 0, 0, a, Q.rowptr.p, (int32_t*)nullptr, (double*)nullptr, over.p);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(1024), 0, 0, n, Q.rowptr.p);
-  HIPCHK(hipGetLastError());
+  launch(db_fold_kernel<false>, grid, BLOCK, 0, 0, a, Q.rowptr.p, (int32_t*)nullptr, (double*)nullptr, over.p);
+  launch(db_scan_kernel, 1, 1024, 0, 0, n, Q.rowptr.p);
   int ho = 0;
   int64_t nnz = 0;
   HIPCHK(hipMemcpy(&ho, over.p, sizeof(int), hipMemcpyDeviceToHost));
@@ -581,8 +571,7 @@ static bool dev_fold_prolongation(const DevCsrSrc& A, const DevCsrSrc& P, const 
   Q.n_rows = n; Q.n_cols = P.n_cols; Q.nnz = nnz;
   Q.col.alloc((size_t)std::max<int64_t>(1, nnz));
   Q.val.alloc((size_t)std::max<int64_t>(1, nnz));
-  hipLaunchKernelGGL((db_fold_kernel<true>), dim3(grid), dim3(BLOCK), 0, 0, a, Q.rowptr.p, Q.col.p, Q.val.p, over.p);
-  HIPCHK(hipGetLastError());
+  launch(db_fold_kernel<true>, grid, BLOCK, 0, 0, a, Q.rowptr.p, Q.col.p, Q.val.p, over.p);
   HIPCHK(hipDeviceSynchronize());
   return true;
 }
@@ -710,28 +699,24 @@ static bool dev_build_lw(const DevCsrSrc& A, bool windowed, int G, int64_t cap, 
   DbLw a{n, U, (int)cap, A.rowptr.p, A.col.p, lcol.p, no16.p, cnt.p, lists.p, counters.p};
   constexpr size_t lw_lds = (size_t)DB_LW_WORDS * 6 + 1024 * sizeof(int);
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&db_lw_list_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lw_lds));
-  hipLaunchKernelGGL(db_lw_list_kernel, dim3((unsigned)nu), dim3(512), lw_lds, 0, a);
-  HIPCHK(hipGetLastError());
+  launch(db_lw_list_kernel, (unsigned)nu, 512, lw_lds, 0, a);
   unsigned long long hc[2];
   HIPCHK(hipMemcpy(hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost));
   if (hc[1]) return false;
   if ((int64_t)hc[0] * 20 > nu && !test_cap) return false;           // (more than 5 % of the units without a window)
-  hipLaunchKernelGGL(db_scan32_kernel, dim3(1), dim3(1024), 0, 0, nu, cnt.p);
-  HIPCHK(hipGetLastError());
+  launch(db_scan32_kernel, 1, 1024, 0, 0, nu, cnt.p);
   int32_t total = 0;
   HIPCHK(hipMemcpy(&total, cnt.p + nu, sizeof(int32_t), hipMemcpyDeviceToHost));
   DevBuf<int32_t> ccol;
   ccol.alloc((size_t)std::max<int32_t>(1, total));
   if (total == 0) HIPCHK(hipMemset(ccol.p, 0, sizeof(int32_t)));
-  hipLaunchKernelGGL(db_lw_compact_kernel, dim3((unsigned)nu), dim3(256), 0, 0, (int)cap, cnt.p, lists.p, ccol.p);
-  HIPCHK(hipGetLastError());
+  launch(db_lw_compact_kernel, (unsigned)nu, 256, 0, 0, (int)cap, cnt.p, lists.p, ccol.p);
   lists.release();
   DevBuf<int32_t> rows;
   DevBuf<uint16_t> rowloc;
   if (windowed) {
     rows.alloc((size_t)n); rowloc.alloc((size_t)n);
-    hipLaunchKernelGGL((db_window_sort_kernel<SELL_WIN>), dim3((unsigned)nu), dim3(SELL_WIN), 0, 0, n, A.rowptr.p, rows.p, rowloc.p);
-    HIPCHK(hipGetLastError());
+    launch(db_window_sort_kernel<SELL_WIN>, (unsigned)nu, SELL_WIN, 0, 0, n, A.rowptr.p, rows.p, rowloc.p);
   }
   DevBuf<int64_t> sp;
   const int64_t stored = dev_slice_offsets(A, windowed ? rows.p : nullptr, n, sp, G);
@@ -793,10 +778,8 @@ static bool dev_build_bsell(const DevBcsrSrc& A, const int32_t* d_rows, int64_t 
   DbBsell a{m, A.n_rows, ns, bs, sel, d_rows, A.rowptr.p, A.col.p, A.val.p, mp.blk_of, mp.lpos, mp.color, mp.fac, mp.bcolor, sp.p, nullptr, nullptr};
   if (ns == 0) HIPCHK(hipMemset(sp.p, 0, sizeof(int64_t)));
   else {
-    hipLaunchKernelGGL(db_bsell_width_kernel, dim3((unsigned)((ns + 3) / 4)), dim3(DB_BLOCK), 0, 0, a);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(1024), 0, 0, ns, sp.p);
-    HIPCHK(hipGetLastError());
+    launch(db_bsell_width_kernel, (unsigned)((ns + 3) / 4), DB_BLOCK, 0, 0, a);
+    launch(db_scan_kernel, 1, 1024, 0, 0, ns, sp.p);
   }
   int64_t steps = 0;
   HIPCHK(hipMemcpy(&steps, sp.p + ns, sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -805,13 +788,11 @@ static bool dev_build_bsell(const DevBcsrSrc& A, const int32_t* d_rows, int64_t 
   DevBuf<double> val;
   const size_t ncol = (size_t)std::max<int64_t>(1, steps * RB), nval = (size_t)std::max<int64_t>(1, steps * bs * WAVE);
   col.alloc(ncol); val.alloc(nval);
-  hipLaunchKernelGGL(db_fill_i32_kernel, dim3((unsigned)((ncol + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, 0, (int64_t)ncol, padcol, col.p);
-  HIPCHK(hipGetLastError());
+  launch(db_fill_i32_kernel, (unsigned)((ncol + BLOCK - 1) / BLOCK), BLOCK, 0, 0, (int64_t)ncol, padcol, col.p);
   HIPCHK(hipMemset(val.p, 0, nval * sizeof(double)));
   if (ns > 0) {
     a.ocol = col.p; a.oval = val.p;
-    hipLaunchKernelGGL(db_bsell_fill_kernel, dim3((unsigned)((ns + 3) / 4)), dim3(DB_BLOCK), 0, 0, a);
-    HIPCHK(hipGetLastError());
+    launch(db_bsell_fill_kernel, (unsigned)((ns + 3) / 4), DB_BLOCK, 0, 0, a);
   }
   HIPCHK(hipDeviceSynchronize());
   D.fmt = FMT_BSELL; D.br = D.bc = bs;

@@ -69,8 +69,7 @@ struct Rccl {
 // device-to-device copy as a kernel of our own (see vec_copy_kernel)
 static inline void dev_copy(double* dst, const double* src, int64_t n, hipStream_t st) {
   if (n <= 0 || dst == src) return;
-  hipLaunchKernelGGL(vec_copy_kernel, dim3((unsigned)(((n + 1) / 2 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, n, src, dst);
-  HIPCHK(hipGetLastError());
+  launch(vec_copy_kernel, (unsigned)(((n + 1) / 2 + BLOCK - 1) / BLOCK), BLOCK, 0, st, n, src, dst);
 }
 
 struct HaloTable {                       // one level of one rank
@@ -111,6 +110,15 @@ struct HaloTable {                       // one level of one rank
 };
 
 struct Dist;
+// The driver of the collective cycle (DistCycle), resolved once by dist_create.  The first four are the specialised V(1,1)
+// stage sequences; STEPWISE serves sm_steps > 1 / sm_symm on a rank-partitioned level and the W-cycle.
+enum class DistPath {
+  JACOBI_FOLDED,       // Jacobi, post-smoothing folded into the prolongation
+  JACOBI_LITERAL,      // Jacobi in the literal stage order
+  GS_BLOCK_HYBRID,     // Gauss-Seidel levels in the block-hybrid form (gs_block_rows)
+  GS_STAGED,           // multicolour / aggregate-block Gauss-Seidel in colour stages
+  STEPWISE,            // one exchange and one launch per smoothing step
+};
 }  // namespace amgx
 struct amgx_dist_t { amgx::Dist* d; };
 namespace amgx {
@@ -143,21 +151,11 @@ struct Comm {
   // fails (a runtime / RCCL build that cannot capture an operation) falls back to direct launches for good.
   bool graph_ok = true, capturing = false;
   struct GKey { std::vector<const void*> p; int status; bool operator<(const GKey& o) const { return status != o.status ? status < o.status : p < o.p; } };
-  struct GVal { hipGraphExec_t exec; int64_t exchanges; };
-  std::map<GKey, GVal> graphs;
+  using Graphs = GraphCache<GKey, int64_t>;
+  Graphs graphs;                         // payload: the exchanges of one application, added to n_exchanges at every replay
   int64_t n_direct_runs = 0;             // applications launched directly; the first one always is (see dist_apply)
   int64_t n_graph_replays = 0;
   std::string graph_note;
-  void drop_graphs() { for (auto& g : graphs) (void)hipGraphExecDestroy(g.second.exec); graphs.clear(); graph_age.clear(); }
-  std::vector<GKey> graph_age;           // capture order: at 16 graphs the OLDEST one goes, not the hot ones
-  void evict_oldest_graph() {
-    while (!graph_age.empty()) {
-      auto it = graphs.find(graph_age.front());
-      graph_age.erase(graph_age.begin());
-      if (it != graphs.end()) { (void)hipGraphExecDestroy(it->second.exec); graphs.erase(it); return; }
-    }
-    drop_graphs();
-  }
   // workspace of amgx_dist_pcg / amgx_dist_gmres (DistKrylov), kept across solves so that its vector addresses -- the key of the
   // preconditioner's whole-cycle graph -- stay the same
   std::shared_ptr<void> krylov_ws;
@@ -165,7 +163,7 @@ struct Comm {
 
   Comm() { for (int i = 0; i < NEV; ++i) { ev_ready[i] = nullptr; ev_done[i] = nullptr; } }
   ~Comm() {
-    drop_graphs();
+    graphs.drop();
     for (int i = 0; i < NEV; ++i) { if (ev_ready[i]) (void)hipEventDestroy(ev_ready[i]); if (ev_done[i]) (void)hipEventDestroy(ev_done[i]); }
     if (flags) (void)hipFree(flags);
     if (nccl) (void)Rccl::get().CommDestroy(nccl);
@@ -222,6 +220,46 @@ struct Comm {
   // ---- halo exchange.  items[i] = (table, vector) of local member i.  Returns a ticket for exchange_end. -------------
   struct Item { HaloTable* t; double* vec; };
 
+  // The wire.  Peer k of a rank has two segments: its share of the pack buffer (`sendbuf`, the rows this rank owns and the
+  // peer keeps as ghosts) and its share of the vector's ghost block (the rows the peer owns).  `to_ghost`: every pack segment
+  // travels into the ghost segment its peer keeps for this rank (owner -> ghost); otherwise every ghost segment travels into
+  // the peer's pack segment (ghost -> owner).
+  static int64_t seg_len(const HaloTable& t, size_t k, bool pack) { const auto& p = pack ? t.send_ptr : t.recv_ptr; return (p[k + 1] - p[k]) * t.bs; }
+  static double* seg(const Item& it, size_t k, bool pack) {
+    return pack ? it.t->sendbuf.p + it.t->send_ptr[k] * it.t->bs : it.vec + (it.t->n + it.t->recv_ptr[k]) * it.t->bs;
+  }
+  // RCCL: one group of sends and receives with this rank's peers (per peer the send first, on every rank)
+  void wire_rccl(const Item& it, bool to_ghost) {
+    Rccl& R = Rccl::get();
+    const HaloTable& t = *it.t;
+    if (t.peers.empty()) return;
+    NCCLCHK(R.GroupStart());
+    for (size_t k = 0; k < t.peers.size(); ++k) {
+      const int64_t n_out = seg_len(t, k, to_ghost), n_in = seg_len(t, k, !to_ghost);
+      if (n_out) NCCLCHK(R.Send(seg(it, k, to_ghost), (size_t)n_out, ncclDouble, t.peers[k], nccl, comm_stream));
+      if (n_in) NCCLCHK(R.Recv(seg(it, k, !to_ghost), (size_t)n_in, ncclDouble, t.peers[k], nccl, comm_stream));
+    }
+    NCCLCHK(R.GroupEnd());
+  }
+  // local ranks: every source segment is copied into the matching segment of the peer
+  void wire_local(const std::vector<Item>& items, bool to_ghost) {
+    for (size_t i = 0; i < items.size(); ++i) {
+      const HaloTable& t = *items[i].t;
+      for (size_t k = 0; k < t.peers.size(); ++k) {
+        const int q = t.peers[k];
+        const int64_t len = seg_len(t, k, to_ghost);
+        if (!len) continue;
+        if (q < 0 || q >= (int)items.size()) throw Err("local exchange: peer out of range");
+        const int kq = items[q].t->peer_pos((int)i);
+        if (kq < 0 || seg_len(*items[q].t, kq, !to_ghost) != len) throw Err("local exchange: send / receive sizes do not match");
+        dev_copy(seg(items[q], kq, !to_ghost), seg(items[i], k, to_ghost), len, comm_stream);
+      }
+    }
+  }
+  void wire(const std::vector<Item>& items, bool to_ghost) {
+    if (kind == AMGX_COMM_RCCL) wire_rccl(items[0], to_ghost); else wire_local(items, to_ghost);
+  }
+
   // owner -> ghost, overwrite (reference CO2CU: BufferM, send, ApplyG; dcc_map.cpp:138-178, 280-302)
   int exchange_begin(const std::vector<Item>& items) {
     Range rg("DCCMap::StartCO2CU");
@@ -230,38 +268,9 @@ struct Comm {
     order(compute, comm_stream, tk, ev_ready[tk]);                 // everything the vectors depend on is enqueued
     for (const Item& it : items) {
       const int64_t len = it.t->n_send() * it.t->bs;
-      if (len) hipLaunchKernelGGL(halo_pack_kernel, dim3(Handle::grid_for(len)), dim3(BLOCK), 0, comm_stream, len, it.t->bs,
-                                  it.t->send_idx.p, it.vec, it.t->sendbuf.p);
+      if (len) launch(halo_pack_kernel, Handle::grid_for(len), BLOCK, 0, comm_stream, len, it.t->bs, it.t->send_idx.p, it.vec, it.t->sendbuf.p);
     }
-    HIPCHK(hipGetLastError());
-    if (kind == AMGX_COMM_RCCL) {
-      Rccl& R = Rccl::get();
-      const HaloTable& t = *items[0].t;
-      double* vec = items[0].vec;
-      if (!t.peers.empty()) {
-        NCCLCHK(R.GroupStart());
-        for (size_t k = 0; k < t.peers.size(); ++k) {
-          const int64_t ns = (t.send_ptr[k + 1] - t.send_ptr[k]) * t.bs, nr = (t.recv_ptr[k + 1] - t.recv_ptr[k]) * t.bs;
-          if (ns) NCCLCHK(R.Send(t.sendbuf.p + t.send_ptr[k] * t.bs, (size_t)ns, ncclDouble, t.peers[k], nccl, comm_stream));
-          if (nr) NCCLCHK(R.Recv(vec + (t.n + t.recv_ptr[k]) * t.bs, (size_t)nr, ncclDouble, t.peers[k], nccl, comm_stream));
-        }
-        NCCLCHK(R.GroupEnd());
-      }
-    } else {
-      for (size_t i = 0; i < items.size(); ++i) {
-        const HaloTable& t = *items[i].t;
-        for (size_t k = 0; k < t.peers.size(); ++k) {
-          const int q = t.peers[k];
-          const int64_t ns = (t.send_ptr[k + 1] - t.send_ptr[k]) * t.bs;
-          if (!ns) continue;
-          if (q < 0 || q >= (int)items.size()) throw Err("local exchange: peer out of range");
-          const HaloTable& tq = *items[q].t;
-          const int kq = tq.peer_pos((int)i);
-          if (kq < 0 || (tq.recv_ptr[kq + 1] - tq.recv_ptr[kq]) * tq.bs != ns) throw Err("local exchange: send / receive sizes do not match");
-          dev_copy(items[q].vec + (tq.n + tq.recv_ptr[kq]) * tq.bs, t.sendbuf.p + t.send_ptr[k] * t.bs, ns, comm_stream);
-        }
-      }
-    }
+    wire(items, true);
     done_value[tk] = signal(comm_stream, NEV + tk, ev_done[tk]);
     return tk;
   }
@@ -273,45 +282,14 @@ struct Comm {
     const int tk = ev_next; ev_next = (ev_next + 1) % NEV;
     ++n_exchanges;
     order(compute, comm_stream, tk, ev_ready[tk]);
-    if (kind == AMGX_COMM_RCCL) {
-      Rccl& R = Rccl::get();
-      const HaloTable& t = *items[0].t;
-      double* vec = items[0].vec;
-      if (!t.peers.empty()) {
-        NCCLCHK(R.GroupStart());
-        for (size_t k = 0; k < t.peers.size(); ++k) {
-          const int64_t ns = (t.send_ptr[k + 1] - t.send_ptr[k]) * t.bs, nr = (t.recv_ptr[k + 1] - t.recv_ptr[k]) * t.bs;
-          if (nr) NCCLCHK(R.Send(vec + (t.n + t.recv_ptr[k]) * t.bs, (size_t)nr, ncclDouble, t.peers[k], nccl, comm_stream));
-          if (ns) NCCLCHK(R.Recv(t.sendbuf.p + t.send_ptr[k] * t.bs, (size_t)ns, ncclDouble, t.peers[k], nccl, comm_stream));
-        }
-        NCCLCHK(R.GroupEnd());
-      }
-    } else {
-      for (size_t i = 0; i < items.size(); ++i) {
-        const HaloTable& t = *items[i].t;
-        for (size_t k = 0; k < t.peers.size(); ++k) {
-          const int q = t.peers[k];
-          const int64_t nr = (t.recv_ptr[k + 1] - t.recv_ptr[k]) * t.bs;
-          if (!nr) continue;
-          if (q < 0 || q >= (int)items.size()) throw Err("local exchange: peer out of range");
-          const HaloTable& tq = *items[q].t;
-          const int kq = tq.peer_pos((int)i);
-          if (kq < 0 || (tq.send_ptr[kq + 1] - tq.send_ptr[kq]) * tq.bs != nr) throw Err("local exchange: send / receive sizes do not match");
-          dev_copy(tq.sendbuf.p + tq.send_ptr[kq] * tq.bs, items[i].vec + (t.n + t.recv_ptr[k]) * t.bs, nr, comm_stream);
-        }
-      }
-    }
+    wire(items, false);
     for (const Item& it : items) {
       const HaloTable& t = *it.t;
       const int64_t gl = t.n_ghost * t.bs;
-      if (gl) hipLaunchKernelGGL(halo_zero_kernel, dim3(Handle::grid_for(gl)), dim3(BLOCK), 0, comm_stream, gl, it.vec + t.n * t.bs);
-      for (size_t k = 0; k < t.peers.size(); ++k) {          // one launch per peer: two peers may both contribute to a row
-        const int64_t len = (t.send_ptr[k + 1] - t.send_ptr[k]) * t.bs;
-        if (len) hipLaunchKernelGGL(halo_unpack_add_kernel, dim3(Handle::grid_for(len)), dim3(BLOCK), 0, comm_stream, len, t.bs,
-                                    t.send_idx.p + t.send_ptr[k], t.sendbuf.p + t.send_ptr[k] * t.bs, it.vec);
-      }
+      if (gl) launch(halo_zero_kernel, Handle::grid_for(gl), BLOCK, 0, comm_stream, gl, it.vec + t.n * t.bs);
+      for (size_t k = 0; k < t.peers.size(); ++k)            // one launch per peer: two peers may both contribute to a row
+        if (const int64_t len = seg_len(t, k, true)) launch(halo_unpack_add_kernel, Handle::grid_for(len), BLOCK, 0, comm_stream, len, t.bs, t.send_idx.p + t.send_ptr[k], seg(it, k, true), it.vec);
     }
-    HIPCHK(hipGetLastError());
     order(comm_stream, compute, NEV + tk, ev_done[tk]);
   }
 };
@@ -324,11 +302,9 @@ struct Dist {
   std::unique_ptr<Handle> top, tail;
   int k = 0;                             // levels 0..k-1 smoothed in rank-partitioned form, level k gathered
   int sm_type = AMGX_SM_JACOBI;
-  bool fold = true;
-  bool overlap = true;
-  bool gsb = false;                      // Gauss-Seidel levels in the block-hybrid form
-  bool generic = false;                  // sm_steps > 1 / sm_symm on a rank-partitioned level, or a W-cycle: the step-by-step driver
-  int cycle = AMGX_CYCLE_V;              //   (DistCycle::generic_cycle) instead of the specialised V(1,1) stage sequences
+  DistPath path = DistPath::JACOBI_FOLDED;   // the driver of the collective cycle; all members of a communicator agree
+  bool overlap = true;                   // interior rows run beside the exchanges (orthogonal to the path)
+  int cycle = AMGX_CYCLE_V;
   std::vector<HaloTable> halo;           // [k]
   std::vector<std::array<int, 4>> stage; // [k] colour ranges of the hybrid Gauss-Seidel stages: [s0,s1) first local part,
                                          //     [s1,s2) boundary ("EX") rows, [s2,s3) second local part (gssmoother.cpp:721-782)
@@ -375,11 +351,12 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
     for (int l = 0; l < hd->n_levels; ++l)
       if (hd->levels && hd->levels[l].sm_type == AMGX_SM_CHEBY)
         throw Err("amgx_dist_create: the Chebyshev smoother (AMGX_SM_CHEBY) is not available on rank-partitioned hierarchies");
-  D->fold = d->fold != 0;
+  const bool fold = d->fold != 0;
+  bool generic = false, gsb = false;
   D->cycle = d->top.cycle;
   if (D->cycle != AMGX_CYCLE_V && D->cycle != AMGX_CYCLE_W) throw Err("amgx_dist_create: rank-partitioned hierarchies run V and W cycles");
   if (d->tail.cycle != d->top.cycle) throw Err("amgx_dist_create: the replicated tail must run the same cycle as the rank-partitioned levels");
-  if (D->cycle == AMGX_CYCLE_W) D->generic = true;
+  if (D->cycle == AMGX_CYCLE_W) generic = true;
   D->overlap = !K.dist_no_overlap;
   amgx_hierarchy_desc td = d->top;
   td.device = c->device; td.use_graph = 0; td.clev = AMGX_CLEV_NONE; td.coarse_n = 0; td.coarse_inv = nullptr;
@@ -396,11 +373,11 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
   for (int l = 0; l < k; ++l) {
     const amgx_level_desc& s = d->top.levels[l];
     if (s.sm_type != D->sm_type) throw Err("amgx_dist_create: all rank-partitioned levels must use the same smoother");
-    if (s.sm_steps > 1 || s.sm_symm) D->generic = true;      // ProxySmoother on a rank-partitioned level (base_smoother.hpp:169-229)
+    if (s.sm_steps > 1 || s.sm_symm) generic = true;      // ProxySmoother on a rank-partitioned level (base_smoother.hpp:169-229)
     if (s.sm_steps != d->top.levels[0].sm_steps || s.sm_symm != d->top.levels[0].sm_symm) throw Err("amgx_dist_create: all rank-partitioned levels must use the same sm_steps / sm_symm");
     D->halo[l].build(d->halo[l], s.A.n_rows, s.A.n_cols, s.A.br, c->nranks, self);
     dist_check_interior(s.A, D->halo[l].n_int);
-    if (D->fold && s.Q.rowptr) {           // the way up splits the same way: interior rows of Q must not read coarse ghosts
+    if (fold && s.Q.rowptr) {           // the way up splits the same way: interior rows of Q must not read coarse ghosts
       const int64_t nco = d->top.levels[l + 1].A.n_rows;
       for (int64_t i = 0; i < D->halo[l].n_int; ++i)
         for (int64_t e = s.Q.rowptr[i]; e < s.Q.rowptr[i + 1]; ++e)
@@ -440,8 +417,8 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
         if (hd.send_idx[i] < first_bnd) { D->send_early[l] = 0; break; }
     }
   }
-  if (D->fold && D->generic) throw Err("amgx_dist_create: fold is the V(1,1) Jacobi form (no sm_steps / sm_symm / W-cycle)");
-  if (D->fold) {
+  if (fold && generic) throw Err("amgx_dist_create: fold is the V(1,1) Jacobi form (no sm_steps / sm_symm / W-cycle)");
+  if (fold) {
     if (D->sm_type != AMGX_SM_JACOBI) throw Err("amgx_dist_create: fold needs Jacobi levels");
     for (int l = 0; l < k; ++l) if (!D->top->folded(D->top->lev[l])) throw Err("amgx_dist_create: fold requested but level " + std::to_string(l) + " has no Q");
   }
@@ -449,13 +426,16 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
     int on = 0;
     for (int l = 0; l < k; ++l) on += D->top->lev[l].paths.hybrid() ? 1 : 0;
     if (on != 0 && on != k) throw Err("amgx_dist_create: either all or none of the rank-partitioned Gauss-Seidel levels use gs_block_rows");
-    D->gsb = on == k;
+    gsb = on == k;
   }
+  D->path = generic ? DistPath::STEPWISE
+          : D->sm_type == AMGX_SM_JACOBI ? (fold ? DistPath::JACOBI_FOLDED : DistPath::JACOBI_LITERAL)
+          : gsb ? DistPath::GS_BLOCK_HYBRID : DistPath::GS_STAGED;
   D->bext.resize(k); D->xext.resize(k); D->text.resize(k); D->rl.resize(k);
   auto zalloc = [&](DevBuf<double>& b, int64_t len) { b.alloc((size_t)std::max<int64_t>(1, len)); HIPCHK(hipMemset(b.p, 0, std::max<int64_t>(1, len) * sizeof(double))); };
   for (int l = 0; l < k; ++l) {
     zalloc(D->bext[l], D->next(l)); zalloc(D->xext[l], D->next(l)); zalloc(D->rl[l], D->n(l));
-    if ((!D->fold && D->sm_type == AMGX_SM_JACOBI) || D->gsb || D->generic) zalloc(D->text[l], D->next(l));
+    if (D->path != DistPath::JACOBI_FOLDED && D->path != DistPath::GS_STAGED) zalloc(D->text[l], D->next(l));     // (the others work out of place)
   }
   // level k: gathered in rank order
   D->counts.assign(d->counts, d->counts + c->nranks);
@@ -491,226 +471,198 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// the collective cycle.  All members of the communicator advance stage by stage (one member under RCCL).
+// the collective cycle.  All members of the communicator advance stage by stage (one member under RCCL): every stage is a
+// loop over the local ranks in member order -- kernels of virtual ranks serialise on the one GPU in that order, and the RCCL
+// group calls keep theirs on every rank.
 struct DistCycle {
   Comm& c;
   std::vector<Dist*>& M;
   std::vector<double*> x;                // level-0 solution vectors (device)
+  std::vector<const double*> b0;         // level-0 right-hand sides
+  const int k = M[0]->k;
   using Span = Handle::Span;
 
+  template <class F>
+  void each(F&& f) { for (size_t i = 0; i < M.size(); ++i) f(*M[i], i); }
   std::vector<Comm::Item> items(int l, int which) {      // which: 0 bext, 1 xext, 2 text
     std::vector<Comm::Item> it;
     for (Dist* d : M) it.push_back({&d->halo[l], which == 0 ? d->bext[l].p : which == 1 ? d->xext[l].p : d->text[l].p});
     return it;
   }
-  double* xl(Dist* d, int i, int l) { return l == 0 ? x[i] : d->xext[l].p; }
-  double* bnext(Dist* d, int l) { return l + 1 < d->k ? d->bext[l + 1].p : d->bk.p; }
+  double* xl(Dist& d, size_t i, int l) { return l == 0 ? x[i] : d.xext[l].p; }
+  const double* bl(Dist& d, size_t i, int l) { return l == 0 ? b0[i] : (const double*)d.bext[l].p; }
+  double* bnext(Dist& d, int l) { return l + 1 < k ? d.bext[l + 1].p : d.bk.p; }
+  const double* xcoarse(Dist& d, int l) { return l + 1 < k ? d.xext[l + 1].p : d.xk_ext.p; }     // owned part first in both
+
+  // The overlapped stage: rows(d, i, span) on every rank around the end of the exchange with ticket `tk` (tk < 0: none in
+  // flight, one launch covers everything).  With Dist::overlap the interior rows run while the exchange travels and the
+  // boundary rows after it; without it everything runs after it.  What `rows` launches decides how a span is cut: formats that
+  // cannot be split run completely in the boundary part, and a level without boundary rows reports everything as interior
+  // (Dist::n_int_span), so that its boundary part is empty.
+  template <class F>
+  void overlapped(int l, int tk, F&& rows) {
+    const bool split = tk >= 0 && M[0]->overlap;
+    if (split) each([&](Dist& d, size_t i) { rows(d, i, Span{Handle::PART_INT, d.n_int_span(l)}); });
+    if (tk >= 0) c.exchange_end(tk);
+    each([&](Dist& d, size_t i) { rows(d, i, split ? Span{Handle::PART_BND, d.n_int_span(l)} : Span()); });
+  }
 
   void gather_level_k() {
-    for (size_t i = 0; i < M.size(); ++i) {
-      Dist* d = M[i];
-      const int bsk = d->top->lev[d->k].bs;
+    each([&](Dist& d, size_t i) {
+      const int bsk = d.top->lev[k].bs;
       if (c.kind == AMGX_COMM_RCCL) {
         Rccl& R = Rccl::get();
-        if (c.nranks == 1 && !d->force_allgather) d->top->copy(d->bglob.p, d->bk.p, d->n(d->k));
-        else if (d->compact.n == 0) NCCLCHK(R.AllGather(d->bk.p, d->bglob.p, (size_t)(d->mcount * bsk), ncclDouble, c.nccl, c.compute));
+        if (c.nranks == 1 && !d.force_allgather) d.top->copy(d.bglob.p, d.bk.p, d.n(k));
+        else if (d.compact.n == 0) NCCLCHK(R.AllGather(d.bk.p, d.bglob.p, (size_t)(d.mcount * bsk), ncclDouble, c.nccl, c.compute));
         else {
-          NCCLCHK(R.AllGather(d->bk.p, d->bpad.p, (size_t)(d->mcount * bsk), ncclDouble, c.nccl, c.compute));
-          const int64_t len = d->offs.back() * bsk;
-          hipLaunchKernelGGL(index_gather_kernel, dim3(Handle::grid_for(len)), dim3(BLOCK), 0, c.compute, len, d->compact.p, d->bpad.p, d->bglob.p);
-          HIPCHK(hipGetLastError());
+          NCCLCHK(R.AllGather(d.bk.p, d.bpad.p, (size_t)(d.mcount * bsk), ncclDouble, c.nccl, c.compute));
+          const int64_t len = d.offs.back() * bsk;
+          launch(index_gather_kernel, Handle::grid_for(len), BLOCK, 0, c.compute, len, d.compact.p, d.bpad.p, d.bglob.p);
         }
       } else {
         for (size_t q = 0; q < M.size(); ++q)
-          if (d->counts[i]) dev_copy(M[q]->bglob.p + d->offs[i] * bsk, d->bk.p, d->counts[i] * bsk, c.compute);
+          if (d.counts[i]) dev_copy(M[q]->bglob.p + d.offs[i] * bsk, d.bk.p, d.counts[i] * bsk, c.compute);
       }
-    }
+    });
   }
-
-  void tail_and_pick() {
-    for (Dist* d : M) {
+  // level k: gather the pieces, run the replicated tail, pick this rank's [owned | ghost] entries of its solution
+  void tail() {
+    gather_level_k();
+    each([&](Dist& d, size_t) {
       // replicated tail: direct launches by default -- a graph launch between directly launched kernels costs ~10 us of
       // stream time (profiles/r02/trace_dist_world1.txt), the tail's handful of kernels do not pay that back
-      d->tail->run_cycle(d->xglob.p, d->bglob.p, d->tail->knobs.dist_tail_graph && !c.capturing);
-      const int64_t len = d->next(d->k);
-      if (len) hipLaunchKernelGGL(index_gather_kernel, dim3(Handle::grid_for(len)), dim3(BLOCK), 0, c.compute, len, d->kmap.p, d->xglob.p, d->xk_ext.p);
-      HIPCHK(hipGetLastError());
-    }
+      d.tail->run_cycle(d.xglob.p, d.bglob.p, d.tail->knobs.dist_tail_graph && !c.capturing);
+      const int64_t len = d.next(k);
+      if (len) launch(index_gather_kernel, Handle::grid_for(len), BLOCK, 0, c.compute, len, d.kmap.p, d.xglob.p, d.xk_ext.p);
+    });
   }
 
-  // ---- Jacobi, post-smoothing folded into the prolongation: 2k - 1 exchanges ------------------------
+  // ---- Jacobi, post-smoothing folded into the prolongation: 2k - 1 exchanges.  The exchange of x_l started
+  //      on the way up ends inside the stage of level l - 1 (the deferred ticket) ----------------------------------------
   void jacobi_folded() {
-    const int k = M[0]->k;
-    for (int l = 0; l < k; ++l) {
-      const int tk = c.exchange_begin(items(l, 0));
-      if (M[0]->overlap)
-        for (size_t i = 0; i < M.size(); ++i) { Dist* d = M[i]; d->top->pre_smooth_restrict(l, xl(d, i, l), d->bext[l].p, d->rl[l].p, bnext(d, l), true, Span{Handle::PART_INT, d->n_int_span(l)}); }
-      c.exchange_end(tk);
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        d->top->pre_smooth_restrict(l, xl(d, i, l), d->bext[l].p, d->rl[l].p, bnext(d, l), true, M[0]->overlap ? Span{Handle::PART_BND, d->n_int_span(l)} : Span());
-      }
-    }
-    gather_level_k();
-    tail_and_pick();
+    for (int l = 0; l < k; ++l)
+      overlapped(l, c.exchange_begin(items(l, 0)), [&](Dist& d, size_t i, Span sp) {
+        d.top->pre_smooth_restrict(l, xl(d, i, l), d.bext[l].p, d.rl[l].p, bnext(d, l), true, sp);
+      });
+    tail();
     int tk = -1;
     for (int l = k - 1; l >= 0; --l) {
-      if (tk >= 0 && M[0]->overlap)
-        for (size_t i = 0; i < M.size(); ++i) { Dist* d = M[i]; d->top->post_smooth(l, xl(d, i, l), nullptr, d->rl[l].p, d->xext[l + 1].p, true, Span{Handle::PART_INT, d->n_int_span(l)}); }
-      const bool split = tk >= 0 && M[0]->overlap;
-      if (tk >= 0) c.exchange_end(tk);
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        const double* xc = l + 1 < k ? d->xext[l + 1].p : d->xk_ext.p;
-        d->top->post_smooth(l, xl(d, i, l), nullptr, d->rl[l].p, xc, true, split ? Span{Handle::PART_BND, d->n_int_span(l)} : Span());
-      }
+      overlapped(l, tk, [&](Dist& d, size_t i, Span sp) { d.top->post_smooth(l, xl(d, i, l), nullptr, d.rl[l].p, xcoarse(d, l), true, sp); });
       tk = l > 0 ? c.exchange_begin(items(l, 1)) : -1;
     }
   }
 
   // ---- Jacobi, literal stage order (base_smoother.cpp:61-74 around dof_map.cpp:636-709): 2k exchanges ----------------
   void jacobi_literal() {
-    const int k = M[0]->k;
-    for (int l = 0; l < k; ++l) {
-      const int tk = c.exchange_begin(items(l, 0));
-      if (M[0]->overlap)
-        for (size_t i = 0; i < M.size(); ++i) { Dist* d = M[i]; d->top->pre_smooth(d->top->lev[l], xl(d, i, l), d->bext[l].p, d->rl[l].p, false, Span{Handle::PART_INT, d->n_int_span(l)}); }
-      c.exchange_end(tk);
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        d->top->pre_smooth(d->top->lev[l], xl(d, i, l), d->bext[l].p, d->rl[l].p, false, M[0]->overlap ? Span{Handle::PART_BND, d->n_int_span(l)} : Span());
-        d->top->transfer_f2c(l, d->rl[l].p, bnext(d, l));
-      }
-    }
-    gather_level_k();
-    tail_and_pick();
+    for (int l = 0; l < k; ++l)
+      overlapped(l, c.exchange_begin(items(l, 0)), [&](Dist& d, size_t i, Span sp) {
+        d.top->pre_smooth(d.top->lev[l], xl(d, i, l), d.bext[l].p, d.rl[l].p, false, sp);
+        if (sp.part != Handle::PART_INT) d.top->transfer_f2c(l, d.rl[l].p, bnext(d, l));      // (once the rank's residual is complete)
+      });
+    tail();
     for (int l = k - 1; l >= 0; --l) {
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        const double* xc = l + 1 < k ? d->xext[l + 1].p : d->xk_ext.p;       // owned part first in both
-        d->top->mult_add(d->top->lev[l].P, 1.0, xc, xl(d, i, l), d->text[l].p);
-      }
-      const int tk = c.exchange_begin(items(l, 2));
-      if (M[0]->overlap)
-        for (size_t i = 0; i < M.size(); ++i) { Dist* d = M[i]; d->top->jacobi_fused(d->top->lev[l], d->text[l].p, d->bext[l].p, xl(d, i, l), Span{Handle::PART_INT, d->n_int_span(l)}); }
-      c.exchange_end(tk);
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        d->top->jacobi_fused(d->top->lev[l], d->text[l].p, d->bext[l].p, xl(d, i, l), M[0]->overlap ? Span{Handle::PART_BND, d->n_int_span(l)} : Span());
-      }
+      each([&](Dist& d, size_t i) { d.top->mult_add(d.top->lev[l].P, 1.0, xcoarse(d, l), xl(d, i, l), d.text[l].p); });
+      overlapped(l, c.exchange_begin(items(l, 2)), [&](Dist& d, size_t i, Span sp) {
+        d.top->jacobi_fused(d.top->lev[l], d.text[l].p, d.bext[l].p, xl(d, i, l), sp);
+      });
     }
   }
 
-  // ---- hybrid (block) Gauss-Seidel: local sweeps with the off-rank values frozen at their sweep-start values
-  //      (HybridGSSmoother, gssmoother.cpp:709-861; stages LOC_1 / EX / LOC_2 = colour ranges, :721-782) ---------------
-  void sweep(Dist* d, int l, int dir, double* xv, const double* b, int c0, int c1) {
-    if (c1 <= c0) return;
-    DevLevel& L = d->top->lev[l];
-    if (d->sm_type == AMGX_SM_BGS) d->top->bgs_sweep(L, dir, xv, b, c0, c1);
-    else d->top->gs_sweep(L, dir, xv, b, false, c0, c1);
-  }
-  // ---- Gauss-Seidel in the block-hybrid form (gsb_sweep_kernel): the blocks of a sweep are independent of each other
+  // ---- hybrid Gauss-Seidel: local sweeps with the off-rank values frozen at their sweep-start values (HybridGSSmoother,
+  //      gssmoother.cpp:709-861).  Both drivers below run the same sequence -- sweep the part whose rows are sent, start the
+  //      exchange of x, sweep the rest behind it, end it, residual + restriction; on the way up the mirror image around the
+  //      exchange of x + P x_c -- and are kept as two: the staged form sweeps colour ranges in place (it zeroes the whole
+  //      vector, prolongs in place, exchanges xext and finishes with the part it began with), the block form sweeps block ranges
+  //      out of place (it zeroes the ghosts only, prolongs into text, exchanges text, has its own residual forms and carries
+  //      the probe).  A description of the ranges and the sweep that covers both is longer than the two loops.
+  //
+  //      Block-hybrid form (gsb_sweep_kernel / bgsb_sweep_kernel): the blocks of a sweep are independent of each other
   //      (couplings that leave a block -- ghost columns included -- use the sweep-start vector), so the boundary blocks are
   //      swept first, the exchange of x starts, and the interior blocks run behind it; on the way up the interior blocks
   //      run while x + P x_c travels.  Two launches per sweep instead of one per colour and stage.
-  void hybrid_gsb(const std::vector<const double*>& b0) {
-    const int k = M[0]->k;
-    auto bl = [&](Dist* d, size_t i, int l) { return l == 0 ? b0[i] : (const double*)d->bext[l].p; };
+  void hybrid_gsb() {
     // (a level with a sent row inside an interior block sweeps all its blocks before the exchange: see Dist::send_early)
-    auto nbi = [&](Dist* d, int l) {
-      const DevLevel& L = d->top->lev[l];
-      return d->send_early[l] ? (int)(d->halo[l].n_int / (L.paths.sweep == SWEEP_GSB ? L.gsb.B : L.bgsb.BB)) : 0;
+    auto nbi = [&](Dist& d, int l) {
+      const DevLevel& L = d.top->lev[l];
+      return d.send_early[l] ? (int)(d.halo[l].n_int / (L.paths.sweep == SWEEP_GSB ? L.gsb.B : L.bgsb.BB)) : 0;
     };
     // scalar levels: gsb_sweep_kernel; square-block levels: bgsb_sweep_kernel (same block ranges, same stages)
-    auto sweep_zero = [&](Dist* d, int l, double* xout, const double* b, int q0, int q1) {
-      DevLevel& L = d->top->lev[l];
-      if (L.paths.bgsb()) d->top->bgsb_sweep(L, 0, nullptr, xout, b, L.bgsb.has_split, q0, q1);
-      else d->top->gsb_sweep(L, 0, L.gsb.has_split ? L.gsb.lowin : L.gsb.full, nullptr, xout, b, q0, q1);
+    auto sweep_zero = [&](Dist& d, size_t i, int l, int q0, int q1) {
+      DevLevel& L = d.top->lev[l];
+      if (L.paths.bgsb()) d.top->bgsb_sweep(L, 0, nullptr, d.xext[l].p, bl(d, i, l), L.bgsb.has_split, q0, q1);
+      else d.top->gsb_sweep(L, 0, L.gsb.has_split ? L.gsb.lowin : L.gsb.full, nullptr, d.xext[l].p, bl(d, i, l), q0, q1);
     };
-    auto sweep_back = [&](Dist* d, int l, const double* xin, double* xout, const double* b, int q0, int q1) {
-      DevLevel& L = d->top->lev[l];
-      if (L.paths.bgsb()) d->top->bgsb_sweep(L, 1, xin, xout, b, false, q0, q1);
-      else d->top->gsb_sweep(L, 1, L.gsb.full, xin, xout, b, q0, q1);
+    auto sweep_back = [&](Dist& d, size_t i, int l, int q0, int q1) {
+      DevLevel& L = d.top->lev[l];
+      if (L.paths.bgsb()) d.top->bgsb_sweep(L, 1, d.text[l].p, xl(d, i, l), bl(d, i, l), false, q0, q1);
+      else d.top->gsb_sweep(L, 1, L.gsb.full, d.text[l].p, xl(d, i, l), bl(d, i, l), q0, q1);
     };
     for (int l = 0; l < k; ++l) {
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        d->top->zero(d->xext[l].p + d->n(l), d->next(l) - d->n(l));
-        sweep_zero(d, l, d->xext[l].p, bl(d, i, l), nbi(d, l), -1);
-      }
+      each([&](Dist& d, size_t i) {
+        d.top->zero(d.xext[l].p + d.n(l), d.next(l) - d.n(l));
+        sweep_zero(d, i, l, nbi(d, l), -1);
+      });
       const int tk = c.exchange_begin(items(l, 1));
-      for (size_t i = 0; i < M.size(); ++i) { Dist* d = M[i]; sweep_zero(d, l, d->xext[l].p, bl(d, i, l), 0, nbi(d, l)); }
+      each([&](Dist& d, size_t i) { sweep_zero(d, i, l, 0, nbi(d, l)); });
       c.exchange_end(tk);
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        DevLevel& L = d->top->lev[l];
-        if (L.paths.sweep == SWEEP_GSB && L.gsb.has_split) d->top->gsb_residual_restrict(l, d->xext[l].p, d->rl[l].p, bnext(d, l));
+      each([&](Dist& d, size_t i) {
+        DevLevel& L = d.top->lev[l];
+        if (L.paths.sweep == SWEEP_GSB && L.gsb.has_split) d.top->gsb_residual_restrict(l, d.xext[l].p, d.rl[l].p, bnext(d, l));
         else {
-          if (L.paths.bgsb() && L.bgsb.has_split) d->top->mult(L.bgsb.rest, d->xext[l].p, d->rl[l].p);      // r = rest x (see DevBGSB)
-          else d->top->residual(L.A, d->xext[l].p, bl(d, i, l), d->rl[l].p);
-          d->top->transfer_f2c(l, d->rl[l].p, bnext(d, l));
+          if (L.paths.bgsb() && L.bgsb.has_split) d.top->mult(L.bgsb.rest, d.xext[l].p, d.rl[l].p);      // r = rest x (see DevBGSB)
+          else d.top->residual(L.A, d.xext[l].p, bl(d, i, l), d.rl[l].p);
+          d.top->transfer_f2c(l, d.rl[l].p, bnext(d, l));
         }
-      }
+      });
     }
-    gather_level_k();
-    tail_and_pick();
+    tail();
     for (int l = k - 1; l >= 0; --l) {
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        const double* xc = l + 1 < k ? d->xext[l + 1].p : d->xk_ext.p;
-        d->top->mult_add(d->top->lev[l].P, 1.0, xc, d->xext[l].p, d->text[l].p);
-      }
+      each([&](Dist& d, size_t) { d.top->mult_add(d.top->lev[l].P, 1.0, xcoarse(d, l), d.xext[l].p, d.text[l].p); });
       const int tk = c.exchange_begin(items(l, 2));
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
+      each([&](Dist& d, size_t i) {
         // (amgx_dist_time_kernel, op 9: HIP events around the interior blocks' launch of the first local rank)
-        const bool probe = i == 0 && d->top->probe_level == l && d->top->probe_kind == 9 && d->top->probe_e0;
-        if (probe) HIPCHK(hipEventRecord(d->top->probe_e0, c.compute));
-        sweep_back(d, l, d->text[l].p, l == 0 ? x[i] : d->xext[l].p, bl(d, i, l), 0, nbi(d, l));
-        if (probe) HIPCHK(hipEventRecord(d->top->probe_e1, c.compute));
-      }
+        const bool probe = i == 0 && d.top->probe_level == l && d.top->probe_kind == 9 && d.top->probe_e0;
+        d.top->probed(probe, [&] { sweep_back(d, i, l, 0, nbi(d, l)); });
+      });
       c.exchange_end(tk);
-      for (size_t i = 0; i < M.size(); ++i) { Dist* d = M[i]; sweep_back(d, l, d->text[l].p, l == 0 ? x[i] : d->xext[l].p, bl(d, i, l), nbi(d, l), -1); }
+      each([&](Dist& d, size_t i) { sweep_back(d, i, l, nbi(d, l), -1); });
     }
   }
 
-  void hybrid_gs(const std::vector<const double*>& b0) {
-    const int k = M[0]->k;
-    auto bl = [&](Dist* d, size_t i, int l) { return l == 0 ? b0[i] : (const double*)d->bext[l].p; };
+  //      Staged multicolour form: stages LOC_1 / EX / LOC_2 = colour ranges (gssmoother.cpp:721-782)
+  void sweep(Dist& d, size_t i, int l, int dir, int c0, int c1) {
+    if (c1 <= c0) return;
+    DevLevel& L = d.top->lev[l];
+    if (d.sm_type == AMGX_SM_BGS) d.top->bgs_sweep(L, dir, d.xext[l].p, bl(d, i, l), c0, c1);
+    else d.top->gs_sweep(L, dir, d.xext[l].p, bl(d, i, l), false, c0, c1);
+  }
+  void hybrid_gs() {
     for (int l = 0; l < k; ++l) {
       // pre: x = 0; forward sweep (all off-rank values are 0, no exchange needed before it); the owner -> ghost exchange
       // of x starts as soon as the boundary stage is done and hides behind the second local stage
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        d->top->zero(d->xext[l].p, d->next(l));
-        sweep(d, l, 0, d->xext[l].p, bl(d, i, l), d->stage[l][0], d->stage[l][2]);
-      }
+      each([&](Dist& d, size_t i) {
+        d.top->zero(d.xext[l].p, d.next(l));
+        sweep(d, i, l, 0, d.stage[l][0], d.stage[l][2]);
+      });
       const int tk = c.exchange_begin(items(l, 1));
-      for (size_t i = 0; i < M.size(); ++i) { Dist* d = M[i]; sweep(d, l, 0, d->xext[l].p, bl(d, i, l), d->stage[l][2], d->stage[l][3]); }
+      each([&](Dist& d, size_t i) { sweep(d, i, l, 0, d.stage[l][2], d.stage[l][3]); });
       c.exchange_end(tk);
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        d->top->residual(d->top->lev[l].A, d->xext[l].p, bl(d, i, l), d->rl[l].p);
-        d->top->transfer_f2c(l, d->rl[l].p, bnext(d, l));
-      }
+      each([&](Dist& d, size_t i) {
+        d.top->residual(d.top->lev[l].A, d.xext[l].p, bl(d, i, l), d.rl[l].p);
+        d.top->transfer_f2c(l, d.rl[l].p, bnext(d, l));
+      });
     }
-    gather_level_k();
-    tail_and_pick();
+    tail();
     for (int l = k - 1; l >= 0; --l) {
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        const double* xc = l + 1 < k ? d->xext[l + 1].p : d->xk_ext.p;
-        d->top->mult_add(d->top->lev[l].P, 1.0, xc, d->xext[l].p, d->xext[l].p);
-      }
+      each([&](Dist& d, size_t) { d.top->mult_add(d.top->lev[l].P, 1.0, xcoarse(d, l), d.xext[l].p, d.xext[l].p); });
       // post: backward sweep = the stages in reverse order; the exchange hides behind the (reversed) second local stage
       const int tk = c.exchange_begin(items(l, 1));
-      for (size_t i = 0; i < M.size(); ++i) { Dist* d = M[i]; sweep(d, l, 1, d->xext[l].p, bl(d, i, l), d->stage[l][2], d->stage[l][3]); }
+      each([&](Dist& d, size_t i) { sweep(d, i, l, 1, d.stage[l][2], d.stage[l][3]); });
       c.exchange_end(tk);
-      for (size_t i = 0; i < M.size(); ++i) {
-        Dist* d = M[i];
-        sweep(d, l, 1, d->xext[l].p, bl(d, i, l), d->stage[l][0], d->stage[l][2]);
-        if (l == 0) d->top->copy(x[i], d->xext[0].p, d->n(0));
-      }
+      each([&](Dist& d, size_t i) {
+        sweep(d, i, l, 1, d.stage[l][0], d.stage[l][2]);
+        if (l == 0) d.top->copy(x[i], d.xext[0].p, d.n(0));
+      });
     }
   }
 
@@ -721,88 +673,70 @@ struct DistCycle {
   //      staged / block-hybrid sweep).  No interior / boundary overlap here: one exchange, one launch per step.
   struct GenState { std::vector<double*> cur, oth; };        // per level: the [owned | ghost] buffer that holds x, and the spare one
   std::vector<GenState> gx;
-  std::vector<const double*> gb0;
-  const double* gbl(size_t i, int l) { return l == 0 ? gb0[i] : (const double*)M[i]->bext[l].p; }
   void gen_exchange(int l) {
     std::vector<Comm::Item> it;
-    for (size_t i = 0; i < M.size(); ++i) it.push_back({&M[i]->halo[l], gx[l].cur[i]});
+    each([&](Dist& d, size_t i) { it.push_back({&d.halo[l], gx[l].cur[i]}); });
     c.exchange_end(c.exchange_begin(it));
   }
   void gen_step(int l, int dir, bool x_zero) {
     if (!x_zero) gen_exchange(l);                              // (from x = 0 the ghost values are zeros already)
-    for (size_t i = 0; i < M.size(); ++i) {
-      Dist* d = M[i];
-      Handle& h = *d->top;
+    each([&](Dist& d, size_t i) {
+      Handle& h = *d.top;
       DevLevel& L = h.lev[l];
       double*& cur = gx[l].cur[i];
       double*& oth = gx[l].oth[i];
-      const double* b = gbl(i, l);
-      if (d->sm_type == AMGX_SM_JACOBI) { h.jacobi_fused(L, cur, b, oth); std::swap(cur, oth); }
+      const double* b = bl(d, i, l);
+      if (d.sm_type == AMGX_SM_JACOBI) { h.jacobi_fused(L, cur, b, oth); std::swap(cur, oth); }
       else if (L.paths.bgsb()) { h.bgsb_sweep(L, dir, cur, oth, b); std::swap(cur, oth); }
       else if (L.paths.sweep == SWEEP_GSB) { h.gsb_sweep(L, dir, L.gsb.full, cur, oth, b); std::swap(cur, oth); }
-      else if (d->sm_type == AMGX_SM_BGS) h.bgs_sweep(L, dir, cur, b);
+      else if (d.sm_type == AMGX_SM_BGS) h.bgs_sweep(L, dir, cur, b);
       else h.gs_sweep(L, dir, cur, b);
-    }
+    });
   }
-  // k steps in direction dir, or k x (forward, backward) with sm_symm
+  // sm_steps steps in direction dir, or sm_steps x (forward, backward) with sm_symm
   void gen_smooth(int l, int dir, bool x_zero) {
     const DevLevel& L0 = M[0]->top->lev[l];
-    const int k = std::max(1, L0.sm_steps);
-    for (int j = 0; j < k; ++j) {
+    const int steps = std::max(1, L0.sm_steps);
+    for (int j = 0; j < steps; ++j) {
       if (L0.sm_symm) { gen_step(l, 0, x_zero && j == 0); gen_step(l, 1, false); }
       else gen_step(l, dir, x_zero && j == 0);
     }
   }
-  void gen_zero(int l) { for (size_t i = 0; i < M.size(); ++i) M[i]->top->zero(gx[l].cur[i], M[i]->next(l)); }
-  void gen_residual_restrict(int l) {                          // r = b - (M + G) x, b_{l+1} = P^T r  (P is rank-local: no exchange)
-    gen_exchange(l);
-    for (size_t i = 0; i < M.size(); ++i) {
-      Dist* d = M[i];
-      d->top->residual(d->top->lev[l].A, gx[l].cur[i], gbl(i, l), d->rl[l].p);
-      d->top->transfer_f2c(l, d->rl[l].p, bnext(d, l));
+  // one level and everything below it, `visits` times: 1 = V, 2 = W (Handle::w_rec on rank-partitioned levels)
+  void gen_cycle(int l, int visits) {
+    if (l == k) { tail(); return; }
+    each([&](Dist& d, size_t i) { d.top->zero(gx[l].cur[i], d.next(l)); });
+    for (int v = 0; v < visits; ++v) {
+      gen_smooth(l, 0, v == 0);
+      gen_exchange(l);                                         // r = b - (M + G) x, b_{l+1} = P^T r  (P is rank-local: no exchange)
+      each([&](Dist& d, size_t i) {
+        d.top->residual(d.top->lev[l].A, gx[l].cur[i], bl(d, i, l), d.rl[l].p);
+        d.top->transfer_f2c(l, d.rl[l].p, bnext(d, l));
+      });
+      gen_cycle(l + 1, visits);
+      each([&](Dist& d, size_t i) {                            // x_l += P x_{l+1}  (x_{l+1} is wherever the steps below left it)
+        const double* xc = l + 1 < k ? (const double*)gx[l + 1].cur[i] : (const double*)d.xk_ext.p;
+        d.top->mult_add(d.top->lev[l].P, 1.0, xc, gx[l].cur[i], gx[l].cur[i]);
+      });
+      gen_smooth(l, 1, false);
     }
   }
-  void gen_prolong(int l) {                                    // x_l += P x_{l+1}
-    const int k = M[0]->k;
-    for (size_t i = 0; i < M.size(); ++i) {
-      Dist* d = M[i];
-      const double* xc = l + 1 < k ? (const double*)gx[l + 1].cur[i] : (const double*)d->xk_ext.p;
-      d->top->mult_add(d->top->lev[l].P, 1.0, xc, gx[l].cur[i], gx[l].cur[i]);
-    }
-  }
-  void gen_v(int l) {
-    const int k = M[0]->k;
-    if (l == k) { gather_level_k(); tail_and_pick(); return; }
-    gen_zero(l);
-    gen_smooth(l, 0, true);
-    gen_residual_restrict(l);
-    gen_v(l + 1);
-    gen_prolong(l);
-    gen_smooth(l, 1, false);
-  }
-  void gen_w(int l) {                                          // Handle::w_rec on rank-partitioned levels
-    const int k = M[0]->k;
-    if (l == k) { gather_level_k(); tail_and_pick(); return; }
-    gen_zero(l);
-    gen_smooth(l, 0, true);
-    gen_residual_restrict(l);
-    gen_w(l + 1);
-    gen_prolong(l);
-    gen_smooth(l, 1, false);
-    gen_smooth(l, 0, false);
-    gen_residual_restrict(l);
-    gen_w(l + 1);
-    gen_prolong(l);
-    gen_smooth(l, 1, false);
-  }
-  void generic_cycle(const std::vector<const double*>& b0) {
-    const int k = M[0]->k;
-    gb0 = b0;
+  void stepwise() {
     gx.assign(k, GenState());
     for (int l = 0; l < k; ++l)
       for (Dist* d : M) { gx[l].cur.push_back(d->xext[l].p); gx[l].oth.push_back(d->text[l].p); }
-    if (M[0]->cycle == AMGX_CYCLE_W) gen_w(0); else gen_v(0);
-    for (size_t i = 0; i < M.size(); ++i) M[i]->top->copy(x[i], gx[0].cur[i], M[i]->n(0));
+    gen_cycle(0, M[0]->cycle == AMGX_CYCLE_W ? 2 : 1);
+    each([&](Dist& d, size_t i) { d.top->copy(x[i], gx[0].cur[i], d.n(0)); });
+  }
+
+  void run() {
+    switch (M[0]->path) {
+      case DistPath::JACOBI_FOLDED: jacobi_folded(); break;
+      case DistPath::JACOBI_LITERAL: jacobi_literal(); break;
+      case DistPath::GS_BLOCK_HYBRID: hybrid_gsb(); break;
+      case DistPath::GS_STAGED: hybrid_gs(); break;
+      case DistPath::STEPWISE: stepwise(); break;
+    }
   }
 };
 
@@ -817,79 +751,51 @@ static void dist_apply(Comm& c, const double* const* b, double* const* x, int b_
   const bool host = !(flags & AMGX_DEVICE_PTR);
   for (size_t i = 0; i < M.size(); ++i)
     if ((!b[i] || !x[i]) && M[i]->n(0) > 0) throw Err("amgx_dist_apply: null vector");
+  auto body = [&]() {
+    DistCycle cy{c, M};
+    for (size_t i = 0; i < M.size(); ++i) {
+      Dist* d = M[i];
+      const int64_t nb = b_status == 0 ? d->next(0) : d->n(0);
+      if (nb == 0) {}
+      else if (host) HIPCHK(hipMemcpyAsync(d->bext[0].p, b[i], nb * sizeof(double), hipMemcpyHostToDevice, c.compute));
+      else if (b[i] != d->bext[0].p) dev_copy(d->bext[0].p, b[i], nb, c.compute);
+      cy.b0.push_back(d->bext[0].p);
+      cy.x.push_back(host ? d->x0.p : x[i]);
+    }
+    if (b_status == 0) c.accumulate(cy.items(0, 0));
+    cy.run();
+  };
   // ---- replay / capture of the whole collective cycle (see Comm::graphs) ----------------------------------------------
-  const bool want_graph = c.graph_ok && !host && !(flags & AMGX_NO_GRAPH) && c.compute != nullptr;
-  Comm::GKey key;
-  if (want_graph) {
+  if (c.graph_ok && !host && !(flags & AMGX_NO_GRAPH) && c.compute != nullptr) {
+    Comm::GKey key;
     key.status = b_status;
     for (size_t i = 0; i < M.size(); ++i) { key.p.push_back(b[i]); key.p.push_back(x[i]); }
-    auto it = c.graphs.find(key);
-    if (it != c.graphs.end()) {
-      HIPCHK(hipGraphLaunch(it->second.exec, c.compute));
-      c.n_exchanges += it->second.exchanges;
+    auto* g = c.graphs.find(key);
+    // The FIRST application of a communicator is always launched directly: RCCL sets up its point-to-point and all-gather
+    // connections lazily inside the first calls, which must not happen inside a stream capture; the capture starts with the
+    // second application, when every connection exists.
+    if (!g && c.n_direct_runs > 0) {
+      // relaxed capture: the communication stream joins the capture through the first cross-stream ordering and is joined
+      // back by the last exchange_end / accumulate, as hipStreamEndCapture requires
+      const int64_t ex0 = c.n_exchanges;
+      Comm::Graphs::Failure why;
+      c.capturing = true;
+      g = c.graphs.capture(key, c.compute, hipStreamCaptureModeRelaxed, body, why);
+      c.capturing = false;
+      const int64_t nex = c.n_exchanges - ex0;              // counted while capturing; from now on added per replay
+      c.n_exchanges = ex0;
+      if (g) g->payload = nex;
+      else {      // the capture did not work out: never try again on this communicator, run this application directly
+        c.graph_ok = false;
+        c.graph_note = "whole-cycle graph capture failed (" + why.text() + "): direct launches";
+      }
+    }
+    if (g) {
+      HIPCHK(hipGraphLaunch(g->exec, c.compute));
+      c.n_exchanges += g->payload;
       ++c.n_graph_replays;
       return;
     }
-  }
-  const int64_t ex0 = c.n_exchanges;
-  // The FIRST application of a communicator is always launched directly: RCCL sets up its point-to-point and all-gather
-  // connections lazily inside the first calls, which must not happen inside a stream capture; the capture starts with the
-  // second application, when every connection exists.
-  const bool capture_now = want_graph && c.n_direct_runs > 0;
-  if (capture_now) {
-    // the communication stream joins the capture through the first cross-stream ordering and is joined back by the last
-    // exchange_end / accumulate, as hipStreamEndCapture requires
-    c.capturing = true;
-    hipError_t e = hipStreamBeginCapture(c.compute, hipStreamCaptureModeRelaxed);
-    if (e != hipSuccess) { c.capturing = false; c.graph_ok = false; (void)hipGetLastError(); }
-  }
-  auto body = [&]() {
-  DistCycle cy{c, M, {}};
-  std::vector<const double*> b0(M.size());
-  for (size_t i = 0; i < M.size(); ++i) {
-    Dist* d = M[i];
-    if ((!b[i] || !x[i]) && d->n(0) > 0) throw Err("amgx_dist_apply: null vector");
-    const int64_t nb = b_status == 0 ? d->next(0) : d->n(0);
-    if (nb == 0) {}
-    else if (host) HIPCHK(hipMemcpyAsync(d->bext[0].p, b[i], nb * sizeof(double), hipMemcpyHostToDevice, c.compute));
-    else if (b[i] != d->bext[0].p) dev_copy(d->bext[0].p, b[i], nb, c.compute);
-    b0[i] = d->bext[0].p;
-    cy.x.push_back(host ? d->x0.p : x[i]);
-  }
-  if (b_status == 0) {
-    std::vector<Comm::Item> it;
-    for (Dist* d : M) it.push_back({&d->halo[0], d->bext[0].p});
-    c.accumulate(it);
-  }
-  if (M[0]->generic) cy.generic_cycle(b0);
-  else if (M[0]->sm_type == AMGX_SM_JACOBI) { if (M[0]->fold) cy.jacobi_folded(); else cy.jacobi_literal(); }
-  else if (M[0]->gsb) cy.hybrid_gsb(b0);
-  else cy.hybrid_gs(b0);
-  };
-  if (c.capturing) {
-    hipGraph_t g = nullptr;
-    bool ok = true;
-    std::string why;
-    try { body(); } catch (const std::exception& ex) { ok = false; why = ex.what(); }
-    const hipError_t e = hipStreamEndCapture(c.compute, &g);
-    c.capturing = false;
-    hipGraphExec_t ge = nullptr;
-    if (ok && e == hipSuccess && g && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess) {
-      (void)hipGraphDestroy(g);
-      if (c.graphs.size() >= 16) c.evict_oldest_graph();
-      const int64_t nex = c.n_exchanges - ex0;
-      c.graphs.emplace(key, Comm::GVal{ge, nex});
-      c.graph_age.push_back(key);
-      HIPCHK(hipGraphLaunch(ge, c.compute));
-      ++c.n_graph_replays;
-      return;
-    }
-    // the capture did not work out: forget it, never try again on this communicator, run this application directly
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    c.graph_ok = false;
-    c.n_exchanges = ex0;
-    c.graph_note = "whole-cycle graph capture failed (" + (why.empty() ? std::string(hipGetErrorString(e)) : why) + "): direct launches";
   }
   ++c.n_direct_runs;
   body();
@@ -1184,7 +1090,7 @@ int amgx_comm_set_stream(amgx_comm cc, void* s) {
     HIPCHK(hipStreamSynchronize(c.compute));
     HIPCHK(hipStreamSynchronize(c.comm_stream));
     c.compute = ns;
-    c.drop_graphs();
+    c.graphs.drop();
     for (amgx::Dist* d : c.members) { d->top->drop_graphs(); d->tail->drop_graphs(); d->top->stream = ns; d->tail->stream = ns; }
   });
 }
@@ -1257,33 +1163,23 @@ int amgx_dist_time_kernel(amgx_comm cc, int level, int op, int reps, double* avg
     if (level < 0 || level >= d0->k) throw Err("amgx_dist_time_kernel: not a rank-partitioned level");
     Handle& h = *d0->top;
     DevLevel& L = h.lev[level];
-    if (op == 8 && (!L.paths.jacobi_down() || !d0->fold)) throw Err("amgx_dist_time_kernel: level has no fused pre-smoothing + restriction kernel");
-    if (op == 9 && !(d0->gsb && L.paths.hybrid())) throw Err("amgx_dist_time_kernel: level has no block-hybrid Gauss-Seidel sweep");
+    if (op == 8 && (!L.paths.jacobi_down() || d0->path != DistPath::JACOBI_FOLDED)) throw Err("amgx_dist_time_kernel: level has no fused pre-smoothing + restriction kernel");
+    if (op == 9 && !(d0->path == DistPath::GS_BLOCK_HYBRID && L.paths.hybrid())) throw Err("amgx_dist_time_kernel: level has no block-hybrid Gauss-Seidel sweep");
     std::vector<const double*> bb;
     std::vector<double*> xx;
     for (Dist* d : c.members) {
-      if (d->n(0)) hipLaunchKernelGGL(fill_kernel, dim3(Handle::grid_for(d->n(0))), dim3(BLOCK), 0, c.compute, d->n(0), (uint64_t)2, d->bext[0].p);
+      if (d->n(0)) launch(fill_kernel, Handle::grid_for(d->n(0)), BLOCK, 0, c.compute, d->n(0), (uint64_t)2, d->bext[0].p);
       bb.push_back(d->bext[0].p); xx.push_back(d->x0.p);
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventCreate(&h.probe_e0));
-    HIPCHK(hipEventCreate(&h.probe_e1));
-    h.probe_kind = op;
+    Handle::ProbeScope probe(h, op);
     double tot = 0.0;
-    try {
-      dist_apply(c, bb.data(), xx.data(), 1, AMGX_DEVICE_PTR | AMGX_NO_GRAPH);        // warm-up (and RCCL's lazy connections)
-      h.probe_level = level;
-      for (int i = 0; i < reps; ++i) {
-        dist_apply(c, bb.data(), xx.data(), 1, AMGX_DEVICE_PTR | AMGX_NO_GRAPH);
-        HIPCHK(hipStreamSynchronize(c.compute));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, h.probe_e0, h.probe_e1));
-        tot += ms;
-      }
-    } catch (...) { h.probe_level = -1; (void)hipEventDestroy(h.probe_e0); (void)hipEventDestroy(h.probe_e1); h.probe_e0 = h.probe_e1 = nullptr; throw; }
-    h.probe_level = -1;
-    (void)hipEventDestroy(h.probe_e0); (void)hipEventDestroy(h.probe_e1);
-    h.probe_e0 = h.probe_e1 = nullptr;
+    dist_apply(c, bb.data(), xx.data(), 1, AMGX_DEVICE_PTR | AMGX_NO_GRAPH);        // warm-up (and RCCL's lazy connections)
+    h.probe_level = level;
+    for (int i = 0; i < reps; ++i) {
+      dist_apply(c, bb.data(), xx.data(), 1, AMGX_DEVICE_PTR | AMGX_NO_GRAPH);
+      HIPCHK(hipStreamSynchronize(c.compute));
+      tot += probe.elapsed_ms();
+    }
     *avg_ms = tot / reps;
   });
 }

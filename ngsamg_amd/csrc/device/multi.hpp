@@ -477,20 +477,16 @@ struct Multi {
   void gemm(int w, int n, int ld, const double* M, const double* x, double* y) {
     if (n <= 0) return;
     const int grid = (n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    if (w == 2) hipLaunchKernelGGL((dense_gemm_nv_kernel<2>), dim3(grid), dim3(BLOCK), 0, h.stream, n, ld, M, x, y);
-    else if (w == 4) hipLaunchKernelGGL((dense_gemm_nv_kernel<4>), dim3(grid), dim3(BLOCK), 0, h.stream, n, ld, M, x, y);
-    else throw Err("multi-vector dense product: width must be 2 or 4");
-    HIPCHK(hipGetLastError());
+    auto run = [&](auto W) { launch(dense_gemm_nv_kernel<W()>, grid, BLOCK, 0, h.stream, n, ld, M, x, y); };
+    if (!dispatch<2, 4>(w, run)) throw Err("multi-vector dense product: width must be 2 or 4");
   }
   void pack(int64_t n, int w, const double* src, int64_t rs, int64_t cs, int c0, double* dst) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(multi_pack_kernel, dim3(Handle::grid_for(n * w)), dim3(BLOCK), 0, h.stream, n, w, src, rs, cs, c0, dst);
-    HIPCHK(hipGetLastError());
+    launch(multi_pack_kernel, Handle::grid_for(n * w), BLOCK, 0, h.stream, n, w, src, rs, cs, c0, dst);
   }
   void unpack(int64_t n, int w, const double* src, double* dst, int64_t rs, int64_t cs, int c0) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(multi_unpack_kernel, dim3(Handle::grid_for(n * w)), dim3(BLOCK), 0, h.stream, n, w, src, dst, rs, cs, c0);
-    HIPCHK(hipGetLastError());
+    launch(multi_unpack_kernel, Handle::grid_for(n * w), BLOCK, 0, h.stream, n, w, src, dst, rs, cs, c0);
   }
 
   void coarse_multi(int w, const double* rhs, double* x) {
@@ -512,8 +508,7 @@ struct Multi {
       double* xl = l == 0 ? x : W.lev[l].x.p;
       const double* bl = l == 0 ? b : W.lev[l].rhs.p;
       if (V.n > 0) {
-        hipLaunchKernelGGL(multi_diag_kernel, dim3(Handle::grid_for(V.n * w)), dim3(BLOCK), 0, h.stream, V.n * w, sh, V.dinv.p, bl, xl, V.omega);
-        HIPCHK(hipGetLastError());
+        launch(multi_diag_kernel, Handle::grid_for(V.n * w), BLOCK, 0, h.stream, V.n * w, sh, V.dinv.p, bl, xl, V.omega);
       }
       spmm<EP_RES>(w, V.A, xl, W.lev[l].res.p, EpArgs{bl, nullptr, nullptr, 0.0, nullptr, 0});
       spmm<EP_MULT>(w, V.PT, W.lev[l].res.p, W.lev[l + 1].rhs.p, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0});
@@ -636,9 +631,8 @@ struct Multi {
     const int grid = Handle::grid_for(len);
     hipStream_t sm = h.stream;
     auto dot = [&](const double* a, const double* c, int slot) {
-      hipLaunchKernelGGL(kr_dot_multi_partial_kernel, dim3(nb), dim3(BLOCK), 0, sm, n, k, a, c, st.kr_partial.p);
-      hipLaunchKernelGGL(kr_dot_final_kernel, dim3(k), dim3(BLOCK), 0, sm, nb, st.kr_partial.p, sc + slot * MULTI_MAX);
-      HIPCHK(hipGetLastError());
+      launch(kr_dot_multi_partial_kernel, nb, BLOCK, 0, sm, n, k, a, c, st.kr_partial.p);
+      launch(kr_dot_final_kernel, k, BLOCK, 0, sm, nb, st.kr_partial.p, sc + slot * MULTI_MAX);
     };
     auto read = [&](int slot, double* out) {
       HIPCHK(hipMemcpyAsync(out, sc + slot * MULTI_MAX, k * sizeof(double), hipMemcpyDeviceToHost, sm));
@@ -656,7 +650,7 @@ struct Multi {
     pack(n, k, B, brs, bcs, 0, b);
     pack(n, k, X, xrs, xcs, 0, x);
     matvec(0, k, x, 0, w, 0, true);                           // d = b - A x
-    hipLaunchKernelGGL(multi_sub_kernel, dim3(grid), dim3(BLOCK), 0, sm, len, b, w, d);
+    launch(multi_sub_kernel, grid, BLOCK, 0, sm, len, b, w, d);
     precond(d, w);
     h.copy(s, w, len);
     int cur = 1;
@@ -677,11 +671,10 @@ struct Multi {
       const int old = cur;
       cur = 1 - cur;
       dot(s, w, 2);
-      hipLaunchKernelGGL(kr_cg_update_multi_kernel, dim3(grid), dim3(BLOCK), 0, sm, len, k, sc + old * MULTI_MAX, sc + 2 * MULTI_MAX, st.kr_active.p, s, w, x, d);
+      launch(kr_cg_update_multi_kernel, grid, BLOCK, 0, sm, len, k, sc + old * MULTI_MAX, sc + 2 * MULTI_MAX, st.kr_active.p, s, w, x, d);
       precond(d, w);
       dot(w, d, cur);
-      hipLaunchKernelGGL(kr_xpby_multi_kernel, dim3(grid), dim3(BLOCK), 0, sm, len, k, sc + cur * MULTI_MAX, sc + old * MULTI_MAX, st.kr_active.p, w, s);
-      HIPCHK(hipGetLastError());
+      launch(kr_xpby_multi_kernel, grid, BLOCK, 0, sm, len, k, sc + cur * MULTI_MAX, sc + old * MULTI_MAX, st.kr_active.p, w, s);
       read(cur, v);                                           // k scalars per iteration, one copy
       bool changed = false;
       for (int j = 0; j < k; ++j) {

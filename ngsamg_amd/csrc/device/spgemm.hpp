@@ -290,8 +290,7 @@ static void spg_launch(spg::SpgArgs a, int64_t n_list) {
   const int64_t grid = (n_list + GROUPS - 1) / GROUPS;
   if (grid > 0x7fffffffLL) throw Err("spgemm: too many rows for one launch");
   a.n_list = n_list;
-  hipLaunchKernelGGL((spg::spg_row_kernel<G, CAP, FILL>), dim3((unsigned)grid), dim3(spg::SPG_BLOCK), lds, 0, a);
-  HIPCHK(hipGetLastError());
+  launch(spg::spg_row_kernel<G, CAP, FILL>, (unsigned)grid, spg::SPG_BLOCK, lds, 0, a);
 }
 
 // a (block-)CSR matrix on the device, 64-bit row pointers as in amgx_matrix
@@ -331,8 +330,7 @@ static bool dev_spgemm(const SpCsr& A, const SpCsr& B, SpCsr& C) {
   const unsigned grid = (unsigned)((n + spg::SPG_BLOCK - 1) / spg::SPG_BLOCK);
   DevBuf<int64_t> bound;
   bound.alloc((size_t)n + 1);
-  hipLaunchKernelGGL(spg::spg_bound_kernel, dim3(grid), dim3(spg::SPG_BLOCK), 0, 0, n, A.rowptr.p, A.col.p, B.rowptr.p, bound.p);
-  HIPCHK(hipGetLastError());
+  launch(spg::spg_bound_kernel, grid, spg::SPG_BLOCK, 0, 0, n, A.rowptr.p, A.col.p, B.rowptr.p, bound.p);
   // row lists of the three size classes (+ the rows no class holds)
   const int64_t lim[5] = {0, 256, 2048, 8192, INT64_MAX};
   DevBuf<int32_t> rows[4];
@@ -341,8 +339,7 @@ static bool dev_spgemm(const SpCsr& A, const SpCsr& B, SpCsr& C) {
   HIPCHK(hipMemset(cnt.p, 0, 4 * sizeof(unsigned long long)));
   for (int t = 1; t < 4; ++t) {            // (class 0 runs over all rows and filters by its bound: no list)
     rows[t].alloc((size_t)n);
-    hipLaunchKernelGGL(spg::spg_list_kernel, dim3(grid), dim3(spg::SPG_BLOCK), 0, 0, n, bound.p, lim[t], lim[t + 1], rows[t].p, cnt.p + t);
-    HIPCHK(hipGetLastError());
+    launch(spg::spg_list_kernel, grid, spg::SPG_BLOCK, 0, 0, n, bound.p, lim[t], lim[t + 1], rows[t].p, cnt.p + t);
   }
   unsigned long long hc[4];
   HIPCHK(hipMemcpy(hc, cnt.p, sizeof(hc), hipMemcpyDeviceToHost));
@@ -364,8 +361,7 @@ static bool dev_spgemm(const SpCsr& A, const SpCsr& B, SpCsr& C) {
     ncnt.alloc((size_t)n + 1);
     HIPCHK(hipMemcpy(ncnt.p, C.rowptr.p, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice));
   }
-  hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(1024), 0, 0, n, C.rowptr.p);
-  HIPCHK(hipGetLastError());
+  launch(db_scan_kernel, 1, 1024, 0, 0, n, C.rowptr.p);
   int64_t nnz = 0;
   HIPCHK(hipMemcpy(&nnz, C.rowptr.p + n, sizeof(int64_t), hipMemcpyDeviceToHost));
   if (nnz >= I32_MAX) return false;
@@ -388,8 +384,7 @@ static bool dev_spgemm(const SpCsr& A, const SpCsr& B, SpCsr& C) {
     int64_t lo = 0;
     for (const Tier& tr : tiers) {
       HIPCHK(hipMemset(cnt.p, 0, sizeof(unsigned long long)));
-      hipLaunchKernelGGL(spg::spg_list_kernel, dim3(grid), dim3(spg::SPG_BLOCK), 0, 0, n, ncnt.p, lo, tr.hi, rows[1].p, cnt.p);
-      HIPCHK(hipGetLastError());
+      launch(spg::spg_list_kernel, grid, spg::SPG_BLOCK, 0, 0, n, ncnt.p, lo, tr.hi, rows[1].p, cnt.p);
       HIPCHK(hipMemcpy(hc, cnt.p, sizeof(unsigned long long), hipMemcpyDeviceToHost));
       lo = tr.hi;
       if (!hc[0]) continue;
@@ -401,15 +396,13 @@ static bool dev_spgemm(const SpCsr& A, const SpCsr& B, SpCsr& C) {
       if (tr.waves == 0) {
         const size_t lds = (size_t)tr.cap * 12 + 16;
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&spg::spg_block_row_gmem_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(spg::spg_block_row_gmem_kernel, dim3((unsigned)g.a.n_list), dim3(64), lds, 0, g);
-        HIPCHK(hipGetLastError());
+        launch(spg::spg_block_row_gmem_kernel, (unsigned)g.a.n_list, 64, lds, 0, g);
         continue;
       }
       const size_t lds = spg::spg_block_lds(tr.cap, cbs) * tr.waves;
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&spg::spg_block_row_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       const int64_t wg = (g.a.n_list + tr.waves - 1) / tr.waves;
-      hipLaunchKernelGGL(spg::spg_block_row_kernel, dim3((unsigned)wg), dim3(64 * tr.waves), lds, 0, g);
-      HIPCHK(hipGetLastError());
+      launch(spg::spg_block_row_kernel, (unsigned)wg, 64 * tr.waves, lds, 0, g);
     }
   }
   HIPCHK(hipDeviceSynchronize());

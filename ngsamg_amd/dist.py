@@ -872,7 +872,7 @@ class DistributedAMG:
         # (AMGX_NO_FOLD=1, the switch that makes the single-GPU handle run the literal kernel sequence, selects the literal
         # stages here too: the decision is taken from the environment on every rank alike, before anything is built)
         # ngs_amg_sm_steps / ngs_amg_sm_symm (ProxySmoother, base_smoother.hpp:169-229) and ngs_amg_mg_cycle = "W" on rank-partitioned
-        # levels: the native driver's step-by-step cycle (csrc/device/dist.hpp, DistCycle::generic_cycle); the folded V(1,1) form
+        # levels: the native driver's step-by-step cycle (csrc/device/dist.hpp, DistCycle::stepwise); the folded V(1,1) form
         # and the stage-by-stage Python test backend cover sm_steps = 1, sm_symm = False, V only
         self.sm_steps, self.sm_symm, self.mg_cycle = int(sm_steps), bool(sm_symm), str(mg_cycle)
         if self.mg_cycle not in ("V", "W"):

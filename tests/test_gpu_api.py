@@ -309,3 +309,32 @@ def test_2d_coefficient_jumps(jump, geom):
     c = ngs_amg.Preconditioner(_mat(p), "ngs_amg.h1_scal", freedofs=p.free, ngs_amg_max_coarse_size=5, ngs_amg_dim=2,
                                ngs_amg_sm_type="gs", ngs_amg_spw=False, ngs_amg_robust_soc=True)
     Solve(_mat(p), p.load, c, ms=25, tol=1e-6)
+
+
+def test_graph_cache_evicts_the_oldest_capture():
+    """a handle keeps at most 16 captured cycles, keyed by the (b, x) addresses, and drops the OLDEST one: 18 distinct device
+    pairs applied twice each (capture, replay), then the first pair again -- its capture is gone by then, it is captured anew and
+    gives its first result bit for bit; every result equals the one of direct launches (use_graph=False) bit for bit.  (The
+    number of graphs a handle holds is not part of the C ABI; the communicator's is: tests/test_gpu_dist.py.)"""
+    import torch
+    from ngsamg_amd.hierarchy import Hierarchy
+    from ngsamg_amd.device import DeviceAMGMatrix
+    p = fem.poisson_fast((10, 10, 10))
+    H = Hierarchy(_mat(p), p.free, p.coords, dim=3, energy=0, max_coarse_size=10)
+    dg = DeviceAMGMatrix(H, sm_type="jacobi", device=0)
+    dd = DeviceAMGMatrix(H, sm_type="jacobi", device=0, use_graph=False)
+    rng = np.random.default_rng(5)
+    nan = lambda: torch.full((p.n,), float("nan"), dtype=torch.float64, device="cuda")
+    pairs = [(torch.from_numpy(rng.standard_normal(p.n) * p.free).cuda(), nan(), nan()) for _ in range(18)]
+    for b, xg, xd in pairs:
+        for rep in range(2):
+            dg.Mult(b, xg)
+            dd.Mult(b, xd)
+            torch.cuda.synchronize()
+            assert torch.equal(xg, xd)
+    b, xg, xd = pairs[0]
+    first = xg.clone()
+    xg.fill_(float("nan"))
+    dg.Mult(b, xg)
+    torch.cuda.synchronize()
+    assert torch.equal(xg, first) and torch.equal(xg, xd)

@@ -915,3 +915,89 @@ def test_loopback_device_local_window_image_on_rank_partitioned_levels(R, box, d
     ref = Oracle(amg.global_levels(), sm_type="jacobi").apply(np.concatenate(bh))
     got = np.concatenate([x.cpu().numpy() for x in xs])
     assert np.linalg.norm(got - ref) <= 1e-12 * np.linalg.norm(ref)
+
+
+# ---- the collective cycle driver: graph cache, the step-by-step driver on the staged sweeps, the literal Jacobi driver ----
+# (all at R = 2, box (10, 10, 10), dist_min_rows = 40, max_coarse_size = 10)
+
+def _small_two_rank_amg(**kw):
+    from ngsamg_amd import dist as D
+    states = [D.assemble_poisson_owned(r, D.proc_grid(2, 3), (10, 10, 10)) for r in range(2)]
+    return D.DistributedAMG(D.LoopbackComm(2), states, dim=3, dist_min_rows=40, device=0, max_coarse_size=10, **kw), states
+
+
+def test_whole_cycle_graph_cache_evicts_the_oldest_capture(monkeypatch):
+    """the communicator keeps at most 16 captured cycles and drops the OLDEST one: 18 distinct (b, x) pairs applied twice each
+    (the first application of a communicator is direct, so the captures start with the second) leave 16 graphs; the first pair,
+    whose capture is gone by then, is captured again and gives its first result bit for bit; every result equals the one of
+    direct launches (AMGX_DIST_GRAPH=0) bit for bit, and so do the exchange counters"""
+    import torch
+    monkeypatch.setenv("AMGX_DIST_GRAPH", "1")
+    ag, states = _small_two_rank_amg()
+    monkeypatch.setenv("AMGX_DIST_GRAPH", "0")
+    ad, _ = _small_two_rank_amg()
+    rng = np.random.default_rng(5)
+    nan = lambda: [torch.full((s.n,), float("nan"), dtype=torch.float64, device="cuda") for s in states]
+    pairs = [([torch.from_numpy(rng.standard_normal(s.n) * s.free).cuda() for s in states], nan(), nan()) for _ in range(18)]
+    for bs, xg, xd in pairs:
+        for rep in range(2):
+            ag.Mult(bs, xg)
+            ad.Mult(bs, xd)
+            torch.cuda.synchronize()
+            assert all(torch.equal(a, b_) for a, b_ in zip(xg, xd))
+    gi = ag._dev.graph_info()
+    assert gi["enabled"] and gi["graphs"] == 16, gi
+    bs, xg, _ = pairs[0]
+    first = [t.clone() for t in xg]
+    for t in xg:
+        t.fill_(float("nan"))
+    ag.Mult(bs, xg)
+    ad.Mult(bs, pairs[0][2])
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b_) for a, b_ in zip(xg, first))
+    gi = ag._dev.graph_info()
+    assert gi["enabled"] and gi["graphs"] == 16, gi
+    assert not ad._dev.graph_info()["enabled"]
+    assert ag._dev.n_exchanges() == ad._dev.n_exchanges()
+
+
+@pytest.mark.parametrize("sm", ["gs", "bgs"])
+@pytest.mark.parametrize("steps,cycle", [(2, "V"), (1, "W")])
+def test_loopback_device_steps_w_staged_gs(sm, steps, cycle):
+    """the step-by-step driver on the multicolour ("gs") and aggregate-block ("bgs") sweeps: every step is one exchange of x and
+    one in-place hybrid sweep, against the oracle's serial hybrid sweep (blocks = ranks) with the same sm_steps / cycle"""
+    import torch
+    from oracle.pyoracle import Oracle
+    from tests.dist_oracle import oracle_bgs, oracle_sm_types
+    amg, states = _small_two_rank_amg(sm_type=sm, sm_steps=steps, mg_cycle=cycle)
+    assert amg.k >= 1
+    rng = np.random.default_rng(0)
+    bh = [rng.standard_normal(s.n) * s.free for s in states]
+    bs = [torch.from_numpy(b).cuda() for b in bh]
+    xs = [torch.full((s.n,), float("nan"), dtype=torch.float64, device="cuda") for s in states]
+    for rep in range(2):
+        amg.Mult(bs, xs)
+    torch.cuda.synchronize()
+    glv = amg.global_levels()
+    ref = Oracle(glv, sm_type=oracle_sm_types(amg), bgs=oracle_bgs(amg, glv), sm_steps=steps, cycle=cycle).apply(np.concatenate(bh))
+    got = np.concatenate([x.cpu().numpy() for x in xs])
+    assert np.linalg.norm(got - ref) <= 1e-10 * np.linalg.norm(ref)
+
+
+def test_overlap_split_equals_unsplit_literal_jacobi(monkeypatch):
+    """test_overlap_split_equals_unsplit for the literal Jacobi driver (fold=False): both of its overlapped stages -- the
+    pre-smoothing and the post-smoothing step behind the exchange of x + P x_c -- give the unsplit result bit for bit"""
+    import torch
+    res = []
+    for no_overlap in (False, True):
+        if no_overlap:
+            monkeypatch.setenv("AMGX_DIST_NO_OVERLAP", "1")
+        amg, states = _small_two_rank_amg(fold=False)
+        assert amg.k >= 1 and not amg.fold and all(s.n_interior > 0 for s in states)
+        rng = np.random.default_rng(2)
+        bs = [torch.from_numpy(rng.standard_normal(s.n) * s.free).cuda() for s in states]
+        xs = [torch.full((s.n,), float("nan"), dtype=torch.float64, device="cuda") for s in states]
+        amg.Mult(bs, xs)
+        torch.cuda.synchronize()
+        res.append(torch.cat(xs))
+    assert torch.equal(res[0], res[1])

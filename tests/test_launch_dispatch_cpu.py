@@ -68,3 +68,14 @@ def test_dispatch_host_program(tmp_path):
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
     assert run.stdout.strip().endswith("bad=0")
+
+
+def test_every_launch_goes_through_launch():
+    """the launch macro occurs once in the native sources, inside launch() (launch.hpp), so that every kernel launch
+    is followed by its own error check"""
+    hits = []
+    for base, _, files in os.walk(os.path.join(ROOT, "ngsamg_amd", "csrc")):
+        for f in sorted(files):
+            with open(os.path.join(base, f), errors="replace") as fh:
+                hits += [(f, i + 1) for i, ln in enumerate(fh) if "hipLaunchKernelGGL" in ln]
+    assert len(hits) == 1 and hits[0][0] == "launch.hpp", hits
