@@ -235,7 +235,7 @@ int amgx_matrix_info(amgx_handle h, int level, int which, int32_t* fmt, int64_t*
  * indices and pointers of A; 0 when the level has no single-precision image) */
 int amgx_matrix_stream_bytes(amgx_handle h, int level, int which, int64_t* bytes);
 
-/* read-only report of the paths amgx_create chose for one level (changes nothing).  Fills out[0 .. min(n_out, 19)):
+/* read-only report of the paths amgx_create chose for one level (changes nothing).  Fills out[0 .. min(n_out, AMGX_LEVEL_PATHS_N)):
  *    0 fused Jacobi down kernel: 0 none, 1 sliced-ELL, 2 sliced-ELL with row windows, 3 local-window sliced-ELL, 4 diagonal image;
  *      5: the fused residual + restriction kernel of a Chebyshev level (sliced-ELL image of A; 1 .. 3 then describe it)
  *    1 its workgroup size (rows per chunk x lanes)      2 its lanes per row (0: none)
@@ -267,8 +267,13 @@ int amgx_matrix_stream_bytes(amgx_handle h, int level, int which, int64_t* bytes
  *      residual and restriction, also on a level whose down pass is not the plain one-step sweep), 1 sliced-ELL, 2 sliced-ELL with
  *      row windows, 3 local-window sliced-ELL (the image of the couplings the sweep did not use).  (The rank-partitioned driver
  *      calls the same kernels on its own condition; this entry describes the single-rank cycle.)
+ *   34, 35, 36 form 7: workgroup size TH and lanes per scalar row G of the bgs_block_kernel<BS, TH, G> the sweep launches, and the
+ *      scalar dofs of the largest block they were chosen from
+ *   37, 38, 39 the kernel of a product with A, P, P^T held in the block CSR format (0: another format, 1 x 1 blocks or no such
+ *      matrix): 100 + W = bcsr_rowlane_kernel with W lane groups per block row, 200 + G = bcsrvec_spmv_kernel with G lanes per
+ *      block row
  * Returns 0, or non-zero for a bad level or n_out < 1. */
-#define AMGX_LEVEL_PATHS_N 34
+#define AMGX_LEVEL_PATHS_N 40
 int amgx_level_paths(amgx_handle h, int level, int64_t* out, int n_out);
 
 /* measurement hook for bench.py: launches one hot-path kernel `reps` times on the handle's stream,

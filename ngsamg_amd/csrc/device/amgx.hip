@@ -256,6 +256,30 @@ struct DevBGS {                         // block Gauss-Seidel over aggregate blo
   DevBuf<int32_t> rowptr, col;          // CSR of A (the level matrix itself may live in a SELL format)
   DevBuf<double> val;
 };
+// the instantiation bgs_block_kernel<BS, TH, G> a level's sweep launches, from the blocks per row `avg` of A and the scalar dofs
+// max_m of the largest block; bgs_sweep launches it and amgx_level_paths reports it.  G = lanes per scalar row ~ row length / 6;
+// TH: one pass over the block's rows where possible (max_m * G <= TH).  The long-row forms (G = 8, 16) are built for 1024 lanes
+// only: G = 8 means max_m > 64, i.e. max_m * 8 > 512, so a <512, 8> kernel could never be picked, and G = 16 always took <1024, 16>.
+// TH >= max_m holds for every block the set-up admits (max_m <= 256 / G, <= 512 / G or <= BGS_MAX_M = 1024 = the largest TH).
+struct BgsShape { int TH, G; };
+static BgsShape bgs_block_shape(double avg, int max_m) {
+  const int G = avg > 30.0 ? (max_m * 16 <= 1024 ? 16 : 8) : 4;
+  const int TH = G != 4 ? 1024 : (max_m * G <= 256 ? 256 : (max_m * G <= 512 ? 512 : 1024));
+  return BgsShape{TH, G};
+}
+// the kernel spmv_ep launches on a matrix in the block CSR format (blocks other than 1 x 1, no BSELL / rigid-body image);
+// amgx_level_paths reports the same value.  rowlane: bcsr_rowlane_kernel with `width` = W lane groups per block row, chosen from
+// the average row length; otherwise bcsrvec_spmv_kernel with `width` = G lanes per block row (DevMatrix::lanes within 2 .. 16).
+// Short rectangular rows, i.e. prolongations with <= 4 blocks per row, stay with the lane-per-block kernel (measured), and so
+// does every block with a unit dimension.  square_ep: an epilogue that is built for square blocks only (EP_JAC, EP_CHEB).
+struct BcsrKernel { bool rowlane; int width; };
+static BcsrKernel bcsr_kernel(const DevMatrix& M, bool square_ep) {
+  if (M.br >= 2 && M.bc >= 2 && (!square_ep || M.br == M.bc) && (M.br == M.bc || M.nnz >= 6 * M.n_rows)) {
+    const double avg = M.n_rows ? (double)M.nnz / (double)M.n_rows : 0.0;
+    return BcsrKernel{true, avg >= 48.0 ? 4 : (avg >= 20.0 ? 2 : 1)};
+  }
+  return BcsrKernel{false, std::min(M.lanes, 16) < 2 ? 2 : std::min(M.lanes, 16)};
+}
 
 struct DevRestrict {                    // column-blocked P^T (see restrict_chunk_kernel)
   int n_chunks = 0;
@@ -1417,11 +1441,8 @@ struct Handle {
       if (!dispatch<6, 3>(M.br, run)) run(Int<2>{});                 // any other block size: the 2 x 2 kernel
     } else if (sp.part == PART_INT) {
       return;                                   // the CSR block formats are not split: everything runs in the boundary part
-    } else if (M.br >= 2 && M.bc >= 2 && ((EP != EP_JAC && EP != EP_CHEB) || M.br == M.bc) && (M.br == M.bc || M.nnz >= 6 * M.n_rows)) {
-      // (short rectangular rows, i.e. prolongations with <= 4 blocks per row, stay with the lane-per-block kernel: measured)
-      // row-per-lane block CSR kernel; W lane groups per block row chosen from the average row length
-      const double avg = M.n_rows ? (double)M.nnz / (double)M.n_rows : 0.0;
-      const int W = avg >= 48.0 ? 4 : (avg >= 20.0 ? 2 : 1);
+    } else if (const BcsrKernel bk = bcsr_kernel(M, EP == EP_JAC || EP == EP_CHEB); bk.rowlane) {
+      const int W = bk.width;
       const int rpw = WAVE / (M.br * W);
       const int64_t waves = (M.n_rows + rpw - 1) / rpw;
       const int grid = (int)std::max<int64_t>(1, (waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
@@ -1438,7 +1459,7 @@ struct Handle {
         if (!dispatch<22, 33, 66, 36, 63, 23, 32>(key, run)) throw Err("unsupported block shape " + std::to_string(M.br) + "x" + std::to_string(M.bc));
       }
     } else {
-      const int G = std::min(M.lanes, 16) < 2 ? 2 : std::min(M.lanes, 16);
+      const int G = bk.width;
       const int grid = grid_for(M.n_rows * G);
       auto run = [&](auto KEY) {                                     // key = 10 * br + bc
         constexpr int BR = KEY() / 10, BC = KEY() % 10;
@@ -1691,10 +1712,9 @@ struct Handle {
       const int c = dir == 0 ? q : cend - 1 - (q - cbeg);
       const int b0 = g.color_ptr[c], b1 = g.color_ptr[c + 1];
       if (b1 == b0) continue;
-      // (TH, G): one pass over the block's rows where possible (M * G <= TH), G lanes per row ~ row length / 6
       const double avg = L.A.n_rows ? (double)L.A.nnz / (double)L.A.n_rows : 0.0;
-      const int G = avg > 30.0 ? (g.max_m * 16 <= 1024 ? 16 : 8) : 4;
-      const int TH = g.max_m * G <= 256 ? 256 : (g.max_m * G <= 512 ? 512 : 1024);
+      const BgsShape shape = bgs_block_shape(avg, g.max_m);
+      const int G = shape.G, TH = shape.TH;
       auto run = [&](auto BS) {
         auto block = [&](auto TT, auto GG) {
           launch(bgs_block_kernel<BS(), TT(), GG()>, b1 - b0, TT(), 0, stream, b0, g.blocklist.p, g.block_ptr.p, g.block_rows.p, g.rowptr.p, g.col.p, g.val.p,
@@ -1703,8 +1723,7 @@ struct Handle {
         if (G == 4 && TH == 256) block(Int<256>{}, Int<4>{});
         else if (G == 4 && TH == 512) block(Int<512>{}, Int<4>{});
         else if (G == 4) block(Int<1024>{}, Int<4>{});
-        else if (G == 8 && TH <= 512) block(Int<512>{}, Int<8>{});
-        else if (G == 8) block(Int<1024>{}, Int<8>{});
+        else if (G == 8) block(Int<1024>{}, Int<8>{});          // (no <512, 8>: unreachable, see bgs_block_shape)
         else block(Int<1024>{}, Int<16>{});
       };
       if (!dispatch<1, 2, 3, 6>(L.bs, run)) throw Err("unsupported block size for block Gauss-Seidel");
@@ -3669,7 +3688,12 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
     const amgx::DevBGSB& bgsb = L.bgsb;
     v[19] = L.paths.sweep;
     switch (L.paths.sweep) {
-      case amgx::SWEEP_BGS: v[23] = L.bgs.n_colors; break;
+      case amgx::SWEEP_BGS: {
+        v[23] = L.bgs.n_colors;
+        const amgx::BgsShape sh = amgx::bgs_block_shape(L.A.n_rows ? (double)L.A.nnz / (double)L.A.n_rows : 0.0, L.bgs.max_m);
+        v[34] = sh.TH; v[35] = sh.G; v[36] = L.bgs.max_m;
+        break;
+      }
       case amgx::SWEEP_BGSB:
       case amgx::SWEEP_BGSB_BC:
         v[21] = amgx::BLOCK; v[22] = bgsb.BB; v[23] = bgsb.n_colors; v[24] = bgsb.n_bcolors; v[25] = bgsb.has_split;
@@ -3697,6 +3721,12 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
       }
       default: break;
     }
+    auto bcsr = [](const amgx::DevMatrix& M) -> int64_t {
+      if (M.empty() || M.fmt != amgx::FMT_CSRVEC || (M.br == 1 && M.bc == 1)) return 0;
+      const amgx::BcsrKernel bk = amgx::bcsr_kernel(M, false);
+      return (bk.rowlane ? 100 : 200) + bk.width;
+    };
+    v[37] = bcsr(L.A); v[38] = bcsr(L.P); v[39] = bcsr(L.PT);
     for (int k = 0; k < std::min(n_out, AMGX_LEVEL_PATHS_N); ++k) out[k] = v[k];
   });
 }

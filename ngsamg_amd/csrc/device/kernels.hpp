@@ -2065,7 +2065,7 @@ __global__ __launch_bounds__(TH) void bgs_block_kernel(int list_begin, const int
   // A block is a chain of dependent round trips (block table -> rows -> row pointers -> entries -> gathers -> inverse ->
   // x); everything that does not depend on the row products is requested up front: this thread's slice of the inverse
   // and the old x value of its output row.
-  const bool fits = M <= TH;
+  const bool fits = M <= TH;                                // (always, with the host's choice of TH: amgx.hip, bgs_block_shape)
   const int S = fits ? TH / M : 1;                          // slices of the column range of the inverse
   const int di = fits ? threadIdx.x % M : 0, dsl = fits ? threadIdx.x / M : S;
   const bool dreg_ok = fits && (M + S - 1) / S <= DMAX;

@@ -587,7 +587,8 @@ class DeviceAMGMatrix:
     _PATH_KEYS = ("kernel", "fused_block", "lanes", "ept", "compact", "max_slots", "max_entries", "dia_k", "xcd_A", "xcd_Apre",
                   "xcd_Q", "xcd_dia", "A_slices16", "A_slices", "Apre_slices16", "Apre_slices", "lw_no_window", "folded", "chunks",
                   "gs_form", "gs_lanes", "gs_threads", "gs_block", "gs_colors", "gs_block_colors", "gs_split", "gs_lowin_maxw",
-                  "gs_full_maxw", "gs_narrow", "gs_mid", "gs_lw", "gs_w_mask", "gs_lw_no_window", "gs_down")
+                  "gs_full_maxw", "gs_narrow", "gs_mid", "gs_lw", "gs_w_mask", "gs_lw_no_window", "gs_down",
+                  "bgs_threads", "bgs_lanes", "bgs_max_m", "bcsr_A", "bcsr_P", "bcsr_PT")
     _GS_FORMS = {0: None, 1: "mc", 2: "mc-block-rowlist", 3: "mc-block-bsell", 4: "hybrid", 5: "hybrid-block", 6: "block-coloured",
                  7: "bgs"}
 
@@ -601,13 +602,17 @@ class DeviceAMGMatrix:
         widest slices of the block-hybrid images, the block-hybrid kernel choices (narrow sweep from zero, mid-width and
         local-window general sweep, blocks of the local-window image without a window), the row-list kernel's lanes per block
         row (bitmask of W) and the form of the block-hybrid down pass's fused residual + restriction ("gs_down": None, "sell",
-        "sell-win" or "sell-lw")"""
+        "sell-win" or "sell-lw"); the aggregate block Gauss-Seidel kernel ("bgs_threads", "bgs_lanes": TH and G of
+        bgs_block_kernel<BS, TH, G>, "bgs_max_m": scalar dofs of the largest block) and the kernel of a product with A, P, P^T in
+        the block CSR format ("bcsr_A", "bcsr_P", "bcsr_PT": None, ("rowlane", W) or ("csrvec", G))"""
         out = np.zeros(len(self._PATH_KEYS), dtype=np.int64)
         self._ck(self._lib.amgx_level_paths(self._h, int(level), out.ctypes.data_as(_lib.c_i64p), out.size))
         d = dict(zip(self._PATH_KEYS, (int(v) for v in out)))
         d["kernel"] = {0: None, 1: "sell", 2: "sell-win", 3: "sell-lw", 4: "dia", 5: "cheby-res"}[d["kernel"]]
         d["gs_form"] = self._GS_FORMS[d["gs_form"]]
         d["gs_down"] = {0: None, 1: "sell", 2: "sell-win", 3: "sell-lw"}[d["gs_down"]]
+        for k in ("bcsr_A", "bcsr_P", "bcsr_PT"):
+            d[k] = None if d[k] == 0 else (("rowlane", "csrvec")[d[k] // 100 - 1], d[k] % 100)
         return d
 
     _SM_NAMES = {_lib.AMGX_SM_JACOBI: "jacobi", _lib.AMGX_SM_GS: "gs", _lib.AMGX_SM_BGS: "bgs", _lib.AMGX_SM_CHEBY: "cheby"}

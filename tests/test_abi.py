@@ -50,6 +50,26 @@ def test_struct_sizes_match_headers(tmp_path):
     assert sizes == [C.sizeof(m) for m in mirrors]
 
 
+def test_level_paths_entries_match_the_header():
+    """amgx_level_paths: the header's AMGX_LEVEL_PATHS_N (through the C compiler), the number of entries its comment documents and
+    the keys of DeviceAMGMatrix.level_paths agree; the read-only entries of the block Gauss-Seidel and block CSR kernel choices
+    sit at the end"""
+    import subprocess
+    import tempfile
+    from ngsamg_amd.device import DeviceAMGMatrix
+    keys = DeviceAMGMatrix._PATH_KEYS
+    with tempfile.TemporaryDirectory() as d:
+        src, exe = os.path.join(d, "n.c"), os.path.join(d, "n")
+        open(src, "w").write('#include <stdio.h>\n#include "amgx.h"\nint main(void){printf("%d\\n", AMGX_LEVEL_PATHS_N);return 0;}\n')
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, src])
+        n = int(subprocess.check_output([exe]))
+    assert n == len(keys) == len(set(keys)) == 40
+    assert keys[34:] == ("bgs_threads", "bgs_lanes", "bgs_max_m", "bcsr_A", "bcsr_P", "bcsr_PT")
+    txt = open(os.path.join(ROOT, "include", "amgx.h")).read()
+    doc = txt[txt.index("read-only report of the paths"):txt.index("#define AMGX_LEVEL_PATHS_N")]
+    assert "34, 35, 36" in doc and "37, 38, 39" in doc and "bgs_block_kernel<BS, TH, G>" in doc and "bcsr_rowlane_kernel" in doc
+
+
 def test_apply_path_fails_loudly_without_gpu():
     """No CPU fallback: creating the device hierarchy without a GPU must raise, not degrade."""
     import torch

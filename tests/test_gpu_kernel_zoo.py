@@ -1,5 +1,5 @@
 """Every device format / kernel variant on synthetic matrices, through the C ABI, against scipy:
-SELL-G for G = 1..16 (with and without 16-bit column deltas), the CSR-vector fallback for irregular rows, block CSR
+SELL-G for G = 1..16 (lanes asserted; slices without 16-bit column deltas: test_gpu_spmv_lanes.py), the CSR-vector fallback for irregular rows, block CSR
 3x3 / 2x2, the row-per-lane 6x6 kernel for W = 1, 2, 4 and rectangular transfer blocks (3x6, 6x3, 1x3, 6x6)."""
 import numpy as np
 import pytest
@@ -54,9 +54,15 @@ def _rel(a, b):
     return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
 
 
+# lanes per row of test_scalar_formats by `avg`.  Sliced ELL (rows of avg - 1 .. avg + 1 entries): the rule doubles G while avg > 3 G,
+# then halves it until the padding of the pairwise layout -- 2 G ceil(ceil(longest / 2) / G) per row -- stays below 1.35, so 9 ends at 2,
+# 20 at 4, 45 at 8.  CSR-vector (0): the band holds 101 of the 120 entries asked for, 15.2 per row on average, one pass of 16 lanes.
+SCALAR_LANES = {3: 1, 9: 2, 20: 4, 45: 8, 90: 16, 12: 4, 0: 16}
+
+
 @pytest.mark.parametrize("n,avg,spread,expect_fmt", [
     (5000, 3, 40, "sell"), (5000, 9, 60, "sell"), (3000, 20, 100, "sell"), (2000, 45, 200, "sell"), (1500, 90, 400, "sell"),
-    (4000, 12, None, "sell"),            # random columns: 16-bit deltas impossible -> 32-bit slices
+    (4000, 12, None, "sell"),            # random columns
     (3000, 0, 50, "csrvec"),             # strongly irregular row lengths -> padding too high -> CSR-vector
 ])
 def test_scalar_formats(n, avg, spread, expect_fmt):
@@ -68,7 +74,7 @@ def test_scalar_formats(n, avg, spread, expect_fmt):
     A = _rand_bcsr(rng, n, n, 1, 1, rl, spread)
     dev = _dev([_level(A)])
     info = dev.matrix_info(0, "A")
-    assert info["fmt"] == expect_fmt, info
+    assert info["fmt"] == expect_fmt and info["lanes"] == SCALAR_LANES[avg], info
     S = A.to_scipy()
     for k in range(2):
         x = rng.standard_normal(n)
