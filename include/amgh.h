@@ -185,6 +185,22 @@ int amgh_matmul(const amgh_matrix* A, const amgh_matrix* B, int64_t* rowptr_out,
 int amgh_dia_detect(const amgh_matrix* A, int32_t max_diags, double max_fill, int32_t* offsets_out, int32_t* K_out);
 int amgh_dia_image(const amgh_matrix* A, int32_t K, const int32_t* offsets, double* vals_out);
 
+/* Lexicographic grids and box chunks of the diagonal image (host/dia.hpp; the device library runs the same code at amgx_create).
+ * amgh_dia_grid: the K upper offsets are those of an nx x ny x nz grid in lexicographic order when offsets[0] = 1, sy = offsets[1],
+ * sz = the smallest offset above sy + 1 (none: 2D, nz = 1), every offset is dx + dy sy + dz sz with dx, dy, dz in {0, 1} and
+ * n_rows divides accordingly.  shape_out[3] = (nx, ny, nz), (0, 0, 0) when refused; dxyz_out[3 K] = (dx, dy, dz) per offset.
+ * amgh_dia_boxes: boxes of nx x yc x zc rows (whole grid lines, clipped at the edge; yc = zc = 0: 2 x 4 in 3D, 8 x 1 in 2D;
+ * halved until a box has at most 2048 rows), numbered y fastest, then z.  counts_out[4] = (boxes, runs, yc, zc) -- all 0 when
+ * the grid takes no boxes --; with the arrays given: run_ptr_out[boxes + 1], and first_out / len_out[runs], the lines of every box
+ * as runs of consecutive rows in the order of the local index.
+ * amgh_dia_box_neighbours: for every row `local` of box `box`, the local index of row + o_k (up != 0) or row - o_k (up = 0)
+ * when that row belongs to the same box, else -1; local_out holds the box's rows. */
+int amgh_dia_grid(int64_t n_rows, int32_t K, const int32_t* offsets, int64_t* shape_out, int32_t* dxyz_out);
+int amgh_dia_boxes(int64_t n_rows, int32_t K, const int32_t* offsets, int32_t yc, int32_t zc, int64_t* counts_out, int64_t* run_ptr_out,
+                   int64_t* first_out, int32_t* len_out);
+int amgh_dia_box_neighbours(int64_t n_rows, int32_t K, const int32_t* offsets, int32_t yc, int32_t zc, int64_t box, int32_t k, int32_t up,
+                            int32_t* local_out);
+
 /* Galerkin product on an accelerator: when a pair is installed, amgh_setup hands the products (P^T A) P of levels
  * with at least `min_rows` fine (block) rows to `run` (which returns 0 = done with *n_rows / *nnz set, 2 = "not for me": the host
  * product runs, anything else = error) and reads the arrays back with `fetch` (which also releases the result).  The device

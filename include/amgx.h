@@ -239,7 +239,9 @@ int amgx_matrix_stream_bytes(amgx_handle h, int level, int which, int64_t* bytes
  *    0 fused Jacobi down kernel: 0 none, 1 sliced-ELL, 2 sliced-ELL with row windows, 3 local-window sliced-ELL, 4 diagonal image;
  *      5: the fused residual + restriction kernel of a Chebyshev level (sliced-ELL image of A; 1 .. 3 then describe it)
  *    1 its workgroup size (rows per chunk x lanes)      2 its lanes per row (0: none)
- *    3 entries of P per thread of its chunk-local restriction (0: none)     4 compact chunks (1: chunks of listed slices)
+ *    3 entries of P per thread of its chunk-local restriction (0: none)
+ *    4 chunk form: 0 consecutive rows, 1 compact chunks (chunks of listed slices), 2 box chunks of the diagonal image (a chunk =
+ *      a box of whole grid lines, dia_box_pre_restrict_kernel; entry 0 stays 4, entries 1, 5, 6 and 18 describe the boxes)
  *    5 most slots (distinct coarse columns) in one chunk                    6 most entries of P in one chunk
  *    7 upper diagonals K of the diagonal image (0: none)
  *    8 .. 11 remapped workgroup placement (1) of A, A', Q and of the diagonal image

@@ -102,6 +102,9 @@ def host():
                                        c_f64p, c_i64p, c_i32p, c_f64p, c_f64p]
     lib.amgh_dia_detect.argtypes = [C.POINTER(amgh_matrix), C.c_int32, C.c_double, c_i32p, c_i32p]
     lib.amgh_dia_image.argtypes = [C.POINTER(amgh_matrix), C.c_int32, c_i32p, c_f64p]
+    lib.amgh_dia_grid.argtypes = [C.c_int64, C.c_int32, c_i32p, c_i64p, c_i32p]
+    lib.amgh_dia_boxes.argtypes = [C.c_int64, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_i64p, c_i64p, c_i64p, c_i32p]
+    lib.amgh_dia_box_neighbours.argtypes = [C.c_int64, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, c_i32p]
     _host = lib
     return lib
 
@@ -263,6 +266,7 @@ AMGH_SYMBOLS = [
     "amgh_transpose_fill", "amgh_matmul", "amgh_kuhn_pattern", "amgh_kuhn_assemble", "amgh_bgs_dinv", "amgh_bgs_coloring",
     "amgh_coloring_blocked", "amgh_hybrid_dinv", "amgh_hybrid_dinv_ext", "amgh_hybrid_dinv_block", "amgh_compact_blocks", "amgh_coloring_blockids", "amgh_hybrid_dinv_block_ids",
     "amgh_set_galerkin_hook", "amgh_robust_pair_soc", "amgh_dia_detect", "amgh_dia_image",
+    "amgh_dia_grid", "amgh_dia_boxes", "amgh_dia_box_neighbours",
 ]
 
 

@@ -293,6 +293,11 @@ struct DevRestrict {                    // column-blocked P^T (see restrict_chun
   // compact chunks (cluster_slices): chunk c works on the 64-row slices slice_list[c * spc .. (c + 1) * spc) instead of spc
   // consecutive ones (-1: no slice); empty = consecutive slices
   DevBuf<int32_t> slice_list;
+  // box chunks (dia::box_grid): chunk c works on the grid lines of box c, a list of runs (first row, length) that the kernel
+  // derives from `box`; lds_doubles = r + max(x_j, products) of the fullest box
+  bool boxed = false;
+  dia::BoxGrid box = {};
+  int64_t box_lds_doubles = 0;
   bool empty() const { return n_chunks == 0; }
   RestrictMat view() const { return RestrictMat{chunk_slot.p, slot_ptr.p, w.p, fi.p, part.p, dest.p}; }
 };
@@ -331,7 +336,8 @@ struct DevCsr {                         // plain CSR copy for the single-workgro
 enum DownPath : int {                   // fused down kernel (pre-smoothing + restriction)
   DOWN_NONE = 0, DOWN_SELL = 1, DOWN_WIN = 2, DOWN_LW = 3, DOWN_DIA = 4,     // Jacobi: A' as SELL / windowed SELL / local window; diagonal image
   DOWN_CHEB = 5,                        // Chebyshev from zero, then residual + restriction
-  DOWN_GSB = 6                          // block-hybrid sweep from zero + gsb_residual_restrict (internal: entry 0 reports it as 0)
+  DOWN_GSB = 6,                         // block-hybrid sweep from zero + gsb_residual_restrict (internal: entry 0 reports it as 0)
+  DOWN_DIA_BOX = 7                      // diagonal image on box chunks (internal: entry 0 reports DOWN_DIA, entry 4 reports 2)
 };
 enum SweepPath : int {                  // Gauss-Seidel form
   SWEEP_NONE = 0, SWEEP_MC = 1, SWEEP_MC_ROWLIST = 2, SWEEP_MC_BSELL = 3, SWEEP_GSB = 4, SWEEP_BGSB = 5, SWEEP_BGSB_BC = 6, SWEEP_BGS = 7
@@ -341,7 +347,7 @@ struct LevelPaths {
   int sweep = SWEEP_NONE;
   bool plain = true;                    // sm_steps <= 1 && !sm_symm: the smoother is one base step, no ProxySmoother around it
   bool folded = false;                  // the V-cycle runs Q on the way up (see fold_prolongation)
-  bool jacobi_down() const { return down == DOWN_SELL || down == DOWN_WIN || down == DOWN_LW || down == DOWN_DIA; }
+  bool jacobi_down() const { return down == DOWN_SELL || down == DOWN_WIN || down == DOWN_LW || down == DOWN_DIA || down == DOWN_DIA_BOX; }
   bool bgsb() const { return sweep == SWEEP_BGSB || sweep == SWEEP_BGSB_BC; }     // block-hybrid forms: square-block levels,
   bool hybrid() const { return sweep == SWEEP_GSB || bgsb(); }                    //   ... or any level
 };
@@ -413,7 +419,7 @@ static void resolve_paths(DevLevel& L) {
   else if (L.gsb.on()) p.sweep = SWEEP_GSB;
   else if (L.gs.n_colors > 0) p.sweep = L.bs == 1 ? SWEEP_MC : (L.gs.bsell_ok ? SWEEP_MC_BSELL : SWEEP_MC_ROWLIST);
   if (p.plain && L.sm_type == AMGX_SM_JACOBI && !L.RF.empty())
-    p.down = !L.ApreLW.empty() ? DOWN_LW : L.dia.on() ? DOWN_DIA : L.Apre.sell.win ? DOWN_WIN : DOWN_SELL;
+    p.down = !L.ApreLW.empty() ? DOWN_LW : L.dia.on() ? (L.RF.boxed ? DOWN_DIA_BOX : DOWN_DIA) : L.Apre.sell.win ? DOWN_WIN : DOWN_SELL;
   else if (p.plain && L.sm_type == AMGX_SM_CHEBY && !L.RF.empty()) p.down = DOWN_CHEB;
   else if (p.plain && p.sweep == SWEEP_GSB && L.gsb.has_split && !L.RG.empty()) p.down = DOWN_GSB;
   L.paths = p;
@@ -1068,13 +1074,28 @@ static std::vector<int32_t> cluster_slices(const amgx_matrix& P, int spc) {
 
 // CH = fine rows per chunk; threads = workgroup size of the kernel that consumes the chunk (= CH unless several lanes share a row)
 // slice_list (optional, one thread per row only): chunk c = the 64-row slices slice_list[c * CH / 64 ...) (cluster_slices)
+// runs (optional, instead of a slice list): chunk c = the rows of the runs runs->run_ptr[c] .. runs->run_ptr[c + 1) (box chunks of
+// the diagonal image); the local index counts through the runs in their order, CH = the rows of the fullest chunk
 static void build_restrict(const Knobs& K, const amgx_matrix& P, DevRestrict& R, int CH = RESTRICT_CHUNK, int max_entries = RESTRICT_MAX_ENTRIES, int threads = 0,
-                           const std::vector<int32_t>* slice_list = nullptr) {
+                           const std::vector<int32_t>* slice_list = nullptr, const dia::BoxRuns* runs = nullptr) {
   if (threads <= 0) threads = CH;
   const int64_t nf = P.n_rows, nc = P.n_cols;
   const int spc = CH / WAVE;
-  if (slice_list && (CH % WAVE != 0 || slice_list->size() % spc != 0)) throw Err("build_restrict: slice list does not match the chunk size");
-  const int64_t nch = slice_list ? (int64_t)slice_list->size() / spc : (nf + CH - 1) / CH;
+  if (slice_list && (runs || CH % WAVE != 0 || slice_list->size() % spc != 0)) throw Err("build_restrict: slice list does not match the chunk size");
+  if (runs) {
+    int64_t covered = 0;
+    for (int64_t c = 0; c < runs->n_boxes(); ++c) {
+      int64_t rows = 0;
+      for (int64_t q = runs->run_ptr[c]; q < runs->run_ptr[c + 1]; ++q) {
+        if (runs->first[q] < 0 || runs->len[q] < 0 || runs->first[q] + runs->len[q] > nf) throw Err("build_restrict: a run leaves the level");
+        rows += runs->len[q];
+      }
+      if (rows > CH || rows > 65536) throw Err("build_restrict: a chunk of runs has more rows than its local index holds");
+      covered += rows;
+    }
+    if (covered != nf) throw Err("build_restrict: the runs do not cover the level's rows once");
+  }
+  const int64_t nch = runs ? runs->n_boxes() : slice_list ? (int64_t)slice_list->size() / spc : (nf + CH - 1) / CH;
   // pass 1 (parallel over chunks): slots (= distinct coarse columns) per chunk; a chunk's entries are the P entries of its rows
   std::vector<int32_t> chunk_slot(nch + 1, 0);
   std::vector<char> too_long(setup_threads(), 0);
@@ -1082,7 +1103,13 @@ static void build_restrict(const Knobs& K, const amgx_matrix& P, DevRestrict& R,
   struct Trip { int32_t J; uint16_t i; double w; };
   auto chunk_trips = [&](int64_t c, std::vector<Trip>& t) {
     t.clear();
-    if (slice_list) {
+    if (runs) {
+      int64_t local = 0;
+      for (int64_t q = runs->run_ptr[c]; q < runs->run_ptr[c + 1]; ++q)
+        for (int64_t i = runs->first[q]; i < runs->first[q] + runs->len[q]; ++i, ++local) {
+          for (int64_t k = P.rowptr[i]; k < P.rowptr[i + 1]; ++k) t.push_back({P.col[k], (uint16_t)local, P.val[k]});
+        }
+    } else if (slice_list) {
       for (int q = 0; q < spc; ++q) {
         const int64_t sl = (*slice_list)[c * spc + q];
         if (sl < 0) continue;
@@ -1143,6 +1170,7 @@ static void build_restrict(const Knobs& K, const amgx_matrix& P, DevRestrict& R,
   for (int64_t c = 0; c < nch; ++c) R.max_slots = std::max(R.max_slots, chunk_slot[c + 1] - chunk_slot[c]);
   R.max_entries = mx_chunk;
   R.ept = mx_chunk <= (int64_t)4 * threads ? 4 : 6;
+  if (runs) R.ept = (int)std::max<int64_t>(1, (mx_chunk + threads - 1) / threads);     // (the box kernel loops: any number of entries per lane)
   if ((CH == 256 || CH == 128) && threads == 512 && max_entries == 4 * 512) R.ept = mx_chunk <= (int64_t)2 * threads ? 2 : 4;     // (local-window chunks: see lw_image)
   if (R.ept > K.fused_ept_max) { R = DevRestrict(); return; }     // (A/B hook: keep the separate kernels instead)
   R.chunk_slot.upload(chunk_slot); R.slot_ptr.upload(slot_ptr); R.optr.upload(optr);
@@ -1976,6 +2004,24 @@ struct Handle {
             if (!dispatch<4>(R.ept, run)) run(Int<6>{});
           };
           if (!dispatch<1, 2, 3, 4, 5, 6, 7, 8>(L.dia.K, run_k)) throw Err("fused restriction (diagonal image): bad number of diagonals");
+        });
+        if (!skip_rsum) restrict_sum(l, R, b_coarse);
+        return;
+      }
+      case DOWN_DIA_BOX: {
+        // symmetric diagonal image on box chunks: one 512-lane workgroup per box of grid lines, whole level in one launch
+        if (!R.boxed || R.box.n_boxes() != R.n_chunks || (int64_t)R.box.nx * R.box.ny * R.box.nz != L.n || L.fused_block != 512 ||
+            R.box.box_rows() > dia::BOX_MAX_ROWS || R.box_lds_doubles < 2 * (int64_t)R.box.box_rows() ||
+            R.box_lds_doubles < R.box.box_rows() + R.max_entries || R.box_lds_doubles > DIA_BOX_LDS_DOUBLES)
+          throw Err("fused restriction (diagonal image, box chunks): box / chunk mismatch");
+        if (sp.part != PART_ALL) throw Err("fused restriction (diagonal image): the level is not split into interior / boundary parts");
+        probed(probe, [&] {
+          if (R.n_chunks <= 0) return;
+          auto run = [&](auto K) {
+            launch(dia_box_pre_restrict_kernel<K()>, R.n_chunks, 512, (size_t)R.box_lds_doubles * sizeof(double), stream, (int)L.n, L.dia.view(), R.box,
+                   R.box.box_rows(), b, L.dinv.p, L.omega, epf, x, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+          };
+          if (!dispatch<2, 3, 4, 5, 6, 7>(L.dia.K, run)) throw Err("fused restriction (diagonal image, box chunks): bad number of diagonals");
         });
         if (!skip_rsum) restrict_sum(l, R, b_coarse);
         return;
@@ -3657,13 +3703,13 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
     int64_t v[AMGX_LEVEL_PATHS_N] = {};
     const int down = L.paths.down;
     if (down != amgx::DOWN_NONE && down != amgx::DOWN_GSB) {          // (the fused block-hybrid form is not a kernel of entry 0)
-      v[0] = down;
+      v[0] = down == amgx::DOWN_DIA_BOX ? (int)amgx::DOWN_DIA : down;
       v[1] = L.fused_block;
-      v[2] = down == amgx::DOWN_CHEB ? L.A.lanes : down == amgx::DOWN_LW ? L.ApreLW.lanes : down == amgx::DOWN_DIA ? 1 : L.Apre.lanes;
+      v[2] = down == amgx::DOWN_CHEB ? L.A.lanes : down == amgx::DOWN_LW ? L.ApreLW.lanes : (down == amgx::DOWN_DIA || down == amgx::DOWN_DIA_BOX) ? 1 : L.Apre.lanes;
       v[3] = R.ept;
     }
     if (!R.empty()) {
-      v[4] = R.slice_list.n ? 1 : 0;
+      v[4] = R.boxed ? 2 : R.slice_list.n ? 1 : 0;
       v[5] = R.max_slots;
       v[6] = R.max_entries;
       v[18] = R.n_chunks;

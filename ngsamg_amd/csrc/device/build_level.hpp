@@ -225,7 +225,8 @@ static bool lw_image(LevelBuild& B) {
 // the fused down kernel streams the symmetric diagonal image of A instead of A' (dia_pre_restrict_kernel) -- 7 of the 15
 // diagonals from HBM at cfg 2, the lower ones are shifted re-reads of the same arrays, and no index stream.  Not on levels
 // a rank-partitioned driver runs stage by stage (dense_first < 0), nor below AMGX_DIA_MIN_ROWS rows (2 M: the smaller levels
-// keep the SELL image).  AMGX_NO_DIA=1 disables it.
+// keep the SELL image), nor where the image would store more than AMGX_DIA_MAX_FILL (1.05) x the entries of A -- thin grids, whose
+// boundary rows fill few of the diagonals.  AMGX_NO_DIA=1 disables it.
 static bool dia_image(LevelBuild& B) {
   const amgx_level_desc& s = B.s;
   DevLevel& L = B.L;
@@ -235,7 +236,7 @@ static bool dia_image(LevelBuild& B) {
   if (B.dev_images ? !B.diagA.plain : !host_diag_plain(s)) return false;
   auto par = [](int64_t nb, auto&& f) { par_for(nb, [&](int64_t a, int64_t b, int) { for (int64_t q = a; q < b; ++q) f(q); }, 1); };
   int32_t off[dia::MAX_UPPER];
-  const int K = dia::detect(s.A.n_rows, s.A.n_cols, s.A.rowptr, s.A.col, s.A.val, dia::MAX_DIAGS, 1.05, off, par);
+  const int K = dia::detect(s.A.n_rows, s.A.n_cols, s.A.rowptr, s.A.col, s.A.val, dia::MAX_DIAGS, B.K.dia_max_fill, off, par);
   if (K <= 0 || K > DIA_MAX_UPPER) return false;
   DevDia& D = L.dia;
   D.K = K;
@@ -251,6 +252,27 @@ static bool dia_image(LevelBuild& B) {
   } else
     D.val.upload(hv);
   L.fused_block = 512;
+  // a lexicographic grid of at least AMGX_DIA_BOX_MIN_ROWS rows: box chunks (dia_box_pre_restrict_kernel); AMGX_NO_DIA_BOX=1 keeps
+  // the chunks below, and so does every level grid_of / box_grid refuse or whose fullest box does not fit the kernel's LDS
+  dia::Grid grid;
+  dia::BoxGrid box;
+  if (!B.K.no_dia_box && s.A.n_rows >= B.K.dia_box_min_rows && K >= 2 && K <= 7 && dia::grid_of(s.A.n_rows, K, off, grid) &&
+      dia::box_grid(grid, K, B.K.dia_box_yc, B.K.dia_box_zc, box)) {
+    const dia::BoxRuns runs = dia::box_runs(box);
+    build_restrict(B.K, s.P, L.RF, box.box_rows(), DIA_BOX_LDS_DOUBLES - box.box_rows(), 512, nullptr, &runs);
+    if (!L.RF.empty()) {
+      L.RF.boxed = true;
+      L.RF.box = box;
+      L.RF.box_lds_doubles = box.box_rows() + std::max<int64_t>(box.box_rows(), L.RF.max_entries);
+      // (more than 64 KB of dynamic LDS has to be allowed per kernel, once)
+      auto allow = [&](auto KK) {
+        HIPCHK(hipFuncSetAttribute((const void*)dia_box_pre_restrict_kernel<KK()>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   DIA_BOX_LDS_DOUBLES * (int)sizeof(double)));
+      };
+      if (L.RF.box_lds_doubles * sizeof(double) > 65536) dispatch<2, 3, 4, 5, 6, 7>(K, allow);
+      return true;
+    }
+  }
   build_restrict_chunks(B.K, s.P, L.RF, 512, 6 * 512, 512, true);
   if (L.RF.empty()) { L.dia = DevDia(); return false; }
   return true;

@@ -30,6 +30,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../host/dia.hpp"     // box chunks of the diagonal image: the geometry helpers the kernel shares with the host
 
 namespace amgx {
 
@@ -1595,6 +1596,128 @@ __global__ __launch_bounds__(512) void dia_pre_restrict_kernel(int n_rows, int n
     part[mydest] = acc;
   }
   for (int slot = myslot + FB; slot < s1; slot += FB) {
+    const int a = slot_ptr[slot] - e0, bnd = slot_ptr[slot + 1] - e0;
+    double acc = 0.0;
+    for (int k = a; k < bnd; ++k) acc += pr[k];
+    part[dest ? dest[slot] : slot] = acc;
+  }
+}
+
+// dia_pre_restrict_kernel on BOX chunks (host/dia.hpp: grid_of, box_grid): the level is a lexicographic grid and a workgroup owns
+// a box of whole grid lines, nx x yc x zc rows, instead of 512 consecutive ones.  A row's far neighbours (one grid line, one grid
+// plane away) are then mostly rows of the same box: the workgroup publishes x_j = omega * (dinv_j * b_j) of its rows in LDS first
+// and the row product takes the in-box neighbours' x_j from there -- the same bits the 512-row kernel forms from b_j and dinv_j,
+// which it reads over the fabric (they belong to chunks on other XCDs).  Out-of-box neighbours are read as before; the lower
+// U_k[row - o_k] comes from global memory in both cases.  512 lanes, up to dia::BOX_MAX_ROWS / 512 = 4 rows per lane, taken one
+// after the other with every operand of a row requested before the first product.  r and the stored x are bitwise those of
+// dia_pre_restrict_kernel (same expressions, same order); the partial sums of the restriction are grouped by box.
+// LDS (dynamic): r of the box [lds_rows], then x_j [lds_rows] that the restriction's products [most entries of a box] replace.
+// The restriction data of a box does not fit the registers beside a row's operands (13 entries per lane at cfg 2): it is requested
+// after the last row product, four entries per lane and pass, the first pass ahead of the barrier.
+// Measured at cfg 2 (profiles/r13/box_ab.txt): 358.9 -> 307.3 us, 2.203 -> 1.950 GB of fabric traffic per launch; <7>: 100 VGPRs.
+constexpr int DIA_BOX_LDS_DOUBLES = 10240;    // 80 KB of LDS per workgroup at most: two workgroups per CU (160 KB)
+template <int K>
+__global__ __launch_bounds__(512, 4) void dia_box_pre_restrict_kernel(int n_rows, DiaMat D, dia::BoxGrid G, int lds_rows, const double* __restrict__ b,
+                                                                      const double* __restrict__ dinv, double omega, int nt, double* __restrict__ x,
+                                                                      const int32_t* __restrict__ chunk_slot, const int32_t* __restrict__ slot_ptr,
+                                                                      const double* __restrict__ w, const uint16_t* __restrict__ fi,
+                                                                      double* __restrict__ part, const int32_t* __restrict__ dest) {
+  constexpr int FB = 512, RPT = dia::BOX_MAX_ROWS / FB, EB = 4;
+  extern __shared__ double box_lds[];
+  double* rl = box_lds;
+  double* xs = box_lds + lds_rows;
+  double* pr = xs;
+  const int c = (int)blockIdx.x;
+  const dia::BoxAt at = dia::box_at(G, c);
+  const int nrow = dia::box_nrows(G, at);
+  const int s0 = chunk_slot[c], s1 = chunk_slot[c + 1];
+  const int e0 = slot_ptr[s0], e1 = slot_ptr[s1];
+  // publish x_j of the box's rows
+  {
+    double bq[RPT], dq[RPT];
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) {
+      const int local = (int)threadIdx.x + j * FB;
+      bq[j] = 0.0; dq[j] = 0.0;
+      if (local < nrow) {
+        const int row = dia::box_global(G, at, dia::box_row(G, at, local));
+        bq[j] = b[row]; dq[j] = dinv[row];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) {
+      const int local = (int)threadIdx.x + j * FB;
+      if (local < nrow) xs[local] = omega * (dq[j] * bq[j]);
+    }
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int local = (int)threadIdx.x; local < nrow; local += FB) {
+    const dia::BoxRow br = dia::box_row(G, at, local);
+    const int row = dia::box_global(G, at, br);
+    // every operand requested before the first product (out-of-range neighbours read row i itself and are masked)
+    double al[K], au[K], bl[K], bu[K], dl[K], du[K];
+    bool inl[K], inu[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const double* __restrict__ U = D.val + (int64_t)k * n_rows;
+      const int o = D.off[k];
+      const int jl = row - o >= 0 ? row - o : row;
+      const int ju = row + o < n_rows ? row + o : row;
+      inl[k] = dia::box_has(G, at, br, k, false);
+      inu[k] = dia::box_has(G, at, br, k, true);
+      al[k] = U[jl]; au[k] = U[row];
+      bl[k] = 0.0; dl[k] = 0.0; bu[k] = 0.0; du[k] = 0.0;
+      if (!inl[k]) { bl[k] = b[jl]; dl[k] = dinv[jl]; }
+      if (!inu[k]) { bu[k] = b[ju]; du[k] = dinv[ju]; }
+    }
+    const double bi = b[row], di = dinv[row];
+    double acc = 0.0;
+#pragma unroll
+    for (int k = K - 1; k >= 0; --k)
+      if (row - D.off[k] >= 0) {
+        const double xj = inl[k] ? xs[local - dia::box_local_offset(G, at, k)] : omega * (dl[k] * bl[k]);
+        acc += al[k] * xj;
+      }
+    if (di != 0.0) acc += omega * bi;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (row + D.off[k] < n_rows) {
+        const double xj = inu[k] ? xs[local + dia::box_local_offset(G, at, k)] : omega * (du[k] * bu[k]);
+        acc += au[k] * xj;
+      }
+    const double r = bi - acc;
+    double xi = omega * (di * bi);
+    if (nt & EPF_FOLD) xi += omega * (di * r);
+    if (nt & EPF_NT) __builtin_nontemporal_store(xi, x + row);
+    else x[row] = xi;
+    rl[local] = r;
+  }
+  // chunk-local restriction: part[slot] = sum over the slot's entries of w * r_lds[fi]
+  double wq[EB];
+  int fq[EB];
+  auto request = [&](int eb) {
+#pragma unroll
+    for (int q = 0; q < EB; ++q) {
+      const int e = eb + q * FB;
+      wq[q] = e < e1 ? ld_nt(w + e) : 0.0;
+      fq[q] = e < e1 ? (int)ld_nt(fi + e) : 0;
+    }
+  };
+  auto products = [&](int eb) {
+#pragma unroll
+    for (int q = 0; q < EB; ++q) {
+      const int e = eb + q * FB;
+      if (e < e1) pr[e - e0] = wq[q] * rl[fq[q]];
+    }
+  };
+  int eb = e0 + (int)threadIdx.x;
+  request(eb);
+  __syncthreads();                               // r of the box is complete, x_j no longer read
+  products(eb);
+  for (eb += EB * FB; eb < e1; eb += EB * FB) { request(eb); products(eb); }
+  __syncthreads();
+  for (int slot = s0 + (int)threadIdx.x; slot < s1; slot += FB) {
     const int a = slot_ptr[slot] - e0, bnd = slot_ptr[slot + 1] - e0;
     double acc = 0.0;
     for (int k = a; k < bnd; ++k) acc += pr[k];

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <thread>
@@ -46,6 +47,10 @@ struct Knobs {
   bool apre_window = false;             // AMGX_APRE_WINDOW: windowed A' on levels >= 1 (A/B hook)
   bool no_dia = false;                  // AMGX_NO_DIA: no symmetric diagonal image (kill switch)
   int64_t dia_min_rows = 2000000;       // AMGX_DIA_MIN_ROWS: smallest level that takes the diagonal image (threshold)
+  double dia_max_fill = 1.05;           // AMGX_DIA_MAX_FILL: stored / present entries up to which a level takes the diagonal image (threshold)
+  bool no_dia_box = false;              // AMGX_NO_DIA_BOX: the diagonal image keeps its chunks of 512 consecutive rows (kill switch)
+  int64_t dia_box_min_rows = 200000;    // AMGX_DIA_BOX_MIN_ROWS: smallest grid level whose diagonal image takes box chunks (threshold)
+  int dia_box_yc = 0, dia_box_zc = 0;   // AMGX_DIA_BOX_SHAPE=YxZ: grid lines per box in y and z; default 2x4 in 3D, 8x1 in 2D (A/B hook)
   bool no_lw = false;                   // AMGX_NO_LW: no local-window images (kill switch)
   bool no_qlw = false;                  // AMGX_NO_QLW: no local-window image of Q (kill switch)
   int64_t lw_min_rows = 100000;         // AMGX_LW_MIN_ROWS: smallest level that takes local-window images (threshold)
@@ -118,6 +123,13 @@ struct Knobs {
     k.apre_window = on("AMGX_APRE_WINDOW");
     k.no_dia = on("AMGX_NO_DIA");
     i64("AMGX_DIA_MIN_ROWS", k.dia_min_rows);
+    if (const char* e = std::getenv("AMGX_DIA_MAX_FILL")) k.dia_max_fill = std::max(1.0, std::atof(e));
+    k.no_dia_box = on("AMGX_NO_DIA_BOX");
+    i64("AMGX_DIA_BOX_MIN_ROWS", k.dia_box_min_rows);
+    if (const char* e = std::getenv("AMGX_DIA_BOX_SHAPE")) {
+      int y = 0, z = 0;
+      if (std::sscanf(e, "%dx%d", &y, &z) == 2 && y > 0 && z > 0) { k.dia_box_yc = y; k.dia_box_zc = z; }
+    }
     k.no_lw = on("AMGX_NO_LW");
     k.no_qlw = on("AMGX_NO_QLW");
     i64("AMGX_LW_MIN_ROWS", k.lw_min_rows);

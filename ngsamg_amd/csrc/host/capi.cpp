@@ -438,4 +438,45 @@ int amgh_dia_image(const amgh_matrix* A, int32_t K, const int32_t* offsets, doub
   });
 }
 
+int amgh_dia_grid(int64_t n_rows, int32_t K, const int32_t* offsets, int64_t* shape_out, int32_t* dxyz_out) {
+  return guard([&] {
+    if (!offsets || !shape_out || !dxyz_out) throw amgh::Error("amgh_dia_grid: bad arguments");
+    dia::Grid g;
+    const bool ok = dia::grid_of(n_rows, K, offsets, g);
+    shape_out[0] = ok ? g.nx : 0; shape_out[1] = ok ? g.ny : 0; shape_out[2] = ok ? g.nz : 0;
+    for (int k = 0; ok && k < K; ++k) { dxyz_out[3 * k] = g.dx[k]; dxyz_out[3 * k + 1] = g.dy[k]; dxyz_out[3 * k + 2] = g.dz[k]; }
+  });
+}
+
+int amgh_dia_boxes(int64_t n_rows, int32_t K, const int32_t* offsets, int32_t yc, int32_t zc, int64_t* counts_out, int64_t* run_ptr_out,
+                   int64_t* first_out, int32_t* len_out) {
+  return guard([&] {
+    if (!offsets || !counts_out) throw amgh::Error("amgh_dia_boxes: bad arguments");
+    dia::Grid g;
+    dia::BoxGrid b;
+    counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
+    if (!dia::grid_of(n_rows, K, offsets, g) || !dia::box_grid(g, K, yc, zc, b)) return;
+    const dia::BoxRuns R = dia::box_runs(b);
+    counts_out[0] = R.n_boxes(); counts_out[1] = (int64_t)R.first.size(); counts_out[2] = b.yc; counts_out[3] = b.zc;
+    if (run_ptr_out) std::copy(R.run_ptr.begin(), R.run_ptr.end(), run_ptr_out);
+    if (first_out) std::copy(R.first.begin(), R.first.end(), first_out);
+    if (len_out) std::copy(R.len.begin(), R.len.end(), len_out);
+  });
+}
+
+int amgh_dia_box_neighbours(int64_t n_rows, int32_t K, const int32_t* offsets, int32_t yc, int32_t zc, int64_t box, int32_t k, int32_t up,
+                            int32_t* local_out) {
+  return guard([&] {
+    dia::Grid g;
+    dia::BoxGrid b;
+    if (!offsets || !local_out || !dia::grid_of(n_rows, K, offsets, g) || !dia::box_grid(g, K, yc, zc, b) || box < 0 || box >= b.n_boxes() ||
+        k < 0 || k >= K)
+      throw amgh::Error("amgh_dia_box_neighbours: bad arguments");
+    const dia::BoxAt a = dia::box_at(b, (int)box);
+    const int lo = dia::box_local_offset(b, a, k);
+    for (int local = 0; local < dia::box_nrows(b, a); ++local)
+      local_out[local] = dia::box_has(b, a, dia::box_row(b, a, local), k, up != 0) ? (up ? local + lo : local - lo) : -1;
+  });
+}
+
 }  // extern "C"

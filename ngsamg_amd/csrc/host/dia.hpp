@@ -100,4 +100,134 @@ void upper_image(int64_t n_rows, const int64_t* rowptr, const int32_t* col, cons
   });
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Lexicographic grids and box chunks (dia_box_pre_restrict_kernel).
+//
+// The K upper offsets of a level whose rows are the vertices of an nx x ny x nz grid in lexicographic order (x fastest) are
+// sums o_k = dx + dy * sy + dz * sz with dx, dy, dz in {0, 1}, sy = nx and sz = nx * ny.  grid_of() recognises that from the
+// offsets alone; box_grid() then cuts the grid into boxes of whole grid lines, nx x yc x zc rows (clipped at the grid's edge,
+// never padded), numbered y fastest, then z.  A box is the chunk of one workgroup: most neighbours of a row are rows of the same
+// box, whose x_j = omega * (dinv_j * b_j) the workgroup hands over through LDS instead of reading b_j and dinv_j again.
+// Inside a box the rows are numbered line by line (y fastest, then z): local = (lz * lines_y + ly) * nx + x.
+// The geometry helpers are shared with the kernel (DIA_HD), so that the CPU tests check the very arithmetic the device runs.
+#ifdef __HIPCC__
+#define DIA_HD __host__ __device__ inline
+#else
+#define DIA_HD inline
+#endif
+
+constexpr int BOX_MAX_LINES = 8;       // grid lines per box
+constexpr int BOX_MAX_ROWS = 2048;     // rows per box (512 lanes x 4 rows; the local index of the restriction data is 16-bit)
+constexpr int BOX_MIN_ROWS = 48;       // a full box must fill 3/4 of one wave at least
+
+struct Grid {
+  int64_t nx = 0, ny = 0, nz = 0;      // nz = 1: a 2D grid
+  int dx[MAX_UPPER] = {}, dy[MAX_UPPER] = {}, dz[MAX_UPPER] = {};
+};
+
+// true (and g filled) when offsets[0 .. K) are those of a lexicographic grid of n rows; false: not a grid (fewer than two
+// offsets, an offset that does not decompose, n not divisible)
+inline bool grid_of(int64_t n, int K, const int32_t* off, Grid& g) {
+  if (K < 2 || K > MAX_UPPER || off[0] != 1 || off[1] < 2) return false;
+  const int64_t sy = off[1];
+  int64_t sz = 0;
+  for (int k = 2; k < K; ++k) if (off[k] > sy + 1) { sz = off[k]; break; }
+  if (sz ? (sz % sy != 0 || n % sz != 0) : n % sy != 0) return false;
+  g = Grid();
+  g.nx = sy;
+  g.ny = sz ? sz / sy : n / sy;
+  g.nz = sz ? n / sz : 1;
+  for (int k = 0; k < K; ++k) {
+    bool found = false;
+    for (int c = 1; c < (sz ? 8 : 4) && !found; ++c)
+      if ((c & 1) + ((c >> 1) & 1) * sy + ((c >> 2) & 1) * sz == off[k]) { g.dx[k] = c & 1; g.dy[k] = (c >> 1) & 1; g.dz[k] = (c >> 2) & 1; found = true; }
+    if (!found) return false;
+  }
+  return true;
+}
+
+// the boxes of a grid, as the kernel takes them (plain data)
+struct BoxGrid {
+  int nx, ny, nz;                      // the grid
+  int yc, zc;                          // a full box: nx x yc x zc rows
+  int nby, nbz;                        // boxes in y and z
+  int dmask;                           // bits 3k, 3k + 1, 3k + 2: dx, dy, dz of diagonal k
+  DIA_HD int n_boxes() const { return nby * nbz; }
+  DIA_HD int box_rows() const { return nx * yc * zc; }
+};
+
+// yc x zc lines per box (0 x 0: 2 x 4 in 3D, 8 x 1 in 2D), halved -- z first -- until a box has at most BOX_MAX_ROWS rows.
+// false: the grid takes no boxes (a line longer than a box may be, a full box below BOX_MIN_ROWS rows, a shape of more than
+// BOX_MAX_LINES lines, more rows than 32-bit indices hold)
+inline bool box_grid(const Grid& g, int K, int yc, int zc, BoxGrid& b) {
+  if (yc <= 0 || zc <= 0) { yc = g.nz > 1 ? 2 : 8; zc = g.nz > 1 ? 4 : 1; }
+  if (g.nz == 1) zc = 1;
+  if (yc * zc > BOX_MAX_LINES || g.nx > BOX_MAX_ROWS || g.nx * g.ny * g.nz > (int64_t)2147483647) return false;
+  while (g.nx * yc * zc > BOX_MAX_ROWS) { if (zc > 1) zc = (zc + 1) / 2; else yc = (yc + 1) / 2; }
+  if (g.nx * yc * zc < BOX_MIN_ROWS) return false;
+  b.nx = (int)g.nx; b.ny = (int)g.ny; b.nz = (int)g.nz;
+  b.yc = yc; b.zc = zc;
+  b.nby = (int)((g.ny + yc - 1) / yc); b.nbz = (int)((g.nz + zc - 1) / zc);
+  b.dmask = 0;
+  for (int k = 0; k < K; ++k) b.dmask |= (g.dx[k] | g.dy[k] << 1 | g.dz[k] << 2) << (3 * k);
+  return true;
+}
+
+// one box: its first line and its (clipped) numbers of lines
+struct BoxAt { int y0, z0, ly, lz; };
+DIA_HD BoxAt box_at(const BoxGrid& g, int box) {
+  BoxAt a;
+  const int bz = box / g.nby, by = box - bz * g.nby;
+  a.y0 = by * g.yc; a.z0 = bz * g.zc;
+  a.ly = g.ny - a.y0 < g.yc ? g.ny - a.y0 : g.yc;
+  a.lz = g.nz - a.z0 < g.zc ? g.nz - a.z0 : g.zc;
+  return a;
+}
+DIA_HD int box_nrows(const BoxGrid& g, const BoxAt& a) { return g.nx * a.ly * a.lz; }
+
+// a row of the box by its local index: x and line (y, z) inside the box
+struct BoxRow { int x, y, z; };
+DIA_HD BoxRow box_row(const BoxGrid& g, const BoxAt& a, int local) {
+  int line = 0, z = 0;
+  for (int q = 1; q < BOX_MAX_LINES; ++q) line += local >= q * g.nx;         // (local < lines * nx bounds both sums)
+  for (int q = 1; q < BOX_MAX_LINES; ++q) z += line >= q * a.ly;
+  return BoxRow{local - line * g.nx, line - z * a.ly, z};
+}
+DIA_HD int box_global(const BoxGrid& g, const BoxAt& a, const BoxRow& r) { return ((a.z0 + r.z) * g.ny + (a.y0 + r.y)) * g.nx + r.x; }
+
+// is row -/+ o_k (up = false / true) a row of the same box?  Its local index is then local -/+ box_local_offset(g, a, k).
+// (row + o_k with x + dx = nx is the first vertex of the next line -- a structural zero of U_k, but the same rule holds.)
+DIA_HD bool box_has(const BoxGrid& g, const BoxAt& a, const BoxRow& r, int k, bool up) {
+  const int dx = (g.dmask >> (3 * k)) & 1, dy = (g.dmask >> (3 * k + 1)) & 1, dz = (g.dmask >> (3 * k + 2)) & 1;
+  if (up) return r.y + dy + (r.x + dx >= g.nx ? 1 : 0) < a.ly && r.z + dz < a.lz;
+  return r.y - dy - (r.x - dx < 0 ? 1 : 0) >= 0 && r.z - dz >= 0;
+}
+DIA_HD int box_local_offset(const BoxGrid& g, const BoxAt& a, int k) {
+  const int dx = (g.dmask >> (3 * k)) & 1, dy = (g.dmask >> (3 * k + 1)) & 1, dz = (g.dmask >> (3 * k + 2)) & 1;
+  return dx + (dy + dz * a.ly) * g.nx;
+}
+
+// the rows of every box as runs (first row, length): the lines of box c are runs run_ptr[c] .. run_ptr[c + 1), in the order of
+// the local index
+struct BoxRuns {
+  std::vector<int64_t> first;
+  std::vector<int32_t> len;
+  std::vector<int64_t> run_ptr;
+  int64_t n_boxes() const { return (int64_t)run_ptr.size() - 1; }
+};
+inline BoxRuns box_runs(const BoxGrid& g) {
+  BoxRuns R;
+  R.run_ptr.push_back(0);
+  for (int c = 0; c < g.n_boxes(); ++c) {
+    const BoxAt a = box_at(g, c);
+    for (int z = 0; z < a.lz; ++z)
+      for (int y = 0; y < a.ly; ++y) {
+        R.first.push_back(box_global(g, a, BoxRow{0, y, z}));
+        R.len.push_back(g.nx);
+      }
+    R.run_ptr.push_back((int64_t)R.first.size());
+  }
+  return R;
+}
+
 }  // namespace dia

@@ -595,7 +595,8 @@ class DeviceAMGMatrix:
     def level_paths(self, level):
         """the paths amgx_create chose for one level (amgx_level_paths, read-only): the fused Jacobi down kernel (None, "sell",
         "sell-win", "sell-lw" or "dia"), its workgroup size and lanes per row, the chunk-local restriction (entries of P per thread,
-        compact chunks, most slots / entries in one chunk, number of chunks), the diagonals of the DIA image, the XCD placement
+        "compact": 0 consecutive rows / 1 compact chunks / 2 box chunks of the DIA image, most slots / entries in one chunk, number
+        of chunks), the diagonals of the DIA image, the XCD placement
         flags, the 16-bit / all slices of A and A', the local-window chunks without a window and whether the level is folded;
         the Gauss-Seidel sweep ("gs_form": None, "mc", "mc-block-rowlist", "mc-block-bsell", "hybrid", "hybrid-block",
         "block-coloured" or "bgs"), its lanes per row, workgroup size, rows per block, colours, block colours, split images, the

@@ -42,7 +42,7 @@ def main():
     d, commit, date = sys.argv[1], sys.argv[2], sys.argv[3]
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     # (pmc tag, kernel-name needle, rank of the grid group by size, output, label)
-    jobs = [("jacobi_spw", "sell_pre_restrict_kernel<512, 0", 0, "traffic_pre_restrict_l0_spw.json", "sell_pre_restrict_kernel<512, 0, EPT, 1> level 0 (cfg 2, default hierarchy)"),
+    jobs = [("jacobi_spw", "dia_box_pre_restrict_kernel<7>", 0, "traffic_pre_restrict_l0_spw.json", "dia_box_pre_restrict_kernel<7> level 0 (cfg 2, default hierarchy; symmetric diagonal image of A, box chunks of 2 x 4 grid lines)"),
             ("jacobi_spw", "sell_lw_win_spmv_kernel<512, 2>", 0, "traffic_q_l0_spw.json", "sell_lw_win_spmv_kernel<512, EP_AXPY> on Q, level 0 (cfg 2, default hierarchy)"),
             ("jacobi_spw", "sell_lw_pre_restrict_kernel<2, 2, 0>", 0, "traffic_lw_pre_restrict_l1_spw.json", "sell_lw_pre_restrict_kernel<2, 2, 0> level 1 (cfg 2, default hierarchy: 1.24 M rows x 52)"),
             ("jacobi_spw", "sell_lw_win_spmv_kernel<512, 2>", 1, "traffic_q_l1_spw.json", "sell_lw_win_spmv_kernel<512, EP_AXPY> on Q, level 1 (cfg 2, default hierarchy)"),
