@@ -61,8 +61,11 @@ enum {
                               /* same recurrence -- ONE reduction point (one all-reduce of two scalars) per iteration and  */
                               /* three launches beside the cycle and the level-0 product instead of five; histories agree   */
                               /* with the classical form to ~1e-6                                                            */
-  AMGX_MULTI_INTERLEAVED = 32 /* multi-vector calls: entry (row i, column j) of a multi-vector lives at i*k + j and ld is      */
+  AMGX_MULTI_INTERLEAVED = 32,/* multi-vector calls: entry (row i, column j) of a multi-vector lives at i*k + j and ld is      */
                               /* ignored.  Without it: column-major, column j starts at j*ld, ld >= level size                */
+  AMGX_MULTI_FUSE = 64        /* amgx_apply_multi / amgx_matvec_multi / amgx_pcg_multi: run fused column groups on every handle */
+                              /* that qualifies under the EXTENDED rule (Chebyshev and block levels, see below); a handle that  */
+                              /* does not qualify runs the column loop -- never an error.  Without it every call is as before   */
 };
 
 typedef struct amgx_level_desc {
@@ -364,13 +367,26 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  * cycles, ProxySmoother) answers the same calls through a column loop over the single-vector path -- all or nothing per handle.
  *   amgx_multi_info  : fused = 1 / 0 as above; the groups a call with k columns runs as (group_width: AMGX_MULTI_MAX entries,
  *                      0 beyond n_groups; all 1 when fused = 0); work_bytes = device memory of the multi-vector work space such a
- *                      call allocates (kept until amgx_destroy).  Any of the output pointers may be NULL. */
+ *                      call allocates (kept until amgx_destroy).  Any of the output pointers may be NULL.
+ * With AMGX_MULTI_FUSE the rule is wider (opt-in per call): V cycle; every level square and in the caller's
+ * numbering; every smoothed level plain (sm_steps = 1, no sm_symm) with AMGX_SM_JACOBI or AMGX_SM_CHEBY, mixed freely from level to
+ * level; block size 1, 2, 3 or 6; A in SELL (plain or windowed), CSR-vector, BSELL or block CSR with a square block; P, P^T scalar,
+ * rigid-body transfer blocks or block CSR (22, 33, 66, 36, 63, 23, 32).  Chebyshev levels run the literal recurrence of the
+ * single-vector smoother with the same coefficients and read the single-precision image where the level has one; amgx_matvec_multi
+ * and the level-0 product of amgx_pcg_multi read the fp64 image.  Gauss-Seidel in any form, W / BS cycles and the ProxySmoother keep
+ * the column loop.
+ *   amgx_multi_plan  : the outputs of amgx_multi_info for a call that carries `flags` (only AMGX_MULTI_FUSE is looked at; flags = 0
+ *                      answers exactly what amgx_multi_info answers); work_bytes counts one more vector per Chebyshev level
+ *   amgx_multi_note  : the first reason why the handle is not fused under `flags` (it names the level), "" when it is fused.  The
+ *                      string lives until the calling thread's next amgx_multi_note */
 #define AMGX_MULTI_MAX 8
 int amgx_apply_multi(amgx_handle h, int k, const double* B, int64_t ldb, double* X, int64_t ldx, int b_status, int flags);
 int amgx_matvec_multi(amgx_handle h, int level, int k, const double* X, int64_t ldx, double* Y, int64_t ldy, int flags);
 int amgx_pcg_multi(amgx_handle h, int k, const double* B, int64_t ldb, double* X, int64_t ldx, double tol, int maxit, int use_precond, int flags,
                    double* errs, int32_t* iters);
 int amgx_multi_info(amgx_handle h, int k, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes);
+int amgx_multi_plan(amgx_handle h, int k, int flags, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes);
+const char* amgx_multi_note(amgx_handle h, int flags);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Rank-partitioned hierarchies (one process per GPU; SURVEY.md 8b "halo tables + RCCL communicator", 8e).

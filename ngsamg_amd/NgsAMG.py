@@ -239,9 +239,9 @@ class AMGMatrix:
     def Mult(self, b, x):
         return self._dev.Mult(b, x)
 
-    def MultMulti(self, B, X, interleaved=False):
+    def MultMulti(self, B, X, interleaved=False, fuse=False):
         """BaseMatrix::Mult on a MultiVector: X[j] = C B[j], k right-hand sides per matrix pass (DeviceAMGMatrix.MultMulti)"""
-        return self._dev.MultMulti(B, X, interleaved=interleaved)
+        return self._dev.MultMulti(B, X, interleaved=interleaved, fuse=fuse)
 
     def MultAdd(self, s, b, x):
         return self._dev.MultAdd(s, b, x)
@@ -407,8 +407,8 @@ class _AMGPreconditioner:
     def Mult(self, b, x):
         return self._need().Mult(b, x)
 
-    def MultMulti(self, B, X, interleaved=False):
-        return self._need().MultMulti(B, X, interleaved=interleaved)
+    def MultMulti(self, B, X, interleaved=False, fuse=False):
+        return self._need().MultMulti(B, X, interleaved=interleaved, fuse=fuse)
 
     def MultAdd(self, s, b, x):
         return self._need().MultAdd(s, b, x)

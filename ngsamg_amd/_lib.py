@@ -241,6 +241,7 @@ AMGX_CLEV_NONE, AMGX_CLEV_INV = 0, 1
 AMGX_HOST_PTR, AMGX_DEVICE_PTR, AMGX_NO_GRAPH = 0, 1, 2
 AMGX_PCG_SINGLE_REDUCTION = 16
 AMGX_MULTI_INTERLEAVED = 32
+AMGX_MULTI_FUSE = 64
 AMGX_MULTI_MAX = 8
 
 AMGX_SYMBOLS = [
@@ -256,7 +257,7 @@ AMGX_SYMBOLS = [
     "amgx_gss4_create", "amgx_gss4_destroy", "amgx_gss4_last_error", "amgx_gss4_set_stream", "amgx_gss4_synchronize",
     "amgx_gss4_info", "amgx_gss4_smooth", "amgx_gss4_smooth_res", "amgx_gss4_mult_add",
     "amgx_device_count", "amgx_spgemm", "amgx_galerkin", "amgx_csr_result_fetch",
-    "amgx_apply_multi", "amgx_matvec_multi", "amgx_pcg_multi", "amgx_multi_info",
+    "amgx_apply_multi", "amgx_matvec_multi", "amgx_pcg_multi", "amgx_multi_info", "amgx_multi_plan", "amgx_multi_note",
     "amgx_smoother_info",
 ]
 
@@ -313,6 +314,9 @@ def hip():
     lib.amgx_matvec_multi.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int]
     lib.amgx_pcg_multi.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, c_f64p, c_i32p]
     lib.amgx_multi_info.argtypes = [vp, C.c_int, c_i32p, c_i32p, c_i32p, c_i64p]
+    lib.amgx_multi_plan.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_i64p]
+    lib.amgx_multi_note.argtypes = [vp, C.c_int]
+    lib.amgx_multi_note.restype = C.c_char_p
     # rank-partitioned hierarchies
     lib.amgx_comm_unique_id.argtypes = [C.c_char_p]
     lib.amgx_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(vp)]

@@ -237,6 +237,13 @@ def check_multi(vecs, sizes, interleaved=False, names=None):
     return k, addrs, lds, all(kinds) and bool(kinds)
 
 
+def check_fuse(fuse):
+    """Validate the fuse= keyword of the multi-vector calls (a plain function: no handle, no native call); returns the flag bits"""
+    if not isinstance(fuse, (bool, np.bool_)):
+        raise NgsAMGError(f"fuse: need True or False, got {fuse!r}")
+    return _lib.AMGX_MULTI_FUSE if fuse else 0
+
+
 def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V", clev="inv", device=0,
                    use_graph=True, cheb_degree=2, cheb_ratio=10, cheb_lambda_max=None, mat_prec="double"):
     """amgx_hierarchy_desc over the host arrays of a hierarchy.  Returns (desc, keep): `keep` holds everything the
@@ -450,20 +457,35 @@ class DeviceAMGMatrix:
             f |= _lib.AMGX_NO_GRAPH
         return f
 
-    def MultMulti(self, B, X, interleaved=False, graph=True):
+    def MultMulti(self, B, X, interleaved=False, graph=True, fuse=False):
         """X[j] = C B[j] for k = 1 .. 8 right-hand sides: 2-D float64 arrays / CUDA tensors of shape (k, n), or (n, k) with
-        interleaved=True.  Handles that qualify (multi_info) read every level matrix once per group of 2, 4 or 8 columns."""
+        interleaved=True.  Handles that qualify (multi_info) read every level matrix once per group of 2, 4 or 8 columns.
+        fuse=True (AMGX_MULTI_FUSE): the wider rule of multi_plan(k, fuse=True) -- Chebyshev and block levels run fused too."""
+        ff = check_fuse(fuse)
         n = self.sizes[0]
         k, (ab, ax), (lb, lx), dev = check_multi((B, X), (n, n), interleaved, ("B", "X"))
-        self._ck(self._lib.amgx_apply_multi(self._h, k, ab, lb, ax, lx, 0, self._multi_flags(dev, interleaved, graph)))
+        self._ck(self._lib.amgx_apply_multi(self._h, k, ab, lb, ax, lx, 0, self._multi_flags(dev, interleaved, graph) | ff))
         return X
 
-    def MatVecMulti(self, level, X, Y, interleaved=False):
+    def MatVecMulti(self, level, X, Y, interleaved=False, fuse=False):
         """Y[j] = A_level X[j]"""
+        ff = check_fuse(fuse)
         n = self._size(level)
         k, (ax, ay), (lx, ly), dev = check_multi((X, Y), (self.ext_sizes[level], n), interleaved, ("X", "Y"))
-        self._ck(self._lib.amgx_matvec_multi(self._h, int(level), k, ax, lx, ay, ly, self._multi_flags(dev, interleaved)))
+        self._ck(self._lib.amgx_matvec_multi(self._h, int(level), k, ax, lx, ay, ly, self._multi_flags(dev, interleaved) | ff))
         return Y
+
+    def multi_plan(self, k, fuse=False):
+        """multi_info for a call that carries fuse=, plus "note": the first reason why the handle is not fused ("" when it is)"""
+        ff = check_fuse(fuse)
+        if not (1 <= int(k) <= _lib.AMGX_MULTI_MAX):
+            raise NgsAMGError(f"multi_plan: k = {k}, need 1 .. {_lib.AMGX_MULTI_MAX}")
+        fused, ng, wb = C.c_int32(), C.c_int32(), C.c_int64()
+        wd = (C.c_int32 * _lib.AMGX_MULTI_MAX)()
+        self._ck(self._lib.amgx_multi_plan(self._h, int(k), ff, C.byref(fused), C.byref(ng), wd, C.byref(wb)))
+        note = self._lib.amgx_multi_note(self._h, ff) or b""
+        return {"fused": int(fused.value), "groups": [int(wd[i]) for i in range(ng.value)], "work_bytes": int(wb.value),
+                "note": note.decode()}
 
     def multi_info(self, k):
         """how a multi-vector call with k columns runs: fused (True: the multi-vector kernels; False: a column loop over the

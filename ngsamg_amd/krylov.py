@@ -122,14 +122,15 @@ class NativeCGSolver(_NativeSolver):
     def Solve(self, rhs, sol=None):
         return self._run(self.mat._lib.amgx_pcg, rhs, sol, ())
 
-    def SolveMulti(self, rhs, sol=None, interleaved=False):
+    def SolveMulti(self, rhs, sol=None, interleaved=False, fuse=False):
         """k right-hand sides at once (amgx_pcg_multi): k independent recurrences that share the level-0 product and the
         preconditioner application.  rhs / sol: 2-D float64 arrays or CUDA tensors, shape (k, n) or, interleaved, (n, k); sol holds
         the initial guesses (default 0).  Afterwards `iterations` is a list of k counts and `errors` a list of k histories; a column
-        that converged is frozen while the others go on."""
+        that converged is frozen while the others go on.  fuse=True: AMGX_MULTI_FUSE for the product and the preconditioner."""
         import ctypes as C
         import numpy as np
-        from .device import _is_torch, check_multi
+        from .device import _is_torch, check_fuse, check_multi
+        ff = check_fuse(fuse)
         n = self.mat.sizes[0]
         if sol is None:
             if _is_torch(rhs):
@@ -141,7 +142,7 @@ class NativeCGSolver(_NativeSolver):
         errs = np.zeros((k, self.maxsteps + 1))
         its = np.zeros(k, dtype=np.int32)
         self.mat._ck(self.mat._lib.amgx_pcg_multi(self.mat._h, k, ab, lb, ax, lx, float(self.tol), int(self.maxsteps), int(self.use_pre),
-                                                  self.mat._multi_flags(dev, interleaved), errs.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  self.mat._multi_flags(dev, interleaved) | ff, errs.ctypes.data_as(C.POINTER(C.c_double)),
                                                   its.ctypes.data_as(C.POINTER(C.c_int32))))
         self.iterations = [int(v) for v in its]
         self.errors = [errs[j, : its[j] + 1].tolist() for j in range(k)]

@@ -2,6 +2,7 @@
 """k right-hand sides: k single-vector calls against one multi-vector call, same handle, same process, alternating.
 
     python tools/bench_multi_rhs.py [nv] [--k 1,2,4,8] [--rounds 5] [--reps 30] [--pcg-reps 30] [--out FILE] [--commit ID]
+                                    [--smoother jacobi|cheby] [--degree D] [--config cfg2|cfg3|cfg5]
 
 Builds the cfg-2 hierarchy as tools/ab_cycle.py does (fem.poisson_fast((nv,)*3), nv = 215, Jacobi) and times, with device vectors and
 graph replay on one stream, per k and per round
@@ -9,7 +10,11 @@ graph replay on one stream, per k and per round
   (b') the same with column-major arguments (one transposition in, one out)
 and the same for amgx_pcg x k against amgx_pcg_multi (tol 1e-8).  Cross-run numbers differ by several per cent between boxes and
 processes, so the only yardstick is (a) of the same round.  Before any time is printed every column of (b) is compared
-with (a): 1e-12 relative for the cycle, 1e-8 for the PCG solutions.  Needs a GPU."""
+with (a): 1e-12 relative for the cycle, 1e-8 for the PCG solutions.  Needs a GPU.
+
+--smoother cheby (with --degree) and --config cfg3 | cfg5 (elasticity without / with rotations, nv = 126, built as tools/bench_cheby.py
+does) select handles that are fused only under AMGX_MULTI_FUSE: (b), (b') and the multi-vector PCG then carry
+fuse=True, (a) stays k calls of amgx_apply / amgx_pcg on the same handle; the result goes to profiles/r14/."""
 import argparse
 import json
 import os
@@ -34,13 +39,16 @@ def _stats(ts):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("nv", nargs="?", type=int, default=215)
+    ap.add_argument("nv", nargs="?", type=int, default=None)
+    ap.add_argument("--smoother", default="jacobi", choices=["jacobi", "cheby"])
+    ap.add_argument("--degree", type=int, default=2, help="Chebyshev degree")
+    ap.add_argument("--config", default="cfg2", choices=["cfg2", "cfg3", "cfg5"])
     ap.add_argument("--k", default="1,2,4,8")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--pcg-reps", type=int, default=30)
     ap.add_argument("--no-pcg", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06", "multi_rhs.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None)
     ap.add_argument("--cycle-only-k", type=int, default=0, help="run nothing but REPS multi-vector cycles of this width (for a kernel trace)")
     args = ap.parse_args()
@@ -52,15 +60,27 @@ def main():
     from ngsamg_amd.hierarchy import Hierarchy
     from ngsamg_amd.device import DeviceAMGMatrix
     from ngsamg_amd.krylov import NativeCGSolver
-    nv = args.nv
+    nv = args.nv or (215 if args.config == "cfg2" else 126)
     ks = [int(v) for v in args.k.split(",")]
-    p = fem.poisson_fast((nv, nv, nv))
-    H = Hierarchy(Matrix(p.n, p.n, 1, 1, p.rowptr, p.col, p.val), p.free, p.coords, dim=3, energy=0, max_coarse_size=50)
+    fuse = args.smoother != "jacobi" or args.config != "cfg2"      # handles that are fused only under AMGX_MULTI_FUSE
+    tag = f"{args.config}_{args.smoother}" + (str(args.degree) if args.smoother == "cheby" else "")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r14", f"multi_fuse_{tag}.json") if fuse else os.path.join(ROOT, "profiles", "r06", "multi_rhs.json")
+    if args.config == "cfg2":
+        p = fem.poisson_fast((nv, nv, nv))
+        H = Hierarchy(Matrix(p.n, p.n, 1, 1, p.rowptr, p.col, p.val), p.free, p.coords, dim=3, energy=0, max_coarse_size=50)
+    else:
+        rot = args.config == "cfg5"
+        p = fem.elasticity_fast((nv, nv, nv), dirichlet="left", mu=1.0, lam=0.5, rotations=rot)
+        H = Hierarchy(Matrix(p.n, p.n, p.bs, p.bs, p.rowptr, p.col, p.val), p.free, p.coords, dim=3, energy=1, max_coarse_size=50,
+                      regularize_cmats=0 if rot else 1, spw=1)
+    kw = dict(sm_type="cheby", cheb_degree=args.degree) if args.smoother == "cheby" else dict(sm_type="jacobi")
     free0, _ = torch.cuda.mem_get_info()
-    dev = DeviceAMGMatrix(H, sm_type="jacobi", device=0)
+    dev = DeviceAMGMatrix(H, device=0, **kw)
     torch.cuda.synchronize()
     free1, _ = torch.cuda.mem_get_info()
-    n = p.n
+    n = p.n * p.bs
+    pfree = np.repeat(p.free, p.bs).astype(np.float64)
     rng = np.random.default_rng(0)
     stream = torch.cuda.Stream()                               # (the legacy default stream cannot be captured into a graph)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -76,18 +96,19 @@ def main():
 
     if args.cycle_only_k:
         k = args.cycle_only_k
-        Bi = torch.from_numpy(rng.standard_normal((n, k)) * p.free[:, None]).cuda()
+        Bi = torch.from_numpy(rng.standard_normal((n, k)) * pfree[:, None]).cuda()
         Xi = torch.empty_like(Bi)
         torch.cuda.synchronize()
-        print("ms per multi cycle:", timed(lambda: dev.MultMulti(Bi, Xi, interleaved=True), args.reps))
+        print("ms per multi cycle:", timed(lambda: dev.MultMulti(Bi, Xi, interleaved=True, fuse=fuse), args.reps))
         return
 
-    out = {"commit": args.commit or _commit(), "nv": nv, "n": int(n), "levels": H.n_levels, "cycle_info": dev.cycle_info(),
+    out = {"commit": args.commit or _commit(), "config": args.config, "smoother": args.smoother, "degree": args.degree if args.smoother == "cheby" else 0,
+           "fuse": fuse, "nv": nv, "n": int(n), "levels": H.n_levels, "cycle_info": dev.cycle_info(),
            "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps, "pcg_reps": args.pcg_reps,
            "handle_bytes": int(free0 - free1), "k": {}}
     for k in ks:
-        info = dev.multi_info(k)
-        B = rng.standard_normal((k, n)) * p.free
+        info = dev.multi_plan(k, fuse=fuse)
+        B = rng.standard_normal((k, n)) * pfree
         bs = [torch.from_numpy(np.ascontiguousarray(B[j])).cuda() for j in range(k)]
         xs = [torch.empty_like(b) for b in bs]
         Bi = torch.from_numpy(np.ascontiguousarray(B.T)).cuda()
@@ -101,10 +122,10 @@ def main():
                 dev.Mult(bs[j], xs[j])
 
         def b():
-            dev.MultMulti(Bi, Xi, interleaved=True)
+            dev.MultMulti(Bi, Xi, interleaved=True, fuse=fuse)
 
         def c():
-            dev.MultMulti(Bc, Xc)
+            dev.MultMulti(Bc, Xc, fuse=fuse)
 
         m0, _ = torch.cuda.mem_get_info()
         for fn in (a, b, c):                                    # warm-up: captures the graphs, allocates the work space
@@ -142,7 +163,7 @@ def main():
 
             def pb():
                 Xi.zero_()
-                cg.SolveMulti(Bi, Xi, interleaved=True)
+                cg.SolveMulti(Bi, Xi, interleaved=True, fuse=fuse)
 
             with torch.cuda.stream(stream):
                 pa()
