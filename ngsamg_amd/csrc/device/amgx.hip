@@ -9,8 +9,10 @@
 // of kernel launches on one HIP stream, captured once per (b, x) pair into a hipGraph and replayed.
 #include "../../../include/amgx.h"
 #include "kernels.hpp"
+#include "multi_kernels.hpp"   // the NV = 2, 4 forms of the product kernels (Handle::product)
+#include "cheb_schedule.hpp"   // the Chebyshev recurrence as a schedule of first / step calls
 #include "knobs.hpp"
-#include "launch.hpp"          // Err, HIPCHK, dispatch, launch
+#include "launch.hpp"          // Err, HIPCHK, IntList, dispatch, contains, launch
 #include "graph_cache.hpp"     // GraphCache
 #include "../host/dia.hpp"
 #include <dlfcn.h>
@@ -146,7 +148,7 @@ struct DevMatrix {
   } bsell;
   // single-precision image (A of a Chebyshev level with mat_prec = AMGX_PREC_F32, plain SELL or BSELL only): the
   // value array of the format above rounded to float, same layout, every index array shared.  Built by mat_f32_image
-  // (build_level.hpp); read by the smoother passes of spmv_ep and by the fused residual + restriction, by nothing else.
+  // (build_level.hpp); read by the smoother passes of Handle::product and by the fused residual + restriction, by nothing else.
   DevBuf<float> val32;
   bool has32() const { return val32.p != nullptr; }
   int64_t stream_bytes32() const { return stream_bytes - 4 * (int64_t)val32.n; }
@@ -267,7 +269,7 @@ static BgsShape bgs_block_shape(double avg, int max_m) {
   const int TH = G != 4 ? 1024 : (max_m * G <= 256 ? 256 : (max_m * G <= 512 ? 512 : 1024));
   return BgsShape{TH, G};
 }
-// the kernel spmv_ep launches on a matrix in the block CSR format (blocks other than 1 x 1, no BSELL / rigid-body image);
+// the kernel Handle::product<1, EP> launches on a matrix in the block CSR format (blocks other than 1 x 1, no BSELL / rigid-body image);
 // amgx_level_paths reports the same value.  rowlane: bcsr_rowlane_kernel with `width` = W lane groups per block row, chosen from
 // the average row length; otherwise bcsrvec_spmv_kernel with `width` = G lanes per block row (DevMatrix::lanes within 2 .. 16).
 // Short rectangular rows, i.e. prolongations with <= 4 blocks per row, stay with the lane-per-block kernel (measured), and so
@@ -1331,7 +1333,7 @@ static bool build_sell_lw_windowed(const Knobs& K, int64_t n, int64_t n_cols, co
 // ---------------------------------------------------------------------------------------------------
 
 enum { PART_ALL = 0, PART_INT = 1, PART_BND = 2 };
-struct Span { int part = PART_ALL; int64_t n_int = 0; };   // see Handle::spmv_ep
+struct Span { int part = PART_ALL; int64_t n_int = 0; };   // see Handle::product
 struct MultiState;                      // multi-vector work space and captured graphs (multi.hpp)
 void multi_drop_graphs(MultiState* s);
 void multi_free(MultiState* s);
@@ -1409,127 +1411,165 @@ struct Handle {
     else { a = split; b = n_units; }
   }
 
+  // ------------------------------------------------------------------ the product launcher
+  // The value lists of the product kernels, each written once: product() dispatches on them and the multi-vector path asks them
+  // whether a kernel exists (multi_*_ok), so a shape cannot be in one place and not in the other.  Shapes: key = 10 * br + bc.
+  using SquareShapes = IntList<22, 33, 66>;                                             // EP_JAC / EP_CHEB: square blocks only
+  using RowlaneShapes = IntList<22, 33, 66, 36, 63, 23, 32>;                            // bcsr_rowlane_kernel, bcsr_spmm_kernel
+  using BcsrVecShapes = IntList<22, 33, 66, 36, 63, 23, 32, 13, 31, 16, 61, 12, 21>;    // bcsrvec_spmv_kernel
+  using BsellSizes = IntList<6, 3, 2>;
+  using SellLanes = IntList<1, 2, 4, 8>;          // any other lane count: the 16-lane kernel
+  using CsrLanes = IntList<2, 4, 8, 16, 32>;      // any other lane count: one wave per row
+
+  // what product<NV > 1> serves: scalar SELL / CSR-vector; block CSR (`square`: under EP_JAC / EP_CHEB); level matrices; transfers
+  static bool multi_scalar_ok(const DevMatrix& M) { return M.br == 1 && M.bc == 1 && (M.fmt == FMT_SELL || M.fmt == FMT_CSRVEC); }
+  static bool multi_bcsr_ok(const DevMatrix& M, bool square) {
+    const int key = M.br * 10 + M.bc;
+    return M.fmt == FMT_CSRVEC && (square ? contains(SquareShapes{}, key) : contains(RowlaneShapes{}, key));
+  }
+  static bool multi_level_ok(const DevMatrix& M) {
+    if (M.br != M.bc) return false;
+    if (M.br == 1) return multi_scalar_ok(M);
+    return M.fmt == FMT_BSELL ? contains(BsellSizes{}, M.br) : multi_bcsr_ok(M, true);
+  }
+  static bool multi_transfer_ok(const DevMatrix& M) { return M.fmt == FMT_RB || (M.br == 1 && M.bc == 1 ? multi_scalar_ok(M) : multi_bcsr_ok(M, false)); }
+
+  // rigid-body transfer blocks: (fine block, coarse block, dimension of Q) = 663, 363, 332, 232, else 220
+  template <class F>
+  static void rb_shape(const DevMatrix::Rb& R, F&& run) {
+    if (R.dim == 3 && R.bf == 6) run(Int<6>{}, Int<6>{}, Int<3>{});
+    else if (R.dim == 3) run(Int<3>{}, Int<6>{}, Int<3>{});
+    else if (R.dim == 2 && R.bf == 3) run(Int<3>{}, Int<3>{}, Int<2>{});
+    else if (R.dim == 2) run(Int<2>{}, Int<3>{}, Int<2>{});
+    else run(Int<2>{}, Int<2>{}, Int<0>{});
+  }
+  // workgroups of the kernels that give every block row of br scalar rows W lane groups
+  static int rowlane_grid(int64_t n_rows, int br, int W) {
+    const int rpw = WAVE / (br * W);
+    const int64_t waves = (n_rows + rpw - 1) / rpw;
+    return (int)std::max<int64_t>(1, (waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+  }
+
+  // y = EP(M x) on NV vectors: NV == 1 the single-vector kernels (kernels.hpp), NV == 2, 4 their forms on interleaved vectors
+  // (multi_kernels.hpp).  One branch per format; in it the unit of the row split, the grid and the value list are written once.
   // sm_pass: a product the smoother or the cycle launches on a level (EP_CHEB steps, the residual after smoothing).  It reads the
   // single-precision image where amgx_create gave the level one (DevMatrix::has32); every other caller reads the fp64 image.
-  template <int EP>
-  void spmv_ep(const DevMatrix& M, const double* x, double* y, const EpArgs& ep, const Span sp = Span(), bool sm_pass = false) {
+  template <int NV, int EP>
+  void product(const DevMatrix& M, const double* x, double* y, const EpArgs& ep, const Span sp = Span(), bool sm_pass = false) {
+    static_assert(NV == 1 || (EP != EP_PRE && EP != EP_CRES), "EP_PRE and EP_CRES are built for single vectors only");
     if (M.n_rows == 0) return;
-    if constexpr (EP == EP_RES || EP == EP_CHEB) {
-      if (sm_pass && M.has32()) { spmv_ep32<EP>(M, x, y, ep, sp); return; }
-    }
+    if (NV > 1 && sp.part != PART_ALL) throw Err("multi-vector product: rank-partitioned levels are not supported");
+    // the float image exists for non-windowed SELL and BSELL, under EP_RES / EP_CHEB
+    constexpr bool EP32 = EP == EP_RES || EP == EP_CHEB;
+    const bool f32 = EP32 && sm_pass && M.has32();
+    if (f32 && !((M.fmt == FMT_SELL && !M.sell.win) || M.fmt == FMT_BSELL)) throw Err("single-precision image on a format that has none");
+    auto image = [&](const auto& v64, const auto& v32, auto&& run) {          // run(view of the image this product reads)
+      if constexpr (EP32) { if (f32) { run(v32); return; } }
+      run(v64);
+    };
+    int64_t a, b;                                     // the units [a, b) of the row split that this launch covers
     if (M.fmt == FMT_RB) {
       if constexpr (EP != EP_MULT && EP != EP_AXPY) throw Err("rigid-body transfer blocks: y = M x and y = yin + s M x only");
       else {
         if (sp.part == PART_INT) return;             // (not split: everything runs in the boundary part)
         const DevMatrix::Rb& R = M.rb;
         const RbMat V = R.view();
-        // (fine block, coarse block, dimension of Q) = 663, 363, 332, 232, else 220
-        auto run = [&](auto BF, auto BC, auto DM) {
-          constexpr int G = 16;
-          if (!R.transposed) launch(rb_prolong_kernel<BF(), BC(), DM(), EP>, grid_for(M.n_rows), BLOCK, 0, stream, M.n_rows, V, x, y, ep);
-          else launch(rb_restrict_kernel<BF(), BC(), DM(), G, EP>, grid_for(M.n_rows * G), BLOCK, 0, stream, M.n_rows, V, x, y, ep);
-        };
-        if (R.dim == 3 && R.bf == 6) run(Int<6>{}, Int<6>{}, Int<3>{});
-        else if (R.dim == 3) run(Int<3>{}, Int<6>{}, Int<3>{});
-        else if (R.dim == 2 && R.bf == 3) run(Int<3>{}, Int<3>{}, Int<2>{});
-        else if (R.dim == 2) run(Int<2>{}, Int<3>{}, Int<2>{});
-        else run(Int<2>{}, Int<2>{}, Int<0>{});
-        return;
+        rb_shape(R, [&](auto BF, auto BC, auto DM) {
+          constexpr int G = 16;                       // lanes per coarse row of the transposed form
+          if constexpr (NV == 1) {
+            if (!R.transposed) launch(rb_prolong_kernel<BF(), BC(), DM(), EP>, grid_for(M.n_rows), BLOCK, 0, stream, M.n_rows, V, x, y, ep);
+            else launch(rb_restrict_kernel<BF(), BC(), DM(), G, EP>, grid_for(M.n_rows * G), BLOCK, 0, stream, M.n_rows, V, x, y, ep);
+          } else {
+            if (!R.transposed) launch(rb_prolong_nv_kernel<BF(), BC(), DM(), NV, EP>, grid_for(M.n_rows), BLOCK, 0, stream, M.n_rows, V, x, y, ep);
+            else launch(rb_restrict_nv_kernel<BF(), BC(), DM(), G, NV, EP>, grid_for(M.n_rows * G), BLOCK, 0, stream, M.n_rows, V, x, y, ep);
+          }
+        });
       }
-    }
-    if (M.fmt == FMT_SELL && M.sell.win) {
+    } else if (M.fmt == FMT_SELL && M.sell.win) {
       if (M.sell.win != SELL_WIN) throw Err("windowed SELL: unexpected window size");
-      int64_t a, b;
       unit_range(sp, SELL_WIN, (M.n_rows + SELL_WIN - 1) / SELL_WIN, a, b);
-      if (b > a)
-        launch(sell_win_spmv_kernel<SELL_WIN, EP>, (int)(b - a), SELL_WIN, 0, stream, M.n_rows, (int)a, M.sell.view(), M.sell.rowloc.p, x, y, ep);
+      if (b <= a) return;
+      if constexpr (NV == 1) launch(sell_win_spmv_kernel<SELL_WIN, EP>, (int)(b - a), SELL_WIN, 0, stream, M.n_rows, (int)a, M.sell.view(), M.sell.rowloc.p, x, y, ep);
+      else launch(sell_win_spmm_kernel<SELL_WIN, NV, EP>, (int)(b - a), SELL_WIN, 0, stream, M.n_rows, M.sell.view(), M.sell.rowloc.p, x, y, ep);
     } else if (M.fmt == FMT_SELL) {
-      int64_t a, b;
       unit_range(sp, WAVE / M.lanes, M.n_slices, a, b);
       if (b <= a) return;
       const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-      auto run = [&](auto G) { launch(sell_spmv_kernel<G(), EP>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, M.sell.view(), x, y, ep); };
-      if (!dispatch<1, 2, 4, 8>(M.lanes, run)) run(Int<16>{});       // any other lane count: the 16-lane kernel
+      image(M.sell.view(), M.sell.view32(M.val32.p), [&](auto V) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(V.val)>>;       // double / float
+        auto run = [&](auto G) {
+          if constexpr (NV == 1) launch(sell_spmv_kernel<G(), EP, T>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep);
+          else launch(sell_spmm_kernel<G(), NV, EP, T>, grid, BLOCK, 0, stream, M.n_rows, M.n_slices, V, x, y, ep);
+        };
+        if (!dispatch(SellLanes{}, M.lanes, run)) run(Int<16>{});
+      });
     } else if (M.br == 1 && M.bc == 1) {
-      int64_t a, b;
       unit_range(sp, 1, M.n_rows, a, b);
       if (b <= a) return;
       const int grid = grid_for((b - a) * M.lanes);
-      auto run = [&](auto G) { launch(csrvec_spmv_kernel<G(), EP>, grid, BLOCK, 0, stream, a, b, M.rowptr.p, M.col.p, M.val.p, x, y, ep); };
-      if (!dispatch<2, 4, 8, 16, 32>(M.lanes, run)) run(Int<64>{});  // any other lane count: one wave per row
+      auto run = [&](auto G) {
+        if constexpr (NV == 1) launch(csrvec_spmv_kernel<G(), EP>, grid, BLOCK, 0, stream, a, b, M.rowptr.p, M.col.p, M.val.p, x, y, ep);
+        else launch(csrvec_spmm_kernel<G(), NV, EP>, grid, BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep);
+      };
+      if (!dispatch(CsrLanes{}, M.lanes, run)) run(Int<64>{});
     } else if constexpr (EP == EP_PRE) {
       throw Err("EP_PRE is only built for scalar matrices");
     } else if (M.fmt == FMT_BSELL) {
       // units of RB = 64 / bs block rows (one slice); slices that straddle n_int belong to the boundary part
-      int64_t a, b;
       unit_range(sp, WAVE / M.br, M.n_slices, a, b);
       if (b <= a) return;
       const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-      auto run = [&](auto BS) { launch(bsell_spmv_kernel<BS(), EP>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, M.bsell.view(knobs.bsell_xmode), x, y, ep); };
-      if (!dispatch<6, 3>(M.br, run)) run(Int<2>{});                 // any other block size: the 2 x 2 kernel
+      const int xmode = NV == 1 ? knobs.bsell_xmode : 0;       // (the gather variants rearrange loads that the NV > 1 kernel does not have)
+      image(M.bsell.view(xmode), M.bsell.view32(M.val32.p, xmode), [&](auto V) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(V.val)>>;
+        auto run = [&](auto BS) {
+          if constexpr (NV == 1) launch(bsell_spmv_kernel<BS(), EP, T>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep);
+          else launch(bsell_spmm_kernel<BS(), NV, EP, T>, grid, BLOCK, 0, stream, M.n_rows, M.n_slices, V, x, y, ep);
+        };
+        if (dispatch(BsellSizes{}, M.br, run)) return;
+        if (NV > 1 || f32) throw Err("unsupported BSELL block size " + std::to_string(M.br));
+        run(Int<2>{});                                // single vector, fp64 image: any other block size takes the 2 x 2 kernel
+      });
     } else if (sp.part == PART_INT) {
-      return;                                   // the CSR block formats are not split: everything runs in the boundary part
-    } else if (const BcsrKernel bk = bcsr_kernel(M, EP == EP_JAC || EP == EP_CHEB); bk.rowlane) {
-      const int W = bk.width;
-      const int rpw = WAVE / (M.br * W);
-      const int64_t waves = (M.n_rows + rpw - 1) / rpw;
-      const int grid = (int)std::max<int64_t>(1, (waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-      // key = 10 * br + bc; EP_JAC / EP_CHEB are built for the square shapes only
-      auto run = [&](auto KEY) {
-        constexpr int BR = KEY() / 10, BC = KEY() % 10;
-        auto run_w = [&](auto WW) { launch(bcsr_rowlane_kernel<BR, BC, WW(), EP>, grid, BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep); };
-        if (!dispatch<4, 2>(W, run_w)) run_w(Int<1>{});
-      };
-      const int key = M.br * 10 + M.bc;
-      if constexpr (EP == EP_JAC || EP == EP_CHEB) {
-        if (!dispatch<22, 33, 66>(key, run)) throw Err("unsupported block shape");
-      } else {
-        if (!dispatch<22, 33, 66, 36, 63, 23, 32>(key, run)) throw Err("unsupported block shape " + std::to_string(M.br) + "x" + std::to_string(M.bc));
-      }
+      return;                                         // the CSR block formats are not split: everything runs in the boundary part
     } else {
-      const int G = bk.width;
-      const int grid = grid_for(M.n_rows * G);
-      auto run = [&](auto KEY) {                                     // key = 10 * br + bc
-        constexpr int BR = KEY() / 10, BC = KEY() % 10;
-        auto run_g = [&](auto GG) { launch(bcsrvec_spmv_kernel<BR, BC, GG(), EP>, grid, BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep); };
-        if (!dispatch<2, 4, 8>(G, run_g)) run_g(Int<16>{});
-      };
-      if (!dispatch<22, 33, 66, 36, 63, 23, 32, 13, 31, 16, 61, 12, 21>(M.br * 10 + M.bc, run))
-        throw Err("unsupported block shape " + std::to_string(M.br) + "x" + std::to_string(M.bc));
+      // NV == 1: bcsr_kernel() chooses between the row-lane and the vector form; NV > 1: ONE kernel, W = 4 lane groups per block row
+      constexpr bool SQ = EP == EP_JAC || EP == EP_CHEB;
+      const BcsrKernel bk = NV == 1 ? bcsr_kernel(M, SQ) : BcsrKernel{true, 4};
+      const int key = M.br * 10 + M.bc;
+      bool ok = true;
+      if (bk.rowlane) {
+        auto run = [&](auto KEY) {
+          constexpr int BR = KEY() / 10, BC = KEY() % 10;
+          if constexpr (NV == 1) {
+            auto run_w = [&](auto W) { launch(bcsr_rowlane_kernel<BR, BC, W(), EP>, rowlane_grid(M.n_rows, BR, W()), BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep); };
+            if (!dispatch<4, 2>(bk.width, run_w)) run_w(Int<1>{});
+          } else launch(bcsr_spmm_kernel<BR, BC, NV, EP, 4>, rowlane_grid(M.n_rows, BR, 4), BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep);
+        };
+        ok = dispatch(std::conditional_t<SQ, SquareShapes, RowlaneShapes>{}, key, run);
+      } else if constexpr (NV == 1) {
+        const int grid = grid_for(M.n_rows * bk.width);
+        auto run = [&](auto KEY) {
+          constexpr int BR = KEY() / 10, BC = KEY() % 10;
+          auto run_g = [&](auto G) { launch(bcsrvec_spmv_kernel<BR, BC, G(), EP>, grid, BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep); };
+          if (!dispatch<2, 4, 8>(bk.width, run_g)) run_g(Int<16>{});
+        };
+        ok = dispatch(BcsrVecShapes{}, key, run);
+      }
+      if (!ok) throw Err("unsupported block shape " + std::to_string(M.br) + "x" + std::to_string(M.bc));
     }
   }
 
-  // the smoother passes on the single-precision image: the float instantiations of the two kernel families that carry one
-  template <int EP>
-  void spmv_ep32(const DevMatrix& M, const double* x, double* y, const EpArgs& ep, const Span sp) {
-    if (M.fmt == FMT_SELL && !M.sell.win) {
-      int64_t a, b;
-      unit_range(sp, WAVE / M.lanes, M.n_slices, a, b);
-      if (b <= a) return;
-      const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-      auto run = [&](auto G) { launch(sell_spmv_kernel<G(), EP, float>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, M.sell.view32(M.val32.p), x, y, ep); };
-      if (!dispatch<1, 2, 4, 8>(M.lanes, run)) run(Int<16>{});       // any other lane count: the 16-lane kernel
-    } else if (M.fmt == FMT_BSELL) {
-      int64_t a, b;
-      unit_range(sp, WAVE / M.br, M.n_slices, a, b);
-      if (b <= a) return;
-      const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-      const BSellMatT<float> V = M.bsell.view32(M.val32.p, knobs.bsell_xmode);
-      auto run = [&](auto BS) { launch(bsell_spmv_kernel<BS(), EP, float>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep); };
-      if (!dispatch<6, 3, 2>(M.br, run)) throw Err("single-precision image: unsupported block size");
-    } else throw Err("single-precision image on a format that has none");
-  }
-
-  void mult(const DevMatrix& M, const double* x, double* y, const Span sp = Span()) { spmv_ep<EP_MULT>(M, x, y, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}, sp); }
-  void residual(const DevMatrix& M, const double* x, const double* b, double* r, const Span sp = Span()) { spmv_ep<EP_RES>(M, x, r, EpArgs{b, nullptr, nullptr, 0.0, nullptr, ep_nt & EPF_HOIST}, sp); }
+  void mult(const DevMatrix& M, const double* x, double* y, const Span sp = Span()) { product<1, EP_MULT>(M, x, y, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}, sp); }
+  void residual(const DevMatrix& M, const double* x, const double* b, double* r, const Span sp = Span()) { product<1, EP_RES>(M, x, r, EpArgs{b, nullptr, nullptr, 0.0, nullptr, ep_nt & EPF_HOIST}, sp); }
   // the residual a smoother or the cycle forms on its level (update_res, the residual before the restriction): a smoother pass
-  void residual_sm(const DevLevel& L, const double* x, const double* b, double* r) { spmv_ep<EP_RES>(L.A, x, r, EpArgs{b, nullptr, nullptr, 0.0, nullptr, ep_nt & EPF_HOIST}, Span(), true); }
+  void residual_sm(const DevLevel& L, const double* x, const double* b, double* r) { product<1, EP_RES>(L.A, x, r, EpArgs{b, nullptr, nullptr, 0.0, nullptr, ep_nt & EPF_HOIST}, Span(), true); }
   // y = yin + s * M x
-  void mult_add(const DevMatrix& M, double s, const double* x, const double* yin, double* y, const Span sp = Span()) { spmv_ep<EP_AXPY>(M, x, y, EpArgs{nullptr, yin, nullptr, s, nullptr, ep_nt & EPF_HOIST}, sp); }
+  void mult_add(const DevMatrix& M, double s, const double* x, const double* yin, double* y, const Span sp = Span()) { product<1, EP_AXPY>(M, x, y, EpArgs{nullptr, yin, nullptr, s, nullptr, ep_nt & EPF_HOIST}, sp); }
   // xout = xin + omega * dinv * (b - A xin)
   void jacobi_fused(const DevLevel& L, const double* xin, const double* b, double* xout, const Span sp = Span()) {
     if (xin == xout) throw Err("jacobi_fused: in-place update is not allowed");
-    spmv_ep<EP_JAC>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, L.omega, nullptr, ep_nt}, sp);
+    product<1, EP_JAC>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, L.omega, nullptr, ep_nt}, sp);
   }
 
   // ---- Chebyshev smoother (AMGX_SM_CHEBY) ----
@@ -1543,38 +1583,21 @@ struct Handle {
   // one fused step: xout = xin + d_new, d_new = c1 * d_old + c2 * Dinv * (b - A xin); d_old == nullptr: xin; d_new == nullptr: not stored
   void cheb_step(const DevLevel& L, const double* xin, const double* b, double* xout, double c1, double c2, const double* d_old, double* d_new) {
     if (xin == xout) throw Err("cheb_step: in-place update is not allowed");
-    spmv_ep<EP_CHEB>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, c2, d_new, ep_nt, d_old, c1}, Span(), true);
+    product<1, EP_CHEB>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, c2, d_new, ep_nt, d_old, c1}, Span(), true);
   }
   // One Chebyshev smooth of degree k with the flag contract of base_smooth.  The iterate lives in `src` (x itself or L.tmp, ignored
-  // with x_zero) and ends in x; the fused steps are out of place and ping-pong between x and L.tmp, so a caller that can choose
-  // (post_smooth) puts the iterate where an even number of passes is left; otherwise one copy moves the result.
-  int cheb_passes(const DevLevel& L, bool res_updated, bool x_zero) const { return L.cheb_degree - 1 + ((!res_updated && !x_zero) ? 1 : 0); }
+  // with x_zero) and ends in x; the passes and their operands are cheb_schedule's (cheb_schedule.hpp).  A caller that can choose
+  // (post_smooth) puts the iterate at cheb_place(); otherwise one copy moves the result.
   void cheb_smooth(DevLevel& L, const double* src, double* x, const double* b, double* res, bool res_updated, bool update_res, bool x_zero) {
     const int k = L.cheb_degree;
     if (k < 1 || !L.d.p) throw Err("Chebyshev smoother: the level has no coefficients");
     if (L.ncols != L.n) throw Err("Chebyshev smoother: rank-partitioned levels are not supported");
     double* const tmp = L.tmp.p;
     if (!x_zero && src != x && src != tmp) throw Err("Chebyshev smoother: the iterate must live in x or in the level's ping-pong buffer");
-    const double* cur;
-    const double* dcur = L.d.p;           // where d of the previous step lives (nullptr: in the iterate itself)
-    int j = 2;                            // next step of the recurrence
-    if (res_updated || x_zero) {
-      double* t0 = ((k - 1) & 1) ? tmp : x;
-      // (from zero: d == x afterwards, nothing stored; otherwise d is stored when another step follows)
-      cheb_first(L, (res_updated ? res : b), x_zero ? nullptr : src, t0, (!x_zero && k > 1) ? L.d.p : nullptr, L.cheb_c0);
-      if (x_zero) dcur = nullptr;
-      cur = t0;
-    } else {
-      double* t0 = src == x ? tmp : x;
-      cheb_step(L, src, b, t0, 0.0, L.cheb_c0, nullptr, k > 1 ? L.d.p : nullptr);
-      cur = t0;
-    }
-    for (; j <= k; ++j) {
-      double* nxt = cur == x ? tmp : x;
-      cheb_step(L, cur, b, nxt, L.cheb_c1[j], L.cheb_c2[j], dcur, j < k ? L.d.p : nullptr);
-      dcur = L.d.p;
-      cur = nxt;
-    }
+    const ChebEntry entry = x_zero ? ChebEntry::ZERO : (res_updated ? ChebEntry::RES_UPDATED : ChebEntry::ITERATE);
+    auto first = [&](const double* v, const double* xin, double* xout, double* dout, double c0) { cheb_first(L, v, xin, xout, dout, c0); };
+    auto step = [&](const double* xin, double* xout, double c1, double c2, const double* d_old, double* d_new) { cheb_step(L, xin, b, xout, c1, c2, d_old, d_new); };
+    const double* cur = cheb_schedule(k, L.cheb_c0, L.cheb_c1, L.cheb_c2, entry, res_updated ? res : b, src, x, tmp, L.d.p, first, step);
     if (cur != x) copy(x, cur, L.len());
     if (update_res) residual_sm(L, x, b, res);
   }
@@ -1877,7 +1900,7 @@ struct Handle {
     const bool jacobi = P.plain && L.sm_type == AMGX_SM_JACOBI;
     if (jacobi && !L.Apre.empty()) {
       // one pass: r = b - A' b, x = omega * Dinv * b   (A' = A * omega*Dinv built at create time)
-      spmv_ep<EP_PRE>(L.Apre, b, r, EpArgs{b, nullptr, L.dinv.p, L.omega, x, ep_nt | (fold ? EPF_FOLD : 0)}, sp);
+      product<1, EP_PRE>(L.Apre, b, r, EpArgs{b, nullptr, L.dinv.p, L.omega, x, ep_nt | (fold ? EPF_FOLD : 0)}, sp);
     } else if (sp.part == PART_INT) {
       return;                                  // the other forms are not split: they run completely in the boundary part
     } else if (jacobi && L.ncols > L.n && !fold) {
@@ -1890,7 +1913,7 @@ struct Handle {
       if (fold && L.bs > 1) {
         // x_pre = omega * Dinv * b into tmp; then ONE pass: r = b - A x_pre and z = x_pre + omega * Dinv * r
         diag_apply(L, b, L.tmp.p, false);
-        spmv_ep<EP_JAC>(L.A, L.tmp.p, x, EpArgs{b, L.tmp.p, L.dinv.p, L.omega, r, ep_nt});
+        product<1, EP_JAC>(L.A, L.tmp.p, x, EpArgs{b, L.tmp.p, L.dinv.p, L.omega, r, ep_nt});
       } else {
         diag_apply(L, b, x, false);          // x = omega * Dinv * b      (x was zero, res == b)
         residual(L.A, x, b, r);              // r = b - A x
@@ -1918,7 +1941,7 @@ struct Handle {
       // r = b - A x = (1/dinv - a_kk) .* x - (A - L_in - D) x = c .* x - rest x
       if (L.gsb.has_split) {
         gsb_sweep(L, 0, L.gsb.lowin, nullptr, x, b);
-        spmv_ep<EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
+        product<1, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
       } else {
         gsb_sweep(L, 0, L.gsb.full, nullptr, x, b);
         residual(L.A, x, b, r);
@@ -2112,7 +2135,7 @@ struct Handle {
     if (!L.gsb.has_split) throw Err("gsb_residual_restrict: the level has no lower / rest split");
     const DevRestrict& R = L.RG;
     if (R.empty()) {
-      spmv_ep<EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
+      product<1, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
       transfer_f2c(l, r, b_coarse);
       return;
     }
@@ -2170,7 +2193,7 @@ struct Handle {
       jacobi_fused(L, L.tmp.p, b, x);      // x = tmp + omega * Dinv * (b - A tmp); res is not needed afterwards
     } else if (P.plain && L.sm_type == AMGX_SM_CHEBY) {
       // k out-of-place passes follow: x + P x_c goes where the last of them lands in x
-      double* t = (L.cheb_degree & 1) ? L.tmp.p : x;
+      double* t = cheb_place(cheb_passes(L.cheb_degree, ChebEntry::ITERATE), x, L.tmp.p);
       mult_add(L.P, 1.0, xc, x, t);
       cheb_smooth(L, t, x, b, r, false, false, false);
     } else if (P.plain && P.sweep == SWEEP_BGSB_BC) {

@@ -37,6 +37,7 @@ namespace amgx {
 constexpr int WAVE = 64;
 constexpr int BLOCK = 256;
 constexpr int WAVES_PER_BLOCK = BLOCK / WAVE;
+constexpr int KR_BLOCKS = 1024;              // partial sums per dot product (krylov.hpp, multi_kernels.hpp, dist.hpp)
 
 enum Epilogue : int {
   EP_MULT = 0,   // y = A x

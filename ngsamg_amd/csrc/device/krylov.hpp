@@ -10,8 +10,6 @@
 
 namespace amgx {
 
-constexpr int KR_BLOCKS = 1024;              // partial sums per dot product
-
 // partial[blockIdx.x + slot * KR_BLOCKS] = sum over this block's grid-stride share of a[i] * b[i]
 __global__ __launch_bounds__(BLOCK) void kr_dot_partial_kernel(int64_t n, const double* __restrict__ a, const double* __restrict__ b,
                                                                double* __restrict__ partial) {

@@ -18,6 +18,14 @@ bool dispatch(int value, F&& f) {
   return ((value == Vs ? (f(Int<Vs>{}), true) : false) || ...);
 }
 
+// a value list with a name: the same list then serves the dispatch and the question whether a kernel exists
+//   using SquareShapes = IntList<22, 33, 66>;     dispatch(SquareShapes{}, key, run)     contains(SquareShapes{}, key)
+template <int... Vs> struct IntList {};
+template <int... Vs, class F>
+bool dispatch(IntList<Vs...>, int value, F&& f) { return dispatch<Vs...>(value, static_cast<F&&>(f)); }
+template <int... Vs>
+constexpr bool contains(IntList<Vs...>, int value) { return ((value == Vs) || ...); }
+
 }  // namespace amgx
 
 #ifdef __HIPCC__

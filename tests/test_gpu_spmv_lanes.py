@@ -1,4 +1,4 @@
-"""The stand-alone SpMV family (Handle::spmv_ep, amgx.hip): every format x lane count the host rules can pick, with the choice
+"""The stand-alone SpMV family (Handle::product<1, EP>, amgx.hip): every format x lane count the host rules can pick, with the choice
 asserted from the device's own report (matrix_info: fmt, lanes; level_paths: 16-bit slices, bcsr_A / bcsr_P / bcsr_PT = the
 value of bcsr_kernel, the function the dispatcher calls) and the result against scipy in float64.  Synthetic matrices through
 the C ABI as in test_gpu_kernel_zoo.py, whose tolerances these are: 1e-13 for products and residuals, 1e-12 for the Jacobi stages.

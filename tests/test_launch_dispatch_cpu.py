@@ -1,6 +1,9 @@
 """The host part of ngsamg_amd/csrc/device/launch.hpp (dispatch<V0, V1, ...>(value, f)) compiled by a plain C++17 host compiler:
 every listed value reaches its own constant exactly once, an unlisted value returns false and calls nothing, and the written-out
-fallback form `if (!dispatch<...>(v, run)) run(Int<F>{})` reaches the fallback constant."""
+fallback form `if (!dispatch<...>(v, run)) run(Int<F>{})` reaches the fallback constant.  The named form -- IntList<...>,
+dispatch(list, value, f), contains(list, value) -- behaves the same, and contains() agrees with dispatch() on every value in -1 .. 70
+for the three block-shape lists of the product launcher (key = 10 * br + bc).  The host part of the file is all this program
+sees, so the lists are written out here as Handle (amgx.hip) names them."""
 import os
 import shutil
 import subprocess
@@ -48,6 +51,38 @@ int main() {
   }
   calls.clear();                             // an empty list matches nothing
   if (amgx::dispatch<>(1, run) || !calls.empty()) { std::printf("empty list matched\n"); ++bad; }
+  // ---- the named form
+  using Lanes = amgx::IntList<1, 2, 4, 8>;
+  for (int v : listed) {
+    calls.clear();
+    if (!amgx::dispatch(Lanes{}, v, run)) { std::printf("named list, listed value %d: returned false\n", v); ++bad; }
+    if (calls.size() != 1 || calls[v] != 1) { std::printf("named list, listed value %d: wrong calls\n", v); ++bad; }
+    if (!amgx::contains(Lanes{}, v)) { std::printf("contains: listed value %d is missing\n", v); ++bad; }
+  }
+  for (int v : unlisted) {
+    calls.clear();
+    if (amgx::dispatch(Lanes{}, v, run)) { std::printf("named list, unlisted value %d: returned true\n", v); ++bad; }
+    if (!calls.empty()) { std::printf("named list, unlisted value %d: something was called\n", v); ++bad; }
+    if (amgx::contains(Lanes{}, v)) { std::printf("contains: unlisted value %d\n", v); ++bad; }
+  }
+  calls.clear();
+  if (amgx::dispatch(amgx::IntList<>{}, 1, run) || !calls.empty() || amgx::contains(amgx::IntList<>{}, 1)) { std::printf("empty named list matched\n"); ++bad; }
+  static_assert(amgx::contains(amgx::IntList<22, 33, 66>{}, 33) && !amgx::contains(amgx::IntList<22, 33, 66>{}, 36), "contains is a constant expression");
+  auto agree = [&](auto list, int n_listed) {
+    int hits = 0;
+    for (int v = -1; v <= 70; ++v) {
+      calls.clear();
+      const bool d = amgx::dispatch(list, v, run);
+      if (d != amgx::contains(list, v)) { std::printf("contains and dispatch differ on %d\n", v); ++bad; }
+      if (d && (calls.size() != 1 || calls[v] != 1)) { std::printf("shape list, value %d: wrong calls\n", v); ++bad; }
+      if (!d && !calls.empty()) { std::printf("shape list, value %d: something was called\n", v); ++bad; }
+      hits += d;
+    }
+    if (hits != n_listed) { std::printf("shape list: %d values matched, %d listed\n", hits, n_listed); ++bad; }
+  };
+  agree(amgx::IntList<22, 33, 66>{}, 3);                                             // square shapes
+  agree(amgx::IntList<22, 33, 66, 36, 63, 23, 32>{}, 7);                             // row-lane / multi-vector kernels
+  agree(amgx::IntList<22, 33, 66, 36, 63, 23, 32, 13, 31, 16, 61, 12, 21>{}, 13);    // vector form
   std::printf("bad=%d\n", bad);
   return bad ? 1 : 0;
 }
