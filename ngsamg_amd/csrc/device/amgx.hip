@@ -11,6 +11,7 @@
 #include "kernels.hpp"
 #include "multi_kernels.hpp"   // the NV = 2, 4 forms of the product kernels (Handle::product)
 #include "cheb_schedule.hpp"   // the Chebyshev recurrence as a schedule of first / step calls
+#include "down_plan.hpp"       // DownPlan, the value lists of the fused down kernels, Span, unit_range
 #include "knobs.hpp"
 #include "launch.hpp"          // Err, HIPCHK, IntList, dispatch, contains, launch
 #include "graph_cache.hpp"     // GraphCache
@@ -356,6 +357,9 @@ struct LevelPaths {
 
 struct DevLevel {
   LevelPaths paths;
+  // the fused down launches (down_plan.hpp, Handle::down_launch): through RF -- Jacobi from zero, or the residual after Chebyshev --
+  // and through RG, the residual after a block-hybrid sweep (gsb_residual_restrict)
+  DownPlan plan_rf, plan_rg;
   DevCsr tA, tApre, tP, tPT;            // only on tail levels
   DevBuf<int32_t> t_rowlist, t_cptr, t_rowcolor;    // colour-major row list (and the colour of every row) of a Gauss-Seidel tail level
   DevRestrict R;
@@ -407,9 +411,58 @@ struct DevLevel {
   }
 };
 
-// The ONLY place where image presence becomes a path.  Precedence of the down kernels: local window before diagonal image before
-// SELL; of the sweeps: bgsb before gsb before multicolour.  Conditions on call-time arguments (the part of a split level, the fold
-// flag) stay with the callers.
+// the SELL image a fused down launch of `mode` reads (lw: its local-window form); the diagonal-image forms read L.dia
+static const DevMatrix& down_image(const DevLevel& L, int mode, bool lw) {
+  return mode == 2 ? L.A : mode == 1 ? (lw ? L.gsb.restLW : L.gsb.rest) : (lw ? L.ApreLW : L.Apre);
+}
+
+// The fused launch of `mode` through R: which image, which kernel instantiation, which chunks.  Everything the launch used to
+// re-check in every cycle is checked here, once: a failure means that amgx_create built data that do not fit together, or a shape
+// that no kernel is instantiated for, so it throws from amgx_create.  jacobi_form: the DownPath of a MODE 0 launch.
+static DownPlan make_down_plan(const DevLevel& L, const DevRestrict& R, int mode, int jacobi_form = DOWN_NONE) {
+  static_assert(DOWN_SLICE == WAVE && DOWN_THREADS == SELL_WIN, "down_plan.hpp counts slices of WAVE lanes; a window is a chunk");
+  auto need = [&](bool ok, const char* what) { if (!ok) throw Err("fused down pass (MODE " + std::to_string(mode) + "): " + what); };
+  const bool compact = R.slice_list.n > 0;
+  const bool dia = mode == 0 && (jacobi_form == DOWN_DIA || jacobi_form == DOWN_DIA_BOX);
+  const bool lw = mode == 1 ? !L.gsb.restLW.empty() : jacobi_form == DOWN_LW;
+  const DevMatrix& M = down_image(L, mode, lw);
+  need(dia || M.fmt == FMT_SELL, "the image is not in a SELL format");
+  DownPlan p;
+  p.on = true; p.mode = mode; p.ept = R.ept; p.n_chunks = R.n_chunks;
+  p.family = dia ? (jacobi_form == DOWN_DIA ? DOWN_FAM_DIA : DOWN_FAM_DIA_BOX) : lw ? DOWN_FAM_LW : M.sell.win ? DOWN_FAM_WIN : DOWN_FAM_SELL;
+  p.diags = dia ? L.dia.K : 0; p.lanes = dia ? 1 : M.lanes; p.f32 = mode == 2 && M.has32();
+  // (RG and the local-window chunks are always built for DOWN_THREADS lanes; the other builders leave their choice in fused_block)
+  p.threads = (mode == 1 || lw) ? DOWN_THREADS : L.fused_block;
+  p.unit_rows = down_rows_per_chunk(p.threads, p.lanes);
+  p.splittable = down_splittable(p.family, compact);
+  // ---- a kernel is instantiated for the shape
+  need(p.family == DOWN_FAM_SELL && mode == 0 && p.lanes == 1 ? contains(DownSizes{}, p.threads) : p.threads == DOWN_THREADS, "no kernel for this workgroup size");
+  switch (p.family) {
+    case DOWN_FAM_SELL:
+      if (p.lanes == 1) need(contains(DownEpt{}, p.ept), "no one-lane sell kernel for this EPT");
+      else need(mode != 1 && contains(DownSellLanes{}, p.lanes) && p.ept == DOWN_MULTI_EPT && !compact, "no multi-lane sell kernel for this shape");
+      break;
+    case DOWN_FAM_WIN: need(mode != 2 && p.lanes == 1 && M.sell.win == SELL_WIN && contains(DownEpt{}, p.ept) && !compact, "no windowed kernel for this shape"); break;
+    case DOWN_FAM_LW: need(mode != 2 && contains(DownLwLanes{}, p.lanes) && contains(DownLwEpt{}, p.ept) && !compact, "no local-window kernel for this shape"); break;
+    case DOWN_FAM_DIA: need(contains(DiaDiags{}, p.diags) && contains(DownEpt{}, p.ept), "no diagonal-image kernel for this shape"); break;
+    default: need(contains(DiaBoxDiags{}, p.diags) && !compact, "no box-chunk kernel for this number of diagonals"); break;     // (it loops over any EPT)
+  }
+  // ---- the chunks of R are the chunks the kernel forms
+  const int64_t rows = R.box.box_rows();
+  if (p.family == DOWN_FAM_DIA_BOX)
+    need(R.boxed && (int64_t)R.box.nx * R.box.ny * R.box.nz == L.n && rows <= dia::BOX_MAX_ROWS && R.box_lds_doubles >= 2 * rows &&
+         R.box_lds_doubles >= rows + R.max_entries && R.box_lds_doubles <= DIA_BOX_LDS_DOUBLES, "box / chunk mismatch");
+  p.lds_bytes = (size_t)R.box_lds_doubles * sizeof(double);     // (0 unless the chunks are boxes)
+  const int64_t expected = p.family == DOWN_FAM_DIA_BOX ? down_expected_chunks(p.family, R.box.n_boxes(), p.threads, p.lanes)
+                           : compact                    ? (int64_t)(R.slice_list.n / down_slices_per_chunk(p.threads))
+                                                        : down_expected_chunks(p.family, dia ? L.n : M.n_slices, p.threads, p.lanes);
+  need(expected == R.n_chunks, "chunk / slice mismatch");
+  return p;
+}
+
+// The ONLY place where image presence becomes a path -- and a path a launch plan.  Precedence of the down kernels: local window
+// before diagonal image before SELL; of the sweeps: bgsb before gsb before multicolour.  Conditions on call-time arguments (the part
+// of a split level, the fold flag, skip_rsum) stay with the callers.
 static void resolve_paths(DevLevel& L) {
   LevelPaths p;
   p.plain = L.sm_steps <= 1 && !L.sm_symm;
@@ -425,6 +478,9 @@ static void resolve_paths(DevLevel& L) {
   else if (p.plain && L.sm_type == AMGX_SM_CHEBY && !L.RF.empty()) p.down = DOWN_CHEB;
   else if (p.plain && p.sweep == SWEEP_GSB && L.gsb.has_split && !L.RG.empty()) p.down = DOWN_GSB;
   L.paths = p;
+  L.plan_rf = p.jacobi_down() ? make_down_plan(L, L.RF, 0, p.down) : p.down == DOWN_CHEB ? make_down_plan(L, L.RF, 2) : DownPlan();
+  // (gsb_residual_restrict also serves the rank-partitioned driver, whatever the cycle's own down path is)
+  L.plan_rg = (L.gsb.on() && L.gsb.has_split && !L.RG.empty()) ? make_down_plan(L, L.RG, 1) : DownPlan();
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1171,9 +1227,18 @@ static void build_restrict(const Knobs& K, const amgx_matrix& P, DevRestrict& R,
   for (int64_t v : fullest) mx_chunk = std::max(mx_chunk, v);
   for (int64_t c = 0; c < nch; ++c) R.max_slots = std::max(R.max_slots, chunk_slot[c + 1] - chunk_slot[c]);
   R.max_entries = mx_chunk;
-  R.ept = mx_chunk <= (int64_t)4 * threads ? 4 : 6;
+  // entries of P per thread: the smallest value of the kernels' list (down_plan.hpp) that holds the fullest chunk.  This is the
+  // guard against a kernel that would drop entries: a caller whose max_entries admits more than the list's last value holds
+  // fails here (make_down_plan then only asks whether the value belongs to the list of the kernel that was chosen)
+  auto ept_of = [&](auto list) {
+    for (int e : values(list)) if (mx_chunk <= (int64_t)e * threads) return e;
+    throw Err("build_restrict: no listed EPT holds the fullest chunk");
+  };
+  // local-window chunks (lw_image, build_gsb_images): DOWN_THREADS lanes, a listed number of them per row, the list's last EPT
+  const bool lw = threads == DOWN_THREADS && threads % CH == 0 && contains(DownLwLanes{}, threads / CH) &&
+                  max_entries == values(DownLwEpt{}).back() * DOWN_THREADS;
   if (runs) R.ept = (int)std::max<int64_t>(1, (mx_chunk + threads - 1) / threads);     // (the box kernel loops: any number of entries per lane)
-  if ((CH == 256 || CH == 128) && threads == 512 && max_entries == 4 * 512) R.ept = mx_chunk <= (int64_t)2 * threads ? 2 : 4;     // (local-window chunks: see lw_image)
+  else R.ept = lw ? ept_of(DownLwEpt{}) : ept_of(DownEpt{});
   if (R.ept > K.fused_ept_max) { R = DevRestrict(); return; }     // (A/B hook: keep the separate kernels instead)
   R.chunk_slot.upload(chunk_slot); R.slot_ptr.upload(slot_ptr); R.optr.upload(optr);
   // Measured NON-win (profiles/r01/restrict_fused.txt): storing the partial sums row by row (scattered stores in the
@@ -1332,8 +1397,6 @@ static bool build_sell_lw_windowed(const Knobs& K, int64_t n, int64_t n_cols, co
 // the handle
 // ---------------------------------------------------------------------------------------------------
 
-enum { PART_ALL = 0, PART_INT = 1, PART_BND = 2 };
-struct Span { int part = PART_ALL; int64_t n_int = 0; };   // see Handle::product
 struct MultiState;                      // multi-vector work space and captured graphs (multi.hpp)
 void multi_drop_graphs(MultiState* s);
 void multi_free(MultiState* s);
@@ -1397,19 +1460,10 @@ struct Handle {
   // ------------------------------------------------------------------ primitive ops (all async on `stream`)
   static int grid_for(int64_t threads) { return (int)std::max<int64_t>(1, (threads + BLOCK - 1) / BLOCK); }
 
-  // Part of the rows a launch covers.  Rank-partitioned levels order their owned rows [interior | boundary] (interior =
-  // no ghost column; the analogue of the reference's split_ind stages, gssmoother.cpp:664-678): the interior part runs
-  // while the halo exchange is in flight, the boundary part after it (hybrid_base_smoother.cpp:501-574).  A kernel works
-  // in units of u rows (slice / window / chunk); units that straddle n_int belong to the boundary part.  Formats that
-  // cannot be split run completely in the boundary part (correct, no overlap).
+  // Part of the rows a launch covers: Span and unit_range (down_plan.hpp).  Formats that cannot be split run completely in the
+  // boundary part (correct, no overlap).
   using Span = ::amgx::Span;
   enum { PART_ALL = ::amgx::PART_ALL, PART_INT = ::amgx::PART_INT, PART_BND = ::amgx::PART_BND };
-  static void unit_range(const Span& sp, int64_t u, int64_t n_units, int64_t& a, int64_t& b) {
-    const int64_t split = std::min<int64_t>(n_units, sp.n_int / u);
-    if (sp.part == PART_ALL) { a = 0; b = n_units; }
-    else if (sp.part == PART_INT) { a = 0; b = split; }
-    else { a = split; b = n_units; }
-  }
 
   // ------------------------------------------------------------------ the product launcher
   // The value lists of the product kernels, each written once: product() dispatches on them and the multi-vector path asks them
@@ -1978,195 +2032,113 @@ struct Handle {
     }
   }
 
-  // pre-smoothing followed by the restriction of the residual (amg_matrix.cpp:193-212), fused where possible
+  // ------------------------------------------------------------------ the fused down launcher
+  // The kernels' operands (b, dinv, omega, nt, x) in the three modes: what is gathered, what the epilogue combines it with, the
+  // flags, and the x that only MODE 0 writes.  MODE 1 is launched without the nt flags.
+  struct DownOps { const double *v, *d; double omega; int flags; double* xout; };
+  DownOps down_ops_jacobi(const DevLevel& L, const double* b, double* x, bool fold) const { return {b, L.dinv.p, L.omega, ep_nt | (fold ? EPF_FOLD : 0), x}; }
+  static DownOps down_ops_gsb(const DevLevel& L, const double* x) { return {x, L.gsb.cvec.p, 0.0, 0, nullptr}; }
+  DownOps down_ops_cheb(const double* x, const double* b) const { return {x, b, 0.0, ep_nt, nullptr}; }
+
+  // One fused down launch of level l as resolve_paths planned it (DownPlan, down_plan.hpp), then the sum of the partial sums into
+  // b_coarse.  One branch per family; in it the value lists (down_plan.hpp) are dispatched once.  A list that does not hold the
+  // plan's value cannot happen: make_down_plan asked the same list.
+  // sp: interior part = the chunks of interior rows only; boundary part = the remaining chunks plus the sum, which needs all of them
+  void down_launch(int l, const DownPlan& p, const DownOps& o, double* b_coarse, const Span sp = Span()) {
+    const DevLevel& L = lev[l];
+    if (!p.on) throw Err("fused down pass: the level has no plan for it");
+    const DevRestrict& R = p.mode == 1 ? L.RG : L.RF;
+    int64_t ca, cb;
+    if (!down_chunk_range(p, sp, ca, cb)) throw Err("fused down pass: diagonal images and compact chunks are not split into interior / boundary parts");
+    const int grid = (int)(cb - ca), c0 = (int)ca;
+    const DevMatrix& M = down_image(L, p.mode, p.family == DOWN_FAM_LW);
+    // (rank-partitioned level: the events go around the interior launch, which runs beside the halo exchange)
+    const bool probe = probe_level == l && probe_kind == 8 && probe_e0 && sp.part != PART_BND;
+    bool miss = false;                  // a value that its list does not hold
+    auto pick = [&](auto list, int value, auto&& run) { if (!dispatch(list, value, run)) miss = true; };
+    probed(probe, [&] {
+      if (grid <= 0) return;
+      if (p.family == DOWN_FAM_SELL) {
+        pick(IntList<0, 1, 2>{}, p.mode, [&](auto MODE) {
+          auto image = [&](auto view) {
+            using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;       // double / float
+            // <rows per chunk, MODE, entries of P per thread, lanes per row, value type>
+            auto sell = [&](auto FB, auto EPT, auto G) {
+              launch(sell_pre_restrict_kernel<FB(), MODE(), EPT(), G(), V>, grid, FB(), 0, stream, M.n_rows, c0, M.n_slices, view, o.v, o.d, o.omega, o.flags,
+                     o.xout, nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, R.slice_list.p);
+            };
+            // which (MODE, lanes) reaches which instantiation (pick sets `miss` where a list does not hold the value):
+            //   MODE 0 / 2, lanes 2 / 4 / 8:  <512, MODE, 4, lanes>        (MODE 1 has no multi-lane form: a miss)
+            //   MODE 0, one lane:             <256 / 512 / 1024, 0, 4 / 6, 1>
+            //   MODE 1 / 2, one lane:         <512, MODE, 4 / 6, 1>
+            if constexpr (MODE() != 1) { if (p.lanes > 1) return pick(DownSellLanes{}, p.lanes, [&](auto G) { sell(Int<DOWN_THREADS>{}, Int<DOWN_MULTI_EPT>{}, G); }); }
+            if (p.lanes > 1) { miss = true; return; }
+            if constexpr (MODE() == 0) pick(DownSizes{}, p.threads, [&](auto FB) { pick(DownEpt{}, p.ept, [&](auto EPT) { sell(FB, EPT, Int<1>{}); }); });
+            else pick(DownEpt{}, p.ept, [&](auto EPT) { sell(Int<DOWN_THREADS>{}, EPT, Int<1>{}); });
+          };
+          // (MODE 2 is a smoother pass: the float kernel on the single-precision image where the level has one)
+          if constexpr (MODE() == 2) { if (p.f32) return image(M.sell.view32(M.val32.p)); }
+          image(M.sell.view());
+        });
+      } else if (p.family == DOWN_FAM_WIN) {
+        pick(IntList<0, 1>{}, p.mode, [&](auto MODE) { pick(DownEpt{}, p.ept, [&](auto EPT) {
+          launch(sell_win_pre_restrict_kernel<SELL_WIN, EPT(), MODE()>, grid, SELL_WIN, 0, stream, M.n_rows, c0, M.sell.view(), M.sell.rowloc.p, o.v, o.d, o.omega,
+                 o.flags, o.xout, R.view());
+        }); });
+      } else if (p.family == DOWN_FAM_LW) {
+        // long-row level: the local-window image (gathers from LDS), chunks of 512 / lanes rows
+        const int32_t *cptr = p.mode == 1 ? L.gsb.lw_cptr.p : L.lw_cptr.p, *ccol = p.mode == 1 ? L.gsb.lw_ccol.p : L.lw_ccol.p;
+        pick(IntList<0, 1>{}, p.mode, [&](auto MODE) { pick(DownLwLanes{}, p.lanes, [&](auto G) { pick(DownLwEpt{}, p.ept, [&](auto EPT) {
+          launch(sell_lw_pre_restrict_kernel<EPT(), G(), MODE()>, grid, DOWN_THREADS, 0, stream, M.n_rows, c0, M.n_slices, M.sell.view(), cptr, ccol, o.v, o.d,
+                 o.omega, o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+        }); }); });
+      } else if (p.family == DOWN_FAM_DIA) {
+        // symmetric diagonal image: 512-row chunks, one thread per row, whole level in one launch
+        pick(DiaDiags{}, p.diags, [&](auto K) { pick(DownEpt{}, p.ept, [&](auto EPT) {
+          launch(dia_pre_restrict_kernel<K(), EPT()>, grid, DOWN_THREADS, 0, stream, (int)L.n, (int)((L.n + WAVE - 1) / WAVE), L.dia.view(), o.v, o.d, o.omega,
+                 o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, R.slice_list.p);
+        }); });
+      } else {
+        // ... on box chunks: one 512-lane workgroup per box of grid lines
+        pick(DiaBoxDiags{}, p.diags, [&](auto K) {
+          launch(dia_box_pre_restrict_kernel<K()>, grid, DOWN_THREADS, p.lds_bytes, stream, (int)L.n, L.dia.view(), R.box, R.box.box_rows(), o.v, o.d, o.omega,
+                 o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+        });
+      }
+    });
+    if (miss) throw Err("fused down pass: no kernel for the plan");
+    if (!skip_rsum && sp.part != PART_INT) restrict_sum(l, R, b_coarse);
+  }
+
+  // pre-smoothing followed by the restriction of the residual (amg_matrix.cpp:193-212), fused where the level has a plan
   // sp: interior part = the row-parallel pass over the interior rows only; boundary part = the remaining rows plus
   // everything that needs all rows (partial-sum reduction / P^T gather)
   void pre_smooth_restrict(int l, double* x, const double* b, double* r, double* b_coarse, bool fold = false, const Span sp = Span()) {
     DevLevel& L = lev[l];
     if (fold && !L.paths.folded) throw Err("pre_smooth_restrict: level has no folded prolongation");
-    const int epf = ep_nt | (fold ? EPF_FOLD : 0);
-    const DevRestrict& R = L.RF;
-    // (rank-partitioned level: the events go around the interior launch, which runs beside the halo exchange)
-    const bool probe = probe_level == l && probe_kind == 8 && probe_e0 && sp.part != PART_BND;
-    switch (L.paths.down) {
-      case DOWN_LW: {
-        // long-row level: the local-window image (gathers from LDS), chunks of 512 / lanes rows
-        const int nch = (L.ApreLW.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
-        if (nch != R.n_chunks) throw Err("fused restriction (local-window image): chunk / slice mismatch");
-        int64_t ca, cb;
-        const int LG = L.ApreLW.lanes;
-        unit_range(sp, 512 / LG, nch, ca, cb);
-        const int grid = (int)(cb - ca), c0 = (int)ca;
-        probed(probe, [&] {
-          if (grid <= 0) return;
-          auto run_g = [&](auto G) {
-            auto run = [&](auto EPT) {
-              launch(sell_lw_pre_restrict_kernel<EPT(), G(), 0>, grid, 512, 0, stream, L.ApreLW.n_rows, c0, L.ApreLW.n_slices, L.ApreLW.sell.view(), L.lw_cptr.p,
-                     L.lw_ccol.p, b, L.dinv.p, L.omega, epf, x, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
-            };
-            if (!dispatch<2>(R.ept, run)) run(Int<4>{});
-          };
-          if (!dispatch<2>(LG, run_g)) run_g(Int<4>{});
-        });
-        if (!skip_rsum && sp.part != PART_INT) restrict_sum(l, R, b_coarse);
-        return;
-      }
-      case DOWN_DIA: {
-        // symmetric diagonal image: 512-row chunks, one thread per row, whole level in one launch
-        const int ns = (int)((L.n + WAVE - 1) / WAVE);
-        const int nch = R.slice_list.n ? R.n_chunks : (ns + (512 / WAVE) - 1) / (512 / WAVE);
-        if (nch != R.n_chunks || L.fused_block != 512) throw Err("fused restriction (diagonal image): chunk / slice mismatch");
-        if (sp.part != PART_ALL) throw Err("fused restriction (diagonal image): the level is not split into interior / boundary parts");
-        probed(probe, [&] {
-          if (nch <= 0) return;
-          auto run_k = [&](auto K) {
-            auto run = [&](auto EPT) {
-              launch(dia_pre_restrict_kernel<K(), EPT()>, nch, 512, 0, stream, (int)L.n, ns, L.dia.view(), b, L.dinv.p, L.omega, epf, x, R.chunk_slot.p,
-                     R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, R.slice_list.p);
-            };
-            if (!dispatch<4>(R.ept, run)) run(Int<6>{});
-          };
-          if (!dispatch<1, 2, 3, 4, 5, 6, 7, 8>(L.dia.K, run_k)) throw Err("fused restriction (diagonal image): bad number of diagonals");
-        });
-        if (!skip_rsum) restrict_sum(l, R, b_coarse);
-        return;
-      }
-      case DOWN_DIA_BOX: {
-        // symmetric diagonal image on box chunks: one 512-lane workgroup per box of grid lines, whole level in one launch
-        if (!R.boxed || R.box.n_boxes() != R.n_chunks || (int64_t)R.box.nx * R.box.ny * R.box.nz != L.n || L.fused_block != 512 ||
-            R.box.box_rows() > dia::BOX_MAX_ROWS || R.box_lds_doubles < 2 * (int64_t)R.box.box_rows() ||
-            R.box_lds_doubles < R.box.box_rows() + R.max_entries || R.box_lds_doubles > DIA_BOX_LDS_DOUBLES)
-          throw Err("fused restriction (diagonal image, box chunks): box / chunk mismatch");
-        if (sp.part != PART_ALL) throw Err("fused restriction (diagonal image): the level is not split into interior / boundary parts");
-        probed(probe, [&] {
-          if (R.n_chunks <= 0) return;
-          auto run = [&](auto K) {
-            launch(dia_box_pre_restrict_kernel<K()>, R.n_chunks, 512, (size_t)R.box_lds_doubles * sizeof(double), stream, (int)L.n, L.dia.view(), R.box,
-                   R.box.box_rows(), b, L.dinv.p, L.omega, epf, x, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
-          };
-          if (!dispatch<2, 3, 4, 5, 6, 7>(L.dia.K, run)) throw Err("fused restriction (diagonal image, box chunks): bad number of diagonals");
-        });
-        if (!skip_rsum) restrict_sum(l, R, b_coarse);
-        return;
-      }
-      case DOWN_SELL:
-      case DOWN_WIN: {
-        const int FB = L.fused_block;
-        const int G = L.Apre.lanes;
-        const int nch = R.slice_list.n ? R.n_chunks : (L.Apre.n_slices + (FB / WAVE) - 1) / (FB / WAVE);
-        if (nch != R.n_chunks) throw Err("fused restriction: chunk / slice mismatch");
-        if (R.slice_list.n && sp.part != PART_ALL) throw Err("fused restriction: compact chunks are not split into interior / boundary parts");
-        int64_t ca, cb;
-        unit_range(sp, FB / G, nch, ca, cb);
-        const int grid = (int)(cb - ca), c0 = (int)ca;
-        probed(probe, [&] {
-          if (grid <= 0) return;
-          // <rows per chunk, MODE 0, entries of P per thread, lanes per row>(..., compact chunk list)
-          auto sell = [&](auto FB_, auto EPT, auto G_, const int32_t* slice_list) {
-            launch(sell_pre_restrict_kernel<FB_(), 0, EPT(), G_()>, grid, FB_(), 0, stream, L.Apre.n_rows, c0, L.Apre.n_slices, L.Apre.sell.view(), b, L.dinv.p,
-                   L.omega, epf, x, nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, slice_list);
-          };
-          if (L.paths.down == DOWN_WIN) {
-            if (FB != SELL_WIN || G != 1) throw Err("fused restriction on a windowed image: unexpected chunk shape");
-            auto run = [&](auto EPT) {
-              launch(sell_win_pre_restrict_kernel<SELL_WIN, EPT()>, grid, SELL_WIN, 0, stream, L.Apre.n_rows, c0, L.Apre.sell.view(), L.Apre.sell.rowloc.p, b,
-                     L.dinv.p, L.omega, epf, x, R.view());
-            };
-            if (!dispatch<4>(R.ept, run)) run(Int<6>{});
-          } else if (G > 1) {
-            if (FB != 512 || R.ept != 4) throw Err("fused restriction with several lanes per row: unexpected chunk shape");
-            auto run = [&](auto G_) { sell(Int<512>{}, Int<4>{}, G_, nullptr); };
-            if (!dispatch<2, 4>(G, run)) run(Int<8>{});
-          } else {
-            auto run_fb = [&](auto FB_) {
-              auto run = [&](auto EPT) { sell(FB_, EPT, Int<1>{}, R.slice_list.p); };
-              if (!dispatch<4>(R.ept, run)) run(Int<6>{});
-            };
-            if (!dispatch<256, 512>(FB, run_fb)) run_fb(Int<1024>{});
-          }
-        });
-        if (!skip_rsum && sp.part != PART_INT) restrict_sum(l, R, b_coarse);
-        return;
-      }
-      case DOWN_CHEB: {
-        if (sp.part != PART_ALL) break;
-        // Chebyshev pre-smoothing from zero, then residual on the SELL image of A + chunk-local restriction in one pass (r stays in LDS)
-        cheb_smooth(L, x, x, b, r, false, false, true);
-        const int G = L.A.lanes;
-        const int nch = R.slice_list.n ? R.n_chunks : (L.A.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
-        if (nch != R.n_chunks || L.fused_block != 512 || L.A.fmt != FMT_SELL || L.A.sell.win) throw Err("fused Chebyshev residual: chunk / slice mismatch");
-        if (nch > 0) {
-          // (a smoother pass: the float kernel on the single-precision image where the level has one)
-          auto run_v = [&](auto view) {
-            using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;
-            auto cres = [&](auto EPT, auto G_, const int32_t* slice_list) {
-              launch(sell_pre_restrict_kernel<512, 2, EPT(), G_(), V>, nch, 512, 0, stream, L.A.n_rows, 0, L.A.n_slices, view, x, b, 0.0, ep_nt, nullptr, nullptr,
-                     R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, slice_list);
-            };
-            if (G > 1) {
-              if (R.ept != 4 || R.slice_list.n) throw Err("fused Chebyshev residual with several lanes per row: unexpected chunk shape");
-              if (!dispatch<2, 4, 8>(G, [&](auto G_) { cres(Int<4>{}, G_, nullptr); })) throw Err("fused Chebyshev residual: unexpected lanes per row");
-            } else {
-              auto run = [&](auto EPT) { cres(EPT, Int<1>{}, R.slice_list.p); };
-              if (!dispatch<4>(R.ept, run)) run(Int<6>{});
-            }
-          };
-          if (L.A.has32()) run_v(L.A.sell.view32(L.A.val32.p));
-          else run_v(L.A.sell.view());
-        }
-        if (!skip_rsum) restrict_sum(l, R, b_coarse);
-        return;
-      }
-      case DOWN_GSB:
-        if (sp.part != PART_ALL) break;
-        // sweep from zero, then residual of the untouched part + chunk-local restriction in one pass (r stays in LDS)
-        gsb_sweep(L, 0, L.gsb.lowin, nullptr, x, b);
-        gsb_residual_restrict(l, x, r, b_coarse);
-        return;
-      default: break;
+    const bool whole = sp.part == PART_ALL;     // (the residual forms run the whole level: a split level takes the unfused path)
+    if (L.paths.jacobi_down()) down_launch(l, L.plan_rf, down_ops_jacobi(L, b, x, fold), b_coarse, sp);
+    else if (L.paths.down == DOWN_CHEB && whole) {
+      // Chebyshev pre-smoothing from zero, then residual on the SELL image of A + chunk-local restriction in one pass (r stays in LDS)
+      cheb_smooth(L, x, x, b, r, false, false, true);
+      down_launch(l, L.plan_rf, down_ops_cheb(x, b), b_coarse);
+    } else if (L.paths.down == DOWN_GSB && whole) {
+      // sweep from zero, then residual of the untouched part + chunk-local restriction in one pass (r stays in LDS)
+      gsb_sweep(L, 0, L.gsb.lowin, nullptr, x, b);
+      gsb_residual_restrict(l, x, r, b_coarse);
+    } else {
+      pre_smooth(L, x, b, r, fold, sp);
+      if (sp.part != PART_INT) transfer_f2c(l, r, b_coarse);
     }
-    pre_smooth(L, x, b, r, fold, sp);
-    if (sp.part != PART_INT) transfer_f2c(l, r, b_coarse);
   }
 
   // after a block-hybrid sweep from zero: r = c .* x - A_rest x (x may carry ghost entries) and b_coarse = P^T r
   void gsb_residual_restrict(int l, const double* x, double* r, double* b_coarse) {
     DevLevel& L = lev[l];
     if (!L.gsb.has_split) throw Err("gsb_residual_restrict: the level has no lower / rest split");
-    const DevRestrict& R = L.RG;
-    if (R.empty()) {
-      product<1, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
-      transfer_f2c(l, r, b_coarse);
-      return;
-    }
-    if (!L.gsb.restLW.empty()) {
-      // long-row level: local-window image of the rest part (the swept x is staged in LDS per chunk)
-      const DevMatrix& M = L.gsb.restLW;
-      const int nch = (M.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
-      if (nch != R.n_chunks) throw Err("fused Gauss-Seidel residual (local-window image): chunk / slice mismatch");
-      auto run_g = [&](auto G) {
-        auto run = [&](auto EPT) {
-          launch(sell_lw_pre_restrict_kernel<EPT(), G(), 1>, nch, 512, 0, stream, M.n_rows, 0, M.n_slices, M.sell.view(), L.gsb.lw_cptr.p, L.gsb.lw_ccol.p, x,
-                 L.gsb.cvec.p, 0.0, 0, nullptr, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
-        };
-        if (!dispatch<2>(R.ept, run)) run(Int<4>{});
-      };
-      if (!dispatch<2>(M.lanes, run_g)) run_g(Int<4>{});
-    } else {
-      const DevMatrix& M = L.gsb.rest;
-      const int nch = (M.n_slices + (512 / WAVE) - 1) / (512 / WAVE);
-      if (nch != R.n_chunks) throw Err("fused Gauss-Seidel residual: chunk / slice mismatch");
-      auto run = [&](auto EPT) {
-        if (M.sell.win)
-          launch(sell_win_pre_restrict_kernel<SELL_WIN, EPT(), 1>, nch, SELL_WIN, 0, stream, M.n_rows, 0, M.sell.view(), M.sell.rowloc.p, x, L.gsb.cvec.p, 0.0, 0, nullptr,
-                 R.view());
-        else
-          launch(sell_pre_restrict_kernel<512, 1, EPT()>, nch, 512, 0, stream, M.n_rows, 0, M.n_slices, M.sell.view(), x, L.gsb.cvec.p, 0.0, 0, nullptr, nullptr,
-                 R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, nullptr);
-      };
-      if (!dispatch<4>(R.ept, run)) run(Int<6>{});
-    }
-    restrict_sum(l, R, b_coarse);
+    if (L.plan_rg.on) { down_launch(l, L.plan_rg, down_ops_gsb(L, x), b_coarse); return; }
+    product<1, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
+    transfer_f2c(l, r, b_coarse);
   }
 
   // coarse-grid correction + post-smoothing: x += P x_c; SmoothBack(x, b, r, 0, 0, 0)   (amg_matrix.cpp:263-302)
@@ -2694,7 +2666,7 @@ static void build_gsb_images(const Knobs& K, const amgx_level_desc& d, DevLevel&
         const bool dev_lw = !K.host_lw;
         const bool verify_lw = K.verify_images;
         int G = 0;
-        for (int gg : {2, 4}) {
+        for (int gg : values(DownLwLanes{})) {
           bool ok = false;
           if (dev_lw) {
             ok = dev_build_lw(part[1], false, gg, K.lw_cap(LW_CAP), K.lw_test_cap_on, nullptr, 0.0, g.restLW, g.lw_cptr, g.lw_ccol);
@@ -2797,7 +2769,7 @@ static void build_gsb_images(const Knobs& K, const amgx_level_desc& d, DevLevel&
       const double avgA = n ? (double)d.A.rowptr[n] / (double)n : 0.0;
       if (P && avgA >= 24.0 && K.lw_wanted(n) && d.A.n_cols == n && K.fused_restrict_ok(*P, 1)) {
         int G = 0;
-        for (int gg : {2, 4}) if (build_sell_lw(K, F, F.val, gg, g.restLW, g.lw_cptr, g.lw_ccol)) { G = gg; break; } else g.restLW = DevMatrix();
+        for (int gg : values(DownLwLanes{})) if (build_sell_lw(K, F, F.val, gg, g.restLW, g.lw_cptr, g.lw_ccol)) { G = gg; break; } else g.restLW = DevMatrix();
         if (G) {
           build_restrict(K, *P, L.RG, 512 / G, 4 * 512, 512);
           if (!L.RG.empty()) return;
@@ -3725,17 +3697,18 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
     const amgx::DevRestrict& R = L.RF;
     int64_t v[AMGX_LEVEL_PATHS_N] = {};
     const int down = L.paths.down;
-    if (down != amgx::DOWN_NONE && down != amgx::DOWN_GSB) {          // (the fused block-hybrid form is not a kernel of entry 0)
+    const amgx::DownPlan& plan = L.plan_rf;
+    if (plan.on) {                        // (the fused block-hybrid form has a plan of its own: entry 33)
       v[0] = down == amgx::DOWN_DIA_BOX ? (int)amgx::DOWN_DIA : down;
-      v[1] = L.fused_block;
-      v[2] = down == amgx::DOWN_CHEB ? L.A.lanes : down == amgx::DOWN_LW ? L.ApreLW.lanes : (down == amgx::DOWN_DIA || down == amgx::DOWN_DIA_BOX) ? 1 : L.Apre.lanes;
-      v[3] = R.ept;
+      v[1] = plan.threads;
+      v[2] = plan.lanes;
+      v[3] = plan.ept;
+      v[18] = plan.n_chunks;
     }
     if (!R.empty()) {
       v[4] = R.boxed ? 2 : R.slice_list.n ? 1 : 0;
       v[5] = R.max_slots;
       v[6] = R.max_entries;
-      v[18] = R.n_chunks;
     }
     v[7] = L.dia.K;
     v[8] = L.A.sell.xcd; v[9] = L.Apre.sell.xcd; v[10] = L.Q.sell.xcd; v[11] = L.dia.xcd;
@@ -3775,7 +3748,7 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
         v[30] = gsb.lw;
         v[32] = gsb.has_fullLW ? gsb.flw_no_window : 0;
         // (the form gsb_residual_restrict picks; only where the cycle's down pass runs it)
-        if (down == amgx::DOWN_GSB) v[33] = !gsb.restLW.empty() ? 3 : gsb.rest.sell.win ? 2 : 1;
+        if (down == amgx::DOWN_GSB) v[33] = L.plan_rg.family == amgx::DOWN_FAM_LW ? 3 : L.plan_rg.family == amgx::DOWN_FAM_WIN ? 2 : 1;
         break;
       case amgx::SWEEP_MC: v[20] = gs.lanes; v[21] = amgx::BLOCK; v[23] = gs.n_colors; v[25] = gs.has_split; break;
       case amgx::SWEEP_MC_BSELL: v[21] = amgx::BLOCK; v[23] = gs.n_colors; v[25] = gs.bsplit; break;
@@ -3820,7 +3793,7 @@ int amgx_time_op(amgx_handle hh, int level, int op, int reps, double* avg_ms) {
         case 5: h.pre_smooth_restrict(level, L.x.p, L.rhs.p, L.res.p, h.lev[level + 1].rhs.p, h.folded(L)); break;
         case 6: h.post_smooth(level, L.x.p, L.rhs.p, L.res.p, h.lev[level + 1].x.p, h.folded(L)); break;
         case 7:
-          if (!L.paths.jacobi_down() && L.paths.down != amgx::DOWN_CHEB) throw amgx::Err("amgx_time_op: level has no fused pre-smoothing + restriction kernel");
+          if (!L.plan_rf.on) throw amgx::Err("amgx_time_op: level has no fused pre-smoothing + restriction kernel");
           h.skip_rsum = true;
           try { h.pre_smooth_restrict(level, L.x.p, L.rhs.p, L.res.p, h.lev[level + 1].rhs.p, h.folded(L)); } catch (...) { h.skip_rsum = false; throw; }
           h.skip_rsum = false;
@@ -3831,7 +3804,7 @@ int amgx_time_op(amgx_handle hh, int level, int op, int reps, double* avg_ms) {
     if (op == 8 || op == 9) {
       // the dominant kernel timed where it runs: inside the cycle, between the previous cycle's last kernel and the
       // partial-sum reduction (cache state and clocks of the real application), averaged over `reps` cycles
-      if (op == 8 && !L.paths.jacobi_down()) throw amgx::Err("amgx_time_op: level has no fused pre-smoothing + restriction kernel");
+      if (op == 8 && !(L.plan_rf.on && L.plan_rf.mode == 0)) throw amgx::Err("amgx_time_op: level has no fused pre-smoothing + restriction kernel");
       if (op == 9 && !(has_c && L.paths.plain && L.paths.hybrid() && L.n == L.ncols && !L.paths.folded))
         throw amgx::Err("amgx_time_op: level has no block-hybrid Gauss-Seidel sweep");
       if (h.stream == nullptr) throw amgx::Err("amgx_time_op: op 8 needs a non-default stream");

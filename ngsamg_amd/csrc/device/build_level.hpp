@@ -203,7 +203,7 @@ static bool lw_image(LevelBuild& B) {
   };
   // (device: window lists by a bitmap in LDS, devbuild.hpp dev_build_lw; AMGX_HOST_LW=1 keeps the host builder)
   const bool dev_lw = B.dev_images && !B.K.host_lw && !B.K.host_images;
-  for (int g : {2, 4}) {
+  for (int g : values(DownLwLanes{})) {
     bool ok = false;
     if (dev_lw) {
       ok = dev_build_lw(B.csrA, false, g, B.K.lw_cap(LW_CAP), B.K.lw_test_cap_on, L.dinv.p, s.omega, L.ApreLW, L.lw_cptr, L.lw_ccol);
@@ -256,7 +256,7 @@ static bool dia_image(LevelBuild& B) {
   // the chunks below, and so does every level grid_of / box_grid refuse or whose fullest box does not fit the kernel's LDS
   dia::Grid grid;
   dia::BoxGrid box;
-  if (!B.K.no_dia_box && s.A.n_rows >= B.K.dia_box_min_rows && K >= 2 && K <= 7 && dia::grid_of(s.A.n_rows, K, off, grid) &&
+  if (!B.K.no_dia_box && s.A.n_rows >= B.K.dia_box_min_rows && contains(DiaBoxDiags{}, K) && dia::grid_of(s.A.n_rows, K, off, grid) &&
       dia::box_grid(grid, K, B.K.dia_box_yc, B.K.dia_box_zc, box)) {
     const dia::BoxRuns runs = dia::box_runs(box);
     build_restrict(B.K, s.P, L.RF, box.box_rows(), DIA_BOX_LDS_DOUBLES - box.box_rows(), 512, nullptr, &runs);
@@ -269,7 +269,7 @@ static bool dia_image(LevelBuild& B) {
         HIPCHK(hipFuncSetAttribute((const void*)dia_box_pre_restrict_kernel<KK()>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    DIA_BOX_LDS_DOUBLES * (int)sizeof(double)));
       };
-      if (L.RF.box_lds_doubles * sizeof(double) > 65536) dispatch<2, 3, 4, 5, 6, 7>(K, allow);
+      if (L.RF.box_lds_doubles * sizeof(double) > 65536) dispatch(DiaBoxDiags{}, K, allow);
       return true;
     }
   }
@@ -292,7 +292,7 @@ static void fused_restrict(LevelBuild& B) {
     L.fused_block = SELL_WIN;              // windowed A': a chunk = a window (sell_win_pre_restrict_kernel)
     build_restrict(B.K, s.P, L.RF, SELL_WIN, 6 * SELL_WIN, SELL_WIN);
   }
-  else if (L.Apre.fmt == FMT_SELL && !L.Apre.sell.win && (G == 1 || G == 2 || G == 4 || G == 8) && B.K.fused_restrict_ok(s.P, G))
+  else if (L.Apre.fmt == FMT_SELL && !L.Apre.sell.win && down_sell_lanes_ok(G) && B.K.fused_restrict_ok(s.P, G))
   {
     L.fused_block = B.K.fused_block;       // same-process A/B: 512 < 1024 (epilogues of more, smaller workgroups overlap better)
     if (G > 1) L.fused_block = 512;        // (several lanes per row: the chunk holds 512 / G rows)
@@ -302,7 +302,7 @@ static void fused_restrict(LevelBuild& B) {
     build_restrict_chunks(B.K, s.P, L.RF, L.fused_block / G, 6 * L.fused_block, L.fused_block, G == 1 && B.dense_first >= 0 && s.A.n_rows == s.A.n_cols);
     // several lanes per row: the kernel exists for 4 entries of P per thread only; a chunk of 512 / G rows with more
     // than 2048 entries (a prolongation with more than 4 G entries per row) keeps the separate kernels
-    if (G > 1 && L.RF.ept != 4) L.RF = DevRestrict();
+    if (G > 1 && L.RF.ept != DOWN_MULTI_EPT) L.RF = DevRestrict();
   }
 }
 
@@ -453,13 +453,13 @@ static void cheb_fused_restrict(LevelBuild& B) {
   const amgx_level_desc& s = B.s;
   DevLevel& L = B.L;
   if (s.sm_type == AMGX_SM_CHEBY && s.A.br == 1 && s.sm_steps <= 1 && !s.sm_symm && L.A.fmt == FMT_SELL && !L.A.sell.win &&
-      (L.A.lanes == 1 || L.A.lanes == 2 || L.A.lanes == 4 || L.A.lanes == 8) && B.K.fused_restrict_ok(s.P, L.A.lanes) &&
+      down_sell_lanes_ok(L.A.lanes) && B.K.fused_restrict_ok(s.P, L.A.lanes) &&
       !B.K.cheb_no_fused_restrict)
   {
     const int G = L.A.lanes;
     L.fused_block = 512;
     build_restrict_chunks(B.K, s.P, L.RF, 512 / G, 6 * 512, 512, G == 1 && B.dense_first >= 0);
-    if (G > 1 && L.RF.ept != 4) L.RF = DevRestrict();
+    if (G > 1 && L.RF.ept != DOWN_MULTI_EPT) L.RF = DevRestrict();
   }
 }
 

@@ -1,0 +1,76 @@
+// The shape of a level's fused down launch (pre-smoothing or residual + chunk-local restriction), decided once at create time:
+// DownPlan, the value lists of the five kernel templates, and the chunk arithmetic.  resolve_paths (amgx.hip) fills the plans and
+// checks them, Handle::down_launch launches from them, amgx_level_paths and amgx_time_op report from them, and the builders
+// (build_level.hpp, build_gsb_images) ask the same lists whether a kernel exists.  Host-only: no HIP in here, so a plain C++17
+// compiler builds it (tests/test_down_plan_cpu.py).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include "launch.hpp"          // IntList, contains
+
+namespace amgx {
+
+// Part of the rows a launch covers.  Rank-partitioned levels order their owned rows [interior | boundary] (interior = no ghost
+// column; the analogue of the reference's split_ind stages, gssmoother.cpp:664-678): the interior part runs while the halo
+// exchange is in flight, the boundary part after it (hybrid_base_smoother.cpp:501-574).
+enum { PART_ALL = 0, PART_INT = 1, PART_BND = 2 };
+struct Span { int part = PART_ALL; int64_t n_int = 0; };
+// A kernel works in units of u rows (slice / window / chunk): the units [a, b) of n_units that the part covers.  Units that
+// straddle n_int belong to the boundary part.
+inline void unit_range(const Span& sp, int64_t u, int64_t n_units, int64_t& a, int64_t& b) {
+  const int64_t split = std::min<int64_t>(n_units, sp.n_int / u);
+  if (sp.part == PART_ALL) { a = 0; b = n_units; }
+  else if (sp.part == PART_INT) { a = 0; b = split; }
+  else { a = split; b = n_units; }
+}
+
+// ---- the kernels that exist.  Row-product families: sell_pre_restrict_kernel, sell_win_pre_restrict_kernel,
+// sell_lw_pre_restrict_kernel, dia_pre_restrict_kernel, dia_box_pre_restrict_kernel (kernels.hpp)
+enum DownFamily : int { DOWN_FAM_SELL = 0, DOWN_FAM_WIN = 1, DOWN_FAM_LW = 2, DOWN_FAM_DIA = 3, DOWN_FAM_DIA_BOX = 4 };
+constexpr int DOWN_SLICE = 64;          // lanes of a SELL slice (= WAVE)
+constexpr int DOWN_THREADS = 512;       // workgroup size of every form but the one-lane MODE 0 sell form, which has DownSizes
+constexpr int DOWN_MULTI_EPT = 4;       // the multi-lane sell form is built for this EPT alone
+using DownEpt = IntList<4, 6>;                    // entries of P per thread: sell (one lane per row), win, dia
+using DownLwEpt = IntList<2, 4>;                  // ... lw
+using DownLwLanes = IntList<2, 4>;                // lanes per row: lw (the builders try them in this order)
+using DownSellLanes = IntList<2, 4, 8>;           // ... the multi-lane sell form (one lane per row is a form of its own)
+using DownSizes = IntList<256, 512, 1024>;        // workgroup sizes of the one-lane MODE 0 sell form
+using DiaDiags = IntList<1, 2, 3, 4, 5, 6, 7, 8>; // upper diagonals: dia
+using DiaBoxDiags = IntList<2, 3, 4, 5, 6, 7>;    // ... dia-box
+// lanes per row of an image the sell family serves at all
+constexpr bool down_sell_lanes_ok(int lanes) { return lanes == 1 || contains(DownSellLanes{}, lanes); }
+
+// ---- the plan.  Values only: std::vector<DevLevel> moves its elements, so the launcher finds the image from (mode, family)
+struct DownPlan {
+  bool on = false;                      // the level has this fused launch
+  // family: a DownFamily; mode: 0 Jacobi from zero, 1 c .* x - A_rest x (after a block-hybrid sweep), 2 rhs - A x (after Chebyshev)
+  int family = DOWN_FAM_SELL, mode = 0;
+  int threads = 0, lanes = 1, ept = 0;  // workgroup size, lanes per row, entries of P per thread
+  int diags = 0, n_chunks = 0;          // upper diagonals (dia, dia-box); chunks = workgroups of the whole level
+  int64_t unit_rows = 0;                // rows of a chunk = the unit of the interior / boundary split
+  // splittable: consecutive chunks of a sell / win / lw image, otherwise the launch covers the whole level; f32: MODE 2 reads the
+  // single-precision image
+  bool splittable = false, f32 = false;
+  size_t lds_bytes = 0;                 // dynamic LDS (dia-box)
+};
+
+// ---- chunk arithmetic.  A chunk is what one workgroup of `threads` lanes owns: threads / 64 slices = threads / lanes rows
+constexpr int down_slices_per_chunk(int threads) { return threads / DOWN_SLICE; }
+constexpr int64_t down_rows_per_chunk(int threads, int lanes) { return threads / lanes; }
+// chunks of consecutive slices.  n: sell / win / lw: the slices of the image (64 lanes each, i.e. 64 / lanes rows); dia: the
+// rows of the level; dia-box: the boxes, one chunk each
+constexpr int64_t down_expected_chunks(int family, int64_t n, int threads, int lanes) {
+  const int64_t slices = family == DOWN_FAM_DIA ? (n * lanes + DOWN_SLICE - 1) / DOWN_SLICE : n, spc = down_slices_per_chunk(threads);
+  return family == DOWN_FAM_DIA_BOX ? n : (slices + spc - 1) / spc;
+}
+// only ranges of consecutive chunks can be split; the diagonal-image forms run the whole level in one launch
+constexpr bool down_splittable(int family, bool compact) { return !compact && (family == DOWN_FAM_SELL || family == DOWN_FAM_WIN || family == DOWN_FAM_LW); }
+// the chunks [a, b) a launch over `sp` covers; false: the plan refuses the part (an unsplittable launch asked for less than all)
+inline bool down_chunk_range(const DownPlan& p, const Span& sp, int64_t& a, int64_t& b) {
+  if (!p.splittable && sp.part != PART_ALL) return false;
+  unit_range(sp, p.unit_rows, p.n_chunks, a, b);
+  return true;
+}
+
+}  // namespace amgx

@@ -8,6 +8,7 @@
 // suite;  A/B hook = opt-in path with a recorded measurement (see the comment at the place that uses it).
 #pragma once
 #include "../../../include/amgx.h"
+#include "down_plan.hpp"       // DownSizes, DOWN_THREADS
 #include <algorithm>
 #include <climits>
 #include <cstdint>
@@ -59,7 +60,7 @@ struct Knobs {
   bool no_fused_restrict = false;       // AMGX_NO_FUSED_RESTRICT: separate smoothing and restriction kernels (kill switch)
   bool no_fused_restrict_multi = false; // AMGX_NO_FUSED_RESTRICT_MULTI: ... on images with several lanes per row only (kill switch)
   bool cheb_no_fused_restrict = false;  // AMGX_CHEB_NO_FUSED_RESTRICT: ... on Chebyshev levels only (kill switch)
-  int fused_block = 512;                // AMGX_FUSED_BLOCK: workgroup size of the fused down kernel, 256 / 512 / 1024 (A/B hook)
+  int fused_block = DOWN_THREADS;               // AMGX_FUSED_BLOCK: workgroup size of the fused down kernel, 256 / 512 / 1024 (A/B hook)
   int fused_ept_max = INT_MAX;          // AMGX_FUSED_EPT_MAX: chunks with more entries of P per thread keep the separate kernels (A/B hook)
   bool rsum_sort = false;               // AMGX_RSUM_SORT: partial sums stored row by row (A/B hook)
   bool no_compact_chunks = false;       // AMGX_NO_COMPACT_CHUNKS: consecutive chunks only (kill switch)
@@ -138,7 +139,7 @@ struct Knobs {
     k.no_fused_restrict = on("AMGX_NO_FUSED_RESTRICT");
     k.no_fused_restrict_multi = on("AMGX_NO_FUSED_RESTRICT_MULTI");
     k.cheb_no_fused_restrict = on("AMGX_CHEB_NO_FUSED_RESTRICT");
-    if (const char* e = std::getenv("AMGX_FUSED_BLOCK")) { const int v = std::atoi(e); k.fused_block = (v == 256 || v == 1024) ? v : 512; }
+    if (const char* e = std::getenv("AMGX_FUSED_BLOCK")) { const int v = std::atoi(e); k.fused_block = contains(DownSizes{}, v) ? v : DOWN_THREADS; }
     if (const char* e = std::getenv("AMGX_FUSED_EPT_MAX")) k.fused_ept_max = std::atoi(e);
     k.rsum_sort = on("AMGX_RSUM_SORT");
     k.no_compact_chunks = on("AMGX_NO_COMPACT_CHUNKS");

@@ -6,6 +6,7 @@
 // Exactly the listed values (and a fallback that is written out) are instantiated; combinations a kernel is not built for are
 // kept out with `if constexpr` inside the lambda.
 #pragma once
+#include <array>
 #include <type_traits>
 
 namespace amgx {
@@ -25,6 +26,9 @@ template <int... Vs, class F>
 bool dispatch(IntList<Vs...>, int value, F&& f) { return dispatch<Vs...>(value, static_cast<F&&>(f)); }
 template <int... Vs>
 constexpr bool contains(IntList<Vs...>, int value) { return ((value == Vs) || ...); }
+// ... and a builder that tries the values in their order:     for (int g : values(DownLwLanes{}))
+template <int... Vs>
+constexpr std::array<int, sizeof...(Vs)> values(IntList<Vs...>) { return {{Vs...}}; }
 
 }  // namespace amgx
 

@@ -6,6 +6,7 @@ coarse inverse and the operator of an outer Krylov iteration stay fp64.
     RoundedHierarchy(H, levels) the same behind the attributes DeviceAMGMatrix and ChebyRef read from a hierarchy
     pcg(cycle, A, b)            ChebyRef.pcg with an operator of its own (the fp64 A next to a cycle on rounded levels)
 """
+import copy
 import dataclasses
 
 import numpy as np
@@ -22,7 +23,12 @@ def rounded_levels(H, levels):
         if i in listed:
             A = lv.A
             val = np.ascontiguousarray(np.asarray(A.val, dtype=np.float64).astype(np.float32).astype(np.float64))
-            lv = dataclasses.replace(lv, A=Matrix(A.n_rows, A.n_cols, A.br, A.bc, A.rowptr, A.col, val))
+            A = Matrix(A.n_rows, A.n_cols, A.br, A.bc, A.rowptr, A.col, val)
+            if dataclasses.is_dataclass(lv):
+                lv = dataclasses.replace(lv, A=A)
+            else:       # (the plain namespaces of a hand-made hierarchy, tests/reorder.py)
+                lv = copy.copy(lv)
+                lv.A = A
         out.append(lv)
     return out
 

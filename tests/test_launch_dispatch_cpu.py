@@ -3,7 +3,9 @@ every listed value reaches its own constant exactly once, an unlisted value retu
 fallback form `if (!dispatch<...>(v, run)) run(Int<F>{})` reaches the fallback constant.  The named form -- IntList<...>,
 dispatch(list, value, f), contains(list, value) -- behaves the same, and contains() agrees with dispatch() on every value in -1 .. 70
 for the three block-shape lists of the product launcher (key = 10 * br + bc).  The host part of the file is all this program
-sees, so the lists are written out here as Handle (amgx.hip) names them."""
+sees, so those lists are written out here as Handle (amgx.hip) names them.  The value lists of the fused down kernels live in the
+host-only down_plan.hpp and are checked as the launcher and the builders use them: contains() and dispatch() agree on every value
+in -1 .. 1100, each list holds exactly the values DESIGN.md 5.2 states, and values() yields them in their order."""
 import os
 import shutil
 import subprocess
@@ -14,7 +16,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 PROGRAM = r"""
 #include "launch.hpp"
+#include "down_plan.hpp"
 #include <cstdio>
+#include <algorithm>
+#include <initializer_list>
 #include <map>
 #include <type_traits>
 
@@ -68,9 +73,9 @@ int main() {
   calls.clear();
   if (amgx::dispatch(amgx::IntList<>{}, 1, run) || !calls.empty() || amgx::contains(amgx::IntList<>{}, 1)) { std::printf("empty named list matched\n"); ++bad; }
   static_assert(amgx::contains(amgx::IntList<22, 33, 66>{}, 33) && !amgx::contains(amgx::IntList<22, 33, 66>{}, 36), "contains is a constant expression");
-  auto agree = [&](auto list, int n_listed) {
+  auto agree = [&](auto list, int n_listed, int hi = 70) {
     int hits = 0;
-    for (int v = -1; v <= 70; ++v) {
+    for (int v = -1; v <= hi; ++v) {
       calls.clear();
       const bool d = amgx::dispatch(list, v, run);
       if (d != amgx::contains(list, v)) { std::printf("contains and dispatch differ on %d\n", v); ++bad; }
@@ -83,6 +88,24 @@ int main() {
   agree(amgx::IntList<22, 33, 66>{}, 3);                                             // square shapes
   agree(amgx::IntList<22, 33, 66, 36, 63, 23, 32>{}, 7);                             // row-lane / multi-vector kernels
   agree(amgx::IntList<22, 33, 66, 36, 63, 23, 32, 13, 31, 16, 61, 12, 21>{}, 13);    // vector form
+  // ---- the lists of the fused down kernels (down_plan.hpp): the values, and contains() == dispatch() on -1 .. 1100
+  auto holds = [&](auto list, std::initializer_list<int> want, const char* name) {
+    agree(list, (int)want.size(), 1100);
+    const auto got = amgx::values(list);
+    if (got.size() != want.size() || !std::equal(got.begin(), got.end(), want.begin())) { std::printf("%s: other values than stated\n", name); ++bad; }
+  };
+  holds(amgx::DownEpt{}, {4, 6}, "DownEpt");
+  holds(amgx::DownLwEpt{}, {2, 4}, "DownLwEpt");
+  holds(amgx::DownLwLanes{}, {2, 4}, "DownLwLanes");
+  holds(amgx::DownSellLanes{}, {2, 4, 8}, "DownSellLanes");
+  holds(amgx::DownSizes{}, {256, 512, 1024}, "DownSizes");
+  holds(amgx::DiaDiags{}, {1, 2, 3, 4, 5, 6, 7, 8}, "DiaDiags");
+  holds(amgx::DiaBoxDiags{}, {2, 3, 4, 5, 6, 7}, "DiaBoxDiags");
+  if (amgx::DOWN_MULTI_EPT != 4 || !amgx::contains(amgx::DownEpt{}, amgx::DOWN_MULTI_EPT) || !amgx::contains(amgx::DownSizes{}, amgx::DOWN_THREADS)) {
+    std::printf("DOWN_MULTI_EPT / DOWN_THREADS are not values of their lists\n");
+    ++bad;
+  }
+  if (amgx::values(amgx::IntList<>{}).size() != 0) { std::printf("values of the empty list\n"); ++bad; }
   std::printf("bad=%d\n", bad);
   return bad ? 1 : 0;
 }
