@@ -388,6 +388,31 @@ int amgx_multi_info(amgx_handle h, int k, int32_t* fused, int32_t* n_groups, int
 int amgx_multi_plan(amgx_handle h, int k, int flags, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes);
 const char* amgx_multi_note(amgx_handle h, int flags);
 
+/* ---- multi-vector algebra: Gram matrices and combinations -------------------------------------------------------------------
+ * Reference interface: NGSolve's MultiVector.InnerProduct (the small matrices X^T Y of a Rayleigh-Ritz step) and
+ * MultiVector * matrix (the updates Y <- X c) -- with amgx_matvec_multi and amgx_apply_multi the four operations of the LOBPCG /
+ * PINVIT loops of ngsolve.eigenvalues (a Python loop there, ngsamg_amd.eigen here).  The handle gives the device, the stream,
+ * the error slot and the work space (kept until amgx_destroy); n is free, it need not be a level size.  Vectors: host or device
+ * pointers by AMGX_HOST_PTR / AMGX_DEVICE_PTR; layout column-major with ld >= n, or with AMGX_MULTI_INTERLEAVED entry (row, column
+ * j) at row*k + j and ld ignored.  The small matrices G and c are ALWAYS host arrays, row-major.  1 <= k <= AMGX_MV_MAX on every
+ * side.  Errors: k out of range, ld < n without the interleaved flag, a null pointer with n > 0, n < 0.
+ *   amgx_mv_gram   : G[i*kb + j] = <A_i, B_j>.  One pass over the vectors (8 n (ka + kb) bytes), any ka, kb: row chunks of all
+ *                    columns are staged in LDS and multiplied by v_mfma_f64_16x16x4_f64.  Deterministic: per-workgroup partial
+ *                    sums from a launch shape that depends on (n, ka, kb, layout) only (amgx_mv_gram_plan reports it), final
+ *                    sums by a second launch in a fixed order, no atomics: two calls on the same data return the same bits.
+ *                    A == B with lda == ldb and ka == kb: only the upper triangle is computed (8 n ka bytes) and mirrored, G is
+ *                    symmetric bit for bit.  Synchronises the stream before it returns (the caller needs G).  n = 0: G = 0.
+ *   amgx_mv_combine: Y_j = beta*Y_j + sum_i c[i*ky + j] X_i, per entry beta*y first, then i ascending, fused multiply-add;
+ *                    8 n (kx + ky (1 + [beta != 0])) bytes.  beta == 0: Y is not read (NaNs in it do not propagate).  Y must not
+ *                    be one of the X arrays: the same base pointer is an error.  c travels through a small ring of device
+ *                    buffers: with device vectors nothing synchronises the host.  n = 0 returns at once.
+ *   amgx_mv_gram_plan: rows of one staged chunk and workgroups of amgx_mv_gram for these sizes (symmetric: the A == B form) */
+#define AMGX_MV_MAX 32
+int amgx_mv_gram(amgx_handle h, int64_t n, int ka, const double* A, int64_t lda, int kb, const double* B, int64_t ldb, double* G, int flags);
+int amgx_mv_combine(amgx_handle h, int64_t n, int kx, const double* X, int64_t ldx, const double* c, int ky, double beta, double* Y, int64_t ldy,
+                    int flags);
+int amgx_mv_gram_plan(amgx_handle h, int64_t n, int ka, int kb, int symmetric, int32_t* chunk_rows, int32_t* n_blocks);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Rank-partitioned hierarchies (one process per GPU; SURVEY.md 8b "halo tables + RCCL communicator", 8e).
  *

@@ -243,6 +243,29 @@ class AMGMatrix:
         """BaseMatrix::Mult on a MultiVector: X[j] = C B[j], k right-hand sides per matrix pass (DeviceAMGMatrix.MultMulti)"""
         return self._dev.MultMulti(B, X, interleaved=interleaved, fuse=fuse)
 
+    def EigenSolve(self, num, mass=None, free=None, X0=None, tol=1e-8, maxit=200, history=True, fuse=False, seed=0):
+        """The num smallest eigenpairs of A x = lambda M x, A = the level-0 matrix, preconditioned by this cycle, all vectors
+        resident on the GPU: ngsamg_amd.eigen.lobpcg (LOBPCG; history=False: PINVIT) on device multi-vectors.  mass: an object
+        with apply_block(mv_in, mv_out) (None: the identity); free: 0/1 mask of the scalar dofs (None: the free dofs of the
+        hierarchy); X0: a (num, n) array or CUDA tensor (None: random columns from seed).  Returns (lams, X, info), X a
+        DeviceMultiVector (X.data: the (num, n) tensor)."""
+        import torch
+        from .eigen import lobpcg
+        from .multivector import DeviceMultiVector, MatVecMulti, MultMulti
+        dev = self._dev
+        device = torch.device("cuda", int(dev._cfg.get("device", 0)))
+        if free is None:
+            lv = self._hier.levels[0]
+            if getattr(lv, "free", None) is not None and len(lv.free) == lv.A.n_rows:
+                free = np.repeat(np.asarray(lv.free, dtype=np.float64), lv.A.br)
+        if free is not None and not hasattr(free, "is_cuda"):
+            free = torch.as_tensor(np.asarray(free, dtype=np.float64), device=device)
+        if X0 is not None and not isinstance(X0, DeviceMultiVector):
+            t = X0 if hasattr(X0, "is_cuda") else torch.as_tensor(np.asarray(X0, dtype=np.float64), device=device)
+            X0 = DeviceMultiVector(dev, t.contiguous())
+        return lobpcg(MatVecMulti(0, dev), MultMulti(dev), num, mass=mass, free=free, X0=X0, tol=tol, maxit=maxit, history=history,
+                      fuse=fuse, seed=seed)
+
     def MultAdd(self, s, b, x):
         return self._dev.MultAdd(s, b, x)
 
@@ -409,6 +432,10 @@ class _AMGPreconditioner:
 
     def MultMulti(self, B, X, interleaved=False, fuse=False):
         return self._need().MultMulti(B, X, interleaved=interleaved, fuse=fuse)
+
+    def EigenSolve(self, num, **kwargs):
+        """the num smallest eigenpairs of the finest matrix on the free dofs, preconditioned by this cycle (AMGMatrix.EigenSolve)"""
+        return self._need().EigenSolve(num, **kwargs)
 
     def MultAdd(self, s, b, x):
         return self._need().MultAdd(s, b, x)

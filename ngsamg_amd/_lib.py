@@ -243,6 +243,7 @@ AMGX_PCG_SINGLE_REDUCTION = 16
 AMGX_MULTI_INTERLEAVED = 32
 AMGX_MULTI_FUSE = 64
 AMGX_MULTI_MAX = 8
+AMGX_MV_MAX = 32                             # columns of a multi-vector in amgx_mv_gram / amgx_mv_combine
 
 AMGX_SYMBOLS = [
     "amgx_last_error", "amgx_create", "amgx_destroy", "amgx_set_stream", "amgx_synchronize", "amgx_apply",
@@ -259,6 +260,7 @@ AMGX_SYMBOLS = [
     "amgx_device_count", "amgx_spgemm", "amgx_galerkin", "amgx_csr_result_fetch",
     "amgx_apply_multi", "amgx_matvec_multi", "amgx_pcg_multi", "amgx_multi_info", "amgx_multi_plan", "amgx_multi_note",
     "amgx_smoother_info",
+    "amgx_mv_gram", "amgx_mv_combine", "amgx_mv_gram_plan",
 ]
 
 AMGH_SYMBOLS = [
@@ -317,6 +319,10 @@ def hip():
     lib.amgx_multi_plan.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_i64p]
     lib.amgx_multi_note.argtypes = [vp, C.c_int]
     lib.amgx_multi_note.restype = C.c_char_p
+    # multi-vector algebra (G and c are host arrays)
+    lib.amgx_mv_gram.argtypes = [vp, C.c_int64, C.c_int, dp, C.c_int64, C.c_int, dp, C.c_int64, c_f64p, C.c_int]
+    lib.amgx_mv_combine.argtypes = [vp, C.c_int64, C.c_int, dp, C.c_int64, c_f64p, C.c_int, C.c_double, dp, C.c_int64, C.c_int]
+    lib.amgx_mv_gram_plan.argtypes = [vp, C.c_int64, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p]
     # rank-partitioned hierarchies
     lib.amgx_comm_unique_id.argtypes = [C.c_char_p]
     lib.amgx_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(vp)]

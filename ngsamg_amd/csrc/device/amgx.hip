@@ -1400,6 +1400,8 @@ static bool build_sell_lw_windowed(const Knobs& K, int64_t n, int64_t n_cols, co
 struct MultiState;                      // multi-vector work space and captured graphs (multi.hpp)
 void multi_drop_graphs(MultiState* s);
 void multi_free(MultiState* s);
+struct MvState;                         // work space of the multi-vector algebra calls (mv.hpp)
+void mv_free(MvState* s);
 
 struct Handle {
   int device = 0;
@@ -1430,6 +1432,7 @@ struct Handle {
   struct GraphKey { const double* b; double* x; int kind; bool operator<(const GraphKey& o) const { return std::tie(b, x, kind) < std::tie(o.b, o.x, o.kind); } };
   GraphCache<GraphKey> graphs;
   MultiState* multi = nullptr;          // created by the first multi-vector call (multi.hpp)
+  MvState* mv = nullptr;                // created by the first amgx_mv_gram / amgx_mv_combine (mv.hpp)
   // staging for host-pointer calls
   DevBuf<double> stage[3];
   DevBuf<double> kr_ws[6];              // work vectors of amgx_pcg / amgx_gmres (krylov.hpp), kept between solves
@@ -1451,6 +1454,7 @@ struct Handle {
 
   ~Handle() {
     if (multi) multi_free(multi);
+    if (mv) mv_free(mv);
     graphs.drop();
     if (own_stream) (void)hipStreamDestroy(own_stream);
   }
@@ -3906,5 +3910,7 @@ static void cheb_estimate(Handle& h) {
 }  // namespace amgx
 
 #include "multi.hpp"
+#include "mv_kernels.hpp"      // Gram matrix and combination of multi-vectors
+#include "mv.hpp"
 #include "dist.hpp"
 #include "gss4.hpp"
