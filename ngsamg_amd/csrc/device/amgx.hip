@@ -339,7 +339,7 @@ struct DevCsr {                         // plain CSR copy for the single-workgro
 enum DownPath : int {                   // fused down kernel (pre-smoothing + restriction)
   DOWN_NONE = 0, DOWN_SELL = 1, DOWN_WIN = 2, DOWN_LW = 3, DOWN_DIA = 4,     // Jacobi: A' as SELL / windowed SELL / local window; diagonal image
   DOWN_CHEB = 5,                        // Chebyshev from zero, then residual + restriction
-  DOWN_GSB = 6,                         // block-hybrid sweep from zero + gsb_residual_restrict (internal: entry 0 reports it as 0)
+  DOWN_GSB = 6,                         // block-hybrid sweep from zero + residual_restrict_after_zero (internal: entry 0 reports it as 0)
   DOWN_DIA_BOX = 7                      // diagonal image on box chunks (internal: entry 0 reports DOWN_DIA, entry 4 reports 2)
 };
 enum SweepPath : int {                  // Gauss-Seidel form
@@ -350,15 +350,23 @@ struct LevelPaths {
   int sweep = SWEEP_NONE;
   bool plain = true;                    // sm_steps <= 1 && !sm_symm: the smoother is one base step, no ProxySmoother around it
   bool folded = false;                  // the V-cycle runs Q on the way up (see fold_prolongation)
+  // the Gauss-Seidel step (Handle::sweep, sweep_from_zero, residual_after_zero read these and never the images' flags)
+  bool in_place = true;                 // the sweep updates x in place; otherwise it reads xin and writes xout (SWEEP_GSB, SWEEP_BGSB)
+  bool zero_split = false;              // the level has the images for "sweep from zero over the lower couplings, residual from the rest"
+  int unit_rows = 0;                    // block rows of one sweep block, the unit of a partial sweep of the hybrid forms (0: the units are colours)
   bool jacobi_down() const { return down == DOWN_SELL || down == DOWN_WIN || down == DOWN_LW || down == DOWN_DIA || down == DOWN_DIA_BOX; }
   bool bgsb() const { return sweep == SWEEP_BGSB || sweep == SWEEP_BGSB_BC; }     // block-hybrid forms: square-block levels,
   bool hybrid() const { return sweep == SWEEP_GSB || bgsb(); }                    //   ... or any level
 };
 
+// Part of a Gauss-Seidel sweep: the units [beg, end) (end < 0: up to the last one).  A unit is a sweep block of
+// LevelPaths::unit_rows block rows on the hybrid forms and a colour on the multicolour and aggregate-block forms.
+struct Units { int beg = 0, end = -1; };
+
 struct DevLevel {
   LevelPaths paths;
   // the fused down launches (down_plan.hpp, Handle::down_launch): through RF -- Jacobi from zero, or the residual after Chebyshev --
-  // and through RG, the residual after a block-hybrid sweep (gsb_residual_restrict)
+  // and through RG, the residual after a block-hybrid sweep (residual_restrict_after_zero)
   DownPlan plan_rf, plan_rg;
   DevCsr tA, tApre, tP, tPT;            // only on tail levels
   DevBuf<int32_t> t_rowlist, t_cptr, t_rowcolor;    // colour-major row list (and the colour of every row) of a Gauss-Seidel tail level
@@ -473,13 +481,16 @@ static void resolve_paths(DevLevel& L) {
   else if (L.bgsb.on()) p.sweep = L.bgsb.bc ? SWEEP_BGSB_BC : SWEEP_BGSB;
   else if (L.gsb.on()) p.sweep = SWEEP_GSB;
   else if (L.gs.n_colors > 0) p.sweep = L.bs == 1 ? SWEEP_MC : (L.gs.bsell_ok ? SWEEP_MC_BSELL : SWEEP_MC_ROWLIST);
+  p.in_place = p.sweep != SWEEP_GSB && p.sweep != SWEEP_BGSB;
+  p.zero_split = p.bgsb() ? L.bgsb.has_split : p.sweep == SWEEP_GSB ? L.gsb.has_split : p.sweep == SWEEP_MC ? L.gs.has_split : p.sweep == SWEEP_MC_BSELL && L.gs.bsplit;
+  p.unit_rows = p.bgsb() ? L.bgsb.BB : p.sweep == SWEEP_GSB ? L.gsb.B : 0;
   if (p.plain && L.sm_type == AMGX_SM_JACOBI && !L.RF.empty())
     p.down = !L.ApreLW.empty() ? DOWN_LW : L.dia.on() ? (L.RF.boxed ? DOWN_DIA_BOX : DOWN_DIA) : L.Apre.sell.win ? DOWN_WIN : DOWN_SELL;
   else if (p.plain && L.sm_type == AMGX_SM_CHEBY && !L.RF.empty()) p.down = DOWN_CHEB;
   else if (p.plain && p.sweep == SWEEP_GSB && L.gsb.has_split && !L.RG.empty()) p.down = DOWN_GSB;
   L.paths = p;
   L.plan_rf = p.jacobi_down() ? make_down_plan(L, L.RF, 0, p.down) : p.down == DOWN_CHEB ? make_down_plan(L, L.RF, 2) : DownPlan();
-  // (gsb_residual_restrict also serves the rank-partitioned driver, whatever the cycle's own down path is)
+  // (residual_restrict_after_zero also serves the rank-partitioned driver, whatever the cycle's own down path is)
   L.plan_rg = (L.gsb.on() && L.gsb.has_split && !L.RG.empty()) ? make_down_plan(L, L.RG, 1) : DownPlan();
 }
 
@@ -1732,19 +1743,20 @@ struct Handle {
   // one block-hybrid Gauss-Seidel sweep (gsb_sweep_kernel): ONE launch; xin == nullptr: sweep from x = 0
   // blk0, blk1: only the blocks [blk0, blk1) (blk1 < 0: all): blocks are independent of each other within a sweep, so the
   // rank-partitioned driver sweeps its boundary and interior blocks in separate launches around the halo exchange
-  void gsb_sweep(const DevLevel& L, int dir, const DevMatrix::Sell& copy, const double* xin, double* xout, const double* b,
-                 int blk0 = 0, int blk1 = -1) {
+  // The image follows from the call: from zero on a level with the split `lowin`, otherwise `full` (or its local-window form).
+  void gsb_sweep(const DevLevel& L, int dir, const double* xin, double* xout, const double* b, int blk0 = 0, int blk1 = -1) {
     Range rg("GSS3<bs=1>::SmoothRHS");
     const DevGSB& g = L.gsb;
     if (blk1 < 0 || blk1 > g.n_blocks) blk1 = g.n_blocks;
     if (blk1 <= blk0) return;
     if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
     const bool fz = xin == nullptr;
-    const bool lw = !fz && &copy == &g.full && g.lw;
+    const bool lowin = fz && L.paths.zero_split;
+    const bool lw = !fz && g.lw;
     GsbArgs a{g.rowid.p, g.slotcolor.p, L.dinv.p, b, g.n_colors, dir, lw ? g.flw_cptr.p : nullptr, lw ? g.flw_ccol.p : nullptr};
-    const SellMat M = lw ? g.fullLW.view() : copy.view();
-    const bool narrow = fz && &copy == &g.lowin && g.narrow;
-    const bool mid = !fz && &copy == &g.full && g.mid;
+    const SellMat M = lw ? g.fullLW.view() : lowin ? g.lowin.view() : g.full.view();
+    const bool narrow = lowin && g.narrow;
+    const bool mid = !fz && g.mid;
     // <workgroup size, lanes per row, from zero, entries per lane and pass, local-window image>; the mid-width and local-window
     // forms exist for more than one lane per row only
     auto run = [&](auto TT) {
@@ -1770,7 +1782,7 @@ struct Handle {
 
   // one block-hybrid Gauss-Seidel sweep on a square-block level (bgsb_sweep_kernel): ONE launch; xin == nullptr: from x = 0
   // blk0 / blk1: the sweep blocks [blk0, blk1) only (rank-partitioned levels: boundary blocks before, interior blocks beside the exchange)
-  void bgsb_sweep(const DevLevel& L, int dir, const double* xin, double* xout, const double* b, bool lower_only = false, int blk0 = 0, int blk1 = -1) {
+  void bgsb_sweep(const DevLevel& L, int dir, const double* xin, double* xout, const double* b, int blk0 = 0, int blk1 = -1) {
     Range rg("GSS3<bs=" + std::to_string(L.bs) + ">::SmoothRHS");
     const DevBGSB& g = L.bgsb;
     const size_t lds = (size_t)2 * g.BB * L.bs * sizeof(double) + (size_t)g.BB * sizeof(int);
@@ -1785,12 +1797,12 @@ struct Handle {
     };
     if (g.bc) {
       // block-coloured form: one in-place launch per block colour; from zero (xin == nullptr) the first colour reads nothing
-      // outside its blocks, the later ones the finished blocks of lower colours through `offlo` (lower_only: the split exists)
+      // outside its blocks, the later ones the finished blocks of lower colours through `offlo` (which exists with the split)
       if (blk0 != 0 || (blk1 >= 0 && blk1 != g.n_blocks)) throw Err("block-coloured Gauss-Seidel sweeps cover the whole level");
       if (xin != nullptr && xin != xout) throw Err("block-coloured Gauss-Seidel sweeps work in place");
       const bool fz = xin == nullptr;
       if (fz && dir != 0) throw Err("block-coloured Gauss-Seidel: the sweep from zero is a forward sweep");
-      if (fz && !(lower_only && g.has_split)) throw Err("block-coloured Gauss-Seidel from zero needs the split images (zero x and sweep in place instead)");
+      if (fz && !L.paths.zero_split) throw Err("block-coloured Gauss-Seidel from zero needs the split images (zero x and sweep in place instead)");
       const BSellMat OFFA = g.off.bsell.view(knobs.bsell_xmode), OFFL = g.offlo.bsell.view(knobs.bsell_xmode);
       for (int q = 0; q < g.n_bcolors; ++q) {
         const int c = dir ? g.n_bcolors - 1 - q : q;
@@ -1805,7 +1817,6 @@ struct Handle {
     if (blk1 < 0 || blk1 > g.n_blocks) blk1 = g.n_blocks;
     if (blk1 <= blk0) return;
     if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
-    (void)lower_only;
     const BSellMat OFF = g.off.bsell.view(knobs.bsell_xmode);
     const bool fz = xin == nullptr;
     if (fz) sweep(Int<1>{}, OFF, nullptr, blk0, blk1 - blk0, xin);
@@ -1836,6 +1847,64 @@ struct Handle {
         else block(Int<1024>{}, Int<16>{});
       };
       if (!dispatch<1, 2, 3, 6>(L.bs, run)) throw Err("unsupported block size for block Gauss-Seidel");
+    }
+  }
+
+  // ---- the Gauss-Seidel step of a level: these functions (and residual_restrict_after_zero below) are the only ones that
+  //      switch over LevelPaths::sweep; the smoothers, the cycles and the rank-partitioned drivers (dist.hpp) call them
+  // One sweep on the iterate `cur`; entries outside the swept units keep the values of `cur`.  Returns the buffer that holds the
+  // result: `cur` for the in-place forms (oth may be null), `oth` for the out-of-place ones.
+  double* sweep(const DevLevel& L, int dir, double* cur, double* oth, const double* b, const Units u = Units()) {
+    switch (L.paths.sweep) {
+      case SWEEP_GSB: gsb_sweep(L, dir, cur, oth, b, u.beg, u.end); return oth;
+      case SWEEP_BGSB: bgsb_sweep(L, dir, cur, oth, b, u.beg, u.end); return oth;
+      case SWEEP_BGSB_BC: bgsb_sweep(L, dir, cur, cur, b, u.beg, u.end); return cur;
+      case SWEEP_BGS: bgs_sweep(L, dir, cur, b, u.beg, u.end); return cur;
+      default: gs_sweep(L, dir, cur, b, false, u.beg, u.end); return cur;
+    }
+  }
+  // The forward sweep from x = 0.  With LevelPaths::zero_split it runs over the couplings to lower colours only -- everything
+  // else multiplies zeros -- and residual_after_zero gets r from the rest, so that A is read once in total.  r: the vector
+  // residual_after_zero will fill; the multicolour identity writes swept rows only, so r is cleared here, beside x.
+  void sweep_from_zero(const DevLevel& L, double* x, const double* b, double* r, const Units u = Units()) {
+    const LevelPaths& P = L.paths;
+    if (!P.in_place) { sweep(L, 0, nullptr, x, b, u); return; }        // (out of place: xin == nullptr is the sweep from zero)
+    if (P.sweep == SWEEP_BGSB_BC && P.zero_split) { bgsb_sweep(L, 0, nullptr, x, b, u.beg, u.end); return; }
+    zero(x, L.len());
+    if (!P.zero_split) { sweep(L, 0, x, nullptr, b, u); return; }
+    if (!r) throw Err("sweep_from_zero: the split multicolour form clears the residual vector too");
+    zero(r, L.len());
+    gs_sweep(L, 0, x, b, true, u.beg, u.end);
+  }
+  // r = b - A x right after sweep_from_zero(L, x, b, r), by the identity the level's images allow (x may carry ghost entries)
+  void residual_after_zero(const DevLevel& L, const double* x, const double* b, double* r) {
+    if (!L.paths.zero_split) { residual(L.A, x, b, r); return; }
+    switch (L.paths.sweep) {
+      case SWEEP_GSB:
+        // inside a block only couplings to lower colours contributed; (b - L_in x)_k = x_k / dinv_k on every swept row, hence
+        // r = b - A x = (1/dinv - a_kk) .* x - (A - L_in - D) x = c .* x - rest x
+        product<1, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
+        return;
+      case SWEEP_BGSB: case SWEEP_BGSB_BC: mult(L.bgsb.rest, x, r); return;        // r = rest x (see DevBGSB)
+      case SWEEP_MC: {
+        // b - L x - D x = 0 on every swept row, hence r = -U x (r on non-free rows is not needed: their prolongation rows are empty)
+        const DevGS& g = L.gs;
+        const int grid = (g.n_slices_total + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+        auto run = [&](auto GG) { launch(gs_upper_residual_kernel<GG()>, grid, BLOCK, 0, stream, g.n_slices_total, g.upper.view(), g.rowid.p, x, r); };
+        if (!dispatch<1, 2, 4, 8>(g.lanes, run)) run(Int<16>{});       // any other lane count: the 16-lane kernel
+        return;
+      }
+      case SWEEP_MC_BSELL: {
+        // block levels, same identity: r_B = -(U x)_B in one launch
+        const DevGS& g = L.gs;
+        const int ns = g.bupper.n_slices;
+        const int grid = (ns + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+        const BSellMat UM = g.bupper.bsell.view(knobs.bsell_xmode);
+        auto run = [&](auto BS) { launch(bgs_bsell_upper_residual_kernel<BS()>, grid, BLOCK, 0, stream, ns, UM, g.rowid.p, x, r); };
+        if (!dispatch<6, 3>(L.bs, run)) run(Int<2>{});                 // any other block size: the 2 x 2 kernel
+        return;
+      }
+      default: throw Err("residual_after_zero: the level's sweep form has no split identity");
     }
   }
 
@@ -1876,28 +1945,15 @@ struct Handle {
     } else if (L.sm_type == AMGX_SM_CHEBY) {
       // symmetric polynomial smoother: Smooth and SmoothBack are the same operation
       cheb_smooth(L, x, x, b, res, res_updated, update_res, x_zero);
-    } else if (L.sm_type == AMGX_SM_BGS) {
-      // BSmoother::Smooth / SmoothBack (block_gssmoother.cpp:434-498): like GSS3 the reference updates the residual by
-      // row-transpose scatters when asked for it; here: gather (RHS) form + one residual SpMV, same x and res
-      bgs_sweep(L, dir, x, b);
-      if (update_res) residual(L.A, x, b, res);
-    } else if (L.paths.sweep == SWEEP_BGSB_BC) {
-      bgsb_sweep(L, dir, x, x, b);                          // block-coloured form: in place
-      if (update_res) residual(L.A, x, b, res);
-    } else if (L.paths.sweep == SWEEP_BGSB) {
-      copy(L.tmp.p, x, L.ext_len());
-      bgsb_sweep(L, dir, L.tmp.p, x, b);
-      if (update_res) residual(L.A, x, b, res);
-    } else if (L.paths.sweep == SWEEP_GSB) {
-      // block-hybrid sweep (out of place: the off-block values are those from the start of the sweep)
-      copy(L.tmp.p, x, L.ext_len());
-      gsb_sweep(L, dir, L.gsb.full, L.tmp.p, x, b);
-      if (update_res) residual(L.A, x, b, res);
     } else {
-      // GSS3::Smooth / SmoothBack (gssmoother.cpp:350-398).  The reference keeps the residual current with
-      // row-transpose scatters (RES form); for symmetric A the gather (RHS) form followed by one residual
-      // SpMV gives the same x and res, and it has no write conflicts on a GPU.
-      gs_sweep(L, dir, x, b);
+      // GSS3::Smooth / SmoothBack (gssmoother.cpp:350-398), BSmoother::Smooth / SmoothBack (block_gssmoother.cpp:434-498).  The
+      // reference keeps the residual current with row-transpose scatters (RES form); for symmetric A the gather (RHS) form
+      // followed by one residual SpMV gives the same x and res, and it has no write conflicts on a GPU.
+      if (L.paths.in_place) sweep(L, dir, x, nullptr, b);
+      else {
+        copy(L.tmp.p, x, L.ext_len());       // (out of place: the off-block values are those from the start of the sweep)
+        sweep(L, dir, L.tmp.p, x, b);
+      }
       if (update_res) residual(L.A, x, b, res);
     }
   }
@@ -1979,56 +2035,10 @@ struct Handle {
       }
     } else if (P.plain && L.sm_type == AMGX_SM_CHEBY) {
       cheb_smooth(L, x, x, b, r, false, true, true);     // from zero: step 1 reads b, no SpMV
-    } else if (P.plain && P.bgsb()) {
-      // forward block-hybrid sweep from x = 0 (nothing outside the workgroup's rows is read), then the residual; with the
-      // split copies A is read once in total: r = rest * x (see DevBGSB)
-      if (L.bgsb.has_split) {
-        bgsb_sweep(L, 0, nullptr, x, b, true);
-        mult(L.bgsb.rest, x, r);
-      } else if (P.sweep == SWEEP_BGSB_BC) {
-        zero(x, L.len());                      // (pseudo-inverted diagonal blocks: no split images)
-        bgsb_sweep(L, 0, x, x, b);
-        residual(L.A, x, b, r);
-      } else {
-        bgsb_sweep(L, 0, nullptr, x, b);
-        residual(L.A, x, b, r);
-      }
-    } else if (P.plain && P.sweep == SWEEP_GSB) {
-      // forward block-hybrid sweep from x = 0: inside a block only couplings to lower colours contribute (all other
-      // values are still 0); afterwards (b - L_in x)_k = x_k / dinv_k on every swept row, hence
-      // r = b - A x = (1/dinv - a_kk) .* x - (A - L_in - D) x = c .* x - rest x
-      if (L.gsb.has_split) {
-        gsb_sweep(L, 0, L.gsb.lowin, nullptr, x, b);
-        product<1, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
-      } else {
-        gsb_sweep(L, 0, L.gsb.full, nullptr, x, b);
-        residual(L.A, x, b, r);
-      }
-    } else if (P.plain && L.sm_type == AMGX_SM_GS && L.gs.has_split && L.bs == 1) {
-      // forward sweep from x = 0: only couplings to lower colours contribute; afterwards b - L x - D x = 0 on every
-      // swept row, hence r = -U x (r on non-free rows is not needed: their prolongation rows are empty)
-      zero(x, L.len());
-      zero(r, L.len());
-      gs_sweep(L, 0, x, b, true);
-      const DevGS& g = L.gs;
-      const int grid = (g.n_slices_total + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-      auto run = [&](auto GG) { launch(gs_upper_residual_kernel<GG()>, grid, BLOCK, 0, stream, g.n_slices_total, g.upper.view(), g.rowid.p, x, r); };
-      if (!dispatch<1, 2, 4, 8>(g.lanes, run)) run(Int<16>{});       // any other lane count: the 16-lane kernel
-    } else if (P.plain && L.sm_type == AMGX_SM_GS && L.gs.bsplit && L.bs > 1) {
-      // block levels, same identity: forward sweep over the lower-colour couplings, then r_B = -(U x)_B in one launch
-      zero(x, L.len());
-      zero(r, L.len());
-      gs_sweep(L, 0, x, b, true);
-      const DevGS& g = L.gs;
-      const int ns = g.bupper.n_slices;
-      const int grid = (ns + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-      const BSellMat UM = g.bupper.bsell.view(knobs.bsell_xmode);
-      auto run = [&](auto BS) { launch(bgs_bsell_upper_residual_kernel<BS()>, grid, BLOCK, 0, stream, ns, UM, g.rowid.p, x, r); };
-      if (!dispatch<6, 3>(L.bs, run)) run(Int<2>{});                 // any other block size: the 2 x 2 kernel
     } else if (P.plain && L.sm_type == AMGX_SM_GS) {
-      zero(x, L.len());
-      gs_sweep(L, 0, x, b);
-      residual(L.A, x, b, r);
+      // forward sweep from x = 0, then the residual by the identity the level's images allow
+      sweep_from_zero(L, x, b, r);
+      residual_after_zero(L, x, b, r);
     } else {
       zero(x, L.len());
       copy(r, b, L.len());
@@ -2128,20 +2138,20 @@ struct Handle {
       down_launch(l, L.plan_rf, down_ops_cheb(x, b), b_coarse);
     } else if (L.paths.down == DOWN_GSB && whole) {
       // sweep from zero, then residual of the untouched part + chunk-local restriction in one pass (r stays in LDS)
-      gsb_sweep(L, 0, L.gsb.lowin, nullptr, x, b);
-      gsb_residual_restrict(l, x, r, b_coarse);
+      sweep_from_zero(L, x, b, r);
+      residual_restrict_after_zero(l, x, b, r, b_coarse);
     } else {
       pre_smooth(L, x, b, r, fold, sp);
       if (sp.part != PART_INT) transfer_f2c(l, r, b_coarse);
     }
   }
 
-  // after a block-hybrid sweep from zero: r = c .* x - A_rest x (x may carry ghost entries) and b_coarse = P^T r
-  void gsb_residual_restrict(int l, const double* x, double* r, double* b_coarse) {
+  // residual_after_zero followed by the restriction b_coarse = P^T r; fused into one launch (r stays in LDS) where the level has
+  // the plan for it
+  void residual_restrict_after_zero(int l, const double* x, const double* b, double* r, double* b_coarse) {
     DevLevel& L = lev[l];
-    if (!L.gsb.has_split) throw Err("gsb_residual_restrict: the level has no lower / rest split");
-    if (L.plan_rg.on) { down_launch(l, L.plan_rg, down_ops_gsb(L, x), b_coarse); return; }
-    product<1, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
+    if (L.paths.sweep == SWEEP_GSB && L.plan_rg.on) { down_launch(l, L.plan_rg, down_ops_gsb(L, x), b_coarse); return; }
+    residual_after_zero(L, x, b, r);
     transfer_f2c(l, r, b_coarse);
   }
 
@@ -2172,15 +2182,10 @@ struct Handle {
       double* t = cheb_place(cheb_passes(L.cheb_degree, ChebEntry::ITERATE), x, L.tmp.p);
       mult_add(L.P, 1.0, xc, x, t);
       cheb_smooth(L, t, x, b, r, false, false, false);
-    } else if (P.plain && P.sweep == SWEEP_BGSB_BC) {
-      mult_add(L.P, 1.0, xc, x, x);        // x += P x_c
-      probed(probe, [&] { bgsb_sweep(L, 1, x, x, b); });          // backward block-coloured sweep, in place (one launch per block colour)
-    } else if (P.plain && P.sweep == SWEEP_BGSB) {
-      mult_add(L.P, 1.0, xc, x, L.tmp.p);  // tmp = x + P x_c
-      probed(probe, [&] { bgsb_sweep(L, 1, L.tmp.p, x, b); });    // backward block-hybrid sweep, tmp -> x
-    } else if (P.plain && P.sweep == SWEEP_GSB && L.n == L.ncols) {
-      mult_add(L.P, 1.0, xc, x, L.tmp.p);  // tmp = x + P x_c
-      probed(probe, [&] { gsb_sweep(L, 1, L.gsb.full, L.tmp.p, x, b); });   // backward block-hybrid sweep, tmp -> x
+    } else if (P.plain && P.hybrid() && (P.sweep != SWEEP_GSB || L.n == L.ncols)) {
+      double* const t = P.in_place ? x : L.tmp.p;
+      mult_add(L.P, 1.0, xc, x, t);        // t = x + P x_c
+      probed(probe, [&] { sweep(L, 1, t, x, b); });               // backward sweep, t -> x: ONE launch, or one per block colour in place
     } else {
       add_c2f(l, 1.0, x, xc);
       level_smooth(L, 1, x, b, r, false, false, false);
@@ -3751,7 +3756,7 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
         v[29] = gsb.mid;
         v[30] = gsb.lw;
         v[32] = gsb.has_fullLW ? gsb.flw_no_window : 0;
-        // (the form gsb_residual_restrict picks; only where the cycle's down pass runs it)
+        // (the form residual_restrict_after_zero picks; only where the cycle's down pass runs it)
         if (down == amgx::DOWN_GSB) v[33] = L.plan_rg.family == amgx::DOWN_FAM_LW ? 3 : L.plan_rg.family == amgx::DOWN_FAM_WIN ? 2 : 1;
         break;
       case amgx::SWEEP_MC: v[20] = gs.lanes; v[21] = amgx::BLOCK; v[23] = gs.n_colors; v[25] = gs.has_split; break;

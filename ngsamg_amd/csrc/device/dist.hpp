@@ -411,8 +411,7 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
       const int64_t ns = hd.n_peers > 0 ? hd.send_ptr[hd.n_peers] : 0;
       if (lp.bgsb() && s.gs_block_ids) throw Err("amgx_dist_create: rank-partitioned block levels sweep runs of consecutive rows (no gs_block_ids)");
       if (lp.sweep == SWEEP_BGSB_BC) throw Err("amgx_dist_create: rank-partitioned block levels sweep in the hybrid form (no gs_block_color)");
-      const int64_t B = lp.sweep == SWEEP_GSB ? D->top->lev[l].gsb.B : D->top->lev[l].bgsb.BB;
-      const int64_t first_bnd = (D->halo[l].n_int / B) * B;
+      const int64_t first_bnd = (D->halo[l].n_int / lp.unit_rows) * lp.unit_rows;
       for (int64_t i = 0; i < ns; ++i)
         if (hd.send_idx[i] < first_bnd) { D->send_early[l] = 0; break; }
     }
@@ -576,26 +575,19 @@ struct DistCycle {
   //      out of place (it zeroes the ghosts only, prolongs into text, exchanges text, has its own residual forms and carries
   //      the probe).  A description of the ranges and the sweep that covers both is longer than the two loops.
   //
-  //      Block-hybrid form (gsb_sweep_kernel / bgsb_sweep_kernel): the blocks of a sweep are independent of each other
-  //      (couplings that leave a block -- ghost columns included -- use the sweep-start vector), so the boundary blocks are
+  //      Block-hybrid form (scalar and square-block levels alike: Handle::sweep with a block range): the blocks of a sweep are
+  //      independent of each other (couplings that leave a block -- ghost columns included -- use the sweep-start vector), so the boundary blocks are
   //      swept first, the exchange of x starts, and the interior blocks run behind it; on the way up the interior blocks
   //      run while x + P x_c travels.  Two launches per sweep instead of one per colour and stage.
   void hybrid_gsb() {
     // (a level with a sent row inside an interior block sweeps all its blocks before the exchange: see Dist::send_early)
-    auto nbi = [&](Dist& d, int l) {
-      const DevLevel& L = d.top->lev[l];
-      return d.send_early[l] ? (int)(d.halo[l].n_int / (L.paths.sweep == SWEEP_GSB ? L.gsb.B : L.bgsb.BB)) : 0;
-    };
-    // scalar levels: gsb_sweep_kernel; square-block levels: bgsb_sweep_kernel (same block ranges, same stages)
+    auto nbi = [&](Dist& d, int l) { return d.send_early[l] ? (int)(d.halo[l].n_int / d.top->lev[l].paths.unit_rows) : 0; };
+    // the blocks [q0, q1) of the level (q1 < 0: up to the last one), from x = 0 and backward on x + P x_c
     auto sweep_zero = [&](Dist& d, size_t i, int l, int q0, int q1) {
-      DevLevel& L = d.top->lev[l];
-      if (L.paths.bgsb()) d.top->bgsb_sweep(L, 0, nullptr, d.xext[l].p, bl(d, i, l), L.bgsb.has_split, q0, q1);
-      else d.top->gsb_sweep(L, 0, L.gsb.has_split ? L.gsb.lowin : L.gsb.full, nullptr, d.xext[l].p, bl(d, i, l), q0, q1);
+      d.top->sweep_from_zero(d.top->lev[l], d.xext[l].p, bl(d, i, l), d.rl[l].p, {q0, q1});
     };
     auto sweep_back = [&](Dist& d, size_t i, int l, int q0, int q1) {
-      DevLevel& L = d.top->lev[l];
-      if (L.paths.bgsb()) d.top->bgsb_sweep(L, 1, d.text[l].p, xl(d, i, l), bl(d, i, l), false, q0, q1);
-      else d.top->gsb_sweep(L, 1, L.gsb.full, d.text[l].p, xl(d, i, l), bl(d, i, l), q0, q1);
+      d.top->sweep(d.top->lev[l], 1, d.text[l].p, xl(d, i, l), bl(d, i, l), {q0, q1});
     };
     for (int l = 0; l < k; ++l) {
       each([&](Dist& d, size_t i) {
@@ -605,15 +597,7 @@ struct DistCycle {
       const int tk = c.exchange_begin(items(l, 1));
       each([&](Dist& d, size_t i) { sweep_zero(d, i, l, 0, nbi(d, l)); });
       c.exchange_end(tk);
-      each([&](Dist& d, size_t i) {
-        DevLevel& L = d.top->lev[l];
-        if (L.paths.sweep == SWEEP_GSB && L.gsb.has_split) d.top->gsb_residual_restrict(l, d.xext[l].p, d.rl[l].p, bnext(d, l));
-        else {
-          if (L.paths.bgsb() && L.bgsb.has_split) d.top->mult(L.bgsb.rest, d.xext[l].p, d.rl[l].p);      // r = rest x (see DevBGSB)
-          else d.top->residual(L.A, d.xext[l].p, bl(d, i, l), d.rl[l].p);
-          d.top->transfer_f2c(l, d.rl[l].p, bnext(d, l));
-        }
-      });
+      each([&](Dist& d, size_t i) { d.top->residual_restrict_after_zero(l, d.xext[l].p, bl(d, i, l), d.rl[l].p, bnext(d, l)); });
     }
     tail();
     for (int l = k - 1; l >= 0; --l) {
@@ -631,10 +615,7 @@ struct DistCycle {
 
   //      Staged multicolour form: stages LOC_1 / EX / LOC_2 = colour ranges (gssmoother.cpp:721-782)
   void sweep(Dist& d, size_t i, int l, int dir, int c0, int c1) {
-    if (c1 <= c0) return;
-    DevLevel& L = d.top->lev[l];
-    if (d.sm_type == AMGX_SM_BGS) d.top->bgs_sweep(L, dir, d.xext[l].p, bl(d, i, l), c0, c1);
-    else d.top->gs_sweep(L, dir, d.xext[l].p, bl(d, i, l), false, c0, c1);
+    if (c1 > c0) d.top->sweep(d.top->lev[l], dir, d.xext[l].p, nullptr, bl(d, i, l), {c0, c1});
   }
   void hybrid_gs() {
     for (int l = 0; l < k; ++l) {
@@ -687,10 +668,7 @@ struct DistCycle {
       double*& oth = gx[l].oth[i];
       const double* b = bl(d, i, l);
       if (d.sm_type == AMGX_SM_JACOBI) { h.jacobi_fused(L, cur, b, oth); std::swap(cur, oth); }
-      else if (L.paths.bgsb()) { h.bgsb_sweep(L, dir, cur, oth, b); std::swap(cur, oth); }
-      else if (L.paths.sweep == SWEEP_GSB) { h.gsb_sweep(L, dir, L.gsb.full, cur, oth, b); std::swap(cur, oth); }
-      else if (d.sm_type == AMGX_SM_BGS) h.bgs_sweep(L, dir, cur, b);
-      else h.gs_sweep(L, dir, cur, b);
+      else if (h.sweep(L, dir, cur, oth, b) == oth) std::swap(cur, oth);       // (the out-of-place forms leave x in the spare buffer)
     });
   }
   // sm_steps steps in direction dir, or sm_steps x (forward, backward) with sm_symm

@@ -426,6 +426,17 @@ def test_loopback_device_elasticity_block_hybrid_gs(R, box, rot, B):
     block rows -- boundary blocks, exchange of x, interior blocks; one-pass pre-smoothing with the `rest` image over
     [owned | ghost] columns; the block diagonal modified by every coupling that leaves a sweep block (other blocks of the rank and
     ghost columns alike) -- == the oracle's serial hybrid GS with the same blocks, colours and diagonal"""
+    _, orc, bh = _elasticity_block_hybrid_gs(R, box, rot, B)
+    assert orc.pcg(np.concatenate(bh), tol=1e-8, maxit=60)[1] < 45
+
+
+def _split_flags(amg):
+    """gs_split of every rank-partitioned level of every rank, as amgx_level_paths reports it"""
+    return [o.top.level_paths(l)["gs_split"] for o in amg._dev.ops for l in range(amg.k)]
+
+
+def _elasticity_block_hybrid_gs(R, box, rot, B, **cycle):
+    """the cycle of the elasticity hierarchy with sm_type = hgs against the oracle's; cycle: sm_steps / sm_symm / mg_cycle"""
     import torch
     from ngsamg_amd import dist as D
     from oracle.pyoracle import Oracle
@@ -434,7 +445,7 @@ def test_loopback_device_elasticity_block_hybrid_gs(R, box, rot, B):
     pg = D.proc_grid(R, 3)
     states = [D.assemble_elasticity_owned(r, pg, box, rotations=rot) for r in range(R)]
     amg = D.DistributedAMG(comm, states, dim=3, dist_min_rows=150, device=0, max_coarse_size=5, energy=1, regularize_cmats=0 if rot else 1,
-                           sm_type="hgs", **({"hgs_block_rows": B} if B else {}))
+                           sm_type="hgs", **({"hgs_block_rows": B} if B else {}), **cycle)
     assert amg.k >= 1 and all(s.gs_B > 0 for s in amg.dist_levels[0])
     bs0 = states[0].bs
     rng = np.random.default_rng(0)
@@ -445,11 +456,26 @@ def test_loopback_device_elasticity_block_hybrid_gs(R, box, rot, B):
         amg.Mult(bs, xs)
     torch.cuda.synchronize()
     glv = amg.global_levels()
-    orc = Oracle(glv, sm_type=oracle_sm_types(amg), bgs=oracle_bgs(amg, glv))
+    okw = {{"mg_cycle": "cycle"}.get(k, k): v for k, v in cycle.items()}
+    orc = Oracle(glv, sm_type=oracle_sm_types(amg), bgs=oracle_bgs(amg, glv), **okw)
     ref = orc.apply(np.concatenate(bh))
     got = np.concatenate([x.cpu().numpy() for x in xs])
     assert np.linalg.norm(got - ref) <= 1e-10 * np.linalg.norm(ref)
-    assert orc.pcg(np.concatenate(bh), tol=1e-8, maxit=60)[1] < 45
+    return amg, orc, bh
+
+
+def test_loopback_device_elasticity_block_hybrid_gs_without_split(monkeypatch):
+    """AMGX_BGSB_NO_SPLIT on rank-partitioned block levels: the sweep from zero in two block ranges around the exchange, then the
+    plain residual on A instead of r = rest x -- the same cycle, so the same oracle"""
+    monkeypatch.setenv("AMGX_BGSB_NO_SPLIT", "1")
+    amg, _, _ = _elasticity_block_hybrid_gs(2, (12, 9, 9), False, 42)
+    assert not any(_split_flags(amg))
+
+
+def test_loopback_device_steps_block_hybrid_gs_elasticity():
+    """the step-by-step driver on square-block hybrid levels (two forward sweeps down, two backward sweeps up, every one out of
+    place behind an exchange of x) against the oracle's serial hybrid sweeps with sm_steps = 2"""
+    _elasticity_block_hybrid_gs(2, (12, 9, 9), False, 42, sm_steps=2, sm_symm=False, mg_cycle="V")
 
 
 def test_rccl_world_size_one_elasticity_hybrid_gs():
@@ -467,6 +493,18 @@ def test_rccl_world_size_one_elasticity_block_hybrid_gs():
 def test_loopback_device_block_hybrid_gs(R, box, dim, dmin):
     """sm_type = hgs on rank-partitioned levels through the native driver (boundary blocks, exchange, interior blocks; two
     launches per sweep) == the oracle's serial hybrid GS with the same blocks (256 owned rows), colours and modified diagonal"""
+    _block_hybrid_gs(R, box, dim, dmin)
+
+
+def test_loopback_device_block_hybrid_gs_without_split(monkeypatch):
+    """AMGX_GSB_NO_SPLIT on rank-partitioned levels: the sweep from zero reads the whole block image, the residual is the plain
+    one on A followed by the unfused restriction -- the same cycle, so the same oracle"""
+    monkeypatch.setenv("AMGX_GSB_NO_SPLIT", "1")
+    amg = _block_hybrid_gs(2, (16, 16, 16), 3, 200)
+    assert not any(_split_flags(amg))
+
+
+def _block_hybrid_gs(R, box, dim, dmin):
     import torch
     from ngsamg_amd import dist as D
     from oracle.pyoracle import Oracle
@@ -486,6 +524,7 @@ def test_loopback_device_block_hybrid_gs(R, box, dim, dmin):
     ref = Oracle(glv, sm_type=oracle_sm_types(amg), bgs=oracle_bgs(amg, glv)).apply(np.concatenate(bh))
     got = np.concatenate([x.cpu().numpy() for x in xs])
     assert np.linalg.norm(got - ref) <= 1e-10 * np.linalg.norm(ref)
+    return amg
 
 
 @pytest.mark.parametrize("sm", ["jacobi", "gs", "hgs"])

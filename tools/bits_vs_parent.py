@@ -1,0 +1,251 @@
+#!/usr/bin/env python3
+"""Bits against another build of the device library: the same (handle, call) cases in a fresh child process per library -- first
+the tree's own build, then NGSAMG_HIP_LIB=<other build>, usually the parent commit's -- every result stored as .npy and compared
+with numpy.array_equal, level_paths(l) of every level of every handle compared as dictionaries.  Prints the table and a verdict.
+
+  python tools/bits_vs_parent.py --parent-lib <libngsamg_hip.so of the parent> --out <dir> [--report <file>]
+
+The cases are the Gauss-Seidel forms (every SweepPath value, with and without the split images where a kill switch exists) and
+the rank-partitioned drivers on two virtual ranks; edit CASES / DIST_CASES for the refactor at hand.  A child that fails ends
+the run: nothing more is started on the GPU after it."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FLAGS = ((False, False, False), (False, True, False), (True, True, True), (False, False, True))     # res_updated, update_res, x_zero
+BC = {"AMGX_BGSB_BC_MIN_ROWS": "0", "AMGX_BGSB_BC_MIN_WG": "0"}
+
+
+# ---- single rank: name, problem, DeviceAMGMatrix arguments, environment at create
+def _poisson(shape):
+    from tests.problems import poisson_case
+    p, H = poisson_case(shape)
+    return H, p.free, 1
+
+
+def _poisson_blocks(shape):
+    H, free, bs = _poisson(shape)
+    H.build_bgs()                                      # (aggregate blocks for sm_type "bgs")
+    return H, free, bs
+
+
+def _elasticity(shape):
+    from tests.problems import elasticity_case
+    p, H = elasticity_case(shape, rotations=False, max_coarse_size=10)
+    return H, p.free, p.bs
+
+
+def _scalar_rows(L, l1=False):
+    import numpy as np
+    from tests import reorder as R
+    A, B, free, H = R.gs_scalar_case(L, "identity")
+    if l1:
+        free = np.ones(A.shape[0], np.uint8)
+        H = R.gs_hierarchy(A, free, l1_dinv=True, seed=L)
+    return H, free, 1
+
+
+def _block_rows(bs, L=151, n=None, odd=False):
+    import numpy as np
+    from tests import reorder as R
+    n = n or {2: 700, 3: 500, 6: 400}[bs]
+    A = R.block_long_row_matrix(bs, L, n, seed=bs + L, odd_only=odd)
+    free = np.ones(n, np.uint8)
+    free[np.random.default_rng(bs).choice(n, size=7, replace=False)] = 0
+    return R.gs_hierarchy(A, free, bs=bs, seed=bs), free, bs
+
+
+CYCLES = [dict(mg_cycle="W"), dict(mg_cycle="BS"), dict(sm_steps=2), dict(sm_symm=True)]
+CASES = []
+for split in (True, False):
+    off = {} if split else {"AMGX_GSB_NO_SPLIT": "1"}
+    tag = "split" if split else "no split"
+    CASES += [(f"hybrid scalar 21^3 {tag}", (_poisson, (21, 21, 21)), dict(sm_type="hgs"), off, True),
+              (f"hybrid scalar rows of 64 {tag}", (_scalar_rows, 64), dict(sm_type="hgs"), off, True)]
+    CASES += [(f"hybrid scalar 21^3 {tag} {kw}", (_poisson, (21, 21, 21)), dict(sm_type="hgs", **kw), off, False) for kw in CYCLES]
+    off = {} if split else {"AMGX_BGSB_NO_SPLIT": "1"}
+    CASES += [(f"hybrid block bs=3 {tag}", (_block_rows, 3), dict(sm_type="hgs"), off, True),
+              (f"block-coloured bs=3 {tag}", (_block_rows, 3), dict(sm_type="hgs"), {**off, **BC}, True),
+              (f"block-coloured elasticity 14x13x12 {tag}", (_elasticity, (14, 13, 12)), dict(sm_type="hgs"), {**off, **BC}, True)]
+    CASES += [(f"hybrid block elasticity 14x13x12 {tag} {kw}", (_elasticity, (14, 13, 12)), dict(sm_type="hgs", **kw), off, False)
+              for kw in [{}] + CYCLES]
+    off = {} if split else {"AMGX_NO_BGS_SPLIT": "1"}
+    CASES += [(f"multicolour bsell bs=3 {tag}", (_block_rows, 3, 151, None, True), dict(sm_type="gs"), {"AMGX_BGS_BSELL_MIN": "1", **off}, True)]
+CASES += [("multicolour scalar 21^3 split", (_poisson, (21, 21, 21)), dict(sm_type="gs"), {}, True),
+          ("multicolour scalar rows of 15 split", (_scalar_rows, 15), dict(sm_type="gs"), {}, True),
+          ("multicolour scalar rows of 15 l1 diagonal, no split", (_scalar_rows, 15, True), dict(sm_type="gs"), {}, True),
+          ("multicolour row list bs=2", (_block_rows, 2, 17, 700), dict(sm_type="gs"), {"AMGX_NO_BGS_BSELL": "1"}, True),
+          ("aggregate blocks 14x13x12", (_poisson_blocks, (14, 13, 12)), dict(sm_type="bgs"), {}, True),
+          ("jacobi 21^3", (_poisson, (21, 21, 21)), dict(sm_type="jacobi"), {}, False)]
+
+# ---- two virtual ranks: name, problem, DistributedAMG arguments, environment at create
+HGS = dict(sm_type="hgs", hgs_block_rows=256)
+ELAST = dict(dist_min_rows=150, max_coarse_size=5, energy=1, regularize_cmats=1, sm_type="hgs", hgs_block_rows=42)
+STEPS = [dict(sm_steps=2, mg_cycle="V"), dict(mg_cycle="W")]
+DIST_CASES = [("dist hybrid scalar split", "poisson", dict(dist_min_rows=200, **HGS), {}),
+              ("dist hybrid scalar no split", "poisson", dict(dist_min_rows=200, **HGS), {"AMGX_GSB_NO_SPLIT": "1"}),
+              ("dist hybrid block split", "elasticity", ELAST, {}),
+              ("dist hybrid block no split", "elasticity", ELAST, {"AMGX_BGSB_NO_SPLIT": "1"}),
+              ("dist staged gs", "poisson", dict(dist_min_rows=200, sm_type="gs", gs_stage_min_rows=50), {}),
+              ("dist staged bgs", "poisson", dict(dist_min_rows=200, sm_type="bgs"), {}),
+              ("dist rank without rows hgs", "empty-rank", dict(dist_min_rows=60, gs_stage_min_rows=50, **HGS), {})]
+for kw in STEPS:
+    DIST_CASES += [(f"dist stepwise {sm} {kw}", "poisson", dict(dist_min_rows=200, **({"sm_type": sm} if sm != "hgs" else HGS), **kw), {})
+                   for sm in ("jacobi", "hgs", "gs", "bgs")]
+    DIST_CASES += [(f"dist stepwise hybrid block {kw}", "elasticity", dict(ELAST, **kw), {})]
+
+
+class _Env:
+    def __init__(self, env):
+        self.env = env
+
+    def __enter__(self):
+        os.environ.update(self.env)
+
+    def __exit__(self, *a):
+        for k in self.env:
+            del os.environ[k]
+
+
+def _single(store):
+    import numpy as np
+    from ngsamg_amd.device import DeviceAMGMatrix
+    paths = {}
+    for name, (make, *args), kw, env, smooth in CASES:
+        H, free, bs = make(*args)
+        with _Env(env):
+            dev = DeviceAMGMatrix(H, device=0, **kw)
+        paths[name] = [dev.level_paths(l) for l in range(dev.n_levels)]
+        fr = np.repeat(np.asarray(free) > 0, bs).astype(np.float64)
+        n = fr.size
+        rng = np.random.default_rng(7)
+        b = rng.standard_normal(n) * fr
+        for rep, graph in enumerate((True, True, False)):            # capture, replay, direct launches
+            x = np.full(n, np.nan)
+            dev.Mult(b, x, graph=graph)
+            if rep:
+                store(f"{name}|Mult graph={graph}", x)
+        if not smooth:
+            continue
+        A0 = H.levels[0].A.to_scipy()
+        for back in (False, True):
+            for ru, ur, xz in FLAGS:
+                x = np.zeros(n) if xz else rng.standard_normal(n) * fr
+                r = b - A0 @ x if ru else rng.standard_normal(n)
+                dev.Smooth(0, x, b, r, ru, ur, xz, back=back)
+                store(f"{name}|Smooth back={back} ru={ru} ur={ur} xz={xz}", np.concatenate([x, r]))
+    return paths
+
+
+def _dist_states(kind):
+    import numpy as np
+    from ngsamg_amd import dist as D
+    if kind == "poisson":
+        return D.LoopbackComm(2), [D.assemble_poisson_owned(r, D.proc_grid(2, 3), (16, 16, 16)) for r in range(2)], 1
+    if kind == "elasticity":
+        st = [D.assemble_elasticity_owned(r, D.proc_grid(2, 3), (12, 9, 9), rotations=False) for r in range(2)]
+        return D.LoopbackComm(2), st, st[0].bs
+    import scipy.sparse as sp
+    from ngsamg_amd import bridge as B
+    locs = []
+    for r in range(4):                               # four ranks with rows behind one that owns nothing
+        L, _ = B.shared_poisson_partition(r, (2, 2, 1), (17, 17, 9))
+        L.rank = r + 1
+        L.dist_procs = [np.asarray(p) + 1 for p in L.dist_procs]
+        locs.append(L)
+    empty = B.SharedLocal(0, sp.csr_matrix((0, 0)), [], free=np.zeros(0, dtype=np.uint8), coords=np.zeros((0, 3)))
+    comm = D.LoopbackComm(5)
+    return comm, B.from_shared_layout(comm, [empty] + locs)[0], 1
+
+
+def _dist(store):
+    import numpy as np
+    import torch
+    from ngsamg_amd import dist as D
+    paths = {}
+    for name, kind, kw, env in DIST_CASES:
+        comm, states, bs = _dist_states(kind)
+        kw = dict(kw)
+        kw.setdefault("max_coarse_size", 10)
+        with _Env(env):
+            amg = D.DistributedAMG(comm, states, dim=3, device=0, **kw)
+        paths[name] = [o.top.level_paths(l) for o in amg._dev.ops for l in range(amg.k)]
+        rng = np.random.default_rng(0)
+        b = [torch.from_numpy(rng.standard_normal(s.n * bs) * np.repeat(s.free, bs)).cuda() for s in states]
+        xs = [torch.full((s.n * bs,), float("nan"), dtype=torch.float64, device="cuda") for s in states]
+        for rep in range(3):                           # direct launches, capture, replay
+            amg.Mult(b, xs)
+            torch.cuda.synchronize()
+            if rep != 1:
+                store(f"{name}|Mult {'direct' if rep == 0 else 'replay'}", np.concatenate([x.cpu().numpy() for x in xs]))
+    return paths
+
+
+def child(out):
+    import numpy as np
+    os.makedirs(out, exist_ok=True)
+    index = {}
+
+    def store(name, v):
+        assert name not in index, name
+        index[name] = f"{len(index):04d}.npy"
+        np.save(os.path.join(out, index[name]), v)
+
+    paths = _single(store)
+    paths.update(_dist(store))
+    with open(os.path.join(out, "index.json"), "w") as f:
+        json.dump({"results": index, "level_paths": paths}, f, default=str)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--report")
+    ap.add_argument("--child")
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child)
+    import numpy as np
+    runs = (("tree", None), ("parent", os.path.abspath(a.parent_lib)))
+    for tag, lib in runs:
+        env = dict(os.environ)
+        env.pop("NGSAMG_HIP_LIB", None)
+        if lib:
+            env["NGSAMG_HIP_LIB"] = lib
+        rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", os.path.join(a.out, tag), "--out", a.out], env=env, timeout=900).returncode
+        if rc != 0:
+            sys.exit(f"the run with the {tag} library ended with status {rc}: nothing more is started")
+    T, P = (json.load(open(os.path.join(a.out, tag, "index.json"))) for tag, _ in runs)
+    lines, bad = [], 0
+    for name in sorted(set(T["results"]) | set(P["results"])):
+        same = name in T["results"] and name in P["results"]
+        if same:
+            x, y = (np.load(os.path.join(a.out, tag, I["results"][name])) for tag, I in (("tree", T), ("parent", P)))
+            same = np.array_equal(x, y) and not np.isnan(x).any()
+        bad += not same
+        lines.append(("same  " if same else "DIFF  ") + name)
+    nres, pbad = len(lines), 0
+    for name in sorted(set(T["level_paths"]) | set(P["level_paths"])):
+        same = T["level_paths"].get(name) == P["level_paths"].get(name)
+        pbad += not same
+        forms = " ".join(f"L{l}:{lp['gs_form']}/split={lp['gs_split']}" for l, lp in enumerate(T["level_paths"].get(name, [])) if lp.get("gs_form"))
+        lines.append(("same  " if same else "DIFF  ") + f"{name}|level_paths of {len(T['level_paths'].get(name, []))} levels: {forms}")
+    head = [f"results: {nres}   identical: {nres - bad}   different: {bad}",
+            f"handles: {len(lines) - nres}   level_paths identical: {len(lines) - nres - pbad}   different: {pbad}",
+            "verdict: " + ("IDENTICAL" if bad == 0 and pbad == 0 else "DIFFERENT"), "", "== cases (handle | call)"]
+    text = "\n".join(head + lines) + "\n"
+    print(text, end="")
+    if a.report:
+        with open(a.report, "w") as f:
+            f.write(text)
+    sys.exit(0 if bad == 0 and pbad == 0 else 1)
+
+
+if __name__ == "__main__":
+    main()
