@@ -466,7 +466,11 @@ typedef struct amgx_halo_desc {
 typedef struct amgx_dist_desc {
   amgx_hierarchy_desc top;    /* levels 0..k of this rank: A = owned rows x [owned | ghost]; P, PT rank-local; Jacobi   */
                               /*   levels with fold: Q (columns = coarse [owned | ghost]); dinv / colours / blocks as    */
-                              /*   usual (dinv over n_cols entries for Jacobi); level k: only A (its shape is used)      */
+                              /*   usual (dinv over n_cols entries for Jacobi and Chebyshev); level k: only A (its shape */
+                              /*   is used).  AMGX_SM_CHEBY levels: one cheb_degree and cheb_ratio on all of them, fp64  */
+                              /*   storage (mat_prec = AMGX_PREC_F32 is refused), no fold; cheb_lambda_max = 0: see      */
+                              /*   amgx_dist_cheb_estimate.  The replicated tail may use AMGX_SM_CHEBY as any handle.    */
+                              /*   Both need amgx_dist_desc.cheby = 1                                                    */
   const amgx_halo_desc* halo; /* [k] halo tables of the levels 0..k-1                                                    */
   amgx_hierarchy_desc tail;   /* replicated coarse hierarchy; its level 0 = level k gathered in rank order (CtrMap,      */
                               /*   src/base/coarsening/dof_contract.cpp:49-223, without the hop back)                    */
@@ -478,6 +482,9 @@ typedef struct amgx_dist_desc {
   const int32_t* gs_stage;    /* optional [4*k]: colour ranges of the hybrid Gauss-Seidel stages per level,              */
                               /*   [s0,s1) first local part, [s1,s2) rows that read ghosts ("EX"), [s2,s3) second local   */
                               /*   part (gssmoother.cpp:721-782); NULL: one stage                                        */
+  int32_t cheby;              /* opt-in, like AMGX_MULTI_FUSE: 1 = the caller asks for AMGX_SM_CHEBY levels in `top` /    */
+                              /*   `tail` (an own option beyond the reference; 2 x cheb_degree halo exchanges per level   */
+                              /*   and application).  0: a descriptor with such a level is refused, as it always was      */
 } amgx_dist_desc;
 
 int amgx_dist_create(amgx_comm c, const amgx_dist_desc* desc, amgx_dist* out);
@@ -487,6 +494,14 @@ int amgx_dist_destroy(amgx_dist d);
  * (b.Distribute() state, amg_matrix.cpp:164; DCCMap DIS2CO).  x: owned entries (CUMULATED on the owners).
  * flags: AMGX_HOST_PTR / AMGX_DEVICE_PTR. */
 int amgx_dist_apply(amgx_comm c, const double* const* b, double* const* x, int b_status, int flags);
+/* lambda_max(Dinv A) of the rank-partitioned AMGX_SM_CHEBY levels created with cheb_lambda_max = 0: the estimator of amgx_create
+ * (30 power steps, 1.1 x the last Rayleigh quotient) on the partitioned operator.  Start vector: the deterministic fill at every
+ * rank's LOCAL scalar index; an owner -> ghost exchange ahead of every product; the two inner products per step are deterministic
+ * local reductions + one all-reduce of two scalars, and every rank decides on the reduced values: all ranks end with bitwise the
+ * same interval, hence the same coefficients.  Collective (it cannot run inside amgx_dist_create: local ranks are created one by
+ * one); idempotent; a no-op when nothing is to be estimated.  amgx_dist_apply / _pcg / _gmres / _time_kernel call it first if it
+ * has not run.  Afterwards amgx_smoother_info on the borrowed top handle answers estimated = 1. */
+int amgx_dist_cheb_estimate(amgx_comm c);
 /* Preconditioned CG on the rank-partitioned level-0 operator, collectively (the reference's driver: NGSolve CGSolver on
  * ParallelVectors, tests/h1/amg_utils.py:337-363, whose inner products are MPI all-reduces): level-0 product with one owner ->
  * ghost exchange behind the interior rows, preconditioner = amgx_dist_apply (replayed from its graph), the two inner products

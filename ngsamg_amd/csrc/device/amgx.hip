@@ -1632,7 +1632,7 @@ struct Handle {
   void mult(const DevMatrix& M, const double* x, double* y, const Span sp = Span()) { product<1, EP_MULT>(M, x, y, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}, sp); }
   void residual(const DevMatrix& M, const double* x, const double* b, double* r, const Span sp = Span()) { product<1, EP_RES>(M, x, r, EpArgs{b, nullptr, nullptr, 0.0, nullptr, ep_nt & EPF_HOIST}, sp); }
   // the residual a smoother or the cycle forms on its level (update_res, the residual before the restriction): a smoother pass
-  void residual_sm(const DevLevel& L, const double* x, const double* b, double* r) { product<1, EP_RES>(L.A, x, r, EpArgs{b, nullptr, nullptr, 0.0, nullptr, ep_nt & EPF_HOIST}, Span(), true); }
+  void residual_sm(const DevLevel& L, const double* x, const double* b, double* r, const Span sp = Span()) { product<1, EP_RES>(L.A, x, r, EpArgs{b, nullptr, nullptr, 0.0, nullptr, ep_nt & EPF_HOIST}, sp, true); }
   // y = yin + s * M x
   void mult_add(const DevMatrix& M, double s, const double* x, const double* yin, double* y, const Span sp = Span()) { product<1, EP_AXPY>(M, x, y, EpArgs{nullptr, yin, nullptr, s, nullptr, ep_nt & EPF_HOIST}, sp); }
   // xout = xin + omega * dinv * (b - A xin)
@@ -1643,16 +1643,25 @@ struct Handle {
 
   // ---- Chebyshev smoother (AMGX_SM_CHEBY) ----
   // xout = (xin ? xin : 0) + c0 * Dinv * v, dout (optional) = the update
-  void cheb_first(const DevLevel& L, const double* v, const double* xin, double* xout, double* dout, double c0) {
-    if (L.n == 0) return;
-    const int grid = grid_for(L.n);
-    auto run = [&](auto BS) { launch(cheb_first_kernel<BS()>, grid, BLOCK, 0, stream, L.n, L.dinv.p, v, xin, xout, dout, c0); };
+  // The block rows [r0, r0 + rows) (default: the owned rows).  A rank-partitioned level may ask for its ghost rows too: v and
+  // dinv carry [owned | ghost] entries there.
+  void cheb_first(const DevLevel& L, const double* v, const double* xin, double* xout, double* dout, double c0, int64_t r0 = 0, int64_t rows = -1) {
+    if (rows < 0) rows = L.n - r0;
+    if (r0 < 0 || r0 + rows > L.ncols) throw Err("cheb_first: rows beyond the level's [owned | ghost] range");
+    if (rows <= 0) return;
+    const int grid = grid_for(rows);
+    const int64_t o = r0 * L.bs;
+    auto run = [&](auto BS) {
+      launch(cheb_first_kernel<BS()>, grid, BLOCK, 0, stream, rows, L.dinv.p + o * L.bs, v + o, xin ? xin + o : nullptr, xout + o, dout ? dout + o : nullptr, c0);
+    };
     if (!dispatch<1, 2, 3, 6>(L.bs, run)) throw Err("unsupported block size " + std::to_string(L.bs));
   }
   // one fused step: xout = xin + d_new, d_new = c1 * d_old + c2 * Dinv * (b - A xin); d_old == nullptr: xin; d_new == nullptr: not stored
-  void cheb_step(const DevLevel& L, const double* xin, const double* b, double* xout, double c1, double c2, const double* d_old, double* d_new) {
+  // sp: the interior / boundary rows of a rank-partitioned level (formats that are not split run in the boundary part: product())
+  void cheb_step(const DevLevel& L, const double* xin, const double* b, double* xout, double c1, double c2, const double* d_old, double* d_new,
+                 const Span sp = Span()) {
     if (xin == xout) throw Err("cheb_step: in-place update is not allowed");
-    product<1, EP_CHEB>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, c2, d_new, ep_nt, d_old, c1}, Span(), true);
+    product<1, EP_CHEB>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, c2, d_new, ep_nt, d_old, c1}, sp, true);
   }
   // One Chebyshev smooth of degree k with the flag contract of base_smooth.  The iterate lives in `src` (x itself or L.tmp, ignored
   // with x_zero) and ends in x; the passes and their operands are cheb_schedule's (cheb_schedule.hpp).  A caller that can choose
@@ -1660,7 +1669,8 @@ struct Handle {
   void cheb_smooth(DevLevel& L, const double* src, double* x, const double* b, double* res, bool res_updated, bool update_res, bool x_zero) {
     const int k = L.cheb_degree;
     if (k < 1 || !L.d.p) throw Err("Chebyshev smoother: the level has no coefficients");
-    if (L.ncols != L.n) throw Err("Chebyshev smoother: rank-partitioned levels are not supported");
+    // (single-rank callers only: on a rank-partitioned level the collective drivers of dist.hpp run the schedule around the exchanges)
+    if (L.ncols != L.n) throw Err("Chebyshev smoother: a rank-partitioned level is smoothed by the collective cycle (amgx_dist_apply)");
     double* const tmp = L.tmp.p;
     if (!x_zero && src != x && src != tmp) throw Err("Chebyshev smoother: the iterate must live in x or in the level's ping-pong buffer");
     const ChebEntry entry = x_zero ? ChebEntry::ZERO : (res_updated ? ChebEntry::RES_UPDATED : ChebEntry::ITERATE);

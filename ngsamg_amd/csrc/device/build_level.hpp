@@ -47,7 +47,8 @@ static void check_level(LevelBuild& B) {
     if (deg < 1 || deg > 8) throw Err("amgx_create: cheb_degree must be 1 .. 8 (0: default 2), got " + std::to_string(s.cheb_degree));
     if (!(s.cheb_lambda_max >= 0.0)) throw Err("amgx_create: cheb_lambda_max must be >= 0 (0: estimated on the device)");
     if (s.cheb_ratio != 0.0 && !(s.cheb_ratio > 1.0)) throw Err("amgx_create: cheb_ratio must be > 1 (0: default 10)");
-    if (s.A.n_cols != s.A.n_rows) throw Err("amgx_create: the Chebyshev smoother is not available on rank-partitioned levels");
+    // (ghost columns: only on the handle a rank-partitioned driver runs stage by stage -- dense_first < 0, amgx_dist_create)
+    if (s.A.n_cols != s.A.n_rows && B.dense_first >= 0) throw Err("amgx_create: a Chebyshev level with ghost columns belongs to a rank-partitioned hierarchy (amgx_dist_create)");
     L.cheb_degree = deg;
     L.cheb_ratio = s.cheb_ratio == 0.0 ? 10.0 : s.cheb_ratio;
     if (s.cheb_lambda_max > 0.0) L.cheb_set_interval(s.cheb_lambda_max);
@@ -756,7 +757,8 @@ static Handle* create(const amgx_hierarchy_desc* d, const Knobs& K, int dense_fi
     alloc_level_vectors(B);
     resolve_paths(B.L);                   // every image of the level is final here; nothing before this line runs a cycle or asks folded()
   }
-  cheb_estimate(*h);
+  // (the levels of a rank-partitioned hierarchy are estimated collectively, on the partitioned operator: amgx_dist_cheb_estimate)
+  if (dense_first >= 0) cheb_estimate(*h);
   clk.lap("Chebyshev intervals (power iteration)");
   if (d->clev == AMGX_CLEV_INV) build_coarse_inverse(*h, d, levels[d->n_levels - 1]);
   build_tail_program(*h, d, levels);

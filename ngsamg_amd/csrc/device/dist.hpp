@@ -110,14 +110,15 @@ struct HaloTable {                       // one level of one rank
 };
 
 struct Dist;
-// The driver of the collective cycle (DistCycle), resolved once by dist_create.  The first four are the specialised V(1,1)
-// stage sequences; STEPWISE serves sm_steps > 1 / sm_symm on a rank-partitioned level and the W-cycle.
+// The driver of the collective cycle (DistCycle), resolved once by dist_create.  The first four and CHEBY are the specialised
+// V(1,1) stage sequences; STEPWISE serves sm_steps > 1 / sm_symm on a rank-partitioned level and the W-cycle.
 enum class DistPath {
   JACOBI_FOLDED,       // Jacobi, post-smoothing folded into the prolongation
   JACOBI_LITERAL,      // Jacobi in the literal stage order
   GS_BLOCK_HYBRID,     // Gauss-Seidel levels in the block-hybrid form (gs_block_rows)
   GS_STAGED,           // multicolour / aggregate-block Gauss-Seidel in colour stages
   STEPWISE,            // one exchange and one launch per smoothing step
+  CHEBY,               // Chebyshev: the schedule of cheb_schedule.hpp, every product step behind the exchange of its iterate
 };
 }  // namespace amgx
 struct amgx_dist_t { amgx::Dist* d; };
@@ -137,6 +138,7 @@ struct Comm {
   std::vector<amgx_handle_t*> handle_views;
   std::string err;
   int64_t n_exchanges = 0;               // statistics: halo exchanges started
+  bool cheb_estimate_done = false;       // the collective lambda_max estimate has run (dist_cheb_estimate: once, before any capture)
   // Cross-stream ordering.  Measured on MI355X (tools/sync_lab.hip, profiles/r02/sync_lab.txt): one exchange-shaped
   // dependency pair costs 15 us of stream time with hipEventRecord / hipStreamWaitEvent and 9 us with
   // hipStreamWriteValue64 / hipStreamWaitValue64 on a device flag; the latter is used where the device supports it.
@@ -347,11 +349,27 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
   if (D->k < 1) throw Err("amgx_dist_create: need at least one rank-partitioned level and the gathered level");
   if (!d->halo || !d->counts || !d->kmap) throw Err("amgx_dist_create: halo tables / level-k tables missing");
   D->sm_type = d->top.levels[0].sm_type;
-  for (const amgx_hierarchy_desc* hd : {&d->top, &d->tail})
-    for (int l = 0; l < hd->n_levels; ++l)
-      if (hd->levels && hd->levels[l].sm_type == AMGX_SM_CHEBY)
-        throw Err("amgx_dist_create: the Chebyshev smoother (AMGX_SM_CHEBY) is not available on rank-partitioned hierarchies");
+  // Chebyshev levels are an opt-in of the descriptor (amgx_dist_desc.cheby): without it the type is refused as it always was
+  if (!d->cheby)
+    for (const amgx_hierarchy_desc* hd : {&d->top, &d->tail})
+      for (int l = 0; l < hd->n_levels; ++l)
+        if (hd->levels && hd->levels[l].sm_type == AMGX_SM_CHEBY)
+          throw Err("amgx_dist_create: the Chebyshev smoother (AMGX_SM_CHEBY) on a rank-partitioned hierarchy is an opt-in: set amgx_dist_desc.cheby = 1");
   const bool fold = d->fold != 0;
+  if (D->sm_type == AMGX_SM_CHEBY) {
+    // Chebyshev on the rank-partitioned levels: every rank runs the same recurrence with the same coefficients, so
+    // degree and ratio are those of level 0 everywhere (lambda_max may differ per level; without one it is estimated collectively)
+    if (fold) throw Err("amgx_dist_create: fold is the V(1,1) Jacobi form (not available with the Chebyshev smoother)");
+    const amgx_level_desc& s0 = d->top.levels[0];
+    for (int l = 0; l < D->k; ++l) {
+      const amgx_level_desc& s = d->top.levels[l];
+      if (s.sm_type != AMGX_SM_CHEBY) continue;             // (refused below: all levels use the same smoother)
+      if (s.cheb_degree != s0.cheb_degree || s.cheb_ratio != s0.cheb_ratio)
+        throw Err("amgx_dist_create: all rank-partitioned levels must use the same cheb_degree and cheb_ratio (level " + std::to_string(l) + " differs from level 0)");
+      if (s.mat_prec == AMGX_PREC_F32)
+        throw Err("amgx_dist_create: level " + std::to_string(l) + ": mat_prec = AMGX_PREC_F32 is not available on rank-partitioned levels");
+    }
+  }
   bool generic = false, gsb = false;
   D->cycle = d->top.cycle;
   if (D->cycle != AMGX_CYCLE_V && D->cycle != AMGX_CYCLE_W) throw Err("amgx_dist_create: rank-partitioned hierarchies run V and W cycles");
@@ -428,6 +446,7 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
     gsb = on == k;
   }
   D->path = generic ? DistPath::STEPWISE
+          : D->sm_type == AMGX_SM_CHEBY ? DistPath::CHEBY
           : D->sm_type == AMGX_SM_JACOBI ? (fold ? DistPath::JACOBI_FOLDED : DistPath::JACOBI_LITERAL)
           : gsb ? DistPath::GS_BLOCK_HYBRID : DistPath::GS_STAGED;
   D->bext.resize(k); D->xext.resize(k); D->text.resize(k); D->rl.resize(k);
@@ -647,6 +666,87 @@ struct DistCycle {
     }
   }
 
+  // ---- Chebyshev.  One smooth is the schedule of cheb_schedule.hpp on the global operator: a product step
+  //      reads the iterate on [owned | ghost] and writes owned rows, d lives on owned rows, and the owner -> ghost exchange of the
+  //      iterate precedes every product step whose input ghosts are not known.  The order of the rows plays no role, so the
+  //      result is the serial cycle's up to rounding.  The schedule is walked ONCE for all local ranks: its vectors are tokens,
+  //      resolved per rank to the two [owned | ghost] buffers X / T the iterate ping-pongs between and to the level's d.
+  //      first_all(out, c0): step 1 from zero on every rank, out(i) = rank i's buffer for x_1.  split: the interior rows of a
+  //      product step run beside the exchange of its iterate.  Returns whether the result lies in T.
+  template <class FirstAll>
+  bool cheb_smooth(int l, ChebEntry entry, bool src_in_t, const std::vector<double*>& X, const std::vector<double*>& T, bool split,
+                   bool ghosts_after_first, FirstAll&& first_all) {
+    double tx = 0.0, tt = 0.0, td = 0.0;
+    auto at = [&](const double* p, size_t i) { return p == &tx ? X[i] : T[i]; };
+    const DevLevel& L0 = M[0]->top->lev[l];
+    int tk = -1;
+    auto first = [&](const double*, const double*, double* xout, double*, double c0) { first_all([&](size_t i) { return at(xout, i); }, c0); };
+    auto exchange = [&](const double* v) {
+      std::vector<Comm::Item> it;
+      each([&](Dist& d, size_t i) { it.push_back({&d.halo[l], at(v, i)}); });
+      tk = c.exchange_begin(it);
+      if (!split) { c.exchange_end(tk); tk = -1; }
+    };
+    auto step = [&](const double* xin, double* xout, double c1, double c2, const double* d_old, double* d_new) {
+      overlapped(l, tk, [&](Dist& d, size_t i, Span sp) {
+        DevLevel& L = d.top->lev[l];
+        d.top->cheb_step(L, at(xin, i), bl(d, i, l), at(xout, i), c1, c2, d_old ? L.d.p : nullptr, d_new ? L.d.p : nullptr, sp);
+      });
+      tk = -1;
+    };
+    const double* end = cheb_schedule(L0.cheb_degree, L0.cheb_c0, L0.cheb_c1, L0.cheb_c2, entry, nullptr, src_in_t ? &tt : &tx, &tx, &tt, &td,
+                                      first, step, exchange, ghosts_after_first);
+    return end == &tt;
+  }
+
+  //      The overlapped V(1,1) driver.  Per level and application 2 * degree exchanges:
+  //        down  b (step 1 from zero is formed on the ghost rows too, from the exchanged b and the ghost entries of Dinv, so x_1
+  //              travels nowhere); x_2 .. x_{degree-1} ahead of their product steps; x_degree ahead of the residual  = degree
+  //        up    x + P x_c and x_1 .. x_{degree-1}, each ahead of its product step                                    = degree
+  //      degree 1 is the literal Jacobi count.  The owned rows of step 1 run beside the exchange of b, the interior rows of every
+  //      later pass beside the exchange of its iterate; with degree 1 the interior part of residual + restriction runs beside the
+  //      exchange of b as well, and the ghost rows of x_1 are formed when it ends.  The iterate lives in xext / text; level 0
+  //      copies out to the caller's x.
+  void cheby() {
+    std::vector<std::vector<double*>> X(k), T(k);
+    for (int l = 0; l < k; ++l)
+      for (Dist* d : M) { X[l].push_back(d->xext[l].p); T[l].push_back(d->text[l].p); }
+    for (int l = 0; l < k; ++l) {
+      const DevLevel& L0 = M[0]->top->lev[l];
+      const int deg = L0.cheb_degree;
+      const std::vector<double*>& X1 = *cheb_place(deg - 1, &X[l], &T[l]);            // where x_1 goes, so that x_degree lands in X
+      int tk = c.exchange_begin(items(l, 0));
+      auto ghost_rows = [&](Dist& d, size_t i) {
+        const DevLevel& L = d.top->lev[l];
+        d.top->cheb_first(L, bl(d, i, l), nullptr, X1[i], nullptr, L0.cheb_c0, L.n, L.ncols - L.n);
+      };
+      const bool in_t = cheb_smooth(l, ChebEntry::ZERO, false, X[l], T[l], true, true, [&](auto&& out, double c0) {
+        each([&](Dist& d, size_t i) { d.top->cheb_first(d.top->lev[l], bl(d, i, l), nullptr, out(i), nullptr, c0); });
+        if (deg > 1) { c.exchange_end(tk); tk = -1; each(ghost_rows); }      // (a product step follows: it reads the ghosts of x_1)
+      });
+      if (in_t) throw Err("rank-partitioned Chebyshev cycle: the iterate did not end in place");
+      if (deg > 1) tk = c.exchange_begin(items(l, 1));
+      overlapped(l, tk, [&](Dist& d, size_t i, Span sp) {
+        Handle& h = *d.top;
+        DevLevel& L = h.lev[l];
+        if (deg == 1 && sp.part != Handle::PART_INT) ghost_rows(d, i);
+        if (L.paths.down == DOWN_CHEB) h.down_launch(l, L.plan_rf, h.down_ops_cheb(d.xext[l].p, bl(d, i, l)), bnext(d, l), sp);
+        else {
+          h.residual_sm(L, d.xext[l].p, bl(d, i, l), d.rl[l].p, sp);
+          if (sp.part != Handle::PART_INT) h.transfer_f2c(l, d.rl[l].p, bnext(d, l));
+        }
+      });
+    }
+    tail();
+    for (int l = k - 1; l >= 0; --l) {
+      const int deg = M[0]->top->lev[l].cheb_degree;
+      const bool in_t = cheb_place(cheb_passes(deg, ChebEntry::ITERATE), &X[l], &T[l]) == &T[l];
+      each([&](Dist& d, size_t i) { d.top->mult_add(d.top->lev[l].P, 1.0, xcoarse(d, l), d.xext[l].p, (in_t ? T[l] : X[l])[i]); });
+      if (cheb_smooth(l, ChebEntry::ITERATE, in_t, X[l], T[l], true, false, [](auto&&, double) {})) throw Err("rank-partitioned Chebyshev cycle: the iterate did not end in place");
+      if (l == 0) each([&](Dist& d, size_t i) { d.top->copy(x[i], d.xext[0].p, d.n(0)); });
+    }
+  }
+
   // ---- step-by-step driver: sm_steps / sm_symm (ProxySmoother, base_smoother.hpp:169-229: k x Smooth, or k x (Smooth + SmoothBack)
   //      for the pre- AND the post-smoothing) and the W-cycle (AMGMatrix::SmoothW, amg_matrix.cpp:37-107) on rank-partitioned
   //      levels.  Every smoothing step is one step of the parallel smoother (hybrid_base_smoother.cpp:246-289): owner -> ghost
@@ -659,8 +759,17 @@ struct DistCycle {
     each([&](Dist& d, size_t i) { it.push_back({&d.halo[l], gx[l].cur[i]}); });
     c.exchange_end(c.exchange_begin(it));
   }
+  // Chebyshev: one step is one smooth of the level's degree -- the schedule with an exchange ahead of every product step (step 1
+  // from zero covers owned rows only here, so x_1 travels) and no overlap; the result is wherever the last pass left it
+  void gen_cheb(int l, bool x_zero) {
+    const bool in_t = cheb_smooth(l, x_zero ? ChebEntry::ZERO : ChebEntry::ITERATE, false, gx[l].cur, gx[l].oth, false, false, [&](auto&& out, double c0) {
+      each([&](Dist& d, size_t i) { d.top->cheb_first(d.top->lev[l], bl(d, i, l), nullptr, out(i), nullptr, c0); });
+    });
+    if (in_t) std::swap(gx[l].cur, gx[l].oth);
+  }
   void gen_step(int l, int dir, bool x_zero) {
-    if (!x_zero) gen_exchange(l);                              // (from x = 0 the ghost values are zeros already)
+    if (M[0]->sm_type == AMGX_SM_CHEBY) { gen_cheb(l, x_zero); return; }
+    if (!x_zero) gen_exchange(l);                             // (from x = 0 the ghost values are zeros already)
     each([&](Dist& d, size_t i) {
       Handle& h = *d.top;
       DevLevel& L = h.lev[l];
@@ -714,9 +823,88 @@ struct DistCycle {
       case DistPath::GS_BLOCK_HYBRID: hybrid_gsb(); break;
       case DistPath::GS_STAGED: hybrid_gs(); break;
       case DistPath::STEPWISE: stepwise(); break;
+      case DistPath::CHEBY: cheby(); break;
     }
   }
 };
+
+// lambda_max(Dinv A) of the rank-partitioned Chebyshev levels that got none: the estimator of cheb_estimate (amgx.hip) on the
+// partitioned operator -- 30 steps, 1.1 x the last Rayleigh quotient.  The start vector is fill_kernel(seed 1) at every rank's
+// LOCAL scalar index; an owner -> ghost exchange of the operand precedes each product; the two dot products are deterministic
+// local reductions, summed over the local ranks in member order by one kernel and over the processes by one all-reduce of two
+// scalars.  The break-or-continue decision is taken on the reduced values, so every rank -- one without rows included -- takes
+// the same branch and ends with bitwise the same interval.  Collective; runs once per communicator, before the first
+// application (the coefficients are kernel arguments: a captured cycle has them baked in).
+static void dist_cheb_estimate(Comm& c) {
+  if (c.cheb_estimate_done) return;
+  std::vector<Dist*>& M = c.members;
+  if (M.empty() || (c.kind == AMGX_COMM_LOCAL && (int)M.size() != c.nranks)) throw Err("amgx_dist_cheb_estimate: not all ranks have a hierarchy");
+  const size_t R = M.size();
+  DevBuf<double> partial, sc;
+  for (int l = 0; l < M[0]->k; ++l) {
+    if (M[0]->top->lev[l].sm_type != AMGX_SM_CHEBY) continue;
+    const bool given = M[0]->top->lev[l].cheb_lmax > 0.0;
+    for (Dist* d : M) if ((d->top->lev[l].cheb_lmax > 0.0) != given) throw Err("amgx_dist_cheb_estimate: level " + std::to_string(l) + ": cheb_lambda_max is set on some ranks only");
+    if (given) continue;
+    if (!partial.p) { partial.alloc((size_t)2 * KR_BLOCKS * R); sc.alloc(2); }
+    HIPCHK(hipMemsetAsync(partial.p, 0, (size_t)2 * KR_BLOCKS * R * sizeof(double), c.compute));   // (slots a short rank never writes)
+    // work vectors of rank i: v = x, t = res, w = tmp of its level (v and w carry ghost entries)
+    auto halo = [&](bool of_w) {
+      std::vector<Comm::Item> it;
+      for (Dist* d : M) it.push_back({&d->halo[l], of_w ? d->top->lev[l].tmp.p : d->top->lev[l].x.p});
+      c.exchange_end(c.exchange_begin(it));
+    };
+    for (Dist* d : M) {
+      DevLevel& L = d->top->lev[l];
+      if (L.len()) launch(fill_kernel, Handle::grid_for(L.len()), BLOCK, 0, c.compute, L.len(), (uint64_t)1, L.tmp.p);
+    }
+    halo(true);
+    for (Dist* d : M) {
+      DevLevel& L = d->top->lev[l];
+      d->top->mult(L.A, L.tmp.p, L.res.p);
+      d->top->cheb_first(L, L.res.p, nullptr, L.x.p, nullptr, 1.0);
+    }
+    double lam = 0.0;
+    for (int it = 0; it < 30; ++it) {
+      halo(false);
+      for (size_t i = 0; i < R; ++i) {
+        Handle& h = *M[i]->top;
+        DevLevel& L = h.lev[l];
+        const int64_t n = L.len();
+        h.mult(L.A, L.x.p, L.res.p);
+        h.cheb_first(L, L.res.p, nullptr, L.tmp.p, nullptr, 1.0);
+        if (!n) continue;
+        const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(KR_BLOCKS, (n + BLOCK - 1) / BLOCK));
+        launch(kr_dot_partial_kernel, nb, BLOCK, 0, c.compute, n, (const double*)L.res.p, (const double*)L.tmp.p, partial.p + i * KR_BLOCKS);
+        launch(kr_dot_partial_kernel, nb, BLOCK, 0, c.compute, n, (const double*)L.res.p, (const double*)L.x.p, partial.p + (R + i) * KR_BLOCKS);
+      }
+      launch(kr_dot_final_kernel, 1, BLOCK, 0, c.compute, (int)(KR_BLOCKS * R), (const double*)partial.p, sc.p);
+      launch(kr_dot_final_kernel, 1, BLOCK, 0, c.compute, (int)(KR_BLOCKS * R), (const double*)(partial.p + R * KR_BLOCKS), sc.p + 1);
+      if (c.kind == AMGX_COMM_RCCL && (c.nranks > 1 || M[0]->force_allgather))
+        NCCLCHK(Rccl::get().AllReduce(sc.p, sc.p, 2, ncclDouble, ncclSum, c.nccl, c.compute));
+      double two[2] = {0.0, 0.0};
+      HIPCHK(hipMemcpyAsync(two, sc.p, 2 * sizeof(double), hipMemcpyDeviceToHost, c.compute));
+      HIPCHK(hipStreamSynchronize(c.compute));
+      if (!(two[1] > 0.0) || !(two[0] > 0.0) || !std::isfinite(two[0] / two[1])) break;      // A v = 0 (no free row): keep the last value
+      lam = two[0] / two[1];
+      for (Dist* d : M) {
+        DevLevel& L = d->top->lev[l];
+        if (L.len()) launch(kr_scale_kernel, Handle::grid_for(L.len()), BLOCK, 0, c.compute, L.len(), 1.0 / lam, (const double*)L.tmp.p, L.x.p, 0);
+      }
+    }
+    if (!(lam > 0.0)) lam = 1.0;
+    for (Dist* d : M) {
+      DevLevel& L = d->top->lev[l];
+      L.cheb_set_interval(1.1 * lam);
+      L.cheb_estimated = 1;
+      const size_t len = (size_t)std::max<int64_t>(1, L.ext_len());
+      for (double* q : {L.x.p, L.res.p, L.tmp.p}) HIPCHK(hipMemsetAsync(q, 0, len * sizeof(double), c.compute));
+    }
+    HIPCHK(hipStreamSynchronize(c.compute));
+    HIPCHK(hipStreamSynchronize(c.comm_stream));
+  }
+  c.cheb_estimate_done = true;
+}
 
 // b_status 0 (DISTRIBUTED): b carries [owned | ghost] entries and the ghost entries are contributions to their owners
 // (b.Distribute() state of the reference, amg_matrix.cpp:164); 1 (CUMULATED): the owned entries are complete.
@@ -726,6 +914,7 @@ static void dist_apply(Comm& c, const double* const* b, double* const* x, int b_
   if (M.empty()) throw Err("amgx_dist_apply: the communicator has no rank-partitioned hierarchy");
   if (c.kind == AMGX_COMM_LOCAL && (int)M.size() != c.nranks) throw Err("amgx_dist_apply: not all local ranks have been created");
   if (!b || !x) throw Err("amgx_dist_apply: null vector list");
+  dist_cheb_estimate(c);                  // (does nothing after the first call)
   const bool host = !(flags & AMGX_DEVICE_PTR);
   for (size_t i = 0; i < M.size(); ++i)
     if ((!b[i] || !x[i]) && M[i]->n(0) > 0) throw Err("amgx_dist_apply: null vector");
@@ -996,6 +1185,7 @@ void check_dist_solve(const char* fn, amgx::Comm& c, bool bad_args, const double
     if ((!b[i] || !x[i]) && d->n(0) > 0) throw amgx::Err(f + ": null vector");
     if (b[i] == d->bext[0].p || x[i] == d->bext[0].p) throw amgx::Err(f + ": b / x alias the cycle's right-hand-side buffer" + alias_note);
   }
+  amgx::dist_cheb_estimate(c);
 }
 // the workspace lives with the communicator: the preconditioner's whole-cycle graph is keyed on the vector addresses, so a
 // second solve replays the graph of the first instead of capturing a new one (and leaving a stale one behind)
@@ -1130,6 +1320,10 @@ int amgx_dist_handles(amgx_dist d, amgx_handle* top, amgx_handle* tail) {
 
 int amgx_dist_apply(amgx_comm cc, const double* const* b, double* const* x, int b_status, int flags) {
   return cguard(cc, [&](amgx::Comm& c) { amgx::dist_apply(c, b, x, b_status, flags); });
+}
+
+int amgx_dist_cheb_estimate(amgx_comm cc) {
+  return cguard(cc, [&](amgx::Comm& c) { amgx::dist_cheb_estimate(c); });
 }
 
 int amgx_dist_time_kernel(amgx_comm cc, int level, int op, int reps, double* avg_ms) {

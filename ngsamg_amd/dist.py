@@ -854,17 +854,34 @@ class DistributedAMG:
     """
 
     def __init__(self, comm, states0, dim=3, omega=0.9, dist_min_rows=50000, max_dist_levels=3, device=0,
-                 backend=None, sm_type="jacobi", fold=True, sm_steps=1, sm_symm=False, mg_cycle="V", **opts):
-        if sm_type not in ("jacobi", "gs", "hgs", "bgs"):
-            raise NgsAMGError("DistributedAMG: sm_type must be jacobi, gs (multicolour stages), hgs (block-hybrid Gauss-Seidel) or bgs"
-                              + (" (the Chebyshev smoother 'cheby' is not available on rank-partitioned levels)" if sm_type == "cheby" else ""))
+                 backend=None, sm_type="jacobi", fold=True, sm_steps=1, sm_symm=False, mg_cycle="V",
+                 cheb_degree=None, cheb_ratio=10.0, cheb_lambda_max=None, **opts):
+        if sm_type not in ("jacobi", "gs", "hgs", "bgs", "cheby"):
+            raise NgsAMGError("DistributedAMG: sm_type must be jacobi, gs (multicolour stages), hgs (block-hybrid Gauss-Seidel), bgs or cheby")
+        # (an opt-in in two words: the type and its degree.  The degree has no default here: it fixes the 2 x degree halo exchanges per
+        #  level and application, and a call that names the type alone is refused as it was before the option existed)
+        if sm_type == "cheby" and cheb_degree is None:
+            raise NgsAMGError("DistributedAMG: sm_type 'cheby' on rank-partitioned levels needs an explicit cheb_degree (1 .. 8): it fixes "
+                              "the 2 x degree halo exchanges per level and application")
+        if sm_type == "cheby" and backend is not None:
+            raise NgsAMGError("DistributedAMG: the Chebyshev smoother runs through the device driver only (backend=None); the stage-by-stage "
+                              "Python backend is test infrastructure for Jacobi and Gauss-Seidel")
         self.comm, self.dim, self.omega, self.sm_type = comm, dim, omega, sm_type
+        # sm_type = "cheby" (DESIGN.md 5.4, 5.11): one degree and ratio for every level; cheb_lambda_max: None (estimated: collectively
+        # on the rank-partitioned levels, by amgx_create in the replicated tail), one value for the rank-partitioned levels, or a
+        # list with one entry per rank-partitioned level (the tail is always estimated)
+        self.cheb_degree, self.cheb_ratio, self.cheb_lambda_max = cheb_degree, cheb_ratio, cheb_lambda_max
+        if sm_type == "cheby":
+            from .device import cheby_args
+            if isinstance(cheb_degree, (list, tuple, np.ndarray)) or isinstance(cheb_ratio, (list, tuple, np.ndarray)):
+                raise NgsAMGError("DistributedAMG: cheb_degree and cheb_ratio are one value for all levels")
+            cheby_args(cheb_degree, cheb_ratio, None)
         # energy = 1: linear elasticity (states from assemble_elasticity_owned: block levels, rigid-body prolongation blocks,
         # coarse block size dim + nrot); block levels run block-Jacobi in the literal stage order
         self.energy = int(opts.get("energy", 0))
         blocks = any(_bs(s) > 1 for s in states0) or self.energy == 1
-        if blocks and sm_type not in ("jacobi", "gs", "hgs"):
-            raise NgsAMGError("DistributedAMG: rank-partitioned block levels support sm_type = jacobi | gs | hgs")
+        if blocks and sm_type not in ("jacobi", "gs", "hgs", "cheby"):
+            raise NgsAMGError("DistributedAMG: rank-partitioned block levels support sm_type = jacobi | gs | hgs | cheby")
         if blocks and sm_type == "hgs" and backend is not None:
             raise NgsAMGError("DistributedAMG: block-hybrid Gauss-Seidel on block levels runs through the device driver only (backend=None)")
         # fold: Jacobi post-smoothing folded into the prolongation (one product with Q on the way up, one halo exchange
@@ -991,6 +1008,17 @@ class DistributedAMG:
         if self._dev is None:
             raise NgsAMGError("gmres: needs the device driver (no CPU path)")
         return self._dev.gmres(bs, xs, tol=tol, maxsteps=maxsteps, restart=restart, use_pre=use_pre)
+
+    def smoother_info(self, level):
+        """the smoother of a level of the whole hierarchy (amgx_smoother_info): levels below k are answered by the top handles of the
+        local ranks, which must agree; level k and beyond by the replicated tail"""
+        if self._dev is None:
+            raise NgsAMGError("smoother_info: needs the device driver")
+        if level >= self.k:
+            return self.ops[0].tail.smoother_info(level - self.k)
+        infos = [op.top.smoother_info(level) for op in self.ops]
+        assert all(i == infos[0] for i in infos), f"level {level}: the local ranks disagree on the smoother: {infos}"
+        return infos[0]
 
     def level_k_map(self, i):
         """level k of local rank i in its [owned | ghost] layout -> index in the gathered (replicated) vector"""
@@ -1336,9 +1364,23 @@ class _DeviceDist:
         for i, top in enumerate(amg.tops):
             types = [sm] * (top.n_levels - 1) + ["jacobi"]
             stp, sym, cyc = getattr(amg, "sm_steps", 1), getattr(amg, "sm_symm", False), getattr(amg, "mg_cycle", "V")
+            cheb = {}
+            if sm == "cheby":
+                lam = amg.cheb_lambda_max
+                if isinstance(lam, (list, tuple, np.ndarray)):
+                    if len(lam) != k:
+                        raise NgsAMGError(f"cheb_lambda_max list must have one entry per rank-partitioned level ({k})")
+                    lam = list(lam)
+                else:
+                    lam = [lam] * k
+                cheb = dict(cheb_degree=amg.cheb_degree, cheb_ratio=amg.cheb_ratio)
+                tcheb = dict(cheb, cheb_lambda_max=lam + [None])
+            else:
+                tcheb = {}
             tdesc, tkeep, _ = hierarchy_desc(top, sm_type=types, omega=amg.omega, clev="none", device=self.device, use_graph=False,
-                                             sm_steps=stp, sm_symm=sym, mg_cycle=cyc)
-            ldesc, lkeep, _ = hierarchy_desc(amg.tail_hier, sm_type=sm, omega=amg.omega, device=self.device, sm_steps=stp, sm_symm=sym, mg_cycle=cyc)
+                                             sm_steps=stp, sm_symm=sym, mg_cycle=cyc, **tcheb)
+            ldesc, lkeep, _ = hierarchy_desc(amg.tail_hier, sm_type=sm, omega=amg.omega, device=self.device, sm_steps=stp, sm_symm=sym, mg_cycle=cyc,
+                                             **cheb)
             halos = (_lib.amgx_halo_desc * k)()
             keep = [tkeep, lkeep, halos]
             for l in range(k):
@@ -1371,6 +1413,7 @@ class _DeviceDist:
             d.counts, d.kmap, d.kmap_len = _lib.ptr(counts, C.c_int64), _lib.ptr(kmap, C.c_int64), kmap.size
             d.rank = int(amg.dist_levels[0][i].rank)
             d.fold = int(amg.fold)
+            d.cheby = int(sm == "cheby")
             if sm == "gs":
                 st = np.ascontiguousarray(np.concatenate([amg.dist_levels[l][i].gs_stage for l in range(k)]), dtype=np.int32)
                 d.gs_stage = _lib.ptr(st, C.c_int32)
@@ -1396,6 +1439,8 @@ class _DeviceDist:
             o.top, o.tail = DeviceAMGMatrix.view(ht, top), DeviceAMGMatrix.view(hl, amg.tail_hier)
             self.ops.append(o)
         self._keep = []           # the native side copied everything
+        # collective lambda_max estimate of the rank-partitioned Chebyshev levels: every rank exists now (a no-op otherwise)
+        self._ck(lib.amgx_dist_cheb_estimate(self._comm))
         self._stream = None
         self._rhs = {}
 

@@ -3,7 +3,10 @@
 the tree's own build, then NGSAMG_HIP_LIB=<other build>, usually the parent commit's -- every result stored as .npy and compared
 with numpy.array_equal, level_paths(l) of every level of every handle compared as dictionaries.  Prints the table and a verdict.
 
-  python tools/bits_vs_parent.py --parent-lib <libngsamg_hip.so of the parent> --out <dir> [--report <file>]
+  python tools/bits_vs_parent.py --parent-lib <libngsamg_hip.so of the parent> --out <dir> [--report <file>] [--parent-root <dir>]
+
+--parent-root: a built checkout of the parent commit; its own copy of this tool (hence its Python package) then drives the parent's
+library -- needed whenever this tree's bindings name an entry point the parent's library does not have.
 
 The cases are the Gauss-Seidel forms (every SweepPath value, with and without the split images where a kill switch exists) and
 the rank-partitioned drivers on two virtual ranks; edit CASES / DIST_CASES for the refactor at hand.  A child that fails ends
@@ -208,6 +211,7 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--report")
     ap.add_argument("--child")
+    ap.add_argument("--parent-root")
     a = ap.parse_args()
     if a.child:
         return child(a.child)
@@ -218,7 +222,8 @@ def main():
         env.pop("NGSAMG_HIP_LIB", None)
         if lib:
             env["NGSAMG_HIP_LIB"] = lib
-        rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", os.path.join(a.out, tag), "--out", a.out], env=env, timeout=900).returncode
+        tool = os.path.join(os.path.abspath(a.parent_root), "tools", "bits_vs_parent.py") if lib and a.parent_root else os.path.abspath(__file__)
+        rc = subprocess.run([sys.executable, tool, "--child", os.path.abspath(os.path.join(a.out, tag)), "--out", os.path.abspath(a.out)], env=env, timeout=900).returncode
         if rc != 0:
             sys.exit(f"the run with the {tag} library ended with status {rc}: nothing more is started")
     T, P = (json.load(open(os.path.join(a.out, tag, "index.json"))) for tag, _ in runs)
