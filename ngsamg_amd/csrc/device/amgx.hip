@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -2322,489 +2323,18 @@ struct Handle {
 // construction
 // ---------------------------------------------------------------------------------------------------
 
-static void build_gs(const Knobs& K, const amgx_level_desc& d, DevLevel& L) {
-  const int64_t n = d.A.n_rows;
-  if (!d.color || d.n_colors <= 0) { if (n > 0) throw Err("AMGX_SM_GS needs a row colouring (color / n_colors)"); return; }
-  const int nc = d.n_colors;
-  // validate: rows of equal colour must not be coupled (otherwise the parallel sweep would race)
-  for (int64_t i = 0; i < n; ++i) {
-    const int ci = d.color[i];
-    if (ci >= nc) throw Err("colour index out of range");
-    if (ci < 0) continue;
-    for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) {
-      const int64_t j = d.A.col[k];
-      if (j >= n) continue;          // ghost column of a rank-partitioned level: frozen during the sweep (hybrid GS)
-      if (j != i && d.color[j] == ci) throw Err("invalid colouring: two coupled rows share a colour");
-    }
-  }
-  std::vector<int64_t> cnt(nc + 1, 0);
-  for (int64_t i = 0; i < n; ++i) if (d.color[i] >= 0) cnt[d.color[i] + 1]++;
-  DevGS& g = L.gs;
-  g.n_colors = nc;
-  if (d.A.br == 1) {
-    // lanes per row: one thread per row only while a colour still has >= 2^17 rows; below that G grows with the row
-    // length so that a row is consumed in ~2-4 steps
-    const int64_t nnz = d.A.rowptr[n];
-    const double avg = n ? (double)nnz / (double)n : 0.0;
-    int G = 1;
-    if (n / std::max(1, nc) < ((int64_t)1 << 17)) while (G < 16 && avg > 4.0 * G) G <<= 1;
-    g.lanes = G;
-    const int R = WAVE / G;
-    // colour-major row list, each colour padded to a multiple of R rows (= whole slices)
-    std::vector<int64_t> cstart(nc + 1, 0);
-    for (int c = 0; c < nc; ++c) cstart[c + 1] = cstart[c] + ((cnt[c + 1] + R - 1) / R) * R;
-    std::vector<int32_t> rows(cstart[nc], -1);
-    std::vector<int64_t> pos(cstart.begin(), cstart.end() - 1);
-    for (int64_t i = 0; i < n; ++i) if (d.color[i] >= 0) rows[pos[d.color[i]]++] = (int32_t)i;
-    g.color_slice_ptr.resize(nc + 1);
-    for (int c = 0; c <= nc; ++c) g.color_slice_ptr[c] = (int)(cstart[c] / R);
-    HostSell S;
-    // (absolute 16-bit column bases, not row-relative: the row product then does not depend on the rowid load)
-    const bool gs_rowrel = K.gs_rowrel;
-    build_sell(d.A, rows.data(), (int64_t)rows.size(), gs_rowrel, G, S);
-    upload_sell(S, g.sell);
-    g.rowid.upload(rows);
-    g.n_slices_total = (int)(S.slice_ptr.size() - 1);
-    // the split form relies on x_k = (b - L x)_k / a_kk, i.e. on dinv being the plain inverse diagonal
-    bool plain_diag = d.dinv != nullptr && d.A.n_rows == d.A.n_cols;
-    for (int64_t i = 0; i < n && plain_diag; ++i) {
-      if (d.color[i] < 0) continue;
-      double aii = 0.0;
-      for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) if (d.A.col[k] == i) aii = d.A.val[k];
-      if (!(std::fabs(d.dinv[i] * aii - 1.0) < 1e-12)) plain_diag = false;
-    }
-    if (plain_diag) {
-      // lower / upper parts w.r.t. the colour order; couplings to non-free columns are dropped (x is 0 there)
-      for (int part = 0; part < 2; ++part) {
-        std::vector<int64_t> rp(n + 1, 0);
-        std::vector<int32_t> cc;
-        std::vector<double> vv;
-        cc.reserve(nnz / 2 + 16); vv.reserve(nnz / 2 + 16);
-        for (int64_t i = 0; i < n; ++i) {
-          const int ci = d.color[i];
-          if (ci >= 0)
-            for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) {
-              const int cj = d.color[d.A.col[k]];
-              if (cj < 0) continue;
-              if ((part == 0 && cj < ci) || (part == 1 && cj > ci)) { cc.push_back(d.A.col[k]); vv.push_back(d.A.val[k]); }
-            }
-          rp[i + 1] = (int64_t)cc.size();
-        }
-        amgx_matrix F = d.A;
-        F.rowptr = rp.data(); F.col = cc.data(); F.val = vv.data();
-        HostSell SP;
-        build_sell(F, rows.data(), (int64_t)rows.size(), gs_rowrel, G, SP);
-        if ((int)(SP.slice_ptr.size() - 1) != g.n_slices_total) throw Err("build_gs: split copy has a different slice count");
-        upload_sell(SP, part == 0 ? g.lower : g.upper);
-      }
-      g.has_split = true;
-    }
-  } else {
-    g.color_row_ptr.assign(nc + 1, 0);
-    for (int c = 0; c < nc; ++c) g.color_row_ptr[c + 1] = g.color_row_ptr[c] + (int)cnt[c + 1];
-    std::vector<int32_t> rows(g.color_row_ptr[nc]);
-    std::vector<int> pos(g.color_row_ptr.begin(), g.color_row_ptr.end() - 1);
-    for (int64_t i = 0; i < n; ++i) if (d.color[i] >= 0) rows[pos[d.color[i]]++] = (int32_t)i;
-    g.rowlist.upload(rows);
-    // colour-major BSELL copy: every colour padded to whole slices of RB block rows (big levels: one more copy of A,
-    // 2x the sweep speed; small levels keep the CSR row-list kernel: their colours are shorter than a slice)
-    const int bs = d.A.br;
-    if ((bs == 2 || bs == 3 || bs == 6) && n / std::max(1, nc) >= K.bgs_bsell_min && !K.no_bgs_bsell) {
-      const int RB = WAVE / bs;
-      std::vector<int64_t> cstart(nc + 1, 0);
-      for (int c = 0; c < nc; ++c) cstart[c + 1] = cstart[c] + ((cnt[c + 1] + RB - 1) / RB) * RB;
-      std::vector<int32_t> prow(cstart[nc], -1);
-      std::vector<int64_t> p2(cstart.begin(), cstart.end() - 1);
-      for (int64_t i = 0; i < n; ++i) if (d.color[i] >= 0) prow[p2[d.color[i]]++] = (int32_t)i;
-      if (build_bsell(d.A, g.bcopy, 1.6, prow.data(), (int64_t)prow.size())) {
-        g.color_slice_ptr.resize(nc + 1);
-        for (int c = 0; c <= nc; ++c) g.color_slice_ptr[c] = (int)(cstart[c] / RB);
-        g.rowid.upload(prow);
-        g.bsell_ok = true;
-        // split copies (see the scalar case): need x_B = Dinv_B (b - L x)_B to imply (b - L x - D x)_B = 0, i.e. Dinv_B = A_BB^-1
-        bool plain_diag = d.dinv != nullptr && d.A.n_rows == d.A.n_cols && !K.no_bgs_split;
-        const int bb = bs * bs;
-        for (int64_t i = 0; i < n && plain_diag; ++i) {
-          if (d.color[i] < 0) continue;
-          const double* aii = nullptr;
-          for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) if (d.A.col[k] == i) aii = d.A.val + k * bb;
-          if (!aii) { plain_diag = false; break; }
-          const double* di = d.dinv + i * bb;
-          for (int r = 0; r < bs && plain_diag; ++r)
-            for (int c = 0; c < bs; ++c) {
-              double v = 0.0;
-              for (int q = 0; q < bs; ++q) v += di[r * bs + q] * aii[q * bs + c];
-              if (!(std::fabs(v - (r == c ? 1.0 : 0.0)) < 1e-10)) { plain_diag = false; break; }
-            }
-        }
-        if (plain_diag) {
-          bool ok = true;
-          for (int part = 0; part < 2 && ok; ++part) {
-            std::vector<int64_t> rp(n + 1, 0);
-            std::vector<int32_t> cc;
-            std::vector<double> vv;
-            for (int64_t i = 0; i < n; ++i) {
-              const int ci = d.color[i];
-              if (ci >= 0)
-                for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) {
-                  const int cj = d.color[d.A.col[k]];
-                  if (cj < 0) continue;
-                  if ((part == 0 && cj < ci) || (part == 1 && cj > ci)) {
-                    cc.push_back(d.A.col[k]);
-                    vv.insert(vv.end(), d.A.val + k * bb, d.A.val + (k + 1) * bb);
-                  }
-                }
-              rp[i + 1] = (int64_t)cc.size();
-            }
-            amgx_matrix F = d.A;
-            F.rowptr = rp.data(); F.col = cc.data(); F.val = vv.data();
-            DevMatrix& T = part == 0 ? g.blower : g.bupper;
-            ok = build_bsell(F, T, 1e9, prow.data(), (int64_t)prow.size()) && T.n_slices == g.bcopy.n_slices;
-          }
-          g.bsplit = ok;
-        }
-      }
-    }
-  }
-}
-
 struct HostCsr {
   std::vector<int64_t> rowptr;
   std::vector<int32_t> col;
   std::vector<double> val;
 };
+static void use_csr(amgx_matrix& M, const HostCsr& c) { M.rowptr = c.rowptr.data(); M.col = c.col.data(); M.val = c.val.data(); }
 
 }  // namespace amgx
 #include "devbuild.hpp"
+#include "gs_images.hpp"        // build_gs, build_gsb, build_bgsb and their AMGX_VERIFY_IMAGES cross-checks
 #include "spgemm.hpp"
 namespace amgx {
-
-// Block-hybrid Gauss-Seidel data (gsb_sweep_kernel).  Validated like the colourings above: two coupled rows of one block
-// sharing a colour would be a data race.
-// csr: the level matrix on the device (big levels): the three images and the split are then formed there (devbuild.hpp)
-// local-window image of the colour-sorted block image `full` (gsb_sweep_kernel<..., LW>): per block of B rows the sorted list of its
-// distinct off-block columns; entries carry codes (in-block: row - r0 < B; off-block: B + position in the list).  Blocks whose list
-// exceeds GSB_LW_CAP keep global 32-bit columns.  rows: the slot -> row list of the block image (-1 = padding), slots = n_blocks * B.
-static bool build_gsb_full_lw(const Knobs& K, const amgx_matrix& A, const std::vector<int32_t>& rows, int64_t slots, int B, int G, DevGSB& g) {
-  const int64_t n = A.n_rows, nnz = A.rowptr[n];
-  const int64_t nb = (n + B - 1) / B;
-  std::vector<int32_t> cnt((size_t)nb + 1, 0);
-  RawVec<int32_t> code;
-  code.resize((size_t)std::max<int64_t>(1, nnz));
-  std::vector<std::vector<int32_t>> lists((size_t)nb);
-  std::vector<char> no16((size_t)n, 0);
-  std::vector<int64_t> n_over(setup_threads(), 0);
-  const int64_t cap = K.lw_cap_small(GSB_LW_CAP);
-  const bool tcap = K.lw_test_cap_on;
-  par_for(nb, [&](int64_t b0, int64_t b1, int t) {
-    std::vector<int32_t> u;
-    for (int64_t kb = b0; kb < b1; ++kb) {
-      const int64_t r0 = kb * B, r1 = std::min<int64_t>(n, r0 + B);
-      u.clear();
-      for (int64_t k = A.rowptr[r0]; k < A.rowptr[r1]; ++k) if (A.col[k] < r0 || A.col[k] >= r1) u.push_back(A.col[k]);
-      std::sort(u.begin(), u.end());
-      u.erase(std::unique(u.begin(), u.end()), u.end());
-      if ((int64_t)u.size() > cap) {
-        for (int64_t i = r0; i < r1; ++i) no16[i] = 1;
-        for (int64_t k = A.rowptr[r0]; k < A.rowptr[r1]; ++k) code[k] = A.col[k];
-        n_over[t]++;
-        continue;
-      }
-      for (int64_t k = A.rowptr[r0]; k < A.rowptr[r1]; ++k) {
-        const int32_t j = A.col[k];
-        code[k] = (j >= r0 && j < r1) ? (int32_t)(j - r0) : (int32_t)(B + (std::lower_bound(u.begin(), u.end(), j) - u.begin()));
-      }
-      cnt[kb + 1] = (int32_t)u.size();
-      lists[kb] = u;
-    }
-  }, 16);
-  int64_t overs = 0;
-  for (int64_t v : n_over) overs += v;
-  if (overs * 20 > nb && !tcap) return false;
-  for (int64_t kb = 0; kb < nb; ++kb) cnt[kb + 1] += cnt[kb];
-  std::vector<int32_t> ccol((size_t)std::max<int32_t>(1, cnt[nb]));
-  par_for(nb, [&](int64_t b0, int64_t b1, int) { for (int64_t kb = b0; kb < b1; ++kb) std::copy(lists[kb].begin(), lists[kb].end(), ccol.begin() + cnt[kb]); }, 64);
-  amgx_matrix Lm = A;
-  Lm.col = code.data();
-  HostSell S;
-  build_sell(Lm, rows.data(), slots, false, G, S, false, &no16);
-  // every slice must fit the kernel's register budget exactly like `full` (same widths: same rows, same lengths)
-  upload_sell(S, g.fullLW);
-  g.flw_cptr.upload(cnt);
-  g.flw_ccol.upload(ccol);
-  g.has_fullLW = true;
-  g.flw_no_window = overs;
-  return true;
-}
-
-static void build_gsb_images(const Knobs& K, const amgx_level_desc& d, DevLevel& L, const amgx_matrix* P, const DevCsrSrc* csr) {
-  const int64_t n = d.A.n_rows;
-  DevGSB& g = L.gsb;
-  const int B = d.gs_block_rows;
-  // lanes per row from the longest row (a lane holds <= 16 entries, + 1 when G = 1); workgroup size TH = B * G
-  int64_t mx = 0;
-  {
-    std::vector<int64_t> tmx(setup_threads(), 0);
-    par_for(n, [&](int64_t i0, int64_t i1, int t) { int64_t m = 0; for (int64_t i = i0; i < i1; ++i) m = std::max<int64_t>(m, d.A.rowptr[i + 1] - d.A.rowptr[i]); tmx[t] = m; });
-    for (int64_t v : tmx) mx = std::max(mx, v);
-  }
-  int G = 1;
-  while (G < 16 && mx > 16 * G + (G == 1 ? 1 : 0)) G <<= 1;
-  // the ranks of a partitioned level agree on ONE block size (the smallest any of them needs, dist.py) while their longest
-  // rows may differ: a rank with shorter rows spreads them over more lanes than it must, so that B * G is a workgroup size
-  while (G < 16 && B >= 16 && B * G < 256) G <<= 1;
-  if (n == 0) {                     // a rank that owns nothing: the form is "on" (the cycle drivers test it) with no block to sweep
-    g.B = B > 0 ? B : 256; g.G = 1; g.TH = 256; g.n_colors = 0; g.n_blocks = 0;
-    return;
-  }
-  const int TH = B * G;
-  if (B < 16 || (TH != 256 && TH != 512 && TH != 1024))
-    throw Err("gs_block_rows = " + std::to_string(B) + " with " + std::to_string(G) + " lanes per row (longest row: " + std::to_string(mx) +
-              " entries) does not give a workgroup of 256, 512 or 1024 lanes");
-  if (d.A.br != 1 || d.A.bc != 1) throw Err("block-hybrid Gauss-Seidel: scalar levels only");
-  if (!d.color || d.n_colors <= 0 || d.n_colors > 254) { if (n > 0) throw Err("block-hybrid Gauss-Seidel needs a blocked colouring with at most 254 colours"); return; }
-  if (!d.dinv) throw Err("dinv missing");
-  const int nc = d.n_colors;
-  par_for(n, [&](int64_t i0, int64_t i1, int) {
-    for (int64_t i = i0; i < i1; ++i) {
-      const int ci = d.color[i];
-      if (ci >= nc) throw Err("colour index out of range");
-      if (ci < 0) continue;
-      const int64_t b0 = (i / B) * B, b1 = b0 + B;
-      for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) {
-        const int64_t j = d.A.col[k];
-        if (j != i && j >= b0 && j < b1 && j < n && d.color[j] == ci) throw Err("invalid blocked colouring: two coupled rows of one block share a colour");
-      }
-    }
-  });
-  g.B = B; g.G = G; g.TH = TH; g.n_colors = nc;
-  g.n_blocks = (int)((n + B - 1) / B);
-  const int64_t slots = (int64_t)g.n_blocks * B;
-  std::vector<int32_t> rows((size_t)slots, -1);
-  std::vector<uint8_t> sc((size_t)slots, 255);
-  par_for(g.n_blocks, [&](int64_t k0, int64_t k1, int) {
-    for (int64_t kb = k0; kb < k1; ++kb) {
-      const int64_t b0 = kb * B, b1 = std::min<int64_t>(n, b0 + B);
-      for (int64_t i = b0; i < b1; ++i) rows[i] = (int32_t)i;
-      std::stable_sort(rows.begin() + b0, rows.begin() + b1, [&](int32_t a, int32_t c) {
-        return (d.color[a] < 0 ? 255 : d.color[a]) < (d.color[c] < 0 ? 255 : d.color[c]); });
-      for (int64_t q = b0; q < b1; ++q) sc[q] = d.color[rows[q]] < 0 ? 255 : (uint8_t)d.color[rows[q]];
-    }
-  }, 16);
-  auto check_width = [&](const HostSell& S, const char* what) {
-    const int64_t ns = (int64_t)S.slice_ptr.size() - 1;
-    for (int64_t q = 0; q < ns; ++q) {
-      const int w = (int)(((S.slice_ptr[q + 1] & ~(int64_t)63) - (S.slice_ptr[q] & ~(int64_t)63)) / WAVE);
-      if (w > 2 * GSB_WP + 1) throw Err(std::string("block-hybrid Gauss-Seidel (") + what + "): a row has more than " + std::to_string((2 * GSB_WP) * G + 1) +
-                                        " entries for gs_block_rows = " + std::to_string(B) + " (use smaller blocks)");
-    }
-  };
-  g.rowid.upload(rows);
-  g.slotcolor.upload(sc);
-  {
-    // long-row square levels: local-window image of `full` for the general sweep
-    const double avgA = n ? (double)d.A.rowptr[n] / (double)n : 0.0;
-    // Measured NON-win at cfg 2 (profiles/r04/gs_experiments.txt): level-1 backward sweep 231 us with the window against 196 us without
-    // (the extra barrier and the window's registers cost more than the gathers of the off-block values, which this kernel issues
-    // back to back in one burst).  Built and tested, off unless AMGX_GSB_LW=1.
-    if (avgA >= 24.0 && K.lw_wanted(n) && d.A.n_cols == n && G > 1 && K.gsb_lw)
-      build_gsb_full_lw(K, d.A, rows, slots, B, G, g);
-  }
-  if (csr) {
-    // device builders: the colour-sorted image of A, the split by kernels, the images of its two parts
-    auto max_width = [&](const DevMatrix::Sell& S, const char* what) {
-      const auto sp = db_download(S.slice_ptr, S.slice_ptr.n);
-      int mw = 0;
-      for (size_t q = 0; q + 1 < sp.size(); ++q) mw = std::max(mw, (int)(((sp[q + 1] & ~(int64_t)63) - (sp[q] & ~(int64_t)63)) / WAVE));
-      if (mw > 2 * GSB_WP + 1) throw Err(std::string("block-hybrid Gauss-Seidel (") + what + "): a row has more than " + std::to_string((2 * GSB_WP) * G + 1) +
-                                         " entries for gs_block_rows = " + std::to_string(B) + " (use smaller blocks)");
-      return mw;
-    };
-    {
-      DevBuf<int64_t> sp;
-      const int64_t stored = dev_slice_offsets(*csr, g.rowid.p, slots, sp, G);
-      dev_build_sell(*csr, g.rowid.p, slots, G, false, false, nullptr, 0.0, nullptr, sp, stored, g.full, nullptr);
-      g.full_maxw = max_width(g.full, "A");
-    }
-    DevBuf<int32_t> dcolor;
-    dcolor.upload(d.color, (size_t)n);
-    DbSplit a{n, B, csr->rowptr.p, csr->col.p, csr->val.p, dcolor.p, L.dinv.p};
-    DevCsrSrc part[2];
-    for (int q = 0; q < 2; ++q) { part[q].n_rows = n; part[q].n_cols = d.A.n_cols; part[q].rowptr.alloc((size_t)n + 1); }
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    launch(db_split_count_kernel, grid, BLOCK, 0, 0, a, part[0].rowptr.p, part[1].rowptr.p);
-    for (int q = 0; q < 2; ++q) {
-      launch(db_scan_kernel, 1, 1024, 0, 0, n, part[q].rowptr.p);
-      HIPCHK(hipMemcpy(&part[q].nnz, part[q].rowptr.p + n, sizeof(int64_t), hipMemcpyDeviceToHost));
-      part[q].col.alloc((size_t)std::max<int64_t>(1, part[q].nnz));
-      part[q].val.alloc((size_t)std::max<int64_t>(1, part[q].nnz));
-    }
-    g.cvec.alloc((size_t)n);
-    DevBuf<int> bad;
-    bad.alloc(1);
-    HIPCHK(hipMemset(bad.p, 0, sizeof(int)));
-    launch(db_split_fill_kernel, grid, BLOCK, 0, 0, a, part[0].rowptr.p, part[1].rowptr.p, part[0].col.p, part[0].val.p,
-                       part[1].col.p, part[1].val.p, g.cvec.p, bad.p);
-    int hbad = 0;
-    HIPCHK(hipMemcpy(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (hbad || K.gsb_no_split) { g.cvec.release(); return; }
-    {
-      DevBuf<int64_t> sp;
-      const int64_t stored = dev_slice_offsets(part[0], g.rowid.p, slots, sp, G);
-      dev_build_sell(part[0], g.rowid.p, slots, G, false, false, nullptr, 0.0, nullptr, sp, stored, g.lowin, nullptr);
-      g.lowin_maxw = max_width(g.lowin, "lower part");
-    }
-    if (!dev_upload_matrix(K, part[1], g.rest, false, 1.6, SELL_WIN, nullptr)) {
-      // (the host builder's CSR fallback for a badly padded remainder: from the host copy of the part)
-      std::vector<int64_t> rp = db_download(part[1].rowptr, (size_t)n + 1);
-      std::vector<int32_t> cc = db_download(part[1].col, (size_t)std::max<int64_t>(1, part[1].nnz));
-      std::vector<double> vv = db_download(part[1].val, (size_t)std::max<int64_t>(1, part[1].nnz));
-      amgx_matrix F = d.A;
-      F.rowptr = rp.data(); F.col = cc.data(); F.val = vv.data();
-      upload_matrix(K, F, g.rest, "A (block-hybrid Gauss-Seidel: rest)", true, false, false, 1.6, SELL_WIN);
-    }
-    g.has_split = true;
-    {
-      // long-row levels: local-window image of the rest part (host builder from the downloaded part)
-      const double avgA = n ? (double)csr->nnz / (double)n : 0.0;
-      if (P && avgA >= 24.0 && K.lw_wanted(n) && d.A.n_cols == n && K.fused_restrict_ok(*P, 1)) {
-        // (device builder first, devbuild.hpp dev_build_lw; the host builder works from the downloaded part)
-        std::vector<int64_t> rp;
-        std::vector<int32_t> cc;
-        std::vector<double> vv;
-        amgx_matrix F = d.A;
-        auto host_lw = [&](int gg, DevMatrix& M, DevBuf<int32_t>& cp, DevBuf<int32_t>& cl) {
-          if (rp.empty()) {
-            rp = db_download(part[1].rowptr, (size_t)n + 1);
-            cc = db_download(part[1].col, (size_t)std::max<int64_t>(1, part[1].nnz));
-            vv = db_download(part[1].val, (size_t)std::max<int64_t>(1, part[1].nnz));
-            F.rowptr = rp.data(); F.col = cc.data(); F.val = vv.data();
-          }
-          return build_sell_lw(K, F, F.val, gg, M, cp, cl);
-        };
-        const bool dev_lw = !K.host_lw;
-        const bool verify_lw = K.verify_images;
-        int G = 0;
-        for (int gg : values(DownLwLanes{})) {
-          bool ok = false;
-          if (dev_lw) {
-            ok = dev_build_lw(part[1], false, gg, K.lw_cap(LW_CAP), K.lw_test_cap_on, nullptr, 0.0, g.restLW, g.lw_cptr, g.lw_ccol);
-            if (ok && verify_lw) {
-              DevMatrix H; DevBuf<int32_t> hp, hc;
-              if (!host_lw(gg, H, hp, hc)) throw Err("AMGX_VERIFY_IMAGES: Gauss-Seidel rest (local window): the host builder declines what the device builder forms");
-              verify_same_lw(g.restLW, g.lw_cptr, g.lw_ccol, H, hp, hc, "Gauss-Seidel rest (local window)");
-            }
-            if (!ok) { g.restLW = DevMatrix(); g.lw_cptr.release(); g.lw_ccol.release(); }
-          }
-          if (!ok) ok = host_lw(gg, g.restLW, g.lw_cptr, g.lw_ccol);
-          if (ok) { G = gg; break; }
-          g.restLW = DevMatrix();
-        }
-        if (G) {
-          build_restrict(K, *P, L.RG, 512 / G, 4 * 512, 512);
-          if (!L.RG.empty()) return;
-          g.restLW = DevMatrix(); g.lw_cptr.release(); g.lw_ccol.release();
-        }
-      }
-    }
-    if (P && g.rest.fmt == FMT_SELL && g.rest.lanes == 1 && K.fused_restrict_ok(*P, 1))
-      build_restrict(K, *P, L.RG, 512, 6 * 512);
-    return;
-  }
-  {
-    HostSell S;
-    build_sell(d.A, rows.data(), slots, false, G, S);
-    check_width(S, "A");
-    g.full_maxw = 0;
-    for (size_t q = 0; q + 1 < S.slice_ptr.size(); ++q)
-      g.full_maxw = std::max(g.full_maxw, (int)(((S.slice_ptr[q + 1] & ~(int64_t)63) - (S.slice_ptr[q] & ~(int64_t)63)) / WAVE));
-    upload_sell(S, g.full);
-  }
-  // split for the pre-smoothing from zero: lowin = in-block couplings to lower colours, rest = everything else but the
-  // diagonal; couplings to non-free columns are dropped (x is 0 there), non-free rows are empty (their residual is not
-  // needed: their prolongation rows are empty)
-  std::vector<double> cv((size_t)n, 0.0);
-  std::vector<int64_t> rp[2];
-  RawVec<int32_t> cc[2];
-  RawVec<double> vv[2];
-  for (int part = 0; part < 2; ++part) rp[part].assign(n + 1, 0);
-  // part of entry (i, k): 0 = in-block coupling to a lower colour, 1 = rest, -1 = dropped (the diagonal, a non-free column)
-  auto part_of = [&](int64_t i, int ci, int64_t j) -> int {
-    if (j == i) return -1;
-    const int cj = j < n ? d.color[j] : 0;            // ghost columns count as live
-    if (cj < 0) return -1;
-    const int64_t b0 = (i / B) * B, b1 = b0 + B;
-    return (j >= b0 && j < b1 && j < n && cj < ci) ? 0 : 1;
-  };
-  par_for(n, [&](int64_t i0, int64_t i1, int) {
-    for (int64_t i = i0; i < i1; ++i) {
-      const int ci = d.color[i];
-      if (ci < 0) continue;
-      for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) {
-        const int pt = part_of(i, ci, d.A.col[k]);
-        if (pt >= 0) rp[pt][i + 1]++;
-      }
-    }
-  });
-  for (int part = 0; part < 2; ++part) {
-    for (int64_t i = 0; i < n; ++i) rp[part][i + 1] += rp[part][i];
-    cc[part].resize((size_t)std::max<int64_t>(1, rp[part][n]));
-    vv[part].resize((size_t)std::max<int64_t>(1, rp[part][n]));
-  }
-  std::vector<char> bad(setup_threads(), 0);
-  par_for(n, [&](int64_t i0, int64_t i1, int t) {
-    for (int64_t i = i0; i < i1; ++i) {
-      const int ci = d.color[i];
-      if (ci < 0) continue;
-      int64_t o[2] = {rp[0][i], rp[1][i]};
-      double aii = 0.0;
-      for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) {
-        const int64_t j = d.A.col[k];
-        if (j == i) { aii = d.A.val[k]; continue; }
-        const int pt = part_of(i, ci, j);
-        if (pt < 0) continue;
-        cc[pt][o[pt]] = (int32_t)j; vv[pt][o[pt]] = d.A.val[k]; ++o[pt];
-      }
-      if (d.dinv[i] != 0.0) cv[i] = 1.0 / d.dinv[i] - aii; else bad[t] = 1;     // a swept row without a diagonal inverse
-    }
-  });
-  bool ok = true;
-  for (char c : bad) if (c) ok = false;
-  if (ok && !K.gsb_no_split) {
-    amgx_matrix F = d.A;
-    F.rowptr = rp[0].data(); F.col = cc[0].data(); F.val = vv[0].data();
-    HostSell S;
-    build_sell(F, rows.data(), slots, false, G, S);
-    check_width(S, "lower part");
-    upload_sell(S, g.lowin);
-    g.lowin_maxw = 0;
-    for (size_t q = 0; q + 1 < S.slice_ptr.size(); ++q)
-      g.lowin_maxw = std::max(g.lowin_maxw, (int)(((S.slice_ptr[q + 1] & ~(int64_t)63) - (S.slice_ptr[q] & ~(int64_t)63)) / WAVE));
-    F.rowptr = rp[1].data(); F.col = cc[1].data(); F.val = vv[1].data();
-    upload_matrix(K, F, g.rest, "A (block-hybrid Gauss-Seidel: rest)", true, false, false, 1.6, SELL_WIN);
-    g.cvec.upload(cv);
-    g.has_split = true;
-    {
-      const double avgA = n ? (double)d.A.rowptr[n] / (double)n : 0.0;
-      if (P && avgA >= 24.0 && K.lw_wanted(n) && d.A.n_cols == n && K.fused_restrict_ok(*P, 1)) {
-        int G = 0;
-        for (int gg : values(DownLwLanes{})) if (build_sell_lw(K, F, F.val, gg, g.restLW, g.lw_cptr, g.lw_ccol)) { G = gg; break; } else g.restLW = DevMatrix();
-        if (G) {
-          build_restrict(K, *P, L.RG, 512 / G, 4 * 512, 512);
-          if (!L.RG.empty()) return;
-          g.restLW = DevMatrix(); g.lw_cptr.release(); g.lw_ccol.release();
-        }
-      }
-    }
-    if (P && g.rest.fmt == FMT_SELL && g.rest.lanes == 1 && K.fused_restrict_ok(*P, 1))
-      build_restrict(K, *P, L.RG, 512, 6 * 512);
-  }
-}
-
-static void build_gsb(const Knobs& K, const amgx_level_desc& d, DevLevel& L, const amgx_matrix* P, const DevCsrSrc* csr = nullptr) {
-  build_gsb_images(K, d, L, P, csr);
-  gsb_set_paths(K, L.gsb);
-}
 
 // ---------------------------------------------------------------------------------------------------
 // Folded post-smoothing.  In the V(1,1) Jacobi cycle the post-smoothing step (amg_matrix.cpp:263-302)
@@ -2814,286 +2344,6 @@ static void build_gsb(const Knobs& K, const amgx_level_desc& d, DevLevel& L, con
 // and the whole post-smoothing is ONE SpMV-AXPY with Q = (I - omega*Dinv*A) P, built once here (host, threads over row
 // ranges).  Q has about half the entries of A (cfg 2: 7.8 vs 14.8 per row), and the pass over P and the round trip of
 // t through HBM disappear.  Same result up to rounding; AMGX_NO_FOLD=1 runs the literal sequence.
-// BSELL image of selected entries of a square-block matrix: `rows` lists block rows in storage order (-1 = padding slot),
-// slices of RB = 64 / bs consecutive list entries; keep(i, j) selects entries, mapcol(i, j) gives the stored block column,
-// padcol = column of padding steps (any valid index of the gathered vector).
-template <class Keep, class MapCol, class Scale>
-static void build_bsell_sel(const amgx_matrix& A, const std::vector<int32_t>& rows, Keep keep, MapCol mapcol, int32_t padcol, DevMatrix& D, Scale scale);
-template <class Keep, class MapCol>
-static void build_bsell_sel(const amgx_matrix& A, const std::vector<int32_t>& rows, Keep keep, MapCol mapcol, int32_t padcol, DevMatrix& D) {
-  build_bsell_sel(A, rows, keep, mapcol, padcol, D, [](int32_t, int32_t) { return 1.0; });
-}
-template <class Keep, class MapCol, class Scale>
-static void build_bsell_sel(const amgx_matrix& A, const std::vector<int32_t>& rows, Keep keep, MapCol mapcol, int32_t padcol, DevMatrix& D, Scale scale) {
-  const int bs = A.br;
-  const int RB = WAVE / bs;
-  const int64_t m = (int64_t)rows.size();
-  if (m % RB) throw Err("build_bsell_sel: the row list must be padded to whole slices");
-  const int64_t ns = m / RB;
-  std::vector<int64_t> sp(ns + 1, 0);
-  par_for(ns, [&](int64_t s0, int64_t s1, int) {
-    for (int64_t s = s0; s < s1; ++s) {
-      int w = 0;
-      for (int rb = 0; rb < RB; ++rb) {
-        const int32_t i = rows[s * RB + rb];
-        if (i < 0) continue;
-        int c = 0;
-        for (int64_t k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k) if (keep(i, A.col[k])) ++c;
-        w = std::max(w, c);
-      }
-      sp[s + 1] = w;
-    }
-  }, 16);
-  for (int64_t s = 0; s < ns; ++s) sp[s + 1] += sp[s];
-  const int64_t steps = sp[ns];
-  RawVec<int32_t> col;
-  RawVec<double> val;
-  par_assign(col, (size_t)std::max<int64_t>(1, steps * RB), padcol);
-  par_assign(val, (size_t)std::max<int64_t>(1, steps * bs * WAVE), 0.0);
-  par_for(ns, [&](int64_t s0, int64_t s1, int) {
-    for (int64_t s = s0; s < s1; ++s)
-      for (int rb = 0; rb < RB; ++rb) {
-        const int32_t i = rows[s * RB + rb];
-        if (i < 0) continue;
-        int64_t kk = sp[s];
-        for (int64_t k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k) {
-          const int32_t j = A.col[k];
-          if (!keep(i, j)) continue;
-          col[kk * RB + rb] = mapcol(i, j);
-          const double* blk = A.val + k * bs * bs;
-          const double sc = scale(i, j);
-          double* vk = val.data() + kk * (bs * WAVE);
-          for (int rr = 0; rr < bs; ++rr) {
-            const int lane = rb * bs + rr;
-            for (int c = 0; c < bs; ++c) {
-              if ((bs & 1) && c == bs - 1) vk[(bs / 2) * (2 * WAVE) + lane] = sc * blk[rr * bs + c];
-              else vk[(c / 2) * (2 * WAVE) + lane * 2 + (c & 1)] = sc * blk[rr * bs + c];
-            }
-          }
-          ++kk;
-        }
-      }
-  }, 16);
-  D.fmt = FMT_BSELL; D.br = D.bc = bs;
-  D.n_rows = A.n_rows; D.n_cols = A.n_cols;
-  D.n_slices = (int)ns;
-  D.stored = steps * RB;
-  D.stream_bytes = steps * ((int64_t)bs * WAVE * 8 + RB * 4) + 8 * (ns + 1);
-  D.bsell.slice_ptr.upload(sp); D.bsell.col.upload(col); D.bsell.val.upload(val);
-}
-
-// Block-hybrid Gauss-Seidel data of a square-block level (bgsb_sweep_kernel); the blocked colouring is validated (two coupled
-// rows of one workgroup block sharing a colour would be a data race)
-// csr: the level matrix on the device (big levels): the images are then gathered there (devbuild.hpp, dev_build_bsell)
-static void build_bgsb(const Knobs& K, const amgx_level_desc& d, DevLevel& L, const DevBcsrSrc* csr = nullptr) {
-  const int64_t n = d.A.n_rows;
-  const int bs = d.A.br, RB = WAVE / bs;
-  DevBGSB& g = L.bgsb;
-  const int BB = d.gs_block_rows;
-  if (bs != 2 && bs != 3 && bs != 6) throw Err("block-hybrid Gauss-Seidel: block sizes 2, 3, 6");
-  if (d.A.n_cols < n) throw Err("block-hybrid Gauss-Seidel on block levels: n_cols < n_rows");
-  // (n_cols > n_rows: trailing ghost columns of a rank-partitioned level; they belong to no sweep block, so their couplings sit in
-  //  `off` / `rest` with global column ids and multiply whatever the caller's exchange left behind the owned entries)
-  if (BB < RB || BB > 2048 || (int64_t)2 * BB * bs * 8 > 96 * 1024) throw Err("block-hybrid Gauss-Seidel: gs_block_rows out of range for this block size");
-  if (n == 0) { g.BB = BB; return; }
-  if (!d.color || d.n_colors <= 0) throw Err("block-hybrid Gauss-Seidel needs a blocked colouring");
-  if (!d.dinv) throw Err("dinv missing");
-  const int nc = d.n_colors;
-  std::vector<char> bad(setup_threads(), 0);
-  par_for(n, [&](int64_t i0, int64_t i1, int t) {
-    for (int64_t i = i0; i < i1; ++i) {
-      const int ci = d.color[i];
-      if (ci >= nc) { bad[t] = 1; return; }
-      if (ci < 0) continue;
-      if (d.gs_block_ids) continue;                       // (checked against the block ids below)
-      const int64_t b0 = (i / BB) * BB, b1 = b0 + BB;
-      for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) {
-        const int64_t j = d.A.col[k];
-        if (j != i && j >= b0 && j < b1 && j < n && d.color[j] == ci) { bad[t] = 2; return; }
-      }
-    }
-  });
-  for (char c : bad) { if (c == 1) throw Err("colour index out of range"); if (c == 2) throw Err("invalid blocked colouring: two coupled block rows of one block share a colour"); }
-  // sweep blocks: runs of BB consecutive rows, or the caller's compact blocks (gs_block_ids, at most BB rows each)
-  std::vector<int32_t> blk_of((size_t)n), lpos((size_t)n), blk_ptr, blk_rows((size_t)n);
-  int nblk = 0;
-  if (d.gs_block_ids) {
-    int32_t mx = -1;
-    for (int64_t i = 0; i < n; ++i) { if (d.gs_block_ids[i] < 0) throw Err("gs_block_ids: negative block id"); mx = std::max(mx, d.gs_block_ids[i]); }
-    nblk = mx + 1;
-    blk_ptr.assign((size_t)nblk + 1, 0);
-    for (int64_t i = 0; i < n; ++i) { blk_of[i] = d.gs_block_ids[i]; blk_ptr[blk_of[i] + 1]++; }
-    for (int q = 0; q < nblk; ++q) { if (blk_ptr[q + 1] > BB) throw Err("gs_block_ids: a block has more than gs_block_rows rows"); blk_ptr[q + 1] += blk_ptr[q]; }
-    std::vector<int32_t> pos(blk_ptr.begin(), blk_ptr.end() - 1);
-    for (int64_t i = 0; i < n; ++i) { lpos[i] = pos[blk_of[i]] - blk_ptr[blk_of[i]]; blk_rows[pos[blk_of[i]]++] = (int32_t)i; }
-  } else {
-    nblk = (int)((n + BB - 1) / BB);
-    blk_ptr.assign((size_t)nblk + 1, 0);
-    for (int q = 0; q <= nblk; ++q) blk_ptr[q] = (int32_t)std::min<int64_t>(n, (int64_t)q * BB);
-    for (int64_t i = 0; i < n; ++i) { blk_of[i] = (int32_t)(i / BB); lpos[i] = (int32_t)(i % BB); blk_rows[i] = (int32_t)i; }
-  }
-  // (the colouring was validated against runs of consecutive rows above; with block ids it is validated here)
-  if (d.gs_block_ids) {
-    std::vector<char> bad2(setup_threads(), 0);
-    par_for(n, [&](int64_t i0, int64_t i1, int t) {
-      for (int64_t i = i0; i < i1; ++i) {
-        const int ci = d.color[i];
-        if (ci < 0) continue;
-        for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) {
-          const int64_t j = d.A.col[k];
-          if (j != i && j < n && blk_of[j] == blk_of[i] && d.color[j] == ci) { bad2[t] = 1; return; }
-        }
-      }
-    });
-    for (char c : bad2) if (c) throw Err("invalid blocked colouring: two coupled block rows of one sweep block share a colour");
-  }
-  g.BB = BB; g.n_blocks = nblk; g.n_colors = nc;
-  // block-coloured form: colour of every sweep block (constant inside a block, coupled blocks differ)
-  std::vector<int32_t> bcol;
-  if (d.gs_block_color && d.gs_n_block_colors > 0) {
-    if (d.A.n_cols != n) throw Err("block-coloured Gauss-Seidel: square levels only (rank-partitioned levels sweep in the hybrid form)");
-    const int nbc = d.gs_n_block_colors;
-    bcol.assign((size_t)nblk, -1);
-    for (int64_t i = 0; i < n; ++i) {
-      const int c = d.gs_block_color[i];
-      if (c < 0 || c >= nbc) throw Err("gs_block_color: colour out of range");
-      if (bcol[blk_of[i]] < 0) bcol[blk_of[i]] = c;
-      else if (bcol[blk_of[i]] != c) throw Err("gs_block_color: not constant inside a sweep block");
-    }
-    std::vector<char> bad3(setup_threads(), 0);
-    par_for(n, [&](int64_t i0, int64_t i1, int t) {
-      for (int64_t i = i0; i < i1; ++i) {
-        if (d.color[i] < 0) continue;
-        for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) {
-          const int64_t j = d.A.col[k];
-          if (d.color[j] >= 0 && blk_of[j] != blk_of[i] && bcol[blk_of[j]] == bcol[blk_of[i]]) { bad3[t] = 1; return; }
-        }
-      }
-    });
-    for (char c : bad3) if (c) throw Err("invalid block colouring: two coupled sweep blocks share a colour (an in-place sweep would race)");
-    std::vector<int32_t> list((size_t)nblk);
-    g.bc_ptr.assign((size_t)nbc + 1, 0);
-    for (int q = 0; q < nblk; ++q) g.bc_ptr[bcol[q] + 1]++;
-    for (int c = 0; c < nbc; ++c) g.bc_ptr[c + 1] += g.bc_ptr[c];
-    std::vector<int> pos(g.bc_ptr.begin(), g.bc_ptr.end() - 1);
-    for (int q = 0; q < nblk; ++q) list[pos[bcol[q]]++] = q;
-    g.blk_list.upload(list);
-    g.bc = true;
-    g.n_bcolors = nbc;
-  }
-  // off: block by block in list order, every block padded to whole slices
-  std::vector<int32_t> rows_off, off_ptr(nblk + 1, 0);
-  rows_off.reserve((size_t)n + (size_t)nblk * RB);
-  for (int blk = 0; blk < nblk; ++blk) {
-    for (int32_t q = blk_ptr[blk]; q < blk_ptr[blk + 1]; ++q) rows_off.push_back(blk_rows[q]);
-    while (rows_off.size() % RB) rows_off.push_back(-1);
-    off_ptr[blk + 1] = (int32_t)(rows_off.size() / RB);
-  }
-  auto same_block = [&blk_of, n](int64_t i, int64_t j) { return j < n && blk_of[i] == blk_of[j]; };
-  // Only the in-block couplings to the colours a sweep has ALREADY visited need its new values; everything else -- couplings
-  // that leave the block, the diagonal block, in-block couplings to the colours still to come -- multiplies sweep-start values
-  // and goes into the streaming phase 0, where all waves work.  The colour phases, which run one after the other inside a
-  // workgroup, are left with ~9 % of A for line blocks (22 % for compact blocks) instead of 20 % (50 %).
-  auto lower_in = [&](int32_t i, int32_t j) { return j != i && same_block(i, j) && d.color[i] >= 0 && d.color[j] >= 0 && d.color[j] < d.color[i]; };
-  auto upper_in = [&](int32_t i, int32_t j) { return j != i && same_block(i, j) && d.color[i] >= 0 && d.color[j] >= 0 && d.color[j] > d.color[i]; };
-  DevBuf<int32_t> d_blk_of, d_lpos, d_color, d_rows;
-  DevBuf<double> d_fac;
-  DbBgsbMaps maps;
-  if (csr) {
-    d_blk_of.upload(blk_of); d_lpos.upload(lpos); d_color.upload(d.color, (size_t)n);
-    maps.blk_of = d_blk_of.p; maps.lpos = d_lpos.p; maps.color = d_color.p;
-    d_rows.upload(rows_off);
-    dev_build_bsell(*csr, d_rows.p, (int64_t)rows_off.size(), BB_OFF, maps, 0, 0.0, g.off);
-  } else
-  build_bsell_sel(d.A, rows_off, [&](int32_t i, int32_t j) { return !lower_in(i, j) && !upper_in(i, j); }, [](int32_t, int32_t j) { return j; }, 0, g.off);
-  // block-coloured form: which entries of `off` couple to a sweep block that a FORWARD sweep visits later (the "high" part);
-  // everything else of `off` (diagonal blocks, couplings to earlier blocks, couplings to rows that are never swept) is "low"
-  auto off_high = [&](int32_t i, int32_t j) { return j != i && j < n && !same_block(i, j) && d.color[i] >= 0 && d.color[j] >= 0 && bcol[blk_of[j]] > bcol[blk_of[i]]; };
-  auto off_low = [&](int32_t i, int32_t j) { return j != i && j < n && !same_block(i, j) && d.color[i] >= 0 && d.color[j] >= 0 && bcol[blk_of[j]] < bcol[blk_of[i]]; };
-  DevBuf<int32_t> d_bcol;
-  if (g.bc && csr) {
-    std::vector<int32_t> bcr((size_t)n);
-    for (int64_t i = 0; i < n; ++i) bcr[i] = bcol[blk_of[i]];
-    d_bcol.upload(bcr);
-    maps.bcolor = d_bcol.p;
-  }
-  // in: per block the swept rows by colour, every (block, colour) group padded to whole slices
-  std::vector<int32_t> rows_in, in_ptr((size_t)nblk * nc + 1, 0), in_row;
-  for (int blk = 0; blk < nblk; ++blk) {
-    for (int c = 0; c < nc; ++c) {
-      for (int32_t q = blk_ptr[blk]; q < blk_ptr[blk + 1]; ++q) if (d.color[blk_rows[q]] == c) rows_in.push_back(blk_rows[q]);
-      while (rows_in.size() % RB) rows_in.push_back(-1);
-      in_ptr[(size_t)blk * nc + c + 1] = (int32_t)(rows_in.size() / RB);
-    }
-  }
-  in_row.resize(rows_in.size());
-  for (size_t q = 0; q < rows_in.size(); ++q) in_row[q] = rows_in[q] < 0 ? -1 : lpos[rows_in[q]];
-  if (csr) {
-    d_rows.upload(rows_in);
-    dev_build_bsell(*csr, d_rows.p, (int64_t)rows_in.size(), BB_IN, maps, 0, 0.0, g.in);
-    dev_build_bsell(*csr, d_rows.p, (int64_t)rows_in.size(), BB_UPIN, maps, 0, 0.0, g.upin);
-  } else {
-    build_bsell_sel(d.A, rows_in, lower_in, [&lpos](int32_t, int32_t j) { return lpos[j]; }, 0, g.in);
-    build_bsell_sel(d.A, rows_in, upper_in, [&lpos](int32_t, int32_t j) { return lpos[j]; }, 0, g.upin);
-  }
-  if (g.upin.n_slices != g.in.n_slices) throw Err("block-hybrid Gauss-Seidel: lower / upper slice mismatch");
-  g.blk_ptr.upload(blk_ptr); g.blk_rows.upload(blk_rows);
-  g.off_ptr.upload(off_ptr); g.in_ptr.upload(in_ptr); g.in_row.upload(in_row);
-  // ---- one-pass pre-smoothing from zero: valid where dinv_k is a true inverse of fac_k * A_kk (not a pseudo-inverse) ----------
-  if (K.bgsb_no_split) return;
-  std::vector<double> fac((size_t)n, 1.0);
-  std::vector<char> nofac(setup_threads(), 0);
-  par_for(n, [&](int64_t i0, int64_t i1, int t) {
-    for (int64_t i = i0; i < i1; ++i) {
-      if (d.color[i] < 0) continue;
-      const double* Akk = nullptr;
-      for (int64_t k = d.A.rowptr[i]; k < d.A.rowptr[i + 1]; ++k) if (d.A.col[k] == i) { Akk = d.A.val + k * bs * bs; break; }
-      if (!Akk) { nofac[t] = 1; return; }
-      const double* Dk = d.dinv + i * bs * bs;
-      // M = Dinv_k A_kk must be (1 / fac) I with fac >= 1
-      double m00 = 0.0;
-      for (int c = 0; c < bs; ++c) m00 += Dk[c] * Akk[c * bs];
-      if (!(m00 > 1e-12 && m00 <= 1.0 + 1e-10)) { nofac[t] = 1; return; }
-      for (int r = 0; r < bs; ++r)
-        for (int c = 0; c < bs; ++c) {
-          double m = 0.0;
-          for (int q = 0; q < bs; ++q) m += Dk[r * bs + q] * Akk[q * bs + c];
-          if (std::fabs(m - (r == c ? m00 : 0.0)) > 1e-10 * m00) { nofac[t] = 1; return; }
-        }
-      fac[i] = 1.0 / m00;
-    }
-  });
-  for (char c : nofac) if (c) return;
-  std::vector<int32_t> rows_nat;
-  for (int64_t i = 0; i < n; ++i) rows_nat.push_back((int32_t)i);
-  while (rows_nat.size() % RB) rows_nat.push_back(-1);
-  if (g.bc) {
-    // block-coloured form: the plain inverse is expected (fac = 1 everywhere), otherwise no split (sweep + full residual)
-    for (int64_t i = 0; i < n; ++i) if (d.color[i] >= 0 && std::fabs(fac[i] - 1.0) > 1e-10) return;
-    if (csr) {
-      d_rows.upload(rows_off);
-      dev_build_bsell(*csr, d_rows.p, (int64_t)rows_off.size(), BB_OFFLO, maps, 0, 0.0, g.offlo);
-      d_rows.upload(rows_nat);
-      dev_build_bsell(*csr, d_rows.p, (int64_t)rows_nat.size(), BB_RESTBC, maps, 0, 0.0, g.rest);
-    } else {
-      build_bsell_sel(d.A, rows_off, off_low, [](int32_t, int32_t j) { return j; }, 0, g.offlo);
-      build_bsell_sel(d.A, rows_nat, [&](int32_t i, int32_t j) { return upper_in(i, j) || off_high(i, j); }, [](int32_t, int32_t j) { return j; }, 0, g.rest,
-                      [](int32_t, int32_t) { return -1.0; });
-    }
-    g.has_split = true;
-    return;
-  }
-  if (csr) {
-    d_fac.upload(fac);
-    maps.fac = d_fac.p;
-    d_rows.upload(rows_nat);
-    dev_build_bsell(*csr, d_rows.p, (int64_t)rows_nat.size(), BB_REST, maps, 0, 0.0, g.rest);
-  } else
-  build_bsell_sel(d.A, rows_nat, [&](int32_t i, int32_t j) { return !lower_in(i, j); }, [](int32_t, int32_t j) { return j; }, 0, g.rest,
-                  [&](int32_t i, int32_t j) { return (i == j && d.color[i] >= 0) ? fac[i] - 1.0 : -1.0; });
-  g.has_split = true;
-}
-
 // (block form: A has bs x bs blocks, P and Q bs x bc blocks, dinv bs x bs per block row)
 static void fold_prolongation(const amgx_matrix& A, const amgx_matrix& P, const double* dinv, double omega, HostCsr& Q) {
   const int64_t n = A.n_rows, nc = P.n_cols;
@@ -3227,7 +2477,6 @@ static void permute_matrix(const amgx_matrix& M, const int32_t* rperm, const int
   }
 }
 
-static void use_csr(amgx_matrix& M, const HostCsr& c) { M.rowptr = c.rowptr.data(); M.col = c.col.data(); M.val = c.val.data(); }
 
 // fills pl (mutable copies of the level descriptors) with colour-major versions of the GS levels; store owns the data
 static void permute_gs_levels(const Knobs& K, const amgx_hierarchy_desc* d, std::vector<amgx_level_desc>& pl, std::vector<LevelPerm>& store) {

@@ -248,7 +248,9 @@ struct DbSplit {
   const int64_t* rowptr; const int32_t* col; const double* val;
   const int32_t* color; const double* dinv;
 };
-__device__ __forceinline__ int db_split_part(const DbSplit& a, int64_t i, int ci, int64_t j) {
+// part of entry (i, j) of a row of colour ci: 0, 1, or -1 = dropped (the diagonal, a non-free column).  The one statement of the
+// rule: the kernels below and the host split (gs_images.hpp) call it.
+__host__ __device__ __forceinline__ int db_split_part(const DbSplit& a, int64_t i, int ci, int64_t j) {
   if (j == i) return -1;
   const int cj = j < a.n ? a.color[j] : 0;            // ghost columns count as live
   if (cj < 0) return -1;
@@ -305,22 +307,18 @@ __global__ __launch_bounds__(BLOCK) void db_split_fill_kernel(DbSplit a, const i
 //   BB_RESTBC the couplings to swept rows of blocks with a HIGHER block colour + BB_UPIN, negated, global columns
 //             (r = rest x after that sweep)
 enum : int { BB_ALL = 0, BB_OFF = 1, BB_IN = 2, BB_UPIN = 3, BB_REST = 4, BB_OFFLO = 5, BB_RESTBC = 6 };
-struct DbBsell {
-  int64_t m, n, ns;                     // list entries (padded to whole slices), block rows of the matrix, slices
-  int bs, sel;
-  const int32_t* rows;                  // block row of every list entry (-1: padding slot); null: natural order
-  const int64_t* rowptr; const int32_t* col; const double* val;
-  const int32_t* blk_of; const int32_t* lpos; const int32_t* color; const double* fac; const int32_t* bcolor;
-  int64_t* sp;                          // [ns + 1] cumulative block steps
-  int32_t* ocol; double* oval;
-};
-__device__ __forceinline__ bool db_bsell_keep(const DbBsell& a, int64_t i, int64_t j) {
-  if (a.sel == BB_ALL) return true;
-  const bool same = j < a.n && j != i && a.blk_of[i] == a.blk_of[j] && a.color[i] >= 0 && a.color[j] >= 0;
+// the maps of a level's sweep blocks the rules below read (host arrays for build_bsell_sel, device arrays for the kernels): block of
+// every row, its position there, its colour, fac (BB_REST) and the block colour of its block (BB_OFFLO, BB_RESTBC)
+struct DbBgsbMaps { const int32_t* blk_of = nullptr; const int32_t* lpos = nullptr; const int32_t* color = nullptr; const double* fac = nullptr; const int32_t* bcolor = nullptr; };
+// The one statement of the selection rules, for the kernels below and the host builder (gs_images.hpp, build_bsell_sel): does image
+// `sel` of a matrix of n block rows keep entry (i, j) ...
+__host__ __device__ __forceinline__ bool db_bsell_keep(const DbBgsbMaps& a, int64_t n, int sel, int64_t i, int64_t j) {
+  if (sel == BB_ALL) return true;
+  const bool same = j < n && j != i && a.blk_of[i] == a.blk_of[j] && a.color[i] >= 0 && a.color[j] >= 0;
   const bool lower = same && a.color[j] < a.color[i], upper = same && a.color[j] > a.color[i];
-  const bool other = (a.sel == BB_OFFLO || a.sel == BB_RESTBC) && j < a.n && j != i && a.blk_of[i] != a.blk_of[j] && a.color[i] >= 0 && a.color[j] >= 0;
+  const bool other = (sel == BB_OFFLO || sel == BB_RESTBC) && j < n && j != i && a.blk_of[i] != a.blk_of[j] && a.color[i] >= 0 && a.color[j] >= 0;
   const bool high = other && a.bcolor[j] > a.bcolor[i], low = other && a.bcolor[j] < a.bcolor[i];
-  switch (a.sel) {
+  switch (sel) {
     case BB_OFF: return !lower && !upper;
     case BB_IN: return lower;
     case BB_UPIN: return upper;
@@ -329,6 +327,23 @@ __device__ __forceinline__ bool db_bsell_keep(const DbBsell& a, int64_t i, int64
     default: return !lower;
   }
 }
+// ... which block column it stores for it ...
+__host__ __device__ __forceinline__ int32_t db_bsell_col(const DbBgsbMaps& a, int sel, int32_t j) {
+  return (sel == BB_IN || sel == BB_UPIN) ? a.lpos[j] : j;
+}
+// ... and the factor on its values
+__host__ __device__ __forceinline__ double db_bsell_factor(const DbBgsbMaps& a, int sel, int64_t i, int64_t j) {
+  return sel == BB_REST ? ((i == j && a.color[i] >= 0) ? a.fac[i] - 1.0 : -1.0) : (sel == BB_RESTBC ? -1.0 : 1.0);
+}
+struct DbBsell {
+  int64_t m, n, ns;                     // list entries (padded to whole slices), block rows of the matrix, slices
+  int bs, sel;
+  const int32_t* rows;                  // block row of every list entry (-1: padding slot); null: natural order
+  const int64_t* rowptr; const int32_t* col; const double* val;
+  DbBgsbMaps mp;
+  int64_t* sp;                          // [ns + 1] cumulative block steps
+  int32_t* ocol; double* oval;
+};
 // steps of every slice: the longest kept row among its RB = 64 / bs list entries (lane = list entry)
 __global__ __launch_bounds__(DB_BLOCK) void db_bsell_width_kernel(DbBsell a) {
   const int64_t s = (int64_t)blockIdx.x * (DB_BLOCK / WAVE) + (threadIdx.x >> 6);
@@ -340,7 +355,7 @@ __global__ __launch_bounds__(DB_BLOCK) void db_bsell_width_kernel(DbBsell a) {
   if (l < RB && q < a.m) {
     const int64_t i = a.rows ? (int64_t)a.rows[q] : (q < a.n ? q : -1);
     if (i >= 0)
-      for (int64_t k = a.rowptr[i]; k < a.rowptr[i + 1]; ++k) if (db_bsell_keep(a, i, a.col[k])) ++w;
+      for (int64_t k = a.rowptr[i]; k < a.rowptr[i + 1]; ++k) if (db_bsell_keep(a.mp, a.n, a.sel, i, a.col[k])) ++w;
   }
   for (int o = 32; o > 0; o >>= 1) w = max(w, __shfl_xor(w, o));
   if (l == 0) { a.sp[s + 1] = w; if (s == 0) a.sp[0] = 0; }
@@ -367,9 +382,9 @@ __global__ __launch_bounds__(DB_BLOCK) void db_bsell_fill_kernel(DbBsell a) {
   int64_t kk = k0;
   for (int64_t k = a.rowptr[i]; k < a.rowptr[i + 1]; ++k) {
     const int32_t j = a.col[k];
-    if (!db_bsell_keep(a, i, j)) continue;
-    if (rr == 0) a.ocol[kk * RB + rb] = (a.sel == BB_IN || a.sel == BB_UPIN) ? a.lpos[j] : j;
-    const double sc = a.sel == BB_REST ? ((i == j && a.color[i] >= 0) ? a.fac[i] - 1.0 : -1.0) : (a.sel == BB_RESTBC ? -1.0 : 1.0);
+    if (!db_bsell_keep(a.mp, a.n, a.sel, i, j)) continue;
+    if (rr == 0) a.ocol[kk * RB + rb] = db_bsell_col(a.mp, a.sel, j);
+    const double sc = db_bsell_factor(a.mp, a.sel, i, j);
     const double* __restrict__ blk = a.val + k * (bs * bs) + rr * bs;
     double* __restrict__ vk = a.oval + kk * (bs * WAVE);
     for (int c = 0; c < bs; ++c) {
@@ -756,7 +771,6 @@ struct DevBcsrSrc {                      // a square-block CSR matrix on the dev
     val.upload(A.val, (size_t)std::max<int64_t>(1, nnz) * bs * bs);
   }
 };
-struct DbBgsbMaps { const int32_t* blk_of = nullptr; const int32_t* lpos = nullptr; const int32_t* color = nullptr; const double* fac = nullptr; const int32_t* bcolor = nullptr; };
 
 static bool dev_bsell_wanted(const Knobs& K, const amgx_matrix& A) {
   if (K.host_images || K.no_bsell) return false;
@@ -775,7 +789,7 @@ static bool dev_build_bsell(const DevBcsrSrc& A, const int32_t* d_rows, int64_t 
   const int64_t ns = (m + RB - 1) / RB;
   DevBuf<int64_t> sp;
   sp.alloc((size_t)ns + 1);
-  DbBsell a{m, A.n_rows, ns, bs, sel, d_rows, A.rowptr.p, A.col.p, A.val.p, mp.blk_of, mp.lpos, mp.color, mp.fac, mp.bcolor, sp.p, nullptr, nullptr};
+  DbBsell a{m, A.n_rows, ns, bs, sel, d_rows, A.rowptr.p, A.col.p, A.val.p, mp, sp.p, nullptr, nullptr};
   if (ns == 0) HIPCHK(hipMemset(sp.p, 0, sizeof(int64_t)));
   else {
     launch(db_bsell_width_kernel, (unsigned)((ns + 3) / 4), DB_BLOCK, 0, 0, a);
@@ -876,9 +890,8 @@ static void verify_same_lw(const DevMatrix& a, const DevBuf<int32_t>& ap, const 
 }
 
 // ---- AMGX_VERIFY_IMAGES: the cross-checks of the construction steps (build_level.hpp), one call from the step that built the
-// image.  Each forms the host builder's image of the same input and compares the two bit by bit.
-static void build_gsb(const Knobs& K, const amgx_level_desc& d, DevLevel& L, const amgx_matrix* P, const DevCsrSrc* csr);     // (amgx.hip)
-static void build_bgsb(const Knobs& K, const amgx_level_desc& d, DevLevel& L, const DevBcsrSrc* csr);
+// image.  Each forms the host builder's image of the same input and compares the two bit by bit.  (Those of the Gauss-Seidel data,
+// verify_gsb / verify_bgsb, stand with their builders in gs_images.hpp.)
 static void fold_prolongation(const amgx_matrix& A, const amgx_matrix& P, const double* dinv, double omega, HostCsr& Q);
 
 // the level matrix: device BSELL image / device SELL image / declined by the device builder
@@ -897,39 +910,6 @@ static void verify_level_declined(const Knobs& K, const amgx_matrix& A) {
   DevMatrix H;
   upload_matrix(K, A, H, "A", true, true, false);
   if (H.fmt == FMT_SELL && H.lanes == 1) throw Err("AMGX_VERIFY_IMAGES: the device builder declined A where the host builder forms a SELL image");
-}
-
-// block-hybrid Gauss-Seidel data of a square-block level
-static void verify_bgsb(const Knobs& K, const amgx_level_desc& s, const DevLevel& L) {
-  DevLevel H;
-  H.n = L.n; H.ncols = L.ncols; H.bs = L.bs;
-  build_bgsb(K, s, H, nullptr);
-  const DevBGSB &x = L.bgsb, &y = H.bgsb;
-  if (x.BB != y.BB || x.n_blocks != y.n_blocks || x.n_colors != y.n_colors || x.has_split != y.has_split) throw Err("AMGX_VERIFY_IMAGES: block-hybrid Gauss-Seidel (blocks): the descriptors differ");
-  verify_same_bsell(x.off, y.off, "block-hybrid Gauss-Seidel: off");
-  verify_same_bsell(x.in, y.in, "block-hybrid Gauss-Seidel: in");
-  verify_same_bsell(x.upin, y.upin, "block-hybrid Gauss-Seidel: upin");
-  if (x.has_split) verify_same_bsell(x.rest, y.rest, "block-hybrid Gauss-Seidel: rest");
-  if (x.bc != y.bc || x.n_bcolors != y.n_bcolors) throw Err("AMGX_VERIFY_IMAGES: block-coloured Gauss-Seidel: the descriptors differ");
-  if (x.bc && x.has_split) verify_same_bsell(x.offlo, y.offlo, "block-coloured Gauss-Seidel: offlo");
-}
-
-// ... of a scalar level
-static void verify_gsb(const Knobs& K, const amgx_level_desc& s, const DevLevel& L) {
-  DevLevel H;
-  H.n = L.n; H.ncols = L.ncols; H.bs = L.bs;
-  build_gsb(K, s, H, &s.P, nullptr);
-  const DevGSB &x = L.gsb, &y = H.gsb;
-  if (x.B != y.B || x.G != y.G || x.TH != y.TH || x.n_blocks != y.n_blocks || x.n_colors != y.n_colors || x.lowin_maxw != y.lowin_maxw || x.full_maxw != y.full_maxw ||
-      x.has_split != y.has_split) throw Err("AMGX_VERIFY_IMAGES: block-hybrid Gauss-Seidel: the descriptors differ");
-  const size_t nsl = (size_t)((int64_t)x.n_blocks * x.B / (WAVE / x.G));
-  verify_same_sell(x.full, y.full, nsl, 0, "block-hybrid Gauss-Seidel: A");
-  if (x.has_split) {
-    verify_same_sell(x.lowin, y.lowin, nsl, 0, "block-hybrid Gauss-Seidel: lower part");
-    verify_same_image(x.rest, y.rest, "block-hybrid Gauss-Seidel: rest");
-    const auto cx = db_download(x.cvec, (size_t)L.n), cy = db_download(y.cvec, (size_t)L.n);
-    if (std::memcmp(cx.data(), cy.data(), (size_t)L.n * sizeof(double)) != 0) throw Err("AMGX_VERIFY_IMAGES: block-hybrid Gauss-Seidel: cvec differs");
-  }
 }
 
 // local-window image of A' with g lanes per row; host_lw(g, image, offsets, columns) is the caller's host builder

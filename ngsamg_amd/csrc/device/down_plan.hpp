@@ -1,8 +1,8 @@
 // The shape of a level's fused down launch (pre-smoothing or residual + chunk-local restriction), decided once at create time:
 // DownPlan, the value lists of the five kernel templates, and the chunk arithmetic.  resolve_paths (amgx.hip) fills the plans and
 // checks them, Handle::down_launch launches from them, amgx_level_paths and amgx_time_op report from them, and the builders
-// (build_level.hpp, build_gsb_images) ask the same lists whether a kernel exists.  Host-only: no HIP in here, so a plain C++17
-// compiler builds it (tests/test_down_plan_cpu.py).
+// (build_level.hpp; gs_images.hpp, build_gsb_images) ask the same lists whether a kernel exists.  Host-only: no HIP in here, so a
+// plain C++17 compiler builds it (tests/test_down_plan_cpu.py).
 #pragma once
 #include <algorithm>
 #include <cstddef>

@@ -85,6 +85,20 @@ CASES += [("multicolour scalar 21^3 split", (_poisson, (21, 21, 21)), dict(sm_ty
           ("multicolour row list bs=2", (_block_rows, 2, 17, 700), dict(sm_type="gs"), {"AMGX_NO_BGS_BSELL": "1"}, True),
           ("aggregate blocks 14x13x12", (_poisson_blocks, (14, 13, 12)), dict(sm_type="bgs"), {}, True),
           ("jacobi 21^3", (_poisson, (21, 21, 21)), dict(sm_type="jacobi"), {}, False)]
+# both image builders of the Gauss-Seidel data: the host loops (small levels, above) and the device kernels (DEV: every level)
+DEV = {"AMGX_DEV_IMAGES_MIN_ROWS": "0"}
+DEV1 = {**DEV, "AMGX_SELL_MAX_LANES": "1"}            # scalar levels: the device builder forms the one-lane images only
+COMPACT = {"AMGX_BGSB_COMPACT": "1"}
+LW = {"AMGX_GSB_LW": "1", "AMGX_LW_MIN_ROWS": "0"}
+CASES += [("hybrid scalar 21^3 device images", (_poisson, (21, 21, 21)), dict(sm_type="hgs"), DEV1, True),
+          ("hybrid scalar rows of 64 device images", (_scalar_rows, 64), dict(sm_type="hgs"), DEV1, True),
+          ("hybrid block bs=3 device images", (_block_rows, 3), dict(sm_type="hgs"), DEV, True),
+          ("block-coloured bs=3 device images", (_block_rows, 3), dict(sm_type="hgs"), {**BC, **DEV}, True),
+          ("compact blocks bs=3", (_block_rows, 3), dict(sm_type="hgs"), COMPACT, True),
+          ("compact blocks bs=3 device images", (_block_rows, 3), dict(sm_type="hgs"), {**COMPACT, **DEV}, True),
+          ("hybrid scalar rows of 64 local window", (_scalar_rows, 64), dict(sm_type="hgs"), LW, True),
+          ("hybrid scalar rows of 64 local window device images", (_scalar_rows, 64), dict(sm_type="hgs"), {**LW, **DEV1}, True),
+          ("multicolour bsell bs=2 split", (_block_rows, 2, 151, None, True), dict(sm_type="gs"), {"AMGX_BGS_BSELL_MIN": "1"}, True)]
 
 # ---- two virtual ranks: name, problem, DistributedAMG arguments, environment at create
 HGS = dict(sm_type="hgs", hgs_block_rows=256)
