@@ -63,9 +63,13 @@ enum {
                               /* with the classical form to ~1e-6                                                            */
   AMGX_MULTI_INTERLEAVED = 32,/* multi-vector calls: entry (row i, column j) of a multi-vector lives at i*k + j and ld is      */
                               /* ignored.  Without it: column-major, column j starts at j*ld, ld >= level size                */
-  AMGX_MULTI_FUSE = 64        /* amgx_apply_multi / amgx_matvec_multi / amgx_pcg_multi: run fused column groups on every handle */
+  AMGX_MULTI_FUSE = 64,       /* amgx_apply_multi / amgx_matvec_multi / amgx_pcg_multi: run fused column groups on every handle */
                               /* that qualifies under the EXTENDED rule (Chebyshev and block levels, see below); a handle that  */
                               /* does not qualify runs the column loop -- never an error.  Without it every call is as before   */
+  AMGX_MULTI_FUSE_GS = 128    /* the same calls, amgx_smooth_multi, amgx_multi_plan / amgx_multi_note: implies AMGX_MULTI_FUSE   */
+                              /* and admits scalar Gauss-Seidel levels (block-hybrid or multicolour form, see below) as well; a  */
+                              /* handle that does not qualify runs the column loop.  Without it every call is as before, calls   */
+                              /* that carry AMGX_MULTI_FUSE alone included                                                       */
 };
 
 typedef struct amgx_level_desc {
@@ -375,8 +379,19 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  * single-vector smoother with the same coefficients and read the single-precision image where the level has one; amgx_matvec_multi
  * and the level-0 product of amgx_pcg_multi read the fp64 image.  Gauss-Seidel in any form, W / BS cycles and the ProxySmoother keep
  * the column loop.
- *   amgx_multi_plan  : the outputs of amgx_multi_info for a call that carries `flags` (only AMGX_MULTI_FUSE is looked at; flags = 0
- *                      answers exactly what amgx_multi_info answers); work_bytes counts one more vector per Chebyshev level
+ * With AMGX_MULTI_FUSE_GS (opt-in per call; it implies AMGX_MULTI_FUSE) a smoothed level may also be AMGX_SM_GS,
+ * mixed freely with Jacobi and Chebyshev levels, if it is scalar (bs = 1), square, in the caller's numbering, plain, and swept in
+ * the block-hybrid or the scalar multicolour form.  Its sweeps keep, per column, the order of additions of the single-vector
+ * sweep: a column of amgx_smooth_multi equals amgx_smooth bit for bit.  Gauss-Seidel on a block level and AMGX_SM_BGS keep the
+ * column loop (amgx_multi_note names the smoother and the level).
+ *   amgx_smooth_multi: one plain smoother step per column, amgx_smooth(level, dir, x_j, b_j, res, 0, 0, x_zero) with a res of its
+ *                      own; layout and pointers as in amgx_matvec_multi, X and B have the level's size (no ghost entries).  With
+ *                      AMGX_MULTI_FUSE_GS on a Gauss-Seidel level that has the multi-vector sweep, groups of 4 and 2 columns run it
+ *                      (whatever the rest of the handle looks like); otherwise, and for a single left-over column, a column loop
+ *                      over the single-vector step.  x_zero is the caller's promise that X is zero, as in amgx_smooth.
+ *   amgx_multi_plan  : the outputs of amgx_multi_info for a call that carries `flags` (only AMGX_MULTI_FUSE and AMGX_MULTI_FUSE_GS
+ *                      are looked at; flags = 0 answers exactly what amgx_multi_info answers); work_bytes counts one more vector per
+ *                      Chebyshev level
  *   amgx_multi_note  : the first reason why the handle is not fused under `flags` (it names the level), "" when it is fused.  The
  *                      string lives until the calling thread's next amgx_multi_note */
 #define AMGX_MULTI_MAX 8
@@ -384,6 +399,7 @@ int amgx_apply_multi(amgx_handle h, int k, const double* B, int64_t ldb, double*
 int amgx_matvec_multi(amgx_handle h, int level, int k, const double* X, int64_t ldx, double* Y, int64_t ldy, int flags);
 int amgx_pcg_multi(amgx_handle h, int k, const double* B, int64_t ldb, double* X, int64_t ldx, double tol, int maxit, int use_precond, int flags,
                    double* errs, int32_t* iters);
+int amgx_smooth_multi(amgx_handle h, int level, int dir, int k, double* X, int64_t ldx, const double* B, int64_t ldb, int x_zero, int flags);
 int amgx_multi_info(amgx_handle h, int k, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes);
 int amgx_multi_plan(amgx_handle h, int k, int flags, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes);
 const char* amgx_multi_note(amgx_handle h, int flags);

@@ -242,6 +242,7 @@ AMGX_HOST_PTR, AMGX_DEVICE_PTR, AMGX_NO_GRAPH = 0, 1, 2
 AMGX_PCG_SINGLE_REDUCTION = 16
 AMGX_MULTI_INTERLEAVED = 32
 AMGX_MULTI_FUSE = 64
+AMGX_MULTI_FUSE_GS = 128                     # implies AMGX_MULTI_FUSE; admits scalar Gauss-Seidel levels
 AMGX_MULTI_MAX = 8
 AMGX_MV_MAX = 32                             # columns of a multi-vector in amgx_mv_gram / amgx_mv_combine
 
@@ -259,6 +260,7 @@ AMGX_SYMBOLS = [
     "amgx_gss4_info", "amgx_gss4_smooth", "amgx_gss4_smooth_res", "amgx_gss4_mult_add",
     "amgx_device_count", "amgx_spgemm", "amgx_galerkin", "amgx_csr_result_fetch",
     "amgx_apply_multi", "amgx_matvec_multi", "amgx_pcg_multi", "amgx_multi_info", "amgx_multi_plan", "amgx_multi_note",
+    "amgx_smooth_multi",
     "amgx_smoother_info",
     "amgx_mv_gram", "amgx_mv_combine", "amgx_mv_gram_plan",
 ]
@@ -315,6 +317,7 @@ def hip():
     lib.amgx_apply_multi.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_int]
     lib.amgx_matvec_multi.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int]
     lib.amgx_pcg_multi.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, c_f64p, c_i32p]
+    lib.amgx_smooth_multi.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_int]
     lib.amgx_multi_info.argtypes = [vp, C.c_int, c_i32p, c_i32p, c_i32p, c_i64p]
     lib.amgx_multi_plan.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_i64p]
     lib.amgx_multi_note.argtypes = [vp, C.c_int]

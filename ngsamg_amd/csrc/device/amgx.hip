@@ -1526,7 +1526,7 @@ struct Handle {
   // single-precision image where amgx_create gave the level one (DevMatrix::has32); every other caller reads the fp64 image.
   template <int NV, int EP>
   void product(const DevMatrix& M, const double* x, double* y, const EpArgs& ep, const Span sp = Span(), bool sm_pass = false) {
-    static_assert(NV == 1 || (EP != EP_PRE && EP != EP_CRES), "EP_PRE and EP_CRES are built for single vectors only");
+    static_assert(NV == 1 || EP != EP_PRE, "EP_PRE is built for single vectors only");
     if (M.n_rows == 0) return;
     if (NV > 1 && sp.part != PART_ALL) throw Err("multi-vector product: rank-partitioned levels are not supported");
     // the float image exists for non-windowed SELL and BSELL, under EP_RES / EP_CHEB
@@ -1584,6 +1584,8 @@ struct Handle {
       if (!dispatch(CsrLanes{}, M.lanes, run)) run(Int<64>{});
     } else if constexpr (EP == EP_PRE) {
       throw Err("EP_PRE is only built for scalar matrices");
+    } else if constexpr (NV > 1 && EP == EP_CRES) {
+      throw Err("multi-vector product: EP_CRES is only built for scalar matrices");
     } else if (M.fmt == FMT_BSELL) {
       // units of RB = 64 / bs block rows (one slice); slices that straddle n_int belong to the boundary part
       unit_range(sp, WAVE / M.br, M.n_slices, a, b);
@@ -1789,6 +1791,60 @@ struct Handle {
       if (!dispatch<1, 2, 4, 8>(g.G, run_g)) run_g(Int<16>{});       // any other lane count: the 16-lane kernel
     };
     if (!dispatch<256, 512>(g.TH, run)) run(Int<1024>{});            // any other workgroup size: 1024
+  }
+
+  // ---- Gauss-Seidel sweeps on NV = 2, 4 interleaved vectors (AMGX_MULTI_FUSE_GS; kernels in multi_kernels.hpp).
+  // Whole levels only; which levels have them is asked here, next to the launchers (Multi::decide_gs, amgx_smooth_multi).
+  bool multi_sweep_ok(const DevLevel& L) const {
+    if (L.sm_type != AMGX_SM_GS || L.bs != 1 || L.n != L.ncols || !L.paths.plain) return false;
+    return L.paths.sweep == SWEEP_GSB || L.paths.sweep == SWEEP_MC;
+  }
+  // gsb_sweep on NV vectors: xin == nullptr is the sweep from zero (over `lowin` where the level has the split: the narrow form
+  // where gsb.narrow holds); every other sweep reads `full` in the plain form
+  template <int NV>
+  void gsb_sweep_nv(const DevLevel& L, int dir, const double* xin, double* xout, const double* b) {
+    const DevGSB& g = L.gsb;
+    if (g.n_blocks <= 0) return;
+    if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
+    const bool fz = xin == nullptr;
+    const bool lowin = fz && L.paths.zero_split;
+    GsbArgs a{g.rowid.p, g.slotcolor.p, L.dinv.p, b, g.n_colors, dir, nullptr, nullptr};
+    const SellMat M = lowin ? g.lowin.view() : g.full.view();
+    const bool narrow = lowin && g.narrow;
+    auto run = [&](auto TT) {
+      auto run_g = [&](auto GG) {
+        auto sweep = [&](auto ZZ, auto WW) { launch(gsb_sweep_nv_kernel<TT(), GG(), ZZ(), WW(), NV>, g.n_blocks, TT(), 0, stream, L.n, M, a, xin, xout); };
+        if (narrow) return sweep(std::true_type{}, Int<2>{});
+        if (fz) return sweep(std::true_type{}, Int<GSB_WP>{});
+        sweep(std::false_type{}, Int<GSB_WP>{});
+      };
+      if (!dispatch<1, 2, 4, 8>(g.G, run_g)) run_g(Int<16>{});       // (the lane counts of gsb_sweep)
+    };
+    if (!dispatch<256, 512>(g.TH, run)) run(Int<1024>{});
+  }
+  // gs_sweep on NV vectors (scalar multicolour levels): one launch per colour, in place
+  template <int NV>
+  void gs_sweep_nv(const DevLevel& L, int dir, double* x, const double* b, bool lower_only = false) {
+    const DevGS& g = L.gs;
+    const DevMatrix::Sell& copy = (lower_only && g.has_split) ? g.lower : g.sell;
+    if (L.bs != 1 || L.paths.sweep != SWEEP_MC) throw Err("multi-vector Gauss-Seidel: the level has no scalar multicolour form");
+    for (int q = 0; q < g.n_colors; ++q) {
+      const int c = dir == 0 ? q : g.n_colors - 1 - q;
+      const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
+      if (s1 == s0) continue;
+      const int grid = (s1 - s0 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+      auto run = [&](auto GG) { launch(gs_color_nv_kernel<GG(), NV>, grid, BLOCK, 0, stream, s0, s1, copy.view(), g.rowid.p, L.dinv.p, b, x); };
+      if (!dispatch<1, 2, 4, 8>(g.lanes, run)) run(Int<16>{});
+    }
+  }
+  // r = -(U x) on NV vectors right after the multicolour sweep from zero over `lower` (residual_after_zero, SWEEP_MC)
+  template <int NV>
+  void gs_upper_residual_nv(const DevLevel& L, const double* x, double* r) {
+    const DevGS& g = L.gs;
+    if (g.n_slices_total <= 0) return;
+    const int grid = (g.n_slices_total + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    auto run = [&](auto GG) { launch(gs_upper_residual_nv_kernel<GG(), NV>, grid, BLOCK, 0, stream, g.n_slices_total, g.upper.view(), g.rowid.p, x, r); };
+    if (!dispatch<1, 2, 4, 8>(g.lanes, run)) run(Int<16>{});
   }
 
   // one block-hybrid Gauss-Seidel sweep on a square-block level (bgsb_sweep_kernel): ONE launch; xin == nullptr: from x = 0

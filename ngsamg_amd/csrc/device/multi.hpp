@@ -7,7 +7,9 @@
 // vectors.  Inside the handle multi-vectors are interleaved, entry (row i, column j) at i*NV + j: a gathered column index
 // then costs one address and 8*NV contiguous bytes.  Every other handle answers the same calls through a column loop over the
 // single-vector path -- unless the call carries AMGX_MULTI_FUSE: then handles whose smoothed levels are plain
-// Jacobi or Chebyshev levels with block size 1, 2, 3 or 6 run fused groups too (Multi::decide_extended).
+// Jacobi or Chebyshev levels with block size 1, 2, 3 or 6 run fused groups too (Multi::decide_extended).  AMGX_MULTI_FUSE_GS
+//  implies that flag and admits scalar Gauss-Seidel levels in the block-hybrid or the multicolour form as well
+// (Multi::decide_gs); their sweeps on NV vectors are Handle::gsb_sweep_nv / gs_sweep_nv.
 //
 // This file is the host side.  The kernels are in multi_kernels.hpp; which of them serves a matrix is decided in ONE place,
 // Handle::product<NV, EP> (amgx.hip), next to the value lists that Handle::multi_*_ok ask; the Chebyshev recurrence is
@@ -39,13 +41,16 @@ struct MultiState {
   std::string why;                      // fused == 0: the first reason
   int fused_x = -1;                     // the same decision under AMGX_MULTI_FUSE (the extended rule)
   std::string why_x;
+  int fused_g = -1;                     // ... and under AMGX_MULTI_FUSE_GS (the extended rule plus scalar Gauss-Seidel levels)
+  std::string why_g;
   MultiWork work[MULTI_MAX + 1];        // by width (2, 4)
   DevBuf<double> col_in, col_out;       // one contiguous column (single-vector path behind an interleaved argument)
   DevBuf<double> stage_b, stage_x;      // host-pointer calls
+  DevBuf<double> sm_x, sm_b, sm_t, sm_r; // amgx_smooth_multi: interleaved x, b and the sweep's other buffer of a group; res of a single column
   DevBuf<double> kr[5];                 // amgx_pcg_multi: b, x, d, w, s (interleaved, width k)
   DevBuf<double> kr_sc, kr_partial;
   DevBuf<int32_t> kr_active;
-  using Key = std::tuple<const double*, double*, int, int, int64_t, int64_t, int>;   // b, x, k, layout, ldb, ldx, extended rule in force
+  using Key = std::tuple<const double*, double*, int, int, int64_t, int64_t, int>;   // b, x, k, layout, ldb, ldx, rule in force (0, 1, 2)
   GraphCache<Key> graphs;
 };
 
@@ -55,17 +60,24 @@ void multi_free(MultiState* s) { delete s; }
 struct Multi {
   Handle& h;
   MultiState& st;
+  const bool gs_flag;                   // the call carries AMGX_MULTI_FUSE_GS (which implies AMGX_MULTI_FUSE)
   const bool fuse_flag;                 // the call carries AMGX_MULTI_FUSE
   const bool fz;                        // this call runs fused groups
   explicit Multi(Handle& hh, int flags = 0)
-      : h(hh), st(state(hh)), fuse_flag(flags & AMGX_MULTI_FUSE), fz(st.fused == 1 || (fuse_flag && st.fused_x == 1)) {}
-  bool extended() const { return fuse_flag && st.fused != 1; }     // the flag decides the path (a scalar Jacobi handle: one path, one graph)
-  const std::string& note() const { return extended() ? st.why_x : st.why; }
+      : h(hh), st(state(hh)), gs_flag(flags & AMGX_MULTI_FUSE_GS), fuse_flag(flags & (AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS)),
+        fz(st.fused == 1 || (fuse_flag && st.fused_x == 1) || (gs_flag && st.fused_g == 1)) {}
+  // the rule in force: the flags decide the path only where the narrower rule does not hold (a scalar Jacobi handle: one path,
+  // one graph; a handle without Gauss-Seidel levels runs the same cycle under both flags)
+  int rule() const {
+    if (st.fused == 1 || !fuse_flag) return 0;
+    return gs_flag && st.fused_x != 1 ? 2 : 1;
+  }
+  const std::string& note() const { const int r = rule(); return r == 2 ? st.why_g : r == 1 ? st.why_x : st.why; }
 
   static MultiState& state(Handle& h) {
     if (!h.multi) h.multi = new MultiState;
     MultiState& s = *h.multi;
-    if (s.fused < 0) { decide(h, s); decide_extended(h, s); }
+    if (s.fused < 0) { decide(h, s); decide_extended(h, s); decide_gs(h, s); }
     return s;
   }
   // all-or-nothing rule of the fused path: V-cycle; every smoothed level scalar, plain Jacobi, square, in the caller's numbering
@@ -111,6 +123,35 @@ struct Multi {
       if (smoothed && V.n > 0 && (!Handle::multi_transfer_ok(V.P) || !Handle::multi_transfer_ok(V.PT))) { s.why_x = "transfer format" + at; return; }
     }
     s.fused_x = 1;
+  }
+
+  // the rule of AMGX_MULTI_FUSE_GS: the extended rule, and a smoothed level may also be AMGX_SM_GS where Handle::multi_sweep_ok
+  // holds -- scalar, square, plain, swept in the block-hybrid (SWEEP_GSB) or the scalar multicolour form (SWEEP_MC).  A superset of
+  // decide_extended(): fused_x == 1 implies fused_g == 1.  Gauss-Seidel on a block level and AMGX_SM_BGS keep the column loop.
+  static void decide_gs(Handle& h, MultiState& s) {
+    s.fused_g = 0;
+    const int L = h.n_levels();
+    if (h.cycle != AMGX_CYCLE_V) { s.why_g = "cycle is not V"; return; }
+    for (int l = 0; l < L; ++l) {
+      const DevLevel& V = h.lev[l];
+      const std::string at = " (level " + std::to_string(l) + ")";
+      const bool smoothed = l + 1 < L;
+      const bool gs = smoothed && V.sm_type == AMGX_SM_GS;
+      if (smoothed) {
+        if (V.sm_type == AMGX_SM_BGS) { s.why_g = "block Gauss-Seidel (bgs) smoother" + at; return; }
+        if (gs && V.bs != 1) { s.why_g = "Gauss-Seidel on a block level" + at; return; }
+        if (!gs && V.sm_type != AMGX_SM_JACOBI && V.sm_type != AMGX_SM_CHEBY) { s.why_g = "smoother is not Jacobi, Chebyshev or Gauss-Seidel" + at; return; }
+        if (!h.plain(V)) { s.why_g = "sm_steps > 1 or sm_symm" + at; return; }
+        if (V.sm_type == AMGX_SM_CHEBY && (V.cheb_degree < 1 || V.cheb_degree > 8)) { s.why_g = "Chebyshev level without coefficients" + at; return; }
+      }
+      if (V.bs != 1 && V.bs != 2 && V.bs != 3 && V.bs != 6) { s.why_g = "block size is not 1, 2, 3 or 6" + at; return; }
+      if (V.n != V.ncols) { s.why_g = "ghost columns" + at; return; }
+      if (h.permuted(l)) { s.why_g = "renumbered level" + at; return; }
+      if (gs && V.n > 0 && !h.multi_sweep_ok(V)) { s.why_g = "Gauss-Seidel sweep form without a multi-vector kernel" + at; return; }
+      if (V.n > 0 && (!Handle::multi_level_ok(V.A) || V.A.br != V.bs)) { s.why_g = "level matrix format" + at; return; }
+      if (smoothed && V.n > 0 && (!Handle::multi_transfer_ok(V.P) || !Handle::multi_transfer_ok(V.PT))) { s.why_g = "transfer format" + at; return; }
+    }
+    s.fused_g = 1;
   }
 
   // first level that the multi cycle hands to ONE dense product (collapsed operator or the coarsest level's inverse)
@@ -184,6 +225,43 @@ struct Multi {
     launch(multi_unpack_kernel, Handle::grid_for(n * w), BLOCK, 0, h.stream, n, w, src, dst, rs, cs, c0);
   }
 
+  // Gauss-Seidel on w interleaved vectors of a level that Handle::multi_sweep_ok admits
+  template <class F>
+  static void width(int w, F&& run) {
+    if (!dispatch<2, 4>(w, run)) throw Err("multi-vector Gauss-Seidel: width must be 2 or 4");
+  }
+  // one sweep on the iterate `cur`; returns the buffer that holds the result (Handle::sweep: `oth` for the out-of-place hybrid form)
+  double* gs_sweep(int w, const DevLevel& V, int dir, double* cur, double* oth, const double* b) {
+    if (V.n == 0) return cur;
+    if (V.paths.sweep == SWEEP_GSB) { width(w, [&](auto W) { h.gsb_sweep_nv<W()>(V, dir, cur, oth, b); }); return oth; }
+    width(w, [&](auto W) { h.gs_sweep_nv<W()>(V, dir, cur, b); });
+    return cur;
+  }
+  // the residual identity of the level's split images can be used on w vectors (Handle::residual_after_zero)
+  static bool gs_split(const DevLevel& V) {
+    if (!V.paths.zero_split) return false;
+    return V.paths.sweep == SWEEP_MC || Handle::multi_scalar_ok(V.gsb.rest);
+  }
+  // forward sweep from zero b -> x, then res = b - A x: Handle::sweep_from_zero + residual_after_zero per column
+  void gs_down(int w, const DevLevel& V, const double* b, double* x, double* res) {
+    if (V.n == 0) return;
+    const bool split = gs_split(V);
+    if (V.paths.sweep == SWEEP_GSB) {
+      width(w, [&](auto W) { h.gsb_sweep_nv<W()>(V, 0, nullptr, x, b); });
+      // r = c .* x - rest x (the sweep from zero read `lowin`: A is read once in total)
+      if (split) { spmm<EP_CRES>(w, V.gsb.rest, x, res, EpArgs{x, nullptr, V.gsb.cvec.p, 0.0, nullptr, 0}); return; }
+    } else {
+      h.zero(x, V.len() * w);
+      if (split && V.gs.has_split) {                           // r = -(U x) on the swept rows, 0 elsewhere
+        h.zero(res, V.len() * w);
+        width(w, [&](auto W) { h.gs_sweep_nv<W()>(V, 0, x, b, true); h.gs_upper_residual_nv<W()>(V, x, res); });
+        return;
+      }
+      width(w, [&](auto W) { h.gs_sweep_nv<W()>(V, 0, x, b); });
+    }
+    spmm<EP_RES>(w, V.A, x, res, EpArgs{b, nullptr, nullptr, 0.0, nullptr, 0}, true);
+  }
+
   void coarse_multi(int w, const double* rhs, double* x) {
     const DevLevel& V = h.lev.back();
     if (h.clev != AMGX_CLEV_INV || h.coarse_n == 0) { h.zero(x, V.len() * w); return; }
@@ -214,6 +292,11 @@ struct Multi {
       double* xl = l == 0 ? x : W.lev[l].x.p;
       const double* bl = l == 0 ? b : W.lev[l].rhs.p;
       double* const tmp = W.lev[l].tmp.p;
+      if (V.sm_type == AMGX_SM_GS) {                           // sweep from zero and the residual by the level's identity
+        gs_down(w, V, bl, xl, W.lev[l].res.p);
+        spmm<EP_MULT>(w, V.PT, W.lev[l].res.p, W.lev[l + 1].rhs.p, none);
+        continue;
+      }
       if (V.sm_type == AMGX_SM_CHEBY) {                        // cheb_smooth from zero per column
         cheb(w, V, ChebEntry::ZERO, xl, xl, bl, tmp, W.lev[l].d.p);
       } else diag(w, V, bl, xl, V.omega);
@@ -227,7 +310,11 @@ struct Multi {
       double* xl = l == 0 ? x : W.lev[l].x.p;
       const double* bl = l == 0 ? b : W.lev[l].rhs.p;
       double* const tmp = W.lev[l].tmp.p;
-      if (V.sm_type == AMGX_SM_CHEBY) {                        // t = x + P x_c where the last of the k passes lands in x
+      if (V.sm_type == AMGX_SM_GS) {                           // t = x + P x_c, backward sweep t -> x (in place: t = x)
+        double* t = V.paths.in_place ? xl : tmp;
+        spmm<EP_AXPY>(w, V.P, W.lev[l + 1].x.p, t, EpArgs{nullptr, xl, nullptr, 1.0, nullptr, 0});
+        if (gs_sweep(w, V, 1, t, xl, bl) != xl) throw Err("multi-vector cycle: the Gauss-Seidel sweep did not end in x");
+      } else if (V.sm_type == AMGX_SM_CHEBY) {                 // t = x + P x_c where the last of the k passes lands in x
         double* t = cheb_place(cheb_passes(V.cheb_degree, ChebEntry::ITERATE), xl, tmp);
         spmm<EP_AXPY>(w, V.P, W.lev[l + 1].x.p, t, EpArgs{nullptr, xl, nullptr, 1.0, nullptr, 0});
         cheb(w, V, ChebEntry::ITERATE, t, xl, bl, tmp, W.lev[l].d.p);
@@ -283,7 +370,7 @@ struct Multi {
     const int64_t brs = interleaved ? k : 1, bcs = interleaved ? 1 : ldb, xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx;
     // only the fused path is captured as a whole; the column loop replays the single-vector graphs of run_cycle
     if (!fz || !(h.use_graph && graph_ok) || h.stream == nullptr) { apply_body(k, B, brs, bcs, X, xrs, xcs, graph_ok, false); return; }
-    const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx, extended() ? 1 : 0};
+    const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx, rule()};
     if (!st.graphs.has(key)) {
       int32_t wd[MULTI_MAX];
       const int ng = multi_groups(k, true, wd);
@@ -328,6 +415,44 @@ struct Multi {
       if (!y_inplace) { fit(W.out, h.lev[0].len() * w); yw = W.out.p; }
       spmm<EP_MULT>(w, V.A, xw, yw, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0});      // (no sm_pass: the fp64 image)
       if (!y_inplace) unpack(n, w, W.out.p, Y, yrs, ycs, c0);
+    }
+  }
+
+  // one plain smoother step per column on a level (amgx_smooth per column).  Groups of 4 and 2 run the multi-vector sweeps where
+  // the call carries AMGX_MULTI_FUSE_GS and the level has them (Handle::multi_sweep_ok, caller's numbering); everything else is a
+  // column loop over level_smooth.  x_zero is the caller's promise of the flag contract; like the single-vector Gauss-Seidel
+  // step, the sweeps do not act on it (they read x), so the columns of a group and the single columns see the same operation.
+  void smooth(int level, int dir, int k, double* X, int64_t ldx, const double* B, int64_t ldb, bool interleaved, bool x_zero) {
+    DevLevel& V = h.lev[level];
+    const int64_t n = V.len();
+    if (V.n != V.ncols) throw Err("amgx_smooth_multi: rank-partitioned levels are not supported");
+    const int64_t xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx, brs = interleaved ? k : 1, bcs = interleaved ? 1 : ldb;
+    const bool nv = gs_flag && !h.permuted(level) && h.multi_sweep_ok(V) && V.n > 0;
+    int32_t wd[MULTI_MAX];
+    const int ng = multi_groups(k, nv, wd);
+    int c0 = 0;
+    for (int g = 0; g < ng; c0 += wd[g], ++g) {
+      const int w = wd[g];
+      if (w == 1) {                                            // amgx_smooth with device pointers
+        double* x1 = X + c0 * xcs;
+        const double* b1 = B + c0 * bcs;
+        if (xrs != 1) { fit(st.col_out, std::max(n, h.lev[0].len())); pack(n, 1, X, xrs, xcs, c0, st.col_out.p); x1 = st.col_out.p; }
+        if (brs != 1) { fit(st.col_in, std::max(n, h.lev[0].len())); pack(n, 1, B, brs, bcs, c0, st.col_in.p); b1 = st.col_in.p; }
+        fit(st.sm_r, n);
+        Staged sg(h, AMGX_DEVICE_PTR);
+        double* dx = sg.inout(0, x1, n, true, level);
+        const double* db = sg.in(1, b1, n, level);
+        double* dr = sg.inout(2, st.sm_r.p, n, false, level);
+        h.level_smooth(V, dir, dx, db, dr, false, false, x_zero);
+        sg.out(0, x1, n, level);
+        if (xrs != 1) unpack(n, 1, st.col_out.p, X, xrs, xcs, c0);
+        continue;
+      }
+      fit(st.sm_x, n * MULTI_MAX / 2); fit(st.sm_b, n * MULTI_MAX / 2); fit(st.sm_t, n * MULTI_MAX / 2);
+      pack(n, w, X, xrs, xcs, c0, st.sm_x.p);
+      pack(n, w, B, brs, bcs, c0, st.sm_b.p);
+      const double* out = gs_sweep(w, V, dir, st.sm_x.p, st.sm_t.p, st.sm_b.p);
+      unpack(n, w, out, X, xrs, xcs, c0);
     }
   }
 
@@ -441,7 +566,7 @@ inline void multi_check(const char* fn, int k, const void* a, const void* b, int
 extern "C" {
 
 int amgx_apply_multi(amgx_handle hh, int k, const double* B, int64_t ldb, double* X, int64_t ldx, int b_status, int flags) {
-  if (k == 1 && hh && hh->h) return amgx_apply(hh, B, X, b_status, flags & ~(AMGX_MULTI_INTERLEAVED | AMGX_MULTI_FUSE));   // the single-vector path itself
+  if (k == 1 && hh && hh->h) return amgx_apply(hh, B, X, b_status, flags & ~(AMGX_MULTI_INTERLEAVED | AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS));   // the single-vector path itself
   (void)b_status;   // single GPU: DISTRIBUTED == CUMULATED, as in amgx_apply
   return guard(hh, [&](amgx::Handle& h) {
     const int64_t n = h.lev[0].len();
@@ -473,6 +598,23 @@ int amgx_matvec_multi(amgx_handle hh, int level, int k, const double* X, int64_t
   });
 }
 
+int amgx_smooth_multi(amgx_handle hh, int level, int dir, int k, double* X, int64_t ldx, const double* B, int64_t ldb, int x_zero, int flags) {
+  return guard(hh, [&](amgx::Handle& h) {
+    if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_smooth_multi: level out of range");
+    if (!h.lev[level].dinv.p) throw amgx::Err("amgx_smooth_multi: level has no smoother");
+    const int64_t n = h.lev[level].len();
+    const bool il = flags & AMGX_MULTI_INTERLEAVED;
+    amgx::multi_check("amgx_smooth_multi", k, X, B, ldx, ldb, n, n, il);
+    amgx::Multi M(h, flags);
+    amgx::MultiStaged sg(h, flags);
+    const int64_t lx = (sg.host && !il) ? n : ldx, lb = (sg.host && !il) ? n : ldb;
+    const double* dB = sg.in(M.st.stage_b, B, n, k, il, ldb);
+    double* dX = const_cast<double*>(sg.in(M.st.stage_x, X, n, k, il, ldx));
+    M.smooth(level, dir, k, dX, lx, dB, lb, il, x_zero != 0);
+    sg.out(M.st.stage_x, X, n, k, il, ldx);
+  });
+}
+
 int amgx_pcg_multi(amgx_handle hh, int k, const double* B, int64_t ldb, double* X, int64_t ldx, double tol, int maxit, int use_precond, int flags,
                    double* errs, int32_t* iters) {
   return guard(hh, [&](amgx::Handle& h) {
@@ -496,9 +638,9 @@ int amgx_multi_info(amgx_handle hh, int k, int32_t* fused, int32_t* n_groups, in
 
 int amgx_multi_plan(amgx_handle hh, int k, int flags, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes) {
   return guard(hh, [&](amgx::Handle& h) {
-    const std::string fn = (flags & AMGX_MULTI_FUSE) ? "amgx_multi_plan" : "amgx_multi_info";
+    const std::string fn = (flags & (AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS)) ? "amgx_multi_plan" : "amgx_multi_info";
     if (k < 1 || k > amgx::MULTI_MAX) throw amgx::Err(fn + ": k must be 1 .. " + std::to_string(amgx::MULTI_MAX) + " (got " + std::to_string(k) + ")");
-    amgx::Multi M(h, flags & AMGX_MULTI_FUSE);
+    amgx::Multi M(h, flags & (AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS));
     int32_t wd[amgx::MULTI_MAX];
     const int ng = amgx::multi_groups(k, M.fz, wd);
     if (fused) *fused = M.fz ? 1 : 0;
@@ -512,7 +654,7 @@ const char* amgx_multi_note(amgx_handle hh, int flags) {
   thread_local std::string note;
   note.clear();
   if (guard(hh, [&](amgx::Handle& h) {
-        amgx::Multi M(h, flags & AMGX_MULTI_FUSE);
+        amgx::Multi M(h, flags & (AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS));
         if (!M.fz) note = M.note();
       }))
     note = amgx_last_error(hh);

@@ -1,4 +1,4 @@
-// Kernels of the multi-vector apply path (DESIGN.md 5.10, 5.13): NV interleaved vectors, entry (row i, column j) at i*NV + j.
+// Kernels of the multi-vector apply path (DESIGN.md 5.10, 5.13, 5.15): NV interleaved vectors, entry (row i, column j) at i*NV + j.
 // Included ahead of the handle so that Handle::product<NV, EP> (amgx.hip) can name them; the host side is multi.hpp.
 //
 // The kernels keep the order of additions of their single-vector counterparts per column (pair accumulators, odd trailing
@@ -57,9 +57,16 @@ __device__ __forceinline__ void store_multi(int64_t row, const double (&acc)[NV]
     const double d = ep.dinv[row];
 #pragma unroll
     for (int j = 0; j < NV; ++j) out[j] = yin[j] + ep.s * (d * (b[j] - acc[j]));
+  } else if constexpr (EP == EP_CRES) {
+    // y = c .* v - A x (c = ep.dinv per row, v = ep.b interleaved): the residual right after a block-hybrid sweep from zero
+    double b[NV];
+    ldv<NV>(ep.b + row * NV, b);
+    const double d = ep.dinv[row];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) out[j] = d * b[j] - acc[j];
   } else {
     // store_scalar<EP_CHEB> per column: d, y2 and yin interleaved like y
-    static_assert(EP == EP_CHEB, "multi-vector epilogues: MULT, RES, AXPY, JAC, CHEB");
+    static_assert(EP == EP_CHEB, "multi-vector epilogues: MULT, RES, AXPY, JAC, CRES, CHEB");
     double b[NV], yin[NV], dd[NV], dn[NV];
     ldv<NV>(ep.b + row * NV, b);
     ldv<NV>(ep.yin + row * NV, yin);
@@ -527,8 +534,242 @@ __global__ __launch_bounds__(BLOCK) void dense_gemm_nv_kernel(int n, int ld, con
   if (lane == 0) stv<NV>(y + (int64_t)row * NV, acc);
 }
 
+// ---- Gauss-Seidel sweeps on NV interleaved vectors (AMGX_MULTI_FUSE_GS) ----------------------------------------
+// gsb_sweep_kernel (kernels.hpp) for NV vectors: the same image, the same slot -> row map, the same colour phases and barriers; the
+// matrix values and the decoded columns of a lane are loaded ONCE and serve all NV columns.  Per column the arithmetic is that of
+// the single-vector kernel -- acc_off over the lane's entries j ascending, the __shfl_xor tree over the G lanes of a row, colours in
+// the same order, x_k + dinv_k * (b_k - acc_off - acc) -- and no operation mixes two columns.
+//   * the block's x lives in LDS interleaved like the vectors (B * NV doubles: 32 KB at B = 1024, NV = 4); b and dinv of a row are
+//     read by the row's writer lane straight from memory (NV contiguous doubles), so the LDS need stays below the 64 KB a launch can
+//     have for every (B, NV) and the plan has nothing to refuse;
+//   * the off-block gathers are consumed in batches of GB entries (GB * NV doubles in flight per lane): all 2 * WP + 1 at once would
+//     be 17 * NV doubles, beyond the register budget of a 1024-lane workgroup;
+//   * plain images only (global columns): the local-window and mid-width forms of the single-vector sweep are launch choices over
+//     the same slot order, so their results are the same bits.
+// The colour loop holds a workgroup barrier: no lane returns before it, n_colors is uniform.
+template <int TH, int G, bool FROM_ZERO, int WP, int NV>
+__global__ __launch_bounds__(TH) void gsb_sweep_nv_kernel(int64_t n_rows, SellMat M, GsbArgs a, const double* __restrict__ xin, double* xout) {
+  constexpr int B = TH / G;                  // rows per block
+  constexpr int RPS = WAVE / G;              // rows per slice
+  constexpr int NE = 2 * WP + 1;             // entries a lane holds
+  constexpr int XQ = (B * NV + TH - 1) / TH; // entries of the block's x per thread
+  constexpr int GB = NV <= 2 ? 4 : 2;        // off-block entries gathered per batch
+  __shared__ __attribute__((aligned(16))) double xs[B * NV];
+  const int blk = blockIdx.x;
+  const int64_t r0 = (int64_t)blk * B;
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+  const int s = __builtin_amdgcn_readfirstlane(blk * (TH / WAVE) + (tid >> 6));
+  // ---- phase 1: every load that depends on nothing
+  const int64_t x0 = r0 * NV;
+  const int64_t xend = (n_rows - r0 < B ? n_rows - r0 : (int64_t)B) * NV;       // entries of the block that exist (last block: partial)
+  double x_own[XQ];
+#pragma unroll
+  for (int q = 0; q < XQ; ++q) {
+    const int k = tid + q * TH;
+    x_own[q] = 0.0;
+    if (!FROM_ZERO) { if (k < xend) x_own[q] = xin[x0 + k]; }
+  }
+  const int slot = s * RPS + lane / G;
+  const int row = a.rowid[slot];
+  const int col_raw = (int)a.slotcolor[slot];
+  const int64_t sp0 = M.slice_ptr[s];
+  const int64_t base = sp0 & ~(int64_t)63;
+  const int w = (int)(((M.slice_ptr[s + 1] & ~(int64_t)63) - base) >> 6);
+  const int np = w >> 1;
+  const bool c16 = sp0 & 1;
+  const double* __restrict__ vb = M.val + base;
+  const int32_t* __restrict__ cb = M.cbase + (base >> 6);
+  double v[NE];
+  int cl[NE];
+  uint32_t ra[WP], rb[WP];
+#pragma unroll
+  for (int p = 0; p < WP; ++p) {
+    v[2 * p] = 0.0; v[2 * p + 1] = 0.0; ra[p] = 0; rb[p] = 0;
+    if (p < np) {                                            // wave-uniform
+      v[2 * p] = ld_nt(vb + (p * WAVE + lane) * 2);
+      v[2 * p + 1] = ld_nt(vb + (p * WAVE + lane) * 2 + 1);
+      if (c16) ra[p] = ld_nt(reinterpret_cast<const uint32_t*>(M.col16 + base) + p * WAVE + lane);
+      else {
+        ra[p] = (uint32_t)ld_nt(M.col32 + base + (p * WAVE + lane) * 2);
+        rb[p] = (uint32_t)ld_nt(M.col32 + base + (p * WAVE + lane) * 2 + 1);
+      }
+    }
+  }
+  int cbv[NE];                           // column bases of the slice (the array has slack at its end, see gsb_sweep_kernel)
+#pragma unroll
+  for (int j = 0; j < NE; ++j) cbv[j] = 0;
+  if (c16) {
+#pragma unroll
+    for (int j = 0; j < NE; ++j) cbv[j] = cb[j];
+  }
+  uint32_t rt = 0;
+  v[2 * WP] = 0.0;
+  if (w & 1) {
+    const int64_t o = (int64_t)(w - 1) * WAVE + lane;
+    v[2 * WP] = ld_nt(vb + o);
+    rt = c16 ? (uint32_t)ld_nt(M.col16 + base + o) : (uint32_t)ld_nt(M.col32 + base + o);
+  }
+  // own-row operands of the writer lanes: NV contiguous doubles of b, one dinv
+  const int mycol = row >= 0 ? col_raw : 255;
+  const bool writer = mycol != 255 && (lane % G) == 0;
+  double bv[NV], dv = 0.0;
+#pragma unroll
+  for (int c = 0; c < NV; ++c) bv[c] = 0.0;
+  if (writer) { ldv<NV>(a.b + (int64_t)row * NV, bv); dv = a.dinv[row]; }
+  // ---- phase 2: the column decode
+#pragma unroll
+  for (int p = 0; p < WP; ++p) {
+    cl[2 * p] = (int)r0; cl[2 * p + 1] = (int)r0;
+    if (p < np) {
+      if (c16) { cl[2 * p] = cbv[2 * p] + (int)(ra[p] & 0xffffu); cl[2 * p + 1] = cbv[2 * p + 1] + (int)(ra[p] >> 16); }
+      else { cl[2 * p] = (int)ra[p]; cl[2 * p + 1] = (int)rb[p]; }
+    }
+  }
+  int cbt = 0;
+#pragma unroll
+  for (int j = 0; j < NE; j += 2) cbt = (w - 1 == j) ? cbv[j] : cbt;
+  cl[2 * WP] = (w & 1) ? (c16 ? cbt + (int)rt : (int)rt) : (int)r0;
+  // the block's x goes to LDS here: its loads were the first ones requested, and their registers are free before the gathers start
+#pragma unroll
+  for (int q = 0; q < XQ; ++q) {
+    const int k = tid + q * TH;
+    if (k < B * NV) xs[k] = x_own[q];
+  }
+  // ---- phase 3: off-block part (sweep-start values), GB entries per batch; in-block entries keep (value, LDS slot).  The empty
+  // asm after a batch pins the batch's sums before the next batch's loads: without it the compiler requests the gathers of all
+  // batches at once and keeps every product (222-232 VGPRs at NV = 4, spills in the 1024-lane workgroups)
+  double acc_off[NV];
+#pragma unroll
+  for (int c = 0; c < NV; ++c) acc_off[c] = 0.0;
+#pragma unroll
+  for (int j0 = 0; j0 < NE; j0 += GB) {
+    double xg[GB][NV];
+    bool inb[GB];
+#pragma unroll
+    for (int u = 0; u < GB; ++u) {
+      if (j0 + u < NE) {
+        const int j = j0 + u;
+        const int loc = cl[j] - (int)r0;
+        inb[u] = loc >= 0 && loc < B && cl[j] < n_rows;
+#pragma unroll
+        for (int c = 0; c < NV; ++c) xg[u][c] = 0.0;
+        // (an in-block entry reads the block's first row instead and drops the value: straight-line code, no branch per entry)
+        if (!FROM_ZERO) ldv<NV>(xin + (inb[u] ? x0 : (int64_t)cl[j] * NV), xg[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < GB; ++u) {
+      if (j0 + u < NE) {
+        const int j = j0 + u;
+        if (!FROM_ZERO) {
+#pragma unroll
+          for (int c = 0; c < NV; ++c) acc_off[c] += inb[u] ? 0.0 : v[j] * xg[u][c];
+        }
+        if (inb[u]) cl[j] -= (int)r0;
+        else { v[j] = 0.0; cl[j] = 0; }
+      }
+    }
+    if (!FROM_ZERO) {
+#pragma unroll
+      for (int c = 0; c < NV; ++c) asm volatile("" : "+v"(acc_off[c]) : : "memory");
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NV; ++c) {
+#pragma unroll
+    for (int o = G >> 1; o > 0; o >>= 1) acc_off[c] += __shfl_xor(acc_off[c], o, G);
+  }
+  const int own = row >= 0 ? row - (int)r0 : 0;
+  __syncthreads();                                           // xs is loaded
+  for (int q = 0; q < a.n_colors; ++q) {
+    const int c = a.backward ? a.n_colors - 1 - q : q;
+    if (__any(mycol == c)) {
+      double acc[NV];
+#pragma unroll
+      for (int cc = 0; cc < NV; ++cc) acc[cc] = 0.0;
+#pragma unroll
+      for (int j = 0; j < NE; ++j) {
+        double xv[NV];
+        ldv<NV>(xs + cl[j] * NV, xv);
+#pragma unroll
+        for (int cc = 0; cc < NV; ++cc) acc[cc] += v[j] * xv[cc];
+      }
+#pragma unroll
+      for (int cc = 0; cc < NV; ++cc) {
+#pragma unroll
+        for (int o = G >> 1; o > 0; o >>= 1) acc[cc] += __shfl_xor(acc[cc], o, G);
+      }
+      if (writer && mycol == c) {
+        double xo[NV];
+        ldv<NV>(xs + own * NV, xo);
+#pragma unroll
+        for (int cc = 0; cc < NV; ++cc) xo[cc] = xo[cc] + dv * (bv[cc] - acc_off[cc] - acc[cc]);
+        stv<NV>(xs + own * NV, xo);
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < XQ; ++q) {
+    const int k = tid + q * TH;
+    if (k < xend) xout[x0 + k] = xs[k];
+  }
+}
+
+// gs_color_kernel (kernels.hpp) with the row product widened to NV gathers: one colour per launch on the colour-major images `sell`
+// and `lower` of DevGS.  Padding rows (rowid < 0) are never written.
+template <int G, int NV>
+__global__ __launch_bounds__(BLOCK) void gs_color_nv_kernel(int slice_begin, int slice_end, SellMat M, const int32_t* __restrict__ rowid,
+                                                            const double* __restrict__ dinv, const double* __restrict__ b, double* x) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int s = __builtin_amdgcn_readfirstlane(slice_begin + blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6));
+  if (s >= slice_end) return;
+  const int row = rowid[(int64_t)s * (WAVE / G) + lane / G];
+  const bool writer = row >= 0 && (lane % G) == 0;
+  double dv = 0.0, bv[NV], xv[NV], acc[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) { bv[j] = 0.0; xv[j] = 0.0; acc[j] = 0.0; }
+  if (writer) { dv = dinv[row]; ldv<NV>(b + (int64_t)row * NV, bv); ldv<NV>(x + (int64_t)row * NV, xv); }
+  if (row >= 0) sell_row_dot_nv<NV>(M, s, lane, row, x, acc);
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+#pragma unroll
+    for (int o = G >> 1; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o, G);
+  }
+  if (writer) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) xv[j] = xv[j] + dv * (bv[j] - acc[j]);
+    stv<NV>(x + (int64_t)row * NV, xv);
+  }
+}
+
+// gs_upper_residual_kernel for NV vectors: r = -(U x) on the colour-major rows of the `upper` image, right after a forward sweep
+// from x = 0
+template <int G, int NV>
+__global__ __launch_bounds__(BLOCK) void gs_upper_residual_nv_kernel(int n_slices, SellMat M, const int32_t* __restrict__ rowid,
+                                                                     const double* __restrict__ x, double* __restrict__ r) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int s = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6));
+  if (s >= n_slices) return;
+  const int row = rowid[(int64_t)s * (WAVE / G) + lane / G];
+  double acc[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+  if (row >= 0) sell_row_dot_nv<NV>(M, s, lane, row, x, acc);
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+#pragma unroll
+    for (int o = G >> 1; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o, G);
+  }
+  if (row >= 0 && (lane % G) == 0) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] = -acc[j];
+    stv<NV>(r + (int64_t)row * NV, acc);
+  }
+}
+
 // ---- element-wise pieces on interleaved vectors (one thread per entry) -------------------------------------------------------
-// x = omega * Dinv * b, width 1 << sh      (diag_apply_kernel<1, false> per column)
+// x = omega * Dinv * b, width 1 << sh     (diag_apply_kernel<1, false> per column)
 __global__ __launch_bounds__(BLOCK) void multi_diag_kernel(int64_t len, int sh, const double* __restrict__ dinv, const double* __restrict__ b,
                                                            double* __restrict__ x, double omega) {
   const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;

@@ -256,7 +256,7 @@ class _BlockOp:
         from .device import check_fuse
         check_fuse(fuse)
         self.op = op
-        self.fuse = bool(fuse)
+        self.fuse = fuse if isinstance(fuse, str) else bool(fuse)
         self.columns = 0
         self.calls = 0
 
@@ -271,7 +271,7 @@ class _BlockOp:
         if hasattr(self.op, "apply_block"):
             self.op.apply_block(mv_in, mv_out)
             return mv_out
-        fuse = self.fuse if fuse is None else bool(fuse)
+        fuse = self.fuse if fuse is None else (fuse if isinstance(fuse, str) else bool(fuse))
         step = _lib.AMGX_MULTI_MAX
         for a in range(0, mv_in.k, step):
             b = min(a + step, mv_in.k)

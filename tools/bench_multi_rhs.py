@@ -2,7 +2,7 @@
 """k right-hand sides: k single-vector calls against one multi-vector call, same handle, same process, alternating.
 
     python tools/bench_multi_rhs.py [nv] [--k 1,2,4,8] [--rounds 5] [--reps 30] [--pcg-reps 30] [--out FILE] [--commit ID]
-                                    [--smoother jacobi|cheby] [--degree D] [--config cfg2|cfg3|cfg5]
+                                    [--smoother jacobi|cheby|gs] [--degree D] [--config cfg2|cfg3|cfg5]
 
 Builds the cfg-2 hierarchy as tools/ab_cycle.py does (fem.poisson_fast((nv,)*3), nv = 215, Jacobi) and times, with device vectors and
 graph replay on one stream, per k and per round
@@ -14,7 +14,10 @@ with (a): 1e-12 relative for the cycle, 1e-8 for the PCG solutions.  Needs a GPU
 
 --smoother cheby (with --degree) and --config cfg3 | cfg5 (elasticity without / with rotations, nv = 126, built as tools/bench_cheby.py
 does) select handles that are fused only under AMGX_MULTI_FUSE: (b), (b') and the multi-vector PCG then carry
-fuse=True, (a) stays k calls of amgx_apply / amgx_pcg on the same handle; the result goes to profiles/r14/."""
+fuse=True, (a) stays k calls of amgx_apply / amgx_pcg on the same handle; the result goes to profiles/r14/.
+
+--smoother gs (with --config cfg2): the library's default smoother, Gauss-Seidel in the block-hybrid form ("hgs" levels), which fuses
+only under AMGX_MULTI_FUSE_GS: (b), (b') and the multi-vector PCG carry fuse="gs"; the result goes to profiles/r21/."""
 import argparse
 import json
 import os
@@ -40,7 +43,7 @@ def _stats(ts):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("nv", nargs="?", type=int, default=None)
-    ap.add_argument("--smoother", default="jacobi", choices=["jacobi", "cheby"])
+    ap.add_argument("--smoother", default="jacobi", choices=["jacobi", "cheby", "gs"])
     ap.add_argument("--degree", type=int, default=2, help="Chebyshev degree")
     ap.add_argument("--config", default="cfg2", choices=["cfg2", "cfg3", "cfg5"])
     ap.add_argument("--k", default="1,2,4,8")
@@ -62,10 +65,16 @@ def main():
     from ngsamg_amd.krylov import NativeCGSolver
     nv = args.nv or (215 if args.config == "cfg2" else 126)
     ks = [int(v) for v in args.k.split(",")]
-    fuse = args.smoother != "jacobi" or args.config != "cfg2"      # handles that are fused only under AMGX_MULTI_FUSE
+    if args.smoother == "gs" and args.config != "cfg2":
+        sys.exit("bench_multi_rhs: --smoother gs is measured at --config cfg2 (Gauss-Seidel on block levels keeps the column loop)")
+    # handles that are fused only under AMGX_MULTI_FUSE (True) / AMGX_MULTI_FUSE_GS ("gs")
+    fuse = "gs" if args.smoother == "gs" else (args.smoother != "jacobi" or args.config != "cfg2")
     tag = f"{args.config}_{args.smoother}" + (str(args.degree) if args.smoother == "cheby" else "")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r14", f"multi_fuse_{tag}.json") if fuse else os.path.join(ROOT, "profiles", "r06", "multi_rhs.json")
+        if fuse == "gs":
+            args.out = os.path.join(ROOT, "profiles", "r21", f"multi_gs_{args.config}.json")
+        else:
+            args.out = os.path.join(ROOT, "profiles", "r14", f"multi_fuse_{tag}.json") if fuse else os.path.join(ROOT, "profiles", "r06", "multi_rhs.json")
     if args.config == "cfg2":
         p = fem.poisson_fast((nv, nv, nv))
         H = Hierarchy(Matrix(p.n, p.n, 1, 1, p.rowptr, p.col, p.val), p.free, p.coords, dim=3, energy=0, max_coarse_size=50)
@@ -74,7 +83,7 @@ def main():
         p = fem.elasticity_fast((nv, nv, nv), dirichlet="left", mu=1.0, lam=0.5, rotations=rot)
         H = Hierarchy(Matrix(p.n, p.n, p.bs, p.bs, p.rowptr, p.col, p.val), p.free, p.coords, dim=3, energy=1, max_coarse_size=50,
                       regularize_cmats=0 if rot else 1, spw=1)
-    kw = dict(sm_type="cheby", cheb_degree=args.degree) if args.smoother == "cheby" else dict(sm_type="jacobi")
+    kw = dict(sm_type="cheby", cheb_degree=args.degree) if args.smoother == "cheby" else dict(sm_type="hgs" if args.smoother == "gs" else "jacobi")
     free0, _ = torch.cuda.mem_get_info()
     dev = DeviceAMGMatrix(H, device=0, **kw)
     torch.cuda.synchronize()
@@ -102,10 +111,16 @@ def main():
         print("ms per multi cycle:", timed(lambda: dev.MultMulti(Bi, Xi, interleaved=True, fuse=fuse), args.reps))
         return
 
+    if fuse == "gs" and dev.multi_plan(4, fuse=fuse)["fused"] != 1:
+        sys.exit("bench_multi_rhs: the handle is not fused under AMGX_MULTI_FUSE_GS: " + dev.multi_plan(4, fuse=fuse)["note"])
     out = {"commit": args.commit or _commit(), "config": args.config, "smoother": args.smoother, "degree": args.degree if args.smoother == "cheby" else 0,
            "fuse": fuse, "nv": nv, "n": int(n), "levels": H.n_levels, "cycle_info": dev.cycle_info(),
            "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps, "pcg_reps": args.pcg_reps,
            "handle_bytes": int(free0 - free1), "k": {}}
+    if fuse == "gs":                                           # the forms under test and the matrix bytes of the byte model, per smoothed level
+        keys = ("gs_form", "gs_lanes", "gs_threads", "gs_block", "gs_colors", "gs_split", "gs_narrow", "gs_mid", "gs_lw", "gs_down")
+        out["levels_gs"] = [dict({key: dev.level_paths(l)[key] for key in keys}, rows=int(dev.sizes[l]),
+                                 A_stream_bytes=dev.matrix_info(l, "A")["stream_bytes"]) for l in range(H.n_levels - 1)]
     for k in ks:
         info = dev.multi_plan(k, fuse=fuse)
         B = rng.standard_normal((k, n)) * pfree
