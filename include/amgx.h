@@ -66,10 +66,14 @@ enum {
   AMGX_MULTI_FUSE = 64,       /* amgx_apply_multi / amgx_matvec_multi / amgx_pcg_multi: run fused column groups on every handle */
                               /* that qualifies under the EXTENDED rule (Chebyshev and block levels, see below); a handle that  */
                               /* does not qualify runs the column loop -- never an error.  Without it every call is as before   */
-  AMGX_MULTI_FUSE_GS = 128    /* the same calls, amgx_smooth_multi, amgx_multi_plan / amgx_multi_note: implies AMGX_MULTI_FUSE   */
+  AMGX_MULTI_FUSE_GS = 128,   /* the same calls, amgx_smooth_multi, amgx_multi_plan / amgx_multi_note: implies AMGX_MULTI_FUSE   */
                               /* and admits scalar Gauss-Seidel levels (block-hybrid or multicolour form, see below) as well; a  */
                               /* handle that does not qualify runs the column loop.  Without it every call is as before, calls   */
                               /* that carry AMGX_MULTI_FUSE alone included                                                       */
+  AMGX_MULTI_FUSE_GS_BLOCK = 256 /* accepted wherever AMGX_MULTI_FUSE_GS is; implies it and AMGX_MULTI_FUSE, and admits          */
+                              /* Gauss-Seidel on 2x2 / 3x3 / 6x6 levels (hybrid-block, block-coloured, multicolour forms, see     */
+                              /* below) as well; never an error: a handle that does not qualify runs the column loop.  Without   */
+                              /* it every call is as before, calls that carry the two flags above included                      */
 };
 
 typedef struct amgx_level_desc {
@@ -384,13 +388,21 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  * the block-hybrid or the scalar multicolour form.  Its sweeps keep, per column, the order of additions of the single-vector
  * sweep: a column of amgx_smooth_multi equals amgx_smooth bit for bit.  Gauss-Seidel on a block level and AMGX_SM_BGS keep the
  * column loop (amgx_multi_note names the smoother and the level).
+ * With AMGX_MULTI_FUSE_GS_BLOCK (opt-in per call; it implies the two flags above) an AMGX_SM_GS level may also have
+ * block size 2, 3 or 6, if it is square, in the caller's numbering, plain, and swept in the hybrid-block, the block-coloured, the
+ * multicolour BSELL or the multicolour row-list form (compact sweep blocks, gs_block_ids, included), and if its sweep block fits
+ * 64 KB of LDS on 4 vectors (2 * gs_block_rows * bs * 4 doubles + the row ids; every default block does, otherwise the note is
+ * "sweep block too large for the multi-vector sweep (level l)").  Per column the sweeps keep the order of additions of the
+ * single-vector kernels at the default AMGX_BSELL_XMODE: a column of amgx_smooth_multi equals amgx_smooth bit for bit there too.
+ * AMGX_SM_BGS, W / BS cycles, sm_steps > 1 / sm_symm (ProxySmoother) and rank-partitioned levels keep the column loop, each with a
+ * note of its own; so do groups wider than 4.
  *   amgx_smooth_multi: one plain smoother step per column, amgx_smooth(level, dir, x_j, b_j, res, 0, 0, x_zero) with a res of its
  *                      own; layout and pointers as in amgx_matvec_multi, X and B have the level's size (no ghost entries).  With
  *                      AMGX_MULTI_FUSE_GS on a Gauss-Seidel level that has the multi-vector sweep, groups of 4 and 2 columns run it
- *                      (whatever the rest of the handle looks like); otherwise, and for a single left-over column, a column loop
+ *                      (whatever the rest of the handle looks like; a square-block level needs AMGX_MULTI_FUSE_GS_BLOCK); otherwise, and for a single left-over column, a column loop
  *                      over the single-vector step.  x_zero is the caller's promise that X is zero, as in amgx_smooth.
- *   amgx_multi_plan  : the outputs of amgx_multi_info for a call that carries `flags` (only AMGX_MULTI_FUSE and AMGX_MULTI_FUSE_GS
- *                      are looked at; flags = 0 answers exactly what amgx_multi_info answers); work_bytes counts one more vector per
+ *   amgx_multi_plan  : the outputs of amgx_multi_info for a call that carries `flags` (only AMGX_MULTI_FUSE, AMGX_MULTI_FUSE_GS and
+ *                      AMGX_MULTI_FUSE_GS_BLOCK are looked at; flags = 0 answers exactly what amgx_multi_info answers); work_bytes counts one more vector per
  *                      Chebyshev level
  *   amgx_multi_note  : the first reason why the handle is not fused under `flags` (it names the level), "" when it is fused.  The
  *                      string lives until the calling thread's next amgx_multi_note */

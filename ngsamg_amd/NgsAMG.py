@@ -248,7 +248,8 @@ class AMGMatrix:
         resident on the GPU: ngsamg_amd.eigen.lobpcg (LOBPCG; history=False: PINVIT) on device multi-vectors.  mass: an object
         with apply_block(mv_in, mv_out) (None: the identity); free: 0/1 mask of the scalar dofs (None: the free dofs of the
         hierarchy); X0: a (num, n) array or CUDA tensor (None: random columns from seed).  Returns (lams, X, info), X a
-        DeviceMultiVector (X.data: the (num, n) tensor)."""
+        DeviceMultiVector (X.data: the (num, n) tensor).  fuse: as in MultMulti; "gs_block" fuses the default Gauss-Seidel smoother
+        of an elasticity hierarchy (AMGX_MULTI_FUSE_GS_BLOCK)."""
         import torch
         from .eigen import lobpcg
         from .multivector import DeviceMultiVector, MatVecMulti, MultMulti

@@ -1890,6 +1890,101 @@ struct Handle {
     else sweep(Int<0>{}, OFF, nullptr, blk0, blk1 - blk0, xin);
   }
 
+  // ---- Gauss-Seidel sweeps of square-block levels on NV = 2, 4 interleaved vectors (AMGX_MULTI_FUSE_GS_BLOCK, DESIGN.md 5.16;
+  // kernels in multi_kernels.hpp).  Whole levels only.  Which block forms have them is asked HERE and nowhere else
+  // (Multi::decide_gs_block, amgx_smooth_multi); multi_sweep_ok above keeps the answer of AMGX_MULTI_FUSE_GS.
+  bool multi_block_sweep_ok(const DevLevel& L) const {
+    if (L.sm_type != AMGX_SM_GS || (L.bs != 2 && L.bs != 3 && L.bs != 6) || L.n != L.ncols || !L.paths.plain) return false;
+    switch (L.paths.sweep) {
+      case SWEEP_BGSB: case SWEEP_BGSB_BC: case SWEEP_MC_BSELL: case SWEEP_MC_ROWLIST: return true;
+      default: return false;
+    }
+  }
+  // dynamic LDS of bgsb_sweep_nv_kernel: x and b' of a sweep block on nv interleaved vectors, and its row ids
+  static size_t multi_block_sweep_lds(const DevLevel& L, int nv) {
+    return (size_t)2 * L.bgsb.BB * L.bs * nv * sizeof(double) + (size_t)L.bgsb.BB * sizeof(int);
+  }
+  // ... which has to fit the 64 KB a launch gets without asking at the widest group (only AMGX_BGSB_ROWS makes blocks that do not)
+  bool multi_block_sweep_fits(const DevLevel& L) const { return !L.paths.bgsb() || multi_block_sweep_lds(L, 4) <= (size_t)64 * 1024; }
+  // bgsb_sweep on NV vectors, whole level: the hybrid form out of place (xin == nullptr: from zero), the block-coloured form in
+  // place, one launch per block colour (xin == nullptr: from zero over `offlo`, which needs the split)
+  template <int NV>
+  void bgsb_sweep_nv(const DevLevel& L, int dir, const double* xin, double* xout, const double* b) {
+    const DevBGSB& g = L.bgsb;
+    if (!L.paths.bgsb()) throw Err("multi-vector Gauss-Seidel: the level has no block-hybrid form");
+    const size_t lds = multi_block_sweep_lds(L, NV);
+    if (lds > (size_t)64 * 1024) throw Err("multi-vector Gauss-Seidel: sweep block too large");
+    const BSellMat IN = dir == 0 ? g.in.bsell.view(0) : g.upin.bsell.view(0), OTH = dir == 0 ? g.upin.bsell.view(0) : g.in.bsell.view(0);
+    auto sweep = [&](auto MODE, const BSellMat& OFF, const int32_t* list, int b0, int nb, const double* x0) {
+      auto run = [&](auto BS) {
+        launch(bgsb_sweep_nv_kernel<BS(), MODE(), NV>, nb, BLOCK, lds, stream, g.BB, b0, list, g.blk_ptr.p, g.blk_rows.p, OFF, g.off_ptr.p, IN, OTH,
+               g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, x0, xout);
+      };
+      if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("block-hybrid Gauss-Seidel: unsupported block size");
+    };
+    if (g.bc) {
+      if (xin != nullptr && xin != xout) throw Err("block-coloured Gauss-Seidel sweeps work in place");
+      const bool fz = xin == nullptr;
+      if (fz && dir != 0) throw Err("block-coloured Gauss-Seidel: the sweep from zero is a forward sweep");
+      if (fz && !L.paths.zero_split) throw Err("block-coloured Gauss-Seidel from zero needs the split images (zero x and sweep in place instead)");
+      const BSellMat OFFA = g.off.bsell.view(0), OFFL = g.offlo.bsell.view(0);
+      for (int q = 0; q < g.n_bcolors; ++q) {
+        const int c = dir ? g.n_bcolors - 1 - q : q;
+        const int b0 = g.bc_ptr[c], nb = g.bc_ptr[c + 1] - b0;
+        if (nb <= 0) continue;
+        if (!fz) sweep(Int<0>{}, OFFA, g.blk_list.p, b0, nb, xout);
+        else if (q == 0) sweep(Int<1>{}, OFFL, g.blk_list.p, b0, nb, nullptr);
+        else sweep(Int<2>{}, OFFL, g.blk_list.p, b0, nb, xout);
+      }
+      return;
+    }
+    if (g.n_blocks <= 0) return;
+    if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
+    const BSellMat OFF = g.off.bsell.view(0);
+    if (xin == nullptr) sweep(Int<1>{}, OFF, nullptr, 0, g.n_blocks, xin);
+    else sweep(Int<0>{}, OFF, nullptr, 0, g.n_blocks, xin);
+  }
+  // gs_sweep on NV vectors of a block level in a multicolour form: one launch per colour, in place (the kernel choices of gs_sweep)
+  template <int NV>
+  void bgs_mc_sweep_nv(const DevLevel& L, int dir, double* x, const double* b, bool lower_only = false) {
+    const DevGS& g = L.gs;
+    if (L.paths.sweep != SWEEP_MC_BSELL && L.paths.sweep != SWEEP_MC_ROWLIST) throw Err("multi-vector Gauss-Seidel: the level has no block multicolour form");
+    for (int q = 0; q < g.n_colors; ++q) {
+      const int c = dir == 0 ? q : g.n_colors - 1 - q;
+      if (L.paths.sweep == SWEEP_MC_BSELL) {
+        const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
+        if (s1 == s0) continue;
+        const int grid = (s1 - s0 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+        const BSellMat BM = (lower_only && g.bsplit) ? g.blower.bsell.view(0) : g.bcopy.bsell.view(0);
+        auto run = [&](auto BS) { launch(bgs_bsell_color_nv_kernel<BS(), NV>, grid, BLOCK, 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x); };
+        if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("multi-vector Gauss-Seidel: unsupported block size");
+      } else {
+        const int r0 = g.color_row_ptr[c], r1 = g.color_row_ptr[c + 1];
+        if (r1 == r0) continue;
+        const double avg = L.A.n_rows ? (double)L.A.nnz / (double)L.A.n_rows : 0.0;
+        const int W = bgs_rowlist_w(avg, r1 - r0);
+        const int rpw = WAVE / (L.bs * W);
+        const int64_t waves = ((int64_t)(r1 - r0) + rpw - 1) / rpw;
+        const int grid = (int)std::max<int64_t>(1, (waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+        auto run = [&](auto BS) {
+          auto run_w = [&](auto WW) { launch(bgs_color_nv_kernel<BS(), WW(), NV>, grid, BLOCK, 0, stream, r0, r1, g.rowlist.p, L.A.rowptr.p, L.A.col.p, L.A.val.p, L.dinv.p, b, x); };
+          if (!dispatch<8, 4, 2>(W, run_w)) run_w(Int<1>{});
+        };
+        if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("multi-vector Gauss-Seidel: unsupported block size");
+      }
+    }
+  }
+  // r = -(U x) on NV vectors right after the multicolour sweep from zero over `blower` (residual_after_zero, SWEEP_MC_BSELL)
+  template <int NV>
+  void bgs_upper_residual_nv(const DevLevel& L, const double* x, double* r) {
+    const DevGS& g = L.gs;
+    const int ns = g.bupper.n_slices;
+    if (ns <= 0) return;
+    const int grid = (ns + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    auto run = [&](auto BS) { launch(bgs_bsell_upper_residual_nv_kernel<BS(), NV>, grid, BLOCK, 0, stream, ns, g.bupper.bsell.view(0), g.rowid.p, x, r); };
+    if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("multi-vector Gauss-Seidel: unsupported block size");
+  }
+
   // one block Gauss-Seidel sweep: colours of the block graph ascending (forward) or descending (backward)
   void bgs_sweep(const DevLevel& L, int dir, double* x, const double* b, int cbeg = 0, int cend = -1) {
     const DevBGS& g = L.bgs;

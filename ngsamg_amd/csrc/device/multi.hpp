@@ -9,7 +9,9 @@
 // single-vector path -- unless the call carries AMGX_MULTI_FUSE: then handles whose smoothed levels are plain
 // Jacobi or Chebyshev levels with block size 1, 2, 3 or 6 run fused groups too (Multi::decide_extended).  AMGX_MULTI_FUSE_GS
 //  implies that flag and admits scalar Gauss-Seidel levels in the block-hybrid or the multicolour form as well
-// (Multi::decide_gs); their sweeps on NV vectors are Handle::gsb_sweep_nv / gs_sweep_nv.
+// (Multi::decide_gs); their sweeps on NV vectors are Handle::gsb_sweep_nv / gs_sweep_nv.  AMGX_MULTI_FUSE_GS_BLOCK
+// implies both and admits Gauss-Seidel on 2x2 / 3x3 / 6x6 levels in the hybrid-block, block-coloured and the two block multicolour
+// forms (Multi::decide_gs_block; Handle::bgsb_sweep_nv / bgs_mc_sweep_nv).
 //
 // This file is the host side.  The kernels are in multi_kernels.hpp; which of them serves a matrix is decided in ONE place,
 // Handle::product<NV, EP> (amgx.hip), next to the value lists that Handle::multi_*_ok ask; the Chebyshev recurrence is
@@ -43,6 +45,8 @@ struct MultiState {
   std::string why_x;
   int fused_g = -1;                     // ... and under AMGX_MULTI_FUSE_GS (the extended rule plus scalar Gauss-Seidel levels)
   std::string why_g;
+  int fused_b = -1;                     // ... and under AMGX_MULTI_FUSE_GS_BLOCK (that rule plus Gauss-Seidel on square-block levels)
+  std::string why_b;
   MultiWork work[MULTI_MAX + 1];        // by width (2, 4)
   DevBuf<double> col_in, col_out;       // one contiguous column (single-vector path behind an interleaved argument)
   DevBuf<double> stage_b, stage_x;      // host-pointer calls
@@ -50,7 +54,7 @@ struct MultiState {
   DevBuf<double> kr[5];                 // amgx_pcg_multi: b, x, d, w, s (interleaved, width k)
   DevBuf<double> kr_sc, kr_partial;
   DevBuf<int32_t> kr_active;
-  using Key = std::tuple<const double*, double*, int, int, int64_t, int64_t, int>;   // b, x, k, layout, ldb, ldx, rule in force (0, 1, 2)
+  using Key = std::tuple<const double*, double*, int, int, int64_t, int64_t, int>;   // b, x, k, layout, ldb, ldx, rule in force (0 .. 3)
   GraphCache<Key> graphs;
 };
 
@@ -60,24 +64,29 @@ void multi_free(MultiState* s) { delete s; }
 struct Multi {
   Handle& h;
   MultiState& st;
+  static constexpr int ALL_FLAGS = AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_GS_BLOCK;
+  const bool block_flag;                // the call carries AMGX_MULTI_FUSE_GS_BLOCK (which implies the two flags below)
   const bool gs_flag;                   // the call carries AMGX_MULTI_FUSE_GS (which implies AMGX_MULTI_FUSE)
   const bool fuse_flag;                 // the call carries AMGX_MULTI_FUSE
   const bool fz;                        // this call runs fused groups
   explicit Multi(Handle& hh, int flags = 0)
-      : h(hh), st(state(hh)), gs_flag(flags & AMGX_MULTI_FUSE_GS), fuse_flag(flags & (AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS)),
-        fz(st.fused == 1 || (fuse_flag && st.fused_x == 1) || (gs_flag && st.fused_g == 1)) {}
+      : h(hh), st(state(hh)), block_flag(flags & AMGX_MULTI_FUSE_GS_BLOCK), gs_flag(flags & (AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_GS_BLOCK)),
+        fuse_flag(flags & ALL_FLAGS),
+        fz(st.fused == 1 || (fuse_flag && st.fused_x == 1) || (gs_flag && st.fused_g == 1) || (block_flag && st.fused_b == 1)) {}
   // the rule in force: the flags decide the path only where the narrower rule does not hold (a scalar Jacobi handle: one path,
-  // one graph; a handle without Gauss-Seidel levels runs the same cycle under both flags)
+  // one graph; a handle without Gauss-Seidel levels runs the same cycle under all flags, one without block Gauss-Seidel levels
+  // the same cycle under the two Gauss-Seidel flags)
   int rule() const {
     if (st.fused == 1 || !fuse_flag) return 0;
+    if (block_flag && st.fused_g != 1 && st.fused_x != 1) return 3;
     return gs_flag && st.fused_x != 1 ? 2 : 1;
   }
-  const std::string& note() const { const int r = rule(); return r == 2 ? st.why_g : r == 1 ? st.why_x : st.why; }
+  const std::string& note() const { const int r = rule(); return r == 3 ? st.why_b : r == 2 ? st.why_g : r == 1 ? st.why_x : st.why; }
 
   static MultiState& state(Handle& h) {
     if (!h.multi) h.multi = new MultiState;
     MultiState& s = *h.multi;
-    if (s.fused < 0) { decide(h, s); decide_extended(h, s); decide_gs(h, s); }
+    if (s.fused < 0) { decide(h, s); decide_extended(h, s); decide_gs(h, s); decide_gs_block(h, s); }
     return s;
   }
   // all-or-nothing rule of the fused path: V-cycle; every smoothed level scalar, plain Jacobi, square, in the caller's numbering
@@ -154,6 +163,38 @@ struct Multi {
     s.fused_g = 1;
   }
 
+  // the rule of AMGX_MULTI_FUSE_GS_BLOCK: the rule above, and an AMGX_SM_GS level may also have block size 2, 3 or 6 where
+  // Handle::multi_block_sweep_ok holds (square, plain; hybrid-block, block-coloured, multicolour BSELL or row-list form) and its
+  // sweep block fits the LDS of the widest group.  A superset of decide_gs(): fused_g == 1 implies fused_b == 1.  AMGX_SM_BGS, W / BS
+  // cycles, sm_steps > 1 / sm_symm (ProxySmoother) and rank-partitioned levels keep the column loop.
+  static void decide_gs_block(Handle& h, MultiState& s) {
+    s.fused_b = 0;
+    const int L = h.n_levels();
+    if (h.cycle != AMGX_CYCLE_V) { s.why_b = "cycle is not V"; return; }
+    for (int l = 0; l < L; ++l) {
+      const DevLevel& V = h.lev[l];
+      const std::string at = " (level " + std::to_string(l) + ")";
+      const bool smoothed = l + 1 < L;
+      const bool gs = smoothed && V.sm_type == AMGX_SM_GS;
+      if (smoothed) {
+        if (V.sm_type == AMGX_SM_BGS) { s.why_b = "block Gauss-Seidel (bgs) smoother" + at; return; }
+        if (!gs && V.sm_type != AMGX_SM_JACOBI && V.sm_type != AMGX_SM_CHEBY) { s.why_b = "smoother is not Jacobi, Chebyshev or Gauss-Seidel" + at; return; }
+        if (!h.plain(V)) { s.why_b = "sm_steps > 1 or sm_symm" + at; return; }
+        if (V.sm_type == AMGX_SM_CHEBY && (V.cheb_degree < 1 || V.cheb_degree > 8)) { s.why_b = "Chebyshev level without coefficients" + at; return; }
+      }
+      if (V.bs != 1 && V.bs != 2 && V.bs != 3 && V.bs != 6) { s.why_b = "block size is not 1, 2, 3 or 6" + at; return; }
+      if (V.n != V.ncols) { s.why_b = "ghost columns" + at; return; }
+      if (h.permuted(l)) { s.why_b = "renumbered level" + at; return; }
+      if (gs && V.n > 0) {
+        if (!(V.bs == 1 ? h.multi_sweep_ok(V) : h.multi_block_sweep_ok(V))) { s.why_b = "Gauss-Seidel sweep form without a multi-vector kernel" + at; return; }
+        if (V.bs != 1 && !h.multi_block_sweep_fits(V)) { s.why_b = "sweep block too large for the multi-vector sweep" + at; return; }
+      }
+      if (V.n > 0 && (!Handle::multi_level_ok(V.A) || V.A.br != V.bs)) { s.why_b = "level matrix format" + at; return; }
+      if (smoothed && V.n > 0 && (!Handle::multi_transfer_ok(V.P) || !Handle::multi_transfer_ok(V.PT))) { s.why_b = "transfer format" + at; return; }
+    }
+    s.fused_b = 1;
+  }
+
   // first level that the multi cycle hands to ONE dense product (collapsed operator or the coarsest level's inverse)
   // (0: the whole cycle is the dense operator, no level work vectors)
   int top() const { return h.dense_level >= 0 ? h.dense_level : h.n_levels() - 1; }
@@ -225,7 +266,7 @@ struct Multi {
     launch(multi_unpack_kernel, Handle::grid_for(n * w), BLOCK, 0, h.stream, n, w, src, dst, rs, cs, c0);
   }
 
-  // Gauss-Seidel on w interleaved vectors of a level that Handle::multi_sweep_ok admits
+  // Gauss-Seidel on w interleaved vectors of a level that Handle::multi_sweep_ok or multi_block_sweep_ok admits
   template <class F>
   static void width(int w, F&& run) {
     if (!dispatch<2, 4>(w, run)) throw Err("multi-vector Gauss-Seidel: width must be 2 or 4");
@@ -233,20 +274,39 @@ struct Multi {
   // one sweep on the iterate `cur`; returns the buffer that holds the result (Handle::sweep: `oth` for the out-of-place hybrid form)
   double* gs_sweep(int w, const DevLevel& V, int dir, double* cur, double* oth, const double* b) {
     if (V.n == 0) return cur;
-    if (V.paths.sweep == SWEEP_GSB) { width(w, [&](auto W) { h.gsb_sweep_nv<W()>(V, dir, cur, oth, b); }); return oth; }
-    width(w, [&](auto W) { h.gs_sweep_nv<W()>(V, dir, cur, b); });
-    return cur;
+    switch (V.paths.sweep) {
+      case SWEEP_GSB: width(w, [&](auto W) { h.gsb_sweep_nv<W()>(V, dir, cur, oth, b); }); return oth;
+      case SWEEP_BGSB: width(w, [&](auto W) { h.bgsb_sweep_nv<W()>(V, dir, cur, oth, b); }); return oth;
+      case SWEEP_BGSB_BC: width(w, [&](auto W) { h.bgsb_sweep_nv<W()>(V, dir, cur, cur, b); }); return cur;
+      case SWEEP_MC_BSELL: case SWEEP_MC_ROWLIST: width(w, [&](auto W) { h.bgs_mc_sweep_nv<W()>(V, dir, cur, b); }); return cur;
+      default: width(w, [&](auto W) { h.gs_sweep_nv<W()>(V, dir, cur, b); }); return cur;
+    }
   }
   // the residual identity of the level's split images can be used on w vectors (Handle::residual_after_zero)
   static bool gs_split(const DevLevel& V) {
     if (!V.paths.zero_split) return false;
-    return V.paths.sweep == SWEEP_MC || Handle::multi_scalar_ok(V.gsb.rest);
+    if (V.paths.bgsb()) return Handle::multi_level_ok(V.bgsb.rest) && V.bgsb.rest.br == V.bs;
+    return V.paths.sweep == SWEEP_MC || V.paths.sweep == SWEEP_MC_BSELL || Handle::multi_scalar_ok(V.gsb.rest);
   }
   // forward sweep from zero b -> x, then res = b - A x: Handle::sweep_from_zero + residual_after_zero per column
   void gs_down(int w, const DevLevel& V, const double* b, double* x, double* res) {
     if (V.n == 0) return;
     const bool split = gs_split(V);
-    if (V.paths.sweep == SWEEP_GSB) {
+    const EpArgs none{nullptr, nullptr, nullptr, 0.0, nullptr, 0};
+    if (V.paths.bgsb()) {
+      // hybrid form: out of place from zero; block-coloured form: from zero over `offlo` with the split, else zero x and sweep in place
+      if (V.paths.sweep == SWEEP_BGSB || V.paths.zero_split) width(w, [&](auto W) { h.bgsb_sweep_nv<W()>(V, 0, nullptr, x, b); });
+      else { h.zero(x, V.len() * w); width(w, [&](auto W) { h.bgsb_sweep_nv<W()>(V, 0, x, x, b); }); }
+      if (split) { spmm<EP_MULT>(w, V.bgsb.rest, x, res, none); return; }        // r = rest x (DevBGSB)
+    } else if (V.paths.sweep == SWEEP_MC_BSELL || V.paths.sweep == SWEEP_MC_ROWLIST) {
+      h.zero(x, V.len() * w);
+      if (split) {                                             // r_B = -(U x)_B on the swept block rows, 0 elsewhere
+        h.zero(res, V.len() * w);
+        width(w, [&](auto W) { h.bgs_mc_sweep_nv<W()>(V, 0, x, b, true); h.bgs_upper_residual_nv<W()>(V, x, res); });
+        return;
+      }
+      width(w, [&](auto W) { h.bgs_mc_sweep_nv<W()>(V, 0, x, b); });
+    } else if (V.paths.sweep == SWEEP_GSB) {
       width(w, [&](auto W) { h.gsb_sweep_nv<W()>(V, 0, nullptr, x, b); });
       // r = c .* x - rest x (the sweep from zero read `lowin`: A is read once in total)
       if (split) { spmm<EP_CRES>(w, V.gsb.rest, x, res, EpArgs{x, nullptr, V.gsb.cvec.p, 0.0, nullptr, 0}); return; }
@@ -419,7 +479,8 @@ struct Multi {
   }
 
   // one plain smoother step per column on a level (amgx_smooth per column).  Groups of 4 and 2 run the multi-vector sweeps where
-  // the call carries AMGX_MULTI_FUSE_GS and the level has them (Handle::multi_sweep_ok, caller's numbering); everything else is a
+  // the call carries AMGX_MULTI_FUSE_GS and the level has them (Handle::multi_sweep_ok, caller's numbering; with
+  // AMGX_MULTI_FUSE_GS_BLOCK also Handle::multi_block_sweep_ok on a square-block level); everything else is a
   // column loop over level_smooth.  x_zero is the caller's promise of the flag contract; like the single-vector Gauss-Seidel
   // step, the sweeps do not act on it (they read x), so the columns of a group and the single columns see the same operation.
   void smooth(int level, int dir, int k, double* X, int64_t ldx, const double* B, int64_t ldb, bool interleaved, bool x_zero) {
@@ -427,7 +488,8 @@ struct Multi {
     const int64_t n = V.len();
     if (V.n != V.ncols) throw Err("amgx_smooth_multi: rank-partitioned levels are not supported");
     const int64_t xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx, brs = interleaved ? k : 1, bcs = interleaved ? 1 : ldb;
-    const bool nv = gs_flag && !h.permuted(level) && h.multi_sweep_ok(V) && V.n > 0;
+    const bool nv = gs_flag && !h.permuted(level) && V.n > 0 &&
+                    (h.multi_sweep_ok(V) || (block_flag && h.multi_block_sweep_ok(V) && h.multi_block_sweep_fits(V)));
     int32_t wd[MULTI_MAX];
     const int ng = multi_groups(k, nv, wd);
     int c0 = 0;
@@ -566,7 +628,7 @@ inline void multi_check(const char* fn, int k, const void* a, const void* b, int
 extern "C" {
 
 int amgx_apply_multi(amgx_handle hh, int k, const double* B, int64_t ldb, double* X, int64_t ldx, int b_status, int flags) {
-  if (k == 1 && hh && hh->h) return amgx_apply(hh, B, X, b_status, flags & ~(AMGX_MULTI_INTERLEAVED | AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS));   // the single-vector path itself
+  if (k == 1 && hh && hh->h) return amgx_apply(hh, B, X, b_status, flags & ~(AMGX_MULTI_INTERLEAVED | amgx::Multi::ALL_FLAGS));   // the single-vector path itself
   (void)b_status;   // single GPU: DISTRIBUTED == CUMULATED, as in amgx_apply
   return guard(hh, [&](amgx::Handle& h) {
     const int64_t n = h.lev[0].len();
@@ -638,9 +700,9 @@ int amgx_multi_info(amgx_handle hh, int k, int32_t* fused, int32_t* n_groups, in
 
 int amgx_multi_plan(amgx_handle hh, int k, int flags, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes) {
   return guard(hh, [&](amgx::Handle& h) {
-    const std::string fn = (flags & (AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS)) ? "amgx_multi_plan" : "amgx_multi_info";
+    const std::string fn = (flags & amgx::Multi::ALL_FLAGS) ? "amgx_multi_plan" : "amgx_multi_info";
     if (k < 1 || k > amgx::MULTI_MAX) throw amgx::Err(fn + ": k must be 1 .. " + std::to_string(amgx::MULTI_MAX) + " (got " + std::to_string(k) + ")");
-    amgx::Multi M(h, flags & (AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS));
+    amgx::Multi M(h, flags & amgx::Multi::ALL_FLAGS);
     int32_t wd[amgx::MULTI_MAX];
     const int ng = amgx::multi_groups(k, M.fz, wd);
     if (fused) *fused = M.fz ? 1 : 0;
@@ -654,7 +716,7 @@ const char* amgx_multi_note(amgx_handle hh, int flags) {
   thread_local std::string note;
   note.clear();
   if (guard(hh, [&](amgx::Handle& h) {
-        amgx::Multi M(h, flags & (AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS));
+        amgx::Multi M(h, flags & amgx::Multi::ALL_FLAGS);
         if (!M.fz) note = M.note();
       }))
     note = amgx_last_error(hh);

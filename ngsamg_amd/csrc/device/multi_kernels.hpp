@@ -768,6 +768,280 @@ __global__ __launch_bounds__(BLOCK) void gs_upper_residual_nv_kernel(int n_slice
   }
 }
 
+// ---- Gauss-Seidel sweeps of SQUARE-BLOCK levels on NV interleaved vectors (AMGX_MULTI_FUSE_GS_BLOCK) -----------
+// One block step of a BSELL row product for NV columns: the value loads of bsell_block_step<BS, false> (pair order, odd trailing
+// column last) and ONE gather of the block's BS * NV contiguous doubles at xb (global memory or LDS).  The values are loaded once
+// and serve all NV columns; per column the additions are those of the single-vector step.
+template <int BS, int NV>
+__device__ __forceinline__ void bsell_block_step_nv(const double* __restrict__ vk, const double* xb, int lane, double (&acc)[NV]) {
+  double xv[BS][NV];
+#pragma unroll
+  for (int cc = 0; cc < BS; ++cc) ldv<NV>(xb + cc * NV, xv[cc]);
+#pragma unroll
+  for (int cp = 0; cp < BS / 2; ++cp) {
+    double v0, v1;
+    ld_nt_pair(vk + cp * (2 * WAVE) + lane * 2, v0, v1);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] += v0 * xv[2 * cp][j] + v1 * xv[2 * cp + 1][j];
+  }
+  if constexpr (BS & 1) {
+    const double vl = ld_nt(vk + (BS / 2) * (2 * WAVE) + lane);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] += vl * xv[BS - 1][j];
+  }
+}
+// (row product of one slice: `w` block steps from (vb, cb), gathered blocks at x + c * BS * NV)
+template <int BS, int NV>
+__device__ __forceinline__ void bsell_slice_dot_nv(const BSellMat& M, int s, int rbl, int lane, const double* x, double (&acc)[NV]) {
+  constexpr int RB = WAVE / BS;
+  const int64_t k0 = M.slice_ptr[s];
+  const int w = (int)(M.slice_ptr[s + 1] - k0);
+  const double* __restrict__ vb = M.val + k0 * (BS * WAVE);
+  const int32_t* __restrict__ cb = M.col + k0 * RB;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+  for (int k = 0; k < w; ++k) {
+    const int c = cb[k * RB + rbl];
+    bsell_block_step_nv<BS, NV>(vb + (int64_t)k * (BS * WAVE), x + (int64_t)c * (BS * NV), lane, acc);
+  }
+}
+// the block solve of a row's lane group for NV columns: u = sum_c od[c] * t_c with t exchanged over the BS lanes from `base` on
+// (the __shfl order of the single-vector kernels).  Every lane of the wave calls it.
+template <int BS, int NV>
+__device__ __forceinline__ void block_solve_nv(const double (&od)[BS], const double (&t)[NV], int base, double (&u)[NV]) {
+#pragma unroll
+  for (int j = 0; j < NV; ++j) u[j] = 0.0;
+#pragma unroll
+  for (int cc = 0; cc < BS; ++cc) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) u[j] += od[cc] * __shfl(t[j], base + cc, WAVE);
+  }
+}
+
+// bgsb_sweep_kernel (kernels.hpp) for NV vectors: the same images (off / offlo, in, upin), the same blk_ptr / blk_rows / blk_list /
+// off_ptr / in_ptr / in_row, the same phases, colours and barriers; MODE as there (0: general, 1: from zero, 2: block-coloured from
+// zero, later block colours).  xs and b' live in LDS interleaved like the vectors (2 * BB * BS * NV doubles + the BB row ids: the
+// launcher computes the size, Handle::multi_block_sweep_lds); a row's dinv is loaded once for all NV columns.  Every lane reaches
+// every barrier; idle lanes (lane >= RB * BS) and padding slots (in_row < 0) never write.
+template <int BS, int MODE, int NV>
+__global__ __launch_bounds__(BLOCK) void bgsb_sweep_nv_kernel(int BB, int block0, const int32_t* __restrict__ blk_list,
+                                                              const int32_t* __restrict__ blk_ptr, const int32_t* __restrict__ blk_rows,
+                                                              BSellMat OFF, const int32_t* __restrict__ off_ptr,
+                                                              BSellMat IN, BSellMat OTH, const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_row,
+                                                              int n_colors, int dir, const double* __restrict__ dinv, const double* __restrict__ b,
+                                                              const double* xin, double* xout) {
+  constexpr bool FROM_ZERO = MODE != 0;
+  constexpr int RB = WAVE / BS;
+  constexpr int RW = BS * NV;                // doubles of one block row
+  extern __shared__ __attribute__((aligned(16))) double bgsb_nv_sh[];
+  double* xs = bgsb_nv_sh;
+  double* bsh = bgsb_nv_sh + (size_t)BB * RW;
+  int* rowsh = reinterpret_cast<int*>(bgsb_nv_sh + (size_t)2 * BB * RW);     // global block row of every local row
+  const int blk = blk_list ? blk_list[block0 + blockIdx.x] : block0 + blockIdx.x;
+  const int p0 = blk_ptr[blk];
+  const int nb = blk_ptr[blk + 1] - p0;
+  for (int e = threadIdx.x; e < nb; e += BLOCK) rowsh[e] = blk_rows[p0 + e];
+  __syncthreads();
+  for (int e = threadIdx.x; e < nb * RW; e += BLOCK) {
+    const int64_t g = (int64_t)rowsh[e / RW] * RW + e % RW;
+    xs[e] = FROM_ZERO ? 0.0 : xin[g];
+    bsh[e] = b[g];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+  const int rbl = lane / BS < RB ? lane / BS : RB - 1;
+  const int r = lane % BS;
+  const bool lane_on = lane < RB * BS;
+  if (MODE != 1) {
+    // phase 0: b' = b - (A_off + A_oth) x_old, gathers from global memory / from LDS
+    const int s0 = off_ptr[blk], s1 = off_ptr[blk + 1];
+    for (int s = s0 + wave; s < s1; s += WAVES_PER_BLOCK) {
+      const int lrow = (s - s0) * RB + rbl;
+      const bool active = lane_on && lrow < nb;
+      double acc[NV];
+      bsell_slice_dot_nv<BS, NV>(OFF, s, rbl, lane, xin, acc);
+      if (active) {
+        double bb[NV];
+        ldv<NV>(bsh + (lrow * BS + r) * NV, bb);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) bb[j] -= acc[j];
+        stv<NV>(bsh + (lrow * BS + r) * NV, bb);
+      }
+    }
+    __syncthreads();
+    const int t0 = in_ptr[blk * n_colors], t1 = MODE == 0 ? in_ptr[(blk + 1) * n_colors] : t0;
+    for (int s = t0 + wave; s < t1; s += WAVES_PER_BLOCK) {
+      const int lrow = in_row[(int64_t)s * RB + rbl];
+      const bool active = lane_on && lrow >= 0;
+      double acc[NV];
+      bsell_slice_dot_nv<BS, NV>(OTH, s, rbl, lane, xs, acc);
+      if (active) {
+        double bb[NV];
+        ldv<NV>(bsh + (lrow * BS + r) * NV, bb);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) bb[j] -= acc[j];
+        stv<NV>(bsh + (lrow * BS + r) * NV, bb);
+      }
+    }
+    __syncthreads();
+  }
+  for (int q = 0; q < n_colors; ++q) {
+    const int c = dir ? n_colors - 1 - q : q;
+    const int s0 = in_ptr[blk * n_colors + c], s1 = in_ptr[blk * n_colors + c + 1];
+    for (int s = s0 + wave; s < s1; s += WAVES_PER_BLOCK) {
+      const int lrow = in_row[(int64_t)s * RB + rbl];
+      const bool active = lane_on && lrow >= 0;
+      double od[BS];
+#pragma unroll
+      for (int cc = 0; cc < BS; ++cc) od[cc] = active ? dinv[(int64_t)rowsh[lrow] * (BS * BS) + r * BS + cc] : 0.0;
+      double acc[NV], t[NV], u[NV];
+      bsell_slice_dot_nv<BS, NV>(IN, s, rbl, lane, xs, acc);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) t[j] = 0.0;
+      if (active) {
+        ldv<NV>(bsh + (lrow * BS + r) * NV, t);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) t[j] = t[j] - acc[j];
+      }
+      block_solve_nv<BS, NV>(od, t, lane - r, u);
+      if (active) {
+        double xo[NV];
+        ldv<NV>(xs + (lrow * BS + r) * NV, xo);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) xo[j] += u[j];
+        stv<NV>(xs + (lrow * BS + r) * NV, xo);
+      }
+    }
+    __syncthreads();
+  }
+  for (int e = threadIdx.x; e < nb * RW; e += BLOCK) xout[(int64_t)rowsh[e / RW] * RW + e % RW] = xs[e];
+}
+
+// bgs_bsell_color_kernel for NV vectors: one colour per launch on the colour-major BSELL copy (gs.bcopy, or gs.blower for the sweep
+// from zero), in place.  Padding slots (rowid < 0) and idle lanes never write.
+template <int BS, int NV>
+__global__ __launch_bounds__(BLOCK) void bgs_bsell_color_nv_kernel(int slice_begin, int slice_end, BSellMat M, const int32_t* __restrict__ rowid,
+                                                                   const double* __restrict__ dinv, const double* __restrict__ b, double* x) {
+  constexpr int RB = WAVE / BS;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int s = __builtin_amdgcn_readfirstlane(slice_begin + blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6));
+  if (s >= slice_end) return;
+  const int rbl = lane / BS < RB ? lane / BS : RB - 1;
+  const int r = lane % BS;
+  const int brow = rowid[(int64_t)s * RB + rbl];
+  const bool active = lane < RB * BS && brow >= 0;
+  const int64_t io = ((int64_t)(brow >= 0 ? brow : 0) * BS + r) * NV;
+  double t[NV], od[BS];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) t[j] = 0.0;
+#pragma unroll
+  for (int c = 0; c < BS; ++c) od[c] = 0.0;
+  if (active) {
+    ldv<NV>(b + io, t);
+#pragma unroll
+    for (int c = 0; c < BS; ++c) od[c] = dinv[(int64_t)brow * (BS * BS) + r * BS + c];
+  }
+  double acc[NV], u[NV];
+  bsell_slice_dot_nv<BS, NV>(M, s, rbl, lane, x, acc);
+#pragma unroll
+  for (int j = 0; j < NV; ++j) t[j] = active ? t[j] - acc[j] : 0.0;
+  block_solve_nv<BS, NV>(od, t, lane - r, u);
+  if (active) {
+    double xo[NV];
+    ldv<NV>(x + io, xo);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) xo[j] += u[j];
+    stv<NV>(x + io, xo);
+  }
+}
+
+// bgs_bsell_upper_residual_kernel for NV vectors: r_B = -(U x)_B on the colour-major block rows of gs.bupper after the sweep from zero
+template <int BS, int NV>
+__global__ __launch_bounds__(BLOCK) void bgs_bsell_upper_residual_nv_kernel(int n_slices, BSellMat M, const int32_t* __restrict__ rowid,
+                                                                            const double* __restrict__ x, double* __restrict__ res) {
+  constexpr int RB = WAVE / BS;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int s = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6));
+  if (s >= n_slices) return;
+  const int rbl = lane / BS < RB ? lane / BS : RB - 1;
+  const int r = lane % BS;
+  const int brow = rowid[(int64_t)s * RB + rbl];
+  const bool active = lane < RB * BS && brow >= 0;
+  double acc[NV];
+  bsell_slice_dot_nv<BS, NV>(M, s, rbl, lane, x, acc);
+  if (active) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] = -acc[j];
+    stv<NV>(res + ((int64_t)brow * BS + r) * NV, acc);
+  }
+}
+
+// bgs_color_kernel for NV vectors: the colour-major row list over the block CSR of A, lane (g, r) owns scalar row r and the blocks
+// g, g + W, ... of its block row (the additions of bcsr_row_dot per column: blocks ascending, block columns ascending)
+template <int BS, int W, int NV>
+__global__ __launch_bounds__(BLOCK) void bgs_color_nv_kernel(int list_begin, int list_end, const int32_t* __restrict__ rowlist,
+                                                             const int32_t* __restrict__ rowptr, const int32_t* __restrict__ cols,
+                                                             const double* __restrict__ vals, const double* __restrict__ dinv,
+                                                             const double* __restrict__ b, double* x) {
+  constexpr int LPR = BS * W;
+  constexpr int RPW = WAVE / LPR;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+  const int rloc = lane / LPR;
+  const int g = (lane % LPR) / BS;
+  const int r = lane % BS;
+  const int64_t q = list_begin + wave * RPW + rloc;
+  const bool active = rloc < RPW && q < list_end;
+  const int row = active ? rowlist[q] : 0;
+  double acc[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+  if (active) {
+    const int e = rowptr[row + 1];
+    for (int k = rowptr[row] + g; k < e; k += W) {
+      const double* __restrict__ a = vals + (int64_t)k * (BS * BS) + r * BS;
+      const double* xb = x + (int64_t)cols[k] * (BS * NV);
+      double av[BS], xv[BS][NV];
+#pragma unroll
+      for (int c = 0; c < BS; ++c) av[c] = a[c];
+#pragma unroll
+      for (int c = 0; c < BS; ++c) ldv<NV>(xb + c * NV, xv[c]);
+#pragma unroll
+      for (int c = 0; c < BS; ++c) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) acc[j] += av[c] * xv[c][j];
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+#pragma unroll
+    for (int o = W >> 1; o > 0; o >>= 1) acc[j] += __shfl_down(acc[j], o * BS, WAVE);
+  }
+  const bool writer = active && g == 0;
+  const int64_t io = ((int64_t)row * BS + r) * NV;
+  double t[NV], od[BS], u[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) t[j] = 0.0;
+#pragma unroll
+  for (int c = 0; c < BS; ++c) od[c] = 0.0;
+  if (writer) {
+    ldv<NV>(b + io, t);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) t[j] = t[j] - acc[j];
+#pragma unroll
+    for (int c = 0; c < BS; ++c) od[c] = dinv[(int64_t)row * (BS * BS) + r * BS + c];
+  }
+  block_solve_nv<BS, NV>(od, t, lane - r, u);
+  if (writer) {
+    double xo[NV];
+    ldv<NV>(x + io, xo);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) xo[j] += u[j];
+    stv<NV>(x + io, xo);
+  }
+}
+
 // ---- element-wise pieces on interleaved vectors (one thread per entry) -------------------------------------------------------
 // x = omega * Dinv * b, width 1 << sh     (diag_apply_kernel<1, false> per column)
 __global__ __launch_bounds__(BLOCK) void multi_diag_kernel(int64_t len, int sh, const double* __restrict__ dinv, const double* __restrict__ b,

@@ -239,11 +239,14 @@ def check_multi(vecs, sizes, interleaved=False, names=None):
 
 def check_fuse(fuse):
     """Validate the fuse= keyword of the multi-vector calls (a plain function: no handle, no native call); returns the flag bits:
-    False -> 0, True -> AMGX_MULTI_FUSE, "gs" -> AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS (scalar Gauss-Seidel levels fuse too)"""
+    False -> 0, True -> AMGX_MULTI_FUSE, "gs" -> AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS (scalar Gauss-Seidel levels fuse too),
+    "gs_block" -> those two | AMGX_MULTI_FUSE_GS_BLOCK (Gauss-Seidel on 2x2 / 3x3 / 6x6 levels fuses too)"""
     if isinstance(fuse, str) and fuse == "gs":
         return _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS
+    if isinstance(fuse, str) and fuse == "gs_block":
+        return _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS | _lib.AMGX_MULTI_FUSE_GS_BLOCK
     if not isinstance(fuse, (bool, np.bool_)):
-        raise NgsAMGError(f"fuse: need True, False or \"gs\", got {fuse!r}")
+        raise NgsAMGError(f"fuse: need True, False, \"gs\" or \"gs_block\", got {fuse!r}")
     return _lib.AMGX_MULTI_FUSE if fuse else 0
 
 
@@ -464,7 +467,9 @@ class DeviceAMGMatrix:
         """X[j] = C B[j] for k = 1 .. 8 right-hand sides: 2-D float64 arrays / CUDA tensors of shape (k, n), or (n, k) with
         interleaved=True.  Handles that qualify (multi_info) read every level matrix once per group of 2, 4 or 8 columns.
         fuse=True (AMGX_MULTI_FUSE): the wider rule of multi_plan(k, fuse=True) -- Chebyshev and block levels run fused too.
-        fuse="gs" (AMGX_MULTI_FUSE_GS as well): scalar Gauss-Seidel levels (block-hybrid or multicolour form) run fused too."""
+        fuse="gs" (AMGX_MULTI_FUSE_GS as well): scalar Gauss-Seidel levels (block-hybrid or multicolour form) run fused too.
+        fuse="gs_block" (AMGX_MULTI_FUSE_GS_BLOCK as well): so does Gauss-Seidel on 2x2 / 3x3 / 6x6 levels (hybrid-block,
+        block-coloured and multicolour forms) -- the default smoother of the elasticity hierarchies."""
         ff = check_fuse(fuse)
         n = self.sizes[0]
         k, (ab, ax), (lb, lx), dev = check_multi((B, X), (n, n), interleaved, ("B", "X"))
@@ -513,7 +518,8 @@ class DeviceAMGMatrix:
     def SmoothMulti(self, level, X, B, x_zero=False, back=False, interleaved=False, fuse=False):
         """one plain smoother step per column: Smooth(level, X[j], B[j], res, x_zero=x_zero, back=back) with a res of its own
         (amgx_smooth_multi).  X, B: (k, n_level), or (n_level, k) with interleaved=True.  fuse="gs": groups of 4 and 2 columns
-        run the multi-vector Gauss-Seidel sweeps on a level that has them; a column equals Smooth bit for bit either way."""
+        run the multi-vector Gauss-Seidel sweeps on a scalar level that has them, fuse="gs_block" on a square-block level too; a
+        column equals Smooth bit for bit either way."""
         ff = check_fuse(fuse)
         n = self._size(level)
         if self.ext_sizes[level] != n:

@@ -126,7 +126,8 @@ class NativeCGSolver(_NativeSolver):
         """k right-hand sides at once (amgx_pcg_multi): k independent recurrences that share the level-0 product and the
         preconditioner application.  rhs / sol: 2-D float64 arrays or CUDA tensors, shape (k, n) or, interleaved, (n, k); sol holds
         the initial guesses (default 0).  Afterwards `iterations` is a list of k counts and `errors` a list of k histories; a column
-        that converged is frozen while the others go on.  fuse=True: AMGX_MULTI_FUSE for the product and the preconditioner; fuse="gs": AMGX_MULTI_FUSE_GS as well."""
+        that converged is frozen while the others go on.  fuse=True: AMGX_MULTI_FUSE for the product and the preconditioner; fuse="gs": AMGX_MULTI_FUSE_GS as well;
+        fuse="gs_block": AMGX_MULTI_FUSE_GS_BLOCK as well (Gauss-Seidel on 2x2 / 3x3 / 6x6 levels)."""
         import ctypes as C
         import numpy as np
         from .device import _is_torch, check_fuse, check_multi

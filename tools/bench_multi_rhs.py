@@ -17,7 +17,9 @@ does) select handles that are fused only under AMGX_MULTI_FUSE:
 fuse=True, (a) stays k calls of amgx_apply / amgx_pcg on the same handle; the result goes to profiles/r14/.
 
 --smoother gs (with --config cfg2): the library's default smoother, Gauss-Seidel in the block-hybrid form ("hgs" levels), which fuses
-only under AMGX_MULTI_FUSE_GS: (b), (b') and the multi-vector PCG carry fuse="gs"; the result goes to profiles/r21/."""
+only under AMGX_MULTI_FUSE_GS: (b), (b') and the multi-vector PCG carry fuse="gs"; the result goes to profiles/r21/.
+--smoother gs with --config cfg3 | cfg5: Gauss-Seidel on the 3x3 / 6x6 levels (block-coloured on level 0, hybrid-block below), fused
+only under AMGX_MULTI_FUSE_GS_BLOCK: the calls carry fuse="gs_block"; the result goes to profiles/r22/."""
 import argparse
 import json
 import os
@@ -65,14 +67,15 @@ def main():
     from ngsamg_amd.krylov import NativeCGSolver
     nv = args.nv or (215 if args.config == "cfg2" else 126)
     ks = [int(v) for v in args.k.split(",")]
-    if args.smoother == "gs" and args.config != "cfg2":
-        sys.exit("bench_multi_rhs: --smoother gs is measured at --config cfg2 (Gauss-Seidel on block levels keeps the column loop)")
-    # handles that are fused only under AMGX_MULTI_FUSE (True) / AMGX_MULTI_FUSE_GS ("gs")
-    fuse = "gs" if args.smoother == "gs" else (args.smoother != "jacobi" or args.config != "cfg2")
+    # handles that are fused only under AMGX_MULTI_FUSE (True) / AMGX_MULTI_FUSE_GS ("gs") / AMGX_MULTI_FUSE_GS_BLOCK ("gs_block")
+    if args.smoother == "gs":
+        fuse = "gs" if args.config == "cfg2" else "gs_block"
+    else:
+        fuse = args.smoother != "jacobi" or args.config != "cfg2"
     tag = f"{args.config}_{args.smoother}" + (str(args.degree) if args.smoother == "cheby" else "")
     if args.out is None:
-        if fuse == "gs":
-            args.out = os.path.join(ROOT, "profiles", "r21", f"multi_gs_{args.config}.json")
+        if isinstance(fuse, str):
+            args.out = os.path.join(ROOT, "profiles", "r21" if fuse == "gs" else "r22", f"multi_gs_{args.config}.json")
         else:
             args.out = os.path.join(ROOT, "profiles", "r14", f"multi_fuse_{tag}.json") if fuse else os.path.join(ROOT, "profiles", "r06", "multi_rhs.json")
     if args.config == "cfg2":
@@ -111,14 +114,15 @@ def main():
         print("ms per multi cycle:", timed(lambda: dev.MultMulti(Bi, Xi, interleaved=True, fuse=fuse), args.reps))
         return
 
-    if fuse == "gs" and dev.multi_plan(4, fuse=fuse)["fused"] != 1:
-        sys.exit("bench_multi_rhs: the handle is not fused under AMGX_MULTI_FUSE_GS: " + dev.multi_plan(4, fuse=fuse)["note"])
+    if isinstance(fuse, str) and dev.multi_plan(4, fuse=fuse)["fused"] != 1:
+        flag = "AMGX_MULTI_FUSE_GS" if fuse == "gs" else "AMGX_MULTI_FUSE_GS_BLOCK"
+        sys.exit(f"bench_multi_rhs: the handle is not fused under {flag}: " + dev.multi_plan(4, fuse=fuse)["note"])
     out = {"commit": args.commit or _commit(), "config": args.config, "smoother": args.smoother, "degree": args.degree if args.smoother == "cheby" else 0,
            "fuse": fuse, "nv": nv, "n": int(n), "levels": H.n_levels, "cycle_info": dev.cycle_info(),
            "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps, "pcg_reps": args.pcg_reps,
            "handle_bytes": int(free0 - free1), "k": {}}
-    if fuse == "gs":                                           # the forms under test and the matrix bytes of the byte model, per smoothed level
-        keys = ("gs_form", "gs_lanes", "gs_threads", "gs_block", "gs_colors", "gs_split", "gs_narrow", "gs_mid", "gs_lw", "gs_down")
+    if isinstance(fuse, str):                                  # the forms under test and the matrix bytes of the byte model, per smoothed level
+        keys = ("gs_form", "gs_lanes", "gs_threads", "gs_block", "gs_colors", "gs_block_colors", "gs_split", "gs_narrow", "gs_mid", "gs_lw", "gs_down")
         out["levels_gs"] = [dict({key: dev.level_paths(l)[key] for key in keys}, rows=int(dev.sizes[l]),
                                  A_stream_bytes=dev.matrix_info(l, "A")["stream_bytes"]) for l in range(H.n_levels - 1)]
     for k in ks:
