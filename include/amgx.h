@@ -289,6 +289,20 @@ int amgx_matrix_stream_bytes(amgx_handle h, int level, int which, int64_t* bytes
 #define AMGX_LEVEL_PATHS_N 40
 int amgx_level_paths(amgx_handle h, int level, int64_t* out, int n_out);
 
+/* further read-only entries of the same kind (amgx_level_paths keeps its 40).  Fills out[0 .. min(n_out, AMGX_LEVEL_EXTRA_N)):
+ *    0 operations of the program the single-workgroup tail kernel runs (the same for every level; 0: the cycle has no such tail)
+ *    1 form of this level's Gauss-Seidel sweeps inside the tail kernel: 1 x in LDS and the rows in registers, 0 x in global
+ *      memory, -1 the level is not part of the tail or its smoother is not Gauss-Seidel
+ *    2, 3 multicolour scalar Gauss-Seidel (form 1 of entry 19 above): slices with 16-bit columns and all slices of the
+ *      colour-major copies (whole copy + the lower / upper split copies where present; 0 otherwise)
+ *    4 ... and whether their 16-bit columns are row-relative (AMGX_GS_ROWREL at amgx_create)
+ *    5, 6 sliced-ELL images of A and A': every row stores its diagonal entry first (0 after AMGX_NO_DIAG_FIRST=1, with several lanes
+ *      per row, with row windows or in another format)          7 the diagonal slot of A' holds omega instead of A'_ii
+ *    8 whole-cycle graphs this handle holds at the moment (the same for every level)
+ * Returns 0, or non-zero for a bad level or n_out < 1. */
+#define AMGX_LEVEL_EXTRA_N 9
+int amgx_level_extra(amgx_handle h, int level, int64_t* out, int n_out);
+
 /* measurement hook for bench.py: launches one hot-path kernel `reps` times on the handle's stream,
  * bracketed by HIP events, and returns the average duration in milliseconds.
  *   op = 0: residual SpMV  r = b - A_level x      (the dominant kernel of the Jacobi V-cycle)
@@ -476,6 +490,10 @@ int amgx_comm_info(amgx_comm c, int32_t* kind, int32_t* n_ranks, int32_t* rank, 
  * after AMGX_DIST_GRAPH=0 or a failed capture (note: why; direct launches from then on); n_graphs = captured cycles held,
  * n_replays = applications served by a graph launch. */
 int amgx_comm_graph_info(amgx_comm c, int32_t* enabled, int64_t* n_graphs, int64_t* n_replays);
+/* how directly launched work on the compute and the communication stream is ordered: event_order = 1 events (hipEventRecord /
+ * hipStreamWaitEvent: AMGX_DIST_EVENTS=1 at amgx_comm_create, or a device without stream memory operations), 0 device flags
+ * (hipStreamWriteValue64 / hipStreamWaitValue64).  Inside a captured graph the order is always a graph edge. */
+int amgx_comm_order_info(amgx_comm c, int32_t* event_order);
 const char* amgx_comm_graph_note(amgx_comm c);
 
 /* halo tables of one level = DCCMap's m_ex_dofs / g_ex_dofs (dcc_map.cpp:480-543) in owner-row form */

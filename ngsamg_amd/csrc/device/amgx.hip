@@ -1434,6 +1434,8 @@ struct Handle {
   int ep_nt = 1;                        // non-temporal epilogue operands (AMGX_NO_EP_NT=1 disables)
   int tail_level = -1;                  // first level executed by tail_kernel (-1: no fused tail)
   int tail_ops = 0;
+  std::vector<int> tail_gs_lds;         // per level: form of its Gauss-Seidel sweeps inside tail_kernel (1: x in LDS, 0: x in global memory,
+                                        //   -1: the level has no such sweep); amgx_level_extra reports it
   DevBuf<TailOp> tail_prog;
   // collapsed coarse levels (kernels.hpp, dense_op_gemv_kernel): the V-cycle on the levels >= dense_level as ONE dense
   // operator, formed at create time by the device's own sub-cycle on the unit vectors (build_dense_tail)
@@ -3189,6 +3191,32 @@ int amgx_level_paths(amgx_handle hh, int level, int64_t* out, int n_out) {
     };
     v[37] = bcsr(L.A); v[38] = bcsr(L.P); v[39] = bcsr(L.PT);
     for (int k = 0; k < std::min(n_out, AMGX_LEVEL_PATHS_N); ++k) out[k] = v[k];
+  });
+}
+
+int amgx_level_extra(amgx_handle hh, int level, int64_t* out, int n_out) {
+  return guard(hh, [&](amgx::Handle& h) {
+    if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_level_extra: level out of range");
+    if (!out || n_out < 1) throw amgx::Err("amgx_level_extra: bad arguments");
+    const amgx::DevLevel& L = h.lev[level];
+    const bool tail = h.dense_level < 0 && h.tail_level > 0;
+    int64_t v[AMGX_LEVEL_EXTRA_N] = {};
+    v[0] = tail ? h.tail_ops : 0;
+    v[1] = tail && level >= h.tail_level && level < (int)h.tail_gs_lds.size() ? h.tail_gs_lds[level] : -1;
+    if (L.paths.sweep == amgx::SWEEP_MC && L.gs.n_slices_total > 0) {
+      const amgx::DevMatrix::Sell* img[3] = {&L.gs.sell, L.gs.has_split ? &L.gs.lower : nullptr, L.gs.has_split ? &L.gs.upper : nullptr};
+      for (const amgx::DevMatrix::Sell* S : img) {
+        if (!S) continue;
+        const std::vector<int64_t> sp = amgx::db_download(S->slice_ptr, (size_t)L.gs.n_slices_total);
+        for (int64_t p : sp) v[2] += p & 1;
+        v[3] += L.gs.n_slices_total;
+      }
+      v[4] = L.gs.sell.rowrel;
+    }
+    if (!L.A.empty() && L.A.fmt == amgx::FMT_SELL) v[5] = L.A.sell.diag_first;
+    if (!L.Apre.empty() && L.Apre.fmt == amgx::FMT_SELL) { v[6] = L.Apre.sell.diag_first; v[7] = L.Apre.sell.wdiag; }
+    v[8] = (int64_t)h.graphs.size();
+    for (int k = 0; k < std::min(n_out, AMGX_LEVEL_EXTRA_N); ++k) out[k] = v[k];
   });
 }
 

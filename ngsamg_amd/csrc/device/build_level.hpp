@@ -610,6 +610,8 @@ static void build_tail_program(Handle& h, const amgx_hierarchy_desc* d, const am
     return 1;
   };
   for (int l = T; l + 1 < L; ++l) upload_tail_level(levels[l], h.lev[l]);
+  h.tail_gs_lds.assign((size_t)L, -1);
+  for (int l = T; l + 1 < L; ++l) if (h.lev[l].sm_type != AMGX_SM_JACOBI) h.tail_gs_lds[l] = gs_lds_ok(l);
   for (int l = T; l + 1 < L; ++l) {       // down
     DevLevel& V = h.lev[l];
     if (V.sm_type == AMGX_SM_JACOBI) {     // r = b - A'b, x = omega*Dinv*b

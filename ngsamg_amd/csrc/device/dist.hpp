@@ -1283,6 +1283,9 @@ int amgx_comm_graph_info(amgx_comm cc, int32_t* enabled, int64_t* n_graphs, int6
     if (n_replays) *n_replays = c.n_graph_replays;
   });
 }
+int amgx_comm_order_info(amgx_comm cc, int32_t* event_order) {
+  return cguard(cc, [&](amgx::Comm& c) { if (event_order) *event_order = c.use_values ? 0 : 1; });
+}
 const char* amgx_comm_graph_note(amgx_comm c) { return (c && c->c) ? c->c->graph_note.c_str() : ""; }
 
 int amgx_dist_create(amgx_comm cc, const amgx_dist_desc* desc, amgx_dist* out) {

@@ -33,8 +33,8 @@ struct Knobs {
   bool host_lw = false;                 // AMGX_HOST_LW: the local-window images come from the host builder (kill switch)
   bool gs_perm = false;                 // AMGX_GS_PERM: colour-major renumbering of Gauss-Seidel levels (A/B hook)
   // ---- matrix formats
-  int sell_max_lanes = 0;               // AMGX_SELL_MAX_LANES: cap on the lanes per row of a SELL image, 0 = none (test hook)
-  int sell_long_row_lanes = 1;          // AMGX_SELL_LONG_ROW_LANES: lanes per row for rows of >= 24 entries (A/B hook)
+  int sell_max_lanes = 0;               // AMGX_SELL_MAX_LANES: cap on the lanes per row of a SELL image (1, 2, 4, 8, 16), 0 = none (test hook)
+  int sell_long_row_lanes = 1;          // AMGX_SELL_LONG_ROW_LANES: least lanes per row (1, 2, 4, 8, 16) for rows of >= 24 entries (A/B hook)
   bool no_sell_window = false;          // AMGX_NO_SELL_WINDOW: no length-sorted windows (kill switch)
   bool no_sell_window_short = false;    // AMGX_NO_SELL_WINDOW_SHORT: no windowed fallback for short ragged rows (kill switch)
   bool no_diag_first = false;           // AMGX_NO_DIAG_FIRST: CSR entry order instead of diagonal first (kill switch)
@@ -110,8 +110,11 @@ struct Knobs {
     i64("AMGX_DEV_IMAGES_MIN_ROWS", k.dev_images_min_rows);
     k.host_lw = on("AMGX_HOST_LW");
     k.gs_perm = on("AMGX_GS_PERM");
-    if (const char* e = std::getenv("AMGX_SELL_MAX_LANES")) k.sell_max_lanes = std::max(1, std::atoi(e));
-    if (const char* e = std::getenv("AMGX_SELL_LONG_ROW_LANES")) k.sell_long_row_lanes = std::max(1, std::atoi(e));
+    // lanes per row: the SELL kernels exist for G in {1, 2, 4, 8, 16} (R = WAVE / G rows per wave), so any other value is rounded
+    // down to the next of them (3 -> 2, 100 -> 16, 0 and negative values -> 1)
+    auto lanes = [](const char* e) { const int v = std::atoi(e); int g = 1; while (g < 16 && 2 * g <= v) g *= 2; return g; };
+    if (const char* e = std::getenv("AMGX_SELL_MAX_LANES")) k.sell_max_lanes = lanes(e);
+    if (const char* e = std::getenv("AMGX_SELL_LONG_ROW_LANES")) k.sell_long_row_lanes = lanes(e);
     k.no_sell_window = on("AMGX_NO_SELL_WINDOW");
     k.no_sell_window_short = on("AMGX_NO_SELL_WINDOW_SHORT");
     k.no_diag_first = on("AMGX_NO_DIAG_FIRST");

@@ -661,6 +661,21 @@ class DeviceAMGMatrix:
             d[k] = None if d[k] == 0 else (("rowlane", "csrvec")[d[k] // 100 - 1], d[k] % 100)
         return d
 
+    _EXTRA_KEYS = ("tail_ops", "tail_gs_lds", "gs_slices16", "gs_slices", "gs_rowrel", "A_diag_first", "Apre_diag_first", "Apre_wdiag",
+                   "graphs")
+
+    def level_extra(self, level):
+        """further read-only paths of one level (amgx_level_extra): the operations of the tail kernel's program ("tail_ops", 0
+        without such a tail), the form of this level's Gauss-Seidel sweeps inside it ("tail_gs_lds": 1 x in LDS, 0 x in global
+        memory, None not a Gauss-Seidel level of the tail), the 16-bit / all slices of the colour-major copies of the multicolour
+        scalar sweep and whether their 16-bit columns are row-relative, whether the sliced-ELL images of A and A' store the diagonal
+        entry of every row first and whether that slot of A' holds omega, and the whole-cycle graphs the handle holds"""
+        out = np.zeros(len(self._EXTRA_KEYS), dtype=np.int64)
+        self._ck(self._lib.amgx_level_extra(self._h, int(level), out.ctypes.data_as(_lib.c_i64p), out.size))
+        d = dict(zip(self._EXTRA_KEYS, (int(v) for v in out)))
+        d["tail_gs_lds"] = None if d["tail_gs_lds"] < 0 else d["tail_gs_lds"]
+        return d
+
     _SM_NAMES = {_lib.AMGX_SM_JACOBI: "jacobi", _lib.AMGX_SM_GS: "gs", _lib.AMGX_SM_BGS: "bgs", _lib.AMGX_SM_CHEBY: "cheby"}
 
     def smoother_info(self, level):

@@ -1559,5 +1559,11 @@ class _DeviceDist:
         return {"enabled": bool(en.value), "graphs": ng.value, "replays": nr.value,
                 "note": (self._lib.amgx_comm_graph_note(self._comm) or b"").decode()}
 
+    def order_info(self):
+        """how directly launched work on the two streams is ordered: "events" or "flags" (amgx_comm_order_info)"""
+        ev = C.c_int32()
+        self._ck(self._lib.amgx_comm_order_info(self._comm, C.byref(ev)))
+        return "events" if ev.value else "flags"
+
     def synchronize(self):
         self._ck(self._lib.amgx_comm_synchronize(self._comm))

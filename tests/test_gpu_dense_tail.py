@@ -1,6 +1,8 @@
 """Collapsed coarse levels (dense_op_gemv_kernel): the V-cycle on the levels >= l_c applied as ONE dense operator that
 amgx_create forms with the device's own sub-cycle.  Checked against the oracle (amg_matrix.cpp:183-302 restated) and
-against the same handle built with separate launches (AMGX_NO_DENSE_TAIL=1); both launch forms must stay green."""
+against the same handle built without the collapse (AMGX_NO_DENSE_TAIL=1): its small coarse levels then run inside the
+single-workgroup tail kernel (cycle_info()["tail_level"] >= 1, asserted; tests/test_gpu_tail_kernel.py), the larger ones as
+separate launches; both launch forms must stay green."""
 import os
 
 import numpy as np
@@ -39,6 +41,7 @@ def test_dense_tail_matches_oracle_and_separate_launches(shape, diri, mcs, sm, o
     ci1, ci0 = d1.cycle_info(), d0.cycle_info()
     assert ci0["dense_level"] == -1
     if H.n_levels >= 3:
+        assert 1 <= ci0["tail_level"] <= H.n_levels - 2      # not separate launches: the last smoothed levels run in tail_kernel
         assert 1 <= ci1["dense_level"] <= H.n_levels - 2 and ci1["dense_n"] == H.levels[ci1["dense_level"]].n
         assert ci1["tail_level"] == -1
     x1, x0 = np.full(p.n, np.nan), np.full(p.n, np.nan)
