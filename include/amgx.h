@@ -138,6 +138,17 @@ typedef struct amgx_level_desc {
                               /*   block sliced-ELL form; levels in another format (CSR-vector, windowed, block CSR: the small ones) stay  */
                               /*   fp64 silently -- amgx_matrix_info(which = 7) tells.  A value that rounds to +-inf is an error.          */
                               /*   Environment of amgx_create: AMGX_NO_MAT_F32=1 ignores every request.                                    */
+                              /*   AMGX_PREC_F32 is also accepted on square-block levels smoothed with AMGX_SM_GS (an error on Jacobi,     */
+                              /*   AMGX_SM_BGS and scalar Gauss-Seidel levels and on rank-partitioned levels).  On a 2x2, 3x3 or 6x6       */
+                              /*   level whose sweeps run in the hybrid-block, block-coloured or multicolour BSELL form, every BSELL       */
+                              /*   image that the sweeps and the residual after the sweep from zero read -- A itself included -- gets a    */
+                              /*   float twin (each image's fp64 value rounded to nearest, index arrays shared); dinv stays that of the    */
+                              /*   true A.  update_res -- the residual of an iterate that a further correction uses: W / BS cycles,        */
+                              /*   amgx_smooth -- reads the fp64 A, where the rounded one would shift the result by cond(A) * 6e-8. The    */
+                              /*   result is that of the fp64 kernels on the rounded images, bit for bit.  Gauss-Seidel levels in any      */
+                              /*   other form (the row list over block CSR, other block sizes) stay fp64 silently -- amgx_level_extra      */
+                              /*   entries 9 .. 11 tell.  AMGX_GS_F32_WIDE=1 at amgx_create: no float images; the rounded values are       */
+                              /*   written into fp64 images of exactly those levels and the fp64 kernels run (A/B twin).                   */
 } amgx_level_desc;
 enum { AMGX_PREC_F64 = 0, AMGX_PREC_F32 = 1 };                    /* amgx_level_desc.mat_prec */
 
@@ -299,8 +310,11 @@ int amgx_level_paths(amgx_handle h, int level, int64_t* out, int n_out);
  *    5, 6 sliced-ELL images of A and A': every row stores its diagonal entry first (0 after AMGX_NO_DIAG_FIRST=1, with several lanes
  *      per row, with row windows or in another format)          7 the diagonal slot of A' holds omega instead of A'_ii
  *    8 whole-cycle graphs this handle holds at the moment (the same for every level)
+ *    9 the Gauss-Seidel sweeps of this level read single-precision images (1; 0 otherwise, also under AMGX_GS_F32_WIDE)
+ *    10, 11 the number of single-precision Gauss-Seidel images of this level (A included) and the bytes of their values
+ *      (under AMGX_GS_F32_WIDE: the fp64 images that hold rounded values, 8 bytes per value, while entry 9 stays 0)
  * Returns 0, or non-zero for a bad level or n_out < 1. */
-#define AMGX_LEVEL_EXTRA_N 9
+#define AMGX_LEVEL_EXTRA_N 12
 int amgx_level_extra(amgx_handle h, int level, int64_t* out, int n_out);
 
 /* measurement hook for bench.py: launches one hot-path kernel `reps` times on the handle's stream,
@@ -318,6 +332,9 @@ int amgx_level_extra(amgx_handle h, int level, int64_t* out, int n_out);
  *           of a Gauss-Seidel cycle); error if the level has no such sweep
  *   op = 10: one fused Chebyshev step  x' = x + d', d' = c1 d + c2 dinv*(b - A_level x)  (a middle step: d read and stored);
  *           error if the level has no Chebyshev smoother
+ *   op = 11: like 9 for the backward Gauss-Seidel sweep of a square-block level (bgsb_sweep_kernel: one launch, or one per block
+ *           colour; the launches per colour of the block multicolour forms); error if the level has no block sweep in the cycle.
+ *           On a level with single-precision Gauss-Seidel images it reads them
  * ops 5 and 10 time what the cycle runs: on a level with a single-precision image (mat_prec) they read that image; op 0 is
  * amgx_residual's kernel and reads the fp64 image. */
 int amgx_time_op(amgx_handle h, int level, int op, int reps, double* avg_ms);
@@ -401,7 +418,9 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  * mixed freely with Jacobi and Chebyshev levels, if it is scalar (bs = 1), square, in the caller's numbering, plain, and swept in
  * the block-hybrid or the scalar multicolour form.  Its sweeps keep, per column, the order of additions of the single-vector
  * sweep: a column of amgx_smooth_multi equals amgx_smooth bit for bit.  Gauss-Seidel on a block level and AMGX_SM_BGS keep the
- * column loop (amgx_multi_note names the smoother and the level).
+ * column loop (amgx_multi_note names the smoother and the level).  So does a handle with a Gauss-Seidel level that reads
+ * single-precision images (mat_prec = AMGX_PREC_F32): the fused sweeps read fp64 images, and the note says "single-precision
+ * Gauss-Seidel images (level l)".
  * With AMGX_MULTI_FUSE_GS_BLOCK (opt-in per call; it implies the two flags above) an AMGX_SM_GS level may also have
  * block size 2, 3 or 6, if it is square, in the caller's numbering, plain, and swept in the hybrid-block, the block-coloured, the
  * multicolour BSELL or the multicolour row-list form (compact sweep blocks, gs_block_ids, included), and if its sweep block fits

@@ -146,12 +146,19 @@ struct DevMatrix {
     DevBuf<int32_t> col;
     DevBuf<double> val;
     BSellMat view(int xmode) const { return BSellMat{slice_ptr.p, col.p, val.p, xmode}; }
+    BSellMat view_of(const double* v, int xmode) const { return BSellMat{slice_ptr.p, col.p, v, xmode}; }
     BSellMatT<float> view32(const float* v32, int xmode) const { return BSellMatT<float>{slice_ptr.p, col.p, v32, xmode}; }
   } bsell;
   // single-precision image (A of a Chebyshev level with mat_prec = AMGX_PREC_F32, plain SELL or BSELL only): the
   // value array of the format above rounded to float, same layout, every index array shared.  Built by mat_f32_image
   // (build_level.hpp); read by the smoother passes of Handle::product and by the fused residual + restriction, by nothing else.
+  // also A and the BSELL sweep images of a Gauss-Seidel block level (DevLevel::gs32), read by its sweeps and residuals.
   DevBuf<float> val32;
+  // The rounded values of A at fp64 width, in the layout of A's format, read by the smoother passes in place of the true ones: under
+  // AMGX_GS_F32_WIDE (A/B twin of 5.17; the sweep-only images hold their rounded values in the fp64 array itself), and on a
+  // Gauss-Seidel level with float sweep images whose A stayed in block CSR (a small level: no float kernel, no bytes to save, but the
+  // same rounded operator in the sweeps and in the residual).  A keeps its true values for amgx_matvec and the Krylov drivers.
+  DevBuf<double> val64r;
   bool has32() const { return val32.p != nullptr; }
   int64_t stream_bytes32() const { return stream_bytes - 4 * (int64_t)val32.n; }
   bool empty() const { return n_rows == 0; }
@@ -386,6 +393,13 @@ struct DevLevel {
   DevBuf<int32_t> qlw_cptr, qlw_ccol;
   DevMatrix Q;                          // scalar Jacobi levels of the V-cycle: (I - omega*Dinv*A) P, see fold_prolongation()
   DevBuf<double> dinv;
+  // Gauss-Seidel block level with mat_prec = AMGX_PREC_F32 (decided by mat_f32_image): the sweeps and the residual
+  // after the sweep from zero read the float images (DevMatrix::val32) of A and of every BSELL image below;
+  // gs32_images / gs32_bytes: how many there are and the bytes of their values.  gs32_wide: the AMGX_GS_F32_WIDE twin instead (the
+  // fp64 kernels on the rounded values; gs32 stays false)
+  bool gs32 = false, gs32_wide = false;
+  int gs32_images = 0;
+  int64_t gs32_bytes = 0;
   DevGS gs;
   DevGSB gsb;
   DevBGSB bgsb;
@@ -472,16 +486,20 @@ static DownPlan make_down_plan(const DevLevel& L, const DevRestrict& R, int mode
 // The ONLY place where image presence becomes a path -- and a path a launch plan.  Precedence of the down kernels: local window
 // before diagonal image before SELL; of the sweeps: bgsb before gsb before multicolour.  Conditions on call-time arguments (the part
 // of a split level, the fold flag, skip_rsum) stay with the callers.
+static int sweep_path(const DevLevel& L) {
+  if (L.sm_type == AMGX_SM_BGS) return SWEEP_BGS;
+  if (L.sm_type != AMGX_SM_GS) return SWEEP_NONE;
+  if (L.bgsb.on()) return L.bgsb.bc ? SWEEP_BGSB_BC : SWEEP_BGSB;
+  if (L.gsb.on()) return SWEEP_GSB;
+  if (L.gs.n_colors > 0) return L.bs == 1 ? SWEEP_MC : (L.gs.bsell_ok ? SWEEP_MC_BSELL : SWEEP_MC_ROWLIST);
+  return SWEEP_NONE;
+}
 static void resolve_paths(DevLevel& L) {
   LevelPaths p;
   p.plain = L.sm_steps <= 1 && !L.sm_symm;
   // (a level without rows -- a rank that owns nothing -- is trivially folded: every kernel on it is a no-op)
   p.folded = p.plain && L.sm_type == AMGX_SM_JACOBI && (L.n == 0 || (!L.Q.empty() && (L.bs > 1 || !L.Apre.empty() || L.dia.on())));
-  if (L.sm_type == AMGX_SM_BGS) p.sweep = SWEEP_BGS;
-  else if (L.sm_type != AMGX_SM_GS) p.sweep = SWEEP_NONE;
-  else if (L.bgsb.on()) p.sweep = L.bgsb.bc ? SWEEP_BGSB_BC : SWEEP_BGSB;
-  else if (L.gsb.on()) p.sweep = SWEEP_GSB;
-  else if (L.gs.n_colors > 0) p.sweep = L.bs == 1 ? SWEEP_MC : (L.gs.bsell_ok ? SWEEP_MC_BSELL : SWEEP_MC_ROWLIST);
+  p.sweep = sweep_path(L);
   p.in_place = p.sweep != SWEEP_GSB && p.sweep != SWEEP_BGSB;
   p.zero_split = p.bgsb() ? L.bgsb.has_split : p.sweep == SWEEP_GSB ? L.gsb.has_split : p.sweep == SWEEP_MC ? L.gs.has_split : p.sweep == SWEEP_MC_BSELL && L.gs.bsplit;
   p.unit_rows = p.bgsb() ? L.bgsb.BB : p.sweep == SWEEP_GSB ? L.gsb.B : 0;
@@ -1531,12 +1549,15 @@ struct Handle {
     static_assert(NV == 1 || EP != EP_PRE, "EP_PRE is built for single vectors only");
     if (M.n_rows == 0) return;
     if (NV > 1 && sp.part != PART_ALL) throw Err("multi-vector product: rank-partitioned levels are not supported");
-    // the float image exists for non-windowed SELL and BSELL, under EP_RES / EP_CHEB
+    // the float image exists for non-windowed SELL and BSELL, under EP_RES / EP_CHEB; for BSELL also under EP_MULT on one vector
+    // (r = rest x of a Gauss-Seidel block level)
     constexpr bool EP32 = EP == EP_RES || EP == EP_CHEB;
-    const bool f32 = EP32 && sm_pass && M.has32();
+    constexpr bool EP32_BSELL = EP32 || (EP == EP_MULT && NV == 1);
+    const bool f32 = sm_pass && M.has32() && (EP32 || (EP32_BSELL && M.fmt == FMT_BSELL));
     if (f32 && !((M.fmt == FMT_SELL && !M.sell.win) || M.fmt == FMT_BSELL)) throw Err("single-precision image on a format that has none");
-    auto image = [&](const auto& v64, const auto& v32, auto&& run) {          // run(view of the image this product reads)
-      if constexpr (EP32) { if (f32) { run(v32); return; } }
+    // run(view of the image this product reads); has32: a float kernel is instantiated for this format and epilogue
+    auto image = [&](auto has32, const auto& v64, const auto& v32, auto&& run) {
+      if constexpr (decltype(has32)::value) { if (f32) { run(v32); return; } }
       run(v64);
     };
     int64_t a, b;                                     // the units [a, b) of the row split that this launch covers
@@ -1567,7 +1588,7 @@ struct Handle {
       unit_range(sp, WAVE / M.lanes, M.n_slices, a, b);
       if (b <= a) return;
       const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-      image(M.sell.view(), M.sell.view32(M.val32.p), [&](auto V) {
+      image(std::bool_constant<EP32>{}, M.sell.view(), M.sell.view32(M.val32.p), [&](auto V) {
         using T = std::remove_const_t<std::remove_pointer_t<decltype(V.val)>>;       // double / float
         auto run = [&](auto G) {
           if constexpr (NV == 1) launch(sell_spmv_kernel<G(), EP, T>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep);
@@ -1594,7 +1615,8 @@ struct Handle {
       if (b <= a) return;
       const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
       const int xmode = NV == 1 ? knobs.bsell_xmode : 0;       // (the gather variants rearrange loads that the NV > 1 kernel does not have)
-      image(M.bsell.view(xmode), M.bsell.view32(M.val32.p, xmode), [&](auto V) {
+      // (AMGX_GS_F32_WIDE: a smoother pass reads the rounded values at fp64 width)
+      image(std::bool_constant<EP32_BSELL>{}, M.bsell.view_of(sm_pass && M.val64r.p ? M.val64r.p : M.bsell.val.p, xmode), M.bsell.view32(M.val32.p, xmode), [&](auto V) {
         using T = std::remove_const_t<std::remove_pointer_t<decltype(V.val)>>;
         auto run = [&](auto BS) {
           if constexpr (NV == 1) launch(bsell_spmv_kernel<BS(), EP, T>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep);
@@ -1610,22 +1632,23 @@ struct Handle {
       // NV == 1: bcsr_kernel() chooses between the row-lane and the vector form; NV > 1: ONE kernel, W = 4 lane groups per block row
       constexpr bool SQ = EP == EP_JAC || EP == EP_CHEB;
       const BcsrKernel bk = NV == 1 ? bcsr_kernel(M, SQ) : BcsrKernel{true, 4};
+      const double* const mval = sm_pass && M.val64r.p ? M.val64r.p : M.val.p;       // (a smoother pass: the rounded values, see val64r)
       const int key = M.br * 10 + M.bc;
       bool ok = true;
       if (bk.rowlane) {
         auto run = [&](auto KEY) {
           constexpr int BR = KEY() / 10, BC = KEY() % 10;
           if constexpr (NV == 1) {
-            auto run_w = [&](auto W) { launch(bcsr_rowlane_kernel<BR, BC, W(), EP>, rowlane_grid(M.n_rows, BR, W()), BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep); };
+            auto run_w = [&](auto W) { launch(bcsr_rowlane_kernel<BR, BC, W(), EP>, rowlane_grid(M.n_rows, BR, W()), BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, mval, x, y, ep); };
             if (!dispatch<4, 2>(bk.width, run_w)) run_w(Int<1>{});
-          } else launch(bcsr_spmm_kernel<BR, BC, NV, EP, 4>, rowlane_grid(M.n_rows, BR, 4), BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep);
+          } else launch(bcsr_spmm_kernel<BR, BC, NV, EP, 4>, rowlane_grid(M.n_rows, BR, 4), BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, mval, x, y, ep);
         };
         ok = dispatch(std::conditional_t<SQ, SquareShapes, RowlaneShapes>{}, key, run);
       } else if constexpr (NV == 1) {
         const int grid = grid_for(M.n_rows * bk.width);
         auto run = [&](auto KEY) {
           constexpr int BR = KEY() / 10, BC = KEY() % 10;
-          auto run_g = [&](auto G) { launch(bcsrvec_spmv_kernel<BR, BC, G(), EP>, grid, BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep); };
+          auto run_g = [&](auto G) { launch(bcsrvec_spmv_kernel<BR, BC, G(), EP>, grid, BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, mval, x, y, ep); };
           if (!dispatch<2, 4, 8>(bk.width, run_g)) run_g(Int<16>{});
         };
         ok = dispatch(BcsrVecShapes{}, key, run);
@@ -1713,6 +1736,22 @@ struct Handle {
     launch(axpy_kernel, grid_for(n), BLOCK, 0, stream, n, s, x, y);
   }
 
+  // The BSELL images that the sweeps of a Gauss-Seidel block level read: the single-precision ones where mat_f32_image gave the level
+  // the images (DevLevel::gs32), otherwise the fp64 ones.  gs_prec: run(value type); gs_view<T>: the view of image M.
+  // Nothing else is decided at launch time.
+  template <class F>
+  static void gs_prec(const DevLevel& L, F&& run) {
+    if (L.gs32) run(float{});
+    else run(double{});
+  }
+  template <class T>
+  static BSellMatT<T> gs_view(const DevMatrix& M, int xmode) {
+    if constexpr (std::is_same_v<T, float>) {
+      if (M.val32.n != M.bsell.val.n) throw Err("single-precision Gauss-Seidel images: a sweep image has no float twin");
+      return M.bsell.view32(M.val32.p, xmode);
+    } else return M.bsell.view(xmode);
+  }
+
   // one multicolour GS sweep (RHS form), forward: colours ascending, backward: descending
   // cbeg, cend: only the colours [cbeg, cend) (cend < 0: all) -- the stages of the hybrid smoother on rank-partitioned
   // levels are colour ranges (dist.hpp)
@@ -1735,9 +1774,15 @@ struct Handle {
         const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
         if (s1 == s0) continue;
         const int grid = (s1 - s0 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-        const BSellMat BM = (lower_only && g.bsplit) ? g.blower.bsell.view(knobs.bsell_xmode) : g.bcopy.bsell.view(knobs.bsell_xmode);
-        auto run = [&](auto BS) { launch(bgs_bsell_color_kernel<BS()>, grid, BLOCK, 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x); };
-        if (!dispatch<6, 3>(L.bs, run)) run(Int<2>{});               // any other block size: the 2 x 2 kernel
+        const DevMatrix& CM = (lower_only && g.bsplit) ? g.blower : g.bcopy;
+        gs_prec(L, [&](auto prec) {
+          using T = decltype(prec);                                   // double / float
+          const BSellMatT<T> BM = gs_view<T>(CM, knobs.bsell_xmode);
+          auto run = [&](auto BS) { launch(bgs_bsell_color_kernel<BS(), T>, grid, BLOCK, 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x); };
+          if (dispatch<6, 3, 2>(L.bs, run)) return;
+          if (L.gs32) throw Err("single-precision Gauss-Seidel images: unsupported block size " + std::to_string(L.bs));
+          run(Int<2>{});                                             // fp64 image, any other block size: the 2 x 2 kernel
+        });
       } else {
         const int r0 = g.color_row_ptr[c], r1 = g.color_row_ptr[c + 1];
         if (r1 == r0) continue;
@@ -1855,14 +1900,20 @@ struct Handle {
     Range rg("GSS3<bs=" + std::to_string(L.bs) + ">::SmoothRHS");
     const DevBGSB& g = L.bgsb;
     const size_t lds = (size_t)2 * g.BB * L.bs * sizeof(double) + (size_t)g.BB * sizeof(int);
-    // forward: colour phases over the couplings to lower colours, the upper ones stream with the sweep-start values; backward: reversed
-    const BSellMat IN = dir == 0 ? g.in.bsell.view(knobs.bsell_xmode) : g.upin.bsell.view(knobs.bsell_xmode), OTH = dir == 0 ? g.upin.bsell.view(knobs.bsell_xmode) : g.in.bsell.view(knobs.bsell_xmode);
-    auto sweep = [&](auto MODE, const BSellMat& OFF, const int32_t* list, int b0, int nb, const double* x0) {
-      auto run = [&](auto BS) {
-        launch(bgsb_sweep_kernel<BS(), MODE()>, nb, BLOCK, lds, stream, g.BB, b0, list, g.blk_ptr.p, g.blk_rows.p, OFF, g.off_ptr.p, IN, OTH,
-               g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, x0, xout);
-      };
-      if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("block-hybrid Gauss-Seidel: unsupported block size");
+    // the images: fp64, or the single-precision ones of a level that has them (gs_image).  IN / OTH -- forward: colour phases over
+    // the couplings to lower colours, the upper ones stream with the sweep-start values; backward: reversed.  OFF: `off`, or `offlo`
+    // for the block-coloured sweep from zero
+    auto sweep = [&](auto MODE, const DevMatrix& off, const int32_t* list, int b0, int nb, const double* x0) {
+      gs_prec(L, [&](auto prec) {
+        using T = decltype(prec);                                     // double / float
+        const int xm = knobs.bsell_xmode;
+        const BSellMatT<T> OFF = gs_view<T>(off, xm), IN = gs_view<T>(dir == 0 ? g.in : g.upin, xm), OTH = gs_view<T>(dir == 0 ? g.upin : g.in, xm);
+        auto run = [&](auto BS) {
+          launch(bgsb_sweep_kernel<BS(), MODE(), T>, nb, BLOCK, lds, stream, g.BB, b0, list, g.blk_ptr.p, g.blk_rows.p, OFF, g.off_ptr.p, IN, OTH,
+                 g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, x0, xout);
+        };
+        if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("block-hybrid Gauss-Seidel: unsupported block size");
+      });
     };
     if (g.bc) {
       // block-coloured form: one in-place launch per block colour; from zero (xin == nullptr) the first colour reads nothing
@@ -1872,24 +1923,22 @@ struct Handle {
       const bool fz = xin == nullptr;
       if (fz && dir != 0) throw Err("block-coloured Gauss-Seidel: the sweep from zero is a forward sweep");
       if (fz && !L.paths.zero_split) throw Err("block-coloured Gauss-Seidel from zero needs the split images (zero x and sweep in place instead)");
-      const BSellMat OFFA = g.off.bsell.view(knobs.bsell_xmode), OFFL = g.offlo.bsell.view(knobs.bsell_xmode);
       for (int q = 0; q < g.n_bcolors; ++q) {
         const int c = dir ? g.n_bcolors - 1 - q : q;
         const int b0 = g.bc_ptr[c], nb = g.bc_ptr[c + 1] - b0;
         if (nb <= 0) continue;
-        if (!fz) sweep(Int<0>{}, OFFA, g.blk_list.p, b0, nb, xout);
-        else if (q == 0) sweep(Int<1>{}, OFFL, g.blk_list.p, b0, nb, nullptr);
-        else sweep(Int<2>{}, OFFL, g.blk_list.p, b0, nb, xout);
+        if (!fz) sweep(Int<0>{}, g.off, g.blk_list.p, b0, nb, xout);
+        else if (q == 0) sweep(Int<1>{}, g.offlo, g.blk_list.p, b0, nb, nullptr);
+        else sweep(Int<2>{}, g.offlo, g.blk_list.p, b0, nb, xout);
       }
       return;
     }
     if (blk1 < 0 || blk1 > g.n_blocks) blk1 = g.n_blocks;
     if (blk1 <= blk0) return;
     if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
-    const BSellMat OFF = g.off.bsell.view(knobs.bsell_xmode);
     const bool fz = xin == nullptr;
-    if (fz) sweep(Int<1>{}, OFF, nullptr, blk0, blk1 - blk0, xin);
-    else sweep(Int<0>{}, OFF, nullptr, blk0, blk1 - blk0, xin);
+    if (fz) sweep(Int<1>{}, g.off, nullptr, blk0, blk1 - blk0, xin);
+    else sweep(Int<0>{}, g.off, nullptr, blk0, blk1 - blk0, xin);
   }
 
   // ---- Gauss-Seidel sweeps of square-block levels on NV = 2, 4 interleaved vectors (AMGX_MULTI_FUSE_GS_BLOCK, DESIGN.md 5.16;
@@ -1897,6 +1946,7 @@ struct Handle {
   // (Multi::decide_gs_block, amgx_smooth_multi); multi_sweep_ok above keeps the answer of AMGX_MULTI_FUSE_GS.
   bool multi_block_sweep_ok(const DevLevel& L) const {
     if (L.sm_type != AMGX_SM_GS || (L.bs != 2 && L.bs != 3 && L.bs != 6) || L.n != L.ncols || !L.paths.plain) return false;
+    if (L.gs32 || L.gs32_wide) return false;           // single-precision images: the NV kernels read fp64 images
     switch (L.paths.sweep) {
       case SWEEP_BGSB: case SWEEP_BGSB_BC: case SWEEP_MC_BSELL: case SWEEP_MC_ROWLIST: return true;
       default: return false;
@@ -2042,14 +2092,16 @@ struct Handle {
   }
   // r = b - A x right after sweep_from_zero(L, x, b, r), by the identity the level's images allow (x may carry ghost entries)
   void residual_after_zero(const DevLevel& L, const double* x, const double* b, double* r) {
-    if (!L.paths.zero_split) { residual(L.A, x, b, r); return; }
+    if (!L.paths.zero_split) { residual_sm(L, x, b, r); return; }
     switch (L.paths.sweep) {
       case SWEEP_GSB:
         // inside a block only couplings to lower colours contributed; (b - L_in x)_k = x_k / dinv_k on every swept row, hence
         // r = b - A x = (1/dinv - a_kk) .* x - (A - L_in - D) x = c .* x - rest x
         product<1, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
         return;
-      case SWEEP_BGSB: case SWEEP_BGSB_BC: mult(L.bgsb.rest, x, r); return;        // r = rest x (see DevBGSB)
+      case SWEEP_BGSB: case SWEEP_BGSB_BC:                                          // r = rest x (see DevBGSB), a smoother pass
+        product<1, EP_MULT>(L.bgsb.rest, x, r, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}, Span(), L.gs32);
+        return;
       case SWEEP_MC: {
         // b - L x - D x = 0 on every swept row, hence r = -U x (r on non-free rows is not needed: their prolongation rows are empty)
         const DevGS& g = L.gs;
@@ -2063,9 +2115,14 @@ struct Handle {
         const DevGS& g = L.gs;
         const int ns = g.bupper.n_slices;
         const int grid = (ns + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-        const BSellMat UM = g.bupper.bsell.view(knobs.bsell_xmode);
-        auto run = [&](auto BS) { launch(bgs_bsell_upper_residual_kernel<BS()>, grid, BLOCK, 0, stream, ns, UM, g.rowid.p, x, r); };
-        if (!dispatch<6, 3>(L.bs, run)) run(Int<2>{});                 // any other block size: the 2 x 2 kernel
+        gs_prec(L, [&](auto prec) {
+          using T = decltype(prec);                                     // double / float
+          const BSellMatT<T> UM = gs_view<T>(g.bupper, knobs.bsell_xmode);
+          auto run = [&](auto BS) { launch(bgs_bsell_upper_residual_kernel<BS(), T>, grid, BLOCK, 0, stream, ns, UM, g.rowid.p, x, r); };
+          if (dispatch<6, 3, 2>(L.bs, run)) return;
+          if (L.gs32) throw Err("single-precision Gauss-Seidel images: unsupported block size " + std::to_string(L.bs));
+          run(Int<2>{});                                               // fp64 image, any other block size: the 2 x 2 kernel
+        });
         return;
       }
       default: throw Err("residual_after_zero: the level's sweep form has no split identity");
@@ -2118,6 +2175,11 @@ struct Handle {
         copy(L.tmp.p, x, L.ext_len());       // (out of place: the off-block values are those from the start of the sweep)
         sweep(L, dir, L.tmp.p, x, b);
       }
+      // The residual of an iterate that a further correction will use (W / BS cycles, ProxySmoother chains, amgx_smooth) reads the fp64
+      // A also on a level with single-precision Gauss-Seidel images: x is close to the solution there, b - A x cancels,
+      // and a residual formed with the rounded A would steer the next correction towards the solution of the ROUNDED system -- a shift of
+      // cond(A) * 6e-8 in the cycle's result (measured: 3.4e-6 in the W-cycle of a 40 x 36 elasticity grid against 5e-8 in its V-cycle).
+      // The residual right after the sweep from zero (residual_after_zero: |r| ~ |b|, nothing cancels) reads the float images.
       if (update_res) residual(L.A, x, b, res);
     }
   }
@@ -2325,6 +2387,7 @@ struct Handle {
     DevLevel& L = lev[l];
     const LevelPaths& P = L.paths;
     const bool probe = probe_level == l && probe_kind == 9 && probe_e0;
+    const bool probe_blk = probe_level == l && probe_kind == 11 && probe_e0;     // amgx_time_op op 11: the block sweep
     if (fold && !L.QLW.empty()) {
       // local-window form of Q: the coarse values a window needs are staged in LDS (sell_lw_win_spmv_kernel); interior / boundary
       // window ranges on rank-partitioned levels (the list of an interior window holds owned coarse columns only)
@@ -2349,10 +2412,10 @@ struct Handle {
     } else if (P.plain && P.hybrid() && (P.sweep != SWEEP_GSB || L.n == L.ncols)) {
       double* const t = P.in_place ? x : L.tmp.p;
       mult_add(L.P, 1.0, xc, x, t);        // t = x + P x_c
-      probed(probe, [&] { sweep(L, 1, t, x, b); });               // backward sweep, t -> x: ONE launch, or one per block colour in place
+      probed(probe || (probe_blk && P.bgsb()), [&] { sweep(L, 1, t, x, b); });      // backward sweep, t -> x: ONE launch, or one per block colour in place
     } else {
       add_c2f(l, 1.0, x, xc);
-      level_smooth(L, 1, x, b, r, false, false, false);
+      probed(probe_blk && P.plain, [&] { level_smooth(L, 1, x, b, r, false, false, false); });    // (plain, no residual: the sweep alone)
     }
   }
 
@@ -3216,6 +3279,7 @@ int amgx_level_extra(amgx_handle hh, int level, int64_t* out, int n_out) {
     if (!L.A.empty() && L.A.fmt == amgx::FMT_SELL) v[5] = L.A.sell.diag_first;
     if (!L.Apre.empty() && L.Apre.fmt == amgx::FMT_SELL) { v[6] = L.Apre.sell.diag_first; v[7] = L.Apre.sell.wdiag; }
     v[8] = (int64_t)h.graphs.size();
+    v[9] = L.gs32 ? 1 : 0; v[10] = L.gs32_images; v[11] = L.gs32_bytes;
     for (int k = 0; k < std::min(n_out, AMGX_LEVEL_EXTRA_N); ++k) out[k] = v[k];
   });
 }
@@ -3248,13 +3312,20 @@ int amgx_time_op(amgx_handle hh, int level, int op, int reps, double* avg_ms) {
         default: throw amgx::Err("amgx_time_op: unknown op");
       }
     };
-    if (op == 8 || op == 9) {
+    // op 11: a square-block Gauss-Seidel level that the V-cycle sweeps with separate launches (not folded, not collapsed)
+    const int sw = L.paths.sweep;
+    const bool block_sweep_in_cycle = has_c && L.paths.plain && L.sm_type == AMGX_SM_GS && L.bs > 1 && L.n == L.ncols && !L.paths.folded &&
+                                      (L.paths.bgsb() || sw == amgx::SWEEP_MC_BSELL || sw == amgx::SWEEP_MC_ROWLIST) &&
+                                      h.cycle == AMGX_CYCLE_V && (h.dense_level < 0 || level < h.dense_level);
+    if (op == 8 || op == 9 || op == 11) {
       // the dominant kernel timed where it runs: inside the cycle, between the previous cycle's last kernel and the
       // partial-sum reduction (cache state and clocks of the real application), averaged over `reps` cycles
       if (op == 8 && !(L.plan_rf.on && L.plan_rf.mode == 0)) throw amgx::Err("amgx_time_op: level has no fused pre-smoothing + restriction kernel");
       if (op == 9 && !(has_c && L.paths.plain && L.paths.hybrid() && L.n == L.ncols && !L.paths.folded))
         throw amgx::Err("amgx_time_op: level has no block-hybrid Gauss-Seidel sweep");
-      if (h.stream == nullptr) throw amgx::Err("amgx_time_op: op 8 needs a non-default stream");
+      if (op == 11 && !block_sweep_in_cycle)
+        throw amgx::Err("amgx_time_op: level has no block Gauss-Seidel sweep in the cycle");
+      if (h.stream == nullptr) throw amgx::Err("amgx_time_op: ops 8, 9 and 11 need a non-default stream");
       amgx::Handle::ProbeScope probe(h, op);
       double tot = 0.0;
       if (h.lev[0].len()) amgx::launch(amgx::fill_kernel, amgx::Handle::grid_for(h.lev[0].len()), amgx::BLOCK, 0, h.stream, h.lev[0].len(), (uint64_t)2, h.lev[0].rhs.p);

@@ -57,8 +57,12 @@ static void check_level(LevelBuild& B) {
   if (B.smoothed()) {
     if (s.mat_prec != AMGX_PREC_F64 && s.mat_prec != AMGX_PREC_F32)
       throw Err("amgx_create: level " + std::to_string(B.l) + ": mat_prec must be AMGX_PREC_F64 (0) or AMGX_PREC_F32 (1), got " + std::to_string(s.mat_prec));
-    if (s.mat_prec == AMGX_PREC_F32 && s.sm_type != AMGX_SM_CHEBY)
-      throw Err("amgx_create: level " + std::to_string(B.l) + ": mat_prec = AMGX_PREC_F32 is available on Chebyshev levels (sm_type = AMGX_SM_CHEBY) only");
+    // (a scalar Gauss-Seidel level has no form with single-precision images: the request stays the error it was)
+    if (s.mat_prec == AMGX_PREC_F32 && s.sm_type != AMGX_SM_CHEBY && !(s.sm_type == AMGX_SM_GS && s.A.br > 1))
+      throw Err("amgx_create: level " + std::to_string(B.l) + ": mat_prec = AMGX_PREC_F32 is available on Chebyshev levels (sm_type = AMGX_SM_CHEBY) "
+                "and on square-block Gauss-Seidel levels (sm_type = AMGX_SM_GS, block size > 1) only");
+    if (s.mat_prec == AMGX_PREC_F32 && s.A.n_cols != s.A.n_rows)
+      throw Err("amgx_create: level " + std::to_string(B.l) + ": mat_prec = AMGX_PREC_F32 is not available on rank-partitioned levels");
   }
   check_matrix(s.A, "A");            // (before anything reads rowptr[n_rows]: a NULL / garbage descriptor is an error, not a crash)
 }
@@ -464,25 +468,83 @@ static void cheb_fused_restrict(LevelBuild& B) {
   }
 }
 
-// Chebyshev levels with mat_prec = AMGX_PREC_F32: the single-precision image of A -- the value array of the level's
-// image rounded to float on the device, every index array shared.  From here on every smoother pass of the level (the EP_CHEB steps,
-// update_res, the residual before the restriction incl. its fused form) reads it; amgx_matvec, amgx_residual, the Krylov operator and
-// the lambda_max estimate keep the fp64 image.  Which levels get one is decided HERE and nowhere else:
-//   plain sliced-ELL (any lanes per row) and BSELL (2x2, 3x3, 6x6) -- the formats of the levels that carry bytes; CSR-vector,
-//   windowed SELL and block CSR levels (small / irregular) stay fp64 silently.
+// Levels with mat_prec = AMGX_PREC_F32: the single-precision images -- the value array of an image rounded to
+// float on the device, every index array shared.  Which levels and which images get one is decided HERE and nowhere else:
+//   Chebyshev levels: A in plain sliced-ELL (any lanes per row) or BSELL (2x2, 3x3, 6x6) -- the formats of the levels that carry bytes;
+//     CSR-vector, windowed SELL and block CSR levels (small / irregular) stay fp64 silently.  From here on every smoother pass of the
+//     level (the EP_CHEB steps, update_res, the residual before the restriction incl. its fused form) reads it.
+//   Gauss-Seidel levels whose sweep form is hybrid-block, block-coloured or multicolour BSELL (SWEEP_BGSB, SWEEP_BGSB_BC,
+//     SWEEP_MC_BSELL; 2x2, 3x3, 6x6): every BSELL image the level has of bgsb.off / in / upin / rest / offlo or gs.bcopy / blower /
+//     bupper, and A itself where it is BSELL (an A that stayed in block CSR -- a small level -- gets its rounded values at fp64
+//     width, DevMatrix::val64r, so that sweeps and residual see one operator).  The sweeps and the residual after the sweep from zero
+//     (its split identities and the unsplit product with A) read them (DevLevel::gs32); update_res of a general sweep reads the
+//     fp64 A (Handle::base_smooth says why).  Every other Gauss-Seidel form (scalar levels, the row list over block CSR) stays
+//     fp64 silently.  No class of images is excluded: see DESIGN.md 6 for what was measured and what was not.
+//     AMGX_GS_F32_WIDE=1 (A/B twin): no float images; the rounded values are written back into the fp64 arrays of exactly these
+//     images (A: into DevMatrix::val64r, its true values stay) and the fp64 kernels run -- same bits, fp64 bytes.
+// amgx_matvec, amgx_residual, the Krylov operator and the lambda_max estimate keep the fp64 image of A.
+// A value that rounds to +-inf is an error that names the level; nothing half-built is left behind.
 // AMGX_NO_MAT_F32=1 ignores every request (the handle is then the double handle, bit for bit).
 static void mat_f32_image(LevelBuild& B) {
   const amgx_level_desc& s = B.s;
   DevLevel& L = B.L;
-  if (!B.smoothed() || s.mat_prec != AMGX_PREC_F32 || s.sm_type != AMGX_SM_CHEBY || B.K.no_mat_f32) return;
-  const bool sell = L.A.fmt == FMT_SELL && !L.A.sell.win;
-  const bool bsell = L.A.fmt == FMT_BSELL && (L.A.br == 2 || L.A.br == 3 || L.A.br == 6);
-  if (!sell && !bsell) return;
-  const int64_t bad = dev_round_to_f32(sell ? L.A.sell.val : L.A.bsell.val, L.A.val32);
-  if (bad) {
-    L.A.val32.release();
-    throw Err("amgx_create: level " + std::to_string(B.l) + ": " + std::to_string(bad) + " value(s) of A are beyond the range of single precision (mat_prec = AMGX_PREC_F32)");
+  if (!B.smoothed() || s.mat_prec != AMGX_PREC_F32 || B.K.no_mat_f32) return;
+  auto beyond = [&](int64_t bad, const char* what) {
+    return Err("amgx_create: level " + std::to_string(B.l) + ": " + std::to_string(bad) + " value(s) of " + what +
+               " are beyond the range of single precision (mat_prec = AMGX_PREC_F32)");
+  };
+  if (s.sm_type == AMGX_SM_CHEBY) {
+    const bool sell = L.A.fmt == FMT_SELL && !L.A.sell.win;
+    const bool bsell = L.A.fmt == FMT_BSELL && (L.A.br == 2 || L.A.br == 3 || L.A.br == 6);
+    if (!sell && !bsell) return;
+    const int64_t bad = dev_round_to_f32(sell ? L.A.sell.val : L.A.bsell.val, L.A.val32);
+    if (bad) {
+      L.A.val32.release();
+      throw beyond(bad, "A");
+    }
+    return;
   }
+  if (s.sm_type != AMGX_SM_GS || (L.bs != 2 && L.bs != 3 && L.bs != 6)) return;
+  const int form = sweep_path(L);
+  if (form != SWEEP_BGSB && form != SWEEP_BGSB_BC && form != SWEEP_MC_BSELL) return;
+  // the images the level's form reads (an image the level does not have is empty: no slices, no values)
+  std::vector<DevMatrix*> sweep_only;
+  if (form == SWEEP_MC_BSELL) sweep_only = {&L.gs.bcopy, &L.gs.blower, &L.gs.bupper};
+  else sweep_only = {&L.bgsb.off, &L.bgsb.in, &L.bgsb.upin, &L.bgsb.rest, &L.bgsb.offlo};
+  const bool wide = B.K.gs_f32_wide;
+  auto undo = [&] {
+    for (DevMatrix* M : sweep_only) M->val32.release();
+    L.A.val32.release(); L.A.val64r.release();
+    L.gs32 = L.gs32_wide = false; L.gs32_images = 0; L.gs32_bytes = 0;
+  };
+  // (the range check comes first, on A: every image holds values of A or, in `rest`, diagonal blocks scaled by a factor in [0, 1].
+  // The wide twin overwrites the sweep images, so it must not start before the level is known to be representable)
+  auto one = [&](DevMatrix& M, const char* what, bool keep64) {
+    if (keep64 && M.fmt == FMT_CSRVEC && M.br > 1 && M.val.n > 0) {        // A in block CSR: rounded values at fp64 width, no float image
+      const int64_t bad = dev_round_to_f32_wide(M.val, M.val64r);
+      if (bad) { undo(); throw beyond(bad, what); }
+      return;
+    }
+    if (M.fmt != FMT_BSELL || M.bsell.val.n == 0) return;
+    int64_t bad;
+    if (!wide) bad = dev_round_to_f32(M.bsell.val, M.val32);
+    else if (keep64) bad = dev_round_to_f32_wide(M.bsell.val, M.val64r);
+    else bad = dev_round_to_f32_wide(M.bsell.val, M.bsell.val);
+    if (bad) { undo(); throw beyond(bad, what); }
+    L.gs32_images += 1;
+    L.gs32_bytes += (wide ? 8 : 4) * (int64_t)M.bsell.val.n;
+  };
+  if (wide) {                     // a dry run on the values of A decides before anything is overwritten
+    DevBuf<float> probe;
+    const DevBuf<double>& av = L.A.fmt == FMT_BSELL ? L.A.bsell.val : L.A.val;
+    const int64_t bad = dev_round_to_f32(av, probe);
+    if (bad) throw beyond(bad, "A");
+  }
+  one(L.A, "A", true);
+  static const char* names_mc[] = {"the colour-major copy of A", "its lower part", "its upper part"};
+  static const char* names_hb[] = {"the image `off`", "the image `in`", "the image `upin`", "the image `rest`", "the image `offlo`"};
+  for (size_t i = 0; i < sweep_only.size(); ++i) one(*sweep_only[i], form == SWEEP_MC_BSELL ? names_mc[i] : names_hb[i], false);
+  (wide ? L.gs32_wide : L.gs32) = true;
 }
 
 // workgroup -> rows mapping of the streaming kernels on this level (SellMat::xcd)

@@ -409,6 +409,15 @@ __global__ __launch_bounds__(BLOCK) void db_to_f32_kernel(int64_t n, const doubl
   if (!isfinite(v)) atomicAdd(n_bad, 1u);
 }
 
+// the same rounding at fp64 width (AMGX_GS_F32_WIDE): dst = (double)(float)src; dst may be src
+__global__ __launch_bounds__(BLOCK) void db_round_f32_wide_kernel(int64_t n, const double* src, double* dst, unsigned int* __restrict__ n_bad) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const float v = (float)src[i];
+  dst[i] = (double)v;
+  if (!isfinite(v)) atomicAdd(n_bad, 1u);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // host side
 
@@ -421,6 +430,20 @@ static int64_t dev_round_to_f32(const DevBuf<double>& src, DevBuf<float>& dst) {
   bad.alloc(1);
   HIPCHK(hipMemset(bad.p, 0, sizeof(unsigned int)));
   launch(db_to_f32_kernel, (unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, 0, n, src.p, dst.p, bad.p);
+  unsigned int h = 0;
+  HIPCHK(hipMemcpy(&h, bad.p, sizeof(h), hipMemcpyDeviceToHost));
+  return (int64_t)h;
+}
+
+// ... and the rounded values at fp64 width; dst may be src itself (in place), otherwise it is allocated here
+static int64_t dev_round_to_f32_wide(const DevBuf<double>& src, DevBuf<double>& dst) {
+  const int64_t n = (int64_t)src.n;
+  if (&dst != &src) dst.alloc(src.n);
+  if (n == 0) return 0;
+  DevBuf<unsigned int> bad;
+  bad.alloc(1);
+  HIPCHK(hipMemset(bad.p, 0, sizeof(unsigned int)));
+  launch(db_round_f32_wide_kernel, (unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, 0, n, (const double*)src.p, dst.p, bad.p);
   unsigned int h = 0;
   HIPCHK(hipMemcpy(&h, bad.p, sizeof(h), hipMemcpyDeviceToHost));
   return (int64_t)h;

@@ -1071,8 +1071,9 @@ __global__ __launch_bounds__(BLOCK) void bgs_color_kernel(int list_begin, int li
 // streams in aligned 1 KiB chunks like bsell_spmv_kernel (the CSR row-list kernel above reads 8-byte elements at block
 // strides: 2-3 TB/s).  x_B += Dinv_B (b_B - A_B: x), the block solve goes through wave shuffles.  rowid[slot] = block row
 // (or -1: padding).  In place: rows of one colour are not coupled, a block row is read and written by one lane group.
-template <int BS>
-__global__ __launch_bounds__(BLOCK) void bgs_bsell_color_kernel(int slice_begin, int slice_end, BSellMat M,
+// V = float: the same kernel on the single-precision image of the copy (values widened where they are multiplied).
+template <int BS, class V = double>
+__global__ __launch_bounds__(BLOCK) void bgs_bsell_color_kernel(int slice_begin, int slice_end, BSellMatT<V> M,
                                                                 const int32_t* __restrict__ rowid, const double* __restrict__ dinv,
                                                                 const double* __restrict__ b, double* x) {
   constexpr int RB = WAVE / BS;
@@ -1085,7 +1086,7 @@ __global__ __launch_bounds__(BLOCK) void bgs_bsell_color_kernel(int slice_begin,
   const bool active = lane < RB * BS && brow >= 0;
   const int64_t k0 = M.slice_ptr[s];
   const int w = (int)(M.slice_ptr[s + 1] - k0);
-  const double* __restrict__ vb = M.val + k0 * (BS * WAVE);
+  const V* __restrict__ vb = M.val + k0 * (BS * WAVE);
   const int32_t* __restrict__ cb = M.col + k0 * RB;
   const int64_t i = (int64_t)(brow >= 0 ? brow : 0) * BS + r;
   double bv = 0.0, od[BS];
@@ -1101,13 +1102,14 @@ __global__ __launch_bounds__(BLOCK) void bgs_bsell_color_kernel(int slice_begin,
   for (int k = 0; k < w; ++k) {
     const int c = cb[k * RB + rbl];
     const double* xv = x + (int64_t)c * BS;
-    const double* __restrict__ vk = vb + (int64_t)k * (BS * WAVE);
+    const V* __restrict__ vk = vb + (int64_t)k * (BS * WAVE);
 #pragma unroll
     for (int cp = 0; cp < BS / 2; ++cp) {
-      const double v0 = ld_nt(vk + cp * (2 * WAVE) + lane * 2), v1 = ld_nt(vk + cp * (2 * WAVE) + lane * 2 + 1);
-      acc += v0 * xv[2 * cp] + v1 * xv[2 * cp + 1];
+      V v0, v1;
+      ld_nt_pair(vk + cp * (2 * WAVE) + lane * 2, v0, v1);
+      acc += (double)v0 * xv[2 * cp] + (double)v1 * xv[2 * cp + 1];
     }
-    if (BS & 1) acc += ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xv[BS - 1];
+    if (BS & 1) acc += (double)ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xv[BS - 1];
   }
   const double t = active ? bv - acc : 0.0;
   const int base = lane - r;
@@ -1118,9 +1120,9 @@ __global__ __launch_bounds__(BLOCK) void bgs_bsell_color_kernel(int slice_begin,
 }
 
 // r_B = -(U x)_B on the colour-major block rows after a forward sweep from x = 0 (see gs_upper_residual_kernel); M holds
-// the couplings to higher colours only, one launch over all colours
-template <int BS>
-__global__ __launch_bounds__(BLOCK) void bgs_bsell_upper_residual_kernel(int n_slices, BSellMat M, const int32_t* __restrict__ rowid,
+// the couplings to higher colours only, one launch over all colours (V = float: its single-precision image)
+template <int BS, class V = double>
+__global__ __launch_bounds__(BLOCK) void bgs_bsell_upper_residual_kernel(int n_slices, BSellMatT<V> M, const int32_t* __restrict__ rowid,
                                                                          const double* __restrict__ x, double* __restrict__ r) {
   constexpr int RB = WAVE / BS;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -1132,20 +1134,21 @@ __global__ __launch_bounds__(BLOCK) void bgs_bsell_upper_residual_kernel(int n_s
   const bool active = lane < RB * BS && brow >= 0;
   const int64_t k0 = M.slice_ptr[s];
   const int w = (int)(M.slice_ptr[s + 1] - k0);
-  const double* __restrict__ vb = M.val + k0 * (BS * WAVE);
+  const V* __restrict__ vb = M.val + k0 * (BS * WAVE);
   const int32_t* __restrict__ cb = M.col + k0 * RB;
   double acc = 0.0;
 #pragma unroll 2
   for (int k = 0; k < w; ++k) {
     const int c = cb[k * RB + rbl];
     const double* xv = x + (int64_t)c * BS;
-    const double* __restrict__ vk = vb + (int64_t)k * (BS * WAVE);
+    const V* __restrict__ vk = vb + (int64_t)k * (BS * WAVE);
 #pragma unroll
     for (int cp = 0; cp < BS / 2; ++cp) {
-      const double v0 = ld_nt(vk + cp * (2 * WAVE) + lane * 2), v1 = ld_nt(vk + cp * (2 * WAVE) + lane * 2 + 1);
-      acc += v0 * xv[2 * cp] + v1 * xv[2 * cp + 1];
+      V v0, v1;
+      ld_nt_pair(vk + cp * (2 * WAVE) + lane * 2, v0, v1);
+      acc += (double)v0 * xv[2 * cp] + (double)v1 * xv[2 * cp + 1];
     }
-    if (BS & 1) acc += ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xv[BS - 1];
+    if (BS & 1) acc += (double)ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xv[BS - 1];
   }
   if (active) r[(int64_t)brow * BS + rr] = -acc;
 }
@@ -1175,11 +1178,13 @@ __global__ __launch_bounds__(BLOCK) void bgs_bsell_upper_residual_kernel(int n_s
 // (xin == xout) and a block reads the new values of every block swept before it -- Gauss-Seidel between the blocks as well as
 // inside them, i.e. exact Gauss-Seidel in the order (block colour, block, in-block colour), instead of the hybrid form's frozen
 // couplings.  PCG at 30^3 nodes: 15 iterations (sequential order 16, hybrid line blocks 19).
-template <int BS, int MODE>
+// V = float: OFF, IN and OTH are the single-precision images: the same index arrays, ONE 8-byte load per value pair,
+// widened where it is multiplied; dinv, x, b, the LDS contents and the order of additions are those of V = double.
+template <int BS, int MODE, class V = double>
 __global__ __launch_bounds__(BLOCK) void bgsb_sweep_kernel(int BB, int block0, const int32_t* __restrict__ blk_list,
                                                            const int32_t* __restrict__ blk_ptr, const int32_t* __restrict__ blk_rows,
-                                                           BSellMat OFF, const int32_t* __restrict__ off_ptr,
-                                                           BSellMat IN, BSellMat OTH, const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_row,
+                                                           BSellMatT<V> OFF, const int32_t* __restrict__ off_ptr,
+                                                           BSellMatT<V> IN, BSellMatT<V> OTH, const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_row,
                                                            int n_colors, int dir, const double* __restrict__ dinv, const double* __restrict__ b,
                                                            const double* xin, double* xout) {
   constexpr bool FROM_ZERO = MODE != 0;
@@ -1210,7 +1215,7 @@ __global__ __launch_bounds__(BLOCK) void bgsb_sweep_kernel(int BB, int block0, c
       const bool active = lane_on && lrow < nb;
       const int64_t k0 = OFF.slice_ptr[s];
       const int w = (int)(OFF.slice_ptr[s + 1] - k0);
-      const double* __restrict__ vb = OFF.val + k0 * (BS * WAVE);
+      const V* __restrict__ vb = OFF.val + k0 * (BS * WAVE);
       const int32_t* __restrict__ cb = OFF.col + k0 * RB;
       double acc = 0.0;
       if (OFF.xmode >= 3) {
@@ -1245,20 +1250,21 @@ __global__ __launch_bounds__(BLOCK) void bgsb_sweep_kernel(int BB, int block0, c
       const bool active = lane_on && lrow >= 0;
       const int64_t k0 = OTH.slice_ptr[s];
       const int w = (int)(OTH.slice_ptr[s + 1] - k0);
-      const double* __restrict__ vb = OTH.val + k0 * (BS * WAVE);
+      const V* __restrict__ vb = OTH.val + k0 * (BS * WAVE);
       const int32_t* __restrict__ cb = OTH.col + k0 * RB;
       double acc = 0.0;
 #pragma unroll 2
       for (int k = 0; k < w; ++k) {
         const int cl = cb[k * RB + rbl];
         const double* xv = xs + cl * BS;
-        const double* __restrict__ vk = vb + (int64_t)k * (BS * WAVE);
+        const V* __restrict__ vk = vb + (int64_t)k * (BS * WAVE);
 #pragma unroll
         for (int cp = 0; cp < BS / 2; ++cp) {
-          const double v0 = ld_nt(vk + cp * (2 * WAVE) + lane * 2), v1 = ld_nt(vk + cp * (2 * WAVE) + lane * 2 + 1);
-          acc += v0 * xv[2 * cp] + v1 * xv[2 * cp + 1];
+          V v0, v1;
+          ld_nt_pair(vk + cp * (2 * WAVE) + lane * 2, v0, v1);
+          acc += (double)v0 * xv[2 * cp] + (double)v1 * xv[2 * cp + 1];
         }
-        if (BS & 1) acc += ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xv[BS - 1];
+        if (BS & 1) acc += (double)ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xv[BS - 1];
       }
       if (active) bsh[lrow * BS + r] -= acc;
     }
@@ -1272,7 +1278,7 @@ __global__ __launch_bounds__(BLOCK) void bgsb_sweep_kernel(int BB, int block0, c
       const bool active = lane_on && lrow >= 0;
       const int64_t k0 = IN.slice_ptr[s];
       const int w = (int)(IN.slice_ptr[s + 1] - k0);
-      const double* __restrict__ vb = IN.val + k0 * (BS * WAVE);
+      const V* __restrict__ vb = IN.val + k0 * (BS * WAVE);
       const int32_t* __restrict__ cb = IN.col + k0 * RB;
       double od[BS];
 #pragma unroll
@@ -1282,13 +1288,14 @@ __global__ __launch_bounds__(BLOCK) void bgsb_sweep_kernel(int BB, int block0, c
       for (int k = 0; k < w; ++k) {
         const int cl = cb[k * RB + rbl];
         const double* xv = xs + cl * BS;
-        const double* __restrict__ vk = vb + (int64_t)k * (BS * WAVE);
+        const V* __restrict__ vk = vb + (int64_t)k * (BS * WAVE);
 #pragma unroll
         for (int cp = 0; cp < BS / 2; ++cp) {
-          const double v0 = ld_nt(vk + cp * (2 * WAVE) + lane * 2), v1 = ld_nt(vk + cp * (2 * WAVE) + lane * 2 + 1);
-          acc += v0 * xv[2 * cp] + v1 * xv[2 * cp + 1];
+          V v0, v1;
+          ld_nt_pair(vk + cp * (2 * WAVE) + lane * 2, v0, v1);
+          acc += (double)v0 * xv[2 * cp] + (double)v1 * xv[2 * cp + 1];
         }
-        if (BS & 1) acc += ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xv[BS - 1];
+        if (BS & 1) acc += (double)ld_nt(vk + (BS / 2) * (2 * WAVE) + lane) * xv[BS - 1];
       }
       const double t = active ? bsh[lrow * BS + r] - acc : 0.0;
       const int base = lane - r;

@@ -80,8 +80,9 @@ struct Knobs {
   bool gsb_no_narrow = false;           // AMGX_GSB_NO_NARROW: the sweep from zero takes the general kernel (kill switch)
   bool gsb_no_mid = false;              // AMGX_GSB_NO_MID: the general sweep never takes the mid-width kernel (kill switch)
   bool bgsb_no_split = false;           // AMGX_BGSB_NO_SPLIT: square-block hybrid levels without the split (kill switch)
-  // ---- Chebyshev levels
+  // ---- single-precision matrix images (Chebyshev levels, Gauss-Seidel block levels)
   bool no_mat_f32 = false;              // AMGX_NO_MAT_F32: mat_prec = AMGX_PREC_F32 is ignored, no single-precision image (kill switch)
+  bool gs_f32_wide = false;             // AMGX_GS_F32_WIDE: Gauss-Seidel levels keep fp64 images that hold the rounded values (A/B hook)
   // ---- epilogues, coarse end of the cycle
   bool no_ep_nt = false;                // AMGX_NO_EP_NT: no non-temporal epilogue operands (kill switch)
   bool no_ep_hoist = false;             // AMGX_NO_EP_HOIST: epilogue operands are not loaded ahead of the row product (kill switch)
@@ -161,6 +162,7 @@ struct Knobs {
     k.gsb_no_mid = on("AMGX_GSB_NO_MID");
     k.bgsb_no_split = on("AMGX_BGSB_NO_SPLIT");
     k.no_mat_f32 = on("AMGX_NO_MAT_F32");
+    k.gs_f32_wide = on("AMGX_GS_F32_WIDE");
     k.no_ep_nt = on("AMGX_NO_EP_NT");
     k.no_ep_hoist = on("AMGX_NO_EP_HOIST");
     k.no_dense_tail = on("AMGX_NO_DENSE_TAIL");

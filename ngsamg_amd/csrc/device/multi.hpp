@@ -186,6 +186,8 @@ struct Multi {
       if (V.n != V.ncols) { s.why_b = "ghost columns" + at; return; }
       if (h.permuted(l)) { s.why_b = "renumbered level" + at; return; }
       if (gs && V.n > 0) {
+        // (the fused sweeps read fp64 images: the column loop keeps a column equal to amgx_apply, bit for bit)
+        if (V.gs32 || V.gs32_wide) { s.why_b = "single-precision Gauss-Seidel images" + at; return; }
         if (!(V.bs == 1 ? h.multi_sweep_ok(V) : h.multi_block_sweep_ok(V))) { s.why_b = "Gauss-Seidel sweep form without a multi-vector kernel" + at; return; }
         if (V.bs != 1 && !h.multi_block_sweep_fits(V)) { s.why_b = "sweep block too large for the multi-vector sweep" + at; return; }
       }

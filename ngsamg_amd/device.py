@@ -49,13 +49,17 @@ def cheby_args(degree, ratio, lambda_max, i=0, n=1):
     return deg, lam, rat
 
 
-_PREC = {"double": _lib.AMGX_PREC_F64, "single": _lib.AMGX_PREC_F32}
+_PREC = {"double": _lib.AMGX_PREC_F64, "single": _lib.AMGX_PREC_F32, "single_gs": _lib.AMGX_PREC_F32}
+# the smoother types a value of mat_prec applies to
+_PREC_TYPES = {"single": ("cheby",), "single_gs": ("cheby", "gs", "hgs")}
 
 
 def mat_prec_levels(mat_prec, types):
     """amgx_level_desc.mat_prec of every level for the smoother types `types` (one per level, the last = the coarsest, which
-    ignores the field).  mat_prec: "double", "single" or a per-level list of the two.  A scalar "single" applies to the
-    Chebyshev levels and needs at least one; a list may say "single" on Chebyshev levels only."""
+    ignores the field).  mat_prec: "double", "single", "single_gs" or a per-level list of them.  A scalar "single" applies to the
+    Chebyshev levels and needs at least one; a list may say "single" on Chebyshev levels only.  "single_gs"
+    applies to the Chebyshev and the Gauss-Seidel ("gs", "hgs") levels in the same way (on a Gauss-Seidel level
+    the images of the block sweeps; a level whose sweep form has none stays fp64)."""
     n = len(types)
     per_level = isinstance(mat_prec, (list, tuple))
     vals = list(mat_prec) if per_level else [mat_prec] * n
@@ -63,18 +67,24 @@ def mat_prec_levels(mat_prec, types):
         raise NgsAMGError("mat_prec list must have one entry per level")
     for v in vals:
         if not isinstance(v, str) or v not in _PREC:
-            raise NgsAMGError(f"unknown mat_prec {v!r} (double | single)")
+            raise NgsAMGError(f"unknown mat_prec {v!r} (double | single | single_gs)")
     out = [0] * n
     for i in (range(n - 1) if n > 1 else range(n)):       # smoothed levels (a single level: a stand-alone smoother)
-        if vals[i] != "single":
+        if vals[i] == "double":
             continue
-        if types[i] == "cheby":
+        if types[i] in _PREC_TYPES[vals[i]]:
             out[i] = _lib.AMGX_PREC_F32
-        elif per_level:
+        elif per_level and vals[i] == "single":
             raise NgsAMGError(f"mat_prec 'single' on level {i}: single-precision matrix storage is available on Chebyshev "
                               f"levels only (sm_type '{types[i]}')")
+        elif per_level:
+            raise NgsAMGError(f"mat_prec 'single_gs' on level {i}: single-precision matrix storage is available on Chebyshev and "
+                              f"Gauss-Seidel levels only (sm_type '{types[i]}')")
     if not per_level and mat_prec == "single" and not any(out):
         raise NgsAMGError("mat_prec 'single': the hierarchy has no Chebyshev level (sm_type 'cheby') to apply it to")
+    if not per_level and mat_prec == "single_gs" and not any(out):
+        raise NgsAMGError("mat_prec 'single_gs': the hierarchy has no Chebyshev or Gauss-Seidel level (sm_type 'cheby', 'gs', 'hgs') "
+                          "to apply it to")
     return out
 
 
@@ -256,8 +266,8 @@ def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False
     descriptor points to and must outlive the amgx_create / amgx_dist_create call.
     cheb_*: levels with sm_type "cheby" (each a scalar or a per-level list); the descriptor carries 0 for a default
     (degree 2, ratio 10) and for a lambda_max that amgx_create estimates on the device.
-    mat_prec: "double" (default), "single" (single-precision storage of A for the smoother passes of the Chebyshev levels) or a
-    per-level list; see mat_prec_levels."""
+    mat_prec: "double" (default), "single" (single-precision storage of A for the smoother passes of the Chebyshev levels),
+    "single_gs" (the same, and the images of the block Gauss-Seidel sweeps) or a per-level list; see mat_prec_levels."""
     levels = hierarchy.levels
     n = len(levels)
     types = sm_type if isinstance(sm_type, (list, tuple)) else [sm_type] * n
@@ -283,7 +293,8 @@ def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False
             d.cheb_degree = deg
             d.cheb_lambda_max = lam
             d.cheb_ratio = 0.0 if rat == 10.0 else rat
-        d.mat_prec = prec[i]
+        # (a scalar Gauss-Seidel level has no sweep form with single-precision images: "single_gs" leaves it fp64)
+        d.mat_prec = 0 if types[i] in ("gs", "hgs") and lv.A.br == 1 else prec[i]
         d.omega = float(omega)
         d.sm_steps = int(sm_steps[i] if isinstance(sm_steps, (list, tuple)) else sm_steps)      # per level: ..._spec flags
         d.sm_symm = int(bool(sm_symm[i] if isinstance(sm_symm, (list, tuple)) else sm_symm))
@@ -662,14 +673,16 @@ class DeviceAMGMatrix:
         return d
 
     _EXTRA_KEYS = ("tail_ops", "tail_gs_lds", "gs_slices16", "gs_slices", "gs_rowrel", "A_diag_first", "Apre_diag_first", "Apre_wdiag",
-                   "graphs")
+                   "graphs", "gs_f32", "gs_f32_images", "gs_f32_bytes")
 
     def level_extra(self, level):
         """further read-only paths of one level (amgx_level_extra): the operations of the tail kernel's program ("tail_ops", 0
         without such a tail), the form of this level's Gauss-Seidel sweeps inside it ("tail_gs_lds": 1 x in LDS, 0 x in global
         memory, None not a Gauss-Seidel level of the tail), the 16-bit / all slices of the colour-major copies of the multicolour
         scalar sweep and whether their 16-bit columns are row-relative, whether the sliced-ELL images of A and A' store the diagonal
-        entry of every row first and whether that slot of A' holds omega, and the whole-cycle graphs the handle holds"""
+        entry of every row first and whether that slot of A' holds omega, the whole-cycle graphs the handle holds, and the
+        single-precision images of a Gauss-Seidel block level (mat_prec "single_gs"): whether the sweeps read them ("gs_f32"), how
+        many there are (A included) and the bytes of their values"""
         out = np.zeros(len(self._EXTRA_KEYS), dtype=np.int64)
         self._ck(self._lib.amgx_level_extra(self._h, int(level), out.ctypes.data_as(_lib.c_i64p), out.size))
         d = dict(zip(self._EXTRA_KEYS, (int(v) for v in out)))
