@@ -70,10 +70,13 @@ enum {
                               /* and admits scalar Gauss-Seidel levels (block-hybrid or multicolour form, see below) as well; a  */
                               /* handle that does not qualify runs the column loop.  Without it every call is as before, calls   */
                               /* that carry AMGX_MULTI_FUSE alone included                                                       */
-  AMGX_MULTI_FUSE_GS_BLOCK = 256 /* accepted wherever AMGX_MULTI_FUSE_GS is; implies it and AMGX_MULTI_FUSE, and admits          */
+  AMGX_MULTI_FUSE_GS_BLOCK = 256,/* accepted wherever AMGX_MULTI_FUSE_GS is; implies it and AMGX_MULTI_FUSE, and admits          */
                               /* Gauss-Seidel on 2x2 / 3x3 / 6x6 levels (hybrid-block, block-coloured, multicolour forms, see     */
                               /* below) as well; never an error: a handle that does not qualify runs the column loop.  Without   */
                               /* it every call is as before, calls that carry the two flags above included                      */
+  AMGX_MULTI_FUSE_DOWN = 512  /* the multi-vector calls: a fused column group runs the down pass of every level that qualifies  */
+                              /* as the single-vector fused down kernel on interleaved vectors (see "multi-vectors" below); it   */
+                              /* implies nothing and never causes an error.  Without it every call is as before                  */
 };
 
 typedef struct amgx_level_desc {
@@ -438,7 +441,35 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  *                      AMGX_MULTI_FUSE_GS_BLOCK are looked at; flags = 0 answers exactly what amgx_multi_info answers); work_bytes counts one more vector per
  *                      Chebyshev level
  *   amgx_multi_note  : the first reason why the handle is not fused under `flags` (it names the level), "" when it is fused.  The
- *                      string lives until the calling thread's next amgx_multi_note */
+ *                      string lives until the calling thread's next amgx_multi_note
+ * With AMGX_MULTI_FUSE_DOWN = 512 (opt-in per call; it implies nothing and modifies whichever fused cycle the other
+ * flags select, the default fused Jacobi handle with no other flag included) a fused group of 2 or 4 columns runs the down pass of
+ * every smoothed scalar level that qualifies as the single-vector cycle does: r = b - A x formed in LDS, the chunk-local P^T r taken
+ * from there, then the sum of the partial sums -- instead of writing r, gathering it through P^T and, on Jacobi levels, the separate
+ * x = w Dinv b.  A level qualifies if the single-vector cycle has the fused down launch for its smoother (Jacobi from zero, the
+ * residual after Chebyshev, the residual after a block-hybrid Gauss-Seidel sweep from zero), the launch reads a plain SELL image
+ * (or, after a Gauss-Seidel sweep, a windowed one) with 512-lane workgroups, and one lane per row with 4 or 6 entries of P per
+ * thread or 2 / 4 / 8 lanes with 4.  A Jacobi level that qualifies and has the folded prolongation Q in a SELL / CSR-vector form
+ * also runs the way up as x = z + Q x_c.  Every other level keeps the literal stages (local-window and diagonal images, other
+ * workgroup sizes, levels without the chunk-local restriction, block levels, the multicolour sweep); mixing per level is allowed.
+ * Per column the kernels keep the order of additions of the single-vector kernels: a column of amgx_down_multi is the same with
+ * and without the bit, bit for bit.  The column loop and k = 1 ignore the bit; amgx_multi_plan counts the partial-sum buffers.
+ *   amgx_down_multi  : the down stage of a level per column; layout and pointers as in amgx_matvec_multi; B and X have the level's
+ *                      size, BC the coarse level's.  The level must be scalar and smoothed, without ghost columns and not
+ *                      renumbered.  x_given = 0: X is output -- pre-smoothing from zero, then b_c = P^T (b - A x), the down stage of
+ *                      the single-vector V-cycle (X holds z = x + w Dinv r on a level with the folded prolongation).  x_given = 1:
+ *                      X is input, the iterate after the level's pre-smoothing, and only the residual + restriction half runs (on a
+ *                      Jacobi level with a fused down launch that is an error: the Jacobi down pass forms x itself).  Without
+ *                      AMGX_MULTI_FUSE_DOWN a column loop over the single-vector functions; with it groups of 4 and 2 columns run
+ *                      the multi-vector kernels where the level qualifies (a Gauss-Seidel level with x_given = 0 also needs
+ *                      AMGX_MULTI_FUSE_GS for its sweep), and a left-over column takes the single-vector path.
+ *   amgx_multi_level_plan: out[0 .. 4] = the down form of the level under `flags` (0 literal, 1 sell, 2 windowed sell), the mode
+ *                      (0 Jacobi from zero, 1 after a block-hybrid sweep, 2 after Chebyshev), folded way up (0 / 1), single-precision
+ *                      image (0 / 1), bytes of LDS of a workgroup on 4 vectors.  All 0 without AMGX_MULTI_FUSE_DOWN.
+ *   amgx_multi_level_note: why the level stays literal under `flags`: "local-window image", "diagonal image", "workgroup size",
+ *                      "no chunk-local restriction", "block level", "multicolour sweep" ("windowed image": the windowed image of A' behind
+ *                      the AMGX_APRE_WINDOW A/B hook); "" when it does not (or without the bit).
+ *                      The string lives until the calling thread's next amgx_multi_level_note */
 #define AMGX_MULTI_MAX 8
 int amgx_apply_multi(amgx_handle h, int k, const double* B, int64_t ldb, double* X, int64_t ldx, int b_status, int flags);
 int amgx_matvec_multi(amgx_handle h, int level, int k, const double* X, int64_t ldx, double* Y, int64_t ldy, int flags);
@@ -448,6 +479,10 @@ int amgx_smooth_multi(amgx_handle h, int level, int dir, int k, double* X, int64
 int amgx_multi_info(amgx_handle h, int k, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes);
 int amgx_multi_plan(amgx_handle h, int k, int flags, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes);
 const char* amgx_multi_note(amgx_handle h, int flags);
+int amgx_down_multi(amgx_handle h, int level, int k, const double* B, int64_t ldb, double* X, int64_t ldx, double* BC, int64_t ldbc, int x_given,
+                    int flags);
+int amgx_multi_level_plan(amgx_handle h, int level, int flags, int32_t* out, int n_out);
+const char* amgx_multi_level_note(amgx_handle h, int level, int flags);
 
 /* ---- multi-vector algebra: Gram matrices and combinations -------------------------------------------------------------------
  * Reference interface: NGSolve's MultiVector.InnerProduct (the small matrices X^T Y of a Rayleigh-Ritz step) and

@@ -250,7 +250,7 @@ class AMGMatrix:
         with apply_block(mv_in, mv_out) (None: the identity); free: 0/1 mask of the scalar dofs (None: the free dofs of the
         hierarchy); X0: a (num, n) array or CUDA tensor (None: random columns from seed).  Returns (lams, X, info), X a
         DeviceMultiVector (X.data: the (num, n) tensor).  fuse: as in MultMulti; "gs_block" fuses the default Gauss-Seidel smoother
-        of an elasticity hierarchy (AMGX_MULTI_FUSE_GS_BLOCK)."""
+        of an elasticity hierarchy (AMGX_MULTI_FUSE_GS_BLOCK); "down" / "gs+down" / "gs_block+down" add AMGX_MULTI_FUSE_DOWN."""
         import torch
         from .eigen import lobpcg
         from .multivector import DeviceMultiVector, MatVecMulti, MultMulti

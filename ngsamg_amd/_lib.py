@@ -244,6 +244,7 @@ AMGX_MULTI_INTERLEAVED = 32
 AMGX_MULTI_FUSE = 64
 AMGX_MULTI_FUSE_GS = 128                     # implies AMGX_MULTI_FUSE; admits scalar Gauss-Seidel levels
 AMGX_MULTI_FUSE_GS_BLOCK = 256               # implies both; admits Gauss-Seidel on 2x2 / 3x3 / 6x6 levels
+AMGX_MULTI_FUSE_DOWN = 512                   # implies nothing; fused groups run the fused down pass where the level qualifies
 AMGX_MULTI_MAX = 8
 AMGX_MV_MAX = 32                             # columns of a multi-vector in amgx_mv_gram / amgx_mv_combine
 
@@ -261,7 +262,7 @@ AMGX_SYMBOLS = [
     "amgx_gss4_info", "amgx_gss4_smooth", "amgx_gss4_smooth_res", "amgx_gss4_mult_add",
     "amgx_device_count", "amgx_spgemm", "amgx_galerkin", "amgx_csr_result_fetch",
     "amgx_apply_multi", "amgx_matvec_multi", "amgx_pcg_multi", "amgx_multi_info", "amgx_multi_plan", "amgx_multi_note",
-    "amgx_smooth_multi",
+    "amgx_smooth_multi", "amgx_down_multi", "amgx_multi_level_plan", "amgx_multi_level_note",
     "amgx_smoother_info",
     "amgx_mv_gram", "amgx_mv_combine", "amgx_mv_gram_plan",
 ]
@@ -324,6 +325,10 @@ def hip():
     lib.amgx_multi_plan.argtypes = [vp, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_i64p]
     lib.amgx_multi_note.argtypes = [vp, C.c_int]
     lib.amgx_multi_note.restype = C.c_char_p
+    lib.amgx_down_multi.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int64, dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_int]
+    lib.amgx_multi_level_plan.argtypes = [vp, C.c_int, C.c_int, c_i32p, C.c_int]
+    lib.amgx_multi_level_note.argtypes = [vp, C.c_int, C.c_int]
+    lib.amgx_multi_level_note.restype = C.c_char_p
     # multi-vector algebra (G and c are host arrays)
     lib.amgx_mv_gram.argtypes = [vp, C.c_int64, C.c_int, dp, C.c_int64, C.c_int, dp, C.c_int64, c_f64p, C.c_int]
     lib.amgx_mv_combine.argtypes = [vp, C.c_int64, C.c_int, dp, C.c_int64, c_f64p, C.c_int, C.c_double, dp, C.c_int64, C.c_int]

@@ -2350,6 +2350,44 @@ struct Handle {
     if (!skip_rsum && sp.part != PART_INT) restrict_sum(l, R, b_coarse);
   }
 
+  // down_launch on NV = 2 or 4 interleaved vectors (AMGX_MULTI_FUSE_DOWN): the same plan, the same operands (the
+  // vectors of `o` interleaved; dinv of MODE 0 and c of MODE 1 per row), the whole level in one launch.  Which plans have a kernel is
+  // down_nv_ok (down_plan.hpp).  part_nv: n_slots * NV partial sums of the caller (the multi-vector work space), summed into b_coarse
+  template <int NV>
+  void down_launch_nv(int l, const DownPlan& p, const DownOps& o, double* part_nv, double* b_coarse) {
+    const DevLevel& L = lev[l];
+    if (!down_nv_ok(p, NV)) throw Err("fused multi-vector down pass: the level has no plan for it");
+    const DevRestrict& R = p.mode == 1 ? L.RG : L.RF;
+    const int grid = p.n_chunks;
+    const DevMatrix& M = down_image(L, p.mode, false);
+    bool miss = false;
+    auto pick = [&](auto list, int value, auto&& run) { if (!dispatch(list, value, run)) miss = true; };
+    if (grid > 0 && p.family == DOWN_FAM_SELL) {
+      pick(IntList<0, 1, 2>{}, p.mode, [&](auto MODE) {
+        auto image = [&](auto view) {
+          using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;       // double / float
+          auto sell = [&](auto EPT, auto G) {
+            launch(sell_pre_restrict_nv_kernel<DOWN_THREADS, MODE(), EPT(), G(), NV, V>, grid, DOWN_THREADS, 0, stream, M.n_rows, 0, M.n_slices, view, o.v, o.d,
+                   o.omega, o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, part_nv, R.dest.p, R.slice_list.p);
+          };
+          if constexpr (MODE() != 1) { if (p.lanes > 1) return pick(DownSellLanes{}, p.lanes, [&](auto G) { sell(Int<DOWN_MULTI_EPT>{}, G); }); }
+          if (p.lanes > 1) { miss = true; return; }
+          pick(DownEpt{}, p.ept, [&](auto EPT) { sell(EPT, Int<1>{}); });
+        };
+        if constexpr (MODE() == 2) { if (p.f32) return image(M.sell.view32(M.val32.p)); }
+        image(M.sell.view());
+      });
+    } else if (grid > 0) {
+      RestrictMat rv = R.view();
+      rv.part = part_nv;
+      pick(DownEpt{}, p.ept, [&](auto EPT) {
+        launch(sell_win_pre_restrict_nv_kernel<SELL_WIN, EPT(), 1, NV>, grid, SELL_WIN, 0, stream, M.n_rows, 0, M.sell.view(), M.sell.rowloc.p, o.v, o.d, rv);
+      });
+    }
+    if (miss) throw Err("fused multi-vector down pass: no kernel for the plan");
+    launch(restrict_sum_nv_kernel<NV>, grid_for((lev[l + 1].n + RSUM_R - 1) / RSUM_R * RSUM_G), BLOCK, 0, stream, lev[l + 1].n, R.optr.p, R.oidx.p, part_nv, b_coarse);
+  }
+
   // pre-smoothing followed by the restriction of the residual (amg_matrix.cpp:193-212), fused where the level has a plan
   // sp: interior part = the row-parallel pass over the interior rows only; boundary part = the remaining rows plus
   // everything that needs all rows (partial-sum reduction / P^T gather)

@@ -55,6 +55,26 @@ struct DownPlan {
   size_t lds_bytes = 0;                 // dynamic LDS (dia-box)
 };
 
+// ---- the same launch on NV = 2 or 4 interleaved vectors (AMGX_MULTI_FUSE_DOWN, DESIGN.md 5.18: sell_pre_restrict_nv_kernel,
+// sell_win_pre_restrict_nv_kernel in multi_kernels.hpp).  Built for 512-lane workgroups only: the sell family in the three modes
+// (one lane per row with EPT 4 / 6; 2 / 4 / 8 lanes with EPT 4, MODE 0 / 2) and the windowed family in MODE 1.  Every other plan
+// keeps the literal stages of the multi-vector cycle.
+using DownNvWidths = IntList<2, 4>;
+constexpr size_t DOWN_NV_LDS_MAX = 65536;           // static LDS of a workgroup
+// static LDS of the NV launch: r of the chunk's rows for NV columns + ONE array of products that the columns use in turn
+constexpr size_t down_nv_lds_bytes(const DownPlan& p, int nv) {
+  return sizeof(double) * ((size_t)(p.lanes > 0 ? p.threads / p.lanes : 0) * (size_t)nv + (size_t)p.ept * (size_t)p.threads);
+}
+constexpr bool down_nv_ok(const DownPlan& p, int nv) {
+  if (!p.on || !contains(DownNvWidths{}, nv) || p.threads != DOWN_THREADS) return false;
+  bool shape = false;
+  if (p.family == DOWN_FAM_SELL && p.mode >= 0 && p.mode <= 2)
+    shape = p.lanes == 1 ? contains(DownEpt{}, p.ept) : (p.mode != 1 && contains(DownSellLanes{}, p.lanes) && p.ept == DOWN_MULTI_EPT);
+  else if (p.family == DOWN_FAM_WIN)
+    shape = p.mode == 1 && p.lanes == 1 && contains(DownEpt{}, p.ept);
+  return shape && down_nv_lds_bytes(p, nv) <= DOWN_NV_LDS_MAX;
+}
+
 // ---- chunk arithmetic.  A chunk is what one workgroup of `threads` lanes owns: threads / 64 slices = threads / lanes rows
 constexpr int down_slices_per_chunk(int threads) { return threads / DOWN_SLICE; }
 constexpr int64_t down_rows_per_chunk(int threads, int lanes) { return threads / lanes; }

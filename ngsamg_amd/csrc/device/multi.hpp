@@ -33,7 +33,8 @@ inline int multi_groups(int k, bool fused, int32_t* width) {
 }
 
 struct MultiWork {                      // work vectors of one fused width, kept from call to call
-  struct Lev { DevBuf<double> x, rhs, res, tmp, d; };   // d: the update vector of a Chebyshev level
+  // d: the update vector of a Chebyshev level; part: the partial sums of the fused down pass (AMGX_MULTI_FUSE_DOWN, n_slots * width)
+  struct Lev { DevBuf<double> x, rhs, res, tmp, d, part; };
   std::vector<Lev> lev;
   DevBuf<double> in, out;               // interleaved copies of a group of the caller's columns (arguments that are not used in place)
 };
@@ -49,12 +50,14 @@ struct MultiState {
   std::string why_b;
   MultiWork work[MULTI_MAX + 1];        // by width (2, 4)
   DevBuf<double> col_in, col_out;       // one contiguous column (single-vector path behind an interleaved argument)
-  DevBuf<double> stage_b, stage_x;      // host-pointer calls
+  DevBuf<double> stage_b, stage_x, stage_c;   // host-pointer calls (stage_c: the coarse multi-vector of amgx_down_multi)
+  DevBuf<double> dn_c, dn_d, dn_part, dn_col; // amgx_down_multi: interleaved b_c, Chebyshev update and partial sums of a group; b_c of a single column
   DevBuf<double> sm_x, sm_b, sm_t, sm_r; // amgx_smooth_multi: interleaved x, b and the sweep's other buffer of a group; res of a single column
   DevBuf<double> kr[5];                 // amgx_pcg_multi: b, x, d, w, s (interleaved, width k)
   DevBuf<double> kr_sc, kr_partial;
   DevBuf<int32_t> kr_active;
-  using Key = std::tuple<const double*, double*, int, int, int64_t, int64_t, int>;   // b, x, k, layout, ldb, ldx, rule in force (0 .. 3)
+  // b, x, k, layout, ldb, ldx, rule in force (0 .. 3; + 4: fused down passes, AMGX_MULTI_FUSE_DOWN on a handle with a level that takes one)
+  using Key = std::tuple<const double*, double*, int, int, int64_t, int64_t, int>;
   GraphCache<Key> graphs;
 };
 
@@ -64,15 +67,18 @@ void multi_free(MultiState* s) { delete s; }
 struct Multi {
   Handle& h;
   MultiState& st;
-  static constexpr int ALL_FLAGS = AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_GS_BLOCK;
+  static constexpr int ALL_FLAGS = AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_GS_BLOCK;   // the flags that widen the rule
+  static constexpr int CALL_FLAGS = ALL_FLAGS | AMGX_MULTI_FUSE_DOWN;                                 // ... and the one that implies nothing
   const bool block_flag;                // the call carries AMGX_MULTI_FUSE_GS_BLOCK (which implies the two flags below)
   const bool gs_flag;                   // the call carries AMGX_MULTI_FUSE_GS (which implies AMGX_MULTI_FUSE)
   const bool fuse_flag;                 // the call carries AMGX_MULTI_FUSE
   const bool fz;                        // this call runs fused groups
+  const bool down_flag;                 // the call carries AMGX_MULTI_FUSE_DOWN: modifies the fused groups, implies nothing
   explicit Multi(Handle& hh, int flags = 0)
       : h(hh), st(state(hh)), block_flag(flags & AMGX_MULTI_FUSE_GS_BLOCK), gs_flag(flags & (AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_GS_BLOCK)),
         fuse_flag(flags & ALL_FLAGS),
-        fz(st.fused == 1 || (fuse_flag && st.fused_x == 1) || (gs_flag && st.fused_g == 1) || (block_flag && st.fused_b == 1)) {}
+        fz(st.fused == 1 || (fuse_flag && st.fused_x == 1) || (gs_flag && st.fused_g == 1) || (block_flag && st.fused_b == 1)),
+        down_flag(flags & AMGX_MULTI_FUSE_DOWN) {}
   // the rule in force: the flags decide the path only where the narrower rule does not hold (a scalar Jacobi handle: one path,
   // one graph; a handle without Gauss-Seidel levels runs the same cycle under all flags, one without block Gauss-Seidel levels
   // the same cycle under the two Gauss-Seidel flags)
@@ -201,6 +207,50 @@ struct Multi {
   // (0: the whole cycle is the dense operator, no level work vectors)
   int top() const { return h.dense_level >= 0 ? h.dense_level : h.n_levels() - 1; }
 
+  // ---- AMGX_MULTI_FUSE_DOWN: the down pass of ONE smoothed level on a fused group.  form 0: the literal stages,
+  // `why` says which property keeps them ("" without the bit, on an empty level and on a level that is not smoothed); form 1 / 2:
+  // Handle::down_launch_nv on `plan` (sell / windowed sell).  fold: a Jacobi level whose way up is x = z + Q x_c.  The rule is
+  // down_nv_ok (down_plan.hpp) on the plan the single-vector cycle runs for the level's smoother.
+  struct DownNv { int form = 0, mode = 0; bool fold = false, f32 = false; const DownPlan* plan = nullptr; const char* why = ""; };
+  DownNv level_down(int l) const {
+    DownNv d;
+    if (!down_flag || l < 0 || l + 1 >= h.n_levels() || h.lev[l].n == 0) return d;
+    const DevLevel& V = h.lev[l];
+    if (V.bs != 1) { d.why = "block level"; return d; }
+    const DownPlan* p = nullptr;
+    if (V.n == V.ncols && !h.permuted(l) && !h.permuted(l + 1) && h.plain(V)) {
+      if (V.sm_type == AMGX_SM_GS) {
+        if (V.paths.sweep != SWEEP_GSB) { d.why = "multicolour sweep"; return d; }
+        if (V.paths.down == DOWN_GSB && V.plan_rg.on && gs_split(V)) p = &V.plan_rg;
+      } else if (V.sm_type == AMGX_SM_JACOBI) {
+        if (V.paths.jacobi_down() && V.plan_rf.on) p = &V.plan_rf;
+      } else if (V.sm_type == AMGX_SM_CHEBY) {
+        if (V.paths.down == DOWN_CHEB && V.plan_rf.on) p = &V.plan_rf;
+      }
+    }
+    if (!p) { d.why = "no chunk-local restriction"; return d; }
+    if (p->family == DOWN_FAM_LW) { d.why = "local-window image"; return d; }
+    if (p->family == DOWN_FAM_DIA || p->family == DOWN_FAM_DIA_BOX) { d.why = "diagonal image"; return d; }
+    if (p->threads != DOWN_THREADS) { d.why = "workgroup size"; return d; }
+    // (what is left: the windowed image of A' behind the AMGX_APRE_WINDOW A/B hook, which has no multi-vector kernel)
+    if (!down_nv_ok(*p, 2) || !down_nv_ok(*p, 4)) { d.why = "windowed image"; return d; }
+    d.form = p->family == DOWN_FAM_SELL ? 1 : 2;
+    d.mode = p->mode; d.f32 = p->f32; d.plan = p;
+    d.fold = V.sm_type == AMGX_SM_JACOBI && h.folded(V) && !V.Q.empty() && Handle::multi_scalar_ok(V.Q) && V.QLW.empty();
+    return d;
+  }
+  static int64_t down_slots(const DevLevel& V, const DownNv& d) { return d.form ? (d.mode == 1 ? V.RG : V.RF).n_slots : 0; }
+  // the cycle of this call runs at least one fused down pass (part of the graph key)
+  bool down_active() const {
+    if (!down_flag || !fz) return false;
+    for (int l = 0; l < top(); ++l) if (level_down(l).form) return true;
+    return false;
+  }
+  template <class Ops>
+  void down_nv(int w, int l, const DownNv& d, const Ops& o, double* part, double* b_coarse) {
+    width(w, [&](auto W) { h.down_launch_nv<W()>(l, *d.plan, o, part, b_coarse); });
+  }
+
   int64_t work_bytes(int k) const {
     if (k == 1) return 0;                                       // amgx_apply itself
     int32_t wd[MULTI_MAX];
@@ -210,6 +260,8 @@ struct Multi {
     int64_t per_col = 2 * n0;                                  // the two interleaved copies of a group of the caller's columns
     for (int l = 0; l <= T && l < h.n_levels(); ++l)           // (a Chebyshev level: one more vector, the update d)
       per_col += ((l > 0 ? 2 : 0) + (l < T ? 2 + (h.lev[l].sm_type == AMGX_SM_CHEBY ? 1 : 0) : 0)) * h.lev[l].len();
+    if (fz)                                                     // (AMGX_MULTI_FUSE_DOWN: the partial sums of every fused down pass)
+      for (int l = 0; l < T && l + 1 < h.n_levels(); ++l) per_col += down_slots(h.lev[l], level_down(l));
     int64_t bytes = 0;
     bool single = false, seen[MULTI_MAX + 1] = {};              // (groups of one width share their work space)
     for (int g = 0; g < ng; ++g) {
@@ -233,6 +285,11 @@ struct Multi {
         if (l < T && h.lev[l].sm_type == AMGX_SM_CHEBY) W.lev[l].d.alloc(len);
       }
     }
+    if (down_flag)                                              // (a call without the bit may have built the work space first)
+      for (int l = 0; l < top(); ++l) {
+        const int64_t need = down_slots(h.lev[l], level_down(l)) * w;
+        if ((int64_t)W.lev[l].part.n < need) W.lev[l].part.alloc((size_t)need);
+      }
     return W;
   }
 
@@ -354,13 +411,26 @@ struct Multi {
       double* xl = l == 0 ? x : W.lev[l].x.p;
       const double* bl = l == 0 ? b : W.lev[l].rhs.p;
       double* const tmp = W.lev[l].tmp.p;
+      // AMGX_MULTI_FUSE_DOWN: r = b - A x stays in LDS, chunk-local P^T r from there, then the sum (Handle::down_launch_nv)
+      const DownNv dn = level_down(l);
+      double* const part = W.lev[l].part.p;
+      double* const bc = W.lev[l + 1].rhs.p;
       if (V.sm_type == AMGX_SM_GS) {                           // sweep from zero and the residual by the level's identity
+        if (dn.form) {                                         // (hybrid form with the split: r = c .* x - rest x)
+          width(w, [&](auto NV) { h.gsb_sweep_nv<NV()>(V, 0, nullptr, xl, bl); });
+          down_nv(w, l, dn, Handle::down_ops_gsb(V, xl), part, bc);
+          continue;
+        }
         gs_down(w, V, bl, xl, W.lev[l].res.p);
         spmm<EP_MULT>(w, V.PT, W.lev[l].res.p, W.lev[l + 1].rhs.p, none);
         continue;
       }
       if (V.sm_type == AMGX_SM_CHEBY) {                        // cheb_smooth from zero per column
         cheb(w, V, ChebEntry::ZERO, xl, xl, bl, tmp, W.lev[l].d.p);
+        if (dn.form) { down_nv(w, l, dn, h.down_ops_cheb(xl, bl), part, bc); continue; }
+      } else if (dn.form) {                                    // x = w Dinv b (z on a level whose way up is Q), r = b - A' b in one pass
+        down_nv(w, l, dn, h.down_ops_jacobi(V, bl, xl, dn.fold), part, bc);
+        continue;
       } else diag(w, V, bl, xl, V.omega);
       spmm<EP_RES>(w, V.A, xl, W.lev[l].res.p, EpArgs{bl, nullptr, nullptr, 0.0, nullptr, 0}, true);
       spmm<EP_MULT>(w, V.PT, W.lev[l].res.p, W.lev[l + 1].rhs.p, none);
@@ -380,6 +450,8 @@ struct Multi {
         double* t = cheb_place(cheb_passes(V.cheb_degree, ChebEntry::ITERATE), xl, tmp);
         spmm<EP_AXPY>(w, V.P, W.lev[l + 1].x.p, t, EpArgs{nullptr, xl, nullptr, 1.0, nullptr, 0});
         cheb(w, V, ChebEntry::ITERATE, t, xl, bl, tmp, W.lev[l].d.p);
+      } else if (level_down(l).fold) {                         // x = z + Q x_c (fold_prolongation): the down pass stored z
+        spmm<EP_AXPY>(w, V.Q, W.lev[l + 1].x.p, xl, EpArgs{nullptr, xl, nullptr, 1.0, nullptr, 0});
       } else {
         spmm<EP_AXPY>(w, V.P, W.lev[l + 1].x.p, tmp, EpArgs{nullptr, xl, nullptr, 1.0, nullptr, 0});
         spmm<EP_JAC>(w, V.A, tmp, xl, EpArgs{bl, tmp, V.dinv.p, V.omega, nullptr, 0});
@@ -432,7 +504,7 @@ struct Multi {
     const int64_t brs = interleaved ? k : 1, bcs = interleaved ? 1 : ldb, xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx;
     // only the fused path is captured as a whole; the column loop replays the single-vector graphs of run_cycle
     if (!fz || !(h.use_graph && graph_ok) || h.stream == nullptr) { apply_body(k, B, brs, bcs, X, xrs, xcs, graph_ok, false); return; }
-    const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx, rule()};
+    const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx, rule() + (down_active() ? 4 : 0)};
     if (!st.graphs.has(key)) {
       int32_t wd[MULTI_MAX];
       const int ng = multi_groups(k, true, wd);
@@ -517,6 +589,57 @@ struct Multi {
       pack(n, w, B, brs, bcs, c0, st.sm_b.p);
       const double* out = gs_sweep(w, V, dir, st.sm_x.p, st.sm_t.p, st.sm_b.p);
       unpack(n, w, out, X, xrs, xcs, c0);
+    }
+  }
+
+  // the down stage of a level per column (amgx_down_multi): x_given = false: pre-smoothing from zero b -> x, then b_c = P^T (b - A x)
+  // (Handle::pre_smooth_restrict with the level's fold); x_given = true: only the residual + restriction half on the caller's x.
+  // Groups of 4 and 2 run Handle::down_launch_nv where the call carries AMGX_MULTI_FUSE_DOWN and the level takes it (level_down; a
+  // Gauss-Seidel sweep from zero also needs AMGX_MULTI_FUSE_GS); everything else is a column loop over the single-vector functions.
+  void down(int level, int k, const double* B, int64_t ldb, double* X, int64_t ldx, double* BC, int64_t ldbc, bool interleaved, bool x_given) {
+    DevLevel& V = h.lev[level];
+    const int64_t n = V.len(), nc = h.lev[level + 1].len(), n0 = h.lev[0].len();
+    const int64_t brs = interleaved ? k : 1, bcs = interleaved ? 1 : ldb, xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx;
+    const int64_t crs = interleaved ? k : 1, ccs = interleaved ? 1 : ldbc;
+    const bool gs = V.sm_type == AMGX_SM_GS, cheby = V.sm_type == AMGX_SM_CHEBY, jacobi = V.sm_type == AMGX_SM_JACOBI;
+    if (x_given && jacobi && V.paths.jacobi_down()) throw Err("amgx_down_multi: x_given on a Jacobi level with a fused down pass (the Jacobi down pass forms x itself)");
+    const DownNv dn = level_down(level);
+    const bool nv = dn.form != 0 && (x_given || !gs || gs_flag);
+    int32_t wd[MULTI_MAX];
+    const int ng = multi_groups(k, nv, wd);
+    int c0 = 0;
+    for (int g = 0; g < ng; c0 += wd[g], ++g) {
+      const int w = wd[g];
+      if (w == 1) {                                            // the single-vector functions with device pointers
+        const double* b1 = B + c0 * bcs;
+        double* x1 = X + c0 * xcs;
+        double* c1 = BC + c0 * ccs;
+        if (brs != 1) { fit(st.col_in, std::max(n, n0)); pack(n, 1, B, brs, bcs, c0, st.col_in.p); b1 = st.col_in.p; }
+        if (xrs != 1) { fit(st.col_out, std::max(n, n0)); x1 = st.col_out.p; if (x_given) pack(n, 1, X, xrs, xcs, c0, x1); }
+        if (crs != 1) { fit(st.dn_col, nc); c1 = st.dn_col.p; }
+        fit(st.sm_r, n);
+        double* const r = st.sm_r.p;
+        if (!x_given) h.pre_smooth_restrict(level, x1, b1, r, c1, h.folded(V));
+        else if (cheby && V.paths.down == DOWN_CHEB) h.down_launch(level, V.plan_rf, h.down_ops_cheb(x1, b1), c1);
+        else if (gs && V.paths.down == DOWN_GSB) h.residual_restrict_after_zero(level, x1, b1, r, c1);
+        else { h.residual_sm(V, x1, b1, r); h.transfer_f2c(level, r, c1); }
+        if (!x_given && xrs != 1) unpack(n, 1, x1, X, xrs, xcs, c0);
+        if (crs != 1) unpack(nc, 1, c1, BC, crs, ccs, c0);
+        continue;
+      }
+      constexpr int WMAX = MULTI_MAX / 2;                      // the widest group
+      fit(st.sm_x, n * WMAX); fit(st.sm_b, n * WMAX); fit(st.sm_t, n * WMAX); fit(st.dn_d, n * WMAX);
+      fit(st.dn_c, nc * WMAX); fit(st.dn_part, down_slots(V, dn) * WMAX);
+      double *xw = st.sm_x.p, *bw = st.sm_b.p;
+      pack(n, w, B, brs, bcs, c0, bw);
+      if (x_given) pack(n, w, X, xrs, xcs, c0, xw);
+      else if (cheby) cheb(w, V, ChebEntry::ZERO, xw, xw, bw, st.sm_t.p, st.dn_d.p);
+      else if (gs) width(w, [&](auto NV) { h.gsb_sweep_nv<NV()>(V, 0, nullptr, xw, bw); });
+      if (jacobi) down_nv(w, level, dn, h.down_ops_jacobi(V, bw, xw, h.folded(V)), st.dn_part.p, st.dn_c.p);
+      else if (cheby) down_nv(w, level, dn, h.down_ops_cheb(xw, bw), st.dn_part.p, st.dn_c.p);
+      else down_nv(w, level, dn, Handle::down_ops_gsb(V, xw), st.dn_part.p, st.dn_c.p);
+      if (!x_given) unpack(n, w, xw, X, xrs, xcs, c0);
+      unpack(nc, w, st.dn_c.p, BC, crs, ccs, c0);
     }
   }
 
@@ -630,7 +753,7 @@ inline void multi_check(const char* fn, int k, const void* a, const void* b, int
 extern "C" {
 
 int amgx_apply_multi(amgx_handle hh, int k, const double* B, int64_t ldb, double* X, int64_t ldx, int b_status, int flags) {
-  if (k == 1 && hh && hh->h) return amgx_apply(hh, B, X, b_status, flags & ~(AMGX_MULTI_INTERLEAVED | amgx::Multi::ALL_FLAGS));   // the single-vector path itself
+  if (k == 1 && hh && hh->h) return amgx_apply(hh, B, X, b_status, flags & ~(AMGX_MULTI_INTERLEAVED | amgx::Multi::CALL_FLAGS));   // the single-vector path itself
   (void)b_status;   // single GPU: DISTRIBUTED == CUMULATED, as in amgx_apply
   return guard(hh, [&](amgx::Handle& h) {
     const int64_t n = h.lev[0].len();
@@ -679,6 +802,56 @@ int amgx_smooth_multi(amgx_handle hh, int level, int dir, int k, double* X, int6
   });
 }
 
+int amgx_down_multi(amgx_handle hh, int level, int k, const double* B, int64_t ldb, double* X, int64_t ldx, double* BC, int64_t ldbc, int x_given,
+                    int flags) {
+  return guard(hh, [&](amgx::Handle& h) {
+    if (level < 0 || level + 1 >= h.n_levels()) throw amgx::Err("amgx_down_multi: level out of range (the level must be smoothed)");
+    const amgx::DevLevel& V = h.lev[level];
+    if (V.bs != 1 || h.lev[level + 1].bs != 1) throw amgx::Err("amgx_down_multi: block level");
+    if (!V.dinv.p) throw amgx::Err("amgx_down_multi: level has no smoother");
+    if (V.n != V.ncols) throw amgx::Err("amgx_down_multi: rank-partitioned levels are not supported");
+    if (h.permuted(level) || h.permuted(level + 1)) throw amgx::Err("amgx_down_multi: renumbered level");
+    const int64_t n = V.len(), nc = h.lev[level + 1].len();
+    const bool il = flags & AMGX_MULTI_INTERLEAVED;
+    amgx::multi_check("amgx_down_multi", k, B, X, ldb, ldx, n, n, il);
+    if (!BC) throw amgx::Err("amgx_down_multi: null multi-vector");
+    if (BC == B || BC == X) throw amgx::Err("amgx_down_multi: the multi-vectors must not alias");
+    if (!il && k > 1 && ldbc < nc) throw amgx::Err("amgx_down_multi: leading dimension below the level size");
+    amgx::Multi M(h, flags);
+    amgx::MultiStaged sg(h, flags);
+    const int64_t lb = (sg.host && !il) ? n : ldb, lx = (sg.host && !il) ? n : ldx, lc = (sg.host && !il) ? nc : ldbc;
+    const double* dB = sg.in(M.st.stage_b, B, n, k, il, ldb);
+    double* dX = const_cast<double*>(sg.in(M.st.stage_x, X, n, k, il, ldx, x_given != 0));
+    double* dC = const_cast<double*>(sg.in(M.st.stage_c, BC, nc, k, il, ldbc, false));
+    M.down(level, k, dB, lb, dX, lx, dC, lc, il, x_given != 0);
+    if (!x_given) sg.out(M.st.stage_x, X, n, k, il, ldx);
+    sg.out(M.st.stage_c, BC, nc, k, il, ldbc);
+  });
+}
+
+int amgx_multi_level_plan(amgx_handle hh, int level, int flags, int32_t* out, int n_out) {
+  return guard(hh, [&](amgx::Handle& h) {
+    if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_multi_level_plan: level out of range");
+    if (!out || n_out < 1) throw amgx::Err("amgx_multi_level_plan: bad arguments");
+    amgx::Multi M(h, flags & amgx::Multi::CALL_FLAGS);
+    const amgx::Multi::DownNv d = M.level_down(level);
+    const int32_t v[5] = {d.form, d.form ? d.mode : 0, d.fold ? 1 : 0, d.f32 ? 1 : 0, d.form ? (int32_t)amgx::down_nv_lds_bytes(*d.plan, 4) : 0};
+    for (int i = 0; i < std::min(n_out, 5); ++i) out[i] = v[i];
+  });
+}
+
+const char* amgx_multi_level_note(amgx_handle hh, int level, int flags) {
+  thread_local std::string note;
+  note.clear();
+  if (guard(hh, [&](amgx::Handle& h) {
+        if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_multi_level_note: level out of range");
+        amgx::Multi M(h, flags & amgx::Multi::CALL_FLAGS);
+        note = M.level_down(level).why;
+      }))
+    note = amgx_last_error(hh);
+  return note.c_str();
+}
+
 int amgx_pcg_multi(amgx_handle hh, int k, const double* B, int64_t ldb, double* X, int64_t ldx, double tol, int maxit, int use_precond, int flags,
                    double* errs, int32_t* iters) {
   return guard(hh, [&](amgx::Handle& h) {
@@ -702,9 +875,9 @@ int amgx_multi_info(amgx_handle hh, int k, int32_t* fused, int32_t* n_groups, in
 
 int amgx_multi_plan(amgx_handle hh, int k, int flags, int32_t* fused, int32_t* n_groups, int32_t* group_width, int64_t* work_bytes) {
   return guard(hh, [&](amgx::Handle& h) {
-    const std::string fn = (flags & amgx::Multi::ALL_FLAGS) ? "amgx_multi_plan" : "amgx_multi_info";
+    const std::string fn = (flags & amgx::Multi::CALL_FLAGS) ? "amgx_multi_plan" : "amgx_multi_info";
     if (k < 1 || k > amgx::MULTI_MAX) throw amgx::Err(fn + ": k must be 1 .. " + std::to_string(amgx::MULTI_MAX) + " (got " + std::to_string(k) + ")");
-    amgx::Multi M(h, flags & amgx::Multi::ALL_FLAGS);
+    amgx::Multi M(h, flags & amgx::Multi::CALL_FLAGS);
     int32_t wd[amgx::MULTI_MAX];
     const int ng = amgx::multi_groups(k, M.fz, wd);
     if (fused) *fused = M.fz ? 1 : 0;

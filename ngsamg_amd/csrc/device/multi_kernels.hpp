@@ -87,9 +87,11 @@ __device__ __forceinline__ void store_multi(int64_t row, const double (&acc)[NV]
 }
 
 // ---- SELL row product for NV interleaved vectors: the batch pipeline of sell_pairs with the gather widened to NV values ----
-template <int K, bool C16, int NV, class V>
+// XD (the fused down kernel on a diagonal-first image, sell_consume's xd): xd[0 .. NV) receives the x values gathered for entry 0 of
+// this lane's row, xd[NV] the matrix value of that entry
+template <int K, bool C16, int NV, class V, bool XD = false>
 __device__ __forceinline__ void sell_consume_nv(const SellRegs<K, V>& R, const int32_t* __restrict__ cb, int r0, int p,
-                                                const double* __restrict__ x, double (&acc0)[NV], double (&acc1)[NV]) {
+                                                const double* __restrict__ x, double (&acc0)[NV], double (&acc1)[NV], double* xd = nullptr) {
   double x0[K][NV], x1[K][NV];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -99,6 +101,13 @@ __device__ __forceinline__ void sell_consume_nv(const SellRegs<K, V>& R, const i
     ldv<NV>(x + (int64_t)c0 * NV, x0[k]);
     ldv<NV>(x + (int64_t)c1 * NV, x1[k]);
   }
+  if constexpr (XD) {
+    if (p == 0) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) xd[j] = x0[0][j];
+      xd[NV] = (double)R.v0[0];
+    }
+  }
 #pragma unroll
   for (int k = 0; k < K; ++k) {
 #pragma unroll
@@ -106,21 +115,22 @@ __device__ __forceinline__ void sell_consume_nv(const SellRegs<K, V>& R, const i
   }
 }
 
-template <int K, int REM, bool C16, int NV, class V>
+template <int K, int REM, bool C16, int NV, class V, bool XD = false>
 __device__ __forceinline__ void sell_tail_nv(int rem, const SellRegs<K, V>* last, int p_last, const V* __restrict__ vb,
                                              const void* __restrict__ cpv, const int32_t* __restrict__ cb, int r0, int p, int lane,
-                                             const double* __restrict__ x, double (&acc0)[NV], double (&acc1)[NV]) {
+                                             const double* __restrict__ x, double (&acc0)[NV], double (&acc1)[NV], double* xd = nullptr) {
   if (rem == REM) {
     SellRegs<REM, V> R;
     sell_load<REM, C16>(R, vb, cpv, p, lane);
-    if (last) sell_consume_nv<K, C16, NV>(*last, cb, r0, p_last, x, acc0, acc1);
-    sell_consume_nv<REM, C16, NV>(R, cb, r0, p, x, acc0, acc1);
-  } else if constexpr (REM > 1) sell_tail_nv<K, REM - 1, C16, NV, V>(rem, last, p_last, vb, cpv, cb, r0, p, lane, x, acc0, acc1);
+    if (last) sell_consume_nv<K, C16, NV, V, XD>(*last, cb, r0, p_last, x, acc0, acc1, xd);
+    sell_consume_nv<REM, C16, NV, V, XD>(R, cb, r0, p, x, acc0, acc1, xd);
+  } else if constexpr (REM > 1) sell_tail_nv<K, REM - 1, C16, NV, V, XD>(rem, last, p_last, vb, cpv, cb, r0, p, lane, x, acc0, acc1, xd);
 }
 
-template <bool C16, int NV, class V, int K = SELL_BATCH>
+template <bool C16, int NV, class V, int K = SELL_BATCH, bool XD = false>
 __device__ __forceinline__ void sell_pairs_nv(int np, const V* __restrict__ vb, const void* __restrict__ cpv, const int32_t* __restrict__ cb,
-                                              int r0, int lane, const double* __restrict__ x, double (&acc0)[NV], double (&acc1)[NV]) {
+                                              int r0, int lane, const double* __restrict__ x, double (&acc0)[NV], double (&acc1)[NV],
+                                              double* xd = nullptr) {
   const int nfull = np / K, rem = np - nfull * K;
   if (nfull > 0) {
     SellRegs<K, V> A;
@@ -128,18 +138,19 @@ __device__ __forceinline__ void sell_pairs_nv(int np, const V* __restrict__ vb, 
     for (int b = 1; b < nfull; ++b) {
       SellRegs<K, V> B;
       sell_load<K, C16>(B, vb, cpv, b * K, lane);
-      sell_consume_nv<K, C16, NV>(A, cb, r0, (b - 1) * K, x, acc0, acc1);
+      sell_consume_nv<K, C16, NV, V, XD>(A, cb, r0, (b - 1) * K, x, acc0, acc1, xd);
       A = B;
     }
-    if (K > 1 && rem) sell_tail_nv<K, (K > 1 ? K - 1 : 1), C16, NV, V>(rem, &A, (nfull - 1) * K, vb, cpv, cb, r0, nfull * K, lane, x, acc0, acc1);
-    else sell_consume_nv<K, C16, NV>(A, cb, r0, (nfull - 1) * K, x, acc0, acc1);
-  } else if (K > 1 && rem) sell_tail_nv<K, (K > 1 ? K - 1 : 1), C16, NV, V>(rem, nullptr, 0, vb, cpv, cb, r0, 0, lane, x, acc0, acc1);
+    if (K > 1 && rem) sell_tail_nv<K, (K > 1 ? K - 1 : 1), C16, NV, V, XD>(rem, &A, (nfull - 1) * K, vb, cpv, cb, r0, nfull * K, lane, x, acc0, acc1, xd);
+    else sell_consume_nv<K, C16, NV, V, XD>(A, cb, r0, (nfull - 1) * K, x, acc0, acc1, xd);
+  } else if (K > 1 && rem) sell_tail_nv<K, (K > 1 ? K - 1 : 1), C16, NV, V, XD>(rem, nullptr, 0, vb, cpv, cb, r0, 0, lane, x, acc0, acc1, xd);
 }
 
-// acc[j] = (SELL row of slice s, this lane) . column j of x          (sell_row_dot_sp for NV vectors)
-template <int NV, class V>
-__device__ __forceinline__ void sell_row_dot_nv(const SellMatT<V>& M, int s, int lane, int row, const double* __restrict__ x, double (&acc)[NV]) {
-  const int64_t sp0 = M.slice_ptr[s], sp1 = M.slice_ptr[s + 1];
+// acc[j] = (SELL row of the slice with pointers sp0, sp1; this lane) . column j of x          (sell_row_dot_sp for NV vectors)
+// XD: xd = NV + 1 doubles of the caller, see sell_consume_nv
+template <int NV, class V, bool XD = false>
+__device__ __forceinline__ void sell_row_dot_nv_sp(const SellMatT<V>& M, int64_t sp0, int64_t sp1, int lane, int row, const double* __restrict__ x,
+                                                   double (&acc)[NV], double* xd = nullptr) {
   const int64_t base = sp0 & ~(int64_t)63;
   const int w = (int)(((sp1 & ~(int64_t)63) - base) >> 6);
   const int np = w >> 1;
@@ -157,17 +168,28 @@ __device__ __forceinline__ void sell_row_dot_nv(const SellMatT<V>& M, int s, int
     vs = ld_nt(vb + o);
     cs = c16 ? (int)ld_nt(M.col16 + base + o) : ld_nt(M.col32 + base + o);
   }
-  if (c16) sell_pairs_nv<true, NV, V>(np, vb, M.col16 + base, cb, r0, lane, x, acc0, acc1);
-  else sell_pairs_nv<false, NV, V>(np, vb, M.col32 + base, nullptr, 0, lane, x, acc0, acc1);
+  if (c16) sell_pairs_nv<true, NV, V, SELL_BATCH, XD>(np, vb, M.col16 + base, cb, r0, lane, x, acc0, acc1, xd);
+  else sell_pairs_nv<false, NV, V, SELL_BATCH, XD>(np, vb, M.col32 + base, nullptr, 0, lane, x, acc0, acc1, xd);
   if (w & 1) {
     const int c = c16 ? r0 + cb[w - 1] + cs : cs;
     double xs[NV];
     ldv<NV>(x + (int64_t)c * NV, xs);
+    if constexpr (XD) {
+      if (np == 0) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) xd[j] = xs[j];
+        xd[NV] = (double)vs;
+      }
+    }
 #pragma unroll
     for (int j = 0; j < NV; ++j) acc0[j] += (double)vs * xs[j];
   }
 #pragma unroll
   for (int j = 0; j < NV; ++j) acc[j] = acc0[j] + acc1[j];
+}
+template <int NV, class V>
+__device__ __forceinline__ void sell_row_dot_nv(const SellMatT<V>& M, int s, int lane, int row, const double* __restrict__ x, double (&acc)[NV]) {
+  sell_row_dot_nv_sp<NV, V>(M, M.slice_ptr[s], M.slice_ptr[s + 1], lane, row, x, acc);
 }
 
 // SELL-64-pair, G lanes per row, NV interleaved vectors (sell_spmv_kernel's multi-vector form, same SellMat view)
@@ -211,6 +233,263 @@ __global__ __launch_bounds__(WB) void sell_win_spmm_kernel(int64_t n_rows, SellM
 #pragma unroll
     for (int j = 0; j < NV; ++j) acc[j] = buf[threadIdx.x * NV + j];
     store_multi<NV, EP>(row, acc, y, ep);
+  }
+}
+
+// ---- the fused down kernels on NV interleaved vectors (AMGX_MULTI_FUSE_DOWN) ---------------------------------
+// The single-vector kernels (kernels.hpp: "The fused down kernels") restated column by column: the same image, the same order of
+// additions in the row product, the same products and slot sums in the restriction.  r of the chunk's rows sits in LDS interleaved
+// (row * NV + column); no operation mixes two columns, every index into an interleaved vector is 64-bit, padding rows and empty
+// slices write nothing, and every barrier is reached by every lane (the column loops have compile-time bounds).
+//
+// ChunkRestrictNV<FB, EPT, NV>: ChunkRestrict for NV columns.  request() is ChunkRestrict::request (nothing it loads is consumed
+// before the row product: raw slot pointers).  reduce() runs ChunkRestrict::reduce once per column on the ONE array pr[EPT * FB],
+// with a barrier between two columns: LDS stays at 8 * (RPC * NV + EPT * FB) <= 40 KB (three workgroups per CU); holding the
+// products of all columns would need 96-112 KB.  The partial sums go to part_nv[dest * NV + column] (R.part), a buffer of the
+// multi-vector work space; restrict_sum_nv_kernel adds them.
+template <int FB, int EPT, int NV>
+struct ChunkRestrictNV {
+  int s1, e0, e1, myslot, mydest, pa_raw, pb_raw;
+  double wq[EPT];
+  int fq[EPT];
+  __device__ __forceinline__ void request(int c, const RestrictMat& R) {
+    const int s0 = R.chunk_slot[c];
+    s1 = R.chunk_slot[c + 1];
+    e0 = R.slot_ptr[s0];
+    e1 = R.slot_ptr[s1];
+#pragma unroll
+    for (int q = 0; q < EPT; ++q) {
+      const int e = e0 + threadIdx.x + q * FB;
+      wq[q] = e < e1 ? ld_nt(R.w + e) : 0.0;
+      fq[q] = e < e1 ? (int)ld_nt(R.fi + e) : 0;
+    }
+    myslot = s0 + threadIdx.x;
+    mydest = myslot; pa_raw = 0; pb_raw = 0;
+    if (myslot < s1) {
+      if (R.dest) mydest = R.dest[myslot];
+      pa_raw = R.slot_ptr[myslot];
+      pb_raw = R.slot_ptr[myslot + 1];
+    }
+  }
+  // r_lds: r of the chunk's rows, interleaved (the caller's barrier has passed); pr = EPT * FB doubles of LDS
+  __device__ __forceinline__ void reduce(const double* r_lds, double* pr, const RestrictMat& R) const {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      if (j > 0) __syncthreads();                               // the sums of column j - 1 have read pr
+#pragma unroll
+      for (int q = 0; q < EPT; ++q) {
+        const int e = threadIdx.x + q * FB;
+        if (e0 + e < e1) pr[e] = wq[q] * r_lds[fq[q] * NV + j];
+      }
+      __syncthreads();
+      if (myslot < s1) {
+        const int pa = pa_raw - e0, pb = pb_raw - e0;
+        double acc = 0.0;
+        for (int k = pa; k < pb; ++k) acc += pr[k];
+        R.part[(int64_t)mydest * NV + j] = acc;
+      }
+      for (int slot = myslot + FB; slot < s1; slot += FB) {     // chunks with more slots than threads
+        const int a = R.slot_ptr[slot] - e0, bnd = R.slot_ptr[slot + 1] - e0;
+        double acc = 0.0;
+        for (int k = a; k < bnd; ++k) acc += pr[k];
+        R.part[(int64_t)(R.dest ? R.dest[slot] : slot) * NV + j] = acc;
+      }
+    }
+  }
+};
+
+// sell_pre_restrict_kernel<FUSED_BLOCK, MODE, EPT, G, V> on NV interleaved vectors, mode by mode: b (the gathered vector), x and --
+// in MODE 2 -- dinv (the right-hand side) are interleaved; dinv of MODE 0 and c of MODE 1 are per row.  The row product is the one of
+// sell_spmm_kernel (sell_row_dot_nv_sp, per column the pair order of sell_row_dot_sp and the lane_group_sum<G> tree).
+template <int FUSED_BLOCK, int MODE, int EPT, int G, int NV, class V = double>
+__global__ __launch_bounds__(FUSED_BLOCK) void sell_pre_restrict_nv_kernel(int64_t n_rows, int chunk0, int n_slices, SellMatT<V> M,
+                                                                           const double* __restrict__ b, const double* __restrict__ dinv,
+                                                                           double omega, int nt, double* __restrict__ x,
+                                                                           const int32_t* __restrict__ chunk_slot,
+                                                                           const int32_t* __restrict__ slot_ptr,
+                                                                           const double* __restrict__ w, const uint16_t* __restrict__ fi,
+                                                                           double* __restrict__ part_nv,
+                                                                           const int32_t* __restrict__ dest,
+                                                                           const int32_t* __restrict__ slice_list = nullptr) {
+  const RestrictMat R{chunk_slot, slot_ptr, w, fi, part_nv, dest};
+  constexpr int RPC = FUSED_BLOCK / G;         // rows per chunk
+  __shared__ double rl[RPC * NV];
+  __shared__ double pr[EPT * FUSED_BLOCK];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int c = chunk0 + sell_unit(M);
+  const int sq = c * (FUSED_BLOCK / WAVE) + (threadIdx.x >> 6);
+  const int s_raw = slice_list ? slice_list[sq] : sq;          // compact chunks: as in the single-vector kernel
+  const int s = __builtin_amdgcn_readfirstlane(s_raw < 0 ? n_slices : s_raw);
+  const int row = s * (WAVE / G) + lane / G;
+  const int lrow = (threadIdx.x >> 6) * (WAVE / G) + lane / G;     // row inside the chunk
+  const bool writer = (lane % G) == 0;
+  const bool has_slice = s < n_slices;
+  const int64_t sp0 = has_slice ? M.slice_ptr[s] : 0, sp1 = has_slice ? M.slice_ptr[s + 1] : 0;
+  ChunkRestrictNV<FUSED_BLOCK, EPT, NV> cr;
+  cr.request(c, R);
+  double r[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) r[j] = 0.0;
+  if (s < n_slices) {
+    // own-row operands ahead of the row product, as in the single-vector kernel; dv: the right-hand side of MODE 2
+    double bi[NV], dv[NV], di = 0.0;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) { bi[j] = 0.0; dv[j] = 0.0; }
+    const int64_t io = (int64_t)row * NV;
+    constexpr bool XD = MODE == 0 && G == 1;
+    const bool wdiag = XD && M.wdiag && M.diag_first;
+    const bool hoist = MODE != 0 || G > 1 || (nt & EPF_HOIST);
+    if (!wdiag && hoist && writer && row < n_rows) {
+      if (MODE != 2) ldv<NV>(b + io, bi);
+      if (MODE == 2) ldv<NV>(dinv + io, dv);
+      else di = (MODE != 1 && (nt & EPF_NT)) ? ld_nt(dinv + row) : dinv[row];
+    }
+    double acc[NV], xd[NV + 1];
+#pragma unroll
+    for (int j = 0; j <= NV; ++j) xd[j] = 0.0;
+    sell_row_dot_nv_sp<NV, V, XD>(M, sp0, sp1, lane, row, b, acc, xd);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] = lane_group_sum<G>(acc[j]);
+    if (writer && row < n_rows) {
+      if (MODE == 1) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) r[j] = di * bi[j] - acc[j];
+      } else if (MODE == 2) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) r[j] = dv[j] - acc[j];
+      } else {
+        if (wdiag) {
+          const double wd = xd[NV];
+#pragma unroll
+          for (int j = 0; j < NV; ++j) {
+            bi[j] = xd[j];
+            acc[j] = acc[j] - wd * bi[j] + (wd != 0.0 ? omega * bi[j] : 0.0);
+          }
+          di = wd / omega;
+        } else if (!hoist) { ldv<NV>(b + io, bi); di = (nt & EPF_NT) ? ld_nt(dinv + row) : dinv[row]; }
+        double xi[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+          r[j] = bi[j] - acc[j];
+          xi[j] = omega * (di * bi[j]);                        // jacobi_down_store per column
+          if (nt & EPF_FOLD) xi[j] += omega * (di * r[j]);
+        }
+        if (nt & EPF_NT) {
+#pragma unroll
+          for (int j = 0; j < NV; ++j) __builtin_nontemporal_store(xi[j], x + io + j);
+        } else stv<NV>(x + io, xi);
+      }
+    }
+  }
+  if (writer) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) rl[lrow * NV + j] = r[j];
+  }
+  __syncthreads();
+  cr.reduce(rl, pr, R);
+}
+
+// sell_win_pre_restrict_kernel<WB, EPT, 1> on NV interleaved vectors: the residual after a block-hybrid sweep from zero on the
+// windowed image of A_rest, r = c .* x - A_rest x (b = the swept x, interleaved; dinv = c per row), row sums through LDS back to
+// natural order as in sell_win_spmm_kernel.  (MODE 0 of the windowed family is the AMGX_APRE_WINDOW A/B hook: not built.)
+template <int WB, int EPT, int MODE, int NV>
+__global__ __launch_bounds__(WB) void sell_win_pre_restrict_nv_kernel(int64_t n_rows, int win0, SellMat M, const uint16_t* __restrict__ rowloc,
+                                                                      const double* __restrict__ b, const double* __restrict__ dinv,
+                                                                      RestrictMat R) {
+  static_assert(MODE == 1, "the windowed multi-vector down kernel is built for MODE 1 alone");
+  __shared__ double buf[WB * NV];
+  __shared__ double pr[EPT * WB];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int c = win0 + sell_unit(M);
+  const int s = __builtin_amdgcn_readfirstlane(c * (WB / WAVE) + (threadIdx.x >> 6));
+  const int64_t slot = (int64_t)s * WAVE + lane;
+  const int64_t row = (int64_t)c * WB + threadIdx.x;
+  ChunkRestrictNV<WB, EPT, NV> cr;
+  cr.request(c, R);
+  double bi[NV], di = 0.0;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) bi[j] = 0.0;
+  if (row < n_rows) { ldv<NV>(b + row * NV, bi); di = dinv[row]; }
+  if (slot < n_rows) {
+    double acc[NV];
+    sell_row_dot_nv<NV>(M, s, lane, 0, b, acc);
+    const int loc = rowloc[slot];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) buf[loc * NV + j] = acc[j];
+  }
+  __syncthreads();
+  double r[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) r[j] = row < n_rows ? di * bi[j] - buf[threadIdx.x * NV + j] : 0.0;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) buf[threadIdx.x * NV + j] = r[j];      // (same thread, same entries: the residuals replace the row sums)
+  __syncthreads();
+  cr.reduce(buf, pr, R);
+}
+
+// restrict_sum_kernel on the interleaved partial sums part_nv[slot * NV + column]: per column the same optr / oidx order, the same
+// first-two-then-rest additions and the same shuffle tree; RSUM_R coarse rows per lane group
+template <int NV>
+__global__ __launch_bounds__(BLOCK) void restrict_sum_nv_kernel(int64_t n_coarse, const int32_t* __restrict__ optr,
+                                                                const int32_t* __restrict__ oidx,
+                                                                const double* __restrict__ part, double* __restrict__ bc) {
+  const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  const int64_t J0 = (t / RSUM_G) * RSUM_R;
+  const int sub = (int)(t % RSUM_G);
+  int kb[RSUM_R], ke[RSUM_R];
+#pragma unroll
+  for (int r = 0; r < RSUM_R; ++r) {
+    const int64_t J = J0 + r;
+    kb[r] = J < n_coarse ? optr[J] + sub : 0;
+    ke[r] = J < n_coarse ? optr[J + 1] : 0;
+  }
+  double acc[RSUM_R][NV];
+  if (oidx) {
+    int i0[RSUM_R], i1[RSUM_R];
+#pragma unroll
+    for (int r = 0; r < RSUM_R; ++r) {
+      i0[r] = kb[r] < ke[r] ? oidx[kb[r]] : -1;
+      i1[r] = kb[r] + RSUM_G < ke[r] ? oidx[kb[r] + RSUM_G] : -1;
+    }
+#pragma unroll
+    for (int r = 0; r < RSUM_R; ++r) {
+      double p0[NV], p1[NV];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) { p0[j] = 0.0; p1[j] = 0.0; }
+      if (i0[r] >= 0) ldv<NV>(part + (int64_t)i0[r] * NV, p0);
+      if (i1[r] >= 0) ldv<NV>(part + (int64_t)i1[r] * NV, p1);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) acc[r][j] = p0[j] + p1[j];
+    }
+#pragma unroll
+    for (int r = 0; r < RSUM_R; ++r)
+      for (int k = kb[r] + 2 * RSUM_G; k < ke[r]; k += RSUM_G) {
+        double p[NV];
+        ldv<NV>(part + (int64_t)oidx[k] * NV, p);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) acc[r][j] += p[j];
+      }
+  } else {
+#pragma unroll
+    for (int r = 0; r < RSUM_R; ++r) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) acc[r][j] = 0.0;
+      for (int k = kb[r]; k < ke[r]; k += RSUM_G) {            // partials stored row by row (dest)
+        double p[NV];
+        ldv<NV>(part + (int64_t)k * NV, p);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) acc[r][j] += p[j];
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < RSUM_R; ++r) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+#pragma unroll
+      for (int o = RSUM_G >> 1; o > 0; o >>= 1) acc[r][j] += __shfl_xor(acc[r][j], o, RSUM_G);
+    }
+    if (J0 + r < n_coarse && sub == 0) stv<NV>(bc + (J0 + r) * NV, acc[r]);
   }
 }
 

@@ -250,14 +250,23 @@ def check_multi(vecs, sizes, interleaved=False, names=None):
 def check_fuse(fuse):
     """Validate the fuse= keyword of the multi-vector calls (a plain function: no handle, no native call); returns the flag bits:
     False -> 0, True -> AMGX_MULTI_FUSE, "gs" -> AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS (scalar Gauss-Seidel levels fuse too),
-    "gs_block" -> those two | AMGX_MULTI_FUSE_GS_BLOCK (Gauss-Seidel on 2x2 / 3x3 / 6x6 levels fuses too)"""
-    if isinstance(fuse, str) and fuse == "gs":
-        return _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS
-    if isinstance(fuse, str) and fuse == "gs_block":
-        return _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS | _lib.AMGX_MULTI_FUSE_GS_BLOCK
+    "gs_block" -> those two | AMGX_MULTI_FUSE_GS_BLOCK (Gauss-Seidel on 2x2 / 3x3 / 6x6 levels fuses too);
+    "down", "gs+down", "gs_block+down" -> the bits of True, "gs", "gs_block" | AMGX_MULTI_FUSE_DOWN (fused groups run the fused down
+    pass on every level that qualifies)"""
+    if isinstance(fuse, str) and fuse in _FUSE_WORDS:
+        return _FUSE_WORDS[fuse]
     if not isinstance(fuse, (bool, np.bool_)):
-        raise NgsAMGError(f"fuse: need True, False, \"gs\" or \"gs_block\", got {fuse!r}")
+        raise NgsAMGError(f"fuse: need True, False, \"gs\", \"gs_block\", \"down\", \"gs+down\" or \"gs_block+down\", got {fuse!r}")
     return _lib.AMGX_MULTI_FUSE if fuse else 0
+
+
+_FUSE_WORDS = {
+    "gs": _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS,
+    "gs_block": _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS | _lib.AMGX_MULTI_FUSE_GS_BLOCK,
+    "down": _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_DOWN,
+    "gs+down": _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS | _lib.AMGX_MULTI_FUSE_DOWN,
+    "gs_block+down": _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS | _lib.AMGX_MULTI_FUSE_GS_BLOCK | _lib.AMGX_MULTI_FUSE_DOWN,
+}
 
 
 def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V", clev="inv", device=0,
@@ -480,7 +489,9 @@ class DeviceAMGMatrix:
         fuse=True (AMGX_MULTI_FUSE): the wider rule of multi_plan(k, fuse=True) -- Chebyshev and block levels run fused too.
         fuse="gs" (AMGX_MULTI_FUSE_GS as well): scalar Gauss-Seidel levels (block-hybrid or multicolour form) run fused too.
         fuse="gs_block" (AMGX_MULTI_FUSE_GS_BLOCK as well): so does Gauss-Seidel on 2x2 / 3x3 / 6x6 levels (hybrid-block,
-        block-coloured and multicolour forms) -- the default smoother of the elasticity hierarchies."""
+        block-coloured and multicolour forms) -- the default smoother of the elasticity hierarchies.
+        fuse="down", "gs+down", "gs_block+down" (AMGX_MULTI_FUSE_DOWN beside the bits of True, "gs", "gs_block"): the fused groups
+        run the residual + restriction of every level that qualifies in one pass (multi_level_plan)."""
         ff = check_fuse(fuse)
         n = self.sizes[0]
         k, (ab, ax), (lb, lx), dev = check_multi((B, X), (n, n), interleaved, ("B", "X"))
@@ -506,6 +517,64 @@ class DeviceAMGMatrix:
         note = self._lib.amgx_multi_note(self._h, ff) or b""
         return {"fused": int(fused.value), "groups": [int(wd[i]) for i in range(ng.value)], "work_bytes": int(wb.value),
                 "note": note.decode()}
+
+    _LEVEL_PLAN_FORMS = ("literal", "sell", "sell-win")
+
+    def multi_level_plan(self, level, fuse=False):
+        """the down pass of one level in a fused group of a call that carries fuse= (amgx_multi_level_plan): "form" ("literal", "sell"
+        or "sell-win"), "mode" (0 Jacobi from zero, 1 after a block-hybrid sweep, 2 after Chebyshev), "folded_up", "float_image",
+        "lds_bytes" (per workgroup on 4 vectors) and "note", the reason a level stays literal ("" when it does not)"""
+        ff = check_fuse(fuse)
+        if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+            raise NgsAMGError(f"multi_level_plan: level must be an integer, got {level!r}")
+        self._size(int(level))
+        out = (C.c_int32 * 5)()
+        self._ck(self._lib.amgx_multi_level_plan(self._h, int(level), ff, out, 5))
+        note = self._lib.amgx_multi_level_note(self._h, int(level), ff) or b""
+        return {"form": self._LEVEL_PLAN_FORMS[int(out[0])], "mode": int(out[1]), "folded_up": bool(out[2]), "float_image": bool(out[3]),
+                "lds_bytes": int(out[4]), "out": [int(v) for v in out], "note": note.decode()}
+
+    def DownMulti(self, level, B, X=None, x_given=False, interleaved=False, fuse=False):
+        """the down stage of a level per column (amgx_down_multi); returns (X, BC).  B: (k, n_level), or (n_level, k) with
+        interleaved=True.  x_given=False: X is output (allocated like B when None): pre-smoothing from zero, then BC[j] = P^T (B[j] -
+        A X[j]) -- the down stage of the V-cycle, X holds z on a level with the folded prolongation.  x_given=True: X is the
+        iterate after the level's pre-smoothing and only the residual + restriction half runs.  fuse="down" / "gs+down": groups of 4
+        and 2 columns run the multi-vector kernels where the level qualifies (multi_level_plan); a column is the same bit for
+        bit either way."""
+        ff = check_fuse(fuse)
+        if not isinstance(x_given, (bool, np.bool_)):
+            raise NgsAMGError(f"DownMulti: x_given must be True or False, got {x_given!r}")
+        if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+            raise NgsAMGError(f"DownMulti: level must be an integer, got {level!r}")
+        level = int(level)
+        n = self._size(level)
+        if level + 1 >= self.n_levels:
+            raise NgsAMGError(f"DownMulti: level {level} is the coarsest level (no restriction)")
+        if self.ext_sizes[level] != n:
+            raise NgsAMGError(f"DownMulti: level {level} carries ghost columns (rank-partitioned levels are not supported)")
+        if X is None:
+            if x_given:
+                raise NgsAMGError("DownMulti: x_given=True needs X")
+            if _is_torch(B):
+                import torch
+                X = torch.empty_like(B)
+            elif isinstance(B, np.ndarray):
+                X = np.empty_like(B)
+            else:
+                raise NgsAMGError("B: need a 2-D float64 numpy array or CUDA tensor")
+        k, (ab, ax), (lb, lx), dev = check_multi((B, X), (n, n), interleaved, ("B", "X"))
+        nc = self.sizes[level + 1]
+        shape = (nc, k) if interleaved else (k, nc)
+        if dev:
+            import torch
+            BC = torch.empty(shape, dtype=torch.float64, device=B.device)
+            ac = BC.data_ptr()
+        else:
+            BC = np.empty(shape)
+            ac = BC.ctypes.data
+        self._ck(self._lib.amgx_down_multi(self._h, level, k, ab, lb, ax, lx, ac, nc, int(bool(x_given)),
+                                           self._multi_flags(dev, interleaved) | ff))
+        return X, BC
 
     def multi_info(self, k):
         """how a multi-vector call with k columns runs: fused (True: the multi-vector kernels; False: a column loop over the

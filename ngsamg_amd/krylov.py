@@ -127,7 +127,8 @@ class NativeCGSolver(_NativeSolver):
         preconditioner application.  rhs / sol: 2-D float64 arrays or CUDA tensors, shape (k, n) or, interleaved, (n, k); sol holds
         the initial guesses (default 0).  Afterwards `iterations` is a list of k counts and `errors` a list of k histories; a column
         that converged is frozen while the others go on.  fuse=True: AMGX_MULTI_FUSE for the product and the preconditioner; fuse="gs": AMGX_MULTI_FUSE_GS as well;
-        fuse="gs_block": AMGX_MULTI_FUSE_GS_BLOCK as well (Gauss-Seidel on 2x2 / 3x3 / 6x6 levels)."""
+        fuse="gs_block": AMGX_MULTI_FUSE_GS_BLOCK as well (Gauss-Seidel on 2x2 / 3x3 / 6x6 levels); "down", "gs+down", "gs_block+down":
+        AMGX_MULTI_FUSE_DOWN beside the bits of True, "gs", "gs_block" (the fused down pass of the preconditioner's groups)."""
         import ctypes as C
         import numpy as np
         from .device import _is_torch, check_fuse, check_multi

@@ -19,7 +19,12 @@ fuse=True, (a) stays k calls of amgx_apply / amgx_pcg on the same handle; the re
 --smoother gs (with --config cfg2): the library's default smoother, Gauss-Seidel in the block-hybrid form ("hgs" levels), which fuses
 only under AMGX_MULTI_FUSE_GS: (b), (b') and the multi-vector PCG carry fuse="gs"; the result goes to profiles/r21/.
 --smoother gs with --config cfg3 | cfg5: Gauss-Seidel on the 3x3 / 6x6 levels (block-coloured on level 0, hybrid-block below), fused
-only under AMGX_MULTI_FUSE_GS_BLOCK: the calls carry fuse="gs_block"; the result goes to profiles/r22/."""
+only under AMGX_MULTI_FUSE_GS_BLOCK: the calls carry fuse="gs_block"; the result goes to profiles/r22/.
+
+--down (with any of the above; --mat-prec single for the float images of a Chebyshev handle; --tag NAME for a run under switches such
+as AMGX_NO_DIA=1 AMGX_NO_LW=1): a third call per round, (d) = (b) with AMGX_MULTI_FUSE_DOWN as well, and the same for
+amgx_pcg_multi.  The yardstick of (d) is (b) of the same round; every line prints multi_level_plan of the smoothed levels; the result
+goes to profiles/r24/."""
 import argparse
 import json
 import os
@@ -55,6 +60,9 @@ def main():
     ap.add_argument("--no-pcg", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None)
+    ap.add_argument("--down", action="store_true", help="also time the calls with AMGX_MULTI_FUSE_DOWN")
+    ap.add_argument("--mat-prec", default="double", choices=["double", "single"])
+    ap.add_argument("--tag", default="", help="suffix of the result file (runs under environment switches)")
     ap.add_argument("--cycle-only-k", type=int, default=0, help="run nothing but REPS multi-vector cycles of this width (for a kernel trace)")
     args = ap.parse_args()
     import numpy as np
@@ -73,8 +81,13 @@ def main():
     else:
         fuse = args.smoother != "jacobi" or args.config != "cfg2"
     tag = f"{args.config}_{args.smoother}" + (str(args.degree) if args.smoother == "cheby" else "")
+    fuse_down = {False: "down", True: "down", "gs": "gs+down", "gs_block": "gs_block+down"}[fuse]
+    if args.down:
+        tag += ("_f32" if args.mat_prec == "single" else "") + (("_" + args.tag) if args.tag else "")
     if args.out is None:
-        if isinstance(fuse, str):
+        if args.down:
+            args.out = os.path.join(ROOT, "profiles", "r24", f"multi_down_{tag}.json")
+        elif isinstance(fuse, str):
             args.out = os.path.join(ROOT, "profiles", "r21" if fuse == "gs" else "r22", f"multi_gs_{args.config}.json")
         else:
             args.out = os.path.join(ROOT, "profiles", "r14", f"multi_fuse_{tag}.json") if fuse else os.path.join(ROOT, "profiles", "r06", "multi_rhs.json")
@@ -87,6 +100,8 @@ def main():
         H = Hierarchy(Matrix(p.n, p.n, p.bs, p.bs, p.rowptr, p.col, p.val), p.free, p.coords, dim=3, energy=1, max_coarse_size=50,
                       regularize_cmats=0 if rot else 1, spw=1)
     kw = dict(sm_type="cheby", cheb_degree=args.degree) if args.smoother == "cheby" else dict(sm_type="hgs" if args.smoother == "gs" else "jacobi")
+    if args.mat_prec != "double":
+        kw["mat_prec"] = args.mat_prec
     free0, _ = torch.cuda.mem_get_info()
     dev = DeviceAMGMatrix(H, device=0, **kw)
     torch.cuda.synchronize()
@@ -112,6 +127,8 @@ def main():
         Xi = torch.empty_like(Bi)
         torch.cuda.synchronize()
         print("ms per multi cycle:", timed(lambda: dev.MultMulti(Bi, Xi, interleaved=True, fuse=fuse), args.reps))
+        if args.down:
+            print("ms per multi cycle with AMGX_MULTI_FUSE_DOWN:", timed(lambda: dev.MultMulti(Bi, Xi, interleaved=True, fuse=fuse_down), args.reps))
         return
 
     if isinstance(fuse, str) and dev.multi_plan(4, fuse=fuse)["fused"] != 1:
@@ -125,6 +142,13 @@ def main():
         keys = ("gs_form", "gs_lanes", "gs_threads", "gs_block", "gs_colors", "gs_block_colors", "gs_split", "gs_narrow", "gs_mid", "gs_lw", "gs_down")
         out["levels_gs"] = [dict({key: dev.level_paths(l)[key] for key in keys}, rows=int(dev.sizes[l]),
                                  A_stream_bytes=dev.matrix_info(l, "A")["stream_bytes"]) for l in range(H.n_levels - 1)]
+    plans = ""
+    if args.down:
+        out["fuse_down"] = fuse_down
+        out["level_plans"] = [dict(dev.multi_level_plan(l, fuse_down), rows=int(dev.sizes[l]), kernel=dev.level_paths(l)["kernel"],
+                                   gs_down=dev.level_paths(l)["gs_down"]) for l in range(H.n_levels - 1)]
+        plans = "   levels: " + " ".join(f"{l}:{q['form']}" + (f"/{q['mode']}" + ("+Q" if q["folded_up"] else "") + ("/f32" if q["float_image"] else "")
+                                                               if q["form"] != "literal" else f"({q['note']})") for l, q in enumerate(out["level_plans"]))
     for k in ks:
         info = dev.multi_plan(k, fuse=fuse)
         B = rng.standard_normal((k, n)) * pfree
@@ -146,8 +170,13 @@ def main():
         def c():
             dev.MultMulti(Bc, Xc, fuse=fuse)
 
+        Xd = torch.full_like(Bi, float("nan"))
+
+        def d():
+            dev.MultMulti(Bi, Xd, interleaved=True, fuse=fuse_down)
+
         m0, _ = torch.cuda.mem_get_info()
-        for fn in (a, b, c):                                    # warm-up: captures the graphs, allocates the work space
+        for fn in (a, b, c) + ((d,) if args.down else ()):      # warm-up: captures the graphs, allocates the work space
             timed(fn, 3)
         torch.cuda.synchronize()
         m1, _ = torch.cuda.mem_get_info()
@@ -155,20 +184,27 @@ def main():
         Xa = torch.stack(xs)
         worst = 0.0
         for j in range(k):
-            for got in (Xi[:, j], Xc[j]):
+            for got in (Xi[:, j], Xc[j]) + ((Xd[:, j],) if args.down else ()):
                 worst = max(worst, float((got - Xa[j]).norm() / Xa[j].norm()))
         if not worst < 1e-12:
             sys.exit(f"bench_multi_rhs: k = {k}: multi-vector cycle deviates from the single-vector one by {worst:.3e}")
-        ta, tb, tc = [], [], []
+        ta, tb, tc, td = [], [], [], []
         for _ in range(args.rounds):                            # alternating blocks
             ta.append(timed(a, args.reps))
             tb.append(timed(b, args.reps))
             tc.append(timed(c, args.reps))
+            if args.down:
+                td.append(timed(d, args.reps))
         rec = {"multi_info": info, "work_bytes_allocated": int(m0 - m1), "max_rel_diff": worst,
                "cycle": {"single_x_k": _stats(ta), "multi_interleaved": _stats(tb), "multi_colmajor": _stats(tc),
                          "ratio_rounds": [x / y for x, y in zip(ta, tb)], "ratio_median": statistics.median(ta) / statistics.median(tb),
                          "ratio_colmajor_median": statistics.median(ta) / statistics.median(tc),
                          "multi_wins_every_round": all(x > y for x, y in zip(ta, tb))}}
+        if args.down:                                           # (the yardstick of (d) is (b) of the same round)
+            rec["multi_level_plan_bytes"] = dev.multi_plan(k, fuse=fuse_down)["work_bytes"]
+            rec["cycle"].update({"multi_down": _stats(td), "ratio_down_median": statistics.median(ta) / statistics.median(td),
+                                 "multi_over_down_rounds": [x / y for x, y in zip(tb, td)],
+                                 "multi_over_down_median": statistics.median(tb) / statistics.median(td)})
         if not args.no_pcg:
             cg = NativeCGSolver(dev, dev, tol=1e-8, maxsteps=100)
             its_a = []
@@ -189,21 +225,43 @@ def main():
                 pb()
             torch.cuda.synchronize()
             its_b = list(cg.iterations)
+
+            def pd():
+                Xd.zero_()
+                cg.SolveMulti(Bi, Xd, interleaved=True, fuse=fuse_down)
+
+            if args.down:
+                with torch.cuda.stream(stream):
+                    pd()
+                torch.cuda.synchronize()
+                its_d = list(cg.iterations)
+                wd = max(float((Xd[:, j] - xs[j]).norm() / xs[j].norm()) for j in range(k))
+                if not wd < 1e-8 or any(abs(x - y) > 1 for x, y in zip(its_b, its_d)):
+                    sys.exit(f"bench_multi_rhs: k = {k}: PCG with AMGX_MULTI_FUSE_DOWN differs: solutions {wd:.3e}, iterations {its_b} vs {its_d}")
             wp = max(float((Xi[:, j] - xs[j]).norm() / xs[j].norm()) for j in range(k))
             if not wp < 1e-8 or any(abs(x - y) > 1 for x, y in zip(its_a, its_b)):
                 sys.exit(f"bench_multi_rhs: k = {k}: PCG differs: solutions {wp:.3e}, iterations {its_a} vs {its_b}")
-            pta, ptb = [], []
+            pta, ptb, ptd = [], [], []
             for _ in range(args.rounds):
                 pta.append(timed(pa, args.pcg_reps))
                 ptb.append(timed(pb, args.pcg_reps))
+                if args.down:
+                    ptd.append(timed(pd, args.pcg_reps))
             rec["pcg"] = {"iterations_single": list(its_a), "iterations_multi": its_b, "max_rel_diff": wp, "single_x_k": _stats(pta),
                           "multi_interleaved": _stats(ptb), "ratio_rounds": [x / y for x, y in zip(pta, ptb)],
                           "ratio_median": statistics.median(pta) / statistics.median(ptb),
                           "multi_wins_every_round": all(x > y for x, y in zip(pta, ptb))}
+            if args.down:
+                rec["pcg"].update({"iterations_down": its_d, "multi_down": _stats(ptd), "ratio_down_median": statistics.median(pta) / statistics.median(ptd),
+                                   "multi_over_down_rounds": [x / y for x, y in zip(ptb, ptd)],
+                                   "multi_over_down_median": statistics.median(ptb) / statistics.median(ptd)})
         out["k"][str(k)] = rec
         print(f"k = {k}: cycle (a) {statistics.median(ta):.3f} ms  (b) {statistics.median(tb):.3f} ms  (b') {statistics.median(tc):.3f} ms  "
-              f"ratio (a)/(b) {rec['cycle']['ratio_median']:.2f}" + (f"   pcg ratio {rec['pcg']['ratio_median']:.2f}" if "pcg" in rec else ""), flush=True)
-        del bs, xs, Bi, Xi, Bc, Xc
+              f"ratio (a)/(b) {rec['cycle']['ratio_median']:.2f}" + (f"   pcg ratio {rec['pcg']['ratio_median']:.2f}" if "pcg" in rec else "") +
+              (f"   (d) {statistics.median(td):.3f} ms  (a)/(d) {rec['cycle']['ratio_down_median']:.2f}  (b)/(d) {rec['cycle']['multi_over_down_median']:.3f}"
+               f" [{min(rec['cycle']['multi_over_down_rounds']):.3f} .. {max(rec['cycle']['multi_over_down_rounds']):.3f}]" +
+               (f"   pcg (b)/(d) {rec['pcg']['multi_over_down_median']:.3f}" if "pcg" in rec else "") + plans if args.down else ""), flush=True)
+        del bs, xs, Bi, Xi, Bc, Xc, Xd
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
