@@ -74,9 +74,13 @@ enum {
                               /* Gauss-Seidel on 2x2 / 3x3 / 6x6 levels (hybrid-block, block-coloured, multicolour forms, see     */
                               /* below) as well; never an error: a handle that does not qualify runs the column loop.  Without   */
                               /* it every call is as before, calls that carry the two flags above included                      */
-  AMGX_MULTI_FUSE_DOWN = 512  /* the multi-vector calls: a fused column group runs the down pass of every level that qualifies  */
+  AMGX_MULTI_FUSE_DOWN = 512, /* the multi-vector calls: a fused column group runs the down pass of every level that qualifies  */
                               /* as the single-vector fused down kernel on interleaved vectors (see "multi-vectors" below); it   */
                               /* implies nothing and never causes an error.  Without it every call is as before                  */
+  AMGX_MULTI_FUSE_DOWN_DIA = 1024 /* accepted wherever AMGX_MULTI_FUSE_DOWN is; implies it (and nothing else) and admits levels  */
+                              /* whose fused down launch reads the symmetric diagonal image, 512-row or box chunks (see below);   */
+                              /* never an error.  Without it every call is as before, calls that carry AMGX_MULTI_FUSE_DOWN      */
+                              /* included                                                                                        */
 };
 
 typedef struct amgx_level_desc {
@@ -454,6 +458,16 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  * workgroup sizes, levels without the chunk-local restriction, block levels, the multicolour sweep); mixing per level is allowed.
  * Per column the kernels keep the order of additions of the single-vector kernels: a column of amgx_down_multi is the same with
  * and without the bit, bit for bit.  The column loop and k = 1 ignore the bit; amgx_multi_plan counts the partial-sum buffers.
+ * With AMGX_MULTI_FUSE_DOWN_DIA = 1024 (opt-in per call; it implies AMGX_MULTI_FUSE_DOWN and nothing else, and is
+ * looked at by amgx_multi_plan, amgx_multi_note, amgx_multi_level_plan, amgx_multi_level_note, amgx_down_multi, amgx_apply_multi and
+ * amgx_pcg_multi) a level whose fused Jacobi down launch reads the symmetric diagonal image qualifies too, with 512-row chunks (1 .. 8
+ * upper diagonals, 4 or 6 entries of P per thread: form "dia") and with box chunks of grid lines (2 .. 7 upper diagonals: form
+ * "dia-box", dynamic LDS of 8 * (box rows * NV + max(box rows * NV, entries of the fullest box)) bytes, at most 160 KB).  The fold rule
+ * is relaxed as well: a Jacobi level that takes a fused down pass under this flag runs the way up as x = z + Q x_c on the plain
+ * windowed Q even where the single-vector cycle runs the local-window image of Q.  Levels with a local-window image of A' keep the
+ * note "local-window image".  Under AMGX_MULTI_FUSE_DOWN alone "diagonal image" remains the note of such a level and the fold rule is
+ * the one above; the column loop and k = 1 ignore the flag like its neighbours.  A column of amgx_down_multi is the same with and
+ * without it, bit for bit.
  *   amgx_down_multi  : the down stage of a level per column; layout and pointers as in amgx_matvec_multi; B and X have the level's
  *                      size, BC the coarse level's.  The level must be scalar and smoothed, without ghost columns and not
  *                      renumbered.  x_given = 0: X is output -- pre-smoothing from zero, then b_c = P^T (b - A x), the down stage of
@@ -463,7 +477,8 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  *                      AMGX_MULTI_FUSE_DOWN a column loop over the single-vector functions; with it groups of 4 and 2 columns run
  *                      the multi-vector kernels where the level qualifies (a Gauss-Seidel level with x_given = 0 also needs
  *                      AMGX_MULTI_FUSE_GS for its sweep), and a left-over column takes the single-vector path.
- *   amgx_multi_level_plan: out[0 .. 4] = the down form of the level under `flags` (0 literal, 1 sell, 2 windowed sell), the mode
+ *   amgx_multi_level_plan: out[0 .. 4] = the down form of the level under `flags` (0 literal, 1 sell, 2 windowed sell; with AMGX_MULTI_FUSE_DOWN_DIA
+ *                      also 3 diagonal image on 512-row chunks, 4 diagonal image on box chunks), the mode
  *                      (0 Jacobi from zero, 1 after a block-hybrid sweep, 2 after Chebyshev), folded way up (0 / 1), single-precision
  *                      image (0 / 1), bytes of LDS of a workgroup on 4 vectors.  All 0 without AMGX_MULTI_FUSE_DOWN.
  *   amgx_multi_level_note: why the level stays literal under `flags`: "local-window image", "diagonal image", "workgroup size",

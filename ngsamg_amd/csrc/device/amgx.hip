@@ -476,6 +476,7 @@ static DownPlan make_down_plan(const DevLevel& L, const DevRestrict& R, int mode
     need(R.boxed && (int64_t)R.box.nx * R.box.ny * R.box.nz == L.n && rows <= dia::BOX_MAX_ROWS && R.box_lds_doubles >= 2 * rows &&
          R.box_lds_doubles >= rows + R.max_entries && R.box_lds_doubles <= DIA_BOX_LDS_DOUBLES, "box / chunk mismatch");
   p.lds_bytes = (size_t)R.box_lds_doubles * sizeof(double);     // (0 unless the chunks are boxes)
+  if (p.family == DOWN_FAM_DIA_BOX) { p.box_rows = rows; p.max_entries = R.max_entries; }     // (what down_nv_dia_lds_bytes sizes the NV launch from)
   const int64_t expected = p.family == DOWN_FAM_DIA_BOX ? down_expected_chunks(p.family, R.box.n_boxes(), p.threads, p.lanes)
                            : compact                    ? (int64_t)(R.slice_list.n / down_slices_per_chunk(p.threads))
                                                         : down_expected_chunks(p.family, dia ? L.n : M.n_slices, p.threads, p.lanes);
@@ -2352,17 +2353,29 @@ struct Handle {
 
   // down_launch on NV = 2 or 4 interleaved vectors (AMGX_MULTI_FUSE_DOWN): the same plan, the same operands (the
   // vectors of `o` interleaved; dinv of MODE 0 and c of MODE 1 per row), the whole level in one launch.  Which plans have a kernel is
-  // down_nv_ok (down_plan.hpp).  part_nv: n_slots * NV partial sums of the caller (the multi-vector work space), summed into b_coarse
+  // down_nv_ok and, for the diagonal-image families (AMGX_MULTI_FUSE_DOWN_DIA), down_nv_dia_ok (down_plan.hpp).  part_nv: n_slots * NV partial sums of the caller (the multi-vector work space), summed into b_coarse
   template <int NV>
   void down_launch_nv(int l, const DownPlan& p, const DownOps& o, double* part_nv, double* b_coarse) {
     const DevLevel& L = lev[l];
-    if (!down_nv_ok(p, NV)) throw Err("fused multi-vector down pass: the level has no plan for it");
+    if (!down_nv_ok(p, NV) && !down_nv_dia_ok(p, NV)) throw Err("fused multi-vector down pass: the level has no plan for it");
     const DevRestrict& R = p.mode == 1 ? L.RG : L.RF;
     const int grid = p.n_chunks;
     const DevMatrix& M = down_image(L, p.mode, false);
     bool miss = false;
     auto pick = [&](auto list, int value, auto&& run) { if (!dispatch(list, value, run)) miss = true; };
-    if (grid > 0 && p.family == DOWN_FAM_SELL) {
+    if (grid > 0 && p.family == DOWN_FAM_DIA) {
+      // symmetric diagonal image (AMGX_MULTI_FUSE_DOWN_DIA; the rule is down_nv_dia_ok): 512-row chunks
+      pick(DiaDiags{}, p.diags, [&](auto K) { pick(DownEpt{}, p.ept, [&](auto EPT) {
+        launch(dia_pre_restrict_nv_kernel<K(), EPT(), NV>, grid, DOWN_THREADS, 0, stream, (int)L.n, (int)((L.n + WAVE - 1) / WAVE), L.dia.view(), o.v, o.d, o.omega,
+               o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, part_nv, R.dest.p, R.slice_list.p);
+      }); });
+    } else if (grid > 0 && p.family == DOWN_FAM_DIA_BOX) {
+      // ... on box chunks; the dynamic LDS was allowed at create time where it exceeds 64 KB (dia_image, build_level.hpp)
+      pick(DiaBoxDiags{}, p.diags, [&](auto K) {
+        launch(dia_box_pre_restrict_nv_kernel<K(), NV>, grid, DOWN_THREADS, down_nv_dia_lds_bytes(p, NV), stream, (int)L.n, L.dia.view(), R.box, (int)p.box_rows,
+               o.v, o.d, o.omega, o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, part_nv, R.dest.p);
+      });
+    } else if (grid > 0 && p.family == DOWN_FAM_SELL) {
       pick(IntList<0, 1, 2>{}, p.mode, [&](auto MODE) {
         auto image = [&](auto view) {
           using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;       // double / float

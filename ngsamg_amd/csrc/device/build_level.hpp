@@ -275,6 +275,17 @@ static bool dia_image(LevelBuild& B) {
                                    DIA_BOX_LDS_DOUBLES * (int)sizeof(double)));
       };
       if (L.RF.box_lds_doubles * sizeof(double) > 65536) dispatch(DiaBoxDiags{}, K, allow);
+      // ... and so has that of the multi-vector forms (AMGX_MULTI_FUSE_DOWN_DIA, sized by down_nv_dia_lds_bytes), for both widths:
+      // here, at create time, because a call that carries the bit may be the one a stream capture records
+      DownPlan nvp;
+      nvp.family = DOWN_FAM_DIA_BOX; nvp.box_rows = box.box_rows(); nvp.max_entries = L.RF.max_entries;
+      for (int nv : values(DownNvWidths{})) dispatch(DownNvWidths{}, nv, [&](auto NV) {
+        const size_t bytes = down_nv_dia_lds_bytes(nvp, NV());
+        if (bytes <= 65536 || bytes > DOWN_NV_DIA_LDS_MAX) return;
+        dispatch(DiaBoxDiags{}, K, [&](auto KK) {
+          HIPCHK(hipFuncSetAttribute((const void*)dia_box_pre_restrict_nv_kernel<KK(), NV()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DOWN_NV_DIA_LDS_MAX));
+        });
+      });
       return true;
     }
   }

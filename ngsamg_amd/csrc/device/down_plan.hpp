@@ -53,6 +53,7 @@ struct DownPlan {
   // single-precision image
   bool splittable = false, f32 = false;
   size_t lds_bytes = 0;                 // dynamic LDS (dia-box)
+  int64_t box_rows = 0, max_entries = 0; // dia-box: rows of a full box, most entries of P in one box (what the LDS of the NV form holds)
 };
 
 // ---- the same launch on NV = 2 or 4 interleaved vectors (AMGX_MULTI_FUSE_DOWN, DESIGN.md 5.18: sell_pre_restrict_nv_kernel,
@@ -73,6 +74,31 @@ constexpr bool down_nv_ok(const DownPlan& p, int nv) {
   else if (p.family == DOWN_FAM_WIN)
     shape = p.mode == 1 && p.lanes == 1 && contains(DownEpt{}, p.ept);
   return shape && down_nv_lds_bytes(p, nv) <= DOWN_NV_LDS_MAX;
+}
+
+// ---- the diagonal-image launches on NV = 2 or 4 interleaved vectors (AMGX_MULTI_FUSE_DOWN_DIA, DESIGN.md 5.19:
+// dia_pre_restrict_nv_kernel, dia_box_pre_restrict_nv_kernel in multi_kernels.hpp).  A rule of its own beside down_nv_ok, which keeps
+// refusing both families: the capability has its own opt-in bit.
+// LDS of the launch.  512-row chunks: r of the chunk's rows for NV columns + ONE array of products that the columns use in turn
+// (ChunkRestrictNV), static.  Box chunks: r of the box for NV columns, then the published x_j for NV columns, which the products of
+// ONE column at a time replace; dynamic.
+constexpr size_t DOWN_NV_DIA_LDS_MAX = 163840;      // the 160 KiB of LDS a workgroup may declare on gfx950
+constexpr size_t down_nv_dia_lds_bytes(const DownPlan& p, int nv) {
+  if (p.family == DOWN_FAM_DIA) return sizeof(double) * ((size_t)DOWN_THREADS * (size_t)nv + (size_t)p.ept * (size_t)DOWN_THREADS);
+  if (p.family != DOWN_FAM_DIA_BOX) return 0;
+  if (p.box_rows < 0 || p.max_entries < 0) return ~(size_t)0;  // (never a plan of resolve_paths: refused by the bound)
+  const size_t xs = (size_t)p.box_rows * (size_t)nv;
+  return sizeof(double) * (xs + std::max(xs, (size_t)p.max_entries));
+}
+// The LDS bound is a guard, not a filter: a box has at most 2048 rows (dia::BOX_MAX_ROWS) and its entries fit 10240 - box_rows
+// doubles (DIA_BOX_LDS_DOUBLES, the single-vector kernel's LDS), so the fullest box a level can have needs
+// 8 * (4 * 2048 + max(4 * 2048, 8192)) = 128 KiB at NV = 4; the 512-row form needs 40 KiB at most.
+constexpr bool down_nv_dia_ok(const DownPlan& p, int nv) {
+  if (!p.on || !contains(DownNvWidths{}, nv) || p.mode != 0 || p.threads != DOWN_THREADS || p.lanes != 1) return false;
+  bool shape = false;
+  if (p.family == DOWN_FAM_DIA) shape = contains(DiaDiags{}, p.diags) && contains(DownEpt{}, p.ept);
+  else if (p.family == DOWN_FAM_DIA_BOX) shape = contains(DiaBoxDiags{}, p.diags);
+  return shape && down_nv_dia_lds_bytes(p, nv) <= DOWN_NV_DIA_LDS_MAX;
 }
 
 // ---- chunk arithmetic.  A chunk is what one workgroup of `threads` lanes owns: threads / 64 slices = threads / lanes rows

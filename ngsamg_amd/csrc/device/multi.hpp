@@ -56,7 +56,8 @@ struct MultiState {
   DevBuf<double> kr[5];                 // amgx_pcg_multi: b, x, d, w, s (interleaved, width k)
   DevBuf<double> kr_sc, kr_partial;
   DevBuf<int32_t> kr_active;
-  // b, x, k, layout, ldb, ldx, rule in force (0 .. 3; + 4: fused down passes, AMGX_MULTI_FUSE_DOWN on a handle with a level that takes one)
+  // b, x, k, layout, ldb, ldx, rule in force (0 .. 3; + 4: fused down passes, AMGX_MULTI_FUSE_DOWN on a handle with a level that takes one;
+  // + 8: AMGX_MULTI_FUSE_DOWN_DIA on a handle where it changes a level's form or fold)
   using Key = std::tuple<const double*, double*, int, int, int64_t, int64_t, int>;
   GraphCache<Key> graphs;
 };
@@ -68,17 +69,19 @@ struct Multi {
   Handle& h;
   MultiState& st;
   static constexpr int ALL_FLAGS = AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_GS_BLOCK;   // the flags that widen the rule
-  static constexpr int CALL_FLAGS = ALL_FLAGS | AMGX_MULTI_FUSE_DOWN;                                 // ... and the one that implies nothing
+  static constexpr int DOWN_FLAGS = AMGX_MULTI_FUSE_DOWN | AMGX_MULTI_FUSE_DOWN_DIA;                   // (the second implies the first, nothing else)
+  static constexpr int CALL_FLAGS = ALL_FLAGS | DOWN_FLAGS;                                           // ... and the ones that imply nothing about the rule
   const bool block_flag;                // the call carries AMGX_MULTI_FUSE_GS_BLOCK (which implies the two flags below)
   const bool gs_flag;                   // the call carries AMGX_MULTI_FUSE_GS (which implies AMGX_MULTI_FUSE)
   const bool fuse_flag;                 // the call carries AMGX_MULTI_FUSE
   const bool fz;                        // this call runs fused groups
   const bool down_flag;                 // the call carries AMGX_MULTI_FUSE_DOWN: modifies the fused groups, implies nothing
+  const bool dia_flag;                  // the call carries AMGX_MULTI_FUSE_DOWN_DIA: implies down_flag; diagonal-image levels take the pass too
   explicit Multi(Handle& hh, int flags = 0)
       : h(hh), st(state(hh)), block_flag(flags & AMGX_MULTI_FUSE_GS_BLOCK), gs_flag(flags & (AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_GS_BLOCK)),
         fuse_flag(flags & ALL_FLAGS),
         fz(st.fused == 1 || (fuse_flag && st.fused_x == 1) || (gs_flag && st.fused_g == 1) || (block_flag && st.fused_b == 1)),
-        down_flag(flags & AMGX_MULTI_FUSE_DOWN) {}
+        down_flag(flags & DOWN_FLAGS), dia_flag(flags & AMGX_MULTI_FUSE_DOWN_DIA) {}
   // the rule in force: the flags decide the path only where the narrower rule does not hold (a scalar Jacobi handle: one path,
   // one graph; a handle without Gauss-Seidel levels runs the same cycle under all flags, one without block Gauss-Seidel levels
   // the same cycle under the two Gauss-Seidel flags)
@@ -211,8 +214,12 @@ struct Multi {
   // `why` says which property keeps them ("" without the bit, on an empty level and on a level that is not smoothed); form 1 / 2:
   // Handle::down_launch_nv on `plan` (sell / windowed sell).  fold: a Jacobi level whose way up is x = z + Q x_c.  The rule is
   // down_nv_ok (down_plan.hpp) on the plan the single-vector cycle runs for the level's smoother.
+  // AMGX_MULTI_FUSE_DOWN_DIA (`dia`): form 3 / 4: the same launch on a diagonal-image plan with 512-row / box chunks
+  // (rule: down_nv_dia_ok), and a Jacobi level that takes a fused down pass folds the way up through the plain windowed Q even where
+  // the single-vector cycle runs the local-window image QLW of it.  Without that bit both stay as AMGX_MULTI_FUSE_DOWN alone has them.
   struct DownNv { int form = 0, mode = 0; bool fold = false, f32 = false; const DownPlan* plan = nullptr; const char* why = ""; };
-  DownNv level_down(int l) const {
+  DownNv level_down(int l) const { return level_down(l, dia_flag); }
+  DownNv level_down(int l, bool dia) const {
     DownNv d;
     if (!down_flag || l < 0 || l + 1 >= h.n_levels() || h.lev[l].n == 0) return d;
     const DevLevel& V = h.lev[l];
@@ -230,13 +237,19 @@ struct Multi {
     }
     if (!p) { d.why = "no chunk-local restriction"; return d; }
     if (p->family == DOWN_FAM_LW) { d.why = "local-window image"; return d; }
-    if (p->family == DOWN_FAM_DIA || p->family == DOWN_FAM_DIA_BOX) { d.why = "diagonal image"; return d; }
+    if (p->family == DOWN_FAM_DIA || p->family == DOWN_FAM_DIA_BOX) {
+      if (!dia || !down_nv_dia_ok(*p, 2) || !down_nv_dia_ok(*p, 4)) { d.why = "diagonal image"; return d; }
+      d.form = p->family == DOWN_FAM_DIA ? 3 : 4;
+      d.mode = 0; d.plan = p;
+      d.fold = h.folded(V) && !V.Q.empty() && Handle::multi_scalar_ok(V.Q);      // (a diagonal image is a Jacobi level's)
+      return d;
+    }
     if (p->threads != DOWN_THREADS) { d.why = "workgroup size"; return d; }
     // (what is left: the windowed image of A' behind the AMGX_APRE_WINDOW A/B hook, which has no multi-vector kernel)
     if (!down_nv_ok(*p, 2) || !down_nv_ok(*p, 4)) { d.why = "windowed image"; return d; }
     d.form = p->family == DOWN_FAM_SELL ? 1 : 2;
     d.mode = p->mode; d.f32 = p->f32; d.plan = p;
-    d.fold = V.sm_type == AMGX_SM_JACOBI && h.folded(V) && !V.Q.empty() && Handle::multi_scalar_ok(V.Q) && V.QLW.empty();
+    d.fold = V.sm_type == AMGX_SM_JACOBI && h.folded(V) && !V.Q.empty() && Handle::multi_scalar_ok(V.Q) && (dia || V.QLW.empty());
     return d;
   }
   static int64_t down_slots(const DevLevel& V, const DownNv& d) { return d.form ? (d.mode == 1 ? V.RG : V.RF).n_slots : 0; }
@@ -244,6 +257,15 @@ struct Multi {
   bool down_active() const {
     if (!down_flag || !fz) return false;
     for (int l = 0; l < top(); ++l) if (level_down(l).form) return true;
+    return false;
+  }
+  // ... and AMGX_MULTI_FUSE_DOWN_DIA changes the form or the fold of at least one of its levels (part of the key on such handles only)
+  bool dia_active() const {
+    if (!dia_flag || !fz) return false;
+    for (int l = 0; l < top(); ++l) {
+      const DownNv a = level_down(l, true), b = level_down(l, false);
+      if (a.form != b.form || a.fold != b.fold) return true;
+    }
     return false;
   }
   template <class Ops>
@@ -504,7 +526,7 @@ struct Multi {
     const int64_t brs = interleaved ? k : 1, bcs = interleaved ? 1 : ldb, xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx;
     // only the fused path is captured as a whole; the column loop replays the single-vector graphs of run_cycle
     if (!fz || !(h.use_graph && graph_ok) || h.stream == nullptr) { apply_body(k, B, brs, bcs, X, xrs, xcs, graph_ok, false); return; }
-    const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx, rule() + (down_active() ? 4 : 0)};
+    const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx, rule() + (down_active() ? 4 : 0) + (dia_active() ? 8 : 0)};
     if (!st.graphs.has(key)) {
       int32_t wd[MULTI_MAX];
       const int ng = multi_groups(k, true, wd);
@@ -835,7 +857,7 @@ int amgx_multi_level_plan(amgx_handle hh, int level, int flags, int32_t* out, in
     if (!out || n_out < 1) throw amgx::Err("amgx_multi_level_plan: bad arguments");
     amgx::Multi M(h, flags & amgx::Multi::CALL_FLAGS);
     const amgx::Multi::DownNv d = M.level_down(level);
-    const int32_t v[5] = {d.form, d.form ? d.mode : 0, d.fold ? 1 : 0, d.f32 ? 1 : 0, d.form ? (int32_t)amgx::down_nv_lds_bytes(*d.plan, 4) : 0};
+    const int32_t v[5] = {d.form, d.form ? d.mode : 0, d.fold ? 1 : 0, d.f32 ? 1 : 0, d.form >= 3 ? (int32_t)amgx::down_nv_dia_lds_bytes(*d.plan, 4) : d.form ? (int32_t)amgx::down_nv_lds_bytes(*d.plan, 4) : 0};
     for (int i = 0; i < std::min(n_out, 5); ++i) out[i] = v[i];
   });
 }

@@ -427,6 +427,240 @@ __global__ __launch_bounds__(WB) void sell_win_pre_restrict_nv_kernel(int64_t n_
   cr.reduce(buf, pr, R);
 }
 
+// ---- the diagonal-image down kernels on NV interleaved vectors (AMGX_MULTI_FUSE_DOWN_DIA) ----------------------
+// dia_pre_restrict_kernel<K, EPT> on interleaved b and x.  The matrix values U_k[row], U_k[row - o_k] and dinv of the row and of its
+// 2K neighbours are loaded once per row; b of the own row and of the neighbours per column.  Per column the expressions and their
+// order are the single-vector kernel's: lower couplings in descending k, the diagonal term omega * b_i where dinv_i != 0, upper
+// couplings in ascending k, x_j = omega * (dinv_j * b_j) for the neighbours, the Jacobi store with and without EPF_FOLD / EPF_NT.
+// b of the own row is loaded, and x stored, NV wide.  The neighbours' b are requested and consumed dia_nv_cols(K, NV) columns at a
+// time: all operands of four columns at K = 7 are 29 matrix / dinv values + 60 b values, and the compiler requests whatever it sees
+// (195-212 VGPRs, one workgroup per CU).  The passes are therefore kept apart by an opaque copy of the row index, from which the
+// 2K addresses of a pass are formed again instead of being held across all passes: two columns per pass (16-byte loads) up to
+// K = 5, one from K = 6 on -- what stays near the 128 VGPRs of two workgroups per CU, where the single-vector kernel runs.
+// A column's own sequence of operations does not change.
+constexpr int DIA_NV_PAIR_MAX_K = 5;
+constexpr int dia_nv_cols(int K, int NV) { return K <= DIA_NV_PAIR_MAX_K && NV >= 2 ? 2 : 1; }
+template <int K, int EPT, int NV>
+__global__ __launch_bounds__(512) void dia_pre_restrict_nv_kernel(int n_rows, int n_slices, DiaMat D, const double* __restrict__ b,
+                                                                  const double* __restrict__ dinv, double omega, int nt, double* __restrict__ x,
+                                                                  const int32_t* __restrict__ chunk_slot, const int32_t* __restrict__ slot_ptr,
+                                                                  const double* __restrict__ w, const uint16_t* __restrict__ fi,
+                                                                  double* __restrict__ part_nv, const int32_t* __restrict__ dest,
+                                                                  const int32_t* __restrict__ slice_list) {
+  constexpr int FB = 512, HC = dia_nv_cols(K, NV);
+  static_assert(NV % HC == 0, "the columns are taken HC at a time");
+  const RestrictMat R{chunk_slot, slot_ptr, w, fi, part_nv, dest};
+  __shared__ double rl[FB * NV];
+  __shared__ double pr[EPT * FB];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int c = D.xcd ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+  const int sq = c * (FB / WAVE) + (threadIdx.x >> 6);
+  const int s_raw = slice_list ? slice_list[sq] : sq;          // compact chunks: as in the single-vector kernel
+  const int s = __builtin_amdgcn_readfirstlane(s_raw < 0 ? n_slices : s_raw);
+  const int row = s * WAVE + lane;
+  ChunkRestrictNV<FB, EPT, NV> cr;
+  cr.request(c, R);                            // chunk-local restriction data first (nothing of it is consumed before the row product)
+  double* const rrow = rl + threadIdx.x * NV;  // r of this lane's row, all columns
+  if (s < n_slices && row < n_rows) {
+    // per row: the matrix values and dinv (out-of-range neighbours read row i itself and are masked)
+    double al[K], au[K], dl[K], du[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const double* __restrict__ U = D.val + (int64_t)k * n_rows;
+      const int o = D.off[k];
+      const int jl = row - o >= 0 ? row - o : row;
+      const int ju = row + o < n_rows ? row + o : row;
+      al[k] = U[jl]; dl[k] = dinv[jl];
+      au[k] = U[row]; du[k] = dinv[ju];
+    }
+    const double di = dinv[row];
+    const int64_t io = (int64_t)row * NV;
+    double bi[NV], xi[NV];
+    ldv<NV>(b + io, bi);
+#pragma unroll
+    for (int h = 0; h < NV; h += HC) {
+      // per pass: every operand requested before the first product
+      double bl[K][HC], bu[K][HC];
+      int rw = row;                              // (opaque per pass: the pass requests nothing before the pass ahead of it has been consumed)
+      asm volatile("" : "+v"(rw));
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int o = D.off[k];
+        const int jl = rw - o >= 0 ? rw - o : rw;
+        const int ju = rw + o < n_rows ? rw + o : rw;
+        ldv<HC>(b + (int64_t)jl * NV + h, bl[k]);
+        ldv<HC>(b + (int64_t)ju * NV + h, bu[k]);
+      }
+#pragma unroll
+      for (int j = 0; j < HC; ++j) {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = K - 1; k >= 0; --k)
+          if (row - D.off[k] >= 0) acc += al[k] * (omega * (dl[k] * bl[k][j]));
+        if (di != 0.0) acc += omega * bi[h + j];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          if (row + D.off[k] < n_rows) acc += au[k] * (omega * (du[k] * bu[k][j]));
+        const double r = bi[h + j] - acc;
+        xi[h + j] = omega * (di * bi[h + j]);
+        if (nt & EPF_FOLD) xi[h + j] += omega * (di * r);
+        rrow[h + j] = r;
+      }
+    }
+    if (nt & EPF_NT) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) __builtin_nontemporal_store(xi[j], x + io + j);
+    } else stv<NV>(x + io, xi);
+  } else {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) rrow[j] = 0.0;                // padding rows and empty slices: r = 0, nothing written to x
+  }
+  __syncthreads();
+  cr.reduce(rl, pr, R);
+}
+
+// dia_box_pre_restrict_kernel<K> on interleaved vectors: the same dia::BoxGrid arithmetic, up to 4 rows per lane.  The workgroup
+// publishes xs[local * NV + j] = omega * (dinv * b_j) of its rows for all columns first; a row then takes, per column, its in-box
+// neighbours from xs and the others from b_j and dinv as the single-vector kernel does (columns dia_nv_cols(K, NV) at a time, see above);
+// r goes to rl[local * NV + j].  After the barrier the restriction runs ONE column at a time on the one product array that aliases
+// xs: per column the request / products passes of four entries per lane and the slot sums in the single-vector kernel's order, with
+// a barrier between two columns.  w and fi are read again per column (they hit the L2 after the first): holding a box's 13 entries
+// per lane at cfg 2 in registers across the row products is what the single-vector kernel avoids, too.
+// LDS (dynamic, down_nv_dia_lds_bytes): r [lds_rows * NV], then x_j [lds_rows * NV] / the products of one column [most entries of a box].
+template <int K, int NV>
+__global__ __launch_bounds__(512, (NV > 2 ? 2 : 4)) void dia_box_pre_restrict_nv_kernel(int n_rows, DiaMat D, dia::BoxGrid G, int lds_rows,
+                                                                      const double* __restrict__ b, const double* __restrict__ dinv,
+                                                                      double omega, int nt, double* __restrict__ x,
+                                                                      const int32_t* __restrict__ chunk_slot, const int32_t* __restrict__ slot_ptr,
+                                                                      const double* __restrict__ w, const uint16_t* __restrict__ fi,
+                                                                      double* __restrict__ part_nv, const int32_t* __restrict__ dest) {
+  constexpr int FB = 512, RPT = dia::BOX_MAX_ROWS / FB, EB = 4, HC = dia_nv_cols(K, NV);
+  static_assert(NV % HC == 0, "the columns are taken HC at a time");
+  extern __shared__ double box_nv_lds[];
+  double* rl = box_nv_lds;
+  double* xs = box_nv_lds + (size_t)lds_rows * NV;
+  double* pr = xs;
+  const int c = (int)blockIdx.x;
+  const dia::BoxAt at = dia::box_at(G, c);
+  const int nrow = dia::box_nrows(G, at);
+  const int s0 = chunk_slot[c], s1 = chunk_slot[c + 1];
+  const int e0 = slot_ptr[s0], e1 = slot_ptr[s1];
+  // publish x_j of the box's rows, all columns
+#pragma unroll
+  for (int j = 0; j < RPT; ++j) {
+    const int local = (int)threadIdx.x + j * FB;
+    if (local < nrow) {
+      const int row = dia::box_global(G, at, dia::box_row(G, at, local));
+      double bq[NV];
+      ldv<NV>(b + (int64_t)row * NV, bq);
+      const double dq = dinv[row];
+#pragma unroll
+      for (int q = 0; q < NV; ++q) xs[local * NV + q] = omega * (dq * bq[q]);
+    }
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int local = (int)threadIdx.x; local < nrow; local += FB) {
+    const dia::BoxRow br = dia::box_row(G, at, local);
+    const int row = dia::box_global(G, at, br);
+    // per row: the matrix values, and dinv of the out-of-box neighbours (out-of-range neighbours read row i itself and are masked)
+    double al[K], au[K], dl[K], du[K];
+    bool inl[K], inu[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const double* __restrict__ U = D.val + (int64_t)k * n_rows;
+      const int o = D.off[k];
+      const int jl = row - o >= 0 ? row - o : row;
+      const int ju = row + o < n_rows ? row + o : row;
+      inl[k] = dia::box_has(G, at, br, k, false);
+      inu[k] = dia::box_has(G, at, br, k, true);
+      al[k] = U[jl]; au[k] = U[row];
+      dl[k] = 0.0; du[k] = 0.0;
+      if (!inl[k]) dl[k] = dinv[jl];
+      if (!inu[k]) du[k] = dinv[ju];
+    }
+    const double di = dinv[row];
+    const int64_t io = (int64_t)row * NV;
+    double bi[NV], xi[NV];
+    ldv<NV>(b + io, bi);
+#pragma unroll
+    for (int h = 0; h < NV; h += HC) {
+      double bl[K][HC], bu[K][HC];
+      int rw = row;                              // (opaque per pass: the pass requests nothing before the pass ahead of it has been consumed)
+      asm volatile("" : "+v"(rw));
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int o = D.off[k];
+        const int jl = rw - o >= 0 ? rw - o : rw;
+        const int ju = rw + o < n_rows ? rw + o : rw;
+#pragma unroll
+        for (int j = 0; j < HC; ++j) { bl[k][j] = 0.0; bu[k][j] = 0.0; }
+        if (!inl[k]) ldv<HC>(b + (int64_t)jl * NV + h, bl[k]);
+        if (!inu[k]) ldv<HC>(b + (int64_t)ju * NV + h, bu[k]);
+      }
+#pragma unroll
+      for (int j = 0; j < HC; ++j) {
+        const int q = h + j;
+        double acc = 0.0;
+#pragma unroll
+        for (int k = K - 1; k >= 0; --k)
+          if (row - D.off[k] >= 0) {
+            const double xj = inl[k] ? xs[(local - dia::box_local_offset(G, at, k)) * NV + q] : omega * (dl[k] * bl[k][j]);
+            acc += al[k] * xj;
+          }
+        if (di != 0.0) acc += omega * bi[q];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          if (row + D.off[k] < n_rows) {
+            const double xj = inu[k] ? xs[(local + dia::box_local_offset(G, at, k)) * NV + q] : omega * (du[k] * bu[k][j]);
+            acc += au[k] * xj;
+          }
+        const double rj = bi[q] - acc;
+        xi[q] = omega * (di * bi[q]);
+        if (nt & EPF_FOLD) xi[q] += omega * (di * rj);
+        rl[local * NV + q] = rj;
+      }
+    }
+    if (nt & EPF_NT) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) __builtin_nontemporal_store(xi[j], x + io + j);
+    } else stv<NV>(x + io, xi);
+  }
+  // chunk-local restriction, column by column: part_nv[slot * NV + j] = sum over the slot's entries of w * r_lds[fi * NV + j]
+  double wq[EB];
+  int fq[EB];
+  auto request = [&](int eb) {
+#pragma unroll
+    for (int q = 0; q < EB; ++q) {
+      const int e = eb + q * FB;
+      wq[q] = e < e1 ? ld_nt(w + e) : 0.0;
+      fq[q] = e < e1 ? (int)ld_nt(fi + e) : 0;
+    }
+  };
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    auto products = [&](int eb) {
+#pragma unroll
+      for (int q = 0; q < EB; ++q) {
+        const int e = eb + q * FB;
+        if (e < e1) pr[e - e0] = wq[q] * rl[fq[q] * NV + j];
+      }
+    };
+    int eb = e0 + (int)threadIdx.x;
+    request(eb);
+    __syncthreads();                             // column 0: r of the box is complete, x_j no longer read; later: the sums of column j - 1 have read pr
+    products(eb);
+    for (eb += EB * FB; eb < e1; eb += EB * FB) { request(eb); products(eb); }
+    __syncthreads();
+    for (int slot = s0 + (int)threadIdx.x; slot < s1; slot += FB) {
+      const int a = slot_ptr[slot] - e0, bnd = slot_ptr[slot + 1] - e0;
+      double acc = 0.0;
+      for (int k = a; k < bnd; ++k) acc += pr[k];
+      part_nv[(int64_t)(dest ? dest[slot] : slot) * NV + j] = acc;
+    }
+  }
+}
+
 // restrict_sum_kernel on the interleaved partial sums part_nv[slot * NV + column]: per column the same optr / oidx order, the same
 // first-two-then-rest additions and the same shuffle tree; RSUM_R coarse rows per lane group
 template <int NV>

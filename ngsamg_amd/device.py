@@ -252,11 +252,14 @@ def check_fuse(fuse):
     False -> 0, True -> AMGX_MULTI_FUSE, "gs" -> AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS (scalar Gauss-Seidel levels fuse too),
     "gs_block" -> those two | AMGX_MULTI_FUSE_GS_BLOCK (Gauss-Seidel on 2x2 / 3x3 / 6x6 levels fuses too);
     "down", "gs+down", "gs_block+down" -> the bits of True, "gs", "gs_block" | AMGX_MULTI_FUSE_DOWN (fused groups run the fused down
-    pass on every level that qualifies)"""
+    pass on every level that qualifies, DESIGN.md 5.18);
+    "down_dia", "gs+down_dia", "gs_block+down_dia" -> the bits of "down", "gs+down", "gs_block+down" | AMGX_MULTI_FUSE_DOWN_DIA (levels
+    with a diagonal image take the fused down pass too, and such Jacobi levels the folded way up)"""
     if isinstance(fuse, str) and fuse in _FUSE_WORDS:
         return _FUSE_WORDS[fuse]
     if not isinstance(fuse, (bool, np.bool_)):
-        raise NgsAMGError(f"fuse: need True, False, \"gs\", \"gs_block\", \"down\", \"gs+down\" or \"gs_block+down\", got {fuse!r}")
+        raise NgsAMGError(f"fuse: need True, False, \"gs\", \"gs_block\", \"down\", \"gs+down\", \"gs_block+down\", "
+                          f"\"down_dia\", \"gs+down_dia\" or \"gs_block+down_dia\", got {fuse!r}")
     return _lib.AMGX_MULTI_FUSE if fuse else 0
 
 
@@ -267,6 +270,10 @@ _FUSE_WORDS = {
     "gs+down": _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS | _lib.AMGX_MULTI_FUSE_DOWN,
     "gs_block+down": _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS | _lib.AMGX_MULTI_FUSE_GS_BLOCK | _lib.AMGX_MULTI_FUSE_DOWN,
 }
+# (AMGX_MULTI_FUSE_DOWN_DIA implies AMGX_MULTI_FUSE_DOWN: the words carry both bits)
+_FUSE_WORDS["down_dia"] = _FUSE_WORDS["down"] | _lib.AMGX_MULTI_FUSE_DOWN_DIA
+_FUSE_WORDS["gs+down_dia"] = _FUSE_WORDS["gs+down"] | _lib.AMGX_MULTI_FUSE_DOWN_DIA
+_FUSE_WORDS["gs_block+down_dia"] = _FUSE_WORDS["gs_block+down"] | _lib.AMGX_MULTI_FUSE_DOWN_DIA
 
 
 def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V", clev="inv", device=0,
@@ -491,7 +498,9 @@ class DeviceAMGMatrix:
         fuse="gs_block" (AMGX_MULTI_FUSE_GS_BLOCK as well): so does Gauss-Seidel on 2x2 / 3x3 / 6x6 levels (hybrid-block,
         block-coloured and multicolour forms) -- the default smoother of the elasticity hierarchies.
         fuse="down", "gs+down", "gs_block+down" (AMGX_MULTI_FUSE_DOWN beside the bits of True, "gs", "gs_block"): the fused groups
-        run the residual + restriction of every level that qualifies in one pass (multi_level_plan)."""
+        run the residual + restriction of every level that qualifies in one pass (multi_level_plan).
+        fuse="down_dia", "gs+down_dia", "gs_block+down_dia" (AMGX_MULTI_FUSE_DOWN_DIA as well): levels with a diagonal image qualify
+        too, and a Jacobi level that takes the pass runs the way up as x = z + Q x_c."""
         ff = check_fuse(fuse)
         n = self.sizes[0]
         k, (ab, ax), (lb, lx), dev = check_multi((B, X), (n, n), interleaved, ("B", "X"))
@@ -518,11 +527,11 @@ class DeviceAMGMatrix:
         return {"fused": int(fused.value), "groups": [int(wd[i]) for i in range(ng.value)], "work_bytes": int(wb.value),
                 "note": note.decode()}
 
-    _LEVEL_PLAN_FORMS = ("literal", "sell", "sell-win")
+    _LEVEL_PLAN_FORMS = ("literal", "sell", "sell-win", "dia", "dia-box")
 
     def multi_level_plan(self, level, fuse=False):
-        """the down pass of one level in a fused group of a call that carries fuse= (amgx_multi_level_plan): "form" ("literal", "sell"
-        or "sell-win"), "mode" (0 Jacobi from zero, 1 after a block-hybrid sweep, 2 after Chebyshev), "folded_up", "float_image",
+        """the down pass of one level in a fused group of a call that carries fuse= (amgx_multi_level_plan): "form" ("literal", "sell",
+        "sell-win", or with a "..._dia" word "dia" / "dia-box"), "mode" (0 Jacobi from zero, 1 after a block-hybrid sweep, 2 after Chebyshev), "folded_up", "float_image",
         "lds_bytes" (per workgroup on 4 vectors) and "note", the reason a level stays literal ("" when it does not)"""
         ff = check_fuse(fuse)
         if isinstance(level, bool) or not isinstance(level, (int, np.integer)):

@@ -24,7 +24,11 @@ only under AMGX_MULTI_FUSE_GS_BLOCK: the calls carry fuse="gs_b
 --down (with any of the above; --mat-prec single for the float images of a Chebyshev handle; --tag NAME for a run under switches such
 as AMGX_NO_DIA=1 AMGX_NO_LW=1): a third call per round, (d) = (b) with AMGX_MULTI_FUSE_DOWN as well, and the same for
 amgx_pcg_multi.  The yardstick of (d) is (b) of the same round; every line prints multi_level_plan of the smoothed levels; the result
-goes to profiles/r24/."""
+goes to profiles/r24/.
+
+--dia (with --down): one more call per round, (e) = (b) with AMGX_MULTI_FUSE_DOWN_DIA as well (fuse="down_dia"), and
+the same for amgx_pcg_multi.  The yardstick of (e) is (b) of the same round, as for (d); every line prints multi_level_plan of the
+smoothed levels under both words; the result goes to profiles/r25/."""
 import argparse
 import json
 import os
@@ -61,10 +65,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None)
     ap.add_argument("--down", action="store_true", help="also time the calls with AMGX_MULTI_FUSE_DOWN")
+    ap.add_argument("--dia", action="store_true", help="with --down: also time the calls with AMGX_MULTI_FUSE_DOWN_DIA")
     ap.add_argument("--mat-prec", default="double", choices=["double", "single"])
     ap.add_argument("--tag", default="", help="suffix of the result file (runs under environment switches)")
     ap.add_argument("--cycle-only-k", type=int, default=0, help="run nothing but REPS multi-vector cycles of this width (for a kernel trace)")
     args = ap.parse_args()
+    if args.dia and not args.down:
+        sys.exit("bench_multi_rhs: --dia needs --down")
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -82,11 +89,12 @@ def main():
         fuse = args.smoother != "jacobi" or args.config != "cfg2"
     tag = f"{args.config}_{args.smoother}" + (str(args.degree) if args.smoother == "cheby" else "")
     fuse_down = {False: "down", True: "down", "gs": "gs+down", "gs_block": "gs_block+down"}[fuse]
+    fuse_dia = fuse_down + "_dia"
     if args.down:
         tag += ("_f32" if args.mat_prec == "single" else "") + (("_" + args.tag) if args.tag else "")
     if args.out is None:
         if args.down:
-            args.out = os.path.join(ROOT, "profiles", "r24", f"multi_down_{tag}.json")
+            args.out = os.path.join(ROOT, "profiles", "r25", f"multi_down_dia_{tag}.json") if args.dia else os.path.join(ROOT, "profiles", "r24", f"multi_down_{tag}.json")
         elif isinstance(fuse, str):
             args.out = os.path.join(ROOT, "profiles", "r21" if fuse == "gs" else "r22", f"multi_gs_{args.config}.json")
         else:
@@ -129,6 +137,8 @@ def main():
         print("ms per multi cycle:", timed(lambda: dev.MultMulti(Bi, Xi, interleaved=True, fuse=fuse), args.reps))
         if args.down:
             print("ms per multi cycle with AMGX_MULTI_FUSE_DOWN:", timed(lambda: dev.MultMulti(Bi, Xi, interleaved=True, fuse=fuse_down), args.reps))
+        if args.dia:
+            print("ms per multi cycle with AMGX_MULTI_FUSE_DOWN_DIA:", timed(lambda: dev.MultMulti(Bi, Xi, interleaved=True, fuse=fuse_dia), args.reps))
         return
 
     if isinstance(fuse, str) and dev.multi_plan(4, fuse=fuse)["fused"] != 1:
@@ -143,12 +153,23 @@ def main():
         out["levels_gs"] = [dict({key: dev.level_paths(l)[key] for key in keys}, rows=int(dev.sizes[l]),
                                  A_stream_bytes=dev.matrix_info(l, "A")["stream_bytes"]) for l in range(H.n_levels - 1)]
     plans = ""
+
+    def level_plans(word):
+        return [dict(dev.multi_level_plan(l, word), rows=int(dev.sizes[l]), kernel=dev.level_paths(l)["kernel"], compact=dev.level_paths(l)["compact"],
+                     gs_down=dev.level_paths(l)["gs_down"]) for l in range(H.n_levels - 1)]
+
+    def plan_text(lp):
+        return " ".join(f"{l}:{q['form']}" + (f"/{q['mode']}" + ("+Q" if q["folded_up"] else "") + ("/f32" if q["float_image"] else "")
+                                              if q["form"] != "literal" else f"({q['note']})") for l, q in enumerate(lp))
+
     if args.down:
         out["fuse_down"] = fuse_down
-        out["level_plans"] = [dict(dev.multi_level_plan(l, fuse_down), rows=int(dev.sizes[l]), kernel=dev.level_paths(l)["kernel"],
-                                   gs_down=dev.level_paths(l)["gs_down"]) for l in range(H.n_levels - 1)]
-        plans = "   levels: " + " ".join(f"{l}:{q['form']}" + (f"/{q['mode']}" + ("+Q" if q["folded_up"] else "") + ("/f32" if q["float_image"] else "")
-                                                               if q["form"] != "literal" else f"({q['note']})") for l, q in enumerate(out["level_plans"]))
+        out["level_plans"] = level_plans(fuse_down)
+        plans = "   levels: " + plan_text(out["level_plans"])
+    if args.dia:
+        out["fuse_dia"] = fuse_dia
+        out["level_plans_dia"] = level_plans(fuse_dia)
+        plans += "   levels with " + fuse_dia + ": " + plan_text(out["level_plans_dia"])
     for k in ks:
         info = dev.multi_plan(k, fuse=fuse)
         B = rng.standard_normal((k, n)) * pfree
@@ -175,8 +196,13 @@ def main():
         def d():
             dev.MultMulti(Bi, Xd, interleaved=True, fuse=fuse_down)
 
+        Xe = torch.full_like(Bi, float("nan"))
+
+        def e():
+            dev.MultMulti(Bi, Xe, interleaved=True, fuse=fuse_dia)
+
         m0, _ = torch.cuda.mem_get_info()
-        for fn in (a, b, c) + ((d,) if args.down else ()):      # warm-up: captures the graphs, allocates the work space
+        for fn in (a, b, c) + ((d,) if args.down else ()) + ((e,) if args.dia else ()):      # warm-up: captures the graphs, allocates the work space
             timed(fn, 3)
         torch.cuda.synchronize()
         m1, _ = torch.cuda.mem_get_info()
@@ -184,17 +210,19 @@ def main():
         Xa = torch.stack(xs)
         worst = 0.0
         for j in range(k):
-            for got in (Xi[:, j], Xc[j]) + ((Xd[:, j],) if args.down else ()):
+            for got in (Xi[:, j], Xc[j]) + ((Xd[:, j],) if args.down else ()) + ((Xe[:, j],) if args.dia else ()):
                 worst = max(worst, float((got - Xa[j]).norm() / Xa[j].norm()))
         if not worst < 1e-12:
             sys.exit(f"bench_multi_rhs: k = {k}: multi-vector cycle deviates from the single-vector one by {worst:.3e}")
-        ta, tb, tc, td = [], [], [], []
+        ta, tb, tc, td, te = [], [], [], [], []
         for _ in range(args.rounds):                            # alternating blocks
             ta.append(timed(a, args.reps))
             tb.append(timed(b, args.reps))
             tc.append(timed(c, args.reps))
             if args.down:
                 td.append(timed(d, args.reps))
+            if args.dia:
+                te.append(timed(e, args.reps))
         rec = {"multi_info": info, "work_bytes_allocated": int(m0 - m1), "max_rel_diff": worst,
                "cycle": {"single_x_k": _stats(ta), "multi_interleaved": _stats(tb), "multi_colmajor": _stats(tc),
                          "ratio_rounds": [x / y for x, y in zip(ta, tb)], "ratio_median": statistics.median(ta) / statistics.median(tb),
@@ -205,6 +233,12 @@ def main():
             rec["cycle"].update({"multi_down": _stats(td), "ratio_down_median": statistics.median(ta) / statistics.median(td),
                                  "multi_over_down_rounds": [x / y for x, y in zip(tb, td)],
                                  "multi_over_down_median": statistics.median(tb) / statistics.median(td)})
+        if args.dia:                                            # (the yardstick of (e) is (b) of the same round, too)
+            rec["multi_level_plan_bytes_dia"] = dev.multi_plan(k, fuse=fuse_dia)["work_bytes"]
+            rec["cycle"].update({"multi_dia": _stats(te), "ratio_dia_median": statistics.median(ta) / statistics.median(te),
+                                 "multi_over_dia_rounds": [x / y for x, y in zip(tb, te)],
+                                 "multi_over_dia_median": statistics.median(tb) / statistics.median(te),
+                                 "multi_spread": (max(tb) - min(tb)) / statistics.median(tb)})
         if not args.no_pcg:
             cg = NativeCGSolver(dev, dev, tol=1e-8, maxsteps=100)
             its_a = []
@@ -238,15 +272,29 @@ def main():
                 wd = max(float((Xd[:, j] - xs[j]).norm() / xs[j].norm()) for j in range(k))
                 if not wd < 1e-8 or any(abs(x - y) > 1 for x, y in zip(its_b, its_d)):
                     sys.exit(f"bench_multi_rhs: k = {k}: PCG with AMGX_MULTI_FUSE_DOWN differs: solutions {wd:.3e}, iterations {its_b} vs {its_d}")
+            def pe():
+                Xe.zero_()
+                cg.SolveMulti(Bi, Xe, interleaved=True, fuse=fuse_dia)
+
+            if args.dia:
+                with torch.cuda.stream(stream):
+                    pe()
+                torch.cuda.synchronize()
+                its_e = list(cg.iterations)
+                we = max(float((Xe[:, j] - xs[j]).norm() / xs[j].norm()) for j in range(k))
+                if not we < 1e-8 or any(abs(x - y) > 1 for x, y in zip(its_b, its_e)):
+                    sys.exit(f"bench_multi_rhs: k = {k}: PCG with AMGX_MULTI_FUSE_DOWN_DIA differs: solutions {we:.3e}, iterations {its_b} vs {its_e}")
             wp = max(float((Xi[:, j] - xs[j]).norm() / xs[j].norm()) for j in range(k))
             if not wp < 1e-8 or any(abs(x - y) > 1 for x, y in zip(its_a, its_b)):
                 sys.exit(f"bench_multi_rhs: k = {k}: PCG differs: solutions {wp:.3e}, iterations {its_a} vs {its_b}")
-            pta, ptb, ptd = [], [], []
+            pta, ptb, ptd, pte = [], [], [], []
             for _ in range(args.rounds):
                 pta.append(timed(pa, args.pcg_reps))
                 ptb.append(timed(pb, args.pcg_reps))
                 if args.down:
                     ptd.append(timed(pd, args.pcg_reps))
+                if args.dia:
+                    pte.append(timed(pe, args.pcg_reps))
             rec["pcg"] = {"iterations_single": list(its_a), "iterations_multi": its_b, "max_rel_diff": wp, "single_x_k": _stats(pta),
                           "multi_interleaved": _stats(ptb), "ratio_rounds": [x / y for x, y in zip(pta, ptb)],
                           "ratio_median": statistics.median(pta) / statistics.median(ptb),
@@ -255,13 +303,22 @@ def main():
                 rec["pcg"].update({"iterations_down": its_d, "multi_down": _stats(ptd), "ratio_down_median": statistics.median(pta) / statistics.median(ptd),
                                    "multi_over_down_rounds": [x / y for x, y in zip(ptb, ptd)],
                                    "multi_over_down_median": statistics.median(ptb) / statistics.median(ptd)})
+            if args.dia:
+                rec["pcg"].update({"iterations_dia": its_e, "multi_dia": _stats(pte), "ratio_dia_median": statistics.median(pta) / statistics.median(pte),
+                                   "multi_over_dia_rounds": [x / y for x, y in zip(ptb, pte)],
+                                   "multi_over_dia_median": statistics.median(ptb) / statistics.median(pte),
+                                   "multi_spread": (max(ptb) - min(ptb)) / statistics.median(ptb)})
         out["k"][str(k)] = rec
         print(f"k = {k}: cycle (a) {statistics.median(ta):.3f} ms  (b) {statistics.median(tb):.3f} ms  (b') {statistics.median(tc):.3f} ms  "
               f"ratio (a)/(b) {rec['cycle']['ratio_median']:.2f}" + (f"   pcg ratio {rec['pcg']['ratio_median']:.2f}" if "pcg" in rec else "") +
               (f"   (d) {statistics.median(td):.3f} ms  (a)/(d) {rec['cycle']['ratio_down_median']:.2f}  (b)/(d) {rec['cycle']['multi_over_down_median']:.3f}"
                f" [{min(rec['cycle']['multi_over_down_rounds']):.3f} .. {max(rec['cycle']['multi_over_down_rounds']):.3f}]" +
-               (f"   pcg (b)/(d) {rec['pcg']['multi_over_down_median']:.3f}" if "pcg" in rec else "") + plans if args.down else ""), flush=True)
-        del bs, xs, Bi, Xi, Bc, Xc, Xd
+               (f"   pcg (b)/(d) {rec['pcg']['multi_over_down_median']:.3f}" if "pcg" in rec else "") if args.down else "") +
+              (f"   (e) {statistics.median(te):.3f} ms  (a)/(e) {rec['cycle']['ratio_dia_median']:.2f}  (b)/(e) {rec['cycle']['multi_over_dia_median']:.3f}"
+               f" [{min(rec['cycle']['multi_over_dia_rounds']):.3f} .. {max(rec['cycle']['multi_over_dia_rounds']):.3f}]  (b) spread {rec['cycle']['multi_spread']:.3f}" +
+               (f"   pcg (a)/(e) {rec['pcg']['ratio_dia_median']:.2f}  (b)/(e) {rec['pcg']['multi_over_dia_median']:.3f}  (b) spread {rec['pcg']['multi_spread']:.3f}"
+                if "pcg" in rec else "") + f"   work space {rec['multi_level_plan_bytes_dia'] / 2**20:.0f} MiB" if args.dia else "") + plans, flush=True)
+        del bs, xs, Bi, Xi, Bc, Xc, Xd, Xe
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
