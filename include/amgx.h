@@ -156,8 +156,32 @@ typedef struct amgx_level_desc {
                               /*   other form (the row list over block CSR, other block sizes) stay fp64 silently -- amgx_level_extra      */
                               /*   entries 9 .. 11 tell.  AMGX_GS_F32_WIDE=1 at amgx_create: no float images; the rounded values are       */
                               /*   written into fp64 images of exactly those levels and the fp64 kernels run (A/B twin).                   */
+                              /* (jacobi_prec below fills the four bytes that padded the struct after mat_prec: sizeof is unchanged.   */
+                              /*  The Python binding, ngsamg_amd/_lib.py, reaches it by that offset and not through its field list; a   */
+                              /*  field appended after it must be added there as well.)                                                 */
+  int32_t jacobi_prec;        /* AMGX_JACOBI_PREC_*: storage of the matrix images that the passes of a SCALAR JACOBI level read (0 = fp64, */
+                              /*   today's behaviour).  Accepted on smoothed scalar levels (block size 1) with sm_type =   */
+                              /*   AMGX_SM_JACOBI and n_cols == n_rows; an error that names level and field on another smoother, a block   */
+                              /*   level, a rank-partitioned level or a value outside 0 .. 2; ignored on the coarsest level of several.    */
+                              /*   AMGX_JACOBI_PREC_F32: after the level's images exist, each of A (plain sliced-ELL), A' (plain           */
+                              /*   sliced-ELL), the local-window image of A', the symmetric diagonal image, Q (plain sliced-ELL) and the   */
+                              /*   local-window image of Q gets a float value array, the stored fp64 values rounded to nearest, every      */
+                              /*   index array shared.  The images are rounded AS STORED (A' holds a_ij * omega * dinv_j, Q holds           */
+                              /*   (I - omega Dinv A) P), so the handle is not the fp64 cycle on a rounded A except on the literal paths.  */
+                              /*   Images in another format, P, P^T, the restriction data, dinv, the tail program and the dense tail stay  */
+                              /*   fp64.  Every product that the Jacobi step and the cycle launch on the level reads the float images:     */
+                              /*   the fused down pass, EP_PRE, EP_JAC, the residual before the restriction, Q on the way up, the stage    */
+                              /*   entry points amgx_jacobi_pre / amgx_cycle_down / amgx_cycle_up / amgx_jacobi_post, amgx_time_op ops 1,  */
+                              /*   5, 6, 7, 8.  update_res (the residual of a non-zero iterate that a further correction uses),            */
+                              /*   amgx_matvec, amgx_residual, amgx_matvec_multi and the Krylov operator keep the fp64 A.  The fp64 value  */
+                              /*   arrays of A', its local-window form, the diagonal image, Q and its local-window form are released; A    */
+                              /*   keeps both.  A value that rounds to +-inf is an error that names the level.                             */
+                              /*   AMGX_JACOBI_PREC_F32_WIDE (A/B twin): no float arrays; the same rounded values are written at fp64      */
+                              /*   width into exactly those images (A: into a separate array) and the fp64 kernels run -- same bits.       */
+                              /*   AMGX_NO_MAT_F32=1 at amgx_create ignores the request.  amgx_jacobi_prec_info tells what was built.      */
 } amgx_level_desc;
 enum { AMGX_PREC_F64 = 0, AMGX_PREC_F32 = 1 };                    /* amgx_level_desc.mat_prec */
+enum { AMGX_JACOBI_PREC_F64 = 0, AMGX_JACOBI_PREC_F32 = 1, AMGX_JACOBI_PREC_F32_WIDE = 2 };     /* amgx_level_desc.jacobi_prec */
 
 typedef struct amgx_hierarchy_desc {
   int32_t n_levels;
@@ -324,6 +348,16 @@ int amgx_level_paths(amgx_handle h, int level, int64_t* out, int n_out);
 #define AMGX_LEVEL_EXTRA_N 12
 int amgx_level_extra(amgx_handle h, int level, int64_t* out, int n_out);
 
+/* what amgx_level_desc.jacobi_prec gave this level.  Fills out[0 .. min(n_out, AMGX_JACOBI_PREC_INFO_N)):
+ *    0 the passes of this level read float images (0 under AMGX_JACOBI_PREC_F32_WIDE)
+ *    1 bit mask of the images converted: A, A', local-window A', diagonal image, Q, local-window Q = bits 0 .. 5
+ *    2 value bytes of the float arrays (under AMGX_JACOBI_PREC_F32_WIDE: of the rounded fp64 arrays)
+ *    3 fp64 value bytes released
+ *    4 the level is the AMGX_JACOBI_PREC_F32_WIDE twin
+ * Returns 0, or non-zero for a bad level or n_out < 1. */
+#define AMGX_JACOBI_PREC_INFO_N 5
+int amgx_jacobi_prec_info(amgx_handle h, int level, int64_t* out, int n_out);
+
 /* measurement hook for bench.py: launches one hot-path kernel `reps` times on the handle's stream,
  * bracketed by HIP events, and returns the average duration in milliseconds.
  *   op = 0: residual SpMV  r = b - A_level x      (the dominant kernel of the Jacobi V-cycle)
@@ -343,7 +377,8 @@ int amgx_level_extra(amgx_handle h, int level, int64_t* out, int n_out);
  *           colour; the launches per colour of the block multicolour forms); error if the level has no block sweep in the cycle.
  *           On a level with single-precision Gauss-Seidel images it reads them
  * ops 5 and 10 time what the cycle runs: on a level with a single-precision image (mat_prec) they read that image; op 0 is
- * amgx_residual's kernel and reads the fp64 image. */
+ * amgx_residual's kernel and reads the fp64 image.  On a scalar Jacobi level with jacobi_prec != 0 ops 1, 5, 6, 7 and 8 read the
+ * level's single-precision images. */
 int amgx_time_op(amgx_handle h, int level, int op, int reps, double* avg_ms);
 
 /* ---- GSS4: Gauss-Seidel on a subset of the rows, on a compressed device copy ------------------------------------------
@@ -428,6 +463,9 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  * column loop (amgx_multi_note names the smoother and the level).  So does a handle with a Gauss-Seidel level that reads
  * single-precision images (mat_prec = AMGX_PREC_F32): the fused sweeps read fp64 images, and the note says "single-precision
  * Gauss-Seidel images (level l)".
+ * A handle with a scalar Jacobi level that reads single-precision images (jacobi_prec != 0) is not fused under any
+ * of these flags, the default rule included, and amgx_down_multi keeps the column loop on such a level: the multi-vector kernels read
+ * fp64 images.  The note says "single-precision Jacobi images (level l)"; a column equals amgx_apply bit for bit.
  * With AMGX_MULTI_FUSE_GS_BLOCK (opt-in per call; it implies the two flags above) an AMGX_SM_GS level may also have
  * block size 2, 3 or 6, if it is square, in the caller's numbering, plain, and swept in the hybrid-block, the block-coloured, the
  * multicolour BSELL or the multicolour row-list form (compact sweep blocks, gs_block_ids, included), and if its sweep block fits

@@ -414,7 +414,10 @@ class _AMGPreconditioner:
                               mg_cycle=str(f.get("mg_cycle", "V")).upper(), clev="inv" if clev == "inv" else "none",
                               device=self._device, use_graph=bool(f.get("use_graph", True)),
                               cheb_degree=int(f.get("cheb_degree", 2)), cheb_ratio=float(f.get("cheb_ratio", 10)),
-                              mat_prec=_mat_prec_flag(f.get("mat_prec", "double")))
+                              mat_prec=_mat_prec_flag(f.get("mat_prec", "double")),
+                              # ngs_amg_jacobi_prec = double | single | single_wide, or one per level (validated by
+                              # device.jacobi_prec_levels)
+                              jacobi_prec=_mat_prec_flag(f.get("jacobi_prec", "double")))
         self._amg = AMGMatrix(hier, dev)
         if f.get("do_test", False):
             self.Test()
@@ -600,8 +603,9 @@ class _StandaloneSmoother(BaseSmoother):
         super().__init__(AMGMatrix(hier, dev), 0)
 
 
-def CreateJacobiSmoother(mat, freedofs=None, omega=0.9, device=0):
-    return _StandaloneSmoother(mat, freedofs, "jacobi", omega=omega, device=device)
+def CreateJacobiSmoother(mat, freedofs=None, omega=0.9, device=0, jacobi_prec="double"):
+    """jacobi_prec="single": the Jacobi step reads a single-precision image of the matrix."""
+    return _StandaloneSmoother(mat, freedofs, "jacobi", omega=omega, device=device, jacobi_prec=jacobi_prec)
 
 
 def CreateChebyshevSmoother(mat, freedofs=None, degree=2, ratio=10, lambda_max=None, pinv=False, device=0, mat_prec="double"):

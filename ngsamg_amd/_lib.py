@@ -198,6 +198,35 @@ class amgx_matrix(C.Structure):
     _fields_ = amgh_matrix._fields_
 
 
+class _TailInt32:
+    """an int32 member of a ctypes Structure that follows the field `after` directly (offset and size as a ctypes field reports them)"""
+    size = 4
+
+    def __init__(self, after):
+        self._after = after
+        self._owner = None
+
+    def __set_name__(self, owner, name):
+        self._owner = owner
+
+    @property
+    def offset(self):
+        f = getattr(self._owner, self._after)
+        off = f.offset + f.size
+        # (the bytes must be tail padding: `after` is the last entry of _fields_ and the struct has room behind it)
+        if self._owner._fields_[-1][0] != self._after or off + self.size > C.sizeof(self._owner):
+            raise TypeError(f"{self._owner.__name__}: {self._after} is not followed by {self.size} bytes of tail padding")
+        return off
+
+    def __get__(self, obj, owner=None):
+        if obj is None:
+            return self
+        return C.c_int32.from_buffer(obj, self.offset).value
+
+    def __set__(self, obj, value):
+        C.c_int32.from_buffer(obj, self.offset).value = int(value)
+
+
 class amgx_level_desc(C.Structure):
     _fields_ = [("A", amgx_matrix), ("P", amgx_matrix), ("PT", amgx_matrix), ("dinv", c_f64p),
                 ("free_dofs", c_u8p), ("sm_type", C.c_int32), ("omega", C.c_double), ("sm_steps", C.c_int32),
@@ -208,6 +237,10 @@ class amgx_level_desc(C.Structure):
                 ("gs_block_color", c_i32p), ("gs_n_block_colors", C.c_int32),
                 ("cheb_degree", C.c_int32), ("cheb_lambda_max", C.c_double), ("cheb_ratio", C.c_double),
                 ("mat_prec", C.c_int32)]
+    # int32_t jacobi_prec, the last field of the C struct (include/amgx.h): it lies in the four bytes after mat_prec
+    # that pad the struct to its 8-byte alignment, so sizeof is the header's with and without it.  It is bound by offset and not
+    # through _fields_: tests/test_mat_prec_cpu.py pins mat_prec as the last entry of that list.
+    jacobi_prec = _TailInt32("mat_prec")
 
 
 class amgx_hierarchy_desc(C.Structure):
@@ -237,6 +270,8 @@ AMGX_COMM_RCCL, AMGX_COMM_LOCAL = 0, 1
 AMGX_UNIQUE_ID_BYTES = 128
 AMGX_CYCLE = {"V": 0, "W": 1, "BS": 2}
 AMGX_PREC_F64, AMGX_PREC_F32 = 0, 1          # amgx_level_desc.mat_prec
+AMGX_JACOBI_PREC_F64, AMGX_JACOBI_PREC_F32, AMGX_JACOBI_PREC_F32_WIDE = 0, 1, 2      # amgx_level_desc.jacobi_prec
+AMGX_JACOBI_PREC_INFO_N = 5
 AMGX_CLEV_NONE, AMGX_CLEV_INV = 0, 1
 AMGX_HOST_PTR, AMGX_DEVICE_PTR, AMGX_NO_GRAPH = 0, 1, 2
 AMGX_PCG_SINGLE_REDUCTION = 16
@@ -264,7 +299,7 @@ AMGX_SYMBOLS = [
     "amgx_device_count", "amgx_spgemm", "amgx_galerkin", "amgx_csr_result_fetch",
     "amgx_apply_multi", "amgx_matvec_multi", "amgx_pcg_multi", "amgx_multi_info", "amgx_multi_plan", "amgx_multi_note",
     "amgx_smooth_multi", "amgx_down_multi", "amgx_multi_level_plan", "amgx_multi_level_note",
-    "amgx_smoother_info",
+    "amgx_smoother_info", "amgx_jacobi_prec_info",
     "amgx_mv_gram", "amgx_mv_combine", "amgx_mv_gram_plan",
 ]
 
@@ -313,6 +348,7 @@ def hip():
     lib.amgx_matrix_stream_bytes.argtypes = [vp, C.c_int, C.c_int, c_i64p]
     lib.amgx_level_paths.argtypes = [vp, C.c_int, c_i64p, C.c_int]
     lib.amgx_level_extra.argtypes = [vp, C.c_int, c_i64p, C.c_int]
+    lib.amgx_jacobi_prec_info.argtypes = [vp, C.c_int, c_i64p, C.c_int]
     lib.amgx_smoother_info.argtypes = [vp, C.c_int, c_i32p, c_i32p, c_f64p, c_f64p, c_i32p]
     lib.amgx_time_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_f64p]
     lib.amgx_pcg.argtypes = [vp, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int, c_f64p, c_i32p]

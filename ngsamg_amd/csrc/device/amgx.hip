@@ -130,6 +130,7 @@ struct DevMatrix {
     int win = 0;
     DevBuf<uint16_t> rowloc;
     SellMat view() const { return SellMat{slice_ptr.p, col32.p, col16.p, cbase.p, val.p, rowrel, diag_first, wdiag, xcd}; }
+    SellMat view_of(const double* v) const { return SellMat{slice_ptr.p, col32.p, col16.p, cbase.p, v, rowrel, diag_first, wdiag, xcd}; }
     SellMatT<float> view32(const float* v32) const { return SellMatT<float>{slice_ptr.p, col32.p, col16.p, cbase.p, v32, rowrel, diag_first, wdiag, xcd}; }
   } sell;
   struct Rb {                          // rigid-body transfer blocks (kernels.hpp, RbMat): P_ik = w_ik Q(t_ik), or its transpose
@@ -153,6 +154,8 @@ struct DevMatrix {
   // value array of the format above rounded to float, same layout, every index array shared.  Built by mat_f32_image
   // (build_level.hpp); read by the smoother passes of Handle::product and by the fused residual + restriction, by nothing else.
   // also A and the BSELL sweep images of a Gauss-Seidel block level (DevLevel::gs32), read by its sweeps and residuals.
+  // also the images of a scalar Jacobi level with jacobi_prec = AMGX_JACOBI_PREC_F32 (A, A', Q and the local-window
+  // forms; DevLevel::jp32), read by the Jacobi passes of the level.  There the fp64 values of every image but A are released.
   DevBuf<float> val32;
   // The rounded values of A at fp64 width, in the layout of A's format, read by the smoother passes in place of the true ones: under
   // AMGX_GS_F32_WIDE (A/B twin of 5.17; the sweep-only images hold their rounded values in the fp64 array itself), and on a
@@ -320,12 +323,17 @@ struct DevDia {
   int xcd = 0;
   int32_t off[DIA_MAX_UPPER] = {};
   DevBuf<double> val;                   // [K * n]
+  DevBuf<float> val32;                  // the same values as float (mat_f32_image); `val` is released where it exists
   bool on() const { return K > 0; }
-  DiaMat view() const {
-    DiaMat m{val.p, xcd, {}};
+  bool has32() const { return val32.p != nullptr; }
+  template <class V>
+  DiaMatT<V> view_as(const V* v) const {
+    DiaMatT<V> m{v, xcd, {}};
     for (int k = 0; k < DIA_MAX_UPPER; ++k) m.off[k] = off[k];
     return m;
   }
+  DiaMat view() const { return view_as<double>(val.p); }
+  DiaMatT<float> view32() const { return view_as<float>(val32.p); }
 };
 
 struct DevCsr {                         // plain CSR copy for the single-workgroup coarse tail
@@ -400,6 +408,13 @@ struct DevLevel {
   bool gs32 = false, gs32_wide = false;
   int gs32_images = 0;
   int64_t gs32_bytes = 0;
+  // scalar Jacobi level with jacobi_prec != 0 (decided by mat_f32_image).  jp32: the Jacobi passes read the float
+  // images (DevMatrix::val32, DevDia::val32).  jp32_wide: the twin -- the fp64 images hold the rounded values (A: DevMatrix::val64r).
+  // jp_mask: the images converted (A, A', A'-LW, DIA, Q, QLW = bits 0 .. 5); jp_bytes: bytes of the converted value arrays;
+  // jp_released: fp64 value bytes given back.
+  bool jp32 = false, jp32_wide = false;
+  int jp_mask = 0;
+  int64_t jp_bytes = 0, jp_released = 0;
   DevGS gs;
   DevGSB gsb;
   DevBGSB bgsb;
@@ -453,7 +468,7 @@ static DownPlan make_down_plan(const DevLevel& L, const DevRestrict& R, int mode
   DownPlan p;
   p.on = true; p.mode = mode; p.ept = R.ept; p.n_chunks = R.n_chunks;
   p.family = dia ? (jacobi_form == DOWN_DIA ? DOWN_FAM_DIA : DOWN_FAM_DIA_BOX) : lw ? DOWN_FAM_LW : M.sell.win ? DOWN_FAM_WIN : DOWN_FAM_SELL;
-  p.diags = dia ? L.dia.K : 0; p.lanes = dia ? 1 : M.lanes; p.f32 = mode == 2 && M.has32();
+  p.diags = dia ? L.dia.K : 0; p.lanes = dia ? 1 : M.lanes; p.f32 = (mode == 2 && M.has32()) || (mode == 0 && (dia ? L.dia.has32() : M.has32()));
   // (RG and the local-window chunks are always built for DOWN_THREADS lanes; the other builders leave their choice in fused_block)
   p.threads = (mode == 1 || lw) ? DOWN_THREADS : L.fused_block;
   p.unit_rows = down_rows_per_chunk(p.threads, p.lanes);
@@ -1552,13 +1567,17 @@ struct Handle {
     if (NV > 1 && sp.part != PART_ALL) throw Err("multi-vector product: rank-partitioned levels are not supported");
     // the float image exists for non-windowed SELL and BSELL, under EP_RES / EP_CHEB; for BSELL also under EP_MULT on one vector
     // (r = rest x of a Gauss-Seidel block level)
+    // for SELL, on one vector, also under the epilogues of a scalar Jacobi level's passes (EP_PRE on A', EP_JAC on A, EP_AXPY on Q; 5.20)
     constexpr bool EP32 = EP == EP_RES || EP == EP_CHEB;
+    constexpr bool EP32_SELL = EP32 || (NV == 1 && (EP == EP_PRE || EP == EP_JAC || EP == EP_AXPY));
     constexpr bool EP32_BSELL = EP32 || (EP == EP_MULT && NV == 1);
-    const bool f32 = sm_pass && M.has32() && (EP32 || (EP32_BSELL && M.fmt == FMT_BSELL));
+    const bool f32 = sm_pass && M.has32() && (EP32 || (EP32_SELL && M.fmt == FMT_SELL) || (EP32_BSELL && M.fmt == FMT_BSELL));
     if (f32 && !((M.fmt == FMT_SELL && !M.sell.win) || M.fmt == FMT_BSELL)) throw Err("single-precision image on a format that has none");
     // run(view of the image this product reads); has32: a float kernel is instantiated for this format and epilogue
     auto image = [&](auto has32, const auto& v64, const auto& v32, auto&& run) {
       if constexpr (decltype(has32)::value) { if (f32) { run(v32); return; } }
+      // (a scalar Jacobi level with single-precision images keeps only the float values of A', Q: DESIGN.md 5.20)
+      if (!v64.val && M.has32()) throw Err("product: the fp64 values of this image were released (single-precision Jacobi images); only the passes of the level read it");
       run(v64);
     };
     int64_t a, b;                                     // the units [a, b) of the row split that this launch covers
@@ -1589,7 +1608,8 @@ struct Handle {
       unit_range(sp, WAVE / M.lanes, M.n_slices, a, b);
       if (b <= a) return;
       const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-      image(std::bool_constant<EP32>{}, M.sell.view(), M.sell.view32(M.val32.p), [&](auto V) {
+      // (AMGX_JACOBI_PREC_F32_WIDE: a Jacobi pass reads the rounded values of A at fp64 width)
+      image(std::bool_constant<EP32_SELL>{}, sm_pass && M.val64r.p ? M.sell.view_of(M.val64r.p) : M.sell.view(), M.sell.view32(M.val32.p), [&](auto V) {
         using T = std::remove_const_t<std::remove_pointer_t<decltype(V.val)>>;       // double / float
         auto run = [&](auto G) {
           if constexpr (NV == 1) launch(sell_spmv_kernel<G(), EP, T>, grid, BLOCK, 0, stream, M.n_rows, (int)a, (int)b, V, x, y, ep);
@@ -1663,11 +1683,11 @@ struct Handle {
   // the residual a smoother or the cycle forms on its level (update_res, the residual before the restriction): a smoother pass
   void residual_sm(const DevLevel& L, const double* x, const double* b, double* r, const Span sp = Span()) { product<1, EP_RES>(L.A, x, r, EpArgs{b, nullptr, nullptr, 0.0, nullptr, ep_nt & EPF_HOIST}, sp, true); }
   // y = yin + s * M x
-  void mult_add(const DevMatrix& M, double s, const double* x, const double* yin, double* y, const Span sp = Span()) { product<1, EP_AXPY>(M, x, y, EpArgs{nullptr, yin, nullptr, s, nullptr, ep_nt & EPF_HOIST}, sp); }
+  void mult_add(const DevMatrix& M, double s, const double* x, const double* yin, double* y, const Span sp = Span(), bool sm_pass = false) { product<1, EP_AXPY>(M, x, y, EpArgs{nullptr, yin, nullptr, s, nullptr, ep_nt & EPF_HOIST}, sp, sm_pass); }
   // xout = xin + omega * dinv * (b - A xin)
   void jacobi_fused(const DevLevel& L, const double* xin, const double* b, double* xout, const Span sp = Span()) {
     if (xin == xout) throw Err("jacobi_fused: in-place update is not allowed");
-    product<1, EP_JAC>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, L.omega, nullptr, ep_nt}, sp);
+    product<1, EP_JAC>(L.A, xin, xout, EpArgs{b, xin, L.dinv.p, L.omega, nullptr, ep_nt}, sp, true);
   }
 
   // ---- Chebyshev smoother (AMGX_SM_CHEBY) ----
@@ -2160,10 +2180,14 @@ struct Handle {
       // RichardsonSmoother::Smooth, base_smoother.cpp:61-74 (SmoothBack identical)
       if (!res_updated && x_zero) diag_apply(L, b, x, true);
       else {
-        if (!res_updated) residual(L.A, x, b, res);
+        // (the residual inside the Jacobi step is a pass of the smoother: it reads the level's single-precision image)
+        if (!res_updated) residual_sm(L, x, b, res);
         diag_apply(L, res, x, true);
       }
-      if (update_res) residual(L.A, x, b, res);
+      // update_res: inside pre-smoothing from zero (pre_smooth: the residual that goes to the restriction, |r| ~ |b|) a pass of the
+      // level as well; anywhere else (the second visit of a W / BS cycle, amgx_smooth) the residual of an iterate that a further
+      // correction uses, which reads the fp64 A for the reason given at the Gauss-Seidel branch below
+      if (update_res) { if (pre_from_zero) residual_sm(L, x, b, res); else residual(L.A, x, b, res); }
     } else if (L.sm_type == AMGX_SM_CHEBY) {
       // symmetric polynomial smoother: Smooth and SmoothBack are the same operation
       cheb_smooth(L, x, x, b, res, res_updated, update_res, x_zero);
@@ -2185,6 +2209,7 @@ struct Handle {
     }
   }
 
+  bool pre_from_zero = false;           // base_smooth runs inside pre_smooth's step chain from x = 0 (see update_res above)
   void smooth_symm(DevLevel& L, double* x, const double* b, double* res, bool ru, bool ur, bool xz) {
     base_smooth(L, 0, x, b, res, ru, ur, xz);
     base_smooth(L, 1, x, b, res, ur, ur, false);
@@ -2241,23 +2266,23 @@ struct Handle {
     const bool jacobi = P.plain && L.sm_type == AMGX_SM_JACOBI;
     if (jacobi && !L.Apre.empty()) {
       // one pass: r = b - A' b, x = omega * Dinv * b   (A' = A * omega*Dinv built at create time)
-      product<1, EP_PRE>(L.Apre, b, r, EpArgs{b, nullptr, L.dinv.p, L.omega, x, ep_nt | (fold ? EPF_FOLD : 0)}, sp);
+      product<1, EP_PRE>(L.Apre, b, r, EpArgs{b, nullptr, L.dinv.p, L.omega, x, ep_nt | (fold ? EPF_FOLD : 0)}, sp, true);
     } else if (sp.part == PART_INT) {
       return;                                  // the other forms are not split: they run completely in the boundary part
     } else if (jacobi && L.ncols > L.n && !fold) {
       // rank-partitioned level without a pre-smoothing image (block levels): x = omega * Dinv * b is needed on the ghost
       // rows too (their b and dinv entries came with the exchange / the setup), so it is formed in the gathered buffer
       diag_apply(L, b, L.tmp.p, false, L.ncols);
-      residual(L.A, L.tmp.p, b, r);
+      residual_sm(L, L.tmp.p, b, r);
       copy(x, L.tmp.p, L.len());
     } else if (jacobi) {
       if (fold && L.bs > 1) {
         // x_pre = omega * Dinv * b into tmp; then ONE pass: r = b - A x_pre and z = x_pre + omega * Dinv * r
         diag_apply(L, b, L.tmp.p, false);
-        product<1, EP_JAC>(L.A, L.tmp.p, x, EpArgs{b, L.tmp.p, L.dinv.p, L.omega, r, ep_nt});
+        product<1, EP_JAC>(L.A, L.tmp.p, x, EpArgs{b, L.tmp.p, L.dinv.p, L.omega, r, ep_nt}, Span(), true);
       } else {
         diag_apply(L, b, x, false);          // x = omega * Dinv * b      (x was zero, res == b)
-        residual(L.A, x, b, r);              // r = b - A x
+        residual_sm(L, x, b, r);             // r = b - A x (the residual before the restriction: a pass of the level)
         if (fold) diag_apply(L, r, x, true); // z = x + omega * Dinv * r  (folded post-smoothing, see fold_prolongation)
       }
     } else if (P.plain && L.sm_type == AMGX_SM_CHEBY) {
@@ -2269,6 +2294,7 @@ struct Handle {
     } else {
       zero(x, L.len());
       copy(r, b, L.len());
+      struct FromZero { bool& f; explicit FromZero(bool& ff) : f(ff) { f = true; } ~FromZero() { f = false; } } scope(pre_from_zero);
       level_smooth(L, 0, x, b, r, true, true, true);
     }
   }
@@ -2318,7 +2344,8 @@ struct Handle {
             else pick(DownEpt{}, p.ept, [&](auto EPT) { sell(Int<DOWN_THREADS>{}, EPT, Int<1>{}); });
           };
           // (MODE 2 is a smoother pass: the float kernel on the single-precision image where the level has one)
-          if constexpr (MODE() == 2) { if (p.f32) return image(M.sell.view32(M.val32.p)); }
+          // (... and MODE 0 on the float A' of a scalar Jacobi level)
+          if constexpr (MODE() != 1) { if (p.f32) return image(M.sell.view32(M.val32.p)); }
           image(M.sell.view());
         });
       } else if (p.family == DOWN_FAM_WIN) {
@@ -2330,20 +2357,35 @@ struct Handle {
         // long-row level: the local-window image (gathers from LDS), chunks of 512 / lanes rows
         const int32_t *cptr = p.mode == 1 ? L.gsb.lw_cptr.p : L.lw_cptr.p, *ccol = p.mode == 1 ? L.gsb.lw_ccol.p : L.lw_ccol.p;
         pick(IntList<0, 1>{}, p.mode, [&](auto MODE) { pick(DownLwLanes{}, p.lanes, [&](auto G) { pick(DownLwEpt{}, p.ept, [&](auto EPT) {
-          launch(sell_lw_pre_restrict_kernel<EPT(), G(), MODE()>, grid, DOWN_THREADS, 0, stream, M.n_rows, c0, M.n_slices, M.sell.view(), cptr, ccol, o.v, o.d,
-                 o.omega, o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+          auto image = [&](auto view) {
+            using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;       // double / float
+            launch(sell_lw_pre_restrict_kernel<EPT(), G(), MODE(), V>, grid, DOWN_THREADS, 0, stream, M.n_rows, c0, M.n_slices, view, cptr, ccol, o.v, o.d,
+                   o.omega, o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+          };
+          if constexpr (MODE() == 0) { if (p.f32) return image(M.sell.view32(M.val32.p)); }
+          image(M.sell.view());
         }); }); });
       } else if (p.family == DOWN_FAM_DIA) {
         // symmetric diagonal image: 512-row chunks, one thread per row, whole level in one launch
         pick(DiaDiags{}, p.diags, [&](auto K) { pick(DownEpt{}, p.ept, [&](auto EPT) {
-          launch(dia_pre_restrict_kernel<K(), EPT()>, grid, DOWN_THREADS, 0, stream, (int)L.n, (int)((L.n + WAVE - 1) / WAVE), L.dia.view(), o.v, o.d, o.omega,
-                 o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, R.slice_list.p);
+          auto image = [&](auto view) {
+            using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;       // double / float
+            launch(dia_pre_restrict_kernel<K(), EPT(), V>, grid, DOWN_THREADS, 0, stream, (int)L.n, (int)((L.n + WAVE - 1) / WAVE), view, o.v, o.d, o.omega,
+                   o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p, R.slice_list.p);
+          };
+          if (p.f32) image(L.dia.view32());
+          else image(L.dia.view());
         }); });
       } else {
         // ... on box chunks: one 512-lane workgroup per box of grid lines
         pick(DiaBoxDiags{}, p.diags, [&](auto K) {
-          launch(dia_box_pre_restrict_kernel<K()>, grid, DOWN_THREADS, p.lds_bytes, stream, (int)L.n, L.dia.view(), R.box, R.box.box_rows(), o.v, o.d, o.omega,
-                 o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+          auto image = [&](auto view) {
+            using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;       // double / float
+            launch(dia_box_pre_restrict_kernel<K(), V>, grid, DOWN_THREADS, p.lds_bytes, stream, (int)L.n, view, R.box, R.box.box_rows(), o.v, o.d, o.omega,
+                   o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
+          };
+          if (p.f32) image(L.dia.view32());
+          else image(L.dia.view());
         });
       }
     });
@@ -2445,11 +2487,17 @@ struct Handle {
       const int64_t nw = (L.QLW.n_rows + SELL_WIN - 1) / SELL_WIN;
       int64_t wa, wb;
       unit_range(sp, SELL_WIN, nw, wa, wb);
-      if (wb > wa)
-        launch(sell_lw_win_spmv_kernel<SELL_WIN, EP_AXPY>, (int)(wb - wa), SELL_WIN, 0, stream, L.QLW.n_rows, (int)wa, L.QLW.sell.view(), L.QLW.sell.rowloc.p,
+      auto image = [&](auto view) {             // (the float image of a level with single-precision Jacobi images)
+        using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;
+        launch(sell_lw_win_spmv_kernel<SELL_WIN, EP_AXPY, V>, (int)(wb - wa), SELL_WIN, 0, stream, L.QLW.n_rows, (int)wa, view, L.QLW.sell.rowloc.p,
                L.qlw_cptr.p, L.qlw_ccol.p, xc, x, EpArgs{nullptr, x, nullptr, 1.0, nullptr, ep_nt & EPF_HOIST});
+      };
+      if (wb > wa) {
+        if (L.QLW.has32()) image(L.QLW.sell.view32(L.QLW.val32.p));
+        else image(L.QLW.sell.view());
+      }
     } else if (fold) {
-      mult_add(L.Q, 1.0, xc, x, x, sp);
+      mult_add(L.Q, 1.0, xc, x, x, sp, true);
     } else if (sp.part == PART_INT) {
       return;                                  // literal forms are driven stage by stage (Dist), not through this function
     } else if (P.plain && L.sm_type == AMGX_SM_JACOBI) {
@@ -3332,6 +3380,16 @@ int amgx_level_extra(amgx_handle hh, int level, int64_t* out, int n_out) {
     v[8] = (int64_t)h.graphs.size();
     v[9] = L.gs32 ? 1 : 0; v[10] = L.gs32_images; v[11] = L.gs32_bytes;
     for (int k = 0; k < std::min(n_out, AMGX_LEVEL_EXTRA_N); ++k) out[k] = v[k];
+  });
+}
+
+int amgx_jacobi_prec_info(amgx_handle hh, int level, int64_t* out, int n_out) {
+  return guard(hh, [&](amgx::Handle& h) {
+    if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_jacobi_prec_info: level out of range");
+    if (!out || n_out < 1) throw amgx::Err("amgx_jacobi_prec_info: bad arguments");
+    const amgx::DevLevel& L = h.lev[level];
+    const int64_t v[AMGX_JACOBI_PREC_INFO_N] = {L.jp32 ? 1 : 0, L.jp_mask, L.jp_bytes, L.jp_released, L.jp32_wide ? 1 : 0};
+    for (int k = 0; k < std::min(n_out, AMGX_JACOBI_PREC_INFO_N); ++k) out[k] = v[k];
   });
 }
 

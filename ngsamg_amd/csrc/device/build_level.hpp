@@ -63,6 +63,15 @@ static void check_level(LevelBuild& B) {
                 "and on square-block Gauss-Seidel levels (sm_type = AMGX_SM_GS, block size > 1) only");
     if (s.mat_prec == AMGX_PREC_F32 && s.A.n_cols != s.A.n_rows)
       throw Err("amgx_create: level " + std::to_string(B.l) + ": mat_prec = AMGX_PREC_F32 is not available on rank-partitioned levels");
+    // single-precision images of a scalar Jacobi level: a field of its own, mat_prec keeps every error above
+    if (s.jacobi_prec != AMGX_JACOBI_PREC_F64) {
+      const std::string at = "amgx_create: level " + std::to_string(B.l) + ": jacobi_prec ";
+      if (s.jacobi_prec != AMGX_JACOBI_PREC_F32 && s.jacobi_prec != AMGX_JACOBI_PREC_F32_WIDE)
+        throw Err(at + "must be AMGX_JACOBI_PREC_F64 (0), AMGX_JACOBI_PREC_F32 (1) or AMGX_JACOBI_PREC_F32_WIDE (2), got " + std::to_string(s.jacobi_prec));
+      if (s.sm_type != AMGX_SM_JACOBI) throw Err(at + "is available on Jacobi levels (sm_type = AMGX_SM_JACOBI) only");
+      if (s.A.br != 1) throw Err(at + "is available on scalar levels (block size 1) only, not on a block Jacobi level");
+      if (s.A.n_cols != s.A.n_rows || B.dense_first < 0) throw Err(at + "is not available on rank-partitioned levels");
+    }
   }
   check_matrix(s.A, "A");            // (before anything reads rowptr[n_rows]: a NULL / garbage descriptor is an error, not a crash)
 }
@@ -496,9 +505,11 @@ static void cheb_fused_restrict(LevelBuild& B) {
 // amgx_matvec, amgx_residual, the Krylov operator and the lambda_max estimate keep the fp64 image of A.
 // A value that rounds to +-inf is an error that names the level; nothing half-built is left behind.
 // AMGX_NO_MAT_F32=1 ignores every request (the handle is then the double handle, bit for bit).
+static void jacobi_f32_images(LevelBuild& B);
 static void mat_f32_image(LevelBuild& B) {
   const amgx_level_desc& s = B.s;
   DevLevel& L = B.L;
+  if (B.smoothed() && s.jacobi_prec != AMGX_JACOBI_PREC_F64 && !B.K.no_mat_f32) jacobi_f32_images(B);
   if (!B.smoothed() || s.mat_prec != AMGX_PREC_F32 || B.K.no_mat_f32) return;
   auto beyond = [&](int64_t bad, const char* what) {
     return Err("amgx_create: level " + std::to_string(B.l) + ": " + std::to_string(bad) + " value(s) of " + what +
@@ -556,6 +567,82 @@ static void mat_f32_image(LevelBuild& B) {
   static const char* names_hb[] = {"the image `off`", "the image `in`", "the image `upin`", "the image `rest`", "the image `offlo`"};
   for (size_t i = 0; i < sweep_only.size(); ++i) one(*sweep_only[i], form == SWEEP_MC_BSELL ? names_mc[i] : names_hb[i], false);
   (wide ? L.gs32_wide : L.gs32) = true;
+}
+
+// Scalar Jacobi levels with jacobi_prec != 0 (check_level has refused every other level).  The images are rounded AS
+// STORED: A' holds a_ij * omega * dinv_j (its diagonal slot omega * dinv_i under wdiag), Q holds (I - omega Dinv A) P.  Converted, where
+// the level has them: A, A', Q in plain sliced-ELL, the local-window images of A' and Q, the symmetric diagonal image.  CSR-vector and
+// windowed sliced-ELL images, P, P^T, the restriction data, dinv, the tail program's copies and the dense tail stay fp64.
+//   AMGX_JACOBI_PREC_F32: a float value array per image (DevMatrix::val32, DevDia::val32); the fp64 values of every image but A are
+//     released -- only the Jacobi passes read them, and those read the float array from here on.  A keeps both: update_res,
+//     amgx_matvec, amgx_residual and the Krylov operator read the fp64 one.
+//   AMGX_JACOBI_PREC_F32_WIDE: the rounded values at fp64 width, in place (A: DevMatrix::val64r); the fp64 kernels run.
+// Range check first, on every image, before anything is overwritten or released; a value beyond float is an error that names the level.
+static void jacobi_f32_images(LevelBuild& B) {
+  const amgx_level_desc& s = B.s;
+  DevLevel& L = B.L;
+  const bool wide = s.jacobi_prec == AMGX_JACOBI_PREC_F32_WIDE;
+  auto plain_sell = [](const DevMatrix& M) { return !M.empty() && M.fmt == FMT_SELL && !M.sell.win && M.sell.val.n > 0; };
+  // the local-window forms: A' in plain slices with window columns, Q windowed with window columns -- sliced-ELL value arrays both
+  auto lw_sell = [](const DevMatrix& M) { return !M.empty() && M.fmt == FMT_SELL && M.sell.val.n > 0; };
+  struct Img { DevMatrix* M; int bit; const char* what; bool keep64; };
+  std::vector<Img> imgs;
+  if (plain_sell(L.A)) imgs.push_back({&L.A, 0, "A", true});
+  if (plain_sell(L.Apre)) imgs.push_back({&L.Apre, 1, "A'", false});
+  if (lw_sell(L.ApreLW)) imgs.push_back({&L.ApreLW, 2, "the local-window image of A'", false});
+  if (plain_sell(L.Q)) imgs.push_back({&L.Q, 4, "Q", false});
+  if (lw_sell(L.QLW)) imgs.push_back({&L.QLW, 5, "the local-window image of Q", false});
+  const bool dia = L.dia.on() && L.dia.val.n > 0;
+  auto beyond = [&](int64_t bad, const char* what) {
+    return Err("amgx_create: level " + std::to_string(B.l) + ": " + std::to_string(bad) + " value(s) of " + what +
+               " are beyond the range of single precision (jacobi_prec = " + (wide ? "AMGX_JACOBI_PREC_F32_WIDE" : "AMGX_JACOBI_PREC_F32") + ")");
+  };
+  auto undo = [&] {
+    for (const Img& im : imgs) { im.M->val32.release(); im.M->val64r.release(); }
+    L.dia.val32.release();
+    L.jp32 = L.jp32_wide = false; L.jp_mask = 0; L.jp_bytes = L.jp_released = 0;
+  };
+  // pass 1: the float arrays (the wide twin drops them again: its dry run)
+  for (const Img& im : imgs) {
+    const int64_t bad = dev_round_to_f32(im.M->sell.val, im.M->val32);
+    if (bad) { undo(); throw beyond(bad, im.what); }
+    if (wide) im.M->val32.release();
+  }
+  if (dia) {
+    const int64_t bad = dev_round_to_f32(L.dia.val, L.dia.val32);
+    if (bad) { undo(); throw beyond(bad, "the diagonal image"); }
+    if (wide) L.dia.val32.release();
+  }
+  // pass 2: nothing can fail for range any more
+  for (const Img& im : imgs) {
+    const int64_t n = (int64_t)im.M->sell.val.n;
+    if (wide) {
+      if (im.keep64) dev_round_to_f32_wide(im.M->sell.val, im.M->val64r);
+      else dev_round_to_f32_wide(im.M->sell.val, im.M->sell.val);
+    } else if (!im.keep64) {
+      im.M->sell.val.release();
+      L.jp_released += 8 * n;
+    }
+    L.jp_mask |= 1 << im.bit;
+    L.jp_bytes += (wide ? 8 : 4) * n;
+  }
+  if (dia) {
+    const int64_t n = (int64_t)L.dia.val.n;
+    if (wide) dev_round_to_f32_wide(L.dia.val, L.dia.val);
+    else {
+      L.dia.val.release();
+      L.jp_released += 8 * n;
+      // (the float box kernel takes the same dynamic LDS as the fp64 one: more than 64 KB has to be allowed per kernel, once)
+      if (L.RF.boxed && L.RF.box_lds_doubles * sizeof(double) > 65536)
+        dispatch(DiaBoxDiags{}, L.dia.K, [&](auto KK) {
+          HIPCHK(hipFuncSetAttribute((const void*)dia_box_pre_restrict_kernel<KK(), float>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     DIA_BOX_LDS_DOUBLES * (int)sizeof(double)));
+        });
+    }
+    L.jp_mask |= 1 << 3;
+    L.jp_bytes += (wide ? 8 : 4) * n;
+  }
+  if (L.jp_mask) (wide ? L.jp32_wide : L.jp32) = true;
 }
 
 // workgroup -> rows mapping of the streaming kernels on this level (SellMat::xcd)

@@ -370,6 +370,9 @@ static Dist* dist_create(Comm* c, const amgx_dist_desc* d, const Knobs& K) {
         throw Err("amgx_dist_create: level " + std::to_string(l) + ": mat_prec = AMGX_PREC_F32 is not available on rank-partitioned levels");
     }
   }
+  for (int l = 0; l < D->k; ++l)
+    if (d->top.levels[l].jacobi_prec != AMGX_JACOBI_PREC_F64)
+      throw Err("amgx_dist_create: level " + std::to_string(l) + ": jacobi_prec is not available on rank-partitioned levels");
   bool generic = false, gsb = false;
   D->cycle = d->top.cycle;
   if (D->cycle != AMGX_CYCLE_V && D->cycle != AMGX_CYCLE_W) throw Err("amgx_dist_create: rank-partitioned hierarchies run V and W cycles");

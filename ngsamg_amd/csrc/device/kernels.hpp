@@ -369,7 +369,8 @@ __device__ __forceinline__ double sell_row_dot(const SellMat& M, int s, int lane
 }
 
 // SELL-64-pair, scalar, G lanes per row (G = 1: one thread per row), one wave per slice of 64/G rows
-// V = float: the same kernel on the single-precision image (EP_RES and EP_CHEB are instantiated: the smoother passes of a Chebyshev level)
+// V = float: the same kernel on the single-precision image (instantiated under EP_RES and EP_CHEB, the smoother passes of a Chebyshev
+// level, and under EP_PRE, EP_JAC and EP_AXPY, the passes of a scalar Jacobi level on A', A and Q: DESIGN.md 5.20)
 template <int G, int EP, class V = double>
 __global__ __launch_bounds__(BLOCK) void sell_spmv_kernel(int64_t n_rows, int slice0, int n_slices, SellMatT<V> M,
                                                           const double* __restrict__ x, double* y, EpArgs ep) {
@@ -1440,7 +1441,7 @@ __device__ __forceinline__ void jacobi_down_store(double bi, double di, double r
 // EPT: 4: prolongations with <= 3 entries per row; 6: the up to 5 of the reference's "classic" rows
 // G = lanes per row (SELL-G image, long rows of the coarser levels): the chunk then holds FUSED_BLOCK / G rows, the G partial
 // row sums are combined by a wave shuffle and the first lane of every group runs the epilogue
-// V = float (MODE 2 only): A is the single-precision image of the level
+// V = float (MODE 2: A of a Chebyshev level; MODE 0: A' of a scalar Jacobi level): the single-precision image
 // (This kernel and sell_lw_pre_restrict_kernel take the six pointers of RestrictMat one by one: with the struct as a kernel argument
 // the compiler holds more of them in scalar registers across the row product -- 2 to 6 SGPRs more here, one fewer there.)
 template <int FUSED_BLOCK, int MODE = 0, int EPT = 4, int G = 1, class V = double>
@@ -1512,11 +1513,14 @@ __global__ __launch_bounds__(FUSED_BLOCK) void sell_pre_restrict_kernel(int64_t 
 // arrays shifted by o_k -- lines another workgroup streamed shortly before (reuse distance <= o_K rows, ~10 MB of traffic
 // at cfg 2), so they come from L2 / Infinity Cache instead of a second copy of the matrix in HBM.  No index stream.
 constexpr int DIA_MAX_UPPER = 8;
-struct DiaMat {
-  const double* val;          // [K * n]: U_k at val + k * n
+// V = type of the stored values (float: the single-precision image of DESIGN.md 5.20, widened where it is multiplied)
+template <class V>
+struct DiaMatT {
+  const V* val;               // [K * n]: U_k at val + k * n
   int xcd;                    // workgroup -> chunk mapping as SellMat::xcd
   int off[DIA_MAX_UPPER];     // o_1 < ... < o_K
 };
+using DiaMat = DiaMatT<double>;
 
 // Fused Jacobi pre-smoothing + residual + chunk-local restriction (sell_pre_restrict_kernel<512, 0, EPT, 1>) on the DIA
 // image of A itself: A' = A diag(omega Dinv) cannot be stored symmetrically, so the kernel forms the neighbours'
@@ -1526,8 +1530,9 @@ struct DiaMat {
 // (This kernel keeps its own copy of the restriction prologue, epilogue and Jacobi store: with ChunkRestrict it has the same registers
 // and 16 to 23 instructions fewer, and measured 1.4 us slower on level 0 of cfg 2 (357.1 against 355.7 us, profiles/r11/refactor_ab.txt).
 // The ordering rule of ChunkRestrict::request holds for the prologue below.)
-template <int K, int EPT = 4>
-__global__ __launch_bounds__(512) void dia_pre_restrict_kernel(int n_rows, int n_slices, DiaMat D, const double* __restrict__ b,
+// V = float: the diagonals are the single-precision image, held as float and widened where they are multiplied
+template <int K, int EPT = 4, class V = double>
+__global__ __launch_bounds__(512) void dia_pre_restrict_kernel(int n_rows, int n_slices, DiaMatT<V> D, const double* __restrict__ b,
                                                                const double* __restrict__ dinv, double omega, int nt, double* __restrict__ x,
                                                                const int32_t* __restrict__ chunk_slot, const int32_t* __restrict__ slot_ptr,
                                                                const double* __restrict__ w, const uint16_t* __restrict__ fi,
@@ -1564,10 +1569,11 @@ __global__ __launch_bounds__(512) void dia_pre_restrict_kernel(int n_rows, int n
   double r = 0.0;
   if (s < n_slices && row < n_rows) {
     // every operand requested before the first product (out-of-range neighbours read row i itself and are masked)
-    double al[K], au[K], bl[K], bu[K], dl[K], du[K];
+    V al[K], au[K];
+    double bl[K], bu[K], dl[K], du[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      const double* __restrict__ U = D.val + (int64_t)k * n_rows;
+      const V* __restrict__ U = D.val + (int64_t)k * n_rows;
       const int o = D.off[k];
       const int jl = row - o >= 0 ? row - o : row;
       const int ju = row + o < n_rows ? row + o : row;
@@ -1578,11 +1584,11 @@ __global__ __launch_bounds__(512) void dia_pre_restrict_kernel(int n_rows, int n
     double acc = 0.0;
 #pragma unroll
     for (int k = K - 1; k >= 0; --k)
-      if (row - D.off[k] >= 0) acc += al[k] * (omega * (dl[k] * bl[k]));
+      if (row - D.off[k] >= 0) acc += (double)al[k] * (omega * (dl[k] * bl[k]));
     if (di != 0.0) acc += omega * bi;
 #pragma unroll
     for (int k = 0; k < K; ++k)
-      if (row + D.off[k] < n_rows) acc += au[k] * (omega * (du[k] * bu[k]));
+      if (row + D.off[k] < n_rows) acc += (double)au[k] * (omega * (du[k] * bu[k]));
     r = bi - acc;
     double xi = omega * (di * bi);
     if (nt & EPF_FOLD) xi += omega * (di * r);
@@ -1624,8 +1630,8 @@ __global__ __launch_bounds__(512) void dia_pre_restrict_kernel(int n_rows, int n
 // after the last row product, four entries per lane and pass, the first pass ahead of the barrier.
 // Measured at cfg 2 (profiles/r13/box_ab.txt): 358.9 -> 307.3 us, 2.203 -> 1.950 GB of fabric traffic per launch; <7>: 100 VGPRs.
 constexpr int DIA_BOX_LDS_DOUBLES = 10240;    // 80 KB of LDS per workgroup at most: two workgroups per CU (160 KB)
-template <int K>
-__global__ __launch_bounds__(512, 4) void dia_box_pre_restrict_kernel(int n_rows, DiaMat D, dia::BoxGrid G, int lds_rows, const double* __restrict__ b,
+template <int K, class V = double>
+__global__ __launch_bounds__(512, 4) void dia_box_pre_restrict_kernel(int n_rows, DiaMatT<V> D, dia::BoxGrid G, int lds_rows, const double* __restrict__ b,
                                                                       const double* __restrict__ dinv, double omega, int nt, double* __restrict__ x,
                                                                       const int32_t* __restrict__ chunk_slot, const int32_t* __restrict__ slot_ptr,
                                                                       const double* __restrict__ w, const uint16_t* __restrict__ fi,
@@ -1664,11 +1670,12 @@ __global__ __launch_bounds__(512, 4) void dia_box_pre_restrict_kernel(int n_rows
     const dia::BoxRow br = dia::box_row(G, at, local);
     const int row = dia::box_global(G, at, br);
     // every operand requested before the first product (out-of-range neighbours read row i itself and are masked)
-    double al[K], au[K], bl[K], bu[K], dl[K], du[K];
+    V al[K], au[K];
+    double bl[K], bu[K], dl[K], du[K];
     bool inl[K], inu[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      const double* __restrict__ U = D.val + (int64_t)k * n_rows;
+      const V* __restrict__ U = D.val + (int64_t)k * n_rows;
       const int o = D.off[k];
       const int jl = row - o >= 0 ? row - o : row;
       const int ju = row + o < n_rows ? row + o : row;
@@ -1685,14 +1692,14 @@ __global__ __launch_bounds__(512, 4) void dia_box_pre_restrict_kernel(int n_rows
     for (int k = K - 1; k >= 0; --k)
       if (row - D.off[k] >= 0) {
         const double xj = inl[k] ? xs[local - dia::box_local_offset(G, at, k)] : omega * (dl[k] * bl[k]);
-        acc += al[k] * xj;
+        acc += (double)al[k] * xj;
       }
     if (di != 0.0) acc += omega * bi;
 #pragma unroll
     for (int k = 0; k < K; ++k)
       if (row + D.off[k] < n_rows) {
         const double xj = inu[k] ? xs[local + dia::box_local_offset(G, at, k)] : omega * (du[k] * bu[k]);
-        acc += au[k] * xj;
+        acc += (double)au[k] * xj;
       }
     const double r = bi - acc;
     double xi = omega * (di * bi);
@@ -1787,8 +1794,9 @@ constexpr int LW_CAP = 4608;                 // distinct columns per chunk the L
 // MODE 0: Jacobi pre-smoothing from zero as described above (b = right-hand side, dinv, x receives omega*Dinv*b [+ fold]).
 // MODE 1: residual after a block-hybrid Gauss-Seidel sweep from zero, r = c .* x - A_rest x (b = the swept x, dinv = c; nothing is
 //         written to x) -- sell_win_pre_restrict_kernel<.., 1>'s job on a local-window image of A_rest.
-template <int EPT = 4, int G = 2, int MODE = 0>
-__global__ __launch_bounds__(512, (EPT <= 2 ? 6 : 4)) void sell_lw_pre_restrict_kernel(int64_t n_rows, int chunk0, int n_slices, SellMat M,
+// V = float (MODE 0 is instantiated): the single-precision local-window image of A' (DESIGN.md 5.20).
+template <int EPT = 4, int G = 2, int MODE = 0, class V = double>
+__global__ __launch_bounds__(512, (EPT <= 2 ? 6 : 4)) void sell_lw_pre_restrict_kernel(int64_t n_rows, int chunk0, int n_slices, SellMatT<V> M,
                                                                    const int32_t* __restrict__ lw_cptr, const int32_t* __restrict__ lw_ccol,
                                                                    const double* __restrict__ b, const double* __restrict__ dinv,
                                                                    double omega, int nt, double* __restrict__ x,
@@ -1845,8 +1853,8 @@ __global__ __launch_bounds__(512, (EPT <= 2 ? 6 : 4)) void sell_lw_pre_restrict_
 // The 512 fine rows of a window interpolate from only ~400 coarse columns: their values are loaded once (sorted list, ~3 KB) and
 // the row products gather from LDS.  Windows whose list would not fit keep 32-bit global columns.
 constexpr int QW_CAP = 2048;                 // distinct coarse columns per window the LDS stage holds (16 KB)
-template <int WB, int EP>
-__global__ __launch_bounds__(WB) void sell_lw_win_spmv_kernel(int64_t n_rows, int win0, SellMat M, const uint16_t* __restrict__ rowloc,
+template <int WB, int EP, class V = double>
+__global__ __launch_bounds__(WB) void sell_lw_win_spmv_kernel(int64_t n_rows, int win0, SellMatT<V> M, const uint16_t* __restrict__ rowloc,
                                                               const int32_t* __restrict__ lw_cptr, const int32_t* __restrict__ lw_ccol,
                                                               const double* __restrict__ x, double* y, EpArgs ep) {
   __shared__ double buf[WB];

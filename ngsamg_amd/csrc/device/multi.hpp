@@ -109,6 +109,7 @@ struct Multi {
       if (V.bs != 1) { s.why = "block level" + at; return; }
       if (V.n != V.ncols) { s.why = "ghost columns" + at; return; }
       if (h.permuted(l)) { s.why = "renumbered level" + at; return; }
+      if (V.jp32 || V.jp32_wide) { s.why = "single-precision Jacobi images" + at; return; }     // (the NV kernels read fp64 images)
       if (V.n > 0 && !Handle::multi_scalar_ok(V.A)) { s.why = "level matrix format" + at; return; }
       if (l + 1 == L) break;
       if (V.sm_type != AMGX_SM_JACOBI) { s.why = "smoother is not Jacobi" + at; return; }
@@ -137,6 +138,7 @@ struct Multi {
       if (V.bs != 1 && V.bs != 2 && V.bs != 3 && V.bs != 6) { s.why_x = "block size is not 1, 2, 3 or 6" + at; return; }
       if (V.n != V.ncols) { s.why_x = "ghost columns" + at; return; }
       if (h.permuted(l)) { s.why_x = "renumbered level" + at; return; }
+      if (V.jp32 || V.jp32_wide) { s.why_x = "single-precision Jacobi images" + at; return; }     // (the NV kernels read fp64 images)
       if (V.n > 0 && (!Handle::multi_level_ok(V.A) || V.A.br != V.bs)) { s.why_x = "level matrix format" + at; return; }
       if (smoothed && V.n > 0 && (!Handle::multi_transfer_ok(V.P) || !Handle::multi_transfer_ok(V.PT))) { s.why_x = "transfer format" + at; return; }
     }
@@ -165,6 +167,7 @@ struct Multi {
       if (V.bs != 1 && V.bs != 2 && V.bs != 3 && V.bs != 6) { s.why_g = "block size is not 1, 2, 3 or 6" + at; return; }
       if (V.n != V.ncols) { s.why_g = "ghost columns" + at; return; }
       if (h.permuted(l)) { s.why_g = "renumbered level" + at; return; }
+      if (V.jp32 || V.jp32_wide) { s.why_g = "single-precision Jacobi images" + at; return; }     // (the NV kernels read fp64 images)
       if (gs && V.n > 0 && !h.multi_sweep_ok(V)) { s.why_g = "Gauss-Seidel sweep form without a multi-vector kernel" + at; return; }
       if (V.n > 0 && (!Handle::multi_level_ok(V.A) || V.A.br != V.bs)) { s.why_g = "level matrix format" + at; return; }
       if (smoothed && V.n > 0 && (!Handle::multi_transfer_ok(V.P) || !Handle::multi_transfer_ok(V.PT))) { s.why_g = "transfer format" + at; return; }
@@ -194,6 +197,7 @@ struct Multi {
       if (V.bs != 1 && V.bs != 2 && V.bs != 3 && V.bs != 6) { s.why_b = "block size is not 1, 2, 3 or 6" + at; return; }
       if (V.n != V.ncols) { s.why_b = "ghost columns" + at; return; }
       if (h.permuted(l)) { s.why_b = "renumbered level" + at; return; }
+      if (V.jp32 || V.jp32_wide) { s.why_b = "single-precision Jacobi images" + at; return; }     // (the NV kernels read fp64 images)
       if (gs && V.n > 0) {
         // (the fused sweeps read fp64 images: the column loop keeps a column equal to amgx_apply, bit for bit)
         if (V.gs32 || V.gs32_wide) { s.why_b = "single-precision Gauss-Seidel images" + at; return; }
@@ -224,6 +228,7 @@ struct Multi {
     if (!down_flag || l < 0 || l + 1 >= h.n_levels() || h.lev[l].n == 0) return d;
     const DevLevel& V = h.lev[l];
     if (V.bs != 1) { d.why = "block level"; return d; }
+    if (V.jp32 || V.jp32_wide) { d.why = "single-precision Jacobi images"; return d; }     // (the NV kernels read fp64 images)
     const DownPlan* p = nullptr;
     if (V.n == V.ncols && !h.permuted(l) && !h.permuted(l + 1) && h.plain(V)) {
       if (V.sm_type == AMGX_SM_GS) {

@@ -88,6 +88,38 @@ def mat_prec_levels(mat_prec, types):
     return out
 
 
+_JPREC = {"double": _lib.AMGX_JACOBI_PREC_F64, "single": _lib.AMGX_JACOBI_PREC_F32, "single_wide": _lib.AMGX_JACOBI_PREC_F32_WIDE}
+
+
+def jacobi_prec_levels(jacobi_prec, types, block_sizes=None):
+    """amgx_level_desc.jacobi_prec of every level for the smoother types `types` and the block sizes of the level
+    matrices (one each per level, the last = the coarsest, which ignores the field; block_sizes None: all scalar).  jacobi_prec:
+    "double", "single", "single_wide" (the A/B twin: rounded values at fp64 width) or a per-level list of them.  A scalar request
+    applies to the scalar Jacobi levels and needs at least one; a list may name such levels only."""
+    n = len(types)
+    bs = list(block_sizes) if block_sizes is not None else [1] * n
+    per_level = isinstance(jacobi_prec, (list, tuple))
+    vals = list(jacobi_prec) if per_level else [jacobi_prec] * n
+    if len(vals) != n or len(bs) != n:
+        raise NgsAMGError("jacobi_prec list must have one entry per level")
+    for v in vals:
+        if not isinstance(v, str) or v not in _JPREC:
+            raise NgsAMGError(f"unknown jacobi_prec {v!r} (double | single | single_wide)")
+    out = [0] * n
+    for i in (range(n - 1) if n > 1 else range(n)):       # smoothed levels (a single level: a stand-alone smoother)
+        if vals[i] == "double":
+            continue
+        if types[i] == "jacobi" and bs[i] == 1:
+            out[i] = _JPREC[vals[i]]
+        elif per_level:
+            raise NgsAMGError(f"jacobi_prec '{vals[i]}' on level {i}: single-precision Jacobi images are available on scalar Jacobi "
+                              f"levels only (sm_type '{types[i]}', block size {bs[i]})")
+    if not per_level and jacobi_prec != "double" and not any(out):
+        raise NgsAMGError(f"jacobi_prec '{jacobi_prec}': the hierarchy has no scalar Jacobi level (sm_type 'jacobi', block size 1) "
+                          "to apply it to")
+    return out
+
+
 def gs_block_rows(A):
     """rows per block of the block-hybrid Gauss-Seidel kernel for a scalar level matrix.  G lanes share a row, each holds
     at most 16 entries (+1 when G = 1) in registers; the workgroup has B * G lanes.  Measured at cfg 2:
@@ -277,19 +309,22 @@ _FUSE_WORDS["gs_block+down_dia"] = _FUSE_WORDS["gs_block+down"] | _lib.AMGX_MULT
 
 
 def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V", clev="inv", device=0,
-                   use_graph=True, cheb_degree=2, cheb_ratio=10, cheb_lambda_max=None, mat_prec="double"):
+                   use_graph=True, cheb_degree=2, cheb_ratio=10, cheb_lambda_max=None, mat_prec="double", jacobi_prec="double"):
     """amgx_hierarchy_desc over the host arrays of a hierarchy.  Returns (desc, keep): `keep` holds everything the
     descriptor points to and must outlive the amgx_create / amgx_dist_create call.
     cheb_*: levels with sm_type "cheby" (each a scalar or a per-level list); the descriptor carries 0 for a default
     (degree 2, ratio 10) and for a lambda_max that amgx_create estimates on the device.
     mat_prec: "double" (default), "single" (single-precision storage of A for the smoother passes of the Chebyshev levels),
-    "single_gs" (the same, and the images of the block Gauss-Seidel sweeps) or a per-level list; see mat_prec_levels."""
+    "single_gs" (the same, and the images of the block Gauss-Seidel sweeps) or a per-level list; see mat_prec_levels.
+    jacobi_prec: "double" (default), "single" (single-precision images of A, A', Q and the diagonal image for the passes of the
+    scalar Jacobi levels), "single_wide" (its A/B twin) or a per-level list; see jacobi_prec_levels."""
     levels = hierarchy.levels
     n = len(levels)
     types = sm_type if isinstance(sm_type, (list, tuple)) else [sm_type] * n
     if len(types) != n:
         raise NgsAMGError("sm_type list must have one entry per level")
     prec = mat_prec_levels(mat_prec, types)
+    jprec = jacobi_prec_levels(jacobi_prec, types, [lv.A.br for lv in levels])
     arr = (_lib.amgx_level_desc * n)()
     keep = [arr, hierarchy]
     info = [None] * n            # per level: block-hybrid Gauss-Seidel data actually used (tests configure the oracle with it)
@@ -311,6 +346,7 @@ def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False
             d.cheb_ratio = 0.0 if rat == 10.0 else rat
         # (a scalar Gauss-Seidel level has no sweep form with single-precision images: "single_gs" leaves it fp64)
         d.mat_prec = 0 if types[i] in ("gs", "hgs") and lv.A.br == 1 else prec[i]
+        d.jacobi_prec = jprec[i]
         d.omega = float(omega)
         d.sm_steps = int(sm_steps[i] if isinstance(sm_steps, (list, tuple)) else sm_steps)      # per level: ..._spec flags
         d.sm_symm = int(bool(sm_symm[i] if isinstance(sm_symm, (list, tuple)) else sm_symm))
@@ -388,7 +424,11 @@ def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False
 
 class DeviceAMGMatrix:
     def __init__(self, hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V",
-                 clev="inv", device=0, use_graph=True, cheb_degree=2, cheb_ratio=10, cheb_lambda_max=None, mat_prec="double"):
+                 clev="inv", device=0, use_graph=True, cheb_degree=2, cheb_ratio=10, cheb_lambda_max=None, mat_prec="double",
+                 jacobi_prec="double"):
+        if jacobi_prec != "double":          # (the same: refused before the library is loaded)
+            jacobi_prec_levels(jacobi_prec, list(sm_type) if isinstance(sm_type, (list, tuple)) else [sm_type] * len(hierarchy.levels),
+                               [lv.A.br for lv in hierarchy.levels])
         if mat_prec != "double":             # a request that cannot be met is refused before the library is loaded
             n_lev = len(hierarchy.levels)
             mat_prec_levels(mat_prec, list(sm_type) if isinstance(sm_type, (list, tuple)) else [sm_type] * n_lev)
@@ -396,10 +436,10 @@ class DeviceAMGMatrix:
         self._lib = lib
         self._cfg = dict(sm_type=sm_type, omega=omega, sm_steps=sm_steps, sm_symm=sm_symm, mg_cycle=mg_cycle, clev=clev,
                          device=device, use_graph=use_graph, cheb_degree=cheb_degree, cheb_ratio=cheb_ratio,
-                         cheb_lambda_max=cheb_lambda_max, mat_prec=mat_prec)
+                         cheb_lambda_max=cheb_lambda_max, mat_prec=mat_prec, jacobi_prec=jacobi_prec)
         self.hierarchy = hierarchy
         desc, self._keep, self.hgs = hierarchy_desc(hierarchy, sm_type, omega, sm_steps, sm_symm, mg_cycle, clev, device, use_graph,
-                                                    cheb_degree, cheb_ratio, cheb_lambda_max, mat_prec)
+                                                    cheb_degree, cheb_ratio, cheb_lambda_max, mat_prec, jacobi_prec)
         self._h = C.c_void_p()
         self._owned = True
         if lib.amgx_create(C.byref(desc), C.byref(self._h)) != 0:
@@ -765,6 +805,20 @@ class DeviceAMGMatrix:
         self._ck(self._lib.amgx_level_extra(self._h, int(level), out.ctypes.data_as(_lib.c_i64p), out.size))
         d = dict(zip(self._EXTRA_KEYS, (int(v) for v in out)))
         d["tail_gs_lds"] = None if d["tail_gs_lds"] < 0 else d["tail_gs_lds"]
+        return d
+
+    _JPREC_KEYS = ("f32", "images", "bytes", "released", "wide")
+    _JPREC_IMAGES = ("A", "Apre", "ApreLW", "dia", "Q", "QLW")
+
+    def jacobi_prec_info(self, level):
+        """what jacobi_prec gave a level (amgx_jacobi_prec_info): whether its passes read float images ("f32"; 0
+        under "single_wide"), the tuple of the images converted ("images": of A, Apre, ApreLW, dia, Q, QLW; "mask": the bits), the
+        value bytes of the converted arrays, the fp64 value bytes released, and whether the level is the twin ("wide")"""
+        out = np.zeros(_lib.AMGX_JACOBI_PREC_INFO_N, dtype=np.int64)
+        self._ck(self._lib.amgx_jacobi_prec_info(self._h, int(level), out.ctypes.data_as(_lib.c_i64p), out.size))
+        d = dict(zip(self._JPREC_KEYS, (int(v) for v in out)))
+        d["mask"] = d["images"]
+        d["images"] = tuple(n for b, n in enumerate(self._JPREC_IMAGES) if d["mask"] >> b & 1)
         return d
 
     _SM_NAMES = {_lib.AMGX_SM_JACOBI: "jacobi", _lib.AMGX_SM_GS: "gs", _lib.AMGX_SM_BGS: "bgs", _lib.AMGX_SM_CHEBY: "cheby"}

@@ -858,6 +858,8 @@ class DistributedAMG:
                  cheb_degree=None, cheb_ratio=10.0, cheb_lambda_max=None, **opts):
         if sm_type not in ("jacobi", "gs", "hgs", "bgs", "cheby"):
             raise NgsAMGError("DistributedAMG: sm_type must be jacobi, gs (multicolour stages), hgs (block-hybrid Gauss-Seidel), bgs or cheby")
+        if opts.get("jacobi_prec", "double") != "double":
+            raise NgsAMGError("DistributedAMG: jacobi_prec (single-precision Jacobi images) is not available on rank-partitioned hierarchies")
         # (an opt-in in two words: the type and its degree.  The degree has no default here: it fixes the 2 x degree halo exchanges per
         #  level and application, and a call that names the type alone is refused as it was before the option existed)
         if sm_type == "cheby" and cheb_degree is None:
