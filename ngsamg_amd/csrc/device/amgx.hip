@@ -1862,7 +1862,7 @@ struct Handle {
   }
 
   // ---- Gauss-Seidel sweeps on NV = 2, 4 interleaved vectors (AMGX_MULTI_FUSE_GS; kernels in multi_kernels.hpp).
-  // Whole levels only; which levels have them is asked here, next to the launchers (Multi::decide_gs, amgx_smooth_multi).
+  // Whole levels only; which levels have them is asked here, next to the launchers (Multi::facts for the rule of multi_rule.hpp and for amgx_smooth_multi).
   bool multi_sweep_ok(const DevLevel& L) const {
     if (L.sm_type != AMGX_SM_GS || L.bs != 1 || L.n != L.ncols || !L.paths.plain) return false;
     return L.paths.sweep == SWEEP_GSB || L.paths.sweep == SWEEP_MC;
@@ -1964,7 +1964,7 @@ struct Handle {
 
   // ---- Gauss-Seidel sweeps of square-block levels on NV = 2, 4 interleaved vectors (AMGX_MULTI_FUSE_GS_BLOCK, DESIGN.md 5.16;
   // kernels in multi_kernels.hpp).  Whole levels only.  Which block forms have them is asked HERE and nowhere else
-  // (Multi::decide_gs_block, amgx_smooth_multi); multi_sweep_ok above keeps the answer of AMGX_MULTI_FUSE_GS.
+  // (through Multi::facts: the rule of multi_rule.hpp, amgx_smooth_multi); multi_sweep_ok above keeps the answer of AMGX_MULTI_FUSE_GS.
   bool multi_block_sweep_ok(const DevLevel& L) const {
     if (L.sm_type != AMGX_SM_GS || (L.bs != 2 && L.bs != 3 && L.bs != 6) || L.n != L.ncols || !L.paths.plain) return false;
     if (L.gs32 || L.gs32_wide) return false;           // single-precision images: the NV kernels read fp64 images

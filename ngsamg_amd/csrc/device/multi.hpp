@@ -7,30 +7,21 @@
 // vectors.  Inside the handle multi-vectors are interleaved, entry (row i, column j) at i*NV + j: a gathered column index
 // then costs one address and 8*NV contiguous bytes.  Every other handle answers the same calls through a column loop over the
 // single-vector path -- unless the call carries AMGX_MULTI_FUSE: then handles whose smoothed levels are plain
-// Jacobi or Chebyshev levels with block size 1, 2, 3 or 6 run fused groups too (Multi::decide_extended).  AMGX_MULTI_FUSE_GS
-//  implies that flag and admits scalar Gauss-Seidel levels in the block-hybrid or the multicolour form as well
-// (Multi::decide_gs); their sweeps on NV vectors are Handle::gsb_sweep_nv / gs_sweep_nv.  AMGX_MULTI_FUSE_GS_BLOCK
-// implies both and admits Gauss-Seidel on 2x2 / 3x3 / 6x6 levels in the hybrid-block, block-coloured and the two block multicolour
-// forms (Multi::decide_gs_block; Handle::bgsb_sweep_nv / bgs_mc_sweep_nv).
+// Jacobi or Chebyshev levels with block size 1, 2, 3 or 6 run fused groups too.  AMGX_MULTI_FUSE_GS implies that
+// flag and admits scalar Gauss-Seidel levels in the block-hybrid or the multicolour form as well; their sweeps on NV vectors are
+// Handle::gsb_sweep_nv / gs_sweep_nv.  AMGX_MULTI_FUSE_GS_BLOCK implies both and admits Gauss-Seidel on 2x2 / 3x3 /
+// 6x6 levels in the hybrid-block, block-coloured and the two block multicolour forms (Handle::bgsb_sweep_nv / bgs_mc_sweep_nv).
 //
-// This file is the host side.  The kernels are in multi_kernels.hpp; which of them serves a matrix is decided in ONE place,
-// Handle::product<NV, EP> (amgx.hip), next to the value lists that Handle::multi_*_ok ask; the Chebyshev recurrence is
-// cheb_schedule (cheb_schedule.hpp), the one Handle::cheb_smooth runs.
+// This file is the host side.  The four rules are ONE function, multi_level_reason (multi_rule.hpp, host-only), on
+// the facts that Multi::facts reads from a level; the cut of k columns into groups, the packing of the caller's columns and the
+// single-column fallback are ONE walker, Multi::walk, and what the C entry points do around their one call is multi_call.  The
+// kernels are in multi_kernels.hpp; which of them serves a matrix is decided in ONE place, Handle::product<NV, EP> (amgx.hip),
+// next to the value lists that Handle::multi_*_ok ask; the Chebyshev recurrence is cheb_schedule (cheb_schedule.hpp), the one
+// Handle::cheb_smooth runs.
 #pragma once
+#include "multi_rule.hpp"      // multi_groups, MultiLevelFacts, multi_level_reason, multi_handle_rule, the flag logic
 
 namespace amgx {
-
-// greedy cut of k columns into fused widths 4, 2 plus at most one single column.  The kernels are written for any NV, but width 8
-// is not instantiated: sell_spmm_kernel<G, 8, EP> needs 134-144 VGPRs = 3 waves per SIMD (66 / 90-98 VGPRs, 7 / 4-5 waves at
-// widths 2 / 4), and measured at cfg 2 its level-0 passes cost 183 us per column against 145 us at width 4, the
-// whole cycle 1.23 x k single applications against 1.40 x -- so 8 columns run as 4 + 4
-inline int multi_groups(int k, bool fused, int32_t* width) {
-  int n = 0;
-  if (!fused) { for (int j = 0; j < k; ++j) width[n++] = 1; return n; }
-  for (int w : {4, 2, 1})
-    while (k >= w) { width[n++] = w; k -= w; }
-  return n;
-}
 
 struct MultiWork {                      // work vectors of one fused width, kept from call to call
   // d: the update vector of a Chebyshev level; part: the partial sums of the fused down pass (AMGX_MULTI_FUSE_DOWN, n_slots * width)
@@ -40,14 +31,11 @@ struct MultiWork {                      // work vectors of one fused width, kept
 };
 
 struct MultiState {
-  int fused = -1;                       // -1: not decided yet
-  std::string why;                      // fused == 0: the first reason
-  int fused_x = -1;                     // the same decision under AMGX_MULTI_FUSE (the extended rule)
-  std::string why_x;
-  int fused_g = -1;                     // ... and under AMGX_MULTI_FUSE_GS (the extended rule plus scalar Gauss-Seidel levels)
-  std::string why_g;
-  int fused_b = -1;                     // ... and under AMGX_MULTI_FUSE_GS_BLOCK (that rule plus Gauss-Seidel on square-block levels)
-  std::string why_b;
+  // the handle under rule 0 (no flag), 1 (AMGX_MULTI_FUSE), 2 (..._GS: plus scalar Gauss-Seidel levels, 5.15) and
+  // 3 (..._GS_BLOCK: plus Gauss-Seidel on square-block levels, 5.16).  -1: not decided yet; 0: why[r] is the first reason
+  int fused[4] = {-1, -1, -1, -1};
+  std::string why[4];
+  std::vector<MultiLevelFacts> facts;   // what the rules read, per level
   MultiWork work[MULTI_MAX + 1];        // by width (2, 4)
   DevBuf<double> col_in, col_out;       // one contiguous column (single-vector path behind an interleaved argument)
   DevBuf<double> stage_b, stage_x, stage_c;   // host-pointer calls (stage_c: the coarse multi-vector of amgx_down_multi)
@@ -65,151 +53,64 @@ struct MultiState {
 void multi_drop_graphs(MultiState* s) { s->graphs.drop(); }       // amgx_set_stream: captures of the old stream go
 void multi_free(MultiState* s) { delete s; }
 
+// a caller's multi-vector on the device: entry (row i, column j) at p[i * rs + j * cs]
+struct MultiView {
+  double* p = nullptr;
+  int64_t rs = 1, cs = 0;
+  MultiView() = default;
+  MultiView(const double* q, int k, int64_t ld, bool interleaved) : p(const_cast<double*>(q)), rs(interleaved ? k : 1), cs(interleaved ? 1 : ld) {}
+};
+// one argument of a walk over column groups (Multi::walk).  A single column of an interleaved argument is packed into `col`
+// (col_len doubles); a fused group into `grp` (rows * MULTI_MAX / 2 doubles: the widest group), or with grp == nullptr into the
+// in / out copy of the width's work space -- unless the argument is exactly that group already, which is then used in place.
+enum { MULTI_ARG_IN = 1, MULTI_ARG_OUT = 2 };
+struct MultiArg { int role; MultiView v; int64_t rows; DevBuf<double>* col; int64_t col_len; DevBuf<double>* grp; };
+
 struct Multi {
   Handle& h;
   MultiState& st;
-  static constexpr int ALL_FLAGS = AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_GS_BLOCK;   // the flags that widen the rule
+  static constexpr int ALL_FLAGS = MULTI_RULE_FLAGS;                                                   // the flags that widen the rule
   static constexpr int DOWN_FLAGS = AMGX_MULTI_FUSE_DOWN | AMGX_MULTI_FUSE_DOWN_DIA;                   // (the second implies the first, nothing else)
   static constexpr int CALL_FLAGS = ALL_FLAGS | DOWN_FLAGS;                                           // ... and the ones that imply nothing about the rule
-  const bool block_flag;                // the call carries AMGX_MULTI_FUSE_GS_BLOCK (which implies the two flags below)
+  const int flags;
+  const bool block_flag;                // the call carries AMGX_MULTI_FUSE_GS_BLOCK (which implies the flag below)
   const bool gs_flag;                   // the call carries AMGX_MULTI_FUSE_GS (which implies AMGX_MULTI_FUSE)
-  const bool fuse_flag;                 // the call carries AMGX_MULTI_FUSE
   const bool fz;                        // this call runs fused groups
   const bool down_flag;                 // the call carries AMGX_MULTI_FUSE_DOWN: modifies the fused groups, implies nothing
   const bool dia_flag;                  // the call carries AMGX_MULTI_FUSE_DOWN_DIA: implies down_flag; diagonal-image levels take the pass too
-  explicit Multi(Handle& hh, int flags = 0)
-      : h(hh), st(state(hh)), block_flag(flags & AMGX_MULTI_FUSE_GS_BLOCK), gs_flag(flags & (AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_GS_BLOCK)),
-        fuse_flag(flags & ALL_FLAGS),
-        fz(st.fused == 1 || (fuse_flag && st.fused_x == 1) || (gs_flag && st.fused_g == 1) || (block_flag && st.fused_b == 1)),
-        down_flag(flags & DOWN_FLAGS), dia_flag(flags & AMGX_MULTI_FUSE_DOWN_DIA) {}
-  // the rule in force: the flags decide the path only where the narrower rule does not hold (a scalar Jacobi handle: one path,
-  // one graph; a handle without Gauss-Seidel levels runs the same cycle under all flags, one without block Gauss-Seidel levels
-  // the same cycle under the two Gauss-Seidel flags)
-  int rule() const {
-    if (st.fused == 1 || !fuse_flag) return 0;
-    if (block_flag && st.fused_g != 1 && st.fused_x != 1) return 3;
-    return gs_flag && st.fused_x != 1 ? 2 : 1;
+  explicit Multi(Handle& hh, int fl = 0)
+      : h(hh), st(state(hh)), flags(fl), block_flag(fl & AMGX_MULTI_FUSE_GS_BLOCK), gs_flag(multi_asked_rule(fl) >= 2),
+        fz(multi_runs_fused(fl, st.fused)), down_flag(fl & DOWN_FLAGS), dia_flag(fl & AMGX_MULTI_FUSE_DOWN_DIA) {
+    if (down_flag) for (int l = 0; l < h.n_levels(); ++l) dn.push_back(level_down(l, dia_flag));     // once per call
   }
-  const std::string& note() const { const int r = rule(); return r == 3 ? st.why_b : r == 2 ? st.why_g : r == 1 ? st.why_x : st.why; }
+  int rule() const { return multi_rule_in_force(flags, st.fused); }       // (part of the graph key)
+  const std::string& note() const { return st.why[rule()]; }
 
+  // what the rule reads of a level: the only place that asks Handle::multi_*_ok
+  static MultiLevelFacts facts(const Handle& h, int l) {
+    const DevLevel& V = h.lev[l];
+    MultiLevelFacts f;
+    f.bs = V.bs; f.empty = V.n == 0; f.square = V.n == V.ncols; f.permuted = h.permuted(l);
+    f.jacobi_f32 = V.jp32 || V.jp32_wide; f.gs_f32 = V.gs32 || V.gs32_wide;
+    f.smoothed = l + 1 < h.n_levels(); f.sm_type = V.sm_type; f.plain = h.plain(V); f.cheb_degree = V.cheb_degree;
+    f.a_scalar = Handle::multi_scalar_ok(V.A); f.a_level = Handle::multi_level_ok(V.A) && V.A.br == V.bs;
+    f.t_scalar = Handle::multi_scalar_ok(V.P) && Handle::multi_scalar_ok(V.PT);
+    f.t_transfer = Handle::multi_transfer_ok(V.P) && Handle::multi_transfer_ok(V.PT);
+    f.sweep_ok = h.multi_sweep_ok(V); f.block_sweep_ok = h.multi_block_sweep_ok(V); f.block_sweep_fits = h.multi_block_sweep_fits(V);
+    return f;
+  }
   static MultiState& state(Handle& h) {
     if (!h.multi) h.multi = new MultiState;
     MultiState& s = *h.multi;
-    if (s.fused < 0) { decide(h, s); decide_extended(h, s); decide_gs(h, s); decide_gs_block(h, s); }
+    if (s.fused[0] < 0) {
+      for (int l = 0; l < h.n_levels(); ++l) s.facts.push_back(facts(h, l));
+      for (int r = 0; r < 4; ++r) {
+        MultiDecision d = multi_handle_rule(r, h.cycle == AMGX_CYCLE_V, s.facts.data(), h.n_levels());
+        s.fused[r] = d.fused; s.why[r] = std::move(d.why);
+      }
+    }
     return s;
   }
-  // all-or-nothing rule of the fused path: V-cycle; every smoothed level scalar, plain Jacobi, square, in the caller's numbering
-  static void decide(Handle& h, MultiState& s) {
-    s.fused = 0;
-    const int L = h.n_levels();
-    if (h.cycle != AMGX_CYCLE_V) { s.why = "cycle is not V"; return; }
-    for (int l = 0; l < L; ++l) {
-      const DevLevel& V = h.lev[l];
-      const std::string at = " (level " + std::to_string(l) + ")";
-      if (V.bs != 1) { s.why = "block level" + at; return; }
-      if (V.n != V.ncols) { s.why = "ghost columns" + at; return; }
-      if (h.permuted(l)) { s.why = "renumbered level" + at; return; }
-      if (V.jp32 || V.jp32_wide) { s.why = "single-precision Jacobi images" + at; return; }     // (the NV kernels read fp64 images)
-      if (V.n > 0 && !Handle::multi_scalar_ok(V.A)) { s.why = "level matrix format" + at; return; }
-      if (l + 1 == L) break;
-      if (V.sm_type != AMGX_SM_JACOBI) { s.why = "smoother is not Jacobi" + at; return; }
-      if (!h.plain(V)) { s.why = "sm_steps > 1 or sm_symm" + at; return; }
-      if (V.n > 0 && (!Handle::multi_scalar_ok(V.P) || !Handle::multi_scalar_ok(V.PT))) { s.why = "transfer format" + at; return; }
-    }
-    s.fused = 1;
-  }
-
-  // the extended rule (AMGX_MULTI_FUSE): Jacobi or Chebyshev per level, block sizes 1, 2, 3, 6, BSELL / block CSR level matrices,
-  // rigid-body or block-CSR transfers.  A superset of decide(): fused == 1 implies fused_x == 1.  Which matrices have a kernel is
-  // asked next to the launcher (Handle::multi_*_ok, on the lists Handle::product dispatches on).
-  static void decide_extended(Handle& h, MultiState& s) {
-    s.fused_x = 0;
-    const int L = h.n_levels();
-    if (h.cycle != AMGX_CYCLE_V) { s.why_x = "cycle is not V"; return; }
-    for (int l = 0; l < L; ++l) {
-      const DevLevel& V = h.lev[l];
-      const std::string at = " (level " + std::to_string(l) + ")";
-      const bool smoothed = l + 1 < L;
-      if (smoothed) {                                          // (the smoother first: it is the reason a caller can act on)
-        if (V.sm_type != AMGX_SM_JACOBI && V.sm_type != AMGX_SM_CHEBY) { s.why_x = "smoother is not Jacobi or Chebyshev" + at; return; }
-        if (!h.plain(V)) { s.why_x = "sm_steps > 1 or sm_symm" + at; return; }
-        if (V.sm_type == AMGX_SM_CHEBY && (V.cheb_degree < 1 || V.cheb_degree > 8)) { s.why_x = "Chebyshev level without coefficients" + at; return; }
-      }
-      if (V.bs != 1 && V.bs != 2 && V.bs != 3 && V.bs != 6) { s.why_x = "block size is not 1, 2, 3 or 6" + at; return; }
-      if (V.n != V.ncols) { s.why_x = "ghost columns" + at; return; }
-      if (h.permuted(l)) { s.why_x = "renumbered level" + at; return; }
-      if (V.jp32 || V.jp32_wide) { s.why_x = "single-precision Jacobi images" + at; return; }     // (the NV kernels read fp64 images)
-      if (V.n > 0 && (!Handle::multi_level_ok(V.A) || V.A.br != V.bs)) { s.why_x = "level matrix format" + at; return; }
-      if (smoothed && V.n > 0 && (!Handle::multi_transfer_ok(V.P) || !Handle::multi_transfer_ok(V.PT))) { s.why_x = "transfer format" + at; return; }
-    }
-    s.fused_x = 1;
-  }
-
-  // the rule of AMGX_MULTI_FUSE_GS: the extended rule, and a smoothed level may also be AMGX_SM_GS where Handle::multi_sweep_ok
-  // holds -- scalar, square, plain, swept in the block-hybrid (SWEEP_GSB) or the scalar multicolour form (SWEEP_MC).  A superset of
-  // decide_extended(): fused_x == 1 implies fused_g == 1.  Gauss-Seidel on a block level and AMGX_SM_BGS keep the column loop.
-  static void decide_gs(Handle& h, MultiState& s) {
-    s.fused_g = 0;
-    const int L = h.n_levels();
-    if (h.cycle != AMGX_CYCLE_V) { s.why_g = "cycle is not V"; return; }
-    for (int l = 0; l < L; ++l) {
-      const DevLevel& V = h.lev[l];
-      const std::string at = " (level " + std::to_string(l) + ")";
-      const bool smoothed = l + 1 < L;
-      const bool gs = smoothed && V.sm_type == AMGX_SM_GS;
-      if (smoothed) {
-        if (V.sm_type == AMGX_SM_BGS) { s.why_g = "block Gauss-Seidel (bgs) smoother" + at; return; }
-        if (gs && V.bs != 1) { s.why_g = "Gauss-Seidel on a block level" + at; return; }
-        if (!gs && V.sm_type != AMGX_SM_JACOBI && V.sm_type != AMGX_SM_CHEBY) { s.why_g = "smoother is not Jacobi, Chebyshev or Gauss-Seidel" + at; return; }
-        if (!h.plain(V)) { s.why_g = "sm_steps > 1 or sm_symm" + at; return; }
-        if (V.sm_type == AMGX_SM_CHEBY && (V.cheb_degree < 1 || V.cheb_degree > 8)) { s.why_g = "Chebyshev level without coefficients" + at; return; }
-      }
-      if (V.bs != 1 && V.bs != 2 && V.bs != 3 && V.bs != 6) { s.why_g = "block size is not 1, 2, 3 or 6" + at; return; }
-      if (V.n != V.ncols) { s.why_g = "ghost columns" + at; return; }
-      if (h.permuted(l)) { s.why_g = "renumbered level" + at; return; }
-      if (V.jp32 || V.jp32_wide) { s.why_g = "single-precision Jacobi images" + at; return; }     // (the NV kernels read fp64 images)
-      if (gs && V.n > 0 && !h.multi_sweep_ok(V)) { s.why_g = "Gauss-Seidel sweep form without a multi-vector kernel" + at; return; }
-      if (V.n > 0 && (!Handle::multi_level_ok(V.A) || V.A.br != V.bs)) { s.why_g = "level matrix format" + at; return; }
-      if (smoothed && V.n > 0 && (!Handle::multi_transfer_ok(V.P) || !Handle::multi_transfer_ok(V.PT))) { s.why_g = "transfer format" + at; return; }
-    }
-    s.fused_g = 1;
-  }
-
-  // the rule of AMGX_MULTI_FUSE_GS_BLOCK: the rule above, and an AMGX_SM_GS level may also have block size 2, 3 or 6 where
-  // Handle::multi_block_sweep_ok holds (square, plain; hybrid-block, block-coloured, multicolour BSELL or row-list form) and its
-  // sweep block fits the LDS of the widest group.  A superset of decide_gs(): fused_g == 1 implies fused_b == 1.  AMGX_SM_BGS, W / BS
-  // cycles, sm_steps > 1 / sm_symm (ProxySmoother) and rank-partitioned levels keep the column loop.
-  static void decide_gs_block(Handle& h, MultiState& s) {
-    s.fused_b = 0;
-    const int L = h.n_levels();
-    if (h.cycle != AMGX_CYCLE_V) { s.why_b = "cycle is not V"; return; }
-    for (int l = 0; l < L; ++l) {
-      const DevLevel& V = h.lev[l];
-      const std::string at = " (level " + std::to_string(l) + ")";
-      const bool smoothed = l + 1 < L;
-      const bool gs = smoothed && V.sm_type == AMGX_SM_GS;
-      if (smoothed) {
-        if (V.sm_type == AMGX_SM_BGS) { s.why_b = "block Gauss-Seidel (bgs) smoother" + at; return; }
-        if (!gs && V.sm_type != AMGX_SM_JACOBI && V.sm_type != AMGX_SM_CHEBY) { s.why_b = "smoother is not Jacobi, Chebyshev or Gauss-Seidel" + at; return; }
-        if (!h.plain(V)) { s.why_b = "sm_steps > 1 or sm_symm" + at; return; }
-        if (V.sm_type == AMGX_SM_CHEBY && (V.cheb_degree < 1 || V.cheb_degree > 8)) { s.why_b = "Chebyshev level without coefficients" + at; return; }
-      }
-      if (V.bs != 1 && V.bs != 2 && V.bs != 3 && V.bs != 6) { s.why_b = "block size is not 1, 2, 3 or 6" + at; return; }
-      if (V.n != V.ncols) { s.why_b = "ghost columns" + at; return; }
-      if (h.permuted(l)) { s.why_b = "renumbered level" + at; return; }
-      if (V.jp32 || V.jp32_wide) { s.why_b = "single-precision Jacobi images" + at; return; }     // (the NV kernels read fp64 images)
-      if (gs && V.n > 0) {
-        // (the fused sweeps read fp64 images: the column loop keeps a column equal to amgx_apply, bit for bit)
-        if (V.gs32 || V.gs32_wide) { s.why_b = "single-precision Gauss-Seidel images" + at; return; }
-        if (!(V.bs == 1 ? h.multi_sweep_ok(V) : h.multi_block_sweep_ok(V))) { s.why_b = "Gauss-Seidel sweep form without a multi-vector kernel" + at; return; }
-        if (V.bs != 1 && !h.multi_block_sweep_fits(V)) { s.why_b = "sweep block too large for the multi-vector sweep" + at; return; }
-      }
-      if (V.n > 0 && (!Handle::multi_level_ok(V.A) || V.A.br != V.bs)) { s.why_b = "level matrix format" + at; return; }
-      if (smoothed && V.n > 0 && (!Handle::multi_transfer_ok(V.P) || !Handle::multi_transfer_ok(V.PT))) { s.why_b = "transfer format" + at; return; }
-    }
-    s.fused_b = 1;
-  }
-
   // first level that the multi cycle hands to ONE dense product (collapsed operator or the coarsest level's inverse)
   // (0: the whole cycle is the dense operator, no level work vectors)
   int top() const { return h.dense_level >= 0 ? h.dense_level : h.n_levels() - 1; }
@@ -222,15 +123,18 @@ struct Multi {
   // (rule: down_nv_dia_ok), and a Jacobi level that takes a fused down pass folds the way up through the plain windowed Q even where
   // the single-vector cycle runs the local-window image QLW of it.  Without that bit both stay as AMGX_MULTI_FUSE_DOWN alone has them.
   struct DownNv { int form = 0, mode = 0; bool fold = false, f32 = false; const DownPlan* plan = nullptr; const char* why = ""; };
-  DownNv level_down(int l) const { return level_down(l, dia_flag); }
+  std::vector<DownNv> dn;               // level_down of every level under this call's flags (empty without AMGX_MULTI_FUSE_DOWN)
+  DownNv level_down(int l) const { return l >= 0 && l < (int)dn.size() ? dn[l] : DownNv(); }
   DownNv level_down(int l, bool dia) const {
     DownNv d;
-    if (!down_flag || l < 0 || l + 1 >= h.n_levels() || h.lev[l].n == 0) return d;
+    if (!down_flag || l < 0 || l + 1 >= h.n_levels()) return d;
+    const MultiLevelFacts& f = st.facts[l];     // (the first two refusals are the fusion rule's, on the same facts)
+    if (f.empty) return d;
     const DevLevel& V = h.lev[l];
-    if (V.bs != 1) { d.why = "block level"; return d; }
-    if (V.jp32 || V.jp32_wide) { d.why = "single-precision Jacobi images"; return d; }     // (the NV kernels read fp64 images)
+    if (f.bs != 1) { d.why = "block level"; return d; }
+    if (f.jacobi_f32) { d.why = "single-precision Jacobi images"; return d; }     // (the NV kernels read fp64 images)
     const DownPlan* p = nullptr;
-    if (V.n == V.ncols && !h.permuted(l) && !h.permuted(l + 1) && h.plain(V)) {
+    if (f.square && !f.permuted && !st.facts[l + 1].permuted && f.plain) {
       if (V.sm_type == AMGX_SM_GS) {
         if (V.paths.sweep != SWEEP_GSB) { d.why = "multicolour sweep"; return d; }
         if (V.paths.down == DOWN_GSB && V.plan_rg.on && gs_split(V)) p = &V.plan_rg;
@@ -268,7 +172,7 @@ struct Multi {
   bool dia_active() const {
     if (!dia_flag || !fz) return false;
     for (int l = 0; l < top(); ++l) {
-      const DownNv a = level_down(l, true), b = level_down(l, false);
+      const DownNv a = level_down(l), b = level_down(l, false);
       if (a.form != b.form || a.fold != b.fold) return true;
     }
     return false;
@@ -343,13 +247,14 @@ struct Multi {
     auto run = [&](auto W) { launch(dense_gemm_nv_kernel<W()>, grid, BLOCK, 0, h.stream, n, ld, M, x, y); };
     if (!dispatch<2, 4>(w, run)) throw Err("multi-vector dense product: width must be 2 or 4");
   }
-  void pack(int64_t n, int w, const double* src, int64_t rs, int64_t cs, int c0, double* dst) {
+  // columns c0 .. c0 + w of a caller's multi-vector <-> w interleaved vectors
+  void pack(int64_t n, int w, const MultiView& src, int c0, double* dst) {
     if (n <= 0) return;
-    launch(multi_pack_kernel, Handle::grid_for(n * w), BLOCK, 0, h.stream, n, w, src, rs, cs, c0, dst);
+    launch(multi_pack_kernel, Handle::grid_for(n * w), BLOCK, 0, h.stream, n, w, src.p, src.rs, src.cs, c0, dst);
   }
-  void unpack(int64_t n, int w, const double* src, double* dst, int64_t rs, int64_t cs, int c0) {
+  void unpack(int64_t n, int w, const double* src, const MultiView& dst, int c0) {
     if (n <= 0) return;
-    launch(multi_unpack_kernel, Handle::grid_for(n * w), BLOCK, 0, h.stream, n, w, src, dst, rs, cs, c0);
+    launch(multi_unpack_kernel, Handle::grid_for(n * w), BLOCK, 0, h.stream, n, w, src, dst.p, dst.rs, dst.cs, c0);
   }
 
   // Gauss-Seidel on w interleaved vectors of a level that Handle::multi_sweep_ok or multi_block_sweep_ok admits
@@ -497,40 +402,53 @@ struct Multi {
     sg.out(1, x, n, 0);
   }
 
-  // X = C B on device multi-vectors; (rs, cs) strides of B / X: entry (i, j) at i*rs + j*cs
-  void apply_body(int k, const double* B, int64_t brs, int64_t bcs, double* X, int64_t xrs, int64_t xcs, bool graph_ok, bool capturing) {
-    const int64_t n = h.lev[0].len();
+  // One walk over the column groups of a call, multi_groups(k, fused).  Per group every argument becomes ONE pointer q[i]: a
+  // contiguous column (`one`) or w interleaved vectors (`group`).  Inputs are packed before the body in the order of `a`, outputs
+  // unpacked from q[i] after it; a body whose result lands in another buffer sets q[i] to it.
+  template <size_t N, class One, class Group>
+  void walk(int k, bool fused, const MultiArg (&a)[N], One&& one, Group&& group) {
     int32_t wd[MULTI_MAX];
-    const int ng = multi_groups(k, fz, wd);
+    const int ng = multi_groups(k, fused, wd);
     int c0 = 0;
     for (int g = 0; g < ng; c0 += wd[g], ++g) {
       const int w = wd[g];
-      if (w == 1) {
-        const double* b1 = B + c0 * bcs;
-        double* x1 = X + c0 * xcs;
-        if (brs != 1) { fit(st.col_in, n); pack(n, 1, B, brs, bcs, c0, st.col_in.p); b1 = st.col_in.p; }
-        if (xrs != 1) { fit(st.col_out, n); x1 = st.col_out.p; }
-        apply_single(b1, x1, graph_ok, capturing);
-        if (xrs != 1) unpack(n, 1, st.col_out.p, X, xrs, xcs, c0);
-        continue;
+      double* q[N];
+      bool staged[N];
+      MultiWork* W = nullptr;
+      for (size_t i = 0; i < N; ++i) {
+        const MultiArg& s = a[i];
+        DevBuf<double>* buf = w == 1 ? s.col : s.grp;
+        int64_t len = w == 1 ? s.col_len : s.rows * (MULTI_MAX / 2);
+        staged[i] = w == 1 ? s.v.rs != 1 : true;
+        if (w > 1 && !s.grp) {
+          if (!W) W = &work(w);
+          buf = s.role & MULTI_ARG_IN ? &W->in : &W->out;
+          len = h.lev[0].len() * w;                            // (sized for level 0, the largest level)
+          // an interleaved argument of exactly this width (16-byte aligned) is used in place
+          staged[i] = !(k == w && s.v.rs == w && s.v.cs == 1 && (reinterpret_cast<uintptr_t>(s.v.p) & 15) == 0);
+        }
+        if (staged[i]) fit(*buf, len);
+        q[i] = staged[i] ? buf->p : s.v.p + c0 * s.v.cs;
+        if (staged[i] && (s.role & MULTI_ARG_IN)) pack(s.rows, w, s.v, c0, q[i]);
       }
-      MultiWork& W = work(w);
-      // interleaved arguments of exactly this width (16-byte aligned) are used in place
-      const bool b_inplace = brs == w && bcs == 1 && k == w && (reinterpret_cast<uintptr_t>(B) & 15) == 0;
-      const bool x_inplace = xrs == w && xcs == 1 && k == w && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-      const double* bw = B;
-      double* xw = X;
-      if (!b_inplace) { fit(W.in, n * w); pack(n, w, B, brs, bcs, c0, W.in.p); bw = W.in.p; }
-      if (!x_inplace) { fit(W.out, n * w); xw = W.out.p; }
-      cycle_v_multi(w, xw, bw);
-      if (!x_inplace) unpack(n, w, W.out.p, X, xrs, xcs, c0);
+      if (w == 1) one(q);
+      else group(w, q);
+      for (size_t i = 0; i < N; ++i)
+        if (staged[i] && (a[i].role & MULTI_ARG_OUT)) unpack(a[i].rows, w, q[i], a[i].v, c0);
     }
   }
 
+  // X = C B on device multi-vectors
+  void apply_body(int k, const MultiView& B, const MultiView& X, bool graph_ok, bool capturing) {
+    const int64_t n = h.lev[0].len();
+    const MultiArg a[2] = {{MULTI_ARG_IN, B, n, &st.col_in, n, nullptr}, {MULTI_ARG_OUT, X, n, &st.col_out, n, nullptr}};
+    walk(k, fz, a, [&](auto& q) { apply_single(q[0], q[1], graph_ok, capturing); }, [&](int w, auto& q) { cycle_v_multi(w, q[1], q[0]); });
+  }
+
   void apply(int k, const double* B, int64_t ldb, double* X, int64_t ldx, bool interleaved, bool graph_ok) {
-    const int64_t brs = interleaved ? k : 1, bcs = interleaved ? 1 : ldb, xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx;
+    const MultiView vb(B, k, ldb, interleaved), vx(X, k, ldx, interleaved);
     // only the fused path is captured as a whole; the column loop replays the single-vector graphs of run_cycle
-    if (!fz || !(h.use_graph && graph_ok) || h.stream == nullptr) { apply_body(k, B, brs, bcs, X, xrs, xcs, graph_ok, false); return; }
+    if (!fz || !(h.use_graph && graph_ok) || h.stream == nullptr) { apply_body(k, vb, vx, graph_ok, false); return; }
     const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx, rule() + (down_active() ? 4 : 0) + (dia_active() ? 8 : 0)};
     if (!st.graphs.has(key)) {
       int32_t wd[MULTI_MAX];
@@ -540,43 +458,25 @@ struct Multi {
         else { fit(st.col_in, h.lev[0].len()); fit(st.col_out, h.lev[0].len()); }
       }
     }
-    st.graphs.run(key, h.stream, [&] { apply_body(k, B, brs, bcs, X, xrs, xcs, false, true); });
+    st.graphs.run(key, h.stream, [&] { apply_body(k, vb, vx, false, true); });
   }
 
   // Y = A_level X on device multi-vectors
   void matvec(int level, int k, const double* X, int64_t ldx, double* Y, int64_t ldy, bool interleaved) {
     const DevLevel& V = h.lev[level];
-    const int64_t n = V.len(), nx = V.ext_len();
-    const int64_t xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx, yrs = interleaved ? k : 1, ycs = interleaved ? 1 : ldy;
-    int32_t wd[MULTI_MAX];
-    const int ng = multi_groups(k, fz, wd);
-    int c0 = 0;
-    for (int g = 0; g < ng; c0 += wd[g], ++g) {
-      const int w = wd[g];
-      if (w == 1) {                                            // amgx_matvec with device pointers
-        const double* x1 = X + c0 * xcs;
-        double* y1 = Y + c0 * ycs;
-        if (xrs != 1) { fit(st.col_in, std::max(nx, h.lev[0].len())); pack(nx, 1, X, xrs, xcs, c0, st.col_in.p); x1 = st.col_in.p; }
-        if (yrs != 1) { fit(st.col_out, std::max(n, h.lev[0].len())); y1 = st.col_out.p; }
-        Staged sg(h, AMGX_DEVICE_PTR);
-        const double* dx = sg.in(0, x1, nx, level);
-        double* dy = sg.inout(1, y1, n, false, level);
-        h.mult(V.A, dx, dy);
-        sg.out(1, y1, n, level);
-        if (yrs != 1) unpack(n, 1, st.col_out.p, Y, yrs, ycs, c0);
-        continue;
-      }
-      MultiWork& W = work(w);
-      const bool x_inplace = xrs == w && xcs == 1 && k == w && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-      const bool y_inplace = yrs == w && ycs == 1 && k == w && (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-      const double* xw = X;
-      double* yw = Y;
-      // (the interleaved copies are sized for level 0, the largest level)
-      if (!x_inplace) { fit(W.in, h.lev[0].len() * w); pack(n, w, X, xrs, xcs, c0, W.in.p); xw = W.in.p; }
-      if (!y_inplace) { fit(W.out, h.lev[0].len() * w); yw = W.out.p; }
-      spmm<EP_MULT>(w, V.A, xw, yw, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0});      // (no sm_pass: the fp64 image)
-      if (!y_inplace) unpack(n, w, W.out.p, Y, yrs, ycs, c0);
-    }
+    const int64_t n = V.len(), nx = V.ext_len(), n0 = h.lev[0].len();
+    // (X has ext_len rows; a handle that runs fused groups has no ghost columns, there ext_len == len)
+    const MultiArg a[2] = {{MULTI_ARG_IN, MultiView(X, k, ldx, interleaved), nx, &st.col_in, std::max(nx, n0), nullptr},
+                           {MULTI_ARG_OUT, MultiView(Y, k, ldy, interleaved), n, &st.col_out, std::max(n, n0), nullptr}};
+    walk(k, fz, a,
+         [&](auto& q) {                                        // amgx_matvec with device pointers
+           Staged sg(h, AMGX_DEVICE_PTR);
+           const double* dx = sg.in(0, q[0], nx, level);
+           double* dy = sg.inout(1, q[1], n, false, level);
+           h.mult(V.A, dx, dy);
+           sg.out(1, q[1], n, level);
+         },
+         [&](int w, auto& q) { spmm<EP_MULT>(w, V.A, q[0], q[1], EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}); });   // (no sm_pass: the fp64 image)
   }
 
   // one plain smoother step per column on a level (amgx_smooth per column).  Groups of 4 and 2 run the multi-vector sweeps where
@@ -586,37 +486,26 @@ struct Multi {
   // step, the sweeps do not act on it (they read x), so the columns of a group and the single columns see the same operation.
   void smooth(int level, int dir, int k, double* X, int64_t ldx, const double* B, int64_t ldb, bool interleaved, bool x_zero) {
     DevLevel& V = h.lev[level];
-    const int64_t n = V.len();
+    const int64_t n = V.len(), col = std::max(n, h.lev[0].len());
     if (V.n != V.ncols) throw Err("amgx_smooth_multi: rank-partitioned levels are not supported");
-    const int64_t xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx, brs = interleaved ? k : 1, bcs = interleaved ? 1 : ldb;
-    const bool nv = gs_flag && !h.permuted(level) && V.n > 0 &&
-                    (h.multi_sweep_ok(V) || (block_flag && h.multi_block_sweep_ok(V) && h.multi_block_sweep_fits(V)));
-    int32_t wd[MULTI_MAX];
-    const int ng = multi_groups(k, nv, wd);
-    int c0 = 0;
-    for (int g = 0; g < ng; c0 += wd[g], ++g) {
-      const int w = wd[g];
-      if (w == 1) {                                            // amgx_smooth with device pointers
-        double* x1 = X + c0 * xcs;
-        const double* b1 = B + c0 * bcs;
-        if (xrs != 1) { fit(st.col_out, std::max(n, h.lev[0].len())); pack(n, 1, X, xrs, xcs, c0, st.col_out.p); x1 = st.col_out.p; }
-        if (brs != 1) { fit(st.col_in, std::max(n, h.lev[0].len())); pack(n, 1, B, brs, bcs, c0, st.col_in.p); b1 = st.col_in.p; }
-        fit(st.sm_r, n);
-        Staged sg(h, AMGX_DEVICE_PTR);
-        double* dx = sg.inout(0, x1, n, true, level);
-        const double* db = sg.in(1, b1, n, level);
-        double* dr = sg.inout(2, st.sm_r.p, n, false, level);
-        h.level_smooth(V, dir, dx, db, dr, false, false, x_zero);
-        sg.out(0, x1, n, level);
-        if (xrs != 1) unpack(n, 1, st.col_out.p, X, xrs, xcs, c0);
-        continue;
-      }
-      fit(st.sm_x, n * MULTI_MAX / 2); fit(st.sm_b, n * MULTI_MAX / 2); fit(st.sm_t, n * MULTI_MAX / 2);
-      pack(n, w, X, xrs, xcs, c0, st.sm_x.p);
-      pack(n, w, B, brs, bcs, c0, st.sm_b.p);
-      const double* out = gs_sweep(w, V, dir, st.sm_x.p, st.sm_t.p, st.sm_b.p);
-      unpack(n, w, out, X, xrs, xcs, c0);
-    }
+    const MultiLevelFacts& f = st.facts[level];
+    const bool nv = gs_flag && !f.permuted && !f.empty && (f.sweep_ok || (block_flag && f.block_sweep_ok && f.block_sweep_fits));
+    const MultiArg a[2] = {{MULTI_ARG_IN | MULTI_ARG_OUT, MultiView(X, k, ldx, interleaved), n, &st.col_out, col, &st.sm_x},
+                           {MULTI_ARG_IN, MultiView(B, k, ldb, interleaved), n, &st.col_in, col, &st.sm_b}};
+    walk(k, nv, a,
+         [&](auto& q) {                                        // amgx_smooth with device pointers
+           fit(st.sm_r, n);
+           Staged sg(h, AMGX_DEVICE_PTR);
+           double* dx = sg.inout(0, q[0], n, true, level);
+           const double* db = sg.in(1, q[1], n, level);
+           double* dr = sg.inout(2, st.sm_r.p, n, false, level);
+           h.level_smooth(V, dir, dx, db, dr, false, false, x_zero);
+           sg.out(0, q[0], n, level);
+         },
+         [&](int w, auto& q) {                                 // (the result is in x or in the sweep's other buffer)
+           fit(st.sm_t, n * (MULTI_MAX / 2));
+           q[0] = gs_sweep(w, V, dir, q[0], st.sm_t.p, q[1]);
+         });
   }
 
   // the down stage of a level per column (amgx_down_multi): x_given = false: pre-smoothing from zero b -> x, then b_c = P^T (b - A x)
@@ -625,55 +514,40 @@ struct Multi {
   // Gauss-Seidel sweep from zero also needs AMGX_MULTI_FUSE_GS); everything else is a column loop over the single-vector functions.
   void down(int level, int k, const double* B, int64_t ldb, double* X, int64_t ldx, double* BC, int64_t ldbc, bool interleaved, bool x_given) {
     DevLevel& V = h.lev[level];
-    const int64_t n = V.len(), nc = h.lev[level + 1].len(), n0 = h.lev[0].len();
-    const int64_t brs = interleaved ? k : 1, bcs = interleaved ? 1 : ldb, xrs = interleaved ? k : 1, xcs = interleaved ? 1 : ldx;
-    const int64_t crs = interleaved ? k : 1, ccs = interleaved ? 1 : ldbc;
+    const int64_t n = V.len(), nc = h.lev[level + 1].len(), col = std::max(n, h.lev[0].len());
     const bool gs = V.sm_type == AMGX_SM_GS, cheby = V.sm_type == AMGX_SM_CHEBY, jacobi = V.sm_type == AMGX_SM_JACOBI;
     if (x_given && jacobi && V.paths.jacobi_down()) throw Err("amgx_down_multi: x_given on a Jacobi level with a fused down pass (the Jacobi down pass forms x itself)");
     const DownNv dn = level_down(level);
     const bool nv = dn.form != 0 && (x_given || !gs || gs_flag);
-    int32_t wd[MULTI_MAX];
-    const int ng = multi_groups(k, nv, wd);
-    int c0 = 0;
-    for (int g = 0; g < ng; c0 += wd[g], ++g) {
-      const int w = wd[g];
-      if (w == 1) {                                            // the single-vector functions with device pointers
-        const double* b1 = B + c0 * bcs;
-        double* x1 = X + c0 * xcs;
-        double* c1 = BC + c0 * ccs;
-        if (brs != 1) { fit(st.col_in, std::max(n, n0)); pack(n, 1, B, brs, bcs, c0, st.col_in.p); b1 = st.col_in.p; }
-        if (xrs != 1) { fit(st.col_out, std::max(n, n0)); x1 = st.col_out.p; if (x_given) pack(n, 1, X, xrs, xcs, c0, x1); }
-        if (crs != 1) { fit(st.dn_col, nc); c1 = st.dn_col.p; }
-        fit(st.sm_r, n);
-        double* const r = st.sm_r.p;
-        if (!x_given) h.pre_smooth_restrict(level, x1, b1, r, c1, h.folded(V));
-        else if (cheby && V.paths.down == DOWN_CHEB) h.down_launch(level, V.plan_rf, h.down_ops_cheb(x1, b1), c1);
-        else if (gs && V.paths.down == DOWN_GSB) h.residual_restrict_after_zero(level, x1, b1, r, c1);
-        else { h.residual_sm(V, x1, b1, r); h.transfer_f2c(level, r, c1); }
-        if (!x_given && xrs != 1) unpack(n, 1, x1, X, xrs, xcs, c0);
-        if (crs != 1) unpack(nc, 1, c1, BC, crs, ccs, c0);
-        continue;
-      }
-      constexpr int WMAX = MULTI_MAX / 2;                      // the widest group
-      fit(st.sm_x, n * WMAX); fit(st.sm_b, n * WMAX); fit(st.sm_t, n * WMAX); fit(st.dn_d, n * WMAX);
-      fit(st.dn_c, nc * WMAX); fit(st.dn_part, down_slots(V, dn) * WMAX);
-      double *xw = st.sm_x.p, *bw = st.sm_b.p;
-      pack(n, w, B, brs, bcs, c0, bw);
-      if (x_given) pack(n, w, X, xrs, xcs, c0, xw);
-      else if (cheby) cheb(w, V, ChebEntry::ZERO, xw, xw, bw, st.sm_t.p, st.dn_d.p);
-      else if (gs) width(w, [&](auto NV) { h.gsb_sweep_nv<NV()>(V, 0, nullptr, xw, bw); });
-      if (jacobi) down_nv(w, level, dn, h.down_ops_jacobi(V, bw, xw, h.folded(V)), st.dn_part.p, st.dn_c.p);
-      else if (cheby) down_nv(w, level, dn, h.down_ops_cheb(xw, bw), st.dn_part.p, st.dn_c.p);
-      else down_nv(w, level, dn, Handle::down_ops_gsb(V, xw), st.dn_part.p, st.dn_c.p);
-      if (!x_given) unpack(n, w, xw, X, xrs, xcs, c0);
-      unpack(nc, w, st.dn_c.p, BC, crs, ccs, c0);
-    }
+    const MultiArg a[3] = {{MULTI_ARG_IN, MultiView(B, k, ldb, interleaved), n, &st.col_in, col, &st.sm_b},
+                           {x_given ? MULTI_ARG_IN : MULTI_ARG_OUT, MultiView(X, k, ldx, interleaved), n, &st.col_out, col, &st.sm_x},
+                           {MULTI_ARG_OUT, MultiView(BC, k, ldbc, interleaved), nc, &st.dn_col, nc, &st.dn_c}};
+    walk(k, nv, a,
+         [&](auto& q) {                                        // the single-vector functions with device pointers
+           const double* b1 = q[0];
+           double *x1 = q[1], *c1 = q[2];
+           fit(st.sm_r, n);
+           double* const r = st.sm_r.p;
+           if (!x_given) h.pre_smooth_restrict(level, x1, b1, r, c1, h.folded(V));
+           else if (cheby && V.paths.down == DOWN_CHEB) h.down_launch(level, V.plan_rf, h.down_ops_cheb(x1, b1), c1);
+           else if (gs && V.paths.down == DOWN_GSB) h.residual_restrict_after_zero(level, x1, b1, r, c1);
+           else { h.residual_sm(V, x1, b1, r); h.transfer_f2c(level, r, c1); }
+         },
+         [&](int w, auto& q) {
+           constexpr int WMAX = MULTI_MAX / 2;                 // the widest group
+           fit(st.sm_t, n * WMAX); fit(st.dn_d, n * WMAX); fit(st.dn_part, down_slots(V, dn) * WMAX);
+           double *bw = q[0], *xw = q[1];
+           if (!x_given && cheby) cheb(w, V, ChebEntry::ZERO, xw, xw, bw, st.sm_t.p, st.dn_d.p);
+           else if (!x_given && gs) width(w, [&](auto NV) { h.gsb_sweep_nv<NV()>(V, 0, nullptr, xw, bw); });
+           if (jacobi) down_nv(w, level, dn, h.down_ops_jacobi(V, bw, xw, h.folded(V)), st.dn_part.p, q[2]);
+           else if (cheby) down_nv(w, level, dn, h.down_ops_cheb(xw, bw), st.dn_part.p, q[2]);
+           else down_nv(w, level, dn, Handle::down_ops_gsb(V, xw), st.dn_part.p, q[2]);
+         });
   }
 
   // k independent preconditioned CG recurrences (Krylov::pcg per column) that share the operator product and the preconditioner
-  // application.  B, X: device multi-vectors (strides as apply_body).
-  void pcg(int k, const double* B, int64_t brs, int64_t bcs, double* X, int64_t xrs, int64_t xcs, double tol, int maxit, bool use_pre,
-           bool graph_ok, double* errs, int32_t* iters) {
+  // application.  B, X: device multi-vectors.
+  void pcg(int k, const MultiView& B, const MultiView& X, double tol, int maxit, bool use_pre, bool graph_ok, double* errs, int32_t* iters) {
     if (h.lev[0].n != h.lev[0].ncols) throw Err("Krylov solvers need a square level-0 matrix (single rank)");
     const int64_t n = h.lev[0].len(), len = n * k;
     for (auto& v : st.kr) fit(v, len);
@@ -700,8 +574,8 @@ struct Multi {
       HIPCHK(hipMemcpyAsync(st.kr_active.p, active, k * sizeof(int32_t), hipMemcpyHostToDevice, sm));
       HIPCHK(hipStreamSynchronize(sm));                       // (the host array changes again before the next copy)
     };
-    pack(n, k, B, brs, bcs, 0, b);
-    pack(n, k, X, xrs, xcs, 0, x);
+    pack(n, k, B, 0, b);
+    pack(n, k, X, 0, x);
     matvec(0, k, x, 0, w, 0, true);                           // d = b - A x
     launch(multi_sub_kernel, grid, BLOCK, 0, sm, len, b, w, d);
     precond(d, w);
@@ -739,7 +613,7 @@ struct Multi {
       }
       if (changed && n_active > 0) push_active();
     }
-    unpack(n, k, x, X, xrs, xcs, 0);
+    unpack(n, k, x, X, 0);
   }
 };
 
@@ -767,12 +641,43 @@ struct MultiStaged {
   }
 };
 
-inline void multi_check(const char* fn, int k, const void* a, const void* b, int64_t lda, int64_t ldb, int64_t rows_a, int64_t rows_b, bool interleaved) {
+// One multi-vector argument of a C entry point: the caller's pointer and leading dimension, its rows, its staged copy in a
+// host-pointer call, and whether that copy is loaded before / stored after the call.
+struct MultiCallArg { const double* p; int64_t ld, rows; DevBuf<double> MultiState::* stage; bool load, store; };
+
+// What every amgx_*_multi entry point does around its one call: the checks of its multi-vectors under its name (`also`: the
+// entry's complaint about its other arguments, raised after them), Multi, the staged copies of host arrays with their compact
+// leading dimension, and the way back of the outputs.  body(M, d, ld, interleaved): device pointers and leading dimensions.
+template <size_t N, class F>
+void multi_call(const char* fn, Handle& h, int k, int flags, const MultiCallArg (&a)[N], const char* also, F&& body) {
   const std::string f(fn);
+  const bool il = flags & AMGX_MULTI_INTERLEAVED;
   if (k < 1 || k > MULTI_MAX) throw Err(f + ": k must be 1 .. " + std::to_string(MULTI_MAX) + " (got " + std::to_string(k) + ")");
-  if (!a || !b) throw Err(f + ": null multi-vector");
-  if (a == b) throw Err(f + ": the multi-vectors must not alias");
-  if (!interleaved && k > 1 && (lda < rows_a || ldb < rows_b)) throw Err(f + ": leading dimension below the level size");
+  for (size_t m = 2; m <= N; ++m) {       // the first two arguments, then each further one
+    for (size_t i = 0; i < m; ++i) if (!a[i].p) throw Err(f + ": null multi-vector");
+    for (size_t i = 0; i < m; ++i) for (size_t j = 0; j < i; ++j) if (a[i].p == a[j].p) throw Err(f + ": the multi-vectors must not alias");
+    for (size_t i = 0; i < m; ++i) if (!il && k > 1 && a[i].ld < a[i].rows) throw Err(f + ": leading dimension below the level size");
+  }
+  if (also) throw Err(f + ": " + also);
+  Multi M(h, flags);
+  MultiStaged sg(h, flags);
+  double* d[N];
+  int64_t ld[N];
+  for (size_t i = 0; i < N; ++i) {
+    d[i] = const_cast<double*>(sg.in(M.st.*a[i].stage, a[i].p, a[i].rows, k, il, a[i].ld, a[i].load));
+    ld[i] = (sg.host && !il) ? a[i].rows : a[i].ld;            // (staged copies are compact)
+  }
+  body(M, d, ld, il);
+  for (size_t i = 0; i < N; ++i) if (a[i].store) sg.out(M.st.*a[i].stage, const_cast<double*>(a[i].p), a[i].rows, k, il, a[i].ld);
+}
+
+// the note functions: the text lives until the thread's next call of the same function
+template <class F>
+const char* multi_note_call(amgx_handle hh, F&& text) {
+  thread_local std::string note;
+  note.clear();
+  if (guard(hh, [&](Handle& h) { note = text(h); })) note = amgx_last_error(hh);
+  return note.c_str();
 }
 
 }  // namespace amgx
@@ -784,15 +689,9 @@ int amgx_apply_multi(amgx_handle hh, int k, const double* B, int64_t ldb, double
   (void)b_status;   // single GPU: DISTRIBUTED == CUMULATED, as in amgx_apply
   return guard(hh, [&](amgx::Handle& h) {
     const int64_t n = h.lev[0].len();
-    const bool il = flags & AMGX_MULTI_INTERLEAVED;
-    amgx::multi_check("amgx_apply_multi", k, B, X, ldb, ldx, n, n, il);
-    amgx::Multi M(h, flags);
-    amgx::MultiStaged sg(h, flags);
-    const int64_t lb = (sg.host && !il) ? n : ldb, lx = (sg.host && !il) ? n : ldx;      // (staged copies are compact)
-    const double* dB = sg.in(M.st.stage_b, B, n, k, il, ldb);
-    double* dX = const_cast<double*>(sg.in(M.st.stage_x, X, n, k, il, ldx, false));
-    M.apply(k, dB, lb, dX, lx, il, !(flags & AMGX_NO_GRAPH));
-    sg.out(M.st.stage_x, X, n, k, il, ldx);
+    const amgx::MultiCallArg a[2] = {{B, ldb, n, &amgx::MultiState::stage_b, true, false}, {X, ldx, n, &amgx::MultiState::stage_x, false, true}};
+    amgx::multi_call("amgx_apply_multi", h, k, flags, a, nullptr,
+                     [&](amgx::Multi& M, auto& d, auto& ld, bool il) { M.apply(k, d[0], ld[0], d[1], ld[1], il, !(flags & AMGX_NO_GRAPH)); });
   });
 }
 
@@ -800,15 +699,9 @@ int amgx_matvec_multi(amgx_handle hh, int level, int k, const double* X, int64_t
   return guard(hh, [&](amgx::Handle& h) {
     if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_matvec_multi: level out of range");
     const int64_t n = h.lev[level].len(), nx = h.lev[level].ext_len();
-    const bool il = flags & AMGX_MULTI_INTERLEAVED;
-    amgx::multi_check("amgx_matvec_multi", k, X, Y, ldx, ldy, nx, n, il);
-    amgx::Multi M(h, flags);
-    amgx::MultiStaged sg(h, flags);
-    const int64_t lx = (sg.host && !il) ? nx : ldx, ly = (sg.host && !il) ? n : ldy;
-    const double* dX = sg.in(M.st.stage_b, X, nx, k, il, ldx);
-    double* dY = const_cast<double*>(sg.in(M.st.stage_x, Y, n, k, il, ldy, false));
-    M.matvec(level, k, dX, lx, dY, ly, il);
-    sg.out(M.st.stage_x, Y, n, k, il, ldy);
+    const amgx::MultiCallArg a[2] = {{X, ldx, nx, &amgx::MultiState::stage_b, true, false}, {Y, ldy, n, &amgx::MultiState::stage_x, false, true}};
+    amgx::multi_call("amgx_matvec_multi", h, k, flags, a, nullptr,
+                     [&](amgx::Multi& M, auto& d, auto& ld, bool il) { M.matvec(level, k, d[0], ld[0], d[1], ld[1], il); });
   });
 }
 
@@ -817,15 +710,9 @@ int amgx_smooth_multi(amgx_handle hh, int level, int dir, int k, double* X, int6
     if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_smooth_multi: level out of range");
     if (!h.lev[level].dinv.p) throw amgx::Err("amgx_smooth_multi: level has no smoother");
     const int64_t n = h.lev[level].len();
-    const bool il = flags & AMGX_MULTI_INTERLEAVED;
-    amgx::multi_check("amgx_smooth_multi", k, X, B, ldx, ldb, n, n, il);
-    amgx::Multi M(h, flags);
-    amgx::MultiStaged sg(h, flags);
-    const int64_t lx = (sg.host && !il) ? n : ldx, lb = (sg.host && !il) ? n : ldb;
-    const double* dB = sg.in(M.st.stage_b, B, n, k, il, ldb);
-    double* dX = const_cast<double*>(sg.in(M.st.stage_x, X, n, k, il, ldx));
-    M.smooth(level, dir, k, dX, lx, dB, lb, il, x_zero != 0);
-    sg.out(M.st.stage_x, X, n, k, il, ldx);
+    const amgx::MultiCallArg a[2] = {{B, ldb, n, &amgx::MultiState::stage_b, true, false}, {X, ldx, n, &amgx::MultiState::stage_x, true, true}};
+    amgx::multi_call("amgx_smooth_multi", h, k, flags, a, nullptr,
+                     [&](amgx::Multi& M, auto& d, auto& ld, bool il) { M.smooth(level, dir, k, d[1], ld[1], d[0], ld[0], il, x_zero != 0); });
   });
 }
 
@@ -839,20 +726,11 @@ int amgx_down_multi(amgx_handle hh, int level, int k, const double* B, int64_t l
     if (V.n != V.ncols) throw amgx::Err("amgx_down_multi: rank-partitioned levels are not supported");
     if (h.permuted(level) || h.permuted(level + 1)) throw amgx::Err("amgx_down_multi: renumbered level");
     const int64_t n = V.len(), nc = h.lev[level + 1].len();
-    const bool il = flags & AMGX_MULTI_INTERLEAVED;
-    amgx::multi_check("amgx_down_multi", k, B, X, ldb, ldx, n, n, il);
-    if (!BC) throw amgx::Err("amgx_down_multi: null multi-vector");
-    if (BC == B || BC == X) throw amgx::Err("amgx_down_multi: the multi-vectors must not alias");
-    if (!il && k > 1 && ldbc < nc) throw amgx::Err("amgx_down_multi: leading dimension below the level size");
-    amgx::Multi M(h, flags);
-    amgx::MultiStaged sg(h, flags);
-    const int64_t lb = (sg.host && !il) ? n : ldb, lx = (sg.host && !il) ? n : ldx, lc = (sg.host && !il) ? nc : ldbc;
-    const double* dB = sg.in(M.st.stage_b, B, n, k, il, ldb);
-    double* dX = const_cast<double*>(sg.in(M.st.stage_x, X, n, k, il, ldx, x_given != 0));
-    double* dC = const_cast<double*>(sg.in(M.st.stage_c, BC, nc, k, il, ldbc, false));
-    M.down(level, k, dB, lb, dX, lx, dC, lc, il, x_given != 0);
-    if (!x_given) sg.out(M.st.stage_x, X, n, k, il, ldx);
-    sg.out(M.st.stage_c, BC, nc, k, il, ldbc);
+    const bool given = x_given != 0;
+    const amgx::MultiCallArg a[3] = {{B, ldb, n, &amgx::MultiState::stage_b, true, false}, {X, ldx, n, &amgx::MultiState::stage_x, given, !given},
+                                     {BC, ldbc, nc, &amgx::MultiState::stage_c, false, true}};
+    amgx::multi_call("amgx_down_multi", h, k, flags, a, nullptr,
+                     [&](amgx::Multi& M, auto& d, auto& ld, bool il) { M.down(level, k, d[0], ld[0], d[1], ld[1], d[2], ld[2], il, given); });
   });
 }
 
@@ -868,31 +746,21 @@ int amgx_multi_level_plan(amgx_handle hh, int level, int flags, int32_t* out, in
 }
 
 const char* amgx_multi_level_note(amgx_handle hh, int level, int flags) {
-  thread_local std::string note;
-  note.clear();
-  if (guard(hh, [&](amgx::Handle& h) {
-        if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_multi_level_note: level out of range");
-        amgx::Multi M(h, flags & amgx::Multi::CALL_FLAGS);
-        note = M.level_down(level).why;
-      }))
-    note = amgx_last_error(hh);
-  return note.c_str();
+  return amgx::multi_note_call(hh, [&](amgx::Handle& h) -> std::string {
+    if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_multi_level_note: level out of range");
+    return amgx::Multi(h, flags & amgx::Multi::CALL_FLAGS).level_down(level).why;
+  });
 }
 
 int amgx_pcg_multi(amgx_handle hh, int k, const double* B, int64_t ldb, double* X, int64_t ldx, double tol, int maxit, int use_precond, int flags,
                    double* errs, int32_t* iters) {
   return guard(hh, [&](amgx::Handle& h) {
     const int64_t n = h.lev[0].len();
-    const bool il = flags & AMGX_MULTI_INTERLEAVED;
-    amgx::multi_check("amgx_pcg_multi", k, B, X, ldb, ldx, n, n, il);
-    if (maxit < 0 || !iters) throw amgx::Err("amgx_pcg_multi: bad arguments (maxit < 0 or iters == NULL)");
-    amgx::Multi M(h, flags);
-    amgx::MultiStaged sg(h, flags);
-    const int64_t lb = (sg.host && !il) ? n : ldb, lx = (sg.host && !il) ? n : ldx;
-    const double* dB = sg.in(M.st.stage_b, B, n, k, il, ldb);
-    double* dX = const_cast<double*>(sg.in(M.st.stage_x, X, n, k, il, ldx));
-    M.pcg(k, dB, il ? k : 1, il ? 1 : lb, dX, il ? k : 1, il ? 1 : lx, tol, maxit, use_precond != 0, !(flags & AMGX_NO_GRAPH), errs, iters);
-    sg.out(M.st.stage_x, X, n, k, il, ldx);
+    const amgx::MultiCallArg a[2] = {{B, ldb, n, &amgx::MultiState::stage_b, true, false}, {X, ldx, n, &amgx::MultiState::stage_x, true, true}};
+    amgx::multi_call("amgx_pcg_multi", h, k, flags, a, (maxit < 0 || !iters) ? "bad arguments (maxit < 0 or iters == NULL)" : nullptr,
+                     [&](amgx::Multi& M, auto& d, auto& ld, bool il) {
+                       M.pcg(k, amgx::MultiView(d[0], k, ld[0], il), amgx::MultiView(d[1], k, ld[1], il), tol, maxit, use_precond != 0, !(flags & AMGX_NO_GRAPH), errs, iters);
+                     });
   });
 }
 
@@ -915,14 +783,11 @@ int amgx_multi_plan(amgx_handle hh, int k, int flags, int32_t* fused, int32_t* n
 }
 
 const char* amgx_multi_note(amgx_handle hh, int flags) {
-  thread_local std::string note;
-  note.clear();
-  if (guard(hh, [&](amgx::Handle& h) {
-        amgx::Multi M(h, flags & amgx::Multi::ALL_FLAGS);
-        if (!M.fz) note = M.note();
-      }))
-    note = amgx_last_error(hh);
-  return note.c_str();
+  return amgx::multi_note_call(hh, [&](amgx::Handle& h) -> std::string {
+    amgx::Multi M(h, flags & amgx::Multi::ALL_FLAGS);
+    return M.fz ? std::string() : M.note();
+  });
 }
 
 }  // extern "C"
+

@@ -408,3 +408,29 @@ def test_solve_multi(name):
         assert np.isfinite(X).all()
     print(f"{name}: iterations with the bit {its[fuse]}, without {its[_base(fuse)]}")
     assert all(0 < a < 100 and abs(a - b) <= 1 for a, b in zip(its[fuse], its[_base(fuse)])), its
+
+
+# ---- a leading dimension above the level size: k = 7 (groups 4 + 2 + 1) and k = 4, host arrays and device tensors -------------------
+def test_stage_with_a_leading_dimension_above_n():
+    from ngsamg_amd import _lib
+    from tests.problems import padded_call
+    problem, sm, env, fuse, levels, _ = STAGE["hgs-21"]
+    dev = _dev(problem(), env, sm)
+    lib, h, level = dev._lib, dev._h, 0
+    assert dev.multi_level_plan(level, fuse)["form"] != "literal"
+    n, nc = dev.sizes[level], dev.sizes[level + 1]
+    B = _block(n, 7, seed=9)
+    Xr, BCr = _down(dev, level, B)                       # the single-vector functions per column, ld = n
+    bits = _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS | _lib.AMGX_MULTI_FUSE_DOWN
+    for flag in (0, bits):
+        for given in (False, True):
+            for k in (7, 4):
+                for device in (False, True):
+                    def down(kk, a, flags):
+                        rc = lib.amgx_down_multi(h, level, kk, a[0][0], a[0][1], a[1][0], a[1][1], a[2][0], a[2][1], int(given), flags | flag)
+                        assert rc == 0, lib.amgx_last_error(h)
+                    X0 = Xr[:k] if given else np.full((k, n), np.nan)
+                    Bout, X, BC = padded_call(dev, down, [B[:k], X0, np.full((k, nc), np.nan)], device)
+                    tag = (flag, given, k, device)
+                    assert np.array_equal(Bout, B[:k]), tag
+                    assert np.array_equal(X, Xr[:k]) and np.array_equal(BC, BCr[:k]), tag

@@ -396,3 +396,29 @@ def test_fused_cycle_is_symmetric(name):
     for u, v in ((0, 1), (2, 3)):
         a, b = float(B[v] @ X[u]), float(B[u] @ X[v])           # v^T C u and u^T C v from one fused call
         assert abs(a - b) <= 1e-10 * abs(a), (name, u, v, a, b)
+
+
+# ---- a leading dimension above the level size: k = 7 (groups 4 + 2 + 1) and k = 4, host arrays and device tensors -------------------
+def test_sweep_with_a_leading_dimension_above_n():
+    from ngsamg_amd import _lib
+    from tests.problems import padded_call
+    name, level = "21-hgs-levels", 0
+    dev = _handle(name)
+    lib, h = dev._lib, dev._h
+    n = dev.sizes[level]
+    free = _problem(name)[1].levels[level].free.astype(np.float64)
+    rng = np.random.default_rng(5)
+    B, X0 = rng.standard_normal((7, n)) * free, rng.standard_normal((7, n)) * free
+    for back in (False, True):
+        one = X0.copy()
+        for j in range(7):
+            dev.Smooth(level, one[j], np.ascontiguousarray(B[j]), np.zeros(n), back=back)
+        for flag in (0, _lib.AMGX_MULTI_FUSE | _lib.AMGX_MULTI_FUSE_GS):      # the column loop and the multi-vector sweeps
+            for k in (7, 4):
+                for device in (False, True):
+                    def smooth(kk, a, flags):
+                        rc = lib.amgx_smooth_multi(h, level, int(back), kk, a[0][0], a[0][1], a[1][0], a[1][1], 0, flags | flag)
+                        assert rc == 0, lib.amgx_last_error(h)
+                    X, Bout = padded_call(dev, smooth, [X0[:k], B[:k]], device)
+                    assert np.array_equal(Bout, B[:k])
+                    assert np.array_equal(X, one[:k]), (back, flag, k, device, float(np.abs(X - one[:k]).max()))

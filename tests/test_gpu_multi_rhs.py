@@ -412,3 +412,41 @@ def test_native_argument_errors():
     assert np.all(Xp[:, n:] == -3.0)
     assert np.array_equal(Xp[:, :n], _mult(dev, np.ascontiguousarray(Bp[:, :n])))
     assert C.sizeof(C.c_int64) == 8
+
+
+# ---- a leading dimension above the level size, k = 7 (groups 4 + 2 + 1) and k = 4, host arrays and device tensors -------------------
+@pytest.mark.parametrize("sm", ["jacobi", "gs"])        # fused groups; the column loop over the single-vector path
+def test_column_major_with_a_leading_dimension_above_n(sm):
+    from tests.problems import padded_call
+    p, H = poisson_case((17, 17, 17), "right|top", 20)
+    dev = _dev(H, NO_DENSE, sm_type=sm)
+    assert dev.multi_info(7)["groups"] == ([4, 2, 1] if sm == "jacobi" else [1] * 7)
+    lib, h = dev._lib, dev._h
+    B = _block(p, 7, seed=60)
+    ref = _mult(dev, B)                                  # the same call with ld = n
+    if sm == "gs":
+        assert np.array_equal(ref, _single(dev, B))
+    rng = np.random.default_rng(61)
+    for k in (7, 4):
+        for device in (False, True):
+            def apply(kk, a, flags):
+                assert lib.amgx_apply_multi(h, kk, a[0][0], a[0][1], a[1][0], a[1][1], 0, flags) == 0, lib.amgx_last_error(h)
+            _, X = padded_call(dev, apply, [B[:k], np.full((k, p.n), np.nan)], device)
+            assert np.array_equal(X, ref[:k]), (sm, k, device)
+            for l in range(2):
+                V = rng.standard_normal((k, dev.ext_sizes[l]))
+                want = np.empty((k, dev.sizes[l]))
+                for j in range(k):
+                    dev.MatVec(l, np.ascontiguousarray(V[j]), want[j])
+
+                def matvec(kk, a, flags):
+                    assert lib.amgx_matvec_multi(h, l, kk, a[0][0], a[0][1], a[1][0], a[1][1], flags) == 0, lib.amgx_last_error(h)
+                Vout, Y = padded_call(dev, matvec, [V, np.full((k, dev.sizes[l]), np.nan)], device)
+                assert np.array_equal(Vout, V)
+                Yw = np.full((k, dev.sizes[l]), np.nan)
+                dev.MatVecMulti(l, V, Yw)                # ld = n
+                assert np.array_equal(Y, Yw), (sm, k, device, l)
+                if sm == "gs":                           # the column loop: amgx_matvec itself
+                    assert np.array_equal(Y, want), (sm, k, device, l)
+                else:
+                    assert max(_rel(Y[j], want[j]) for j in range(k)) < 1e-13, (sm, k, device, l)

@@ -4,12 +4,14 @@ the tree's own build, then NGSAMG_HIP_LIB=<other build>, usually the parent comm
 with numpy.array_equal, level_paths(l) of every level of every handle compared as dictionaries.  Prints the table and a verdict.
 
   python tools/bits_vs_parent.py --parent-lib <libngsamg_hip.so of the parent> --out <dir> [--report <file>] [--parent-root <dir>]
+                                 [--cases single,dist,multi]
 
 --parent-root: a built checkout of the parent commit; its own copy of this tool (hence its Python package) then drives the parent's
 library -- needed whenever this tree's bindings name an entry point the parent's library does not have.
 
 The cases are the Gauss-Seidel forms (every SweepPath value, with and without the split images where a kill switch exists) and
-the rank-partitioned drivers on two virtual ranks; edit CASES / DIST_CASES for the refactor at hand.  A child that fails ends
+the rank-partitioned drivers on two virtual ranks, and the four multi-vector entries under every fuse word with the answers of
+multi_plan / multi_level_plan (MULTI_CASES); edit CASES / DIST_CASES / MULTI_CASES for the refactor at hand.  A child that fails ends
 the run: nothing more is started on the GPU after it."""
 import argparse
 import json
@@ -117,6 +119,18 @@ for kw in STEPS:
     DIST_CASES += [(f"dist stepwise hybrid block {kw}", "elasticity", dict(ELAST, **kw), {})]
 
 
+# ---- the multi-vector entries (MultMulti, MatVecMulti, SmoothMulti, DownMulti) under every fuse word, and what multi_plan /
+# multi_level_plan answer (notes and work_bytes included): name, problem, DeviceAMGMatrix arguments, environment at create
+NO_DENSE = {"AMGX_NO_DENSE_TAIL": "1"}
+FUSE_WORDS = (False, True, "gs", "gs_block", "down", "gs+down", "gs_block+down", "down_dia", "gs+down_dia", "gs_block+down_dia")
+MULTI_CASES = [("multi jacobi 17^3", (_poisson, (17, 17, 17)), dict(sm_type="jacobi"), NO_DENSE),
+               ("multi cheby 17^3", (_poisson, (17, 17, 17)), dict(sm_type="cheby", cheb_degree=2, cheb_lambda_max=2.0), NO_DENSE),
+               ("multi hybrid scalar 17^3", (_poisson, (17, 17, 17)), dict(sm_type="hgs"), NO_DENSE),
+               ("multi hybrid block elasticity 9x8x7", (_elasticity, (9, 8, 7)), dict(sm_type="hgs"), NO_DENSE)]
+# k = 7: groups 4 + 2 + 1; k = 4: one group, used in place when interleaved.  (k, interleaved, device tensors)
+MULTI_SHAPES = ((7, False, True), (4, True, True), (7, True, False), (4, False, False))
+
+
 class _Env:
     def __init__(self, env):
         self.env = env
@@ -203,7 +217,50 @@ def _dist(store):
     return paths
 
 
-def child(out):
+def _multi(store):
+    import numpy as np
+    import torch
+    from ngsamg_amd._lib import NgsAMGError
+    from ngsamg_amd.device import DeviceAMGMatrix
+    plans = {}
+    for name, (make, *args), kw, env in MULTI_CASES:
+        H, free, bs = make(*args)
+        with _Env(env):
+            dev = DeviceAMGMatrix(H, device=0, **kw)
+        fr = np.repeat(np.asarray(free) > 0, bs).astype(np.float64)
+        n, nx = dev.sizes[0], dev.ext_sizes[0]
+        rng = np.random.default_rng(11)
+        B, X0, V = rng.standard_normal((7, n)) * fr, rng.standard_normal((7, n)) * fr, rng.standard_normal((7, nx))
+        plans[name] = []
+        for fuse in FUSE_WORDS:
+            plans[name].append({"fuse": fuse, "plan": [dev.multi_plan(k, fuse) for k in range(1, 9)],
+                                "levels": [dev.multi_level_plan(l, fuse) for l in range(dev.n_levels)]})
+            for k, il, on_dev in MULTI_SHAPES:
+                def lay(M):                              # the (k, rows) block in the layout and kind of this call
+                    M = np.array(M[:k].T if il else M[:k], order="C")
+                    return torch.from_numpy(M).cuda() if on_dev else M
+
+                def call(tag, f, outputs):               # outputs: indices of the results among the values f returns
+                    try:
+                        got = f()
+                        torch.cuda.synchronize()
+                        got = np.concatenate([np.asarray(got[i].cpu() if on_dev else got[i]).ravel() for i in outputs])
+                    except NgsAMGError as e:               # a refusal is a result too: the text must stay
+                        got = np.frombuffer(str(e).encode(), dtype=np.uint8)
+                    store(f"{name}|fuse={fuse} k={k} il={il} dev={on_dev}|{tag}", got)
+
+                nan = np.full((7, n), np.nan)
+                for rep, graph in enumerate((True, True, False)):        # capture, replay, direct launches
+                    call(f"MultMulti graph={graph} rep={rep}", lambda: (dev.MultMulti(lay(B), lay(nan), interleaved=il, graph=graph, fuse=fuse),), (0,))
+                call("MatVecMulti", lambda: (dev.MatVecMulti(0, lay(V), lay(nan), interleaved=il, fuse=fuse),), (0,))
+                for back in (False, True):
+                    call(f"SmoothMulti back={back}", lambda: (dev.SmoothMulti(0, lay(X0), lay(B), back=back, interleaved=il, fuse=fuse),), (0,))
+                call("DownMulti", lambda: dev.DownMulti(0, lay(B), interleaved=il, fuse=fuse), (0, 1))
+                call("DownMulti x_given", lambda: dev.DownMulti(0, lay(B), lay(X0), x_given=True, interleaved=il, fuse=fuse), (1,))
+    return plans
+
+
+def child(out, families):
     import numpy as np
     os.makedirs(out, exist_ok=True)
     index = {}
@@ -213,8 +270,10 @@ def child(out):
         index[name] = f"{len(index):04d}.npy"
         np.save(os.path.join(out, index[name]), v)
 
-    paths = _single(store)
-    paths.update(_dist(store))
+    paths = {}
+    for family, run in (("single", _single), ("dist", _dist), ("multi", _multi)):
+        if family in families:
+            paths.update(run(store))
     with open(os.path.join(out, "index.json"), "w") as f:
         json.dump({"results": index, "level_paths": paths}, f, default=str)
 
@@ -226,9 +285,10 @@ def main():
     ap.add_argument("--report")
     ap.add_argument("--child")
     ap.add_argument("--parent-root")
+    ap.add_argument("--cases", default="single,dist,multi", help="the families to run: single (CASES), dist (DIST_CASES), multi (MULTI_CASES)")
     a = ap.parse_args()
     if a.child:
-        return child(a.child)
+        return child(a.child, a.cases.split(","))
     import numpy as np
     runs = (("tree", None), ("parent", os.path.abspath(a.parent_lib)))
     for tag, lib in runs:
@@ -237,7 +297,7 @@ def main():
         if lib:
             env["NGSAMG_HIP_LIB"] = lib
         tool = os.path.join(os.path.abspath(a.parent_root), "tools", "bits_vs_parent.py") if lib and a.parent_root else os.path.abspath(__file__)
-        rc = subprocess.run([sys.executable, tool, "--child", os.path.abspath(os.path.join(a.out, tag)), "--out", os.path.abspath(a.out)], env=env, timeout=900).returncode
+        rc = subprocess.run([sys.executable, tool, "--child", os.path.abspath(os.path.join(a.out, tag)), "--out", os.path.abspath(a.out), "--cases", a.cases], env=env, timeout=900).returncode
         if rc != 0:
             sys.exit(f"the run with the {tag} library ended with status {rc}: nothing more is started")
     T, P = (json.load(open(os.path.join(a.out, tag, "index.json"))) for tag, _ in runs)
