@@ -71,6 +71,17 @@ struct Range {
   Range(const Range&) = delete;
   Range& operator=(const Range&) = delete;
 };
+// GSS3<bs>::SmoothRHS of the reference, the marker of a Gauss-Seidel sweep on any number of vectors.  Literals: the launchers build
+// no string per call, so the marker costs one test where AMGX_ROCTX is not set.
+static const char* gs_range_name(int bs) {
+  switch (bs) {
+    case 1: return "GSS3<bs=1>::SmoothRHS";
+    case 2: return "GSS3<bs=2>::SmoothRHS";
+    case 3: return "GSS3<bs=3>::SmoothRHS";
+    case 6: return "GSS3<bs=6>::SmoothRHS";
+    default: return "GSS3<bs>::SmoothRHS";             // (the sweep kernels are listed for these four)
+  }
+}
 static const char* level_range_name(int l) {          // lev_timers of the reference: levels >= 4 share "rest"
   static const char* n[] = {"level 0", "level 1", "level 2", "level 3", "rest"};
   return n[l < 4 ? l : 4];
@@ -1511,6 +1522,8 @@ struct Handle {
 
   // ------------------------------------------------------------------ primitive ops (all async on `stream`)
   static int grid_for(int64_t threads) { return (int)std::max<int64_t>(1, (threads + BLOCK - 1) / BLOCK); }
+  // workgroups of the kernels that give every unit (a slice, a row of a dense matrix) one wave
+  static int wave_grid(int64_t units) { return (int)((units + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK); }
 
   // Part of the rows a launch covers: Span and unit_range (down_plan.hpp).  Formats that cannot be split run completely in the
   // boundary part (correct, no overlap).
@@ -1552,8 +1565,7 @@ struct Handle {
   // workgroups of the kernels that give every block row of br scalar rows W lane groups
   static int rowlane_grid(int64_t n_rows, int br, int W) {
     const int rpw = WAVE / (br * W);
-    const int64_t waves = (n_rows + rpw - 1) / rpw;
-    return (int)std::max<int64_t>(1, (waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+    return std::max(1, wave_grid((n_rows + rpw - 1) / rpw));
   }
 
   // y = EP(M x) on NV vectors: NV == 1 the single-vector kernels (kernels.hpp), NV == 2, 4 their forms on interleaved vectors
@@ -1607,7 +1619,7 @@ struct Handle {
     } else if (M.fmt == FMT_SELL) {
       unit_range(sp, WAVE / M.lanes, M.n_slices, a, b);
       if (b <= a) return;
-      const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+      const int grid = wave_grid(b - a);
       // (AMGX_JACOBI_PREC_F32_WIDE: a Jacobi pass reads the rounded values of A at fp64 width)
       image(std::bool_constant<EP32_SELL>{}, sm_pass && M.val64r.p ? M.sell.view_of(M.val64r.p) : M.sell.view(), M.sell.view32(M.val32.p), [&](auto V) {
         using T = std::remove_const_t<std::remove_pointer_t<decltype(V.val)>>;       // double / float
@@ -1634,7 +1646,7 @@ struct Handle {
       // units of RB = 64 / bs block rows (one slice); slices that straddle n_int belong to the boundary part
       unit_range(sp, WAVE / M.br, M.n_slices, a, b);
       if (b <= a) return;
-      const int grid = (int)((b - a + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+      const int grid = wave_grid(b - a);
       const int xmode = NV == 1 ? knobs.bsell_xmode : 0;       // (the gather variants rearrange loads that the NV > 1 kernel does not have)
       // (AMGX_GS_F32_WIDE: a smoother pass reads the rounded values at fp64 width)
       image(std::bool_constant<EP32_BSELL>{}, M.bsell.view_of(sm_pass && M.val64r.p ? M.val64r.p : M.bsell.val.p, xmode), M.bsell.view32(M.val32.p, xmode), [&](auto V) {
@@ -1757,191 +1769,208 @@ struct Handle {
     launch(axpy_kernel, grid_for(n), BLOCK, 0, stream, n, s, x, y);
   }
 
-  // The BSELL images that the sweeps of a Gauss-Seidel block level read: the single-precision ones where mat_f32_image gave the level
-  // the images (DevLevel::gs32), otherwise the fp64 ones.  gs_prec: run(value type); gs_view<T>: the view of image M.
-  // Nothing else is decided at launch time.
+  // ------------------------------------------------------------------ the Gauss-Seidel launchers
+  // Like product<NV, EP>: NV == 1 names the kernel of kernels.hpp, NV == 2, 4 its form on interleaved vectors (multi_kernels.hpp;
+  // AMGX_MULTI_FUSE_GS and AMGX_MULTI_FUSE_GS_BLOCK).  Colour order, grids, lane and size lists and the checks
+  // on the iterate are written once; what the widths do not share is stated once too, as a fact about NV:
+  //   units        NV > 1 sweeps whole levels (gs_units), as product<NV > 1> takes no Span
+  //   images       NV > 1 reads fp64 images in the plain view; one vector the single-precision images of a level that has them and the
+  //                view of knobs.bsell_xmode (gs_prec, gs_view).  No NV kernel is built on float.
+  //   block size   a size the BSELL kernels are not listed for takes the 2 x 2 kernel on one vector and an fp64 image, and is an error
+  //                on NV > 1 and on float images (gs_bsell_size)
+  //   hybrid form  the local-window image and the mid-width kernel of gsb_sweep are built for one vector (GSB_FORMS there)
+  //   LDS          bgsb_sweep asks for multi_block_sweep_lds(L, NV); NV > 1 refuses what exceeds 64 KB
+  // The roctx markers cover every width (gs_range_name: literals, no string per call).
+  // And, in the routing below: the split identity (split_identity), the epilogue arguments (residual_after_zero) and the aggregate
+  // blocks, which have no NV form (sweep).
   template <class F>
-  static void gs_prec(const DevLevel& L, F&& run) {
-    if (L.gs32) run(float{});
-    else run(double{});
+  static void gs_lanes(int lanes, F&& run) { if (!dispatch<1, 2, 4, 8>(lanes, run)) run(Int<16>{}); }      // any other lane count: the 16-lane kernel
+  // the units [beg, end) among the n of a level that a sweep covers; false: none
+  template <int NV>
+  static bool gs_units(const Units u, int n, int& beg, int& end) {
+    if (NV > 1 && (u.beg != 0 || u.end >= 0)) throw Err("multi-vector Gauss-Seidel: the sweeps cover whole levels");
+    beg = u.beg;
+    end = (u.end < 0 || u.end > n) ? n : u.end;
+    return end > beg;
   }
-  template <class T>
-  static BSellMatT<T> gs_view(const DevMatrix& M, int xmode) {
+  // The BSELL images that the sweeps of a Gauss-Seidel block level read: the single-precision ones where mat_f32_image gave the level
+  // the images (DevLevel::gs32), otherwise the fp64 ones.  gs_prec: run(value type); gs_view<NV, T>: the view of image M.
+  // Nothing else is decided at launch time.
+  template <int NV, class F>
+  static void gs_prec(const DevLevel& L, F&& run) {
+    if constexpr (NV == 1) { if (L.gs32) { run(float{}); return; } }
+    run(double{});
+  }
+  template <int NV, class T>
+  BSellMatT<T> gs_view(const DevMatrix& M) const {
+    const int xmode = NV == 1 ? knobs.bsell_xmode : 0;       // (the gather variants rearrange loads that the NV > 1 kernels do not have)
     if constexpr (std::is_same_v<T, float>) {
       if (M.val32.n != M.bsell.val.n) throw Err("single-precision Gauss-Seidel images: a sweep image has no float twin");
       return M.bsell.view32(M.val32.p, xmode);
     } else return M.bsell.view(xmode);
   }
+  // the block sizes of the BSELL colour and upper-residual kernels
+  template <int NV, class T, class F>
+  static void gs_bsell_size(int bs, F&& run) {
+    if (dispatch<6, 3, 2>(bs, run)) return;
+    if (NV > 1) throw Err("multi-vector Gauss-Seidel: unsupported block size");
+    if (std::is_same_v<T, float>) throw Err("single-precision Gauss-Seidel images: unsupported block size " + std::to_string(bs));
+    run(Int<2>{});                                             // one vector, fp64 image, any other block size: the 2 x 2 kernel
+  }
 
-  // one multicolour GS sweep (RHS form), forward: colours ascending, backward: descending
-  // cbeg, cend: only the colours [cbeg, cend) (cend < 0: all) -- the stages of the hybrid smoother on rank-partitioned
-  // levels are colour ranges (dist.hpp)
-  void gs_sweep(const DevLevel& L, int dir, double* x, const double* b, bool lower_only = false, int cbeg = 0, int cend = -1) {
-    Range rg("GSS3<bs=" + std::to_string(L.bs) + ">::SmoothRHS");
+  // one multicolour GS sweep (RHS form), in place, one launch per colour; forward: colours ascending, backward: descending
+  // u: only the colours [beg, end) -- the stages of the hybrid smoother on rank-partitioned levels are colour ranges (dist.hpp)
+  // lower_only: over the couplings to lower colours (the sweep from zero of a level with the split images)
+  template <int NV = 1>
+  void gs_sweep(const DevLevel& L, int dir, double* x, const double* b, bool lower_only = false, const Units u = Units()) {
+    Range rg(gs_range_name(L.bs));
     const DevGS& g = L.gs;
     const DevMatrix::Sell& copy = (lower_only && g.has_split) ? g.lower : g.sell;
     if (L.paths.hybrid()) throw Err("gs_sweep: the level uses the block-hybrid form");
     if (g.n_colors == 0 && L.n > 0) throw Err("Gauss-Seidel requested but the level has no colouring");
-    if (cend < 0 || cend > g.n_colors) cend = g.n_colors;
+    int cbeg, cend;
+    gs_units<NV>(u, g.n_colors, cbeg, cend);
     for (int q = cbeg; q < cend; ++q) {
       const int c = dir == 0 ? q : cend - 1 - (q - cbeg);
       if (L.bs == 1) {
         const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
         if (s1 == s0) continue;
-        const int grid = (s1 - s0 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-        auto run = [&](auto GG) { launch(gs_color_kernel<GG()>, grid, BLOCK, 0, stream, s0, s1, copy.view(), g.rowid.p, L.dinv.p, b, x); };
-        if (!dispatch<1, 2, 4, 8>(g.lanes, run)) run(Int<16>{});     // any other lane count: the 16-lane kernel
+        gs_lanes(g.lanes, [&](auto GG) {
+          if constexpr (NV == 1) launch(gs_color_kernel<GG()>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, copy.view(), g.rowid.p, L.dinv.p, b, x);
+          else launch(gs_color_nv_kernel<GG(), NV>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, copy.view(), g.rowid.p, L.dinv.p, b, x);
+        });
       } else if (g.bsell_ok) {
         const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
         if (s1 == s0) continue;
-        const int grid = (s1 - s0 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
         const DevMatrix& CM = (lower_only && g.bsplit) ? g.blower : g.bcopy;
-        gs_prec(L, [&](auto prec) {
+        gs_prec<NV>(L, [&](auto prec) {
           using T = decltype(prec);                                   // double / float
-          const BSellMatT<T> BM = gs_view<T>(CM, knobs.bsell_xmode);
-          auto run = [&](auto BS) { launch(bgs_bsell_color_kernel<BS(), T>, grid, BLOCK, 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x); };
-          if (dispatch<6, 3, 2>(L.bs, run)) return;
-          if (L.gs32) throw Err("single-precision Gauss-Seidel images: unsupported block size " + std::to_string(L.bs));
-          run(Int<2>{});                                             // fp64 image, any other block size: the 2 x 2 kernel
+          const BSellMatT<T> BM = gs_view<NV, T>(CM);
+          gs_bsell_size<NV, T>(L.bs, [&](auto BS) {
+            if constexpr (NV == 1) launch(bgs_bsell_color_kernel<BS(), T>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x);
+            else launch(bgs_bsell_color_nv_kernel<BS(), NV>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x);
+          });
         });
       } else {
         const int r0 = g.color_row_ptr[c], r1 = g.color_row_ptr[c + 1];
         if (r1 == r0) continue;
         const double avg = L.A.n_rows ? (double)L.A.nnz / (double)L.A.n_rows : 0.0;
         const int W = bgs_rowlist_w(avg, r1 - r0);
-        const int rpw = WAVE / (L.bs * W);
-        const int64_t waves = ((int64_t)(r1 - r0) + rpw - 1) / rpw;
-        const int grid = (int)std::max<int64_t>(1, (waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+        const int grid = rowlane_grid(r1 - r0, L.bs, W);
         auto run = [&](auto BS) {
-          auto run_w = [&](auto WW) { launch(bgs_color_kernel<BS(), WW()>, grid, BLOCK, 0, stream, r0, r1, g.rowlist.p, L.A.rowptr.p, L.A.col.p, L.A.val.p, L.dinv.p, b, x); };
+          auto run_w = [&](auto WW) {
+            if constexpr (NV == 1) launch(bgs_color_kernel<BS(), WW()>, grid, BLOCK, 0, stream, r0, r1, g.rowlist.p, L.A.rowptr.p, L.A.col.p, L.A.val.p, L.dinv.p, b, x);
+            else launch(bgs_color_nv_kernel<BS(), WW(), NV>, grid, BLOCK, 0, stream, r0, r1, g.rowlist.p, L.A.rowptr.p, L.A.col.p, L.A.val.p, L.dinv.p, b, x);
+          };
           if (!dispatch<8, 4, 2>(W, run_w)) run_w(Int<1>{});
         };
         if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("unsupported block size for GS");
       }
     }
   }
+  // r = -(U x) right after the multicolour sweep from zero over the lower couplings, one launch over all colours: b - L x - D x = 0
+  // on every swept row (r on non-free rows is not needed: their prolongation rows are empty).  Scalar levels: `upper`; block levels
+  // in the BSELL form: r_B = -(U x)_B from `bupper`.
+  template <int NV = 1>
+  void gs_upper_residual(const DevLevel& L, const double* x, double* r) {
+    const DevGS& g = L.gs;
+    const int ns = L.bs == 1 ? g.n_slices_total : g.bupper.n_slices;
+    if (ns <= 0) return;
+    if (L.bs == 1) {
+      gs_lanes(g.lanes, [&](auto GG) {
+        if constexpr (NV == 1) launch(gs_upper_residual_kernel<GG()>, wave_grid(ns), BLOCK, 0, stream, ns, g.upper.view(), g.rowid.p, x, r);
+        else launch(gs_upper_residual_nv_kernel<GG(), NV>, wave_grid(ns), BLOCK, 0, stream, ns, g.upper.view(), g.rowid.p, x, r);
+      });
+      return;
+    }
+    gs_prec<NV>(L, [&](auto prec) {
+      using T = decltype(prec);                                       // double / float
+      const BSellMatT<T> UM = gs_view<NV, T>(g.bupper);
+      gs_bsell_size<NV, T>(L.bs, [&](auto BS) {
+        if constexpr (NV == 1) launch(bgs_bsell_upper_residual_kernel<BS(), T>, wave_grid(ns), BLOCK, 0, stream, ns, UM, g.rowid.p, x, r);
+        else launch(bgs_bsell_upper_residual_nv_kernel<BS(), NV>, wave_grid(ns), BLOCK, 0, stream, ns, UM, g.rowid.p, x, r);
+      });
+    });
+  }
 
-  // one block-hybrid Gauss-Seidel sweep (gsb_sweep_kernel): ONE launch; xin == nullptr: sweep from x = 0
-  // blk0, blk1: only the blocks [blk0, blk1) (blk1 < 0: all): blocks are independent of each other within a sweep, so the
-  // rank-partitioned driver sweeps its boundary and interior blocks in separate launches around the halo exchange
-  // The image follows from the call: from zero on a level with the split `lowin`, otherwise `full` (or its local-window form).
-  void gsb_sweep(const DevLevel& L, int dir, const double* xin, double* xout, const double* b, int blk0 = 0, int blk1 = -1) {
-    Range rg("GSS3<bs=1>::SmoothRHS");
+  // one block-hybrid Gauss-Seidel sweep (gsb_sweep_kernel): ONE launch, out of place; xin == nullptr: sweep from x = 0
+  // u: only the blocks [beg, end): blocks are independent of each other within a sweep, so the rank-partitioned driver sweeps its
+  // boundary and interior blocks in separate launches around the halo exchange
+  // The image follows from the call: from zero on a level with the split `lowin` (the narrow form where gsb.narrow holds), otherwise
+  // `full` (one vector: or its local-window form).
+  template <int NV = 1>
+  void gsb_sweep(const DevLevel& L, int dir, const double* xin, double* xout, const double* b, const Units u = Units()) {
+    Range rg(gs_range_name(1));
+    constexpr bool GSB_FORMS = NV == 1;      // the local-window image and the mid-width kernel exist
     const DevGSB& g = L.gsb;
-    if (blk1 < 0 || blk1 > g.n_blocks) blk1 = g.n_blocks;
-    if (blk1 <= blk0) return;
+    int blk0, blk1;
+    if (!gs_units<NV>(u, g.n_blocks, blk0, blk1)) return;
     if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
     const bool fz = xin == nullptr;
     const bool lowin = fz && L.paths.zero_split;
-    const bool lw = !fz && g.lw;
+    const bool lw = GSB_FORMS && !fz && g.lw;
     GsbArgs a{g.rowid.p, g.slotcolor.p, L.dinv.p, b, g.n_colors, dir, lw ? g.flw_cptr.p : nullptr, lw ? g.flw_ccol.p : nullptr};
     const SellMat M = lw ? g.fullLW.view() : lowin ? g.lowin.view() : g.full.view();
     const bool narrow = lowin && g.narrow;
-    const bool mid = !fz && g.mid;
+    const bool mid = GSB_FORMS && !fz && g.mid;
     // <workgroup size, lanes per row, from zero, entries per lane and pass, local-window image>; the mid-width and local-window
     // forms exist for more than one lane per row only
     auto run = [&](auto TT) {
-      auto run_g = [&](auto GG) {
+      gs_lanes(g.G, [&](auto GG) {
         auto sweep = [&](auto ZZ, auto WW, auto LW) {
-          launch(gsb_sweep_kernel<TT(), GG(), ZZ(), WW(), LW()>, blk1 - blk0, TT(), 0, stream, L.n, blk0, M, a, xin, xout);
+          if constexpr (NV == 1) launch(gsb_sweep_kernel<TT(), GG(), ZZ(), WW(), LW()>, blk1 - blk0, TT(), 0, stream, L.n, blk0, M, a, xin, xout);
+          else launch(gsb_sweep_nv_kernel<TT(), GG(), ZZ(), WW(), NV>, blk1 - blk0, TT(), 0, stream, L.n, M, a, xin, xout);    // (whole level: no first block)
         };
         constexpr std::false_type no{};
         constexpr std::true_type yes{};
         if (narrow) return sweep(yes, Int<2>{}, no);
         if (fz) return sweep(yes, Int<GSB_WP>{}, no);
-        if constexpr (GG() > 1) {
+        if constexpr (GSB_FORMS && GG() > 1) {
           if (lw && mid) return sweep(no, Int<5>{}, yes);
           if (lw) return sweep(no, Int<GSB_WP>{}, yes);
           if (mid) return sweep(no, Int<5>{}, no);
         }
         sweep(no, Int<GSB_WP>{}, no);
-      };
-      if (!dispatch<1, 2, 4, 8>(g.G, run_g)) run_g(Int<16>{});       // any other lane count: the 16-lane kernel
+      });
     };
     if (!dispatch<256, 512>(g.TH, run)) run(Int<1024>{});            // any other workgroup size: 1024
   }
 
-  // ---- Gauss-Seidel sweeps on NV = 2, 4 interleaved vectors (AMGX_MULTI_FUSE_GS; kernels in multi_kernels.hpp).
-  // Whole levels only; which levels have them is asked here, next to the launchers (Multi::facts for the rule of multi_rule.hpp and for amgx_smooth_multi).
-  bool multi_sweep_ok(const DevLevel& L) const {
-    if (L.sm_type != AMGX_SM_GS || L.bs != 1 || L.n != L.ncols || !L.paths.plain) return false;
-    return L.paths.sweep == SWEEP_GSB || L.paths.sweep == SWEEP_MC;
-  }
-  // gsb_sweep on NV vectors: xin == nullptr is the sweep from zero (over `lowin` where the level has the split: the narrow form
-  // where gsb.narrow holds); every other sweep reads `full` in the plain form
-  template <int NV>
-  void gsb_sweep_nv(const DevLevel& L, int dir, const double* xin, double* xout, const double* b) {
-    const DevGSB& g = L.gsb;
-    if (g.n_blocks <= 0) return;
-    if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
-    const bool fz = xin == nullptr;
-    const bool lowin = fz && L.paths.zero_split;
-    GsbArgs a{g.rowid.p, g.slotcolor.p, L.dinv.p, b, g.n_colors, dir, nullptr, nullptr};
-    const SellMat M = lowin ? g.lowin.view() : g.full.view();
-    const bool narrow = lowin && g.narrow;
-    auto run = [&](auto TT) {
-      auto run_g = [&](auto GG) {
-        auto sweep = [&](auto ZZ, auto WW) { launch(gsb_sweep_nv_kernel<TT(), GG(), ZZ(), WW(), NV>, g.n_blocks, TT(), 0, stream, L.n, M, a, xin, xout); };
-        if (narrow) return sweep(std::true_type{}, Int<2>{});
-        if (fz) return sweep(std::true_type{}, Int<GSB_WP>{});
-        sweep(std::false_type{}, Int<GSB_WP>{});
-      };
-      if (!dispatch<1, 2, 4, 8>(g.G, run_g)) run_g(Int<16>{});       // (the lane counts of gsb_sweep)
-    };
-    if (!dispatch<256, 512>(g.TH, run)) run(Int<1024>{});
-  }
-  // gs_sweep on NV vectors (scalar multicolour levels): one launch per colour, in place
-  template <int NV>
-  void gs_sweep_nv(const DevLevel& L, int dir, double* x, const double* b, bool lower_only = false) {
-    const DevGS& g = L.gs;
-    const DevMatrix::Sell& copy = (lower_only && g.has_split) ? g.lower : g.sell;
-    if (L.bs != 1 || L.paths.sweep != SWEEP_MC) throw Err("multi-vector Gauss-Seidel: the level has no scalar multicolour form");
-    for (int q = 0; q < g.n_colors; ++q) {
-      const int c = dir == 0 ? q : g.n_colors - 1 - q;
-      const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
-      if (s1 == s0) continue;
-      const int grid = (s1 - s0 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-      auto run = [&](auto GG) { launch(gs_color_nv_kernel<GG(), NV>, grid, BLOCK, 0, stream, s0, s1, copy.view(), g.rowid.p, L.dinv.p, b, x); };
-      if (!dispatch<1, 2, 4, 8>(g.lanes, run)) run(Int<16>{});
-    }
-  }
-  // r = -(U x) on NV vectors right after the multicolour sweep from zero over `lower` (residual_after_zero, SWEEP_MC)
-  template <int NV>
-  void gs_upper_residual_nv(const DevLevel& L, const double* x, double* r) {
-    const DevGS& g = L.gs;
-    if (g.n_slices_total <= 0) return;
-    const int grid = (g.n_slices_total + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    auto run = [&](auto GG) { launch(gs_upper_residual_nv_kernel<GG(), NV>, grid, BLOCK, 0, stream, g.n_slices_total, g.upper.view(), g.rowid.p, x, r); };
-    if (!dispatch<1, 2, 4, 8>(g.lanes, run)) run(Int<16>{});
-  }
-
-  // one block-hybrid Gauss-Seidel sweep on a square-block level (bgsb_sweep_kernel): ONE launch; xin == nullptr: from x = 0
-  // blk0 / blk1: the sweep blocks [blk0, blk1) only (rank-partitioned levels: boundary blocks before, interior blocks beside the exchange)
-  void bgsb_sweep(const DevLevel& L, int dir, const double* xin, double* xout, const double* b, int blk0 = 0, int blk1 = -1) {
-    Range rg("GSS3<bs=" + std::to_string(L.bs) + ">::SmoothRHS");
+  // one block-hybrid Gauss-Seidel sweep on a square-block level (bgsb_sweep_kernel).  Hybrid form: ONE launch, out of place
+  // (xin == nullptr: from x = 0); u: the sweep blocks [beg, end) only (rank-partitioned levels: boundary blocks before, interior
+  // blocks beside the exchange).  Block-coloured form: whole level, in place, one launch per block colour.
+  template <int NV = 1>
+  void bgsb_sweep(const DevLevel& L, int dir, const double* xin, double* xout, const double* b, const Units u = Units()) {
+    Range rg(gs_range_name(L.bs));
     const DevBGSB& g = L.bgsb;
-    const size_t lds = (size_t)2 * g.BB * L.bs * sizeof(double) + (size_t)g.BB * sizeof(int);
-    // the images: fp64, or the single-precision ones of a level that has them (gs_image).  IN / OTH -- forward: colour phases over
+    const size_t lds = multi_block_sweep_lds(L, NV);
+    if (NV > 1 && lds > (size_t)64 * 1024) throw Err("multi-vector Gauss-Seidel: sweep block too large");
+    // the images: fp64, or the single-precision ones of a level that has them (gs_prec).  IN / OTH -- forward: colour phases over
     // the couplings to lower colours, the upper ones stream with the sweep-start values; backward: reversed.  OFF: `off`, or `offlo`
     // for the block-coloured sweep from zero
     auto sweep = [&](auto MODE, const DevMatrix& off, const int32_t* list, int b0, int nb, const double* x0) {
-      gs_prec(L, [&](auto prec) {
+      gs_prec<NV>(L, [&](auto prec) {
         using T = decltype(prec);                                     // double / float
-        const int xm = knobs.bsell_xmode;
-        const BSellMatT<T> OFF = gs_view<T>(off, xm), IN = gs_view<T>(dir == 0 ? g.in : g.upin, xm), OTH = gs_view<T>(dir == 0 ? g.upin : g.in, xm);
+        const BSellMatT<T> OFF = gs_view<NV, T>(off), IN = gs_view<NV, T>(dir == 0 ? g.in : g.upin), OTH = gs_view<NV, T>(dir == 0 ? g.upin : g.in);
         auto run = [&](auto BS) {
-          launch(bgsb_sweep_kernel<BS(), MODE(), T>, nb, BLOCK, lds, stream, g.BB, b0, list, g.blk_ptr.p, g.blk_rows.p, OFF, g.off_ptr.p, IN, OTH,
-                 g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, x0, xout);
+          if constexpr (NV == 1)
+            launch(bgsb_sweep_kernel<BS(), MODE(), T>, nb, BLOCK, lds, stream, g.BB, b0, list, g.blk_ptr.p, g.blk_rows.p, OFF, g.off_ptr.p, IN, OTH,
+                   g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, x0, xout);
+          else
+            launch(bgsb_sweep_nv_kernel<BS(), MODE(), NV>, nb, BLOCK, lds, stream, g.BB, b0, list, g.blk_ptr.p, g.blk_rows.p, OFF, g.off_ptr.p, IN, OTH,
+                   g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, x0, xout);
         };
         if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("block-hybrid Gauss-Seidel: unsupported block size");
       });
     };
+    const bool fz = xin == nullptr;
+    int blk0, blk1;
+    const bool some = gs_units<NV>(u, g.n_blocks, blk0, blk1);
     if (g.bc) {
-      // block-coloured form: one in-place launch per block colour; from zero (xin == nullptr) the first colour reads nothing
-      // outside its blocks, the later ones the finished blocks of lower colours through `offlo` (which exists with the split)
-      if (blk0 != 0 || (blk1 >= 0 && blk1 != g.n_blocks)) throw Err("block-coloured Gauss-Seidel sweeps cover the whole level");
-      if (xin != nullptr && xin != xout) throw Err("block-coloured Gauss-Seidel sweeps work in place");
-      const bool fz = xin == nullptr;
+      // from zero the first colour reads nothing outside its blocks, the later ones the finished blocks of lower colours through
+      // `offlo` (which exists with the split)
+      if (u.beg != 0 || (u.end >= 0 && u.end != g.n_blocks)) throw Err("block-coloured Gauss-Seidel sweeps cover the whole level");
+      if (!fz && xin != xout) throw Err("block-coloured Gauss-Seidel sweeps work in place");
       if (fz && dir != 0) throw Err("block-coloured Gauss-Seidel: the sweep from zero is a forward sweep");
       if (fz && !L.paths.zero_split) throw Err("block-coloured Gauss-Seidel from zero needs the split images (zero x and sweep in place instead)");
       for (int q = 0; q < g.n_bcolors; ++q) {
@@ -1954,17 +1983,19 @@ struct Handle {
       }
       return;
     }
-    if (blk1 < 0 || blk1 > g.n_blocks) blk1 = g.n_blocks;
-    if (blk1 <= blk0) return;
+    if (!some) return;
     if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
-    const bool fz = xin == nullptr;
     if (fz) sweep(Int<1>{}, g.off, nullptr, blk0, blk1 - blk0, xin);
     else sweep(Int<0>{}, g.off, nullptr, blk0, blk1 - blk0, xin);
   }
 
-  // ---- Gauss-Seidel sweeps of square-block levels on NV = 2, 4 interleaved vectors (AMGX_MULTI_FUSE_GS_BLOCK, DESIGN.md 5.16;
-  // kernels in multi_kernels.hpp).  Whole levels only.  Which block forms have them is asked HERE and nowhere else
-  // (through Multi::facts: the rule of multi_rule.hpp, amgx_smooth_multi); multi_sweep_ok above keeps the answer of AMGX_MULTI_FUSE_GS.
+  // ---- which levels have the sweeps on NV = 2, 4 vectors is asked here, next to the launchers, and nowhere else (through
+  // Multi::facts: the rule of multi_rule.hpp, amgx_smooth_multi).  Scalar levels (AMGX_MULTI_FUSE_GS):
+  bool multi_sweep_ok(const DevLevel& L) const {
+    if (L.sm_type != AMGX_SM_GS || L.bs != 1 || L.n != L.ncols || !L.paths.plain) return false;
+    return L.paths.sweep == SWEEP_GSB || L.paths.sweep == SWEEP_MC;
+  }
+  // ... square-block levels (AMGX_MULTI_FUSE_GS_BLOCK; multi_sweep_ok keeps the answer of AMGX_MULTI_FUSE_GS)
   bool multi_block_sweep_ok(const DevLevel& L) const {
     if (L.sm_type != AMGX_SM_GS || (L.bs != 2 && L.bs != 3 && L.bs != 6) || L.n != L.ncols || !L.paths.plain) return false;
     if (L.gs32 || L.gs32_wide) return false;           // single-precision images: the NV kernels read fp64 images
@@ -1973,90 +2004,12 @@ struct Handle {
       default: return false;
     }
   }
-  // dynamic LDS of bgsb_sweep_nv_kernel: x and b' of a sweep block on nv interleaved vectors, and its row ids
+  // dynamic LDS of bgsb_sweep: x and b' of a sweep block on nv (interleaved) vectors, and its row ids
   static size_t multi_block_sweep_lds(const DevLevel& L, int nv) {
     return (size_t)2 * L.bgsb.BB * L.bs * nv * sizeof(double) + (size_t)L.bgsb.BB * sizeof(int);
   }
   // ... which has to fit the 64 KB a launch gets without asking at the widest group (only AMGX_BGSB_ROWS makes blocks that do not)
   bool multi_block_sweep_fits(const DevLevel& L) const { return !L.paths.bgsb() || multi_block_sweep_lds(L, 4) <= (size_t)64 * 1024; }
-  // bgsb_sweep on NV vectors, whole level: the hybrid form out of place (xin == nullptr: from zero), the block-coloured form in
-  // place, one launch per block colour (xin == nullptr: from zero over `offlo`, which needs the split)
-  template <int NV>
-  void bgsb_sweep_nv(const DevLevel& L, int dir, const double* xin, double* xout, const double* b) {
-    const DevBGSB& g = L.bgsb;
-    if (!L.paths.bgsb()) throw Err("multi-vector Gauss-Seidel: the level has no block-hybrid form");
-    const size_t lds = multi_block_sweep_lds(L, NV);
-    if (lds > (size_t)64 * 1024) throw Err("multi-vector Gauss-Seidel: sweep block too large");
-    const BSellMat IN = dir == 0 ? g.in.bsell.view(0) : g.upin.bsell.view(0), OTH = dir == 0 ? g.upin.bsell.view(0) : g.in.bsell.view(0);
-    auto sweep = [&](auto MODE, const BSellMat& OFF, const int32_t* list, int b0, int nb, const double* x0) {
-      auto run = [&](auto BS) {
-        launch(bgsb_sweep_nv_kernel<BS(), MODE(), NV>, nb, BLOCK, lds, stream, g.BB, b0, list, g.blk_ptr.p, g.blk_rows.p, OFF, g.off_ptr.p, IN, OTH,
-               g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, x0, xout);
-      };
-      if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("block-hybrid Gauss-Seidel: unsupported block size");
-    };
-    if (g.bc) {
-      if (xin != nullptr && xin != xout) throw Err("block-coloured Gauss-Seidel sweeps work in place");
-      const bool fz = xin == nullptr;
-      if (fz && dir != 0) throw Err("block-coloured Gauss-Seidel: the sweep from zero is a forward sweep");
-      if (fz && !L.paths.zero_split) throw Err("block-coloured Gauss-Seidel from zero needs the split images (zero x and sweep in place instead)");
-      const BSellMat OFFA = g.off.bsell.view(0), OFFL = g.offlo.bsell.view(0);
-      for (int q = 0; q < g.n_bcolors; ++q) {
-        const int c = dir ? g.n_bcolors - 1 - q : q;
-        const int b0 = g.bc_ptr[c], nb = g.bc_ptr[c + 1] - b0;
-        if (nb <= 0) continue;
-        if (!fz) sweep(Int<0>{}, OFFA, g.blk_list.p, b0, nb, xout);
-        else if (q == 0) sweep(Int<1>{}, OFFL, g.blk_list.p, b0, nb, nullptr);
-        else sweep(Int<2>{}, OFFL, g.blk_list.p, b0, nb, xout);
-      }
-      return;
-    }
-    if (g.n_blocks <= 0) return;
-    if (xin == xout) throw Err("block-hybrid Gauss-Seidel sweeps are out of place");
-    const BSellMat OFF = g.off.bsell.view(0);
-    if (xin == nullptr) sweep(Int<1>{}, OFF, nullptr, 0, g.n_blocks, xin);
-    else sweep(Int<0>{}, OFF, nullptr, 0, g.n_blocks, xin);
-  }
-  // gs_sweep on NV vectors of a block level in a multicolour form: one launch per colour, in place (the kernel choices of gs_sweep)
-  template <int NV>
-  void bgs_mc_sweep_nv(const DevLevel& L, int dir, double* x, const double* b, bool lower_only = false) {
-    const DevGS& g = L.gs;
-    if (L.paths.sweep != SWEEP_MC_BSELL && L.paths.sweep != SWEEP_MC_ROWLIST) throw Err("multi-vector Gauss-Seidel: the level has no block multicolour form");
-    for (int q = 0; q < g.n_colors; ++q) {
-      const int c = dir == 0 ? q : g.n_colors - 1 - q;
-      if (L.paths.sweep == SWEEP_MC_BSELL) {
-        const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
-        if (s1 == s0) continue;
-        const int grid = (s1 - s0 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-        const BSellMat BM = (lower_only && g.bsplit) ? g.blower.bsell.view(0) : g.bcopy.bsell.view(0);
-        auto run = [&](auto BS) { launch(bgs_bsell_color_nv_kernel<BS(), NV>, grid, BLOCK, 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x); };
-        if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("multi-vector Gauss-Seidel: unsupported block size");
-      } else {
-        const int r0 = g.color_row_ptr[c], r1 = g.color_row_ptr[c + 1];
-        if (r1 == r0) continue;
-        const double avg = L.A.n_rows ? (double)L.A.nnz / (double)L.A.n_rows : 0.0;
-        const int W = bgs_rowlist_w(avg, r1 - r0);
-        const int rpw = WAVE / (L.bs * W);
-        const int64_t waves = ((int64_t)(r1 - r0) + rpw - 1) / rpw;
-        const int grid = (int)std::max<int64_t>(1, (waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-        auto run = [&](auto BS) {
-          auto run_w = [&](auto WW) { launch(bgs_color_nv_kernel<BS(), WW(), NV>, grid, BLOCK, 0, stream, r0, r1, g.rowlist.p, L.A.rowptr.p, L.A.col.p, L.A.val.p, L.dinv.p, b, x); };
-          if (!dispatch<8, 4, 2>(W, run_w)) run_w(Int<1>{});
-        };
-        if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("multi-vector Gauss-Seidel: unsupported block size");
-      }
-    }
-  }
-  // r = -(U x) on NV vectors right after the multicolour sweep from zero over `blower` (residual_after_zero, SWEEP_MC_BSELL)
-  template <int NV>
-  void bgs_upper_residual_nv(const DevLevel& L, const double* x, double* r) {
-    const DevGS& g = L.gs;
-    const int ns = g.bupper.n_slices;
-    if (ns <= 0) return;
-    const int grid = (ns + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    auto run = [&](auto BS) { launch(bgs_bsell_upper_residual_nv_kernel<BS(), NV>, grid, BLOCK, 0, stream, ns, g.bupper.bsell.view(0), g.rowid.p, x, r); };
-    if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("multi-vector Gauss-Seidel: unsupported block size");
-  }
 
   // one block Gauss-Seidel sweep: colours of the block graph ascending (forward) or descending (backward)
   void bgs_sweep(const DevLevel& L, int dir, double* x, const double* b, int cbeg = 0, int cend = -1) {
@@ -2085,67 +2038,63 @@ struct Handle {
     }
   }
 
-  // ---- the Gauss-Seidel step of a level: these functions (and residual_restrict_after_zero below) are the only ones that
-  //      switch over LevelPaths::sweep; the smoothers, the cycles and the rank-partitioned drivers (dist.hpp) call them
+  // ---- the Gauss-Seidel step of a level on NV vectors: these functions (and residual_restrict_after_zero below) are the only ones
+  //      that switch over LevelPaths::sweep; the smoothers, the cycles, the rank-partitioned drivers (dist.hpp) and the multi-vector
+  //      path (multi.hpp, under its width dispatch) call them
   // One sweep on the iterate `cur`; entries outside the swept units keep the values of `cur`.  Returns the buffer that holds the
   // result: `cur` for the in-place forms (oth may be null), `oth` for the out-of-place ones.
+  template <int NV = 1>
   double* sweep(const DevLevel& L, int dir, double* cur, double* oth, const double* b, const Units u = Units()) {
     switch (L.paths.sweep) {
-      case SWEEP_GSB: gsb_sweep(L, dir, cur, oth, b, u.beg, u.end); return oth;
-      case SWEEP_BGSB: bgsb_sweep(L, dir, cur, oth, b, u.beg, u.end); return oth;
-      case SWEEP_BGSB_BC: bgsb_sweep(L, dir, cur, cur, b, u.beg, u.end); return cur;
-      case SWEEP_BGS: bgs_sweep(L, dir, cur, b, u.beg, u.end); return cur;
-      default: gs_sweep(L, dir, cur, b, false, u.beg, u.end); return cur;
+      case SWEEP_GSB: gsb_sweep<NV>(L, dir, cur, oth, b, u); return oth;
+      case SWEEP_BGSB: bgsb_sweep<NV>(L, dir, cur, oth, b, u); return oth;
+      case SWEEP_BGSB_BC: bgsb_sweep<NV>(L, dir, cur, cur, b, u); return cur;
+      case SWEEP_BGS:
+        if constexpr (NV > 1) throw Err("multi-vector Gauss-Seidel: aggregate blocks have no multi-vector form");
+        else { bgs_sweep(L, dir, cur, b, u.beg, u.end); return cur; }
+      default: gs_sweep<NV>(L, dir, cur, b, false, u); return cur;
     }
+  }
+  // r = b - A x after the sweep from zero comes from the identity of the level's split images.  One vector: wherever the level has
+  // them.  NV > 1: where the identity is a product, only where product<NV> serves the `rest` image; otherwise r = b - A x from A
+  // (the sweep from zero still runs over the split image).  The multicolour identities have kernels of their own for every NV.
+  static bool split_identity(const DevLevel& L, int nv) {
+    const LevelPaths& P = L.paths;
+    if (nv == 1 || !P.zero_split) return P.zero_split;
+    if (P.bgsb()) return multi_level_ok(L.bgsb.rest) && L.bgsb.rest.br == L.bs;
+    return P.sweep != SWEEP_GSB || multi_scalar_ok(L.gsb.rest);
   }
   // The forward sweep from x = 0.  With LevelPaths::zero_split it runs over the couplings to lower colours only -- everything
   // else multiplies zeros -- and residual_after_zero gets r from the rest, so that A is read once in total.  r: the vector
   // residual_after_zero will fill; the multicolour identity writes swept rows only, so r is cleared here, beside x.
+  template <int NV = 1>
   void sweep_from_zero(const DevLevel& L, double* x, const double* b, double* r, const Units u = Units()) {
     const LevelPaths& P = L.paths;
-    if (!P.in_place) { sweep(L, 0, nullptr, x, b, u); return; }        // (out of place: xin == nullptr is the sweep from zero)
-    if (P.sweep == SWEEP_BGSB_BC && P.zero_split) { bgsb_sweep(L, 0, nullptr, x, b, u.beg, u.end); return; }
-    zero(x, L.len());
-    if (!P.zero_split) { sweep(L, 0, x, nullptr, b, u); return; }
+    if (!P.in_place) { sweep<NV>(L, 0, nullptr, x, b, u); return; }    // (out of place: xin == nullptr is the sweep from zero)
+    if (P.sweep == SWEEP_BGSB_BC && P.zero_split) { bgsb_sweep<NV>(L, 0, nullptr, x, b, u); return; }
+    zero(x, L.len() * NV);
+    if (!P.zero_split) { sweep<NV>(L, 0, x, nullptr, b, u); return; }
     if (!r) throw Err("sweep_from_zero: the split multicolour form clears the residual vector too");
-    zero(r, L.len());
-    gs_sweep(L, 0, x, b, true, u.beg, u.end);
+    zero(r, L.len() * NV);
+    gs_sweep<NV>(L, 0, x, b, true, u);
   }
   // r = b - A x right after sweep_from_zero(L, x, b, r), by the identity the level's images allow (x may carry ghost entries)
+  // The products are passes of the smoother on the level.  One vector hoists its epilogue loads where ep_nt says so and reads the
+  // single-precision image of `rest` on a level with such Gauss-Seidel images; NV > 1 passes no epilogue flags and reads fp64.
+  template <int NV = 1>
   void residual_after_zero(const DevLevel& L, const double* x, const double* b, double* r) {
-    if (!L.paths.zero_split) { residual_sm(L, x, b, r); return; }
+    const int nt = NV == 1 ? ep_nt & EPF_HOIST : 0;
+    if (!split_identity(L, NV)) { product<NV, EP_RES>(L.A, x, r, EpArgs{b, nullptr, nullptr, 0.0, nullptr, nt}, Span(), true); return; }
     switch (L.paths.sweep) {
       case SWEEP_GSB:
         // inside a block only couplings to lower colours contributed; (b - L_in x)_k = x_k / dinv_k on every swept row, hence
         // r = b - A x = (1/dinv - a_kk) .* x - (A - L_in - D) x = c .* x - rest x
-        product<1, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, ep_nt & EPF_HOIST});
+        product<NV, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, nt});
         return;
-      case SWEEP_BGSB: case SWEEP_BGSB_BC:                                          // r = rest x (see DevBGSB), a smoother pass
-        product<1, EP_MULT>(L.bgsb.rest, x, r, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}, Span(), L.gs32);
+      case SWEEP_BGSB: case SWEEP_BGSB_BC:                                          // r = rest x (see DevBGSB)
+        product<NV, EP_MULT>(L.bgsb.rest, x, r, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}, Span(), NV == 1 && L.gs32);
         return;
-      case SWEEP_MC: {
-        // b - L x - D x = 0 on every swept row, hence r = -U x (r on non-free rows is not needed: their prolongation rows are empty)
-        const DevGS& g = L.gs;
-        const int grid = (g.n_slices_total + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-        auto run = [&](auto GG) { launch(gs_upper_residual_kernel<GG()>, grid, BLOCK, 0, stream, g.n_slices_total, g.upper.view(), g.rowid.p, x, r); };
-        if (!dispatch<1, 2, 4, 8>(g.lanes, run)) run(Int<16>{});       // any other lane count: the 16-lane kernel
-        return;
-      }
-      case SWEEP_MC_BSELL: {
-        // block levels, same identity: r_B = -(U x)_B in one launch
-        const DevGS& g = L.gs;
-        const int ns = g.bupper.n_slices;
-        const int grid = (ns + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-        gs_prec(L, [&](auto prec) {
-          using T = decltype(prec);                                     // double / float
-          const BSellMatT<T> UM = gs_view<T>(g.bupper, knobs.bsell_xmode);
-          auto run = [&](auto BS) { launch(bgs_bsell_upper_residual_kernel<BS(), T>, grid, BLOCK, 0, stream, ns, UM, g.rowid.p, x, r); };
-          if (dispatch<6, 3, 2>(L.bs, run)) return;
-          if (L.gs32) throw Err("single-precision Gauss-Seidel images: unsupported block size " + std::to_string(L.bs));
-          run(Int<2>{});                                               // fp64 image, any other block size: the 2 x 2 kernel
-        });
-        return;
-      }
+      case SWEEP_MC: case SWEEP_MC_BSELL: gs_upper_residual<NV>(L, x, r); return;   // r = -(U x) on the swept rows
       default: throw Err("residual_after_zero: the level's sweep form has no split identity");
     }
   }
@@ -2154,7 +2103,7 @@ struct Handle {
     Range rg("coarse inv");
     const DevLevel& L = lev.back();
     if (clev != AMGX_CLEV_INV || coarse_n == 0) { zero(x, L.len()); return; }   // amg_matrix.cpp:242-246
-    const int grid = (int)((coarse_n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+    const int grid = wave_grid(coarse_n);
     if (coarse_ld != coarse_n) launch(dense_op_gemv_kernel, grid, BLOCK, 0, stream, (int)coarse_n, (int)coarse_ld, coarse_inv.p, rhs, x);
     else launch(dense_gemv_kernel, grid, BLOCK, 0, stream, (int)coarse_n, coarse_inv.p, rhs, x);
   }
@@ -2524,7 +2473,7 @@ struct Handle {
     const int L = n_levels();
     if (dense_level >= 0 && dense_level == l0) {           // the whole (sub-)cycle is the dense operator: x = B b
       Range rg("rest");
-      launch(dense_op_gemv_kernel, (dense_n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, BLOCK, 0, stream,
+      launch(dense_op_gemv_kernel, wave_grid(dense_n), BLOCK, 0, stream,
                          dense_n, dense_ld, dense_op.p, b, x);
       return;
     }
@@ -2540,7 +2489,7 @@ struct Handle {
     }
     if (dense) {
       Range rg("rest");                                    // levels >= dense_level incl. "coarse inv": x_T = B b_T
-      launch(dense_op_gemv_kernel, (dense_n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, BLOCK, 0, stream,
+      launch(dense_op_gemv_kernel, wave_grid(dense_n), BLOCK, 0, stream,
                          dense_n, dense_ld, dense_op.p, lev[T].rhs.p, lev[T].x.p);
     } else if (tail) {
       Range rg("rest");                                    // the coarse tail incl. "coarse inv" in one workgroup

@@ -8,9 +8,11 @@
 // then costs one address and 8*NV contiguous bytes.  Every other handle answers the same calls through a column loop over the
 // single-vector path -- unless the call carries AMGX_MULTI_FUSE: then handles whose smoothed levels are plain
 // Jacobi or Chebyshev levels with block size 1, 2, 3 or 6 run fused groups too.  AMGX_MULTI_FUSE_GS implies that
-// flag and admits scalar Gauss-Seidel levels in the block-hybrid or the multicolour form as well; their sweeps on NV vectors are
-// Handle::gsb_sweep_nv / gs_sweep_nv.  AMGX_MULTI_FUSE_GS_BLOCK implies both and admits Gauss-Seidel on 2x2 / 3x3 /
-// 6x6 levels in the hybrid-block, block-coloured and the two block multicolour forms (Handle::bgsb_sweep_nv / bgs_mc_sweep_nv).
+// flag and admits scalar Gauss-Seidel levels in the block-hybrid or the multicolour form as well.  AMGX_MULTI_FUSE_GS_BLOCK (DESIGN.md
+// 5.16) implies both and admits Gauss-Seidel on 2x2 / 3x3 / 6x6 levels in the hybrid-block, block-coloured and the two block multicolour
+// forms.  The Gauss-Seidel step on NV vectors is the single-vector one: Handle::sweep<NV>, sweep_from_zero<NV> and
+// residual_after_zero<NV> (amgx.hip) route it, Handle::gs_sweep<NV>, gsb_sweep<NV> and bgsb_sweep<NV> launch it; this file adds the
+// width dispatch (Multi::width) and nothing else.
 //
 // This file is the host side.  The four rules are ONE function, multi_level_reason (multi_rule.hpp, host-only), on
 // the facts that Multi::facts reads from a level; the cut of k columns into groups, the packing of the caller's columns and the
@@ -137,7 +139,7 @@ struct Multi {
     if (f.square && !f.permuted && !st.facts[l + 1].permuted && f.plain) {
       if (V.sm_type == AMGX_SM_GS) {
         if (V.paths.sweep != SWEEP_GSB) { d.why = "multicolour sweep"; return d; }
-        if (V.paths.down == DOWN_GSB && V.plan_rg.on && gs_split(V)) p = &V.plan_rg;
+        if (V.paths.down == DOWN_GSB && V.plan_rg.on && Handle::split_identity(V, 2)) p = &V.plan_rg;     // (2: any width above one)
       } else if (V.sm_type == AMGX_SM_JACOBI) {
         if (V.paths.jacobi_down() && V.plan_rf.on) p = &V.plan_rf;
       } else if (V.sm_type == AMGX_SM_CHEBY) {
@@ -243,7 +245,7 @@ struct Multi {
   }
   void gemm(int w, int n, int ld, const double* M, const double* x, double* y) {
     if (n <= 0) return;
-    const int grid = (n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    const int grid = Handle::wave_grid(n);
     auto run = [&](auto W) { launch(dense_gemm_nv_kernel<W()>, grid, BLOCK, 0, h.stream, n, ld, M, x, y); };
     if (!dispatch<2, 4>(w, run)) throw Err("multi-vector dense product: width must be 2 or 4");
   }
@@ -262,55 +264,17 @@ struct Multi {
   static void width(int w, F&& run) {
     if (!dispatch<2, 4>(w, run)) throw Err("multi-vector Gauss-Seidel: width must be 2 or 4");
   }
-  // one sweep on the iterate `cur`; returns the buffer that holds the result (Handle::sweep: `oth` for the out-of-place hybrid form)
+  // one sweep on the iterate `cur`; returns the buffer that holds the result (Handle::sweep: `oth` for the out-of-place hybrid forms)
   double* gs_sweep(int w, const DevLevel& V, int dir, double* cur, double* oth, const double* b) {
     if (V.n == 0) return cur;
-    switch (V.paths.sweep) {
-      case SWEEP_GSB: width(w, [&](auto W) { h.gsb_sweep_nv<W()>(V, dir, cur, oth, b); }); return oth;
-      case SWEEP_BGSB: width(w, [&](auto W) { h.bgsb_sweep_nv<W()>(V, dir, cur, oth, b); }); return oth;
-      case SWEEP_BGSB_BC: width(w, [&](auto W) { h.bgsb_sweep_nv<W()>(V, dir, cur, cur, b); }); return cur;
-      case SWEEP_MC_BSELL: case SWEEP_MC_ROWLIST: width(w, [&](auto W) { h.bgs_mc_sweep_nv<W()>(V, dir, cur, b); }); return cur;
-      default: width(w, [&](auto W) { h.gs_sweep_nv<W()>(V, dir, cur, b); }); return cur;
-    }
+    double* out = nullptr;
+    width(w, [&](auto W) { out = h.sweep<W()>(V, dir, cur, oth, b); });
+    return out;
   }
-  // the residual identity of the level's split images can be used on w vectors (Handle::residual_after_zero)
-  static bool gs_split(const DevLevel& V) {
-    if (!V.paths.zero_split) return false;
-    if (V.paths.bgsb()) return Handle::multi_level_ok(V.bgsb.rest) && V.bgsb.rest.br == V.bs;
-    return V.paths.sweep == SWEEP_MC || V.paths.sweep == SWEEP_MC_BSELL || Handle::multi_scalar_ok(V.gsb.rest);
-  }
-  // forward sweep from zero b -> x, then res = b - A x: Handle::sweep_from_zero + residual_after_zero per column
+  // forward sweep from zero b -> x, then res = b - A x by the identity the level's images allow on w vectors (Handle::split_identity)
   void gs_down(int w, const DevLevel& V, const double* b, double* x, double* res) {
     if (V.n == 0) return;
-    const bool split = gs_split(V);
-    const EpArgs none{nullptr, nullptr, nullptr, 0.0, nullptr, 0};
-    if (V.paths.bgsb()) {
-      // hybrid form: out of place from zero; block-coloured form: from zero over `offlo` with the split, else zero x and sweep in place
-      if (V.paths.sweep == SWEEP_BGSB || V.paths.zero_split) width(w, [&](auto W) { h.bgsb_sweep_nv<W()>(V, 0, nullptr, x, b); });
-      else { h.zero(x, V.len() * w); width(w, [&](auto W) { h.bgsb_sweep_nv<W()>(V, 0, x, x, b); }); }
-      if (split) { spmm<EP_MULT>(w, V.bgsb.rest, x, res, none); return; }        // r = rest x (DevBGSB)
-    } else if (V.paths.sweep == SWEEP_MC_BSELL || V.paths.sweep == SWEEP_MC_ROWLIST) {
-      h.zero(x, V.len() * w);
-      if (split) {                                             // r_B = -(U x)_B on the swept block rows, 0 elsewhere
-        h.zero(res, V.len() * w);
-        width(w, [&](auto W) { h.bgs_mc_sweep_nv<W()>(V, 0, x, b, true); h.bgs_upper_residual_nv<W()>(V, x, res); });
-        return;
-      }
-      width(w, [&](auto W) { h.bgs_mc_sweep_nv<W()>(V, 0, x, b); });
-    } else if (V.paths.sweep == SWEEP_GSB) {
-      width(w, [&](auto W) { h.gsb_sweep_nv<W()>(V, 0, nullptr, x, b); });
-      // r = c .* x - rest x (the sweep from zero read `lowin`: A is read once in total)
-      if (split) { spmm<EP_CRES>(w, V.gsb.rest, x, res, EpArgs{x, nullptr, V.gsb.cvec.p, 0.0, nullptr, 0}); return; }
-    } else {
-      h.zero(x, V.len() * w);
-      if (split && V.gs.has_split) {                           // r = -(U x) on the swept rows, 0 elsewhere
-        h.zero(res, V.len() * w);
-        width(w, [&](auto W) { h.gs_sweep_nv<W()>(V, 0, x, b, true); h.gs_upper_residual_nv<W()>(V, x, res); });
-        return;
-      }
-      width(w, [&](auto W) { h.gs_sweep_nv<W()>(V, 0, x, b); });
-    }
-    spmm<EP_RES>(w, V.A, x, res, EpArgs{b, nullptr, nullptr, 0.0, nullptr, 0}, true);
+    width(w, [&](auto W) { h.sweep_from_zero<W()>(V, x, b, res); h.residual_after_zero<W()>(V, x, b, res); });
   }
 
   void coarse_multi(int w, const double* rhs, double* x) {
@@ -349,7 +313,7 @@ struct Multi {
       double* const bc = W.lev[l + 1].rhs.p;
       if (V.sm_type == AMGX_SM_GS) {                           // sweep from zero and the residual by the level's identity
         if (dn.form) {                                         // (hybrid form with the split: r = c .* x - rest x)
-          width(w, [&](auto NV) { h.gsb_sweep_nv<NV()>(V, 0, nullptr, xl, bl); });
+          width(w, [&](auto NV) { h.sweep_from_zero<NV()>(V, xl, bl, nullptr); });
           down_nv(w, l, dn, Handle::down_ops_gsb(V, xl), part, bc);
           continue;
         }
@@ -538,7 +502,7 @@ struct Multi {
            fit(st.sm_t, n * WMAX); fit(st.dn_d, n * WMAX); fit(st.dn_part, down_slots(V, dn) * WMAX);
            double *bw = q[0], *xw = q[1];
            if (!x_given && cheby) cheb(w, V, ChebEntry::ZERO, xw, xw, bw, st.sm_t.p, st.dn_d.p);
-           else if (!x_given && gs) width(w, [&](auto NV) { h.gsb_sweep_nv<NV()>(V, 0, nullptr, xw, bw); });
+           else if (!x_given && gs) width(w, [&](auto NV) { h.sweep_from_zero<NV()>(V, xw, bw, nullptr); });
            if (jacobi) down_nv(w, level, dn, h.down_ops_jacobi(V, bw, xw, h.folded(V)), st.dn_part.p, q[2]);
            else if (cheby) down_nv(w, level, dn, h.down_ops_cheb(xw, bw), st.dn_part.p, q[2]);
            else down_nv(w, level, dn, Handle::down_ops_gsb(V, xw), st.dn_part.p, q[2]);

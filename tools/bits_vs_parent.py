@@ -11,8 +11,9 @@ library -- needed whenever this tree's bindings name an entry point the parent's
 
 The cases are the Gauss-Seidel forms (every SweepPath value, with and without the split images where a kill switch exists) and
 the rank-partitioned drivers on two virtual ranks, and the four multi-vector entries under every fuse word with the answers of
-multi_plan / multi_level_plan (MULTI_CASES); edit CASES / DIST_CASES / MULTI_CASES for the refactor at hand.  A child that fails ends
-the run: nothing more is started on the GPU after it."""
+multi_plan / multi_level_plan (MULTI_CASES: every Gauss-Seidel form that has sweeps on 2 and 4 vectors, each on a handle that must run
+fused groups under its fuse word in both builds); edit CASES / DIST_CASES / MULTI_CASES for the refactor at hand.  A child that fails
+ends the run: nothing more is started on the GPU after it."""
 import argparse
 import json
 import os
@@ -123,10 +124,27 @@ for kw in STEPS:
 # multi_level_plan answer (notes and work_bytes included): name, problem, DeviceAMGMatrix arguments, environment at create
 NO_DENSE = {"AMGX_NO_DENSE_TAIL": "1"}
 FUSE_WORDS = (False, True, "gs", "gs_block", "down", "gs+down", "gs_block+down", "down_dia", "gs+down_dia", "gs_block+down_dia")
-MULTI_CASES = [("multi jacobi 17^3", (_poisson, (17, 17, 17)), dict(sm_type="jacobi"), NO_DENSE),
-               ("multi cheby 17^3", (_poisson, (17, 17, 17)), dict(sm_type="cheby", cheb_degree=2, cheb_lambda_max=2.0), NO_DENSE),
-               ("multi hybrid scalar 17^3", (_poisson, (17, 17, 17)), dict(sm_type="hgs"), NO_DENSE),
-               ("multi hybrid block elasticity 9x8x7", (_elasticity, (9, 8, 7)), dict(sm_type="hgs"), NO_DENSE)]
+# last entry: the fuse word under which the handle has to run fused groups in BOTH builds (None: no such demand) -- a Gauss-Seidel
+# case that stayed in the column loop would compare the single-vector sweeps with themselves
+MULTI_CASES = [("multi jacobi 17^3", (_poisson, (17, 17, 17)), dict(sm_type="jacobi"), NO_DENSE, None),
+               ("multi cheby 17^3", (_poisson, (17, 17, 17)), dict(sm_type="cheby", cheb_degree=2, cheb_lambda_max=2.0), NO_DENSE, None),
+               ("multi hybrid scalar 17^3", (_poisson, (17, 17, 17)), dict(sm_type="hgs"), NO_DENSE, "gs"),
+               ("multi hybrid block elasticity 9x8x7", (_elasticity, (9, 8, 7)), dict(sm_type="hgs"), NO_DENSE, "gs_block")]
+# every other Gauss-Seidel form that has sweeps on 2 and 4 vectors (shapes and environments of tests/test_gpu_multi_gs.py and
+# tests/test_gpu_multi_gs_block.py)
+BSELL1 = {"AMGX_BGS_BSELL_MIN": "1"}
+MULTI_CASES += [
+    ("multi multicolour scalar 21^3", (_poisson, (21, 21, 21)), dict(sm_type="gs"), NO_DENSE, "gs"),
+    ("multi multicolour scalar rows of 15 l1 diagonal, no split", (_scalar_rows, 15, True), dict(sm_type="gs"), NO_DENSE, "gs"),
+    ("multi hybrid scalar 21^3 no split", (_poisson, (21, 21, 21)), dict(sm_type="hgs"), {**NO_DENSE, "AMGX_GSB_NO_SPLIT": "1"}, "gs"),
+    ("multi hybrid scalar 21^3 512 threads", (_poisson, (21, 21, 21)), dict(sm_type="hgs"), {**NO_DENSE, "AMGX_GSB_THREADS": "512"}, "gs"),
+    ("multi hybrid scalar 33x30x28 1024 threads", (_poisson, (33, 30, 28)), dict(sm_type="hgs"), {**NO_DENSE, "AMGX_GSB_THREADS": "1024"}, "gs"),
+    ("multi multicolour bsell elasticity 9x8x7", (_elasticity, (9, 8, 7)), dict(sm_type="gs"), {**NO_DENSE, **BSELL1}, "gs_block"),
+    ("multi multicolour bsell elasticity 9x8x7 no split", (_elasticity, (9, 8, 7)), dict(sm_type="gs"), {**NO_DENSE, **BSELL1, "AMGX_NO_BGS_SPLIT": "1"}, "gs_block"),
+    ("multi multicolour row list elasticity 9x8x7", (_elasticity, (9, 8, 7)), dict(sm_type="gs"), NO_DENSE, "gs_block"),
+    ("multi block-coloured elasticity 9x8x7", (_elasticity, (9, 8, 7)), dict(sm_type="hgs"), {**NO_DENSE, **BC}, "gs_block"),
+    ("multi block-coloured elasticity 9x8x7 no split", (_elasticity, (9, 8, 7)), dict(sm_type="hgs"), {**NO_DENSE, **BC, "AMGX_BGSB_NO_SPLIT": "1"}, "gs_block"),
+    ("multi hybrid block elasticity 9x8x7 no split", (_elasticity, (9, 8, 7)), dict(sm_type="hgs"), {**NO_DENSE, "AMGX_BGSB_NO_SPLIT": "1"}, "gs_block")]
 # k = 7: groups 4 + 2 + 1; k = 4: one group, used in place when interleaved.  (k, interleaved, device tensors)
 MULTI_SHAPES = ((7, False, True), (4, True, True), (7, True, False), (4, False, False))
 
@@ -148,6 +166,7 @@ def _single(store):
     from ngsamg_amd.device import DeviceAMGMatrix
     paths = {}
     for name, (make, *args), kw, env, smooth in CASES:
+        print(name, flush=True)
         H, free, bs = make(*args)
         with _Env(env):
             dev = DeviceAMGMatrix(H, device=0, **kw)
@@ -200,6 +219,7 @@ def _dist(store):
     from ngsamg_amd import dist as D
     paths = {}
     for name, kind, kw, env in DIST_CASES:
+        print(name, flush=True)
         comm, states, bs = _dist_states(kind)
         kw = dict(kw)
         kw.setdefault("max_coarse_size", 10)
@@ -223,15 +243,18 @@ def _multi(store):
     from ngsamg_amd._lib import NgsAMGError
     from ngsamg_amd.device import DeviceAMGMatrix
     plans = {}
-    for name, (make, *args), kw, env in MULTI_CASES:
+    for name, (make, *args), kw, env, need in MULTI_CASES:
+        print(name, flush=True)
         H, free, bs = make(*args)
         with _Env(env):
             dev = DeviceAMGMatrix(H, device=0, **kw)
+        if need and not dev.multi_plan(4, need)["fused"]:
+            sys.exit(f"{name}: the handle keeps the column loop under fuse={need!r}: {dev.multi_plan(4, need)['note']}")
         fr = np.repeat(np.asarray(free) > 0, bs).astype(np.float64)
         n, nx = dev.sizes[0], dev.ext_sizes[0]
         rng = np.random.default_rng(11)
         B, X0, V = rng.standard_normal((7, n)) * fr, rng.standard_normal((7, n)) * fr, rng.standard_normal((7, nx))
-        plans[name] = []
+        plans[name] = [dev.level_paths(l) for l in range(dev.n_levels)]
         for fuse in FUSE_WORDS:
             plans[name].append({"fuse": fuse, "plan": [dev.multi_plan(k, fuse) for k in range(1, 9)],
                                 "levels": [dev.multi_level_plan(l, fuse) for l in range(dev.n_levels)]})
@@ -314,7 +337,9 @@ def main():
         same = T["level_paths"].get(name) == P["level_paths"].get(name)
         pbad += not same
         forms = " ".join(f"L{l}:{lp['gs_form']}/split={lp['gs_split']}" for l, lp in enumerate(T["level_paths"].get(name, [])) if lp.get("gs_form"))
-        lines.append(("same  " if same else "DIFF  ") + f"{name}|level_paths of {len(T['level_paths'].get(name, []))} levels: {forms}")
+        n_lev = sum("gs_form" in lp for lp in T["level_paths"].get(name, []))       # (a multi case: its plan dictionaries follow)
+        need = {c[0]: c[4] for c in MULTI_CASES}.get(name)
+        lines.append(("same  " if same else "DIFF  ") + f"{name}|level_paths of {n_lev} levels: {forms}" + (f" | fused under {need} in both builds" if need else ""))
     head = [f"results: {nres}   identical: {nres - bad}   different: {bad}",
             f"handles: {len(lines) - nres}   level_paths identical: {len(lines) - nres - pbad}   different: {pbad}",
             "verdict: " + ("IDENTICAL" if bad == 0 and pbad == 0 else "DIFFERENT"), "", "== cases (handle | call)"]
