@@ -156,6 +156,28 @@ typedef struct amgx_level_desc {
                               /*   other form (the row list over block CSR, other block sizes) stay fp64 silently -- amgx_level_extra      */
                               /*   entries 9 .. 11 tell.  AMGX_GS_F32_WIDE=1 at amgx_create: no float images; the rounded values are       */
                               /*   written into fp64 images of exactly those levels and the fp64 kernels run (A/B twin).                   */
+                              /*   AMGX_PREC_F32_SCALAR_GS (2): single-precision images for Gauss-Seidel on a SCALAR       */
+                              /*   level.  Accepted on a smoothed level with sm_type = AMGX_SM_GS, block size 1 and n_cols == n_rows; an    */
+                              /*   error that names the level and mat_prec on any other smoother, on a block level and on a level with     */
+                              /*   ghost columns (amgx_dist_create: "rank-partitioned"); ignored on the coarsest level of several, taken   */
+                              /*   by the only level of a single-level handle.  After the level's Gauss-Seidel images exist, each of the   */
+                              /*   block-hybrid images full, fullLW, lowin, rest, restLW or of the multicolour images sell, lower, upper   */
+                              /*   that the level has gets a float value array: the stored fp64 values rounded to nearest, every index     */
+                              /*   array, rowid, slotcolor and the window lists shared.  The fp64 value arrays of these images are         */
+                              /*   released.  dinv, cvec (1 / dinv - a_kk), all vectors, P, P^T, the chunk-local restriction data, the     */
+                              /*   tail program's copies and the dense tail stay fp64 and true: with the split images the diagonal acts    */
+                              /*   with its true value, so the handle is not the fp64 cycle on a rounded A; without them (AMGX_GSB_NO_SPLIT;*/
+                              /*   multicolour without the split) it is, bit for bit.  A itself gets an image only on a level without     */
+                              /*   split images, where the residual after the sweep from zero reads A: a float array where A is plain     */
+                              /*   sliced-ELL, else rounded values at fp64 width in a separate array.  Read by: the general sweep, the     */
+                              /*   sweep from zero, the residual after it in every form (separate, fused with the chunk-local restriction  */
+                              /*   on sliced-ELL, row windows or the local window), the colour launches and the upper residual, and        */
+                              /*   update_res inside pre-smoothing from zero.  update_res anywhere else, amgx_matvec, amgx_residual,       */
+                              /*   amgx_matvec_multi and the Krylov operator read the fp64 A.  A value that rounds to +-inf is an error    */
+                              /*   that names the level ("single precision"); nothing half-built is left.  AMGX_NO_MAT_F32=1 ignores the   */
+                              /*   request.  AMGX_GS_F32_WIDE=1 (A/B twin): no float arrays; the rounded values are written at fp64 width  */
+                              /*   into exactly those images (A: a separate array) and the fp64 kernels run -- same bits.                  */
+                              /*   amgx_gs_prec_info tells what was built.                                                                 */
                               /* (jacobi_prec below fills the four bytes that padded the struct after mat_prec: sizeof is unchanged.   */
                               /*  The Python binding, ngsamg_amd/_lib.py, reaches it by that offset and not through its field list; a   */
                               /*  field appended after it must be added there as well.)                                                 */
@@ -181,6 +203,7 @@ typedef struct amgx_level_desc {
                               /*   AMGX_NO_MAT_F32=1 at amgx_create ignores the request.  amgx_jacobi_prec_info tells what was built.      */
 } amgx_level_desc;
 enum { AMGX_PREC_F64 = 0, AMGX_PREC_F32 = 1 };                    /* amgx_level_desc.mat_prec */
+enum { AMGX_PREC_F32_SCALAR_GS = 2 }; /* amgx_level_desc.mat_prec, scalar AMGX_SM_GS levels only */
 enum { AMGX_JACOBI_PREC_F64 = 0, AMGX_JACOBI_PREC_F32 = 1, AMGX_JACOBI_PREC_F32_WIDE = 2 };     /* amgx_level_desc.jacobi_prec */
 
 typedef struct amgx_hierarchy_desc {
@@ -344,6 +367,7 @@ int amgx_level_paths(amgx_handle h, int level, int64_t* out, int n_out);
  *    9 the Gauss-Seidel sweeps of this level read single-precision images (1; 0 otherwise, also under AMGX_GS_F32_WIDE)
  *    10, 11 the number of single-precision Gauss-Seidel images of this level (A included) and the bytes of their values
  *      (under AMGX_GS_F32_WIDE: the fp64 images that hold rounded values, 8 bytes per value, while entry 9 stays 0)
+ *      (a scalar level with mat_prec = AMGX_PREC_F32_SCALAR_GS reports the same three; amgx_gs_prec_info names the images)
  * Returns 0, or non-zero for a bad level or n_out < 1. */
 #define AMGX_LEVEL_EXTRA_N 12
 int amgx_level_extra(amgx_handle h, int level, int64_t* out, int n_out);
@@ -357,6 +381,16 @@ int amgx_level_extra(amgx_handle h, int level, int64_t* out, int n_out);
  * Returns 0, or non-zero for a bad level or n_out < 1. */
 #define AMGX_JACOBI_PREC_INFO_N 5
 int amgx_jacobi_prec_info(amgx_handle h, int level, int64_t* out, int n_out);
+
+/* what mat_prec = AMGX_PREC_F32_SCALAR_GS gave this level.  Fills out[0 .. min(n_out, AMGX_GS_PREC_INFO_N)):
+ *    0 the sweeps of this level read float images (0 under AMGX_GS_F32_WIDE)
+ *    1 bit mask of the images converted: A, full, fullLW, lowin, rest, restLW, sell, lower, upper = bits 0 .. 8
+ *    2 value bytes of the converted arrays (under AMGX_GS_F32_WIDE: of the rounded fp64 arrays)
+ *    3 fp64 value bytes released
+ *    4 the level is the AMGX_GS_F32_WIDE twin
+ * Returns 0, or non-zero for a bad level or n_out < 1. */
+#define AMGX_GS_PREC_INFO_N 5
+int amgx_gs_prec_info(amgx_handle h, int level, int64_t* out, int n_out);
 
 /* measurement hook for bench.py: launches one hot-path kernel `reps` times on the handle's stream,
  * bracketed by HIP events, and returns the average duration in milliseconds.
@@ -378,7 +412,7 @@ int amgx_jacobi_prec_info(amgx_handle h, int level, int64_t* out, int n_out);
  *           On a level with single-precision Gauss-Seidel images it reads them
  * ops 5 and 10 time what the cycle runs: on a level with a single-precision image (mat_prec) they read that image; op 0 is
  * amgx_residual's kernel and reads the fp64 image.  On a scalar Jacobi level with jacobi_prec != 0 ops 1, 5, 6, 7 and 8 read the
- * level's single-precision images. */
+ * level's single-precision images, on a scalar Gauss-Seidel level with mat_prec = AMGX_PREC_F32_SCALAR_GS ops 5 and 9. */
 int amgx_time_op(amgx_handle h, int level, int op, int reps, double* avg_ms);
 
 /* ---- GSS4: Gauss-Seidel on a subset of the rows, on a compressed device copy ------------------------------------------
@@ -463,6 +497,9 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  * column loop (amgx_multi_note names the smoother and the level).  So does a handle with a Gauss-Seidel level that reads
  * single-precision images (mat_prec = AMGX_PREC_F32): the fused sweeps read fp64 images, and the note says "single-precision
  * Gauss-Seidel images (level l)".
+ * A handle with a scalar Gauss-Seidel level that has single-precision images (mat_prec = AMGX_PREC_F32_SCALAR_GS; the
+ * AMGX_GS_F32_WIDE twin too) is not fused under AMGX_MULTI_FUSE_GS / _GS_BLOCK with the same note, and amgx_smooth_multi, amgx_down_multi
+ * and the two _DOWN bits keep the column loop on such a level: the fp64 values of its sweep images are released.
  * A handle with a scalar Jacobi level that reads single-precision images (jacobi_prec != 0) is not fused under any
  * of these flags, the default rule included, and amgx_down_multi keeps the column loop on such a level: the multi-vector kernels read
  * fp64 images.  The note says "single-precision Jacobi images (level l)"; a column equals amgx_apply bit for bit.

@@ -34,9 +34,10 @@ def _flags(kwargs):
 
 
 def _mat_prec_flag(v):
-    """ngs_amg_mat_prec = double | single | single_gs, or one of them per level (an own option: single-precision storage of the level
-    matrix for the smoother passes of the Chebyshev levels; single_gs: also the images of the block Gauss-Seidel
-    sweeps); validated by device.mat_prec_levels"""
+    """ngs_amg_mat_prec = double | single | single_gs | single_gs_all, or one of them per level (an own option: single-precision storage
+    of the level matrix for the smoother passes of the Chebyshev levels; single_gs: also the images of the block
+    Gauss-Seidel sweeps; single_gs_all: also those of the scalar Gauss-Seidel sweeps); validated by
+    device.mat_prec_levels"""
     if isinstance(v, (list, tuple)):
         return [x.lower() if isinstance(x, str) else x for x in v]
     return v.lower() if isinstance(v, str) else v
@@ -620,7 +621,8 @@ def CreateChebyshevSmoother(mat, freedofs=None, degree=2, ratio=10, lambda_max=N
 def CreateHybridGSS(mat, freedofs=None, pinv=False, NG_MPI_overlap=True, NG_MPI_thread=False, symm=False,
                     symm_loc=False, nsteps=1, nsteps_loc=1, device=0, mat_prec="double"):
     """single GPU: the hybrid smoother degenerates to (multicolour) Gauss-Seidel on the local matrix.
-    mat_prec="single_gs": block sweeps in a BSELL form read single-precision images; other forms stay fp64."""
+    mat_prec="single_gs": block sweeps in a BSELL form read single-precision images; other forms stay fp64.
+    mat_prec="single_gs_all": the sweeps of a scalar matrix read single-precision images too."""
     return _StandaloneSmoother(mat, freedofs, "gs", pinv=pinv, nsteps=nsteps, symm=symm, device=device, mat_prec=mat_prec)
 
 

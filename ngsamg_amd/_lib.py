@@ -270,6 +270,8 @@ AMGX_COMM_RCCL, AMGX_COMM_LOCAL = 0, 1
 AMGX_UNIQUE_ID_BYTES = 128
 AMGX_CYCLE = {"V": 0, "W": 1, "BS": 2}
 AMGX_PREC_F64, AMGX_PREC_F32 = 0, 1          # amgx_level_desc.mat_prec
+AMGX_PREC_F32_SCALAR_GS = 2                  # ... on scalar AMGX_SM_GS levels only
+AMGX_GS_PREC_INFO_N = 5
 AMGX_JACOBI_PREC_F64, AMGX_JACOBI_PREC_F32, AMGX_JACOBI_PREC_F32_WIDE = 0, 1, 2      # amgx_level_desc.jacobi_prec
 AMGX_JACOBI_PREC_INFO_N = 5
 AMGX_CLEV_NONE, AMGX_CLEV_INV = 0, 1
@@ -299,7 +301,7 @@ AMGX_SYMBOLS = [
     "amgx_device_count", "amgx_spgemm", "amgx_galerkin", "amgx_csr_result_fetch",
     "amgx_apply_multi", "amgx_matvec_multi", "amgx_pcg_multi", "amgx_multi_info", "amgx_multi_plan", "amgx_multi_note",
     "amgx_smooth_multi", "amgx_down_multi", "amgx_multi_level_plan", "amgx_multi_level_note",
-    "amgx_smoother_info", "amgx_jacobi_prec_info",
+    "amgx_smoother_info", "amgx_jacobi_prec_info", "amgx_gs_prec_info",
     "amgx_mv_gram", "amgx_mv_combine", "amgx_mv_gram_plan",
 ]
 
@@ -349,6 +351,7 @@ def hip():
     lib.amgx_level_paths.argtypes = [vp, C.c_int, c_i64p, C.c_int]
     lib.amgx_level_extra.argtypes = [vp, C.c_int, c_i64p, C.c_int]
     lib.amgx_jacobi_prec_info.argtypes = [vp, C.c_int, c_i64p, C.c_int]
+    lib.amgx_gs_prec_info.argtypes = [vp, C.c_int, c_i64p, C.c_int]
     lib.amgx_smoother_info.argtypes = [vp, C.c_int, c_i32p, c_i32p, c_f64p, c_f64p, c_i32p]
     lib.amgx_time_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_f64p]
     lib.amgx_pcg.argtypes = [vp, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int, c_f64p, c_i32p]

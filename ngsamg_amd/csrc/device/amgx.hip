@@ -143,6 +143,10 @@ struct DevMatrix {
     SellMat view() const { return SellMat{slice_ptr.p, col32.p, col16.p, cbase.p, val.p, rowrel, diag_first, wdiag, xcd}; }
     SellMat view_of(const double* v) const { return SellMat{slice_ptr.p, col32.p, col16.p, cbase.p, v, rowrel, diag_first, wdiag, xcd}; }
     SellMatT<float> view32(const float* v32) const { return SellMatT<float>{slice_ptr.p, col32.p, col16.p, cbase.p, v32, rowrel, diag_first, wdiag, xcd}; }
+    // the sweep-only images of a scalar Gauss-Seidel level (DevGS::sell / lower / upper, DevGSB::full / fullLW / lowin) carry their float
+    // values here (mat_f32_image); `val` is released where they exist.  An image inside a DevMatrix uses DevMatrix::val32.
+    DevBuf<float> val32;
+    SellMatT<float> view32() const { return view32(val32.p); }
   } sell;
   struct Rb {                          // rigid-body transfer blocks (kernels.hpp, RbMat): P_ik = w_ik Q(t_ik), or its transpose
     int dim = 0, bf = 0, bc = 0;       // spatial dimension of Q (0: w I), fine / coarse block size
@@ -426,6 +430,13 @@ struct DevLevel {
   bool jp32 = false, jp32_wide = false;
   int jp_mask = 0;
   int64_t jp_bytes = 0, jp_released = 0;
+  // scalar Gauss-Seidel level with mat_prec = AMGX_PREC_F32_SCALAR_GS (decided by mat_f32_image).  sgs32: the sweeps and
+  // the residual after the sweep from zero read float images.  sgs32_wide: the AMGX_GS_F32_WIDE twin -- the fp64 images hold the rounded
+  // values (A: DevMatrix::val64r).  sgs_mask: the images converted (A, full, fullLW, lowin, rest, restLW, sell, lower, upper = bits
+  // 0 .. 8); sgs_bytes: bytes of the converted value arrays; sgs_released: fp64 value bytes given back.
+  bool sgs32 = false, sgs32_wide = false;
+  int sgs_mask = 0;
+  int64_t sgs_bytes = 0, sgs_released = 0;
   DevGS gs;
   DevGSB gsb;
   DevBGSB bgsb;
@@ -479,7 +490,7 @@ static DownPlan make_down_plan(const DevLevel& L, const DevRestrict& R, int mode
   DownPlan p;
   p.on = true; p.mode = mode; p.ept = R.ept; p.n_chunks = R.n_chunks;
   p.family = dia ? (jacobi_form == DOWN_DIA ? DOWN_FAM_DIA : DOWN_FAM_DIA_BOX) : lw ? DOWN_FAM_LW : M.sell.win ? DOWN_FAM_WIN : DOWN_FAM_SELL;
-  p.diags = dia ? L.dia.K : 0; p.lanes = dia ? 1 : M.lanes; p.f32 = (mode == 2 && M.has32()) || (mode == 0 && (dia ? L.dia.has32() : M.has32()));
+  p.diags = dia ? L.dia.K : 0; p.lanes = dia ? 1 : M.lanes; p.f32 = ((mode == 2 || mode == 1) && M.has32()) || (mode == 0 && (dia ? L.dia.has32() : M.has32()));
   // (RG and the local-window chunks are always built for DOWN_THREADS lanes; the other builders leave their choice in fused_block)
   p.threads = (mode == 1 || lw) ? DOWN_THREADS : L.fused_block;
   p.unit_rows = down_rows_per_chunk(p.threads, p.lanes);
@@ -1581,15 +1592,17 @@ struct Handle {
     // (r = rest x of a Gauss-Seidel block level)
     // for SELL, on one vector, also under the epilogues of a scalar Jacobi level's passes (EP_PRE on A', EP_JAC on A, EP_AXPY on Q; 5.20)
     constexpr bool EP32 = EP == EP_RES || EP == EP_CHEB;
-    constexpr bool EP32_SELL = EP32 || (NV == 1 && (EP == EP_PRE || EP == EP_JAC || EP == EP_AXPY));
+    // ... and under EP_CRES on `rest` of a scalar Gauss-Seidel level (plain and windowed sliced-ELL; 5.21)
+    constexpr bool EP32_SELL = EP32 || (NV == 1 && (EP == EP_PRE || EP == EP_JAC || EP == EP_AXPY || EP == EP_CRES));
+    constexpr bool EP32_WIN = NV == 1 && EP == EP_CRES;
     constexpr bool EP32_BSELL = EP32 || (EP == EP_MULT && NV == 1);
     const bool f32 = sm_pass && M.has32() && (EP32 || (EP32_SELL && M.fmt == FMT_SELL) || (EP32_BSELL && M.fmt == FMT_BSELL));
-    if (f32 && !((M.fmt == FMT_SELL && !M.sell.win) || M.fmt == FMT_BSELL)) throw Err("single-precision image on a format that has none");
+    if (f32 && !((M.fmt == FMT_SELL && (!M.sell.win || EP32_WIN)) || M.fmt == FMT_BSELL)) throw Err("single-precision image on a format that has none");
     // run(view of the image this product reads); has32: a float kernel is instantiated for this format and epilogue
     auto image = [&](auto has32, const auto& v64, const auto& v32, auto&& run) {
       if constexpr (decltype(has32)::value) { if (f32) { run(v32); return; } }
       // (a scalar Jacobi level with single-precision images keeps only the float values of A', Q: DESIGN.md 5.20)
-      if (!v64.val && M.has32()) throw Err("product: the fp64 values of this image were released (single-precision Jacobi images); only the passes of the level read it");
+      if (!v64.val && M.has32()) throw Err("product: the fp64 values of this image were released (single-precision Jacobi or Gauss-Seidel images); only the passes of the level read it");
       run(v64);
     };
     int64_t a, b;                                     // the units [a, b) of the row split that this launch covers
@@ -1614,8 +1627,12 @@ struct Handle {
       if (M.sell.win != SELL_WIN) throw Err("windowed SELL: unexpected window size");
       unit_range(sp, SELL_WIN, (M.n_rows + SELL_WIN - 1) / SELL_WIN, a, b);
       if (b <= a) return;
-      if constexpr (NV == 1) launch(sell_win_spmv_kernel<SELL_WIN, EP>, (int)(b - a), SELL_WIN, 0, stream, M.n_rows, (int)a, M.sell.view(), M.sell.rowloc.p, x, y, ep);
-      else launch(sell_win_spmm_kernel<SELL_WIN, NV, EP>, (int)(b - a), SELL_WIN, 0, stream, M.n_rows, M.sell.view(), M.sell.rowloc.p, x, y, ep);
+      // (a smoother pass reads the rounded values of A at fp64 width where the level has them, see val64r)
+      image(std::bool_constant<EP32_WIN>{}, sm_pass && M.val64r.p ? M.sell.view_of(M.val64r.p) : M.sell.view(), M.sell.view32(M.val32.p), [&](auto V) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(V.val)>>;       // double / float
+        if constexpr (NV == 1) launch(sell_win_spmv_kernel<SELL_WIN, EP, T>, (int)(b - a), SELL_WIN, 0, stream, M.n_rows, (int)a, V, M.sell.rowloc.p, x, y, ep);
+        else launch(sell_win_spmm_kernel<SELL_WIN, NV, EP>, (int)(b - a), SELL_WIN, 0, stream, M.n_rows, V, M.sell.rowloc.p, x, y, ep);
+      });
     } else if (M.fmt == FMT_SELL) {
       unit_range(sp, WAVE / M.lanes, M.n_slices, a, b);
       if (b <= a) return;
@@ -1633,9 +1650,10 @@ struct Handle {
       unit_range(sp, 1, M.n_rows, a, b);
       if (b <= a) return;
       const int grid = grid_for((b - a) * M.lanes);
+      const double* const sval = sm_pass && M.val64r.p ? M.val64r.p : M.val.p;       // (a smoother pass: the rounded values, see val64r)
       auto run = [&](auto G) {
-        if constexpr (NV == 1) launch(csrvec_spmv_kernel<G(), EP>, grid, BLOCK, 0, stream, a, b, M.rowptr.p, M.col.p, M.val.p, x, y, ep);
-        else launch(csrvec_spmm_kernel<G(), NV, EP>, grid, BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, M.val.p, x, y, ep);
+        if constexpr (NV == 1) launch(csrvec_spmv_kernel<G(), EP>, grid, BLOCK, 0, stream, a, b, M.rowptr.p, M.col.p, sval, x, y, ep);
+        else launch(csrvec_spmm_kernel<G(), NV, EP>, grid, BLOCK, 0, stream, M.n_rows, M.rowptr.p, M.col.p, sval, x, y, ep);
       };
       if (!dispatch(CsrLanes{}, M.lanes, run)) run(Int<64>{});
     } else if constexpr (EP == EP_PRE) {
@@ -1775,7 +1793,7 @@ struct Handle {
   // on the iterate are written once; what the widths do not share is stated once too, as a fact about NV:
   //   units        NV > 1 sweeps whole levels (gs_units), as product<NV > 1> takes no Span
   //   images       NV > 1 reads fp64 images in the plain view; one vector the single-precision images of a level that has them and the
-  //                view of knobs.bsell_xmode (gs_prec, gs_view).  No NV kernel is built on float.
+  //                view of knobs.bsell_xmode (gs_prec, gs_view; scalar levels: sgs_image).  No NV kernel is built on float.
   //   block size   a size the BSELL kernels are not listed for takes the 2 x 2 kernel on one vector and an fp64 image, and is an error
   //                on NV > 1 and on float images (gs_bsell_size)
   //   hybrid form  the local-window image and the mid-width kernel of gsb_sweep are built for one vector (GSB_FORMS there)
@@ -1809,6 +1827,21 @@ struct Handle {
       return M.bsell.view32(M.val32.p, xmode);
     } else return M.bsell.view(xmode);
   }
+  // The sliced-ELL images that the sweeps of a SCALAR Gauss-Seidel level read: run(view) gets the float view on one vector of a level
+  // with single-precision images (DevLevel::sgs32), otherwise the fp64 one.  An fp64 view of released values is an
+  // error here, never a null pointer in a kernel (the NV kernels read fp64 images: such a level keeps the column loop).
+  template <int NV, class F>
+  static void sgs_image(const DevLevel& L, const DevMatrix::Sell& S, F&& run) {
+    if constexpr (NV == 1) {
+      if (L.sgs32) {
+        if (!S.val32.p && S.val.p) throw Err("single-precision Gauss-Seidel images: a sweep image has no float twin");
+        run(S.view32());
+        return;
+      }
+    }
+    if (!S.val.p && S.val32.p) throw Err("Gauss-Seidel sweep: the fp64 values of this image were released (single-precision Gauss-Seidel images); only the single-vector passes of the level read it");
+    run(S.view());
+  }
   // the block sizes of the BSELL colour and upper-residual kernels
   template <int NV, class T, class F>
   static void gs_bsell_size(int bs, F&& run) {
@@ -1835,9 +1868,12 @@ struct Handle {
       if (L.bs == 1) {
         const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
         if (s1 == s0) continue;
-        gs_lanes(g.lanes, [&](auto GG) {
-          if constexpr (NV == 1) launch(gs_color_kernel<GG()>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, copy.view(), g.rowid.p, L.dinv.p, b, x);
-          else launch(gs_color_nv_kernel<GG(), NV>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, copy.view(), g.rowid.p, L.dinv.p, b, x);
+        sgs_image<NV>(L, copy, [&](auto M) {
+          using V = std::remove_const_t<std::remove_pointer_t<decltype(M.val)>>;       // double / float
+          gs_lanes(g.lanes, [&](auto GG) {
+            if constexpr (NV == 1) launch(gs_color_kernel<GG(), V>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, M, g.rowid.p, L.dinv.p, b, x);
+            else launch(gs_color_nv_kernel<GG(), NV>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, M, g.rowid.p, L.dinv.p, b, x);
+          });
         });
       } else if (g.bsell_ok) {
         const int s0 = g.color_slice_ptr[c], s1 = g.color_slice_ptr[c + 1];
@@ -1877,9 +1913,12 @@ struct Handle {
     const int ns = L.bs == 1 ? g.n_slices_total : g.bupper.n_slices;
     if (ns <= 0) return;
     if (L.bs == 1) {
-      gs_lanes(g.lanes, [&](auto GG) {
-        if constexpr (NV == 1) launch(gs_upper_residual_kernel<GG()>, wave_grid(ns), BLOCK, 0, stream, ns, g.upper.view(), g.rowid.p, x, r);
-        else launch(gs_upper_residual_nv_kernel<GG(), NV>, wave_grid(ns), BLOCK, 0, stream, ns, g.upper.view(), g.rowid.p, x, r);
+      sgs_image<NV>(L, g.upper, [&](auto M) {
+        using V = std::remove_const_t<std::remove_pointer_t<decltype(M.val)>>;         // double / float
+        gs_lanes(g.lanes, [&](auto GG) {
+          if constexpr (NV == 1) launch(gs_upper_residual_kernel<GG(), V>, wave_grid(ns), BLOCK, 0, stream, ns, M, g.rowid.p, x, r);
+          else launch(gs_upper_residual_nv_kernel<GG(), NV>, wave_grid(ns), BLOCK, 0, stream, ns, M, g.rowid.p, x, r);
+        });
       });
       return;
     }
@@ -1910,30 +1949,33 @@ struct Handle {
     const bool lowin = fz && L.paths.zero_split;
     const bool lw = GSB_FORMS && !fz && g.lw;
     GsbArgs a{g.rowid.p, g.slotcolor.p, L.dinv.p, b, g.n_colors, dir, lw ? g.flw_cptr.p : nullptr, lw ? g.flw_ccol.p : nullptr};
-    const SellMat M = lw ? g.fullLW.view() : lowin ? g.lowin.view() : g.full.view();
+    const DevMatrix::Sell& image = lw ? g.fullLW : lowin ? g.lowin : g.full;
     const bool narrow = lowin && g.narrow;
     const bool mid = GSB_FORMS && !fz && g.mid;
-    // <workgroup size, lanes per row, from zero, entries per lane and pass, local-window image>; the mid-width and local-window
-    // forms exist for more than one lane per row only
-    auto run = [&](auto TT) {
-      gs_lanes(g.G, [&](auto GG) {
-        auto sweep = [&](auto ZZ, auto WW, auto LW) {
-          if constexpr (NV == 1) launch(gsb_sweep_kernel<TT(), GG(), ZZ(), WW(), LW()>, blk1 - blk0, TT(), 0, stream, L.n, blk0, M, a, xin, xout);
-          else launch(gsb_sweep_nv_kernel<TT(), GG(), ZZ(), WW(), NV>, blk1 - blk0, TT(), 0, stream, L.n, M, a, xin, xout);    // (whole level: no first block)
-        };
-        constexpr std::false_type no{};
-        constexpr std::true_type yes{};
-        if (narrow) return sweep(yes, Int<2>{}, no);
-        if (fz) return sweep(yes, Int<GSB_WP>{}, no);
-        if constexpr (GSB_FORMS && GG() > 1) {
-          if (lw && mid) return sweep(no, Int<5>{}, yes);
-          if (lw) return sweep(no, Int<GSB_WP>{}, yes);
-          if (mid) return sweep(no, Int<5>{}, no);
-        }
-        sweep(no, Int<GSB_WP>{}, no);
-      });
-    };
-    if (!dispatch<256, 512>(g.TH, run)) run(Int<1024>{});            // any other workgroup size: 1024
+    // <workgroup size, lanes per row, from zero, entries per lane and pass, local-window image, value type>; the mid-width and
+    // local-window forms exist for more than one lane per row only
+    sgs_image<NV>(L, image, [&](auto M) {
+      using V = std::remove_const_t<std::remove_pointer_t<decltype(M.val)>>;             // double / float
+      auto run = [&](auto TT) {
+        gs_lanes(g.G, [&](auto GG) {
+          auto sweep = [&](auto ZZ, auto WW, auto LW) {
+            if constexpr (NV == 1) launch(gsb_sweep_kernel<TT(), GG(), ZZ(), WW(), LW(), V>, blk1 - blk0, TT(), 0, stream, L.n, blk0, M, a, xin, xout);
+            else launch(gsb_sweep_nv_kernel<TT(), GG(), ZZ(), WW(), NV>, blk1 - blk0, TT(), 0, stream, L.n, M, a, xin, xout);    // (whole level: no first block)
+          };
+          constexpr std::false_type no{};
+          constexpr std::true_type yes{};
+          if (narrow) return sweep(yes, Int<2>{}, no);
+          if (fz) return sweep(yes, Int<GSB_WP>{}, no);
+          if constexpr (GSB_FORMS && GG() > 1) {
+            if (lw && mid) return sweep(no, Int<5>{}, yes);
+            if (lw) return sweep(no, Int<GSB_WP>{}, yes);
+            if (mid) return sweep(no, Int<5>{}, no);
+          }
+          sweep(no, Int<GSB_WP>{}, no);
+        });
+      };
+      if (!dispatch<256, 512>(g.TH, run)) run(Int<1024>{});            // any other workgroup size: 1024
+    });
   }
 
   // one block-hybrid Gauss-Seidel sweep on a square-block level (bgsb_sweep_kernel).  Hybrid form: ONE launch, out of place
@@ -1993,6 +2035,7 @@ struct Handle {
   // Multi::facts: the rule of multi_rule.hpp, amgx_smooth_multi).  Scalar levels (AMGX_MULTI_FUSE_GS):
   bool multi_sweep_ok(const DevLevel& L) const {
     if (L.sm_type != AMGX_SM_GS || L.bs != 1 || L.n != L.ncols || !L.paths.plain) return false;
+    if (L.sgs32 || L.sgs32_wide) return false;         // single-precision images: the NV kernels read fp64 images
     return L.paths.sweep == SWEEP_GSB || L.paths.sweep == SWEEP_MC;
   }
   // ... square-block levels (AMGX_MULTI_FUSE_GS_BLOCK; multi_sweep_ok keeps the answer of AMGX_MULTI_FUSE_GS)
@@ -2089,7 +2132,7 @@ struct Handle {
       case SWEEP_GSB:
         // inside a block only couplings to lower colours contributed; (b - L_in x)_k = x_k / dinv_k on every swept row, hence
         // r = b - A x = (1/dinv - a_kk) .* x - (A - L_in - D) x = c .* x - rest x
-        product<NV, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, nt});
+        product<NV, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, nt}, Span(), NV == 1 && L.sgs32);
         return;
       case SWEEP_BGSB: case SWEEP_BGSB_BC:                                          // r = rest x (see DevBGSB)
         product<NV, EP_MULT>(L.bgsb.rest, x, r, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}, Span(), NV == 1 && L.gs32);
@@ -2154,7 +2197,9 @@ struct Handle {
       // and a residual formed with the rounded A would steer the next correction towards the solution of the ROUNDED system -- a shift of
       // cond(A) * 6e-8 in the cycle's result (measured: 3.4e-6 in the W-cycle of a 40 x 36 elasticity grid against 5e-8 in its V-cycle).
       // The residual right after the sweep from zero (residual_after_zero: |r| ~ |b|, nothing cancels) reads the float images.
-      if (update_res) residual(L.A, x, b, res);
+      // A scalar level with single-precision images follows 5.20: inside pre-smoothing from zero the residual goes to
+      // the restriction (|r| ~ |b|) and is a pass of the level, on the image the sweeps read
+      if (update_res) { if (pre_from_zero && (L.sgs32 || L.sgs32_wide)) residual_sm(L, x, b, res); else residual(L.A, x, b, res); }
     }
   }
 
@@ -2293,14 +2338,20 @@ struct Handle {
             else pick(DownEpt{}, p.ept, [&](auto EPT) { sell(Int<DOWN_THREADS>{}, EPT, Int<1>{}); });
           };
           // (MODE 2 is a smoother pass: the float kernel on the single-precision image where the level has one)
-          // (... and MODE 0 on the float A' of a scalar Jacobi level)
-          if constexpr (MODE() != 1) { if (p.f32) return image(M.sell.view32(M.val32.p)); }
+          // (... and MODE 0 on the float A' of a scalar Jacobi level; MODE 1 on the float `rest` of a scalar
+          //  Gauss-Seidel level)
+          if (p.f32) return image(M.sell.view32(M.val32.p));
           image(M.sell.view());
         });
       } else if (p.family == DOWN_FAM_WIN) {
         pick(IntList<0, 1>{}, p.mode, [&](auto MODE) { pick(DownEpt{}, p.ept, [&](auto EPT) {
-          launch(sell_win_pre_restrict_kernel<SELL_WIN, EPT(), MODE()>, grid, SELL_WIN, 0, stream, M.n_rows, c0, M.sell.view(), M.sell.rowloc.p, o.v, o.d, o.omega,
-                 o.flags, o.xout, R.view());
+          auto image = [&](auto view) {
+            using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;       // double / float
+            launch(sell_win_pre_restrict_kernel<SELL_WIN, EPT(), MODE(), V>, grid, SELL_WIN, 0, stream, M.n_rows, c0, view, M.sell.rowloc.p, o.v, o.d, o.omega,
+                   o.flags, o.xout, R.view());
+          };
+          if constexpr (MODE() == 1) { if (p.f32) return image(M.sell.view32(M.val32.p)); }
+          image(M.sell.view());
         }); });
       } else if (p.family == DOWN_FAM_LW) {
         // long-row level: the local-window image (gathers from LDS), chunks of 512 / lanes rows
@@ -2311,7 +2362,7 @@ struct Handle {
             launch(sell_lw_pre_restrict_kernel<EPT(), G(), MODE(), V>, grid, DOWN_THREADS, 0, stream, M.n_rows, c0, M.n_slices, view, cptr, ccol, o.v, o.d,
                    o.omega, o.flags, o.xout, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, R.part.p, R.dest.p);
           };
-          if constexpr (MODE() == 0) { if (p.f32) return image(M.sell.view32(M.val32.p)); }
+          if (p.f32) return image(M.sell.view32(M.val32.p));
           image(M.sell.view());
         }); }); });
       } else if (p.family == DOWN_FAM_DIA) {
@@ -3328,6 +3379,8 @@ int amgx_level_extra(amgx_handle hh, int level, int64_t* out, int n_out) {
     if (!L.Apre.empty() && L.Apre.fmt == amgx::FMT_SELL) { v[6] = L.Apre.sell.diag_first; v[7] = L.Apre.sell.wdiag; }
     v[8] = (int64_t)h.graphs.size();
     v[9] = L.gs32 ? 1 : 0; v[10] = L.gs32_images; v[11] = L.gs32_bytes;
+    // (a scalar Gauss-Seidel level with single-precision images, DESIGN.md 5.21: the same three meanings)
+    if (L.sgs32 || L.sgs32_wide) { v[9] = L.sgs32 ? 1 : 0; v[10] = __builtin_popcount((unsigned)L.sgs_mask); v[11] = L.sgs_bytes; }
     for (int k = 0; k < std::min(n_out, AMGX_LEVEL_EXTRA_N); ++k) out[k] = v[k];
   });
 }
@@ -3339,6 +3392,16 @@ int amgx_jacobi_prec_info(amgx_handle hh, int level, int64_t* out, int n_out) {
     const amgx::DevLevel& L = h.lev[level];
     const int64_t v[AMGX_JACOBI_PREC_INFO_N] = {L.jp32 ? 1 : 0, L.jp_mask, L.jp_bytes, L.jp_released, L.jp32_wide ? 1 : 0};
     for (int k = 0; k < std::min(n_out, AMGX_JACOBI_PREC_INFO_N); ++k) out[k] = v[k];
+  });
+}
+
+int amgx_gs_prec_info(amgx_handle hh, int level, int64_t* out, int n_out) {
+  return guard(hh, [&](amgx::Handle& h) {
+    if (level < 0 || level >= h.n_levels()) throw amgx::Err("amgx_gs_prec_info: level out of range");
+    if (!out || n_out < 1) throw amgx::Err("amgx_gs_prec_info: bad arguments");
+    const amgx::DevLevel& L = h.lev[level];
+    const int64_t v[AMGX_GS_PREC_INFO_N] = {L.sgs32 ? 1 : 0, L.sgs_mask, L.sgs_bytes, L.sgs_released, L.sgs32_wide ? 1 : 0};
+    for (int k = 0; k < std::min(n_out, AMGX_GS_PREC_INFO_N); ++k) out[k] = v[k];
   });
 }
 

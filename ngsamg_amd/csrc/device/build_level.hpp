@@ -55,9 +55,17 @@ static void check_level(LevelBuild& B) {
   }
   // single-precision matrix storage (the coarsest level of a cycle, which has no smoother passes, ignores the field)
   if (B.smoothed()) {
-    if (s.mat_prec != AMGX_PREC_F64 && s.mat_prec != AMGX_PREC_F32)
-      throw Err("amgx_create: level " + std::to_string(B.l) + ": mat_prec must be AMGX_PREC_F64 (0) or AMGX_PREC_F32 (1), got " + std::to_string(s.mat_prec));
-    // (a scalar Gauss-Seidel level has no form with single-precision images: the request stays the error it was)
+    if (s.mat_prec != AMGX_PREC_F64 && s.mat_prec != AMGX_PREC_F32 && s.mat_prec != AMGX_PREC_F32_SCALAR_GS)
+      throw Err("amgx_create: level " + std::to_string(B.l) + ": mat_prec must be AMGX_PREC_F64 (0), AMGX_PREC_F32 (1) or AMGX_PREC_F32_SCALAR_GS (2), got " +
+                std::to_string(s.mat_prec));
+    // single-precision images of a scalar Gauss-Seidel level: a value of its own, AMGX_PREC_F32 keeps every error below
+    if (s.mat_prec == AMGX_PREC_F32_SCALAR_GS) {
+      const std::string at = "amgx_create: level " + std::to_string(B.l) + ": mat_prec = AMGX_PREC_F32_SCALAR_GS ";
+      if (s.sm_type != AMGX_SM_GS) throw Err(at + "is available on Gauss-Seidel levels (sm_type = AMGX_SM_GS) only");
+      if (s.A.br != 1) throw Err(at + "is available on scalar levels (block size 1) only; a square-block Gauss-Seidel level takes AMGX_PREC_F32");
+      if (s.A.n_cols != s.A.n_rows || B.dense_first < 0) throw Err(at + "is not available on rank-partitioned levels");
+    }
+    // (AMGX_PREC_F32 on a scalar Gauss-Seidel level stays the error it was: its images are asked for with AMGX_PREC_F32_SCALAR_GS)
     if (s.mat_prec == AMGX_PREC_F32 && s.sm_type != AMGX_SM_CHEBY && !(s.sm_type == AMGX_SM_GS && s.A.br > 1))
       throw Err("amgx_create: level " + std::to_string(B.l) + ": mat_prec = AMGX_PREC_F32 is available on Chebyshev levels (sm_type = AMGX_SM_CHEBY) "
                 "and on square-block Gauss-Seidel levels (sm_type = AMGX_SM_GS, block size > 1) only");
@@ -505,11 +513,14 @@ static void cheb_fused_restrict(LevelBuild& B) {
 // amgx_matvec, amgx_residual, the Krylov operator and the lambda_max estimate keep the fp64 image of A.
 // A value that rounds to +-inf is an error that names the level; nothing half-built is left behind.
 // AMGX_NO_MAT_F32=1 ignores every request (the handle is then the double handle, bit for bit).
+//   Scalar Gauss-Seidel levels with mat_prec = AMGX_PREC_F32_SCALAR_GS: scalar_gs_f32_images below.
 static void jacobi_f32_images(LevelBuild& B);
+static void scalar_gs_f32_images(LevelBuild& B);
 static void mat_f32_image(LevelBuild& B) {
   const amgx_level_desc& s = B.s;
   DevLevel& L = B.L;
   if (B.smoothed() && s.jacobi_prec != AMGX_JACOBI_PREC_F64 && !B.K.no_mat_f32) jacobi_f32_images(B);
+  if (B.smoothed() && s.mat_prec == AMGX_PREC_F32_SCALAR_GS && !B.K.no_mat_f32) scalar_gs_f32_images(B);
   if (!B.smoothed() || s.mat_prec != AMGX_PREC_F32 || B.K.no_mat_f32) return;
   auto beyond = [&](int64_t bad, const char* what) {
     return Err("amgx_create: level " + std::to_string(B.l) + ": " + std::to_string(bad) + " value(s) of " + what +
@@ -643,6 +654,83 @@ static void jacobi_f32_images(LevelBuild& B) {
     L.jp_bytes += (wide ? 8 : 4) * n;
   }
   if (L.jp_mask) (wide ? L.jp32_wide : L.jp32) = true;
+}
+
+// Scalar Gauss-Seidel levels with mat_prec = AMGX_PREC_F32_SCALAR_GS (check_level has refused every other level).  Each
+// sweep image the level's form has -- block-hybrid: gsb.full, fullLW, lowin, rest, restLW; multicolour: gs.sell, lower, upper -- gets a
+// float value array, the stored fp64 values rounded to nearest; index arrays, rowid, slotcolor and the window lists are shared.  dinv,
+// gsb.cvec, the vectors, P, P^T, the restriction data, the tail program's copies and the dense tail stay fp64 and true.
+//   A gets an image only on a level WITHOUT split images, where residual_after_zero reads A (residual_sm): a float array where A is
+//   plain sliced-ELL, else -- a format without a float kernel -- the rounded values at fp64 width in DevMatrix::val64r.  A keeps its
+//   true fp64 values for update_res, amgx_matvec, amgx_residual and the Krylov operator.  `rest` in CSR-vector form (a badly padded
+//   remainder: a small level) has no float kernel either: its values are rounded in place at fp64 width.
+//   The fp64 value arrays of the sweep images are released: only the sweeps and the residual after the sweep from zero read them, and
+//   those read the float arrays from here on (Handle::sgs_image and Handle::product refuse an fp64 view of a released image).
+//   AMGX_GS_F32_WIDE=1 (A/B twin): no float arrays; the rounded values at fp64 width, in place (A: val64r); the fp64 kernels run.
+// Range check first, on every image, before anything is overwritten or released; a value beyond float is an error that names the level.
+static void scalar_gs_f32_images(LevelBuild& B) {
+  DevLevel& L = B.L;
+  const int form = sweep_path(L);
+  if (form != SWEEP_GSB && form != SWEEP_MC) return;       // (a level without rows or without a colouring: nothing to convert)
+  const bool wide = B.K.gs_f32_wide;
+  // val: the fp64 values; v32: where the float array goes (null: no float kernel for the format); v64r / keep64: A keeps its true values
+  struct Img { DevBuf<double>* val; DevBuf<float>* v32; DevBuf<double>* v64r; int bit; const char* what; bool keep64; };
+  std::vector<Img> imgs;
+  auto sell_img = [&](DevMatrix::Sell& S, int bit, const char* what) { if (S.val.n > 0) imgs.push_back({&S.val, &S.val32, nullptr, bit, what, false}); };
+  auto mat_img = [&](DevMatrix& M, int bit, const char* what) {
+    if (M.empty()) return;
+    if (M.fmt == FMT_SELL) { if (M.sell.val.n > 0) imgs.push_back({&M.sell.val, &M.val32, nullptr, bit, what, false}); }
+    else if (M.fmt == FMT_CSRVEC && M.br == 1 && M.val.n > 0) imgs.push_back({&M.val, nullptr, nullptr, bit, what, false});
+  };
+  bool split = false;
+  if (form == SWEEP_GSB) {
+    DevGSB& g = L.gsb;
+    split = g.has_split;
+    sell_img(g.full, 1, "the image `full`");
+    if (g.has_fullLW) sell_img(g.fullLW, 2, "the local-window image of `full`");
+    if (split) {
+      sell_img(g.lowin, 3, "the image `lowin`");
+      mat_img(g.rest, 4, "the image `rest`");
+      mat_img(g.restLW, 5, "the local-window image of `rest`");
+    }
+  } else {
+    DevGS& g = L.gs;
+    split = g.has_split;
+    sell_img(g.sell, 6, "the colour-major copy of A");
+    if (split) { sell_img(g.lower, 7, "its lower part"); sell_img(g.upper, 8, "its upper part"); }
+  }
+  if (!split && !L.A.empty()) {
+    const bool plain_sell = L.A.fmt == FMT_SELL && !L.A.sell.win;
+    DevBuf<double>* av = L.A.fmt == FMT_SELL ? &L.A.sell.val : (L.A.fmt == FMT_CSRVEC && L.A.br == 1 ? &L.A.val : nullptr);
+    if (av && av->n > 0) imgs.push_back({av, plain_sell ? &L.A.val32 : nullptr, &L.A.val64r, 0, "A", true});
+  }
+  auto beyond = [&](int64_t bad, const char* what) {
+    return Err("amgx_create: level " + std::to_string(B.l) + ": " + std::to_string(bad) + " value(s) of " + what +
+               " are beyond the range of single precision (mat_prec = AMGX_PREC_F32_SCALAR_GS)");
+  };
+  auto undo = [&] {
+    for (const Img& im : imgs) { if (im.v32) im.v32->release(); if (im.v64r) im.v64r->release(); }
+    L.sgs32 = L.sgs32_wide = false; L.sgs_mask = 0; L.sgs_bytes = L.sgs_released = 0;
+  };
+  // pass 1: the float arrays; an image that gets none (the twin; a format without a float kernel) drops its array again: a dry run
+  for (const Img& im : imgs) {
+    DevBuf<float> probe;
+    DevBuf<float>& dst = im.v32 ? *im.v32 : probe;
+    const int64_t bad = dev_round_to_f32(*im.val, dst);
+    if (bad) { undo(); throw beyond(bad, im.what); }
+    if (wide) dst.release();
+  }
+  // pass 2: nothing can fail for range any more
+  for (const Img& im : imgs) {
+    const int64_t n = (int64_t)im.val->n;
+    const bool f32 = !wide && im.v32;
+    if (im.keep64) { if (!f32) dev_round_to_f32_wide(*im.val, *im.v64r); }          // A: the true values stay
+    else if (!f32) dev_round_to_f32_wide(*im.val, *im.val);                          // the twin, or `rest` in CSR-vector form: in place
+    else { im.val->release(); L.sgs_released += 8 * n; }
+    L.sgs_mask |= 1 << im.bit;
+    L.sgs_bytes += (f32 ? 4 : 8) * n;
+  }
+  if (L.sgs_mask) (wide ? L.sgs32_wide : L.sgs32) = true;
 }
 
 // workgroup -> rows mapping of the streaming kernels on this level (SellMat::xcd)

@@ -362,8 +362,8 @@ template <int K = SELL_BATCH, class V = double>
 __device__ __forceinline__ double sell_row_dot(const SellMatT<V>& M, int s, int lane, int row, const double* x, double* xd) {
   return sell_row_dot_sp<K>(M, M.slice_ptr[s], M.slice_ptr[s + 1], lane, row, x, xd);
 }
-template <int K = SELL_BATCH>
-__device__ __forceinline__ double sell_row_dot(const SellMat& M, int s, int lane, int row, const double* x) {
+template <int K = SELL_BATCH, class V = double>
+__device__ __forceinline__ double sell_row_dot(const SellMatT<V>& M, int s, int lane, int row, const double* x) {
   double xd[2];
   return sell_row_dot<K>(M, s, lane, row, x, xd);
 }
@@ -414,8 +414,9 @@ __global__ __launch_bounds__(BLOCK) void sell_spmv_kernel(int64_t n_rows, int sl
 #define SELL_WIN_SIZE 512      // A/B (profiles/r01/unroll_ab.txt): 256 is 2 % slower, 1024 ties
 #endif
 constexpr int SELL_WIN = SELL_WIN_SIZE;
-template <int WB, int EP>
-__global__ __launch_bounds__(WB) void sell_win_spmv_kernel(int64_t n_rows, int win0, SellMat M, const uint16_t* __restrict__ rowloc,
+// V = float: the single-precision image of a windowed `rest` of a scalar Gauss-Seidel level (instantiated under EP_CRES)
+template <int WB, int EP, class V = double>
+__global__ __launch_bounds__(WB) void sell_win_spmv_kernel(int64_t n_rows, int win0, SellMatT<V> M, const uint16_t* __restrict__ rowloc,
                                                            const double* __restrict__ x, double* y, EpArgs ep) {
   __shared__ double buf[WB];
   const int lane = threadIdx.x & (WAVE - 1);
@@ -813,8 +814,9 @@ __global__ __launch_bounds__(BLOCK) void bcsr_rowlane_kernel(int64_t n_rows, con
 // multicolour Gauss-Seidel, scalar: one colour per launch, colour-major SELL copy of A.
 //   x_k += dinv_k * (b_k - A_k: x)        (RHS form, reference gssmoother.cpp:209-212)
 // Rows of one colour have no mutual couplings, so the in-place update is race-free.
-template <int G>
-__global__ __launch_bounds__(BLOCK) void gs_color_kernel(int slice_begin, int slice_end, SellMat M,
+// V = float: the single-precision colour-major copy (`sell`, `lower`) of a level with mat_prec = AMGX_PREC_F32_SCALAR_GS
+template <int G, class V = double>
+__global__ __launch_bounds__(BLOCK) void gs_color_kernel(int slice_begin, int slice_end, SellMatT<V> M,
                                                          const int32_t* __restrict__ rowid,
                                                          const double* __restrict__ dinv,
                                                          const double* __restrict__ b, double* x) {
@@ -869,10 +871,14 @@ constexpr int GSB_LW_CAP = 3072;             // off-block columns per block the 
 
 // WP = pair-steps a lane holds (2 * WP + 1 entries): GSB_WP in general; the sweep from zero reads the short `lowin` rows and
 // is instantiated with WP = 2 where they fit (fewer registers: more resident workgroups to hide each other's colour phases)
-template <int TH, int G, bool FROM_ZERO, int WP = GSB_WP, bool LW = false>
+// V = float: the single-precision images `full` / `fullLW` / `lowin`.  The lane keeps its entries as V -- a pair is
+// ONE 8-byte load, the odd trailing entry a 4-byte one -- and widens a value where it multiplies; index decode, gathers, LDS contents
+// (xs, bs, ds, xw), accumulators, shuffles and the order of the additions are those of V = double.
+template <int TH, int G, bool FROM_ZERO, int WP = GSB_WP, bool LW = false, class V = double>
 // (second launch-bounds argument = waves per SIMD the register budget must allow: the mid-width general sweep asks for two 1024-lane
-//  or three 512-lane workgroups per CU)
-__global__ __launch_bounds__(TH, (TH == 256 ? GSB_MINW : (WP <= 5 && !FROM_ZERO ? (TH == 1024 ? 8 : 6) : 1))) void gsb_sweep_kernel(int64_t n_rows, int block0, SellMat M, GsbArgs a,
+//  or three 512-lane workgroups per CU.  The float form of the mid-width LOCAL-WINDOW sweep at 1024 lanes asks for one: at 64 registers
+//  the fp64 kernel of that shape keeps 84 bytes per lane in scratch memory, and no float kernel is built with scratch)
+__global__ __launch_bounds__(TH, (TH == 256 ? GSB_MINW : (WP <= 5 && !FROM_ZERO ? (TH == 1024 ? (LW && sizeof(V) == 4 ? 4 : 8) : 6) : 1))) void gsb_sweep_kernel(int64_t n_rows, int block0, SellMatT<V> M, GsbArgs a,
                                                         const double* __restrict__ xin, double* xout) {
   constexpr int B = TH / G;                  // rows per block
   constexpr int RPS = WAVE / G;              // rows per slice
@@ -908,17 +914,16 @@ __global__ __launch_bounds__(TH, (TH == 256 ? GSB_MINW : (WP <= 5 && !FROM_ZERO 
   const int w = (int)(((M.slice_ptr[s + 1] & ~(int64_t)63) - base) >> 6);
   const int np = w >> 1;
   const bool c16 = sp0 & 1;
-  const double* __restrict__ vb = M.val + base;
+  const V* __restrict__ vb = M.val + base;
   const int32_t* __restrict__ cb = M.cbase + (base >> 6);
-  double v[2 * WP + 1];
+  V v[2 * WP + 1];
   int cl[2 * WP + 1];
   uint32_t ra[WP], rb[WP];           // raw index words: 16-bit form = one packed pair in ra; 32-bit form = ra, rb
 #pragma unroll
   for (int p = 0; p < WP; ++p) {
-    v[2 * p] = 0.0; v[2 * p + 1] = 0.0; ra[p] = 0; rb[p] = 0;
+    v[2 * p] = 0; v[2 * p + 1] = 0; ra[p] = 0; rb[p] = 0;
     if (p < np) {                                            // wave-uniform
-      v[2 * p] = ld_nt(vb + (p * WAVE + lane) * 2);
-      v[2 * p + 1] = ld_nt(vb + (p * WAVE + lane) * 2 + 1);
+      ld_nt_pair(vb + (p * WAVE + lane) * 2, v[2 * p], v[2 * p + 1]);
       if (c16) ra[p] = ld_nt(reinterpret_cast<const uint32_t*>(M.col16 + base) + p * WAVE + lane);
       else {
         ra[p] = (uint32_t)ld_nt(M.col32 + base + (p * WAVE + lane) * 2);
@@ -934,7 +939,7 @@ __global__ __launch_bounds__(TH, (TH == 256 ? GSB_MINW : (WP <= 5 && !FROM_ZERO 
     for (int j = 0; j < 2 * WP + 1; ++j) cbv[j] = cb[j];
   }
   uint32_t rt = 0;
-  v[2 * WP] = 0.0;
+  v[2 * WP] = 0;
   if (w & 1) {
     const int64_t o = (int64_t)(w - 1) * WAVE + lane;
     v[2 * WP] = ld_nt(vb + o);
@@ -992,8 +997,8 @@ __global__ __launch_bounds__(TH, (TH == 256 ? GSB_MINW : (WP <= 5 && !FROM_ZERO 
 #pragma unroll
   for (int j = 0; j < 2 * WP + 1; ++j) {
     const bool inb = cl[j] >= 0;
-    if (!FROM_ZERO) acc_off += inb ? 0.0 : v[j] * xg[j];
-    if (!inb) { v[j] = 0.0; cl[j] = 0; }
+    if (!FROM_ZERO) acc_off += inb ? 0.0 : (double)v[j] * xg[j];
+    if (!inb) { v[j] = 0; cl[j] = 0; }
   }
 #pragma unroll
   for (int o = G >> 1; o > 0; o >>= 1) acc_off += __shfl_xor(acc_off, o, G);
@@ -1006,7 +1011,7 @@ __global__ __launch_bounds__(TH, (TH == 256 ? GSB_MINW : (WP <= 5 && !FROM_ZERO 
     if (__any(mycol == c)) {                                 // slices hold one or two colours (slots are colour-sorted)
       double acc = 0.0;
 #pragma unroll
-      for (int j = 0; j < 2 * WP + 1; ++j) acc += v[j] * xs[cl[j]];
+      for (int j = 0; j < 2 * WP + 1; ++j) acc += (double)v[j] * xs[cl[j]];
 #pragma unroll
       for (int o = G >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, G);
       if (writer && mycol == c) xs[own] = xs[own] + dv * (bv - acc_off - acc);
@@ -1019,8 +1024,8 @@ __global__ __launch_bounds__(TH, (TH == 256 ? GSB_MINW : (WP <= 5 && !FROM_ZERO 
 // r = -(U x) on the colour-major rows: the residual right after a forward sweep from x = 0, where
 // (b - L x - D x)_k = 0 holds for every swept row (see Handle::pre_smooth), so only the entries coupling to HIGHER
 // colours are needed.  One launch over all colours (no ordering required).
-template <int G>
-__global__ __launch_bounds__(BLOCK) void gs_upper_residual_kernel(int n_slices, SellMat M, const int32_t* __restrict__ rowid,
+template <int G, class V = double>
+__global__ __launch_bounds__(BLOCK) void gs_upper_residual_kernel(int n_slices, SellMatT<V> M, const int32_t* __restrict__ rowid,
                                                                   const double* __restrict__ x, double* __restrict__ r) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int s = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6));
@@ -1441,7 +1446,8 @@ __device__ __forceinline__ void jacobi_down_store(double bi, double di, double r
 // EPT: 4: prolongations with <= 3 entries per row; 6: the up to 5 of the reference's "classic" rows
 // G = lanes per row (SELL-G image, long rows of the coarser levels): the chunk then holds FUSED_BLOCK / G rows, the G partial
 // row sums are combined by a wave shuffle and the first lane of every group runs the epilogue
-// V = float (MODE 2: A of a Chebyshev level; MODE 0: A' of a scalar Jacobi level): the single-precision image
+// V = float (MODE 2: A of a Chebyshev level; MODE 0: A' of a scalar Jacobi level; MODE 1: `rest` of a scalar
+// Gauss-Seidel level): the single-precision image
 // (This kernel and sell_lw_pre_restrict_kernel take the six pointers of RestrictMat one by one: with the struct as a kernel argument
 // the compiler holds more of them in scalar registers across the row product -- 2 to 6 SGPRs more here, one fewer there.)
 template <int FUSED_BLOCK, int MODE = 0, int EPT = 4, int G = 1, class V = double>
@@ -1748,8 +1754,9 @@ __global__ __launch_bounds__(512, 4) void dia_box_pre_restrict_kernel(int n_rows
 // natural order, which on these levels is 1 % of the matrix stream.
 // MODE 1: the residual after a block-hybrid Gauss-Seidel sweep from zero, r = c .* x - A_rest x (b = the swept x, dinv = c, win0 = 0,
 // nothing written to x): A_rest has ragged rows (each row lost its in-block lower-colour couplings), plain slices pad ~27 %.
-template <int WB, int EPT = 4, int MODE = 0>
-__global__ __launch_bounds__(WB) void sell_win_pre_restrict_kernel(int64_t n_rows, int win0, SellMat M, const uint16_t* __restrict__ rowloc,
+// V = float (MODE 1 is instantiated): the single-precision image of a windowed `rest`.
+template <int WB, int EPT = 4, int MODE = 0, class V = double>
+__global__ __launch_bounds__(WB) void sell_win_pre_restrict_kernel(int64_t n_rows, int win0, SellMatT<V> M, const uint16_t* __restrict__ rowloc,
                                                                    const double* __restrict__ b, const double* __restrict__ dinv, double omega, int nt,
                                                                    double* __restrict__ x, RestrictMat R) {
   __shared__ double buf[WB];
@@ -1794,7 +1801,7 @@ constexpr int LW_CAP = 4608;                 // distinct columns per chunk the L
 // MODE 0: Jacobi pre-smoothing from zero as described above (b = right-hand side, dinv, x receives omega*Dinv*b [+ fold]).
 // MODE 1: residual after a block-hybrid Gauss-Seidel sweep from zero, r = c .* x - A_rest x (b = the swept x, dinv = c; nothing is
 //         written to x) -- sell_win_pre_restrict_kernel<.., 1>'s job on a local-window image of A_rest.
-// V = float (MODE 0 is instantiated): the single-precision local-window image of A' (DESIGN.md 5.20).
+// V = float: the single-precision local-window image of A' (MODE 0) or of `rest` (MODE 1).
 template <int EPT = 4, int G = 2, int MODE = 0, class V = double>
 __global__ __launch_bounds__(512, (EPT <= 2 ? 6 : 4)) void sell_lw_pre_restrict_kernel(int64_t n_rows, int chunk0, int n_slices, SellMatT<V> M,
                                                                    const int32_t* __restrict__ lw_cptr, const int32_t* __restrict__ lw_ccol,

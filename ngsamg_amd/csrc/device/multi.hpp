@@ -93,7 +93,7 @@ struct Multi {
     const DevLevel& V = h.lev[l];
     MultiLevelFacts f;
     f.bs = V.bs; f.empty = V.n == 0; f.square = V.n == V.ncols; f.permuted = h.permuted(l);
-    f.jacobi_f32 = V.jp32 || V.jp32_wide; f.gs_f32 = V.gs32 || V.gs32_wide;
+    f.jacobi_f32 = V.jp32 || V.jp32_wide; f.gs_f32 = V.gs32 || V.gs32_wide; f.sgs_f32 = V.sgs32 || V.sgs32_wide;
     f.smoothed = l + 1 < h.n_levels(); f.sm_type = V.sm_type; f.plain = h.plain(V); f.cheb_degree = V.cheb_degree;
     f.a_scalar = Handle::multi_scalar_ok(V.A); f.a_level = Handle::multi_level_ok(V.A) && V.A.br == V.bs;
     f.t_scalar = Handle::multi_scalar_ok(V.P) && Handle::multi_scalar_ok(V.PT);
@@ -135,6 +135,7 @@ struct Multi {
     const DevLevel& V = h.lev[l];
     if (f.bs != 1) { d.why = "block level"; return d; }
     if (f.jacobi_f32) { d.why = "single-precision Jacobi images"; return d; }     // (the NV kernels read fp64 images)
+    if (f.sgs_f32) { d.why = "single-precision Gauss-Seidel images"; return d; }  // (... and the fp64 values of `rest` are released)
     const DownPlan* p = nullptr;
     if (f.square && !f.permuted && !st.facts[l + 1].permuted && f.plain) {
       if (V.sm_type == AMGX_SM_GS) {

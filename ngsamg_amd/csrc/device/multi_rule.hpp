@@ -30,6 +30,7 @@ struct MultiLevelFacts {
   bool permuted = false;                // stored in another numbering than the caller's
   bool jacobi_f32 = false;              // single-precision Jacobi images; the NV kernels read fp64 images
   bool gs_f32 = false;                  // single-precision Gauss-Seidel images
+  bool sgs_f32 = false;                 // ... of a scalar level (the twin too): the fp64 values of its sweep images are released
   bool smoothed = false;                // not the coarsest level
   int sm_type = AMGX_SM_JACOBI;
   bool plain = true;                    // sm_steps == 1 and no sm_symm
@@ -70,6 +71,7 @@ inline const char* multi_level_reason(int rule, const MultiLevelFacts& f) {
     if (gs && !f.empty) {
       // (the fused sweeps read fp64 images: the column loop keeps a column equal to amgx_apply, bit for bit)
       if (rule >= 3 && f.gs_f32) return "single-precision Gauss-Seidel images";
+      if (f.sgs_f32) return "single-precision Gauss-Seidel images";
       if (!(f.bs == 1 ? f.sweep_ok : f.block_sweep_ok)) return "Gauss-Seidel sweep form without a multi-vector kernel";
       if (f.bs != 1 && !f.block_sweep_fits) return "sweep block too large for the multi-vector sweep";
     }

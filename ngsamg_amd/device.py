@@ -49,17 +49,19 @@ def cheby_args(degree, ratio, lambda_max, i=0, n=1):
     return deg, lam, rat
 
 
-_PREC = {"double": _lib.AMGX_PREC_F64, "single": _lib.AMGX_PREC_F32, "single_gs": _lib.AMGX_PREC_F32}
+_PREC = {"double": _lib.AMGX_PREC_F64, "single": _lib.AMGX_PREC_F32, "single_gs": _lib.AMGX_PREC_F32, "single_gs_all": _lib.AMGX_PREC_F32_SCALAR_GS}
 # the smoother types a value of mat_prec applies to
-_PREC_TYPES = {"single": ("cheby",), "single_gs": ("cheby", "gs", "hgs")}
+_PREC_TYPES = {"single": ("cheby",), "single_gs": ("cheby", "gs", "hgs"), "single_gs_all": ("cheby", "gs", "hgs")}
 
 
 def mat_prec_levels(mat_prec, types):
     """amgx_level_desc.mat_prec of every level for the smoother types `types` (one per level, the last = the coarsest, which
-    ignores the field).  mat_prec: "double", "single", "single_gs" or a per-level list of them.  A scalar "single" applies to the
+    ignores the field).  mat_prec: "double", "single", "single_gs", "single_gs_all" or a per-level list of them.  A scalar "single" applies to the
     Chebyshev levels and needs at least one; a list may say "single" on Chebyshev levels only.  "single_gs"
     applies to the Chebyshev and the Gauss-Seidel ("gs", "hgs") levels in the same way (on a Gauss-Seidel level
-    the images of the block sweeps; a level whose sweep form has none stays fp64)."""
+    the images of the block sweeps; a level whose sweep form has none stays fp64).  "single_gs_all" = "single_gs" + the scalar
+    Gauss-Seidel levels: AMGX_PREC_F32_SCALAR_GS (2) on "gs" / "hgs" levels -- hierarchy_desc turns it into
+    AMGX_PREC_F32 where the level has blocks -- and AMGX_PREC_F32 (1) on "cheby" levels."""
     n = len(types)
     per_level = isinstance(mat_prec, (list, tuple))
     vals = list(mat_prec) if per_level else [mat_prec] * n
@@ -67,23 +69,23 @@ def mat_prec_levels(mat_prec, types):
         raise NgsAMGError("mat_prec list must have one entry per level")
     for v in vals:
         if not isinstance(v, str) or v not in _PREC:
-            raise NgsAMGError(f"unknown mat_prec {v!r} (double | single | single_gs)")
+            raise NgsAMGError(f"unknown mat_prec {v!r} (double | single | single_gs | single_gs_all)")
     out = [0] * n
     for i in (range(n - 1) if n > 1 else range(n)):       # smoothed levels (a single level: a stand-alone smoother)
         if vals[i] == "double":
             continue
         if types[i] in _PREC_TYPES[vals[i]]:
-            out[i] = _lib.AMGX_PREC_F32
+            out[i] = _lib.AMGX_PREC_F32_SCALAR_GS if vals[i] == "single_gs_all" and types[i] in ("gs", "hgs") else _lib.AMGX_PREC_F32
         elif per_level and vals[i] == "single":
             raise NgsAMGError(f"mat_prec 'single' on level {i}: single-precision matrix storage is available on Chebyshev "
                               f"levels only (sm_type '{types[i]}')")
         elif per_level:
-            raise NgsAMGError(f"mat_prec 'single_gs' on level {i}: single-precision matrix storage is available on Chebyshev and "
+            raise NgsAMGError(f"mat_prec '{vals[i]}' on level {i}: single-precision matrix storage is available on Chebyshev and "
                               f"Gauss-Seidel levels only (sm_type '{types[i]}')")
     if not per_level and mat_prec == "single" and not any(out):
         raise NgsAMGError("mat_prec 'single': the hierarchy has no Chebyshev level (sm_type 'cheby') to apply it to")
-    if not per_level and mat_prec == "single_gs" and not any(out):
-        raise NgsAMGError("mat_prec 'single_gs': the hierarchy has no Chebyshev or Gauss-Seidel level (sm_type 'cheby', 'gs', 'hgs') "
+    if not per_level and mat_prec in ("single_gs", "single_gs_all") and not any(out):
+        raise NgsAMGError(f"mat_prec '{mat_prec}': the hierarchy has no Chebyshev or Gauss-Seidel level (sm_type 'cheby', 'gs', 'hgs') "
                           "to apply it to")
     return out
 
@@ -315,7 +317,8 @@ def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False
     cheb_*: levels with sm_type "cheby" (each a scalar or a per-level list); the descriptor carries 0 for a default
     (degree 2, ratio 10) and for a lambda_max that amgx_create estimates on the device.
     mat_prec: "double" (default), "single" (single-precision storage of A for the smoother passes of the Chebyshev levels),
-    "single_gs" (the same, and the images of the block Gauss-Seidel sweeps) or a per-level list; see mat_prec_levels.
+    "single_gs" (the same, and the images of the block Gauss-Seidel sweeps), "single_gs_all" (the same, and the images of the
+    scalar Gauss-Seidel sweeps) or a per-level list; see mat_prec_levels.
     jacobi_prec: "double" (default), "single" (single-precision images of A, A', Q and the diagonal image for the passes of the
     scalar Jacobi levels), "single_wide" (its A/B twin) or a per-level list; see jacobi_prec_levels."""
     levels = hierarchy.levels
@@ -344,8 +347,12 @@ def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False
             d.cheb_degree = deg
             d.cheb_lambda_max = lam
             d.cheb_ratio = 0.0 if rat == 10.0 else rat
-        # (a scalar Gauss-Seidel level has no sweep form with single-precision images: "single_gs" leaves it fp64)
-        d.mat_prec = 0 if types[i] in ("gs", "hgs") and lv.A.br == 1 else prec[i]
+        # ("single_gs" leaves a scalar Gauss-Seidel level fp64; "single_gs_all" asks for its images, 5.21, and is
+        #  "single_gs" on a block level)
+        if types[i] in ("gs", "hgs") and lv.A.br == 1:
+            d.mat_prec = prec[i] if prec[i] == _lib.AMGX_PREC_F32_SCALAR_GS else 0
+        else:
+            d.mat_prec = _lib.AMGX_PREC_F32 if prec[i] == _lib.AMGX_PREC_F32_SCALAR_GS else prec[i]
         d.jacobi_prec = jprec[i]
         d.omega = float(omega)
         d.sm_steps = int(sm_steps[i] if isinstance(sm_steps, (list, tuple)) else sm_steps)      # per level: ..._spec flags
@@ -819,6 +826,20 @@ class DeviceAMGMatrix:
         d = dict(zip(self._JPREC_KEYS, (int(v) for v in out)))
         d["mask"] = d["images"]
         d["images"] = tuple(n for b, n in enumerate(self._JPREC_IMAGES) if d["mask"] >> b & 1)
+        return d
+
+    _GSPREC_IMAGES = ("A", "full", "fullLW", "lowin", "rest", "restLW", "sell", "lower", "upper")
+
+    def gs_prec_info(self, level):
+        """what mat_prec "single_gs_all" gave a scalar Gauss-Seidel level (amgx_gs_prec_info): whether its sweeps read
+        float images ("f32"; 0 under AMGX_GS_F32_WIDE), the tuple of the images converted ("images": of A, full, fullLW, lowin, rest,
+        restLW, sell, lower, upper; "mask": the bits), the value bytes of the converted arrays, the fp64 value bytes released, and
+        whether the level is the twin ("wide")"""
+        out = np.zeros(_lib.AMGX_GS_PREC_INFO_N, dtype=np.int64)
+        self._ck(self._lib.amgx_gs_prec_info(self._h, int(level), out.ctypes.data_as(_lib.c_i64p), out.size))
+        d = dict(zip(self._JPREC_KEYS, (int(v) for v in out)))
+        d["mask"] = d["images"]
+        d["images"] = tuple(n for b, n in enumerate(self._GSPREC_IMAGES) if d["mask"] >> b & 1)
         return d
 
     _SM_NAMES = {_lib.AMGX_SM_JACOBI: "jacobi", _lib.AMGX_SM_GS: "gs", _lib.AMGX_SM_BGS: "bgs", _lib.AMGX_SM_CHEBY: "cheby"}

@@ -860,6 +860,10 @@ class DistributedAMG:
             raise NgsAMGError("DistributedAMG: sm_type must be jacobi, gs (multicolour stages), hgs (block-hybrid Gauss-Seidel), bgs or cheby")
         if opts.get("jacobi_prec", "double") != "double":
             raise NgsAMGError("DistributedAMG: jacobi_prec (single-precision Jacobi images) is not available on rank-partitioned hierarchies")
+        mp = opts.get("mat_prec", "double")
+        if any(isinstance(v, str) and v.lower() == "single_gs_all" for v in (mp if isinstance(mp, (list, tuple)) else [mp])):
+            raise NgsAMGError("DistributedAMG: mat_prec 'single_gs_all' (single-precision images of scalar Gauss-Seidel levels) is not "
+                              "available on rank-partitioned hierarchies")
         # (an opt-in in two words: the type and its degree.  The degree has no default here: it fixes the 2 x degree halo exchanges per
         #  level and application, and a call that names the type alone is refused as it was before the option existed)
         if sm_type == "cheby" and cheb_degree is None:
