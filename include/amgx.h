@@ -77,10 +77,15 @@ enum {
   AMGX_MULTI_FUSE_DOWN = 512, /* the multi-vector calls: a fused column group runs the down pass of every level that qualifies  */
                               /* as the single-vector fused down kernel on interleaved vectors (see "multi-vectors" below); it   */
                               /* implies nothing and never causes an error.  Without it every call is as before                  */
-  AMGX_MULTI_FUSE_DOWN_DIA = 1024 /* accepted wherever AMGX_MULTI_FUSE_DOWN is; implies it (and nothing else) and admits levels  */
+  AMGX_MULTI_FUSE_DOWN_DIA = 1024,/* accepted wherever AMGX_MULTI_FUSE_DOWN is; implies it (and nothing else) and admits levels  */
                               /* whose fused down launch reads the symmetric diagonal image, 512-row or box chunks (see below);   */
                               /* never an error.  Without it every call is as before, calls that carry AMGX_MULTI_FUSE_DOWN      */
                               /* included                                                                                        */
+  AMGX_MULTI_FUSE_F32 = 2048  /* accepted wherever AMGX_MULTI_FUSE_GS is; implies nothing and is never an error.  With it a      */
+                              /* Gauss-Seidel level whose sweeps read single-precision images no longer keeps the handle in the   */
+                              /* column loop under AMGX_MULTI_FUSE_GS (scalar levels) / AMGX_MULTI_FUSE_GS_BLOCK (2x2 / 3x3 / 6x6    */
+                              /* levels), where the multi-vector kernels exist on the float arrays (see below).  Without it     */
+                              /* every call is as before                                                                         */
 };
 
 typedef struct amgx_level_desc {
@@ -543,6 +548,31 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  * note "local-window image".  Under AMGX_MULTI_FUSE_DOWN alone "diagonal image" remains the note of such a level and the fold rule is
  * the one above; the column loop and k = 1 ignore the flag like its neighbours.  A column of amgx_down_multi is the same with and
  * without it, bit for bit.
+ * With AMGX_MULTI_FUSE_F32 = 2048 (opt-in per call; it implies nothing, is never an error and is looked at wherever
+ * AMGX_MULTI_FUSE_GS is: amgx_apply_multi, amgx_pcg_multi, amgx_smooth_multi, amgx_multi_plan / amgx_multi_note, amgx_down_multi,
+ * amgx_multi_level_plan / amgx_multi_level_note) a Gauss-Seidel level with single-precision images is admitted by the rule of
+ * AMGX_MULTI_FUSE_GS (scalar levels, mat_prec = AMGX_PREC_F32_SCALAR_GS) or AMGX_MULTI_FUSE_GS_BLOCK (2x2 / 3x3 / 6x6 levels, mat_prec =
+ * AMGX_PREC_F32), which must be carried too.  The AMGX_GS_F32_WIDE twins are admitted by the same flag and run the fp64
+ * multi-vector kernels on their rounded values.  What a fused group of such a handle runs, stated once:
+ *   fused on 2 or 4 columns, reading the float arrays the single-vector passes read with their order of additions per column
+ *   (a column of amgx_smooth_multi equals amgx_smooth bit for bit): every Gauss-Seidel sweep, the sweep from zero included; the
+ *   residual after the sweep from zero where it is a product of its own on a sliced-ELL or BSELL image (`rest`, `upper` / `bupper`,
+ *   or A of a level without the split images); the transfers of scalar levels.
+ *   per column through the single-vector kernels, because the single-vector cycle is not the literal cycle there: the levels of the
+ *   single-workgroup coarse tail (which reads true fp64 copies of A); the residual that is fused with the chunk-local restriction
+ *   after a block-hybrid sweep from zero on a scalar level; on 2x2 / 3x3 / 6x6 levels the transfers P^T and P, the coarsest solve, and
+ *   the residual of a level without the split images whose A is block CSR (block-CSR products on one and on 2 / 4 vectors add in
+ *   different orders).
+ * So a column of amgx_apply_multi equals amgx_apply bit for bit, up to the dense product of a collapsed coarse tail.
+ * A level qualifies if every image its fused passes read has a multi-vector kernel on the array the single-vector pass reads: float
+ * arrays of the sliced-ELL / BSELL sweep images, of `rest` (plain or windowed sliced-ELL, BSELL) and of A (plain sliced-ELL, BSELL)
+ * on a level without the split images; an image in a format without a float kernel (CSR-vector `rest`, windowed or CSR A) keeps its
+ * rounded values at fp64 width, which both paths read.  A level that does not qualify keeps the note "single-precision Gauss-Seidel
+ * images (level l)"; so does every such level without the flag.  "single-precision Jacobi images" stays a refusal under every flag,
+ * and on a handle without such Gauss-Seidel levels the flag changes nothing.  The two _DOWN bits still keep the literal stages on
+ * such a level (amgx_multi_level_note: "single-precision Gauss-Seidel images"); amgx_down_multi with x_given = 0 under
+ * AMGX_MULTI_FUSE_DOWN | AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_F32 runs the multi-vector float sweep from zero on groups of 4 and 2
+ * columns and then the single-vector residual and restriction per column.
  *   amgx_down_multi  : the down stage of a level per column; layout and pointers as in amgx_matvec_multi; B and X have the level's
  *                      size, BC the coarse level's.  The level must be scalar and smoothed, without ghost columns and not
  *                      renumbered.  x_given = 0: X is output -- pre-smoothing from zero, then b_c = P^T (b - A x), the down stage of

@@ -251,7 +251,8 @@ class AMGMatrix:
         with apply_block(mv_in, mv_out) (None: the identity); free: 0/1 mask of the scalar dofs (None: the free dofs of the
         hierarchy); X0: a (num, n) array or CUDA tensor (None: random columns from seed).  Returns (lams, X, info), X a
         DeviceMultiVector (X.data: the (num, n) tensor).  fuse: as in MultMulti; "gs_block" fuses the default Gauss-Seidel smoother
-        of an elasticity hierarchy (AMGX_MULTI_FUSE_GS_BLOCK); "down" / "gs+down" / "gs_block+down" add AMGX_MULTI_FUSE_DOWN."""
+        of an elasticity hierarchy (AMGX_MULTI_FUSE_GS_BLOCK); "down" / "gs+down" / "gs_block+down" add AMGX_MULTI_FUSE_DOWN;
+        "gs+f32" / "gs_block+f32" fuse a Gauss-Seidel hierarchy created with single-precision images (AMGX_MULTI_FUSE_F32)."""
         import torch
         from .eigen import lobpcg
         from .multivector import DeviceMultiVector, MatVecMulti, MultMulti

@@ -1592,10 +1592,11 @@ struct Handle {
     // (r = rest x of a Gauss-Seidel block level)
     // for SELL, on one vector, also under the epilogues of a scalar Jacobi level's passes (EP_PRE on A', EP_JAC on A, EP_AXPY on Q; 5.20)
     constexpr bool EP32 = EP == EP_RES || EP == EP_CHEB;
-    // ... and under EP_CRES on `rest` of a scalar Gauss-Seidel level (plain and windowed sliced-ELL; 5.21)
-    constexpr bool EP32_SELL = EP32 || (NV == 1 && (EP == EP_PRE || EP == EP_JAC || EP == EP_AXPY || EP == EP_CRES));
-    constexpr bool EP32_WIN = NV == 1 && EP == EP_CRES;
-    constexpr bool EP32_BSELL = EP32 || (EP == EP_MULT && NV == 1);
+    // ... and under EP_CRES on `rest` of a scalar Gauss-Seidel level (plain and windowed sliced-ELL; 5.21).  EP_CRES and the EP_MULT of
+    // BSELL are built on NV > 1 too: the residual after the fused sweep from zero on float images (5.22)
+    constexpr bool EP32_SELL = EP32 || EP == EP_CRES || (NV == 1 && (EP == EP_PRE || EP == EP_JAC || EP == EP_AXPY));
+    constexpr bool EP32_WIN = EP == EP_CRES;
+    constexpr bool EP32_BSELL = EP32 || EP == EP_MULT;
     const bool f32 = sm_pass && M.has32() && (EP32 || (EP32_SELL && M.fmt == FMT_SELL) || (EP32_BSELL && M.fmt == FMT_BSELL));
     if (f32 && !((M.fmt == FMT_SELL && (!M.sell.win || EP32_WIN)) || M.fmt == FMT_BSELL)) throw Err("single-precision image on a format that has none");
     // run(view of the image this product reads); has32: a float kernel is instantiated for this format and epilogue
@@ -1631,7 +1632,7 @@ struct Handle {
       image(std::bool_constant<EP32_WIN>{}, sm_pass && M.val64r.p ? M.sell.view_of(M.val64r.p) : M.sell.view(), M.sell.view32(M.val32.p), [&](auto V) {
         using T = std::remove_const_t<std::remove_pointer_t<decltype(V.val)>>;       // double / float
         if constexpr (NV == 1) launch(sell_win_spmv_kernel<SELL_WIN, EP, T>, (int)(b - a), SELL_WIN, 0, stream, M.n_rows, (int)a, V, M.sell.rowloc.p, x, y, ep);
-        else launch(sell_win_spmm_kernel<SELL_WIN, NV, EP>, (int)(b - a), SELL_WIN, 0, stream, M.n_rows, V, M.sell.rowloc.p, x, y, ep);
+        else launch(sell_win_spmm_kernel<SELL_WIN, NV, EP, T>, (int)(b - a), SELL_WIN, 0, stream, M.n_rows, V, M.sell.rowloc.p, x, y, ep);
       });
     } else if (M.fmt == FMT_SELL) {
       unit_range(sp, WAVE / M.lanes, M.n_slices, a, b);
@@ -1792,8 +1793,10 @@ struct Handle {
   // AMGX_MULTI_FUSE_GS and AMGX_MULTI_FUSE_GS_BLOCK).  Colour order, grids, lane and size lists and the checks
   // on the iterate are written once; what the widths do not share is stated once too, as a fact about NV:
   //   units        NV > 1 sweeps whole levels (gs_units), as product<NV > 1> takes no Span
-  //   images       NV > 1 reads fp64 images in the plain view; one vector the single-precision images of a level that has them and the
-  //                view of knobs.bsell_xmode (gs_prec, gs_view; scalar levels: sgs_image).  No NV kernel is built on float.
+  //   images       every width reads the single-precision images of a level that has them (gs_prec, gs_view; scalar levels: sgs_image):
+  //                the six NV sweep kernels are built on float too.  NV > 1 reaches such a level only where the call
+  //                carries AMGX_MULTI_FUSE_F32 and multi_f32_ok holds.  NV > 1 reads BSELL images in the plain view, one vector in the
+  //                view of knobs.bsell_xmode
   //   block size   a size the BSELL kernels are not listed for takes the 2 x 2 kernel on one vector and an fp64 image, and is an error
   //                on NV > 1 and on float images (gs_bsell_size)
   //   hybrid form  the local-window image and the mid-width kernel of gsb_sweep are built for one vector (GSB_FORMS there)
@@ -1816,7 +1819,7 @@ struct Handle {
   // Nothing else is decided at launch time.
   template <int NV, class F>
   static void gs_prec(const DevLevel& L, F&& run) {
-    if constexpr (NV == 1) { if (L.gs32) { run(float{}); return; } }
+    if (L.gs32) { run(float{}); return; }
     run(double{});
   }
   template <int NV, class T>
@@ -1827,17 +1830,15 @@ struct Handle {
       return M.bsell.view32(M.val32.p, xmode);
     } else return M.bsell.view(xmode);
   }
-  // The sliced-ELL images that the sweeps of a SCALAR Gauss-Seidel level read: run(view) gets the float view on one vector of a level
-  // with single-precision images (DevLevel::sgs32), otherwise the fp64 one.  An fp64 view of released values is an
-  // error here, never a null pointer in a kernel (the NV kernels read fp64 images: such a level keeps the column loop).
+  // The sliced-ELL images that the sweeps of a SCALAR Gauss-Seidel level read: run(view) gets the float view on a level with
+  // single-precision images (DevLevel::sgs32; NV > 1: 5.22), otherwise the fp64 one.  An fp64 view of released values
+  // is an error here, never a null pointer in a kernel.
   template <int NV, class F>
   static void sgs_image(const DevLevel& L, const DevMatrix::Sell& S, F&& run) {
-    if constexpr (NV == 1) {
-      if (L.sgs32) {
-        if (!S.val32.p && S.val.p) throw Err("single-precision Gauss-Seidel images: a sweep image has no float twin");
-        run(S.view32());
-        return;
-      }
+    if (L.sgs32) {
+      if (!S.val32.p && S.val.p) throw Err("single-precision Gauss-Seidel images: a sweep image has no float twin");
+      run(S.view32());
+      return;
     }
     if (!S.val.p && S.val32.p) throw Err("Gauss-Seidel sweep: the fp64 values of this image were released (single-precision Gauss-Seidel images); only the single-vector passes of the level read it");
     run(S.view());
@@ -1872,7 +1873,7 @@ struct Handle {
           using V = std::remove_const_t<std::remove_pointer_t<decltype(M.val)>>;       // double / float
           gs_lanes(g.lanes, [&](auto GG) {
             if constexpr (NV == 1) launch(gs_color_kernel<GG(), V>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, M, g.rowid.p, L.dinv.p, b, x);
-            else launch(gs_color_nv_kernel<GG(), NV>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, M, g.rowid.p, L.dinv.p, b, x);
+            else launch(gs_color_nv_kernel<GG(), NV, V>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, M, g.rowid.p, L.dinv.p, b, x);
           });
         });
       } else if (g.bsell_ok) {
@@ -1884,7 +1885,7 @@ struct Handle {
           const BSellMatT<T> BM = gs_view<NV, T>(CM);
           gs_bsell_size<NV, T>(L.bs, [&](auto BS) {
             if constexpr (NV == 1) launch(bgs_bsell_color_kernel<BS(), T>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x);
-            else launch(bgs_bsell_color_nv_kernel<BS(), NV>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x);
+            else launch(bgs_bsell_color_nv_kernel<BS(), NV, T>, wave_grid(s1 - s0), BLOCK, 0, stream, s0, s1, BM, g.rowid.p, L.dinv.p, b, x);
           });
         });
       } else {
@@ -1917,7 +1918,7 @@ struct Handle {
         using V = std::remove_const_t<std::remove_pointer_t<decltype(M.val)>>;         // double / float
         gs_lanes(g.lanes, [&](auto GG) {
           if constexpr (NV == 1) launch(gs_upper_residual_kernel<GG(), V>, wave_grid(ns), BLOCK, 0, stream, ns, M, g.rowid.p, x, r);
-          else launch(gs_upper_residual_nv_kernel<GG(), NV>, wave_grid(ns), BLOCK, 0, stream, ns, M, g.rowid.p, x, r);
+          else launch(gs_upper_residual_nv_kernel<GG(), NV, V>, wave_grid(ns), BLOCK, 0, stream, ns, M, g.rowid.p, x, r);
         });
       });
       return;
@@ -1927,7 +1928,7 @@ struct Handle {
       const BSellMatT<T> UM = gs_view<NV, T>(g.bupper);
       gs_bsell_size<NV, T>(L.bs, [&](auto BS) {
         if constexpr (NV == 1) launch(bgs_bsell_upper_residual_kernel<BS(), T>, wave_grid(ns), BLOCK, 0, stream, ns, UM, g.rowid.p, x, r);
-        else launch(bgs_bsell_upper_residual_nv_kernel<BS(), NV>, wave_grid(ns), BLOCK, 0, stream, ns, UM, g.rowid.p, x, r);
+        else launch(bgs_bsell_upper_residual_nv_kernel<BS(), NV, T>, wave_grid(ns), BLOCK, 0, stream, ns, UM, g.rowid.p, x, r);
       });
     });
   }
@@ -1960,7 +1961,7 @@ struct Handle {
         gs_lanes(g.G, [&](auto GG) {
           auto sweep = [&](auto ZZ, auto WW, auto LW) {
             if constexpr (NV == 1) launch(gsb_sweep_kernel<TT(), GG(), ZZ(), WW(), LW(), V>, blk1 - blk0, TT(), 0, stream, L.n, blk0, M, a, xin, xout);
-            else launch(gsb_sweep_nv_kernel<TT(), GG(), ZZ(), WW(), NV>, blk1 - blk0, TT(), 0, stream, L.n, M, a, xin, xout);    // (whole level: no first block)
+            else launch(gsb_sweep_nv_kernel<TT(), GG(), ZZ(), WW(), NV, V>, blk1 - blk0, TT(), 0, stream, L.n, M, a, xin, xout);    // (whole level: no first block)
           };
           constexpr std::false_type no{};
           constexpr std::true_type yes{};
@@ -1999,7 +2000,7 @@ struct Handle {
             launch(bgsb_sweep_kernel<BS(), MODE(), T>, nb, BLOCK, lds, stream, g.BB, b0, list, g.blk_ptr.p, g.blk_rows.p, OFF, g.off_ptr.p, IN, OTH,
                    g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, x0, xout);
           else
-            launch(bgsb_sweep_nv_kernel<BS(), MODE(), NV>, nb, BLOCK, lds, stream, g.BB, b0, list, g.blk_ptr.p, g.blk_rows.p, OFF, g.off_ptr.p, IN, OTH,
+            launch(bgsb_sweep_nv_kernel<BS(), MODE(), NV, T>, nb, BLOCK, lds, stream, g.BB, b0, list, g.blk_ptr.p, g.blk_rows.p, OFF, g.off_ptr.p, IN, OTH,
                    g.in_ptr.p, g.in_row.p, g.n_colors, dir, L.dinv.p, b, x0, xout);
         };
         if (!dispatch<2, 3, 6>(L.bs, run)) throw Err("block-hybrid Gauss-Seidel: unsupported block size");
@@ -2033,19 +2034,63 @@ struct Handle {
 
   // ---- which levels have the sweeps on NV = 2, 4 vectors is asked here, next to the launchers, and nowhere else (through
   // Multi::facts: the rule of multi_rule.hpp, amgx_smooth_multi).  Scalar levels (AMGX_MULTI_FUSE_GS):
-  bool multi_sweep_ok(const DevLevel& L) const {
+  // f32: the call carries AMGX_MULTI_FUSE_F32; without it a level with single-precision images has no NV sweep
+  bool multi_sweep_ok(const DevLevel& L, bool f32 = false) const {
     if (L.sm_type != AMGX_SM_GS || L.bs != 1 || L.n != L.ncols || !L.paths.plain) return false;
-    if (L.sgs32 || L.sgs32_wide) return false;         // single-precision images: the NV kernels read fp64 images
+    if ((L.sgs32 || L.sgs32_wide) && !(f32 && multi_f32_ok(L))) return false;       // single-precision images
     return L.paths.sweep == SWEEP_GSB || L.paths.sweep == SWEEP_MC;
   }
   // ... square-block levels (AMGX_MULTI_FUSE_GS_BLOCK; multi_sweep_ok keeps the answer of AMGX_MULTI_FUSE_GS)
-  bool multi_block_sweep_ok(const DevLevel& L) const {
+  bool multi_block_sweep_ok(const DevLevel& L, bool f32 = false) const {
     if (L.sm_type != AMGX_SM_GS || (L.bs != 2 && L.bs != 3 && L.bs != 6) || L.n != L.ncols || !L.paths.plain) return false;
-    if (L.gs32 || L.gs32_wide) return false;           // single-precision images: the NV kernels read fp64 images
+    if ((L.gs32 || L.gs32_wide) && !(f32 && multi_f32_ok(L))) return false;         // single-precision images
     switch (L.paths.sweep) {
       case SWEEP_BGSB: case SWEEP_BGSB_BC: case SWEEP_MC_BSELL: case SWEEP_MC_ROWLIST: return true;
       default: return false;
     }
+  }
+  // The float question (AMGX_MULTI_FUSE_F32): the level has single-precision Gauss-Seidel images (or is their
+  // AMGX_GS_F32_WIDE twin) and every image its fused passes read -- the sweeps, the sweep from zero, the residual after it -- has a kernel
+  // on NV vectors for the array the single-vector pass reads: the float array, on the twin the rounded values at fp64 width.  So a
+  // fused pass reads the values of the single-vector pass, image by image.  Scalar levels: the sweep images are sliced-ELL with a float
+  // array; `rest` is plain or windowed sliced-ELL with a float array, or CSR-vector (a badly padded remainder) with the rounded values
+  // at fp64 width in place; A of a level without the split is plain sliced-ELL with a float array, or keeps the rounded values in
+  // val64r.  Block levels: every sweep image is BSELL with a float array; A is BSELL with one, or block CSR with val64r.  Anything
+  // else -- an image without the array its single-vector pass reads -- does not qualify.
+  bool multi_f32_ok(const DevLevel& L) const {
+    const LevelPaths& P = L.paths;
+    if (L.bs == 1) {
+      if (!(L.sgs32 || L.sgs32_wide) || (P.sweep != SWEEP_GSB && P.sweep != SWEEP_MC)) return false;
+      const bool wide = L.sgs32_wide;
+      auto sell = [&](const DevMatrix::Sell& S) { return S.val.n + S.val32.n == 0 || (wide ? S.val.p != nullptr : S.val32.p != nullptr); };
+      auto a_ok = [&] { return multi_scalar_ok(L.A) && (wide ? L.A.val64r.p != nullptr : (L.A.has32() ? L.A.fmt == FMT_SELL && !L.A.sell.win : L.A.val64r.p != nullptr)); };
+      if (P.sweep == SWEEP_GSB) {
+        const DevGSB& g = L.gsb;
+        if (!sell(g.full)) return false;
+        if (!P.zero_split) return a_ok();
+        if (!sell(g.lowin) || !multi_scalar_ok(g.rest)) return false;
+        if (g.rest.fmt != FMT_SELL) return g.rest.val.p != nullptr && !g.rest.has32();
+        return g.rest.sell.val.n + g.rest.val32.n == 0 || (wide ? g.rest.sell.val.p != nullptr : g.rest.has32());
+      }
+      const DevGS& g = L.gs;
+      if (!sell(g.sell)) return false;
+      if (!P.zero_split) return a_ok();
+      return sell(g.lower) && sell(g.upper);
+    }
+    if (!(L.gs32 || L.gs32_wide) || (P.sweep != SWEEP_BGSB && P.sweep != SWEEP_BGSB_BC && P.sweep != SWEEP_MC_BSELL)) return false;
+    const bool wide = L.gs32_wide;
+    auto img = [&](const DevMatrix& M) { return M.empty() || (M.fmt == FMT_BSELL && (M.bsell.val.n == 0 || wide || M.val32.n == M.bsell.val.n)); };
+    auto a_ok = [&] { return L.A.fmt == FMT_BSELL ? (wide ? L.A.val64r.p != nullptr : L.A.has32()) : L.A.val64r.p != nullptr; };
+    if (P.bgsb()) {
+      const DevBGSB& g = L.bgsb;
+      if (!img(g.off) || !img(g.in) || !img(g.upin)) return false;
+      if (!P.zero_split) return a_ok();
+      return img(g.offlo) && img(g.rest) && split_identity(L, 2);
+    }
+    const DevGS& g = L.gs;
+    if (!img(g.bcopy)) return false;
+    if (!P.zero_split) return a_ok();
+    return img(g.blower) && img(g.bupper);
   }
   // dynamic LDS of bgsb_sweep: x and b' of a sweep block on nv (interleaved) vectors, and its row ids
   static size_t multi_block_sweep_lds(const DevLevel& L, int nv) {
@@ -2122,8 +2167,8 @@ struct Handle {
     gs_sweep<NV>(L, 0, x, b, true, u);
   }
   // r = b - A x right after sweep_from_zero(L, x, b, r), by the identity the level's images allow (x may carry ghost entries)
-  // The products are passes of the smoother on the level.  One vector hoists its epilogue loads where ep_nt says so and reads the
-  // single-precision image of `rest` on a level with such Gauss-Seidel images; NV > 1 passes no epilogue flags and reads fp64.
+  // The products are passes of the smoother on the level: they read the single-precision image of `rest` on a level with such
+  // Gauss-Seidel images, on every width.  One vector hoists its epilogue loads where ep_nt says so; NV > 1 passes no epilogue flags.
   template <int NV = 1>
   void residual_after_zero(const DevLevel& L, const double* x, const double* b, double* r) {
     const int nt = NV == 1 ? ep_nt & EPF_HOIST : 0;
@@ -2132,10 +2177,10 @@ struct Handle {
       case SWEEP_GSB:
         // inside a block only couplings to lower colours contributed; (b - L_in x)_k = x_k / dinv_k on every swept row, hence
         // r = b - A x = (1/dinv - a_kk) .* x - (A - L_in - D) x = c .* x - rest x
-        product<NV, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, nt}, Span(), NV == 1 && L.sgs32);
+        product<NV, EP_CRES>(L.gsb.rest, x, r, EpArgs{x, nullptr, L.gsb.cvec.p, 0.0, nullptr, nt}, Span(), L.sgs32);
         return;
       case SWEEP_BGSB: case SWEEP_BGSB_BC:                                          // r = rest x (see DevBGSB)
-        product<NV, EP_MULT>(L.bgsb.rest, x, r, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}, Span(), NV == 1 && L.gs32);
+        product<NV, EP_MULT>(L.bgsb.rest, x, r, EpArgs{nullptr, nullptr, nullptr, 0.0, nullptr, 0}, Span(), L.gs32);
         return;
       case SWEEP_MC: case SWEEP_MC_BSELL: gs_upper_residual<NV>(L, x, r); return;   // r = -(U x) on the swept rows
       default: throw Err("residual_after_zero: the level's sweep form has no split identity");

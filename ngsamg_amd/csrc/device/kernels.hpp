@@ -562,6 +562,11 @@ using BSellMat = BSellMatT<double>;
 // block step six 8-byte gathers (ten distinct lines each: one per block row of the wave) next to three streaming loads.  Halving the
 // gather instructions (V2) or replacing them by one load + a lane exchange (bsell_block_step_shfl) did NOT pay (BSellMat::xmode 1 / 2,
 // measured neutral / 7-13 % slower, see amgx.hip bsell_xmode): both stay opt-in.
+// The pair sum `acc += v0 x0 + v1 x1` is left to the compiler's contraction here and in every kernel that writes it out (the colour,
+// upper-residual and hybrid-block sweep kernels below, bsell_spmv_kernel): it comes out as acc + fma(v0, x0, v1 * x1).  The NV float
+// kernels (multi_kernels.hpp: bsell_block_step_nv, bsell_spmm_kernel under EP_MULT) spell that fma out, because on widened operands
+// the compiler chose the other product for some columns; a column of theirs equals these kernels bit for bit only while the
+// contraction here stays this one.  tests/test_gpu_multi_f32.py and tests/test_gpu_multi_gs_block.py are the guard.
 template <int BS, bool V2, class V>
 __device__ __forceinline__ void bsell_block_step(const V* __restrict__ vk, const double* __restrict__ xv, int lane, double& acc) {
   if (V2 && (BS % 2) == 0) {

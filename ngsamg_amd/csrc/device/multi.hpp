@@ -34,10 +34,11 @@ struct MultiWork {                      // work vectors of one fused width, kept
 
 struct MultiState {
   // the handle under rule 0 (no flag), 1 (AMGX_MULTI_FUSE), 2 (..._GS: plus scalar Gauss-Seidel levels, 5.15) and
-  // 3 (..._GS_BLOCK: plus Gauss-Seidel on square-block levels, 5.16).  -1: not decided yet; 0: why[r] is the first reason
-  int fused[4] = {-1, -1, -1, -1};
-  std::string why[4];
-  std::vector<MultiLevelFacts> facts;   // what the rules read, per level
+  // 3 (..._GS_BLOCK: plus Gauss-Seidel on square-block levels, 5.16).  -1: not decided yet; 0: why[.][r] is the first reason.
+  // First index: the call carries AMGX_MULTI_FUSE_F32 (5.22), which fills MultiLevelFacts::f32_ok and the two sweep answers in.
+  int fused[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};
+  std::string why[2][4];
+  std::vector<MultiLevelFacts> facts[2]; // what the rules read, per level
   MultiWork work[MULTI_MAX + 1];        // by width (2, 4)
   DevBuf<double> col_in, col_out;       // one contiguous column (single-vector path behind an interleaved argument)
   DevBuf<double> stage_b, stage_x, stage_c;   // host-pointer calls (stage_c: the coarse multi-vector of amgx_down_multi)
@@ -47,7 +48,8 @@ struct MultiState {
   DevBuf<double> kr_sc, kr_partial;
   DevBuf<int32_t> kr_active;
   // b, x, k, layout, ldb, ldx, rule in force (0 .. 3; + 4: fused down passes, AMGX_MULTI_FUSE_DOWN on a handle with a level that takes one;
-  // + 8: AMGX_MULTI_FUSE_DOWN_DIA on a handle where it changes a level's form or fold)
+  // + 8: AMGX_MULTI_FUSE_DOWN_DIA on a handle where it changes a level's form or fold; + 16: AMGX_MULTI_FUSE_F32 on a handle where it
+  // changes the decision)
   using Key = std::tuple<const double*, double*, int, int, int64_t, int64_t, int>;
   GraphCache<Key> graphs;
 };
@@ -73,23 +75,27 @@ struct Multi {
   MultiState& st;
   static constexpr int ALL_FLAGS = MULTI_RULE_FLAGS;                                                   // the flags that widen the rule
   static constexpr int DOWN_FLAGS = AMGX_MULTI_FUSE_DOWN | AMGX_MULTI_FUSE_DOWN_DIA;                   // (the second implies the first, nothing else)
-  static constexpr int CALL_FLAGS = ALL_FLAGS | DOWN_FLAGS;                                           // ... and the ones that imply nothing about the rule
+  static constexpr int CALL_FLAGS = ALL_FLAGS | DOWN_FLAGS | AMGX_MULTI_FUSE_F32;                     // ... and the ones that imply nothing about the rule
+  static constexpr int NOTE_FLAGS = ALL_FLAGS | AMGX_MULTI_FUSE_F32;                                  // what amgx_multi_note looks at
   const int flags;
+  const int fb;                         // the call carries AMGX_MULTI_FUSE_F32: which decision of MultiState is read
   const bool block_flag;                // the call carries AMGX_MULTI_FUSE_GS_BLOCK (which implies the flag below)
   const bool gs_flag;                   // the call carries AMGX_MULTI_FUSE_GS (which implies AMGX_MULTI_FUSE)
   const bool fz;                        // this call runs fused groups
   const bool down_flag;                 // the call carries AMGX_MULTI_FUSE_DOWN: modifies the fused groups, implies nothing
   const bool dia_flag;                  // the call carries AMGX_MULTI_FUSE_DOWN_DIA: implies down_flag; diagonal-image levels take the pass too
   explicit Multi(Handle& hh, int fl = 0)
-      : h(hh), st(state(hh)), flags(fl), block_flag(fl & AMGX_MULTI_FUSE_GS_BLOCK), gs_flag(multi_asked_rule(fl) >= 2),
-        fz(multi_runs_fused(fl, st.fused)), down_flag(fl & DOWN_FLAGS), dia_flag(fl & AMGX_MULTI_FUSE_DOWN_DIA) {
+      : h(hh), st(state(hh)), flags(fl), fb(fl & AMGX_MULTI_FUSE_F32 ? 1 : 0), block_flag(fl & AMGX_MULTI_FUSE_GS_BLOCK), gs_flag(multi_asked_rule(fl) >= 2),
+        fz(multi_runs_fused(fl, st.fused[fb])), down_flag(fl & DOWN_FLAGS), dia_flag(fl & AMGX_MULTI_FUSE_DOWN_DIA) {
     if (down_flag) for (int l = 0; l < h.n_levels(); ++l) dn.push_back(level_down(l, dia_flag));     // once per call
   }
-  int rule() const { return multi_rule_in_force(flags, st.fused); }       // (part of the graph key)
-  const std::string& note() const { return st.why[rule()]; }
+  int rule() const { return multi_rule_in_force(flags, st.fused[fb]); }   // (part of the graph key)
+  const std::string& note() const { return st.why[fb][rule()]; }
+  // AMGX_MULTI_FUSE_F32 changes what this call runs (part of the graph key on such handles only, like dia_active)
+  bool f32_active() const { return fb && (fz != multi_runs_fused(flags, st.fused[0]) || rule() != multi_rule_in_force(flags, st.fused[0])); }
 
   // what the rule reads of a level: the only place that asks Handle::multi_*_ok
-  static MultiLevelFacts facts(const Handle& h, int l) {
+  static MultiLevelFacts facts(const Handle& h, int l, bool f32) {
     const DevLevel& V = h.lev[l];
     MultiLevelFacts f;
     f.bs = V.bs; f.empty = V.n == 0; f.square = V.n == V.ncols; f.permuted = h.permuted(l);
@@ -98,24 +104,60 @@ struct Multi {
     f.a_scalar = Handle::multi_scalar_ok(V.A); f.a_level = Handle::multi_level_ok(V.A) && V.A.br == V.bs;
     f.t_scalar = Handle::multi_scalar_ok(V.P) && Handle::multi_scalar_ok(V.PT);
     f.t_transfer = Handle::multi_transfer_ok(V.P) && Handle::multi_transfer_ok(V.PT);
-    f.sweep_ok = h.multi_sweep_ok(V); f.block_sweep_ok = h.multi_block_sweep_ok(V); f.block_sweep_fits = h.multi_block_sweep_fits(V);
+    f.sweep_ok = h.multi_sweep_ok(V, f32); f.block_sweep_ok = h.multi_block_sweep_ok(V, f32); f.block_sweep_fits = h.multi_block_sweep_fits(V);
+    f.f32_ok = f32 && h.multi_f32_ok(V);
     return f;
   }
   static MultiState& state(Handle& h) {
     if (!h.multi) h.multi = new MultiState;
     MultiState& s = *h.multi;
-    if (s.fused[0] < 0) {
-      for (int l = 0; l < h.n_levels(); ++l) s.facts.push_back(facts(h, l));
-      for (int r = 0; r < 4; ++r) {
-        MultiDecision d = multi_handle_rule(r, h.cycle == AMGX_CYCLE_V, s.facts.data(), h.n_levels());
-        s.fused[r] = d.fused; s.why[r] = std::move(d.why);
+    if (s.fused[0][0] < 0) {
+      for (int b = 0; b < 2; ++b) {
+        for (int l = 0; l < h.n_levels(); ++l) s.facts[b].push_back(facts(h, l, b == 1));
+        for (int r = 0; r < 4; ++r) {
+          MultiDecision d = multi_handle_rule(r, h.cycle == AMGX_CYCLE_V, s.facts[b].data(), h.n_levels());
+          s.fused[b][r] = d.fused; s.why[b][r] = std::move(d.why);
+        }
       }
     }
     return s;
   }
   // first level that the multi cycle hands to ONE dense product (collapsed operator or the coarsest level's inverse)
   // (0: the whole cycle is the dense operator, no level work vectors)
-  int top() const { return h.dense_level >= 0 ? h.dense_level : h.n_levels() - 1; }
+  int top() const { return h.dense_level >= 0 ? h.dense_level : tail_cols() ? h.tail_level : h.n_levels() - 1; }
+  // AMGX_MULTI_FUSE_F32 on a handle with single-precision Gauss-Seidel images (`exact`): where the single-vector
+  // cycle of a Gauss-Seidel level differs from the literal stages, the fused group takes the single-vector kernel per column, so that a
+  // column reads the values and keeps the order of additions of amgx_apply.  tail_cols: the levels from tail_level on run as the
+  // single-workgroup tail program (which reads its own fp64 copies of the TRUE A, never the float images).  col_down: the residual
+  // after the sweep from zero runs fused with the chunk-local restriction (DOWN_GSB), which has no multi-vector form on float images.
+  bool exact() const {
+    if (!fb) return false;
+    for (const DevLevel& V : h.lev) if (V.sgs32 || V.sgs32_wide || V.gs32 || V.gs32_wide) return true;
+    return false;
+  }
+  bool tail_cols() const { return h.dense_level < 0 && h.tail_level > 0 && exact(); }
+  bool col_down(int l) const { const DevLevel& V = h.lev[l]; return V.sm_type == AMGX_SM_GS && V.paths.down == DOWN_GSB && !level_down(l).form && exact(); }
+  // col_block: a Gauss-Seidel level with square blocks.  On one vector Handle::product picks the kernel of a block-CSR matrix per matrix
+  // (row-lane or vector form), on NV vectors there is one kernel with another order of additions; so the transfers P^T and P and the
+  // coarsest solve run per column.  The sweeps are fused, and so is the residual after the sweep from zero where it reads a BSELL image
+  // (res_fused: `rest` / `bupper` of a level with the split, else A in BSELL): the NV BSELL kernels keep the single-vector order.
+  bool col_block(int l) const { const DevLevel& V = h.lev[l]; return V.sm_type == AMGX_SM_GS && V.bs != 1 && exact(); }
+  bool res_fused(int l) const {
+    const DevLevel& V = h.lev[l];
+    if (!Handle::split_identity(V, 2)) return V.A.fmt == FMT_BSELL;
+    return !V.paths.bgsb() || V.bgsb.rest.fmt == FMT_BSELL;
+  }
+  bool col_coarse() const { return h.lev.back().bs != 1 && exact(); }
+  bool col_stages() const {
+    if (tail_cols() || col_coarse()) return true;
+    for (int l = 0; l < top(); ++l) if (col_down(l) || col_block(l)) return true;
+    return false;
+  }
+  // the contiguous column buffers of those stages (allocated before a capture)
+  void fit_cols() {
+    const int64_t n0 = h.lev[0].len();
+    fit(st.col_in, n0); fit(st.col_out, n0); fit(st.dn_col, n0); fit(st.sm_r, n0);
+  }
 
   // ---- AMGX_MULTI_FUSE_DOWN: the down pass of ONE smoothed level on a fused group.  form 0: the literal stages,
   // `why` says which property keeps them ("" without the bit, on an empty level and on a level that is not smoothed); form 1 / 2:
@@ -130,14 +172,14 @@ struct Multi {
   DownNv level_down(int l, bool dia) const {
     DownNv d;
     if (!down_flag || l < 0 || l + 1 >= h.n_levels()) return d;
-    const MultiLevelFacts& f = st.facts[l];     // (the first two refusals are the fusion rule's, on the same facts)
+    const MultiLevelFacts& f = st.facts[fb][l]; // (the first two refusals are the fusion rule's, on the same facts)
     if (f.empty) return d;
     const DevLevel& V = h.lev[l];
     if (f.bs != 1) { d.why = "block level"; return d; }
     if (f.jacobi_f32) { d.why = "single-precision Jacobi images"; return d; }     // (the NV kernels read fp64 images)
     if (f.sgs_f32) { d.why = "single-precision Gauss-Seidel images"; return d; }  // (... and the fp64 values of `rest` are released)
     const DownPlan* p = nullptr;
-    if (f.square && !f.permuted && !st.facts[l + 1].permuted && f.plain) {
+    if (f.square && !f.permuted && !st.facts[fb][l + 1].permuted && f.plain) {
       if (V.sm_type == AMGX_SM_GS) {
         if (V.paths.sweep != SWEEP_GSB) { d.why = "multicolour sweep"; return d; }
         if (V.paths.down == DOWN_GSB && V.plan_rg.on && Handle::split_identity(V, 2)) p = &V.plan_rg;     // (2: any width above one)
@@ -209,8 +251,8 @@ struct Multi {
   static void fit(DevBuf<double>& b, int64_t n) { if ((int64_t)b.n < n) b.alloc((size_t)n); }
   MultiWork& work(int w) {
     MultiWork& W = st.work[w];
-    if (W.lev.empty()) {
-      const int T = top();
+    if (W.lev.empty()) {                                        // (top() is the same for every fused call of a handle: a handle that
+      const int T = top();                                      //  AMGX_MULTI_FUSE_F32 fuses is not fused without it)
       W.lev.resize(T + 1);
       for (int l = 0; l <= T; ++l) {
         const size_t len = (size_t)h.lev[l].len() * w;
@@ -278,6 +320,48 @@ struct Multi {
     width(w, [&](auto W) { h.sweep_from_zero<W()>(V, x, b, res); h.residual_after_zero<W()>(V, x, b, res); });
   }
 
+  // the residual after the sweep from zero and its restriction through the single-vector functions, column by column of a group
+  // (x, b: w interleaved vectors of level l; bc: of level l + 1).  The column buffers are those of fit_cols.
+  void down_cols(int w, int l, const double* b, const double* x, double* bc) {
+    DevLevel& V = h.lev[l];
+    const int64_t n = V.len(), nc = h.lev[l + 1].len();
+    fit_cols();
+    double *b1 = st.col_in.p, *x1 = st.col_out.p, *c1 = st.dn_col.p, *r = st.sm_r.p;
+    for (int j = 0; j < w; ++j) {
+      pack(n, 1, MultiView(b, w, 0, true), j, b1);
+      pack(n, 1, MultiView(x, w, 0, true), j, x1);
+      h.zero(r, n);                                            // (the multicolour identity writes swept rows only)
+      if (V.paths.down == DOWN_GSB) h.residual_restrict_after_zero(l, x1, b1, r, c1);
+      else { h.residual_after_zero(V, x1, b1, r); h.transfer_f2c(l, r, c1); }
+      unpack(nc, 1, c1, MultiView(bc, w, 0, true), j);
+    }
+  }
+
+  // b_c = P^T r through the single-vector restriction, column by column of a group (r: level l; bc: level l + 1)
+  void restrict_cols(int w, int l, const double* r, double* bc) {
+    const int64_t n = h.lev[l].len(), nc = h.lev[l + 1].len();
+    fit_cols();
+    double *r1 = st.col_in.p, *c1 = st.dn_col.p;
+    for (int j = 0; j < w; ++j) {
+      pack(n, 1, MultiView(r, w, 0, true), j, r1);
+      h.transfer_f2c(l, r1, c1);
+      unpack(nc, 1, c1, MultiView(bc, w, 0, true), j);
+    }
+  }
+  // t = x + P x_c through the single-vector product, column by column of a group (x, t: level l; xc: level l + 1; t may be x)
+  void up_cols(int w, int l, const double* xc, const double* x, double* t) {
+    DevLevel& V = h.lev[l];
+    const int64_t n = V.len(), nc = h.lev[l + 1].len();
+    fit_cols();
+    double *c1 = st.dn_col.p, *x1 = st.col_out.p, *t1 = st.sm_r.p;
+    for (int j = 0; j < w; ++j) {
+      pack(nc, 1, MultiView(xc, w, 0, true), j, c1);
+      pack(n, 1, MultiView(x, w, 0, true), j, x1);
+      h.mult_add(V.P, 1.0, c1, x1, t1);
+      unpack(n, 1, t1, MultiView(t, w, 0, true), j);
+    }
+  }
+
   void coarse_multi(int w, const double* rhs, double* x) {
     const DevLevel& V = h.lev.back();
     if (h.clev != AMGX_CLEV_INV || h.coarse_n == 0) { h.zero(x, V.len() * w); return; }
@@ -318,6 +402,16 @@ struct Multi {
           down_nv(w, l, dn, Handle::down_ops_gsb(V, xl), part, bc);
           continue;
         }
+        if (col_block(l) && res_fused(l)) {                    // (fused sweep and residual on the BSELL images, P^T per column)
+          gs_down(w, V, bl, xl, W.lev[l].res.p);
+          restrict_cols(w, l, W.lev[l].res.p, bc);
+          continue;
+        }
+        if (col_down(l) || col_block(l)) {                     // (residual + restriction as the single-vector cycle runs them, per column)
+          width(w, [&](auto NV) { h.sweep_from_zero<NV()>(V, xl, bl, W.lev[l].res.p); });
+          down_cols(w, l, bl, xl, bc);
+          continue;
+        }
         gs_down(w, V, bl, xl, W.lev[l].res.p);
         spmm<EP_MULT>(w, V.PT, W.lev[l].res.p, W.lev[l + 1].rhs.p, none);
         continue;
@@ -333,7 +427,23 @@ struct Multi {
       spmm<EP_MULT>(w, V.PT, W.lev[l].res.p, W.lev[l + 1].rhs.p, none);
     }
     if (h.dense_level > 0) gemm(w, h.dense_n, h.dense_ld, h.dense_op.p, W.lev[T].rhs.p, W.lev[T].x.p);
-    else coarse_multi(w, W.lev[T].rhs.p, W.lev[T].x.p);
+    else if (tail_cols()) {                                    // the tail program of the single-vector cycle, column by column
+      const DevLevel& V = h.lev[T];
+      const MultiView rhs(W.lev[T].rhs.p, w, 0, true), xt(W.lev[T].x.p, w, 0, true);
+      for (int j = 0; j < w; ++j) {
+        pack(V.len(), 1, rhs, j, V.rhs.p);
+        launch(tail_kernel, 1, TAIL_BLOCK, 0, h.stream, h.tail_ops, h.tail_prog.p);
+        unpack(V.len(), 1, V.x.p, xt, j);
+      }
+    } else if (col_coarse()) {                                 // the coarsest solve of the single-vector cycle, column by column
+      const int64_t nT = h.lev[T].len();
+      fit_cols();
+      for (int j = 0; j < w; ++j) {
+        pack(nT, 1, MultiView(W.lev[T].rhs.p, w, 0, true), j, st.col_in.p);
+        h.coarse_solve(st.col_in.p, st.col_out.p);
+        unpack(nT, 1, st.col_out.p, MultiView(W.lev[T].x.p, w, 0, true), j);
+      }
+    } else coarse_multi(w, W.lev[T].rhs.p, W.lev[T].x.p);
     for (int l = T - 1; l >= 0; --l) {
       const DevLevel& V = h.lev[l];
       double* xl = l == 0 ? x : W.lev[l].x.p;
@@ -341,7 +451,8 @@ struct Multi {
       double* const tmp = W.lev[l].tmp.p;
       if (V.sm_type == AMGX_SM_GS) {                           // t = x + P x_c, backward sweep t -> x (in place: t = x)
         double* t = V.paths.in_place ? xl : tmp;
-        spmm<EP_AXPY>(w, V.P, W.lev[l + 1].x.p, t, EpArgs{nullptr, xl, nullptr, 1.0, nullptr, 0});
+        if (col_block(l)) up_cols(w, l, W.lev[l + 1].x.p, xl, t);
+        else spmm<EP_AXPY>(w, V.P, W.lev[l + 1].x.p, t, EpArgs{nullptr, xl, nullptr, 1.0, nullptr, 0});
         if (gs_sweep(w, V, 1, t, xl, bl) != xl) throw Err("multi-vector cycle: the Gauss-Seidel sweep did not end in x");
       } else if (V.sm_type == AMGX_SM_CHEBY) {                 // t = x + P x_c where the last of the k passes lands in x
         double* t = cheb_place(cheb_passes(V.cheb_degree, ChebEntry::ITERATE), xl, tmp);
@@ -414,7 +525,7 @@ struct Multi {
     const MultiView vb(B, k, ldb, interleaved), vx(X, k, ldx, interleaved);
     // only the fused path is captured as a whole; the column loop replays the single-vector graphs of run_cycle
     if (!fz || !(h.use_graph && graph_ok) || h.stream == nullptr) { apply_body(k, vb, vx, graph_ok, false); return; }
-    const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx, rule() + (down_active() ? 4 : 0) + (dia_active() ? 8 : 0)};
+    const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx, rule() + (down_active() ? 4 : 0) + (dia_active() ? 8 : 0) + (f32_active() ? 16 : 0)};
     if (!st.graphs.has(key)) {
       int32_t wd[MULTI_MAX];
       const int ng = multi_groups(k, true, wd);
@@ -422,6 +533,7 @@ struct Multi {
         if (wd[g] > 1) { MultiWork& W = work(wd[g]); fit(W.in, h.lev[0].len() * wd[g]); fit(W.out, h.lev[0].len() * wd[g]); }
         else { fit(st.col_in, h.lev[0].len()); fit(st.col_out, h.lev[0].len()); }
       }
+      if (col_stages()) fit_cols();
     }
     st.graphs.run(key, h.stream, [&] { apply_body(k, vb, vx, false, true); });
   }
@@ -453,7 +565,7 @@ struct Multi {
     DevLevel& V = h.lev[level];
     const int64_t n = V.len(), col = std::max(n, h.lev[0].len());
     if (V.n != V.ncols) throw Err("amgx_smooth_multi: rank-partitioned levels are not supported");
-    const MultiLevelFacts& f = st.facts[level];
+    const MultiLevelFacts& f = st.facts[fb][level];
     const bool nv = gs_flag && !f.permuted && !f.empty && (f.sweep_ok || (block_flag && f.block_sweep_ok && f.block_sweep_fits));
     const MultiArg a[2] = {{MULTI_ARG_IN | MULTI_ARG_OUT, MultiView(X, k, ldx, interleaved), n, &st.col_out, col, &st.sm_x},
                            {MULTI_ARG_IN, MultiView(B, k, ldb, interleaved), n, &st.col_in, col, &st.sm_b}};
@@ -483,7 +595,11 @@ struct Multi {
     const bool gs = V.sm_type == AMGX_SM_GS, cheby = V.sm_type == AMGX_SM_CHEBY, jacobi = V.sm_type == AMGX_SM_JACOBI;
     if (x_given && jacobi && V.paths.jacobi_down()) throw Err("amgx_down_multi: x_given on a Jacobi level with a fused down pass (the Jacobi down pass forms x itself)");
     const DownNv dn = level_down(level);
-    const bool nv = dn.form != 0 && (x_given || !gs || gs_flag);
+    // AMGX_MULTI_FUSE_F32: a Gauss-Seidel level with single-precision images keeps the literal stages (level_down),
+    // but with AMGX_MULTI_FUSE_GS its sweep from zero runs on the group; residual and restriction follow per column
+    const MultiLevelFacts& f = st.facts[fb][level];
+    const bool sweep32 = !x_given && gs && down_flag && gs_flag && f.f32_ok && f.sweep_ok && !f.permuted && !f.empty;
+    const bool nv = sweep32 || (dn.form != 0 && (x_given || !gs || gs_flag));
     const MultiArg a[3] = {{MULTI_ARG_IN, MultiView(B, k, ldb, interleaved), n, &st.col_in, col, &st.sm_b},
                            {x_given ? MULTI_ARG_IN : MULTI_ARG_OUT, MultiView(X, k, ldx, interleaved), n, &st.col_out, col, &st.sm_x},
                            {MULTI_ARG_OUT, MultiView(BC, k, ldbc, interleaved), nc, &st.dn_col, nc, &st.dn_c}};
@@ -502,6 +618,11 @@ struct Multi {
            constexpr int WMAX = MULTI_MAX / 2;                 // the widest group
            fit(st.sm_t, n * WMAX); fit(st.dn_d, n * WMAX); fit(st.dn_part, down_slots(V, dn) * WMAX);
            double *bw = q[0], *xw = q[1];
+           if (sweep32) {
+             width(w, [&](auto NV) { h.sweep_from_zero<NV()>(V, xw, bw, st.sm_t.p); });
+             down_cols(w, level, bw, xw, q[2]);                // the single-vector residual and restriction of every column
+             return;
+           }
            if (!x_given && cheby) cheb(w, V, ChebEntry::ZERO, xw, xw, bw, st.sm_t.p, st.dn_d.p);
            else if (!x_given && gs) width(w, [&](auto NV) { h.sweep_from_zero<NV()>(V, xw, bw, nullptr); });
            if (jacobi) down_nv(w, level, dn, h.down_ops_jacobi(V, bw, xw, h.folded(V)), st.dn_part.p, q[2]);
@@ -749,7 +870,7 @@ int amgx_multi_plan(amgx_handle hh, int k, int flags, int32_t* fused, int32_t* n
 
 const char* amgx_multi_note(amgx_handle hh, int flags) {
   return amgx::multi_note_call(hh, [&](amgx::Handle& h) -> std::string {
-    amgx::Multi M(h, flags & amgx::Multi::ALL_FLAGS);
+    amgx::Multi M(h, flags & amgx::Multi::NOTE_FLAGS);
     return M.fz ? std::string() : M.note();
   });
 }

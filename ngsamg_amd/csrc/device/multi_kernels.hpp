@@ -211,8 +211,9 @@ __global__ __launch_bounds__(BLOCK) void sell_spmm_kernel(int64_t n_rows, int n_
 }
 
 // windowed SELL (sell_win_spmv_kernel's multi-vector form): the NV row sums go through LDS back to natural order
-template <int WB, int NV, int EP>
-__global__ __launch_bounds__(WB) void sell_win_spmm_kernel(int64_t n_rows, SellMat M, const uint16_t* __restrict__ rowloc,
+// V = float: the single-precision image (EP_CRES on `rest` of a scalar Gauss-Seidel level is instantiated)
+template <int WB, int NV, int EP, class V = double>
+__global__ __launch_bounds__(WB) void sell_win_spmm_kernel(int64_t n_rows, SellMatT<V> M, const uint16_t* __restrict__ rowloc,
                                                            const double* __restrict__ x, double* y, EpArgs ep) {
   __shared__ double buf[WB * NV];
   const int lane = threadIdx.x & (WAVE - 1);
@@ -856,7 +857,11 @@ __global__ __launch_bounds__(BLOCK) void bsell_spmm_kernel(int64_t n_rows, int n
       V v0, v1;
       ld_nt_pair(vk + cp * (2 * WAVE) + lane * 2, v0, v1);
 #pragma unroll
-      for (int j = 0; j < NV; ++j) acc[j] += (double)v0 * xv[2 * cp][j] + (double)v1 * xv[2 * cp + 1][j];
+      for (int j = 0; j < NV; ++j) {
+        // (r = rest x on the float image, DESIGN.md 5.22: the pair sum spelled out, see bsell_block_step_nv)
+        if constexpr (sizeof(V) == 4 && EP == EP_MULT) acc[j] += __builtin_fma((double)v0, xv[2 * cp][j], (double)v1 * xv[2 * cp + 1][j]);
+        else acc[j] += (double)v0 * xv[2 * cp][j] + (double)v1 * xv[2 * cp + 1][j];
+      }
     }
     if constexpr (BS & 1) {
       const double vl = (double)ld_nt(vk + (BS / 2) * (2 * WAVE) + lane);
@@ -1060,8 +1065,10 @@ __global__ __launch_bounds__(BLOCK) void dense_gemm_nv_kernel(int n, int ld, con
 //   * plain images only (global columns): the local-window and mid-width forms of the single-vector sweep are launch choices over
 //     the same slot order, so their results are the same bits.
 // The colour loop holds a workgroup barrier: no lane returns before it, n_colors is uniform.
-template <int TH, int G, bool FROM_ZERO, int WP, int NV>
-__global__ __launch_bounds__(TH) void gsb_sweep_nv_kernel(int64_t n_rows, SellMat M, GsbArgs a, const double* __restrict__ xin, double* xout) {
+// V = float (AMGX_MULTI_FUSE_F32): the single-precision image, same index arrays; a lane keeps its values as loaded
+// and widens them where it multiplies, as gsb_sweep_kernel<..., float> does.
+template <int TH, int G, bool FROM_ZERO, int WP, int NV, class V = double>
+__global__ __launch_bounds__(TH) void gsb_sweep_nv_kernel(int64_t n_rows, SellMatT<V> M, GsbArgs a, const double* __restrict__ xin, double* xout) {
   constexpr int B = TH / G;                  // rows per block
   constexpr int RPS = WAVE / G;              // rows per slice
   constexpr int NE = 2 * WP + 1;             // entries a lane holds
@@ -1090,17 +1097,16 @@ __global__ __launch_bounds__(TH) void gsb_sweep_nv_kernel(int64_t n_rows, SellMa
   const int w = (int)(((M.slice_ptr[s + 1] & ~(int64_t)63) - base) >> 6);
   const int np = w >> 1;
   const bool c16 = sp0 & 1;
-  const double* __restrict__ vb = M.val + base;
+  const V* __restrict__ vb = M.val + base;
   const int32_t* __restrict__ cb = M.cbase + (base >> 6);
-  double v[NE];
+  V v[NE];
   int cl[NE];
   uint32_t ra[WP], rb[WP];
 #pragma unroll
   for (int p = 0; p < WP; ++p) {
-    v[2 * p] = 0.0; v[2 * p + 1] = 0.0; ra[p] = 0; rb[p] = 0;
+    v[2 * p] = 0; v[2 * p + 1] = 0; ra[p] = 0; rb[p] = 0;
     if (p < np) {                                            // wave-uniform
-      v[2 * p] = ld_nt(vb + (p * WAVE + lane) * 2);
-      v[2 * p + 1] = ld_nt(vb + (p * WAVE + lane) * 2 + 1);
+      ld_nt_pair(vb + (p * WAVE + lane) * 2, v[2 * p], v[2 * p + 1]);
       if (c16) ra[p] = ld_nt(reinterpret_cast<const uint32_t*>(M.col16 + base) + p * WAVE + lane);
       else {
         ra[p] = (uint32_t)ld_nt(M.col32 + base + (p * WAVE + lane) * 2);
@@ -1116,7 +1122,7 @@ __global__ __launch_bounds__(TH) void gsb_sweep_nv_kernel(int64_t n_rows, SellMa
     for (int j = 0; j < NE; ++j) cbv[j] = cb[j];
   }
   uint32_t rt = 0;
-  v[2 * WP] = 0.0;
+  v[2 * WP] = 0;
   if (w & 1) {
     const int64_t o = (int64_t)(w - 1) * WAVE + lane;
     v[2 * WP] = ld_nt(vb + o);
@@ -1176,10 +1182,10 @@ __global__ __launch_bounds__(TH) void gsb_sweep_nv_kernel(int64_t n_rows, SellMa
         const int j = j0 + u;
         if (!FROM_ZERO) {
 #pragma unroll
-          for (int c = 0; c < NV; ++c) acc_off[c] += inb[u] ? 0.0 : v[j] * xg[u][c];
+          for (int c = 0; c < NV; ++c) acc_off[c] += inb[u] ? 0.0 : (double)v[j] * xg[u][c];
         }
         if (inb[u]) cl[j] -= (int)r0;
-        else { v[j] = 0.0; cl[j] = 0; }
+        else { v[j] = 0; cl[j] = 0; }
       }
     }
     if (!FROM_ZERO) {
@@ -1205,7 +1211,7 @@ __global__ __launch_bounds__(TH) void gsb_sweep_nv_kernel(int64_t n_rows, SellMa
         double xv[NV];
         ldv<NV>(xs + cl[j] * NV, xv);
 #pragma unroll
-        for (int cc = 0; cc < NV; ++cc) acc[cc] += v[j] * xv[cc];
+        for (int cc = 0; cc < NV; ++cc) acc[cc] += (double)v[j] * xv[cc];
       }
 #pragma unroll
       for (int cc = 0; cc < NV; ++cc) {
@@ -1231,8 +1237,8 @@ __global__ __launch_bounds__(TH) void gsb_sweep_nv_kernel(int64_t n_rows, SellMa
 
 // gs_color_kernel (kernels.hpp) with the row product widened to NV gathers: one colour per launch on the colour-major images `sell`
 // and `lower` of DevGS.  Padding rows (rowid < 0) are never written.
-template <int G, int NV>
-__global__ __launch_bounds__(BLOCK) void gs_color_nv_kernel(int slice_begin, int slice_end, SellMat M, const int32_t* __restrict__ rowid,
+template <int G, int NV, class V = double>
+__global__ __launch_bounds__(BLOCK) void gs_color_nv_kernel(int slice_begin, int slice_end, SellMatT<V> M, const int32_t* __restrict__ rowid,
                                                             const double* __restrict__ dinv, const double* __restrict__ b, double* x) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int s = __builtin_amdgcn_readfirstlane(slice_begin + blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6));
@@ -1258,8 +1264,8 @@ __global__ __launch_bounds__(BLOCK) void gs_color_nv_kernel(int slice_begin, int
 
 // gs_upper_residual_kernel for NV vectors: r = -(U x) on the colour-major rows of the `upper` image, right after a forward sweep
 // from x = 0
-template <int G, int NV>
-__global__ __launch_bounds__(BLOCK) void gs_upper_residual_nv_kernel(int n_slices, SellMat M, const int32_t* __restrict__ rowid,
+template <int G, int NV, class V = double>
+__global__ __launch_bounds__(BLOCK) void gs_upper_residual_nv_kernel(int n_slices, SellMatT<V> M, const int32_t* __restrict__ rowid,
                                                                      const double* __restrict__ x, double* __restrict__ r) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int s = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6));
@@ -1285,37 +1291,43 @@ __global__ __launch_bounds__(BLOCK) void gs_upper_residual_nv_kernel(int n_slice
 // One block step of a BSELL row product for NV columns: the value loads of bsell_block_step<BS, false> (pair order, odd trailing
 // column last) and ONE gather of the block's BS * NV contiguous doubles at xb (global memory or LDS).  The values are loaded once
 // and serve all NV columns; per column the additions are those of the single-vector step.
-template <int BS, int NV>
-__device__ __forceinline__ void bsell_block_step_nv(const double* __restrict__ vk, const double* xb, int lane, double (&acc)[NV]) {
+// V = float: the single-precision image; a value is widened where it multiplies (bsell_block_step<BS, false, float>).
+template <int BS, int NV, class V>
+__device__ __forceinline__ void bsell_block_step_nv(const V* __restrict__ vk, const double* xb, int lane, double (&acc)[NV]) {
   double xv[BS][NV];
 #pragma unroll
   for (int cc = 0; cc < BS; ++cc) ldv<NV>(xb + cc * NV, xv[cc]);
 #pragma unroll
   for (int cp = 0; cp < BS / 2; ++cp) {
-    double v0, v1;
+    V v0, v1;
     ld_nt_pair(vk + cp * (2 * WAVE) + lane * 2, v0, v1);
+    // (float: the pair sum is written as the fused multiply-add every other kernel of the family compiles to, v0 x0 + [v1 x1]; left to
+    // the compiler, the widened operands come out as [v0 x0] + v1 x1 in some columns -- another rounding, measured 7e-15 per sweep)
 #pragma unroll
-    for (int j = 0; j < NV; ++j) acc[j] += v0 * xv[2 * cp][j] + v1 * xv[2 * cp + 1][j];
+    for (int j = 0; j < NV; ++j) {
+      if constexpr (sizeof(V) == 4) acc[j] += __builtin_fma((double)v0, xv[2 * cp][j], (double)v1 * xv[2 * cp + 1][j]);
+      else acc[j] += v0 * xv[2 * cp][j] + v1 * xv[2 * cp + 1][j];
+    }
   }
   if constexpr (BS & 1) {
-    const double vl = ld_nt(vk + (BS / 2) * (2 * WAVE) + lane);
+    const double vl = (double)ld_nt(vk + (BS / 2) * (2 * WAVE) + lane);
 #pragma unroll
     for (int j = 0; j < NV; ++j) acc[j] += vl * xv[BS - 1][j];
   }
 }
 // (row product of one slice: `w` block steps from (vb, cb), gathered blocks at x + c * BS * NV)
-template <int BS, int NV>
-__device__ __forceinline__ void bsell_slice_dot_nv(const BSellMat& M, int s, int rbl, int lane, const double* x, double (&acc)[NV]) {
+template <int BS, int NV, class V>
+__device__ __forceinline__ void bsell_slice_dot_nv(const BSellMatT<V>& M, int s, int rbl, int lane, const double* x, double (&acc)[NV]) {
   constexpr int RB = WAVE / BS;
   const int64_t k0 = M.slice_ptr[s];
   const int w = (int)(M.slice_ptr[s + 1] - k0);
-  const double* __restrict__ vb = M.val + k0 * (BS * WAVE);
+  const V* __restrict__ vb = M.val + k0 * (BS * WAVE);
   const int32_t* __restrict__ cb = M.col + k0 * RB;
 #pragma unroll
   for (int j = 0; j < NV; ++j) acc[j] = 0.0;
   for (int k = 0; k < w; ++k) {
     const int c = cb[k * RB + rbl];
-    bsell_block_step_nv<BS, NV>(vb + (int64_t)k * (BS * WAVE), x + (int64_t)c * (BS * NV), lane, acc);
+    bsell_block_step_nv<BS, NV, V>(vb + (int64_t)k * (BS * WAVE), x + (int64_t)c * (BS * NV), lane, acc);
   }
 }
 // the block solve of a row's lane group for NV columns: u = sum_c od[c] * t_c with t exchanged over the BS lanes from `base` on
@@ -1336,11 +1348,11 @@ __device__ __forceinline__ void block_solve_nv(const double (&od)[BS], const dou
 // zero, later block colours).  xs and b' live in LDS interleaved like the vectors (2 * BB * BS * NV doubles + the BB row ids: the
 // launcher computes the size, Handle::multi_block_sweep_lds); a row's dinv is loaded once for all NV columns.  Every lane reaches
 // every barrier; idle lanes (lane >= RB * BS) and padding slots (in_row < 0) never write.
-template <int BS, int MODE, int NV>
+template <int BS, int MODE, int NV, class V = double>
 __global__ __launch_bounds__(BLOCK) void bgsb_sweep_nv_kernel(int BB, int block0, const int32_t* __restrict__ blk_list,
                                                               const int32_t* __restrict__ blk_ptr, const int32_t* __restrict__ blk_rows,
-                                                              BSellMat OFF, const int32_t* __restrict__ off_ptr,
-                                                              BSellMat IN, BSellMat OTH, const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_row,
+                                                              BSellMatT<V> OFF, const int32_t* __restrict__ off_ptr,
+                                                              BSellMatT<V> IN, BSellMatT<V> OTH, const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_row,
                                                               int n_colors, int dir, const double* __restrict__ dinv, const double* __restrict__ b,
                                                               const double* xin, double* xout) {
   constexpr bool FROM_ZERO = MODE != 0;
@@ -1372,7 +1384,7 @@ __global__ __launch_bounds__(BLOCK) void bgsb_sweep_nv_kernel(int BB, int block0
       const int lrow = (s - s0) * RB + rbl;
       const bool active = lane_on && lrow < nb;
       double acc[NV];
-      bsell_slice_dot_nv<BS, NV>(OFF, s, rbl, lane, xin, acc);
+      bsell_slice_dot_nv<BS, NV, V>(OFF, s, rbl, lane, xin, acc);
       if (active) {
         double bb[NV];
         ldv<NV>(bsh + (lrow * BS + r) * NV, bb);
@@ -1387,7 +1399,7 @@ __global__ __launch_bounds__(BLOCK) void bgsb_sweep_nv_kernel(int BB, int block0
       const int lrow = in_row[(int64_t)s * RB + rbl];
       const bool active = lane_on && lrow >= 0;
       double acc[NV];
-      bsell_slice_dot_nv<BS, NV>(OTH, s, rbl, lane, xs, acc);
+      bsell_slice_dot_nv<BS, NV, V>(OTH, s, rbl, lane, xs, acc);
       if (active) {
         double bb[NV];
         ldv<NV>(bsh + (lrow * BS + r) * NV, bb);
@@ -1408,7 +1420,7 @@ __global__ __launch_bounds__(BLOCK) void bgsb_sweep_nv_kernel(int BB, int block0
 #pragma unroll
       for (int cc = 0; cc < BS; ++cc) od[cc] = active ? dinv[(int64_t)rowsh[lrow] * (BS * BS) + r * BS + cc] : 0.0;
       double acc[NV], t[NV], u[NV];
-      bsell_slice_dot_nv<BS, NV>(IN, s, rbl, lane, xs, acc);
+      bsell_slice_dot_nv<BS, NV, V>(IN, s, rbl, lane, xs, acc);
 #pragma unroll
       for (int j = 0; j < NV; ++j) t[j] = 0.0;
       if (active) {
@@ -1432,8 +1444,8 @@ __global__ __launch_bounds__(BLOCK) void bgsb_sweep_nv_kernel(int BB, int block0
 
 // bgs_bsell_color_kernel for NV vectors: one colour per launch on the colour-major BSELL copy (gs.bcopy, or gs.blower for the sweep
 // from zero), in place.  Padding slots (rowid < 0) and idle lanes never write.
-template <int BS, int NV>
-__global__ __launch_bounds__(BLOCK) void bgs_bsell_color_nv_kernel(int slice_begin, int slice_end, BSellMat M, const int32_t* __restrict__ rowid,
+template <int BS, int NV, class V = double>
+__global__ __launch_bounds__(BLOCK) void bgs_bsell_color_nv_kernel(int slice_begin, int slice_end, BSellMatT<V> M, const int32_t* __restrict__ rowid,
                                                                    const double* __restrict__ dinv, const double* __restrict__ b, double* x) {
   constexpr int RB = WAVE / BS;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -1455,7 +1467,7 @@ __global__ __launch_bounds__(BLOCK) void bgs_bsell_color_nv_kernel(int slice_beg
     for (int c = 0; c < BS; ++c) od[c] = dinv[(int64_t)brow * (BS * BS) + r * BS + c];
   }
   double acc[NV], u[NV];
-  bsell_slice_dot_nv<BS, NV>(M, s, rbl, lane, x, acc);
+  bsell_slice_dot_nv<BS, NV, V>(M, s, rbl, lane, x, acc);
 #pragma unroll
   for (int j = 0; j < NV; ++j) t[j] = active ? t[j] - acc[j] : 0.0;
   block_solve_nv<BS, NV>(od, t, lane - r, u);
@@ -1469,8 +1481,8 @@ __global__ __launch_bounds__(BLOCK) void bgs_bsell_color_nv_kernel(int slice_beg
 }
 
 // bgs_bsell_upper_residual_kernel for NV vectors: r_B = -(U x)_B on the colour-major block rows of gs.bupper after the sweep from zero
-template <int BS, int NV>
-__global__ __launch_bounds__(BLOCK) void bgs_bsell_upper_residual_nv_kernel(int n_slices, BSellMat M, const int32_t* __restrict__ rowid,
+template <int BS, int NV, class V = double>
+__global__ __launch_bounds__(BLOCK) void bgs_bsell_upper_residual_nv_kernel(int n_slices, BSellMatT<V> M, const int32_t* __restrict__ rowid,
                                                                             const double* __restrict__ x, double* __restrict__ res) {
   constexpr int RB = WAVE / BS;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -1481,7 +1493,7 @@ __global__ __launch_bounds__(BLOCK) void bgs_bsell_upper_residual_nv_kernel(int 
   const int brow = rowid[(int64_t)s * RB + rbl];
   const bool active = lane < RB * BS && brow >= 0;
   double acc[NV];
-  bsell_slice_dot_nv<BS, NV>(M, s, rbl, lane, x, acc);
+  bsell_slice_dot_nv<BS, NV, V>(M, s, rbl, lane, x, acc);
   if (active) {
 #pragma unroll
     for (int j = 0; j < NV; ++j) acc[j] = -acc[j];

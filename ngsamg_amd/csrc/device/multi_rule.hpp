@@ -31,6 +31,9 @@ struct MultiLevelFacts {
   bool jacobi_f32 = false;              // single-precision Jacobi images; the NV kernels read fp64 images
   bool gs_f32 = false;                  // single-precision Gauss-Seidel images
   bool sgs_f32 = false;                 // ... of a scalar level (the twin too): the fp64 values of its sweep images are released
+  // the call carries AMGX_MULTI_FUSE_F32 and every image this level's fused passes read has a multi-vector kernel on its float array
+  // (Handle::multi_f32_ok)
+  bool f32_ok = false;
   bool smoothed = false;                // not the coarsest level
   int sm_type = AMGX_SM_JACOBI;
   bool plain = true;                    // sm_steps == 1 and no sm_symm
@@ -69,9 +72,10 @@ inline const char* multi_level_reason(int rule, const MultiLevelFacts& f) {
     if (f.permuted) return "renumbered level";
     if (f.jacobi_f32) return "single-precision Jacobi images";
     if (gs && !f.empty) {
-      // (the fused sweeps read fp64 images: the column loop keeps a column equal to amgx_apply, bit for bit)
-      if (rule >= 3 && f.gs_f32) return "single-precision Gauss-Seidel images";
-      if (f.sgs_f32) return "single-precision Gauss-Seidel images";
+      // (without AMGX_MULTI_FUSE_F32 the fused sweeps read fp64 images: the column loop keeps a column equal to amgx_apply, bit for
+      // bit.  With it, f32_ok says that the fused passes read the arrays of the single-vector passes)
+      if (rule >= 3 && f.gs_f32 && !f.f32_ok) return "single-precision Gauss-Seidel images";
+      if (f.sgs_f32 && !f.f32_ok) return "single-precision Gauss-Seidel images";
       if (!(f.bs == 1 ? f.sweep_ok : f.block_sweep_ok)) return "Gauss-Seidel sweep form without a multi-vector kernel";
       if (f.bs != 1 && !f.block_sweep_fits) return "sweep block too large for the multi-vector sweep";
     }
@@ -94,6 +98,7 @@ inline MultiDecision multi_handle_rule(int rule, bool cycle_is_v, const MultiLev
 }
 
 // ---- a call's flags.  AMGX_MULTI_FUSE_GS_BLOCK implies ..._GS implies AMGX_MULTI_FUSE; the two ..._DOWN bits imply nothing here.
+// AMGX_MULTI_FUSE_F32 implies nothing either: it picks which of the two decisions per rule is read (the facts with f32_ok filled in).
 // fused[r]: the handle under rule r (each rule admits what the one before admits).
 constexpr int MULTI_RULE_FLAGS = AMGX_MULTI_FUSE | AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_GS_BLOCK;
 inline int multi_asked_rule(int flags) {        // the widest rule the flags ask for

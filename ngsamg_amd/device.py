@@ -288,12 +288,15 @@ def check_fuse(fuse):
     "down", "gs+down", "gs_block+down" -> the bits of True, "gs", "gs_block" | AMGX_MULTI_FUSE_DOWN (fused groups run the fused down
     pass on every level that qualifies, DESIGN.md 5.18);
     "down_dia", "gs+down_dia", "gs_block+down_dia" -> the bits of "down", "gs+down", "gs_block+down" | AMGX_MULTI_FUSE_DOWN_DIA (levels
-    with a diagonal image take the fused down pass too, and such Jacobi levels the folded way up)"""
+    with a diagonal image take the fused down pass too, and such Jacobi levels the folded way up, DESIGN.md 5.19);
+    "gs+f32", "gs_block+f32", "gs+down+f32", "gs_block+down+f32" -> the bits of the word before "+f32" | AMGX_MULTI_FUSE_F32 (Gauss-Seidel
+    levels with single-precision images fuse too, through the multi-vector sweeps on the float arrays)"""
     if isinstance(fuse, str) and fuse in _FUSE_WORDS:
         return _FUSE_WORDS[fuse]
     if not isinstance(fuse, (bool, np.bool_)):
         raise NgsAMGError(f"fuse: need True, False, \"gs\", \"gs_block\", \"down\", \"gs+down\", \"gs_block+down\", "
-                          f"\"down_dia\", \"gs+down_dia\" or \"gs_block+down_dia\", got {fuse!r}")
+                          f"\"down_dia\", \"gs+down_dia\" or \"gs_block+down_dia\", got {fuse!r}"
+                          f" (or, with single-precision Gauss-Seidel images, \"gs+f32\", \"gs_block+f32\", \"gs+down+f32\", \"gs_block+down+f32\")")
     return _lib.AMGX_MULTI_FUSE if fuse else 0
 
 
@@ -308,6 +311,10 @@ _FUSE_WORDS = {
 _FUSE_WORDS["down_dia"] = _FUSE_WORDS["down"] | _lib.AMGX_MULTI_FUSE_DOWN_DIA
 _FUSE_WORDS["gs+down_dia"] = _FUSE_WORDS["gs+down"] | _lib.AMGX_MULTI_FUSE_DOWN_DIA
 _FUSE_WORDS["gs_block+down_dia"] = _FUSE_WORDS["gs_block+down"] | _lib.AMGX_MULTI_FUSE_DOWN_DIA
+# (AMGX_MULTI_FUSE_F32 implies nothing: the words carry the bits of the word before "+f32" and the new one)
+for _w in ("gs", "gs_block", "gs+down", "gs_block+down"):
+    _FUSE_WORDS[_w + "+f32"] = _FUSE_WORDS[_w] | _lib.AMGX_MULTI_FUSE_F32
+del _w
 
 
 def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V", clev="inv", device=0,
@@ -547,7 +554,9 @@ class DeviceAMGMatrix:
         fuse="down", "gs+down", "gs_block+down" (AMGX_MULTI_FUSE_DOWN beside the bits of True, "gs", "gs_block"): the fused groups
         run the residual + restriction of every level that qualifies in one pass (multi_level_plan).
         fuse="down_dia", "gs+down_dia", "gs_block+down_dia" (AMGX_MULTI_FUSE_DOWN_DIA as well): levels with a diagonal image qualify
-        too, and a Jacobi level that takes the pass runs the way up as x = z + Q x_c."""
+        too, and a Jacobi level that takes the pass runs the way up as x = z + Q x_c.
+        fuse="gs+f32", "gs_block+f32", "gs+down+f32", "gs_block+down+f32" (AMGX_MULTI_FUSE_F32 as well): Gauss-Seidel levels with
+        single-precision images (mat_prec="single_gs_all" / "single_gs") run fused too, on the float arrays."""
         ff = check_fuse(fuse)
         n = self.sizes[0]
         k, (ab, ax), (lb, lx), dev = check_multi((B, X), (n, n), interleaved, ("B", "X"))
@@ -563,7 +572,8 @@ class DeviceAMGMatrix:
         return Y
 
     def multi_plan(self, k, fuse=False):
-        """multi_info for a call that carries fuse=, plus "note": the first reason why the handle is not fused ("" when it is)"""
+        """multi_info for a call that carries fuse=, plus "note": the first reason why the handle is not fused ("" when it is).
+        A handle with single-precision Gauss-Seidel images answers fused under "gs+f32" / "gs_block+f32" only."""
         ff = check_fuse(fuse)
         if not (1 <= int(k) <= _lib.AMGX_MULTI_MAX):
             raise NgsAMGError(f"multi_plan: k = {k}, need 1 .. {_lib.AMGX_MULTI_MAX}")
@@ -654,8 +664,9 @@ class DeviceAMGMatrix:
     def SmoothMulti(self, level, X, B, x_zero=False, back=False, interleaved=False, fuse=False):
         """one plain smoother step per column: Smooth(level, X[j], B[j], res, x_zero=x_zero, back=back) with a res of its own
         (amgx_smooth_multi).  X, B: (k, n_level), or (n_level, k) with interleaved=True.  fuse="gs": groups of 4 and 2 columns
-        run the multi-vector Gauss-Seidel sweeps on a scalar level that has them, fuse="gs_block" on a square-block level too; a
-        column equals Smooth bit for bit either way."""
+        run the multi-vector Gauss-Seidel sweeps on a scalar level that has them, fuse="gs_block" on a square-block level too;
+        fuse="gs+f32" / "gs_block+f32" also on a level whose sweeps read single-precision images (the float sweeps).  A column
+        equals Smooth bit for bit either way."""
         ff = check_fuse(fuse)
         n = self._size(level)
         if self.ext_sizes[level] != n:

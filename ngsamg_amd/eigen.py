@@ -65,7 +65,8 @@ def lobpcg(A, pre, num, mass=None, free=None, X0=None, tol=1e-8, maxit=200, hist
     multivector.MultMulti(dev) on the device); mass=None is the identity.  free: 0/1 mask of the dofs (None: all free).  X0: the
     start block (a multi-vector of either backend; None: random columns from `seed`, which needs operators that can allocate).
     history=True is LOBPCG (basis [X, W, P]), False PINVIT (basis [X, W]).  fuse: passed to the device adapters
-    (False, True, "gs", "gs_block", or "down" / "gs+down" / "gs_block+down" for the fused down pass as well: device.check_fuse).
+    (False, True, "gs", "gs_block", or "down" / "gs+down" / "gs_block+down" for the fused down pass as well; "gs+f32" / "gs_block+f32"
+    on a preconditioner with single-precision Gauss-Seidel images: device.check_fuse).
 
     Returns (lams, X, info).  Convergence measure per column: res_j = |A x_j - theta_j M x_j| / (|theta_j| |M x_j|); a column
     with res_j <= tol is locked: it stays in the Rayleigh-Ritz basis but gets no new search directions and no operator or

@@ -28,7 +28,13 @@ goes to profiles/r24/.
 
 --dia (with --down): one more call per round, (e) = (b) with AMGX_MULTI_FUSE_DOWN_DIA as well (fuse="down_dia"), and
 the same for amgx_pcg_multi.  The yardstick of (e) is (b) of the same round, as for (d); every line prints multi_level_plan of the
-smoothed levels under both words; the result goes to profiles/r25/."""
+smoothed levels under both words; the result goes to profiles/r25/.
+
+--mat-prec single_gs_all (with --smoother gs --config cfg2) / single_gs (with --smoother gs --config cfg3 | cfg5): the handle with
+single-precision Gauss-Seidel images, fused only under AMGX_MULTI_FUSE_F32 as well.  Per round (a) k single
+applications on it, (b) one multi call with fuse="gs+f32" / "gs_block+f32", (c) the same call without "+f32" (the column loop), (d) the
+fused call on a double handle created in the same process; the same for amgx_pcg_multi with the iteration counts of each.  Before any
+time counts, (b) equals (a) to 1e-12 and (c) equals (a) bit for bit.  The result goes to profiles/r30/."""
 import argparse
 import json
 import os
@@ -51,6 +57,108 @@ def _stats(ts):
     return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts), "rounds_ms": ts}
 
 
+def _f32(args, H, p, kw, fuse, ks, nv):
+    """--mat-prec single_gs_all | single_gs: per alternating round, in one process, (a) k single applications on the
+    single-precision handle, (b) one multi call on it with the "+f32" word, (c) the same call without "+f32" (the column loop), (d) the
+    fused call on a double handle; and the same for amgx_pcg_multi with iteration counts"""
+    import numpy as np
+    import torch
+    from ngsamg_amd.device import DeviceAMGMatrix
+    from ngsamg_amd.krylov import NativeCGSolver
+    single = DeviceAMGMatrix(H, device=0, mat_prec=args.mat_prec, **kw)
+    double = DeviceAMGMatrix(H, device=0, **kw)
+    word = fuse + "+f32"
+    plan, old = single.multi_plan(4, fuse=word), single.multi_plan(4, fuse=fuse)
+    if plan["fused"] != 1 or old["fused"] != 0 or double.multi_plan(4, fuse=fuse)["fused"] != 1:
+        sys.exit(f"bench_multi_rhs: plans are not (fused, column loop, fused): {plan} {old}")
+    n = p.n * p.bs
+    pfree = np.repeat(p.free, p.bs).astype(np.float64)
+    rng = np.random.default_rng(0)
+    stream = torch.cuda.Stream()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(fn, reps):
+        with torch.cuda.stream(stream):
+            ev0.record(stream)
+            for _ in range(reps):
+                fn()
+            ev1.record(stream)
+        ev1.synchronize()
+        return ev0.elapsed_time(ev1) / reps
+
+    out = {"commit": args.commit or _commit(), "config": args.config, "smoother": args.smoother, "mat_prec": args.mat_prec, "fuse": word, "nv": nv,
+           "n": int(n), "levels": H.n_levels, "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps,
+           "pcg_reps": args.pcg_reps, "note_without_f32": old["note"],
+           "float_levels": [l for l in range(H.n_levels) if single.level_extra(l)["gs_f32"]], "k": {}}
+    for k in ks:
+        B = rng.standard_normal((k, n)) * pfree
+        bs = [torch.from_numpy(np.ascontiguousarray(B[j])).cuda() for j in range(k)]
+        xs = [torch.empty_like(b) for b in bs]
+        Bi = torch.from_numpy(np.ascontiguousarray(B.T)).cuda()
+        X = {key: torch.full_like(Bi, float("nan")) for key in "bcd"}
+        calls = {"a": lambda: [single.Mult(bs[j], xs[j]) for j in range(k)],
+                 "b": lambda: single.MultMulti(Bi, X["b"], interleaved=True, fuse=word),
+                 "c": lambda: single.MultMulti(Bi, X["c"], interleaved=True, fuse=fuse),
+                 "d": lambda: double.MultMulti(Bi, X["d"], interleaved=True, fuse=fuse)}
+        for fn in calls.values():
+            timed(fn, 3)
+        torch.cuda.synchronize()
+        Xa = torch.stack(xs)
+        diff = {key: max(float((X[key][:, j] - Xa[j]).norm() / Xa[j].norm()) for j in range(k)) for key in "bcd"}
+        if not (diff["b"] < 1e-12 and diff["c"] == 0.0 and diff["d"] < 1e-5):
+            sys.exit(f"bench_multi_rhs: k = {k}: columns deviate from the single applications: {diff}")
+        t = {key: [] for key in calls}
+        for _ in range(args.rounds):
+            for key, fn in calls.items():
+                t[key].append(timed(fn, args.reps))
+        med = {key: statistics.median(v) for key, v in t.items()}
+        rec = {"max_rel_diff": diff, "cycle": dict({key: _stats(v) for key, v in t.items()}, a_over_b=med["a"] / med["b"], d_over_b=med["d"] / med["b"],
+                                                    a_over_c=med["a"] / med["c"], a_spread=(max(t["a"]) - min(t["a"])) / med["a"])}
+        line = (f"k = {k}: cycle (a) {med['a']:.3f} ms (spread {rec['cycle']['a_spread']:.3f})  (b) {med['b']:.3f}  (c) {med['c']:.3f}  (d) {med['d']:.3f}  "
+                f"(a)/(b) {med['a'] / med['b']:.2f}  (d)/(b) {med['d'] / med['b']:.2f}")
+        if not args.no_pcg:
+            cgs, cgd = NativeCGSolver(single, single, tol=1e-8, maxsteps=100), NativeCGSolver(double, double, tol=1e-8, maxsteps=100)
+            its = {}
+
+            def pa():
+                its["a"] = []
+                for j in range(k):
+                    xs[j].zero_()
+                    cgs.Solve(bs[j], xs[j])
+                    its["a"].append(cgs.iterations)
+
+            def multi(key, cg, f):
+                def run():
+                    X[key].zero_()
+                    cg.SolveMulti(Bi, X[key], interleaved=True, fuse=f)
+                    its[key] = list(cg.iterations)
+                return run
+
+            pcalls = {"a": pa, "b": multi("b", cgs, word), "c": multi("c", cgs, fuse), "d": multi("d", cgd, fuse)}
+            with torch.cuda.stream(stream):
+                for fn in pcalls.values():
+                    fn()
+            torch.cuda.synchronize()
+            wp = max(float((X["b"][:, j] - xs[j]).norm() / xs[j].norm()) for j in range(k))
+            if not wp < 1e-8 or any(abs(x - y) > 1 for x, y in zip(its["a"], its["b"])):
+                sys.exit(f"bench_multi_rhs: k = {k}: PCG differs: solutions {wp:.3e}, iterations {its}")
+            pt = {key: [] for key in pcalls}
+            for _ in range(args.rounds):
+                for key, fn in pcalls.items():
+                    pt[key].append(timed(fn, args.pcg_reps))
+            pm = {key: statistics.median(v) for key, v in pt.items()}
+            rec["pcg"] = dict({key: _stats(v) for key, v in pt.items()}, iterations=dict(its), max_rel_diff=wp, a_over_b=pm["a"] / pm["b"],
+                              d_over_b=pm["d"] / pm["b"], a_spread=(max(pt["a"]) - min(pt["a"])) / pm["a"])
+            line += f"   pcg (a) {pm['a']:.2f} ms (b) {pm['b']:.2f} (d) {pm['d']:.2f}  (a)/(b) {pm['a'] / pm['b']:.2f}  (d)/(b) {pm['d'] / pm['b']:.2f}  iterations {its}"
+        out["k"][str(k)] = rec
+        print(line, flush=True)
+    path = args.out
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps({"out": path, "a_over_b": {k: v["cycle"]["a_over_b"] for k, v in out["k"].items()}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("nv", nargs="?", type=int, default=None)
@@ -66,7 +174,7 @@ def main():
     ap.add_argument("--commit", default=None)
     ap.add_argument("--down", action="store_true", help="also time the calls with AMGX_MULTI_FUSE_DOWN")
     ap.add_argument("--dia", action="store_true", help="with --down: also time the calls with AMGX_MULTI_FUSE_DOWN_DIA")
-    ap.add_argument("--mat-prec", default="double", choices=["double", "single"])
+    ap.add_argument("--mat-prec", default="double", choices=["double", "single", "single_gs_all", "single_gs"])
     ap.add_argument("--tag", default="", help="suffix of the result file (runs under environment switches)")
     ap.add_argument("--cycle-only-k", type=int, default=0, help="run nothing but REPS multi-vector cycles of this width (for a kernel trace)")
     args = ap.parse_args()
@@ -93,7 +201,9 @@ def main():
     if args.down:
         tag += ("_f32" if args.mat_prec == "single" else "") + (("_" + args.tag) if args.tag else "")
     if args.out is None:
-        if args.down:
+        if args.mat_prec in ("single_gs_all", "single_gs"):
+            args.out = os.path.join(ROOT, "profiles", "r30", f"multi_f32_{args.config}.json")
+        elif args.down:
             args.out = os.path.join(ROOT, "profiles", "r25", f"multi_down_dia_{tag}.json") if args.dia else os.path.join(ROOT, "profiles", "r24", f"multi_down_{tag}.json")
         elif isinstance(fuse, str):
             args.out = os.path.join(ROOT, "profiles", "r21" if fuse == "gs" else "r22", f"multi_gs_{args.config}.json")
@@ -108,6 +218,11 @@ def main():
         H = Hierarchy(Matrix(p.n, p.n, p.bs, p.bs, p.rowptr, p.col, p.val), p.free, p.coords, dim=3, energy=1, max_coarse_size=50,
                       regularize_cmats=0 if rot else 1, spw=1)
     kw = dict(sm_type="cheby", cheb_degree=args.degree) if args.smoother == "cheby" else dict(sm_type="hgs" if args.smoother == "gs" else "jacobi")
+    if args.mat_prec in ("single_gs_all", "single_gs"):
+        want = "single_gs_all" if args.config == "cfg2" else "single_gs"
+        if args.smoother != "gs" or args.mat_prec != want:
+            sys.exit(f"bench_multi_rhs: --mat-prec {args.mat_prec} needs --smoother gs and --config " + ("cfg2" if args.mat_prec == "single_gs_all" else "cfg3 | cfg5"))
+        return _f32(args, H, p, kw, fuse, ks, nv)
     if args.mat_prec != "double":
         kw["mat_prec"] = args.mat_prec
     free0, _ = torch.cuda.mem_get_info()
