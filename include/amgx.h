@@ -81,11 +81,16 @@ enum {
                               /* whose fused down launch reads the symmetric diagonal image, 512-row or box chunks (see below);   */
                               /* never an error.  Without it every call is as before, calls that carry AMGX_MULTI_FUSE_DOWN      */
                               /* included                                                                                        */
-  AMGX_MULTI_FUSE_F32 = 2048  /* accepted wherever AMGX_MULTI_FUSE_GS is; implies nothing and is never an error.  With it a      */
+  AMGX_MULTI_FUSE_F32 = 2048, /* accepted wherever AMGX_MULTI_FUSE_GS is; implies nothing and is never an error.  With it a      */
                               /* Gauss-Seidel level whose sweeps read single-precision images no longer keeps the handle in the   */
                               /* column loop under AMGX_MULTI_FUSE_GS (scalar levels) / AMGX_MULTI_FUSE_GS_BLOCK (2x2 / 3x3 / 6x6    */
                               /* levels), where the multi-vector kernels exist on the float arrays (see below).  Without it     */
                               /* every call is as before                                                                         */
+  AMGX_MULTI_FUSE_DOWN_F32 = 4096 /* accepted wherever AMGX_MULTI_FUSE_DOWN is; implies it and AMGX_MULTI_FUSE_F32 (and nothing  */
+                              /* else: the Gauss-Seidel bits stay the caller's) and admits scalar Gauss-Seidel levels with        */
+                              /* single-precision images to the fused down pass, the local-window form of `rest` included (see    */
+                              /* below); never an error.  Without it every call is as before, calls that carry                    */
+                              /* AMGX_MULTI_FUSE_DOWN | AMGX_MULTI_FUSE_F32 included                                               */
 };
 
 typedef struct amgx_level_desc {
@@ -573,6 +578,20 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  * such a level (amgx_multi_level_note: "single-precision Gauss-Seidel images"); amgx_down_multi with x_given = 0 under
  * AMGX_MULTI_FUSE_DOWN | AMGX_MULTI_FUSE_GS | AMGX_MULTI_FUSE_F32 runs the multi-vector float sweep from zero on groups of 4 and 2
  * columns and then the single-vector residual and restriction per column.
+ * With AMGX_MULTI_FUSE_DOWN_F32 = 4096 (opt-in per call; it implies AMGX_MULTI_FUSE_DOWN and AMGX_MULTI_FUSE_F32 and
+ * nothing else, is never an error and is looked at wherever AMGX_MULTI_FUSE_DOWN is) the refusal "single-precision Gauss-Seidel
+ * images" of the down pass is lifted for a scalar level whose single-vector cycle fuses the residual after the block-hybrid sweep from
+ * zero with the chunk-local restriction, where the level qualifies under AMGX_MULTI_FUSE_F32 and the image that launch reads has the
+ * array the single-vector launch reads (the float array; on the AMGX_GS_F32_WIDE twin the rounded values at fp64 width).  The forms:
+ * "sell" and "sell-win" as under AMGX_MULTI_FUSE_DOWN, on the float array; and, under this flag alone, "sell-lw" (form 5), the
+ * local-window image of `rest` with 2 or 4 lanes per row and 2 or 4 entries of P per thread, where both widths fit
+ * 8 * (W * NV + (512 / lanes) * NV + EPT * 512) bytes of dynamic LDS in 160 KB (W: the longest column list of the level's chunks);
+ * otherwise the level keeps the note "local-window image".  A fused group then runs the multi-vector float sweep from zero and this
+ * launch instead of k single-vector residual + restriction passes; per column the kernels keep the order of additions of the
+ * single-vector float kernels, so a column of amgx_down_multi and of amgx_apply_multi is the same with and without the flag, bit for
+ * bit.  On a handle without single-precision Gauss-Seidel images the flag changes nothing beyond AMGX_MULTI_FUSE_DOWN |
+ * AMGX_MULTI_FUSE_F32 (levels with a local-window image on fp64 handles keep their note); "single-precision Jacobi images",
+ * "multicolour sweep", "block level" and "workgroup size" stay refusals.
  *   amgx_down_multi  : the down stage of a level per column; layout and pointers as in amgx_matvec_multi; B and X have the level's
  *                      size, BC the coarse level's.  The level must be scalar and smoothed, without ghost columns and not
  *                      renumbered.  x_given = 0: X is output -- pre-smoothing from zero, then b_c = P^T (b - A x), the down stage of
@@ -583,7 +602,8 @@ int amgx_gmres(amgx_handle h, const double* b, double* x, double tol, int maxit,
  *                      the multi-vector kernels where the level qualifies (a Gauss-Seidel level with x_given = 0 also needs
  *                      AMGX_MULTI_FUSE_GS for its sweep), and a left-over column takes the single-vector path.
  *   amgx_multi_level_plan: out[0 .. 4] = the down form of the level under `flags` (0 literal, 1 sell, 2 windowed sell; with AMGX_MULTI_FUSE_DOWN_DIA
- *                      also 3 diagonal image on 512-row chunks, 4 diagonal image on box chunks), the mode
+ *                      also 3 diagonal image on 512-row chunks, 4 diagonal image on box chunks; with AMGX_MULTI_FUSE_DOWN_F32 also 5
+ *                      local-window image), the mode
  *                      (0 Jacobi from zero, 1 after a block-hybrid sweep, 2 after Chebyshev), folded way up (0 / 1), single-precision
  *                      image (0 / 1), bytes of LDS of a workgroup on 4 vectors.  All 0 without AMGX_MULTI_FUSE_DOWN.
  *   amgx_multi_level_note: why the level stays literal under `flags`: "local-window image", "diagonal image", "workgroup size",

@@ -284,6 +284,7 @@ AMGX_MULTI_FUSE_GS_BLOCK = 256               # implies both; admits Gauss-Seidel
 AMGX_MULTI_FUSE_DOWN = 512                   # implies nothing; fused groups run the fused down pass where the level qualifies
 AMGX_MULTI_FUSE_DOWN_DIA = 1024              # implies AMGX_MULTI_FUSE_DOWN alone; diagonal-image levels take the fused down pass too
 AMGX_MULTI_FUSE_F32 = 2048                   # implies nothing; Gauss-Seidel levels with single-precision images fuse too (with _GS / _GS_BLOCK)
+AMGX_MULTI_FUSE_DOWN_F32 = 4096              # implies AMGX_MULTI_FUSE_DOWN and AMGX_MULTI_FUSE_F32 alone; scalar Gauss-Seidel levels with float images take the fused down pass
 AMGX_MULTI_MAX = 8
 AMGX_MV_MAX = 32                             # columns of a multi-vector in amgx_mv_gram / amgx_mv_combine
 

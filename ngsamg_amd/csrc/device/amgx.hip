@@ -518,6 +518,14 @@ static DownPlan make_down_plan(const DevLevel& L, const DevRestrict& R, int mode
                            : compact                    ? (int64_t)(R.slice_list.n / down_slices_per_chunk(p.threads))
                                                         : down_expected_chunks(p.family, dia ? L.n : M.n_slices, p.threads, p.lanes);
   need(expected == R.n_chunks, "chunk / slice mismatch");
+  if (p.family == DOWN_FAM_LW) {           // the longest column list of a chunk (what down_nv_lw_lds_bytes sizes the NV launch from)
+    const DevBuf<int32_t>& cp = mode == 1 ? L.gsb.lw_cptr : L.lw_cptr;
+    need((int64_t)cp.n >= (int64_t)R.n_chunks + 1, "chunk / column-list mismatch");
+    std::vector<int32_t> h((size_t)R.n_chunks + 1);
+    HIPCHK(hipMemcpy(h.data(), cp.p, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c + 1 < h.size(); ++c) p.lw_max_list = std::max(p.lw_max_list, (int)(h[c + 1] - h[c]));
+    need(p.lw_max_list <= LW_CAP, "a column list beyond the window capacity");
+  }
   return p;
 }
 
@@ -2440,14 +2448,15 @@ struct Handle {
 
   // down_launch on NV = 2 or 4 interleaved vectors (AMGX_MULTI_FUSE_DOWN): the same plan, the same operands (the
   // vectors of `o` interleaved; dinv of MODE 0 and c of MODE 1 per row), the whole level in one launch.  Which plans have a kernel is
-  // down_nv_ok and, for the diagonal-image families (AMGX_MULTI_FUSE_DOWN_DIA), down_nv_dia_ok (down_plan.hpp).  part_nv: n_slots * NV partial sums of the caller (the multi-vector work space), summed into b_coarse
+  // down_nv_ok, for the diagonal-image families (AMGX_MULTI_FUSE_DOWN_DIA) down_nv_dia_ok and for the local-window family
+  // (AMGX_MULTI_FUSE_DOWN_F32) down_nv_lw_ok (down_plan.hpp).  part_nv: n_slots * NV partial sums of the caller (the multi-vector work space), summed into b_coarse
   template <int NV>
   void down_launch_nv(int l, const DownPlan& p, const DownOps& o, double* part_nv, double* b_coarse) {
     const DevLevel& L = lev[l];
-    if (!down_nv_ok(p, NV) && !down_nv_dia_ok(p, NV)) throw Err("fused multi-vector down pass: the level has no plan for it");
+    if (!down_nv_ok(p, NV) && !down_nv_dia_ok(p, NV) && !down_nv_lw_ok(p, NV)) throw Err("fused multi-vector down pass: the level has no plan for it");
     const DevRestrict& R = p.mode == 1 ? L.RG : L.RF;
     const int grid = p.n_chunks;
-    const DevMatrix& M = down_image(L, p.mode, false);
+    const DevMatrix& M = down_image(L, p.mode, p.family == DOWN_FAM_LW);
     bool miss = false;
     auto pick = [&](auto list, int value, auto&& run) { if (!dispatch(list, value, run)) miss = true; };
     if (grid > 0 && p.family == DOWN_FAM_DIA) {
@@ -2474,14 +2483,33 @@ struct Handle {
           if (p.lanes > 1) { miss = true; return; }
           pick(DownEpt{}, p.ept, [&](auto EPT) { sell(EPT, Int<1>{}); });
         };
-        if constexpr (MODE() == 2) { if (p.f32) return image(M.sell.view32(M.val32.p)); }
+        // (the float image as in down_launch: MODE 2 of a Chebyshev level, MODE 1 on `rest` of a scalar Gauss-Seidel level under
+        //  AMGX_MULTI_FUSE_DOWN_F32; a float A' of MODE 0 never gets here: Multi::level_down refuses the level)
+        if constexpr (MODE() != 0) { if (p.f32) return image(M.sell.view32(M.val32.p)); }
         image(M.sell.view());
       });
+    } else if (grid > 0 && p.family == DOWN_FAM_LW) {
+      // local-window image of `rest` (AMGX_MULTI_FUSE_DOWN_F32; the rule is down_nv_lw_ok): chunks of 512 / lanes rows;
+      // the dynamic LDS was allowed at create time where it exceeds 64 KB (allow_down_nv_lw, build_level.hpp)
+      pick(DownLwLanes{}, p.lanes, [&](auto G) { pick(DownLwEpt{}, p.ept, [&](auto EPT) {
+        auto image = [&](auto view) {
+          using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;       // double / float
+          launch(sell_lw_pre_restrict_nv_kernel<EPT(), G(), 1, NV, V>, grid, DOWN_THREADS, down_nv_lw_lds_bytes(p, NV), stream, M.n_rows, M.n_slices, view,
+                 p.lw_max_list, L.gsb.lw_cptr.p, L.gsb.lw_ccol.p, o.v, o.d, R.chunk_slot.p, R.slot_ptr.p, R.w.p, R.fi.p, part_nv, R.dest.p);
+        };
+        if (p.f32) return image(M.sell.view32(M.val32.p));
+        image(M.sell.view());
+      }); });
     } else if (grid > 0) {
       RestrictMat rv = R.view();
       rv.part = part_nv;
       pick(DownEpt{}, p.ept, [&](auto EPT) {
-        launch(sell_win_pre_restrict_nv_kernel<SELL_WIN, EPT(), 1, NV>, grid, SELL_WIN, 0, stream, M.n_rows, 0, M.sell.view(), M.sell.rowloc.p, o.v, o.d, rv);
+        auto image = [&](auto view) {
+          using V = std::remove_const_t<std::remove_pointer_t<decltype(view.val)>>;       // double / float
+          launch(sell_win_pre_restrict_nv_kernel<SELL_WIN, EPT(), 1, NV, V>, grid, SELL_WIN, 0, stream, M.n_rows, 0, view, M.sell.rowloc.p, o.v, o.d, rv);
+        };
+        if (p.f32) return image(M.sell.view32(M.val32.p));
+        image(M.sell.view());
       });
     }
     if (miss) throw Err("fused multi-vector down pass: no kernel for the plan");

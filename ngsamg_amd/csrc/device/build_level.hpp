@@ -656,6 +656,21 @@ static void jacobi_f32_images(LevelBuild& B) {
   if (L.jp_mask) (wide ? L.jp32_wide : L.jp32) = true;
 }
 
+// The multi-vector form of the local-window down launch (AMGX_MULTI_FUSE_DOWN_F32, sized by down_nv_lw_lds_bytes) holds the window of
+// the longest list for NV columns: more than 64 KB of dynamic LDS has to be allowed per kernel, once -- here, at create time, because a
+// call that carries the bit may be the one a stream capture records.  For both widths, for the value type the launch reads.
+static void allow_down_nv_lw(const DevLevel& L) {
+  const DownPlan& p = L.plan_rg;
+  if (!p.on || p.family != DOWN_FAM_LW) return;
+  for (int nv : values(DownNvWidths{})) dispatch(DownNvWidths{}, nv, [&](auto NV) {
+    if (!down_nv_lw_ok(p, NV()) || down_nv_lw_lds_bytes(p, NV()) <= 65536) return;
+    dispatch(DownLwLanes{}, p.lanes, [&](auto G) { dispatch(DownLwEpt{}, p.ept, [&](auto EPT) {
+      if (p.f32) HIPCHK(hipFuncSetAttribute((const void*)sell_lw_pre_restrict_nv_kernel<EPT(), G(), 1, NV(), float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DOWN_NV_DIA_LDS_MAX));
+      else HIPCHK(hipFuncSetAttribute((const void*)sell_lw_pre_restrict_nv_kernel<EPT(), G(), 1, NV(), double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DOWN_NV_DIA_LDS_MAX));
+    }); });
+  });
+}
+
 // Scalar Gauss-Seidel levels with mat_prec = AMGX_PREC_F32_SCALAR_GS (check_level has refused every other level).  Each
 // sweep image the level's form has -- block-hybrid: gsb.full, fullLW, lowin, rest, restLW; multicolour: gs.sell, lower, upper -- gets a
 // float value array, the stored fp64 values rounded to nearest; index arrays, rowid, slotcolor and the window lists are shared.  dinv,
@@ -1006,6 +1021,7 @@ static Handle* create(const amgx_hierarchy_desc* d, const Knobs& K, int dense_fi
     set_xcd_modes(B);
     alloc_level_vectors(B);
     resolve_paths(B.L);                   // every image of the level is final here; nothing before this line runs a cycle or asks folded()
+    allow_down_nv_lw(B.L);
   }
   // (the levels of a rank-partitioned hierarchy are estimated collectively, on the partitioned operator: amgx_dist_cheb_estimate)
   if (dense_first >= 0) cheb_estimate(*h);

@@ -54,6 +54,7 @@ struct DownPlan {
   bool splittable = false, f32 = false;
   size_t lds_bytes = 0;                 // dynamic LDS (dia-box)
   int64_t box_rows = 0, max_entries = 0; // dia-box: rows of a full box, most entries of P in one box (what the LDS of the NV form holds)
+  int lw_max_list = 0;                  // lw: the longest column list of the level's chunks (<= LW_CAP; what the LDS window of the NV form holds)
 };
 
 // ---- the same launch on NV = 2 or 4 interleaved vectors (AMGX_MULTI_FUSE_DOWN, DESIGN.md 5.18: sell_pre_restrict_nv_kernel,
@@ -99,6 +100,22 @@ constexpr bool down_nv_dia_ok(const DownPlan& p, int nv) {
   if (p.family == DOWN_FAM_DIA) shape = contains(DiaDiags{}, p.diags) && contains(DownEpt{}, p.ept);
   else if (p.family == DOWN_FAM_DIA_BOX) shape = contains(DiaBoxDiags{}, p.diags);
   return shape && down_nv_dia_lds_bytes(p, nv) <= DOWN_NV_DIA_LDS_MAX;
+}
+
+// ---- the local-window launch on NV = 2 or 4 interleaved vectors (AMGX_MULTI_FUSE_DOWN_F32, DESIGN.md 5.23:
+// sell_lw_pre_restrict_nv_kernel in multi_kernels.hpp).  A rule of its own beside down_nv_ok, which keeps refusing the family: the
+// capability has its own opt-in bit.  Built for MODE 1 alone (the residual after a block-hybrid sweep from zero on the local-window
+// image of `rest`), 512 lanes per workgroup, the lanes and EPT of the single-vector family.
+// LDS of the launch, dynamic: the window x[ccol[k]] of the longest list for NV columns, r of the chunk's rows for NV columns, ONE
+// array of products that the columns use in turn (ChunkRestrictNV).  The bound is the 160 KiB of DOWN_NV_DIA_LDS_MAX.
+constexpr size_t down_nv_lw_lds_bytes(const DownPlan& p, int nv) {
+  if (p.lanes <= 0 || p.lw_max_list < 0 || p.ept < 0 || nv < 0) return ~(size_t)0;     // (never a plan of resolve_paths: refused by the bound)
+  return sizeof(double) * ((size_t)p.lw_max_list * (size_t)nv + (size_t)(DOWN_THREADS / p.lanes) * (size_t)nv + (size_t)p.ept * (size_t)DOWN_THREADS);
+}
+constexpr bool down_nv_lw_ok(const DownPlan& p, int nv) {
+  if (!p.on || !contains(DownNvWidths{}, nv) || p.family != DOWN_FAM_LW || p.mode != 1 || p.threads != DOWN_THREADS) return false;
+  if (!contains(DownLwLanes{}, p.lanes) || !contains(DownLwEpt{}, p.ept)) return false;
+  return down_nv_lw_lds_bytes(p, nv) <= DOWN_NV_DIA_LDS_MAX;
 }
 
 // ---- chunk arithmetic.  A chunk is what one workgroup of `threads` lanes owns: threads / 64 slices = threads / lanes rows

@@ -49,7 +49,7 @@ struct MultiState {
   DevBuf<int32_t> kr_active;
   // b, x, k, layout, ldb, ldx, rule in force (0 .. 3; + 4: fused down passes, AMGX_MULTI_FUSE_DOWN on a handle with a level that takes one;
   // + 8: AMGX_MULTI_FUSE_DOWN_DIA on a handle where it changes a level's form or fold; + 16: AMGX_MULTI_FUSE_F32 on a handle where it
-  // changes the decision)
+  // changes the decision; + 32: AMGX_MULTI_FUSE_DOWN_F32 on a handle where it changes a level's form)
   using Key = std::tuple<const double*, double*, int, int, int64_t, int64_t, int>;
   GraphCache<Key> graphs;
 };
@@ -74,9 +74,11 @@ struct Multi {
   Handle& h;
   MultiState& st;
   static constexpr int ALL_FLAGS = MULTI_RULE_FLAGS;                                                   // the flags that widen the rule
-  static constexpr int DOWN_FLAGS = AMGX_MULTI_FUSE_DOWN | AMGX_MULTI_FUSE_DOWN_DIA;                   // (the second implies the first, nothing else)
+  static constexpr int DOWN_FLAGS = AMGX_MULTI_FUSE_DOWN | AMGX_MULTI_FUSE_DOWN_DIA | AMGX_MULTI_FUSE_DOWN_F32;   // (the second implies the first, nothing else)
   static constexpr int CALL_FLAGS = ALL_FLAGS | DOWN_FLAGS | AMGX_MULTI_FUSE_F32;                     // ... and the ones that imply nothing about the rule
-  static constexpr int NOTE_FLAGS = ALL_FLAGS | AMGX_MULTI_FUSE_F32;                                  // what amgx_multi_note looks at
+  static constexpr int NOTE_FLAGS = ALL_FLAGS | AMGX_MULTI_FUSE_F32 | AMGX_MULTI_FUSE_DOWN_F32;       // what amgx_multi_note looks at
+  // AMGX_MULTI_FUSE_DOWN_F32 implies AMGX_MULTI_FUSE_DOWN and AMGX_MULTI_FUSE_F32 and nothing else
+  static constexpr int implied(int fl) { return fl & AMGX_MULTI_FUSE_DOWN_F32 ? fl | AMGX_MULTI_FUSE_DOWN | AMGX_MULTI_FUSE_F32 : fl; }
   const int flags;
   const int fb;                         // the call carries AMGX_MULTI_FUSE_F32: which decision of MultiState is read
   const bool block_flag;                // the call carries AMGX_MULTI_FUSE_GS_BLOCK (which implies the flag below)
@@ -84,10 +86,11 @@ struct Multi {
   const bool fz;                        // this call runs fused groups
   const bool down_flag;                 // the call carries AMGX_MULTI_FUSE_DOWN: modifies the fused groups, implies nothing
   const bool dia_flag;                  // the call carries AMGX_MULTI_FUSE_DOWN_DIA: implies down_flag; diagonal-image levels take the pass too
+  const bool d32_flag;                  // the call carries AMGX_MULTI_FUSE_DOWN_F32: implies down_flag and fb; levels with float Gauss-Seidel images take the pass too
   explicit Multi(Handle& hh, int fl = 0)
-      : h(hh), st(state(hh)), flags(fl), fb(fl & AMGX_MULTI_FUSE_F32 ? 1 : 0), block_flag(fl & AMGX_MULTI_FUSE_GS_BLOCK), gs_flag(multi_asked_rule(fl) >= 2),
-        fz(multi_runs_fused(fl, st.fused[fb])), down_flag(fl & DOWN_FLAGS), dia_flag(fl & AMGX_MULTI_FUSE_DOWN_DIA) {
-    if (down_flag) for (int l = 0; l < h.n_levels(); ++l) dn.push_back(level_down(l, dia_flag));     // once per call
+      : h(hh), st(state(hh)), flags(implied(fl)), fb(flags & AMGX_MULTI_FUSE_F32 ? 1 : 0), block_flag(fl & AMGX_MULTI_FUSE_GS_BLOCK), gs_flag(multi_asked_rule(fl) >= 2),
+        fz(multi_runs_fused(flags, st.fused[fb])), down_flag(fl & DOWN_FLAGS), dia_flag(fl & AMGX_MULTI_FUSE_DOWN_DIA), d32_flag(fl & AMGX_MULTI_FUSE_DOWN_F32) {
+    if (down_flag) for (int l = 0; l < h.n_levels(); ++l) dn.push_back(level_down(l, dia_flag, d32_flag));     // once per call
   }
   int rule() const { return multi_rule_in_force(flags, st.fused[fb]); }   // (part of the graph key)
   const std::string& note() const { return st.why[fb][rule()]; }
@@ -169,7 +172,11 @@ struct Multi {
   struct DownNv { int form = 0, mode = 0; bool fold = false, f32 = false; const DownPlan* plan = nullptr; const char* why = ""; };
   std::vector<DownNv> dn;               // level_down of every level under this call's flags (empty without AMGX_MULTI_FUSE_DOWN)
   DownNv level_down(int l) const { return l >= 0 && l < (int)dn.size() ? dn[l] : DownNv(); }
-  DownNv level_down(int l, bool dia) const {
+  // AMGX_MULTI_FUSE_DOWN_F32 (`d32`): a Gauss-Seidel level with single-precision images whose single-vector cycle runs
+  // plan_rg takes the pass too, where Handle::multi_f32_ok holds and the image the launch reads has the array the single-vector launch
+  // reads (the float array where the plan says f32, the rounded values at fp64 width on the AMGX_GS_F32_WIDE twin); form 5: the
+  // local-window image of `rest` (rule: down_nv_lw_ok), admitted on such levels alone.
+  DownNv level_down(int l, bool dia, bool d32) const {
     DownNv d;
     if (!down_flag || l < 0 || l + 1 >= h.n_levels()) return d;
     const MultiLevelFacts& f = st.facts[fb][l]; // (the first two refusals are the fusion rule's, on the same facts)
@@ -177,7 +184,15 @@ struct Multi {
     const DevLevel& V = h.lev[l];
     if (f.bs != 1) { d.why = "block level"; return d; }
     if (f.jacobi_f32) { d.why = "single-precision Jacobi images"; return d; }     // (the NV kernels read fp64 images)
-    if (f.sgs_f32) { d.why = "single-precision Gauss-Seidel images"; return d; }  // (... and the fp64 values of `rest` are released)
+    if (f.sgs_f32) {                                                              // (... and the fp64 values of `rest` are released)
+      // a fused pass reads the array the single-vector pass of the same handle reads: lifted for plan_rg under the bit, nowhere else
+      bool lifted = d32 && f.f32_ok && V.sm_type == AMGX_SM_GS && V.paths.sweep == SWEEP_GSB && V.paths.down == DOWN_GSB && V.plan_rg.on && Handle::split_identity(V, 2);
+      if (lifted) {
+        const DevMatrix& M = down_image(V, 1, V.plan_rg.family == DOWN_FAM_LW);
+        lifted = M.fmt == FMT_SELL && (V.plan_rg.f32 ? M.has32() : (V.sgs32_wide && M.sell.val.p != nullptr));
+      }
+      if (!lifted) { d.why = "single-precision Gauss-Seidel images"; return d; }
+    }
     const DownPlan* p = nullptr;
     if (f.square && !f.permuted && !st.facts[fb][l + 1].permuted && f.plain) {
       if (V.sm_type == AMGX_SM_GS) {
@@ -190,7 +205,12 @@ struct Multi {
       }
     }
     if (!p) { d.why = "no chunk-local restriction"; return d; }
-    if (p->family == DOWN_FAM_LW) { d.why = "local-window image"; return d; }
+    d.plan = p;                                                                   // (also of a level that stays literal: amgx_multi_level_plan reports its shape)
+    if (p->family == DOWN_FAM_LW) {                                               // (on levels with float Gauss-Seidel images under their bit alone)
+      if (!d32 || !f.sgs_f32 || !down_nv_lw_ok(*p, 2) || !down_nv_lw_ok(*p, 4)) { d.why = "local-window image"; return d; }
+      d.form = 5; d.mode = p->mode; d.f32 = p->f32; d.plan = p;
+      return d;
+    }
     if (p->family == DOWN_FAM_DIA || p->family == DOWN_FAM_DIA_BOX) {
       if (!dia || !down_nv_dia_ok(*p, 2) || !down_nv_dia_ok(*p, 4)) { d.why = "diagonal image"; return d; }
       d.form = p->family == DOWN_FAM_DIA ? 3 : 4;
@@ -217,9 +237,15 @@ struct Multi {
   bool dia_active() const {
     if (!dia_flag || !fz) return false;
     for (int l = 0; l < top(); ++l) {
-      const DownNv a = level_down(l), b = level_down(l, false);
+      const DownNv a = level_down(l), b = level_down(l, false, d32_flag);
       if (a.form != b.form || a.fold != b.fold) return true;
     }
+    return false;
+  }
+  // ... and AMGX_MULTI_FUSE_DOWN_F32 the form of at least one of its levels (part of the key on such handles only)
+  bool d32_active() const {
+    if (!d32_flag || !fz) return false;
+    for (int l = 0; l < top(); ++l) if (level_down(l).form != level_down(l, dia_flag, false).form) return true;
     return false;
   }
   template <class Ops>
@@ -525,7 +551,7 @@ struct Multi {
     const MultiView vb(B, k, ldb, interleaved), vx(X, k, ldx, interleaved);
     // only the fused path is captured as a whole; the column loop replays the single-vector graphs of run_cycle
     if (!fz || !(h.use_graph && graph_ok) || h.stream == nullptr) { apply_body(k, vb, vx, graph_ok, false); return; }
-    const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx, rule() + (down_active() ? 4 : 0) + (dia_active() ? 8 : 0) + (f32_active() ? 16 : 0)};
+    const MultiState::Key key{B, X, k, interleaved ? 1 : 0, interleaved ? 0 : ldb, interleaved ? 0 : ldx, rule() + (down_active() ? 4 : 0) + (dia_active() ? 8 : 0) + (f32_active() ? 16 : 0) + (d32_active() ? 32 : 0)};
     if (!st.graphs.has(key)) {
       int32_t wd[MULTI_MAX];
       const int ng = multi_groups(k, true, wd);
@@ -598,7 +624,8 @@ struct Multi {
     // AMGX_MULTI_FUSE_F32: a Gauss-Seidel level with single-precision images keeps the literal stages (level_down),
     // but with AMGX_MULTI_FUSE_GS its sweep from zero runs on the group; residual and restriction follow per column
     const MultiLevelFacts& f = st.facts[fb][level];
-    const bool sweep32 = !x_given && gs && down_flag && gs_flag && f.f32_ok && f.sweep_ok && !f.permuted && !f.empty;
+    // (AMGX_MULTI_FUSE_DOWN_F32, DESIGN.md 5.23: where the level has a form under the call's flags, the NV down launch comes first)
+    const bool sweep32 = !x_given && gs && down_flag && gs_flag && f.f32_ok && f.sweep_ok && !f.permuted && !f.empty && !dn.form;
     const bool nv = sweep32 || (dn.form != 0 && (x_given || !gs || gs_flag));
     const MultiArg a[3] = {{MULTI_ARG_IN, MultiView(B, k, ldb, interleaved), n, &st.col_in, col, &st.sm_b},
                            {x_given ? MULTI_ARG_IN : MULTI_ARG_OUT, MultiView(X, k, ldx, interleaved), n, &st.col_out, col, &st.sm_x},
@@ -826,8 +853,14 @@ int amgx_multi_level_plan(amgx_handle hh, int level, int flags, int32_t* out, in
     if (!out || n_out < 1) throw amgx::Err("amgx_multi_level_plan: bad arguments");
     amgx::Multi M(h, flags & amgx::Multi::CALL_FLAGS);
     const amgx::Multi::DownNv d = M.level_down(level);
-    const int32_t v[5] = {d.form, d.form ? d.mode : 0, d.fold ? 1 : 0, d.f32 ? 1 : 0, d.form >= 3 ? (int32_t)amgx::down_nv_dia_lds_bytes(*d.plan, 4) : d.form ? (int32_t)amgx::down_nv_lds_bytes(*d.plan, 4) : 0};
+    const int32_t v[5] = {d.form, d.form ? d.mode : 0, d.fold ? 1 : 0, d.f32 ? 1 : 0,
+                          d.form == 5  ? (int32_t)amgx::down_nv_lw_lds_bytes(*d.plan, 4)
+                          : d.form >= 3 ? (int32_t)amgx::down_nv_dia_lds_bytes(*d.plan, 4) : d.form ? (int32_t)amgx::down_nv_lds_bytes(*d.plan, 4) : 0};
     for (int i = 0; i < std::min(n_out, 5); ++i) out[i] = v[i];
+    // out[5 .. 7]: the shape of the level's fused down plan, whether or not a fused group takes it: lanes per row, entries of P per
+    // thread, the longest column list of a local-window chunk (all 0 without a plan)
+    const int32_t shape[3] = {d.plan ? d.plan->lanes : 0, d.plan ? d.plan->ept : 0, d.plan ? d.plan->lw_max_list : 0};
+    for (int i = 5; i < std::min(n_out, 8); ++i) out[i] = shape[i - 5];
   });
 }
 

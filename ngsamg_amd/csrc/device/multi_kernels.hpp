@@ -148,9 +148,11 @@ __device__ __forceinline__ void sell_pairs_nv(int np, const V* __restrict__ vb, 
 
 // acc[j] = (SELL row of the slice with pointers sp0, sp1; this lane) . column j of x          (sell_row_dot_sp for NV vectors)
 // XD: xd = NV + 1 doubles of the caller, see sell_consume_nv
+// x32 (optional): the interleaved vector that slices in the 32-bit encoding gather from (local-window images: 16-bit slices index the
+// NV-wide LDS window x, 32-bit slices -- chunks whose window would not fit -- carry global columns), as in sell_row_dot_sp
 template <int NV, class V, bool XD = false>
 __device__ __forceinline__ void sell_row_dot_nv_sp(const SellMatT<V>& M, int64_t sp0, int64_t sp1, int lane, int row, const double* __restrict__ x,
-                                                   double (&acc)[NV], double* xd = nullptr) {
+                                                   double (&acc)[NV], double* xd = nullptr, const double* __restrict__ x32 = nullptr) {
   const int64_t base = sp0 & ~(int64_t)63;
   const int w = (int)(((sp1 & ~(int64_t)63) - base) >> 6);
   const int np = w >> 1;
@@ -168,12 +170,14 @@ __device__ __forceinline__ void sell_row_dot_nv_sp(const SellMatT<V>& M, int64_t
     vs = ld_nt(vb + o);
     cs = c16 ? (int)ld_nt(M.col16 + base + o) : ld_nt(M.col32 + base + o);
   }
+  const double* __restrict__ xw32 = x32 ? x32 : x;
   if (c16) sell_pairs_nv<true, NV, V, SELL_BATCH, XD>(np, vb, M.col16 + base, cb, r0, lane, x, acc0, acc1, xd);
-  else sell_pairs_nv<false, NV, V, SELL_BATCH, XD>(np, vb, M.col32 + base, nullptr, 0, lane, x, acc0, acc1, xd);
+  else sell_pairs_nv<false, NV, V, SELL_BATCH, XD>(np, vb, M.col32 + base, nullptr, 0, lane, xw32, acc0, acc1, xd);
   if (w & 1) {
     const int c = c16 ? r0 + cb[w - 1] + cs : cs;
     double xs[NV];
-    ldv<NV>(x + (int64_t)c * NV, xs);
+    if (c16) ldv<NV>(x + (int64_t)c * NV, xs);             // (two loads, not one through a selected pointer: x may be LDS, xw32 global)
+    else ldv<NV>(xw32 + (int64_t)c * NV, xs);
     if constexpr (XD) {
       if (np == 0) {
 #pragma unroll
@@ -393,8 +397,9 @@ __global__ __launch_bounds__(FUSED_BLOCK) void sell_pre_restrict_nv_kernel(int64
 // sell_win_pre_restrict_kernel<WB, EPT, 1> on NV interleaved vectors: the residual after a block-hybrid sweep from zero on the
 // windowed image of A_rest, r = c .* x - A_rest x (b = the swept x, interleaved; dinv = c per row), row sums through LDS back to
 // natural order as in sell_win_spmm_kernel.  (MODE 0 of the windowed family is the AMGX_APRE_WINDOW A/B hook: not built.)
-template <int WB, int EPT, int MODE, int NV>
-__global__ __launch_bounds__(WB) void sell_win_pre_restrict_nv_kernel(int64_t n_rows, int win0, SellMat M, const uint16_t* __restrict__ rowloc,
+// V = float: the single-precision image of a windowed `rest` (AMGX_MULTI_FUSE_DOWN_F32)
+template <int WB, int EPT, int MODE, int NV, class V = double>
+__global__ __launch_bounds__(WB) void sell_win_pre_restrict_nv_kernel(int64_t n_rows, int win0, SellMatT<V> M, const uint16_t* __restrict__ rowloc,
                                                                       const double* __restrict__ b, const double* __restrict__ dinv,
                                                                       RestrictMat R) {
   static_assert(MODE == 1, "the windowed multi-vector down kernel is built for MODE 1 alone");
@@ -426,6 +431,97 @@ __global__ __launch_bounds__(WB) void sell_win_pre_restrict_nv_kernel(int64_t n_
   for (int j = 0; j < NV; ++j) buf[threadIdx.x * NV + j] = r[j];      // (same thread, same entries: the residuals replace the row sums)
   __syncthreads();
   cr.reduce(buf, pr, R);
+}
+
+// LdsWindow for NV interleaved vectors: xw[k * NV + j] = src[ccol[k0 + k] * NV + j] for the listed columns of unit c.  request()
+// issues the NV-wide loads into registers and consumes nothing, publish() writes them to LDS (every thread takes part, the caller's
+// barrier follows).  wcap: the doubles-per-column capacity of the caller's window (the longest list of the level, DownPlan::lw_max_list):
+// no list is longer, the bound only keeps a damaged list from writing past the window.
+template <int CAP, int TB, int NV>
+struct LdsWindowNV {
+  static constexpr int NQ = (CAP + TB - 1) / TB;
+  int k0, k1;
+  double xv[NQ][NV];
+  __device__ __forceinline__ void request(int c, int wcap, const int32_t* __restrict__ cptr, const int32_t* __restrict__ ccol, const double* __restrict__ src) {
+    k0 = cptr[c]; k1 = cptr[c + 1];
+    if (k1 - k0 > wcap) k1 = k0 + wcap;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int k = k0 + threadIdx.x + q * TB;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) xv[q][j] = 0.0;
+      if (k < k1) ldv<NV>(src + (int64_t)ccol[k] * NV, xv[q]);
+    }
+  }
+  __device__ __forceinline__ void publish(double* xw) const {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int k = threadIdx.x + q * TB;
+      if (k0 + k < k1) stv<NV>(xw + k * NV, xv[q]);
+    }
+  }
+};
+
+// sell_lw_pre_restrict_kernel<EPT, G, 1, V> on NV interleaved vectors (AMGX_MULTI_FUSE_DOWN_F32): the residual after a
+// block-hybrid sweep from zero on the local-window image of A_rest, r = c .* x - A_rest x (b = the swept x, interleaved; dinv = c per
+// row).  The window holds the chunk's listed columns of x for all NV columns, staged once; 16-bit slices gather NV-wide from it,
+// 32-bit slices (chunks beyond the capacity) from global memory.  Per column the pair order of sell_row_dot_sp and the tree of
+// lane_group_sum<G>.  Dynamic LDS (down_nv_lw_lds_bytes, down_plan.hpp): [wcap * NV] the window | [512 / G * NV] r | [EPT * 512] the
+// products of one column at a time.  V = float: the single-precision image; the AMGX_GS_F32_WIDE twin runs V = double on its rounded
+// values.  (MODE 0 of the family, the Jacobi pass on A', is not built.)
+template <int EPT, int G, int MODE, int NV, class V = double>
+__global__ __launch_bounds__(512) void sell_lw_pre_restrict_nv_kernel(int64_t n_rows, int n_slices, SellMatT<V> M, int wcap,
+                                                                      const int32_t* __restrict__ lw_cptr, const int32_t* __restrict__ lw_ccol,
+                                                                      const double* __restrict__ b, const double* __restrict__ dinv,
+                                                                      const int32_t* __restrict__ chunk_slot, const int32_t* __restrict__ slot_ptr,
+                                                                      const double* __restrict__ w, const uint16_t* __restrict__ fi,
+                                                                      double* __restrict__ part_nv, const int32_t* __restrict__ dest) {
+  static_assert(MODE == 1, "the local-window multi-vector down kernel is built for MODE 1 alone");
+  constexpr int FB = 512;
+  constexpr int ROWS = FB / G;
+  const RestrictMat R{chunk_slot, slot_ptr, w, fi, part_nv, dest};
+  extern __shared__ __attribute__((aligned(16))) double lw_nv_lds[];
+  double* const xw = lw_nv_lds;
+  double* const rl = xw + (int64_t)wcap * NV;
+  double* const pr = rl + ROWS * NV;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int c = sell_unit(M);
+  const int s = __builtin_amdgcn_readfirstlane(c * (FB / WAVE) + (threadIdx.x >> 6));
+  const int row = s * (WAVE / G) + lane / G;
+  const int lrow = (threadIdx.x >> 6) * (WAVE / G) + lane / G;
+  const bool writer = (lane % G) == 0;
+  // the window and the restriction data: all loads of the prologue are requested before anything is consumed
+  LdsWindowNV<LW_CAP, FB, NV> win;
+  win.request(c, wcap, lw_cptr, lw_ccol, b);
+  const bool has_slice = s < n_slices;
+  const int64_t sp0 = has_slice ? M.slice_ptr[s] : 0, sp1 = has_slice ? M.slice_ptr[s + 1] : 0;
+  ChunkRestrictNV<FB, EPT, NV> cr;
+  cr.request(c, R);
+  double bi[NV], di = 0.0;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) bi[j] = 0.0;
+  if (writer && has_slice && row < n_rows) { ldv<NV>(b + (int64_t)row * NV, bi); di = dinv[row]; }
+  win.publish(xw);
+  __syncthreads();
+  double r[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) r[j] = 0.0;
+  if (has_slice) {
+    double acc[NV];
+    sell_row_dot_nv_sp<NV, V>(M, sp0, sp1, lane, 0, xw, acc, nullptr, b);   // 16-bit slices: indices into the window; 32-bit: global columns
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] = lane_group_sum<G>(acc[j]);
+    if (writer && row < n_rows) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) r[j] = di * bi[j] - acc[j];
+    }
+  }
+  if (writer) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) rl[lrow * NV + j] = r[j];
+  }
+  __syncthreads();
+  cr.reduce(rl, pr, R);
 }
 
 // ---- the diagonal-image down kernels on NV interleaved vectors (AMGX_MULTI_FUSE_DOWN_DIA) ----------------------

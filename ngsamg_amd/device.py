@@ -290,13 +290,16 @@ def check_fuse(fuse):
     "down_dia", "gs+down_dia", "gs_block+down_dia" -> the bits of "down", "gs+down", "gs_block+down" | AMGX_MULTI_FUSE_DOWN_DIA (levels
     with a diagonal image take the fused down pass too, and such Jacobi levels the folded way up, DESIGN.md 5.19);
     "gs+f32", "gs_block+f32", "gs+down+f32", "gs_block+down+f32" -> the bits of the word before "+f32" | AMGX_MULTI_FUSE_F32 (Gauss-Seidel
-    levels with single-precision images fuse too, through the multi-vector sweeps on the float arrays)"""
+    levels with single-precision images fuse too, through the multi-vector sweeps on the float arrays, DESIGN.md 5.22);
+    "gs+down_f32", "gs_block+down_f32" -> the bits of "gs+down+f32", "gs_block+down+f32" | AMGX_MULTI_FUSE_DOWN_F32 (scalar Gauss-Seidel
+    levels with single-precision images take the fused down pass too, the local-window form of `rest` included)"""
     if isinstance(fuse, str) and fuse in _FUSE_WORDS:
         return _FUSE_WORDS[fuse]
     if not isinstance(fuse, (bool, np.bool_)):
         raise NgsAMGError(f"fuse: need True, False, \"gs\", \"gs_block\", \"down\", \"gs+down\", \"gs_block+down\", "
                           f"\"down_dia\", \"gs+down_dia\" or \"gs_block+down_dia\", got {fuse!r}"
-                          f" (or, with single-precision Gauss-Seidel images, \"gs+f32\", \"gs_block+f32\", \"gs+down+f32\", \"gs_block+down+f32\")")
+                          f" (or, with single-precision Gauss-Seidel images, \"gs+f32\", \"gs_block+f32\", \"gs+down+f32\", \"gs_block+down+f32\","
+                          f" \"gs+down_f32\", \"gs_block+down_f32\")")
     return _lib.AMGX_MULTI_FUSE if fuse else 0
 
 
@@ -315,6 +318,9 @@ _FUSE_WORDS["gs_block+down_dia"] = _FUSE_WORDS["gs_block+down"] | _lib.AMGX_MULT
 for _w in ("gs", "gs_block", "gs+down", "gs_block+down"):
     _FUSE_WORDS[_w + "+f32"] = _FUSE_WORDS[_w] | _lib.AMGX_MULTI_FUSE_F32
 del _w
+# (AMGX_MULTI_FUSE_DOWN_F32 implies AMGX_MULTI_FUSE_DOWN and AMGX_MULTI_FUSE_F32: the words carry the three bits; the Gauss-Seidel bits are the word's)
+_FUSE_WORDS["gs+down_f32"] = _FUSE_WORDS["gs+down+f32"] | _lib.AMGX_MULTI_FUSE_DOWN_F32
+_FUSE_WORDS["gs_block+down_f32"] = _FUSE_WORDS["gs_block+down+f32"] | _lib.AMGX_MULTI_FUSE_DOWN_F32
 
 
 def hierarchy_desc(hierarchy, sm_type="gs", omega=0.9, sm_steps=1, sm_symm=False, mg_cycle="V", clev="inv", device=0,
@@ -556,7 +562,9 @@ class DeviceAMGMatrix:
         fuse="down_dia", "gs+down_dia", "gs_block+down_dia" (AMGX_MULTI_FUSE_DOWN_DIA as well): levels with a diagonal image qualify
         too, and a Jacobi level that takes the pass runs the way up as x = z + Q x_c.
         fuse="gs+f32", "gs_block+f32", "gs+down+f32", "gs_block+down+f32" (AMGX_MULTI_FUSE_F32 as well): Gauss-Seidel levels with
-        single-precision images (mat_prec="single_gs_all" / "single_gs") run fused too, on the float arrays."""
+        single-precision images (mat_prec="single_gs_all" / "single_gs") run fused too, on the float arrays.
+        fuse="gs+down_f32", "gs_block+down_f32" (AMGX_MULTI_FUSE_DOWN_F32 as well): the scalar levels of such a handle take the fused
+        down pass on their float `rest` image too (sell, sell-win and the local-window form "sell-lw": multi_level_plan)."""
         ff = check_fuse(fuse)
         n = self.sizes[0]
         k, (ab, ax), (lb, lx), dev = check_multi((B, X), (n, n), interleaved, ("B", "X"))
@@ -585,20 +593,25 @@ class DeviceAMGMatrix:
                 "note": note.decode()}
 
     _LEVEL_PLAN_FORMS = ("literal", "sell", "sell-win", "dia", "dia-box")
+    _LEVEL_PLAN_FORMS_ALL = _LEVEL_PLAN_FORMS + ("sell-lw",)                 # form 5: under AMGX_MULTI_FUSE_DOWN_F32 alone
 
     def multi_level_plan(self, level, fuse=False):
         """the down pass of one level in a fused group of a call that carries fuse= (amgx_multi_level_plan): "form" ("literal", "sell",
-        "sell-win", or with a "..._dia" word "dia" / "dia-box"), "mode" (0 Jacobi from zero, 1 after a block-hybrid sweep, 2 after Chebyshev), "folded_up", "float_image",
-        "lds_bytes" (per workgroup on 4 vectors) and "note", the reason a level stays literal ("" when it does not)"""
+        "sell-win", with a "..._dia" word "dia" / "dia-box", with a "...+down_f32" word on a level with single-precision Gauss-Seidel
+        images "sell-lw"), "mode" (0 Jacobi from zero, 1 after a block-hybrid sweep, 2 after Chebyshev), "folded_up", "float_image" (the launch
+        reads a float array), "lds_bytes" (per workgroup on 4 vectors) and "note", the reason a level stays literal ("" when it does not);
+        "lanes", "ept" and "lw_max_list": lanes per row, entries of P per thread and the longest column list of a local-window chunk of
+        the level's fused down plan, whether or not a fused group takes it (0 without a plan or without a "down" word)"""
         ff = check_fuse(fuse)
         if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
             raise NgsAMGError(f"multi_level_plan: level must be an integer, got {level!r}")
         self._size(int(level))
-        out = (C.c_int32 * 5)()
-        self._ck(self._lib.amgx_multi_level_plan(self._h, int(level), ff, out, 5))
+        out = (C.c_int32 * 8)()
+        self._ck(self._lib.amgx_multi_level_plan(self._h, int(level), ff, out, 8))
         note = self._lib.amgx_multi_level_note(self._h, int(level), ff) or b""
-        return {"form": self._LEVEL_PLAN_FORMS[int(out[0])], "mode": int(out[1]), "folded_up": bool(out[2]), "float_image": bool(out[3]),
-                "lds_bytes": int(out[4]), "out": [int(v) for v in out], "note": note.decode()}
+        return {"form": self._LEVEL_PLAN_FORMS_ALL[int(out[0])],"mode": int(out[1]), "folded_up": bool(out[2]), "float_image": bool(out[3]),
+                "lds_bytes": int(out[4]), "out": [int(v) for v in out[:5]], "note": note.decode(),
+                "lanes": int(out[5]), "ept": int(out[6]), "lw_max_list": int(out[7])}
 
     def DownMulti(self, level, B, X=None, x_given=False, interleaved=False, fuse=False):
         """the down stage of a level per column (amgx_down_multi); returns (X, BC).  B: (k, n_level), or (n_level, k) with
@@ -606,7 +619,8 @@ class DeviceAMGMatrix:
         A X[j]) -- the down stage of the V-cycle, X holds z on a level with the folded prolongation.  x_given=True: X is the
         iterate after the level's pre-smoothing and only the residual + restriction half runs.  fuse="down" / "gs+down": groups of 4
         and 2 columns run the multi-vector kernels where the level qualifies (multi_level_plan); a column is the same bit for
-        bit either way."""
+        bit either way.  fuse="gs+down_f32": so do the scalar Gauss-Seidel levels of a handle with single-precision images, on the
+        float array the single-vector launch reads."""
         ff = check_fuse(fuse)
         if not isinstance(x_given, (bool, np.bool_)):
             raise NgsAMGError(f"DownMulti: x_given must be True or False, got {x_given!r}")

@@ -34,7 +34,14 @@ smoothed levels under both words; the result goes to profiles/r25/.
 single-precision Gauss-Seidel images, fused only under AMGX_MULTI_FUSE_F32 as well.  Per round (a) k single
 applications on it, (b) one multi call with fuse="gs+f32" / "gs_block+f32", (c) the same call without "+f32" (the column loop), (d) the
 fused call on a double handle created in the same process; the same for amgx_pcg_multi with the iteration counts of each.  Before any
-time counts, (b) equals (a) to 1e-12 and (c) equals (a) bit for bit.  The result goes to profiles/r30/."""
+time counts, (b) equals (a) to 1e-12 and (c) equals (a) bit for bit.  The result goes to profiles/r30/.
+
+--down-f32 (with --smoother gs --config cfg2 --mat-prec single_gs_all): two more calls per round on the single-precision handle, (e) =
+(b) with AMGX_MULTI_FUSE_DOWN as well (fuse="gs+down+f32": the levels keep the literal stages) and (f) = the call with
+AMGX_MULTI_FUSE_DOWN_F32 (fuse="gs+down_f32"), alternating with (a) .. (d) in the same process; the same for
+amgx_pcg_multi.  The yardstick of (f) is (b) of the same round, and (d) stands beside it.  Every line prints multi_level_plan per level
+under the new word; the columns of (e) and (f) are compared with (a) before any time counts.  Per level 0 .. 2 the down stage alone is
+timed through DownMulti (the column loop, "gs+down+f32", "gs+down_f32").  The result goes to profiles/r31/."""
 import argparse
 import json
 import os
@@ -68,6 +75,9 @@ def _f32(args, H, p, kw, fuse, ks, nv):
     single = DeviceAMGMatrix(H, device=0, mat_prec=args.mat_prec, **kw)
     double = DeviceAMGMatrix(H, device=0, **kw)
     word = fuse + "+f32"
+    d32 = args.down_f32
+    word_e, word_f = fuse + "+down+f32", fuse + "+down_f32"
+    extra = "ef" if d32 else ""
     plan, old = single.multi_plan(4, fuse=word), single.multi_plan(4, fuse=fuse)
     if plan["fused"] != 1 or old["fused"] != 0 or double.multi_plan(4, fuse=fuse)["fused"] != 1:
         sys.exit(f"bench_multi_rhs: plans are not (fused, column loop, fused): {plan} {old}")
@@ -90,22 +100,52 @@ def _f32(args, H, p, kw, fuse, ks, nv):
            "n": int(n), "levels": H.n_levels, "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps,
            "pcg_reps": args.pcg_reps, "note_without_f32": old["note"],
            "float_levels": [l for l in range(H.n_levels) if single.level_extra(l)["gs_f32"]], "k": {}}
+    plans = ""
+    if d32:
+        out["fuse_down_f32"] = word_f
+        out["level_plans"] = [dict(single.multi_level_plan(l, word_f), rows=int(single.sizes[l]), gs_down=single.level_paths(l)["gs_down"]) for l in range(H.n_levels - 1)]
+        plans = "   levels under " + word_f + ": " + " ".join(
+            f"{l}:{q['form']}" + (f"/f32 lanes {q['lanes']} ept {q['ept']} W {q['lw_max_list']} lds {q['lds_bytes']}" if q["form"] != "literal" else
+                                  f"({q['note']}" + (f", W {q['lw_max_list']}" if q["lw_max_list"] else "") + ")") for l, q in enumerate(out["level_plans"]))
+        # the down stage alone, levels 0 .. 2, k = 2 and 4: the column loop, the float sweep + per-column residual, the NV launch
+        out["down_levels"] = {}
+        for l in range(min(3, H.n_levels - 1)):
+            nl = int(single.sizes[l])
+            for k in (2, 4):
+                Bl = torch.from_numpy(np.random.default_rng(l).standard_normal((nl, k))).cuda()
+                Xl = torch.empty_like(Bl)
+                res, tl = {}, {w: [] for w in ("loop", word_e, word_f)}
+                for w in tl:
+                    res[w] = single.DownMulti(l, Bl, Xl, interleaved=True, fuse=False if w == "loop" else w)[1].clone()
+                torch.cuda.synchronize()
+                if not (torch.equal(res[word_e], res["loop"]) and torch.equal(res[word_f], res["loop"])):
+                    sys.exit(f"bench_multi_rhs: DownMulti of level {l}, k = {k}: the words do not give the column loop's bits")
+                for _ in range(args.rounds):
+                    for w in tl:
+                        tl[w].append(timed(lambda: single.DownMulti(l, Bl, Xl, interleaved=True, fuse=False if w == "loop" else w), args.reps))
+                md = {w: statistics.median(v) for w, v in tl.items()}
+                out["down_levels"][f"{l}/{k}"] = {w: _stats(v) for w, v in tl.items()}
+                print(f"down stage level {l} ({nl} rows, {out['level_plans'][l]['form']}) k = {k}: column loop {md['loop']:.3f} ms  {word_e} {md[word_e]:.3f}  {word_f} {md[word_f]:.3f}"
+                      f"  ({word_e})/({word_f}) {md[word_e] / md[word_f]:.2f}", flush=True)
     for k in ks:
         B = rng.standard_normal((k, n)) * pfree
         bs = [torch.from_numpy(np.ascontiguousarray(B[j])).cuda() for j in range(k)]
         xs = [torch.empty_like(b) for b in bs]
         Bi = torch.from_numpy(np.ascontiguousarray(B.T)).cuda()
-        X = {key: torch.full_like(Bi, float("nan")) for key in "bcd"}
+        X = {key: torch.full_like(Bi, float("nan")) for key in "bcd" + extra}
         calls = {"a": lambda: [single.Mult(bs[j], xs[j]) for j in range(k)],
                  "b": lambda: single.MultMulti(Bi, X["b"], interleaved=True, fuse=word),
                  "c": lambda: single.MultMulti(Bi, X["c"], interleaved=True, fuse=fuse),
                  "d": lambda: double.MultMulti(Bi, X["d"], interleaved=True, fuse=fuse)}
+        if d32:
+            calls["e"] = lambda: single.MultMulti(Bi, X["e"], interleaved=True, fuse=word_e)
+            calls["f"] = lambda: single.MultMulti(Bi, X["f"], interleaved=True, fuse=word_f)
         for fn in calls.values():
             timed(fn, 3)
         torch.cuda.synchronize()
         Xa = torch.stack(xs)
-        diff = {key: max(float((X[key][:, j] - Xa[j]).norm() / Xa[j].norm()) for j in range(k)) for key in "bcd"}
-        if not (diff["b"] < 1e-12 and diff["c"] == 0.0 and diff["d"] < 1e-5):
+        diff = {key: max(float((X[key][:, j] - Xa[j]).norm() / Xa[j].norm()) for j in range(k)) for key in "bcd" + extra}
+        if not (diff["b"] < 1e-12 and diff["c"] == 0.0 and diff["d"] < 1e-5 and all(diff[key] < 1e-12 for key in extra)):
             sys.exit(f"bench_multi_rhs: k = {k}: columns deviate from the single applications: {diff}")
         t = {key: [] for key in calls}
         for _ in range(args.rounds):
@@ -116,6 +156,11 @@ def _f32(args, H, p, kw, fuse, ks, nv):
                                                     a_over_c=med["a"] / med["c"], a_spread=(max(t["a"]) - min(t["a"])) / med["a"])}
         line = (f"k = {k}: cycle (a) {med['a']:.3f} ms (spread {rec['cycle']['a_spread']:.3f})  (b) {med['b']:.3f}  (c) {med['c']:.3f}  (d) {med['d']:.3f}  "
                 f"(a)/(b) {med['a'] / med['b']:.2f}  (d)/(b) {med['d'] / med['b']:.2f}")
+        if d32:
+            rec["cycle"].update(a_over_f=med["a"] / med["f"], b_over_f=med["b"] / med["f"], e_over_f=med["e"] / med["f"], d_over_f=med["d"] / med["f"],
+                                b_over_f_rounds=[x / y for x, y in zip(t["b"], t["f"])])
+            line += (f"  (e) {med['e']:.3f}  (f) {med['f']:.3f}  (a)/(f) {med['a'] / med['f']:.2f}  (b)/(f) {med['b'] / med['f']:.3f}"
+                     f" [{min(rec['cycle']['b_over_f_rounds']):.3f} .. {max(rec['cycle']['b_over_f_rounds']):.3f}]  (d)/(f) {med['d'] / med['f']:.2f}")
         if not args.no_pcg:
             cgs, cgd = NativeCGSolver(single, single, tol=1e-8, maxsteps=100), NativeCGSolver(double, double, tol=1e-8, maxsteps=100)
             its = {}
@@ -135,12 +180,16 @@ def _f32(args, H, p, kw, fuse, ks, nv):
                 return run
 
             pcalls = {"a": pa, "b": multi("b", cgs, word), "c": multi("c", cgs, fuse), "d": multi("d", cgd, fuse)}
+            if d32:
+                pcalls["f"] = multi("f", cgs, word_f)
             with torch.cuda.stream(stream):
                 for fn in pcalls.values():
                     fn()
             torch.cuda.synchronize()
             wp = max(float((X["b"][:, j] - xs[j]).norm() / xs[j].norm()) for j in range(k))
-            if not wp < 1e-8 or any(abs(x - y) > 1 for x, y in zip(its["a"], its["b"])):
+            if d32:
+                wp = max(wp, max(float((X["f"][:, j] - xs[j]).norm() / xs[j].norm()) for j in range(k)))
+            if not wp < 1e-8 or any(abs(x - y) > 1 for x, y in zip(its["a"], its["b"])) or (d32 and its["f"] != its["b"]):
                 sys.exit(f"bench_multi_rhs: k = {k}: PCG differs: solutions {wp:.3e}, iterations {its}")
             pt = {key: [] for key in pcalls}
             for _ in range(args.rounds):
@@ -150,8 +199,11 @@ def _f32(args, H, p, kw, fuse, ks, nv):
             rec["pcg"] = dict({key: _stats(v) for key, v in pt.items()}, iterations=dict(its), max_rel_diff=wp, a_over_b=pm["a"] / pm["b"],
                               d_over_b=pm["d"] / pm["b"], a_spread=(max(pt["a"]) - min(pt["a"])) / pm["a"])
             line += f"   pcg (a) {pm['a']:.2f} ms (b) {pm['b']:.2f} (d) {pm['d']:.2f}  (a)/(b) {pm['a'] / pm['b']:.2f}  (d)/(b) {pm['d'] / pm['b']:.2f}  iterations {its}"
+            if d32:
+                rec["pcg"].update(a_over_f=pm["a"] / pm["f"], b_over_f=pm["b"] / pm["f"], d_over_f=pm["d"] / pm["f"])
+                line += f"  (f) {pm['f']:.2f}  (a)/(f) {pm['a'] / pm['f']:.2f}  (b)/(f) {pm['b'] / pm['f']:.3f}  (d)/(f) {pm['d'] / pm['f']:.2f}"
         out["k"][str(k)] = rec
-        print(line, flush=True)
+        print(line + plans, flush=True)
     path = args.out
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
@@ -175,11 +227,14 @@ def main():
     ap.add_argument("--down", action="store_true", help="also time the calls with AMGX_MULTI_FUSE_DOWN")
     ap.add_argument("--dia", action="store_true", help="with --down: also time the calls with AMGX_MULTI_FUSE_DOWN_DIA")
     ap.add_argument("--mat-prec", default="double", choices=["double", "single", "single_gs_all", "single_gs"])
+    ap.add_argument("--down-f32", action="store_true", help="with --mat-prec single_gs_all: also time the calls with AMGX_MULTI_FUSE_DOWN_F32")
     ap.add_argument("--tag", default="", help="suffix of the result file (runs under environment switches)")
     ap.add_argument("--cycle-only-k", type=int, default=0, help="run nothing but REPS multi-vector cycles of this width (for a kernel trace)")
     args = ap.parse_args()
     if args.dia and not args.down:
         sys.exit("bench_multi_rhs: --dia needs --down")
+    if args.down_f32 and not (args.smoother == "gs" and args.config == "cfg2" and args.mat_prec == "single_gs_all"):
+        sys.exit("bench_multi_rhs: --down-f32 needs --smoother gs --config cfg2 --mat-prec single_gs_all")
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -202,7 +257,8 @@ def main():
         tag += ("_f32" if args.mat_prec == "single" else "") + (("_" + args.tag) if args.tag else "")
     if args.out is None:
         if args.mat_prec in ("single_gs_all", "single_gs"):
-            args.out = os.path.join(ROOT, "profiles", "r30", f"multi_f32_{args.config}.json")
+            args.out = (os.path.join(ROOT, "profiles", "r31", f"multi_down_f32_{args.config}.json") if args.down_f32 else
+                        os.path.join(ROOT, "profiles", "r30", f"multi_f32_{args.config}.json"))
         elif args.down:
             args.out = os.path.join(ROOT, "profiles", "r25", f"multi_down_dia_{tag}.json") if args.dia else os.path.join(ROOT, "profiles", "r24", f"multi_down_{tag}.json")
         elif isinstance(fuse, str):
